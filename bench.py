@@ -6,10 +6,16 @@ payloads of a decodable AV1 stream.  That is `value`.  What the timed region lea
 the source: the end-to-end legs (`e2e_gpu_entropy`, `e2e`) add it and are reported next to `value`, never as it.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 4k10-gop|1080p8-gop|4k10|1080p8] [--segments S] [--qindex Q]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one closed GOP of every segment (S segments in lockstep x 30 frames; intra-only workloads: 3 batches of S key frames).
 N ranks (one per GPU; `--gpus N` alone spawns them, or torch.distributed.run does) each code their own segments: no data-path
 collective, scaling is weak.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`).  `--full` adds everything
+else the bench measures: the per-kernel event profile of the timed steps, the rooflines (with a pass of its own, the coder
+serialised), the PSNR-Y of the last batch, the CPU baseline, the end-to-end legs, the dav1d check and the comparison with libaom.
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (see dump_outputs).
 
 Default workload = the configuration BASELINE.json's metric ("encoded 4K30 frames/sec") is quoted on: configs[3], 4K 10-bit,
 closed GOPs of 30 frames (1 key + 29 P), every stage on one GPU.
@@ -28,6 +34,9 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 METRIC = "encoded 4K30 frames/sec (whole node) at fixed QP; PSNR-Y delta vs libaom"
+DUMP_LIMIT = 64 << 20   # bytes of .npy data --dump-outputs writes at most
+DUMP_SAMPLE = 1 << 17   # values kept of one array of one batch; larger ones are sampled at fixed, seeded positions
+DUMP_SEED = 0xA51C0DE
 
 
 def parse():
@@ -50,7 +59,18 @@ def parse():
                          "the width is a multiple of 32; 8: every frame in 8x8 blocks")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="no GPU: exercise the rank/sharding/timing/aggregation plumbing with a stand-in step (gloo tests)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: kernel profile, rooflines, quality, CPU baseline, "
+                         "end-to-end legs (--no-cpu-baseline / --no-e2e leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the session returned in the last timed step as DIR/<name>.npy "
+                         "(rank 0's segments; float32 / float64; a fixed sample of the large ones, %d MB at most)" % (DUMP_LIMIT >> 20))
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.dry_run_cpu:
+        ap.error("--dump-outputs needs the GPU path: the CPU dry run computes nothing")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------ baselines
@@ -377,6 +397,40 @@ def pmc_numbers(kind, workload, frames_per_launch):
     return None, None, None
 
 
+class OutputCapture:
+    """--dump-outputs: what the timed path hands its caller (GopSession.collect: tile sizes and payloads, the restoration flags, the
+    symbols of key frames in 32x32 blocks), batch by batch in collection order.  The session reuses its buffers, so every array is
+    copied when collected; one larger than DUMP_SAMPLE values is sampled at the same seeded relative positions in every batch."""
+
+    def __init__(self):
+        self.arrays = {}
+        self.pos = np.sort(np.random.default_rng(DUMP_SEED).random(DUMP_SAMPLE))
+
+    def add(self, fr):
+        for name, a in fr.items():
+            if isinstance(a, np.ndarray):
+                if a.size > DUMP_SAMPLE:      # indexed in place: some views are strided, a flat copy of them would be large
+                    a = a[np.unravel_index((self.pos * a.size).astype(np.int64), a.shape)]
+                self.arrays.setdefault(name, []).append(np.array(a).reshape(-1))
+
+    def write(self, path):
+        """DIR/<name>.npy: integers of up to 16 bits as float32, wider ones as float64 (exact either way); if the whole exceeds
+        DUMP_LIMIT, every array is thinned by the same factor at evenly spaced positions.  Returns the names written."""
+        os.makedirs(path, exist_ok=True)
+        out = {}
+        for name, parts in self.arrays.items():
+            a = np.concatenate(parts)
+            if a.size:
+                out[name] = a.astype(np.float64 if a.dtype.itemsize >= 4 else np.float32)
+        total = sum(a.nbytes for a in out.values())
+        room = DUMP_LIMIT - (1 << 16)         # the .npy headers
+        for name, a in out.items():
+            if total > room:
+                a = a[np.linspace(0, a.size - 1, max(1, a.size * room // total)).astype(np.int64)]
+            np.save(os.path.join(path, name + ".npy"), a)
+        return sorted(out)
+
+
 def segment_of_rank(rank, frames_per_step):
     """closed-GOP sharding: rank r codes the r-th run of frames_per_step frames (no data exchanged between ranks)"""
     return rank * frames_per_step
@@ -394,7 +448,8 @@ def aggregate(dist, dt, device, op="max"):
 
 def dry_run(args, rank, world, dist):
     """CPU stand-in used by tests/test_distributed.py: same control flow as the GPU path (timed step between barriers, max over
-    ranks; then the end-to-end leg on EVERY rank between barriers, frames summed over ranks, host threads shared), sleeps as work."""
+    ranks; with --full, then the end-to-end leg on EVERY rank between barriers, frames summed over ranks, host threads shared),
+    sleeps as work."""
     frames = args.segments or 4
     first = segment_of_rank(rank, frames)
 
@@ -408,18 +463,20 @@ def dry_run(args, rank, world, dist):
         time.sleep(0.01 * (1 + rank))        # uneven ranks: the aggregate must follow the slowest
     barrier()
     dt = aggregate(dist, time.perf_counter() - t0, "cpu")
-    threads = usable_cpus(share=world)
-    barrier()
-    t0 = time.perf_counter()
-    time.sleep(0.02 * (1 + rank))
-    barrier()
-    e2e_dt = aggregate(dist, time.perf_counter() - t0, "cpu")
-    e2e_frames = aggregate(dist, float(frames), "cpu", "sum")
+    out = {"metric": "dry-run", "value": frames * args.steps * world / dt, "unit": "frames/s", "n_gpus": world,
+           "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "scaling": "weak",
+           "first_frame_rank0": first, "frames_per_step": frames}
+    if args.full:
+        threads = usable_cpus(share=world)
+        barrier()
+        t0 = time.perf_counter()
+        time.sleep(0.02 * (1 + rank))
+        barrier()
+        e2e_dt = aggregate(dist, time.perf_counter() - t0, "cpu")
+        e2e_frames = aggregate(dist, float(frames), "cpu", "sum")
+        out.update(e2e_gpu_entropy_frames_per_s=e2e_frames / e2e_dt, e2e_gpu_entropy={"ranks": world, "host_threads_per_rank": threads})
     if rank == 0:
-        print(json.dumps({"metric": "dry-run", "value": frames * args.steps * world / dt, "unit": "frames/s", "n_gpus": world,
-                          "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "scaling": "weak",
-                          "first_frame_rank0": first, "frames_per_step": frames,
-                          "e2e_gpu_entropy_frames_per_s": e2e_frames / e2e_dt, "e2e_gpu_entropy": {"ranks": world, "host_threads_per_rank": threads}}))
+        print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
 
@@ -520,10 +577,13 @@ def main():
     t_gen = time.perf_counter() - t_gen
     kbs = 32 if (args.key_block_size == 32 and W % 32 == 0) else 0
     sess = av1mi.GopSession(ctx, W, H, bd, args.qindex, gop, segs, gpu_entropy=1, key_block_size=kbs)
-    stat = {"payload": 0, "frames": 0}
+    stat = {"payload": 0, "frames": 0, "timed": False}
+    cap = OutputCapture() if args.dump_outputs and rank == 0 else None
 
     def collect():
         fr = sess.collect()
+        if cap is not None and stat["timed"] and stat["frames"] >= (args.steps - 1) * frames:     # a batch of the last timed step
+            cap.add(fr)
         stat["frames"] += segs
         if "tile_size" in fr:
             stat["payload"] += int(fr["tile_payload"].size)
@@ -553,26 +613,26 @@ def main():
     drain()
     barrier()
     stat["payload"] = stat["frames"] = 0
-    # every launch of the timed region is bracketed by its own HIP event pair on the stream it is launched on
-    ctx.prof_reset()
-    ctx.prof_enable(True)
+    stat["timed"] = True
+    if args.full:
+        # every launch of the timed region is bracketed by its own HIP event pair on the stream it is launched on
+        ctx.prof_reset()
+        ctx.prof_enable(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     drain()
     barrier()
     dt = time.perf_counter() - t0
-    ctx.prof_enable(False)
-    prof = ctx.prof_get()
+    if args.full:
+        ctx.prof_enable(False)
+        prof = ctx.prof_get()
     dt = aggregate(dist, dt, sync_t.device if dist is not None else None)
+    if cap is not None:
+        cap.write(args.dump_outputs)
     fallbacks = int(sess.entropy_fallbacks())
-    words = av1mi.C.c_uint64()
-    ctx.lib.av1mi_av1_entropy_last_list_words(ctx.h, av1mi.C.byref(words))      # of the last batch (a P-frame batch in GOP workloads)
     total_frames = frames * args.steps * world
     fps = total_frames / dt
-    b_ = 1 if bd == 8 else 2
-    fs = W * H * 3 // 2 * segs                       # samples per launch (one batch)
-    payload_per_batch = stat["payload"] / max(args.steps * batches, 1)
     out = {
         "metric": METRIC, "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -584,15 +644,20 @@ def main():
                                   else "intra-only (all key frames), %d frames per batch" % segs, args.qindex),
                    "value_is": "ENCODED frames/s with the source frames already resident in HBM (av1mi_gop_submit_device) and the coded tile payloads of a "
                                "decodable AV1 stream written to pinned host memory: the GOP session the product runs, minus the PCIe upload of the source.  "
-                               "`e2e_gpu_entropy_frames_per_s` adds the upload (pinned host source); `e2e_frames_per_s` is north_star's split with entropy "
-                               "coding on the host cores; `block_pipeline_frames_per_s` is the round-1/2 definition of `value` (kernels of the main "
-                               "stream only, no entropy coding), derived from this run's kernel times",
+                               "With --full: `e2e_gpu_entropy_frames_per_s` adds the upload (pinned host source); `e2e_frames_per_s` is north_star's split "
+                               "with entropy coding on the host cores; `block_pipeline_frames_per_s` is the round-1/2 definition of `value` (kernels of the "
+                               "main stream only, no entropy coding), derived from this run's kernel times",
                    "frames_per_step": frames, "segments": segs, "qindex": args.qindex, "key_block_size": kbs or 8, "entropy_fallbacks": fallbacks,
                    "coded_bytes_per_frame": stat["payload"] / max(stat["frames"], 1),
                    "sharding": "closed-GOP segment per GPU, no collective", "device": ctx.device_name,
                    "source_generation_s": t_gen},
     }
-    if rank == 0:
+    if args.full and rank == 0:
+        words = av1mi.C.c_uint64()
+        ctx.lib.av1mi_av1_entropy_last_list_words(ctx.h, av1mi.C.byref(words))      # of the last batch (a P-frame batch in GOP workloads)
+        b_ = 1 if bd == 8 else 2
+        fs = W * H * 3 // 2 * segs                       # samples per launch (one batch)
+        payload_per_batch = stat["payload"] / max(args.steps * batches, 1)
         nbatch = args.steps * batches
         # algorithmic bytes per BATCH (one launch, or the launches of one batch together), SURVEY.md §8d / DESIGN.md §3
         alg = {"intra_pipeline": (2 * b_ + 2) * fs, "inter_pipeline": (3 * b_ + 2) * fs, "me_integer": 2 * b_ * fs * 2.0 / 3.0,
@@ -683,7 +748,7 @@ def main():
     for t in d_src:
         for b in t:
             b.free()
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         # END TO END on every rank, between barriers: the scaling risks SURVEY §8e names (host cores, PCIe) are in this leg
         threads = usable_cpus(share=world)
         es = min(args.e2e_segments, segs)

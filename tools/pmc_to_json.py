@@ -1,17 +1,18 @@
 #!/usr/bin/env python3
-"""gpurun_out/pmc_<tag>/pass*/**/*counter_collection.csv  ->  profiles/<out>.json
+"""$PROF_OUT/pmc_<tag>/pass*/**/*counter_collection.csv  ->  profiles/<out>.json (PROF_OUT: the profiling scripts' output folder, prof_out)
 Per kernel: mean FETCH_SIZE / WRITE_SIZE (KB, as rocprofv3 reports them) per launch and the derived HBM byte counts.
 usage: pmc_to_json.py <tag> <frames_per_step> <out.json> [calib_tag]"""
 import csv
 import glob
 import json
+import os
 import sys
 from collections import defaultdict
 
 
 def load(tag):
     acc = defaultdict(lambda: defaultdict(list))
-    for f in glob.glob("gpurun_out/pmc_%s/pass*/**/*counter_collection.csv" % tag, recursive=True):
+    for f in glob.glob(os.path.join(os.environ.get("PROF_OUT", "prof_out"), "pmc_%s/pass*/**/*counter_collection.csv" % tag), recursive=True):
         for row in csv.DictReader(open(f)):
             k = row["Kernel_Name"].split("(")[0].replace("void ", "").replace("av1mi::", "")
             acc[k][row["Counter_Name"]].append(float(row["Counter_Value"]))
