@@ -1,7 +1,7 @@
 // av1_bitstream_core.hpp — shared pieces of the host AV1 bitstream writers (av1_bitstream.cpp: the 8x8-block writer the GPU
 // pipeline feeds; av1_blockstream.cpp: the general block-structured writer): fixed-length bit writer, OBU framing, the symbol
 // encoder (spec 8.2), the CDF context of a tile with its defaults (av1_default_cdfs.inc), syntax constants and the frame header
-// (spec 5.9.2).  Internal to libav1mi_host.so.
+// (spec 5.9.2).  The tile syntax the two writers share is in av1_tile_syntax.hpp.  Internal to libav1mi_host.so.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -253,12 +253,7 @@ enum { DC_PRED, V_PRED, H_PRED, D45_PRED, D135_PRED, D113_PRED, D157_PRED, D203_
 enum { T_DCT_DCT, T_ADST_DCT, T_DCT_ADST, T_ADST_ADST, T_FLIPADST_DCT, T_DCT_FLIPADST, T_FLIPADST_FLIPADST, T_ADST_FLIPADST,
        T_FLIPADST_ADST, T_IDTX };
 static const uint8_t kIntraModeContext[13] = { 0, 1, 2, 3, 4, 4, 4, 4, 3, 0, 1, 2, 0 };   // Intra_Mode_Context (9.3)
-// symbol of a 2-D-class transform type inside each set = inverse of Tx_Type_Intra_Inv_Set1/2, Tx_Type_Inter_Inv_Set1/3 (5.11.47)
-static const int8_t kIntraSet1Sym[16] = { 1, 5, 6, 4, -1, -1, -1, -1, -1, 0, 2, 3, -1, -1, -1, -1 };
-static const int8_t kIntraSet2Sym[16] = { 1, 3, 4, 2, -1, -1, -1, -1, -1, 0, -1, -1, -1, -1, -1, -1 };
-static const int8_t kInterSet1Sym[16] = { 7, 8, 9, 12, 10, 11, 13, 14, 15, 0, 1, 2, 3, 4, 5, 6 };
 inline bool is_directional(int m) { return m >= V_PRED && m <= D67_PRED; }
-inline bool tx_class_2d(int t) { return t <= T_FLIPADST_ADST; }
 
 // ------------------------------------------------------------------------------------------------ frame-level derived values
 struct FrameInfo {

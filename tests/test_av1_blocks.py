@@ -166,26 +166,42 @@ def test_random_trees_of_inter_and_intra_blocks(O, w, h, bd, q, tiles, sel, red,
 
 
 def test_the_block_writer_and_the_8x8_writer_agree_byte_for_byte(O):
-    """two statements of the syntax, one stream: a key frame of 8x8 blocks described both ways"""
+    """two callers of one tile syntax, one stream: frames of 8x8 blocks described both ways.  A key frame with the 2-D transform types; a
+    key frame with the identity and 1-D types as well (the scan and the contexts of their class); a P frame with them, whose isolated
+    inter blocks (non-zero vectors: NEWMV against an empty list in both writers) hand their luma type's class to their chroma blocks"""
     import av1stream
     w, h, bd, q = 136, 72, 8, 120
-    rng = np.random.default_rng(5)
-    lay = B.Layout(w, h)
-    parts, blocks = B.random_frame(O, rng, lay, bd, q, chooser=B.uniform_chooser(B.BLOCK_8X8), one_d_types=False)
-    tu = B.encode(lay, bd, q, parts, blocks)
-    nb = (w // 8) * (h // 8)
-    arr = {k: np.zeros(nb, dt) for k, dt in (("y_mode", np.uint8), ("uv_mode", np.uint8), ("angle_y", np.int8), ("angle_uv", np.int8), ("skip", np.uint8),
-                                             ("tx_type", np.uint8))}
-    cfl, ly, lu, lv = np.zeros((nb, 2), np.int8), np.zeros((nb, 8, 8), np.int16), np.zeros((nb, 4, 4), np.int16), np.zeros((nb, 4, 4), np.int16)
-    for b in blocks:
-        i = (b["r"] // 2) * (w // 8) + b["c"] // 2
-        for k in ("y_mode", "uv_mode", "angle_y", "angle_uv", "skip"):
-            arr[k][i] = b[k]
-        cfl[i] = b["cfl"]
-        if not b["skip"]:
-            arr["tx_type"][i] = b["tx_types"][0]
-            ly[i], lu[i], lv[i] = b["levels"][0][0], b["levels"][1][0], b["levels"][2][0]
-    assert tu == av1stream.temporal_unit(w, h, bd, q, cfl_alpha=cfl, lev_y=ly, lev_u=lu, lev_v=lv, **arr)
+    for key, one_d, seed in ((True, False, 5), (True, True, 6), (False, True, 24)):
+        rng = np.random.default_rng(seed)
+        lay = B.Layout(w, h)
+
+        def moving(i, b):
+            if b["is_inter"] and b["mv"] == (0, 0):
+                b["mv"] = (2, -4)
+        parts, blocks = B.random_frame(O, rng, lay, bd, q, key=key, p_inter=0.0 if key else 0.6, chooser=B.uniform_chooser(B.BLOCK_8X8), one_d_types=one_d,
+                                       symbols=moving)
+        tu = B.encode(lay, bd, q, parts, blocks, key=key)
+        nb = (w // 8) * (h // 8)
+        arr = {k: np.zeros(nb, dt) for k, dt in (("y_mode", np.uint8), ("uv_mode", np.uint8), ("angle_y", np.int8), ("angle_uv", np.int8), ("skip", np.uint8),
+                                                 ("tx_type", np.uint8), ("is_inter", np.uint8))}
+        cfl, ly, lu, lv = np.zeros((nb, 2), np.int8), np.zeros((nb, 8, 8), np.int16), np.zeros((nb, 4, 4), np.int16), np.zeros((nb, 4, 4), np.int16)
+        mv = np.zeros((nb, 2), np.int16)
+        for b in blocks:
+            i = (b["r"] // 2) * (w // 8) + b["c"] // 2
+            for k in ("y_mode", "uv_mode", "angle_y", "angle_uv", "skip", "is_inter"):
+                arr[k][i] = b[k]
+            cfl[i], mv[i] = b["cfl"], b["mv"]
+            if not b["skip"]:
+                arr["tx_type"][i] = b["tx_types"][0]
+                ly[i], lu[i], lv[i] = b["levels"][0][0], b["levels"][1][0], b["levels"][2][0]
+        if key:
+            arr.pop("is_inter")
+        else:
+            arr["mv"] = mv
+        coded = [b for b in blocks if not b["skip"] and b["levels"][0][0].any()]
+        assert one_d == any(b["tx_types"][0] > 9 for b in coded)
+        assert key or sum(b["is_inter"] and b["tx_types"][0] > 9 and bool(b["levels"][1][0].any() or b["levels"][2][0].any()) for b in coded) >= 2
+        assert tu == av1stream.temporal_unit(w, h, bd, q, frame_type=0 if key else 1, cfl_alpha=cfl, lev_y=ly, lev_u=lu, lev_v=lv, **arr)
 
 
 def test_the_block_writer_refuses_what_it_cannot_code(O):
