@@ -3,7 +3,8 @@
 // cores sustains ~100 4K frames/s while the block pipeline produces 4 900 — so the same syntax also runs here, and what crosses
 // PCIe is the coded tile payloads (0.7 MB per 4K frame) instead of 25 MB of int16 levels.
 //
-// The syntax is av1_ops.hpp (shared source with the host's CPU twin, byte-identical to the dav1d-verified writer), in three stages:
+// The syntax is av1_ops.hpp + av1_ops32.hpp (key frames in 32x32 blocks; shared source with the host's CPU twin, byte-identical
+// to the dav1d-verified writer), in three stages:
 //   k_av1_info     thread per block: level-context summary of the block + (inter) the mode that codes its vector
 //   k_av1_tokens   workgroup per tile, thread per block in z-order: the block's syntax elements, counted, placed, written —
 //                  literals into the tile's list, adaptive symbols as entries grouped by CDF slot
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void
     }
     __syncthreads();
     __threadfence_block();
-    replay_block(rec, k.nrec, S.pos, zi, first, list, grouped, lo, hi, half == 0);
+    replay_block<kBlocksPerTile>(rec, k.nrec, S.pos, zi, first, list, grouped, lo, hi, half == 0);
   }
 }
 
@@ -235,7 +236,7 @@ __global__ __launch_bounds__(64) void k_av1_tokens32(Av1EntLaunch L, int ntiles_
   if (!live || s_bad[tl]) return;
   int first = 0;
   for (int q = 0; q < b; q++) first += s_n[tl][q];
-  replay_block32(rec, nrec, cnt, b, first, L.ops + (size_t)t * L.ops_cap, L.grouped + (size_t)t * L.grouped_cap);
+  replay_block<kBlocks32>(rec, nrec, cnt, b, first, L.ops + (size_t)t * L.ops_cap, L.grouped + (size_t)t * L.grouped_cap);
 }
 
 // CHAINS: workgroup = one CDF slot of 64 consecutive tiles, one lane per tile.  The slot is the same for the whole wave (no
@@ -462,7 +463,7 @@ struct av1mi_av1ent_state {      // per-context scratch of the coder, grown on d
   size_t last_tiles = 0;          // tiles of the most recent job (av1mi_av1_entropy_last_list_words)
   uint16_t *d_image[2][4] = {};   // [key][qcat] default CDF images
   uint16_t *d_image32[4] = {};    // [qcat] the 32x32 band's
-  av1ops::SlotTable tab32;
+  av1ops::SlotTable tab32;        // the 32x32 band's slot table (the same for every q category)
   int image_words[2] = { 0, 0 };
   av1ops::SlotTable tab[2];
 };
@@ -503,7 +504,7 @@ int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hip
   if (j->nframes == 0) return AV1MI_OK;
   av1mi_av1ent_state *st = av1mi::ctx_av1ent(ctx);
   if (!st) return av1mi::ctx_fail(ctx, AV1MI_E_NOMEM, "AV1 entropy state");
-  const int key = j->key ? 1 : 0, qcat = j->base_q_idx <= 20 ? 0 : j->base_q_idx <= 60 ? 1 : j->base_q_idx <= 120 ? 2 : 3;
+  const int key = j->key ? 1 : 0, qcat = av1ops::q_category(j->base_q_idx);
   if (!st->d_image[key][qcat]) {
     av1ops::SlotTable tab;
     const std::vector<uint16_t> img = av1ops::default_slot_image(key != 0, qcat, &tab);
@@ -523,7 +524,7 @@ int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hip
   av1mi::Av1EntLaunch L;
   memset(&L, 0, sizeof(L));
   L.sb_rows32 = j->key_rows32 / 64;
-  if (j->key_rows32) { av1ops::build_slot_table_k32(&L.tab32); L.cdf_image32 = st->d_image32[qcat]; }
+  if (j->key_rows32) { L.tab32 = st->tab32; L.cdf_image32 = st->d_image32[qcat]; }
   L.fv.w8 = j->width / 8; L.fv.h8 = j->height / 8; L.fv.key = key;
   L.fv.y_mode = j->d_modes_y; L.fv.uv_mode = j->d_modes_uv; L.fv.mv = j->d_mvs; L.fv.skip = j->d_skip;
   L.fv.lev_y = j->d_lev_y; L.fv.lev_u = j->d_lev_u; L.fv.lev_v = j->d_lev_v;
@@ -619,6 +620,7 @@ void av1ent_free(av1mi_av1ent_state *st) {
   for (void *p : { st->info, st->ops[0], st->ops[1], st->nops[0], st->nops[1], st->grouped, st->slot_tb, st->rec, st->slots, st->tile_off }) if (p) (void)hipFree(p);
   for (hipEvent_t ev : { st->lists_ready[0], st->lists_ready[1], st->lists_free[0], st->lists_free[1] }) if (ev) (void)hipEventDestroy(ev);
   for (auto &k : st->d_image) for (uint16_t *p : k) if (p) (void)hipFree(p);
+  for (uint16_t *p : st->d_image32) if (p) (void)hipFree(p);
   delete st;
 }
 av1mi_av1ent_state *av1ent_new() { return new (std::nothrow) av1mi_av1ent_state(); }

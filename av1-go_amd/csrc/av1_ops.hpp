@@ -12,6 +12,8 @@
 // Tool set = what the GPU block pipeline produces (host/av1_bitstream.hpp lists what the host writer can code beyond it): 8x8
 // blocks, one 64x64 superblock per tile, TX_MODE_LARGEST, DCT_DCT luma, key frames with 13 intra modes (angle delta 0) or inter
 // frames with single-reference blocks, cdef_bits = 0, Wiener restoration on 64x64 units, reduced_tx_set = 0, CDF update on.
+// Key frames in 32x32 blocks (av1_ops32.hpp) share the restoration, key-frame mode and coefficient syntax and the replay of this
+// file: a band enters them through its slot description (BandSlots) and its transform sizes' magnitude map (MagMap).
 #pragma once
 #include <stdint.h>
 
@@ -78,17 +80,31 @@ enum Slot : int {
 };
 enum { MVC_CLASS = 0, MVC_CLASS0 = 1, MVC_CLASS0_FR = 2, MVC_SIGN = 4, MVC_BITS = 5, MVC_FR = 15 };
 
+// What the syntax shared by the bands needs of a band's slot set (S_* here, K_* of the 32x32 band in av1_ops32.hpp): where each
+// group starts, and the eob_pt alphabets (eob_extra has eob_n - 2 contexts).  The coefficient groups follow each other in this
+// order in both sets.
+struct BandSlots {
+  int use_wiener, kf_y_mode, uv_mode, angle;
+  int txb_skip_y, txb_skip_c, eob_y, eob_c, eobx_y, eobx_c, dc_sign_y, dc_sign_c, base_eob_y, base_eob_c, base_y, base_c, br_y, br_c;
+  int eob_y_n, eob_c_n;
+};
+constexpr BandSlots kSlots8 = { S_USE_WIENER, S_KF_Y_MODE, S_UV_MODE, S_ANGLE, S_TXB_SKIP_Y, S_TXB_SKIP_C, S_EOB64_Y, S_EOB16_C, S_EOBX_Y,
+                                S_EOBX_C, S_DC_SIGN_Y, S_DC_SIGN_C, S_BASE_EOB_Y, S_BASE_EOB_C, S_BASE_Y, S_BASE_C, S_BR_Y, S_BR_C, 7, 5 };
+
+// alphabet size of a coefficient slot of the band; 0 for the band's other slots
+template <const BandSlots &B> AV1_HD int coeff_nsym(int s) {
+  if (s < B.txb_skip_y || s >= B.br_c + 21) return 0;
+  if (s == B.eob_y) return B.eob_y_n;
+  if (s == B.eob_c) return B.eob_c_n;
+  return s < B.base_eob_y ? 2 : s < B.base_y ? 3 : 4;
+}
 // alphabet size of a slot
 AV1_HD int slot_nsym(int s, bool key) {
+  if (const int n = coeff_nsym<kSlots8>(s)) return n;
   if (s < S_PART8) return 2;
   if (s < S_PART16) return 4;
   if (s < S_USE_WIENER) return 10;
-  if (s < S_EOB64_Y) return 2;
-  if (s == S_EOB64_Y) return 7;
-  if (s == S_EOB16_C) return 5;
-  if (s < S_BASE_EOB_Y) return 2;
-  if (s < S_BASE_Y) return 3;
-  if (s < S_COMMON_END) return 4;
+  if (s < S_COMMON_END) return 2;
   if (key) {
     if (s < S_UV_MODE) return 13;
     if (s < S_ANGLE) return 14;
@@ -103,6 +119,8 @@ AV1_HD int slot_nsym(int s, bool key) {
   }
   return 16;
 }
+// the q category of the coefficient CDFs (the default CDF set the frame starts from)
+AV1_HD int q_category(int base_q_idx) { return base_q_idx <= 20 ? 0 : base_q_idx <= 60 ? 1 : base_q_idx <= 120 ? 2 : 3; }
 // uint16 entries of a slot: N <= 4: four (ONE 64-bit word [v0 v1 v2 counter]: the coder's step is one LDS read and one LDS
 // write), N <= 8: eight, else sixteen (128-bit words); unused entries are 0, the counter is the LAST entry
 AV1_HD int slot_words(int nsym) { return nsym <= 4 ? 4 : nsym <= 8 ? 8 : 16; }
@@ -153,13 +171,14 @@ AV1_HD int group_positions(const uint8_t *cnt_slot, uint16_t *pos_slot, int base
   for (int b = 0; b < kBlocksPerTile; b++) { const int c = cnt_slot[b]; pos_slot[b] = (uint16_t)run; run += c; }
   return run - base;
 }
-// the block's records -> list words (from index `first`) and grouped entries; pos = [slots][64] running positions.  The GPU replays
-// in two passes over half of the slots each (half the positions in LDS): a pass takes the symbols of slots [slot_lo, slot_hi), whose
-// positions start at pos row 0, and the literals when `literals` is set
-AV1_HD void replay_block(const uint16_t *rec, int nrec, uint16_t *pos, int zi, int first, op_t *list, uint32_t *grouped, int slot_lo = 0,
+// block `blk` of a tile of kBlocks: its records -> list words (from index `first`) and grouped entries; pos = [slots][kBlocks]
+// running positions.  The 8x8 kernel replays in two passes over half of the slots each (half the positions in LDS): a pass takes
+// the symbols of slots [slot_lo, slot_hi), whose positions start at pos row 0, and the literals when `literals` is set
+template <int kBlocks>
+AV1_HD void replay_block(const uint16_t *rec, int nrec, uint16_t *pos, int blk, int first, op_t *list, uint32_t *grouped, int slot_lo = 0,
                          int slot_hi = 1 << 16, bool literals = true) {
   int n = first;
-  for (int i0 = 0; i0 < nrec; i0 += 8) {
+  for (int i0 = 0; i0 < nrec; i0 += 8) {        // eight records per load (a dependent 2-byte load per record is a memory round trip each)
     struct alignas(16) R8 { uint32_t w[4]; } q = *reinterpret_cast<const R8 *>(rec + i0);
     AV1_UNROLL      // (fully unrolled the eight records are register halves; indexed at run time the array lived in scratch memory)
     for (int j = 0; j < 8; j++, n++) {
@@ -168,7 +187,7 @@ AV1_HD void replay_block(const uint16_t *rec, int nrec, uint16_t *pos, int zi, i
       if (r & 0x8000u) { if (literals) list[n] = op_lit((int)((r >> 11) & 15), r & 0x7FFu); }
       else {
         const int sl = (int)(r >> 4);
-        if (sl >= slot_lo && sl < slot_hi) { uint16_t &p = pos[(sl - slot_lo) * kBlocksPerTile + zi]; grouped[p] = ((uint32_t)n << 4) | (r & 15u); p++; }
+        if (sl >= slot_lo && sl < slot_hi) { uint16_t &p = pos[(sl - slot_lo) * kBlocks + blk]; grouped[p] = ((uint32_t)n << 4) | (r & 15u); p++; }
       }
     }
   }
@@ -340,7 +359,7 @@ template <class K> AV1_HD void tok_signed_subexp_ref(K &k, int v, int low, int h
   tok_subexp(k, mx, kk, (r << 1) <= mx ? tok_recenter(r, v) : tok_recenter(mx - 1 - r, mx - 1 - v));
 }
 // read_lr for the superblock at (sbr, sbc): with one superblock per tile the reference taps are always the defaults
-AV1_HD void tok_lr(const FrameView &f, Sink &k, int sbr, int sbc) {
+template <const BandSlots &B, class K> AV1_HD void tok_lr(const FrameView &f, K &k, int sbr, int sbc) {
   const int mi_r = sbr * 16, mi_c = sbc * 16;
   for (int p = 0; p < 3; p++) {
     if (!f.lr_on[p]) continue;
@@ -350,13 +369,22 @@ AV1_HD void tok_lr(const FrameView &f, Sink &k, int sbr, int sbc) {
     const int8_t *u = f.lr_unit[p ? 1 : 0];
     for (int ur = row0; ur < row1; ur++)
       for (int uc = col0; uc < col1; uc++) {
-        k.sym(S_USE_WIENER, u[0] == 1);
+        k.sym(B.use_wiener, u[0] == 1);
         if (u[0] != 1) continue;
         const int kmin[3] = { -5, -23, -17 }, kmax[3] = { 10, 8, 46 }, kk[3] = { 1, 2, 3 }, mid[3] = { 3, -7, 15 };
         for (int pass = 0; pass < 2; pass++)
           for (int j = p ? 1 : 0; j < 3; j++) tok_signed_subexp_ref(k, u[1 + pass * 3 + j], kmin[j], kmax[j] + 1, kk[j], mid[j]);
       }
   }
+}
+// the mode syntax of a key frame's block (5.11.7, angle deltas 0, chroma from luma allowed): y mode in the context of the
+// neighbours' y modes (above / left: DC_PRED where there is none), its angle delta, uv mode, its angle delta
+template <const BandSlots &B, class K> AV1_HD void tok_kf_modes(K &k, int ym, int uvm, int above, int left) {
+  static const uint8_t kCtx[13] = { 0, 1, 2, 3, 4, 4, 4, 4, 3, 0, 1, 2, 0 };     // Intra_Mode_Context
+  k.sym(B.kf_y_mode + kCtx[above] * 5 + kCtx[left], ym);
+  if (ym >= 1 && ym <= 8) k.sym(B.angle + ym - 1, 3);
+  k.sym(B.uv_mode + ym, uvm);
+  if (uvm >= 1 && uvm <= 8) k.sym(B.angle + uvm - 1, 3);
 }
 // the partition symbols that precede block (bx, by) of superblock (sbr, sbc): every level whose first block it is
 AV1_HD void tok_partition_prefix(const FrameView &f, Sink &k, int sbr, int sbc, int bx, int by) {
@@ -375,7 +403,6 @@ AV1_HD void tok_partition_prefix(const FrameView &f, Sink &k, int sbr, int sbc, 
   k.sym(S_PART8, 0);                                       // PARTITION_NONE
 }
 
-// coeffs (5.11.39) of an N x N block (N = 8 luma, 4 chroma)
 // Default_Scan_4x4 / Default_Scan_8x8 for row-major blocks: diagonals, odd ones walked downwards from the top row
 struct ScanTables { uint8_t s4[16], s8[64], i4[16], i8[64]; };      // scan order -> position, and position -> scan order
 AV1_HD void fill_scan_tables(ScanTables *t) {
@@ -396,47 +423,59 @@ AV1_HD void fill_scan_tables(ScanTables *t) {
 enum { kMagStride = 10, kMagBytes = 100 };      // (8 + 2)^2: the context templates reach two columns / rows beyond a level; 25 dwords (odd) per thread
 struct TokScratch { uint8_t *mag; const ScanTables *scan; };
 
-// coeffs() (5.11.39) of one transform block: `lev` = its N x N levels, row-major (16-byte aligned)
-template <int N> AV1_HD void tok_coeffs(Sink &k, const TokScratch &ts, int plane, const int16_t *lev, int above_cul, int above_dc, int left_cul, int left_dc, bool key,
-                                        int y_mode) {
-  const int nc = N * N, LG = N == 4 ? 2 : 3, MS = kMagStride;
-  const uint8_t *scan = N == 4 ? ts.scan->s4 : ts.scan->s8;
-  // min(|level|, 15) | sign << 7 of the whole block, zero-padded to the right and below: every later read is from this copy
-  // (the exact value of the rare levels above 14 is re-read from `lev`)
-  uint8_t *mag = ts.mag;
-  const uint8_t *iscan = N == 4 ? ts.scan->i4 : ts.scan->i8;
-  for (int i = 0; i < (N + 2) * MS / 4; i++) reinterpret_cast<u32a *>(mag)[i] = 0;      // rows 0 .. N + 1: all a context template reaches
-  int eob = 0;      // 1 + the scan index of the last non-zero level, found while the block is copied (not by walking the scan backwards)
-  for (int r = 0; r < nc / 8; r++) {
-    struct alignas(16) L8 { int16_t v[8]; } q = *reinterpret_cast<const L8 *>(lev + 8 * r);
-    for (int j = 0; j < 8; j++) {
-      const int pos = 8 * r + j, v = q.v[j], a = iabs(v);
-      if (v) eob = imax(eob, iscan[pos] + 1);
-      mag[(pos >> LG) * MS + (pos & (N - 1))] = (uint8_t)((a > 15 ? 15 : a) | (v < 0 ? 128 : 0));
+// The MAGNITUDE MAP of the transform block at hand: min(|level|, 15) and the sign of every level, zero-padded two rows and columns
+// beyond the block (all a context template reaches), + the block's scan order.  Every read of a level after the first goes to this
+// copy (the exact value of the rare levels above 14 is re-read from `lev`).  Two storage formats, chosen by N: a
+// byte per level for N <= 8 (here), four bits + a sign bitmap for N >= 16 (av1_ops32.hpp).  What the syntax reads of a map:
+//   load(lev) -> eob    pos(c): the position of scan index c    at(i): the magnitude at i = row * MS + col    neg(pos): the sign
+template <int N, bool kBytes = (N <= 8)> struct MagMap;
+// N = 4, 8: min(|level|, 15) | sign << 7, rows of kMagStride
+template <int N> struct MagMap<N, true> {
+  enum { LG = N == 4 ? 2 : 3, MS = kMagStride };
+  uint8_t *mag;
+  const uint8_t *scan, *iscan;
+  AV1_HD MagMap(const TokScratch &ts) : mag(ts.mag), scan(N == 4 ? ts.scan->s4 : ts.scan->s8), iscan(N == 4 ? ts.scan->i4 : ts.scan->i8) {}
+  AV1_HD int load(const int16_t *lev) {
+    for (int i = 0; i < (N + 2) * MS / 4; i++) reinterpret_cast<u32a *>(mag)[i] = 0;      // rows 0 .. N + 1
+    int eob = 0;      // 1 + the scan index of the last non-zero level, found while the block is copied (not by walking the scan backwards)
+    for (int r = 0; r < N * N / 8; r++) {
+      struct alignas(16) L8 { int16_t v[8]; } q = *reinterpret_cast<const L8 *>(lev + 8 * r);
+      for (int j = 0; j < 8; j++) {
+        const int pos = 8 * r + j, v = q.v[j], a = iabs(v);
+        if (v) eob = imax(eob, iscan[pos] + 1);
+        mag[(pos >> LG) * MS + (pos & (N - 1))] = (uint8_t)((a > 15 ? 15 : a) | (v < 0 ? 128 : 0));
+      }
     }
+    return eob;
   }
-  auto at = [&](int pos) { return mag[(pos >> LG) * MS + (pos & (N - 1))]; };
-  const bool chroma = plane > 0;
-  const int skip_slot = chroma ? S_TXB_SKIP_C + ((above_cul | above_dc) != 0) + ((left_cul | left_dc) != 0) : S_TXB_SKIP_Y;
-  k.sym(skip_slot, eob == 0);
+  AV1_HD int pos(int c) const { return scan[c]; }
+  AV1_HD int at(int i) const { return mag[i] & 15; }
+  AV1_HD int neg(int p) const { return mag[(p >> LG) * MS + (p & (N - 1))] >> 7; }
+};
+
+// coeffs() (5.11.39) of one N x N transform block (N = 4, 8, 16, 32): `lev` = its levels, row-major (16-byte aligned); the slots of
+// band B; above / left: the neighbours' level summaries (cul = min(63, sum |level|), dc = 0 none / 1 negative / 2 positive);
+// (tx_slot, tx_sym): the luma transform type, coded right after all_zero (tx_slot < 0: implied, not coded)
+template <int N, const BandSlots &B, class K, class TS>
+AV1_HD void tok_coeffs(K &k, const TS &ts, bool chroma, const int16_t *lev, int above_cul, int above_dc, int left_cul, int left_dc, int tx_slot,
+                       int tx_sym) {
+  MagMap<N> M(ts);
+  const int nc = N * N, LG = M.LG, MS = M.MS;
+  const int eob = M.load(lev);
+  k.sym(chroma ? B.txb_skip_c + ((above_cul | above_dc) != 0) + ((left_cul | left_dc) != 0) : B.txb_skip_y, eob == 0);
   if (!eob) return;
-  if (!chroma) {
-    if (key) k.sym(S_INTRA_TX + y_mode, 1);    // DCT_DCT in Tx_Type_Intra_Inv_Set1
-    else k.sym(S_INTER_TX, 7);                 // DCT_DCT in the 16-type inter set
-  }
+  if (tx_slot >= 0) k.sym(tx_slot, tx_sym);
   const int eob_pt = eob < 3 ? eob : ilog2((unsigned)(eob - 1)) + 2;
-  k.sym(chroma ? S_EOB16_C : S_EOB64_Y, eob_pt - 1);
+  k.sym(chroma ? B.eob_c : B.eob_y, eob_pt - 1);
   if (eob_pt >= 3) {
-    const int off = eob - ((1 << (eob_pt - 2)) + 1);
-    int shift = eob_pt - 3;
-    k.sym((chroma ? S_EOBX_C : S_EOBX_Y) + eob_pt - 3, (off >> shift) & 1);
+    const int off = eob - ((1 << (eob_pt - 2)) + 1), shift = eob_pt - 3;
+    k.sym((chroma ? B.eobx_c : B.eobx_y) + eob_pt - 3, (off >> shift) & 1);
     if (shift > 0) k.lit((unsigned)(off & ((1 << shift) - 1)), shift);
   }
-  const int base_eob = chroma ? S_BASE_EOB_C : S_BASE_EOB_Y, base = chroma ? S_BASE_C : S_BASE_Y, br = chroma ? S_BR_C : S_BR_Y;
+  const int base_eob = chroma ? B.base_eob_c : B.base_eob_y, base = chroma ? B.base_c : B.base_y, br = chroma ? B.br_c : B.br_y;
   for (int c = eob - 1; c >= 0; c--) {
-    const int pos = scan[c], row = pos >> LG, col = pos & (N - 1);
-    const uint8_t *m = mag + row * MS + col;
-    const int m0 = m[0] & 15, m1 = m[1] & 15, m2 = m[2] & 15, mb = m[MS] & 15, md = m[MS + 1] & 15, mbb = m[2 * MS] & 15;
+    const int pos = M.pos(c), row = pos >> LG, col = pos & (N - 1), at = row * MS + col;
+    const int m0 = M.at(at), m1 = M.at(at + 1), m2 = M.at(at + 2), mb = M.at(at + MS), md = M.at(at + MS + 1), mbb = M.at(at + 2 * MS);
     int a = m0;
     if (a == 15) a = iabs(lev[pos]);
     if (c == eob - 1) {
@@ -462,16 +501,16 @@ template <int N> AV1_HD void tok_coeffs(Sink &k, const TokScratch &ts, int plane
     }
   }
   for (int c = 0; c < eob; c++) {
-    const int pos = scan[c], m = at(pos);
+    const int pos = M.pos(c), m = M.at((pos >> LG) * MS + (pos & (N - 1)));
     if (!m) continue;
-    const int neg = m >> 7;
+    const int neg = M.neg(pos);
     if (c == 0) {
       const int sg = (above_dc == 2) - (above_dc == 1) + (left_dc == 2) - (left_dc == 1);
-      k.sym((chroma ? S_DC_SIGN_C : S_DC_SIGN_Y) + (sg < 0 ? 1 : sg > 0 ? 2 : 0), neg);
+      k.sym((chroma ? B.dc_sign_c : B.dc_sign_y) + (sg < 0 ? 1 : sg > 0 ? 2 : 0), neg);
     } else {
       k.lit((unsigned)neg, 1);
     }
-    if ((m & 15) == 15) {
+    if (m == 15) {
       const int a = iabs(lev[pos]);
       if (a > 14) {
         const unsigned x = (unsigned)(a - 14);
@@ -504,7 +543,7 @@ AV1_HD void tok_block(const FrameView &f, Sink &k, const TokScratch &ts, int sbr
   demorton8((unsigned)zi, &bx, &by);
   const int r8 = sbr * 8 + by, c8 = sbc * 8 + bx;
   if (r8 >= f.h8 || c8 >= f.w8) return;
-  if (zi == 0) tok_lr(f, k, sbr, sbc);
+  if (zi == 0) tok_lr<kSlots8>(f, k, sbr, sbc);
   tok_partition_prefix(f, k, sbr, sbc, bx, by);
   const int b = r8 * f.w8 + c8;
   const bool au = by > 0, al = bx > 0;
@@ -514,13 +553,8 @@ AV1_HD void tok_block(const FrameView &f, Sink &k, const TokScratch &ts, int sbr
   k.sym(S_SKIP + (au && !f.key ? f.skip[b - f.w8] : 0) + (al && !f.key ? f.skip[b - 1] : 0), skip);
   int ym = 0;
   if (f.key) {
-    static const uint8_t kCtx[13] = { 0, 1, 2, 3, 4, 4, 4, 4, 3, 0, 1, 2, 0 };     // Intra_Mode_Context
     ym = f.y_mode[b];
-    k.sym(S_KF_Y_MODE + kCtx[au ? f.y_mode[b - f.w8] : 0] * 5 + kCtx[al ? f.y_mode[b - 1] : 0], ym);
-    if (ym >= 1 && ym <= 8) k.sym(S_ANGLE + ym - 1, 3);
-    const int uvm = f.uv_mode[b];
-    k.sym(S_UV_MODE + ym, uvm);
-    if (uvm >= 1 && uvm <= 8) k.sym(S_ANGLE + uvm - 1, 3);
+    tok_kf_modes<kSlots8>(k, ym, f.uv_mode[b], au ? f.y_mode[b - f.w8] : 0, al ? f.y_mode[b - 1] : 0);
   } else {
     k.sym(S_IS_INTER + 0, 1);                  // every neighbour is an inter block: context 0
     const int rctx = (au || al) ? 1 : 0;       // single_ref contexts 2 (an inter neighbour) / 1 (none)
@@ -566,21 +600,20 @@ AV1_HD void tok_block(const FrameView &f, Sink &k, const TokScratch &ts, int sbr
     }
   }
   if (skip) return;
-  tok_coeffs<8>(k, ts, 0, f.lev_y + (long)b * 64, ia.cul[0], ia.dc[0], il.cul[0], il.dc[0], f.key != 0, ym);
+  // the luma transform type: DCT_DCT in Tx_Type_Intra_Inv_Set1 (key frames) or in the 16-type inter set
+  tok_coeffs<8, kSlots8>(k, ts, false, f.lev_y + (long)b * 64, ia.cul[0], ia.dc[0], il.cul[0], il.dc[0], f.key ? S_INTRA_TX + ym : S_INTER_TX, f.key ? 1 : 7);
   AV1_NOUNROLL
   for (int p = 1; p < 3; p++)
-    tok_coeffs<4>(k, ts, p, (p == 1 ? f.lev_u : f.lev_v) + (long)b * 16, ia.cul[p], ia.dc[p], il.cul[p], il.dc[p], f.key != 0, ym);
+    tok_coeffs<4, kSlots8>(k, ts, true, (p == 1 ? f.lev_u : f.lev_v) + (long)b * 16, ia.cul[p], ia.dc[p], il.cul[p], il.dc[p], -1, 0);
 }
 
 // ------------------------------------------------------------------------------------------------ op coder
-// The range coder of the host writer (RangeEnc, av1_bitstream.cpp) over one tile's op list.  `cdf` = the tile's slot storage
-// (offsets from SlotTable), bytes go to `out` (capacity `cap`); returns the payload size, or -1 on overflow.
-AV1_HD void build_slot_table(bool key, SlotTable *t) {
-  const int n = key ? S_KEY_END : S_INTER_END;
+// The slot table of a band of n slots whose alphabet sizes are nsym(s); the slots from n to S_MAX are unused (2 symbols, offset 0)
+template <class F> AV1_HD void build_slot_table(int n, F nsym, SlotTable *t) {
   int o = 0;
   for (int s = 0; s < S_MAX; s++) {
     if (s < n) {
-      t->nsym[s] = (uint8_t)slot_nsym(s, key);
+      t->nsym[s] = (uint8_t)nsym(s);
       const int w = slot_words(t->nsym[s]), al = w < 8 ? 4 : 8;      // 64-bit words on 8 bytes, 128-bit words on 16
       o = (o + al - 1) & ~(al - 1);
       t->off[s] = (uint16_t)o;
@@ -589,6 +622,7 @@ AV1_HD void build_slot_table(bool key, SlotTable *t) {
   }
   t->words = (o + 7) & ~7;
 }
+AV1_HD void build_slot_table(bool key, SlotTable *t) { build_slot_table(key ? S_KEY_END : S_INTER_END, [key](int s) { return slot_nsym(s, key); }, t); }
 
 // The range coder (spec 8.2 mirrored; the arithmetic of the host writer's RangeEnc, av1_bitstream.cpp), built so that its steady
 // state never waits for global memory (on gfx9 a wait for ANY outstanding vector-memory operation, stores included, is the only

@@ -26,6 +26,33 @@ bool opstream_supported(const av1mi_obu_frame &f, std::string *why) {
   return true;
 }
 
+namespace {
+// stages 2 and 3 of a tile whose blocks are tokenized and placed (pos = [slots][kBlocks] positions of the blocks' first entries, the
+// slots' totals and bases, run = the tile's grouped entries): replay, one chain per slot from the default CDFs `image` (the GPU: the
+// tile's threads take the slots, longest first), the serial range coder over the finished list (the GPU: one lane per tile)
+template <int kBlocks>
+bool code_tile(const uint16_t *rec, int block_records, const int *nrec, const int *first, uint16_t *pos, int nslots, const uint16_t *total,
+               const uint16_t *base, int run, const av1ops::SlotTable &tab, const uint16_t *image, std::vector<uint8_t> *out, std::string *err) {
+  using namespace av1ops;
+  if (run > 65535) { if (err) *err = "tile too large for 16-bit entry positions"; return false; }
+  const int nops = first[kBlocks];
+  std::vector<op_t> list((size_t)nops, 0);
+  std::vector<uint32_t> grouped((size_t)run, 0);
+  for (int b = 0; b < kBlocks; b++) replay_block<kBlocks>(rec + (size_t)b * block_records, nrec[b], pos, b, first[b], list.data(), grouped.data());
+  for (int sl = 0; sl < nslots; sl++)
+    if (total[sl]) run_chain(&image[tab.off[sl]], tab.nsym[sl], &grouped[(size_t)base[sl]], total[sl], list.data());
+  out->resize((size_t)nops * 2 + 64);       // a step adds at most 15 bits
+  Coder c;
+  uint16_t stage[Coder::kStage];
+  c.init(out->data(), (int)out->size(), stage);
+  for (int i = 0; i < nops; i++) code_word(c, list[(size_t)i]);
+  const int n = c.finish();
+  if (n < 0) { if (err) *err = "tile payload overflow"; return false; }
+  out->resize((size_t)n);
+  return true;
+}
+}  // namespace
+
 // tile payloads (range-coded, finished) of a frame through tokenize + code; tiles in raster order
 // key_rows32 > 0: a key frame whose first key_rows32 luma rows (whole superblock rows) are coded in 32x32 blocks (av1_ops32.hpp; the
 // symbol arrays in the session's layout: those rows' modes one per 32x32 block from entry 0, levels block-contiguous over the 32x32
@@ -59,14 +86,12 @@ bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> 
   v.info = info.data();
   for (size_t b = 0; b < nb; b++) { memset(&info[b], 0, sizeof(BlockInfo)); block_summary(v, (int)b, &info[b]); }
   if (!v.key) for (int r = 0; r < v.h8; r++) for (int c = 0; c < v.w8; c++) inter_mode_decision(v, r, c, &info[(size_t)r * v.w8 + c]);
-  const int qcat = f.base_q_idx <= 20 ? 0 : f.base_q_idx <= 60 ? 1 : f.base_q_idx <= 120 ? 2 : 3;
+  const int qcat = q_category(f.base_q_idx);
   SlotTable tab;
   const std::vector<uint16_t> image = default_slot_image(v.key != 0, qcat, &tab);
   const int sbr_n = (v.h8 + 7) / 8, sbc_n = (v.w8 + 7) / 8;
   tiles->assign((size_t)sbr_n * sbc_n, {});
   const int nslots = v.key ? S_KEY_END : S_INTER_END;
-  std::vector<op_t> list;
-  std::vector<uint32_t> grouped;
   std::vector<uint8_t> cnt((size_t)S_MAX * kBlocksPerTile);
   std::vector<uint16_t> pos((size_t)S_MAX * kBlocksPerTile), rec((size_t)kBlocksPerTile * kBlockRecords);
   ScanTables scan;
@@ -105,22 +130,9 @@ bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> 
           if (!count_block32(&rec32[(size_t)b * kBlockRecords32], nrec[b], cnt32.data(), b)) { if (err) *err = "too many symbols of one slot in a block"; return false; }
         uint16_t base[K_END], total[K_END];
         const int run = place_tile32(cnt32.data(), total, base);
-        if (run > 65535) { if (err) *err = "tile too large for 16-bit entry positions"; return false; }
-        const int nops = first[kBlocks32];
-        list.assign((size_t)nops, 0);
-        grouped.assign((size_t)run, 0);
-        for (int b = 0; b < kBlocks32; b++) replay_block32(&rec32[(size_t)b * kBlockRecords32], nrec[b], cnt32.data(), b, first[b], list.data(), grouped.data());
-        for (int sl = 0; sl < K_END; sl++)
-          if (total[sl]) run_chain(&image32[tab32.off[sl]], tab32.nsym[sl], &grouped[(size_t)base[sl]], total[sl], list.data());
-        std::vector<uint8_t> &out = (*tiles)[(size_t)sbr * sbc_n + sbc];
-        out.resize((size_t)nops * 2 + 64);
-        Coder c;
-        uint16_t stage[Coder::kStage];
-        c.init(out.data(), (int)out.size(), stage);
-        for (int i = 0; i < nops; i++) code_word(c, list[(size_t)i]);
-        const int n = c.finish();
-        if (n < 0) { if (err) *err = "tile payload overflow"; return false; }
-        out.resize((size_t)n);
+        if (!code_tile<kBlocks32>(rec32.data(), kBlockRecords32, nrec, first, cnt32.data(), K_END, total, base, run, tab32, image32.data(),
+                                  &(*tiles)[(size_t)sbr * sbc_n + sbc], err))
+          return false;
         continue;
       }
       // stage 1, tokenize (the GPU: one thread per block): records + counts, place, replay
@@ -143,31 +155,16 @@ bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> 
         st_ops_sum += first[kBlocksPerTile];
         if (over) { st_over++; continue; }
       }
-      const int nops = first[kBlocksPerTile];
-      int base[S_MAX], total[S_MAX], run = 0;
+      uint16_t base[S_MAX], total[S_MAX];
+      int run = 0;
       for (int sl = 0; sl < nslots; sl++) {
-        base[sl] = run;
-        total[sl] = group_positions(&cnt[(size_t)sl * kBlocksPerTile], &pos[(size_t)sl * kBlocksPerTile], run);
-        run = (run + total[sl] + kListAlign - 1) & ~(kListAlign - 1);
+        const int n = group_positions(&cnt[(size_t)sl * kBlocksPerTile], &pos[(size_t)sl * kBlocksPerTile], run);
+        base[sl] = (uint16_t)run; total[sl] = (uint16_t)n;
+        run = (run + n + kListAlign - 1) & ~(kListAlign - 1);
       }
-      if (run > 65535) { if (err) *err = "tile too large for 16-bit entry positions"; return false; }
-      list.assign((size_t)nops, 0);
-      grouped.assign((size_t)run, 0);
-      for (int zi = 0; zi < kBlocksPerTile; zi++)
-        replay_block(&rec[(size_t)zi * kBlockRecords], nrec[zi], pos.data(), zi, first[zi], list.data(), grouped.data());
-      // stage 2, one chain per slot (the GPU: the tile's threads take the slots, longest first)
-      for (int sl = 0; sl < nslots; sl++)
-        if (total[sl]) run_chain(&image[tab.off[sl]], tab.nsym[sl], &grouped[(size_t)base[sl]], total[sl], list.data());
-      // stage 3, the serial range coder over the finished list (the GPU: one lane per tile)
-      std::vector<uint8_t> &out = (*tiles)[(size_t)sbr * sbc_n + sbc];
-      out.resize((size_t)nops * 2 + 64);       // a step adds at most 15 bits
-      Coder c;
-      uint16_t stage[Coder::kStage];
-      c.init(out.data(), (int)out.size(), stage);
-      for (int i = 0; i < nops; i++) code_word(c, list[(size_t)i]);
-      const int n = c.finish();
-      if (n < 0) { if (err) *err = "tile payload overflow"; return false; }
-      out.resize((size_t)n);
+      if (!code_tile<kBlocksPerTile>(rec.data(), kBlockRecords, nrec, first, pos.data(), nslots, total, base, run, tab, image.data(),
+                                     &(*tiles)[(size_t)sbr * sbc_n + sbc], err))
+        return false;
     }
   if (stats)
     fprintf(stderr, "[av1mi tok stats] %d tiles: records per block <= %d (capacity %d), symbols of a slot in a block <= %d (255), list words per tile <= %d, mean %.0f; %d tiles over a block capacity\n",
