@@ -88,7 +88,7 @@ class LrDecideJob(C.Structure):
 class GopConfig(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("bit_depth", C.c_int), ("base_q_idx", C.c_int), ("gop_length", C.c_int),
                 ("segments", C.c_int), ("search_range", C.c_int), ("gpu_entropy", C.c_int), ("visible_width", C.c_int),
-                ("visible_height", C.c_int), ("coder_streams", C.c_int), ("key_block_size", C.c_int)]
+                ("visible_height", C.c_int), ("coder_streams", C.c_int), ("key_block_size", C.c_int), ("input_format", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -114,6 +114,35 @@ def policy_frame_params(base_q_idx, bit_depth, frame_type):
     return p
 
 
+INPUT_PLANAR, INPUT_PACKED10, INPUT_P010, INPUT_NV12 = 0, 1, 2, 3      # enum av1mi_input_format
+
+
+def input_plane_bytes(fmt, bit_depth, plane, width, rows):
+    """bytes of one plane of a stack of `rows` luma rows in an input format (av1mi_input_plane_bytes); 0 = invalid; no GPU needed"""
+    lib = load()
+    lib.av1mi_input_plane_bytes.restype = C.c_size_t
+    lib.av1mi_input_plane_bytes.argtypes = [C.c_int] * 5
+    return int(lib.av1mi_input_plane_bytes(int(fmt), int(bit_depth), int(plane), int(width), int(rows)))
+
+
+def input_pack(fmt, bit_depth, y, u, v, out=None):
+    """planar planes (y [rows, width], u / v half size; uint8 or uint16) -> the format's planes as uint8 arrays (av1mi_input_pack, host
+    code); out: optional (buffer, byte offset) per plane to pack into instead of fresh arrays"""
+    lib = load()
+    lib.av1mi_input_pack.argtypes = [C.c_int] * 4 + [C.c_void_p] * 6
+    dt = np.uint8 if bit_depth == 8 else np.uint16
+    y, u, v = (np.ascontiguousarray(a, dt) for a in (y, u, v))
+    rows, width = y.shape
+    n = [input_plane_bytes(fmt, bit_depth, p, width, rows) for p in range(3)]
+    if out is None:
+        out = [(np.zeros(max(k, 1), np.uint8), 0) for k in n]
+    ptr = [(b.ctypes.data + off) if k else None for (b, off), k in zip(out, n)]
+    rc = lib.av1mi_input_pack(int(fmt), int(bit_depth), width, rows, y.ctypes.data, u.ctypes.data, v.ctypes.data, *ptr)
+    if rc:
+        raise Av1miError(rc, "av1mi_input_pack(format %d, bit depth %d, %dx%d)" % (fmt, bit_depth, width, rows))
+    return [b[off:off + k] for (b, off), k in zip(out, n)]
+
+
 def _view(ptr, shape, dtype):
     n = int(np.prod(shape)) * np.dtype(dtype).itemsize
     return np.frombuffer((C.c_uint8 * n).from_address(ptr), dtype=dtype).reshape(shape)
@@ -123,12 +152,14 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0):
+                 key_block_size=0, input_format=0):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
-        key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size)"""
+        key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
+        source handed to input_planes() / submit_device())"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
-        self.cfg = GopConfig(width, height, bit_depth, base_q_idx, gop_length, segments, search_range, gpu_entropy, vw, vh, coder_streams, key_block_size)
+        self.cfg = GopConfig(width, height, bit_depth, base_q_idx, gop_length, segments, search_range, gpu_entropy, vw, vh, coder_streams, key_block_size, input_format)
+        self.input_format = input_format
         self.g = C.c_void_p()
         ctx.lib.av1mi_gop_open.argtypes = [C.c_void_p, C.POINTER(GopConfig), C.POINTER(C.c_void_p)]
         ctx._chk(ctx.lib.av1mi_gop_open(ctx.h, C.byref(self.cfg), C.byref(self.g)))
@@ -143,15 +174,19 @@ class GopSession:
         y, u, v = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self.ctx._chk(self.ctx.lib.av1mi_gop_acquire_input(self.g, C.byref(y), C.byref(u), C.byref(v)))
         S, w, h = self.segments, self.w, self.h
+        if self.input_format != INPUT_PLANAR:      # the session's format: flat byte views of av1mi_input_plane_bytes each (no third plane when semi-planar)
+            n = [input_plane_bytes(self.input_format, self.bd, p, w, S * h) for p in range(3)]
+            return tuple(_view(ptr.value, (k,), np.uint8) for ptr, k in zip((y, u, v), n) if k)
         return (_view(y.value, (S * h, w), self.dt), _view(u.value, (S * h // 2, w // 2), self.dt), _view(v.value, (S * h // 2, w // 2), self.dt))
 
     def submit(self, frame_type=-1):
         self.ctx._chk(self.ctx.lib.av1mi_gop_submit(self.g, int(frame_type)))
 
-    def submit_device(self, d_y, d_u, d_v, frame_type=-1):
-        """a batch whose source planes (DevBuf) are already in device memory: no upload (av1mi_gop_submit_device)"""
+    def submit_device(self, d_y, d_u, d_v=None, frame_type=-1):
+        """a batch whose source planes (DevBuf, in the session's input format; d_v None for P010 / NV12) are already in device
+        memory: no upload (av1mi_gop_submit_device)"""
         self.ctx.lib.av1mi_gop_submit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        self.ctx._chk(self.ctx.lib.av1mi_gop_submit_device(self.g, d_y.ptr, d_u.ptr, d_v.ptr, int(frame_type)))
+        self.ctx._chk(self.ctx.lib.av1mi_gop_submit_device(self.g, d_y.ptr, d_u.ptr, d_v.ptr if d_v is not None else None, int(frame_type)))
 
     def pending(self):
         return self.ctx.lib.av1mi_gop_pending(self.g)
@@ -216,7 +251,7 @@ class GopSession:
             self.g = None
 
 
-N_KERNEL_KINDS = 17   # enum av1mi_kernel_kind
+N_KERNEL_KINDS = 18   # enum av1mi_kernel_kind
 _lib = None
 
 
@@ -379,6 +414,12 @@ class Context:
         self._chk(self.lib.av1mi_deblock_frames(self.h, C.c_void_p(d_src.ptr), src_stride, C.c_void_p(d_dst.ptr), dst_stride, w, h,
                                                 bd, int(is_chroma), C.c_void_p(d_mi.ptr), mi_stride, C.c_size_t(mi_frame_stride),
                                                 sharpness, nframes))
+
+    def input_convert(self, fmt, bit_depth, width, rows, d_in, d_out):
+        """d_in: the format's planes (2 or 3 DevBuf), d_out: planar Y, U, V (DevBuf); one launch, asynchronous (av1mi_input_convert)"""
+        self.lib.av1mi_input_convert.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 6
+        i = [b.ptr for b in d_in] + [None] * (3 - len(d_in))
+        self._chk(self.lib.av1mi_input_convert(self.h, int(fmt), int(bit_depth), int(width), int(rows), *i, *[b.ptr for b in d_out]))
 
     def prof_enable(self, on):
         self._chk(self.lib.av1mi_prof_enable(self.h, int(on)))

@@ -122,6 +122,15 @@ struct InterLaunch {
   const void *ref_alt[3]; const uint8_t *ref_sel;   // optional: ref_sel[f * 3 + p] == 0 -> frame f predicts plane p from ref_alt[p]
 };
 hipError_t launch_me_int(const InterLaunch &L, hipStream_t s);
+
+// the input stage (input_kernels.hip): the planes of a batch in a wire / surface format (enum av1mi_input_format, not PLANAR) ->
+// planar planes; ny luma and nc chroma samples per plane.  The unit counts are filled in by the launcher.
+struct InputLaunch {
+  const void *in[3]; void *out[3];
+  size_t ny, nc;
+  size_t units, units_y, units_c;
+};
+hipError_t launch_input_convert(int format, InputLaunch L, hipStream_t s);
 hipError_t launch_inter_pipe(const InterLaunch &L, hipStream_t s);
 
 int tx_width(int tx_size);

@@ -285,7 +285,7 @@ int av1mi_prof_get(av1mi_ctx *ctx, int kind, int *launches, double *total_ms) {
 }
 const char *av1mi_kernel_kind_name(int kind) {
   static const char *n[AV1MI_K_KINDS] = { "fwd_txfm", "inv_txfm", "quantize", "dequantize", "intra_pred", "mc", "deblock",
-                                          "cdef", "loop_restoration", "intra_pipeline", "inter_pipeline", "misc", "entropy_code", "entropy_pack", "entropy_tokens", "me_integer", "entropy_chains" };
+                                          "cdef", "loop_restoration", "intra_pipeline", "inter_pipeline", "misc", "entropy_code", "entropy_pack", "entropy_tokens", "me_integer", "entropy_chains", "input_convert" };
   return kind < 0 || kind >= AV1MI_K_KINDS ? "?" : n[kind];
 }
 
@@ -510,6 +510,24 @@ int av1mi_extend_frames(av1mi_ctx *ctx, void *d_plane, int stride, int w, int h,
     return fail(ctx, AV1MI_E_INVAL, "bad plane geometry %dx%d (visible %dx%d) stride %d", w, h, visible_w, visible_h, stride);
   if (nframes < 0 || nframes > 65535) return fail(ctx, AV1MI_E_INVAL, "nframes %d out of range", nframes);
   HIP_TRY(ctx, av1mi::launch_extend(d_plane, stride, w, h, visible_w, visible_h, bd, nframes, ctx->stream));
+  return AV1MI_OK;
+}
+
+int av1mi_input_convert(av1mi_ctx *ctx, int format, int bit_depth, int width, int rows, const void *d_in0, const void *d_in1, const void *d_in2,
+                        void *d_y, void *d_u, void *d_v) {
+  BIND(ctx);
+  if (format == AV1MI_INPUT_PLANAR || !av1mi_input_plane_bytes(format, bit_depth, 0, width, rows))
+    return fail(ctx, AV1MI_E_INVAL, "input format %d with bit depth %d, %d x %d rows: nothing to convert or not a valid combination", format, bit_depth, width, rows);
+  const bool semi = format != AV1MI_INPUT_PACKED10;      // P010 / NV12: two input planes
+  if (semi) d_in2 = d_in1;
+  const void *ptrs[] = { d_in0, d_in1, d_in2, d_y, d_u, d_v };
+  for (const void *p : ptrs) if (!p || ((uintptr_t)p & 15)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned device pointer (16 bytes)");
+  av1mi::InputLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.in[0] = d_in0; L.in[1] = d_in1; L.in[2] = d_in2; L.out[0] = d_y; L.out[1] = d_u; L.out[2] = d_v;
+  L.ny = (size_t)width * rows; L.nc = L.ny / 4;
+  ProfScope ps(ctx, AV1MI_K_INPUT);
+  HIP_TRY(ctx, av1mi::launch_input_convert(format, L, ctx->stream));
   return AV1MI_OK;
 }
 

@@ -5,12 +5,17 @@
 //
 // Streams.  The context's stream runs the kernels; the session adds an upload stream and a download stream.  Per batch:
 //   up:   wait slot.filters_done (the kernels that last read this slot's source)  -> H2D of the three source planes -> uploaded
-//   main: wait uploaded -> k_intra_pipe | k_me_int + k_inter_pipe -> symbols_ready -> deblock x3, CDEF, LR x3 -> reference
+//   main: wait uploaded -> [k_input_convert] -> k_intra_pipe | k_me_int + k_inter_pipe -> symbols_ready -> deblock x3, CDEF, LR x3 -> reference
 //   down: wait symbols_ready -> D2H of the symbols into pinned memory -> downloaded
 //   side: (GPU entropy coding) wait symbols_ready -> k_av1_* -> payloads gathered into the slot's pinned buffer -> ent_done
 // Source and symbol buffers exist kSlots = 3 times (slot = batch % 3): batch t + 2 uploads while batch t + 1 is in the block
 // pipeline and the coder works on batch t, whose predecessor the host is still reading.  Four streams, one hardware queue each
 // (a fifth would share a queue with one of these and serialise behind it).
+//
+// Input formats (av1mi_gop_config.input_format).  PLANAR is the path above and nothing else.  Otherwise the source crosses PCIe (or
+// arrives from the caller, av1mi_gop_submit_device) in a wire / surface format and one launch of k_input_convert (input_kernels.hip)
+// on the main stream turns it into the slot's planar d_src planes, which the block pipeline reads as ever; a slot then owns pinned
+// + device WIRE buffers (h_in / d_in) instead of pinned planar planes.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -60,8 +65,10 @@ void frame_params(int q, int bd, int frame_type, av1mi_frame_params *p) {
 enum { kSlots = 3, kFallbacksToHostMode = 3 };      // batches in flight: one uploading / in the block pipeline, one in the coder, one being read by the host
 
 struct Slot {
-  void *h_src[3] = { nullptr, nullptr, nullptr };       // pinned
+  void *h_src[3] = { nullptr, nullptr, nullptr };       // pinned (PLANAR sessions only)
   void *d_src[3] = { nullptr, nullptr, nullptr };
+  // the source in the session's wire / surface format (other sessions): pinned + device, [2] unused by the semi-planar formats
+  void *h_in[3] = { nullptr, nullptr, nullptr }, *d_in[3] = { nullptr, nullptr, nullptr };
   // symbols: device + pinned host mirror
   void *d_lev[3] = { nullptr, nullptr, nullptr }, *h_lev[3] = { nullptr, nullptr, nullptr };
   void *d_modes[2] = { nullptr, nullptr }, *h_modes[2] = { nullptr, nullptr };
@@ -85,6 +92,8 @@ struct av1mi_gop {
   av1mi_ctx *ctx = nullptr;
   av1mi_gop_config cfg{};
   size_t ny = 0, nc = 0, nb = 0, bps = 1;      // per BATCH (segments stacked): luma samples, chroma samples, blocks
+  int fmt = AV1MI_INPUT_PLANAR;                // cfg.input_format
+  size_t in_bytes[3] = {};                     // fmt != PLANAR: bytes of a batch's planes in that format (av1mi_input_plane_bytes)
   hipStream_t up = nullptr, down = nullptr;     // with the context's main and side streams: four, one hardware queue each
   Slot slot[kSlots];
   void *d_rec[3] = {}, *d_dbl[3] = {}, *d_cdef[3] = {}, *d_ref[3] = {};
@@ -137,6 +146,9 @@ int setup(av1mi_gop *g) {
   g->bps = c.bit_depth == 8 ? 1 : 2;
   g->ny = (size_t)w * h * S; g->nc = g->ny / 4; g->nb = g->ny / 64;
   g->vw = c.visible_width ? c.visible_width : w; g->vh = c.visible_height ? c.visible_height : h;
+  g->fmt = c.input_format;
+  if (g->fmt != AV1MI_INPUT_PLANAR)
+    for (int p = 0; p < 3; p++) g->in_bytes[p] = av1mi_input_plane_bytes(g->fmt, c.bit_depth, p, w, h * S);
   G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
   G_HIP(hipStreamCreateWithFlags(&g->up, hipStreamNonBlocking));
   // (created in every mode, used only where symbols go to the host at submit time or a batch falls back.  HIP deals its four
@@ -149,7 +161,12 @@ int setup(av1mi_gop *g) {
   for (Slot &s : g->slot) {
     for (int p = 0; p < 3; p++) {
       const size_t n = (p ? g->nc : g->ny);
-      G_TRY(host_alloc(g, &s.h_src[p], n * g->bps)); G_TRY(dev_alloc(g, &s.d_src[p], n * g->bps));
+      if (g->fmt == AV1MI_INPUT_PLANAR) {
+        G_TRY(host_alloc(g, &s.h_src[p], n * g->bps)); G_TRY(dev_alloc(g, &s.d_src[p], n * g->bps));
+      } else {      // the planar planes are the conversion's output: device only
+        G_TRY(dev_alloc(g, &s.d_src[p], n * g->bps));
+        if (g->in_bytes[p]) { G_TRY(host_alloc(g, &s.h_in[p], g->in_bytes[p])); G_TRY(dev_alloc(g, &s.d_in[p], g->in_bytes[p])); }
+      }
       // the pinned mirror of the levels (as large as the source) is needed when the symbols go to the host; with the GPU coder
       // only a batch the coder gives back needs it, and it is allocated then (pinning memory is a good part of the start-up time)
       if (c.gpu_entropy != 1) G_TRY(host_alloc(g, &s.h_lev[p], n * 2));
@@ -249,6 +266,12 @@ int av1mi_gop_open(av1mi_ctx *ctx, const av1mi_gop_config *cfg, av1mi_gop **out)
   if (cfg->base_q_idx < 1 || cfg->base_q_idx > 255 || cfg->gop_length < 1 || cfg->segments < 1 || cfg->segments > 4096 || cfg->search_range < 0 ||
       cfg->search_range > 15 || cfg->gpu_entropy < 0 || cfg->gpu_entropy > 2 || cfg->coder_streams < 0 || cfg->coder_streams > 3)
     return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "bad base_q_idx / gop_length / segments / search_range / gpu_entropy");
+  if (cfg->input_format < AV1MI_INPUT_PLANAR || cfg->input_format > AV1MI_INPUT_NV12)
+    return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "input_format %d unknown (0 planar, 1 packed 10-bit, 2 P010, 3 NV12)", cfg->input_format);
+  if ((cfg->input_format == AV1MI_INPUT_PACKED10 || cfg->input_format == AV1MI_INPUT_P010) && cfg->bit_depth != 10)
+    return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "input_format %d (%s) needs bit_depth 10, not %d", cfg->input_format, cfg->input_format == AV1MI_INPUT_P010 ? "P010" : "packed 10-bit",
+                           cfg->bit_depth);
+  if (cfg->input_format == AV1MI_INPUT_NV12 && cfg->bit_depth != 8) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "input_format 3 (NV12) needs bit_depth 8, not %d", cfg->bit_depth);
   if (cfg->key_block_size != 0 && cfg->key_block_size != 8 && cfg->key_block_size != 32) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "key_block_size %d not supported (8 or 32)", cfg->key_block_size);
   if (cfg->key_block_size == 32 && (cfg->width & 31))
     return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "key_block_size 32 needs a width that is a multiple of 32");
@@ -310,7 +333,8 @@ int av1mi_gop_acquire_input(av1mi_gop *g, void **y, void **u, void **v) {
   G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
   Slot &s = g->slot[g->submitted % kSlots];
   if (s.upload_pending) { G_HIP(hipEventSynchronize(s.uploaded)); s.upload_pending = false; }   // the copy engine still reads these buffers
-  *y = s.h_src[0]; *u = s.h_src[1]; *v = s.h_src[2];
+  if (g->fmt == AV1MI_INPUT_PLANAR) { *y = s.h_src[0]; *u = s.h_src[1]; *v = s.h_src[2]; }
+  else { *y = s.h_in[0]; *u = s.h_in[1]; *v = s.h_in[2]; }      // in the session's format; no third plane in the semi-planar ones
   g->acquired = true;
   return AV1MI_OK;
 }
@@ -344,7 +368,33 @@ static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src
   Slot &s = g->slot[g->submitted % kSlots];
   hipStream_t main = av1mi::ctx_stream(g->ctx);
   const void *src[3] = { s.d_src[0], s.d_src[1], s.d_src[2] };
-  if (dev_src) {
+  if (g->fmt != AV1MI_INPUT_PLANAR) {
+    // The source arrives in a wire / surface format and is converted into the slot's planar d_src on the MAIN stream.  Two hazards:
+    //  - d_src is read by the slot's previous batch up to its restoration decision.  That ran on the main stream too, so the
+    //    conversion is ordered behind it by the stream itself; no event.
+    //  - d_in, the device wire buffer, is read by the conversion of the slot's previous batch.  The upload into it waits for that
+    //    batch's filters_done, which was recorded on the main stream AFTER that conversion.
+    // `uploaded` keeps its two meanings: the main stream waits for it before the conversion, and av1mi_gop_acquire_input waits for it
+    // before the host may overwrite the pinned wire buffers.
+    av1mi::InputLaunch L;
+    memset(&L, 0, sizeof(L));
+    if (dev_src) {
+      for (int p = 0; p < 3; p++) L.in[p] = dev_src[p];
+    } else {
+      if (s.kernel_pending) G_HIP(hipStreamWaitEvent(g->up, s.filters_done, 0));
+      for (int p = 0; p < 3; p++)
+        if (g->in_bytes[p]) G_HIP(hipMemcpyAsync(s.d_in[p], s.h_in[p], g->in_bytes[p], hipMemcpyHostToDevice, g->up));
+      G_HIP(hipEventRecord(s.uploaded, g->up));
+      s.upload_pending = true;
+      G_HIP(hipStreamWaitEvent(main, s.uploaded, 0));
+      for (int p = 0; p < 3; p++) L.in[p] = s.d_in[p];
+    }
+    for (int p = 0; p < 3; p++) L.out[p] = s.d_src[p];
+    L.ny = g->ny; L.nc = g->nc;
+    const av1mi::ProfToken pt = av1mi::ctx_prof_begin(g->ctx, AV1MI_K_INPUT, main);
+    G_HIP(av1mi::launch_input_convert(g->fmt, L, main));
+    av1mi::ctx_prof_end(g->ctx, pt, main);
+  } else if (dev_src) {
     for (int p = 0; p < 3; p++) src[p] = dev_src[p];
   } else {
     // upload: not before the kernels that last read this slot's source have finished (the restoration decision is the last reader)
@@ -507,7 +557,9 @@ int av1mi_gop_submit(av1mi_gop *g, int frame_type) {
 
 int av1mi_gop_submit_device(av1mi_gop *g, const void *d_y, const void *d_u, const void *d_v, int frame_type) {
   if (!g) return AV1MI_E_INVAL;
-  if (!d_y || !d_u || !d_v || (((uintptr_t)d_y | (uintptr_t)d_u | (uintptr_t)d_v) & 7)) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "null or misaligned device source plane");
+  if (g->fmt == AV1MI_INPUT_P010 || g->fmt == AV1MI_INPUT_NV12) d_v = d_u;      // semi-planar: no third plane
+  if (!d_y || !d_u || !d_v || (((uintptr_t)d_y | (uintptr_t)d_u | (uintptr_t)d_v) & (g->fmt == AV1MI_INPUT_PLANAR ? 7 : 15)))
+    return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "null or misaligned device source plane");
   const void *src[3] = { d_y, d_u, d_v };
   return submit_batch(g, frame_type, src);
 }

@@ -168,6 +168,11 @@ int RunBackend(const BackendJob &job, std::string *err) {
     cfg.gpu_entropy = job.gpu_entropy ? 1 : 0;
     // key frames in 32x32 blocks where the frame allows it (the coded width a multiple of 32)
     cfg.key_block_size = (job.key_block_size == 32 && (w & 31) == 0) ? 32 : 8;
+    // -av1mi_pack10 1: a 10-bit source crosses PCIe at 10 bits per sample; the session's pinned buffers are then three packed planes
+    const bool packed = job.pack10 && y.bd == 10;
+    if (packed) cfg.input_format = AV1MI_INPUT_PACKED10;
+    const size_t py_bytes = packed ? fy / 2 * 5 / 4 : fy, pc_bytes = py_bytes / 4;      // one segment's planes in the pinned buffers
+    std::vector<std::vector<unsigned char>> scratch(packed ? (size_t)S : 0);          // per reader thread: one planar frame to pack from
     CHK(av1mi_gop_open(ctx, &cfg, &gop));
     av1::SequenceParams sp; sp.width = y.w; sp.height = y.h; sp.bit_depth = y.bd;
     for (const std::string &side : job.tracks)
@@ -215,11 +220,21 @@ int RunBackend(const BackendJob &job, std::string *err) {
           if (!exists(s, t)) {
             // a shorter last GOP / fewer GOPs than segments: the slot is coded (the batch is one launch) and its output dropped.  Flat
             // planes, not whatever the pinned buffer held: stale pixels could cost the GPU coder's tile capacity for the whole batch
-            memset((unsigned char *)py + fy * s, 0, fy); memset((unsigned char *)pu + fc * s, 0, fc); memset((unsigned char *)pv + fc * s, 0, fc);
+            // (zero samples pack to zero bytes)
+            memset((unsigned char *)py + py_bytes * s, 0, py_bytes); memset((unsigned char *)pu + pc_bytes * s, 0, pc_bytes); memset((unsigned char *)pv + pc_bytes * s, 0, pc_bytes);
             continue;
           }
           reads.th.emplace_back([&, s, t, py, pu, pv]() {
-            reads.ok[(size_t)s] = y.read((long)s * G + t, w, h, (unsigned char *)py + fy * s, (unsigned char *)pu + fc * s, (unsigned char *)pv + fc * s);
+            if (!packed) {
+              reads.ok[(size_t)s] = y.read((long)s * G + t, w, h, (unsigned char *)py + fy * s, (unsigned char *)pu + fc * s, (unsigned char *)pv + fc * s);
+              return;
+            }
+            // the frame (edge padding included) into this thread's scratch, then packed into the segment's byte range of the pinned planes
+            std::vector<unsigned char> &f = scratch[(size_t)s];
+            f.resize(fy + 2 * fc);
+            reads.ok[(size_t)s] = y.read((long)s * G + t, w, h, f.data(), f.data() + fy, f.data() + fy + fc) &&
+                                  av1mi_input_pack(AV1MI_INPUT_PACKED10, 10, w, h, f.data(), f.data() + fy, f.data() + fy + fc, (unsigned char *)py + py_bytes * s,
+                                                   (unsigned char *)pu + pc_bytes * s, (unsigned char *)pv + pc_bytes * s) == AV1MI_OK;
           });
         }
         return true;

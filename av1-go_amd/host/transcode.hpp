@@ -51,6 +51,9 @@ struct BackendJob {
                            // symbols are downloaded and coded on the host cores.  Same bytes either way.
   int key_block_size = 32; // -av1mi_key_block_size 8 | 32: key frames in 32x32 blocks where the coded width (the source's rounded up to 8) is a multiple of 32 (av1mi_gop_config.key_block_size;
                            // +3.7 dB at equal size on the synthetic key frames at q 128 for ~9 % of the throughput), else 8x8 like every other frame
+  int pack10 = 0;          // -av1mi_pack10 0 | 1: with a 10-bit source, pack the frames to 10 bits per sample on the reader threads before the PCIe upload
+                           // (av1mi.h AV1MI_INPUT_PACKED10: 5 / 8 of the bytes on the link and in the pinned buffers; same output bytes).  Accepted and
+                           // without effect with an 8-bit source
   std::vector<std::string> tracks;   // -av1mi_tracks <file.mka> (repeatable): Matroska side files whose audio / subtitle tracks are copied
                                      // next to the video (the reference's `-c:a copy -c:s copy`, transcode.go:134-137, after an external demux)
 };

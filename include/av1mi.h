@@ -83,7 +83,7 @@ int av1mi_timer_end(av1mi_ctx *ctx, float *elapsed_ms);
 enum av1mi_kernel_kind {
   AV1MI_K_FWD_TXFM, AV1MI_K_INV_TXFM, AV1MI_K_QUANT, AV1MI_K_DEQUANT, AV1MI_K_INTRA_PRED, AV1MI_K_MC,
   AV1MI_K_DEBLOCK, AV1MI_K_CDEF, AV1MI_K_LR, AV1MI_K_INTRA_PIPE, AV1MI_K_INTER_PIPE, AV1MI_K_MISC, AV1MI_K_ENTROPY,
-  AV1MI_K_ENTROPY_PACK, AV1MI_K_ENTROPY_TOKENS, AV1MI_K_ME_INT, AV1MI_K_ENTROPY_CHAINS, AV1MI_K_KINDS
+  AV1MI_K_ENTROPY_PACK, AV1MI_K_ENTROPY_TOKENS, AV1MI_K_ME_INT, AV1MI_K_ENTROPY_CHAINS, AV1MI_K_INPUT, AV1MI_K_KINDS
 };
 int av1mi_prof_enable(av1mi_ctx *ctx, int on);
 int av1mi_prof_reset(av1mi_ctx *ctx);
@@ -325,6 +325,37 @@ uint32_t av1mi_av1_entropy_ops_per_tile(void);
 int av1mi_av1_entropy_last_list_words(av1mi_ctx *ctx, uint64_t *words);
 uint32_t av1mi_av1_entropy_slot_bytes(void);
 
+/* ---- input formats: the layouts a source batch (segments stacked, stride = width, `rows` = segments * height luma rows) may
+ * arrive in.  Every kernel of the block pipeline reads PLANAR; the other three are wire / surface formats that one streaming
+ * kernel (av1-go_amd/csrc/input_kernels.hip) turns into planar planes on the device.
+ *   PACKED10 halves the zeros on the PCIe link: a 10-bit sample in a 16-bit container carries 6 padding bits, packed planes are
+ *     5 / 8 of the bytes.  Normative layout: each plane is ONE little-endian bit string in the planar plane's raster order, sample
+ *     i occupies bits [10 i, 10 i + 10).  Equivalently bytes 5k .. 5k + 4 hold samples s0..s3 = 4k .. 4k + 3 as
+ *       s0 & 0xff, (s0 >> 8) | (s1 & 0x3f) << 2, (s1 >> 6) | (s2 & 0x0f) << 4, (s2 >> 4) | (s3 & 0x03) << 6, s3 >> 2.
+ *     No row or segment padding: width and height are multiples of 8, so a segment's luma plane is a multiple of 64 samples (80
+ *     bytes) and its chroma plane a multiple of 16 samples (20 bytes): every segment starts on a 4-byte boundary.
+ *   P010 / NV12 are what hardware and most software decoders leave in memory (the reference hands its encoder exactly these,
+ *     internal/ffmpeg/transcode.go:99-111,173-178): the luma plane as in PLANAR (P010: the value in bits 15..6 of a uint16, the
+ *     low 6 bits are ignored), then ONE plane of rows / 2 rows of width / 2 interleaved (U, V) pairs of the luma's element type. */
+enum av1mi_input_format {
+  AV1MI_INPUT_PLANAR   = 0,  /* Y, U, V planes, uint8 (8-bit) or uint16 with the value in the low bits (10-bit) */
+  AV1MI_INPUT_PACKED10 = 1,  /* bit_depth 10 only: Y, U, V planes, 10 bits per sample, no padding */
+  AV1MI_INPUT_P010     = 2,  /* bit_depth 10 only: Y plane uint16 with the value in bits 15..6, then one plane of interleaved U,V pairs */
+  AV1MI_INPUT_NV12     = 3   /* bit_depth 8 only: Y plane uint8, then one plane of interleaved U,V pairs */
+};
+/* bytes of plane 0..2 of a stack of `rows` luma rows (multiple of 8, like width) in `format`; 0 for an invalid combination of
+ * format and bit depth, a bad size, and for plane 2 of the semi-planar formats.  No GPU needed. */
+size_t av1mi_input_plane_bytes(int format, int bit_depth, int plane, int width, int rows);
+/* planar planes in (uint8 / uint16 as PLANAR), the format's planes out (av1mi_input_plane_bytes each; out2 unused by the
+ * semi-planar formats); plain host code, no GPU needed.  PACKED10 packs any 4-byte-aligned run of whole 16-sample groups on its
+ * own, so the segments of a batch can be packed by different threads into their byte ranges of one buffer (the product's reader
+ * threads do).  AV1MI_OK or AV1MI_E_INVAL (null pointer, invalid combination). */
+int av1mi_input_pack(int format, int bit_depth, int width, int rows, const void *y, const void *u, const void *v, void *out0, void *out1, void *out2);
+/* the conversion on the device, one launch for the three planes: d_in0..2 in `format` (d_in2 ignored by the semi-planar formats)
+ * -> planar d_y, d_u, d_v.  Asynchronous on the context's stream; all pointers 16-byte aligned; PLANAR is refused (nothing to do). */
+int av1mi_input_convert(av1mi_ctx *ctx, int format, int bit_depth, int width, int rows, const void *d_in0, const void *d_in1, const void *d_in2,
+                        void *d_y, void *d_u, void *d_v);
+
 /* ---- GOP session: the encoder object a cgo replacement of RunTranscode drives (reference call site
  * internal/daemon/daemon.go:101 -> internal/ffmpeg/transcode.go:194; SURVEY.md §8b "av1mi_open(config) / av1mi_encode /
  * av1mi_flush").  It owns the closed-GOP orchestration and the encoder's filter-parameter POLICY, so that no caller
@@ -366,6 +397,9 @@ typedef struct av1mi_gop_config {
   int key_block_size;    /* 0 / 8: key frames in 8x8 blocks like every frame.  32: key frames in 32x32 blocks (luma 32x32 DCT, chroma 16x16,
                             transform type by mode) over every COMPLETE superblock row, 8x8 blocks in a last partial row: +3.7 dB at equal
                             size on the synthetic key frames at q 128, +1.85 dB at q 24.  Needs width % 32 == 0 */
+  int input_format;      /* enum av1mi_input_format: the layout of the source the session is fed (pinned buffers of av1mi_gop_acquire_input,
+                            device buffers of av1mi_gop_submit_device).  0 = planar.  Anything else adds one conversion launch per batch
+                            in front of the block pipeline (k_input_convert) and changes nothing about what is coded */
 } av1mi_gop_config;
 
 /* Frame-header parameters chosen by the session's policy for one frame (non-normative encoder choices; the bitstream carries
@@ -415,13 +449,16 @@ int av1mi_gop_open(av1mi_ctx *ctx, const av1mi_gop_config *cfg, av1mi_gop **out)
 void av1mi_gop_close(av1mi_gop *g);
 /* pinned host planes for the NEXT batch: segment s occupies rows [s * height, (s + 1) * height) of the luma plane
  * (stride = width samples, uint8 for 8-bit, uint16 otherwise) and the matching rows of the half-size chroma planes.
- * Blocks until the upload that last used these buffers has finished. */
+ * Blocks until the upload that last used these buffers has finished.
+ * A session whose input_format is not PLANAR hands out the buffers in THAT format (sizes: av1mi_input_plane_bytes with rows =
+ * segments * height): PACKED10 three byte buffers, P010 / NV12 the luma plane in *y, the interleaved plane in *u and *v = NULL. */
 int av1mi_gop_acquire_input(av1mi_gop *g, void **y, void **u, void **v);
 /* queue the batch in the acquired buffers.  frame_type: 0 key, 1 inter, -1 = by position in the GOP (gop_length).
  * AV1MI_E_INVAL when av1mi_gop_max_in_flight() batches are already in flight (collect first). */
 int av1mi_gop_submit(av1mi_gop *g, int frame_type);
 /* The same for a batch whose source planes are ALREADY in device memory (same layout as the pinned planes: segments stacked, stride =
- * width): no upload is queued, the kernels read the caller's buffers, which must stay valid and unchanged until the batch has been
+ * width; in the session's input_format, d_v ignored by P010 / NV12, 16-byte aligned unless PLANAR): no upload is queued, the kernels
+ * read the caller's buffers, which must stay valid and unchanged until the batch has been
  * collected.  No av1mi_gop_acquire_input() before it.  (A decoder that leaves its frames in HBM feeds the session this way; bench.py
  * times this path, the bench contract's "inputs already resident in HBM".) */
 int av1mi_gop_submit_device(av1mi_gop *g, const void *d_y, const void *d_u, const void *d_v, int frame_type);
