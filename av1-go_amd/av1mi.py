@@ -88,7 +88,8 @@ class LrDecideJob(C.Structure):
 class GopConfig(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("bit_depth", C.c_int), ("base_q_idx", C.c_int), ("gop_length", C.c_int),
                 ("segments", C.c_int), ("search_range", C.c_int), ("gpu_entropy", C.c_int), ("visible_width", C.c_int),
-                ("visible_height", C.c_int), ("coder_streams", C.c_int), ("key_block_size", C.c_int), ("input_format", C.c_int)]
+                ("visible_height", C.c_int), ("coder_streams", C.c_int), ("key_block_size", C.c_int), ("input_format", C.c_int), ("source_width", C.c_int),
+                ("source_height", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -143,6 +144,22 @@ def input_pack(fmt, bit_depth, y, u, v, out=None):
     return [b[off:off + k] for (b, off), k in zip(out, n)]
 
 
+def scale_filter(src_n, dst_n):
+    """the resampler's table for src_n -> dst_n samples (av1mi_scale_filter, host code): (taps, first [dst_n] int32, coef [dst_n, taps]
+    int16); no GPU needed"""
+    lib = load()
+    lib.av1mi_scale_filter.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
+    t = C.c_int()
+    rc = lib.av1mi_scale_filter(int(src_n), int(dst_n), C.byref(t), None, None)
+    if rc:
+        raise Av1miError(rc, "av1mi_scale_filter(%d -> %d)" % (src_n, dst_n))
+    first, coef = np.empty(dst_n, np.int32), np.empty((dst_n, t.value), np.int16)
+    rc = lib.av1mi_scale_filter(int(src_n), int(dst_n), C.byref(t), first.ctypes.data, coef.ctypes.data)
+    if rc:
+        raise Av1miError(rc, "av1mi_scale_filter(%d -> %d)" % (src_n, dst_n))
+    return t.value, first, coef
+
+
 def _view(ptr, shape, dtype):
     n = int(np.prod(shape)) * np.dtype(dtype).itemsize
     return np.frombuffer((C.c_uint8 * n).from_address(ptr), dtype=dtype).reshape(shape)
@@ -152,13 +169,17 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0):
+                 key_block_size=0, input_format=0, source=None):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
-        source handed to input_planes() / submit_device())"""
+        source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
+        they are to be scaled to the coded frame (av1mi_gop_config.source_width): the input buffers then have that size rounded up to 8"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
-        self.cfg = GopConfig(width, height, bit_depth, base_q_idx, gop_length, segments, search_range, gpu_entropy, vw, vh, coder_streams, key_block_size, input_format)
+        sw, sh = source if source is not None else (0, 0)
+        self.cfg = GopConfig(width, height, bit_depth, base_q_idx, gop_length, segments, search_range, gpu_entropy, vw, vh, coder_streams, key_block_size, input_format,
+                             sw, sh)
+        self.in_w, self.in_h = ((sw + 7) & ~7, (sh + 7) & ~7) if source is not None else (width, height)      # geometry of the input buffers
         self.input_format = input_format
         self.g = C.c_void_p()
         ctx.lib.av1mi_gop_open.argtypes = [C.c_void_p, C.POINTER(GopConfig), C.POINTER(C.c_void_p)]
@@ -173,7 +194,7 @@ class GopSession:
         """numpy views of the pinned host planes of the next batch: shapes [segments * height, width] and the half-size chroma"""
         y, u, v = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self.ctx._chk(self.ctx.lib.av1mi_gop_acquire_input(self.g, C.byref(y), C.byref(u), C.byref(v)))
-        S, w, h = self.segments, self.w, self.h
+        S, w, h = self.segments, self.in_w, self.in_h
         if self.input_format != INPUT_PLANAR:      # the session's format: flat byte views of av1mi_input_plane_bytes each (no third plane when semi-planar)
             n = [input_plane_bytes(self.input_format, self.bd, p, w, S * h) for p in range(3)]
             return tuple(_view(ptr.value, (k,), np.uint8) for ptr, k in zip((y, u, v), n) if k)
@@ -420,6 +441,13 @@ class Context:
         self.lib.av1mi_input_convert.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 6
         i = [b.ptr for b in d_in] + [None] * (3 - len(d_in))
         self._chk(self.lib.av1mi_input_convert(self.h, int(fmt), int(bit_depth), int(width), int(rows), *i, *[b.ptr for b in d_out]))
+
+    def scale_planes(self, bit_depth, src_w, src_h, dst_w, dst_h, frames, d_src, d_dst):
+        """d_src: planar Y, U, V (DevBuf) of `frames` stacked frames of true size src_w x src_h in buffers of that size rounded up to 8;
+        d_dst: the same for dst_w x dst_h; one launch, asynchronous (av1mi_scale_planes)"""
+        self.lib.av1mi_scale_planes.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 2
+        src, dst = (C.c_void_p * 3)(*[b.ptr for b in d_src]), (C.c_void_p * 3)(*[b.ptr for b in d_dst])
+        self._chk(self.lib.av1mi_scale_planes(self.h, int(bit_depth), int(src_w), int(src_h), int(dst_w), int(dst_h), int(frames), src, dst))
 
     def prof_enable(self, on):
         self._chk(self.lib.av1mi_prof_enable(self.h, int(on)))

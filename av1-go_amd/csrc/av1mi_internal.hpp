@@ -133,6 +133,16 @@ struct InputLaunch {
 hipError_t launch_input_convert(int format, InputLaunch L, hipStream_t s);
 hipError_t launch_inter_pipe(const InterLaunch &L, hipStream_t s);
 
+// the resampler of the input stage (scale_kernels.hip): a plan holds the device tables of one geometry (true luma size of the source ->
+// target luma size, both buffers at their sizes rounded up to 8); one launch scales the three planes of `frames` stacked frames
+struct ScalePlan;
+hipError_t scale_plan_create(int bd, int sw, int sh, int dw, int dh, ScalePlan **out);      // synchronous (allocates, uploads)
+void scale_plan_destroy(ScalePlan *P);
+bool scale_plan_is(const ScalePlan *P, int bd, int sw, int sh, int dw, int dh);
+hipError_t launch_scale(const ScalePlan *P, int frames, const void *const *src, void *const *dst, hipStream_t s);
+// the argument rules shared by av1mi_scale_planes and the session: null = fine, else the reason
+const char *scale_geometry_error(int sw, int sh, int dw, int dh);
+
 int tx_width(int tx_size);
 int tx_height(int tx_size);
 hipError_t launch_inv_txfm(int tx_size, const TxLaunch &L, int bd, hipStream_t s);

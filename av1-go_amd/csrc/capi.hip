@@ -20,6 +20,7 @@ struct av1mi_ctx {
   void *scratch = nullptr;  // staging for the host-pointer single-block forms
   size_t scratch_bytes = 0;
   av1mi_av1ent_state *av1ent = nullptr;   // the AV1-syntax tile coder's scratch (av1_entropy_kernels.hip)
+  av1mi::ScalePlan *scale_plan = nullptr; // av1mi_scale_planes: the tables of the geometry it was last called with
   // per-kernel profile: one event pair per launch while enabled
   bool prof_on = false;
   struct ProfRec { int kind; hipEvent_t e0, e1; };
@@ -193,6 +194,7 @@ void av1mi_close(av1mi_ctx *ctx) {
   if (ctx->back) { (void)hipStreamSynchronize(ctx->back); (void)hipStreamDestroy(ctx->back); }
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->av1ent) av1mi::av1ent_free(ctx->av1ent);
+  av1mi::scale_plan_destroy(ctx->scale_plan);
   for (auto &r : ctx->prof_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
   for (auto e : ctx->prof_pool) (void)hipEventDestroy(e);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -528,6 +530,28 @@ int av1mi_input_convert(av1mi_ctx *ctx, int format, int bit_depth, int width, in
   L.ny = (size_t)width * rows; L.nc = L.ny / 4;
   ProfScope ps(ctx, AV1MI_K_INPUT);
   HIP_TRY(ctx, av1mi::launch_input_convert(format, L, ctx->stream));
+  return AV1MI_OK;
+}
+
+int av1mi_scale_planes(av1mi_ctx *ctx, int bit_depth, int src_w, int src_h, int dst_w, int dst_h, int frames, const void *const d_src[3],
+                       void *const d_dst[3]) {
+  BIND(ctx);
+  if (bit_depth != 8 && bit_depth != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bit_depth);
+  if (const char *why = av1mi::scale_geometry_error(src_w, src_h, dst_w, dst_h)) return fail(ctx, AV1MI_E_INVAL, "%dx%d -> %dx%d: %s", src_w, src_h, dst_w, dst_h, why);
+  if (frames < 1 || (size_t)frames * (size_t)((src_h > dst_h ? src_h : dst_h) + 7) > 65535u * 32u) return fail(ctx, AV1MI_E_INVAL, "frames %d out of range", frames);
+  if (!d_src || !d_dst) return fail(ctx, AV1MI_E_INVAL, "null plane array");
+  for (int p = 0; p < 3; p++)
+    if (!d_src[p] || !d_dst[p] || (((uintptr_t)d_src[p] | (uintptr_t)d_dst[p]) & 15)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned device pointer (16 bytes)");
+  if (!av1mi::scale_plan_is(ctx->scale_plan, bit_depth, src_w, src_h, dst_w, dst_h)) {
+    if (ctx->scale_plan) {      // a launch that still reads the old tables may be in flight
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      av1mi::scale_plan_destroy(ctx->scale_plan);
+      ctx->scale_plan = nullptr;
+    }
+    HIP_TRY(ctx, av1mi::scale_plan_create(bit_depth, src_w, src_h, dst_w, dst_h, &ctx->scale_plan));
+  }
+  ProfScope ps(ctx, AV1MI_K_INPUT);
+  HIP_TRY(ctx, av1mi::launch_scale(ctx->scale_plan, frames, d_src, d_dst, ctx->stream));
   return AV1MI_OK;
 }
 

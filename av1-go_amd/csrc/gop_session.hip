@@ -16,6 +16,11 @@
 // arrives from the caller, av1mi_gop_submit_device) in a wire / surface format and one launch of k_input_convert (input_kernels.hip)
 // on the main stream turns it into the slot's planar d_src planes, which the block pipeline reads as ever; a slot then owns pinned
 // + device WIRE buffers (h_in / d_in) instead of pinned planar planes.
+//
+// Scaling (av1mi_gop_config.source_width / source_height).  The session is fed SOURCE frames (any input format, at the source size
+// rounded up to 8) and one launch of the resampler (scale_kernels.hip) on the main stream, behind the conversion where there is one,
+// fills the slot's planar d_src planes at the coded size.  A slot then owns the source in the session's format (h_in / d_in, as above)
+// and, unless the format is planar already, device-only planar planes at the source size (d_pre) between the two launches.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -69,6 +74,7 @@ struct Slot {
   void *d_src[3] = { nullptr, nullptr, nullptr };
   // the source in the session's wire / surface format (other sessions): pinned + device, [2] unused by the semi-planar formats
   void *h_in[3] = { nullptr, nullptr, nullptr }, *d_in[3] = { nullptr, nullptr, nullptr };
+  void *d_pre[3] = { nullptr, nullptr, nullptr };       // scaling sessions whose format is not planar: the converted planes at the source size
   // symbols: device + pinned host mirror
   void *d_lev[3] = { nullptr, nullptr, nullptr }, *h_lev[3] = { nullptr, nullptr, nullptr };
   void *d_modes[2] = { nullptr, nullptr }, *h_modes[2] = { nullptr, nullptr };
@@ -93,7 +99,10 @@ struct av1mi_gop {
   av1mi_gop_config cfg{};
   size_t ny = 0, nc = 0, nb = 0, bps = 1;      // per BATCH (segments stacked): luma samples, chroma samples, blocks
   int fmt = AV1MI_INPUT_PLANAR;                // cfg.input_format
-  size_t in_bytes[3] = {};                     // fmt != PLANAR: bytes of a batch's planes in that format (av1mi_input_plane_bytes)
+  size_t in_bytes[3] = {};                     // fmt != PLANAR or scaling: bytes of a batch's planes as the session is fed them
+  av1mi::ScalePlan *scale = nullptr;           // scaling sessions: the resampler's tables
+  int sw8 = 0, sh8 = 0;                        // ... and the source size rounded up to 8 (the geometry of the fed buffers)
+  size_t pre_ny = 0, pre_nc = 0;               // ... luma / chroma samples of a batch at that size
   hipStream_t up = nullptr, down = nullptr;     // with the context's main and side streams: four, one hardware queue each
   Slot slot[kSlots];
   void *d_rec[3] = {}, *d_dbl[3] = {}, *d_cdef[3] = {}, *d_ref[3] = {};
@@ -147,9 +156,15 @@ int setup(av1mi_gop *g) {
   g->ny = (size_t)w * h * S; g->nc = g->ny / 4; g->nb = g->ny / 64;
   g->vw = c.visible_width ? c.visible_width : w; g->vh = c.visible_height ? c.visible_height : h;
   g->fmt = c.input_format;
-  if (g->fmt != AV1MI_INPUT_PLANAR)
-    for (int p = 0; p < 3; p++) g->in_bytes[p] = av1mi_input_plane_bytes(g->fmt, c.bit_depth, p, w, h * S);
+  const bool scaling = c.source_width != 0;
+  if (scaling) {
+    g->sw8 = (c.source_width + 7) & ~7; g->sh8 = (c.source_height + 7) & ~7;
+    g->pre_ny = (size_t)g->sw8 * g->sh8 * S; g->pre_nc = g->pre_ny / 4;
+  }
+  if (g->fmt != AV1MI_INPUT_PLANAR || scaling)
+    for (int p = 0; p < 3; p++) g->in_bytes[p] = av1mi_input_plane_bytes(g->fmt, c.bit_depth, p, scaling ? g->sw8 : w, (scaling ? g->sh8 : h) * S);
   G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
+  if (scaling) G_HIP(av1mi::scale_plan_create(c.bit_depth, c.source_width, c.source_height, g->vw, g->vh, &g->scale));
   G_HIP(hipStreamCreateWithFlags(&g->up, hipStreamNonBlocking));
   // (created in every mode, used only where symbols go to the host at submit time or a batch falls back.  HIP deals its four
   // default hardware queues to streams in creation order: main, up, down, side — and the coder's back stream, the fifth, shares
@@ -161,11 +176,12 @@ int setup(av1mi_gop *g) {
   for (Slot &s : g->slot) {
     for (int p = 0; p < 3; p++) {
       const size_t n = (p ? g->nc : g->ny);
-      if (g->fmt == AV1MI_INPUT_PLANAR) {
+      if (g->fmt == AV1MI_INPUT_PLANAR && !scaling) {
         G_TRY(host_alloc(g, &s.h_src[p], n * g->bps)); G_TRY(dev_alloc(g, &s.d_src[p], n * g->bps));
-      } else {      // the planar planes are the conversion's output: device only
+      } else {      // the planar planes are the conversion's / the resampler's output: device only
         G_TRY(dev_alloc(g, &s.d_src[p], n * g->bps));
         if (g->in_bytes[p]) { G_TRY(host_alloc(g, &s.h_in[p], g->in_bytes[p])); G_TRY(dev_alloc(g, &s.d_in[p], g->in_bytes[p])); }
+        if (scaling && g->fmt != AV1MI_INPUT_PLANAR) G_TRY(dev_alloc(g, &s.d_pre[p], (p ? g->pre_nc : g->pre_ny) * g->bps));
       }
       // the pinned mirror of the levels (as large as the source) is needed when the symbols go to the host; with the GPU coder
       // only a batch the coder gives back needs it, and it is allocated then (pinning memory is a good part of the start-up time)
@@ -272,6 +288,13 @@ int av1mi_gop_open(av1mi_ctx *ctx, const av1mi_gop_config *cfg, av1mi_gop **out)
     return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "input_format %d (%s) needs bit_depth 10, not %d", cfg->input_format, cfg->input_format == AV1MI_INPUT_P010 ? "P010" : "packed 10-bit",
                            cfg->bit_depth);
   if (cfg->input_format == AV1MI_INPUT_NV12 && cfg->bit_depth != 8) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "input_format 3 (NV12) needs bit_depth 8, not %d", cfg->bit_depth);
+  if ((cfg->source_width != 0) != (cfg->source_height != 0) || cfg->source_width < 0 || cfg->source_height < 0)
+    return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "source size %dx%d: give both source_width and source_height, or neither", cfg->source_width, cfg->source_height);
+  if (cfg->source_width) {
+    const int tw = cfg->visible_width ? cfg->visible_width : cfg->width, th = cfg->visible_height ? cfg->visible_height : cfg->height;
+    if (const char *why = av1mi::scale_geometry_error(cfg->source_width, cfg->source_height, tw, th))
+      return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "source size %dx%d -> %dx%d: %s", cfg->source_width, cfg->source_height, tw, th, why);
+  }
   if (cfg->key_block_size != 0 && cfg->key_block_size != 8 && cfg->key_block_size != 32) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "key_block_size %d not supported (8 or 32)", cfg->key_block_size);
   if (cfg->key_block_size == 32 && (cfg->width & 31))
     return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "key_block_size 32 needs a width that is a multiple of 32");
@@ -304,6 +327,7 @@ void av1mi_gop_close(av1mi_gop *g) {
   }
   for (void *p : g->dev_allocs) (void)hipFree(p);
   for (void *p : g->host_allocs) (void)hipHostFree(p);
+  av1mi::scale_plan_destroy(g->scale);
   delete g;
 }
 
@@ -333,7 +357,7 @@ int av1mi_gop_acquire_input(av1mi_gop *g, void **y, void **u, void **v) {
   G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
   Slot &s = g->slot[g->submitted % kSlots];
   if (s.upload_pending) { G_HIP(hipEventSynchronize(s.uploaded)); s.upload_pending = false; }   // the copy engine still reads these buffers
-  if (g->fmt == AV1MI_INPUT_PLANAR) { *y = s.h_src[0]; *u = s.h_src[1]; *v = s.h_src[2]; }
+  if (g->fmt == AV1MI_INPUT_PLANAR && !g->scale) { *y = s.h_src[0]; *u = s.h_src[1]; *v = s.h_src[2]; }
   else { *y = s.h_in[0]; *u = s.h_in[1]; *v = s.h_in[2]; }      // in the session's format; no third plane in the semi-planar ones
   g->acquired = true;
   return AV1MI_OK;
@@ -368,18 +392,18 @@ static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src
   Slot &s = g->slot[g->submitted % kSlots];
   hipStream_t main = av1mi::ctx_stream(g->ctx);
   const void *src[3] = { s.d_src[0], s.d_src[1], s.d_src[2] };
-  if (g->fmt != AV1MI_INPUT_PLANAR) {
-    // The source arrives in a wire / surface format and is converted into the slot's planar d_src on the MAIN stream.  Two hazards:
-    //  - d_src is read by the slot's previous batch up to its restoration decision.  That ran on the main stream too, so the
-    //    conversion is ordered behind it by the stream itself; no event.
-    //  - d_in, the device wire buffer, is read by the conversion of the slot's previous batch.  The upload into it waits for that
-    //    batch's filters_done, which was recorded on the main stream AFTER that conversion.
-    // `uploaded` keeps its two meanings: the main stream waits for it before the conversion, and av1mi_gop_acquire_input waits for it
-    // before the host may overwrite the pinned wire buffers.
-    av1mi::InputLaunch L;
-    memset(&L, 0, sizeof(L));
+  if (g->fmt != AV1MI_INPUT_PLANAR || g->scale) {
+    // The source arrives in a wire / surface format and / or at another size, and is converted / scaled into the slot's planar d_src on
+    // the MAIN stream.  Two hazards:
+    //  - d_src (and d_pre, the planes between conversion and scaling) is read by the slot's previous batch up to its restoration
+    //    decision.  That ran on the main stream too, so the launches here are ordered behind it by the stream itself; no event.
+    //  - d_in, the device buffer of the source as fed, is read by the conversion / scaling of the slot's previous batch.  The upload
+    //    into it waits for that batch's filters_done, which was recorded on the main stream AFTER those launches.
+    // `uploaded` keeps its two meanings: the main stream waits for it before the first launch, and av1mi_gop_acquire_input waits for
+    // it before the host may overwrite the pinned buffers.
+    const void *in[3];
     if (dev_src) {
-      for (int p = 0; p < 3; p++) L.in[p] = dev_src[p];
+      for (int p = 0; p < 3; p++) in[p] = dev_src[p];
     } else {
       if (s.kernel_pending) G_HIP(hipStreamWaitEvent(g->up, s.filters_done, 0));
       for (int p = 0; p < 3; p++)
@@ -387,13 +411,23 @@ static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src
       G_HIP(hipEventRecord(s.uploaded, g->up));
       s.upload_pending = true;
       G_HIP(hipStreamWaitEvent(main, s.uploaded, 0));
-      for (int p = 0; p < 3; p++) L.in[p] = s.d_in[p];
+      for (int p = 0; p < 3; p++) in[p] = s.d_in[p];
     }
-    for (int p = 0; p < 3; p++) L.out[p] = s.d_src[p];
-    L.ny = g->ny; L.nc = g->nc;
-    const av1mi::ProfToken pt = av1mi::ctx_prof_begin(g->ctx, AV1MI_K_INPUT, main);
-    G_HIP(av1mi::launch_input_convert(g->fmt, L, main));
-    av1mi::ctx_prof_end(g->ctx, pt, main);
+    if (g->fmt != AV1MI_INPUT_PLANAR) {
+      av1mi::InputLaunch L;
+      memset(&L, 0, sizeof(L));
+      for (int p = 0; p < 3; p++) { L.in[p] = in[p]; L.out[p] = g->scale ? s.d_pre[p] : s.d_src[p]; }
+      L.ny = g->scale ? g->pre_ny : g->ny; L.nc = g->scale ? g->pre_nc : g->nc;
+      const av1mi::ProfToken pt = av1mi::ctx_prof_begin(g->ctx, AV1MI_K_INPUT, main);
+      G_HIP(av1mi::launch_input_convert(g->fmt, L, main));
+      av1mi::ctx_prof_end(g->ctx, pt, main);
+      for (int p = 0; p < 3; p++) in[p] = s.d_pre[p];
+    }
+    if (g->scale) {
+      const av1mi::ProfToken pt = av1mi::ctx_prof_begin(g->ctx, AV1MI_K_INPUT, main);
+      G_HIP(av1mi::launch_scale(g->scale, S, in, s.d_src, main));
+      av1mi::ctx_prof_end(g->ctx, pt, main);
+    }
   } else if (dev_src) {
     for (int p = 0; p < 3; p++) src[p] = dev_src[p];
   } else {

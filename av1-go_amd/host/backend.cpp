@@ -154,15 +154,25 @@ int RunBackend(const BackendJob &job, std::string *err) {
   do { int rc_ = (call); if (rc_ != AV1MI_OK) { *err = std::string(#call) + ": " + av1mi_last_error(ctx); code = 2; goto done; } } while (0)
   if (!y.open(job.input, err)) { code = 1; goto done; }
   {
-    const int G = job.gop, w = (y.w + 7) & ~7, h = (y.h + 7) & ~7;       // the coded size; y.w x y.h is what a decoder outputs
+    // the target: what the argv's filter chain yields on this source (transcode.go:92-115), or -av1mi_scale; no chain = the source
+    int tw = y.w, th = y.h;
+    bool square = y.sar_n == y.sar_d;
+    if (job.have_vf && !ScaleTarget(y.w, y.h, y.sar_n, y.sar_d, job.vf, &tw, &th, &square, err)) { code = 1; goto done; }
+    if (job.scale_w) { tw = job.scale_w; th = job.scale_h; square = true; }
+    const bool scaling = tw != y.w || th != y.h || job.scale_w != 0;
+    const int G = job.gop, w = (tw + 7) & ~7, h = (th + 7) & ~7;       // the coded size; tw x th is what a decoder outputs
+    // what the reader threads deliver: the coded size (the source's edge replicated into the padding), or — when the GPU scales — the
+    // source size rounded up to 8
+    const int rw = scaling ? (y.w + 7) & ~7 : w, rh = scaling ? (y.h + 7) & ~7 : h;
     int S = std::max(job.segments, 1);
     if (y.known_frames() >= 0) S = (int)std::max<long>(1, std::min<long>(S, (y.known_frames() + G - 1) / G));      // no more segments than the file has GOPs
     long total_frames = 0;
     const int threads = job.threads > 0 ? job.threads : (int)std::max(1u, std::thread::hardware_concurrency());
-    const size_t bps = y.bd == 8 ? 1 : 2, fy = (size_t)w * h * bps, fc = fy / 4;
+    const size_t bps = y.bd == 8 ? 1 : 2, fy = (size_t)rw * rh * bps, fc = fy / 4;
     av1mi_gop_config cfg;
     memset(&cfg, 0, sizeof(cfg));
-    if (w != y.w || h != y.h) { cfg.visible_width = y.w; cfg.visible_height = y.h; }
+    if (w != tw || h != th) { cfg.visible_width = tw; cfg.visible_height = th; }
+    if (scaling) { cfg.source_width = y.w; cfg.source_height = y.h; }
     cfg.width = w; cfg.height = h; cfg.bit_depth = y.bd; cfg.base_q_idx = job.quality < 1 ? 1 : job.quality; cfg.gop_length = G; cfg.segments = S;
     cfg.search_range = 8;
     cfg.gpu_entropy = job.gpu_entropy ? 1 : 0;
@@ -174,7 +184,9 @@ int RunBackend(const BackendJob &job, std::string *err) {
     const size_t py_bytes = packed ? fy / 2 * 5 / 4 : fy, pc_bytes = py_bytes / 4;      // one segment's planes in the pinned buffers
     std::vector<std::vector<unsigned char>> scratch(packed ? (size_t)S : 0);          // per reader thread: one planar frame to pack from
     CHK(av1mi_gop_open(ctx, &cfg, &gop));
-    av1::SequenceParams sp; sp.width = y.w; sp.height = y.h; sp.bit_depth = y.bd;
+    av1::SequenceParams sp; sp.width = tw; sp.height = th; sp.bit_depth = y.bd;
+    // pixels that stay non-square: the track at least says at which shape to show them
+    if (!square) sink.set_display_size((int)((long)tw * y.sar_n / y.sar_d), th);
     for (const std::string &side : job.tracks)
       if (!sink.add_side_file(side, err)) { code = 1; goto done; }
     if (!sink.open(job.output, sp, y.fps_n, y.fps_d, err)) { code = 1; goto done; }
@@ -226,14 +238,14 @@ int RunBackend(const BackendJob &job, std::string *err) {
           }
           reads.th.emplace_back([&, s, t, py, pu, pv]() {
             if (!packed) {
-              reads.ok[(size_t)s] = y.read((long)s * G + t, w, h, (unsigned char *)py + fy * s, (unsigned char *)pu + fc * s, (unsigned char *)pv + fc * s);
+              reads.ok[(size_t)s] = y.read((long)s * G + t, rw, rh, (unsigned char *)py + fy * s, (unsigned char *)pu + fc * s, (unsigned char *)pv + fc * s);
               return;
             }
             // the frame (edge padding included) into this thread's scratch, then packed into the segment's byte range of the pinned planes
             std::vector<unsigned char> &f = scratch[(size_t)s];
             f.resize(fy + 2 * fc);
-            reads.ok[(size_t)s] = y.read((long)s * G + t, w, h, f.data(), f.data() + fy, f.data() + fy + fc) &&
-                                  av1mi_input_pack(AV1MI_INPUT_PACKED10, 10, w, h, f.data(), f.data() + fy, f.data() + fy + fc, (unsigned char *)py + py_bytes * s,
+            reads.ok[(size_t)s] = y.read((long)s * G + t, rw, rh, f.data(), f.data() + fy, f.data() + fy + fc) &&
+                                  av1mi_input_pack(AV1MI_INPUT_PACKED10, 10, rw, rh, f.data(), f.data() + fy, f.data() + fy + fc, (unsigned char *)py + py_bytes * s,
                                                    (unsigned char *)pu + pc_bytes * s, (unsigned char *)pv + pc_bytes * s) == AV1MI_OK;
           });
         }

@@ -48,6 +48,20 @@ long long av1mi_host_y4m_scan(const char *path, int group, unsigned long long *s
   geometry[0] = y.w; geometry[1] = y.h; geometry[2] = y.bd; geometry[3] = y.fps_n; geometry[4] = y.fps_d;
   return total;
 }
+// the header's sample aspect ratio as Y4mSource keeps it; 0, or -1 when the file does not open
+int av1mi_host_y4m_sar(const char *path, int *sar) {
+  Y4mSource y;
+  std::string e;
+  if (!y.open(path, &e)) return -1;
+  sar[0] = y.sar_n; sar[1] = y.sar_d;
+  return 0;
+}
+// ScaleTarget (transcode.hpp): the size a filter chain yields on a source; 0, or -1 for a chain with an unsupported filter
+int av1mi_host_scale_target(int iw, int ih, int sar_n, int sar_d, const char *chain, int *w, int *h) {
+  std::string e;
+  bool square = false;
+  return ScaleTarget(iw, ih, sar_n, sar_d, chain ? chain : "", w, h, &square, &e) ? 0 : -1;
+}
 // StreamSink (mux.hpp) alone, for the CPU tests: n_units byte strings (unit i = bytes [off[i], off[i + 1]) of `units`, standing in for
 // temporal units; unit i is a key frame when i % gop == 0) muxed at fps_n / fps_d together with the tracks of the Matroska side files
 // `sides` (paths separated by '\n').  Returns 0, or -1 with the text in err.
@@ -197,6 +211,20 @@ int av1mi_host_mux_units(const char *path, int w, int h, int bd, int fps_n, int 
                          const uint8_t *keys, int n) {
   StreamSink sink; std::string err;
   av1::SequenceParams sp; sp.width = w; sp.height = h; sp.bit_depth = bd;
+  if (!sink.open(path, sp, fps_n, fps_d, &err)) return 1;
+  for (int i = 0; i < n; i++) {
+    std::vector<uint8_t> tu(data, data + sizes[i]);
+    data += sizes[i];
+    if (!sink.write(tu, keys[i] != 0, &err)) { sink.abort(); return 2; }
+  }
+  return sink.close(&err) ? 0 : 3;
+}
+// av1mi_host_mux_units with a display size on the video track (0, 0 = none)
+int av1mi_host_mux_units_display(const char *path, int w, int h, int bd, int fps_n, int fps_d, const uint8_t *data, const long long *sizes,
+                                 const uint8_t *keys, int n, int display_w, int display_h) {
+  StreamSink sink; std::string err;
+  av1::SequenceParams sp; sp.width = w; sp.height = h; sp.bit_depth = bd;
+  if (display_w || display_h) sink.set_display_size(display_w, display_h);
   if (!sink.open(path, sp, fps_n, fps_d, &err)) return 1;
   for (int i = 0; i < n; i++) {
     std::vector<uint8_t> tu(data, data + sizes[i]);

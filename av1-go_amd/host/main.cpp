@@ -1,5 +1,7 @@
 // av1mi_transcode — CLI with the reference's process contract (exit code, stderr text, output file last):
-//   av1mi_transcode [ffmpeg-style args] -i in.y4m [-global_quality:v:0 Q] [-g GOP] out.av1-tmp.mkv
+//   av1mi_transcode [ffmpeg-style args] -i in.y4m [-global_quality:v:0 Q] [-g GOP] [-vf:v:0 CHAIN] [-av1mi_scale WxH] out.av1-tmp.mkv
+//                   (CHAIN: the reference's scale filters, evaluated on the source's size and sample aspect ratio and applied on the GPU;
+//                   -av1mi_scale: an explicit output size, wins over the chain; any other filter is refused)
 //   av1mi_transcode --job in.y4m [--ratio 0.9] [--state DIR] [--wait S] [--replace-source 1]   (the ProcessJob lifecycle;
 //                   the source is only replaced on request: the output is video-only)
 #include <cstdio>

@@ -301,6 +301,7 @@ bool StreamSink::open(const std::string &path, const av1::SequenceParams &sp, in
     std::vector<uint8_t> av1c = { 0x81, 0x1F, (uint8_t)((sp.bit_depth == 10 ? 0x40 : 0x00) | 0x0C), 0x00 };   // profile 0, level index 31, 4:2:0
     av1c.insert(av1c.end(), seq.begin(), seq.end());
     std::vector<uint8_t> video; el_uint(video, 0xB0, (uint64_t)sp.width); el_uint(video, 0xBA, (uint64_t)sp.height);
+    if (display_w_ > 0 && display_h_ > 0) { el_uint(video, 0x54B0, (uint64_t)display_w_); el_uint(video, 0x54BA, (uint64_t)display_h_); }
     std::vector<uint8_t> te;
     el_uint(te, 0xD7, 1); el_uint(te, 0x73C5, 1); el_uint(te, 0x83, 1); el_uint(te, 0x9C, 0);
     el_str(te, 0x86, "V_AV1"); el_bin(te, 0x63A2, av1c);

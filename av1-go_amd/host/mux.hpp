@@ -44,6 +44,9 @@ class StreamSink {
  public:
   // before open(): every track of a Matroska side file is copied next to the video track (Matroska output only)
   bool add_side_file(const std::string &path, std::string *err);
+  // before open(): the size a player shows the video track at when the pixels are not square (Matroska DisplayWidth / DisplayHeight);
+  // not called = no such elements (square pixels)
+  void set_display_size(int w, int h) { display_w_ = w; display_h_ = h; }
   bool open(const std::string &path, const av1::SequenceParams &sp, int fps_n, int fps_d, std::string *err);
   // one temporal unit (temporal delimiter first) in presentation order
   bool write(const std::vector<uint8_t> &temporal_unit, bool key, std::string *err);
@@ -54,6 +57,7 @@ class StreamSink {
   FILE *f_ = nullptr;
   std::string path_;
   int fps_n_ = 30, fps_d_ = 1;
+  int display_w_ = 0, display_h_ = 0;
   long frames_ = 0;
   // Matroska state
   long seg_data_start_ = 0, duration_pos_ = 0, cluster_start_ = 0, cluster_size_pos_ = 0;

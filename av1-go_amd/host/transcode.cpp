@@ -52,6 +52,55 @@ bool TranscodeArgs(const std::string &ffmpegPath, const std::string &inputPath, 
   return true;
 }
 
+static const char kSarScale[] = "scale_vaapi=w='if(gt(iw,iw*sar),iw,iw*sar)':h='if(gt(iw,iw*sar),iw/sar,ih)'";   // :97
+static const char kEvenScale[] = "scale_vaapi=w=ceil(iw/2)*2:h=ceil(ih/2)*2";                                        // :98, :107
+
+static bool plain_int(const std::string &t, int *v) {
+  if (t.empty() || t.size() > 6) return false;
+  for (char c : t) if (c < '0' || c > '9') return false;
+  *v = std::atoi(t.c_str());
+  return true;
+}
+
+bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err) {
+  if (sar_n <= 0 || sar_d <= 0) sar_n = sar_d = 1;
+  long cw = iw, ch = ih;
+  bool sq = sar_n == sar_d;
+  // split at commas outside quotes
+  std::vector<std::string> parts;
+  std::string cur;
+  bool quoted = false;
+  for (char c : chain) {
+    if (c == '\'') quoted = !quoted;
+    if (c == ',' && !quoted) { parts.push_back(cur); cur.clear(); } else cur.push_back(c);
+  }
+  parts.push_back(cur);
+  for (const std::string &f : parts) {
+    int a = 0, b = 0;
+    if (f == kSarScale) {
+      if (sar_n < sar_d) ch = cw * sar_d / sar_n;      // gt(iw, iw * sar), i.e. sar < 1: (iw, iw / sar) — iw, as the expression is written
+      else cw = cw * sar_n / sar_d;                    // else (iw * sar, ih)
+      sar_n = sar_d = 1; sq = true;
+    } else if (f == kEvenScale) {
+      cw = (cw + 1) / 2 * 2; ch = (ch + 1) / 2 * 2;
+    } else if (f.empty() || f == "hwdownload" || f == "hwupload" || f == "setsar=1" || f.compare(0, 7, "format=") == 0) {
+    } else if (f.compare(0, 6, "scale=") == 0 && f.find(':') != std::string::npos && plain_int(f.substr(6, f.find(':') - 6), &a) &&
+               plain_int(f.substr(f.find(':') + 1), &b)) {
+      cw = a; ch = b; sar_n = sar_d = 1; sq = true;
+    } else if (f.compare(0, 14, "scale_vaapi=w=") == 0 && f.find(":h=") != std::string::npos && plain_int(f.substr(14, f.find(":h=") - 14), &a) &&
+               plain_int(f.substr(f.find(":h=") + 3), &b)) {
+      cw = a; ch = b; sar_n = sar_d = 1; sq = true;
+    } else {
+      if (err) *err = "Invalid argument: unsupported filter " + f.substr(0, f.find('='));
+      return false;
+    }
+    if (cw < 1 || ch < 1 || cw > 65535 || ch > 65535) { if (err) *err = "Invalid argument: filter " + f.substr(0, f.find('=')) + " yields an impossible size"; return false; }
+  }
+  *w = (int)cw; *h = (int)ch;
+  if (square) *square = sq;
+  return true;
+}
+
 bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std::string *err) {
   if (args.size() < 3) { if (err) *err = "Invalid argument: too few arguments"; return false; }
   job->output = args.back();
@@ -67,6 +116,20 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
     else if (args[i] == "-av1mi_tracks") job->tracks.push_back(args[i + 1]);
     else if (args[i] == "-av1mi_key_block_size") job->key_block_size = std::atoi(args[i + 1].c_str());
     else if (args[i] == "-av1mi_pack10") job->pack10 = std::atoi(args[i + 1].c_str());
+    else if (args[i] == "-vf:v:0" || args[i] == "-vf") { job->vf = args[i + 1]; job->have_vf = true; }
+    else if (args[i] == "-av1mi_scale") {
+      const std::string &v = args[i + 1];
+      const size_t x = v.find('x');
+      if (x == std::string::npos || !plain_int(v.substr(0, x), &job->scale_w) || !plain_int(v.substr(x + 1), &job->scale_h) || job->scale_w < 16 || job->scale_h < 16 ||
+          job->scale_w > 4096 || job->scale_h > 4096) {
+        if (err) *err = "Invalid argument: -av1mi_scale takes WxH with 16 .. 4096 each, not " + v;
+        return false;
+      }
+    }
+  }
+  if (job->have_vf) {      // a filter that cannot be applied must not be skipped silently: the chain is checked before anything runs
+    int w, h;
+    if (!ScaleTarget(16, 16, 1, 1, job->vf, &w, &h, nullptr, err)) return false;
   }
   if (!have_in) { if (err) *err = "Invalid argument: no input (-i) given"; return false; }
   if (job->quality < 0 || job->quality > 255 || job->gop < 1 || job->gop > 256 || job->segments < 1 || job->segments > 256 || job->threads < 0 || (job->key_block_size != 8 && job->key_block_size != 32) || (job->pack10 != 0 && job->pack10 != 1)) { if (err) *err = "Invalid argument: quality/gop/key block size/pack10 out of range"; return false; }

@@ -54,10 +54,21 @@ struct BackendJob {
   int pack10 = 0;          // -av1mi_pack10 0 | 1: with a 10-bit source, pack the frames to 10 bits per sample on the reader threads before the PCIe upload
                            // (av1mi.h AV1MI_INPUT_PACKED10: 5 / 8 of the bytes on the link and in the pinned buffers; same output bytes).  Accepted and
                            // without effect with an 8-bit source
+  bool have_vf = false;    // "-vf:v:0" / "-vf" was given: the filter chain below is evaluated on the source's size and sample aspect ratio
+  std::string vf;          // (ScaleTarget) and the frames are scaled on the GPU to what it yields; absent = the source size is coded as before
+  int scale_w = 0, scale_h = 0;      // -av1mi_scale WxH: an explicit target (16 .. 4096 each); wins over the chain
   std::vector<std::string> tracks;   // -av1mi_tracks <file.mka> (repeatable): Matroska side files whose audio / subtitle tracks are copied
                                      // next to the video (the reference's `-c:a copy -c:s copy`, transcode.go:134-137, after an external demux)
 };
 bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std::string *err);
+
+// The video filter chain of the argv (transcode.go:92-115), evaluated as it is written on a source of iw x ih samples with sample aspect
+// ratio sar_n : sar_d.  Recognised, literally: the reference's SAR scale (transcode.go:97: (w, h) = sar < 1 ? (iw, iw / sar) :
+// (iw * sar, ih), truncated to integers — the first branch divides iw, as written upstream), its even-size scale (:98 / :107: each
+// dimension rounded up to even), `hwdownload`, `hwupload`, `format=...`, `setsar=1` (no effect on planar 4:2:0 frames), and
+// `scale=W:H` / `scale_vaapi=w=W:h=H` with plain integers.  Returns false and "Invalid argument: unsupported filter <name>" for
+// anything else.  *square: the chain leaves square pixels (it resampled by the SAR, or to an explicit size).
+bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err);
 
 // transcode.go:194-315 contract: (0, "") on success AND the output file exists; (code, text <= 800 chars) on failure;
 // (-1, text) when the backend could not run at all (no HIP device, library error before any frame).

@@ -45,6 +45,7 @@ bool Y4mSource::open(const std::string &path, std::string *err) {
     else if (t[0] == 'H') h = atoi(t.c_str() + 1);
     else if (t[0] == 'F') sscanf(t.c_str() + 1, "%d:%d", &fps_n, &fps_d);
     else if (t[0] == 'C') cs = t.substr(1);
+    else if (t[0] == 'A') { if (sscanf(t.c_str() + 1, "%d:%d", &sar_n, &sar_d) != 2 || sar_n <= 0 || sar_d <= 0) sar_n = sar_d = 1; }
   }
   if (cs.rfind("420p10", 0) == 0) bd = 10;
   else if (cs.rfind("420", 0) == 0 && cs.find("p1") == std::string::npos) bd = 8;

@@ -21,6 +21,7 @@ class Y4mSource {
  public:
   ~Y4mSource();
   int w = 0, h = 0, bd = 8, fps_n = 30, fps_d = 1;
+  int sar_n = 1, sar_d = 1;      // the header's A<n>:<d> (sample aspect ratio); absent, A0:0 or malformed = 1:1
   // false + *err (FFmpeg-style text) on a missing file, a header that is not Y4M, an unsupported colourspace or size
   bool open(const std::string &path, std::string *err);
   bool seekable() const { return seekable_; }

@@ -356,6 +356,32 @@ int av1mi_input_pack(int format, int bit_depth, int width, int rows, const void 
 int av1mi_input_convert(av1mi_ctx *ctx, int format, int bit_depth, int width, int rows, const void *d_in0, const void *d_in1, const void *d_in2,
                         void *d_y, void *d_u, void *d_v);
 
+/* ---- scaling: the resampler of the input stage (av1-go_amd/csrc/scale_kernels.hip).  Integer arithmetic, bit exact by definition.
+ * One dimension, N true source samples -> M output samples, N / M in [1/4, 4]:
+ *   taps     T = 2 * ceil(3 * max(N, M) / M) (evaluated in integers: 6 when enlarging or copying, 12 for 2:1, at most 24);
+ *   stretch  s = max(N, M) / M;
+ *   output j: centre c = ((2 j + 1) N - M) / (2 M)  (= (j + 0.5) N / M - 0.5), first tap first[j] = floor(c) - T / 2 + 1 (floor in integers),
+ *            weight of tap k = L((first[j] + k - c) / s), L(x) = sinc(x) sinc(x / 3) for |x| < 3 and 0 beyond (sinc(x) = sin(pi x) / (pi x)), in
+ *            double precision; the weights are normalised to sum 1, multiplied by 16384 and rounded to nearest (floor(x + 0.5)); the
+ *            rounding remainder 16384 - sum goes to the tap of largest magnitude (the first of equals): EVERY ROW SUMS TO EXACTLY 16384;
+ *   source index of tap k = clamp(first[j] + k, 0, N - 1): edge replication at the TRUE size.
+ * A plane is resampled horizontally first, t = (sum coef * x + (1 << 9)) >> 10 — a signed 16-bit intermediate that keeps 4 extra bits
+ * and is not clamped (>> is the arithmetic shift) —, then vertically, out = clamp((sum coef * t + (1 << 17)) >> 18, 0, 2^bit_depth - 1).
+ * Y, U and V are resampled independently by the same rule at their own sizes: chroma N = (N_luma + 1) / 2, M = M_luma / 2, no
+ * chroma-siting shift.  N == M gives the unit impulse in every row: that pass is the identity.  Bounds: the largest sum of |coef| of a
+ * row is below 1.6 * 16384, so the intermediate stays below 2^15 at 10 bits, a coefficient (at most 16385) fits int16 and both sums int32. */
+/* the table for src_n -> dst_n samples (8 .. 4096 each, ratio within [1/4, 4]; else AV1MI_E_INVAL): *taps = T; first[dst_n] and
+ * coef[dst_n * T] (row j = the taps of output j) are filled unless first == NULL (then only T is returned, to size coef).  Plain host
+ * code, no GPU needed. */
+int av1mi_scale_filter(int src_n, int dst_n, int *taps, int32_t *first, int16_t *coef);
+/* `frames` stacked frames of three planar planes (uint8 for 8-bit, uint16 otherwise) of TRUE luma size src_w x src_h, in buffers of that
+ * size rounded up to 8 in both directions (stride and rows per frame; the half for chroma; nothing beyond the true size is read), ->
+ * the planes scaled to dst_w x dst_h in buffers of THAT size rounded up to 8 (the coded size); the padding of the destination receives
+ * the last true column / row.  Sizes 16 .. 4096, ratios within [1/4, 4].  One launch, asynchronous on the context's stream; all
+ * pointers 16-byte aligned.  Counted under AV1MI_K_INPUT in the profile. */
+int av1mi_scale_planes(av1mi_ctx *ctx, int bit_depth, int src_w, int src_h, int dst_w, int dst_h, int frames, const void *const d_src[3],
+                       void *const d_dst[3]);
+
 /* ---- GOP session: the encoder object a cgo replacement of RunTranscode drives (reference call site
  * internal/daemon/daemon.go:101 -> internal/ffmpeg/transcode.go:194; SURVEY.md §8b "av1mi_open(config) / av1mi_encode /
  * av1mi_flush").  It owns the closed-GOP orchestration and the encoder's filter-parameter POLICY, so that no caller
@@ -400,6 +426,14 @@ typedef struct av1mi_gop_config {
   int input_format;      /* enum av1mi_input_format: the layout of the source the session is fed (pinned buffers of av1mi_gop_acquire_input,
                             device buffers of av1mi_gop_submit_device).  0 = planar.  Anything else adds one conversion launch per batch
                             in front of the block pipeline (k_input_convert) and changes nothing about what is coded */
+  /* Scaling (0, 0 = none).  Otherwise the TRUE size of the frames the session is fed; width / height / visible_* above keep their
+   * meaning for the coded frame, whose true size (visible_*, or width x height) is the scaling target.  The buffers of
+   * av1mi_gop_acquire_input / av1mi_gop_submit_device then hold SOURCE frames, in the session's input_format, at the source size rounded
+   * up to 8 in both directions (stacked with that many rows per segment; the padding may be left undefined, it is never read), and
+   * one launch per batch (av1mi_scale_planes' kernel, after k_input_convert where the format is not planar) fills the planar planes
+   * of the coded size, which are device-only.  16 .. 4096 each, ratio to the target within [1/4, 4]; a source equal to the target is
+   * accepted and takes the scaling path (the identity). */
+  int source_width, source_height;
 } av1mi_gop_config;
 
 /* Frame-header parameters chosen by the session's policy for one frame (non-normative encoder choices; the bitstream carries
