@@ -160,7 +160,7 @@ namespace av1mi {
 av1mi_av1ent_state *av1ent_new();
 void av1ent_free(av1mi_av1ent_state *st);
 av1mi_av1ent_state *ctx_av1ent(av1mi_ctx *ctx);
-hipStream_t ctx_side_stream(av1mi_ctx *ctx);
+hipStream_t ctx_side_stream(av1mi_ctx *ctx);      // these two are created at their first use; null = creation failed
 hipStream_t ctx_back_stream(av1mi_ctx *ctx);
 // the AV1 tile coder of include/av1mi.h's av1mi_av1_entropy_job in two halves: info + tokens + chains on `front`, the serial range
 // coder + scan + gather on `back` (the same stream, or a second one: the lists are double-buffered, so the front half of the next
@@ -179,5 +179,11 @@ int ctx_fail(av1mi_ctx *ctx, int code, const char *fmt, ...);
 struct ProfToken { hipEvent_t e0 = nullptr; int kind = 0; };
 ProfToken ctx_prof_begin(av1mi_ctx *ctx, int kind, hipStream_t st);
 void ctx_prof_end(av1mi_ctx *ctx, const ProfToken &t, hipStream_t st);
+// ... and the same as a scope around the launch(es); st null = the context's stream
+struct ProfScope {
+  av1mi_ctx *ctx; hipStream_t st; ProfToken t;
+  ProfScope(av1mi_ctx *c, int kind, hipStream_t s = nullptr) : ctx(c), st(s ? s : ctx_stream(c)), t(ctx_prof_begin(c, kind, st)) {}
+  ~ProfScope() { ctx_prof_end(ctx, t, st); }
+};
 
 }  // namespace av1mi

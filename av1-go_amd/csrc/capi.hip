@@ -32,15 +32,7 @@ struct av1mi_ctx {
 
 namespace {
 
-int fail(av1mi_ctx *ctx, int code, const char *fmt, ...) {
-  if (ctx) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(ctx->err, sizeof(ctx->err), fmt, ap);
-    va_end(ap);
-  }
-  return code;
-}
+constexpr auto &fail = av1mi::ctx_fail;      // the one failure formatter, under the name the checks below use
 #define HIP_TRY(ctx, expr)                                                                     \
   do {                                                                                         \
     hipError_t e_ = (expr);                                                                    \
@@ -58,17 +50,7 @@ hipEvent_t prof_event(av1mi_ctx *ctx) {
   (void)hipEventCreate(&e);
   return e;
 }
-// RAII bracket around one kernel launch
-struct ProfScope {
-  av1mi_ctx *ctx; int kind; hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipStream_t st;
-  ProfScope(av1mi_ctx *c, int k, hipStream_t s = nullptr) : ctx(c), kind(k), st(s ? s : c->stream) {
-    if (ctx->prof_on) { e0 = prof_event(ctx); e1 = prof_event(ctx); (void)hipEventRecord(e0, st); }
-  }
-  ~ProfScope() {
-    if (e0) { (void)hipEventRecord(e1, st); ctx->prof_recs.push_back({ kind, e0, e1 }); }
-  }
-};
+using av1mi::ProfScope;
 void prof_drain(av1mi_ctx *ctx) {
   if (ctx->prof_recs.empty()) return;
   (void)hipStreamSynchronize(ctx->stream);
@@ -103,6 +85,13 @@ int ensure_scratch(av1mi_ctx *ctx, size_t bytes) {
   ctx->scratch_bytes = bytes;
   return AV1MI_OK;
 }
+// the argument rules that every entry point states in the same words
+int check_bd(av1mi_ctx *ctx, int bd) { return bd != 8 && bd != 10 ? fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bd) : AV1MI_OK; }
+int check_nframes(av1mi_ctx *ctx, int nframes) { return nframes < 0 || nframes > 65535 ? fail(ctx, AV1MI_E_INVAL, "nframes %d out of range", nframes) : AV1MI_OK; }
+int check_lr_unit(av1mi_ctx *ctx, int unit_size, int subsampled) {      // 32 is a chroma unit size only
+  if (unit_size == 64 || unit_size == 128 || unit_size == 256 || (unit_size == 32 && subsampled)) return AV1MI_OK;
+  return fail(ctx, AV1MI_E_INVAL, "restoration unit size %d not allowed", unit_size);
+}
 int check_tx_launch(av1mi_ctx *ctx, int tx_size, const void *coef, const void *plane, int stride, int nblocks) {
   if (tx_size < 0 || tx_size >= AV1MI_TX_SIZES_ALL) return fail(ctx, AV1MI_E_INVAL, "tx_size %d out of range", tx_size);
   if (!coef || !plane) return fail(ctx, AV1MI_E_INVAL, "null device pointer");
@@ -121,18 +110,12 @@ av1mi_av1ent_state *ctx_av1ent(av1mi_ctx *ctx) {
   if (!ctx->av1ent) ctx->av1ent = av1ent_new();
   return ctx->av1ent;
 }
-hipStream_t ctx_side_stream(av1mi_ctx *ctx) {
-  if (!ctx->side) {
-    if (hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking) != hipSuccess) return nullptr;
-  }
-  return ctx->side;
+static hipStream_t lazy_stream(hipStream_t *st) {
+  if (!*st && hipStreamCreateWithFlags(st, hipStreamNonBlocking) != hipSuccess) return nullptr;
+  return *st;
 }
-hipStream_t ctx_back_stream(av1mi_ctx *ctx) {
-  if (!ctx->back) {
-    if (hipStreamCreateWithFlags(&ctx->back, hipStreamNonBlocking) != hipSuccess) return nullptr;
-  }
-  return ctx->back;
-}
+hipStream_t ctx_side_stream(av1mi_ctx *ctx) { return lazy_stream(&ctx->side); }
+hipStream_t ctx_back_stream(av1mi_ctx *ctx) { return lazy_stream(&ctx->back); }
 ProfToken ctx_prof_begin(av1mi_ctx *ctx, int kind, hipStream_t st) {
   ProfToken t;
   t.kind = kind;
@@ -299,7 +282,7 @@ int av1mi_inv_txfm_add_grid(av1mi_ctx *ctx, int tx_size, const int32_t *d_coef, 
                             int blocks_per_row, int nblocks, const uint8_t *d_tx_types, int uniform_type) {
   BIND(ctx);
   if (int rc = check_tx_launch(ctx, tx_size, d_coef, d_plane, stride, nblocks)) return rc;
-  if (bd != 8 && bd != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bd);
+  if (int rc = check_bd(ctx, bd)) return rc;
   if (blocks_per_row <= 0) return fail(ctx, AV1MI_E_INVAL, "blocks_per_row %d <= 0", blocks_per_row);
   if (!d_tx_types && !tx_valid(tx_size, uniform_type))
     return fail(ctx, AV1MI_E_INVAL, "tx_type %d is not defined for tx_size %d", uniform_type, tx_size);
@@ -311,7 +294,7 @@ int av1mi_inv_txfm_add_list(av1mi_ctx *ctx, int tx_size, const int32_t *d_coef, 
                             const av1mi_txb *d_list, int nblocks) {
   BIND(ctx);
   if (int rc = check_tx_launch(ctx, tx_size, d_coef, d_plane, stride, nblocks)) return rc;
-  if (bd != 8 && bd != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bd);
+  if (int rc = check_bd(ctx, bd)) return rc;
   if (!d_list) return fail(ctx, AV1MI_E_INVAL, "null block list");
   av1mi::TxLaunch L = { const_cast<int32_t *>(d_coef), d_plane, stride, nblocks, d_list, nullptr, 0, 1 };
   { ProfScope ps(ctx, AV1MI_K_INV_TXFM); HIP_TRY(ctx, av1mi::launch_inv_txfm(tx_size, L, bd, ctx->stream)); }
@@ -343,7 +326,7 @@ int av1mi_intra_pred_list(av1mi_ctx *ctx, int tx_size, const void *d_ref, int re
   BIND(ctx);
   if (tx_size < 0 || tx_size >= AV1MI_TX_SIZES_ALL) return fail(ctx, AV1MI_E_INVAL, "tx_size %d out of range", tx_size);
   if (!d_ref || !d_dst || !d_list) return fail(ctx, AV1MI_E_INVAL, "null device pointer");
-  if (bd != 8 && bd != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bd);
+  if (int rc = check_bd(ctx, bd)) return rc;
   if (nblocks < 0 || ref_stride <= 0 || dst_stride <= 0 || (dst_stride & 3))
     return fail(ctx, AV1MI_E_INVAL, "bad geometry (nblocks %d, strides %d/%d)", nblocks, ref_stride, dst_stride);
   if ((uintptr_t)d_dst & 7) return fail(ctx, AV1MI_E_INVAL, "misaligned device pointer");
@@ -355,7 +338,7 @@ int av1mi_intra_pred_list(av1mi_ctx *ctx, int tx_size, const void *d_ref, int re
 int av1mi_cfl_pred_list(av1mi_ctx *ctx, int tx_size, const void *d_luma, int luma_stride, void *d_dst, int dst_stride, int bd,
                         const av1mi_cfl_blk *d_list, int nblocks) {
   BIND(ctx);
-  if (bd != 8 && bd != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bd);
+  if (int rc = check_bd(ctx, bd)) return rc;
   if (tx_size < 0 || tx_size >= AV1MI_TX_SIZES_ALL || av1mi::tx_width(tx_size) > 32 || av1mi::tx_height(tx_size) > 32)
     return fail(ctx, AV1MI_E_INVAL, "chroma-from-luma is defined for blocks up to 32x32 (tx_size %d)", tx_size);
   if (nblocks < 0) return fail(ctx, AV1MI_E_INVAL, "nblocks %d < 0", nblocks);
@@ -373,7 +356,7 @@ int av1mi_mc_list(av1mi_ctx *ctx, int size_id, const void *d_ref, int ref_stride
   BIND(ctx);
   if (size_id < 0 || size_id >= AV1MI_TX_SIZES_ALL) return fail(ctx, AV1MI_E_INVAL, "size_id %d out of range", size_id);
   if (!d_ref || !d_dst || !d_list || d_ref == d_dst) return fail(ctx, AV1MI_E_INVAL, "null or aliased device pointer");
-  if (bd != 8 && bd != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bd);
+  if (int rc = check_bd(ctx, bd)) return rc;
   if (nblocks < 0 || plane_w <= 0 || plane_h <= 0 || ref_stride < plane_w || dst_stride <= 0 || (dst_stride & 3))
     return fail(ctx, AV1MI_E_INVAL, "bad geometry");
   if ((uintptr_t)d_dst & 7) return fail(ctx, AV1MI_E_INVAL, "misaligned device pointer");
@@ -387,12 +370,12 @@ int av1mi_deblock_frames(av1mi_ctx *ctx, const void *d_src, int src_stride, void
                          int nframes) {
   BIND(ctx);
   if (!d_src || !d_dst || !d_mi || d_src == d_dst) return fail(ctx, AV1MI_E_INVAL, "null or aliased device pointer");
-  if (bd != 8 && bd != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bd);
+  if (int rc = check_bd(ctx, bd)) return rc;
   if (w <= 0 || h <= 0 || (w & 3) || (h & 3) || src_stride < w || dst_stride < w || (src_stride & 3) || (dst_stride & 3) ||
       mi_stride < w / 4)
     return fail(ctx, AV1MI_E_INVAL, "bad plane geometry %dx%d strides %d/%d/%d", w, h, src_stride, dst_stride, mi_stride);
   if (sharpness < 0 || sharpness > 7) return fail(ctx, AV1MI_E_INVAL, "sharpness %d out of range", sharpness);
-  if (nframes < 0 || nframes > 65535) return fail(ctx, AV1MI_E_INVAL, "nframes %d out of range", nframes);
+  if (int rc = check_nframes(ctx, nframes)) return rc;
   if (((uintptr_t)d_src & 7) || ((uintptr_t)d_dst & 7)) return fail(ctx, AV1MI_E_INVAL, "misaligned device pointer");
   if (nframes == 0) return AV1MI_OK;
   av1mi::DeblockLaunch L = { d_src, d_dst, src_stride, dst_stride, w, h, bd, is_chroma ? 1 : 0, d_mi, mi_stride, sharpness,
@@ -408,7 +391,7 @@ int av1mi_deblock_plane(av1mi_ctx *ctx, const void *d_src, int src_stride, void 
 int av1mi_cdef_frames(av1mi_ctx *ctx, const av1mi_cdef_job *j) {
   BIND(ctx);
   if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
-  if (j->bit_depth != 8 && j->bit_depth != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", j->bit_depth);
+  if (int rc = check_bd(ctx, j->bit_depth)) return rc;
   if (j->width <= 0 || j->height <= 0 || (j->width & 7) || (j->height & 7)) return fail(ctx, AV1MI_E_INVAL, "frame %dx%d must be a multiple of 8", j->width, j->height);
   if (j->damping < 3 || j->damping > 6 || j->nframes < 0 || j->nframes > 65535) return fail(ctx, AV1MI_E_INVAL, "bad damping/nframes");
   if (j->stride_y < j->width || j->stride_uv < j->width / 2 || (j->stride_y & 3) || (j->stride_uv & 3)) return fail(ctx, AV1MI_E_INVAL, "bad strides");
@@ -432,11 +415,10 @@ int av1mi_lr_frames(av1mi_ctx *ctx, const void *d_cdef, const void *d_deblocked,
   BIND(ctx);
   if (!d_cdef || !d_deblocked || !d_out || !d_units || d_out == d_cdef || d_out == d_deblocked)
     return fail(ctx, AV1MI_E_INVAL, "null or aliased device pointer");
-  if (bd != 8 && bd != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bd);
+  if (int rc = check_bd(ctx, bd)) return rc;
   if (w <= 0 || h <= 0 || stride < w) return fail(ctx, AV1MI_E_INVAL, "bad plane geometry %dx%d stride %d", w, h, stride);
-  if (!(unit_size == 64 || unit_size == 128 || unit_size == 256 || (unit_size == 32 && subsampled)))
-    return fail(ctx, AV1MI_E_INVAL, "restoration unit size %d not allowed", unit_size);
-  if (nframes < 0 || nframes > 65535) return fail(ctx, AV1MI_E_INVAL, "nframes %d out of range", nframes);
+  if (int rc = check_lr_unit(ctx, unit_size, subsampled)) return rc;
+  if (int rc = check_nframes(ctx, nframes)) return rc;
   if (nframes == 0) return AV1MI_OK;
   av1mi::LrLaunch L = { d_cdef, d_deblocked, d_out, stride, w, h, bd, subsampled ? 1 : 0, unit_size, nframes, d_units, unit_frame_stride, nullptr, nullptr, 0, 0, nullptr, 0, 0 };
   { ProfScope ps(ctx, AV1MI_K_LR); HIP_TRY(ctx, av1mi::launch_lr(L, ctx->stream)); }
@@ -452,10 +434,9 @@ int av1mi_lr_frames_decide(av1mi_ctx *ctx, const void *d_cdef, const void *d_deb
   BIND(ctx);
   if (!d_cdef || !d_deblocked || !d_out || !d_units || !d_orig || !d_scratch || !d_on || d_out == d_cdef || d_out == d_deblocked)
     return fail(ctx, AV1MI_E_INVAL, "null or aliased device pointer");
-  if (bd != 8 && bd != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bd);
+  if (int rc = check_bd(ctx, bd)) return rc;
   if (w <= 0 || h <= 0 || stride < w) return fail(ctx, AV1MI_E_INVAL, "bad plane geometry %dx%d stride %d", w, h, stride);
-  if (!(unit_size == 64 || unit_size == 128 || unit_size == 256 || (unit_size == 32 && subsampled)))
-    return fail(ctx, AV1MI_E_INVAL, "restoration unit size %d not allowed", unit_size);
+  if (int rc = check_lr_unit(ctx, unit_size, subsampled)) return rc;
   if (nframes < 0 || nframes > 65535 || on_stride < 1) return fail(ctx, AV1MI_E_INVAL, "nframes %d / on_stride %d out of range", nframes, on_stride);
   if (nframes == 0) return AV1MI_OK;
   const int stripes = av1mi::lr_stripes(h, subsampled ? 1 : 0);
@@ -477,11 +458,11 @@ int av1mi_lr_yuv_decide(av1mi_ctx *ctx, const av1mi_lr_decide_job *j) {
                          j->d_orig_y, j->d_orig_u, j->d_orig_v, j->d_units_y, j->d_units_uv, j->d_scratch, j->d_on };
   for (const void *p : ptrs) if (!p) return fail(ctx, AV1MI_E_INVAL, "null device pointer");
   if ((uintptr_t)j->d_scratch & 15) return fail(ctx, AV1MI_E_INVAL, "misaligned scratch");
-  if (j->bit_depth != 8 && j->bit_depth != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", j->bit_depth);
+  if (int rc = check_bd(ctx, j->bit_depth)) return rc;
   if (j->width <= 0 || j->height <= 0 || (j->width & 1) || (j->height & 1) || j->stride_y < j->width || j->stride_uv < j->width / 2)
     return fail(ctx, AV1MI_E_INVAL, "bad frame geometry %dx%d strides %d/%d", j->width, j->height, j->stride_y, j->stride_uv);
-  if (!(j->unit_size == 64 || j->unit_size == 128 || j->unit_size == 256)) return fail(ctx, AV1MI_E_INVAL, "restoration unit size %d not allowed", j->unit_size);
-  if (j->nframes < 0 || j->nframes > 65535) return fail(ctx, AV1MI_E_INVAL, "nframes %d out of range", j->nframes);
+  if (int rc = check_lr_unit(ctx, j->unit_size, 0)) return rc;
+  if (int rc = check_nframes(ctx, j->nframes)) return rc;
   if (j->nframes == 0) return AV1MI_OK;
   const int n = j->nframes, sy = av1mi::lr_stripes(j->height, 0), sc = av1mi::lr_stripes(j->height / 2, 1);
   unsigned long long *sse = (unsigned long long *)j->d_scratch;
@@ -507,10 +488,10 @@ int av1mi_lr_yuv_decide(av1mi_ctx *ctx, const av1mi_lr_decide_job *j) {
 int av1mi_extend_frames(av1mi_ctx *ctx, void *d_plane, int stride, int w, int h, int visible_w, int visible_h, int bd, int nframes) {
   BIND(ctx);
   if (!d_plane) return fail(ctx, AV1MI_E_INVAL, "null device pointer");
-  if (bd != 8 && bd != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bd);
+  if (int rc = check_bd(ctx, bd)) return rc;
   if (w <= 0 || h <= 0 || stride < w || visible_w <= 0 || visible_h <= 0 || visible_w > w || visible_h > h)
     return fail(ctx, AV1MI_E_INVAL, "bad plane geometry %dx%d (visible %dx%d) stride %d", w, h, visible_w, visible_h, stride);
-  if (nframes < 0 || nframes > 65535) return fail(ctx, AV1MI_E_INVAL, "nframes %d out of range", nframes);
+  if (int rc = check_nframes(ctx, nframes)) return rc;
   HIP_TRY(ctx, av1mi::launch_extend(d_plane, stride, w, h, visible_w, visible_h, bd, nframes, ctx->stream));
   return AV1MI_OK;
 }
@@ -536,7 +517,7 @@ int av1mi_input_convert(av1mi_ctx *ctx, int format, int bit_depth, int width, in
 int av1mi_scale_planes(av1mi_ctx *ctx, int bit_depth, int src_w, int src_h, int dst_w, int dst_h, int frames, const void *const d_src[3],
                        void *const d_dst[3]) {
   BIND(ctx);
-  if (bit_depth != 8 && bit_depth != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bit_depth);
+  if (int rc = check_bd(ctx, bit_depth)) return rc;
   if (const char *why = av1mi::scale_geometry_error(src_w, src_h, dst_w, dst_h)) return fail(ctx, AV1MI_E_INVAL, "%dx%d -> %dx%d: %s", src_w, src_h, dst_w, dst_h, why);
   if (frames < 1 || (size_t)frames * (size_t)((src_h > dst_h ? src_h : dst_h) + 7) > 65535u * 32u) return fail(ctx, AV1MI_E_INVAL, "frames %d out of range", frames);
   if (!d_src || !d_dst) return fail(ctx, AV1MI_E_INVAL, "null plane array");
@@ -558,7 +539,7 @@ int av1mi_scale_planes(av1mi_ctx *ctx, int bit_depth, int src_w, int src_h, int 
 int av1mi_intra_encode(av1mi_ctx *ctx, const av1mi_intra_job *j) {
   BIND(ctx);
   if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
-  if (j->bit_depth != 8 && j->bit_depth != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", j->bit_depth);
+  if (int rc = check_bd(ctx, j->bit_depth)) return rc;
   if (j->block_size != 8 && j->block_size != 16 && j->block_size != 32) return fail(ctx, AV1MI_E_INVAL, "block_size %d not supported (8, 16 or 32)", j->block_size);
   if (j->open_loop && j->block_size == 32) return fail(ctx, AV1MI_E_INVAL, "the open-loop mode decision exists for 8x8 and 16x16 blocks");
   if (j->width <= 0 || j->height <= 0 || j->width % j->block_size || j->height % j->block_size || j->width > 16384 || j->height > 16384)
@@ -590,7 +571,7 @@ int av1mi_intra_encode(av1mi_ctx *ctx, const av1mi_intra_job *j) {
 int av1mi_inter_encode(av1mi_ctx *ctx, const av1mi_inter_job *j) {
   BIND(ctx);
   if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
-  if (j->bit_depth != 8 && j->bit_depth != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", j->bit_depth);
+  if (int rc = check_bd(ctx, j->bit_depth)) return rc;
   if (j->width <= 0 || j->height <= 0 || (j->width & 7) || (j->height & 7) || j->width > 16384 || j->height > 16384)
     return fail(ctx, AV1MI_E_INVAL, "frame %dx%d must be a multiple of 8", j->width, j->height);
   if (j->nframes < 0 || j->nframes > 65535 || j->qindex < 0 || j->qindex > 255 || j->search_range < 0 || j->search_range > 15)
@@ -646,7 +627,7 @@ int av1mi_dequantize(av1mi_ctx *ctx, const int16_t *d_levels, int32_t *d_dqcoef,
                      int dc_q, int ac_q, int log_scale, int bd) {
   BIND(ctx);
   if (int rc = check_q(ctx, d_levels, d_dqcoef, n, coef_per_blk, dc_q, ac_q, log_scale)) return rc;
-  if (bd != 8 && bd != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bd);
+  if (int rc = check_bd(ctx, bd)) return rc;
   { ProfScope ps(ctx, AV1MI_K_DEQUANT); HIP_TRY(ctx, av1mi::launch_dequantize(d_levels, d_dqcoef, (long long)n, coef_per_blk, dc_q, ac_q, log_scale, bd, ctx->stream)); }
   return AV1MI_OK;
 }
@@ -654,7 +635,7 @@ int av1mi_dequantize(av1mi_ctx *ctx, const int16_t *d_levels, int32_t *d_dqcoef,
 int av1mi_inv_txfm2d_add(av1mi_ctx *ctx, const int32_t *coef, void *dst, int stride, int tx_size, int tx_type, int bd) {
   BIND(ctx);
   if (!coef || !dst) return fail(ctx, AV1MI_E_INVAL, "null pointer");
-  if (bd != 8 && bd != 10) return fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bd);
+  if (int rc = check_bd(ctx, bd)) return rc;
   if (!tx_valid(tx_size, tx_type)) return fail(ctx, AV1MI_E_INVAL, "tx_type %d is not defined for tx_size %d", tx_type, tx_size);
   const int w = av1mi::tx_width(tx_size), h = av1mi::tx_height(tx_size);
   if (stride < w) return fail(ctx, AV1MI_E_INVAL, "stride %d < width %d", stride, w);

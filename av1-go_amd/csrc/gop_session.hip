@@ -3,24 +3,25 @@
 // host/backend.cpp, that disagreed on the P-frame deblocking level).  What stands in for the encode the reference delegates
 // to its FFmpeg child (internal/ffmpeg/transcode.go:120,194); the caller it serves is internal/daemon/daemon.go:101.
 //
-// Streams.  The context's stream runs the kernels; the session adds an upload stream and a download stream.  Per batch:
-//   up:   wait slot.filters_done (the kernels that last read this slot's source)  -> H2D of the three source planes -> uploaded
-//   main: wait uploaded -> [k_input_convert] -> k_intra_pipe | k_me_int + k_inter_pipe -> symbols_ready -> deblock x3, CDEF, LR x3 -> reference
-//   down: wait symbols_ready -> D2H of the symbols into pinned memory -> downloaded
-//   side: (GPU entropy coding) wait symbols_ready -> k_av1_* -> payloads gathered into the slot's pinned buffer -> ent_done
+// Streams.  The context's stream runs the kernels; the session adds an upload stream and a download stream.  A batch is the stages
+// of submit_batch, in this order on every stream:
+//   feed_source       up:   wait slot.filters_done (the kernels that last read this slot's source) -> H2D of the fed buffers -> uploaded
+//                     main: wait uploaded -> [k_input_convert] -> [k_scale]
+//   code_blocks       main: k_intra_pipe | k_me_int + k_inter_pipe -> kernel_done
+//   download_symbols  down: wait kernel_done -> D2H of the symbols into pinned memory
+//   loop_filters      main: deblock x3, CDEF, LR x3 + decision -> reference -> filters_done;  down: the decision -> downloaded
+//   start_coder       side: (GPU entropy coding) wait filters_done -> k_av1_* -> payloads gathered into the slot's pinned buffer -> ent_done
 // Source and symbol buffers exist kSlots = 3 times (slot = batch % 3): batch t + 2 uploads while batch t + 1 is in the block
 // pipeline and the coder works on batch t, whose predecessor the host is still reading.  Four streams, one hardware queue each
 // (a fifth would share a queue with one of these and serialise behind it).
 //
-// Input formats (av1mi_gop_config.input_format).  PLANAR is the path above and nothing else.  Otherwise the source crosses PCIe (or
-// arrives from the caller, av1mi_gop_submit_device) in a wire / surface format and one launch of k_input_convert (input_kernels.hip)
-// on the main stream turns it into the slot's planar d_src planes, which the block pipeline reads as ever; a slot then owns pinned
-// + device WIRE buffers (h_in / d_in) instead of pinned planar planes.
-//
-// Scaling (av1mi_gop_config.source_width / source_height).  The session is fed SOURCE frames (any input format, at the source size
-// rounded up to 8) and one launch of the resampler (scale_kernels.hip) on the main stream, behind the conversion where there is one,
-// fills the slot's planar d_src planes at the coded size.  A slot then owns the source in the session's format (h_in / d_in, as above)
-// and, unless the format is planar already, device-only planar planes at the source size (d_pre) between the two launches.
+// The source path: fed buffers -> 0-2 input stages -> planar planes.  A batch is FED in the session's format
+// (av1mi_gop_config.input_format) at the fed size: the coded size, or with scaling (source_width / source_height) the source size
+// rounded up to 8.  It crosses PCIe from the slot's pinned h_in into d_in, or arrives from the caller (av1mi_gop_submit_device).
+// The input stages, fixed at open, run on the main stream: convert (format not PLANAR: one launch of k_input_convert,
+// input_kernels.hip), then scale (one launch of the resampler, scale_kernels.hip).  The last one fills the slot's planar d_src
+// planes at the coded size, which the block pipeline and the restoration decision read; with both, the converted planes at the
+// source size (d_pre) lie between them.  A planar session without scaling is the session with ZERO stages: what it is fed IS d_src.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -69,12 +70,14 @@ void frame_params(int q, int bd, int frame_type, av1mi_frame_params *p) {
 
 enum { kSlots = 3, kFallbacksToHostMode = 3 };      // batches in flight: one uploading / in the block pipeline, one in the coder, one being read by the host
 
+// plane p of the session's 4:2:0 frames: subsampling shift, coded and true (visible) size of one frame, samples and bytes of a batch
+struct Plane { int ss = 0, w = 0, h = 0, vw = 0, vh = 0; size_t n = 0, bytes = 0; };
+
 struct Slot {
-  void *h_src[3] = { nullptr, nullptr, nullptr };       // pinned (PLANAR sessions only)
-  void *d_src[3] = { nullptr, nullptr, nullptr };
-  // the source in the session's wire / surface format (other sessions): pinned + device, [2] unused by the semi-planar formats
+  // the source as fed (the session's format, at the fed size): pinned + device, [2] unused by the semi-planar formats
   void *h_in[3] = { nullptr, nullptr, nullptr }, *d_in[3] = { nullptr, nullptr, nullptr };
-  void *d_pre[3] = { nullptr, nullptr, nullptr };       // scaling sessions whose format is not planar: the converted planes at the source size
+  void *d_pre[3] = { nullptr, nullptr, nullptr };       // sessions that convert AND scale: the converted planes at the source size
+  void *d_src[3] = { nullptr, nullptr, nullptr };       // planar, coded size: what the block pipeline and the restoration decision read
   // symbols: device + pinned host mirror
   void *d_lev[3] = { nullptr, nullptr, nullptr }, *h_lev[3] = { nullptr, nullptr, nullptr };
   void *d_modes[2] = { nullptr, nullptr }, *h_modes[2] = { nullptr, nullptr };
@@ -97,12 +100,13 @@ struct Slot {
 struct av1mi_gop {
   av1mi_ctx *ctx = nullptr;
   av1mi_gop_config cfg{};
-  size_t ny = 0, nc = 0, nb = 0, bps = 1;      // per BATCH (segments stacked): luma samples, chroma samples, blocks
+  Plane plane[3];                              // the coded planes
+  size_t nb = 0, bps = 1;                      // blocks of a BATCH (segments stacked), bytes per sample
   int fmt = AV1MI_INPUT_PLANAR;                // cfg.input_format
-  size_t in_bytes[3] = {};                     // fmt != PLANAR or scaling: bytes of a batch's planes as the session is fed them
+  int stages = 0;                              // input stages: convert (fmt != PLANAR) + scale (source size given)
   av1mi::ScalePlan *scale = nullptr;           // scaling sessions: the resampler's tables
-  int sw8 = 0, sh8 = 0;                        // ... and the source size rounded up to 8 (the geometry of the fed buffers)
-  size_t pre_ny = 0, pre_nc = 0;               // ... luma / chroma samples of a batch at that size
+  size_t fed_ny = 0;                           // luma samples of a batch at the fed size
+  size_t in_bytes[3] = {}, pre_bytes[3] = {};  // bytes of a batch's planes as the session is fed them / as planar planes at the fed size
   hipStream_t up = nullptr, down = nullptr;     // with the context's main and side streams: four, one hardware queue each
   Slot slot[kSlots];
   void *d_rec[3] = {}, *d_dbl[3] = {}, *d_cdef[3] = {}, *d_ref[3] = {};
@@ -149,70 +153,41 @@ int host_alloc(av1mi_gop *g, void **p, size_t bytes) {
   return AV1MI_OK;
 }
 
-int setup(av1mi_gop *g) {
+int slot_buffers(av1mi_gop *g, Slot &s) {
   const av1mi_gop_config &c = g->cfg;
-  const int w = c.width, h = c.height, S = c.segments;
-  g->bps = c.bit_depth == 8 ? 1 : 2;
-  g->ny = (size_t)w * h * S; g->nc = g->ny / 4; g->nb = g->ny / 64;
-  g->vw = c.visible_width ? c.visible_width : w; g->vh = c.visible_height ? c.visible_height : h;
-  g->fmt = c.input_format;
-  const bool scaling = c.source_width != 0;
-  if (scaling) {
-    g->sw8 = (c.source_width + 7) & ~7; g->sh8 = (c.source_height + 7) & ~7;
-    g->pre_ny = (size_t)g->sw8 * g->sh8 * S; g->pre_nc = g->pre_ny / 4;
-  }
-  if (g->fmt != AV1MI_INPUT_PLANAR || scaling)
-    for (int p = 0; p < 3; p++) g->in_bytes[p] = av1mi_input_plane_bytes(g->fmt, c.bit_depth, p, scaling ? g->sw8 : w, (scaling ? g->sh8 : h) * S);
-  G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
-  if (scaling) G_HIP(av1mi::scale_plan_create(c.bit_depth, c.source_width, c.source_height, g->vw, g->vh, &g->scale));
-  G_HIP(hipStreamCreateWithFlags(&g->up, hipStreamNonBlocking));
-  // (created in every mode, used only where symbols go to the host at submit time or a batch falls back.  HIP deals its four
-  // default hardware queues to streams in creation order: main, up, down, side — and the coder's back stream, the fifth, shares
-  // the main stream's queue, i.e. the range coder of batch t and the block pipeline of batch t + 1 run one after the other.
-  // Measured A/B on one box: that is the FASTEST arrangement, 1 800 frames/s end to end at 4K against 1 500-1 600 with a queue
-  // per stream (without this stream, or with GPU_MAX_HW_QUEUES=8) and 1 500 with the coder on the main stream itself: the
-  // range coder is one long wave per CU, and beside it every kernel of the block pipeline runs at a fraction of its speed.)
-  G_HIP(hipStreamCreateWithFlags(&g->down, hipStreamNonBlocking));
-  for (Slot &s : g->slot) {
-    for (int p = 0; p < 3; p++) {
-      const size_t n = (p ? g->nc : g->ny);
-      if (g->fmt == AV1MI_INPUT_PLANAR && !scaling) {
-        G_TRY(host_alloc(g, &s.h_src[p], n * g->bps)); G_TRY(dev_alloc(g, &s.d_src[p], n * g->bps));
-      } else {      // the planar planes are the conversion's / the resampler's output: device only
-        G_TRY(dev_alloc(g, &s.d_src[p], n * g->bps));
-        if (g->in_bytes[p]) { G_TRY(host_alloc(g, &s.h_in[p], g->in_bytes[p])); G_TRY(dev_alloc(g, &s.d_in[p], g->in_bytes[p])); }
-        if (scaling && g->fmt != AV1MI_INPUT_PLANAR) G_TRY(dev_alloc(g, &s.d_pre[p], (p ? g->pre_nc : g->pre_ny) * g->bps));
-      }
-      // the pinned mirror of the levels (as large as the source) is needed when the symbols go to the host; with the GPU coder
-      // only a batch the coder gives back needs it, and it is allocated then (pinning memory is a good part of the start-up time)
-      if (c.gpu_entropy != 1) G_TRY(host_alloc(g, &s.h_lev[p], n * 2));
-      G_TRY(dev_alloc(g, &s.d_lev[p], n * 2));
-    }
-    for (int k = 0; k < 2; k++) { G_TRY(host_alloc(g, &s.h_modes[k], g->nb)); G_TRY(dev_alloc(g, &s.d_modes[k], g->nb)); }
-    G_TRY(host_alloc(g, &s.h_mv, g->nb * 4)); G_TRY(dev_alloc(g, &s.d_mv, g->nb * 4));
-    G_TRY(host_alloc(g, &s.h_skip, g->nb)); G_TRY(dev_alloc(g, &s.d_skip, g->nb));
-    G_HIP(hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming));
-    G_HIP(hipEventCreateWithFlags(&s.kernel_done, hipEventDisableTiming));
-    G_HIP(hipEventCreateWithFlags(&s.filters_done, hipEventDisableTiming));
-    G_TRY(dev_alloc(g, &s.d_lr_on, (size_t)S * 3 + 4)); G_TRY(host_alloc(g, &s.h_lr_on, (size_t)S * 3));      // (+ 4: the kernels read the flags as aligned dwords)
-    G_HIP(hipEventCreateWithFlags(&s.downloaded, hipEventDisableTiming));
-    if (c.gpu_entropy) {
-      g->tiles = ((w + 63) / 64) * ((h + 63) / 64);
-      g->ent_cap = (size_t)w * h * S;            // one byte per luma sample: several times what a frame codes to at any sane quantiser
-      G_TRY(host_alloc(g, &s.h_ent_out, g->ent_cap));        // pinned and device-visible: the gather kernel writes it over PCIe
-      G_TRY(dev_alloc(g, &s.d_tile_size, (size_t)g->tiles * S * 4)); G_TRY(host_alloc(g, &s.h_tile_size, (size_t)g->tiles * S * 4));
-      G_TRY(dev_alloc(g, &s.d_total, 16)); G_TRY(host_alloc(g, &s.h_total, 16));
-      G_HIP(hipEventCreateWithFlags(&s.ent_done, hipEventDisableTiming));
-    }
-  }
+  const int S = c.segments;
   for (int p = 0; p < 3; p++) {
-    const size_t n = (p ? g->nc : g->ny) * g->bps;
-    G_TRY(dev_alloc(g, &g->d_rec[p], n)); G_TRY(dev_alloc(g, &g->d_dbl[p], n)); G_TRY(dev_alloc(g, &g->d_cdef[p], n)); G_TRY(dev_alloc(g, &g->d_ref[p], n));
+    const Plane &P = g->plane[p];
+    // The source: pinned + device as fed, device-only planes behind each input stage.  With ZERO stages the fed buffer IS the planar
+    // plane (d_in == d_src, one allocation): the upload lands where the kernels read.
+    if (g->in_bytes[p]) G_TRY(host_alloc(g, &s.h_in[p], g->in_bytes[p]));
+    G_TRY(dev_alloc(g, &s.d_src[p], P.bytes));
+    if (!g->stages) s.d_in[p] = s.d_src[p];
+    else if (g->in_bytes[p]) G_TRY(dev_alloc(g, &s.d_in[p], g->in_bytes[p]));
+    if (g->stages == 2) G_TRY(dev_alloc(g, &s.d_pre[p], g->pre_bytes[p]));
+    // the pinned mirror of the levels (as large as the source) is needed when the symbols go to the host; with the GPU coder
+    // only a batch the coder gives back needs it, and it is allocated then (pinning memory is a good part of the start-up time)
+    if (c.gpu_entropy != 1) G_TRY(host_alloc(g, &s.h_lev[p], P.n * 2));
+    G_TRY(dev_alloc(g, &s.d_lev[p], P.n * 2));
   }
-  G_TRY(dev_alloc(g, &g->d_lr_scratch, av1mi_lr_yuv_decide_scratch_bytes(h, S)));
-  G_TRY(dev_alloc(g, &g->d_zero_skip, g->nb));
-  G_TRY(av1mi_memset(g->ctx, g->d_zero_skip, 0, g->nb));
-  // constant side information: one map per frame type, shared by every frame of a batch (frame stride 0)
+  for (int k = 0; k < 2; k++) { G_TRY(host_alloc(g, &s.h_modes[k], g->nb)); G_TRY(dev_alloc(g, &s.d_modes[k], g->nb)); }
+  G_TRY(host_alloc(g, &s.h_mv, g->nb * 4)); G_TRY(dev_alloc(g, &s.d_mv, g->nb * 4));
+  G_TRY(host_alloc(g, &s.h_skip, g->nb)); G_TRY(dev_alloc(g, &s.d_skip, g->nb));
+  for (hipEvent_t *e : { &s.uploaded, &s.kernel_done, &s.filters_done, &s.downloaded }) G_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  G_TRY(dev_alloc(g, &s.d_lr_on, (size_t)S * 3 + 4)); G_TRY(host_alloc(g, &s.h_lr_on, (size_t)S * 3));      // (+ 4: the kernels read the flags as aligned dwords)
+  if (c.gpu_entropy) {
+    G_TRY(host_alloc(g, &s.h_ent_out, g->ent_cap));        // pinned and device-visible: the gather kernel writes it over PCIe
+    G_TRY(dev_alloc(g, &s.d_tile_size, (size_t)g->tiles * S * 4)); G_TRY(host_alloc(g, &s.h_tile_size, (size_t)g->tiles * S * 4));
+    G_TRY(dev_alloc(g, &s.d_total, 16)); G_TRY(host_alloc(g, &s.h_total, 16));
+    G_HIP(hipEventCreateWithFlags(&s.ent_done, hipEventDisableTiming));
+  }
+  return AV1MI_OK;
+}
+
+// constant side information: one map per frame type, shared by every frame of a batch (frame stride 0)
+int side_information(av1mi_gop *g) {
+  const av1mi_gop_config &c = g->cfg;
+  const int w = c.width, h = c.height;
   const size_t fy = (size_t)w * h, fc = fy / 4;
   const int nsb = ((w + 63) / 64) * ((h + 63) / 64);
   auto units = [](int n) { const int u = (n + 32) / 64; return u > 1 ? u : 1; };
@@ -254,8 +229,87 @@ int setup(av1mi_gop *g) {
     for (size_t i = 0; i < uc; i++) memcpy(&lr[i * 8], P.lr_unit_uv, 8);
     G_TRY(dev_alloc(g, &g->d_lr[1], uc * 8)); G_TRY(av1mi_upload(g->ctx, g->d_lr[1], lr.data(), uc * 8));
   }
-  G_TRY(av1mi_sync(g->ctx));
   return AV1MI_OK;
+}
+
+// av1mi_gop_open's argument rules: null = fine, else the reason (written into buf)
+const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
+#define WHY(...) (snprintf(buf, sizeof(buf), __VA_ARGS__), buf)
+  if (!c) return WHY("null config");
+  if (c->width <= 0 || c->height <= 0 || (c->width & 7) || (c->height & 7) || c->width > 16384 || c->height > 16384)
+    return WHY("frame %dx%d must be a multiple of 8", c->width, c->height);
+  if (c->visible_width < 0 || c->visible_height < 0 || (c->visible_width && (c->visible_width > c->width || c->width - c->visible_width >= 8)) ||
+      (c->visible_height && (c->visible_height > c->height || c->height - c->visible_height >= 8)))
+    return WHY("visible size %dx%d must lie within 7 samples below the coded size %dx%d", c->visible_width, c->visible_height, c->width, c->height);
+  if (c->bit_depth != 8 && c->bit_depth != 10) return WHY("bit depth %d not supported (8 or 10)", c->bit_depth);
+  if (c->base_q_idx < 1 || c->base_q_idx > 255 || c->gop_length < 1 || c->segments < 1 || c->segments > 4096 || c->search_range < 0 ||
+      c->search_range > 15 || c->gpu_entropy < 0 || c->gpu_entropy > 2 || c->coder_streams < 0 || c->coder_streams > 3)
+    return WHY("bad base_q_idx / gop_length / segments / search_range / gpu_entropy");
+  if (c->input_format < AV1MI_INPUT_PLANAR || c->input_format > AV1MI_INPUT_NV12)
+    return WHY("input_format %d unknown (0 planar, 1 packed 10-bit, 2 P010, 3 NV12)", c->input_format);
+  if ((c->input_format == AV1MI_INPUT_PACKED10 || c->input_format == AV1MI_INPUT_P010) && c->bit_depth != 10)
+    return WHY("input_format %d (%s) needs bit_depth 10, not %d", c->input_format, c->input_format == AV1MI_INPUT_P010 ? "P010" : "packed 10-bit", c->bit_depth);
+  if (c->input_format == AV1MI_INPUT_NV12 && c->bit_depth != 8) return WHY("input_format 3 (NV12) needs bit_depth 8, not %d", c->bit_depth);
+  if ((c->source_width != 0) != (c->source_height != 0) || c->source_width < 0 || c->source_height < 0)
+    return WHY("source size %dx%d: give both source_width and source_height, or neither", c->source_width, c->source_height);
+  if (c->source_width) {
+    const int tw = c->visible_width ? c->visible_width : c->width, th = c->visible_height ? c->visible_height : c->height;
+    if (const char *why = av1mi::scale_geometry_error(c->source_width, c->source_height, tw, th))
+      return WHY("source size %dx%d -> %dx%d: %s", c->source_width, c->source_height, tw, th, why);
+  }
+  if (c->key_block_size != 0 && c->key_block_size != 8 && c->key_block_size != 32) return WHY("key_block_size %d not supported (8 or 32)", c->key_block_size);
+  if (c->key_block_size == 32 && (c->width & 31))
+    return WHY("key_block_size 32 needs a width that is a multiple of 32");
+  if (c->gpu_entropy && (c->width > 4096 || c->height > 4096)) return WHY("the AV1 tile coder takes frames up to 4096x4096");
+  if ((size_t)c->height * c->segments > 65535u * 8u) return WHY("segments x height too large for one launch");
+  return nullptr;
+#undef WHY
+}
+
+int setup(av1mi_gop *g) {
+  const av1mi_gop_config &c = g->cfg;
+  const int w = c.width, h = c.height, S = c.segments;
+  g->bps = c.bit_depth == 8 ? 1 : 2;
+  g->vw = c.visible_width ? c.visible_width : w; g->vh = c.visible_height ? c.visible_height : h;
+  for (int p = 0; p < 3; p++) {
+    Plane &P = g->plane[p];
+    P.ss = p > 0;
+    P.w = w >> P.ss; P.h = h >> P.ss; P.vw = (g->vw + P.ss) >> P.ss; P.vh = (g->vh + P.ss) >> P.ss;
+    P.n = (size_t)P.w * P.h * S; P.bytes = P.n * g->bps;
+  }
+  g->nb = g->plane[0].n / 64;
+  g->fmt = c.input_format;
+  const bool scaling = c.source_width != 0;
+  g->stages = (g->fmt != AV1MI_INPUT_PLANAR) + scaling;
+  // the fed size: the coded size, or the source size rounded up to 8
+  const int fed_w = scaling ? (c.source_width + 7) & ~7 : w, fed_rows = (scaling ? (c.source_height + 7) & ~7 : h) * S;
+  g->fed_ny = (size_t)fed_w * fed_rows;
+  for (int p = 0; p < 3; p++) {
+    g->in_bytes[p] = av1mi_input_plane_bytes(g->fmt, c.bit_depth, p, fed_w, fed_rows);
+    g->pre_bytes[p] = av1mi_input_plane_bytes(AV1MI_INPUT_PLANAR, c.bit_depth, p, fed_w, fed_rows);
+  }
+  if (c.gpu_entropy) {
+    g->tiles = ((w + 63) / 64) * ((h + 63) / 64);
+    g->ent_cap = (size_t)w * h * S;            // one byte per luma sample: several times what a frame codes to at any sane quantiser
+  }
+  G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
+  if (c.source_width) G_HIP(av1mi::scale_plan_create(c.bit_depth, c.source_width, c.source_height, g->vw, g->vh, &g->scale));
+  G_HIP(hipStreamCreateWithFlags(&g->up, hipStreamNonBlocking));
+  // (created in every mode, used only where symbols go to the host at submit time or a batch falls back.  HIP deals its four
+  // default hardware queues to streams in creation order: main, up, down, side — and the coder's back stream, the fifth, shares
+  // the main stream's queue, i.e. the range coder of batch t and the block pipeline of batch t + 1 run one after the other.
+  // Measured A/B on one box: that is the FASTEST arrangement, 1 800 frames/s end to end at 4K against 1 500-1 600 with a queue
+  // per stream (without this stream, or with GPU_MAX_HW_QUEUES=8) and 1 500 with the coder on the main stream itself: the
+  // range coder is one long wave per CU, and beside it every kernel of the block pipeline runs at a fraction of its speed.)
+  G_HIP(hipStreamCreateWithFlags(&g->down, hipStreamNonBlocking));
+  for (Slot &s : g->slot) G_TRY(slot_buffers(g, s));
+  for (int p = 0; p < 3; p++)      // reconstruction, deblocked, CDEF and reference planes: single (the chain is serial in t)
+    for (void **d : { &g->d_rec[p], &g->d_dbl[p], &g->d_cdef[p], &g->d_ref[p] }) G_TRY(dev_alloc(g, d, g->plane[p].bytes));
+  G_TRY(dev_alloc(g, &g->d_lr_scratch, av1mi_lr_yuv_decide_scratch_bytes(h, S)));
+  G_TRY(dev_alloc(g, &g->d_zero_skip, g->nb));
+  G_TRY(av1mi_memset(g->ctx, g->d_zero_skip, 0, g->nb));
+  G_TRY(side_information(g));
+  return av1mi_sync(g->ctx);
 }
 
 }  // namespace
@@ -271,35 +325,8 @@ int av1mi_policy_frame_params(int base_q_idx, int bit_depth, int frame_type, av1
 int av1mi_gop_open(av1mi_ctx *ctx, const av1mi_gop_config *cfg, av1mi_gop **out) {
   if (!ctx || !out) return AV1MI_E_INVAL;
   *out = nullptr;
-  if (!cfg) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "null config");
-  if (cfg->width <= 0 || cfg->height <= 0 || (cfg->width & 7) || (cfg->height & 7) || cfg->width > 16384 || cfg->height > 16384)
-    return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "frame %dx%d must be a multiple of 8", cfg->width, cfg->height);
-  if (cfg->visible_width < 0 || cfg->visible_height < 0 || (cfg->visible_width && (cfg->visible_width > cfg->width || cfg->width - cfg->visible_width >= 8)) ||
-      (cfg->visible_height && (cfg->visible_height > cfg->height || cfg->height - cfg->visible_height >= 8)))
-    return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "visible size %dx%d must lie within 7 samples below the coded size %dx%d", cfg->visible_width, cfg->visible_height,
-                           cfg->width, cfg->height);
-  if (cfg->bit_depth != 8 && cfg->bit_depth != 10) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", cfg->bit_depth);
-  if (cfg->base_q_idx < 1 || cfg->base_q_idx > 255 || cfg->gop_length < 1 || cfg->segments < 1 || cfg->segments > 4096 || cfg->search_range < 0 ||
-      cfg->search_range > 15 || cfg->gpu_entropy < 0 || cfg->gpu_entropy > 2 || cfg->coder_streams < 0 || cfg->coder_streams > 3)
-    return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "bad base_q_idx / gop_length / segments / search_range / gpu_entropy");
-  if (cfg->input_format < AV1MI_INPUT_PLANAR || cfg->input_format > AV1MI_INPUT_NV12)
-    return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "input_format %d unknown (0 planar, 1 packed 10-bit, 2 P010, 3 NV12)", cfg->input_format);
-  if ((cfg->input_format == AV1MI_INPUT_PACKED10 || cfg->input_format == AV1MI_INPUT_P010) && cfg->bit_depth != 10)
-    return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "input_format %d (%s) needs bit_depth 10, not %d", cfg->input_format, cfg->input_format == AV1MI_INPUT_P010 ? "P010" : "packed 10-bit",
-                           cfg->bit_depth);
-  if (cfg->input_format == AV1MI_INPUT_NV12 && cfg->bit_depth != 8) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "input_format 3 (NV12) needs bit_depth 8, not %d", cfg->bit_depth);
-  if ((cfg->source_width != 0) != (cfg->source_height != 0) || cfg->source_width < 0 || cfg->source_height < 0)
-    return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "source size %dx%d: give both source_width and source_height, or neither", cfg->source_width, cfg->source_height);
-  if (cfg->source_width) {
-    const int tw = cfg->visible_width ? cfg->visible_width : cfg->width, th = cfg->visible_height ? cfg->visible_height : cfg->height;
-    if (const char *why = av1mi::scale_geometry_error(cfg->source_width, cfg->source_height, tw, th))
-      return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "source size %dx%d -> %dx%d: %s", cfg->source_width, cfg->source_height, tw, th, why);
-  }
-  if (cfg->key_block_size != 0 && cfg->key_block_size != 8 && cfg->key_block_size != 32) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "key_block_size %d not supported (8 or 32)", cfg->key_block_size);
-  if (cfg->key_block_size == 32 && (cfg->width & 31))
-    return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "key_block_size 32 needs a width that is a multiple of 32");
-  if (cfg->gpu_entropy && (cfg->width > 4096 || cfg->height > 4096)) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "the AV1 tile coder takes frames up to 4096x4096");
-  if ((size_t)cfg->height * cfg->segments > 65535u * 8u) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "segments x height too large for one launch");
+  char why[512];
+  if (config_error(cfg, why)) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "%s", why);
   av1mi_gop *g = new (std::nothrow) av1mi_gop();
   if (!g) return AV1MI_E_NOMEM;
   g->ctx = ctx; g->cfg = *cfg;
@@ -318,13 +345,9 @@ void av1mi_gop_close(av1mi_gop *g) {
   (void)av1mi_sync(g->ctx);
   if (g->up) { (void)hipStreamSynchronize(g->up); (void)hipStreamDestroy(g->up); }
   if (g->down) { (void)hipStreamSynchronize(g->down); (void)hipStreamDestroy(g->down); }
-  for (Slot &s : g->slot) {
-    if (s.uploaded) (void)hipEventDestroy(s.uploaded);
-    if (s.kernel_done) (void)hipEventDestroy(s.kernel_done);
-    if (s.filters_done) (void)hipEventDestroy(s.filters_done);
-    if (s.downloaded) (void)hipEventDestroy(s.downloaded);
-    if (s.ent_done) (void)hipEventDestroy(s.ent_done);
-  }
+  for (Slot &s : g->slot)
+    for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done })
+      if (e) (void)hipEventDestroy(e);
   for (void *p : g->dev_allocs) (void)hipFree(p);
   for (void *p : g->host_allocs) (void)hipHostFree(p);
   av1mi::scale_plan_destroy(g->scale);
@@ -335,31 +358,161 @@ int av1mi_gop_max_in_flight(void) { return kSlots; }
 
 }  // extern "C"
 
-// modes (key frames) or vectors + skip flags (inter frames) of a slot -> its pinned host buffers
-static int download_modes(av1mi_gop *g, Slot &s, hipStream_t st) {
-  if (s.frame_type == 0) {
-    for (int k = 0; k < 2; k++) G_HIP(hipMemcpyAsync(s.h_modes[k], s.d_modes[k], g->nb, hipMemcpyDeviceToHost, st));
-  } else {
-    G_HIP(hipMemcpyAsync(s.h_mv, s.d_mv, g->nb * 4, hipMemcpyDeviceToHost, st));
-    G_HIP(hipMemcpyAsync(s.h_skip, s.d_skip, g->nb, hipMemcpyDeviceToHost, st));
+// ---- a batch: the stages of submit_batch, each named for what it enqueues ---------------------------------------------------------
+
+// The source as fed -> src: the three planar planes at the coded size that the rest of the batch reads.  dev_src: the fed planes in
+// device memory (av1mi_gop_submit_device), or null = upload the slot's pinned buffers first.  Two hazards:
+//  - d_src (and d_pre, the planes between conversion and scaling) is read by the slot's previous batch up to its restoration
+//    decision.  That ran on the main stream too, so the launches here are ordered behind it by the stream itself; no event.
+//  - d_in, the device buffer of the source as fed (with zero stages: d_src itself), is read by the input stages / the kernels of the
+//    slot's previous batch.  The upload into it waits for that batch's filters_done, which was recorded on the main stream AFTER those
+//    launches (the restoration decision is the last reader).
+// `uploaded` keeps its two meanings: the main stream waits for it before the first launch, and av1mi_gop_acquire_input waits for
+// it before the host may overwrite the pinned buffers.
+static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const void *src[3]) {
+  hipStream_t main = av1mi::ctx_stream(g->ctx);
+  for (int p = 0; p < 3; p++) src[p] = dev_src ? dev_src[p] : s.d_in[p];
+  if (!dev_src) {
+    if (s.kernel_pending) G_HIP(hipStreamWaitEvent(g->up, s.filters_done, 0));
+    for (int p = 0; p < 3; p++)
+      if (g->in_bytes[p]) G_HIP(hipMemcpyAsync(s.d_in[p], s.h_in[p], g->in_bytes[p], hipMemcpyHostToDevice, g->up));
+    G_HIP(hipEventRecord(s.uploaded, g->up));
+    s.upload_pending = true;
+    G_HIP(hipStreamWaitEvent(main, s.uploaded, 0));
+  }
+  if (g->fmt != AV1MI_INPUT_PLANAR) {      // stage: convert, at the fed size
+    av1mi::InputLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int p = 0; p < 3; p++) { L.in[p] = src[p]; L.out[p] = g->scale ? s.d_pre[p] : s.d_src[p]; }
+    L.ny = g->fed_ny; L.nc = g->fed_ny / 4;
+    av1mi::ProfScope ps(g->ctx, AV1MI_K_INPUT, main);
+    G_HIP(av1mi::launch_input_convert(g->fmt, L, main));
+    for (int p = 0; p < 3; p++) src[p] = L.out[p];
+  }
+  if (g->scale) {                          // stage: scale, fed size -> coded size
+    av1mi::ProfScope ps(g->ctx, AV1MI_K_INPUT, main);
+    G_HIP(av1mi::launch_scale(g->scale, g->cfg.segments, src, s.d_src, main));
+    for (int p = 0; p < 3; p++) src[p] = s.d_src[p];
   }
   return AV1MI_OK;
 }
 
-extern "C" {
+// the block pipeline: key (8x8 blocks | two bands, 32x32 + 8x8) or inter; then kernel_done.  (The symbols of this slot were downloaded
+// before the slot was collected, so they may be overwritten.)
+static int code_blocks(av1mi_gop *g, Slot &s, int frame_type, const void *const src[3]) {
+  const av1mi_gop_config &c = g->cfg;
+  const int w = c.width, h = c.height;
+  if (frame_type == 0) {
+    av1mi_intra_job j;
+    memset(&j, 0, sizeof(j));
+    j.width = w; j.height = h; j.bit_depth = c.bit_depth; j.nframes = c.segments; j.qindex = c.base_q_idx; j.block_size = 8; j.stride_y = g->plane[0].w; j.stride_uv = g->plane[1].w;
+    j.d_src_y = src[0]; j.d_src_u = src[1]; j.d_src_v = src[2];
+    j.d_rec_y = g->d_rec[0]; j.d_rec_u = g->d_rec[1]; j.d_rec_v = g->d_rec[2];
+    j.d_lev_y = (int16_t *)s.d_lev[0]; j.d_lev_u = (int16_t *)s.d_lev[1]; j.d_lev_v = (int16_t *)s.d_lev[2];
+    j.d_modes_y = (uint8_t *)s.d_modes[0]; j.d_modes_uv = (uint8_t *)s.d_modes[1];
+    j.open_loop = g->intra_open_loop;
+    if (!g->key32) {
+      G_TRY(av1mi_intra_encode(g->ctx, &j));
+    } else {
+      // two bands of every frame: the complete superblock rows in 32x32 blocks, a last partial row (if any) in 8x8 blocks.  Tiles are
+      // single superblocks, so the bands share nothing.
+      const int hA = g->key_rows32, hB = h - hA;
+      j.open_loop = 0; j.frame_rows = h; j.modes_frame_stride = g->key_modes_stride;
+      if (hA) { j.height = hA; j.block_size = 32; G_TRY(av1mi_intra_encode(g->ctx, &j)); }
+      if (hB) {
+        size_t o[3];      // samples of a plane above the second band
+        for (int p = 0; p < 3; p++) o[p] = (size_t)(hA >> g->plane[p].ss) * g->plane[p].w;
+        j.height = hB; j.block_size = 8;
+        j.d_src_y = (const char *)src[0] + o[0] * g->bps; j.d_src_u = (const char *)src[1] + o[1] * g->bps; j.d_src_v = (const char *)src[2] + o[2] * g->bps;
+        j.d_rec_y = (char *)g->d_rec[0] + o[0] * g->bps; j.d_rec_u = (char *)g->d_rec[1] + o[1] * g->bps; j.d_rec_v = (char *)g->d_rec[2] + o[2] * g->bps;
+        j.d_lev_y = (int16_t *)s.d_lev[0] + o[0]; j.d_lev_u = (int16_t *)s.d_lev[1] + o[1]; j.d_lev_v = (int16_t *)s.d_lev[2] + o[2];
+        j.d_modes_y = (uint8_t *)s.d_modes[0] + g->key_modes_band; j.d_modes_uv = (uint8_t *)s.d_modes[1] + g->key_modes_band;
+        G_TRY(av1mi_intra_encode(g->ctx, &j));
+      }
+    }
+  } else {
+    av1mi_inter_job j;
+    memset(&j, 0, sizeof(j));
+    j.width = w; j.height = h; j.bit_depth = c.bit_depth; j.nframes = c.segments; j.qindex = c.base_q_idx; j.search_range = c.search_range; j.stride_y = g->plane[0].w; j.stride_uv = g->plane[1].w;
+    j.d_src_y = src[0]; j.d_src_u = src[1]; j.d_src_v = src[2];
+    j.d_ref_y = g->d_ref[0]; j.d_ref_u = g->d_ref[1]; j.d_ref_v = g->d_ref[2];
+    j.d_rec_y = g->d_rec[0]; j.d_rec_u = g->d_rec[1]; j.d_rec_v = g->d_rec[2];
+    j.d_lev_y = (int16_t *)s.d_lev[0]; j.d_lev_u = (int16_t *)s.d_lev[1]; j.d_lev_v = (int16_t *)s.d_lev[2];
+    j.d_mvs = (int16_t *)s.d_mv; j.d_skip = (uint8_t *)s.d_skip;
+    // per segment and plane: the restored plane of the previous frame, or its CDEF output where restoration was switched off
+    j.d_ref_alt_y = g->d_cdef[0]; j.d_ref_alt_u = g->d_cdef[1]; j.d_ref_alt_v = g->d_cdef[2];
+    j.d_ref_sel = (const uint8_t *)g->slot[g->last].d_lr_on;
+    G_TRY(av1mi_inter_encode(g->ctx, &j));
+  }
+  G_HIP(hipEventRecord(s.kernel_done, av1mi::ctx_stream(g->ctx)));
+  s.kernel_pending = true;
+  s.frame_type = frame_type;
+  return AV1MI_OK;
+}
 
-int av1mi_gop_pending(av1mi_gop *g) { return g ? (int)(g->submitted - g->collected) : 0; }
-long av1mi_gop_entropy_fallbacks(av1mi_gop *g) { return g ? g->fallbacks : 0; }
+// the symbols of a slot -> its pinned host mirrors, on the download stream: the levels, then the modes (key frames) or the vectors +
+// skip flags (inter frames)
+static int download_symbols(av1mi_gop *g, Slot &s) {
+  for (int p = 0; p < 3; p++) G_HIP(hipMemcpyAsync(s.h_lev[p], s.d_lev[p], g->plane[p].n * 2, hipMemcpyDeviceToHost, g->down));
+  if (s.frame_type == 0) {
+    for (int k = 0; k < 2; k++) G_HIP(hipMemcpyAsync(s.h_modes[k], s.d_modes[k], g->nb, hipMemcpyDeviceToHost, g->down));
+  } else {
+    G_HIP(hipMemcpyAsync(s.h_mv, s.d_mv, g->nb * 4, hipMemcpyDeviceToHost, g->down));
+    G_HIP(hipMemcpyAsync(s.h_skip, s.d_skip, g->nb, hipMemcpyDeviceToHost, g->down));
+  }
+  return AV1MI_OK;
+}
 
-int av1mi_gop_acquire_input(av1mi_gop *g, void **y, void **u, void **v) {
-  if (!g || !y || !u || !v) return AV1MI_E_INVAL;
-  if (g->submitted - g->collected >= kSlots) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "%d batches in flight: collect before acquiring the next input", (int)kSlots);
-  G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
-  Slot &s = g->slot[g->submitted % kSlots];
-  if (s.upload_pending) { G_HIP(hipEventSynchronize(s.uploaded)); s.upload_pending = false; }   // the copy engine still reads these buffers
-  if (g->fmt == AV1MI_INPUT_PLANAR && !g->scale) { *y = s.h_src[0]; *u = s.h_src[1]; *v = s.h_src[2]; }
-  else { *y = s.h_in[0]; *u = s.h_in[1]; *v = s.h_in[2]; }      // in the session's format; no third plane in the semi-planar ones
-  g->acquired = true;
+static int extend_plane(av1mi_gop *g, const Plane &P, void *d) {
+  return av1mi_extend_frames(g->ctx, d, P.w, P.w, P.h, P.vw, P.vh, g->cfg.bit_depth, g->cfg.segments);
+}
+
+// in-loop filters: reconstruction -> what the next frame predicts from; then filters_done and (symbols_down) the decision -> downloaded
+static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
+  const av1mi_gop_config &c = g->cfg;
+  const int w = c.width, h = c.height, S = c.segments, bd = c.bit_depth, key = s.frame_type == 0;
+  const av1mi_frame_params &P = g->params[s.frame_type];
+  for (int p = 0; p < 3; p++) {
+    const Plane &L = g->plane[p];
+    G_TRY(av1mi_deblock_frames(g->ctx, g->d_rec[p], L.w, g->d_dbl[p], L.w, L.w, L.h, bd, L.ss, (const uint32_t *)g->d_mi[key && g->key32 ? 2 : s.frame_type][L.ss], L.w / 4, 0,
+                               P.lf_sharpness, S));
+  }
+  av1mi_cdef_job cj;
+  memset(&cj, 0, sizeof(cj));
+  cj.width = w; cj.height = h; cj.bit_depth = bd; cj.nframes = S; cj.damping = P.cdef_damping; cj.stride_y = g->plane[0].w; cj.stride_uv = g->plane[1].w;
+  cj.d_src_y = g->d_dbl[0]; cj.d_src_u = g->d_dbl[1]; cj.d_src_v = g->d_dbl[2];
+  cj.d_dst_y = g->d_cdef[0]; cj.d_dst_u = g->d_cdef[1]; cj.d_dst_v = g->d_cdef[2];
+  cj.d_sb_strength = (const uint8_t *)g->d_cdef_sb[s.frame_type]; cj.sb_frame_stride = 0;
+  // key frames are coded with skip = 0 everywhere (no block is exempt from CDEF); P frames: the kernel's skip flags, per frame
+  // (the slot's next inter kernel is kSlots batches away and ordered behind this CDEF on the main stream, nothing else writes them)
+  cj.d_skip8 = (const uint8_t *)(key ? g->d_zero_skip : s.d_skip); cj.skip_frame_stride = key ? 0 : (size_t)(w / 8) * (h / 8);
+  G_TRY(av1mi_cdef_frames(g->ctx, &cj));
+  // a true size that is not a multiple of 8: the decoder's restoration clamps at the true last column / row (CDEF above read the
+  // planes as they were: it works on the coded size in a decoder too)
+  const bool padded = g->vw != w || g->vh != h;
+  if (padded)
+    for (int p = 0; p < 3; p++) { G_TRY(extend_plane(g, g->plane[p], g->d_dbl[p])); G_TRY(extend_plane(g, g->plane[p], g->d_cdef[p])); }
+  // loop restoration of every frame, and the decision per segment and plane whether it stays ON (it must lower the squared error
+  // against the source): d_ref always receives the restored planes, the next batch's kernels choose between d_ref and d_cdef
+  av1mi_lr_decide_job lj;
+  memset(&lj, 0, sizeof(lj));
+  lj.width = w; lj.height = h; lj.bit_depth = bd; lj.nframes = S; lj.unit_size = P.lr_unit_size; lj.stride_y = g->plane[0].w; lj.stride_uv = g->plane[1].w;
+  lj.d_cdef_y = g->d_cdef[0]; lj.d_cdef_u = g->d_cdef[1]; lj.d_cdef_v = g->d_cdef[2];
+  lj.d_dbl_y = g->d_dbl[0]; lj.d_dbl_u = g->d_dbl[1]; lj.d_dbl_v = g->d_dbl[2];
+  lj.d_out_y = g->d_ref[0]; lj.d_out_u = g->d_ref[1]; lj.d_out_v = g->d_ref[2];
+  lj.d_orig_y = src[0]; lj.d_orig_u = src[1]; lj.d_orig_v = src[2];
+  lj.d_units_y = (const int8_t *)g->d_lr[0]; lj.d_units_uv = (const int8_t *)g->d_lr[1];
+  lj.d_scratch = g->d_lr_scratch; lj.d_on = (uint8_t *)s.d_lr_on;
+  lj.no_self_guided_units = P.lr_unit_y[0] != 2 && P.lr_unit_uv[0] != 2;
+  G_TRY(av1mi_lr_yuv_decide(g->ctx, &lj));
+  if (padded)      // ... and so do its motion-compensation reads of this frame
+    for (int p = 0; p < 3; p++) G_TRY(extend_plane(g, g->plane[p], g->d_ref[p]));
+  G_HIP(hipEventRecord(s.filters_done, av1mi::ctx_stream(g->ctx)));
+  if (s.symbols_down) {
+    G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
+    G_HIP(hipMemcpyAsync(s.h_lr_on, s.d_lr_on, (size_t)S * 3, hipMemcpyDeviceToHost, g->down));
+    G_HIP(hipEventRecord(s.downloaded, g->down));
+  }
   return AV1MI_OK;
 }
 
@@ -379,207 +532,85 @@ static int finish_entropy(av1mi_gop *g, Slot &s, hipStream_t st) {
   return entropy_results(g, s, st);
 }
 
-// one batch through the block pipeline, the filters and (gpu_entropy) the tile coder; dev_src: the source planes in device memory
-// (av1mi_gop_submit_device), or null = upload the slot's pinned planes first
+// the AV1 tile entropy coder beside the next batch's block pipeline: tokenizer + chains on the context's side stream (after
+// the filters: the restoration units a tile codes depend on the decision), the serial range coder on its back stream (so the
+// next batch's tokenizer does not wait for it)
+static int start_coder(av1mi_gop *g, Slot &s) {
+  const av1mi_gop_config &c = g->cfg;
+  const av1mi_frame_params &P = g->params[s.frame_type];
+  hipStream_t main = av1mi::ctx_stream(g->ctx), side = av1mi::ctx_side_stream(g->ctx), back = av1mi::ctx_back_stream(g->ctx);
+  if (!side || !back) return av1mi::ctx_fail(g->ctx, AV1MI_E_DEVICE, "no side stream");
+  if (g->coder_streams == 1) back = side;                 // diagnostic arrangements (AV1MI_CODER_STREAMS): the whole coder on the side stream
+  else if (g->coder_streams == 2) side = back = main;     // ... or on the main stream, serialised behind the filters
+  if (side != main) G_HIP(hipStreamWaitEvent(side, s.filters_done, 0));
+  av1mi_av1_entropy_job ej;
+  memset(&ej, 0, sizeof(ej));
+  ej.width = c.width; ej.height = c.height; ej.nframes = c.segments; ej.key = s.frame_type == 0; ej.base_q_idx = c.base_q_idx;
+  ej.d_lev_y = (const int16_t *)s.d_lev[0]; ej.d_lev_u = (const int16_t *)s.d_lev[1]; ej.d_lev_v = (const int16_t *)s.d_lev[2];
+  ej.d_modes_y = (const uint8_t *)s.d_modes[0]; ej.d_modes_uv = (const uint8_t *)s.d_modes[1];
+  ej.d_mvs = (const int16_t *)s.d_mv; ej.d_skip = (const uint8_t *)s.d_skip;
+  ej.lr_on[0] = P.lr_unit_y[0] == 1; ej.lr_on[1] = ej.lr_on[2] = P.lr_unit_uv[0] == 1;
+  ej.d_lr_on = (const uint8_t *)s.d_lr_on;
+  ej.visible_width = g->vw; ej.visible_height = g->vh;
+  ej.key_rows32 = s.frame_type == 0 && g->key32 ? g->key_rows32 : 0;
+  memcpy(ej.lr_unit_y, P.lr_unit_y, 8); memcpy(ej.lr_unit_uv, P.lr_unit_uv, 8);
+  ej.d_out = (uint8_t *)s.h_ent_out; ej.out_cap = g->ent_cap; ej.d_tile_size = (uint32_t *)s.d_tile_size; ej.d_total = (uint64_t *)s.d_total;
+  if (g->coder_streams == 3) {
+    // tokenizer + chains of THIS batch on the side stream; the range coder of the PREVIOUS batch on the main stream, behind this
+    // batch's filters: two queues that are both busy all the time ((pipeline + filters + coder) beside (tokenizer + chains)) instead of
+    // a short one and a long one
+    G_TRY(av1mi::av1_entropy_front(g->ctx, &ej, side, &s.ent_ticket));
+    Slot &prev = g->slot[(g->submitted + kSlots - 1) % kSlots];
+    if (g->submitted > 0 && prev.ent_ticket >= 0) G_TRY(finish_entropy(g, prev, main));
+  } else {
+    G_TRY(av1mi::av1_entropy_submit(g->ctx, &ej, side, back));
+    G_TRY(entropy_results(g, s, back));
+  }
+  s.ent_pending = true;
+  return AV1MI_OK;
+}
+
+// one batch through the stages above; dev_src as for feed_source
 static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src) {
   if (g->submitted - g->collected >= kSlots) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "%d batches in flight: collect first", (int)kSlots);
   if (frame_type < -1 || frame_type > 1) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "frame_type %d", frame_type);
   if (frame_type < 0) frame_type = g->gop_pos == 0 ? 0 : 1;
   if (frame_type == 1 && g->submitted == 0) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "the first frame of a session must be a key frame");
   G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
-  const av1mi_gop_config &c = g->cfg;
-  const int w = c.width, h = c.height, S = c.segments, bd = c.bit_depth;
   Slot &s = g->slot[g->submitted % kSlots];
-  hipStream_t main = av1mi::ctx_stream(g->ctx);
-  const void *src[3] = { s.d_src[0], s.d_src[1], s.d_src[2] };
-  if (g->fmt != AV1MI_INPUT_PLANAR || g->scale) {
-    // The source arrives in a wire / surface format and / or at another size, and is converted / scaled into the slot's planar d_src on
-    // the MAIN stream.  Two hazards:
-    //  - d_src (and d_pre, the planes between conversion and scaling) is read by the slot's previous batch up to its restoration
-    //    decision.  That ran on the main stream too, so the launches here are ordered behind it by the stream itself; no event.
-    //  - d_in, the device buffer of the source as fed, is read by the conversion / scaling of the slot's previous batch.  The upload
-    //    into it waits for that batch's filters_done, which was recorded on the main stream AFTER those launches.
-    // `uploaded` keeps its two meanings: the main stream waits for it before the first launch, and av1mi_gop_acquire_input waits for
-    // it before the host may overwrite the pinned buffers.
-    const void *in[3];
-    if (dev_src) {
-      for (int p = 0; p < 3; p++) in[p] = dev_src[p];
-    } else {
-      if (s.kernel_pending) G_HIP(hipStreamWaitEvent(g->up, s.filters_done, 0));
-      for (int p = 0; p < 3; p++)
-        if (g->in_bytes[p]) G_HIP(hipMemcpyAsync(s.d_in[p], s.h_in[p], g->in_bytes[p], hipMemcpyHostToDevice, g->up));
-      G_HIP(hipEventRecord(s.uploaded, g->up));
-      s.upload_pending = true;
-      G_HIP(hipStreamWaitEvent(main, s.uploaded, 0));
-      for (int p = 0; p < 3; p++) in[p] = s.d_in[p];
-    }
-    if (g->fmt != AV1MI_INPUT_PLANAR) {
-      av1mi::InputLaunch L;
-      memset(&L, 0, sizeof(L));
-      for (int p = 0; p < 3; p++) { L.in[p] = in[p]; L.out[p] = g->scale ? s.d_pre[p] : s.d_src[p]; }
-      L.ny = g->scale ? g->pre_ny : g->ny; L.nc = g->scale ? g->pre_nc : g->nc;
-      const av1mi::ProfToken pt = av1mi::ctx_prof_begin(g->ctx, AV1MI_K_INPUT, main);
-      G_HIP(av1mi::launch_input_convert(g->fmt, L, main));
-      av1mi::ctx_prof_end(g->ctx, pt, main);
-      for (int p = 0; p < 3; p++) in[p] = s.d_pre[p];
-    }
-    if (g->scale) {
-      const av1mi::ProfToken pt = av1mi::ctx_prof_begin(g->ctx, AV1MI_K_INPUT, main);
-      G_HIP(av1mi::launch_scale(g->scale, S, in, s.d_src, main));
-      av1mi::ctx_prof_end(g->ctx, pt, main);
-    }
-  } else if (dev_src) {
-    for (int p = 0; p < 3; p++) src[p] = dev_src[p];
-  } else {
-    // upload: not before the kernels that last read this slot's source have finished (the restoration decision is the last reader)
-    if (s.kernel_pending) G_HIP(hipStreamWaitEvent(g->up, s.filters_done, 0));
-    for (int p = 0; p < 3; p++) G_HIP(hipMemcpyAsync(s.d_src[p], s.h_src[p], (p ? g->nc : g->ny) * g->bps, hipMemcpyHostToDevice, g->up));
-    G_HIP(hipEventRecord(s.uploaded, g->up));
-    s.upload_pending = true;
-    G_HIP(hipStreamWaitEvent(main, s.uploaded, 0));
-  }
-  if (s.ent_pending) G_HIP(hipStreamWaitEvent(main, s.ent_done, 0));      // the GPU coder of the slot's previous batch still reads its symbols
-  // the block pipeline (the symbols of this slot were downloaded before the slot was collected, so they may be overwritten)
-  if (frame_type == 0) {
-    av1mi_intra_job j;
-    memset(&j, 0, sizeof(j));
-    j.width = w; j.height = h; j.bit_depth = bd; j.nframes = S; j.qindex = c.base_q_idx; j.block_size = 8; j.stride_y = w; j.stride_uv = w / 2;
-    j.d_src_y = src[0]; j.d_src_u = src[1]; j.d_src_v = src[2];
-    j.d_rec_y = g->d_rec[0]; j.d_rec_u = g->d_rec[1]; j.d_rec_v = g->d_rec[2];
-    j.d_lev_y = (int16_t *)s.d_lev[0]; j.d_lev_u = (int16_t *)s.d_lev[1]; j.d_lev_v = (int16_t *)s.d_lev[2];
-    j.d_modes_y = (uint8_t *)s.d_modes[0]; j.d_modes_uv = (uint8_t *)s.d_modes[1];
-    j.open_loop = g->intra_open_loop;
-    if (!g->key32) {
-      G_TRY(av1mi_intra_encode(g->ctx, &j));
-    } else {
-      // two bands of every frame: the complete superblock rows in 32x32 blocks, a last partial row (if any) in 8x8 blocks.  Tiles are
-      // single superblocks, so the bands share nothing.
-      const int hA = g->key_rows32, hB = h - hA;
-      j.open_loop = 0; j.frame_rows = h; j.modes_frame_stride = g->key_modes_stride;
-      if (hA) { j.height = hA; j.block_size = 32; G_TRY(av1mi_intra_encode(g->ctx, &j)); }
-      if (hB) {
-        const size_t oy = (size_t)hA * w, oc = (size_t)(hA / 2) * (w / 2);
-        j.height = hB; j.block_size = 8;
-        j.d_src_y = (const char *)src[0] + oy * g->bps; j.d_src_u = (const char *)src[1] + oc * g->bps; j.d_src_v = (const char *)src[2] + oc * g->bps;
-        j.d_rec_y = (char *)g->d_rec[0] + oy * g->bps; j.d_rec_u = (char *)g->d_rec[1] + oc * g->bps; j.d_rec_v = (char *)g->d_rec[2] + oc * g->bps;
-        j.d_lev_y = (int16_t *)s.d_lev[0] + oy; j.d_lev_u = (int16_t *)s.d_lev[1] + oc; j.d_lev_v = (int16_t *)s.d_lev[2] + oc;
-        j.d_modes_y = (uint8_t *)s.d_modes[0] + g->key_modes_band; j.d_modes_uv = (uint8_t *)s.d_modes[1] + g->key_modes_band;
-        G_TRY(av1mi_intra_encode(g->ctx, &j));
-      }
-    }
-  } else {
-    av1mi_inter_job j;
-    memset(&j, 0, sizeof(j));
-    j.width = w; j.height = h; j.bit_depth = bd; j.nframes = S; j.qindex = c.base_q_idx; j.search_range = c.search_range; j.stride_y = w; j.stride_uv = w / 2;
-    j.d_src_y = src[0]; j.d_src_u = src[1]; j.d_src_v = src[2];
-    j.d_ref_y = g->d_ref[0]; j.d_ref_u = g->d_ref[1]; j.d_ref_v = g->d_ref[2];
-    j.d_rec_y = g->d_rec[0]; j.d_rec_u = g->d_rec[1]; j.d_rec_v = g->d_rec[2];
-    j.d_lev_y = (int16_t *)s.d_lev[0]; j.d_lev_u = (int16_t *)s.d_lev[1]; j.d_lev_v = (int16_t *)s.d_lev[2];
-    j.d_mvs = (int16_t *)s.d_mv; j.d_skip = (uint8_t *)s.d_skip;
-    // per segment and plane: the restored plane of the previous frame, or its CDEF output where restoration was switched off
-    j.d_ref_alt_y = g->d_cdef[0]; j.d_ref_alt_u = g->d_cdef[1]; j.d_ref_alt_v = g->d_cdef[2];
-    j.d_ref_sel = (const uint8_t *)g->slot[g->last].d_lr_on;
-    G_TRY(av1mi_inter_encode(g->ctx, &j));
-  }
-  G_HIP(hipEventRecord(s.kernel_done, main));
-  s.kernel_pending = true;
-  s.frame_type = frame_type;
+  const void *src[3];
+  G_TRY(feed_source(g, s, dev_src, src));
+  if (s.ent_pending) G_HIP(hipStreamWaitEvent(av1mi::ctx_stream(g->ctx), s.ent_done, 0));      // the GPU coder of the slot's previous batch still reads its symbols
+  G_TRY(code_blocks(g, s, frame_type, src));
   // symbols -> pinned host memory, beside the filters.  Not when the GPU codes the tiles (gpu_entropy == 1): the host then needs
   // the payloads only (and a fifth busy stream would share a hardware queue with one of the other four)
-  s.symbols_down = c.gpu_entropy != 1 || g->symbols_always;
+  s.symbols_down = g->cfg.gpu_entropy != 1 || g->symbols_always;
   if (s.symbols_down) {
     G_HIP(hipStreamWaitEvent(g->down, s.kernel_done, 0));
-    for (int p = 0; p < 3; p++) G_HIP(hipMemcpyAsync(s.h_lev[p], s.d_lev[p], (p ? g->nc : g->ny) * 2, hipMemcpyDeviceToHost, g->down));
-    G_TRY(download_modes(g, s, g->down));
+    G_TRY(download_symbols(g, s));
   }
-  // in-loop filters: reconstruction -> what the next frame predicts from
-  const av1mi_frame_params &P = g->params[frame_type];
-  for (int p = 0; p < 3; p++) {
-    const int pw = p ? w / 2 : w, ph = p ? h / 2 : h;
-    G_TRY(av1mi_deblock_frames(g->ctx, g->d_rec[p], pw, g->d_dbl[p], pw, pw, ph, bd, p > 0, (const uint32_t *)g->d_mi[frame_type == 0 && g->key32 ? 2 : frame_type][p > 0], pw / 4, 0,
-                               P.lf_sharpness, S));
-  }
-  av1mi_cdef_job cj;
-  memset(&cj, 0, sizeof(cj));
-  cj.width = w; cj.height = h; cj.bit_depth = bd; cj.nframes = S; cj.damping = P.cdef_damping; cj.stride_y = w; cj.stride_uv = w / 2;
-  cj.d_src_y = g->d_dbl[0]; cj.d_src_u = g->d_dbl[1]; cj.d_src_v = g->d_dbl[2];
-  cj.d_dst_y = g->d_cdef[0]; cj.d_dst_u = g->d_cdef[1]; cj.d_dst_v = g->d_cdef[2];
-  cj.d_sb_strength = (const uint8_t *)g->d_cdef_sb[frame_type]; cj.sb_frame_stride = 0;
-  // key frames are coded with skip = 0 everywhere (no block is exempt from CDEF); P frames: the kernel's skip flags, per frame
-  // (the slot's next inter kernel is kSlots batches away and ordered behind this CDEF on the main stream, nothing else writes them)
-  cj.d_skip8 = (const uint8_t *)(frame_type == 0 ? g->d_zero_skip : s.d_skip); cj.skip_frame_stride = frame_type == 0 ? 0 : (size_t)(w / 8) * (h / 8);
-  G_TRY(av1mi_cdef_frames(g->ctx, &cj));
-  // a true size that is not a multiple of 8: the decoder's restoration clamps at the true last column / row (CDEF above read the
-  // planes as they were: it works on the coded size in a decoder too)
-  const bool padded = g->vw != w || g->vh != h;
-  if (padded)
-    for (int p = 0; p < 3; p++) {
-      const int pw = p ? w / 2 : w, ph = p ? h / 2 : h, pvw = p ? (g->vw + 1) / 2 : g->vw, pvh = p ? (g->vh + 1) / 2 : g->vh;
-      G_TRY(av1mi_extend_frames(g->ctx, g->d_dbl[p], pw, pw, ph, pvw, pvh, bd, S));
-      G_TRY(av1mi_extend_frames(g->ctx, g->d_cdef[p], pw, pw, ph, pvw, pvh, bd, S));
-    }
-  // loop restoration of every frame, and the decision per segment and plane whether it stays ON (it must lower the squared error
-  // against the source): d_ref always receives the restored planes, the next batch's kernels choose between d_ref and d_cdef
-  {
-    av1mi_lr_decide_job lj;
-    memset(&lj, 0, sizeof(lj));
-    lj.width = w; lj.height = h; lj.bit_depth = bd; lj.nframes = S; lj.unit_size = P.lr_unit_size; lj.stride_y = w; lj.stride_uv = w / 2;
-    lj.d_cdef_y = g->d_cdef[0]; lj.d_cdef_u = g->d_cdef[1]; lj.d_cdef_v = g->d_cdef[2];
-    lj.d_dbl_y = g->d_dbl[0]; lj.d_dbl_u = g->d_dbl[1]; lj.d_dbl_v = g->d_dbl[2];
-    lj.d_out_y = g->d_ref[0]; lj.d_out_u = g->d_ref[1]; lj.d_out_v = g->d_ref[2];
-    lj.d_orig_y = src[0]; lj.d_orig_u = src[1]; lj.d_orig_v = src[2];
-    lj.d_units_y = (const int8_t *)g->d_lr[0]; lj.d_units_uv = (const int8_t *)g->d_lr[1];
-    lj.d_scratch = g->d_lr_scratch; lj.d_on = (uint8_t *)s.d_lr_on;
-    lj.no_self_guided_units = P.lr_unit_y[0] != 2 && P.lr_unit_uv[0] != 2;
-    G_TRY(av1mi_lr_yuv_decide(g->ctx, &lj));
-  }
-  if (padded)      // ... and so do its motion-compensation reads of this frame
-    for (int p = 0; p < 3; p++)
-      G_TRY(av1mi_extend_frames(g->ctx, g->d_ref[p], p ? w / 2 : w, p ? w / 2 : w, p ? h / 2 : h, p ? (g->vw + 1) / 2 : g->vw, p ? (g->vh + 1) / 2 : g->vh, bd, S));
-  G_HIP(hipEventRecord(s.filters_done, main));
-  if (s.symbols_down) {
-    G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
-    G_HIP(hipMemcpyAsync(s.h_lr_on, s.d_lr_on, (size_t)S * 3, hipMemcpyDeviceToHost, g->down));
-    G_HIP(hipEventRecord(s.downloaded, g->down));
-  }
-  if (c.gpu_entropy) {
-    // the AV1 tile entropy coder beside the next batch's block pipeline: tokenizer + chains on the context's side stream (after
-    // the filters: the restoration units a tile codes depend on the decision), the serial range coder on its back stream (so the
-    // next batch's tokenizer does not wait for it)
-    hipStream_t side = av1mi::ctx_side_stream(g->ctx), back = av1mi::ctx_back_stream(g->ctx);
-    if (!side || !back) return av1mi::ctx_fail(g->ctx, AV1MI_E_DEVICE, "no side stream");
-    if (g->coder_streams == 1) back = side;                 // diagnostic arrangements (AV1MI_CODER_STREAMS): the whole coder on the side stream
-    else if (g->coder_streams == 2) side = back = main;     // ... or on the main stream, serialised behind the filters
-    if (side != main) G_HIP(hipStreamWaitEvent(side, s.filters_done, 0));
-    av1mi_av1_entropy_job ej;
-    memset(&ej, 0, sizeof(ej));
-    ej.width = w; ej.height = h; ej.nframes = S; ej.key = frame_type == 0; ej.base_q_idx = c.base_q_idx;
-    ej.d_lev_y = (const int16_t *)s.d_lev[0]; ej.d_lev_u = (const int16_t *)s.d_lev[1]; ej.d_lev_v = (const int16_t *)s.d_lev[2];
-    ej.d_modes_y = (const uint8_t *)s.d_modes[0]; ej.d_modes_uv = (const uint8_t *)s.d_modes[1];
-    ej.d_mvs = (const int16_t *)s.d_mv; ej.d_skip = (const uint8_t *)s.d_skip;
-    ej.lr_on[0] = P.lr_unit_y[0] == 1; ej.lr_on[1] = ej.lr_on[2] = P.lr_unit_uv[0] == 1;
-    ej.d_lr_on = (const uint8_t *)s.d_lr_on;
-    ej.visible_width = g->vw; ej.visible_height = g->vh;
-    ej.key_rows32 = frame_type == 0 && g->key32 ? g->key_rows32 : 0;
-    memcpy(ej.lr_unit_y, P.lr_unit_y, 8); memcpy(ej.lr_unit_uv, P.lr_unit_uv, 8);
-    ej.d_out = (uint8_t *)s.h_ent_out; ej.out_cap = g->ent_cap; ej.d_tile_size = (uint32_t *)s.d_tile_size; ej.d_total = (uint64_t *)s.d_total;
-    if (g->coder_streams == 3) {
-      // tokenizer + chains of THIS batch on the side stream; the range coder of the PREVIOUS batch on the main stream, behind this
-      // batch's filters: two queues that are both busy all the time ((pipeline + filters + coder) beside (tokenizer + chains)) instead of
-      // a short one and a long one
-      G_TRY(av1mi::av1_entropy_front(g->ctx, &ej, side, &s.ent_ticket));
-      Slot &prev = g->slot[(g->submitted + kSlots - 1) % kSlots];
-      if (g->submitted > 0 && prev.ent_ticket >= 0) G_TRY(finish_entropy(g, prev, main));
-    } else {
-      G_TRY(av1mi::av1_entropy_submit(g->ctx, &ej, side, back));
-      G_TRY(entropy_results(g, s, back));
-    }
-    s.ent_pending = true;
-  }
+  G_TRY(loop_filters(g, s, src));
+  if (g->cfg.gpu_entropy) G_TRY(start_coder(g, s));
   g->last = (int)(g->submitted % kSlots);
   g->submitted++;
-  g->gop_pos = frame_type == 0 ? 1 % c.gop_length : (g->gop_pos + 1) % c.gop_length;
+  g->gop_pos = frame_type == 0 ? 1 % g->cfg.gop_length : (g->gop_pos + 1) % g->cfg.gop_length;
   g->acquired = false;
+  return AV1MI_OK;
+}
+
+extern "C" {
+
+int av1mi_gop_pending(av1mi_gop *g) { return g ? (int)(g->submitted - g->collected) : 0; }
+long av1mi_gop_entropy_fallbacks(av1mi_gop *g) { return g ? g->fallbacks : 0; }
+
+int av1mi_gop_acquire_input(av1mi_gop *g, void **y, void **u, void **v) {
+  if (!g || !y || !u || !v) return AV1MI_E_INVAL;
+  if (g->submitted - g->collected >= kSlots) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "%d batches in flight: collect before acquiring the next input", (int)kSlots);
+  G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
+  Slot &s = g->slot[g->submitted % kSlots];
+  if (s.upload_pending) { G_HIP(hipEventSynchronize(s.uploaded)); s.upload_pending = false; }   // the copy engine still reads these buffers
+  *y = s.h_in[0]; *u = s.h_in[1]; *v = s.h_in[2];      // in the session's format; no third plane in the semi-planar ones
+  g->acquired = true;
   return AV1MI_OK;
 }
 
@@ -635,9 +666,8 @@ int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out) {
         // stalls the device), not one slot at a time in the middle of later batches
         for (Slot &o : g->slot)
           for (int p = 0; p < 3; p++)
-            if (!o.h_lev[p]) G_TRY(host_alloc(g, &o.h_lev[p], (p ? g->nc : g->ny) * 2));
-        for (int p = 0; p < 3; p++) G_HIP(hipMemcpyAsync(s.h_lev[p], s.d_lev[p], (p ? g->nc : g->ny) * 2, hipMemcpyDeviceToHost, g->down));
-        G_TRY(download_modes(g, s, g->down));
+            if (!o.h_lev[p]) G_TRY(host_alloc(g, &o.h_lev[p], g->plane[p].n * 2));
+        G_TRY(download_symbols(g, s));
         G_HIP(hipStreamSynchronize(g->down));
         symbols(true);
       }
@@ -662,7 +692,7 @@ int av1mi_gop_download_reference(av1mi_gop *g, void *y, void *u, void *v) {
   if (g->submitted) G_TRY(av1mi_download(g->ctx, on.data(), g->slot[g->last].d_lr_on, on.size()));
   void *dst[3] = { y, u, v };
   for (int p = 0; p < 3; p++) {
-    const size_t per = (p ? g->nc : g->ny) * g->bps / (size_t)S;
+    const size_t per = g->plane[p].bytes / (size_t)S;
     for (int sg = 0; sg < S; sg++)
       G_TRY(av1mi_download(g->ctx, (char *)dst[p] + per * sg, (const char *)(on[(size_t)sg * 3 + p] ? g->d_ref[p] : g->d_cdef[p]) + per * sg, per));
   }

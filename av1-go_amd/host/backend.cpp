@@ -181,7 +181,8 @@ int RunBackend(const BackendJob &job, std::string *err) {
     // -av1mi_pack10 1: a 10-bit source crosses PCIe at 10 bits per sample; the session's pinned buffers are then three packed planes
     const bool packed = job.pack10 && y.bd == 10;
     if (packed) cfg.input_format = AV1MI_INPUT_PACKED10;
-    const size_t py_bytes = packed ? fy / 2 * 5 / 4 : fy, pc_bytes = py_bytes / 4;      // one segment's planes in the pinned buffers
+    // one segment's planes in the pinned buffers
+    const size_t py_bytes = av1mi_input_plane_bytes(cfg.input_format, y.bd, 0, rw, rh), pc_bytes = av1mi_input_plane_bytes(cfg.input_format, y.bd, 1, rw, rh);
     std::vector<std::vector<unsigned char>> scratch(packed ? (size_t)S : 0);          // per reader thread: one planar frame to pack from
     CHK(av1mi_gop_open(ctx, &cfg, &gop));
     av1::SequenceParams sp; sp.width = tw; sp.height = th; sp.bit_depth = y.bd;
