@@ -31,7 +31,7 @@ struct Av1EntLaunch {
   op_t *ops; uint32_t ops_cap;  // per tile: the list (literal ops, tuples)
   uint32_t *grouped; uint32_t grouped_cap;   // per tile: the entries of the adaptive symbols, grouped by slot
   uint16_t *slot_total, *slot_base;          // per tile x S_MAX: entries of the slot, position of its first entry
-  uint16_t *rec;                             // per tile x 64 blocks x kBlockRecords: the tokenizer's records
+  uint16_t *rec;                             // per tile of 8x8 blocks x 64 blocks x kBlockRecords: the tokenizer's records
   uint32_t *nops;               // per tile
   uint8_t *slots; uint32_t slot_cap;   // per tile payload slot
   uint32_t *tile_size;          // per tile: payload bytes (0 = overflow)
@@ -47,10 +47,12 @@ struct Av1EntLaunch {
   int sb_rows32, band, nslots;
 };
 
-__device__ __forceinline__ FrameView frame_view(const Av1EntLaunch &L, int f) {
+// frame f of the launch; kKey: 1 / 0 = the launch is known to hold key / inter frames (the choice at run time between the two sets of
+// pointers put them into scratch memory)
+template <int kKey = -1> __device__ __forceinline__ FrameView frame_view(const Av1EntLaunch &L, int f) {
   FrameView v = L.fv;
   const long nb = (long)v.w8 * v.h8;
-  if (v.key) { v.y_mode += nb * f; v.uv_mode += nb * f; }
+  if (kKey < 0 ? v.key != 0 : kKey != 0) { v.y_mode += nb * f; v.uv_mode += nb * f; }
   else { v.mv += nb * 2 * f; v.skip += nb * f; }
   v.lev_y += nb * 64 * f; v.lev_u += nb * 16 * f; v.lev_v += nb * 16 * f;
   v.info = L.info + nb * f;
@@ -97,7 +99,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void
     if (zi == 0) fill_scan_tables(&S.scan);
   }
   __syncthreads();
-  uint16_t *rec = L.rec + ((size_t)t * kBlocksPerTile + zi) * kBlockRecords;
+  const int below = tiles - L.sb_rows32 * L.sbc_n;      // the records are this band's alone: the frame's tiles below the 32x32 band
+  uint16_t *rec = L.rec + (((size_t)f * below + (tt - (tiles - below))) * kBlocksPerTile + zi) * kBlockRecords;
   const TokScratch ts = { S.p1.mag + zi * kMagBytes, &S.scan };
   Sink k = { rec, S.p1.cnt, zi, 0, 0, false };
   tok_block(v, k, ts, sbr, sbc, zi);
@@ -179,64 +182,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void
   }
 }
 
-// The tiles of a key frame's 32x32 band: ONE LANE PER 32x32 BLOCK (16 tiles per workgroup) tokenizes serially (av1_ops32.hpp
-// tok_block32: 1024 + 2 x 256 coefficients), the four lanes of a tile then place the slots and replay their records into the list
-// and the grouped entries — after which the chains, the range coder and the gather treat the tile like any other.  In LDS: per tile
-// the 16-bit counts / positions of its 180 slots x 4 blocks and the blocks' level summaries, per lane the magnitude map of the
-// transform block at hand.  Key frames are one frame of a GOP; see DESIGN 7-1 for a finer-grained form.
-constexpr int kTiles32 = 16;      // per workgroup
-static_assert(kBlocks32 * kMag32Bytes >= K_END * kBlocks32 * 2 && kMag32Bytes % 8 == 0, "a tile's counters live where its four magnitude maps were");
-__global__ __launch_bounds__(64) void k_av1_tokens32(Av1EntLaunch L, int ntiles_all) {
-  __shared__ ScanTables32 scan;
-  __shared__ __attribute__((aligned(16))) uint8_t s_mag[64 * kMag32Bytes];      // 47 KB: three workgroups per CU
-  __shared__ Sum32 s_sum[kTiles32][kBlocks32];
-  __shared__ int s_n[kTiles32][kBlocks32], s_nrec[kTiles32][kBlocks32], s_bad[kTiles32];
-  const int tiles = L.sbr_n * L.sbc_n, tl = threadIdx.x >> 2, b = threadIdx.x & 3, t = blockIdx.x * kTiles32 + tl;
-  bool live = t < ntiles_all;
-  int f = 0, sbr = 0, sbc = 0;
-  if (live) { f = t / tiles; const int tt = t - f * tiles; sbr = tt / L.sbc_n; sbc = tt - sbr * L.sbc_n; live = sbr < L.sb_rows32; }
-  fill_scan_tables32(&scan, (int)threadIdx.x, 64);
-  if (b == 0) s_bad[tl] = 0;
-  const FrameView v = frame_view(L, live ? f : 0);
-  const bool inside = live && !((b & 1) && sbc * 8 + 4 >= v.w8);      // width % 64 == 32: a last column of half superblocks
-  if (inside) block_sums32(v, block_index32(v, sbr, sbc, b), &s_sum[tl][b]);
-  __syncthreads();
-  uint16_t *rec = L.rec + ((size_t)(live ? t : 0) * kBlocks32 + b) * kBlockRecords32;
-  int nrec = 0;
-  if (live) { s_n[tl][b] = 0; s_nrec[tl][b] = 0; }
-  if (inside) {
-    Sink32 k = { rec, nullptr, b, (int)kBlockRecords32, 0, 0, false, 0, 0, 0, 0 };
-    const TokScratch32 ts = { s_mag + threadIdx.x * kMag32Bytes, &scan };
-    tok_block32(v, k, ts, sbr, sbc, b, s_sum[tl]);
-    s_n[tl][b] = k.n; s_nrec[tl][b] = nrec = k.nrec;
-    if (k.overflow) atomicOr(&s_bad[tl], 1);
-  }
-  __syncthreads();
-  // the magnitude maps are dead: the tile's 180 x 4 counters take their place
-  uint16_t *cnt = reinterpret_cast<uint16_t *>(s_mag + tl * kBlocks32 * kMag32Bytes);
-  for (int i = b; i < K_END * kBlocks32; i += kBlocks32) cnt[i] = 0;
-  __syncthreads();
-  if (live && !count_block32(rec, nrec, cnt, b)) atomicOr(&s_bad[tl], 1);
-  __syncthreads();
-  if (live && b == 0) {       // place: the tile's first lane (180 slots x 4 blocks: nothing beside the tokenizing)
-    uint16_t *total = L.slot_total + (size_t)t * S_MAX, *base = L.slot_base + (size_t)t * S_MAX;
-    const int run = place_tile32(cnt, total, base);
-    for (int sl = K_END; sl < S_MAX; sl++) { total[sl] = 0; base[sl] = 0; }
-    const int n = s_n[tl][0] + s_n[tl][1] + s_n[tl][2] + s_n[tl][3];
-    if (s_bad[tl] || (uint32_t)n > L.ops_cap || run > 65535) {
-      s_bad[tl] = 1;
-      atomicOr(L.status, 1u);
-      L.nops[t] = 0;
-      for (int sl = 0; sl < K_END; sl++) total[sl] = 0;
-    } else {
-      L.nops[t] = (uint32_t)n;
+// The tiles of a key frame's 32x32 band: ONE WAVE PER TILE, the lanes over scan ranges of the transform block at hand (av1_ops32.hpp
+// tok_tile32: the levels are read once into magnitude maps in LDS, a counting sweep gives the slots' totals and bases, an emitting
+// sweep writes list words and grouped entries straight to their places) — after which the chains, the range coder and the gather treat
+// the tile like any other.  No records in memory (L.rec is the 8x8 band's).  15.7 KB of LDS per wave: ten waves per CU.
+struct Wave32 {
+  template <class T> using Var = LaneVar<T, 1>;
+  template <class F> __device__ __forceinline__ void each(F f) { f((int)threadIdx.x); __syncthreads(); }
+  __device__ __forceinline__ int scan(Var<int> &v) {
+    const int lane = (int)threadIdx.x, x = v.v[0];
+    int inc = x;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int y = __shfl_up(inc, d, 64);
+      if (lane >= d) inc += y;
     }
+    v.v[0] = inc - x;
+    return __shfl(inc, 63, 64);
   }
-  __syncthreads();
-  if (!live || s_bad[tl]) return;
-  int first = 0;
-  for (int q = 0; q < b; q++) first += s_n[tl][q];
-  replay_block<kBlocks32>(rec, nrec, cnt, b, first, L.ops + (size_t)t * L.ops_cap, L.grouped + (size_t)t * L.grouped_cap);
+  __device__ __forceinline__ int first(Var<int> &v) { return __shfl(v.v[0], 0, 64); }
+};
+__global__ __launch_bounds__(64) void k_av1_tokens32(Av1EntLaunch L) {
+  __shared__ Tile32Mem S;
+  const int tiles = L.sbr_n * L.sbc_n, band = L.sb_rows32 * L.sbc_n, f = blockIdx.x / band, tt = blockIdx.x - f * band, sbr = tt / L.sbc_n, sbc = tt - sbr * L.sbc_n;
+  const size_t t = (size_t)f * tiles + tt;          // (the band's tiles are a frame's first)
+  const FrameView v = frame_view<1>(L, f);
+  Wave32 w;
+  const int n = tok_tile32(w, S, v, sbr, sbc, L.ops + t * L.ops_cap, L.ops_cap, L.grouped + t * L.grouped_cap, L.slot_total + t * S_MAX, L.slot_base + t * S_MAX);
+  if (threadIdx.x == 0) {
+    if (n < 0) atomicOr(L.status, 1u);
+    L.nops[t] = n < 0 ? 0u : (uint32_t)n;
+  }
 }
 
 // CHAINS: workgroup = one CDF slot of 64 consecutive tiles, one lane per tile.  The slot is the same for the whole wave (no
@@ -422,7 +398,7 @@ hipError_t launch_av1_front(av1mi_ctx *ctx, const Av1EntLaunch &L, hipStream_t s
   ProfToken t = ctx_prof_begin(ctx, AV1MI_K_ENTROPY_TOKENS, s);
   hipLaunchKernelGGL(k_av1_info, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, L);
   if (L.sb_rows32 < L.sbr_n) hipLaunchKernelGGL(k_av1_tokens, dim3((unsigned)ntiles_all), dim3(64), 0, s, L);
-  if (L.sb_rows32) hipLaunchKernelGGL(k_av1_tokens32, dim3((unsigned)((ntiles_all + kTiles32 - 1) / kTiles32)), dim3(64), 0, s, L, ntiles_all);
+  if (L.sb_rows32) hipLaunchKernelGGL(k_av1_tokens32, dim3((unsigned)(L.sb_rows32 * L.sbc_n * L.nframes)), dim3(64), 0, s, L);
   ctx_prof_end(ctx, t, s);
   t = ctx_prof_begin(ctx, AV1MI_K_ENTROPY_CHAINS, s);
   Av1EntLaunch C = L;
@@ -546,7 +522,7 @@ int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hip
       (rc = grow(ctx, &st->ops[par], &st->ops_b[par], nt * L.ops_cap * sizeof(av1ops::op_t))) || (rc = grow(ctx, &st->nops[par], &st->nops_b[par], nt * 4)) ||
       (rc = grow(ctx, &st->grouped, &st->grouped_b, nt * L.grouped_cap * sizeof(uint32_t))) ||
       (rc = grow(ctx, &st->slot_tb, &st->slot_tb_b, nt * av1ops::S_MAX * 4)) ||
-      (rc = grow(ctx, &st->rec, &st->rec_b, nt * av1ops::kBlocksPerTile * av1ops::kBlockRecords * sizeof(uint16_t))) ||
+      (rc = grow(ctx, &st->rec, &st->rec_b, (size_t)(L.sbr_n - L.sb_rows32) * L.sbc_n * j->nframes * av1ops::kBlocksPerTile * av1ops::kBlockRecords * sizeof(uint16_t))) ||
       (rc = grow(ctx, &st->slots, &st->slots_b, nt * L.slot_cap)) || (rc = grow(ctx, &st->tile_off, &st->off_b, (nt + 1) * 8)))
     return rc;
   L.info = (av1ops::BlockInfo *)st->info; L.ops = (av1ops::op_t *)st->ops[par]; L.nops = (uint32_t *)st->nops[par]; L.grouped = (uint32_t *)st->grouped;

@@ -31,6 +31,7 @@
 namespace av1ops {
 
 // uint16 / byte storage that is also read and written as 32- and 64-bit words
+typedef uint16_t __attribute__((may_alias)) u16a;
 typedef uint32_t __attribute__((may_alias)) u32a;
 typedef uint64_t __attribute__((may_alias)) u64a;
 
@@ -453,15 +454,13 @@ template <int N> struct MagMap<N, true> {
   AV1_HD int neg(int p) const { return mag[(p >> LG) * MS + (p & (N - 1))] >> 7; }
 };
 
-// coeffs() (5.11.39) of one N x N transform block (N = 4, 8, 16, 32): `lev` = its levels, row-major (16-byte aligned); the slots of
-// band B; above / left: the neighbours' level summaries (cul = min(63, sum |level|), dc = 0 none / 1 negative / 2 positive);
-// (tx_slot, tx_sym): the luma transform type, coded right after all_zero (tx_slot < 0: implied, not coded)
-template <int N, const BandSlots &B, class K, class TS>
-AV1_HD void tok_coeffs(K &k, const TS &ts, bool chroma, const int16_t *lev, int above_cul, int above_dc, int left_cul, int left_dc, int tx_slot,
-                       int tx_sym) {
-  MagMap<N> M(ts);
-  const int nc = N * N, LG = M.LG, MS = M.MS;
-  const int eob = M.load(lev);
+// coeffs() (5.11.39) of one N x N transform block (N = 4, 8, 16, 32) in three parts, each a function of the magnitude map alone, so
+// that any range of scan positions can be tokenized on its own (the 32x32 band does: av1_ops32.hpp): the LEADING symbols (all_zero,
+// the transform type, eob_pt and its extra bits), PASS 1 over scan positions c_hi ... c_lo (descending; base levels and ranges), PASS 2
+// over c_lo ... c_hi - 1 (ascending; signs and Golomb bits).  Every context reads the level at the position and its five lower-right
+// neighbours, nothing of the coder's state.
+template <int N, const BandSlots &B, class K>
+AV1_HD void tok_coeffs_lead(K &k, bool chroma, int eob, int above_cul, int above_dc, int left_cul, int left_dc, int tx_slot, int tx_sym) {
   k.sym(chroma ? B.txb_skip_c + ((above_cul | above_dc) != 0) + ((left_cul | left_dc) != 0) : B.txb_skip_y, eob == 0);
   if (!eob) return;
   if (tx_slot >= 0) k.sym(tx_slot, tx_sym);
@@ -472,8 +471,12 @@ AV1_HD void tok_coeffs(K &k, const TS &ts, bool chroma, const int16_t *lev, int 
     k.sym((chroma ? B.eobx_c : B.eobx_y) + eob_pt - 3, (off >> shift) & 1);
     if (shift > 0) k.lit((unsigned)(off & ((1 << shift) - 1)), shift);
   }
+}
+template <int N, const BandSlots &B, class K, class M_>
+AV1_HD void tok_coeffs_pass1(K &k, const M_ &M, bool chroma, const int16_t *lev, int eob, int c_hi, int c_lo) {
+  const int nc = N * N, LG = M.LG, MS = M.MS;
   const int base_eob = chroma ? B.base_eob_c : B.base_eob_y, base = chroma ? B.base_c : B.base_y, br = chroma ? B.br_c : B.br_y;
-  for (int c = eob - 1; c >= 0; c--) {
+  for (int c = c_hi; c >= c_lo; c--) {
     const int pos = M.pos(c), row = pos >> LG, col = pos & (N - 1), at = row * MS + col;
     const int m0 = M.at(at), m1 = M.at(at + 1), m2 = M.at(at + 2), mb = M.at(at + MS), md = M.at(at + MS + 1), mbb = M.at(at + 2 * MS);
     int a = m0;
@@ -500,7 +503,11 @@ AV1_HD void tok_coeffs(K &k, const TS &ts, bool chroma, const int16_t *lev, int 
       }
     }
   }
-  for (int c = 0; c < eob; c++) {
+}
+template <int N, const BandSlots &B, class K, class M_>
+AV1_HD void tok_coeffs_pass2(K &k, const M_ &M, bool chroma, const int16_t *lev, int above_dc, int left_dc, int c_lo, int c_hi) {
+  const int LG = M.LG, MS = M.MS;
+  for (int c = c_lo; c < c_hi; c++) {
     const int pos = M.pos(c), m = M.at((pos >> LG) * MS + (pos & (N - 1)));
     if (!m) continue;
     const int neg = M.neg(pos);
@@ -520,6 +527,19 @@ AV1_HD void tok_coeffs(K &k, const TS &ts, bool chroma, const int16_t *lev, int 
       }
     }
   }
+}
+// the whole of coeffs(), one thread per transform block: `lev` = its levels, row-major (16-byte aligned); the slots of band B; above /
+// left: the neighbours' level summaries (cul = min(63, sum |level|), dc = 0 none / 1 negative / 2 positive); (tx_slot, tx_sym): the luma
+// transform type, coded right after all_zero (tx_slot < 0: implied, not coded)
+template <int N, const BandSlots &B, class K, class TS>
+AV1_HD void tok_coeffs(K &k, const TS &ts, bool chroma, const int16_t *lev, int above_cul, int above_dc, int left_cul, int left_dc, int tx_slot,
+                       int tx_sym) {
+  MagMap<N> M(ts);
+  const int eob = M.load(lev);
+  tok_coeffs_lead<N, B>(k, chroma, eob, above_cul, above_dc, left_cul, left_dc, tx_slot, tx_sym);
+  if (!eob) return;
+  tok_coeffs_pass1<N, B>(k, M, chroma, lev, eob, eob - 1, 0);
+  tok_coeffs_pass2<N, B>(k, M, chroma, lev, above_dc, left_dc, 0, eob);
 }
 
 AV1_HD void tok_mv_comp(Sink &k, int comp, int diff) {            // read_mv_component (5.11.33), quarter-sample precision

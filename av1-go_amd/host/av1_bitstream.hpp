@@ -55,6 +55,9 @@ bool frame_obu_from_tiles(const av1mi_obu_frame &f, const uint8_t *payloads, con
 std::vector<uint8_t> range_code_raw(const uint32_t *fl, const uint32_t *fh, const uint8_t *sym, const uint8_t *nsym, size_t count);
 bool opstream_supported(const av1mi_obu_frame &f, std::string *why);
 bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> *tiles, std::string *err, int key_rows32 = 0);
+int opstream_slots();      // entries of a tile's per-slot arrays
+int opstream_tile32(const av1mi_obu_frame &f, int sbr, int sbc, uint32_t ops_cap, uint32_t *list, uint32_t *grouped, uint16_t *slot_total, uint16_t *slot_base,
+                    std::string *err);
 // the general block-structured writer (av1_blockstream.cpp, include/av1mi_host.h av1mi_obu_blocks): one temporal unit
 bool blocks_temporal_unit(const av1mi_obu_blocks &d, bool with_sequence_header, std::vector<uint8_t> *out, std::string *err, int threads = 1,
                           const size_t (*tile_start)[2] = nullptr);

@@ -27,18 +27,13 @@ bool opstream_supported(const av1mi_obu_frame &f, std::string *why) {
 }
 
 namespace {
-// stages 2 and 3 of a tile whose blocks are tokenized and placed (pos = [slots][kBlocks] positions of the blocks' first entries, the
-// slots' totals and bases, run = the tile's grouped entries): replay, one chain per slot from the default CDFs `image` (the GPU: the
-// tile's threads take the slots, longest first), the serial range coder over the finished list (the GPU: one lane per tile)
-template <int kBlocks>
-bool code_tile(const uint16_t *rec, int block_records, const int *nrec, const int *first, uint16_t *pos, int nslots, const uint16_t *total,
-               const uint16_t *base, int run, const av1ops::SlotTable &tab, const uint16_t *image, std::vector<uint8_t> *out, std::string *err) {
+// stages 2 and 3 of a tile whose list holds the literals and whose adaptive symbols are grouped by slot (totals, bases): one chain per
+// slot from the default CDFs `image` (the GPU: one lane per (tile, slot)), the serial range coder over the finished list (the GPU: one
+// lane per tile)
+bool code_list(std::vector<av1ops::op_t> &list, const std::vector<uint32_t> &grouped, int nslots, const uint16_t *total, const uint16_t *base,
+               const av1ops::SlotTable &tab, const uint16_t *image, std::vector<uint8_t> *out, std::string *err) {
   using namespace av1ops;
-  if (run > 65535) { if (err) *err = "tile too large for 16-bit entry positions"; return false; }
-  const int nops = first[kBlocks];
-  std::vector<op_t> list((size_t)nops, 0);
-  std::vector<uint32_t> grouped((size_t)run, 0);
-  for (int b = 0; b < kBlocks; b++) replay_block<kBlocks>(rec + (size_t)b * block_records, nrec[b], pos, b, first[b], list.data(), grouped.data());
+  const int nops = (int)list.size();
   for (int sl = 0; sl < nslots; sl++)
     if (total[sl]) run_chain(&image[tab.off[sl]], tab.nsym[sl], &grouped[(size_t)base[sl]], total[sl], list.data());
   out->resize((size_t)nops * 2 + 64);       // a step adds at most 15 bits
@@ -49,6 +44,51 @@ bool code_tile(const uint16_t *rec, int block_records, const int *nrec, const in
   const int n = c.finish();
   if (n < 0) { if (err) *err = "tile payload overflow"; return false; }
   out->resize((size_t)n);
+  return true;
+}
+// a tile of 8x8 blocks, tokenized and placed (pos = [slots][kBlocks] positions of the blocks' first entries, the slots' totals and bases,
+// run = the tile's grouped entries): replay, then stages 2 and 3
+template <int kBlocks>
+bool code_tile(const uint16_t *rec, int block_records, const int *nrec, const int *first, uint16_t *pos, int nslots, const uint16_t *total,
+               const uint16_t *base, int run, const av1ops::SlotTable &tab, const uint16_t *image, std::vector<uint8_t> *out, std::string *err) {
+  using namespace av1ops;
+  if (run > 65535) { if (err) *err = "tile too large for 16-bit entry positions"; return false; }
+  std::vector<op_t> list((size_t)first[kBlocks], 0);
+  std::vector<uint32_t> grouped((size_t)run, 0);
+  for (int b = 0; b < kBlocks; b++) replay_block<kBlocks>(rec + (size_t)b * block_records, nrec[b], pos, b, first[b], list.data(), grouped.data());
+  return code_list(list, grouped, nslots, total, base, tab, image, out, err);
+}
+// the wave of av1_ops32.hpp's tok_tile32 as a loop: the lanes of a phase one after the other
+struct WaveLoop {
+  template <class T> using Var = av1ops::LaneVar<T, av1ops::kLanes32>;
+  template <class F> void each(F f) { for (int lane = 0; lane < av1ops::kLanes32; lane++) f(lane); }
+  int scan(Var<int> &v) {
+    int run = 0;
+    for (int lane = 0; lane < av1ops::kLanes32; lane++) { const int x = v.v[lane]; v.v[lane] = run; run += x; }
+    return run;
+  }
+  int first(Var<int> &v) { return v.v[0]; }
+};
+void frame_view_of(const av1mi_obu_frame &f, av1ops::FrameView *v) {
+  memset(v, 0, sizeof(*v));
+  v->w8 = f.width / 8; v->h8 = f.height / 8; v->key = f.frame_type == 0;
+  v->y_mode = f.y_mode; v->uv_mode = f.uv_mode; v->mv = f.mv; v->skip = f.skip; v->lev_y = f.lev_y; v->lev_u = f.lev_u; v->lev_v = f.lev_v;
+  for (int p = 0; p < 3; p++) {
+    v->lr_on[p] = f.lr_type[p] == 1;
+    const int ph = p ? (visible_height(f) + 1) >> 1 : visible_height(f), pw = p ? (visible_width(f) + 1) >> 1 : visible_width(f);
+    v->lr_rows[p] = std::max((ph + 32) / 64, 1); v->lr_cols[p] = std::max((pw + 32) / 64, 1);
+  }
+}
+// the op-stream coder takes ONE unit record per plane class (what the session's policy produces): check and copy it
+bool lr_units_of(const av1mi_obu_frame &f, av1ops::FrameView *v, std::string *err) {
+  for (int p = 0; p < 3; p++) {
+    if (!v->lr_on[p]) continue;
+    const int8_t *u = f.lr_units[p];
+    const size_t n = (size_t)v->lr_rows[p] * v->lr_cols[p];
+    for (size_t i = 1; i < n; i++) if (memcmp(u, u + i * 8, 8)) { if (err) *err = "restoration units must be uniform per plane"; return false; }
+    if (p == 2 && v->lr_on[1] && memcmp(u, f.lr_units[1], 8)) { if (err) *err = "U and V restoration units must be equal"; return false; }
+    memcpy(v->lr_unit[p ? 1 : 0], u, 8);
+  }
   return true;
 }
 }  // namespace
@@ -62,25 +102,10 @@ bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> 
   if (!opstream_supported(f, err)) return false;
   if (key_rows32 && (f.frame_type != 0 || (key_rows32 & 63) || key_rows32 > f.height || (f.width & 31))) { if (err) *err = "bad 32x32 band"; return false; }
   FrameView v;
-  memset(&v, 0, sizeof(v));
-  v.w8 = f.width / 8; v.h8 = f.height / 8; v.key = f.frame_type == 0;
-  v.y_mode = f.y_mode; v.uv_mode = f.uv_mode; v.mv = f.mv; v.skip = f.skip; v.lev_y = f.lev_y; v.lev_u = f.lev_u; v.lev_v = f.lev_v;
+  frame_view_of(f, &v);
   std::vector<uint8_t> zskip;
   if (!v.key && !v.skip) { zskip.assign((size_t)v.w8 * v.h8, 0); v.skip = zskip.data(); }
-  for (int p = 0; p < 3; p++) {
-    v.lr_on[p] = f.lr_type[p] == 1;
-    const int ph = p ? (visible_height(f) + 1) >> 1 : visible_height(f), pw = p ? (visible_width(f) + 1) >> 1 : visible_width(f);
-    v.lr_rows[p] = std::max((ph + 32) / 64, 1); v.lr_cols[p] = std::max((pw + 32) / 64, 1);
-  }
-  // the op-stream coder takes ONE unit record per plane class (what the session's policy produces): check and copy it
-  for (int p = 0; p < 3; p++) {
-    if (!v.lr_on[p]) continue;
-    const int8_t *u = f.lr_units[p];
-    const size_t n = (size_t)v.lr_rows[p] * v.lr_cols[p];
-    for (size_t i = 1; i < n; i++) if (memcmp(u, u + i * 8, 8)) { if (err) *err = "restoration units must be uniform per plane"; return false; }
-    if (p == 2 && v.lr_on[1] && memcmp(u, f.lr_units[1], 8)) { if (err) *err = "U and V restoration units must be equal"; return false; }
-    memcpy(v.lr_unit[p ? 1 : 0], u, 8);
-  }
+  if (!lr_units_of(f, &v, err)) return false;
   const size_t nb = (size_t)v.w8 * v.h8;
   std::vector<BlockInfo> info(nb);
   v.info = info.data();
@@ -102,37 +127,23 @@ bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> 
   // words per tile — to stderr; tiles over capacity are skipped instead of failing the call
   const bool stats = getenv("AV1MI_TOK_STATS") != nullptr;
   int st_rec = 0, st_cnt = 0, st_ops = 0, st_over = 0; long st_ops_sum = 0;
-  // the 32x32 band's own slot table, default CDFs, scan tables and scratch
+  // the 32x32 band's own slot table and default CDFs, and what a tile's wave keeps in LDS
   SlotTable tab32;
   const std::vector<uint16_t> image32 = key_rows32 ? default_slot_image_k32(qcat, &tab32) : std::vector<uint16_t>();
-  std::vector<uint16_t> rec32(key_rows32 ? (size_t)kBlocksPerTile * kBlockRecords : 0), cnt32((size_t)K_END * kBlocks32);
-  std::vector<ScanTables32> scan32(key_rows32 ? 1 : 0);
-  if (key_rows32) fill_scan_tables32(scan32.data());
-  alignas(16) uint8_t mag32[kMag32Bytes];
+  std::vector<Tile32Mem> mem32(key_rows32 ? 1 : 0);
+  const uint32_t ops_cap32 = 1u << 20;       // (no tile has as many words: 4 x 1536 coefficients)
+  std::vector<op_t> list32(key_rows32 ? ops_cap32 : 0);
+  std::vector<uint32_t> grouped32(key_rows32 ? 65536 : 0);
   for (int sbr = 0; sbr < sbr_n; sbr++)
     for (int sbc = 0; sbc < sbc_n; sbc++) {
       if (sbr * 64 < key_rows32) {
-        // a tile of the 32x32 band: tokenized serially (the GPU: one lane per tile), then the same chains and the same range coder
-        std::fill(cnt32.begin(), cnt32.end(), 0);
-        const TokScratch32 ts32 = { mag32, scan32.data() };
-        Sum32 sums[kBlocks32];
-        const bool half = sbc * 8 + 4 >= v.w8;      // width % 64 == 32: the superblock's right blocks lie outside the frame
-        for (int b = 0; b < kBlocks32; b++) if (!(half && (b & 1))) block_sums32(v, block_index32(v, sbr, sbc, b), &sums[b]);
-        int nrec[kBlocks32], first[kBlocks32 + 1];
-        first[0] = 0;
-        for (int b = 0; b < kBlocks32; b++) {        // (the GPU: one lane per block)
-          Sink32 k = { &rec32[(size_t)b * kBlockRecords32], cnt32.data(), b, (int)kBlockRecords32, 0, 0, false, 0, 0, 0, 0 };
-          tok_block32(v, k, ts32, sbr, sbc, b, sums);
-          if (k.overflow) { if (err) *err = "a block exceeds the tokenizer's record area"; return false; }
-          nrec[b] = k.nrec; first[b + 1] = first[b] + k.n;
-        }
-        for (int b = 0; b < kBlocks32; b++)
-          if (!count_block32(&rec32[(size_t)b * kBlockRecords32], nrec[b], cnt32.data(), b)) { if (err) *err = "too many symbols of one slot in a block"; return false; }
-        uint16_t base[K_END], total[K_END];
-        const int run = place_tile32(cnt32.data(), total, base);
-        if (!code_tile<kBlocks32>(rec32.data(), kBlockRecords32, nrec, first, cnt32.data(), K_END, total, base, run, tab32, image32.data(),
-                                  &(*tiles)[(size_t)sbr * sbc_n + sbc], err))
-          return false;
+        // a tile of the 32x32 band: the lanes of its wave over scan ranges (tok_tile32), then the same chains and the same range coder
+        WaveLoop wave;
+        uint16_t base[S_MAX], total[S_MAX];
+        const int words = tok_tile32(wave, mem32[0], v, sbr, sbc, list32.data(), ops_cap32, grouped32.data(), total, base);
+        if (words < 0) { if (err) *err = "tile too large for 16-bit entry positions"; return false; }
+        std::vector<op_t> list(list32.begin(), list32.begin() + words);
+        if (!code_list(list, grouped32, K_END, total, base, tab32, image32.data(), &(*tiles)[(size_t)sbr * sbc_n + sbc], err)) return false;
         continue;
       }
       // stage 1, tokenize (the GPU: one thread per block): records + counts, place, replay
@@ -170,6 +181,23 @@ bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> 
     fprintf(stderr, "[av1mi tok stats] %d tiles: records per block <= %d (capacity %d), symbols of a slot in a block <= %d (255), list words per tile <= %d, mean %.0f; %d tiles over a block capacity\n",
             sbr_n * sbc_n, st_rec, (int)kBlockRecords, st_cnt, st_ops, (double)st_ops_sum / (sbr_n * sbc_n), st_over);
   return true;
+}
+
+int opstream_slots() { return av1ops::S_MAX; }
+
+// One tile of a key frame's 32x32 band through tok_tile32 into the caller's areas, as the GPU kernel calls it (tests: the capacity of
+// the list is the caller's): returns the list words, -1 when the tile does not fit (then nothing but the totals and bases is written),
+// -2 for a frame outside the tool set
+int opstream_tile32(const av1mi_obu_frame &f, int sbr, int sbc, uint32_t ops_cap, uint32_t *list, uint32_t *grouped, uint16_t *slot_total, uint16_t *slot_base,
+                    std::string *err) {
+  using namespace av1ops;
+  if (!opstream_supported(f, err) || f.frame_type != 0 || (f.width & 31) || sbr < 0 || sbc < 0 || (sbr + 1) * 64 > f.height || sbc * 64 >= f.width) return -2;
+  FrameView v;
+  frame_view_of(f, &v);
+  if (!lr_units_of(f, &v, err)) return -2;
+  std::vector<Tile32Mem> mem(1);
+  WaveLoop wave;
+  return tok_tile32(wave, mem[0], v, sbr, sbc, list, ops_cap, grouped, slot_total, slot_base);
 }
 
 }  // namespace av1

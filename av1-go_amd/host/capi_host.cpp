@@ -195,6 +195,15 @@ long long av1mi_host_opstream_key32_temporal_unit(const av1mi_obu_frame *f, int 
   if ((long long)b.size() <= cap && out) memcpy(out, b.data(), b.size());
   return (long long)b.size();
 }
+int av1mi_host_opstream_slots(void) { return av1::opstream_slots(); }
+// one tile (superblock sbr, sbc) of a key frame's 32x32 band through the tile tokenizer of csrc/av1_ops32.hpp, into the caller's list
+// (ops_cap words), grouped entries (ops_cap + 4 * slots words) and per-slot totals / bases (av1mi_host_opstream_slots() entries each): the list words, -1 = the tile does not fit, -2 = outside the tool set
+int av1mi_host_opstream_tile32(const av1mi_obu_frame *f, int sbr, int sbc, uint32_t ops_cap, uint32_t *list, uint32_t *grouped, uint16_t *slot_total,
+                               uint16_t *slot_base) {
+  if (!f || !list || !grouped || !slot_total || !slot_base) return -2;
+  std::string e;
+  return av1::opstream_tile32(*f, sbr, sbc, ops_cap, list, grouped, slot_total, slot_base, &e);
+}
 long long av1mi_host_opstream_temporal_unit(const av1mi_obu_frame *f, int with_sequence_header, uint8_t *out, long long cap, char *err, int errcap) {
   return av1mi_host_opstream_key32_temporal_unit(f, 0, with_sequence_header, out, cap, err, errcap);
 }
