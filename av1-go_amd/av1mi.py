@@ -89,7 +89,7 @@ class GopConfig(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("bit_depth", C.c_int), ("base_q_idx", C.c_int), ("gop_length", C.c_int),
                 ("segments", C.c_int), ("search_range", C.c_int), ("gpu_entropy", C.c_int), ("visible_width", C.c_int),
                 ("visible_height", C.c_int), ("coder_streams", C.c_int), ("key_block_size", C.c_int), ("input_format", C.c_int), ("source_width", C.c_int),
-                ("source_height", C.c_int)]
+                ("source_height", C.c_int), ("quality_stats", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -103,7 +103,7 @@ class GopFrame(C.Structure):
                 ("uv_mode", C.c_void_p), ("mv", C.c_void_p), ("skip", C.c_void_p), ("lev_y", C.c_void_p), ("lev_u", C.c_void_p),
                 ("lev_v", C.c_void_p), ("tiles_per_frame", C.c_int), ("tile_size", C.c_void_p), ("tile_payload", C.c_void_p),
                 ("payload_bytes", C.c_uint64), ("lr_on", C.c_void_p), ("key_block_size", C.c_int), ("key_modes_stride", C.c_int),
-                ("key_modes_band", C.c_int)]
+                ("key_modes_band", C.c_int), ("quality", C.c_void_p)]
 
 
 def policy_frame_params(base_q_idx, bit_depth, frame_type):
@@ -113,6 +113,23 @@ def policy_frame_params(base_q_idx, bit_depth, frame_type):
     if rc:
         raise Av1miError(rc, "av1mi_policy_frame_params")
     return p
+
+
+# av1mi_quality (include/av1mi.h): one record per (frame, plane)
+QUALITY_DTYPE = np.dtype([("sse", "<u8"), ("ssim_sum", "<f8"), ("samples", "<u4"), ("windows", "<u4")])
+assert QUALITY_DTYPE.itemsize == 24
+
+
+def quality_psnr(rec, bit_depth):
+    """10 log10(L^2 samples / sse) of one record, or of several taken together (summed sse over summed samples); inf when sse is 0"""
+    sse, n = float(np.sum(rec["sse"], dtype=np.uint64)), float(np.sum(rec["samples"], dtype=np.uint64))
+    L = float((1 << bit_depth) - 1)
+    return float("inf") if sse == 0 else 10.0 * np.log10(L * L * n / sse)
+
+
+def quality_ssim(rec):
+    """ssim_sum / windows of one record"""
+    return float(rec["ssim_sum"]) / float(rec["windows"])
 
 
 INPUT_PLANAR, INPUT_PACKED10, INPUT_P010, INPUT_NV12 = 0, 1, 2, 3      # enum av1mi_input_format
@@ -169,16 +186,17 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
-        they are to be scaled to the coded frame (av1mi_gop_config.source_width): the input buffers then have that size rounded up to 8"""
+        they are to be scaled to the coded frame (av1mi_gop_config.source_width): the input buffers then have that size rounded up to 8;
+        quality_stats: 1 = every batch is measured on the GPU, collect()["quality"] holds the records (av1mi_gop_config.quality_stats)"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
         sw, sh = source if source is not None else (0, 0)
         self.cfg = GopConfig(width, height, bit_depth, base_q_idx, gop_length, segments, search_range, gpu_entropy, vw, vh, coder_streams, key_block_size, input_format,
-                             sw, sh)
+                             sw, sh, int(quality_stats))
         self.in_w, self.in_h = ((sw + 7) & ~7, (sh + 7) & ~7) if source is not None else (width, height)      # geometry of the input buffers
         self.input_format = input_format
         self.g = C.c_void_p()
@@ -229,6 +247,8 @@ class GopSession:
         f = self.collect_raw()
         S, nb = f.segments, f.blocks_per_frame
         out = dict(params=f.params, frame_type=f.params.frame_type, lr_on=_view(f.lr_on, (S, 3), np.uint8), raw=f)      # restoration on / off per segment and plane
+        if f.quality:      # quality_stats: records [segment, plane] (QUALITY_DTYPE)
+            out["quality"] = _view(f.quality, (S, 3), QUALITY_DTYPE)
         if f.key_block_size == 32:
             out["key_block_size"] = 32
         if f.key_block_size == 32 and f.lev_y:
@@ -272,7 +292,12 @@ class GopSession:
             self.g = None
 
 
-N_KERNEL_KINDS = 18   # enum av1mi_kernel_kind
+# enum av1mi_kernel_kind.  N_PIPELINE_KINDS counts the kinds of the coding pipeline, AV1MI_K_FWD_TXFM .. AV1MI_K_INPUT; it is NOT
+# AV1MI_K_KINDS (19 since AV1MI_K_QUALITY, the measuring stage, follows them).  N_KERNEL_KINDS is its older name: callers take
+# N_KERNEL_KINDS - 1 for AV1MI_K_INPUT, so it stays 18.  Whoever wants every kind asks the library (Context.kernel_kinds()).
+N_PIPELINE_KINDS = 18
+N_KERNEL_KINDS = N_PIPELINE_KINDS
+K_QUALITY = 18        # AV1MI_K_QUALITY
 _lib = None
 
 
@@ -449,21 +474,46 @@ class Context:
         src, dst = (C.c_void_p * 3)(*[b.ptr for b in d_src]), (C.c_void_p * 3)(*[b.ptr for b in d_dst])
         self._chk(self.lib.av1mi_scale_planes(self.h, int(bit_depth), int(src_w), int(src_h), int(dst_w), int(dst_h), int(frames), src, dst))
 
+    def quality_planes(self, bit_depth, width, height, frames, d_src, d_dec0, d_dec1=None, d_select=None):
+        """records [frames, 3] (QUALITY_DTYPE) of `frames` stacked frames of TRUE luma size width x height: d_src against d_dec0, or d_dec1
+        where d_select (DevBuf of frames * 3 bytes) holds 0; planar Y, U, V DevBufs at the size rounded up to 8 (av1mi_quality_planes);
+        synchronous here: the records are downloaded"""
+        self.lib.av1mi_quality_planes.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 5
+        arr = lambda bufs: (C.c_void_p * 3)(*[b.ptr for b in bufs]) if bufs is not None else None
+        d_out = self.alloc(frames * 3 * QUALITY_DTYPE.itemsize)
+        try:
+            self._chk(self.lib.av1mi_quality_planes(self.h, int(bit_depth), int(width), int(height), int(frames), arr(d_src), arr(d_dec0), arr(d_dec1),
+                                                    d_select.ptr if d_select is not None else None, d_out.ptr))
+            return d_out.download((frames, 3), QUALITY_DTYPE)
+        finally:
+            d_out.free()
+
     def prof_enable(self, on):
         self._chk(self.lib.av1mi_prof_enable(self.h, int(on)))
 
     def prof_reset(self):
         self._chk(self.lib.av1mi_prof_reset(self.h))
 
+    def kernel_kinds(self):
+        """the names of the loaded library's kernel kinds, in enum order (av1mi_kernel_kind_name answers "?" from AV1MI_K_KINDS on),
+        so a library with fewer kinds than this file knows is asked for no kind it lacks"""
+        self.lib.av1mi_kernel_kind_name.restype = C.c_char_p
+        names = []
+        while len(names) < 256:
+            name = self.lib.av1mi_kernel_kind_name(len(names))
+            if name == b"?":
+                break
+            names.append(name.decode())
+        return names
+
     def prof_get(self):
         """{kind name: (launches, total_ms)} for kinds that were launched"""
-        self.lib.av1mi_kernel_kind_name.restype = C.c_char_p
         out = {}
-        for k in range(N_KERNEL_KINDS):
+        for k, name in enumerate(self.kernel_kinds()):
             n, ms = C.c_int(), C.c_double()
             self._chk(self.lib.av1mi_prof_get(self.h, k, C.byref(n), C.byref(ms)))
             if n.value:
-                out[self.lib.av1mi_kernel_kind_name(k).decode()] = (n.value, ms.value)
+                out[name] = (n.value, ms.value)
         return out
 
     # ---- K6

@@ -143,6 +143,18 @@ hipError_t launch_scale(const ScalePlan *P, int frames, const void *const *src, 
 // the argument rules shared by av1mi_scale_planes and the session: null = fine, else the reason
 const char *scale_geometry_error(int sw, int sh, int dw, int dh);
 
+// the quality records (quality_kernels.hip): source against the decoded picture, three planes of `frames` stacked frames of TRUE luma
+// size w x h in buffers of that size rounded up to 8; two launches (tiles, then a fixed-order sum per frame and plane).  dec1 / sel
+// may be null; scratch: quality_scratch_bytes() bytes, 8-byte aligned; out: frames * 3 records (device memory or pinned host memory)
+struct QualityLaunch {
+  int bd, w, h, frames;
+  const void *const *src, *const *dec0, *const *dec1;
+  const uint8_t *sel;
+  void *scratch; av1mi_quality *out;
+};
+size_t quality_scratch_bytes(int bd, int w, int h, int frames);
+hipError_t launch_quality(const QualityLaunch &Q, hipStream_t s);
+
 int tx_width(int tx_size);
 int tx_height(int tx_size);
 hipError_t launch_inv_txfm(int tx_size, const TxLaunch &L, int bd, hipStream_t s);

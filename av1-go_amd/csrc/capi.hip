@@ -8,6 +8,7 @@
 #include <vector>
 #include "av1mi_internal.hpp"
 #include "qtables.hpp"
+#include "quality.hpp"
 
 struct av1mi_ctx {
   int device = 0;
@@ -21,6 +22,8 @@ struct av1mi_ctx {
   size_t scratch_bytes = 0;
   av1mi_av1ent_state *av1ent = nullptr;   // the AV1-syntax tile coder's scratch (av1_entropy_kernels.hip)
   av1mi::ScalePlan *scale_plan = nullptr; // av1mi_scale_planes: the tables of the geometry it was last called with
+  void *quality_scratch = nullptr;        // av1mi_quality_planes: the tiles' partial sums (grown on demand)
+  size_t quality_scratch_bytes = 0;
   // per-kernel profile: one event pair per launch while enabled
   bool prof_on = false;
   struct ProfRec { int kind; hipEvent_t e0, e1; };
@@ -176,6 +179,7 @@ void av1mi_close(av1mi_ctx *ctx) {
   if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
   if (ctx->back) { (void)hipStreamSynchronize(ctx->back); (void)hipStreamDestroy(ctx->back); }
   if (ctx->scratch) (void)hipFree(ctx->scratch);
+  if (ctx->quality_scratch) (void)hipFree(ctx->quality_scratch);
   if (ctx->av1ent) av1mi::av1ent_free(ctx->av1ent);
   av1mi::scale_plan_destroy(ctx->scale_plan);
   for (auto &r : ctx->prof_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -270,7 +274,7 @@ int av1mi_prof_get(av1mi_ctx *ctx, int kind, int *launches, double *total_ms) {
 }
 const char *av1mi_kernel_kind_name(int kind) {
   static const char *n[AV1MI_K_KINDS] = { "fwd_txfm", "inv_txfm", "quantize", "dequantize", "intra_pred", "mc", "deblock",
-                                          "cdef", "loop_restoration", "intra_pipeline", "inter_pipeline", "misc", "entropy_code", "entropy_pack", "entropy_tokens", "me_integer", "entropy_chains", "input_convert" };
+                                          "cdef", "loop_restoration", "intra_pipeline", "inter_pipeline", "misc", "entropy_code", "entropy_pack", "entropy_tokens", "me_integer", "entropy_chains", "input_convert", "quality" };
   return kind < 0 || kind >= AV1MI_K_KINDS ? "?" : n[kind];
 }
 
@@ -533,6 +537,31 @@ int av1mi_scale_planes(av1mi_ctx *ctx, int bit_depth, int src_w, int src_h, int 
   }
   ProfScope ps(ctx, AV1MI_K_INPUT);
   HIP_TRY(ctx, av1mi::launch_scale(ctx->scale_plan, frames, d_src, d_dst, ctx->stream));
+  return AV1MI_OK;
+}
+
+int av1mi_quality_planes(av1mi_ctx *ctx, int bit_depth, int width, int height, int frames, const void *const d_src[3], const void *const d_dec0[3],
+                         const void *const d_dec1[3], const uint8_t *d_select, av1mi_quality *d_out) {
+  BIND(ctx);
+  if (const char *why = av1mi::quality::geometry_error(bit_depth, width, height, frames)) return fail(ctx, AV1MI_E_INVAL, "av1mi_quality_planes %dx%d: %s", width, height, why);
+  if (!d_src || !d_dec0 || !d_out || (d_select && !d_dec1)) return fail(ctx, AV1MI_E_INVAL, "null pointer (d_select needs d_dec1)");
+  for (int p = 0; p < 3; p++) {
+    if (!d_src[p] || !d_dec0[p] || (d_dec1 && !d_dec1[p])) return fail(ctx, AV1MI_E_INVAL, "null device pointer (plane %d)", p);
+    if ((((uintptr_t)d_src[p] | (uintptr_t)d_dec0[p] | (uintptr_t)(d_dec1 ? d_dec1[p] : nullptr)) & 15) || ((uintptr_t)d_out & 7))
+      return fail(ctx, AV1MI_E_INVAL, "misaligned device pointer (planes 16 bytes, records 8)");
+  }
+  const size_t need = av1mi::quality_scratch_bytes(bit_depth, width, height, frames);
+  if (ctx->quality_scratch_bytes < need) {      // (hipFree waits for the launches that still read the old one)
+    if (ctx->quality_scratch) (void)hipFree(ctx->quality_scratch);
+    ctx->quality_scratch = nullptr; ctx->quality_scratch_bytes = 0;
+    HIP_TRY(ctx, hipMalloc(&ctx->quality_scratch, need));
+    ctx->quality_scratch_bytes = need;
+  }
+  av1mi::QualityLaunch Q;
+  Q.bd = bit_depth; Q.w = width; Q.h = height; Q.frames = frames; Q.src = d_src; Q.dec0 = d_dec0; Q.dec1 = d_dec1; Q.sel = d_select;
+  Q.scratch = ctx->quality_scratch; Q.out = d_out;
+  ProfScope ps(ctx, AV1MI_K_QUALITY);
+  HIP_TRY(ctx, av1mi::launch_quality(Q, ctx->stream));
   return AV1MI_OK;
 }
 

@@ -10,6 +10,7 @@
 //   code_blocks       main: k_intra_pipe | k_me_int + k_inter_pipe -> kernel_done
 //   download_symbols  down: wait kernel_done -> D2H of the symbols into pinned memory
 //   loop_filters      main: deblock x3, CDEF, LR x3 + decision -> reference -> filters_done;  down: the decision -> downloaded
+//   measure_quality   main: (quality_stats) k_quality_tiles + k_quality_sum, the records written into the slot's pinned memory -> quality_done
 //   start_coder       side: (GPU entropy coding) wait filters_done -> k_av1_* -> payloads gathered into the slot's pinned buffer -> ent_done
 // Source and symbol buffers exist kSlots = 3 times (slot = batch % 3): batch t + 2 uploads while batch t + 1 is in the block
 // pipeline and the coder works on batch t, whose predecessor the host is still reading.  Four streams, one hardware queue each
@@ -29,6 +30,7 @@
 #include <new>
 #include <vector>
 #include "av1mi_internal.hpp"
+#include "quality.hpp"
 
 namespace {
 
@@ -93,6 +95,9 @@ struct Slot {
   bool ent_pending = false;
   bool symbols_down = false;          // this batch's symbols were sent to the host at submit time
   int ent_ticket = -1;                // >= 0: the range coder of this batch is still to be launched (coder_streams 3: av1_entropy_back)
+  // quality_stats: the batch's records [segment * 3 + plane], pinned and written by the GPU (k_quality_sum); quality_done follows
+  void *h_quality = nullptr;
+  hipEvent_t quality_done = nullptr;
 };
 
 }  // namespace
@@ -115,6 +120,7 @@ struct av1mi_gop {
   int key_modes_band = 0, key_modes_stride = 0;  // mode bytes per segment: the 32x32 blocks, then (from key_modes_band) the 8x8 blocks of the last rows
   void *d_cdef_sb[2] = {}, *d_lr[2] = {}, *d_zero_skip = nullptr;
   void *d_lr_scratch = nullptr;                // the restoration decision's partial sums (three planes)
+  void *d_quality_scratch = nullptr;           // quality_stats: the tiles' partial sums of one batch (the main stream orders its users)
   int vw = 0, vh = 0;                          // the true frame size (== the coded size unless cfg.visible_* say otherwise)
   int last = 0;                                // slot of the most recent batch (its d_lr_on selects the next batch's references)
   av1mi_frame_params params[2];                // key, inter
@@ -180,6 +186,10 @@ int slot_buffers(av1mi_gop *g, Slot &s) {
     G_TRY(dev_alloc(g, &s.d_tile_size, (size_t)g->tiles * S * 4)); G_TRY(host_alloc(g, &s.h_tile_size, (size_t)g->tiles * S * 4));
     G_TRY(dev_alloc(g, &s.d_total, 16)); G_TRY(host_alloc(g, &s.h_total, 16));
     G_HIP(hipEventCreateWithFlags(&s.ent_done, hipEventDisableTiming));
+  }
+  if (c.quality_stats) {
+    G_TRY(host_alloc(g, &s.h_quality, (size_t)S * 3 * sizeof(av1mi_quality)));
+    G_HIP(hipEventCreateWithFlags(&s.quality_done, hipEventDisableTiming));
   }
   return AV1MI_OK;
 }
@@ -262,6 +272,8 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
     return WHY("key_block_size 32 needs a width that is a multiple of 32");
   if (c->gpu_entropy && (c->width > 4096 || c->height > 4096)) return WHY("the AV1 tile coder takes frames up to 4096x4096");
   if ((size_t)c->height * c->segments > 65535u * 8u) return WHY("segments x height too large for one launch");
+  if (c->quality_stats && ((c->visible_width ? c->visible_width : c->width) < 16 || (c->visible_height ? c->visible_height : c->height) < 16))
+    return WHY("quality_stats needs a true luma size of at least 16x16");
   return nullptr;
 #undef WHY
 }
@@ -306,6 +318,7 @@ int setup(av1mi_gop *g) {
   for (int p = 0; p < 3; p++)      // reconstruction, deblocked, CDEF and reference planes: single (the chain is serial in t)
     for (void **d : { &g->d_rec[p], &g->d_dbl[p], &g->d_cdef[p], &g->d_ref[p] }) G_TRY(dev_alloc(g, d, g->plane[p].bytes));
   G_TRY(dev_alloc(g, &g->d_lr_scratch, av1mi_lr_yuv_decide_scratch_bytes(h, S)));
+  if (c.quality_stats) G_TRY(dev_alloc(g, &g->d_quality_scratch, av1mi::quality_scratch_bytes(c.bit_depth, g->vw, g->vh, S)));
   G_TRY(dev_alloc(g, &g->d_zero_skip, g->nb));
   G_TRY(av1mi_memset(g->ctx, g->d_zero_skip, 0, g->nb));
   G_TRY(side_information(g));
@@ -346,7 +359,7 @@ void av1mi_gop_close(av1mi_gop *g) {
   if (g->up) { (void)hipStreamSynchronize(g->up); (void)hipStreamDestroy(g->up); }
   if (g->down) { (void)hipStreamSynchronize(g->down); (void)hipStreamDestroy(g->down); }
   for (Slot &s : g->slot)
-    for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done })
+    for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done, s.quality_done })
       if (e) (void)hipEventDestroy(e);
   for (void *p : g->dev_allocs) (void)hipFree(p);
   for (void *p : g->host_allocs) (void)hipHostFree(p);
@@ -366,7 +379,8 @@ int av1mi_gop_max_in_flight(void) { return kSlots; }
 //    decision.  That ran on the main stream too, so the launches here are ordered behind it by the stream itself; no event.
 //  - d_in, the device buffer of the source as fed (with zero stages: d_src itself), is read by the input stages / the kernels of the
 //    slot's previous batch.  The upload into it waits for that batch's filters_done, which was recorded on the main stream AFTER those
-//    launches (the restoration decision is the last reader).
+//    launches (the restoration decision is the last reader), and with quality_stats for its quality_done (measure_quality reads the
+//    source after the filters).
 // `uploaded` keeps its two meanings: the main stream waits for it before the first launch, and av1mi_gop_acquire_input waits for
 // it before the host may overwrite the pinned buffers.
 static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const void *src[3]) {
@@ -374,6 +388,7 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
   for (int p = 0; p < 3; p++) src[p] = dev_src ? dev_src[p] : s.d_in[p];
   if (!dev_src) {
     if (s.kernel_pending) G_HIP(hipStreamWaitEvent(g->up, s.filters_done, 0));
+    if (s.kernel_pending && g->cfg.quality_stats) G_HIP(hipStreamWaitEvent(g->up, s.quality_done, 0));
     for (int p = 0; p < 3; p++)
       if (g->in_bytes[p]) G_HIP(hipMemcpyAsync(s.d_in[p], s.h_in[p], g->in_bytes[p], hipMemcpyHostToDevice, g->up));
     G_HIP(hipEventRecord(s.uploaded, g->up));
@@ -516,6 +531,26 @@ static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
   return AV1MI_OK;
 }
 
+// quality_stats: the batch's records.  The planar source at the coded size against what a decoder outputs — per segment and plane the
+// restored plane (d_ref) or, where the decision just made switched restoration off, the CDEF plane (d_cdef) — over the TRUE frame size.
+// On the main stream behind the filters: the next batch's filters overwrite d_ref / d_cdef later on the same stream, and this slot's
+// d_lr_on is next written kSlots batches on, so stream order is the guard.  The summing launch writes the records straight into the
+// slot's pinned memory; quality_done is what av1mi_gop_collect waits for (this batch's own event, not the stream), and what the
+// slot's next upload waits for before it overwrites the source.
+static int measure_quality(av1mi_gop *g, Slot &s, const void *const src[3]) {
+  hipStream_t main = av1mi::ctx_stream(g->ctx);
+  av1mi::QualityLaunch Q;
+  Q.bd = g->cfg.bit_depth; Q.w = g->vw; Q.h = g->vh; Q.frames = g->cfg.segments;
+  Q.src = src; Q.dec0 = g->d_ref; Q.dec1 = g->d_cdef; Q.sel = (const uint8_t *)s.d_lr_on;
+  Q.scratch = g->d_quality_scratch; Q.out = (av1mi_quality *)s.h_quality;
+  {
+    av1mi::ProfScope ps(g->ctx, AV1MI_K_QUALITY, main);
+    G_HIP(av1mi::launch_quality(Q, main));
+  }
+  G_HIP(hipEventRecord(s.quality_done, main));
+  return AV1MI_OK;
+}
+
 // the coder's results of a slot -> its pinned mirrors, then ent_done (on the stream the range coder ran on)
 static int entropy_results(av1mi_gop *g, Slot &s, hipStream_t st) {
   const int S = g->cfg.segments;
@@ -590,6 +625,7 @@ static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src
     G_TRY(download_symbols(g, s));
   }
   G_TRY(loop_filters(g, s, src));
+  if (g->cfg.quality_stats) G_TRY(measure_quality(g, s, src));
   if (g->cfg.gpu_entropy) G_TRY(start_coder(g, s));
   g->last = (int)(g->submitted % kSlots);
   g->submitted++;
@@ -638,6 +674,7 @@ int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out) {
   memset(out, 0, sizeof(*out));
   out->params = g->params[s.frame_type];
   out->lr_on = (const uint8_t *)s.h_lr_on;
+  if (g->cfg.quality_stats) { G_HIP(hipEventSynchronize(s.quality_done)); out->quality = (const av1mi_quality *)s.h_quality; }
   out->segments = g->cfg.segments;
   out->blocks_per_frame = g->nb / (size_t)g->cfg.segments;
   out->key_block_size = s.frame_type == 0 && g->key32 ? 32 : 8;

@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/av1mi.h"
+#include "../csrc/quality.hpp"
 #include "av1_bitstream.hpp"
 #include "mux.hpp"
 #include "y4m.hpp"
@@ -176,6 +177,12 @@ int RunBackend(const BackendJob &job, std::string *err) {
     cfg.width = w; cfg.height = h; cfg.bit_depth = y.bd; cfg.base_q_idx = job.quality < 1 ? 1 : job.quality; cfg.gop_length = G; cfg.segments = S;
     cfg.search_range = 8;
     cfg.gpu_entropy = job.gpu_entropy ? 1 : 0;
+    // -av1mi_stats / -av1mi_min_psnr: the session measures every batch on the GPU; the records arrive with the collected batch
+    const bool measure = !job.stats_path.empty() || job.min_psnr > 0;
+    cfg.quality_stats = measure ? 1 : 0;
+    std::string stats;                 // the stats file's lines, in presentation order
+    av1mi::quality::Summary summary;
+    long long total_bytes = 0;
     // key frames in 32x32 blocks where the frame allows it (the coded width a multiple of 32)
     cfg.key_block_size = (job.key_block_size == 32 && (w & 31) == 0) ? 32 : 8;
     // -av1mi_pack10 1: a 10-bit source crosses PCIe at 10 bits per sample; the session's pinned buffers are then three packed planes
@@ -192,9 +199,12 @@ int RunBackend(const BackendJob &job, std::string *err) {
       if (!sink.add_side_file(side, err)) { code = 1; goto done; }
     if (!sink.open(job.output, sp, y.fps_n, y.fps_d, err)) { code = 1; goto done; }
     std::vector<std::vector<std::vector<uint8_t>>> units((size_t)S);   // [segment][frame] temporal units of the batch in flight
+    struct Rec { av1mi_quality q[3]; };
+    std::vector<std::vector<Rec>> records((size_t)S);                  // ... and their quality records (measure)
     const int lag = av1mi_gop_max_in_flight() - 1;      // batches the GPU holds while the host works on the oldest
     for (long g0 = 0;; g0 += S) {
       for (auto &u : units) u.clear();
+      for (auto &r : records) r.clear();
       // the next GROUP of S GOPs: a file is read in place, a stream one group ahead of the encoder (y4m.hpp)
       const long have_frames = y.prepare(g0 * G, (long)S * G, err);
       if (have_frames < 0) { code = 1; goto done; }
@@ -215,6 +225,12 @@ int RunBackend(const BackendJob &job, std::string *err) {
           std::vector<uint8_t> tu;
           if (!SessionTemporalUnit(fr, s, w, h, y.bd, cfg.visible_width, cfg.visible_height, t == 0, threads, &tu, err)) return false;
           units[(size_t)s].push_back(std::move(tu));
+          if (measure) {
+            if (!fr.quality) { *err = "the session returned no quality records"; return false; }
+            Rec r;
+            memcpy(r.q, fr.quality + (size_t)s * 3, sizeof(r.q));
+            records[(size_t)s].push_back(r);
+          }
         }
         return true;
       };
@@ -266,9 +282,38 @@ int RunBackend(const BackendJob &job, std::string *err) {
       for (int s = 0; s < S; s++)
         for (size_t t = 0; t < units[(size_t)s].size(); t++)
           if (!sink.write(units[(size_t)s][t], t == 0, err)) { code = 1; goto done; }
+      if (measure)
+        for (int s = 0; s < S; s++)
+          for (size_t t = 0; t < units[(size_t)s].size(); t++) {
+            char line[512];
+            int n = snprintf(line, sizeof(line), "n:%ld type:%c bytes:%zu", summary.frames, t == 0 ? 'K' : 'P', units[(size_t)s][t].size());
+            n += av1mi::quality::format_figures(av1mi::quality::frame_figures(records[(size_t)s][t].q, y.bd), line + n, sizeof(line) - (size_t)n);
+            stats.append(line, (size_t)n); stats += '\n';
+            summary.add(records[(size_t)s][t].q, y.bd);
+            total_bytes += (long long)units[(size_t)s][t].size();
+          }
     }
     if (total_frames == 0) { *err = job.input + ": Invalid data found when processing input (no frames)"; code = 1; goto done; }
     if (!sink.close(err)) { code = 1; goto done; }
+    if (measure) {
+      const av1mi::quality::Figures f = summary.figures(y.bd);
+      if (!job.stats_path.empty()) {
+        char line[512];
+        int n = snprintf(line, sizeof(line), "summary frames:%ld bytes:%lld", summary.frames, total_bytes);
+        n += av1mi::quality::format_figures(f, line + n, sizeof(line) - (size_t)n);
+        stats.append(line, (size_t)n); stats += '\n';
+        FILE *sf = fopen(job.stats_path.c_str(), "wb");
+        const bool ok = sf && fwrite(stats.data(), 1, stats.size(), sf) == stats.size();
+        if ((sf && fclose(sf)) || !ok) { *err = job.stats_path + ": could not write the stats file"; remove(job.output.c_str()); code = 1; goto done; }
+      }
+      if (job.min_psnr > 0 && f.psnr[0] < job.min_psnr) {      // the quality gate: the file is not good enough to stand in for its source
+        char why[160];
+        snprintf(why, sizeof(why), "quality gate: psnr_y %.6f dB below the bound %.6f dB", f.psnr[0], job.min_psnr);
+        *err = why;
+        remove(job.output.c_str());
+        code = 3; goto done;
+      }
+    }
   }
 done:
   sink.abort();

@@ -6,6 +6,7 @@
 #include "mux.hpp"
 #include "y4m.hpp"
 #include "backend.hpp"
+#include "../csrc/quality.hpp"
 
 using namespace av1mi_host;
 
@@ -116,6 +117,47 @@ int av1mi_host_process_job(const char *source, long long orig_size, double ratio
   strncpy(status, job.Status.c_str(), cap - 1); status[cap - 1] = 0;
   strncpy(reason, job.Reason.c_str(), cap - 1); reason[cap - 1] = 0;
   return e.empty() ? 0 : 1;
+}
+// ProcessJob with the quality gate: the argument list above plus TranscodeConfig::MinPSNR (dB, 0 = off)
+int av1mi_host_process_job_q(const char *source, long long orig_size, double ratio, const char *state_dir, int wait_s, int replace_source,
+                             char *status, char *reason, int cap, double min_psnr) {
+  Job job; job.ID = "test"; job.SourcePath = source; job.OriginalSize = orig_size;
+  TranscodeConfig cfg; cfg.MaxSizeRatio = ratio; cfg.JobStateDir = state_dir ? state_dir : ""; cfg.StableWaitSeconds = wait_s;
+  cfg.ReplaceSource = replace_source != 0; cfg.MinPSNR = min_psnr;
+  ProbeResult pr; pr.HasVideo = true; pr.has_video_stream = true; pr.VideoStream.Height = 720;
+  const std::string e = ProcessJob(&job, "av1mi", pr, cfg);
+  strncpy(status, job.Status.c_str(), cap - 1); status[cap - 1] = 0;
+  strncpy(reason, job.Reason.c_str(), cap - 1); reason[cap - 1] = 0;
+  return e.empty() ? 0 : 1;
+}
+// the quality records on the host (csrc/quality.hpp): the CPU twin of av1mi_quality_planes and the derived figures
+int av1mi_quality_planes_host(int bit_depth, int width, int height, int frames, const void *const src[3], const void *const dec0[3], const void *const dec1[3],
+                              const uint8_t *select, av1mi_quality *out) {
+  return av1mi::quality::planes_host(bit_depth, width, height, frames, src, dec0, dec1, select, out);
+}
+double av1mi_quality_psnr(const av1mi_quality *q, int bit_depth) { return av1mi::quality::psnr_from_sse((double)q->sse, (double)q->samples, bit_depth); }
+double av1mi_quality_ssim(const av1mi_quality *q) { return q->ssim_sum / (double)q->windows; }
+// test hooks: the constants, ParseBackendJob's view of the two options, and the stats file's summary line from n frames' records
+// (q: n * 3 records; bytes: n temporal unit sizes); returns the line's length
+void av1mi_host_quality_constants(int bit_depth, long long *c1, long long *c2) { *c1 = av1mi::quality::ssim_c1(bit_depth); *c2 = av1mi::quality::ssim_c2(bit_depth); }
+int av1mi_host_parse_quality_options(const char *joined, char *stats_path, int cap, double *min_psnr, char *err, int errcap) {
+  std::vector<std::string> a; std::string s = joined; size_t p = 0, q;
+  while ((q = s.find('\n', p)) != std::string::npos) { a.push_back(s.substr(p, q - p)); p = q + 1; }
+  a.push_back(s.substr(p));
+  BackendJob job; std::string e;
+  const bool ok = ParseBackendJob(a, &job, &e);
+  strncpy(stats_path, job.stats_path.c_str(), cap - 1); stats_path[cap - 1] = 0;
+  strncpy(err, e.c_str(), errcap - 1); err[errcap - 1] = 0;
+  *min_psnr = job.min_psnr;
+  return ok ? 0 : -1;
+}
+int av1mi_host_quality_summary_line(const av1mi_quality *q, const long long *bytes, int n, int bit_depth, char *buf, int cap) {
+  av1mi::quality::Summary sum;
+  long long total = 0;
+  for (int i = 0; i < n; i++) { sum.add(q + 3 * i, bit_depth); total += bytes[i]; }
+  int k = snprintf(buf, cap, "summary frames:%ld bytes:%lld", sum.frames, total);
+  if (k < 0 || k >= cap) return -1;
+  return k + av1mi::quality::format_figures(sum.figures(bit_depth), buf + k, (size_t)(cap - k));
 }
 // AV1 bitstream writer (av1_bitstream.hpp): one temporal unit (delimiter [+ sequence header] + frame) for a frame description.
 // Returns the size in bytes (copied into out when it fits in cap), -1 on a description the writer cannot code (text in err).

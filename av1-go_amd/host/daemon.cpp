@@ -130,7 +130,20 @@ std::string ProcessJob(Job *job, const std::string &backendPath, const ProbeResu
     return "failed to build transcode args: " + err;
   }
   if (cfg.Device) { const std::string out = args.back(); args.back() = "-av1mi_device"; args.push_back(std::to_string(cfg.Device)); args.push_back(out); }
+  if (cfg.MinPSNR > 0) {
+    char bound[32];
+    snprintf(bound, sizeof(bound), "%.6f", cfg.MinPSNR);
+    const std::string out = args.back(); args.back() = "-av1mi_min_psnr"; args.push_back(bound); args.push_back(out);
+  }
   const RunResult rr = RunTranscode(backendPath, args);                                                                                 // :101
+  if (rr.exitCode == 3 && rr.err.compare(0, 14, "quality gate: ") == 0) {      // refused like a file the size gate refuses (:129-150)
+    job->Status = "skipped"; job->Reason = rr.err;
+    write_why(job->SourcePath, job->Reason);
+    write_text(dir + "/" + stem + ".av1qsvd-skip", "skip");
+    remove(outputPath.c_str());
+    save_job(*job, cfg.JobStateDir);
+    return "";
+  }
   if (!rr.err.empty() || rr.exitCode != 0) {                                                                                            // :102-112
     job->Status = "failed"; job->Reason = "ffmpeg exit code " + std::to_string(rr.exitCode) + ": " + rr.err;
     save_job(*job, cfg.JobStateDir); write_why(job->SourcePath, job->Reason); remove(outputPath.c_str());

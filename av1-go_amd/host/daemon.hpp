@@ -38,6 +38,10 @@ struct TranscodeConfig {           // daemon.go:185-188; Device is this backend'
   // would destroy its other streams: the step is off unless explicitly asked for, and the coded file is then kept beside
   // the source as "<base>.av1mi.mkv".
   bool ReplaceSource = false;
+  // The quality gate, this backend's addition beside the size gate: the luma PSNR (dB) of the whole coded file against its source, measured
+  // on the GPU while coding, must reach this bound; 0 = off.  A file below it is treated as one the size gate refuses: skipped, why-file,
+  // skip marker, output removed, source untouched.
+  double MinPSNR = 0;
 };
 
 // daemon.go:57-182.  Returns "" where the reference returns nil, else the error text; job.Status / job.Reason are

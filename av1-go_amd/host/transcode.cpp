@@ -116,6 +116,13 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
     else if (args[i] == "-av1mi_tracks") job->tracks.push_back(args[i + 1]);
     else if (args[i] == "-av1mi_key_block_size") job->key_block_size = std::atoi(args[i + 1].c_str());
     else if (args[i] == "-av1mi_pack10") job->pack10 = std::atoi(args[i + 1].c_str());
+    else if (args[i] == "-av1mi_stats") job->stats_path = args[i + 1];
+    else if (args[i] == "-av1mi_min_psnr") {
+      char *end = nullptr;
+      job->min_psnr = std::strtod(args[i + 1].c_str(), &end);
+      // a finite bound: nan fails the first comparison, inf (which every lossy file would miss) the second
+      if (args[i + 1].empty() || *end || !(job->min_psnr >= 0) || !(job->min_psnr <= 1e308)) { if (err) *err = "Invalid argument: -av1mi_min_psnr takes a finite bound in dB (0 = off), not " + args[i + 1]; return false; }
+    }
     else if (args[i] == "-vf:v:0" || args[i] == "-vf") { job->vf = args[i + 1]; job->have_vf = true; }
     else if (args[i] == "-av1mi_scale") {
       const std::string &v = args[i + 1];
@@ -145,6 +152,7 @@ RunResult RunTranscode(const std::string &backendPath, const std::vector<std::st
   if (code == 0) return { 0, "" };
   if (err.size() > 800) err = err.substr(0, 800) + "...";      // transcode.go:295-297
   if (code < 0) return { -1, "av1mi execution failed: " + err };   // transcode.go:311 (could not run)
+  if (code == 3) return { 3, err };                                // the quality gate: "quality gate: psnr_y ..." as it is
   return { code, "av1mi failed with exit code " + std::to_string(code) + ": " + err };   // transcode.go:299
 }
 

@@ -57,6 +57,10 @@ struct BackendJob {
   bool have_vf = false;    // "-vf:v:0" / "-vf" was given: the filter chain below is evaluated on the source's size and sample aspect ratio
   std::string vf;          // (ScaleTarget) and the frames are scaled on the GPU to what it yields; absent = the source size is coded as before
   int scale_w = 0, scale_h = 0;      // -av1mi_scale WxH: an explicit target (16 .. 4096 each); wins over the chain
+  std::string stats_path;  // -av1mi_stats <file>: per-frame PSNR / SSIM of the decoded picture against the source as coded, measured on the GPU
+                           // (av1mi_gop_config.quality_stats), one line per frame in presentation order + a summary line
+  double min_psnr = 0;     // -av1mi_min_psnr <dB>: the quality gate on the summary's psnr_y (0 = off), with or without a stats file: below it the
+                           // transcode fails with exit code 3, "quality gate: psnr_y ...", and the output is removed
   std::vector<std::string> tracks;   // -av1mi_tracks <file.mka> (repeatable): Matroska side files whose audio / subtitle tracks are copied
                                      // next to the video (the reference's `-c:a copy -c:s copy`, transcode.go:134-137, after an external demux)
 };
@@ -71,7 +75,8 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
 bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err);
 
 // transcode.go:194-315 contract: (0, "") on success AND the output file exists; (code, text <= 800 chars) on failure;
-// (-1, text) when the backend could not run at all (no HIP device, library error before any frame).
+// (-1, text) when the backend could not run at all (no HIP device, library error before any frame).  Exit code 3 is the quality gate
+// (-av1mi_min_psnr): its text is handed on as it is, "quality gate: psnr_y ...", for ProcessJob to treat like the size gate.
 struct RunResult { int exitCode; std::string err; };
 RunResult RunTranscode(const std::string &backendPath, const std::vector<std::string> &args);
 

@@ -83,7 +83,7 @@ int av1mi_timer_end(av1mi_ctx *ctx, float *elapsed_ms);
 enum av1mi_kernel_kind {
   AV1MI_K_FWD_TXFM, AV1MI_K_INV_TXFM, AV1MI_K_QUANT, AV1MI_K_DEQUANT, AV1MI_K_INTRA_PRED, AV1MI_K_MC,
   AV1MI_K_DEBLOCK, AV1MI_K_CDEF, AV1MI_K_LR, AV1MI_K_INTRA_PIPE, AV1MI_K_INTER_PIPE, AV1MI_K_MISC, AV1MI_K_ENTROPY,
-  AV1MI_K_ENTROPY_PACK, AV1MI_K_ENTROPY_TOKENS, AV1MI_K_ME_INT, AV1MI_K_ENTROPY_CHAINS, AV1MI_K_INPUT, AV1MI_K_KINDS
+  AV1MI_K_ENTROPY_PACK, AV1MI_K_ENTROPY_TOKENS, AV1MI_K_ME_INT, AV1MI_K_ENTROPY_CHAINS, AV1MI_K_INPUT, AV1MI_K_QUALITY, AV1MI_K_KINDS
 };
 int av1mi_prof_enable(av1mi_ctx *ctx, int on);
 int av1mi_prof_reset(av1mi_ctx *ctx);
@@ -382,6 +382,37 @@ int av1mi_scale_filter(int src_n, int dst_n, int *taps, int32_t *first, int16_t 
 int av1mi_scale_planes(av1mi_ctx *ctx, int bit_depth, int src_w, int src_h, int dst_w, int dst_h, int frames, const void *const d_src[3],
                        void *const d_dst[3]);
 
+/* ---- quality: per-plane squared error and SSIM of a decoded picture b against the source a (av1-go_amd/csrc/quality_kernels.hip; the
+ * arithmetic, shared with the host, in av1-go_amd/csrc/quality.hpp).  Each plane is handled on its own over its TRUE size W x H: luma the
+ * frame's true size, chroma (W_luma + 1) / 2 x (H_luma + 1) / 2.  Normative:
+ *   sse       sum (a - b)^2 over all W H samples, exact; columns and rows beyond the last whole 4x4 block included.
+ *             PSNR (derived on the host) = 10 log10(L^2 W H / sse), L = 2^bit_depth - 1; inf when sse = 0.
+ *   SSIM      the 8x8-window, step-4 form of the x264 / FFmpeg `ssim` filter.  4x4 blocks over floor(W / 4) x floor(H / 4), a partial
+ *             block at the right or bottom is ignored; per block s1 = sum a, s2 = sum b, ss = sum (a^2 + b^2), s12 = sum a b.  One
+ *             window for every (x, y) in [0, floor(W / 4) - 1) x [0, floor(H / 4) - 1): the sum of blocks (x, y), (x + 1, y), (x, y + 1),
+ *             (x + 1, y + 1).  Per window, in 64-bit integers:
+ *               vars = 64 ss - s1^2 - s2^2,  covar = 64 s12 - s1 s2,
+ *               c1 = floor(0.01^2 L^2 64 + 0.5),  c2 = floor(0.03^2 L^2 64 63 + 0.5)      (8 bit: 416, 235963; 10 bit: 6698, 3797644)
+ *             then each of the four factors converted to double (all below 2^35: exact) and
+ *               ssim = ((2 s1 s2 + c1) (2 covar + c2)) / ((s1^2 + s2^2 + c1) (vars + c2)):
+ *             one product above, one below, one IEEE division; no addition follows a product (nothing to contract).
+ *   ssim_sum  the sum of the windows' values in double, `windows` their count; the reported SSIM is ssim_sum / windows.  The order of
+ *             the additions is fixed per implementation: the device gives the same bits run to run, and agrees with the host twin to
+ *             rounding (relative 1e-12).
+ *   "All"     SSIM: (4 Y + U + V) / 6; PSNR: from the summed sse over the summed sample counts.
+ * A plane with no window cannot be measured: a true luma size under 16 x 16 is AV1MI_E_INVAL. */
+typedef struct av1mi_quality { uint64_t sse; double ssim_sum; uint32_t samples, windows; } av1mi_quality;
+/* The records of `frames` stacked 4:2:0 frames of TRUE luma size width x height, planar planes (uint8 for 8-bit, uint16 otherwise) in
+ * buffers of that size rounded up to 8 in both directions (stride and rows per frame; the half for chroma; nothing beyond the true
+ * size is read).  Per (frame, plane) the decoded picture is read from d_dec0, or from d_dec1 where d_select[frame * 3 + plane] == 0
+ * (the layout and meaning of the session's restoration flags: 1 = the restored plane, the first candidate); d_select NULL = always
+ * d_dec0, and d_dec1 may then be NULL too.  d_out: frames * 3 records [frame * 3 + plane], 8-byte aligned; planes 16-byte aligned.
+ * Two launches (tiles, then a fixed-order sum: no atomics), asynchronous on the context's stream; AV1MI_K_QUALITY in the profile.
+ * The CPU twin on host pointers, av1mi_quality_planes_host, and the derived figures av1mi_quality_psnr / av1mi_quality_ssim are
+ * exported by libav1mi_host.so and declared beside the arithmetic in av1-go_amd/csrc/quality.hpp. */
+int av1mi_quality_planes(av1mi_ctx *ctx, int bit_depth, int width, int height, int frames, const void *const d_src[3], const void *const d_dec0[3],
+                         const void *const d_dec1[3], const uint8_t *d_select, av1mi_quality *d_out);
+
 /* ---- GOP session: the encoder object a cgo replacement of RunTranscode drives (reference call site
  * internal/daemon/daemon.go:101 -> internal/ffmpeg/transcode.go:194; SURVEY.md §8b "av1mi_open(config) / av1mi_encode /
  * av1mi_flush").  It owns the closed-GOP orchestration and the encoder's filter-parameter POLICY, so that no caller
@@ -434,6 +465,12 @@ typedef struct av1mi_gop_config {
    * of the coded size, which are device-only.  16 .. 4096 each, ratio to the target within [1/4, 4]; a source equal to the target is
    * accepted and takes the scaling path (the identity). */
   int source_width, source_height;
+  /* != 0: every batch is measured (stage measure_quality behind the in-loop filters: av1mi_quality_planes' two launches on the planar
+   * source at the coded size — the scaled / converted frame where the session scales or converts — against the picture a decoder
+   * outputs: the restored plane, or the CDEF plane where restoration was switched off) and av1mi_gop_frame.quality carries the
+   * records.  0 (default): nothing is launched or allocated.  Needs a true luma size of at least 16 x 16.  Changes nothing about what
+   * is coded. */
+  int quality_stats;
 } av1mi_gop_config;
 
 /* Frame-header parameters chosen by the session's policy for one frame (non-normative encoder choices; the bitstream carries
@@ -476,6 +513,9 @@ typedef struct av1mi_gop_frame {    /* one collected frame batch; host pointers 
                                        blocks of the last partial row; the levels
                                        are block-contiguous per region in the same planes (a region's blocks tile its rows of the plane) */
   int key_modes_stride, key_modes_band;
+  /* av1mi_gop_config.quality_stats: segments * 3 records [segment * 3 + plane] of this batch (source against the decoded picture, over
+   * the true frame size), in pinned memory; NULL when the option is off */
+  const av1mi_quality *quality;
 } av1mi_gop_frame;
 
 typedef struct av1mi_gop av1mi_gop;
