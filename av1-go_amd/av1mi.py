@@ -71,7 +71,8 @@ class InterJob(C.Structure):
                 ("d_rec_y", C.c_void_p), ("d_rec_u", C.c_void_p), ("d_rec_v", C.c_void_p),
                 ("d_lev_y", C.c_void_p), ("d_lev_u", C.c_void_p), ("d_lev_v", C.c_void_p),
                 ("d_mvs", C.c_void_p), ("d_skip", C.c_void_p),
-                ("d_ref_alt_y", C.c_void_p), ("d_ref_alt_u", C.c_void_p), ("d_ref_alt_v", C.c_void_p), ("d_ref_sel", C.c_void_p)]
+                ("d_ref_alt_y", C.c_void_p), ("d_ref_alt_u", C.c_void_p), ("d_ref_alt_v", C.c_void_p), ("d_ref_sel", C.c_void_p),
+                ("coarse_range", C.c_int)]
 
 
 class LrDecideJob(C.Structure):
@@ -89,7 +90,7 @@ class GopConfig(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("bit_depth", C.c_int), ("base_q_idx", C.c_int), ("gop_length", C.c_int),
                 ("segments", C.c_int), ("search_range", C.c_int), ("gpu_entropy", C.c_int), ("visible_width", C.c_int),
                 ("visible_height", C.c_int), ("coder_streams", C.c_int), ("key_block_size", C.c_int), ("input_format", C.c_int), ("source_width", C.c_int),
-                ("source_height", C.c_int), ("quality_stats", C.c_int)]
+                ("source_height", C.c_int), ("quality_stats", C.c_int), ("coarse_range", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -186,17 +187,18 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None, quality_stats=0):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
         they are to be scaled to the coded frame (av1mi_gop_config.source_width): the input buffers then have that size rounded up to 8;
-        quality_stats: 1 = every batch is measured on the GPU, collect()["quality"] holds the records (av1mi_gop_config.quality_stats)"""
+        quality_stats: 1 = every batch is measured on the GPU, collect()["quality"] holds the records (av1mi_gop_config.quality_stats);
+        coarse_range: 0, or a multiple of 4 up to 64: P frames search around a coarse centre per 64x64 tile (av1mi_gop_config.coarse_range)"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
         sw, sh = source if source is not None else (0, 0)
         self.cfg = GopConfig(width, height, bit_depth, base_q_idx, gop_length, segments, search_range, gpu_entropy, vw, vh, coder_streams, key_block_size, input_format,
-                             sw, sh, int(quality_stats))
+                             sw, sh, int(quality_stats), int(coarse_range))
         self.in_w, self.in_h = ((sw + 7) & ~7, (sh + 7) & ~7) if source is not None else (width, height)      # geometry of the input buffers
         self.input_format = input_format
         self.g = C.c_void_p()
@@ -598,7 +600,37 @@ class Context:
     def inter_encode(self, job):
         self._chk(self.lib.av1mi_inter_encode(self.h, C.byref(job)))
 
-    def inter_encode_arrays(self, src, ref, bd, qindex, search_range=8):
+    def me_search(self, src_y, ref_y, bd, search_range=8, coarse_range=0, ref_alt_y=None, ref_sel=None):
+        """the motion search alone (av1mi_me_search): src_y / ref_y [frames, h, w] luma; ref_alt_y + ref_sel ([frames, 3] uint8, 0 = predict
+        from ref_alt_y) as in av1mi_inter_job.  Returns dict(mvs [frames, blocks, 2] — the integer vectors in 1/8 samples —, centres
+        [frames, tiles, 2], q_src / q_ref [frames, h / 4, w / 4] (None when coarse_range is 0))"""
+        dt = np.uint8 if bd == 8 else np.uint16
+        S, R = np.ascontiguousarray(src_y, dt), np.ascontiguousarray(ref_y, dt)
+        nf, h, w = S.shape
+        nb, tiles = (h // 8) * (w // 8), ((h + 63) // 64) * ((w + 63) // 64)
+        bufs = dict(src_y=self.to_device(S), ref_y=self.to_device(R), mvs=self.alloc(nf * nb * 4))
+        if ref_sel is not None:
+            sel = np.zeros((nf * 3 + 3) & ~3, np.uint8)      # read as aligned dwords
+            sel[:nf * 3] = np.ascontiguousarray(ref_sel, np.uint8).reshape(-1)
+            bufs["ref_alt_y"], bufs["ref_sel"] = self.to_device(np.ascontiguousarray(ref_alt_y, dt)), self.to_device(sel)
+        job = InterJob(w, h, bd, nf, 0, search_range, w, w // 2)
+        job.coarse_range = coarse_range
+        for k, b in bufs.items():
+            setattr(job, "d_" + k, b.ptr)
+        q = [self.alloc(nf * (h // 4) * (w // 4)) for _ in range(2)]
+        cen = self.alloc(nf * tiles * 4)
+        self.lib.av1mi_me_search.argtypes = [C.c_void_p, C.POINTER(InterJob), C.c_void_p, C.c_void_p, C.c_void_p]
+        try:
+            self._chk(self.lib.av1mi_me_search(self.h, C.byref(job), q[0].ptr, q[1].ptr, cen.ptr))
+            out = dict(mvs=bufs["mvs"].download((nf, nb, 2), np.int16), centres=cen.download((nf, tiles, 2), np.int16), q_src=None, q_ref=None)
+            if coarse_range:
+                out["q_src"], out["q_ref"] = (b.download((nf, h // 4, w // 4), np.uint8) for b in q)
+            return out
+        finally:
+            for b in list(bufs.values()) + q + [cen]:
+                b.free()
+
+    def inter_encode_arrays(self, src, ref, bd, qindex, search_range=8, coarse_range=0):
         """tests: src / ref = (Y, U, V) with arrays [frames, h, w]; returns dict like the oracle's"""
         dt = np.uint8 if bd == 8 else np.uint16
         S = [np.ascontiguousarray(a, dt) for a in src]
@@ -612,6 +644,7 @@ class Context:
             bufs["lev_" + p] = self.alloc(S[i].size * 2)
         bufs["mvs"], bufs["skip"] = self.alloc(nf * nb * 4), self.alloc(nf * nb)
         job = InterJob(w, h, bd, nf, qindex, search_range, w, w // 2)
+        job.coarse_range = coarse_range
         for k, b in bufs.items():
             setattr(job, "d_" + k, b.ptr)
         self.inter_encode(job)

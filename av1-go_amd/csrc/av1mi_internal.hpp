@@ -120,8 +120,15 @@ struct InterLaunch {
   int w, h, stride_y, stride_uv, bd, nframes, dc_q, ac_q, range;
   int dc_quant, ac_quant;   // (1 << 16) / step (libaom quant_fp): computed once by the host, see block_code.hpp
   const void *ref_alt[3]; const uint8_t *ref_sel;   // optional: ref_sel[f * 3 + p] == 0 -> frame f predicts plane p from ref_alt[p]
+  const int16_t *centres = nullptr;                 // optional (k_me_int): a search centre (x, y) in luma samples per 64x64 tile and frame, multiples of 4
 };
 hipError_t launch_me_int(const InterLaunch &L, hipStream_t s);
+// the coarse search (me_coarse_kernels.hip): where its quarter planes and centres lie in a scratch area of `bytes` bytes (16-byte
+// aligned): the source's quarter planes at 0, the reference's at off_ref (qw x qh samples per frame, rows qs = qw rounded up to 4
+// bytes apart, frames stacked), the centres (an int16 pair per tile and frame) at off_centres
+struct MeLayout { int qw, qh, qs, tiles; size_t off_ref, off_centres, bytes; };
+MeLayout me_layout(int w, int h, int nframes);
+hipError_t launch_me_coarse(const InterLaunch &L, int coarse_range, void *scratch, hipStream_t s);
 
 // the input stage (input_kernels.hip): the planes of a batch in a wire / surface format (enum av1mi_input_format, not PLANAR) ->
 // planar planes; ny luma and nc chroma samples per plane.  The unit counts are filled in by the launcher.
@@ -189,6 +196,9 @@ int ctx_fail(av1mi_ctx *ctx, int code, const char *fmt, ...);
 // the per-kernel profile (av1mi_prof_*) for launches made outside capi.hip, on any stream of the context: an event pair around the
 // launch(es) while profiling is enabled, nothing otherwise
 struct ProfToken { hipEvent_t e0 = nullptr; int kind = 0; };
+// av1mi_inter_encode with the coarse search's scratch area given by the caller (the GOP session owns one); d_me is unused, and may be
+// null, when the job's coarse_range is 0
+int inter_encode_with(av1mi_ctx *ctx, const struct av1mi_inter_job *j, void *d_me);
 ProfToken ctx_prof_begin(av1mi_ctx *ctx, int kind, hipStream_t st);
 void ctx_prof_end(av1mi_ctx *ctx, const ProfToken &t, hipStream_t st);
 // ... and the same as a scope around the launch(es); st null = the context's stream

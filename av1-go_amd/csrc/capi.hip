@@ -24,6 +24,8 @@ struct av1mi_ctx {
   av1mi::ScalePlan *scale_plan = nullptr; // av1mi_scale_planes: the tables of the geometry it was last called with
   void *quality_scratch = nullptr;        // av1mi_quality_planes: the tiles' partial sums (grown on demand)
   size_t quality_scratch_bytes = 0;
+  void *me_scratch = nullptr;             // av1mi_inter_encode / av1mi_me_search with a coarse_range: quarter planes + centres (grown on demand)
+  size_t me_scratch_bytes = 0;
   // per-kernel profile: one event pair per launch while enabled
   bool prof_on = false;
   struct ProfRec { int kind; hipEvent_t e0, e1; };
@@ -180,6 +182,7 @@ void av1mi_close(av1mi_ctx *ctx) {
   if (ctx->back) { (void)hipStreamSynchronize(ctx->back); (void)hipStreamDestroy(ctx->back); }
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->quality_scratch) (void)hipFree(ctx->quality_scratch);
+  if (ctx->me_scratch) (void)hipFree(ctx->me_scratch);
   if (ctx->av1ent) av1mi::av1ent_free(ctx->av1ent);
   av1mi::scale_plan_destroy(ctx->scale_plan);
   for (auto &r : ctx->prof_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -274,7 +277,7 @@ int av1mi_prof_get(av1mi_ctx *ctx, int kind, int *launches, double *total_ms) {
 }
 const char *av1mi_kernel_kind_name(int kind) {
   static const char *n[AV1MI_K_KINDS] = { "fwd_txfm", "inv_txfm", "quantize", "dequantize", "intra_pred", "mc", "deblock",
-                                          "cdef", "loop_restoration", "intra_pipeline", "inter_pipeline", "misc", "entropy_code", "entropy_pack", "entropy_tokens", "me_integer", "entropy_chains", "input_convert", "quality" };
+                                          "cdef", "loop_restoration", "intra_pipeline", "inter_pipeline", "misc", "entropy_code", "entropy_pack", "entropy_tokens", "me_integer", "entropy_chains", "input_convert", "quality", "me_coarse" };
   return kind < 0 || kind >= AV1MI_K_KINDS ? "?" : n[kind];
 }
 
@@ -597,34 +600,105 @@ int av1mi_intra_encode(av1mi_ctx *ctx, const av1mi_intra_job *j) {
   return AV1MI_OK;
 }
 
-int av1mi_inter_encode(av1mi_ctx *ctx, const av1mi_inter_job *j) {
-  BIND(ctx);
+}  // extern "C"
+
+// the argument rules of an inter job and its launch description; search_only: the job of av1mi_me_search, which reads and writes luma
+// and vectors alone
+static int inter_launch(av1mi_ctx *ctx, const av1mi_inter_job *j, bool search_only, av1mi::InterLaunch *out) {
   if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
   if (int rc = check_bd(ctx, j->bit_depth)) return rc;
   if (j->width <= 0 || j->height <= 0 || (j->width & 7) || (j->height & 7) || j->width > 16384 || j->height > 16384)
     return fail(ctx, AV1MI_E_INVAL, "frame %dx%d must be a multiple of 8", j->width, j->height);
   if (j->nframes < 0 || j->nframes > 65535 || j->qindex < 0 || j->qindex > 255 || j->search_range < 0 || j->search_range > 15)
     return fail(ctx, AV1MI_E_INVAL, "bad nframes/qindex/search_range");
-  if (j->stride_y < j->width || j->stride_uv < j->width / 2 || (j->stride_y & 3) || (j->stride_uv & 3))
+  if (j->coarse_range < 0 || j->coarse_range > 64 || (j->coarse_range & 3))
+    return fail(ctx, AV1MI_E_INVAL, "coarse_range %d must be 0 or a multiple of 4 up to 64", j->coarse_range);
+  if (j->stride_y < j->width || (j->stride_y & 3) || (!search_only && (j->stride_uv < j->width / 2 || (j->stride_uv & 3))))
     return fail(ctx, AV1MI_E_INVAL, "bad strides %d/%d", j->stride_y, j->stride_uv);
-  const void *ptrs[] = { j->d_src_y, j->d_src_u, j->d_src_v, j->d_ref_y, j->d_ref_u, j->d_ref_v, j->d_rec_y, j->d_rec_u, j->d_rec_v,
-                         j->d_lev_y, j->d_lev_u, j->d_lev_v, j->d_mvs, j->d_skip };
-  for (const void *p : ptrs) if (!p || ((uintptr_t)p & 7)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned device pointer");
-  if (j->d_ref_y == j->d_rec_y || j->d_ref_u == j->d_rec_u || j->d_ref_v == j->d_rec_v) return fail(ctx, AV1MI_E_INVAL, "reference and reconstruction must differ");
-  av1mi::InterLaunch L;
+  if (search_only) {
+    const void *ptrs[] = { j->d_src_y, j->d_ref_y, j->d_mvs };
+    for (const void *p : ptrs) if (!p || ((uintptr_t)p & 7)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned device pointer");
+  } else {
+    const void *ptrs[] = { j->d_src_y, j->d_src_u, j->d_src_v, j->d_ref_y, j->d_ref_u, j->d_ref_v, j->d_rec_y, j->d_rec_u, j->d_rec_v,
+                           j->d_lev_y, j->d_lev_u, j->d_lev_v, j->d_mvs, j->d_skip };
+    for (const void *p : ptrs) if (!p || ((uintptr_t)p & 7)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned device pointer");
+    if (j->d_ref_y == j->d_rec_y || j->d_ref_u == j->d_rec_u || j->d_ref_v == j->d_rec_v) return fail(ctx, AV1MI_E_INVAL, "reference and reconstruction must differ");
+  }
+  av1mi::InterLaunch &L = *out;
   L.src[0] = j->d_src_y; L.src[1] = j->d_src_u; L.src[2] = j->d_src_v;
   L.ref[0] = j->d_ref_y; L.ref[1] = j->d_ref_u; L.ref[2] = j->d_ref_v;
   L.ref_alt[0] = j->d_ref_alt_y; L.ref_alt[1] = j->d_ref_alt_u; L.ref_alt[2] = j->d_ref_alt_v; L.ref_sel = j->d_ref_sel;
-  if (L.ref_sel && (!L.ref_alt[0] || !L.ref_alt[1] || !L.ref_alt[2])) return fail(ctx, AV1MI_E_INVAL, "d_ref_sel without d_ref_alt_*");
+  if (L.ref_sel && (!L.ref_alt[0] || (!search_only && (!L.ref_alt[1] || !L.ref_alt[2])))) return fail(ctx, AV1MI_E_INVAL, "d_ref_sel without d_ref_alt_*");
+  if (L.ref_sel && (((uintptr_t)L.ref_sel & 3) || ((uintptr_t)L.ref_alt[0] & 7))) return fail(ctx, AV1MI_E_INVAL, "misaligned d_ref_sel / d_ref_alt_y");
   L.rec[0] = j->d_rec_y; L.rec[1] = j->d_rec_u; L.rec[2] = j->d_rec_v;
   L.lev[0] = j->d_lev_y; L.lev[1] = j->d_lev_u; L.lev[2] = j->d_lev_v;
   L.mvs = j->d_mvs; L.skip = j->d_skip;
   L.w = j->width; L.h = j->height; L.stride_y = j->stride_y; L.stride_uv = j->stride_uv; L.bd = j->bit_depth; L.nframes = j->nframes;
   L.dc_q = av1mi_dc_q(j->qindex, j->bit_depth); L.ac_q = av1mi_ac_q(j->qindex, j->bit_depth); L.range = j->search_range;
   L.dc_quant = (1 << 16) / L.dc_q; L.ac_quant = (1 << 16) / L.ac_q;
+  L.centres = nullptr;
+  return AV1MI_OK;
+}
+// the context's own scratch area of the coarse search, large enough for L (hipFree waits for the launches that still read the old one)
+static int ensure_me_scratch(av1mi_ctx *ctx, const av1mi::InterLaunch &L) {
+  const size_t need = av1mi::me_layout(L.w, L.h, L.nframes).bytes;
+  if (ctx->me_scratch_bytes >= need) return AV1MI_OK;
+  if (ctx->me_scratch) (void)hipFree(ctx->me_scratch);
+  ctx->me_scratch = nullptr; ctx->me_scratch_bytes = 0;
+  HIP_TRY(ctx, hipMalloc(&ctx->me_scratch, need));
+  ctx->me_scratch_bytes = need;
+  return AV1MI_OK;
+}
+// coarse search (optional) + integer search of L; with a coarse search L.centres is set to the centres in d_me
+static int launch_search(av1mi_ctx *ctx, av1mi::InterLaunch &L, int coarse_range, void *d_me) {
+  if (coarse_range) {
+    if (!d_me || ((uintptr_t)d_me & 15)) return fail(ctx, AV1MI_E_INVAL, "coarse_range %d without a scratch area", coarse_range);
+    { ProfScope ps(ctx, AV1MI_K_ME_COARSE); HIP_TRY(ctx, av1mi::launch_me_coarse(L, coarse_range, d_me, ctx->stream)); }
+    L.centres = (const int16_t *)((const char *)d_me + av1mi::me_layout(L.w, L.h, L.nframes).off_centres);
+  }
   // one event pair per kernel, so that either can be the bench's roofline kernel and be matched with rocprofv3's per-kernel stats
   { ProfScope ps(ctx, AV1MI_K_ME_INT); HIP_TRY(ctx, av1mi::launch_me_int(L, ctx->stream)); }
-  { ProfScope ps(ctx, AV1MI_K_INTER_PIPE); HIP_TRY(ctx, av1mi::launch_inter_pipe(L, ctx->stream)); }
+  return AV1MI_OK;
+}
+
+namespace av1mi {
+int inter_encode_with(av1mi_ctx *ctx, const av1mi_inter_job *j, void *d_me) {
+  BIND(ctx);
+  InterLaunch L;
+  if (int rc = inter_launch(ctx, j, false, &L)) return rc;
+  if (int rc = launch_search(ctx, L, j->coarse_range, d_me)) return rc;
+  { ProfScope ps(ctx, AV1MI_K_INTER_PIPE); HIP_TRY(ctx, launch_inter_pipe(L, ctx->stream)); }
+  return AV1MI_OK;
+}
+}  // namespace av1mi
+
+extern "C" {
+
+int av1mi_inter_encode(av1mi_ctx *ctx, const av1mi_inter_job *j) {
+  BIND(ctx);
+  av1mi::InterLaunch L;
+  if (int rc = inter_launch(ctx, j, false, &L)) return rc;
+  if (j->coarse_range) if (int rc = ensure_me_scratch(ctx, L)) return rc;
+  return av1mi::inter_encode_with(ctx, j, j->coarse_range ? ctx->me_scratch : nullptr);
+}
+
+int av1mi_me_search(av1mi_ctx *ctx, const av1mi_inter_job *j, uint8_t *d_q_src, uint8_t *d_q_ref, int16_t *d_centres) {
+  BIND(ctx);
+  av1mi::InterLaunch L;
+  if (int rc = inter_launch(ctx, j, true, &L)) return rc;
+  if (!d_centres || ((uintptr_t)d_centres & 3)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned d_centres");
+  if (L.nframes == 0) return AV1MI_OK;
+  const av1mi::MeLayout M = av1mi::me_layout(L.w, L.h, L.nframes);
+  if (j->coarse_range) if (int rc = ensure_me_scratch(ctx, L)) return rc;
+  if (int rc = launch_search(ctx, L, j->coarse_range, ctx->me_scratch)) return rc;
+  const size_t cbytes = (size_t)M.tiles * L.nframes * 4;
+  if (!j->coarse_range) { HIP_TRY(ctx, hipMemsetAsync(d_centres, 0, cbytes, ctx->stream)); return AV1MI_OK; }
+  const char *sc = (const char *)ctx->me_scratch;
+  HIP_TRY(ctx, hipMemcpyAsync(d_centres, sc + M.off_centres, cbytes, hipMemcpyDeviceToDevice, ctx->stream));
+  // the planes without the row padding of the scratch area
+  uint8_t *dst[2] = { d_q_src, d_q_ref };
+  for (int k = 0; k < 2; k++)
+    if (dst[k]) HIP_TRY(ctx, hipMemcpy2DAsync(dst[k], (size_t)M.qw, sc + (k ? M.off_ref : 0), (size_t)M.qs, (size_t)M.qw, (size_t)M.qh * L.nframes, hipMemcpyDeviceToDevice, ctx->stream));
   return AV1MI_OK;
 }
 

@@ -7,7 +7,7 @@
 // of submit_batch, in this order on every stream:
 //   feed_source       up:   wait slot.filters_done (the kernels that last read this slot's source) -> H2D of the fed buffers -> uploaded
 //                     main: wait uploaded -> [k_input_convert] -> [k_scale]
-//   code_blocks       main: k_intra_pipe | k_me_int + k_inter_pipe -> kernel_done
+//   code_blocks       main: k_intra_pipe | [k_me_down + k_me_coarse] + k_me_int + k_inter_pipe -> kernel_done
 //   download_symbols  down: wait kernel_done -> D2H of the symbols into pinned memory
 //   loop_filters      main: deblock x3, CDEF, LR x3 + decision -> reference -> filters_done;  down: the decision -> downloaded
 //   measure_quality   main: (quality_stats) k_quality_tiles + k_quality_sum, the records written into the slot's pinned memory -> quality_done
@@ -120,6 +120,7 @@ struct av1mi_gop {
   int key_modes_band = 0, key_modes_stride = 0;  // mode bytes per segment: the 32x32 blocks, then (from key_modes_band) the 8x8 blocks of the last rows
   void *d_cdef_sb[2] = {}, *d_lr[2] = {}, *d_zero_skip = nullptr;
   void *d_lr_scratch = nullptr;                // the restoration decision's partial sums (three planes)
+  void *d_me = nullptr;                        // coarse_range: the coarse search's quarter planes and centres of one batch (single: the chain is serial in t)
   void *d_quality_scratch = nullptr;           // quality_stats: the tiles' partial sums of one batch (the main stream orders its users)
   int vw = 0, vh = 0;                          // the true frame size (== the coded size unless cfg.visible_* say otherwise)
   int last = 0;                                // slot of the most recent batch (its d_lr_on selects the next batch's references)
@@ -272,6 +273,8 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
     return WHY("key_block_size 32 needs a width that is a multiple of 32");
   if (c->gpu_entropy && (c->width > 4096 || c->height > 4096)) return WHY("the AV1 tile coder takes frames up to 4096x4096");
   if ((size_t)c->height * c->segments > 65535u * 8u) return WHY("segments x height too large for one launch");
+  if (c->coarse_range < 0 || c->coarse_range > 64 || (c->coarse_range & 3))
+    return WHY("coarse_range %d must be 0 (off) or a multiple of 4 up to 64", c->coarse_range);
   if (c->quality_stats && ((c->visible_width ? c->visible_width : c->width) < 16 || (c->visible_height ? c->visible_height : c->height) < 16))
     return WHY("quality_stats needs a true luma size of at least 16x16");
   return nullptr;
@@ -318,6 +321,7 @@ int setup(av1mi_gop *g) {
   for (int p = 0; p < 3; p++)      // reconstruction, deblocked, CDEF and reference planes: single (the chain is serial in t)
     for (void **d : { &g->d_rec[p], &g->d_dbl[p], &g->d_cdef[p], &g->d_ref[p] }) G_TRY(dev_alloc(g, d, g->plane[p].bytes));
   G_TRY(dev_alloc(g, &g->d_lr_scratch, av1mi_lr_yuv_decide_scratch_bytes(h, S)));
+  if (c.coarse_range) G_TRY(dev_alloc(g, &g->d_me, av1mi::me_layout(w, h, S).bytes));
   if (c.quality_stats) G_TRY(dev_alloc(g, &g->d_quality_scratch, av1mi::quality_scratch_bytes(c.bit_depth, g->vw, g->vh, S)));
   G_TRY(dev_alloc(g, &g->d_zero_skip, g->nb));
   G_TRY(av1mi_memset(g->ctx, g->d_zero_skip, 0, g->nb));
@@ -457,7 +461,10 @@ static int code_blocks(av1mi_gop *g, Slot &s, int frame_type, const void *const 
     // per segment and plane: the restored plane of the previous frame, or its CDEF output where restoration was switched off
     j.d_ref_alt_y = g->d_cdef[0]; j.d_ref_alt_u = g->d_cdef[1]; j.d_ref_alt_v = g->d_cdef[2];
     j.d_ref_sel = (const uint8_t *)g->slot[g->last].d_lr_on;
-    G_TRY(av1mi_inter_encode(g->ctx, &j));
+    // coarse_range: k_me_down + k_me_coarse at the head of the batch, in the session's own scratch area (the previous batch's k_me_int,
+    // its last reader, ran on this stream)
+    j.coarse_range = c.coarse_range;
+    G_TRY(av1mi::inter_encode_with(g->ctx, &j, g->d_me));
   }
   G_HIP(hipEventRecord(s.kernel_done, av1mi::ctx_stream(g->ctx)));
   s.kernel_pending = true;

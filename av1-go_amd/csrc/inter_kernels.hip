@@ -50,7 +50,10 @@ __device__ __forceinline__ const void *ref_plane(const InterLaunch &L, int f, in
 // aligned dwords) and issues two QSADs with the row's two source dwords, which all lanes read from the same LDS address.
 // RC: the search range as a compile-time constant (0 = take L.range at run time): with the default +-8 every quotient, item
 // count and validity bound below is a constant.
-template <typename Pix, int RC>
+// CEN: the search runs around a centre per tile and frame (L.centres, the coarse search of me_coarse_kernels.hip; multiples of 4, so
+// the window's groups of four stay aligned): the window is staged around tile origin + centre, the displacements d rank as without
+// one ((0, 0) = the centre itself first) and the vector written is centre + d.  Without it the kernel is the one it was.
+template <typename Pix, int RC, bool CEN>
 __global__ __launch_bounds__(256) void k_me_int(InterLaunch L) {
   // window row stride in bytes: 41 dwords.  The window reads are ds_read2_b32 / ds_read_b32 (32 banks per 32-lane group); a lane
   // reads dword (by 8 + 3 dp + r) 41 + 2 bx + g (+ 0, 1, 2): 3 x 41 = 27 mod 32, so the six dy triples of a block start 5 banks
@@ -69,6 +72,11 @@ __global__ __launch_bounds__(256) void k_me_int(InterLaunch L) {
   const int sbw = (L.w + 63) / 64;
   const Tile3 tl = xcd_tile(sbw, (L.h + 63) / 64, L.nframes);
   const int f = tl.z, sby = tl.y, sbx = tl.x;
+  int cx = 0, cy = 0;
+  if constexpr (CEN) {      // (uniform in the workgroup: a scalar load of the pair)
+    const uint32_t c = reinterpret_cast<const uint32_t *>(L.centres)[(f * ((L.h + 63) / 64) + sby) * sbw + sbx];
+    cx = (int16_t)(c & 0xffffu); cy = (int16_t)(c >> 16);
+  }
   const Pix *src = reinterpret_cast<const Pix *>(L.src[0]) + (size_t)f * L.h * L.stride_y;
   const Pix *ref = reinterpret_cast<const Pix *>(ref_plane(L, f, 0)) + (size_t)f * L.h * L.stride_y;
   // staging, four samples per lane per step (the window starts on a 4-sample boundary and its width is a multiple of 4);
@@ -76,7 +84,7 @@ __global__ __launch_bounds__(256) void k_me_int(InterLaunch L) {
   const int wg = WDX >> 2;
   for (int i = tid; i < WDY * wg; i += 256) {
     const int r = i / wg, c = (i - r * wg) * 4;
-    const int fy = min(max(sby * 64 - R + r, 0), L.h - 1), fx = sbx * 64 - R4 + c;
+    const int fy = min(max(sby * 64 - R + r + cy, 0), L.h - 1), fx = sbx * 64 - R4 + c + cx;
     const Pix *row = ref + row_off(fy, L.stride_y);
     uint32_t u;
     if (fx >= 0 && fx + 3 < L.w) {
@@ -205,8 +213,8 @@ __global__ __launch_bounds__(256) void k_me_int(InterLaunch L) {
     if (fbx < bw && fby < bh) {
       const int rank = s_best[tid] & 0xFFFF;
       const int dy = rank ? (rank - 1) / NC - R : 0, dx = rank ? (rank - 1) % NC - R : 0;
-      mvs[((size_t)fby * bw + fbx) * 2] = (int16_t)(dx * 8);
-      mvs[((size_t)fby * bw + fbx) * 2 + 1] = (int16_t)(dy * 8);
+      mvs[((size_t)fby * bw + fbx) * 2] = (int16_t)((cx + dx) * 8);
+      mvs[((size_t)fby * bw + fbx) * 2 + 1] = (int16_t)((cy + dy) * 8);
     }
   }
 }
@@ -682,12 +690,20 @@ hipError_t launch_me_int(const InterLaunch &L, hipStream_t s) {
   if (L.nframes <= 0) return hipSuccess;
   const int sbs = ((L.w + 63) / 64) * ((L.h + 63) / 64);
   const dim3 g1((unsigned)(sbs * L.nframes));   // 1-D: the kernel orders the tiles (xcd_tile)
-  if (L.range == 8) {
-    if (L.bd == 8) hipLaunchKernelGGL((k_me_int<uint8_t, 8>), g1, dim3(256), 0, s, L);
-    else hipLaunchKernelGGL((k_me_int<uint16_t, 8>), g1, dim3(256), 0, s, L);
+  if (L.centres) {
+    if (L.range == 8) {
+      if (L.bd == 8) hipLaunchKernelGGL((k_me_int<uint8_t, 8, true>), g1, dim3(256), 0, s, L);
+      else hipLaunchKernelGGL((k_me_int<uint16_t, 8, true>), g1, dim3(256), 0, s, L);
+    } else {
+      if (L.bd == 8) hipLaunchKernelGGL((k_me_int<uint8_t, 0, true>), g1, dim3(256), 0, s, L);
+      else hipLaunchKernelGGL((k_me_int<uint16_t, 0, true>), g1, dim3(256), 0, s, L);
+    }
+  } else if (L.range == 8) {
+    if (L.bd == 8) hipLaunchKernelGGL((k_me_int<uint8_t, 8, false>), g1, dim3(256), 0, s, L);
+    else hipLaunchKernelGGL((k_me_int<uint16_t, 8, false>), g1, dim3(256), 0, s, L);
   } else {
-    if (L.bd == 8) hipLaunchKernelGGL((k_me_int<uint8_t, 0>), g1, dim3(256), 0, s, L);
-    else hipLaunchKernelGGL((k_me_int<uint16_t, 0>), g1, dim3(256), 0, s, L);
+    if (L.bd == 8) hipLaunchKernelGGL((k_me_int<uint8_t, 0, false>), g1, dim3(256), 0, s, L);
+    else hipLaunchKernelGGL((k_me_int<uint16_t, 0, false>), g1, dim3(256), 0, s, L);
   }
   return hipGetLastError();
 }

@@ -176,6 +176,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
     if (scaling) { cfg.source_width = y.w; cfg.source_height = y.h; }
     cfg.width = w; cfg.height = h; cfg.bit_depth = y.bd; cfg.base_q_idx = job.quality < 1 ? 1 : job.quality; cfg.gop_length = G; cfg.segments = S;
     cfg.search_range = 8;
+    cfg.coarse_range = job.me_range;      // -av1mi_me_range: the coarse search in front of it
     cfg.gpu_entropy = job.gpu_entropy ? 1 : 0;
     // -av1mi_stats / -av1mi_min_psnr: the session measures every batch on the GPU; the records arrive with the collected batch
     const bool measure = !job.stats_path.empty() || job.min_psnr > 0;

@@ -42,6 +42,8 @@ struct TranscodeConfig {           // daemon.go:185-188; Device is this backend'
   // on the GPU while coding, must reach this bound; 0 = off.  A file below it is treated as one the size gate refuses: skipped, why-file,
   // skip marker, output removed, source untouched.
   double MinPSNR = 0;
+  // The wide-range motion search (-av1mi_me_range, av1mi_gop_config.coarse_range): 0 = off, else a multiple of 4 up to 64.
+  int MeRange = 0;
 };
 
 // daemon.go:57-182.  Returns "" where the reference returns nil, else the error text; job.Status / job.Reason are

@@ -1,10 +1,11 @@
 // av1mi_transcode — CLI with the reference's process contract (exit code, stderr text, output file last):
 //   av1mi_transcode [ffmpeg-style args] -i in.y4m [-global_quality:v:0 Q] [-g GOP] [-vf:v:0 CHAIN] [-av1mi_scale WxH]
-//                   [-av1mi_stats FILE] [-av1mi_min_psnr DB] out.av1-tmp.mkv
+//                   [-av1mi_stats FILE] [-av1mi_min_psnr DB] [-av1mi_me_range N] out.av1-tmp.mkv
 //                   (-av1mi_stats: per-frame PSNR / SSIM measured on the GPU; -av1mi_min_psnr: fail with exit code 3 below that luma PSNR)
+//                   (-av1mi_me_range: 0, or a multiple of 4 up to 64: the P frames' motion search follows N + 8 samples per frame)
 //                   (CHAIN: the reference's scale filters, evaluated on the source's size and sample aspect ratio and applied on the GPU;
 //                   -av1mi_scale: an explicit output size, wins over the chain; any other filter is refused)
-//   av1mi_transcode --job in.y4m [--ratio 0.9] [--state DIR] [--wait S] [--replace-source 1] [--min-psnr DB]   (the ProcessJob lifecycle;
+//   av1mi_transcode --job in.y4m [--ratio 0.9] [--state DIR] [--wait S] [--replace-source 1] [--min-psnr DB] [--me-range N]   (the ProcessJob lifecycle;
 //                   the source is only replaced on request: the output is video-only)
 #include <cstdio>
 #include <cstdlib>
@@ -28,6 +29,7 @@ int main(int argc, char **argv) {
       else if (!strcmp(argv[i], "--wait")) cfg.StableWaitSeconds = atoi(argv[i + 1]);
       else if (!strcmp(argv[i], "--replace-source")) { cfg.ReplaceSource = atoi(argv[i + 1]) != 0; }
       else if (!strcmp(argv[i], "--min-psnr")) cfg.MinPSNR = atof(argv[i + 1]);
+      else if (!strcmp(argv[i], "--me-range")) cfg.MeRange = atoi(argv[i + 1]);
     }
     struct stat st;
     if (!stat(job.SourcePath.c_str(), &st)) job.OriginalSize = st.st_size;
@@ -36,7 +38,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "job %s: %s%s%s\n", job.Status.c_str(), job.Reason.c_str(), e.empty() ? "" : " | ", e.c_str());
     return e.empty() ? 0 : 1;
   }
-  if (argc >= 3 && !strcmp(argv[1], "--jobs")) {   // --jobs a.y4m b.y4m ... [--gpus N] [--workers W] [--ratio R] [--state DIR] [--min-psnr DB]
+  if (argc >= 3 && !strcmp(argv[1], "--jobs")) {   // --jobs a.y4m b.y4m ... [--gpus N] [--workers W] [--ratio R] [--state DIR] [--min-psnr DB] [--me-range N]
     std::vector<Job> jobs;
     TranscodeConfig cfg; cfg.StableWaitSeconds = 0;
     int gpus = 1, workers = 0;
@@ -46,6 +48,7 @@ int main(int argc, char **argv) {
       else if (!strcmp(argv[i], "--ratio") && i + 1 < argc) cfg.MaxSizeRatio = atof(argv[++i]);
       else if (!strcmp(argv[i], "--state") && i + 1 < argc) cfg.JobStateDir = argv[++i];
       else if (!strcmp(argv[i], "--min-psnr") && i + 1 < argc) cfg.MinPSNR = atof(argv[++i]);
+      else if (!strcmp(argv[i], "--me-range") && i + 1 < argc) cfg.MeRange = atoi(argv[++i]);
       else {
         Job j; j.ID = "job" + std::to_string(jobs.size()); j.SourcePath = argv[i];
         struct stat st;

@@ -117,6 +117,9 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
     else if (args[i] == "-av1mi_key_block_size") job->key_block_size = std::atoi(args[i + 1].c_str());
     else if (args[i] == "-av1mi_pack10") job->pack10 = std::atoi(args[i + 1].c_str());
     else if (args[i] == "-av1mi_stats") job->stats_path = args[i + 1];
+    else if (args[i] == "-av1mi_me_range") {
+      if (!plain_int(args[i + 1], &job->me_range) || job->me_range > 64 || (job->me_range & 3)) { if (err) *err = "Invalid argument: -av1mi_me_range takes 0 or a multiple of 4 up to 64, not " + args[i + 1]; return false; }
+    }
     else if (args[i] == "-av1mi_min_psnr") {
       char *end = nullptr;
       job->min_psnr = std::strtod(args[i + 1].c_str(), &end);

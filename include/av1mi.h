@@ -83,7 +83,7 @@ int av1mi_timer_end(av1mi_ctx *ctx, float *elapsed_ms);
 enum av1mi_kernel_kind {
   AV1MI_K_FWD_TXFM, AV1MI_K_INV_TXFM, AV1MI_K_QUANT, AV1MI_K_DEQUANT, AV1MI_K_INTRA_PRED, AV1MI_K_MC,
   AV1MI_K_DEBLOCK, AV1MI_K_CDEF, AV1MI_K_LR, AV1MI_K_INTRA_PIPE, AV1MI_K_INTER_PIPE, AV1MI_K_MISC, AV1MI_K_ENTROPY,
-  AV1MI_K_ENTROPY_PACK, AV1MI_K_ENTROPY_TOKENS, AV1MI_K_ME_INT, AV1MI_K_ENTROPY_CHAINS, AV1MI_K_INPUT, AV1MI_K_QUALITY, AV1MI_K_KINDS
+  AV1MI_K_ENTROPY_PACK, AV1MI_K_ENTROPY_TOKENS, AV1MI_K_ME_INT, AV1MI_K_ENTROPY_CHAINS, AV1MI_K_INPUT, AV1MI_K_QUALITY, AV1MI_K_ME_COARSE, AV1MI_K_KINDS
 };
 int av1mi_prof_enable(av1mi_ctx *ctx, int on);
 int av1mi_prof_reset(av1mi_ctx *ctx);
@@ -287,8 +287,38 @@ typedef struct av1mi_inter_job {
    * instead of d_ref_* (the restored planes).  d_ref_sel: 4-byte aligned, allocated up to a multiple of 4 bytes (read as dwords). */
   const void *d_ref_alt_y, *d_ref_alt_u, *d_ref_alt_v;
   const uint8_t *d_ref_sel;
+  int coarse_range;     /* 0 (default): the integer search runs around the zero vector.  Otherwise a multiple of 4 up to 64: the coarse search
+                           ("motion search" below) gives every 64x64 tile a centre first; its quarter planes and centres live in the context
+                           (allocated at the first such job, reused and grown afterwards) */
 } av1mi_inter_job;
 int av1mi_inter_encode(av1mi_ctx *ctx, const av1mi_inter_job *job);
+
+/* ---- motion search: the optional coarse search in front of the integer search (av1-go_amd/csrc/me_coarse_kernels.hip), and the integer
+ * search around its centres (k_me_int, inter_kernels.hip).  Integer arithmetic, bit exact by definition; P = a luma plane of one
+ * frame, w x h (multiples of 8).
+ *   8-bit view     m8(v) = v >> (bit_depth - 8): what the integer search has always compared.
+ *   quarter plane  Q[y][x] = (sum over i, j < 4 of m8(P[4 y + i][4 x + j]) + 8) >> 4, one byte per sample, (w / 4) x (h / 4).  Built for
+ *                  the source luma and for the luma plane the frame predicts from (d_ref_y, or d_ref_alt_y where d_ref_sel[f * 3] == 0).
+ *   coarse search  per 64x64 tile (tx, ty) of a frame, Rc = coarse_range / 4: the 16 x 16 block of the SOURCE's quarter plane at
+ *                  (16 tx, 16 ty) against the reference's quarter plane displaced by every (dx, dy) in [-Rc, Rc]^2; score = the sum of
+ *                  absolute differences over all 256 samples; every coordinate of either plane is clamped into [0, w / 4 - 1] x
+ *                  [0, h / 4 - 1] (edge replication; this also defines partial tiles).  The winner is the minimum of
+ *                  (SAD << 16) | rank, rank = 0 for (0, 0), else 1 + (dy + Rc) (2 Rc + 1) + dx + Rc: ties go to the zero displacement,
+ *                  then to raster order.  SAD <= 65 280 and rank <= 1 089: both halves fit.  Centre of the tile = (4 dx, 4 dy) luma samples.
+ *   integer search per 8x8 block at (x, y), c = the centre of its tile, R = search_range: every d in [-R, R]^2, score = the sum over the
+ *                  block's EVEN rows of |m8(S[y + r][x + k]) - m8(Ref[clamp(y + r + c.y + d.y)][clamp(x + k + c.x + d.x)])| (clamped into
+ *                  the plane), winner = the minimum of (SAD << 16) | rank with rank = 0 for d = (0, 0) — the centre itself —, else
+ *                  1 + (d.y + R) (2 R + 1) + d.x + R.  The vector handed to the refinement is (c + d) * 8, in 1/8 luma samples.
+ *                  Without a coarse search c = (0, 0): the search as it has always been.
+ *   range          coarse_range is 0 (off) or a multiple of 4 up to 64; the reach is coarse_range + search_range <= 79 samples: vectors
+ *                  stay below 2^10 eighth samples, far inside AV1's +-2^14 and int16. */
+/* The search alone, without coding — the per-stage entry the parity tests use.  `job` as for av1mi_inter_encode, of which only the
+ * geometry, bit_depth, nframes, search_range, coarse_range, stride_y, d_src_y, d_ref_y, d_ref_alt_y, d_ref_sel and d_mvs are read
+ * (the other pointers may be null).  Outputs, all in device memory: d_mvs receives the INTEGER vectors ((c + d) * 8 per block);
+ * d_centres (nframes * tiles int16 pairs (x, y), tiles = ceil(w / 64) * ceil(h / 64), raster per frame; 4-byte aligned) the centres —
+ * zeros when coarse_range is 0 —; d_q_src / d_q_ref (nframes * (w / 4) * (h / 4) bytes each, rows w / 4 bytes apart, frames stacked;
+ * either may be null; untouched when coarse_range is 0) the quarter planes.  Asynchronous on the context's stream. */
+int av1mi_me_search(av1mi_ctx *ctx, const av1mi_inter_job *job, uint8_t *d_q_src, uint8_t *d_q_ref, int16_t *d_centres);
 
 /* ---- K9: the AV1 tile entropy coder on the GPU (av1-go_amd/csrc/av1_entropy_kernels.hip).  Codes the outputs
  * of av1mi_intra_encode (key = 1) or av1mi_inter_encode (key = 0) of `nframes` stacked frames in AV1's tile syntax — the tool
@@ -471,6 +501,11 @@ typedef struct av1mi_gop_config {
    * records.  0 (default): nothing is launched or allocated.  Needs a true luma size of at least 16 x 16.  Changes nothing about what
    * is coded. */
   int quality_stats;
+  /* 0 (default): P frames search +-search_range around the zero vector, as ever; nothing else is allocated or launched.  A multiple of
+   * 4 up to 64: the coarse search ("motion search" above; two launches at the head of every P batch, k_me_down + k_me_coarse) gives
+   * every 64x64 tile of every segment a centre for the integer search: vectors reach coarse_range + search_range samples.  The
+   * quarter planes and centres exist once per session. */
+  int coarse_range;
 } av1mi_gop_config;
 
 /* Frame-header parameters chosen by the session's policy for one frame (non-normative encoder choices; the bitstream carries
