@@ -90,7 +90,8 @@ class GopConfig(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("bit_depth", C.c_int), ("base_q_idx", C.c_int), ("gop_length", C.c_int),
                 ("segments", C.c_int), ("search_range", C.c_int), ("gpu_entropy", C.c_int), ("visible_width", C.c_int),
                 ("visible_height", C.c_int), ("coder_streams", C.c_int), ("key_block_size", C.c_int), ("input_format", C.c_int), ("source_width", C.c_int),
-                ("source_height", C.c_int), ("quality_stats", C.c_int), ("coarse_range", C.c_int)]
+                ("source_height", C.c_int), ("quality_stats", C.c_int), ("coarse_range", C.c_int), ("source_chroma", C.c_int),
+                ("source_bit_depth", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -144,6 +145,24 @@ def input_plane_bytes(fmt, bit_depth, plane, width, rows):
     return int(lib.av1mi_input_plane_bytes(int(fmt), int(bit_depth), int(plane), int(width), int(rows)))
 
 
+CHROMA_420, CHROMA_422, CHROMA_444, CHROMA_400 = 0, 1, 2, 3      # enum av1mi_source_chroma
+
+
+def source_plane_bytes(chroma, source_bit_depth, plane, width, rows):
+    """bytes of one plane of a source stacked to `rows` luma rows in a chroma layout (av1mi_source_plane_bytes); 0 = invalid, or the
+    chroma planes of a grey source; no GPU needed"""
+    lib = load()
+    lib.av1mi_source_plane_bytes.restype = C.c_size_t
+    lib.av1mi_source_plane_bytes.argtypes = [C.c_int] * 5
+    return int(lib.av1mi_source_plane_bytes(int(chroma), int(source_bit_depth), int(plane), int(width), int(rows)))
+
+
+def source_plane_shapes(chroma, width, rows):
+    """[rows, width] of the three planes of a source in a chroma layout, buffers of width x rows luma samples; None = no such plane"""
+    c = {CHROMA_420: (rows // 2, width // 2), CHROMA_422: (rows, width // 2), CHROMA_444: (rows, width), CHROMA_400: None}[chroma]
+    return [(rows, width), c, c]
+
+
 def input_pack(fmt, bit_depth, y, u, v, out=None):
     """planar planes (y [rows, width], u / v half size; uint8 or uint16) -> the format's planes as uint8 arrays (av1mi_input_pack, host
     code); out: optional (buffer, byte offset) per plane to pack into instead of fresh arrays"""
@@ -187,18 +206,21 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
         they are to be scaled to the coded frame (av1mi_gop_config.source_width): the input buffers then have that size rounded up to 8;
         quality_stats: 1 = every batch is measured on the GPU, collect()["quality"] holds the records (av1mi_gop_config.quality_stats);
-        coarse_range: 0, or a multiple of 4 up to 64: P frames search around a coarse centre per 64x64 tile (av1mi_gop_config.coarse_range)"""
+        coarse_range: 0, or a multiple of 4 up to 64: P frames search around a coarse centre per 64x64 tile (av1mi_gop_config.coarse_range);
+        source_chroma / source_bit_depth: CHROMA_* and 8 / 10 / 12 of the source the session is fed (av1mi_gop_config.source_chroma): the
+        input buffers then have that layout (source_plane_shapes), and no chroma planes for a grey source"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
         sw, sh = source if source is not None else (0, 0)
         self.cfg = GopConfig(width, height, bit_depth, base_q_idx, gop_length, segments, search_range, gpu_entropy, vw, vh, coder_streams, key_block_size, input_format,
-                             sw, sh, int(quality_stats), int(coarse_range))
+                             sw, sh, int(quality_stats), int(coarse_range), int(source_chroma), int(source_bit_depth))
+        self.source_chroma, self.src_bd = int(source_chroma), int(source_bit_depth) or bit_depth
         self.in_w, self.in_h = ((sw + 7) & ~7, (sh + 7) & ~7) if source is not None else (width, height)      # geometry of the input buffers
         self.input_format = input_format
         self.g = C.c_void_p()
@@ -215,6 +237,9 @@ class GopSession:
         y, u, v = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self.ctx._chk(self.ctx.lib.av1mi_gop_acquire_input(self.g, C.byref(y), C.byref(u), C.byref(v)))
         S, w, h = self.segments, self.in_w, self.in_h
+        if self.source_chroma != CHROMA_420 or self.src_bd != self.bd:      # the source's layout; a grey source has a luma plane only
+            dt = np.uint8 if self.src_bd == 8 else np.uint16
+            return tuple(_view(ptr.value, shp, dt) for ptr, shp in zip((y, u, v), source_plane_shapes(self.source_chroma, w, S * h)) if shp)
         if self.input_format != INPUT_PLANAR:      # the session's format: flat byte views of av1mi_input_plane_bytes each (no third plane when semi-planar)
             n = [input_plane_bytes(self.input_format, self.bd, p, w, S * h) for p in range(3)]
             return tuple(_view(ptr.value, (k,), np.uint8) for ptr, k in zip((y, u, v), n) if k)
@@ -224,10 +249,10 @@ class GopSession:
         self.ctx._chk(self.ctx.lib.av1mi_gop_submit(self.g, int(frame_type)))
 
     def submit_device(self, d_y, d_u, d_v=None, frame_type=-1):
-        """a batch whose source planes (DevBuf, in the session's input format; d_v None for P010 / NV12) are already in device
+        """a batch whose source planes (DevBuf, in the session's input format; d_v None for P010 / NV12, d_u and d_v None for a grey source) are already in device
         memory: no upload (av1mi_gop_submit_device)"""
         self.ctx.lib.av1mi_gop_submit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        self.ctx._chk(self.ctx.lib.av1mi_gop_submit_device(self.g, d_y.ptr, d_u.ptr, d_v.ptr if d_v is not None else None, int(frame_type)))
+        self.ctx._chk(self.ctx.lib.av1mi_gop_submit_device(self.g, d_y.ptr, d_u.ptr if d_u is not None else None, d_v.ptr if d_v is not None else None, int(frame_type)))
 
     def pending(self):
         return self.ctx.lib.av1mi_gop_pending(self.g)
@@ -468,6 +493,13 @@ class Context:
         self.lib.av1mi_input_convert.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 6
         i = [b.ptr for b in d_in] + [None] * (3 - len(d_in))
         self._chk(self.lib.av1mi_input_convert(self.h, int(fmt), int(bit_depth), int(width), int(rows), *i, *[b.ptr for b in d_out]))
+
+    def chroma_convert(self, chroma, source_bit_depth, bit_depth, width, height, frames, d_in, d_out):
+        """d_in: the source's planes (3 DevBuf or None) of `frames` stacked frames of TRUE size width x height in a chroma layout, d_out:
+        the 4:2:0 planes Y, U, V (DevBuf; Y may be None where the depths are equal); one launch, asynchronous (av1mi_chroma_convert)"""
+        self.lib.av1mi_chroma_convert.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 6
+        ptr = [b.ptr if b is not None else None for b in list(d_in) + list(d_out)]
+        self._chk(self.lib.av1mi_chroma_convert(self.h, int(chroma), int(source_bit_depth), int(bit_depth), int(width), int(height), int(frames), *ptr))
 
     def scale_planes(self, bit_depth, src_w, src_h, dst_w, dst_h, frames, d_src, d_dst):
         """d_src: planar Y, U, V (DevBuf) of `frames` stacked frames of true size src_w x src_h in buffers of that size rounded up to 8;

@@ -138,6 +138,15 @@ struct InputLaunch {
   size_t units, units_y, units_c;
 };
 hipError_t launch_input_convert(int format, InputLaunch L, hipStream_t s);
+// the chroma stage (input_kernels.hip, include/av1mi.h "chroma formats"): `frames` stacked frames of TRUE luma size w x h in the
+// source's layout -> 4:2:0 planes at bit depth bd; in[0] / out[0] are unused where src_bd == bd (the luma plane is not converted)
+struct ChromaLaunch {
+  const void *in[3]; void *out[3];
+  int chroma, src_bd, bd, w, h, frames;
+};
+// the argument rules shared by av1mi_chroma_convert and the session: null = fine, else the reason
+const char *chroma_format_error(int chroma, int src_bd, int bd);
+hipError_t launch_chroma_convert(const ChromaLaunch &L, hipStream_t s);
 hipError_t launch_inter_pipe(const InterLaunch &L, hipStream_t s);
 
 // the resampler of the input stage (scale_kernels.hip): a plan holds the device tables of one geometry (true luma size of the source ->

@@ -521,6 +521,28 @@ int av1mi_input_convert(av1mi_ctx *ctx, int format, int bit_depth, int width, in
   return AV1MI_OK;
 }
 
+int av1mi_chroma_convert(av1mi_ctx *ctx, int source_chroma, int source_bit_depth, int bit_depth, int width, int height, int frames,
+                         const void *d_in0, const void *d_in1, const void *d_in2, void *d_y, void *d_u, void *d_v) {
+  BIND(ctx);
+  if (const char *why = av1mi::chroma_format_error(source_chroma, source_bit_depth, bit_depth))
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_chroma_convert (chroma %d, %d -> %d bits): %s", source_chroma, source_bit_depth, bit_depth, why);
+  if (width < 8 || height < 8 || width > 16384 || height > 16384) return fail(ctx, AV1MI_E_INVAL, "av1mi_chroma_convert: frame %dx%d out of range (8 .. 16384)", width, height);
+  if (frames < 1 || (size_t)frames * (size_t)(height + 7) > 65535u * 32u) return fail(ctx, AV1MI_E_INVAL, "frames %d out of range", frames);
+  const bool luma = source_bit_depth != bit_depth, grey = source_chroma == AV1MI_CHROMA_400;
+  if (!luma) { d_in0 = nullptr; d_y = nullptr; }
+  if (grey) d_in1 = d_in2 = nullptr;
+  const void *need[] = { luma ? d_in0 : ctx, grey ? ctx : d_in1, grey ? ctx : d_in2, luma ? d_y : ctx, d_u, d_v };
+  for (const void *p : need) if (!p) return fail(ctx, AV1MI_E_INVAL, "null device pointer");
+  const void *ptrs[] = { d_in0, d_in1, d_in2, d_y, d_u, d_v };
+  for (const void *p : ptrs) if ((uintptr_t)p & 15) return fail(ctx, AV1MI_E_INVAL, "misaligned device pointer (16 bytes)");
+  av1mi::ChromaLaunch L;
+  L.in[0] = d_in0; L.in[1] = d_in1; L.in[2] = d_in2; L.out[0] = d_y; L.out[1] = d_u; L.out[2] = d_v;
+  L.chroma = source_chroma; L.src_bd = source_bit_depth; L.bd = bit_depth; L.w = width; L.h = height; L.frames = frames;
+  ProfScope ps(ctx, AV1MI_K_INPUT);
+  HIP_TRY(ctx, av1mi::launch_chroma_convert(L, ctx->stream));
+  return AV1MI_OK;
+}
+
 int av1mi_scale_planes(av1mi_ctx *ctx, int bit_depth, int src_w, int src_h, int dst_w, int dst_h, int frames, const void *const d_src[3],
                        void *const d_dst[3]) {
   BIND(ctx);

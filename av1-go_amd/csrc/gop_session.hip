@@ -6,7 +6,7 @@
 // Streams.  The context's stream runs the kernels; the session adds an upload stream and a download stream.  A batch is the stages
 // of submit_batch, in this order on every stream:
 //   feed_source       up:   wait slot.filters_done (the kernels that last read this slot's source) -> H2D of the fed buffers -> uploaded
-//                     main: wait uploaded -> [k_input_convert] -> [k_scale]
+//                     main: wait uploaded -> [k_input_convert] -> [k_chroma_convert] -> [k_scale]
 //   code_blocks       main: k_intra_pipe | [k_me_down + k_me_coarse] + k_me_int + k_inter_pipe -> kernel_done
 //   download_symbols  down: wait kernel_done -> D2H of the symbols into pinned memory
 //   loop_filters      main: deblock x3, CDEF, LR x3 + decision -> reference -> filters_done;  down: the decision -> downloaded
@@ -23,6 +23,9 @@
 // input_kernels.hip), then scale (one launch of the resampler, scale_kernels.hip).  The last one fills the slot's planar d_src
 // planes at the coded size, which the block pipeline and the restoration decision read; with both, the converted planes at the
 // source size (d_pre) lie between them.  A planar session without scaling is the session with ZERO stages: what it is fed IS d_src.
+// A source that is not 4:2:0, or deeper than the coded depth (source_chroma / source_bit_depth; planar only), takes the place of the
+// convert stage with the stage chroma: one launch of k_chroma_convert from the fed layout (av1mi_source_plane_bytes) to planar 4:2:0
+// at the fed size.  Where the depths are equal its luma plane passes THROUGH: the fed luma plane is the planar one, as with zero stages.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -108,7 +111,9 @@ struct av1mi_gop {
   Plane plane[3];                              // the coded planes
   size_t nb = 0, bps = 1;                      // blocks of a BATCH (segments stacked), bytes per sample
   int fmt = AV1MI_INPUT_PLANAR;                // cfg.input_format
-  int stages = 0;                              // input stages: convert (fmt != PLANAR) + scale (source size given)
+  int stages = 0;                              // input stages: convert (fmt != PLANAR) or chroma (source_chroma / source_bit_depth) + scale (source size given)
+  bool chroma_stage = false, luma_through = false;   // the stage chroma exists; ... and leaves the luma plane alone (equal depths)
+  int src_bd = 8;                              // the depth of the source as fed (== cfg.bit_depth without the stage)
   av1mi::ScalePlan *scale = nullptr;           // scaling sessions: the resampler's tables
   size_t fed_ny = 0;                           // luma samples of a batch at the fed size
   size_t in_bytes[3] = {}, pre_bytes[3] = {};  // bytes of a batch's planes as the session is fed them / as planar planes at the fed size
@@ -169,9 +174,11 @@ int slot_buffers(av1mi_gop *g, Slot &s) {
     // plane (d_in == d_src, one allocation): the upload lands where the kernels read.
     if (g->in_bytes[p]) G_TRY(host_alloc(g, &s.h_in[p], g->in_bytes[p]));
     G_TRY(dev_alloc(g, &s.d_src[p], P.bytes));
-    if (!g->stages) s.d_in[p] = s.d_src[p];
+    // A luma plane that passes through the stage chroma needs no plane behind that stage: without scaling it is d_src as well.
+    const bool through = g->luma_through && p == 0;
+    if (!g->stages || (through && g->stages == 1)) s.d_in[p] = s.d_src[p];
     else if (g->in_bytes[p]) G_TRY(dev_alloc(g, &s.d_in[p], g->in_bytes[p]));
-    if (g->stages == 2) G_TRY(dev_alloc(g, &s.d_pre[p], g->pre_bytes[p]));
+    if (g->stages == 2 && !through) G_TRY(dev_alloc(g, &s.d_pre[p], g->pre_bytes[p]));
     // the pinned mirror of the levels (as large as the source) is needed when the symbols go to the host; with the GPU coder
     // only a batch the coder gives back needs it, and it is allocated then (pinning memory is a good part of the start-up time)
     if (c.gpu_entropy != 1) G_TRY(host_alloc(g, &s.h_lev[p], P.n * 2));
@@ -261,6 +268,15 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
   if ((c->input_format == AV1MI_INPUT_PACKED10 || c->input_format == AV1MI_INPUT_P010) && c->bit_depth != 10)
     return WHY("input_format %d (%s) needs bit_depth 10, not %d", c->input_format, c->input_format == AV1MI_INPUT_P010 ? "P010" : "packed 10-bit", c->bit_depth);
   if (c->input_format == AV1MI_INPUT_NV12 && c->bit_depth != 8) return WHY("input_format 3 (NV12) needs bit_depth 8, not %d", c->bit_depth);
+  if (c->source_chroma < AV1MI_CHROMA_420 || c->source_chroma > AV1MI_CHROMA_400)
+    return WHY("source_chroma %d unknown (0 4:2:0, 1 4:2:2, 2 4:4:4, 3 grey)", c->source_chroma);
+  if (c->source_bit_depth != 0 && c->source_bit_depth != 8 && c->source_bit_depth != 10 && c->source_bit_depth != 12)
+    return WHY("source_bit_depth %d not supported (8, 10 or 12; 0 = bit_depth)", c->source_bit_depth);
+  if (const char *why = av1mi::chroma_format_error(c->source_chroma, c->source_bit_depth ? c->source_bit_depth : c->bit_depth, c->bit_depth))
+    return WHY("source_bit_depth %d with bit_depth %d: %s", c->source_bit_depth, c->bit_depth, why);
+  if ((c->source_chroma != AV1MI_CHROMA_420 || (c->source_bit_depth && c->source_bit_depth != c->bit_depth)) && c->input_format != AV1MI_INPUT_PLANAR)
+    return WHY("a source that is not 4:2:0 at bit_depth (source_chroma %d, source_bit_depth %d) needs input_format 0 (planar), not %d", c->source_chroma,
+               c->source_bit_depth, c->input_format);
   if ((c->source_width != 0) != (c->source_height != 0) || c->source_width < 0 || c->source_height < 0)
     return WHY("source size %dx%d: give both source_width and source_height, or neither", c->source_width, c->source_height);
   if (c->source_width) {
@@ -295,12 +311,15 @@ int setup(av1mi_gop *g) {
   g->nb = g->plane[0].n / 64;
   g->fmt = c.input_format;
   const bool scaling = c.source_width != 0;
-  g->stages = (g->fmt != AV1MI_INPUT_PLANAR) + scaling;
+  g->src_bd = c.source_bit_depth ? c.source_bit_depth : c.bit_depth;
+  g->chroma_stage = c.source_chroma != AV1MI_CHROMA_420 || g->src_bd != c.bit_depth;
+  g->luma_through = g->chroma_stage && g->src_bd == c.bit_depth;
+  g->stages = (g->fmt != AV1MI_INPUT_PLANAR) + g->chroma_stage + scaling;      // (config_error: never convert AND chroma)
   // the fed size: the coded size, or the source size rounded up to 8
   const int fed_w = scaling ? (c.source_width + 7) & ~7 : w, fed_rows = (scaling ? (c.source_height + 7) & ~7 : h) * S;
   g->fed_ny = (size_t)fed_w * fed_rows;
   for (int p = 0; p < 3; p++) {
-    g->in_bytes[p] = av1mi_input_plane_bytes(g->fmt, c.bit_depth, p, fed_w, fed_rows);
+    g->in_bytes[p] = g->chroma_stage ? av1mi_source_plane_bytes(c.source_chroma, g->src_bd, p, fed_w, fed_rows) : av1mi_input_plane_bytes(g->fmt, c.bit_depth, p, fed_w, fed_rows);
     g->pre_bytes[p] = av1mi_input_plane_bytes(AV1MI_INPUT_PLANAR, c.bit_depth, p, fed_w, fed_rows);
   }
   if (c.gpu_entropy) {
@@ -407,6 +426,16 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
     av1mi::ProfScope ps(g->ctx, AV1MI_K_INPUT, main);
     G_HIP(av1mi::launch_input_convert(g->fmt, L, main));
     for (int p = 0; p < 3; p++) src[p] = L.out[p];
+  }
+  if (g->chroma_stage) {                   // stage: chroma, at the fed size (its TRUE size: the source's, or the visible size)
+    const av1mi_gop_config &c = g->cfg;
+    av1mi::ChromaLaunch L;
+    for (int p = 0; p < 3; p++) { L.in[p] = src[p]; L.out[p] = g->scale ? s.d_pre[p] : s.d_src[p]; }
+    L.chroma = c.source_chroma; L.src_bd = g->src_bd; L.bd = c.bit_depth; L.frames = c.segments;
+    L.w = g->scale ? c.source_width : g->vw; L.h = g->scale ? c.source_height : g->vh;
+    av1mi::ProfScope ps(g->ctx, AV1MI_K_INPUT, main);
+    G_HIP(av1mi::launch_chroma_convert(L, main));
+    for (int p = g->luma_through ? 1 : 0; p < 3; p++) src[p] = L.out[p];      // (a luma plane that passes through stays where it was fed)
   }
   if (g->scale) {                          // stage: scale, fed size -> coded size
     av1mi::ProfScope ps(g->ctx, AV1MI_K_INPUT, main);
@@ -652,7 +681,7 @@ int av1mi_gop_acquire_input(av1mi_gop *g, void **y, void **u, void **v) {
   G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
   Slot &s = g->slot[g->submitted % kSlots];
   if (s.upload_pending) { G_HIP(hipEventSynchronize(s.uploaded)); s.upload_pending = false; }   // the copy engine still reads these buffers
-  *y = s.h_in[0]; *u = s.h_in[1]; *v = s.h_in[2];      // in the session's format; no third plane in the semi-planar ones
+  *y = s.h_in[0]; *u = s.h_in[1]; *v = s.h_in[2];      // in the session's format; no third plane in the semi-planar ones, no chroma for a grey source
   g->acquired = true;
   return AV1MI_OK;
 }
@@ -666,7 +695,8 @@ int av1mi_gop_submit(av1mi_gop *g, int frame_type) {
 int av1mi_gop_submit_device(av1mi_gop *g, const void *d_y, const void *d_u, const void *d_v, int frame_type) {
   if (!g) return AV1MI_E_INVAL;
   if (g->fmt == AV1MI_INPUT_P010 || g->fmt == AV1MI_INPUT_NV12) d_v = d_u;      // semi-planar: no third plane
-  if (!d_y || !d_u || !d_v || (((uintptr_t)d_y | (uintptr_t)d_u | (uintptr_t)d_v) & (g->fmt == AV1MI_INPUT_PLANAR ? 7 : 15)))
+  if (g->chroma_stage && g->cfg.source_chroma == AV1MI_CHROMA_400) d_u = d_v = d_y;      // grey: no chroma planes (the stage reads none)
+  if (!d_y || !d_u || !d_v || (((uintptr_t)d_y | (uintptr_t)d_u | (uintptr_t)d_v) & (g->fmt == AV1MI_INPUT_PLANAR && !g->chroma_stage ? 7 : 15)))
     return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "null or misaligned device source plane");
   const void *src[3] = { d_y, d_u, d_v };
   return submit_batch(g, frame_type, src);

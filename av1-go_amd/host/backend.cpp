@@ -3,7 +3,7 @@
 // libav1mi.so's GOP session (include/av1mi.h av1mi_gop_*), entropy coding + OBU packing in av1_bitstream.cpp on the host
 // cores, so nothing about the encoder is decided here.
 //
-// Input is Y4M (4:2:0, 8- or 10-bit), from a file or from a stream ("-i -", a FIFO: y4m.hpp), because demux / H.264 decode stay
+// Input is Y4M (4:2:0, 8- or 10-bit; with a job that converts to 4:2:0 also 4:2:2, 4:4:4 and grey, up to 12 bits), from a file or from a stream ("-i -", a FIFO: y4m.hpp), because demux / H.264 decode stay
 // FFmpeg's job (SURVEY.md §8b "Gap to flag"): any decoder process can pipe its frames in.
 // Output, chosen by the file name: ".obu" = Section-5 low-overhead OBU stream (what `dav1d -i x.obu` / `aomdec --obu` read),
 // ".ivf" = IVF, anything else (the reference's "<base>.av1-tmp.mkv") = Matroska with one V_AV1 video track (mux.cpp);
@@ -153,7 +153,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
   int code = 0;
 #define CHK(call)                                                                                   \
   do { int rc_ = (call); if (rc_ != AV1MI_OK) { *err = std::string(#call) + ": " + av1mi_last_error(ctx); code = 2; goto done; } } while (0)
-  if (!y.open(job.input, err)) { code = 1; goto done; }
+  if (!y.open(job.input, err, job.to_420)) { code = 1; goto done; }
   {
     // the target: what the argv's filter chain yields on this source (transcode.go:92-115), or -av1mi_scale; no chain = the source
     int tw = y.w, th = y.h;
@@ -187,10 +187,14 @@ int RunBackend(const BackendJob &job, std::string *err) {
     // key frames in 32x32 blocks where the frame allows it (the coded width a multiple of 32)
     cfg.key_block_size = (job.key_block_size == 32 && (w & 31) == 0) ? 32 : 8;
     // -av1mi_pack10 1: a 10-bit source crosses PCIe at 10 bits per sample; the session's pinned buffers are then three packed planes
-    const bool packed = job.pack10 && y.bd == 10;
+    // A source that is not 4:2:0 at the coded depth (only a job that converts opens one): fed in its own layout, converted on the GPU
+    const bool convert = y.chroma != AV1MI_CHROMA_420 || y.src_bd != y.bd;
+    if (convert) { cfg.source_chroma = y.chroma; cfg.source_bit_depth = y.src_bd; }
+    const bool packed = job.pack10 && y.bd == 10 && !convert;      // (planar 4:2:0 10-bit only)
     if (packed) cfg.input_format = AV1MI_INPUT_PACKED10;
-    // one segment's planes in the pinned buffers
-    const size_t py_bytes = av1mi_input_plane_bytes(cfg.input_format, y.bd, 0, rw, rh), pc_bytes = av1mi_input_plane_bytes(cfg.input_format, y.bd, 1, rw, rh);
+    // one segment's planes in the pinned buffers (no chroma planes for a grey source)
+    const size_t py_bytes = convert ? av1mi_source_plane_bytes(y.chroma, y.src_bd, 0, rw, rh) : av1mi_input_plane_bytes(cfg.input_format, y.bd, 0, rw, rh);
+    const size_t pc_bytes = convert ? av1mi_source_plane_bytes(y.chroma, y.src_bd, 1, rw, rh) : av1mi_input_plane_bytes(cfg.input_format, y.bd, 1, rw, rh);
     std::vector<std::vector<unsigned char>> scratch(packed ? (size_t)S : 0);          // per reader thread: one planar frame to pack from
     CHK(av1mi_gop_open(ctx, &cfg, &gop));
     av1::SequenceParams sp; sp.width = tw; sp.height = th; sp.bit_depth = y.bd;
@@ -251,12 +255,13 @@ int RunBackend(const BackendJob &job, std::string *err) {
             // a shorter last GOP / fewer GOPs than segments: the slot is coded (the batch is one launch) and its output dropped.  Flat
             // planes, not whatever the pinned buffer held: stale pixels could cost the GPU coder's tile capacity for the whole batch
             // (zero samples pack to zero bytes)
-            memset((unsigned char *)py + py_bytes * s, 0, py_bytes); memset((unsigned char *)pu + pc_bytes * s, 0, pc_bytes); memset((unsigned char *)pv + pc_bytes * s, 0, pc_bytes);
+            memset((unsigned char *)py + py_bytes * s, 0, py_bytes);
+            if (pc_bytes) { memset((unsigned char *)pu + pc_bytes * s, 0, pc_bytes); memset((unsigned char *)pv + pc_bytes * s, 0, pc_bytes); }
             continue;
           }
           reads.th.emplace_back([&, s, t, py, pu, pv]() {
             if (!packed) {
-              reads.ok[(size_t)s] = y.read((long)s * G + t, rw, rh, (unsigned char *)py + fy * s, (unsigned char *)pu + fc * s, (unsigned char *)pv + fc * s);
+              reads.ok[(size_t)s] = y.read((long)s * G + t, rw, rh, (unsigned char *)py + py_bytes * s, (unsigned char *)pu + pc_bytes * s, (unsigned char *)pv + pc_bytes * s);
               return;
             }
             // the frame (edge padding included) into this thread's scratch, then packed into the segment's byte range of the pinned planes

@@ -49,6 +49,27 @@ long long av1mi_host_y4m_scan(const char *path, int group, unsigned long long *s
   geometry[0] = y.w; geometry[1] = y.h; geometry[2] = y.bd; geometry[3] = y.fps_n; geometry[4] = y.fps_d;
   return total;
 }
+// Y4mSource::open alone, with or without the job's opt-in to other layouts than 4:2:0 (any_layout): 0 and geometry = { w, h, coded bit
+// depth, chroma layout (enum av1mi_source_chroma), source bit depth }, *frame_bytes = one frame's samples in the file, *frames = the
+// frames a seekable file holds (-1 for a stream); -1 with the text in err when the source is refused
+int av1mi_host_y4m_layout(const char *path, int any_layout, int *geometry, unsigned long long *frame_bytes, long long *frames, char *err, int cap) {
+  Y4mSource y;
+  std::string e;
+  if (!y.open(path, &e, any_layout != 0)) { strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0; return -1; }
+  geometry[0] = y.w; geometry[1] = y.h; geometry[2] = y.bd; geometry[3] = y.chroma; geometry[4] = y.src_bd;
+  *frame_bytes = y.frame_bytes(); *frames = y.known_frames();
+  return 0;
+}
+// ParseBackendJob's view of the conversion to 4:2:0 (BackendJob::to_420) for an argv joined with '\n': 1 / 0, or -1 with the text in err
+int av1mi_host_parse_format_option(const char *joined, char *err, int cap) {
+  std::vector<std::string> a; std::string s = joined; size_t p = 0, q;
+  while ((q = s.find('\n', p)) != std::string::npos) { a.push_back(s.substr(p, q - p)); p = q + 1; }
+  a.push_back(s.substr(p));
+  BackendJob job; std::string e;
+  const bool ok = ParseBackendJob(a, &job, &e);
+  strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
+  return ok ? (job.to_420 ? 1 : 0) : -1;
+}
 // the header's sample aspect ratio as Y4mSource keeps it; 0, or -1 when the file does not open
 int av1mi_host_y4m_sar(const char *path, int *sar) {
   Y4mSource y;

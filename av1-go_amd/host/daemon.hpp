@@ -44,6 +44,9 @@ struct TranscodeConfig {           // daemon.go:185-188; Device is this backend'
   double MinPSNR = 0;
   // The wide-range motion search (-av1mi_me_range, av1mi_gop_config.coarse_range): 0 = off, else a multiple of 4 up to 64.
   int MeRange = 0;
+  // -av1mi_format 420 on every job (BackendJob::to_420).  The reference's chain, which ProcessJob always passes, already says so with
+  // its format=nv12; the option states it for callers that build their own argv without a chain.
+  bool Format420 = false;
 };
 
 // daemon.go:57-182.  Returns "" where the reference returns nil, else the error text; job.Status / job.Reason are

@@ -1,11 +1,13 @@
 // av1mi_transcode — CLI with the reference's process contract (exit code, stderr text, output file last):
 //   av1mi_transcode [ffmpeg-style args] -i in.y4m [-global_quality:v:0 Q] [-g GOP] [-vf:v:0 CHAIN] [-av1mi_scale WxH]
-//                   [-av1mi_stats FILE] [-av1mi_min_psnr DB] [-av1mi_me_range N] out.av1-tmp.mkv
+//                   [-av1mi_stats FILE] [-av1mi_min_psnr DB] [-av1mi_me_range N] [-av1mi_format 420] out.av1-tmp.mkv
+//                   (-av1mi_format 420, or a format= filter naming a 4:2:0 format in CHAIN: 4:2:2 / 4:4:4 / grey and 12-bit sources are
+//                   accepted and converted to 4:2:0 on the GPU)
 //                   (-av1mi_stats: per-frame PSNR / SSIM measured on the GPU; -av1mi_min_psnr: fail with exit code 3 below that luma PSNR)
 //                   (-av1mi_me_range: 0, or a multiple of 4 up to 64: the P frames' motion search follows N + 8 samples per frame)
 //                   (CHAIN: the reference's scale filters, evaluated on the source's size and sample aspect ratio and applied on the GPU;
 //                   -av1mi_scale: an explicit output size, wins over the chain; any other filter is refused)
-//   av1mi_transcode --job in.y4m [--ratio 0.9] [--state DIR] [--wait S] [--replace-source 1] [--min-psnr DB] [--me-range N]   (the ProcessJob lifecycle;
+//   av1mi_transcode --job in.y4m [--ratio 0.9] [--state DIR] [--wait S] [--replace-source 1] [--min-psnr DB] [--me-range N] [--format 420]   (the ProcessJob lifecycle;
 //                   the source is only replaced on request: the output is video-only)
 #include <cstdio>
 #include <cstdlib>
@@ -30,6 +32,7 @@ int main(int argc, char **argv) {
       else if (!strcmp(argv[i], "--replace-source")) { cfg.ReplaceSource = atoi(argv[i + 1]) != 0; }
       else if (!strcmp(argv[i], "--min-psnr")) cfg.MinPSNR = atof(argv[i + 1]);
       else if (!strcmp(argv[i], "--me-range")) cfg.MeRange = atoi(argv[i + 1]);
+      else if (!strcmp(argv[i], "--format")) cfg.Format420 = !strcmp(argv[i + 1], "420");
     }
     struct stat st;
     if (!stat(job.SourcePath.c_str(), &st)) job.OriginalSize = st.st_size;
@@ -38,7 +41,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "job %s: %s%s%s\n", job.Status.c_str(), job.Reason.c_str(), e.empty() ? "" : " | ", e.c_str());
     return e.empty() ? 0 : 1;
   }
-  if (argc >= 3 && !strcmp(argv[1], "--jobs")) {   // --jobs a.y4m b.y4m ... [--gpus N] [--workers W] [--ratio R] [--state DIR] [--min-psnr DB] [--me-range N]
+  if (argc >= 3 && !strcmp(argv[1], "--jobs")) {   // --jobs a.y4m b.y4m ... [--gpus N] [--workers W] [--ratio R] [--state DIR] [--min-psnr DB] [--me-range N] [--format 420]
     std::vector<Job> jobs;
     TranscodeConfig cfg; cfg.StableWaitSeconds = 0;
     int gpus = 1, workers = 0;
@@ -49,6 +52,7 @@ int main(int argc, char **argv) {
       else if (!strcmp(argv[i], "--state") && i + 1 < argc) cfg.JobStateDir = argv[++i];
       else if (!strcmp(argv[i], "--min-psnr") && i + 1 < argc) cfg.MinPSNR = atof(argv[++i]);
       else if (!strcmp(argv[i], "--me-range") && i + 1 < argc) cfg.MeRange = atoi(argv[++i]);
+      else if (!strcmp(argv[i], "--format") && i + 1 < argc) cfg.Format420 = !strcmp(argv[++i], "420");
       else {
         Job j; j.ID = "job" + std::to_string(jobs.size()); j.SourcePath = argv[i];
         struct stat st;

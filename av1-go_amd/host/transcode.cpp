@@ -62,7 +62,7 @@ static bool plain_int(const std::string &t, int *v) {
   return true;
 }
 
-bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err) {
+bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err, bool *to_420) {
   if (sar_n <= 0 || sar_d <= 0) sar_n = sar_d = 1;
   long cw = iw, ch = ih;
   bool sq = sar_n == sar_d;
@@ -83,7 +83,11 @@ bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain,
       sar_n = sar_d = 1; sq = true;
     } else if (f == kEvenScale) {
       cw = (cw + 1) / 2 * 2; ch = (ch + 1) / 2 * 2;
-    } else if (f.empty() || f == "hwdownload" || f == "hwupload" || f == "setsar=1" || f.compare(0, 7, "format=") == 0) {
+    } else if (f.empty() || f == "hwdownload" || f == "hwupload" || f == "setsar=1") {
+    } else if (f.compare(0, 7, "format=") == 0) {      // the encoder is handed 4:2:0 whatever the decoder produced (transcode.go:99-110); nothing else can be honoured
+      const std::string name = f.substr(7);
+      if (name != "nv12" && name != "p010" && name != "p010le" && name != "yuv420p" && name != "yuv420p10le") { if (err) *err = "Invalid argument: unsupported filter " + f; return false; }
+      if (to_420) *to_420 = true;
     } else if (f.compare(0, 6, "scale=") == 0 && f.find(':') != std::string::npos && plain_int(f.substr(6, f.find(':') - 6), &a) &&
                plain_int(f.substr(f.find(':') + 1), &b)) {
       cw = a; ch = b; sar_n = sar_d = 1; sq = true;
@@ -117,6 +121,10 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
     else if (args[i] == "-av1mi_key_block_size") job->key_block_size = std::atoi(args[i + 1].c_str());
     else if (args[i] == "-av1mi_pack10") job->pack10 = std::atoi(args[i + 1].c_str());
     else if (args[i] == "-av1mi_stats") job->stats_path = args[i + 1];
+    else if (args[i] == "-av1mi_format") {
+      if (args[i + 1] != "420") { if (err) *err = "Invalid argument: -av1mi_format takes 420 (the only layout that is coded), not " + args[i + 1]; return false; }
+      job->to_420 = true;
+    }
     else if (args[i] == "-av1mi_me_range") {
       if (!plain_int(args[i + 1], &job->me_range) || job->me_range > 64 || (job->me_range & 3)) { if (err) *err = "Invalid argument: -av1mi_me_range takes 0 or a multiple of 4 up to 64, not " + args[i + 1]; return false; }
     }
@@ -139,7 +147,9 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
   }
   if (job->have_vf) {      // a filter that cannot be applied must not be skipped silently: the chain is checked before anything runs
     int w, h;
-    if (!ScaleTarget(16, 16, 1, 1, job->vf, &w, &h, nullptr, err)) return false;
+    bool to_420 = false;
+    if (!ScaleTarget(16, 16, 1, 1, job->vf, &w, &h, nullptr, err, &to_420)) return false;
+    if (to_420) job->to_420 = true;
   }
   if (!have_in) { if (err) *err = "Invalid argument: no input (-i) given"; return false; }
   if (job->quality < 0 || job->quality > 255 || job->gop < 1 || job->gop > 256 || job->segments < 1 || job->segments > 256 || job->threads < 0 || (job->key_block_size != 8 && job->key_block_size != 32) || (job->pack10 != 0 && job->pack10 != 1)) { if (err) *err = "Invalid argument: quality/gop/key block size/pack10 out of range"; return false; }

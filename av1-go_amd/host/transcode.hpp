@@ -63,6 +63,10 @@ struct BackendJob {
                            // transcode fails with exit code 3, "quality gate: psnr_y ...", and the output is removed
   int me_range = 0;        // -av1mi_me_range N: 0 (default), or a multiple of 4 up to 64: P frames search around a coarse centre per 64x64 tile
                            // (av1mi_gop_config.coarse_range): vectors reach N + 8 samples per frame instead of 8
+  bool to_420 = false;     // the job converts its source to 4:2:0: the chain has a format= filter naming a 4:2:0 format (nv12, p010, p010le, yuv420p,
+                           // yuv420p10le — the reference's chain always does, transcode.go:99-110), or -av1mi_format 420 was given.  The source may then be
+                           // 4:2:2, 4:4:4 or grey, at 8, 10 or 12 bits (Y4mSource::open's any_layout); it is converted on the GPU (av1mi.h "chroma formats").
+                           // The coded depth follows the SOURCE (8 -> 8, 10 -> 10, 12 -> 10), not the format's name.  Without it such a source is refused
   std::vector<std::string> tracks;   // -av1mi_tracks <file.mka> (repeatable): Matroska side files whose audio / subtitle tracks are copied
                                      // next to the video (the reference's `-c:a copy -c:s copy`, transcode.go:134-137, after an external demux)
 };
@@ -71,10 +75,12 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
 // The video filter chain of the argv (transcode.go:92-115), evaluated as it is written on a source of iw x ih samples with sample aspect
 // ratio sar_n : sar_d.  Recognised, literally: the reference's SAR scale (transcode.go:97: (w, h) = sar < 1 ? (iw, iw / sar) :
 // (iw * sar, ih), truncated to integers — the first branch divides iw, as written upstream), its even-size scale (:98 / :107: each
-// dimension rounded up to even), `hwdownload`, `hwupload`, `format=...`, `setsar=1` (no effect on planar 4:2:0 frames), and
+// dimension rounded up to even), `hwdownload`, `hwupload`, `setsar=1` (no effect on planar 4:2:0 frames), `format=` naming a 4:2:0
+// format (nv12, p010, p010le, yuv420p, yuv420p10le: no effect on the size; *to_420, when given, is set — BackendJob::to_420; any other
+// format is "Invalid argument: unsupported filter format=<name>"), and
 // `scale=W:H` / `scale_vaapi=w=W:h=H` with plain integers.  Returns false and "Invalid argument: unsupported filter <name>" for
 // anything else.  *square: the chain leaves square pixels (it resampled by the SAR, or to an explicit size).
-bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err);
+bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err, bool *to_420 = nullptr);
 
 // transcode.go:194-315 contract: (0, "") on success AND the output file exists; (code, text <= 800 chars) on failure;
 // (-1, text) when the backend could not run at all (no HIP device, library error before any frame).  Exit code 3 is the quality gate

@@ -25,7 +25,31 @@ static bool read_line(FILE *f, std::string *line, size_t cap = 1 << 16) {      /
   return false;
 }
 
-bool Y4mSource::open(const std::string &path, std::string *err) {
+// "C<tag>" of a job that converts to 4:2:0: layout (enum av1mi_source_chroma) and depth, false for everything else (4:1:1, 9 / 14 /
+// 16 bits, alpha)
+static bool parse_layout(const std::string &cs, int *chroma, int *depth) {
+  std::string rest;
+  if (cs.compare(0, 4, "mono") == 0) {
+    *chroma = 3; rest = cs.substr(4);
+    if (rest.empty()) { *depth = 8; return true; }
+  } else if (cs.compare(0, 3, "420") == 0 || cs.compare(0, 3, "422") == 0 || cs.compare(0, 3, "444") == 0) {
+    *chroma = cs[2] == '0' ? 0 : cs[1] == '2' ? 1 : 2;
+    rest = cs.substr(3);
+    const bool deep = rest.size() > 1 && rest[0] == 'p' && rest[1] >= '0' && rest[1] <= '9';
+    if (!deep) {      // 8 bits: 4:2:0 carries a siting suffix (jpeg, mpeg2, paldv), the others nothing (444alpha is not 4:4:4)
+      *depth = 8;
+      return *chroma == 0 || rest.empty();
+    }
+    rest = rest.substr(1);
+  } else {
+    return false;
+  }
+  if (rest == "10") { *depth = 10; return true; }
+  if (rest == "12") { *depth = 12; return true; }
+  return false;
+}
+
+bool Y4mSource::open(const std::string &path, std::string *err, bool any_layout) {
   path_ = path;
   const bool is_stdin = path == "-" || path == "pipe:0" || path == "pipe:" || path == "/dev/stdin";
   if (is_stdin) { f_ = stdin; own_ = false; }
@@ -47,14 +71,21 @@ bool Y4mSource::open(const std::string &path, std::string *err) {
     else if (t[0] == 'C') cs = t.substr(1);
     else if (t[0] == 'A') { if (sscanf(t.c_str() + 1, "%d:%d", &sar_n, &sar_d) != 2 || sar_n <= 0 || sar_d <= 0) sar_n = sar_d = 1; }
   }
-  if (cs.rfind("420p10", 0) == 0) bd = 10;
+  if (any_layout) {
+    if (!parse_layout(cs, &chroma, &src_bd)) { *err = "Invalid argument: unsupported Y4M colourspace " + cs + " (4:2:0, 4:2:2, 4:4:4 or mono at 8, 10 or 12 bits only)"; return false; }
+    bd = src_bd == 12 ? 10 : src_bd;
+  }
+  else if (cs.rfind("420p10", 0) == 0) bd = 10;
   else if (cs.rfind("420", 0) == 0 && cs.find("p1") == std::string::npos) bd = 8;
   else { *err = "Invalid argument: unsupported Y4M colourspace " + cs + " (4:2:0 8/10-bit only)"; return false; }
+  if (!any_layout) { chroma = 0; src_bd = bd; }
   if (w < 8 || h < 8) { *err = "Invalid argument: frame size below 8x8"; return false; }
   if (w > 4096 || h > 4096) { *err = "Invalid argument: frames above 4096x4096 need more than 64 tile rows / columns"; return false; }
   if (fps_n <= 0 || fps_d <= 0) { fps_n = 30; fps_d = 1; }
-  // Y4M 4:2:0 planes of a w x h picture: w * h luma and two ceil(w / 2) * ceil(h / 2) chroma planes
-  frame_bytes_ = ((size_t)w * h + 2 * (size_t)((w + 1) / 2) * ((h + 1) / 2)) * (bd == 8 ? 1 : 2);
+  // Y4M planes of a w x h picture: w * h luma and two chroma planes of ceil(w / 2) * ceil(h / 2) (4:2:0), ceil(w / 2) * h (4:2:2),
+  // w * h (4:4:4) or nothing (mono)
+  const size_t chroma_samples = chroma == 0 ? (size_t)((w + 1) / 2) * ((h + 1) / 2) : chroma == 1 ? (size_t)((w + 1) / 2) * h : chroma == 2 ? (size_t)w * h : 0;
+  frame_bytes_ = ((size_t)w * h + 2 * chroma_samples) * (bd == 8 ? 1 : 2);
   // in place only when the file seeks AND every frame header is the bare "FRAME\n" (frame parameters make the frames unequal in size)
   struct stat st;
   seekable_ = false;
@@ -145,7 +176,9 @@ bool Y4mSource::read(long i, int cw, int ch, unsigned char *Y, unsigned char *U,
     for (int r = ph; r < dh; r++) memcpy(dst + (size_t)r * dw * bps, dst + (size_t)(ph - 1) * dw * bps, (size_t)dw * bps);
     return true;
   };
-  return plane(Y, w, h, cw, ch) && plane(U, (w + 1) / 2, (h + 1) / 2, cw / 2, ch / 2) && plane(V, (w + 1) / 2, (h + 1) / 2, cw / 2, ch / 2);
+  if (chroma == 3) return plane(Y, w, h, cw, ch);
+  const int pw = chroma == 2 ? w : (w + 1) / 2, ph = chroma == 0 ? (h + 1) / 2 : h, dw = chroma == 2 ? cw : cw / 2, dh = chroma == 0 ? ch / 2 : ch;
+  return plane(Y, w, h, cw, ch) && plane(U, pw, ph, dw, dh) && plane(V, pw, ph, dw, dh);
 }
 
 }  // namespace av1mi_host

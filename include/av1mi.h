@@ -386,6 +386,37 @@ int av1mi_input_pack(int format, int bit_depth, int width, int rows, const void 
 int av1mi_input_convert(av1mi_ctx *ctx, int format, int bit_depth, int width, int rows, const void *d_in0, const void *d_in1, const void *d_in2,
                         void *d_y, void *d_u, void *d_v);
 
+/* ---- chroma formats: sources that are not 4:2:0, or deeper than the coded depth (av1-go_amd/csrc/input_kernels.hip, k_chroma_convert).
+ * A source has a chroma layout, source_chroma (4:2:0, 4:2:2, 4:4:4 or 4:0:0 = grey), and a depth, source_bit_depth (8, 10 or 12).  It is
+ * coded as 4:2:0 at bit_depth: 8 -> 8, 10 -> 10, 12 -> 10; no other pair of depths is valid.  Integer arithmetic, bit exact by definition.
+ * With d = source_bit_depth - bit_depth (0 or 2) and max = (1 << bit_depth) - 1:
+ *   layout   the planes of a frame of TRUE luma size w x h lie in buffers of that size rounded up to 8 in both directions, W8 x H8 (uint8
+ *            for an 8-bit source, uint16 with the value in the low bits otherwise; frames stacked, no row padding):
+ *              luma W8 x H8;  chroma 4:2:0 W8 / 2 x H8 / 2,  4:2:2 W8 / 2 x H8,  4:4:4 W8 x H8,  4:0:0 none.
+ *            The TRUE chroma plane size w_p x h_p is ceil(w / 2) x ceil(h / 2), ceil(w / 2) x h and w x h (luma: w x h).
+ *   reads    in(x, y) = plane[min(y, h_p - 1)][min(max(x, 0), w_p - 1)]: clamped at the TRUE size.  Nothing beyond it is read; the
+ *            buffers' padding may be undefined.
+ *   writes   every sample of the 4:2:0 output planes (W8 x H8 luma, W8 / 2 x H8 / 2 chroma; uint8 at bit_depth 8, else uint16), padding
+ *            included, by ONE rule:  out = min((S + (1 << (s - 1))) >> s, max), and out = S where s = 0:
+ *              luma, and 4:2:0 chroma   S = in(x, y)                                                              s = d
+ *              4:2:2 chroma             S = in(x, 2 y) + in(x, 2 y + 1)                                           s = 1 + d
+ *              4:4:4 chroma             S = sum over r in {2 y, 2 y + 1} of in(2 x - 1, r) + 2 in(2 x, r) + in(2 x + 1, r)   s = 3 + d
+ *              4:0:0                    both chroma planes are 1 << (bit_depth - 1) everywhere
+ *            Each output sample is rounded once (all-max 12-bit: (4095 + 2) >> 2 = 1024, hence the min).  The chroma ends up co-sited
+ *            with the even luma column and midway between two luma rows: the siting of C420mpeg2, and of what 4:2:2 video carries.
+ * The sequence header keeps chroma_sample_position 0 and mono_chrome 0: a grey source is coded as 4:2:0 with flat chroma. */
+enum av1mi_source_chroma { AV1MI_CHROMA_420 = 0, AV1MI_CHROMA_422 = 1, AV1MI_CHROMA_444 = 2, AV1MI_CHROMA_400 = 3 };
+/* bytes of plane 0..2 of a source stacked to `rows` luma rows (multiple of 8, like width: the buffers' size) in the layout above; 0 for
+ * an invalid layout / depth / size and for the chroma planes of a grey source.  No GPU needed. */
+size_t av1mi_source_plane_bytes(int source_chroma, int source_bit_depth, int plane, int width, int rows);
+/* the conversion on the device, ONE launch for all planes of `frames` stacked frames of TRUE luma size width x height (8 .. 16384):
+ * d_in0..2 in the layout above (d_in1 / d_in2 ignored for a grey source) -> the 4:2:0 planes d_y, d_u, d_v at bit_depth.  Where the
+ * depths are equal (d = 0) the source's luma plane IS the output's: it is not part of the launch, d_in0 and d_y are ignored and may be
+ * null.  Asynchronous on the context's stream; all pointers 16-byte aligned; an invalid layout, pair of depths or size is
+ * AV1MI_E_INVAL.  Counted under AV1MI_K_INPUT in the profile. */
+int av1mi_chroma_convert(av1mi_ctx *ctx, int source_chroma, int source_bit_depth, int bit_depth, int width, int height, int frames,
+                         const void *d_in0, const void *d_in1, const void *d_in2, void *d_y, void *d_u, void *d_v);
+
 /* ---- scaling: the resampler of the input stage (av1-go_amd/csrc/scale_kernels.hip).  Integer arithmetic, bit exact by definition.
  * One dimension, N true source samples -> M output samples, N / M in [1/4, 4]:
  *   taps     T = 2 * ceil(3 * max(N, M) / M) (evaluated in integers: 6 when enlarging or copying, 12 for 2:1, at most 24);
@@ -506,6 +537,16 @@ typedef struct av1mi_gop_config {
    * every 64x64 tile of every segment a centre for the integer search: vectors reach coarse_range + search_range samples.  The
    * quarter planes and centres exist once per session. */
   int coarse_range;
+  /* Chroma formats (0, 0 = none: a 4:2:0 source at bit_depth, the session as it has always been — same allocations, same launches).
+   * source_chroma: enum av1mi_source_chroma; source_bit_depth: 8, 10 or 12, 0 = bit_depth.  Otherwise the session is FED the source in
+   * the layout of "chroma formats" above at the fed size (buffers of av1mi_gop_acquire_input / av1mi_gop_submit_device: sizes
+   * av1mi_source_plane_bytes with rows = segments * the fed height; no chroma planes for a grey source), and the stage "chroma" (one
+   * launch per batch, k_chroma_convert) runs between "convert" and "scale": it reads the fed buffers at their TRUE size (source_width x
+   * source_height where the session scales, else visible_* or width x height) and writes the planar 4:2:0 planes the scaler or the
+   * block pipeline reads.  Where the depths are equal the fed luma plane IS the planar luma plane (the caller still replicates the luma
+   * edge into its padding when the session does not scale; chroma padding may be undefined).  input_format must be PLANAR.  Scaling,
+   * visible_*, quality_stats (measured against the converted frame) and coarse_range work unchanged behind the stage. */
+  int source_chroma, source_bit_depth;
 } av1mi_gop_config;
 
 /* Frame-header parameters chosen by the session's policy for one frame (non-normative encoder choices; the bitstream carries
@@ -560,7 +601,8 @@ void av1mi_gop_close(av1mi_gop *g);
  * (stride = width samples, uint8 for 8-bit, uint16 otherwise) and the matching rows of the half-size chroma planes.
  * Blocks until the upload that last used these buffers has finished.
  * A session whose input_format is not PLANAR hands out the buffers in THAT format (sizes: av1mi_input_plane_bytes with rows =
- * segments * height): PACKED10 three byte buffers, P010 / NV12 the luma plane in *y, the interleaved plane in *u and *v = NULL. */
+ * segments * height): PACKED10 three byte buffers, P010 / NV12 the luma plane in *y, the interleaved plane in *u and *v = NULL.
+ * A session with source_chroma / source_bit_depth hands out planes of av1mi_source_plane_bytes each; grey sources: *u = *v = NULL. */
 int av1mi_gop_acquire_input(av1mi_gop *g, void **y, void **u, void **v);
 /* queue the batch in the acquired buffers.  frame_type: 0 key, 1 inter, -1 = by position in the GOP (gop_length).
  * AV1MI_E_INVAL when av1mi_gop_max_in_flight() batches are already in flight (collect first). */
