@@ -254,6 +254,11 @@ class GopSession:
         self.ctx.lib.av1mi_gop_submit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         self.ctx._chk(self.ctx.lib.av1mi_gop_submit_device(self.g, d_y.ptr, d_u.ptr if d_u is not None else None, d_v.ptr if d_v is not None else None, int(frame_type)))
 
+    def set_q(self, base_q_idx):
+        """the quantiser (1..255) of every batch submitted from now on; batches in flight keep theirs (av1mi_gop_set_base_q_idx)"""
+        self.ctx.lib.av1mi_gop_set_base_q_idx.argtypes = [C.c_void_p, C.c_int]
+        self.ctx._chk(self.ctx.lib.av1mi_gop_set_base_q_idx(self.g, int(base_q_idx)))
+
     def pending(self):
         return self.ctx.lib.av1mi_gop_pending(self.g)
 

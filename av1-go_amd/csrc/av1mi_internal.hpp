@@ -171,6 +171,14 @@ struct QualityLaunch {
 size_t quality_scratch_bytes(int bd, int w, int h, int frames);
 hipError_t launch_quality(const QualityLaunch &Q, hipStream_t s);
 
+// side information that follows a batch's quantiser (levels_kernels.hip): up to three arrays of dwords patched in place in one launch,
+// word = (word & keep) | bits unless (word & hold) != 0
+struct LevelsLaunch {
+  struct Array { uint32_t *words; size_t n; uint32_t keep, bits, hold; } a[3];
+  int arrays;
+};
+hipError_t launch_mi_levels(const LevelsLaunch &L, hipStream_t s);
+
 int tx_width(int tx_size);
 int tx_height(int tx_size);
 hipError_t launch_inv_txfm(int tx_size, const TxLaunch &L, int bd, hipStream_t s);

@@ -92,6 +92,8 @@ struct Slot {
   // restoration on / off per (segment, plane), decided by the GPU against the source (k_lr + k_lr_decide): device + pinned mirror
   void *d_lr_on = nullptr, *h_lr_on = nullptr;
   int frame_type = 0;
+  int q = 0;                          // the batch's quantiser (av1mi_gop_set_base_q_idx) and what the policy derives from it for its frame type
+  av1mi_frame_params params{};
   // GPU entropy coding (gpu_entropy != 0): coded tile payloads (pinned host memory, written by the GPU) + sizes (device + pinned mirror)
   void *h_ent_out = nullptr, *d_tile_size = nullptr, *h_tile_size = nullptr, *d_total = nullptr, *h_total = nullptr;
   hipEvent_t ent_done = nullptr;      // coder + download of sizes / total finished (side stream)
@@ -129,7 +131,9 @@ struct av1mi_gop {
   void *d_quality_scratch = nullptr;           // quality_stats: the tiles' partial sums of one batch (the main stream orders its users)
   int vw = 0, vh = 0;                          // the true frame size (== the coded size unless cfg.visible_* say otherwise)
   int last = 0;                                // slot of the most recent batch (its d_lr_on selects the next batch's references)
-  av1mi_frame_params params[2];                // key, inter
+  av1mi_frame_params params[2];                // key, inter: at the session's own quantiser (cfg.base_q_idx), what side_information builds from
+  int next_q = 0;                              // the quantiser of the batches to come (av1mi_gop_set_base_q_idx; cfg.base_q_idx until then)
+  int mi_q[3] = {}, cdef_q[2] = {};            // the quantiser whose levels d_mi[t] / whose strengths d_cdef_sb[t] hold now (follow_q rewrites them)
   size_t ent_cap = 0; int tiles = 0;           // GPU entropy coding: payload capacity of a batch, tiles per frame
   long submitted = 0, collected = 0;           // batches
   long fallbacks = 0;                          // batches the GPU coder could not hold (handed out as symbols instead)
@@ -232,12 +236,14 @@ int side_information(av1mi_gop *g) {
     }
     G_TRY(dev_alloc(g, &g->d_mi[t][0], mi.size() * 4)); G_TRY(av1mi_upload(g->ctx, g->d_mi[t][0], mi.data(), mi.size() * 4));
     G_TRY(dev_alloc(g, &g->d_mi[t][1], mic.size() * 4)); G_TRY(av1mi_upload(g->ctx, g->d_mi[t][1], mic.data(), mic.size() * 4));
+    g->mi_q[t] = c.base_q_idx;
   }
   for (int t = 0; t < 2; t++) {      // CDEF strengths: one set per frame type
     const av1mi_frame_params &P = g->params[t];
     std::vector<uint8_t> sb((size_t)nsb * 4);
     for (int i = 0; i < nsb; i++) { sb[4 * i] = P.cdef_y >> 2; sb[4 * i + 1] = P.cdef_y & 3; sb[4 * i + 2] = P.cdef_uv >> 2; sb[4 * i + 3] = P.cdef_uv & 3; }
     G_TRY(dev_alloc(g, &g->d_cdef_sb[t], sb.size())); G_TRY(av1mi_upload(g->ctx, g->d_cdef_sb[t], sb.data(), sb.size()));
+    g->cdef_q[t] = c.base_q_idx;
   }
   {
     const av1mi_frame_params &P = g->params[0];     // the restoration units do not depend on the frame type
@@ -310,6 +316,7 @@ int setup(av1mi_gop *g) {
   }
   g->nb = g->plane[0].n / 64;
   g->fmt = c.input_format;
+  g->next_q = c.base_q_idx;
   const bool scaling = c.source_width != 0;
   g->src_bd = c.source_bit_depth ? c.source_bit_depth : c.bit_depth;
   g->chroma_stage = c.source_chroma != AV1MI_CHROMA_420 || g->src_bd != c.bit_depth;
@@ -453,7 +460,7 @@ static int code_blocks(av1mi_gop *g, Slot &s, int frame_type, const void *const 
   if (frame_type == 0) {
     av1mi_intra_job j;
     memset(&j, 0, sizeof(j));
-    j.width = w; j.height = h; j.bit_depth = c.bit_depth; j.nframes = c.segments; j.qindex = c.base_q_idx; j.block_size = 8; j.stride_y = g->plane[0].w; j.stride_uv = g->plane[1].w;
+    j.width = w; j.height = h; j.bit_depth = c.bit_depth; j.nframes = c.segments; j.qindex = s.q; j.block_size = 8; j.stride_y = g->plane[0].w; j.stride_uv = g->plane[1].w;
     j.d_src_y = src[0]; j.d_src_u = src[1]; j.d_src_v = src[2];
     j.d_rec_y = g->d_rec[0]; j.d_rec_u = g->d_rec[1]; j.d_rec_v = g->d_rec[2];
     j.d_lev_y = (int16_t *)s.d_lev[0]; j.d_lev_u = (int16_t *)s.d_lev[1]; j.d_lev_v = (int16_t *)s.d_lev[2];
@@ -481,7 +488,7 @@ static int code_blocks(av1mi_gop *g, Slot &s, int frame_type, const void *const 
   } else {
     av1mi_inter_job j;
     memset(&j, 0, sizeof(j));
-    j.width = w; j.height = h; j.bit_depth = c.bit_depth; j.nframes = c.segments; j.qindex = c.base_q_idx; j.search_range = c.search_range; j.stride_y = g->plane[0].w; j.stride_uv = g->plane[1].w;
+    j.width = w; j.height = h; j.bit_depth = c.bit_depth; j.nframes = c.segments; j.qindex = s.q; j.search_range = c.search_range; j.stride_y = g->plane[0].w; j.stride_uv = g->plane[1].w;
     j.d_src_y = src[0]; j.d_src_u = src[1]; j.d_src_v = src[2];
     j.d_ref_y = g->d_ref[0]; j.d_ref_u = g->d_ref[1]; j.d_ref_v = g->d_ref[2];
     j.d_rec_y = g->d_rec[0]; j.d_rec_u = g->d_rec[1]; j.d_rec_v = g->d_rec[2];
@@ -518,11 +525,43 @@ static int extend_plane(av1mi_gop *g, const Plane &P, void *d) {
   return av1mi_extend_frames(g->ctx, d, P.w, P.w, P.h, P.vw, P.vh, g->cfg.bit_depth, g->cfg.segments);
 }
 
+// The device state derived from the quantiser follows the batch: the deblocking map pair this batch's filters read (key / inter / key in
+// 32x32 blocks) and the CDEF strength records of its frame type.  They exist once (the batches are serial on the main stream), so
+// where they hold the levels of another quantiser than the batch's, ONE launch of k_mi_levels (levels_kernels.hip) on the main stream
+// patches the level fields in place: behind the previous batch's filters, their last readers, and in front of this batch's.  The
+// geometry the host wrote at open stays.  No host copy, no synchronisation; and no launch while the quantiser stays what the arrays hold,
+// so a session on which av1mi_gop_set_base_q_idx is never called launches what it always did.
+static int follow_q(av1mi_gop *g, const Slot &s) {
+  const int t = s.frame_type, m = t == 0 && g->key32 ? 2 : t;
+  const av1mi_frame_params &P = s.params;
+  av1mi::LevelsLaunch L;
+  memset(&L, 0, sizeof(L));
+  if (g->mi_q[m] != s.q) {
+    const size_t fy = (size_t)g->cfg.width * g->cfg.height;
+    const uint32_t keep = ~0x00FFFF00u, hold = 1u << 24;      // the two level bytes; off-screen words ("skipped inter block") keep level 0
+    L.a[L.arrays++] = { (uint32_t *)g->d_mi[m][0], fy / 16, keep, (uint32_t)P.lf_level[0] << 8 | (uint32_t)P.lf_level[1] << 16, hold };
+    L.a[L.arrays++] = { (uint32_t *)g->d_mi[m][1], fy / 64, keep, (uint32_t)P.lf_level[2] << 8 | (uint32_t)P.lf_level[2] << 16, hold };
+    g->mi_q[m] = s.q;
+  }
+  if (g->cdef_q[t] != s.q) {      // one dword per superblock: primary / secondary strength of luma, then of chroma
+    const size_t nsb = (size_t)((g->cfg.width + 63) / 64) * ((g->cfg.height + 63) / 64);
+    L.a[L.arrays++] = { (uint32_t *)g->d_cdef_sb[t], nsb, 0u,
+                        (uint32_t)(P.cdef_y >> 2) | (uint32_t)(P.cdef_y & 3) << 8 | (uint32_t)(P.cdef_uv >> 2) << 16 | (uint32_t)(P.cdef_uv & 3) << 24, 0u };
+    g->cdef_q[t] = s.q;
+  }
+  if (!L.arrays) return AV1MI_OK;
+  hipStream_t main = av1mi::ctx_stream(g->ctx);
+  av1mi::ProfScope ps(g->ctx, AV1MI_K_MISC, main);
+  G_HIP(av1mi::launch_mi_levels(L, main));
+  return AV1MI_OK;
+}
+
 // in-loop filters: reconstruction -> what the next frame predicts from; then filters_done and (symbols_down) the decision -> downloaded
 static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
   const av1mi_gop_config &c = g->cfg;
   const int w = c.width, h = c.height, S = c.segments, bd = c.bit_depth, key = s.frame_type == 0;
-  const av1mi_frame_params &P = g->params[s.frame_type];
+  const av1mi_frame_params &P = s.params;
+  G_TRY(follow_q(g, s));
   for (int p = 0; p < 3; p++) {
     const Plane &L = g->plane[p];
     G_TRY(av1mi_deblock_frames(g->ctx, g->d_rec[p], L.w, g->d_dbl[p], L.w, L.w, L.h, bd, L.ss, (const uint32_t *)g->d_mi[key && g->key32 ? 2 : s.frame_type][L.ss], L.w / 4, 0,
@@ -608,7 +647,7 @@ static int finish_entropy(av1mi_gop *g, Slot &s, hipStream_t st) {
 // next batch's tokenizer does not wait for it)
 static int start_coder(av1mi_gop *g, Slot &s) {
   const av1mi_gop_config &c = g->cfg;
-  const av1mi_frame_params &P = g->params[s.frame_type];
+  const av1mi_frame_params &P = s.params;
   hipStream_t main = av1mi::ctx_stream(g->ctx), side = av1mi::ctx_side_stream(g->ctx), back = av1mi::ctx_back_stream(g->ctx);
   if (!side || !back) return av1mi::ctx_fail(g->ctx, AV1MI_E_DEVICE, "no side stream");
   if (g->coder_streams == 1) back = side;                 // diagnostic arrangements (AV1MI_CODER_STREAMS): the whole coder on the side stream
@@ -616,7 +655,7 @@ static int start_coder(av1mi_gop *g, Slot &s) {
   if (side != main) G_HIP(hipStreamWaitEvent(side, s.filters_done, 0));
   av1mi_av1_entropy_job ej;
   memset(&ej, 0, sizeof(ej));
-  ej.width = c.width; ej.height = c.height; ej.nframes = c.segments; ej.key = s.frame_type == 0; ej.base_q_idx = c.base_q_idx;
+  ej.width = c.width; ej.height = c.height; ej.nframes = c.segments; ej.key = s.frame_type == 0; ej.base_q_idx = s.q;
   ej.d_lev_y = (const int16_t *)s.d_lev[0]; ej.d_lev_u = (const int16_t *)s.d_lev[1]; ej.d_lev_v = (const int16_t *)s.d_lev[2];
   ej.d_modes_y = (const uint8_t *)s.d_modes[0]; ej.d_modes_uv = (const uint8_t *)s.d_modes[1];
   ej.d_mvs = (const int16_t *)s.d_mv; ej.d_skip = (const uint8_t *)s.d_skip;
@@ -649,6 +688,10 @@ static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src
   if (frame_type == 1 && g->submitted == 0) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "the first frame of a session must be a key frame");
   G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
   Slot &s = g->slot[g->submitted % kSlots];
+  // the batch's quantiser: fixed here, whatever av1mi_gop_set_base_q_idx is told while the batch is in flight
+  s.q = g->next_q;
+  if (s.q == g->cfg.base_q_idx) s.params = g->params[frame_type];
+  else frame_params(s.q, g->cfg.bit_depth, frame_type, &s.params);
   const void *src[3];
   G_TRY(feed_source(g, s, dev_src, src));
   if (s.ent_pending) G_HIP(hipStreamWaitEvent(av1mi::ctx_stream(g->ctx), s.ent_done, 0));      // the GPU coder of the slot's previous batch still reads its symbols
@@ -671,6 +714,13 @@ static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src
 }
 
 extern "C" {
+
+int av1mi_gop_set_base_q_idx(av1mi_gop *g, int base_q_idx) {
+  if (!g) return AV1MI_E_INVAL;
+  if (base_q_idx < 1 || base_q_idx > 255) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "base_q_idx %d must lie in 1..255", base_q_idx);
+  g->next_q = base_q_idx;
+  return AV1MI_OK;
+}
 
 int av1mi_gop_pending(av1mi_gop *g) { return g ? (int)(g->submitted - g->collected) : 0; }
 long av1mi_gop_entropy_fallbacks(av1mi_gop *g) { return g ? g->fallbacks : 0; }
@@ -709,7 +759,7 @@ int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out) {
   Slot &s = g->slot[g->collected % kSlots];
   if (s.symbols_down) G_HIP(hipEventSynchronize(s.downloaded));
   memset(out, 0, sizeof(*out));
-  out->params = g->params[s.frame_type];
+  out->params = s.params;
   out->lr_on = (const uint8_t *)s.h_lr_on;
   if (g->cfg.quality_stats) { G_HIP(hipEventSynchronize(s.quality_done)); out->quality = (const av1mi_quality *)s.h_quality; }
   out->segments = g->cfg.segments;

@@ -16,12 +16,14 @@
 #include <unistd.h>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <thread>
 #include <vector>
 #include "../../include/av1mi.h"
 #include "../csrc/quality.hpp"
 #include "av1_bitstream.hpp"
 #include "mux.hpp"
+#include "ratecontrol.hpp"
 #include "y4m.hpp"
 
 namespace av1mi_host {
@@ -206,10 +208,29 @@ int RunBackend(const BackendJob &job, std::string *err) {
     std::vector<std::vector<std::vector<uint8_t>>> units((size_t)S);   // [segment][frame] temporal units of the batch in flight
     struct Rec { av1mi_quality q[3]; };
     std::vector<std::vector<Rec>> records((size_t)S);                  // ... and their quality records (measure)
+    // A target (-b:v:0 / -av1mi_target_bpp): the controller lives across the groups.  It is asked at ONE point of the loop (before each
+    // submit) and told at one (after each assemble), so the quantisers, and with them the output bytes, are a function of the input alone.
+    std::unique_ptr<RateControl> rc;
+    std::vector<std::vector<int>> qs((size_t)S);                       // ... and, with a target, their quantisers (the stats file's q:)
+    long long rc_bytes = 0, rc_frames = 0;
+    if (job.bitrate || job.target_bpp_u) {
+      av1mi_rc_params rp;
+      memset(&rp, 0, sizeof(rp));
+      av1mi_rc_defaults(&rp);
+      if (job.bitrate) { rp.target_num = job.bitrate * y.fps_d; rp.target_den = 8ll * y.fps_n; }
+      else { rp.target_num = job.target_bpp_u * tw * th; rp.target_den = 8000000; }
+      if (job.qmin) rp.qmin = job.qmin;
+      if (job.qmax) rp.qmax = job.qmax;
+      rp.gop_length = G; rp.bit_depth = y.bd;
+      rp.start_q = std::min(std::max(cfg.base_q_idx, rp.qmin), rp.qmax);
+      if (const char *why = RateControl::ParamError(rp)) { *err = std::string("Invalid argument: rate control: ") + why; code = 1; goto done; }
+      rc.reset(new RateControl(rp));
+    }
     const int lag = av1mi_gop_max_in_flight() - 1;      // batches the GPU holds while the host works on the oldest
     for (long g0 = 0;; g0 += S) {
       for (auto &u : units) u.clear();
       for (auto &r : records) r.clear();
+      for (auto &v : qs) v.clear();
       // the next GROUP of S GOPs: a file is read in place, a stream one group ahead of the encoder (y4m.hpp)
       const long have_frames = y.prepare(g0 * G, (long)S * G, err);
       if (have_frames < 0) { code = 1; goto done; }
@@ -225,10 +246,13 @@ int RunBackend(const BackendJob &job, std::string *err) {
         return true;
       };
       auto assemble = [&](int t) -> bool {         // the collected batch t -> temporal units (frame header + tile group, or the host coder)
+        long long batch_bytes = 0;
         for (int s = 0; s < S; s++) {
           if (!exists(s, t)) continue;
           std::vector<uint8_t> tu;
           if (!SessionTemporalUnit(fr, s, w, h, y.bd, cfg.visible_width, cfg.visible_height, t == 0, threads, &tu, err)) return false;
+          batch_bytes += (long long)tu.size();
+          if (rc) qs[(size_t)s].push_back(fr.params.base_q_idx);
           units[(size_t)s].push_back(std::move(tu));
           if (measure) {
             if (!fr.quality) { *err = "the session returned no quality records"; return false; }
@@ -236,6 +260,10 @@ int RunBackend(const BackendJob &job, std::string *err) {
             memcpy(r.q, fr.quality + (size_t)s * 3, sizeof(r.q));
             records[(size_t)s].push_back(r);
           }
+        }
+        if (rc) {      // the truth replaces the controller's prediction for this batch; segments that do not exist count nowhere
+          rc_bytes += batch_bytes;
+          if (rc->Collected(batch_bytes) != 0) { *err = "rate control: nothing in flight"; return false; }
         }
         return true;
       };
@@ -277,6 +305,14 @@ int RunBackend(const BackendJob &job, std::string *err) {
       if (T > 0 && !start_reads(0)) { code = 2; goto done; }
       for (int t = 0; t < T; t++) {
         if (!reads.join()) { *err = job.input + ": Invalid data found when processing input (truncated frame)"; code = 1; goto done; }
+        if (rc) {
+          int frames = 0;
+          for (int s = 0; s < S; s++) frames += exists(s, t) ? 1 : 0;
+          rc_frames += frames;
+          const int q = rc->NextQ(t == 0 ? 0 : 1, frames);
+          if (q < 1) { *err = "rate control: no quantiser for the next batch"; code = 2; goto done; }
+          CHK(av1mi_gop_set_base_q_idx(gop, q));
+        }
         CHK(av1mi_gop_submit(gop, t == 0 ? 0 : 1));
         const bool have = t >= lag;
         if (have && !collect_oldest()) { code = 2; goto done; }            // the GPU works on the frames after it meanwhile
@@ -294,6 +330,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
             char line[512];
             int n = snprintf(line, sizeof(line), "n:%ld type:%c bytes:%zu", summary.frames, t == 0 ? 'K' : 'P', units[(size_t)s][t].size());
             n += av1mi::quality::format_figures(av1mi::quality::frame_figures(records[(size_t)s][t].q, y.bd), line + n, sizeof(line) - (size_t)n);
+            if (rc) n += snprintf(line + n, sizeof(line) - (size_t)n, " q:%d", qs[(size_t)s][t]);
             stats.append(line, (size_t)n); stats += '\n';
             summary.add(records[(size_t)s][t].q, y.bd);
             total_bytes += (long long)units[(size_t)s][t].size();
@@ -301,6 +338,12 @@ int RunBackend(const BackendJob &job, std::string *err) {
     }
     if (total_frames == 0) { *err = job.input + ": Invalid data found when processing input (no frames)"; code = 1; goto done; }
     if (!sink.close(err)) { code = 1; goto done; }
+    if (rc && rc_frames > 0) {
+      const av1mi_rc_params &rp = rc->params();
+      const double fps = (double)y.fps_n / y.fps_d, px = (double)tw * th, want = 8.0 * rp.target_num / rp.target_den, got = 8.0 * rc_bytes / rc_frames;
+      fprintf(stderr, "[av1mi] rate control: target %.0f bit/s (%.4f bit/pixel), achieved %.0f bit/s (%.4f bit/pixel) over %lld frames\n", want * fps, want / px,
+              got * fps, got / px, rc_frames);
+    }
     if (measure) {
       const av1mi::quality::Figures f = summary.figures(y.bd);
       if (!job.stats_path.empty()) {

@@ -23,6 +23,30 @@ int av1mi_host_transcode_args(const char *in, const char *out, int has_video, in
   strncpy(buf, j.c_str(), cap - 1); buf[cap - 1] = 0;
   return ok ? (int)a.size() : -1;
 }
+// the argv ProcessJob runs: the reference's (TranscodeArgs) plus what a TranscodeConfig with TargetBitsPerPixel adds; same convention
+int av1mi_host_job_args(const char *in, const char *out, int height, int webrip, double target_bpp, char *buf, int cap) {
+  ProbeResult pr; pr.has_video_stream = true; pr.VideoStream.Height = height;
+  std::vector<std::string> a; std::string err;
+  if (!TranscodeArgs("ffmpeg", in, out, pr, webrip != 0, &a, &err)) return -1;
+  TranscodeConfig cfg; cfg.TargetBitsPerPixel = target_bpp;
+  AppendConfigArgs(cfg, &a);
+  std::string j;
+  for (size_t i = 0; i < a.size(); i++) j += (i ? "\n" : "") + a[i];
+  strncpy(buf, j.c_str(), cap - 1); buf[cap - 1] = 0;
+  return (int)a.size();
+}
+// ParseBackendJob's view of the rate options for an argv joined with '\n': 0 and out = { bits per second, millionths of a bit per pixel,
+// qmin, qmax, quality }, or -1 with the text in err
+int av1mi_host_parse_rate_options(const char *joined, long long *out, char *err, int cap) {
+  std::vector<std::string> a; std::string s = joined; size_t p = 0, q;
+  while ((q = s.find('\n', p)) != std::string::npos) { a.push_back(s.substr(p, q - p)); p = q + 1; }
+  a.push_back(s.substr(p));
+  BackendJob job; std::string e;
+  const bool ok = ParseBackendJob(a, &job, &e);
+  strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
+  out[0] = job.bitrate; out[1] = job.target_bpp_u; out[2] = job.qmin; out[3] = job.qmax; out[4] = job.quality;
+  return ok ? 0 : -1;
+}
 // Y4mSource (y4m.hpp) alone, for the CPU tests: reads the whole input in groups of `group` frames the way RunBackend does and
 // returns the number of frames (-1 on error, text in err); *sum = a checksum over every frame's padded planes; *seekable = the mode
 long long av1mi_host_y4m_scan(const char *path, int group, unsigned long long *sum, int *seekable, int *geometry, char *err, int cap) {

@@ -111,6 +111,23 @@ bool CheckFileStable(const std::string &path, int waitSeconds, bool *stable, std
   return true;
 }
 
+void AppendConfigArgs(const TranscodeConfig &cfg, std::vector<std::string> *a) {
+  std::vector<std::string> &args = *a;
+  if (cfg.Device) { const std::string out = args.back(); args.back() = "-av1mi_device"; args.push_back(std::to_string(cfg.Device)); args.push_back(out); }
+  if (cfg.MeRange) { const std::string out = args.back(); args.back() = "-av1mi_me_range"; args.push_back(std::to_string(cfg.MeRange)); args.push_back(out); }
+  if (cfg.Format420) { const std::string out = args.back(); args.back() = "-av1mi_format"; args.push_back("420"); args.push_back(out); }
+  if (cfg.MinPSNR > 0) {
+    char bound[32];
+    snprintf(bound, sizeof(bound), "%.6f", cfg.MinPSNR);
+    const std::string out = args.back(); args.back() = "-av1mi_min_psnr"; args.push_back(bound); args.push_back(out);
+  }
+  if (cfg.TargetBitsPerPixel > 0) {
+    char bpp[32];
+    snprintf(bpp, sizeof(bpp), "%.6f", cfg.TargetBitsPerPixel);
+    const std::string out = args.back(); args.back() = "-av1mi_target_bpp"; args.push_back(bpp); args.push_back(out);
+  }
+}
+
 std::string ProcessJob(Job *job, const std::string &backendPath, const ProbeResult &probeResult, const TranscodeConfig &cfg) {
   bool stable = false;
   std::string err;
@@ -129,14 +146,7 @@ std::string ProcessJob(Job *job, const std::string &backendPath, const ProbeResu
     job->Status = "failed"; job->Reason = "failed to build ffmpeg args: " + err; save_job(*job, cfg.JobStateDir);
     return "failed to build transcode args: " + err;
   }
-  if (cfg.Device) { const std::string out = args.back(); args.back() = "-av1mi_device"; args.push_back(std::to_string(cfg.Device)); args.push_back(out); }
-  if (cfg.MeRange) { const std::string out = args.back(); args.back() = "-av1mi_me_range"; args.push_back(std::to_string(cfg.MeRange)); args.push_back(out); }
-  if (cfg.Format420) { const std::string out = args.back(); args.back() = "-av1mi_format"; args.push_back("420"); args.push_back(out); }
-  if (cfg.MinPSNR > 0) {
-    char bound[32];
-    snprintf(bound, sizeof(bound), "%.6f", cfg.MinPSNR);
-    const std::string out = args.back(); args.back() = "-av1mi_min_psnr"; args.push_back(bound); args.push_back(out);
-  }
+  AppendConfigArgs(cfg, &args);
   const RunResult rr = RunTranscode(backendPath, args);                                                                                 // :101
   if (rr.exitCode == 3 && rr.err.compare(0, 14, "quality gate: ") == 0) {      // refused like a file the size gate refuses (:129-150)
     job->Status = "skipped"; job->Reason = rr.err;

@@ -47,7 +47,13 @@ struct TranscodeConfig {           // daemon.go:185-188; Device is this backend'
   // -av1mi_format 420 on every job (BackendJob::to_420).  The reference's chain, which ProcessJob always passes, already says so with
   // its format=nv12; the option states it for callers that build their own argv without a chain.
   bool Format420 = false;
+  // A target size instead of the fixed quantiser: bits per pixel per frame (-av1mi_target_bpp; 0 = off, the default: the argv is then the
+  // reference's, and -global_quality maps 1:1 to the quantiser).  The reference's own estimate expects 0.15 / 0.12 / 0.10 at quality
+  // 23 / 24 / 25 (cmd/av1d/main.go:413-427): a caller that wants the size gate to pass asks for that here.
+  double TargetBitsPerPixel = 0;
 };
+// the options a TranscodeConfig adds to the reference's argv (TranscodeArgs), in front of the output path; nothing for a default config
+void AppendConfigArgs(const TranscodeConfig &cfg, std::vector<std::string> *args);
 
 // daemon.go:57-182.  Returns "" where the reference returns nil, else the error text; job.Status / job.Reason are
 // updated exactly as upstream ("running" -> "success" | "failed" | "skipped").

@@ -1,13 +1,15 @@
 // av1mi_transcode — CLI with the reference's process contract (exit code, stderr text, output file last):
 //   av1mi_transcode [ffmpeg-style args] -i in.y4m [-global_quality:v:0 Q] [-g GOP] [-vf:v:0 CHAIN] [-av1mi_scale WxH]
-//                   [-av1mi_stats FILE] [-av1mi_min_psnr DB] [-av1mi_me_range N] [-av1mi_format 420] out.av1-tmp.mkv
+//                   [-av1mi_stats FILE] [-av1mi_min_psnr DB] [-av1mi_me_range N] [-av1mi_format 420]
+//                   [-b:v:0 BITS[k|M] | -av1mi_target_bpp X] [-qmin Q] [-qmax Q] out.av1-tmp.mkv
+//                   (-b:v:0 / -av1mi_target_bpp: a target instead of the fixed quantiser; -global_quality is then where the controller starts)
 //                   (-av1mi_format 420, or a format= filter naming a 4:2:0 format in CHAIN: 4:2:2 / 4:4:4 / grey and 12-bit sources are
 //                   accepted and converted to 4:2:0 on the GPU)
 //                   (-av1mi_stats: per-frame PSNR / SSIM measured on the GPU; -av1mi_min_psnr: fail with exit code 3 below that luma PSNR)
 //                   (-av1mi_me_range: 0, or a multiple of 4 up to 64: the P frames' motion search follows N + 8 samples per frame)
 //                   (CHAIN: the reference's scale filters, evaluated on the source's size and sample aspect ratio and applied on the GPU;
 //                   -av1mi_scale: an explicit output size, wins over the chain; any other filter is refused)
-//   av1mi_transcode --job in.y4m [--ratio 0.9] [--state DIR] [--wait S] [--replace-source 1] [--min-psnr DB] [--me-range N] [--format 420]   (the ProcessJob lifecycle;
+//   av1mi_transcode --job in.y4m [--ratio 0.9] [--state DIR] [--wait S] [--replace-source 1] [--min-psnr DB] [--me-range N] [--format 420] [--target-bpp X]   (the ProcessJob lifecycle;
 //                   the source is only replaced on request: the output is video-only)
 #include <cstdio>
 #include <cstdlib>
@@ -33,6 +35,7 @@ int main(int argc, char **argv) {
       else if (!strcmp(argv[i], "--min-psnr")) cfg.MinPSNR = atof(argv[i + 1]);
       else if (!strcmp(argv[i], "--me-range")) cfg.MeRange = atoi(argv[i + 1]);
       else if (!strcmp(argv[i], "--format")) cfg.Format420 = !strcmp(argv[i + 1], "420");
+      else if (!strcmp(argv[i], "--target-bpp")) cfg.TargetBitsPerPixel = atof(argv[i + 1]);
     }
     struct stat st;
     if (!stat(job.SourcePath.c_str(), &st)) job.OriginalSize = st.st_size;
@@ -53,6 +56,7 @@ int main(int argc, char **argv) {
       else if (!strcmp(argv[i], "--min-psnr") && i + 1 < argc) cfg.MinPSNR = atof(argv[++i]);
       else if (!strcmp(argv[i], "--me-range") && i + 1 < argc) cfg.MeRange = atoi(argv[++i]);
       else if (!strcmp(argv[i], "--format") && i + 1 < argc) cfg.Format420 = !strcmp(argv[++i], "420");
+      else if (!strcmp(argv[i], "--target-bpp") && i + 1 < argc) cfg.TargetBitsPerPixel = atof(argv[++i]);
       else {
         Job j; j.ID = "job" + std::to_string(jobs.size()); j.SourcePath = argv[i];
         struct stat st;

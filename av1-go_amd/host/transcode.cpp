@@ -1,6 +1,7 @@
 // transcode.cpp — see transcode.hpp.  Argument vector and error strings follow internal/ffmpeg/transcode.go.
 #include "transcode.hpp"
 #include "backend.hpp"
+#include <cmath>
 #include <cstdio>
 
 namespace av1mi_host {
@@ -134,6 +135,30 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
       // a finite bound: nan fails the first comparison, inf (which every lossy file would miss) the second
       if (args[i + 1].empty() || *end || !(job->min_psnr >= 0) || !(job->min_psnr <= 1e308)) { if (err) *err = "Invalid argument: -av1mi_min_psnr takes a finite bound in dB (0 = off), not " + args[i + 1]; return false; }
     }
+    else if (args[i] == "-b:v:0" || args[i] == "-b:v") {
+      const std::string &v = args[i + 1];
+      size_t n = 0;
+      long long bits = 0;
+      while (n < v.size() && n < 13 && v[n] >= '0' && v[n] <= '9') bits = bits * 10 + (v[n++] - '0');
+      const std::string suffix = v.substr(n);
+      if (suffix == "k" || suffix == "K") bits *= 1000; else if (suffix == "M") bits *= 1000000;
+      if (n == 0 || n > 12 || (!suffix.empty() && suffix != "k" && suffix != "K" && suffix != "M") || bits < 1 || bits > 1000000000000ll) {
+        if (err) *err = "Invalid argument: " + args[i] + " takes bits per second (a positive integer, suffix k or M), not " + v;
+        return false;
+      }
+      job->bitrate = bits;
+    }
+    else if (args[i] == "-av1mi_target_bpp") {
+      char *end = nullptr;
+      const double x = std::strtod(args[i + 1].c_str(), &end);
+      if (args[i + 1].empty() || *end || !(x >= 0.000001) || !(x <= 64)) { if (err) *err = "Invalid argument: -av1mi_target_bpp takes bits per pixel per frame (0.000001 .. 64), not " + args[i + 1]; return false; }
+      job->target_bpp_u = std::llround(x * 1e6);
+    }
+    else if (args[i] == "-qmin" || args[i] == "-qmax") {
+      int v = 0;
+      if (!plain_int(args[i + 1], &v) || v < 1 || v > 255) { if (err) *err = "Invalid argument: " + args[i] + " takes a quantiser index 1 .. 255, not " + args[i + 1]; return false; }
+      (args[i] == "-qmin" ? job->qmin : job->qmax) = v;
+    }
     else if (args[i] == "-vf:v:0" || args[i] == "-vf") { job->vf = args[i + 1]; job->have_vf = true; }
     else if (args[i] == "-av1mi_scale") {
       const std::string &v = args[i + 1];
@@ -151,6 +176,9 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
     if (!ScaleTarget(16, 16, 1, 1, job->vf, &w, &h, nullptr, err, &to_420)) return false;
     if (to_420) job->to_420 = true;
   }
+  if (job->bitrate && job->target_bpp_u) { if (err) *err = "Invalid argument: -b:v:0 and -av1mi_target_bpp are two forms of one target: give one"; return false; }
+  if ((job->qmin || job->qmax) && !job->bitrate && !job->target_bpp_u) { if (err) *err = "Invalid argument: -qmin / -qmax need a target (-b:v:0 or -av1mi_target_bpp)"; return false; }
+  if (job->qmin && job->qmax && job->qmin > job->qmax) { if (err) *err = "Invalid argument: -qmin " + std::to_string(job->qmin) + " above -qmax " + std::to_string(job->qmax); return false; }
   if (!have_in) { if (err) *err = "Invalid argument: no input (-i) given"; return false; }
   if (job->quality < 0 || job->quality > 255 || job->gop < 1 || job->gop > 256 || job->segments < 1 || job->segments > 256 || job->threads < 0 || (job->key_block_size != 8 && job->key_block_size != 32) || (job->pack10 != 0 && job->pack10 != 1)) { if (err) *err = "Invalid argument: quality/gop/key block size/pack10 out of range"; return false; }
   return true;

@@ -63,6 +63,13 @@ struct BackendJob {
                            // transcode fails with exit code 3, "quality gate: psnr_y ...", and the output is removed
   int me_range = 0;        // -av1mi_me_range N: 0 (default), or a multiple of 4 up to 64: P frames search around a coarse centre per 64x64 tile
                            // (av1mi_gop_config.coarse_range): vectors reach N + 8 samples per frame instead of 8
+  // A target instead of the fixed quantiser (host/ratecontrol.hpp: one quantiser per batch, chosen from the bytes of the batches before).
+  // -b:v:0 N (alias -b:v; FFmpeg's k / M suffixes): bits per second of the video; -av1mi_target_bpp X: bits per pixel per frame of the coded
+  // picture's true size, the form of the reference's own estimate (cmd/av1d/main.go:413-427: 0.15 / 0.12 / 0.10).  One of the two at most.
+  // -global_quality:v:0 is then the START quantiser; -qmin / -qmax (only with a target) bound what the controller may choose.  0 = not given
+  long long bitrate = 0;
+  long long target_bpp_u = 0;   // in millionths of a bit per pixel
+  int qmin = 0, qmax = 0;
   bool to_420 = false;     // the job converts its source to 4:2:0: the chain has a format= filter naming a 4:2:0 format (nv12, p010, p010le, yuv420p,
                            // yuv420p10le — the reference's chain always does, transcode.go:99-110), or -av1mi_format 420 was given.  The source may then be
                            // 4:2:2, 4:4:4 or grey, at 8, 10 or 12 bits (Y4mSource::open's any_layout); it is converted on the GPU (av1mi.h "chroma formats").

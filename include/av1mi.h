@@ -613,6 +613,16 @@ int av1mi_gop_submit(av1mi_gop *g, int frame_type);
  * collected.  No av1mi_gop_acquire_input() before it.  (A decoder that leaves its frames in HBM feeds the session this way; bench.py
  * times this path, the bench contract's "inputs already resident in HBM".) */
 int av1mi_gop_submit_device(av1mi_gop *g, const void *d_y, const void *d_u, const void *d_v, int frame_type);
+/* The quantiser belongs to the BATCH.  Every batch submitted after this call (av1mi_gop_submit, av1mi_gop_submit_device) is coded at
+ * base_q_idx, until the next call; a session on which it is never called codes every batch at av1mi_gop_config.base_q_idx and allocates
+ * and launches what it always did.  1..255, else AV1MI_E_INVAL (with a text, and nothing changes).  Batches already in flight keep the
+ * quantiser they were submitted with.  One value per batch: all its segments share it (the stacked launches take one).  From it follow
+ * the batch's av1mi_frame_params (av1mi_policy_frame_params(base_q_idx, bit_depth, frame type): what av1mi_gop_collect hands out in
+ * av1mi_gop_frame.params, base_q_idx included), the quantiser of the block pipeline, the default CDF set of the tile coder, the
+ * deblocking levels, the CDEF strengths and damping.  The call neither synchronises nor copies anything from the host: where the
+ * device-side deblocking maps and CDEF records hold another quantiser's levels than the batch's, one small launch (k_mi_levels) in
+ * front of the batch's filters patches the level fields in place. */
+int av1mi_gop_set_base_q_idx(av1mi_gop *g, int base_q_idx);
 /* wait for the oldest batch in flight and describe its symbols; AV1MI_E_INVAL when nothing is in flight */
 int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out);
 /* number of batches in flight (0..av1mi_gop_max_in_flight()) */

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "av1mi.h"
+#include "av1mi_rc.h"   /* the one-pass rate controller: av1mi_rc_open / _next_q / _collected / _close / _qstep / _defaults */
 
 #ifdef __cplusplus
 extern "C" {
