@@ -5,9 +5,9 @@
 //
 // The syntax is av1_ops.hpp + av1_ops32.hpp (key frames in 32x32 blocks; shared source with the host's CPU twin, byte-identical
 // to the dav1d-verified writer), in three stages:
-//   k_av1_info     thread per block: level-context summary of the block + (inter) the mode that codes its vector
-//   k_av1_tokens   workgroup per tile, thread per block in z-order: the block's syntax elements, counted, placed, written —
-//                  literals into the tile's list, adaptive symbols as entries grouped by CDF slot
+//   k_av1_info     inter frames, thread per block: the mode that codes the block's vector
+//   k_av1_tokens   workgroup per tile, thread per block in z-order (av1_ops8.hpp): the block's syntax elements, counted, placed,
+//                  written — literals into the tile's list, adaptive symbols as entries grouped by CDF slot
 //   k_av1_chains   a slot's CDF evolves with that slot's symbols only: one lane per (tile, slot) walks the slot's entries with the
 //                  CDF in registers and writes, at each element's place in the list, the tuple (icdf[s - 1], icdf[s], n - s) the
 //                  range coder needs.  The serial dependency of a tile drops from all its symbols (4000-8000) to its longest
@@ -18,7 +18,7 @@
 #include <string.h>
 #include <vector>
 #include "av1_ops_cdfs.hpp"
-#include "av1_ops32.hpp"
+#include "av1_ops8.hpp"
 #include "av1mi_internal.hpp"
 
 namespace av1mi {
@@ -60,133 +60,19 @@ template <int kKey = -1> __device__ __forceinline__ FrameView frame_view(const A
   return v;
 }
 
+// inter frames only: the tokenizer of a key frame reads nothing of a block's info
 __global__ __launch_bounds__(256) void k_av1_info(Av1EntLaunch L) {
   const long nb = (long)L.fv.w8 * L.fv.h8, i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= nb * L.nframes) return;
   const int f = (int)(i / nb), b = (int)(i - (long)f * nb);
-  const FrameView v = frame_view(L, f);
+  const FrameView v = frame_view<0>(L, f);
   BlockInfo o = {};
-  block_summary(v, b, &o);
-  if (!v.key) inter_mode_decision(v, b / v.w8, b % v.w8, &o);
+  inter_mode_decision(v, b / v.w8, b % v.w8, &o);
   L.info[nb * f + b] = o;
 }
 
-// the records are replayed in two passes over half of the slots each: the 16-bit positions [slots][64 blocks] of ALL slots were 25 KB
-// of LDS = 6 workgroups per CU; 12.5 KB fit beside nothing larger (counts + magnitudes: 19 KB) = 8, what the registers allow
-constexpr int kReplaySlots = (S_MAX + 1) / 2;
-struct TokLds {
-  union {
-    struct { uint8_t cnt[S_MAX * kBlocksPerTile]; alignas(16) uint8_t mag[kBlocksPerTile * kMagBytes]; } p1;    // while tokenizing
-    uint16_t pos[kReplaySlots * kBlocksPerTile];                                                               // while replaying: half of the slots at a time
-  };
-  uint16_t total[S_MAX], base[S_MAX];
-  ScanTables scan;
-};
-
-// TOKENIZE once (records + counts; every read of a coefficient after the first goes to the thread's LDS copy of the block),
-// PLACE (the counts of the tile's 64 blocks -> where each block's entries of each slot go), REPLAY (records -> list words and
-// grouped entries).  The counts are bytes and share their LDS with the 16-bit positions that replace them: a thread keeps the
-// counts of its slots in registers across the switch.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void k_av1_tokens(Av1EntLaunch L) {
-  const int tiles = L.sbr_n * L.sbc_n, t = blockIdx.x, f = t / tiles, tt = t - f * tiles, sbr = tt / L.sbc_n, sbc = tt - sbr * L.sbc_n;
-  if (sbr < L.sb_rows32) return;           // a tile of the 32x32 band: k_av1_tokens32
-  const FrameView v = frame_view(L, f);
-  const int zi = threadIdx.x, nslots = v.key ? S_KEY_END : S_INTER_END;
-  __shared__ TokLds S;
-  {
-    uint32_t *m = reinterpret_cast<uint32_t *>(S.p1.cnt);
-    for (int i = zi; i < S_MAX * kBlocksPerTile / 4; i += 64) m[i] = 0;
-    if (zi == 0) fill_scan_tables(&S.scan);
-  }
-  __syncthreads();
-  const int below = tiles - L.sb_rows32 * L.sbc_n;      // the records are this band's alone: the frame's tiles below the 32x32 band
-  uint16_t *rec = L.rec + (((size_t)f * below + (tt - (tiles - below))) * kBlocksPerTile + zi) * kBlockRecords;
-  const TokScratch ts = { S.p1.mag + zi * kMagBytes, &S.scan };
-  Sink k = { rec, S.p1.cnt, zi, 0, 0, false };
-  tok_block(v, k, ts, sbr, sbc, zi);
-  int x = k.n;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(x, d, 64);
-    if (zi >= d) x += y;
-  }
-  const int total = __shfl(x, 63, 64), first = x - k.n;
-  if ((uint32_t)total > L.ops_cap || __any(k.overflow)) {
-    if (zi == 0) { atomicOr(L.status, 1u); L.nops[t] = 0; }
-    for (int sl = zi; sl < S_MAX; sl += 64) L.slot_total[(size_t)t * S_MAX + sl] = 0;
-    return;
-  }
-  if (zi == 0) L.nops[t] = (uint32_t)total;
-  __syncthreads();
-  // place: thread zi owns slots zi, zi + 64, ...: their counts into registers, their totals to everybody
-  constexpr int kOwn = (S_MAX + 63) / 64;
-  uint32_t c[kOwn][kBlocksPerTile / 4];
-#pragma unroll
-  for (int q = 0; q < kOwn; q++) {
-    const int sl = zi + 64 * q;
-    int sum = 0;
-#pragma unroll
-    for (int w = 0; w < kBlocksPerTile / 4; w++) {
-      const uint32_t u = sl < nslots ? reinterpret_cast<const uint32_t *>(S.p1.cnt)[sl * (kBlocksPerTile / 4) + w] : 0u;
-      c[q][w] = u;
-      sum = (int)__builtin_amdgcn_sad_u8(u, 0u, (unsigned)sum);      // the four counts of the dword in one instruction
-    }
-    if (sl < S_MAX) S.total[sl] = (uint16_t)sum;
-  }
-  __syncthreads();         // every count is in a register now: the positions may overwrite them
-  {
-    int mine = 0;       // thread zi places slots [4 zi, 4 zi + 4): slots follow each other on 16-byte boundaries
-    for (int q = 0; q < 4; q++) { const int sl = 4 * zi + q; if (sl < nslots) mine += (S.total[sl] + kListAlign - 1) & ~(kListAlign - 1); }
-    int inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int y = __shfl_up(inc, d, 64);
-      if (zi >= d) inc += y;
-    }
-    int run = inc - mine;
-    for (int q = 0; q < 4; q++) { const int sl = 4 * zi + q; if (sl < nslots) { S.base[sl] = (uint16_t)run; run += (S.total[sl] + kListAlign - 1) & ~(kListAlign - 1); } }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < kOwn; q++) {
-    const int sl = zi + 64 * q;
-    if (sl >= S_MAX) continue;
-    const bool on = sl < nslots;
-    L.slot_total[(size_t)t * S_MAX + sl] = on ? S.total[sl] : (uint16_t)0;
-    L.slot_base[(size_t)t * S_MAX + sl] = on ? S.base[sl] : (uint16_t)0;
-  }
-  // replay: the thread's own records (it wrote them itself), literals into the list, adaptive symbols into their slot's entries
-  op_t *list = L.ops + (size_t)t * L.ops_cap;
-  uint32_t *grouped = L.grouped + (size_t)t * L.grouped_cap;
-#pragma unroll
-  for (int half = 0; half < 2; half++) {
-    const int lo = half * kReplaySlots, hi = lo + kReplaySlots;
-    if (half) __syncthreads();                      // the first half's positions have been used up
-#pragma unroll
-    for (int q = 0; q < kOwn; q++) {
-      const int sl = zi + 64 * q;
-      if (sl < lo || sl >= hi || sl >= nslots) continue;
-      int run = S.base[sl];
-#pragma unroll
-      for (int w = 0; w < kBlocksPerTile / 4; w++) {
-        const uint32_t u = c[q][w];
-        const int p0 = run, p1 = p0 + (int)(u & 0xFF), p2 = p1 + (int)((u >> 8) & 0xFF), p3 = p2 + (int)((u >> 16) & 0xFF);
-        run = p3 + (int)(u >> 24);
-        uint32_t *d = reinterpret_cast<uint32_t *>(S.pos + (sl - lo) * kBlocksPerTile + 4 * w);
-        d[0] = (uint32_t)p0 | ((uint32_t)p1 << 16); d[1] = (uint32_t)p2 | ((uint32_t)p3 << 16);
-      }
-    }
-    __syncthreads();
-    __threadfence_block();
-    replay_block<kBlocksPerTile>(rec, k.nrec, S.pos, zi, first, list, grouped, lo, hi, half == 0);
-  }
-}
-
-// The tiles of a key frame's 32x32 band: ONE WAVE PER TILE, the lanes over scan ranges of the transform block at hand (av1_ops32.hpp
-// tok_tile32: the levels are read once into magnitude maps in LDS, a counting sweep gives the slots' totals and bases, an emitting
-// sweep writes list words and grouped entries straight to their places) — after which the chains, the range coder and the gather treat
-// the tile like any other.  No records in memory (L.rec is the 8x8 band's).  15.7 KB of LDS per wave: ten waves per CU.
-struct Wave32 {
+// The wave of a tile tokenizer (av1_ops32.hpp: each / scan / first / Var): one workgroup of 64 lanes
+struct TileWave {
   template <class T> using Var = LaneVar<T, 1>;
   template <class F> __device__ __forceinline__ void each(F f) { f((int)threadIdx.x); __syncthreads(); }
   __device__ __forceinline__ int scan(Var<int> &v) {
@@ -202,12 +88,38 @@ struct Wave32 {
   }
   __device__ __forceinline__ int first(Var<int> &v) { return __shfl(v.v[0], 0, 64); }
 };
+
+// The tiles of 8x8 blocks: ONE WAVE PER TILE, a lane per block in z-order (av1_ops8.hpp tok_tile8): the neighbours' level summaries into
+// LDS, TOKENIZE once (records + counts; every read of a coefficient after the first goes to the lane's LDS copy of the block), PLACE (the
+// counts of the tile's 64 blocks -> where each block's entries of each slot go), REPLAY (records -> list words and grouped entries) —
+// once for a tile that uses at most kReplaySlots slots, in two passes otherwise.  19.9 KB of LDS per wave: eight waves per CU, what the
+// registers allow.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void k_av1_tokens(Av1EntLaunch L) {
+  const int tiles = L.sbr_n * L.sbc_n, t = blockIdx.x, f = t / tiles, tt = t - f * tiles, sbr = tt / L.sbc_n, sbc = tt - sbr * L.sbc_n;
+  if (sbr < L.sb_rows32) return;           // a tile of the 32x32 band: k_av1_tokens32
+  const FrameView v = frame_view(L, f);
+  __shared__ Tile8Mem S;
+  const int below = tiles - L.sb_rows32 * L.sbc_n;      // the records are this band's alone: the frame's tiles below the 32x32 band
+  uint16_t *rec = L.rec + ((size_t)f * below + (tt - (tiles - below))) * kBlocksPerTile * kBlockRecords;
+  TileWave w;
+  const int n = tok_tile8(w, S, v, sbr, sbc, rec, L.ops + (size_t)t * L.ops_cap, L.ops_cap, L.grouped + (size_t)t * L.grouped_cap,
+                          L.slot_total + (size_t)t * S_MAX, L.slot_base + (size_t)t * S_MAX);
+  if (threadIdx.x == 0) {
+    if (n < 0) atomicOr(L.status, 1u);
+    L.nops[t] = n < 0 ? 0u : (uint32_t)n;
+  }
+}
+
+// The tiles of a key frame's 32x32 band: ONE WAVE PER TILE, the lanes over scan ranges of the transform block at hand (av1_ops32.hpp
+// tok_tile32: the levels are read once into magnitude maps in LDS, a counting sweep gives the slots' totals and bases, an emitting
+// sweep writes list words and grouped entries straight to their places) — after which the chains, the range coder and the gather treat
+// the tile like any other.  No records in memory (L.rec is the 8x8 band's).  15.7 KB of LDS per wave: ten waves per CU.
 __global__ __launch_bounds__(64) void k_av1_tokens32(Av1EntLaunch L) {
   __shared__ Tile32Mem S;
   const int tiles = L.sbr_n * L.sbc_n, band = L.sb_rows32 * L.sbc_n, f = blockIdx.x / band, tt = blockIdx.x - f * band, sbr = tt / L.sbc_n, sbc = tt - sbr * L.sbc_n;
   const size_t t = (size_t)f * tiles + tt;          // (the band's tiles are a frame's first)
   const FrameView v = frame_view<1>(L, f);
-  Wave32 w;
+  TileWave w;
   const int n = tok_tile32(w, S, v, sbr, sbc, L.ops + t * L.ops_cap, L.ops_cap, L.grouped + t * L.grouped_cap, L.slot_total + t * S_MAX, L.slot_base + t * S_MAX);
   if (threadIdx.x == 0) {
     if (n < 0) atomicOr(L.status, 1u);
@@ -396,7 +308,7 @@ hipError_t launch_av1_front(av1mi_ctx *ctx, const Av1EntLaunch &L, hipStream_t s
   const long nb = (long)L.fv.w8 * L.fv.h8 * L.nframes;
   const int ntiles_all = L.sbr_n * L.sbc_n * L.nframes, ngroups = (ntiles_all + 63) / 64;
   ProfToken t = ctx_prof_begin(ctx, AV1MI_K_ENTROPY_TOKENS, s);
-  hipLaunchKernelGGL(k_av1_info, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, L);
+  if (!L.fv.key) hipLaunchKernelGGL(k_av1_info, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, L);
   if (L.sb_rows32 < L.sbr_n) hipLaunchKernelGGL(k_av1_tokens, dim3((unsigned)ntiles_all), dim3(64), 0, s, L);
   if (L.sb_rows32) hipLaunchKernelGGL(k_av1_tokens32, dim3((unsigned)(L.sb_rows32 * L.sbc_n * L.nframes)), dim3(64), 0, s, L);
   ctx_prof_end(ctx, t, s);

@@ -147,8 +147,8 @@ enum { kBlocksPerTile = 64, kSplitHorz = 14, kSplitVert = 15, kListAlign = 4, kB
 // The tokenizer runs ONCE per block and leaves 16-bit RECORDS, one per syntax element in decoding order:
 //   literal: 1 | n (4 bits, 1..11, << 11) | value (11 bits);     adaptive symbol: 0 | slot (<< 4) | symbol (4 bits)
 // while it counts, per (slot, block), the adaptive symbols (cnt[slot][block], uint8).  Once the counts of all 64 blocks of the tile
-// are known every block's first entry of every slot has its place in the grouped entries (group_positions), and REPLAY turns
-// the block's records into list words and grouped entries without looking at the frame again.
+// are known every block's first entry of every slot has its place in the grouped entries, and REPLAY turns the block's records
+// into list words and grouped entries without looking at the frame again (av1_ops8.hpp: tok_tile8).
 struct Sink {
   uint16_t *rec;            // the block's records (kBlockRecords of them)
   uint8_t *cnt;             // [S_MAX][64]
@@ -166,41 +166,13 @@ struct Sink {
     if (nbits > 0) put(0x8000u | ((unsigned)nbits << 11) | (v & ((1u << nbits) - 1u)));
   }
 };
-// counts of ONE slot over the tile's 64 blocks -> positions of the blocks' first entries; returns the slot's number of entries
-AV1_HD int group_positions(const uint8_t *cnt_slot, uint16_t *pos_slot, int base) {
-  int run = base;
-  for (int b = 0; b < kBlocksPerTile; b++) { const int c = cnt_slot[b]; pos_slot[b] = (uint16_t)run; run += c; }
-  return run - base;
-}
-// block `blk` of a tile of kBlocks: its records -> list words (from index `first`) and grouped entries; pos = [slots][kBlocks]
-// running positions.  The 8x8 kernel replays in two passes over half of the slots each (half the positions in LDS): a pass takes
-// the symbols of slots [slot_lo, slot_hi), whose positions start at pos row 0, and the literals when `literals` is set
-template <int kBlocks>
-AV1_HD void replay_block(const uint16_t *rec, int nrec, uint16_t *pos, int blk, int first, op_t *list, uint32_t *grouped, int slot_lo = 0,
-                         int slot_hi = 1 << 16, bool literals = true) {
-  int n = first;
-  for (int i0 = 0; i0 < nrec; i0 += 8) {        // eight records per load (a dependent 2-byte load per record is a memory round trip each)
-    struct alignas(16) R8 { uint32_t w[4]; } q = *reinterpret_cast<const R8 *>(rec + i0);
-    AV1_UNROLL      // (fully unrolled the eight records are register halves; indexed at run time the array lived in scratch memory)
-    for (int j = 0; j < 8; j++, n++) {
-      if (i0 + j >= nrec) break;
-      const unsigned r = (q.w[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
-      if (r & 0x8000u) { if (literals) list[n] = op_lit((int)((r >> 11) & 15), r & 0x7FFu); }
-      else {
-        const int sl = (int)(r >> 4);
-        if (sl >= slot_lo && sl < slot_hi) { uint16_t &p = pos[(sl - slot_lo) * kBlocks + blk]; grouped[p] = ((uint32_t)n << 4) | (r & 15u); p++; }
-      }
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ frame view
-// what the tokenizer reads: the block pipeline's outputs of ONE frame (device or host pointers) + per-block summaries
-// cul = min(63, sum |level|), dc = 0 none / 1 negative / 2 positive per plane.  Inter frames, from the block's MV prediction list
-// (inter_mode_decision; the list is built ONCE per block): mode = 0 NEAREST 1 NEAR 2 GLOBAL 3 NEW | ref index << 2, flags bit 0 =
-// coded with NEWMV, num = entries of the list, drl bit i = entry i has a nearest-class weight (>= 640), (px, py) = the entry a
-// NEWMV difference is coded against
-struct BlockInfo { uint8_t cul[3], dc[3], mode, flags; uint8_t num, drl; int16_t px, py; uint8_t pad[2]; };
+// what the tokenizer reads: the block pipeline's outputs of ONE frame (device or host pointers) + (inter frames) per-block info from
+// the block's MV prediction list (inter_mode_decision; the list is built ONCE per block): mode = 0 NEAREST 1 NEAR 2 GLOBAL 3 NEW | ref
+// index << 2, flags bit 0 = coded with NEWMV, num = entries of the list, drl bit i = entry i has a nearest-class weight (>= 640),
+// (px, py) = the entry a NEWMV difference is coded against.  (What a block's neighbours need of its LEVELS is the tile's own business:
+// block_levels_summary, kept by the tile tokenizer.)
+struct BlockInfo { uint8_t mode, flags, num, drl; int16_t px, py; };
 struct FrameView {
   int w8, h8;                   // frame size in 8x8 blocks
   int key;                      // 1 key frame, 0 inter frame
@@ -230,18 +202,23 @@ AV1_HD void demorton8(unsigned k, int *bx, int *by) {
   *bx = x; *by = y;
 }
 
-// per-block summary (pass 0): level contexts the neighbours will need
-AV1_HD void block_summary(const FrameView &f, int b, BlockInfo *o) {
-  const int16_t *p[3] = { f.lev_y + (long)b * 64, f.lev_u + (long)b * 16, f.lev_v + (long)b * 16 };
-  const bool skip = !f.key && f.skip[b];
-  for (int pl = 0; pl < 3; pl++) {
-    int cul = 0;
-    const int n = pl ? 16 : 64;
-    for (int i = 0; i < n; i++) cul += iabs(p[pl][i]);
-    o->cul[pl] = skip ? 0 : (uint8_t)imin(cul, 63);
-    o->dc[pl] = skip ? 0 : (uint8_t)(p[pl][0] < 0 ? 1 : p[pl][0] > 0 ? 2 : 0);
+// What the neighbours inside the tile read of block b's levels, in one byte: the DC's sign class (0 none / 1 negative / 2 positive) of
+// Y, U, V in bits 0-1, 2-3, 4-5, "U / V has a non-zero level" in bits 6 / 7 (all a context takes of a neighbour's sum |level| is
+// whether it is zero, and only chroma asks: luma's all_zero context is 0 when the transform covers the block).  0 for a skipped block.
+AV1_HD unsigned block_levels_summary(const FrameView &f, int b) {
+  if (!f.key && f.skip[b]) return 0;
+  auto cls = [](int v) { return v < 0 ? 1u : v > 0 ? 2u : 0u; };
+  unsigned s = cls(f.lev_y[(long)b * 64]);
+  for (int p = 1; p < 3; p++) {
+    const int16_t *lev = (p == 1 ? f.lev_u : f.lev_v) + (long)b * 16;
+    struct alignas(16) L8 { uint32_t w[4]; } q0 = *reinterpret_cast<const L8 *>(lev), q1 = *reinterpret_cast<const L8 *>(lev + 8);
+    const uint32_t any = q0.w[0] | q0.w[1] | q0.w[2] | q0.w[3] | q1.w[0] | q1.w[1] | q1.w[2] | q1.w[3];
+    s |= cls(lev[0]) << (2 * p) | (any ? 64u << (p - 1) : 0u);
   }
+  return s;
 }
+AV1_HD int summary_dc(unsigned s, int p) { return (int)((s >> (2 * p)) & 3u); }
+AV1_HD int summary_cul(unsigned s, int p) { return p ? (int)((s >> (5 + p)) & 1u) : 0; }      // zero or not (chroma)
 
 // ------------------------------------------------------------------------------------------------ MV prediction list (7.10.2)
 // identical to TileEnc::mv_stack of the host writer (all blocks 8x8, single reference LAST_FRAME, every candidate weight 4)
@@ -557,8 +534,9 @@ AV1_HD void tok_mv_comp(Sink &k, int comp, int diff) {            // read_mv_com
   }
 }
 
-// all ops of the block with z-order index `zi` of superblock (sbr, sbc); returns without ops for blocks outside the frame
-AV1_HD void tok_block(const FrameView &f, Sink &k, const TokScratch &ts, int sbr, int sbc, int zi) {
+// all ops of the block with z-order index `zi` of superblock (sbr, sbc); returns without ops for blocks outside the frame.
+// sums[by * 8 + bx]: block_levels_summary of the tile's blocks
+AV1_HD void tok_block(const FrameView &f, Sink &k, const TokScratch &ts, int sbr, int sbc, int zi, const uint8_t *sums) {
   int bx, by;
   demorton8((unsigned)zi, &bx, &by);
   const int r8 = sbr * 8 + by, c8 = sbc * 8 + bx;
@@ -567,8 +545,7 @@ AV1_HD void tok_block(const FrameView &f, Sink &k, const TokScratch &ts, int sbr
   tok_partition_prefix(f, k, sbr, sbc, bx, by);
   const int b = r8 * f.w8 + c8;
   const bool au = by > 0, al = bx > 0;
-  const BlockInfo zero = {};
-  const BlockInfo ia = au ? f.info[b - f.w8] : zero, il = al ? f.info[b - 1] : zero;
+  const unsigned sa = au ? sums[(by - 1) * 8 + bx] : 0u, sl = al ? sums[by * 8 + bx - 1] : 0u;
   const int skip = f.key ? 0 : f.skip[b];
   k.sym(S_SKIP + (au && !f.key ? f.skip[b - f.w8] : 0) + (al && !f.key ? f.skip[b - 1] : 0), skip);
   int ym = 0;
@@ -588,7 +565,7 @@ AV1_HD void tok_block(const FrameView &f, Sink &k, const TokScratch &ts, int sbr
     const int mode = me.mode & 3, ref_idx = me.mode >> 2, num = me.num;
     const int mx = f.mv[2 * b], my = f.mv[2 * b + 1];
     const int close = (au ? 1 : 0) + (al ? 1 : 0);
-    int num_new = (au ? ia.flags & 1 : 0) + (al ? il.flags & 1 : 0);
+    int num_new = (au ? f.info[b - f.w8].flags & 1 : 0) + (al ? f.info[b - 1].flags & 1 : 0);
     if (au && bx < 7 && c8 + 1 < f.w8 && morton8((unsigned)bx + 1, (unsigned)by - 1) < morton8((unsigned)bx, (unsigned)by)) num_new += f.info[b - f.w8 + 1].flags & 1;
     const int new_ctx = close == 0 ? 0 : close == 1 ? 3 - imin(num_new, 1) : 5 - imin(num_new, 1);
     const int ref_ctx = close == 0 ? 0 : close == 1 ? 3 : 5;
@@ -621,10 +598,10 @@ AV1_HD void tok_block(const FrameView &f, Sink &k, const TokScratch &ts, int sbr
   }
   if (skip) return;
   // the luma transform type: DCT_DCT in Tx_Type_Intra_Inv_Set1 (key frames) or in the 16-type inter set
-  tok_coeffs<8, kSlots8>(k, ts, false, f.lev_y + (long)b * 64, ia.cul[0], ia.dc[0], il.cul[0], il.dc[0], f.key ? S_INTRA_TX + ym : S_INTER_TX, f.key ? 1 : 7);
+  tok_coeffs<8, kSlots8>(k, ts, false, f.lev_y + (long)b * 64, 0, summary_dc(sa, 0), 0, summary_dc(sl, 0), f.key ? S_INTRA_TX + ym : S_INTER_TX, f.key ? 1 : 7);
   AV1_NOUNROLL
   for (int p = 1; p < 3; p++)
-    tok_coeffs<4, kSlots8>(k, ts, true, (p == 1 ? f.lev_u : f.lev_v) + (long)b * 16, ia.cul[p], ia.dc[p], il.cul[p], il.dc[p], -1, 0);
+    tok_coeffs<4, kSlots8>(k, ts, true, (p == 1 ? f.lev_u : f.lev_v) + (long)b * 16, summary_cul(sa, p), summary_dc(sa, p), summary_cul(sl, p), summary_dc(sl, p), -1, 0);
 }
 
 // ------------------------------------------------------------------------------------------------ op coder

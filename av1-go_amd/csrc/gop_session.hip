@@ -331,7 +331,9 @@ int setup(av1mi_gop *g) {
   }
   if (c.gpu_entropy) {
     g->tiles = ((w + 63) / 64) * ((h + 63) / 64);
-    g->ent_cap = (size_t)w * h * S;            // one byte per luma sample: several times what a frame codes to at any sane quantiser
+    // the size of the batch's frames as packed 4:2:0 samples: a frame codes to several times less at any sane quantiser, and to about
+    // that at the finest one (one byte per luma sample, the capacity before, gave an 8-bit key frame at base_q_idx 1 back to the host)
+    g->ent_cap = (size_t)w * h * S * 3 * c.bit_depth / 16;
   }
   G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
   if (c.source_width) G_HIP(av1mi::scale_plan_create(c.bit_depth, c.source_width, c.source_height, g->vw, g->vh, &g->scale));

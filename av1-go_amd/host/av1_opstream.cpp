@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "../csrc/av1_ops_cdfs.hpp"
+#include "../csrc/av1_ops8.hpp"
 #include "av1_bitstream.hpp"
 
 namespace av1mi_host {
@@ -46,19 +47,7 @@ bool code_list(std::vector<av1ops::op_t> &list, const std::vector<uint32_t> &gro
   out->resize((size_t)n);
   return true;
 }
-// a tile of 8x8 blocks, tokenized and placed (pos = [slots][kBlocks] positions of the blocks' first entries, the slots' totals and bases,
-// run = the tile's grouped entries): replay, then stages 2 and 3
-template <int kBlocks>
-bool code_tile(const uint16_t *rec, int block_records, const int *nrec, const int *first, uint16_t *pos, int nslots, const uint16_t *total,
-               const uint16_t *base, int run, const av1ops::SlotTable &tab, const uint16_t *image, std::vector<uint8_t> *out, std::string *err) {
-  using namespace av1ops;
-  if (run > 65535) { if (err) *err = "tile too large for 16-bit entry positions"; return false; }
-  std::vector<op_t> list((size_t)first[kBlocks], 0);
-  std::vector<uint32_t> grouped((size_t)run, 0);
-  for (int b = 0; b < kBlocks; b++) replay_block<kBlocks>(rec + (size_t)b * block_records, nrec[b], pos, b, first[b], list.data(), grouped.data());
-  return code_list(list, grouped, nslots, total, base, tab, image, out, err);
-}
-// the wave of av1_ops32.hpp's tok_tile32 as a loop: the lanes of a phase one after the other
+// the wave of the tile tokenizers (av1_ops32.hpp tok_tile32, av1_ops8.hpp tok_tile8) as a loop: the lanes of a phase one after the other
 struct WaveLoop {
   template <class T> using Var = av1ops::LaneVar<T, av1ops::kLanes32>;
   template <class F> void each(F f) { for (int lane = 0; lane < av1ops::kLanes32; lane++) f(lane); }
@@ -109,7 +98,7 @@ bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> 
   const size_t nb = (size_t)v.w8 * v.h8;
   std::vector<BlockInfo> info(nb);
   v.info = info.data();
-  for (size_t b = 0; b < nb; b++) { memset(&info[b], 0, sizeof(BlockInfo)); block_summary(v, (int)b, &info[b]); }
+  for (size_t b = 0; b < nb; b++) memset(&info[b], 0, sizeof(BlockInfo));
   if (!v.key) for (int r = 0; r < v.h8; r++) for (int c = 0; c < v.w8; c++) inter_mode_decision(v, r, c, &info[(size_t)r * v.w8 + c]);
   const int qcat = q_category(f.base_q_idx);
   SlotTable tab;
@@ -117,12 +106,12 @@ bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> 
   const int sbr_n = (v.h8 + 7) / 8, sbc_n = (v.w8 + 7) / 8;
   tiles->assign((size_t)sbr_n * sbc_n, {});
   const int nslots = v.key ? S_KEY_END : S_INTER_END;
-  std::vector<uint8_t> cnt((size_t)S_MAX * kBlocksPerTile);
-  std::vector<uint16_t> pos((size_t)S_MAX * kBlocksPerTile), rec((size_t)kBlocksPerTile * kBlockRecords);
-  ScanTables scan;
-  fill_scan_tables(&scan);
-  alignas(16) uint8_t mag[kMagBytes];
-  const TokScratch ts = { mag, &scan };
+  // what a tile's wave of 8x8 blocks keeps in LDS, its records, and its outputs
+  std::vector<Tile8Mem> mem8(1);
+  std::vector<uint16_t> rec((size_t)kBlocksPerTile * kBlockRecords);
+  const uint32_t ops_cap8 = 1u << 20;        // (no tile has as many words)
+  std::vector<op_t> list8(ops_cap8);
+  std::vector<uint32_t> grouped8(65536 + kListAlign);
   // AV1MI_TOK_STATS=1 (diagnostic): the capacities a frame would need — records per block, symbols of one slot in one block, list
   // words per tile — to stderr; tiles over capacity are skipped instead of failing the call
   const bool stats = getenv("AV1MI_TOK_STATS") != nullptr;
@@ -146,36 +135,26 @@ bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> 
         if (!code_list(list, grouped32, K_END, total, base, tab32, image32.data(), &(*tiles)[(size_t)sbr * sbc_n + sbc], err)) return false;
         continue;
       }
-      // stage 1, tokenize (the GPU: one thread per block): records + counts, place, replay
-      std::fill(cnt.begin(), cnt.end(), 0);
-      int first[kBlocksPerTile + 1], nrec[kBlocksPerTile];
-      first[0] = 0;
-      bool over = false;
-      for (int zi = 0; zi < kBlocksPerTile; zi++) {
-        Sink k = { &rec[(size_t)zi * kBlockRecords], cnt.data(), zi, 0, 0, false };
-        tok_block(v, k, ts, sbr, sbc, zi);
-        if (k.overflow && !stats) { if (err) *err = "a block exceeds the tokenizer's record area"; return false; }
-        over |= k.overflow;
-        nrec[zi] = k.nrec;
-        first[zi + 1] = first[zi] + k.n;
-        if (k.nrec > st_rec) st_rec = k.nrec;
-      }
-      if (stats) {
-        for (uint8_t c : cnt) if (c > st_cnt) st_cnt = c;
-        if (first[kBlocksPerTile] > st_ops) st_ops = first[kBlocksPerTile];
-        st_ops_sum += first[kBlocksPerTile];
-        if (over) { st_over++; continue; }
-      }
+      // stage 1 (av1_ops8.hpp tok_tile8, the GPU: a lane per block): summaries, records + counts, place, replay
+      WaveLoop wave;
       uint16_t base[S_MAX], total[S_MAX];
-      int run = 0;
-      for (int sl = 0; sl < nslots; sl++) {
-        const int n = group_positions(&cnt[(size_t)sl * kBlocksPerTile], &pos[(size_t)sl * kBlocksPerTile], run);
-        base[sl] = (uint16_t)run; total[sl] = (uint16_t)n;
-        run = (run + n + kListAlign - 1) & ~(kListAlign - 1);
+      const int words = tok_tile8(wave, mem8[0], v, sbr, sbc, rec.data(), list8.data(), ops_cap8, grouped8.data(), total, base);
+      if (stats) {       // the blocks once more, one by one, for what the tile's call does not tell
+        std::vector<uint8_t> cnt((size_t)S_MAX * kBlocksPerTile, 0);
+        const TokScratch ts = { mem8[0].p1.mag, &mem8[0].scan };
+        int ops = 0;
+        for (int zi = 0; zi < kBlocksPerTile; zi++) {
+          Sink k = { rec.data(), cnt.data(), zi, 0, 0, false };
+          tok_block(v, k, ts, sbr, sbc, zi, mem8[0].sums);
+          st_rec = std::max(st_rec, k.nrec); ops += k.n;
+        }
+        for (uint8_t c : cnt) st_cnt = std::max(st_cnt, (int)c);
+        st_ops = std::max(st_ops, ops); st_ops_sum += ops;
+        if (words < 0) { st_over++; continue; }
       }
-      if (!code_tile<kBlocksPerTile>(rec.data(), kBlockRecords, nrec, first, pos.data(), nslots, total, base, run, tab, image.data(),
-                                     &(*tiles)[(size_t)sbr * sbc_n + sbc], err))
-        return false;
+      if (words < 0) { if (err) *err = "a tile exceeds the tokenizer's capacities (records or symbols of a slot per block, entries per tile)"; return false; }
+      std::vector<op_t> list(list8.begin(), list8.begin() + words);
+      if (!code_list(list, grouped8, nslots, total, base, tab, image.data(), &(*tiles)[(size_t)sbr * sbc_n + sbc], err)) return false;
     }
   if (stats)
     fprintf(stderr, "[av1mi tok stats] %d tiles: records per block <= %d (capacity %d), symbols of a slot in a block <= %d (255), list words per tile <= %d, mean %.0f; %d tiles over a block capacity\n",
@@ -184,6 +163,27 @@ bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> 
 }
 
 int opstream_slots() { return av1ops::S_MAX; }
+
+// One tile of 8x8 blocks (key or inter frame) through tok_tile8 into the caller's areas, as the GPU kernel calls it (tests: the
+// capacity of the list is the caller's): returns the list words, -1 when the tile is refused (then nothing but the totals is written),
+// -2 for a frame outside the tool set
+int opstream_tile8(const av1mi_obu_frame &f, int sbr, int sbc, uint32_t ops_cap, uint32_t *list, uint32_t *grouped, uint16_t *slot_total, uint16_t *slot_base,
+                   std::string *err) {
+  using namespace av1ops;
+  if (!opstream_supported(f, err) || sbr < 0 || sbc < 0 || sbr * 64 >= f.height || sbc * 64 >= f.width) return -2;
+  FrameView v;
+  frame_view_of(f, &v);
+  std::vector<uint8_t> zskip;
+  if (!v.key && !v.skip) { zskip.assign((size_t)v.w8 * v.h8, 0); v.skip = zskip.data(); }
+  if (!lr_units_of(f, &v, err)) return -2;
+  std::vector<BlockInfo> info(v.key ? 0 : (size_t)v.w8 * v.h8);
+  v.info = info.data();
+  if (!v.key) for (int r = 0; r < v.h8; r++) for (int c = 0; c < v.w8; c++) { memset(&info[(size_t)r * v.w8 + c], 0, sizeof(BlockInfo)); inter_mode_decision(v, r, c, &info[(size_t)r * v.w8 + c]); }
+  std::vector<Tile8Mem> mem(1);
+  std::vector<uint16_t> rec((size_t)kBlocksPerTile * kBlockRecords);
+  WaveLoop wave;
+  return tok_tile8(wave, mem[0], v, sbr, sbc, rec.data(), list, ops_cap, grouped, slot_total, slot_base);
+}
 
 // One tile of a key frame's 32x32 band through tok_tile32 into the caller's areas, as the GPU kernel calls it (tests: the capacity of
 // the list is the caller's): returns the list words, -1 when the tile does not fit (then nothing but the totals and bases is written),

@@ -291,6 +291,14 @@ int av1mi_host_opstream_tile32(const av1mi_obu_frame *f, int sbr, int sbc, uint3
   std::string e;
   return av1::opstream_tile32(*f, sbr, sbc, ops_cap, list, grouped, slot_total, slot_base, &e);
 }
+// the same for one tile of 8x8 blocks of a key or an inter frame (csrc/av1_ops8.hpp); -1 = the tile is refused (more than ops_cap words, or one
+// of the tokenizer's own capacities): every slot total is 0, nothing else is written
+int av1mi_host_opstream_tile8(const av1mi_obu_frame *f, int sbr, int sbc, uint32_t ops_cap, uint32_t *list, uint32_t *grouped, uint16_t *slot_total,
+                              uint16_t *slot_base) {
+  if (!f || !list || !grouped || !slot_total || !slot_base) return -2;
+  std::string e;
+  return av1::opstream_tile8(*f, sbr, sbc, ops_cap, list, grouped, slot_total, slot_base, &e);
+}
 long long av1mi_host_opstream_temporal_unit(const av1mi_obu_frame *f, int with_sequence_header, uint8_t *out, long long cap, char *err, int errcap) {
   return av1mi_host_opstream_key32_temporal_unit(f, 0, with_sequence_header, out, cap, err, errcap);
 }
