@@ -91,7 +91,7 @@ class GopConfig(C.Structure):
                 ("segments", C.c_int), ("search_range", C.c_int), ("gpu_entropy", C.c_int), ("visible_width", C.c_int),
                 ("visible_height", C.c_int), ("coder_streams", C.c_int), ("key_block_size", C.c_int), ("input_format", C.c_int), ("source_width", C.c_int),
                 ("source_height", C.c_int), ("quality_stats", C.c_int), ("coarse_range", C.c_int), ("source_chroma", C.c_int),
-                ("source_bit_depth", C.c_int)]
+                ("source_bit_depth", C.c_int), ("store_frames", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -118,6 +118,9 @@ def policy_frame_params(base_q_idx, bit_depth, frame_type):
 
 
 # av1mi_quality (include/av1mi.h): one record per (frame, plane)
+# av1mi_scene_record (include/av1mi.h "scene analysis"): one record per frame
+SCENE_DTYPE = np.dtype([("inter_sad", "<u8"), ("intra_sad", "<u8"), ("blocks", "<u4"), ("reserved", "<u4")])
+assert SCENE_DTYPE.itemsize == 24
 QUALITY_DTYPE = np.dtype([("sse", "<u8"), ("ssim_sum", "<f8"), ("samples", "<u4"), ("windows", "<u4")])
 assert QUALITY_DTYPE.itemsize == 24
 
@@ -206,7 +209,7 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
@@ -214,12 +217,14 @@ class GopSession:
         quality_stats: 1 = every batch is measured on the GPU, collect()["quality"] holds the records (av1mi_gop_config.quality_stats);
         coarse_range: 0, or a multiple of 4 up to 64: P frames search around a coarse centre per 64x64 tile (av1mi_gop_config.coarse_range);
         source_chroma / source_bit_depth: CHROMA_* and 8 / 10 / 12 of the source the session is fed (av1mi_gop_config.source_chroma): the
-        input buffers then have that layout (source_plane_shapes), and no chroma planes for a grey source"""
+        input buffers then have that layout (source_plane_shapes), and no chroma planes for a grey source;
+        store_frames: the session owns two frame stores of that many fed frames (av1mi_gop_config.store_frames): store_put(),
+        store_analyse() and submit_stored() feed it, submit() is refused"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
         sw, sh = source if source is not None else (0, 0)
         self.cfg = GopConfig(width, height, bit_depth, base_q_idx, gop_length, segments, search_range, gpu_entropy, vw, vh, coder_streams, key_block_size, input_format,
-                             sw, sh, int(quality_stats), int(coarse_range), int(source_chroma), int(source_bit_depth))
+                             sw, sh, int(quality_stats), int(coarse_range), int(source_chroma), int(source_bit_depth), int(store_frames))
         self.source_chroma, self.src_bd = int(source_chroma), int(source_bit_depth) or bit_depth
         self.in_w, self.in_h = ((sw + 7) & ~7, (sh + 7) & ~7) if source is not None else (width, height)      # geometry of the input buffers
         self.input_format = input_format
@@ -253,6 +258,26 @@ class GopSession:
         memory: no upload (av1mi_gop_submit_device)"""
         self.ctx.lib.av1mi_gop_submit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         self.ctx._chk(self.ctx.lib.av1mi_gop_submit_device(self.g, d_y.ptr, d_u.ptr if d_u is not None else None, d_v.ptr if d_v is not None else None, int(frame_type)))
+
+    def store_put(self, store, first, count):
+        """the `count` frames written into input_planes() (frame i where segment i would lie) -> positions first .. of store 0 / 1
+        (av1mi_gop_store_put); nothing is coded"""
+        self.ctx.lib.av1mi_gop_store_put.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        self.ctx._chk(self.ctx.lib.av1mi_gop_store_put(self.g, int(store), int(first), int(count)))
+
+    def store_analyse(self, store, frames):
+        """the scene records (SCENE_DTYPE [frames]) of frames 0 .. frames - 1 of a store (av1mi_gop_store_analyse)"""
+        out = np.zeros(frames, SCENE_DTYPE)
+        self.ctx.lib.av1mi_gop_store_analyse.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        self.ctx._chk(self.ctx.lib.av1mi_gop_store_analyse(self.g, int(store), int(frames), out.ctypes.data))
+        return out
+
+    def submit_stored(self, store, index, frame_type):
+        """a batch gathered from a store: index[s] = the store position of segment s's frame, -1 = a flat slot (av1mi_gop_submit_stored)"""
+        idx = np.ascontiguousarray(index, np.int32)
+        assert idx.size == self.segments
+        self.ctx.lib.av1mi_gop_submit_stored.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        self.ctx._chk(self.ctx.lib.av1mi_gop_submit_stored(self.g, int(store), idx.ctypes.data, int(frame_type)))
 
     def set_q(self, base_q_idx):
         """the quantiser (1..255) of every batch submitted from now on; batches in flight keep theirs (av1mi_gop_set_base_q_idx)"""
@@ -330,6 +355,7 @@ class GopSession:
 N_PIPELINE_KINDS = 18
 N_KERNEL_KINDS = N_PIPELINE_KINDS
 K_QUALITY = 18        # AV1MI_K_QUALITY
+K_SCENE = 20          # AV1MI_K_SCENE: the scene analysis and the frame gather
 _lib = None
 
 
@@ -526,6 +552,28 @@ class Context:
             return d_out.download((frames, 3), QUALITY_DTYPE)
         finally:
             d_out.free()
+
+    def scene_analyse(self, Y, bit_depth):
+        """the scene records (SCENE_DTYPE [frames]) of a run of luma planes Y [frames, h, w], h and w multiples of 8 (av1mi_scene_analyse);
+        synchronous here: the records are downloaded"""
+        Y = np.ascontiguousarray(Y, np.uint8 if bit_depth == 8 else np.uint16)
+        n, h, w = Y.shape
+        self.lib.av1mi_scene_analyse.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2
+        d_y, d_out = self.to_device(Y), self.alloc(n * SCENE_DTYPE.itemsize)
+        try:
+            self._chk(self.lib.av1mi_scene_analyse(self.h, int(bit_depth), w, h, n, d_y.ptr, d_out.ptr))
+            return d_out.download((n,), SCENE_DTYPE)
+        finally:
+            d_y.free()
+            d_out.free()
+
+    def frames_gather(self, plane_bytes, segments, d_table, d_dst):
+        """one launch: per segment and plane plane_bytes[p] bytes from the device pointer d_table (DevBuf of segments * 3 uint64) holds at
+        [s * 3 + p], zeros where it holds 0, to d_dst[p] (DevBuf) + s * plane_bytes[p] (av1mi_frames_gather); asynchronous"""
+        self.lib.av1mi_frames_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        nb = (C.c_size_t * 3)(*[int(b) for b in plane_bytes])
+        dst = (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_dst])
+        self._chk(self.lib.av1mi_frames_gather(self.h, nb, int(segments), d_table.ptr, dst))
 
     def prof_enable(self, on):
         self._chk(self.lib.av1mi_prof_enable(self.h, int(on)))

@@ -217,6 +217,41 @@ def session_temporal_unit(width, height, bit_depth, raw_frame, seg, with_sequenc
     return out[:n].tobytes()
 
 
+SCENECUT_DEFAULT = 15      # host/sceneplan.hpp AV1MI_SCENECUT_DEFAULT
+
+
+def scene_is_cut(rec, scenecut):
+    """the cut rule on one scene record (a numpy record of av1mi.SCENE_DTYPE): av1mi_scene_is_cut"""
+    h = lib()
+    h.av1mi_scene_is_cut.argtypes = [C.c_void_p, C.c_int]
+    a = np.ascontiguousarray(rec).reshape(1).copy()
+    return bool(h.av1mi_scene_is_cut(a.ctypes.data, int(scenecut)))
+
+
+def plan_gops(n, G, S, cut, min_len=0):
+    """av1mi_plan_gops (host/sceneplan.hpp): the GOPs of a window of n <= S G frames with cut[f] != 0 marking cuts -> (K, start [S], len [S]);
+    ValueError where the planner refuses its arguments"""
+    h = lib()
+    h.av1mi_plan_gops.argtypes = [C.c_int] * 4 + [C.c_void_p] * 3
+    c = np.zeros(max(int(n), 1), np.uint8)
+    c[:len(cut)] = np.asarray(cut, np.uint8)[:len(c)]
+    start, ln = np.full(max(S, 1), -7, np.int32), np.full(max(S, 1), -7, np.int32)
+    K = h.av1mi_plan_gops(int(n), int(G), int(S), int(min_len), c.ctypes.data, start.ctypes.data, ln.ctypes.data)
+    if K < 0:
+        raise ValueError("av1mi_plan_gops(n %d, G %d, S %d, min_len %d) refused" % (n, G, S, min_len))
+    return K, start, ln
+
+
+def run_transcode(argv):
+    """av1mi_run_transcode (include/av1mi_host.h) on an argument vector: (exit code, error text)"""
+    h = lib()
+    h.av1mi_run_transcode.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_size_t]
+    a = [str(x).encode() for x in argv]
+    buf = C.create_string_buffer(2048)
+    code = h.av1mi_run_transcode(len(a), (C.c_char_p * len(a))(*a), buf, 2048)
+    return code, buf.value.decode()
+
+
 def header_from_params(p, width, height, lr_on=None, visible=None):
     """keyword arguments of temporal_unit() for a frame whose filter parameters are an av1mi_frame_params (GOP session policy);
     lr_on: the encoder's restoration ON / OFF decision per plane (the session's frame["lr_on"][segment]; None = the policy's types);

@@ -171,6 +171,21 @@ struct QualityLaunch {
 size_t quality_scratch_bytes(int bd, int w, int h, int frames);
 hipError_t launch_quality(const QualityLaunch &Q, hipStream_t s);
 
+// the scene analysis (scene_kernels.hip, include/av1mi.h "scene analysis"): `frames` stacked luma planes of w x h samples (multiples of
+// 8; uint8 at bd 8, else uint16 viewed through >> (bd - 8)) -> one record per frame, three launches.  scratch: scene_layout().bytes
+// bytes, 16-byte aligned: the quarter planes at 0 (rows qs bytes apart, frames stacked), a pair (inter, intra) per block at off_blocks;
+// out: `frames` records (device memory or pinned host memory)
+struct SceneLayout { int qw, qh, qs, nbx, nby; size_t off_blocks, bytes; };
+SceneLayout scene_layout(int w, int h, int frames);
+struct SceneLaunch {
+  int bd, w, h, frames;
+  const void *luma; void *scratch; av1mi_scene_record *out;
+};
+hipError_t launch_scene(const SceneLaunch &S, hipStream_t s);
+// the gather (scene_kernels.hip): table[segment * 3 + plane] = where that segment's plane of plane_bytes[plane] bytes lies in device
+// memory (16-byte aligned), or null = zeros -> dst[plane] + segment * plane_bytes[plane]; ONE launch.  table is device memory.
+hipError_t launch_frames_gather(const size_t plane_bytes[3], int segments, const void *const *table, void *const dst[3], hipStream_t s);
+
 // side information that follows a batch's quantiser (levels_kernels.hip): up to three arrays of dwords patched in place in one launch,
 // word = (word & keep) | bits unless (word & hold) != 0
 struct LevelsLaunch {

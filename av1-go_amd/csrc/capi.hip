@@ -26,6 +26,8 @@ struct av1mi_ctx {
   size_t quality_scratch_bytes = 0;
   void *me_scratch = nullptr;             // av1mi_inter_encode / av1mi_me_search with a coarse_range: quarter planes + centres (grown on demand)
   size_t me_scratch_bytes = 0;
+  void *scene_scratch = nullptr;          // av1mi_scene_analyse: quarter planes + block results (grown on demand)
+  size_t scene_scratch_bytes = 0;
   // per-kernel profile: one event pair per launch while enabled
   bool prof_on = false;
   struct ProfRec { int kind; hipEvent_t e0, e1; };
@@ -183,6 +185,7 @@ void av1mi_close(av1mi_ctx *ctx) {
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->quality_scratch) (void)hipFree(ctx->quality_scratch);
   if (ctx->me_scratch) (void)hipFree(ctx->me_scratch);
+  if (ctx->scene_scratch) (void)hipFree(ctx->scene_scratch);
   if (ctx->av1ent) av1mi::av1ent_free(ctx->av1ent);
   av1mi::scale_plan_destroy(ctx->scale_plan);
   for (auto &r : ctx->prof_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -277,7 +280,7 @@ int av1mi_prof_get(av1mi_ctx *ctx, int kind, int *launches, double *total_ms) {
 }
 const char *av1mi_kernel_kind_name(int kind) {
   static const char *n[AV1MI_K_KINDS] = { "fwd_txfm", "inv_txfm", "quantize", "dequantize", "intra_pred", "mc", "deblock",
-                                          "cdef", "loop_restoration", "intra_pipeline", "inter_pipeline", "misc", "entropy_code", "entropy_pack", "entropy_tokens", "me_integer", "entropy_chains", "input_convert", "quality", "me_coarse" };
+                                          "cdef", "loop_restoration", "intra_pipeline", "inter_pipeline", "misc", "entropy_code", "entropy_pack", "entropy_tokens", "me_integer", "entropy_chains", "input_convert", "quality", "me_coarse", "scene" };
   return kind < 0 || kind >= AV1MI_K_KINDS ? "?" : n[kind];
 }
 
@@ -587,6 +590,40 @@ int av1mi_quality_planes(av1mi_ctx *ctx, int bit_depth, int width, int height, i
   Q.scratch = ctx->quality_scratch; Q.out = d_out;
   ProfScope ps(ctx, AV1MI_K_QUALITY);
   HIP_TRY(ctx, av1mi::launch_quality(Q, ctx->stream));
+  return AV1MI_OK;
+}
+
+int av1mi_scene_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int frames, const void *d_luma, av1mi_scene_record *d_records) {
+  BIND(ctx);
+  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return fail(ctx, AV1MI_E_INVAL, "av1mi_scene_analyse: bit depth %d not supported (8, 10 or 12)", bit_depth);
+  if (width < 8 || height < 8 || (width & 7) || (height & 7) || width > 16384 || height > 16384)
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_scene_analyse: the planes' size %dx%d must be a multiple of 8 (8 .. 16384)", width, height);
+  if (frames < 1 || frames > 65535) return fail(ctx, AV1MI_E_INVAL, "av1mi_scene_analyse: frames %d out of range (1 .. 65535)", frames);
+  if (!d_luma || !d_records || ((uintptr_t)d_luma & 15) || ((uintptr_t)d_records & 7)) return fail(ctx, AV1MI_E_INVAL, "av1mi_scene_analyse: null or misaligned device pointer (planes 16 bytes, records 8)");
+  const size_t need = av1mi::scene_layout(width, height, frames).bytes;
+  if (ctx->scene_scratch_bytes < need) {      // (hipFree waits for the launches that still read the old one)
+    if (ctx->scene_scratch) (void)hipFree(ctx->scene_scratch);
+    ctx->scene_scratch = nullptr; ctx->scene_scratch_bytes = 0;
+    HIP_TRY(ctx, hipMalloc(&ctx->scene_scratch, need));
+    ctx->scene_scratch_bytes = need;
+  }
+  av1mi::SceneLaunch S;
+  S.bd = bit_depth; S.w = width; S.h = height; S.frames = frames; S.luma = d_luma; S.scratch = ctx->scene_scratch; S.out = d_records;
+  ProfScope ps(ctx, AV1MI_K_SCENE);
+  HIP_TRY(ctx, av1mi::launch_scene(S, ctx->stream));
+  return AV1MI_OK;
+}
+
+int av1mi_frames_gather(av1mi_ctx *ctx, const size_t plane_bytes[3], int segments, const void *const *d_src_table, void *const d_dst[3]) {
+  BIND(ctx);
+  if (!plane_bytes || !d_src_table || !d_dst || ((uintptr_t)d_src_table & 7)) return fail(ctx, AV1MI_E_INVAL, "av1mi_frames_gather: null pointer or misaligned table");
+  if (segments < 1 || segments > 4096) return fail(ctx, AV1MI_E_INVAL, "av1mi_frames_gather: segments %d out of range (1 .. 4096)", segments);
+  for (int p = 0; p < 3; p++) {
+    if ((plane_bytes[p] & 3) || plane_bytes[p] > 0x7FFFFFF0u) return fail(ctx, AV1MI_E_INVAL, "av1mi_frames_gather: plane %d of %zu bytes (a multiple of 4 below 2^31)", p, plane_bytes[p]);
+    if (plane_bytes[p] && (!d_dst[p] || ((uintptr_t)d_dst[p] & 15))) return fail(ctx, AV1MI_E_INVAL, "av1mi_frames_gather: null or misaligned destination (plane %d)", p);
+  }
+  ProfScope ps(ctx, AV1MI_K_SCENE);
+  HIP_TRY(ctx, av1mi::launch_frames_gather(plane_bytes, segments, d_src_table, d_dst, ctx->stream));
   return AV1MI_OK;
 }
 

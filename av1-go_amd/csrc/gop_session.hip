@@ -5,7 +5,9 @@
 //
 // Streams.  The context's stream runs the kernels; the session adds an upload stream and a download stream.  A batch is the stages
 // of submit_batch, in this order on every stream:
-//   feed_source       up:   wait slot.filters_done (the kernels that last read this slot's source) -> H2D of the fed buffers -> uploaded
+//   feed_source       (a batch from the frame store, av1mi_gop_submit_stored: main: wait store.filled -> k_frames_gather into the fed buffers
+//                     -> store.read_done, in place of the upload; the input stages follow as below)
+//                     up:   wait slot.filters_done (the kernels that last read this slot's source) -> H2D of the fed buffers -> uploaded
 //                     main: wait uploaded -> [k_input_convert] -> [k_chroma_convert] -> [k_scale]
 //   code_blocks       main: k_intra_pipe | [k_me_down + k_me_coarse] + k_me_int + k_inter_pipe -> kernel_done
 //   download_symbols  down: wait kernel_done -> D2H of the symbols into pinned memory
@@ -26,6 +28,13 @@
 // A source that is not 4:2:0, or deeper than the coded depth (source_chroma / source_bit_depth; planar only), takes the place of the
 // convert stage with the stage chroma: one launch of k_chroma_convert from the fed layout (av1mi_source_plane_bytes) to planar 4:2:0
 // at the fed size.  Where the depths are equal its luma plane passes THROUGH: the fed luma plane is the planar one, as with zero stages.
+//
+// The frame store (av1mi_gop_config.store_frames; nothing of it exists at 0).  Two stores of store_frames fed frames, a plane per
+// buffer, frames in file order.  The upload stream carries everything that fills and reads a store for the analysis: the puts (pinned
+// buffer -> store), then the three launches of the scene analysis, whose last one writes the records into pinned memory; scene_done is
+// what av1mi_gop_store_analyse waits for, so the batches of the OTHER store that are in flight on the main stream are not waited for.
+// The main stream reads a store only in a batch's gather: it waits for store.filled (recorded behind the last put) and records
+// store.read_done behind the gather, which the next put into that store waits for on the upload stream.  No host wait orders the two.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -103,6 +112,15 @@ struct Slot {
   // quality_stats: the batch's records [segment * 3 + plane], pinned and written by the GPU (k_quality_sum); quality_done follows
   void *h_quality = nullptr;
   hipEvent_t quality_done = nullptr;
+  // store_frames: the gather's table of this slot's batch, [segment * 3 + plane] source pointers: pinned, and the device copy the kernel reads
+  void *h_table = nullptr, *d_table = nullptr;
+};
+
+// one frame store: a buffer per plane, store_frames frames of frame_bytes[p] each
+struct Store {
+  void *d[3] = { nullptr, nullptr, nullptr };
+  hipEvent_t filled = nullptr, read_done = nullptr;      // behind the last put (upload stream) / behind the last gather (main stream)
+  bool has_fill = false, has_reader = false;
 };
 
 }  // namespace
@@ -142,6 +160,15 @@ struct av1mi_gop {
   bool acquired = false;
   int coder_streams = 0;                       // 0 = tokenizer + chains on the side stream, range coder on the back stream (default)
   int intra_open_loop = 0;                     // key frames: open-loop mode decision (k_intra_modes) instead of the closed-loop search
+  // the frame store (cfg.store_frames != 0)
+  int fed_w = 0, fed_h = 0;                    // luma size of one fed frame
+  size_t frame_bytes[3] = {};                  // one fed frame's planes: in_bytes[p] / segments
+  Store store[2];
+  void *d_scene = nullptr, *h_records = nullptr;      // the analysis' scratch area (one store's) and its records, pinned
+  hipEvent_t scene_done = nullptr;
+  long puts = 0;                               // av1mi_gop_store_put calls: the pinned buffers of slot puts % kSlots are handed out next
+  hipEvent_t put_done[kSlots] = {};            // the copy that last read those pinned buffers
+  bool put_pending[kSlots] = {};
   std::vector<void *> dev_allocs, host_allocs;
 };
 
@@ -198,6 +225,10 @@ int slot_buffers(av1mi_gop *g, Slot &s) {
     G_TRY(dev_alloc(g, &s.d_tile_size, (size_t)g->tiles * S * 4)); G_TRY(host_alloc(g, &s.h_tile_size, (size_t)g->tiles * S * 4));
     G_TRY(dev_alloc(g, &s.d_total, 16)); G_TRY(host_alloc(g, &s.h_total, 16));
     G_HIP(hipEventCreateWithFlags(&s.ent_done, hipEventDisableTiming));
+  }
+  if (c.store_frames) {
+    G_TRY(host_alloc(g, &s.h_table, (size_t)S * 3 * sizeof(void *)));
+    G_TRY(dev_alloc(g, &s.d_table, (size_t)S * 3 * sizeof(void *)));
   }
   if (c.quality_stats) {
     G_TRY(host_alloc(g, &s.h_quality, (size_t)S * 3 * sizeof(av1mi_quality)));
@@ -299,6 +330,8 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
     return WHY("coarse_range %d must be 0 (off) or a multiple of 4 up to 64", c->coarse_range);
   if (c->quality_stats && ((c->visible_width ? c->visible_width : c->width) < 16 || (c->visible_height ? c->visible_height : c->height) < 16))
     return WHY("quality_stats needs a true luma size of at least 16x16");
+  if (c->store_frames < 0 || c->store_frames > 65535) return WHY("store_frames %d out of range (0 = none, up to 65535)", c->store_frames);
+  if (c->store_frames && c->input_format != AV1MI_INPUT_PLANAR) return WHY("a frame store (store_frames %d) needs input_format 0 (planar), not %d", c->store_frames, c->input_format);
   return nullptr;
 #undef WHY
 }
@@ -325,6 +358,7 @@ int setup(av1mi_gop *g) {
   // the fed size: the coded size, or the source size rounded up to 8
   const int fed_w = scaling ? (c.source_width + 7) & ~7 : w, fed_rows = (scaling ? (c.source_height + 7) & ~7 : h) * S;
   g->fed_ny = (size_t)fed_w * fed_rows;
+  g->fed_w = fed_w; g->fed_h = fed_rows / S;
   for (int p = 0; p < 3; p++) {
     g->in_bytes[p] = g->chroma_stage ? av1mi_source_plane_bytes(c.source_chroma, g->src_bd, p, fed_w, fed_rows) : av1mi_input_plane_bytes(g->fmt, c.bit_depth, p, fed_w, fed_rows);
     g->pre_bytes[p] = av1mi_input_plane_bytes(AV1MI_INPUT_PLANAR, c.bit_depth, p, fed_w, fed_rows);
@@ -351,6 +385,19 @@ int setup(av1mi_gop *g) {
   G_TRY(dev_alloc(g, &g->d_lr_scratch, av1mi_lr_yuv_decide_scratch_bytes(h, S)));
   if (c.coarse_range) G_TRY(dev_alloc(g, &g->d_me, av1mi::me_layout(w, h, S).bytes));
   if (c.quality_stats) G_TRY(dev_alloc(g, &g->d_quality_scratch, av1mi::quality_scratch_bytes(c.bit_depth, g->vw, g->vh, S)));
+  if (c.store_frames) {
+    for (int p = 0; p < 3; p++) g->frame_bytes[p] = g->in_bytes[p] / (size_t)S;
+    for (Store &st : g->store) {
+      for (int p = 0; p < 3; p++)
+        if (g->frame_bytes[p]) G_TRY(dev_alloc(g, &st.d[p], g->frame_bytes[p] * (size_t)c.store_frames));
+      G_HIP(hipEventCreateWithFlags(&st.filled, hipEventDisableTiming));
+      G_HIP(hipEventCreateWithFlags(&st.read_done, hipEventDisableTiming));
+    }
+    G_TRY(dev_alloc(g, &g->d_scene, av1mi::scene_layout(g->fed_w, g->fed_h, c.store_frames).bytes));
+    G_TRY(host_alloc(g, &g->h_records, (size_t)c.store_frames * sizeof(av1mi_scene_record)));
+    G_HIP(hipEventCreateWithFlags(&g->scene_done, hipEventDisableTiming));
+    for (hipEvent_t &e : g->put_done) G_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
   G_TRY(dev_alloc(g, &g->d_zero_skip, g->nb));
   G_TRY(av1mi_memset(g->ctx, g->d_zero_skip, 0, g->nb));
   G_TRY(side_information(g));
@@ -393,6 +440,8 @@ void av1mi_gop_close(av1mi_gop *g) {
   for (Slot &s : g->slot)
     for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done, s.quality_done })
       if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : { g->store[0].filled, g->store[0].read_done, g->store[1].filled, g->store[1].read_done, g->scene_done, g->put_done[0], g->put_done[1], g->put_done[2] })
+    if (e) (void)hipEventDestroy(e);
   for (void *p : g->dev_allocs) (void)hipFree(p);
   for (void *p : g->host_allocs) (void)hipHostFree(p);
   av1mi::scale_plan_destroy(g->scale);
@@ -415,10 +464,28 @@ int av1mi_gop_max_in_flight(void) { return kSlots; }
 //    source after the filters).
 // `uploaded` keeps its two meanings: the main stream waits for it before the first launch, and av1mi_gop_acquire_input waits for
 // it before the host may overwrite the pinned buffers.
-static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const void *src[3]) {
+// A batch from the frame store (index != null: the store position per segment, -1 = a flat slot) is gathered into d_in on the main
+// stream instead of being uploaded: the stream itself orders the gather behind the slot's previous readers, store.filled orders it
+// behind the puts, and store.read_done lets the next put into that store wait for it.
+static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const void *src[3], int store = 0, const int32_t *index = nullptr) {
   hipStream_t main = av1mi::ctx_stream(g->ctx);
   for (int p = 0; p < 3; p++) src[p] = dev_src ? dev_src[p] : s.d_in[p];
-  if (!dev_src) {
+  if (index) {
+    Store &st = g->store[store];
+    const int S = g->cfg.segments;
+    const void **table = (const void **)s.h_table;
+    for (int sg = 0; sg < S; sg++)
+      for (int p = 0; p < 3; p++)
+        table[sg * 3 + p] = index[sg] < 0 || !g->frame_bytes[p] ? nullptr : (const char *)st.d[p] + g->frame_bytes[p] * (size_t)index[sg];
+    G_HIP(hipMemcpyAsync(s.d_table, s.h_table, (size_t)S * 3 * sizeof(void *), hipMemcpyHostToDevice, main));
+    G_HIP(hipStreamWaitEvent(main, st.filled, 0));
+    {
+      av1mi::ProfScope ps(g->ctx, AV1MI_K_SCENE, main);
+      G_HIP(av1mi::launch_frames_gather(g->frame_bytes, S, (const void *const *)s.d_table, s.d_in, main));
+    }
+    G_HIP(hipEventRecord(st.read_done, main));
+    st.has_reader = true;
+  } else if (!dev_src) {
     if (s.kernel_pending) G_HIP(hipStreamWaitEvent(g->up, s.filters_done, 0));
     if (s.kernel_pending && g->cfg.quality_stats) G_HIP(hipStreamWaitEvent(g->up, s.quality_done, 0));
     for (int p = 0; p < 3; p++)
@@ -683,7 +750,7 @@ static int start_coder(av1mi_gop *g, Slot &s) {
 }
 
 // one batch through the stages above; dev_src as for feed_source
-static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src) {
+static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src, int store = 0, const int32_t *index = nullptr) {
   if (g->submitted - g->collected >= kSlots) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "%d batches in flight: collect first", (int)kSlots);
   if (frame_type < -1 || frame_type > 1) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "frame_type %d", frame_type);
   if (frame_type < 0) frame_type = g->gop_pos == 0 ? 0 : 1;
@@ -695,7 +762,7 @@ static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src
   if (s.q == g->cfg.base_q_idx) s.params = g->params[frame_type];
   else frame_params(s.q, g->cfg.bit_depth, frame_type, &s.params);
   const void *src[3];
-  G_TRY(feed_source(g, s, dev_src, src));
+  G_TRY(feed_source(g, s, dev_src, src, store, index));
   if (s.ent_pending) G_HIP(hipStreamWaitEvent(av1mi::ctx_stream(g->ctx), s.ent_done, 0));      // the GPU coder of the slot's previous batch still reads its symbols
   G_TRY(code_blocks(g, s, frame_type, src));
   // symbols -> pinned host memory, beside the filters.  Not when the GPU codes the tiles (gpu_entropy == 1): the host then needs
@@ -711,7 +778,7 @@ static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src
   g->last = (int)(g->submitted % kSlots);
   g->submitted++;
   g->gop_pos = frame_type == 0 ? 1 % g->cfg.gop_length : (g->gop_pos + 1) % g->cfg.gop_length;
-  g->acquired = false;
+  if (!index) g->acquired = false;      // (a batch from the store leaves the pinned buffers, which feed the next put, alone)
   return AV1MI_OK;
 }
 
@@ -729,8 +796,15 @@ long av1mi_gop_entropy_fallbacks(av1mi_gop *g) { return g ? g->fallbacks : 0; }
 
 int av1mi_gop_acquire_input(av1mi_gop *g, void **y, void **u, void **v) {
   if (!g || !y || !u || !v) return AV1MI_E_INVAL;
-  if (g->submitted - g->collected >= kSlots) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "%d batches in flight: collect before acquiring the next input", (int)kSlots);
   G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
+  if (g->cfg.store_frames) {      // the pinned buffers feed the store, not a batch: a ring of their own, whatever is in flight
+    const int k = (int)(g->puts % kSlots);
+    if (g->put_pending[k]) { G_HIP(hipEventSynchronize(g->put_done[k])); g->put_pending[k] = false; }
+    *y = g->slot[k].h_in[0]; *u = g->slot[k].h_in[1]; *v = g->slot[k].h_in[2];
+    g->acquired = true;
+    return AV1MI_OK;
+  }
+  if (g->submitted - g->collected >= kSlots) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "%d batches in flight: collect before acquiring the next input", (int)kSlots);
   Slot &s = g->slot[g->submitted % kSlots];
   if (s.upload_pending) { G_HIP(hipEventSynchronize(s.uploaded)); s.upload_pending = false; }   // the copy engine still reads these buffers
   *y = s.h_in[0]; *u = s.h_in[1]; *v = s.h_in[2];      // in the session's format; no third plane in the semi-planar ones, no chroma for a grey source
@@ -740,8 +814,59 @@ int av1mi_gop_acquire_input(av1mi_gop *g, void **y, void **u, void **v) {
 
 int av1mi_gop_submit(av1mi_gop *g, int frame_type) {
   if (!g) return AV1MI_E_INVAL;
+  if (g->cfg.store_frames) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "a session with a frame store is fed through av1mi_gop_store_put / av1mi_gop_submit_stored");
   if (!g->acquired) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit without av1mi_gop_acquire_input");
   return submit_batch(g, frame_type, nullptr);
+}
+
+int av1mi_gop_store_put(av1mi_gop *g, int store, int first, int count) {
+  if (!g) return AV1MI_E_INVAL;
+  const int N = g->cfg.store_frames;
+  if (!N) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "the session has no frame store (store_frames 0)");
+  if (store < 0 || store > 1 || count < 1 || count > g->cfg.segments || first < 0 || first > N - count)
+    return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "store_put: store %d, frames %d .. %d + %d of %d (at most %d at a time)", store, first, first, count, N, g->cfg.segments);
+  if (!g->acquired) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "store_put without av1mi_gop_acquire_input");
+  G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
+  Store &st = g->store[store];
+  const int k = (int)(g->puts % kSlots);
+  if (st.has_reader) G_HIP(hipStreamWaitEvent(g->up, st.read_done, 0));      // the batches that gather from this store
+  for (int p = 0; p < 3; p++)
+    if (g->frame_bytes[p])
+      G_HIP(hipMemcpyAsync((char *)st.d[p] + g->frame_bytes[p] * (size_t)first, g->slot[k].h_in[p], g->frame_bytes[p] * (size_t)count, hipMemcpyHostToDevice, g->up));
+  G_HIP(hipEventRecord(g->put_done[k], g->up));
+  g->put_pending[k] = true;
+  G_HIP(hipEventRecord(st.filled, g->up));
+  st.has_fill = true;
+  g->puts++;
+  g->acquired = false;
+  return AV1MI_OK;
+}
+
+int av1mi_gop_store_analyse(av1mi_gop *g, int store, int frames, av1mi_scene_record *out) {
+  if (!g) return AV1MI_E_INVAL;
+  if (!g->cfg.store_frames) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "the session has no frame store (store_frames 0)");
+  if (store < 0 || store > 1 || frames < 1 || frames > g->cfg.store_frames || !out)
+    return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "store_analyse: store %d, %d frames of %d", store, frames, g->cfg.store_frames);
+  G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
+  av1mi::SceneLaunch L;
+  L.bd = g->src_bd; L.w = g->fed_w; L.h = g->fed_h; L.frames = frames;
+  L.luma = g->store[store].d[0]; L.scratch = g->d_scene; L.out = (av1mi_scene_record *)g->h_records;
+  // on the upload stream, behind the puts; the summing launch writes the records into pinned memory
+  G_HIP(av1mi::launch_scene(L, g->up));
+  G_HIP(hipEventRecord(g->scene_done, g->up));
+  G_HIP(hipEventSynchronize(g->scene_done));
+  memcpy(out, g->h_records, (size_t)frames * sizeof(av1mi_scene_record));
+  return AV1MI_OK;
+}
+
+int av1mi_gop_submit_stored(av1mi_gop *g, int store, const int32_t *index, int frame_type) {
+  if (!g) return AV1MI_E_INVAL;
+  if (!g->cfg.store_frames) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "the session has no frame store (store_frames 0)");
+  if (store < 0 || store > 1 || !index || !g->store[store].has_fill) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: store %d holds nothing, or no index", store);
+  if (frame_type != 0 && frame_type != 1) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: frame_type %d (0 key or 1 inter: the layout is the caller's)", frame_type);
+  for (int s = 0; s < g->cfg.segments; s++)
+    if (index[s] < -1 || index[s] >= g->cfg.store_frames) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: index[%d] = %d outside the store of %d frames", s, (int)index[s], g->cfg.store_frames);
+  return submit_batch(g, frame_type, nullptr, store, index);
 }
 
 int av1mi_gop_submit_device(av1mi_gop *g, const void *d_y, const void *d_u, const void *d_v, int frame_type) {

@@ -9,6 +9,11 @@
 // ".ivf" = IVF, anything else (the reference's "<base>.av1-tmp.mkv") = Matroska with one V_AV1 video track (mux.cpp);
 // audio / subtitle copy (transcode.go:134-137) needs a demuxer and is not done.
 //
+// With -av1mi_scenecut the GOPs of a group do not start every `gop` frames but where the scene analysis finds cuts: the group's frames go
+// into the session's frame store in file order (av1mi_gop_store_put), are analysed there (av1mi_gop_store_analyse), the planner
+// (sceneplan.hpp) lays the GOPs out, and every batch is gathered from the store (av1mi_gop_submit_stored).  The session has two stores:
+// the next group's frames are read and put while this group's batches run.
+//
 // `segments` closed GOPs of the file are coded in lockstep (the session's batch dimension); while the host codes the
 // symbols of frame t the GPU already works on frames t + 1 and t + 2 (three batches in flight).
 #include "backend.hpp"
@@ -24,6 +29,7 @@
 #include "av1_bitstream.hpp"
 #include "mux.hpp"
 #include "ratecontrol.hpp"
+#include "sceneplan.hpp"
 #include "y4m.hpp"
 
 namespace av1mi_host {
@@ -194,6 +200,9 @@ int RunBackend(const BackendJob &job, std::string *err) {
     if (convert) { cfg.source_chroma = y.chroma; cfg.source_bit_depth = y.src_bd; }
     const bool packed = job.pack10 && y.bd == 10 && !convert;      // (planar 4:2:0 10-bit only)
     if (packed) cfg.input_format = AV1MI_INPUT_PACKED10;
+    // -av1mi_scenecut: the frame store holds one group
+    const bool stored = job.scenecut > 0;
+    if (stored) cfg.store_frames = S * G;
     // one segment's planes in the pinned buffers (no chroma planes for a grey source)
     const size_t py_bytes = convert ? av1mi_source_plane_bytes(y.chroma, y.src_bd, 0, rw, rh) : av1mi_input_plane_bytes(cfg.input_format, y.bd, 0, rw, rh);
     const size_t pc_bytes = convert ? av1mi_source_plane_bytes(y.chroma, y.src_bd, 1, rw, rh) : av1mi_input_plane_bytes(cfg.input_format, y.bd, 1, rw, rh);
@@ -227,19 +236,69 @@ int RunBackend(const BackendJob &job, std::string *err) {
       rc.reset(new RateControl(rp));
     }
     const int lag = av1mi_gop_max_in_flight() - 1;      // batches the GPU holds while the host works on the oldest
+    // the layout of the group in flight: GOP s holds frames start[s] .. start[s] + len[s] - 1 of the group.  Fixed (s G, up to G frames)
+    // unless the planner moves the boundaries onto cuts (stored)
+    std::vector<int32_t> start((size_t)S), len((size_t)S), index((size_t)S);
+    std::vector<uint8_t> cut;                           // stored: the frames of the group the analysis flagged
+    std::vector<av1mi_scene_record> scene;
+    int cur_store = 0;
+    long next_frames = -1;                              // stored: frames of the group that is (being) put into the other store; -1 = not asked yet
+    // One chunk of a group -> a store (stored): frames f0 .. f0 + n - 1 of the group the reader has prepared, read by one thread each into
+    // the session's pinned buffers IN FILE ORDER, then put.  begin starts the threads, end joins them and queues the copy.
+    struct Reads {
+      std::vector<std::thread> th; std::vector<char> ok;
+      bool join() { for (auto &x : th) if (x.joinable()) x.join(); th.clear(); for (char c : ok) if (!c) return false; return true; }
+      ~Reads() { for (auto &x : th) if (x.joinable()) x.join(); }
+    };
+    Reads puts;
+    auto put_begin = [&](long f0, int n) -> bool {
+      void *py, *pu, *pv;
+      if (av1mi_gop_acquire_input(gop, &py, &pu, &pv) != AV1MI_OK) { *err = std::string("av1mi_gop_acquire_input: ") + av1mi_last_error(ctx); return false; }
+      puts.ok.assign((size_t)n, 1);
+      for (int i = 0; i < n; i++)
+        puts.th.emplace_back([&, i, f0, py, pu, pv]() {
+          puts.ok[(size_t)i] = y.read(f0 + i, rw, rh, (unsigned char *)py + py_bytes * i, (unsigned char *)pu + pc_bytes * i, (unsigned char *)pv + pc_bytes * i);
+        });
+      return true;
+    };
+    auto put_end = [&](int store, long f0, int n) -> int {      // 0, or the exit code
+      if (!puts.join()) { *err = job.input + ": Invalid data found when processing input (truncated frame)"; return 1; }
+      if (av1mi_gop_store_put(gop, store, (int)f0, n) != AV1MI_OK) { *err = std::string("av1mi_gop_store_put: ") + av1mi_last_error(ctx); return 2; }
+      return 0;
+    };
     for (long g0 = 0;; g0 += S) {
       for (auto &u : units) u.clear();
       for (auto &r : records) r.clear();
       for (auto &v : qs) v.clear();
       // the next GROUP of S GOPs: a file is read in place, a stream one group ahead of the encoder (y4m.hpp)
-      const long have_frames = y.prepare(g0 * G, (long)S * G, err);
-      if (have_frames < 0) { code = 1; goto done; }
+      long have_frames;
+      if (stored && next_frames >= 0) have_frames = next_frames;      // already in the store: it was put while the group before ran
+      else {
+        have_frames = y.prepare(g0 * G, (long)S * G, err);
+        if (have_frames < 0) { code = 1; goto done; }
+        for (long f0 = 0; stored && f0 < have_frames; f0 += S) {      // the first group: nothing runs beside it
+          const int n = (int)std::min<long>(S, have_frames - f0);
+          if (!put_begin(f0, n)) { code = 2; goto done; }
+          if ((code = put_end(cur_store, f0, n)) != 0) goto done;
+        }
+      }
       if (have_frames == 0) break;
       total_frames += have_frames;
-      // frames of this group that exist: segment s, position t -> frame s * G + t of the group
-      auto exists = [&](int s, int t) { return (long)s * G + t < have_frames; };
+      for (int s = 0; s < S; s++) { start[(size_t)s] = s * G; len[(size_t)s] = (int32_t)std::max<long>(0, std::min<long>(G, have_frames - (long)s * G)); }
+      if (stored) {
+        scene.resize((size_t)have_frames); cut.assign((size_t)have_frames, 0);
+        CHK(av1mi_gop_store_analyse(gop, cur_store, (int)have_frames, scene.data()));
+        for (long f = 0; f < have_frames; f++) cut[(size_t)f] = (uint8_t)av1mi_scene_is_cut(&scene[(size_t)f], job.scenecut);
+        if (av1mi_plan_gops((int)have_frames, G, S, job.min_gop, cut.data(), start.data(), len.data()) < 0) { *err = "Invalid argument: -av1mi_min_gop does not fit the GOP length"; code = 1; goto done; }
+        // the group after this one: prepared now (this group's frames are all in the store), put chunk by chunk beside the batches below
+        next_frames = y.prepare((g0 + S) * G, (long)S * G, err);
+        if (next_frames < 0) { code = 1; goto done; }
+      }
+      long next_put = 0;                                  // stored: frames of the next group already put
+      // frames of this group that exist: segment s, position t -> frame start[s] + t of the group
+      auto exists = [&](int s, int t) { return t < len[(size_t)s]; };
       int T = 0;
-      for (int t = 0; t < G; t++) if (exists(0, t)) T = t + 1;
+      for (int s = 0; s < S; s++) T = std::max(T, (int)len[(size_t)s]);
       av1mi_gop_frame fr;
       auto collect_oldest = [&]() -> bool {
         if (av1mi_gop_collect(gop, &fr) != AV1MI_OK) { *err = std::string("av1mi_gop_collect: ") + av1mi_last_error(ctx); return false; }
@@ -269,11 +328,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
       };
       // The frames of batch t + 1 are read (one thread per segment) WHILE the host assembles batch t - lag: the session hands out
       // the next input buffers as soon as the oldest batch has been collected.
-      struct Reads {
-        std::vector<std::thread> th; std::vector<char> ok;
-        bool join() { for (auto &x : th) if (x.joinable()) x.join(); th.clear(); for (char c : ok) if (!c) return false; return true; }
-        ~Reads() { for (auto &x : th) if (x.joinable()) x.join(); }
-      } reads;
+      Reads reads;
       auto start_reads = [&](int t) -> bool {
         void *py, *pu, *pv;
         if (av1mi_gop_acquire_input(gop, &py, &pu, &pv) != AV1MI_OK) { *err = std::string("av1mi_gop_acquire_input: ") + av1mi_last_error(ctx); return false; }
@@ -289,22 +344,22 @@ int RunBackend(const BackendJob &job, std::string *err) {
           }
           reads.th.emplace_back([&, s, t, py, pu, pv]() {
             if (!packed) {
-              reads.ok[(size_t)s] = y.read((long)s * G + t, rw, rh, (unsigned char *)py + py_bytes * s, (unsigned char *)pu + pc_bytes * s, (unsigned char *)pv + pc_bytes * s);
+              reads.ok[(size_t)s] = y.read((long)start[(size_t)s] + t, rw, rh, (unsigned char *)py + py_bytes * s, (unsigned char *)pu + pc_bytes * s, (unsigned char *)pv + pc_bytes * s);
               return;
             }
             // the frame (edge padding included) into this thread's scratch, then packed into the segment's byte range of the pinned planes
             std::vector<unsigned char> &f = scratch[(size_t)s];
             f.resize(fy + 2 * fc);
-            reads.ok[(size_t)s] = y.read((long)s * G + t, rw, rh, f.data(), f.data() + fy, f.data() + fy + fc) &&
+            reads.ok[(size_t)s] = y.read((long)start[(size_t)s] + t, rw, rh, f.data(), f.data() + fy, f.data() + fy + fc) &&
                                   av1mi_input_pack(AV1MI_INPUT_PACKED10, 10, rw, rh, f.data(), f.data() + fy, f.data() + fy + fc, (unsigned char *)py + py_bytes * s,
                                                    (unsigned char *)pu + pc_bytes * s, (unsigned char *)pv + pc_bytes * s) == AV1MI_OK;
           });
         }
         return true;
       };
-      if (T > 0 && !start_reads(0)) { code = 2; goto done; }
+      if (!stored && T > 0 && !start_reads(0)) { code = 2; goto done; }
       for (int t = 0; t < T; t++) {
-        if (!reads.join()) { *err = job.input + ": Invalid data found when processing input (truncated frame)"; code = 1; goto done; }
+        if (!stored && !reads.join()) { *err = job.input + ": Invalid data found when processing input (truncated frame)"; code = 1; goto done; }
         if (rc) {
           int frames = 0;
           for (int s = 0; s < S; s++) frames += exists(s, t) ? 1 : 0;
@@ -313,14 +368,27 @@ int RunBackend(const BackendJob &job, std::string *err) {
           if (q < 1) { *err = "rate control: no quantiser for the next batch"; code = 2; goto done; }
           CHK(av1mi_gop_set_base_q_idx(gop, q));
         }
-        CHK(av1mi_gop_submit(gop, t == 0 ? 0 : 1));
+        if (stored) {
+          for (int s = 0; s < S; s++) index[(size_t)s] = exists(s, t) ? start[(size_t)s] + t : -1;      // (-1: a flat slot, its output dropped)
+          CHK(av1mi_gop_submit_stored(gop, cur_store, index.data(), t == 0 ? 0 : 1));
+        } else CHK(av1mi_gop_submit(gop, t == 0 ? 0 : 1));
         const bool have = t >= lag;
         if (have && !collect_oldest()) { code = 2; goto done; }            // the GPU works on the frames after it meanwhile
-        if (t + 1 < T && !start_reads(t + 1)) { code = 2; goto done; }
+        // what is read beside the host's work on the oldest batch: the next batch's frames, or (stored) the next chunk of the next group
+        const int chunk = stored ? (int)std::min<long>(S, next_frames - next_put) : 0;
+        if (!stored && t + 1 < T && !start_reads(t + 1)) { code = 2; goto done; }
+        if (chunk > 0 && !put_begin(next_put, chunk)) { code = 2; goto done; }
         if (have && !assemble(t - lag)) { code = 2; goto done; }
+        if (chunk > 0) { if ((code = put_end(cur_store ^ 1, next_put, chunk)) != 0) goto done; next_put += chunk; }
       }
       for (int t = std::max(0, T - lag); t < T; t++)
         if (!collect_oldest() || !assemble(t)) { code = 2; goto done; }
+      for (; stored && next_put < next_frames; ) {      // (a group of short GOPs has fewer batches than the next group has chunks)
+        const int n = (int)std::min<long>(S, next_frames - next_put);
+        if (!put_begin(next_put, n)) { code = 2; goto done; }
+        if ((code = put_end(cur_store ^ 1, next_put, n)) != 0) goto done;
+        next_put += n;
+      }
       for (int s = 0; s < S; s++)
         for (size_t t = 0; t < units[(size_t)s].size(); t++)
           if (!sink.write(units[(size_t)s][t], t == 0, err)) { code = 1; goto done; }
@@ -331,10 +399,12 @@ int RunBackend(const BackendJob &job, std::string *err) {
             int n = snprintf(line, sizeof(line), "n:%ld type:%c bytes:%zu", summary.frames, t == 0 ? 'K' : 'P', units[(size_t)s][t].size());
             n += av1mi::quality::format_figures(av1mi::quality::frame_figures(records[(size_t)s][t].q, y.bd), line + n, sizeof(line) - (size_t)n);
             if (rc) n += snprintf(line + n, sizeof(line) - (size_t)n, " q:%d", qs[(size_t)s][t]);
+            if (stored && cut[(size_t)start[(size_t)s] + t]) n += snprintf(line + n, sizeof(line) - (size_t)n, " cut:1");
             stats.append(line, (size_t)n); stats += '\n';
             summary.add(records[(size_t)s][t].q, y.bd);
             total_bytes += (long long)units[(size_t)s][t].size();
           }
+      if (stored) cur_store ^= 1;
     }
     if (total_frames == 0) { *err = job.input + ": Invalid data found when processing input (no frames)"; code = 1; goto done; }
     if (!sink.close(err)) { code = 1; goto done; }

@@ -129,6 +129,12 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
     else if (args[i] == "-av1mi_me_range") {
       if (!plain_int(args[i + 1], &job->me_range) || job->me_range > 64 || (job->me_range & 3)) { if (err) *err = "Invalid argument: -av1mi_me_range takes 0 or a multiple of 4 up to 64, not " + args[i + 1]; return false; }
     }
+    else if (args[i] == "-av1mi_scenecut") {
+      if (!plain_int(args[i + 1], &job->scenecut) || job->scenecut > 99) { if (err) *err = "Invalid argument: -av1mi_scenecut takes a sensitivity 1 .. 99 (0 = off), not " + args[i + 1]; return false; }
+    }
+    else if (args[i] == "-av1mi_min_gop") {
+      if (!plain_int(args[i + 1], &job->min_gop) || job->min_gop < 1 || job->min_gop > 256) { if (err) *err = "Invalid argument: -av1mi_min_gop takes a length in frames (1 .. gop - gop / 2), not " + args[i + 1]; return false; }
+    }
     else if (args[i] == "-av1mi_min_psnr") {
       char *end = nullptr;
       job->min_psnr = std::strtod(args[i + 1].c_str(), &end);
@@ -179,6 +185,9 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
   if (job->bitrate && job->target_bpp_u) { if (err) *err = "Invalid argument: -b:v:0 and -av1mi_target_bpp are two forms of one target: give one"; return false; }
   if ((job->qmin || job->qmax) && !job->bitrate && !job->target_bpp_u) { if (err) *err = "Invalid argument: -qmin / -qmax need a target (-b:v:0 or -av1mi_target_bpp)"; return false; }
   if (job->qmin && job->qmax && job->qmin > job->qmax) { if (err) *err = "Invalid argument: -qmin " + std::to_string(job->qmin) + " above -qmax " + std::to_string(job->qmax); return false; }
+  if (job->scenecut && job->pack10) { if (err) *err = "Invalid argument: -av1mi_scenecut keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
+  if (job->min_gop && !job->scenecut) { if (err) *err = "Invalid argument: -av1mi_min_gop needs -av1mi_scenecut"; return false; }
+  if (job->min_gop && job->gop >= 1 && job->min_gop > job->gop - job->gop / 2) { if (err) *err = "Invalid argument: -av1mi_min_gop " + std::to_string(job->min_gop) + " above gop - gop / 2 = " + std::to_string(job->gop - job->gop / 2); return false; }
   if (!have_in) { if (err) *err = "Invalid argument: no input (-i) given"; return false; }
   if (job->quality < 0 || job->quality > 255 || job->gop < 1 || job->gop > 256 || job->segments < 1 || job->segments > 256 || job->threads < 0 || (job->key_block_size != 8 && job->key_block_size != 32) || (job->pack10 != 0 && job->pack10 != 1)) { if (err) *err = "Invalid argument: quality/gop/key block size/pack10 out of range"; return false; }
   return true;

@@ -74,6 +74,11 @@ struct BackendJob {
                            // yuv420p10le — the reference's chain always does, transcode.go:99-110), or -av1mi_format 420 was given.  The source may then be
                            // 4:2:2, 4:4:4 or grey, at 8, 10 or 12 bits (Y4mSource::open's any_layout); it is converted on the GPU (av1mi.h "chroma formats").
                            // The coded depth follows the SOURCE (8 -> 8, 10 -> 10, 12 -> 10), not the format's name.  Without it such a source is refused
+  int scenecut = 0;        // -av1mi_scenecut N: 0 (default) = off; 1 .. 99 = the sensitivity of the scene-cut rule (include/av1mi.h "scene analysis";
+                           // host/sceneplan.hpp AV1MI_SCENECUT_DEFAULT is the measured middle).  Every group of segments x gop frames is put into the
+                           // session's frame store in file order, analysed on the GPU, and its GOP boundaries are moved onto the cuts found
+                           // (av1mi_plan_gops): key frames land on the cuts, GOPs are min_gop .. 3/2 gop frames long.  Not with -av1mi_pack10 1
+  int min_gop = 0;         // -av1mi_min_gop M: the shortest GOP the planner makes, 1 .. gop - gop / 2; 0 = max(1, gop / 4).  Only with -av1mi_scenecut
   std::vector<std::string> tracks;   // -av1mi_tracks <file.mka> (repeatable): Matroska side files whose audio / subtitle tracks are copied
                                      // next to the video (the reference's `-c:a copy -c:s copy`, transcode.go:134-137, after an external demux)
 };

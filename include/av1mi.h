@@ -83,7 +83,7 @@ int av1mi_timer_end(av1mi_ctx *ctx, float *elapsed_ms);
 enum av1mi_kernel_kind {
   AV1MI_K_FWD_TXFM, AV1MI_K_INV_TXFM, AV1MI_K_QUANT, AV1MI_K_DEQUANT, AV1MI_K_INTRA_PRED, AV1MI_K_MC,
   AV1MI_K_DEBLOCK, AV1MI_K_CDEF, AV1MI_K_LR, AV1MI_K_INTRA_PIPE, AV1MI_K_INTER_PIPE, AV1MI_K_MISC, AV1MI_K_ENTROPY,
-  AV1MI_K_ENTROPY_PACK, AV1MI_K_ENTROPY_TOKENS, AV1MI_K_ME_INT, AV1MI_K_ENTROPY_CHAINS, AV1MI_K_INPUT, AV1MI_K_QUALITY, AV1MI_K_ME_COARSE, AV1MI_K_KINDS
+  AV1MI_K_ENTROPY_PACK, AV1MI_K_ENTROPY_TOKENS, AV1MI_K_ME_INT, AV1MI_K_ENTROPY_CHAINS, AV1MI_K_INPUT, AV1MI_K_QUALITY, AV1MI_K_ME_COARSE, AV1MI_K_SCENE, AV1MI_K_KINDS
 };
 int av1mi_prof_enable(av1mi_ctx *ctx, int on);
 int av1mi_prof_reset(av1mi_ctx *ctx);
@@ -474,6 +474,39 @@ typedef struct av1mi_quality { uint64_t sse; double ssim_sum; uint32_t samples, 
 int av1mi_quality_planes(av1mi_ctx *ctx, int bit_depth, int width, int height, int frames, const void *const d_src[3], const void *const d_dec0[3],
                          const void *const d_dec1[3], const uint8_t *d_select, av1mi_quality *d_out);
 
+/* ---- scene analysis: how much of every frame of a run of consecutive frames its predecessor explains (av1-go_amd/csrc/scene_kernels.hip),
+ * and the gather that builds a batch from frames held in device memory.  Integer arithmetic, bit exact by definition; P_f = the luma
+ * plane of frame f, in a buffer of W8 x H8 samples (the true size rounded up to 8, the last column / row replicated into the padding).
+ *   quarter plane  Q_f, exactly as "motion search" defines it: m8(v) = v >> (bit_depth - 8), Q_f[y][x] = (sum over i, j < 4 of
+ *                  m8(P_f[4 y + i][4 x + j]) + 8) >> 4, (W8 / 4) x (H8 / 4) samples.
+ *   blocks         8 x 8 quarter samples (32 x 32 luma): block (bx, by), bx < ceil(W8 / 32), by < ceil(H8 / 32), covers the quarter
+ *                  samples (x, y) in [8 bx, 8 bx + 8) x [8 by, 8 by + 8).  Q(x, y) below reads Q[clamp(y, 0, H8 / 4 - 1)][clamp(x, 0,
+ *                  W8 / 4 - 1)]: every coordinate, displaced or not, is clamped into the plane, so partial blocks replicate the edge.
+ *   per frame f >= 1 of the run and block b:
+ *                  inter(b) = the minimum over (dx, dy) in [-2, 2]^2 of the sum over the block's 64 samples of
+ *                             |Q_f(x, y) - Q_{f-1}(x + dx, y + dy)|;
+ *                  intra(b) = the sum of |Q_f(x, y) - m|, m = (sum of Q_f(x, y) + 32) >> 6.
+ *                  The frame's record: inter_sad and intra_sad are the sums over all blocks, blocks their number.  Frame 0 of a run has
+ *                  no predecessor: inter_sad = 0.  Every sum fits: a block's is at most 64 x 255 = 16 320.
+ *   determinism    two stages like the quality records: per-block pairs, then one fixed-order sum per frame; the only atomic is an
+ *                  integer minimum.  A run gives the same bytes every time.
+ *   a cut          frame f is a cut iff 100 inter_sad >= (100 - scenecut) intra_sad and intra_sad > 0, scenecut in 1..99 the
+ *                  sensitivity (the host's rule: av1-go_amd/host/sceneplan.hpp; the product's default is AV1MI_SCENECUT_DEFAULT there).
+ * Fades, flashes and cuts nearer to the start of a GOP than its minimum length are not handled. */
+typedef struct av1mi_scene_record { uint64_t inter_sad, intra_sad; uint32_t blocks, reserved; } av1mi_scene_record;
+/* The records of `frames` (1 .. 65535) consecutive frames whose luma planes are stacked in d_luma: width x height samples each, both
+ * multiples of 8 (the buffers' size), uint8 at bit_depth 8, uint16 at 10 or 12.  d_records: `frames` records in device memory, 8-byte
+ * aligned; d_luma 16-byte aligned.  Three launches (quarter planes, blocks, sum), asynchronous on the context's stream; the quarter
+ * planes and block results live in the context (grown on demand).  AV1MI_K_SCENE in the profile. */
+int av1mi_scene_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int frames, const void *d_luma, av1mi_scene_record *d_records);
+/* The gather, ONE launch: for every segment s < segments and plane p < 3, plane_bytes[p] bytes from d_src_table[s * 3 + p] — a table of
+ * segments * 3 device pointers IN DEVICE MEMORY, each 16-byte aligned, or null for a flat slot, which is written as zeros — to
+ * d_dst[p] + s * plane_bytes[p]: the stacked layout every stage of a batch reads.  plane_bytes: multiples of 4 (0 = no such plane);
+ * d_dst[p] 16-byte aligned.  A 4:2:0 plane of a frame whose size is a multiple of 8 is a multiple of 16 bytes (the smallest: 8 x 8
+ * luma = 64 bytes, 4 x 4 chroma = 16) and moves in 16-byte units; any other in single dwords.  Asynchronous on the context's stream;
+ * AV1MI_K_SCENE in the profile. */
+int av1mi_frames_gather(av1mi_ctx *ctx, const size_t plane_bytes[3], int segments, const void *const *d_src_table, void *const d_dst[3]);
+
 /* ---- GOP session: the encoder object a cgo replacement of RunTranscode drives (reference call site
  * internal/daemon/daemon.go:101 -> internal/ffmpeg/transcode.go:194; SURVEY.md §8b "av1mi_open(config) / av1mi_encode /
  * av1mi_flush").  It owns the closed-GOP orchestration and the encoder's filter-parameter POLICY, so that no caller
@@ -547,6 +580,16 @@ typedef struct av1mi_gop_config {
    * edge into its padding when the session does not scale; chroma padding may be undefined).  input_format must be PLANAR.  Scaling,
    * visible_*, quality_stats (measured against the converted frame) and coarse_range work unchanged behind the stage. */
   int source_chroma, source_bit_depth;
+  /* The frame store (0 = none: nothing below is allocated, launched or accepted).  Otherwise the session owns TWO stores of store_frames
+   * fed frames each, in the fed layout (what av1mi_gop_acquire_input hands out, one frame = one segment's share of it), plus the scene
+   * analysis' quarter planes and block results for one store and pinned records.  A group of frames is put into a store in FILE ORDER
+   * (av1mi_gop_store_put), analysed (av1mi_gop_store_analyse) and then coded in any layout of segments and positions
+   * (av1mi_gop_submit_stored): one launch (k_frames_gather) builds each batch's fed buffers from the store in place of the upload.
+   * input_format must be PLANAR; source_chroma / source_bit_depth / scaling work unchanged, because the store holds what the session is
+   * fed.  The analysis reads the luma planes' padding: the caller replicates the edge into it (also where the session scales).  Such
+   * a session is fed through the store or av1mi_gop_submit_device; av1mi_gop_submit is refused.  At 4K 10-bit, 12 segments x 30
+   * frames, the two stores are 2 x 9 GB. */
+  int store_frames;
 } av1mi_gop_config;
 
 /* Frame-header parameters chosen by the session's policy for one frame (non-normative encoder choices; the bitstream carries
@@ -605,7 +648,10 @@ void av1mi_gop_close(av1mi_gop *g);
  * A session with source_chroma / source_bit_depth hands out planes of av1mi_source_plane_bytes each; grey sources: *u = *v = NULL. */
 int av1mi_gop_acquire_input(av1mi_gop *g, void **y, void **u, void **v);
 /* queue the batch in the acquired buffers.  frame_type: 0 key, 1 inter, -1 = by position in the GOP (gop_length).
- * AV1MI_E_INVAL when av1mi_gop_max_in_flight() batches are already in flight (collect first). */
+ * AV1MI_E_INVAL when av1mi_gop_max_in_flight() batches are already in flight (collect first).
+ * An explicit frame type is all the session needs to know about a GOP: gop_length only drives frame_type -1, and no buffer, table or
+ * counter is sized by it.  A caller that gives types may place its key batches freely; the product's planner (host/sceneplan.hpp) lets
+ * up to 3/2 gop_length batches lie between two of them. */
 int av1mi_gop_submit(av1mi_gop *g, int frame_type);
 /* The same for a batch whose source planes are ALREADY in device memory (same layout as the pinned planes: segments stacked, stride =
  * width; in the session's input_format, d_v ignored by P010 / NV12, 16-byte aligned unless PLANAR): no upload is queued, the kernels
@@ -623,6 +669,20 @@ int av1mi_gop_submit_device(av1mi_gop *g, const void *d_y, const void *d_u, cons
  * device-side deblocking maps and CDEF records hold another quantiser's levels than the batch's, one small launch (k_mi_levels) in
  * front of the batch's filters patches the level fields in place. */
 int av1mi_gop_set_base_q_idx(av1mi_gop *g, int base_q_idx);
+/* ---- the frame store (av1mi_gop_config.store_frames).  `store` is 0 or 1.
+ * av1mi_gop_store_put: the count <= segments frames the caller wrote into the buffers of av1mi_gop_acquire_input (frame i where segment
+ * i of a batch would lie) go to positions first .. first + count - 1 of the store, on the upload stream; nothing is coded.  In a session
+ * with a store av1mi_gop_acquire_input rotates over the session's pinned buffers whatever is in flight, and waits only for the copy that
+ * last read the buffer it hands out.  The copy waits (an event, not the host) for every batch submitted so far that reads this store. */
+int av1mi_gop_store_put(av1mi_gop *g, int store, int first, int count);
+/* The scene analysis over frames 0 .. frames - 1 of the store (a run: frame 0 gets inter_sad 0), `frames` records copied to out.  It
+ * runs on the upload stream behind the puts and waits for ITS records only: batches of the other store that are in flight keep running. */
+int av1mi_gop_store_analyse(av1mi_gop *g, int store, int frames, av1mi_scene_record *out);
+/* A batch from the store: index[s] (segments entries) = the store position of segment s's frame, or -1 for a flat slot (zeros, as the
+ * product feeds a segment that has no frame; its output is to be dropped).  The gather stands in for the upload, the stages follow as
+ * ever.  frame_type must be 0 or 1: the layout is the caller's.  A later av1mi_gop_store_put into the same store is ordered behind this
+ * batch's gather by an event. */
+int av1mi_gop_submit_stored(av1mi_gop *g, int store, const int32_t *index, int frame_type);
 /* wait for the oldest batch in flight and describe its symbols; AV1MI_E_INVAL when nothing is in flight */
 int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out);
 /* number of batches in flight (0..av1mi_gop_max_in_flight()) */
