@@ -91,7 +91,7 @@ class GopConfig(C.Structure):
                 ("segments", C.c_int), ("search_range", C.c_int), ("gpu_entropy", C.c_int), ("visible_width", C.c_int),
                 ("visible_height", C.c_int), ("coder_streams", C.c_int), ("key_block_size", C.c_int), ("input_format", C.c_int), ("source_width", C.c_int),
                 ("source_height", C.c_int), ("quality_stats", C.c_int), ("coarse_range", C.c_int), ("source_chroma", C.c_int),
-                ("source_bit_depth", C.c_int), ("store_frames", C.c_int)]
+                ("source_bit_depth", C.c_int), ("store_frames", C.c_int), ("deinterlace", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -209,7 +209,7 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
@@ -219,12 +219,14 @@ class GopSession:
         source_chroma / source_bit_depth: CHROMA_* and 8 / 10 / 12 of the source the session is fed (av1mi_gop_config.source_chroma): the
         input buffers then have that layout (source_plane_shapes), and no chroma planes for a grey source;
         store_frames: the session owns two frame stores of that many fed frames (av1mi_gop_config.store_frames): store_put(),
-        store_analyse() and submit_stored() feed it, submit() is refused"""
+        store_analyse() and submit_stored() feed it, submit() is refused;
+        deinterlace: 0 none, 1 top field first, 2 bottom field first (av1mi_gop_config.deinterlace; needs store_frames): submit_stored()
+        gathers through the deinterlacer"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
         sw, sh = source if source is not None else (0, 0)
         self.cfg = GopConfig(width, height, bit_depth, base_q_idx, gop_length, segments, search_range, gpu_entropy, vw, vh, coder_streams, key_block_size, input_format,
-                             sw, sh, int(quality_stats), int(coarse_range), int(source_chroma), int(source_bit_depth), int(store_frames))
+                             sw, sh, int(quality_stats), int(coarse_range), int(source_chroma), int(source_bit_depth), int(store_frames), int(deinterlace))
         self.source_chroma, self.src_bd = int(source_chroma), int(source_bit_depth) or bit_depth
         self.in_w, self.in_h = ((sw + 7) & ~7, (sh + 7) & ~7) if source is not None else (width, height)      # geometry of the input buffers
         self.input_format = input_format
@@ -342,6 +344,15 @@ class GopSession:
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
         self.ctx._chk(self.ctx.lib.av1mi_gop_download_reference(self.g, vp(y), vp(u), vp(v)))
         return y, u, v
+
+    def download_fed(self):
+        """the fed buffers of the last submitted batch (av1mi_gop_download_fed): arrays shaped like input_planes()"""
+        S, w, h = self.segments, self.in_w, self.in_h
+        dt = np.uint8 if self.src_bd == 8 else np.uint16
+        out = [np.empty(shp, dt) if shp else None for shp in source_plane_shapes(self.source_chroma, w, S * h)]
+        self.ctx.lib.av1mi_gop_download_fed.argtypes = [C.c_void_p] * 4
+        self.ctx._chk(self.ctx.lib.av1mi_gop_download_fed(self.g, *[a.ctypes.data if a is not None else None for a in out]))
+        return tuple(a for a in out if a is not None)
 
     def close(self):
         if self.g:
@@ -574,6 +585,16 @@ class Context:
         nb = (C.c_size_t * 3)(*[int(b) for b in plane_bytes])
         dst = (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_dst])
         self._chk(self.lib.av1mi_frames_gather(self.h, nb, int(segments), d_table.ptr, dst))
+
+    def deinterlace_gather(self, bit_depth, plane_sizes, true_sizes, parity, segments, d_table, d_dst):
+        """one launch: the gather with the deinterlacer in it (av1mi_deinterlace_gather).  plane_sizes / true_sizes: (w, h) in samples per
+        plane, (0, 0) = no such plane; d_table: DevBuf of segments * 9 uint64, [(s * 3 + p) * 3 + i] = plane p of segment s's frame P, C, N
+        (C 0 = zeros); d_dst[p]: DevBuf (None for an absent plane); asynchronous"""
+        self.lib.av1mi_deinterlace_gather.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        arr = lambda v: (C.c_int * 3)(*[int(x) for x in v])
+        dst = (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_dst])
+        self._chk(self.lib.av1mi_deinterlace_gather(self.h, int(bit_depth), arr([s[0] for s in plane_sizes]), arr([s[1] for s in plane_sizes]),
+                                                    arr([s[0] for s in true_sizes]), arr([s[1] for s in true_sizes]), int(parity), int(segments), d_table.ptr, dst))
 
     def prof_enable(self, on):
         self._chk(self.lib.av1mi_prof_enable(self.h, int(on)))

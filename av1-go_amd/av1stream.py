@@ -242,6 +242,32 @@ def plan_gops(n, G, S, cut, min_len=0):
     return K, start, ln
 
 
+DEINTERLACE_MODES = ("off", "auto", "tff", "bff")      # BackendJob::deinterlace, -av1mi_deinterlace
+
+
+def y4m_interlace(path):
+    """the I parameter of a Y4M header as the host's reader keeps it: "p" (Ip, I? or absent), "t", "b" or "m"; ValueError when the file
+    does not open"""
+    h = lib()
+    h.av1mi_host_y4m_interlace.argtypes = [C.c_char_p]
+    k = h.av1mi_host_y4m_interlace(str(path).encode())
+    if k < 0:
+        raise ValueError("not a Y4M source: %s" % path)
+    return "ptbm"[k]
+
+
+def parse_deinterlace_option(argv):
+    """what an argument vector asks of the deinterlacer (-av1mi_deinterlace, or a deinterlacing filter in the chain): one of
+    DEINTERLACE_MODES; ValueError with the host's text where the vector is refused"""
+    h = lib()
+    h.av1mi_host_parse_deinterlace_option.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
+    err = C.create_string_buffer(1024)
+    k = h.av1mi_host_parse_deinterlace_option("\n".join(str(x) for x in argv).encode(), err, 1024)
+    if k < 0:
+        raise ValueError(err.value.decode())
+    return DEINTERLACE_MODES[k]
+
+
 def run_transcode(argv):
     """av1mi_run_transcode (include/av1mi_host.h) on an argument vector: (exit code, error text)"""
     h = lib()

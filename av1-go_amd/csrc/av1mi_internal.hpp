@@ -185,6 +185,16 @@ hipError_t launch_scene(const SceneLaunch &S, hipStream_t s);
 // the gather (scene_kernels.hip): table[segment * 3 + plane] = where that segment's plane of plane_bytes[plane] bytes lies in device
 // memory (16-byte aligned), or null = zeros -> dst[plane] + segment * plane_bytes[plane]; ONE launch.  table is device memory.
 hipError_t launch_frames_gather(const size_t plane_bytes[3], int segments, const void *const *table, void *const dst[3], hipStream_t s);
+// the deinterlacing gather (deint_kernels.hip, include/av1mi.h "deinterlacing"): the gather above with the filter in it.  table[(segment *
+// 3 + plane) * 3 + {0, 1, 2}] = that segment's plane of frames P, C and N in device memory (the run's clamping applied by the caller;
+// C null = zeros); plane_w x plane_h: the buffers' size in samples (0 = no such plane), true_w x true_h the size the filter works at,
+// less than 8 below it; bd 8 = uint8 samples, else uint16; parity 0 = the even lines are kept.  ONE launch.
+struct DeintLaunch {
+  int bd, parity, segments;
+  int plane_w[3], plane_h[3], true_w[3], true_h[3];
+  const void *const *table; void *dst[3];
+};
+hipError_t launch_deint_gather(const DeintLaunch &L, hipStream_t s);
 
 // side information that follows a batch's quantiser (levels_kernels.hip): up to three arrays of dwords patched in place in one launch,
 // word = (word & keep) | bits unless (word & hold) != 0

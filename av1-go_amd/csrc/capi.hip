@@ -627,6 +627,29 @@ int av1mi_frames_gather(av1mi_ctx *ctx, const size_t plane_bytes[3], int segment
   return AV1MI_OK;
 }
 
+int av1mi_deinterlace_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int parity,
+                             int segments, const void *const *d_table, void *const d_dst[3]) {
+  BIND(ctx);
+  if (!plane_w || !plane_h || !true_w || !true_h || !d_table || !d_dst || ((uintptr_t)d_table & 7)) return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: null pointer or misaligned table");
+  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: bit depth %d not supported (8, 10 or 12)", bit_depth);
+  if (parity != 0 && parity != 1) return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: parity %d (0 = top field first, 1 = bottom field first)", parity);
+  if (segments < 1 || segments > 4096) return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: segments %d out of range (1 .. 4096)", segments);
+  av1mi::DeintLaunch L;
+  L.bd = bit_depth; L.parity = parity; L.segments = segments; L.table = d_table;
+  for (int p = 0; p < 3; p++) {
+    const bool have = plane_w[p] > 0 && plane_h[p] > 0;
+    if (plane_w[p] < 0 || plane_h[p] < 0 || plane_w[p] > 16384 || plane_h[p] > 16384 || ((size_t)plane_w[p] * (bit_depth == 8 ? 1 : 2) & 3))
+      return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: plane %d of %dx%d samples (rows of whole dwords, up to 16384x16384)", p, plane_w[p], plane_h[p]);
+    if (have && (true_w[p] < 1 || true_h[p] < 1 || true_w[p] > plane_w[p] || true_h[p] > plane_h[p] || plane_w[p] - true_w[p] >= 8 || plane_h[p] - true_h[p] >= 8))
+      return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: plane %d: the true size %dx%d must lie within 7 samples below the buffer's %dx%d", p, true_w[p], true_h[p], plane_w[p], plane_h[p]);
+    if (have && (!d_dst[p] || ((uintptr_t)d_dst[p] & 15))) return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: null or misaligned destination (plane %d)", p);
+    L.plane_w[p] = have ? plane_w[p] : 0; L.plane_h[p] = have ? plane_h[p] : 0; L.true_w[p] = true_w[p]; L.true_h[p] = true_h[p]; L.dst[p] = d_dst[p];
+  }
+  ProfScope ps(ctx, AV1MI_K_SCENE);
+  HIP_TRY(ctx, av1mi::launch_deint_gather(L, ctx->stream));
+  return AV1MI_OK;
+}
+
 int av1mi_intra_encode(av1mi_ctx *ctx, const av1mi_intra_job *j) {
   BIND(ctx);
   if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");

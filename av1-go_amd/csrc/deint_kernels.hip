@@ -1,0 +1,242 @@
+// deint_kernels.hip — the deinterlacing gather behind av1mi_gop_config.deinterlace (include/av1mi.h "deinterlacing"): k_deint_gather
+// stands where k_frames_gather (scene_kernels.hip) stands in a session that does not deinterlace.  ONE launch builds the fed buffers of
+// a batch from the frame store, and on the way replaces the lines of every frame's second field.
+//
+//   work      an item is (segment, plane, band of kBand output rows, group of 64 cells); a cell is 16 bytes of a row, one lane's.  A wave
+//             owns an item, a workgroup four consecutive items of one (segment, plane): both are uniform in a workgroup.
+//   rows      the wave walks down its band.  Per kept row it holds a SET in registers: the C row's cell with 3 samples on either side, and
+//             the cells of the same row of P and N.  A missing row y needs the sets of rows up and dn plus the cells P[y] and C[y]; the set
+//             that was dn becomes up two rows later, so inside a band every row of C, P and N is loaded once (a band re-reads the one kept
+//             row above it).  Kept rows are stored from the set's own cell: a straight copy.
+//   columns   the 3 samples beside a cell are the neighbouring lanes' edge dwords, moved by ds_bpermute_b32 (the LDS crossbar; no LDS
+//             memory is allocated).  Lanes 0 and 63 of a wave, whose neighbour is another wave's, load those dwords (1 at 8 bits, 2 at 16)
+//             from memory.  At the plane's true edge the window is clamped in registers; nothing beyond the buffer's row is read.
+//   tails     a plane whose rows are whole 16-byte units moves in dwordx4; any other (rows are always whole dwords) in single dwords,
+//             the last cell of a row partly.
+//   padding   output columns beyond the true width repeat the last true column's OUTPUT, output rows beyond the true height the last
+//             true row's: both by construction (a row y >= h is computed as row h - 1).  The input's padding is never used.
+// Arithmetic: include/av1mi.h; restated in numpy by tests/deinterlace_ref.py.  Reference tree: nothing (transcode.go:120).
+#include "av1mi_internal.hpp"
+
+namespace av1mi {
+
+namespace {
+constexpr int kBand = 16;      // output rows per item (even)
+
+struct DeintGeom {
+  void *dst[3];
+  uint32_t plane_bytes[3];     // of one segment's plane in the destination (= a frame's plane in the store)
+  uint32_t row_bytes[3];       // multiples of 4
+  int32_t rows[3];             // buffer rows
+  int32_t w[3], h[3];          // true size in samples
+  uint32_t cells[3];           // 16-byte cells per row (the last one may be partial)
+  uint32_t groups[3];          // groups of 64 cells per row
+  uint32_t items[3];           // groups x bands
+  uint32_t wgs[3];             // workgroups per (segment, plane)
+  uint32_t per_seg;
+  int parity, segments;
+};
+
+template <typename Pix>
+__device__ __forceinline__ int elem(const uint32_t *d, int i) {
+  if constexpr (sizeof(Pix) == 1) return (int)((d[i >> 2] >> (8 * (i & 3))) & 0xffu);
+  else return (int)((d[i >> 1] >> (16 * (i & 1))) & 0xffffu);
+}
+
+// the cell at byte `off` of a row of rb bytes; dwords beyond the row, and all of an inactive lane's, are 0
+__device__ __forceinline__ void load_cell(const char *row, uint32_t off, uint32_t rb, bool whole, bool active, uint32_t c[4]) {
+  c[0] = c[1] = c[2] = c[3] = 0;
+  if (!active) return;
+  if (whole) {
+    const uint4 v = *reinterpret_cast<const uint4 *>(row + off);
+    c[0] = v.x; c[1] = v.y; c[2] = v.z; c[3] = v.w;
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+      if (off + 4u * q < rb) c[q] = *reinterpret_cast<const uint32_t *>(row + off + 4u * q);
+  }
+}
+__device__ __forceinline__ void store_cell(char *row, uint32_t off, uint32_t rb, bool whole, bool active, const uint32_t c[4]) {
+  if (!active) return;
+  if (whole) *reinterpret_cast<uint4 *>(row + off) = make_uint4(c[0], c[1], c[2], c[3]);
+  else {
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+      if (off + 4u * q < rb) *reinterpret_cast<uint32_t *>(row + off + 4u * q) = c[q];
+  }
+}
+
+// samples of a cell -> its dwords, the columns beyond the true width (sample index above `lastj`) repeating the last true one
+template <typename Pix, int NS>
+__device__ __forceinline__ void pack_cell(int o[NS], int lastj, uint32_t c[4]) {
+#pragma unroll
+  for (int j = 1; j < NS; j++) o[j] = j > lastj ? o[j - 1] : o[j];
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    if constexpr (sizeof(Pix) == 1) c[q] = (uint32_t)o[4 * q] | (uint32_t)o[4 * q + 1] << 8 | (uint32_t)o[4 * q + 2] << 16 | (uint32_t)o[4 * q + 3] << 24;
+    else c[q] = (uint32_t)o[2 * q] | (uint32_t)o[2 * q + 1] << 16;
+  }
+}
+
+// one kept row as the filter needs it: the C row's cell with HD dwords on either side (c[HD .. HD + 3] is the cell), and the cells of the
+// same row of P and N
+template <int ND>
+struct RowSet { uint32_t c[ND], p[4], n[4]; };
+
+__device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
+
+}  // namespace
+
+// grid: per_seg x segments; 4 waves = 4 consecutive items of one (segment, plane)
+template <typename Pix>
+__global__ __launch_bounds__(256) void k_deint_gather(DeintGeom G, const void *const *table) {
+  constexpr int NS = 16 / (int)sizeof(Pix);      // samples per cell
+  constexpr int HD = (int)sizeof(Pix);           // dwords that hold 3 samples beside a cell (they hold 4)
+  constexpr int ND = 4 + 2 * HD;
+  constexpr int NW = NS + 6;                     // the window: samples x0 - 3 .. x0 + NS + 2
+  const unsigned seg = blockIdx.x / G.per_seg;
+  unsigned wg = blockIdx.x - seg * G.per_seg;
+  int p = 0;
+  if (wg >= G.wgs[0]) { wg -= G.wgs[0]; p = 1; }
+  if (p == 1 && wg >= G.wgs[1]) { wg -= G.wgs[1]; p = 2; }
+#define PL(a) (p == 0 ? G.a[0] : p == 1 ? G.a[1] : G.a[2])
+  const uint32_t rb = PL(row_bytes), cells = PL(cells), groups = PL(groups), items = PL(items);
+  const int rows = PL(rows), w = PL(w), h = PL(h), k = G.parity;
+  char *dst = (char *)PL(dst) + (size_t)seg * PL(plane_bytes);
+#undef PL
+  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  const unsigned item = wg * 4u + wave;
+  if (item >= items) return;                     // (uniform in the wave; the kernel has no barrier)
+  const unsigned band = item / groups, grp = item - band * groups;
+  const uint32_t cx = grp * 64u + lane, off = cx * 16u;
+  const bool active = cx < cells, whole = !(rb & 15u);
+  const int r0 = (int)band * kBand, r1 = min(r0 + kBand, rows);
+  const char *const *tab = reinterpret_cast<const char *const *>(table) + ((size_t)seg * 3 + p) * 3;
+  const char *P = tab[0], *C = tab[1], *N = tab[2];
+  if (!C) {                                      // a flat slot
+    const uint32_t z[4] = { 0, 0, 0, 0 };
+    for (int y = r0; y < r1; y++) store_cell(dst + (size_t)y * rb, off, rb, whole, active, z);
+    return;
+  }
+  const int x0 = (int)cx * NS;                   // the cell's first sample; x0 <= w - 1 in every active lane (the buffer is < 8 samples wider)
+  const int lastj = w - 1 - x0;                  // sample of the cell that is the last true column (>= NS: the cell is all true)
+  const bool first_cell = cx == 0, edge = first_cell || lastj < NS + 2;
+
+  // the set of kept row r
+  auto load_set = [&](RowSet<ND> &S, int r) {
+    const size_t ro = (size_t)r * rb;
+    uint32_t cell[4];
+    load_cell(C + ro, off, rb, whole, active, cell);
+    load_cell(P + ro, off, rb, whole, active, S.p);
+    load_cell(N + ro, off, rb, whole, active, S.n);
+#pragma unroll
+    for (int q = 0; q < 4; q++) S.c[HD + q] = cell[q];
+#pragma unroll
+    for (int q = 0; q < HD; q++) {               // every lane of the wave is here: the branch around load_set is uniform
+      S.c[q] = __shfl_up(cell[4 - HD + q], 1);
+      S.c[HD + 4 + q] = __shfl_down(cell[q], 1);
+    }
+    if (lane == 0 && active && cx > 0) {         // the neighbours are another wave's
+#pragma unroll
+      for (int q = 0; q < HD; q++) S.c[q] = *reinterpret_cast<const uint32_t *>(C + ro + off - 4u * (HD - q));
+    }
+    if (lane == 63 && cx + 1 < cells) {
+#pragma unroll
+      for (int q = 0; q < HD; q++) S.c[HD + 4 + q] = off + 16u + 4u * q < rb ? *reinterpret_cast<const uint32_t *>(C + ro + off + 16u + 4u * q) : 0u;
+    }
+  };
+  // the window of a set's C row, clamped at the true edge
+  auto window = [&](const RowSet<ND> &S, int W[NW]) {
+#pragma unroll
+    for (int i = 0; i < NW; i++) W[i] = elem<Pix>(S.c, i + (4 / (int)sizeof(Pix)) * HD - 3);
+    if (edge) {
+      if (first_cell) W[0] = W[1] = W[2] = W[3];
+#pragma unroll
+      for (int i = 4; i < NW; i++) W[i] = i > lastj + 3 ? W[i - 1] : W[i];
+    }
+  };
+
+  RowSet<ND> up, dn;
+  int held_up = -1, held_dn = -1;
+#pragma unroll 1
+  for (int y = r0; y < r1; y++) {
+    const int ye = min(y, h - 1);
+    char *out_row = dst + (size_t)y * rb;
+    if (h == 1 || (ye & 1) == k) {               // a kept row
+      if (ye != held_dn) { load_set(dn, ye); held_dn = ye; }
+      uint32_t c[4] = { dn.c[HD], dn.c[HD + 1], dn.c[HD + 2], dn.c[HD + 3] };
+      if (lastj < NS - 1) {                      // the cell reaches into the padding
+        int o[NS];
+#pragma unroll
+        for (int j = 0; j < NS; j++) o[j] = elem<Pix>(c, j);
+        pack_cell<Pix, NS>(o, lastj, c);
+      }
+      store_cell(out_row, off, rb, whole, active, c);
+      continue;
+    }
+    const int ur = ye >= 1 ? ye - 1 : ye + 1, dr = ye + 1 <= h - 1 ? ye + 1 : ye - 1;
+    if (ur != held_up) {
+      if (ur == held_dn) up = dn; else load_set(up, ur);
+      held_up = ur;
+    }
+    if (dr != held_dn) {
+      if (dr == ur) dn = up; else load_set(dn, dr);
+      held_dn = dr;
+    }
+    uint32_t py[4], cy[4];
+    load_cell(P + (size_t)ye * rb, off, rb, whole, active, py);
+    load_cell(C + (size_t)ye * rb, off, rb, whole, active, cy);
+    int A[NW], B[NW], o[NS];
+    window(up, A);
+    window(dn, B);
+#pragma unroll
+    for (int j = 0; j < NS; j++) {
+      const int c = j + 3;
+      int best = iabs(A[c - 1] - B[c - 1]) + iabs(A[c] - B[c]) + iabs(A[c + 1] - B[c + 1]), ba = A[c], bb = B[c];
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int d = i == 0 ? -1 : i == 1 ? 1 : i == 2 ? -2 : 2;
+        const int sc = iabs(A[c - 1 + d] - B[c - 1 - d]) + iabs(A[c + d] - B[c - d]) + iabs(A[c + 1 + d] - B[c + 1 - d]);
+        const bool better = sc < best;
+        best = better ? sc : best; ba = better ? A[c + d] : ba; bb = better ? B[c - d] : bb;
+      }
+      const int s = (ba + bb + 1) >> 1;
+      const int t0 = elem<Pix>(py, j), t1 = elem<Pix>(cy, j), t = (t0 + t1 + 1) >> 1;
+      int m = (iabs(t0 - t1) + 1) >> 1;
+      m = max(m, (iabs(elem<Pix>(up.p, j) - A[c]) + iabs(elem<Pix>(dn.p, j) - B[c]) + 1) >> 1);
+      m = max(m, (iabs(elem<Pix>(up.n, j) - A[c]) + iabs(elem<Pix>(dn.n, j) - B[c]) + 1) >> 1);
+      o[j] = min(max(s, t - m), t + m);
+    }
+    uint32_t c[4];
+    pack_cell<Pix, NS>(o, lastj, c);
+    store_cell(out_row, off, rb, whole, active, c);
+  }
+}
+
+hipError_t launch_deint_gather(const DeintLaunch &L, hipStream_t s) {
+  DeintGeom G;
+  const uint32_t bps = L.bd == 8 ? 1 : 2;
+  G.per_seg = 0; G.segments = L.segments; G.parity = L.parity;
+  for (int p = 0; p < 3; p++) {
+    const size_t rb = (size_t)L.plane_w[p] * bps, bytes = rb * (size_t)L.plane_h[p];
+    const bool have = L.plane_w[p] > 0 && L.plane_h[p] > 0;
+    if (bytes > 0x7FFFFFF0u || (rb & 3)) return hipErrorInvalidValue;
+    if (have && (L.true_w[p] < 1 || L.true_h[p] < 1 || L.true_w[p] > L.plane_w[p] || L.true_h[p] > L.plane_h[p] || L.plane_w[p] - L.true_w[p] >= 8 ||
+                 L.plane_h[p] - L.true_h[p] >= 8))
+      return hipErrorInvalidValue;
+    G.dst[p] = L.dst[p]; G.plane_bytes[p] = have ? (uint32_t)bytes : 0; G.row_bytes[p] = (uint32_t)rb; G.rows[p] = L.plane_h[p]; G.w[p] = L.true_w[p]; G.h[p] = L.true_h[p];
+    G.cells[p] = have ? (uint32_t)((rb + 15) >> 4) : 0;
+    G.groups[p] = (G.cells[p] + 63) / 64;
+    G.items[p] = have ? G.groups[p] * (uint32_t)((L.plane_h[p] + kBand - 1) / kBand) : 0;
+    G.wgs[p] = (G.items[p] + 3) / 4;
+    G.per_seg += G.wgs[p];
+  }
+  if (L.segments <= 0 || !G.per_seg) return hipSuccess;
+  if ((size_t)G.per_seg * L.segments > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  const dim3 grid(G.per_seg * (unsigned)L.segments);
+  if (L.bd == 8) hipLaunchKernelGGL(k_deint_gather<uint8_t>, grid, dim3(256), 0, s, G, L.table);
+  else hipLaunchKernelGGL(k_deint_gather<uint16_t>, grid, dim3(256), 0, s, G, L.table);
+  return hipGetLastError();
+}
+
+}  // namespace av1mi

@@ -6,7 +6,8 @@
 // Streams.  The context's stream runs the kernels; the session adds an upload stream and a download stream.  A batch is the stages
 // of submit_batch, in this order on every stream:
 //   feed_source       (a batch from the frame store, av1mi_gop_submit_stored: main: wait store.filled -> k_frames_gather into the fed buffers
-//                     -> store.read_done, in place of the upload; the input stages follow as below)
+//                     -> store.read_done, in place of the upload; the input stages follow as below.  A session that deinterlaces
+//                     (av1mi_gop_config.deinterlace) launches k_deint_gather in its place: same events, and the store is only read)
 //                     up:   wait slot.filters_done (the kernels that last read this slot's source) -> H2D of the fed buffers -> uploaded
 //                     main: wait uploaded -> [k_input_convert] -> [k_chroma_convert] -> [k_scale]
 //   code_blocks       main: k_intra_pipe | [k_me_down + k_me_coarse] + k_me_int + k_inter_pipe -> kernel_done
@@ -35,6 +36,7 @@
 // what av1mi_gop_store_analyse waits for, so the batches of the OTHER store that are in flight on the main stream are not waited for.
 // The main stream reads a store only in a batch's gather: it waits for store.filled (recorded behind the last put) and records
 // store.read_done behind the gather, which the next put into that store waits for on the upload stream.  No host wait orders the two.
+#include <algorithm>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -121,6 +123,7 @@ struct Store {
   void *d[3] = { nullptr, nullptr, nullptr };
   hipEvent_t filled = nullptr, read_done = nullptr;      // behind the last put (upload stream) / behind the last gather (main stream)
   bool has_fill = false, has_reader = false;
+  int run = 0;                                           // frames 0 .. run - 1 were put since position 0 was last put: the deinterlacer's run
 };
 
 }  // namespace
@@ -169,6 +172,7 @@ struct av1mi_gop {
   long puts = 0;                               // av1mi_gop_store_put calls: the pinned buffers of slot puts % kSlots are handed out next
   hipEvent_t put_done[kSlots] = {};            // the copy that last read those pinned buffers
   bool put_pending[kSlots] = {};
+  av1mi::DeintLaunch deint{};                  // cfg.deinterlace: the geometry of the fed planes (buffers and true sizes); table and dst per batch
   std::vector<void *> dev_allocs, host_allocs;
 };
 
@@ -227,8 +231,10 @@ int slot_buffers(av1mi_gop *g, Slot &s) {
     G_HIP(hipEventCreateWithFlags(&s.ent_done, hipEventDisableTiming));
   }
   if (c.store_frames) {
-    G_TRY(host_alloc(g, &s.h_table, (size_t)S * 3 * sizeof(void *)));
-    G_TRY(dev_alloc(g, &s.d_table, (size_t)S * 3 * sizeof(void *)));
+    // (a session that deinterlaces keeps three pointers per segment and plane: the frames before, at and after the position)
+    const size_t entries = (size_t)S * 3 * (c.deinterlace ? 3 : 1);
+    G_TRY(host_alloc(g, &s.h_table, entries * sizeof(void *)));
+    G_TRY(dev_alloc(g, &s.d_table, entries * sizeof(void *)));
   }
   if (c.quality_stats) {
     G_TRY(host_alloc(g, &s.h_quality, (size_t)S * 3 * sizeof(av1mi_quality)));
@@ -332,6 +338,8 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
     return WHY("quality_stats needs a true luma size of at least 16x16");
   if (c->store_frames < 0 || c->store_frames > 65535) return WHY("store_frames %d out of range (0 = none, up to 65535)", c->store_frames);
   if (c->store_frames && c->input_format != AV1MI_INPUT_PLANAR) return WHY("a frame store (store_frames %d) needs input_format 0 (planar), not %d", c->store_frames, c->input_format);
+  if (c->deinterlace < 0 || c->deinterlace > 2) return WHY("deinterlace %d unknown (0 none, 1 top field first, 2 bottom field first)", c->deinterlace);
+  if (c->deinterlace && !c->store_frames) return WHY("deinterlace %d needs a frame store (store_frames > 0): the filter reads the frames before and after each frame", c->deinterlace);
   return nullptr;
 #undef WHY
 }
@@ -397,6 +405,19 @@ int setup(av1mi_gop *g) {
     G_TRY(host_alloc(g, &g->h_records, (size_t)c.store_frames * sizeof(av1mi_scene_record)));
     G_HIP(hipEventCreateWithFlags(&g->scene_done, hipEventDisableTiming));
     for (hipEvent_t &e : g->put_done) G_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (c.deinterlace) {
+      // the fed planes: buffers fed_w x fed_h luma and the chroma of the source's layout; their true size is the source's (where the
+      // session scales) or the visible size
+      av1mi::DeintLaunch &L = g->deint;
+      const int tw = scaling ? c.source_width : g->vw, th = scaling ? c.source_height : g->vh;
+      const int sx = c.source_chroma == AV1MI_CHROMA_444 ? 0 : 1, sy = c.source_chroma == AV1MI_CHROMA_420 ? 1 : 0;
+      L.bd = g->src_bd; L.parity = c.deinterlace - 1; L.segments = S;
+      for (int p = 0; p < 3; p++) {
+        const bool have = g->frame_bytes[p] != 0;
+        L.plane_w[p] = !have ? 0 : p ? g->fed_w >> sx : g->fed_w; L.plane_h[p] = !have ? 0 : p ? g->fed_h >> sy : g->fed_h;
+        L.true_w[p] = p ? (tw + sx) >> sx : tw; L.true_h[p] = p ? (th + sy) >> sy : th;
+      }
+    }
   }
   G_TRY(dev_alloc(g, &g->d_zero_skip, g->nb));
   G_TRY(av1mi_memset(g->ctx, g->d_zero_skip, 0, g->nb));
@@ -474,14 +495,30 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
     Store &st = g->store[store];
     const int S = g->cfg.segments;
     const void **table = (const void **)s.h_table;
+    const int dei = g->cfg.deinterlace;
+    auto frame = [&](int p, int pos) { return (const void *)((const char *)st.d[p] + g->frame_bytes[p] * (size_t)pos); };
     for (int sg = 0; sg < S; sg++)
-      for (int p = 0; p < 3; p++)
-        table[sg * 3 + p] = index[sg] < 0 || !g->frame_bytes[p] ? nullptr : (const char *)st.d[p] + g->frame_bytes[p] * (size_t)index[sg];
-    G_HIP(hipMemcpyAsync(s.d_table, s.h_table, (size_t)S * 3 * sizeof(void *), hipMemcpyHostToDevice, main));
+      for (int p = 0; p < 3; p++) {
+        const bool flat = index[sg] < 0 || !g->frame_bytes[p];
+        if (!dei) table[sg * 3 + p] = flat ? nullptr : frame(p, index[sg]);
+        else {      // P, C, N follow the POSITION in the store's run, clamped at its ends
+          const void **e = table + (sg * 3 + p) * 3;
+          e[0] = flat ? nullptr : frame(p, index[sg] > 0 ? index[sg] - 1 : 0);
+          e[1] = flat ? nullptr : frame(p, index[sg]);
+          e[2] = flat ? nullptr : frame(p, index[sg] + 1 < st.run ? index[sg] + 1 : st.run - 1);
+        }
+      }
+    G_HIP(hipMemcpyAsync(s.d_table, s.h_table, (size_t)S * 3 * (dei ? 3 : 1) * sizeof(void *), hipMemcpyHostToDevice, main));
     G_HIP(hipStreamWaitEvent(main, st.filled, 0));
-    {
+    if (!dei) {
       av1mi::ProfScope ps(g->ctx, AV1MI_K_SCENE, main);
       G_HIP(av1mi::launch_frames_gather(g->frame_bytes, S, (const void *const *)s.d_table, s.d_in, main));
+    } else {
+      av1mi::ProfScope ps(g->ctx, AV1MI_K_SCENE, main);
+      av1mi::DeintLaunch L = g->deint;
+      L.table = (const void *const *)s.d_table;
+      for (int p = 0; p < 3; p++) L.dst[p] = s.d_in[p];
+      G_HIP(av1mi::launch_deint_gather(L, main));
     }
     G_HIP(hipEventRecord(st.read_done, main));
     st.has_reader = true;
@@ -837,6 +874,7 @@ int av1mi_gop_store_put(av1mi_gop *g, int store, int first, int count) {
   g->put_pending[k] = true;
   G_HIP(hipEventRecord(st.filled, g->up));
   st.has_fill = true;
+  st.run = first == 0 ? count : std::max(st.run, first + count);
   g->puts++;
   g->acquired = false;
   return AV1MI_OK;
@@ -866,6 +904,9 @@ int av1mi_gop_submit_stored(av1mi_gop *g, int store, const int32_t *index, int f
   if (frame_type != 0 && frame_type != 1) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: frame_type %d (0 key or 1 inter: the layout is the caller's)", frame_type);
   for (int s = 0; s < g->cfg.segments; s++)
     if (index[s] < -1 || index[s] >= g->cfg.store_frames) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: index[%d] = %d outside the store of %d frames", s, (int)index[s], g->cfg.store_frames);
+  for (int s = 0; g->cfg.deinterlace && s < g->cfg.segments; s++)
+    if (index[s] >= g->store[store].run)
+      return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: index[%d] = %d beyond the store's run of %d frames (deinterlacing reads the neighbours inside it)", s, (int)index[s], g->store[store].run);
   return submit_batch(g, frame_type, nullptr, store, index);
 }
 
@@ -931,6 +972,17 @@ int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out) {
     }
   }
   g->collected++;
+  return AV1MI_OK;
+}
+
+int av1mi_gop_download_fed(av1mi_gop *g, void *y, void *u, void *v) {
+  if (!g || !y) return AV1MI_E_INVAL;
+  if (!g->submitted) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "download_fed: nothing was submitted");
+  G_TRY(av1mi_sync(g->ctx));
+  G_HIP(hipStreamSynchronize(g->up));
+  void *dst[3] = { y, u, v };
+  for (int p = 0; p < 3; p++)
+    if (g->in_bytes[p] && dst[p]) G_TRY(av1mi_download(g->ctx, dst[p], g->slot[g->last].d_in[p], g->in_bytes[p]));
   return AV1MI_OK;
 }
 

@@ -9,6 +9,8 @@
 // ".ivf" = IVF, anything else (the reference's "<base>.av1-tmp.mkv") = Matroska with one V_AV1 video track (mux.cpp);
 // audio / subtitle copy (transcode.go:134-137) needs a demuxer and is not done.
 //
+// With -av1mi_deinterlace (or a deinterlacer in the chain) an interlaced source takes the same stored path, without the analysis unless
+// -av1mi_scenecut asks for it: the session's gather deinterlaces every frame on its way from the store (av1mi_gop_config.deinterlace).
 // With -av1mi_scenecut the GOPs of a group do not start every `gop` frames but where the scene analysis finds cuts: the group's frames go
 // into the session's frame store in file order (av1mi_gop_store_put), are analysed there (av1mi_gop_store_analyse), the planner
 // (sceneplan.hpp) lays the GOPs out, and every batch is gathered from the store (av1mi_gop_submit_stored).  The session has two stores:
@@ -200,8 +202,15 @@ int RunBackend(const BackendJob &job, std::string *err) {
     if (convert) { cfg.source_chroma = y.chroma; cfg.source_bit_depth = y.src_bd; }
     const bool packed = job.pack10 && y.bd == 10 && !convert;      // (planar 4:2:0 10-bit only)
     if (packed) cfg.input_format = AV1MI_INPUT_PACKED10;
-    // -av1mi_scenecut: the frame store holds one group
-    const bool stored = job.scenecut > 0;
+    // -av1mi_deinterlace: auto follows the header's I parameter, tff / bff force a parity
+    int dei = job.deinterlace == 2 ? 1 : job.deinterlace == 3 ? 2 : 0;
+    if (job.deinterlace == 1) {
+      if (y.interlace == 3) { *err = "Invalid argument: -av1mi_deinterlace auto: the source is mixed-mode interlaced (Im); field-rate output and inverse telecine are not built"; code = 1; goto done; }
+      dei = y.interlace;
+    }
+    cfg.deinterlace = dei;
+    // -av1mi_scenecut, or a job that deinterlaces: the frame store holds one group (the deinterlacer's run)
+    const bool analysed = job.scenecut > 0, stored = analysed || dei != 0;
     if (stored) cfg.store_frames = S * G;
     // one segment's planes in the pinned buffers (no chroma planes for a grey source)
     const size_t py_bytes = convert ? av1mi_source_plane_bytes(y.chroma, y.src_bd, 0, rw, rh) : av1mi_input_plane_bytes(cfg.input_format, y.bd, 0, rw, rh);
@@ -285,11 +294,13 @@ int RunBackend(const BackendJob &job, std::string *err) {
       if (have_frames == 0) break;
       total_frames += have_frames;
       for (int s = 0; s < S; s++) { start[(size_t)s] = s * G; len[(size_t)s] = (int32_t)std::max<long>(0, std::min<long>(G, have_frames - (long)s * G)); }
-      if (stored) {
+      if (analysed) {
         scene.resize((size_t)have_frames); cut.assign((size_t)have_frames, 0);
         CHK(av1mi_gop_store_analyse(gop, cur_store, (int)have_frames, scene.data()));
         for (long f = 0; f < have_frames; f++) cut[(size_t)f] = (uint8_t)av1mi_scene_is_cut(&scene[(size_t)f], job.scenecut);
         if (av1mi_plan_gops((int)have_frames, G, S, job.min_gop, cut.data(), start.data(), len.data()) < 0) { *err = "Invalid argument: -av1mi_min_gop does not fit the GOP length"; code = 1; goto done; }
+      }
+      if (stored) {      // (a job that only deinterlaces keeps the nominal layout above)
         // the group after this one: prepared now (this group's frames are all in the store), put chunk by chunk beside the batches below
         next_frames = y.prepare((g0 + S) * G, (long)S * G, err);
         if (next_frames < 0) { code = 1; goto done; }
@@ -399,7 +410,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
             int n = snprintf(line, sizeof(line), "n:%ld type:%c bytes:%zu", summary.frames, t == 0 ? 'K' : 'P', units[(size_t)s][t].size());
             n += av1mi::quality::format_figures(av1mi::quality::frame_figures(records[(size_t)s][t].q, y.bd), line + n, sizeof(line) - (size_t)n);
             if (rc) n += snprintf(line + n, sizeof(line) - (size_t)n, " q:%d", qs[(size_t)s][t]);
-            if (stored && cut[(size_t)start[(size_t)s] + t]) n += snprintf(line + n, sizeof(line) - (size_t)n, " cut:1");
+            if (analysed && cut[(size_t)start[(size_t)s] + t]) n += snprintf(line + n, sizeof(line) - (size_t)n, " cut:1");
             stats.append(line, (size_t)n); stats += '\n';
             summary.add(records[(size_t)s][t].q, y.bd);
             total_bytes += (long long)units[(size_t)s][t].size();

@@ -102,6 +102,24 @@ int av1mi_host_y4m_sar(const char *path, int *sar) {
   sar[0] = y.sar_n; sar[1] = y.sar_d;
   return 0;
 }
+// the header's I parameter as Y4mSource keeps it (0 progressive, 1 It, 2 Ib, 3 Im); -1 when the file does not open
+int av1mi_host_y4m_interlace(const char *path) {
+  Y4mSource y;
+  std::string e;
+  if (!y.open(path, &e)) return -1;
+  return y.interlace;
+}
+// ParseBackendJob's view of -av1mi_deinterlace and the chain's deinterlacers for an argv joined with '\n': BackendJob::deinterlace (0 off,
+// 1 auto, 2 tff, 3 bff), or -1 with the text in err
+int av1mi_host_parse_deinterlace_option(const char *joined, char *err, int cap) {
+  std::vector<std::string> a; std::string s = joined; size_t p = 0, q;
+  while ((q = s.find('\n', p)) != std::string::npos) { a.push_back(s.substr(p, q - p)); p = q + 1; }
+  a.push_back(s.substr(p));
+  BackendJob job; std::string e;
+  const bool ok = ParseBackendJob(a, &job, &e);
+  strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
+  return ok ? job.deinterlace : -1;
+}
 // ScaleTarget (transcode.hpp): the size a filter chain yields on a source; 0, or -1 for a chain with an unsupported filter
 int av1mi_host_scale_target(int iw, int ih, int sar_n, int sar_d, const char *chain, int *w, int *h) {
   std::string e;

@@ -63,7 +63,7 @@ static bool plain_int(const std::string &t, int *v) {
   return true;
 }
 
-bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err, bool *to_420) {
+bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err, bool *to_420, bool *deint) {
   if (sar_n <= 0 || sar_d <= 0) sar_n = sar_d = 1;
   long cw = iw, ch = ih;
   bool sq = sar_n == sar_d;
@@ -89,6 +89,17 @@ bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain,
       const std::string name = f.substr(7);
       if (name != "nv12" && name != "p010" && name != "p010le" && name != "yuv420p" && name != "yuv420p10le") { if (err) *err = "Invalid argument: unsupported filter " + f; return false; }
       if (to_420) *to_420 = true;
+    } else if (f == "yadif" || f == "bwdif" || f == "deinterlace_vaapi" || f.compare(0, 6, "yadif=") == 0 || f.compare(0, 6, "bwdif=") == 0 ||
+               f.compare(0, 18, "deinterlace_vaapi=") == 0) {
+      // same-rate deinterlacing is what is built (include/av1mi.h "deinterlacing"): one frame per frame.  Field-rate modes, a forced
+      // parity or a deint= selection cannot be honoured from here and are not skipped
+      const size_t eq = f.find('=');
+      const std::string arg = eq == std::string::npos ? "" : f.substr(eq + 1);
+      if (!arg.empty() && arg != "mode=0" && arg != "mode=send_frame") {
+        if (err) *err = "Invalid argument: unsupported filter argument " + f + " (only mode=0 / mode=send_frame: one frame per frame)";
+        return false;
+      }
+      if (deint) *deint = true;
     } else if (f.compare(0, 6, "scale=") == 0 && f.find(':') != std::string::npos && plain_int(f.substr(6, f.find(':') - 6), &a) &&
                plain_int(f.substr(f.find(':') + 1), &b)) {
       cw = a; ch = b; sar_n = sar_d = 1; sq = true;
@@ -109,7 +120,7 @@ bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain,
 bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std::string *err) {
   if (args.size() < 3) { if (err) *err = "Invalid argument: too few arguments"; return false; }
   job->output = args.back();
-  bool have_in = false;
+  bool have_in = false, deint_given = false;
   for (size_t i = 0; i + 1 < args.size(); i++) {
     if (args[i] == "-i") { job->input = args[i + 1]; have_in = true; }
     else if (args[i] == "-global_quality:v:0") job->quality = std::atoi(args[i + 1].c_str());
@@ -131,6 +142,12 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
     }
     else if (args[i] == "-av1mi_scenecut") {
       if (!plain_int(args[i + 1], &job->scenecut) || job->scenecut > 99) { if (err) *err = "Invalid argument: -av1mi_scenecut takes a sensitivity 1 .. 99 (0 = off), not " + args[i + 1]; return false; }
+    }
+    else if (args[i] == "-av1mi_deinterlace") {
+      const std::string &v = args[i + 1];
+      if (v == "off") job->deinterlace = 0; else if (v == "auto") job->deinterlace = 1; else if (v == "tff") job->deinterlace = 2; else if (v == "bff") job->deinterlace = 3;
+      else { if (err) *err = "Invalid argument: -av1mi_deinterlace takes off, auto, tff or bff, not " + v; return false; }
+      deint_given = true;
     }
     else if (args[i] == "-av1mi_min_gop") {
       if (!plain_int(args[i + 1], &job->min_gop) || job->min_gop < 1 || job->min_gop > 256) { if (err) *err = "Invalid argument: -av1mi_min_gop takes a length in frames (1 .. gop - gop / 2), not " + args[i + 1]; return false; }
@@ -178,14 +195,16 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
   }
   if (job->have_vf) {      // a filter that cannot be applied must not be skipped silently: the chain is checked before anything runs
     int w, h;
-    bool to_420 = false;
-    if (!ScaleTarget(16, 16, 1, 1, job->vf, &w, &h, nullptr, err, &to_420)) return false;
+    bool to_420 = false, deint = false;
+    if (!ScaleTarget(16, 16, 1, 1, job->vf, &w, &h, nullptr, err, &to_420, &deint)) return false;
     if (to_420) job->to_420 = true;
+    if (deint && !deint_given) job->deinterlace = 1;      // a deinterlacer in the chain means auto; an explicit option keeps its say
   }
   if (job->bitrate && job->target_bpp_u) { if (err) *err = "Invalid argument: -b:v:0 and -av1mi_target_bpp are two forms of one target: give one"; return false; }
   if ((job->qmin || job->qmax) && !job->bitrate && !job->target_bpp_u) { if (err) *err = "Invalid argument: -qmin / -qmax need a target (-b:v:0 or -av1mi_target_bpp)"; return false; }
   if (job->qmin && job->qmax && job->qmin > job->qmax) { if (err) *err = "Invalid argument: -qmin " + std::to_string(job->qmin) + " above -qmax " + std::to_string(job->qmax); return false; }
   if (job->scenecut && job->pack10) { if (err) *err = "Invalid argument: -av1mi_scenecut keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
+  if (job->deinterlace && job->pack10) { if (err) *err = "Invalid argument: -av1mi_deinterlace keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
   if (job->min_gop && !job->scenecut) { if (err) *err = "Invalid argument: -av1mi_min_gop needs -av1mi_scenecut"; return false; }
   if (job->min_gop && job->gop >= 1 && job->min_gop > job->gop - job->gop / 2) { if (err) *err = "Invalid argument: -av1mi_min_gop " + std::to_string(job->min_gop) + " above gop - gop / 2 = " + std::to_string(job->gop - job->gop / 2); return false; }
   if (!have_in) { if (err) *err = "Invalid argument: no input (-i) given"; return false; }

@@ -78,6 +78,11 @@ struct BackendJob {
                            // host/sceneplan.hpp AV1MI_SCENECUT_DEFAULT is the measured middle).  Every group of segments x gop frames is put into the
                            // session's frame store in file order, analysed on the GPU, and its GOP boundaries are moved onto the cuts found
                            // (av1mi_plan_gops): key frames land on the cuts, GOPs are min_gop .. 3/2 gop frames long.  Not with -av1mi_pack10 1
+  int deinterlace = 0;     // -av1mi_deinterlace off | auto | tff | bff (0 .. 3).  off (default): every source is coded as its frames are.  auto: a source whose
+                           // Y4M header says It / Ib is deinterlaced on the GPU with that parity (include/av1mi.h "deinterlacing": same-rate, one
+                           // frame per frame), a progressive one is coded as ever, Im is refused (field-rate output and inverse telecine are not
+                           // built).  tff / bff force a parity, for sources whose header lies.  A chain that names yadif, bwdif or deinterlace_vaapi
+                           // (bare, mode=0 or mode=send_frame) means auto.  The job then runs through the frame store.  Not with -av1mi_pack10 1
   int min_gop = 0;         // -av1mi_min_gop M: the shortest GOP the planner makes, 1 .. gop - gop / 2; 0 = max(1, gop / 4).  Only with -av1mi_scenecut
   std::vector<std::string> tracks;   // -av1mi_tracks <file.mka> (repeatable): Matroska side files whose audio / subtitle tracks are copied
                                      // next to the video (the reference's `-c:a copy -c:s copy`, transcode.go:134-137, after an external demux)
@@ -89,10 +94,13 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
 // (iw * sar, ih), truncated to integers — the first branch divides iw, as written upstream), its even-size scale (:98 / :107: each
 // dimension rounded up to even), `hwdownload`, `hwupload`, `setsar=1` (no effect on planar 4:2:0 frames), `format=` naming a 4:2:0
 // format (nv12, p010, p010le, yuv420p, yuv420p10le: no effect on the size; *to_420, when given, is set — BackendJob::to_420; any other
-// format is "Invalid argument: unsupported filter format=<name>"), and
+// format is "Invalid argument: unsupported filter format=<name>"), the deinterlacers `yadif`, `bwdif` and `deinterlace_vaapi`, bare or with
+// `mode=0` / `mode=send_frame` (one frame per frame: *deint, when given, is set — BackendJob::deinterlace auto; any other argument is
+// "Invalid argument: unsupported filter argument <filter>=<argument> ..."), and
 // `scale=W:H` / `scale_vaapi=w=W:h=H` with plain integers.  Returns false and "Invalid argument: unsupported filter <name>" for
 // anything else.  *square: the chain leaves square pixels (it resampled by the SAR, or to an explicit size).
-bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err, bool *to_420 = nullptr);
+bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err, bool *to_420 = nullptr,
+                 bool *deint = nullptr);
 
 // transcode.go:194-315 contract: (0, "") on success AND the output file exists; (code, text <= 800 chars) on failure;
 // (-1, text) when the backend could not run at all (no HIP device, library error before any frame).  Exit code 3 is the quality gate

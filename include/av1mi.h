@@ -507,6 +507,37 @@ int av1mi_scene_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, in
  * AV1MI_K_SCENE in the profile. */
 int av1mi_frames_gather(av1mi_ctx *ctx, const size_t plane_bytes[3], int segments, const void *const *d_src_table, void *const d_dst[3]);
 
+/* ---- deinterlacing: an interlaced source becomes progressive frames inside the gather (av1-go_amd/csrc/deint_kernels.hip).  AV1 has no
+ * interlaced coding and no field signalling: combing that is coded stays in the picture.  The filter is SAME-RATE: one output frame per
+ * input frame, at the time of the frame's FIRST field.  Integer arithmetic, bit exact by definition.
+ *   geometry  every plane of the fed layout is filtered on its own: true size w x h, buffer size = the true size rounded up to 8 in luma
+ *             terms.  Parity k = 0 for top field first (the even lines are the first field and are kept), 1 for bottom field first.  A
+ *             run is the frames 0 .. n - 1 of a store; for frame f: C = frame f, P = frame max(f - 1, 0), N = frame min(f + 1, n - 1).
+ *             The ends of a run have no neighbour and take the frame itself, as frame 0 of a run has no predecessor in the scene analysis.
+ *   lines     lines with y mod 2 == k are copied.  The others are missing; for a missing line y: up = y - 1 if y >= 1 else y + 1,
+ *             dn = y + 1 if y + 1 <= h - 1 else y - 1: both are kept lines.  All x arguments below clamp to [0, w - 1].  A plane with
+ *             h == 1 is copied.
+ *   spatial   a(j) = C[up][x + j], b(j) = C[dn][x + j].  For d in the order 0, -1, +1, -2, +2: score(d) = sum over j in -1 .. 1 of
+ *             |a(j + d) - b(j - d)|; the first d whose score is strictly smaller than every earlier one's wins; s = (a(d) + b(-d) + 1) >> 1.
+ *   temporal  t0 = P[y][x] (the other field of the previous frame, one field before the kept one), t1 = C[y][x] (one field after it),
+ *             t = (t0 + t1 + 1) >> 1.
+ *   bound     m = the maximum of (|t0 - t1| + 1) >> 1, (|P[up][x] - a(0)| + |P[dn][x] - b(0)| + 1) >> 1 and the same expression with N
+ *             in place of P.
+ *   output    min(max(s, t - m), t + m).  A still picture gives m = 0 and the weave, exactly; motion opens the bound to the edge-directed
+ *             value.  The buffer's sample at (x, y) beyond the true size is the filter's value at (min(x, w - 1), min(y, h - 1)): the
+ *             padding of the output replicates its own edge, which is what the analysis and the block pipeline expect of a fed frame.
+ *             Nothing beyond the true size is read: the input's padding may be undefined.
+ * Field-rate output, inverse telecine and neighbours across the boundaries of a run are not built. */
+/* The gather with the filter in it, ONE launch for all planes and segments.  d_table: segments * 9 device pointers IN DEVICE MEMORY,
+ * [(s * 3 + p) * 3 + i] = plane p of segment s's frame P (i = 0), C (1) and N (2), the run's clamping applied by whoever fills it; a null
+ * C makes the slot flat (zeros).  Planes whose rows are whole 16-byte units must be 16-byte aligned, any other 4-byte.  plane_w x
+ * plane_h: the buffers' size in samples (0 = no such plane; rows of whole dwords), true_w x true_h the size the filter works at, less than
+ * 8 below it.  bit_depth 8 (uint8 samples), 10 or 12 (uint16); parity 0 or 1.  The filtered plane goes to d_dst[p] + s * the plane's
+ * bytes (16-byte aligned).  The sources are only read.  Asynchronous on the context's stream; AV1MI_K_SCENE in the profile, like the
+ * gather it stands in for. */
+int av1mi_deinterlace_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int parity,
+                             int segments, const void *const *d_table, void *const d_dst[3]);
+
 /* ---- GOP session: the encoder object a cgo replacement of RunTranscode drives (reference call site
  * internal/daemon/daemon.go:101 -> internal/ffmpeg/transcode.go:194; SURVEY.md §8b "av1mi_open(config) / av1mi_encode /
  * av1mi_flush").  It owns the closed-GOP orchestration and the encoder's filter-parameter POLICY, so that no caller
@@ -590,6 +621,15 @@ typedef struct av1mi_gop_config {
    * a session is fed through the store or av1mi_gop_submit_device; av1mi_gop_submit is refused.  At 4K 10-bit, 12 segments x 30
    * frames, the two stores are 2 x 9 GB. */
   int store_frames;
+  /* Deinterlacing (0 = none: nothing new is allocated, launched or accepted; 1 = top field first, 2 = bottom field first; "deinterlacing"
+   * above).  Needs store_frames > 0 (and with it a planar input_format): the filter looks at the frames before and after each frame, which
+   * only the store holds.  av1mi_gop_submit_stored then launches k_deint_gather in place of k_frames_gather: the slot's fed buffers
+   * receive the filtered frames, with a run = the frames 0 .. n - 1 the store was last filled with (the highest position put since the
+   * store's position 0 was put), and the store itself is never written.  Everything behind the fed buffers is untouched: chroma
+   * conversion, scaling, visible_*, quality records (measured against the deinterlaced frame), coarse_range, rate control.
+   * av1mi_gop_store_analyse keeps reading the frames AS FED: averaging 4x4 samples blends the two fields, so cuts are found as before.
+   * av1mi_gop_submit_device does not deinterlace. */
+  int deinterlace;
 } av1mi_gop_config;
 
 /* Frame-header parameters chosen by the session's policy for one frame (non-normative encoder choices; the bitstream carries
@@ -694,6 +734,10 @@ long av1mi_gop_entropy_fallbacks(av1mi_gop *g);
 /* the reference frame(s) produced by the LAST submitted batch (after all in-loop filters): host buffers of the stacked-plane
  * sizes; synchronises the session.  For tests and PSNR. */
 int av1mi_gop_download_reference(av1mi_gop *g, void *y, void *u, void *v);
+/* the fed buffers of the LAST submitted batch as the input stages read them (the session's own device buffers: what the upload, the
+ * gather or the deinterlacing gather wrote; not a batch of av1mi_gop_submit_device): host buffers of the sizes av1mi_gop_acquire_input
+ * hands out, a null u / v is skipped; synchronises the session.  For tests. */
+int av1mi_gop_download_fed(av1mi_gop *g, void *y, void *u, void *v);
 
 /* ---- host-pointer single-block forms (SURVEY.md §8b "per-stage test entry points"): copy in, run the
  * same kernels, copy out, synchronous. */

@@ -135,6 +135,9 @@ long long av1mi_obu_write_blocks_temporal_unit(const av1mi_obu_blocks *f, int wi
  * "-i <input.y4m>", "-global_quality:v:0 <q>" and the output path (last argument), plus its own "-g", "-av1mi_device",
  * "-av1mi_segments", "-av1mi_gpu_entropy", "-av1mi_key_block_size", "-av1mi_tracks", "-threads", "-av1mi_scale WxH"; "-vf:v:0 <chain>"
  * is evaluated on the source (its scale filters are applied on the GPU, a filter that cannot be applied is an error: INTEGRATION.md §1);
+ * "-av1mi_deinterlace off | auto | tff | bff" (off = default; auto deinterlaces a source whose Y4M header says It / Ib on the GPU, at the
+ * same frame rate, and refuses Im; a chain that names yadif, bwdif or deinterlace_vaapi — bare, mode=0 or mode=send_frame — means auto;
+ * include/av1mi.h "deinterlacing", av1mi_gop_config.deinterlace);
  * everything else is accepted and ignored.  Returns 0 and leaves the output file in place on
  * success; -1 when the backend could not run at all (no HIP device: transcode.go:311); another non-zero code on failure.
  * err receives the reference-shaped text ("av1mi failed with exit code N: ...", at most 800 characters + "..."). */
