@@ -166,6 +166,24 @@ def source_plane_shapes(chroma, width, rows):
     return [(rows, width), c, c]
 
 
+class SourcePlane(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("frame_bytes", C.c_size_t)]
+
+
+class SourceLayout(C.Structure):      # av1mi_source_layout
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("true_width", C.c_int), ("true_height", C.c_int), ("bit_depth", C.c_int), ("plane", SourcePlane * 3)]
+
+
+def gop_source_layout(cfg):
+    """what a session opened with `cfg` (GopConfig) is fed (av1mi_gop_source_layout); raises where av1mi_gop_open would refuse cfg; no GPU needed"""
+    lib, out = load(), SourceLayout()
+    lib.av1mi_gop_source_layout.argtypes = [C.POINTER(GopConfig), C.POINTER(SourceLayout)]
+    rc = lib.av1mi_gop_source_layout(C.byref(cfg), C.byref(out))
+    if rc:
+        raise Av1miError(rc, "av1mi_gop_source_layout")
+    return out
+
+
 def input_pack(fmt, bit_depth, y, u, v, out=None):
     """planar planes (y [rows, width], u / v half size; uint8 or uint16) -> the format's planes as uint8 arrays (av1mi_input_pack, host
     code); out: optional (buffer, byte offset) per plane to pack into instead of fresh arrays"""
@@ -227,30 +245,28 @@ class GopSession:
         sw, sh = source if source is not None else (0, 0)
         self.cfg = GopConfig(width, height, bit_depth, base_q_idx, gop_length, segments, search_range, gpu_entropy, vw, vh, coder_streams, key_block_size, input_format,
                              sw, sh, int(quality_stats), int(coarse_range), int(source_chroma), int(source_bit_depth), int(store_frames), int(deinterlace))
-        self.source_chroma, self.src_bd = int(source_chroma), int(source_bit_depth) or bit_depth
-        self.in_w, self.in_h = ((sw + 7) & ~7, (sh + 7) & ~7) if source is not None else (width, height)      # geometry of the input buffers
-        self.input_format = input_format
         self.g = C.c_void_p()
         ctx.lib.av1mi_gop_open.argtypes = [C.c_void_p, C.POINTER(GopConfig), C.POINTER(C.c_void_p)]
         ctx._chk(ctx.lib.av1mi_gop_open(ctx.h, C.byref(self.cfg), C.byref(self.g)))
+        self.layout = gop_source_layout(self.cfg)      # the geometry of the input buffers
         for name in ("av1mi_gop_close", "av1mi_gop_acquire_input", "av1mi_gop_submit", "av1mi_gop_collect", "av1mi_gop_pending",
                      "av1mi_gop_download_reference"):
             getattr(ctx.lib, name).argtypes = None
         ctx.lib.av1mi_gop_close.restype = None
         self.dt = np.uint8 if bit_depth == 8 else np.uint16
 
+    def fed_planes(self):
+        """(shape, dtype) of the planes of a batch as the session is fed them, from the layout: the planes it has, segments stacked; a
+        wire format's planes (input_format not planar) as flat bytes"""
+        S, wire = self.segments, self.cfg.input_format != INPUT_PLANAR
+        dt = np.uint8 if wire or self.layout.bit_depth == 8 else np.uint16
+        return [((S * P.frame_bytes,) if wire else (S * P.height, P.width), dt) for P in self.layout.plane if P.frame_bytes]
+
     def input_planes(self):
-        """numpy views of the pinned host planes of the next batch: shapes [segments * height, width] and the half-size chroma"""
-        y, u, v = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        self.ctx._chk(self.ctx.lib.av1mi_gop_acquire_input(self.g, C.byref(y), C.byref(u), C.byref(v)))
-        S, w, h = self.segments, self.in_w, self.in_h
-        if self.source_chroma != CHROMA_420 or self.src_bd != self.bd:      # the source's layout; a grey source has a luma plane only
-            dt = np.uint8 if self.src_bd == 8 else np.uint16
-            return tuple(_view(ptr.value, shp, dt) for ptr, shp in zip((y, u, v), source_plane_shapes(self.source_chroma, w, S * h)) if shp)
-        if self.input_format != INPUT_PLANAR:      # the session's format: flat byte views of av1mi_input_plane_bytes each (no third plane when semi-planar)
-            n = [input_plane_bytes(self.input_format, self.bd, p, w, S * h) for p in range(3)]
-            return tuple(_view(ptr.value, (k,), np.uint8) for ptr, k in zip((y, u, v), n) if k)
-        return (_view(y.value, (S * h, w), self.dt), _view(u.value, (S * h // 2, w // 2), self.dt), _view(v.value, (S * h // 2, w // 2), self.dt))
+        """numpy views of the pinned host planes of the next batch (fed_planes(): e.g. [segments * height, width] and the half-size chroma)"""
+        ptr = (C.c_void_p(), C.c_void_p(), C.c_void_p())
+        self.ctx._chk(self.ctx.lib.av1mi_gop_acquire_input(self.g, *[C.byref(p) for p in ptr]))
+        return tuple(_view(p.value, shape, dt) for p, (shape, dt) in zip(ptr, self.fed_planes()))
 
     def submit(self, frame_type=-1):
         self.ctx._chk(self.ctx.lib.av1mi_gop_submit(self.g, int(frame_type)))
@@ -347,12 +363,10 @@ class GopSession:
 
     def download_fed(self):
         """the fed buffers of the last submitted batch (av1mi_gop_download_fed): arrays shaped like input_planes()"""
-        S, w, h = self.segments, self.in_w, self.in_h
-        dt = np.uint8 if self.src_bd == 8 else np.uint16
-        out = [np.empty(shp, dt) if shp else None for shp in source_plane_shapes(self.source_chroma, w, S * h)]
+        out = [np.empty(shape, dt) for shape, dt in self.fed_planes()]
         self.ctx.lib.av1mi_gop_download_fed.argtypes = [C.c_void_p] * 4
-        self.ctx._chk(self.ctx.lib.av1mi_gop_download_fed(self.g, *[a.ctypes.data if a is not None else None for a in out]))
-        return tuple(a for a in out if a is not None)
+        self.ctx._chk(self.ctx.lib.av1mi_gop_download_fed(self.g, *([a.ctypes.data for a in out] + [None] * (3 - len(out)))))
+        return tuple(out)
 
     def close(self):
         if self.g:

@@ -19,16 +19,20 @@
 // pipeline and the coder works on batch t, whose predecessor the host is still reading.  Four streams, one hardware queue each
 // (a fifth would share a queue with one of these and serialise behind it).
 //
-// The source path: fed buffers -> 0-2 input stages -> planar planes.  A batch is FED in the session's format
-// (av1mi_gop_config.input_format) at the fed size: the coded size, or with scaling (source_width / source_height) the source size
-// rounded up to 8.  It crosses PCIe from the slot's pinned h_in into d_in, or arrives from the caller (av1mi_gop_submit_device).
-// The input stages, fixed at open, run on the main stream: convert (format not PLANAR: one launch of k_input_convert,
-// input_kernels.hip), then scale (one launch of the resampler, scale_kernels.hip).  The last one fills the slot's planar d_src
-// planes at the coded size, which the block pipeline and the restoration decision read; with both, the converted planes at the
-// source size (d_pre) lie between them.  A planar session without scaling is the session with ZERO stages: what it is fed IS d_src.
-// A source that is not 4:2:0, or deeper than the coded depth (source_chroma / source_bit_depth; planar only), takes the place of the
-// convert stage with the stage chroma: one launch of k_chroma_convert from the fed layout (av1mi_source_plane_bytes) to planar 4:2:0
-// at the fed size.  Where the depths are equal its luma plane passes THROUGH: the fed luma plane is the planar one, as with zero stages.
+// The source path: ONE layout, ONE chain.  av1mi_gop_source_layout (include/av1mi.h) says what a batch is FED: the buffers' luma size
+// (the coded size, or with scaling the source size rounded up to 8), the true size inside them, the depth, and per plane its size and
+// the bytes of one frame.  The session keeps that layout; every number of the fed side — buffers, store, gathers, analysis, the stages'
+// launches, av1mi_gop_download_fed, the planes av1mi_gop_submit_device expects — is read from it.  A fed batch crosses PCIe from the
+// slot's pinned h_in into d_in, is gathered there from a store, or is the caller's.  The CHAIN, built once by setup(), holds the 0-2
+// input stages that turn it into the planar 4:2:0 planes at the coded size (d_src) which the block pipeline and the restoration
+// decision read, one launch each on the main stream:
+//   convert  input_format not PLANAR: k_input_convert (input_kernels.hip), wire format -> planar, at the fed size;  or
+//   chroma   a source that is not 4:2:0 at bit_depth (planar only): k_chroma_convert, fed layout -> planar 4:2:0 at the fed size.
+//            Where the depths are equal it passes the luma plane THROUGH: the plane stays in the buffer it is in;  then
+//   scale    source_width given: the resampler (scale_kernels.hip), fed size -> coded size.
+// slot_buffers() walks the chain once per slot and plane: the last stage that writes a plane writes d_src, a stage before it a plane
+// between (d_pre), and a plane that no stage writes IS d_src from the start (all planes with ZERO stages, the luma plane behind chroma
+// alone): the upload lands where the kernels read.  feed_source() walks it once per batch.
 //
 // The frame store (av1mi_gop_config.store_frames; nothing of it exists at 0).  Two stores of store_frames fed frames, a plane per
 // buffer, frames in file order.  The upload stream carries everything that fills and reads a store for the analysis: the puts (pinned
@@ -84,7 +88,7 @@ void frame_params(int q, int bd, int frame_type, av1mi_frame_params *p) {
   memcpy(p->lr_unit_y, wy, 8); memcpy(p->lr_unit_uv, wc, 8);
 }
 
-enum { kSlots = 3, kFallbacksToHostMode = 3 };      // batches in flight: one uploading / in the block pipeline, one in the coder, one being read by the host
+enum { kSlots = 3, kFallbacksToHostMode = 3, kMaxStages = 2 };      // batches in flight: one uploading / in the block pipeline, one in the coder, one being read by the host
 
 // plane p of the session's 4:2:0 frames: subsampling shift, coded and true (visible) size of one frame, samples and bytes of a batch
 struct Plane { int ss = 0, w = 0, h = 0, vw = 0, vh = 0; size_t n = 0, bytes = 0; };
@@ -92,7 +96,8 @@ struct Plane { int ss = 0, w = 0, h = 0, vw = 0, vh = 0; size_t n = 0, bytes = 0
 struct Slot {
   // the source as fed (the session's format, at the fed size): pinned + device, [2] unused by the semi-planar formats
   void *h_in[3] = { nullptr, nullptr, nullptr }, *d_in[3] = { nullptr, nullptr, nullptr };
-  void *d_pre[3] = { nullptr, nullptr, nullptr };       // sessions that convert AND scale: the converted planes at the source size
+  void *d_pre[3] = { nullptr, nullptr, nullptr };       // two stages: the planar planes at the fed size that the first one writes
+  void *stage_out[kMaxStages][3] = {};                  // where stage k writes plane p, resolved at open; null = the plane passes through
   void *d_src[3] = { nullptr, nullptr, nullptr };       // planar, coded size: what the block pipeline and the restoration decision read
   // symbols: device + pinned host mirror
   void *d_lev[3] = { nullptr, nullptr, nullptr }, *h_lev[3] = { nullptr, nullptr, nullptr };
@@ -118,7 +123,7 @@ struct Slot {
   void *h_table = nullptr, *d_table = nullptr;
 };
 
-// one frame store: a buffer per plane, store_frames frames of frame_bytes[p] each
+// one frame store: a buffer per plane, store_frames frames of layout.plane[p].frame_bytes each
 struct Store {
   void *d[3] = { nullptr, nullptr, nullptr };
   hipEvent_t filled = nullptr, read_done = nullptr;      // behind the last put (upload stream) / behind the last gather (main stream)
@@ -133,13 +138,10 @@ struct av1mi_gop {
   av1mi_gop_config cfg{};
   Plane plane[3];                              // the coded planes
   size_t nb = 0, bps = 1;                      // blocks of a BATCH (segments stacked), bytes per sample
-  int fmt = AV1MI_INPUT_PLANAR;                // cfg.input_format
-  int stages = 0;                              // input stages: convert (fmt != PLANAR) or chroma (source_chroma / source_bit_depth) + scale (source size given)
-  bool chroma_stage = false, luma_through = false;   // the stage chroma exists; ... and leaves the luma plane alone (equal depths)
-  int src_bd = 8;                              // the depth of the source as fed (== cfg.bit_depth without the stage)
+  av1mi_source_layout layout{};                // what the session is fed (av1mi_gop_source_layout(cfg)): the fed side's only geometry
+  int stages = 0, chain[kMaxStages] = {};      // the input stages in launch order (Stage)
+  uintptr_t fed_align = 8;                     // of the planes av1mi_gop_submit_device is given: 16 where convert or chroma reads them (16-byte loads)
   av1mi::ScalePlan *scale = nullptr;           // scaling sessions: the resampler's tables
-  size_t fed_ny = 0;                           // luma samples of a batch at the fed size
-  size_t in_bytes[3] = {}, pre_bytes[3] = {};  // bytes of a batch's planes as the session is fed them / as planar planes at the fed size
   hipStream_t up = nullptr, down = nullptr;     // with the context's main and side streams: four, one hardware queue each
   Slot slot[kSlots];
   void *d_rec[3] = {}, *d_dbl[3] = {}, *d_cdef[3] = {}, *d_ref[3] = {};
@@ -163,16 +165,12 @@ struct av1mi_gop {
   bool acquired = false;
   int coder_streams = 0;                       // 0 = tokenizer + chains on the side stream, range coder on the back stream (default)
   int intra_open_loop = 0;                     // key frames: open-loop mode decision (k_intra_modes) instead of the closed-loop search
-  // the frame store (cfg.store_frames != 0)
-  int fed_w = 0, fed_h = 0;                    // luma size of one fed frame
-  size_t frame_bytes[3] = {};                  // one fed frame's planes: in_bytes[p] / segments
-  Store store[2];
+  Store store[2];                              // the frame store (cfg.store_frames != 0)
   void *d_scene = nullptr, *h_records = nullptr;      // the analysis' scratch area (one store's) and its records, pinned
   hipEvent_t scene_done = nullptr;
   long puts = 0;                               // av1mi_gop_store_put calls: the pinned buffers of slot puts % kSlots are handed out next
   hipEvent_t put_done[kSlots] = {};            // the copy that last read those pinned buffers
   bool put_pending[kSlots] = {};
-  av1mi::DeintLaunch deint{};                  // cfg.deinterlace: the geometry of the fed planes (buffers and true sizes); table and dst per batch
   std::vector<void *> dev_allocs, host_allocs;
 };
 
@@ -200,20 +198,28 @@ int host_alloc(av1mi_gop *g, void **p, size_t bytes) {
   return AV1MI_OK;
 }
 
+enum Stage { kConvert, kChroma, kScale };      // the input stages (the chain of "The source path")
+// Does stage k write plane p?  All do but chroma at equal depths, which passes the luma plane through
+bool stage_writes(const av1mi_gop *g, int k, int p) { return !(g->chain[k] == kChroma && p == 0 && g->layout.bit_depth == g->cfg.bit_depth); }
+size_t fed_bytes(const av1mi_gop *g, int p) { return g->layout.plane[p].frame_bytes * (size_t)g->cfg.segments; }      // plane p of a batch as fed
+
 int slot_buffers(av1mi_gop *g, Slot &s) {
   const av1mi_gop_config &c = g->cfg;
   const int S = c.segments;
   for (int p = 0; p < 3; p++) {
     const Plane &P = g->plane[p];
-    // The source: pinned + device as fed, device-only planes behind each input stage.  With ZERO stages the fed buffer IS the planar
-    // plane (d_in == d_src, one allocation): the upload lands where the kernels read.
-    if (g->in_bytes[p]) G_TRY(host_alloc(g, &s.h_in[p], g->in_bytes[p]));
+    // the source: pinned + device as fed, then the chain's planes (a plane that no stage writes is fed straight into d_src)
+    if (fed_bytes(g, p)) G_TRY(host_alloc(g, &s.h_in[p], fed_bytes(g, p)));
     G_TRY(dev_alloc(g, &s.d_src[p], P.bytes));
-    // A luma plane that passes through the stage chroma needs no plane behind that stage: without scaling it is d_src as well.
-    const bool through = g->luma_through && p == 0;
-    if (!g->stages || (through && g->stages == 1)) s.d_in[p] = s.d_src[p];
-    else if (g->in_bytes[p]) G_TRY(dev_alloc(g, &s.d_in[p], g->in_bytes[p]));
-    if (g->stages == 2 && !through) G_TRY(dev_alloc(g, &s.d_pre[p], g->pre_bytes[p]));
+    int last = -1;
+    for (int k = 0; k < g->stages; k++) if (stage_writes(g, k, p)) last = k;
+    if (last < 0) s.d_in[p] = s.d_src[p];
+    else if (fed_bytes(g, p)) G_TRY(dev_alloc(g, &s.d_in[p], fed_bytes(g, p)));
+    for (int k = 0; k <= last; k++) {
+      if (!stage_writes(g, k, p)) continue;
+      if (k < last) G_TRY(dev_alloc(g, &s.d_pre[p], av1mi_input_plane_bytes(AV1MI_INPUT_PLANAR, c.bit_depth, p, g->layout.width, g->layout.height * S)));
+      s.stage_out[k][p] = k < last ? s.d_pre[p] : s.d_src[p];
+    }
     // the pinned mirror of the levels (as large as the source) is needed when the symbols go to the host; with the GPU coder
     // only a batch the coder gives back needs it, and it is allocated then (pinning memory is a good part of the start-up time)
     if (c.gpu_entropy != 1) G_TRY(host_alloc(g, &s.h_lev[p], P.n * 2));
@@ -356,21 +362,12 @@ int setup(av1mi_gop *g) {
     P.n = (size_t)P.w * P.h * S; P.bytes = P.n * g->bps;
   }
   g->nb = g->plane[0].n / 64;
-  g->fmt = c.input_format;
   g->next_q = c.base_q_idx;
-  const bool scaling = c.source_width != 0;
-  g->src_bd = c.source_bit_depth ? c.source_bit_depth : c.bit_depth;
-  g->chroma_stage = c.source_chroma != AV1MI_CHROMA_420 || g->src_bd != c.bit_depth;
-  g->luma_through = g->chroma_stage && g->src_bd == c.bit_depth;
-  g->stages = (g->fmt != AV1MI_INPUT_PLANAR) + g->chroma_stage + scaling;      // (config_error: never convert AND chroma)
-  // the fed size: the coded size, or the source size rounded up to 8
-  const int fed_w = scaling ? (c.source_width + 7) & ~7 : w, fed_rows = (scaling ? (c.source_height + 7) & ~7 : h) * S;
-  g->fed_ny = (size_t)fed_w * fed_rows;
-  g->fed_w = fed_w; g->fed_h = fed_rows / S;
-  for (int p = 0; p < 3; p++) {
-    g->in_bytes[p] = g->chroma_stage ? av1mi_source_plane_bytes(c.source_chroma, g->src_bd, p, fed_w, fed_rows) : av1mi_input_plane_bytes(g->fmt, c.bit_depth, p, fed_w, fed_rows);
-    g->pre_bytes[p] = av1mi_input_plane_bytes(AV1MI_INPUT_PLANAR, c.bit_depth, p, fed_w, fed_rows);
-  }
+  G_TRY(av1mi_gop_source_layout(&c, &g->layout));
+  // the chain (config_error: never convert AND chroma)
+  if (c.input_format != AV1MI_INPUT_PLANAR) { g->chain[g->stages++] = kConvert; g->fed_align = 16; }
+  if (c.source_chroma != AV1MI_CHROMA_420 || g->layout.bit_depth != c.bit_depth) { g->chain[g->stages++] = kChroma; g->fed_align = 16; }
+  if (c.source_width) g->chain[g->stages++] = kScale;
   if (c.gpu_entropy) {
     g->tiles = ((w + 63) / 64) * ((h + 63) / 64);
     // the size of the batch's frames as packed 4:2:0 samples: a frame codes to several times less at any sane quantiser, and to about
@@ -394,30 +391,16 @@ int setup(av1mi_gop *g) {
   if (c.coarse_range) G_TRY(dev_alloc(g, &g->d_me, av1mi::me_layout(w, h, S).bytes));
   if (c.quality_stats) G_TRY(dev_alloc(g, &g->d_quality_scratch, av1mi::quality_scratch_bytes(c.bit_depth, g->vw, g->vh, S)));
   if (c.store_frames) {
-    for (int p = 0; p < 3; p++) g->frame_bytes[p] = g->in_bytes[p] / (size_t)S;
     for (Store &st : g->store) {
       for (int p = 0; p < 3; p++)
-        if (g->frame_bytes[p]) G_TRY(dev_alloc(g, &st.d[p], g->frame_bytes[p] * (size_t)c.store_frames));
+        if (g->layout.plane[p].frame_bytes) G_TRY(dev_alloc(g, &st.d[p], g->layout.plane[p].frame_bytes * (size_t)c.store_frames));
       G_HIP(hipEventCreateWithFlags(&st.filled, hipEventDisableTiming));
       G_HIP(hipEventCreateWithFlags(&st.read_done, hipEventDisableTiming));
     }
-    G_TRY(dev_alloc(g, &g->d_scene, av1mi::scene_layout(g->fed_w, g->fed_h, c.store_frames).bytes));
+    G_TRY(dev_alloc(g, &g->d_scene, av1mi::scene_layout(g->layout.width, g->layout.height, c.store_frames).bytes));
     G_TRY(host_alloc(g, &g->h_records, (size_t)c.store_frames * sizeof(av1mi_scene_record)));
     G_HIP(hipEventCreateWithFlags(&g->scene_done, hipEventDisableTiming));
     for (hipEvent_t &e : g->put_done) G_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (c.deinterlace) {
-      // the fed planes: buffers fed_w x fed_h luma and the chroma of the source's layout; their true size is the source's (where the
-      // session scales) or the visible size
-      av1mi::DeintLaunch &L = g->deint;
-      const int tw = scaling ? c.source_width : g->vw, th = scaling ? c.source_height : g->vh;
-      const int sx = c.source_chroma == AV1MI_CHROMA_444 ? 0 : 1, sy = c.source_chroma == AV1MI_CHROMA_420 ? 1 : 0;
-      L.bd = g->src_bd; L.parity = c.deinterlace - 1; L.segments = S;
-      for (int p = 0; p < 3; p++) {
-        const bool have = g->frame_bytes[p] != 0;
-        L.plane_w[p] = !have ? 0 : p ? g->fed_w >> sx : g->fed_w; L.plane_h[p] = !have ? 0 : p ? g->fed_h >> sy : g->fed_h;
-        L.true_w[p] = p ? (tw + sx) >> sx : tw; L.true_h[p] = p ? (th + sy) >> sy : th;
-      }
-    }
   }
   G_TRY(dev_alloc(g, &g->d_zero_skip, g->nb));
   G_TRY(av1mi_memset(g->ctx, g->d_zero_skip, 0, g->nb));
@@ -432,6 +415,28 @@ extern "C" {
 int av1mi_policy_frame_params(int base_q_idx, int bit_depth, int frame_type, av1mi_frame_params *out) {
   if (!out || base_q_idx < 0 || base_q_idx > 255 || (bit_depth != 8 && bit_depth != 10) || frame_type < 0 || frame_type > 1) return AV1MI_E_INVAL;
   frame_params(base_q_idx, bit_depth, frame_type, out);
+  return AV1MI_OK;
+}
+
+int av1mi_gop_source_layout(const av1mi_gop_config *c, av1mi_source_layout *out) {
+  char why[512];
+  if (!out || config_error(c, why)) return AV1MI_E_INVAL;
+  av1mi_source_layout L = {};
+  const bool scaling = c->source_width != 0;      // the ONE place that says: scaling ? the source's size : the coded / visible size
+  L.width = scaling ? (c->source_width + 7) & ~7 : c->width; L.height = scaling ? (c->source_height + 7) & ~7 : c->height;
+  L.true_width = scaling ? c->source_width : c->visible_width ? c->visible_width : c->width;
+  L.true_height = scaling ? c->source_height : c->visible_height ? c->visible_height : c->height;
+  L.bit_depth = c->source_bit_depth ? c->source_bit_depth : c->bit_depth;
+  // a wire format (4:2:0 at bit_depth: config_error) or a planar source in its chroma layout; 4:2:0 planar is both
+  const int fmt = c->input_format, sx = c->source_chroma != AV1MI_CHROMA_444, sy = c->source_chroma == AV1MI_CHROMA_420;
+  const int pairs = fmt == AV1MI_INPUT_P010 || fmt == AV1MI_INPUT_NV12;      // the second plane interleaves U and V
+  for (int p = 0; p < 3; p++) {
+    L.plane[p].frame_bytes = fmt != AV1MI_INPUT_PLANAR ? av1mi_input_plane_bytes(fmt, L.bit_depth, p, L.width, L.height)
+                                                        : av1mi_source_plane_bytes(c->source_chroma, L.bit_depth, p, L.width, L.height);
+    if (!L.plane[p].frame_bytes) continue;
+    L.plane[p].width = p ? (L.width >> sx) << pairs : L.width; L.plane[p].height = p ? L.height >> sy : L.height;
+  }
+  *out = L;
   return AV1MI_OK;
 }
 
@@ -490,16 +495,18 @@ int av1mi_gop_max_in_flight(void) { return kSlots; }
 // behind the puts, and store.read_done lets the next put into that store wait for it.
 static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const void *src[3], int store = 0, const int32_t *index = nullptr) {
   hipStream_t main = av1mi::ctx_stream(g->ctx);
+  const av1mi_gop_config &c = g->cfg;
+  const av1mi_source_layout &Y = g->layout;
+  const int S = c.segments, dei = c.deinterlace;
   for (int p = 0; p < 3; p++) src[p] = dev_src ? dev_src[p] : s.d_in[p];
   if (index) {
     Store &st = g->store[store];
-    const int S = g->cfg.segments;
     const void **table = (const void **)s.h_table;
-    const int dei = g->cfg.deinterlace;
-    auto frame = [&](int p, int pos) { return (const void *)((const char *)st.d[p] + g->frame_bytes[p] * (size_t)pos); };
+    const size_t frame_bytes[3] = { Y.plane[0].frame_bytes, Y.plane[1].frame_bytes, Y.plane[2].frame_bytes };
+    auto frame = [&](int p, int pos) { return (const void *)((const char *)st.d[p] + frame_bytes[p] * (size_t)pos); };
     for (int sg = 0; sg < S; sg++)
       for (int p = 0; p < 3; p++) {
-        const bool flat = index[sg] < 0 || !g->frame_bytes[p];
+        const bool flat = index[sg] < 0 || !frame_bytes[p];
         if (!dei) table[sg * 3 + p] = flat ? nullptr : frame(p, index[sg]);
         else {      // P, C, N follow the POSITION in the store's run, clamped at its ends
           const void **e = table + (sg * 3 + p) * 3;
@@ -512,48 +519,45 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
     G_HIP(hipStreamWaitEvent(main, st.filled, 0));
     if (!dei) {
       av1mi::ProfScope ps(g->ctx, AV1MI_K_SCENE, main);
-      G_HIP(av1mi::launch_frames_gather(g->frame_bytes, S, (const void *const *)s.d_table, s.d_in, main));
-    } else {
+      G_HIP(av1mi::launch_frames_gather(frame_bytes, S, (const void *const *)s.d_table, s.d_in, main));
+    } else {      // the fed planes at their true sizes: chroma subsampled where the layout's plane is smaller than the luma buffer
       av1mi::ProfScope ps(g->ctx, AV1MI_K_SCENE, main);
-      av1mi::DeintLaunch L = g->deint;
-      L.table = (const void *const *)s.d_table;
-      for (int p = 0; p < 3; p++) L.dst[p] = s.d_in[p];
+      av1mi::DeintLaunch L;
+      L.bd = Y.bit_depth; L.parity = dei - 1; L.segments = S; L.table = (const void *const *)s.d_table;
+      for (int p = 0; p < 3; p++) {
+        const int sx = Y.plane[p].width < Y.width, sy = Y.plane[p].height < Y.height;
+        L.plane_w[p] = Y.plane[p].width; L.plane_h[p] = Y.plane[p].height; L.dst[p] = s.d_in[p];
+        L.true_w[p] = (Y.true_width + sx) >> sx; L.true_h[p] = (Y.true_height + sy) >> sy;
+      }
       G_HIP(av1mi::launch_deint_gather(L, main));
     }
     G_HIP(hipEventRecord(st.read_done, main));
     st.has_reader = true;
   } else if (!dev_src) {
     if (s.kernel_pending) G_HIP(hipStreamWaitEvent(g->up, s.filters_done, 0));
-    if (s.kernel_pending && g->cfg.quality_stats) G_HIP(hipStreamWaitEvent(g->up, s.quality_done, 0));
+    if (s.kernel_pending && c.quality_stats) G_HIP(hipStreamWaitEvent(g->up, s.quality_done, 0));
     for (int p = 0; p < 3; p++)
-      if (g->in_bytes[p]) G_HIP(hipMemcpyAsync(s.d_in[p], s.h_in[p], g->in_bytes[p], hipMemcpyHostToDevice, g->up));
+      if (fed_bytes(g, p)) G_HIP(hipMemcpyAsync(s.d_in[p], s.h_in[p], fed_bytes(g, p), hipMemcpyHostToDevice, g->up));
     G_HIP(hipEventRecord(s.uploaded, g->up));
     s.upload_pending = true;
     G_HIP(hipStreamWaitEvent(main, s.uploaded, 0));
   }
-  if (g->fmt != AV1MI_INPUT_PLANAR) {      // stage: convert, at the fed size
-    av1mi::InputLaunch L;
-    memset(&L, 0, sizeof(L));
-    for (int p = 0; p < 3; p++) { L.in[p] = src[p]; L.out[p] = g->scale ? s.d_pre[p] : s.d_src[p]; }
-    L.ny = g->fed_ny; L.nc = g->fed_ny / 4;
+  // the chain: a stage reads the planes where they are now and moves those it writes to its outputs (resolved by slot_buffers)
+  for (int k = 0; k < g->stages; k++) {
+    void *const *out = s.stage_out[k];
     av1mi::ProfScope ps(g->ctx, AV1MI_K_INPUT, main);
-    G_HIP(av1mi::launch_input_convert(g->fmt, L, main));
-    for (int p = 0; p < 3; p++) src[p] = L.out[p];
-  }
-  if (g->chroma_stage) {                   // stage: chroma, at the fed size (its TRUE size: the source's, or the visible size)
-    const av1mi_gop_config &c = g->cfg;
-    av1mi::ChromaLaunch L;
-    for (int p = 0; p < 3; p++) { L.in[p] = src[p]; L.out[p] = g->scale ? s.d_pre[p] : s.d_src[p]; }
-    L.chroma = c.source_chroma; L.src_bd = g->src_bd; L.bd = c.bit_depth; L.frames = c.segments;
-    L.w = g->scale ? c.source_width : g->vw; L.h = g->scale ? c.source_height : g->vh;
-    av1mi::ProfScope ps(g->ctx, AV1MI_K_INPUT, main);
-    G_HIP(av1mi::launch_chroma_convert(L, main));
-    for (int p = g->luma_through ? 1 : 0; p < 3; p++) src[p] = L.out[p];      // (a luma plane that passes through stays where it was fed)
-  }
-  if (g->scale) {                          // stage: scale, fed size -> coded size
-    av1mi::ProfScope ps(g->ctx, AV1MI_K_INPUT, main);
-    G_HIP(av1mi::launch_scale(g->scale, g->cfg.segments, src, s.d_src, main));
-    for (int p = 0; p < 3; p++) src[p] = s.d_src[p];
+    if (g->chain[k] == kConvert) {
+      av1mi::InputLaunch L{};
+      for (int p = 0; p < 3; p++) { L.in[p] = src[p]; L.out[p] = out[p]; }
+      L.ny = (size_t)Y.width * Y.height * S; L.nc = L.ny / 4;
+      G_HIP(av1mi::launch_input_convert(c.input_format, L, main));
+    } else if (g->chain[k] == kChroma) {      // at the fed frames' TRUE size
+      av1mi::ChromaLaunch L;
+      for (int p = 0; p < 3; p++) { L.in[p] = src[p]; L.out[p] = out[p]; }
+      L.chroma = c.source_chroma; L.src_bd = Y.bit_depth; L.bd = c.bit_depth; L.frames = S; L.w = Y.true_width; L.h = Y.true_height;
+      G_HIP(av1mi::launch_chroma_convert(L, main));
+    } else G_HIP(av1mi::launch_scale(g->scale, S, src, out, main));
+    for (int p = 0; p < 3; p++) if (out[p]) src[p] = out[p];      // (a plane that passes through stays where it was fed: the caller's, in a device batch)
   }
   return AV1MI_OK;
 }
@@ -868,8 +872,8 @@ int av1mi_gop_store_put(av1mi_gop *g, int store, int first, int count) {
   const int k = (int)(g->puts % kSlots);
   if (st.has_reader) G_HIP(hipStreamWaitEvent(g->up, st.read_done, 0));      // the batches that gather from this store
   for (int p = 0; p < 3; p++)
-    if (g->frame_bytes[p])
-      G_HIP(hipMemcpyAsync((char *)st.d[p] + g->frame_bytes[p] * (size_t)first, g->slot[k].h_in[p], g->frame_bytes[p] * (size_t)count, hipMemcpyHostToDevice, g->up));
+    if (const size_t fb = g->layout.plane[p].frame_bytes)
+      G_HIP(hipMemcpyAsync((char *)st.d[p] + fb * (size_t)first, g->slot[k].h_in[p], fb * (size_t)count, hipMemcpyHostToDevice, g->up));
   G_HIP(hipEventRecord(g->put_done[k], g->up));
   g->put_pending[k] = true;
   G_HIP(hipEventRecord(st.filled, g->up));
@@ -887,7 +891,7 @@ int av1mi_gop_store_analyse(av1mi_gop *g, int store, int frames, av1mi_scene_rec
     return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "store_analyse: store %d, %d frames of %d", store, frames, g->cfg.store_frames);
   G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
   av1mi::SceneLaunch L;
-  L.bd = g->src_bd; L.w = g->fed_w; L.h = g->fed_h; L.frames = frames;
+  L.bd = g->layout.bit_depth; L.w = g->layout.width; L.h = g->layout.height; L.frames = frames;
   L.luma = g->store[store].d[0]; L.scratch = g->d_scene; L.out = (av1mi_scene_record *)g->h_records;
   // on the upload stream, behind the puts; the summing launch writes the records into pinned memory
   G_HIP(av1mi::launch_scene(L, g->up));
@@ -912,9 +916,9 @@ int av1mi_gop_submit_stored(av1mi_gop *g, int store, const int32_t *index, int f
 
 int av1mi_gop_submit_device(av1mi_gop *g, const void *d_y, const void *d_u, const void *d_v, int frame_type) {
   if (!g) return AV1MI_E_INVAL;
-  if (g->fmt == AV1MI_INPUT_P010 || g->fmt == AV1MI_INPUT_NV12) d_v = d_u;      // semi-planar: no third plane
-  if (g->chroma_stage && g->cfg.source_chroma == AV1MI_CHROMA_400) d_u = d_v = d_y;      // grey: no chroma planes (the stage reads none)
-  if (!d_y || !d_u || !d_v || (((uintptr_t)d_y | (uintptr_t)d_u | (uintptr_t)d_v) & (g->fmt == AV1MI_INPUT_PLANAR && !g->chroma_stage ? 7 : 15)))
+  if (!g->layout.plane[2].frame_bytes) d_v = d_u;            // planes the layout does not have (semi-planar: the third; grey: both chroma
+  if (!g->layout.plane[1].frame_bytes) d_u = d_v = d_y;      // planes) are not read
+  if (!d_y || !d_u || !d_v || (((uintptr_t)d_y | (uintptr_t)d_u | (uintptr_t)d_v) & (g->fed_align - 1)))
     return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "null or misaligned device source plane");
   const void *src[3] = { d_y, d_u, d_v };
   return submit_batch(g, frame_type, src);
@@ -982,7 +986,7 @@ int av1mi_gop_download_fed(av1mi_gop *g, void *y, void *u, void *v) {
   G_HIP(hipStreamSynchronize(g->up));
   void *dst[3] = { y, u, v };
   for (int p = 0; p < 3; p++)
-    if (g->in_bytes[p] && dst[p]) G_TRY(av1mi_download(g->ctx, dst[p], g->slot[g->last].d_in[p], g->in_bytes[p]));
+    if (fed_bytes(g, p) && dst[p]) G_TRY(av1mi_download(g->ctx, dst[p], g->slot[g->last].d_in[p], fed_bytes(g, p)));
   return AV1MI_OK;
 }
 

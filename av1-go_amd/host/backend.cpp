@@ -172,14 +172,10 @@ int RunBackend(const BackendJob &job, std::string *err) {
     if (job.scale_w) { tw = job.scale_w; th = job.scale_h; square = true; }
     const bool scaling = tw != y.w || th != y.h || job.scale_w != 0;
     const int G = job.gop, w = (tw + 7) & ~7, h = (th + 7) & ~7;       // the coded size; tw x th is what a decoder outputs
-    // what the reader threads deliver: the coded size (the source's edge replicated into the padding), or — when the GPU scales — the
-    // source size rounded up to 8
-    const int rw = scaling ? (y.w + 7) & ~7 : w, rh = scaling ? (y.h + 7) & ~7 : h;
     int S = std::max(job.segments, 1);
     if (y.known_frames() >= 0) S = (int)std::max<long>(1, std::min<long>(S, (y.known_frames() + G - 1) / G));      // no more segments than the file has GOPs
     long total_frames = 0;
     const int threads = job.threads > 0 ? job.threads : (int)std::max(1u, std::thread::hardware_concurrency());
-    const size_t bps = y.bd == 8 ? 1 : 2, fy = (size_t)rw * rh * bps, fc = fy / 4;
     av1mi_gop_config cfg;
     memset(&cfg, 0, sizeof(cfg));
     if (w != tw || h != th) { cfg.visible_width = tw; cfg.visible_height = th; }
@@ -212,9 +208,12 @@ int RunBackend(const BackendJob &job, std::string *err) {
     // -av1mi_scenecut, or a job that deinterlaces: the frame store holds one group (the deinterlacer's run)
     const bool analysed = job.scenecut > 0, stored = analysed || dei != 0;
     if (stored) cfg.store_frames = S * G;
-    // one segment's planes in the pinned buffers (no chroma planes for a grey source)
-    const size_t py_bytes = convert ? av1mi_source_plane_bytes(y.chroma, y.src_bd, 0, rw, rh) : av1mi_input_plane_bytes(cfg.input_format, y.bd, 0, rw, rh);
-    const size_t pc_bytes = convert ? av1mi_source_plane_bytes(y.chroma, y.src_bd, 1, rw, rh) : av1mi_input_plane_bytes(cfg.input_format, y.bd, 1, rw, rh);
+    // What the reader threads deliver, one segment's share of the pinned buffers: frames of the coded size (the source's edge replicated
+    // into the padding) or, when the GPU scales, of the source size rounded up to 8; no chroma planes for a grey source.  (A config the
+    // layout refuses, av1mi_gop_open refuses below, with the reason.)
+    av1mi_source_layout fed = {};
+    (void)av1mi_gop_source_layout(&cfg, &fed);
+    auto at = [&](void *plane, int p, int i) { return (unsigned char *)plane + fed.plane[p].frame_bytes * (size_t)i; };      // frame i of a pinned plane
     std::vector<std::vector<unsigned char>> scratch(packed ? (size_t)S : 0);          // per reader thread: one planar frame to pack from
     CHK(av1mi_gop_open(ctx, &cfg, &gop));
     av1::SequenceParams sp; sp.width = tw; sp.height = th; sp.bit_depth = y.bd;
@@ -266,7 +265,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
       puts.ok.assign((size_t)n, 1);
       for (int i = 0; i < n; i++)
         puts.th.emplace_back([&, i, f0, py, pu, pv]() {
-          puts.ok[(size_t)i] = y.read(f0 + i, rw, rh, (unsigned char *)py + py_bytes * i, (unsigned char *)pu + pc_bytes * i, (unsigned char *)pv + pc_bytes * i);
+          puts.ok[(size_t)i] = y.read(f0 + i, fed.width, fed.height, at(py, 0, i), at(pu, 1, i), at(pv, 2, i));
         });
       return true;
     };
@@ -349,21 +348,21 @@ int RunBackend(const BackendJob &job, std::string *err) {
             // a shorter last GOP / fewer GOPs than segments: the slot is coded (the batch is one launch) and its output dropped.  Flat
             // planes, not whatever the pinned buffer held: stale pixels could cost the GPU coder's tile capacity for the whole batch
             // (zero samples pack to zero bytes)
-            memset((unsigned char *)py + py_bytes * s, 0, py_bytes);
-            if (pc_bytes) { memset((unsigned char *)pu + pc_bytes * s, 0, pc_bytes); memset((unsigned char *)pv + pc_bytes * s, 0, pc_bytes); }
+            void *const plane[3] = { py, pu, pv };
+            for (int p = 0; p < 3; p++) if (fed.plane[p].frame_bytes) memset(at(plane[p], p, s), 0, fed.plane[p].frame_bytes);
             continue;
           }
           reads.th.emplace_back([&, s, t, py, pu, pv]() {
             if (!packed) {
-              reads.ok[(size_t)s] = y.read((long)start[(size_t)s] + t, rw, rh, (unsigned char *)py + py_bytes * s, (unsigned char *)pu + pc_bytes * s, (unsigned char *)pv + pc_bytes * s);
+              reads.ok[(size_t)s] = y.read((long)start[(size_t)s] + t, fed.width, fed.height, at(py, 0, s), at(pu, 1, s), at(pv, 2, s));
               return;
             }
             // the frame (edge padding included) into this thread's scratch, then packed into the segment's byte range of the pinned planes
             std::vector<unsigned char> &f = scratch[(size_t)s];
+            const size_t fy = (size_t)fed.width * fed.height * 2, fc = fy / 4;      // planar 10-bit planes
             f.resize(fy + 2 * fc);
-            reads.ok[(size_t)s] = y.read((long)start[(size_t)s] + t, rw, rh, f.data(), f.data() + fy, f.data() + fy + fc) &&
-                                  av1mi_input_pack(AV1MI_INPUT_PACKED10, 10, rw, rh, f.data(), f.data() + fy, f.data() + fy + fc, (unsigned char *)py + py_bytes * s,
-                                                   (unsigned char *)pu + pc_bytes * s, (unsigned char *)pv + pc_bytes * s) == AV1MI_OK;
+            reads.ok[(size_t)s] = y.read((long)start[(size_t)s] + t, fed.width, fed.height, f.data(), f.data() + fy, f.data() + fy + fc) &&
+                                  av1mi_input_pack(AV1MI_INPUT_PACKED10, 10, fed.width, fed.height, f.data(), f.data() + fy, f.data() + fy + fc, at(py, 0, s), at(pu, 1, s), at(pv, 2, s)) == AV1MI_OK;
           });
         }
         return true;

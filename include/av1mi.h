@@ -632,6 +632,26 @@ typedef struct av1mi_gop_config {
   int deinterlace;
 } av1mi_gop_config;
 
+/* The source layout: what a session opened with a config is FED, as one description.  Everything a caller sizes or strides by — the
+ * pinned buffers of av1mi_gop_acquire_input, the device planes of av1mi_gop_submit_device, a frame of the store, what
+ * av1mi_gop_download_fed writes — follows from it, and the session itself reads its geometry from nothing else.  One FED frame (one
+ * segment's share of a batch) has up to three planes; a batch's plane is `segments` frames stacked: segments * frame_bytes bytes,
+ * frame s at byte s * frame_bytes.  (av1mi_input_plane_bytes / av1mi_source_plane_bytes give the same numbers for rows = segments *
+ * height: both are linear in the rows.) */
+typedef struct av1mi_source_layout {
+  int width, height;            /* luma size of a fed frame's BUFFER: the coded size, or where the session scales the source size rounded up to 8 */
+  int true_width, true_height;  /* the picture inside it: source_width x source_height where the session scales, else the visible size */
+  int bit_depth;                /* of the fed samples: source_bit_depth, or bit_depth */
+  struct {
+    int width, height;          /* in samples; 0 x 0 = no such plane (the chroma of a grey source, the third plane of P010 / NV12).  The
+                                   interleaved plane of P010 / NV12 counts U and V: width x height / 2; PACKED10 counts the samples it packs */
+    size_t frame_bytes;         /* one frame of it; 0 = no such plane */
+  } plane[3];
+} av1mi_source_layout;
+/* cfg -> its layout.  Plain host code, no GPU needed.  AV1MI_E_INVAL (and *out untouched) for a null pointer and for every config
+ * av1mi_gop_open refuses. */
+int av1mi_gop_source_layout(const av1mi_gop_config *cfg, av1mi_source_layout *out);
+
 /* Frame-header parameters chosen by the session's policy for one frame (non-normative encoder choices; the bitstream carries
  * them): deblocking level from the quantiser step (libaom's LPF_PICK_FROM_Q fit, key / inter frames differ for 8-bit), one
  * CDEF strength set and damping from the step, Wiener restoration with fixed taps on 64x64 units. */
@@ -685,7 +705,8 @@ void av1mi_gop_close(av1mi_gop *g);
  * Blocks until the upload that last used these buffers has finished.
  * A session whose input_format is not PLANAR hands out the buffers in THAT format (sizes: av1mi_input_plane_bytes with rows =
  * segments * height): PACKED10 three byte buffers, P010 / NV12 the luma plane in *y, the interleaved plane in *u and *v = NULL.
- * A session with source_chroma / source_bit_depth hands out planes of av1mi_source_plane_bytes each; grey sources: *u = *v = NULL. */
+ * A session with source_chroma / source_bit_depth hands out planes of av1mi_source_plane_bytes each; grey sources: *u = *v = NULL.
+ * av1mi_gop_source_layout says all of this for a config: plane p holds segments * plane[p].frame_bytes bytes, NULL where that is 0. */
 int av1mi_gop_acquire_input(av1mi_gop *g, void **y, void **u, void **v);
 /* queue the batch in the acquired buffers.  frame_type: 0 key, 1 inter, -1 = by position in the GOP (gop_length).
  * AV1MI_E_INVAL when av1mi_gop_max_in_flight() batches are already in flight (collect first).

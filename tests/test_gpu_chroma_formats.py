@@ -200,6 +200,36 @@ def test_444_session_with_scaling(ctx, av1mi):
     _check(ctx, av1mi, R.C444, 12, 192, 112, 60, 6, true=(144, 108), source=(144, 108), visible=(192, 108), vias=("submit",))
 
 
+def test_device_batches_with_a_luma_plane_that_passes_through_to_the_scaler(ctx, av1mi):
+    """a 4:4:4 8-bit source of 40 x 24 in device memory, scaled to 24 x 16, one segment, a key and an inter batch: the scaler reads the
+    CALLER's luma plane (chroma, then scale; no plane of the session's lies between).  The bytes of the same session fed through
+    input_planes(), and the caller's luma buffers come back unchanged"""
+    w, h, q, gop = 24, 16, 110, 2
+    batches = _source_batches(R.C444, 8, 40, 24, 1, gop, 14)
+    kw = dict(source=(40, 24), source_chroma=R.C444, source_bit_depth=8)
+    base = _run(ctx, av1mi, w, h, 8, q, gop, 1, batches, "submit", **kw)
+    assert [o["frame_type"] for o in base] == [0, 1]
+    s = av1mi.GopSession(ctx, w, h, 8, q, gop, 1, gpu_entropy=1, **kw)
+    held = [[ctx.to_device(a) for a in planes] for planes in batches]
+    got = []
+    try:
+        for bufs in held:
+            s.submit_device(*bufs)
+            fr = s.collect()
+            got.append({k: v.copy() for k, v in fr.items() if isinstance(v, np.ndarray)})
+            got[-1]["frame_type"] = fr["frame_type"]
+            got[-1]["ref_y"], got[-1]["ref_u"], got[-1]["ref_v"] = s.download_reference()
+        assert s.entropy_fallbacks() == 0
+        for bufs, planes in zip(held, batches):
+            assert (bufs[0].download(planes[0].shape, planes[0].dtype) == planes[0]).all(), "the session wrote the caller's luma plane"
+    finally:
+        s.close()
+        for bufs in held:
+            for b in bufs:
+                b.free()
+    _same(base, got, "4:4:4 from device memory, scaled")
+
+
 def test_cropped_size_sessions(ctx, av1mi):
     """70 x 38 coded at 72 x 40: a luma plane that passes through (4:2:2 10-bit; the caller replicates its edge) and one that is
     converted (4:4:4 12-bit; its padding undefined as well)"""

@@ -150,6 +150,49 @@ def test_session_gathers_through_the_deinterlacer(ctx, av1mi, clip, woven):
                     assert (got[t][i] == refs[t][i][sg * rows:(sg + 1) * rows]).all(), "segment %d frame %d plane %d: dav1d decodes another picture" % (sg, t, i)
 
 
+def test_stored_422_session_deinterlaces_converts_and_scales(ctx, av1mi):
+    """every source stage behind one store: a 4:2:2 8-bit source of true size 70 x 38 (buffers 72 x 40, the texture goes on into the
+    padding) is deinterlaced, converted (its luma plane passes through) and scaled to 48 x 24; 2 segments, 3 batches, all in flight.
+    The fed buffers are the reference's frames, and the bytes those of a plain 4:2:0 session at 48 x 24 fed what the numpy
+    references make of them"""
+    import chroma_formats_ref as CR
+    import test_gpu_chroma_formats as TC
+    import test_gpu_scale as TS
+    tw, th, w, h, segs, gop, q = 70, 38, 48, 24, 2, 3, 110
+    clip = K.pan_clip(72, 40, segs * gop, 8, 0, seed=11, chroma=(1, 0))
+    true = [(tw, th)] + [CR.true_chroma_size(CR.C422, tw, th)] * 2
+    run = [R.run(a, tw_p, th_p, 0) for a, (tw_p, th_p) in zip(clip, true)]
+    index = [[sg * gop + t for sg in range(segs)] for t in range(gop)]
+    fed = [[np.concatenate([run[p][f] for f in idx]) for p in range(3)] for idx in index]
+    table = TS._lib_table(av1mi)
+    scaled = []
+    for planes in fed:
+        y, u, v = CR.convert_stack(CR.C422, 8, 8, tw, th, segs, planes)
+        frames = [[y[sg * 40:sg * 40 + th, :tw], u[sg * 20:sg * 20 + 19, :35], v[sg * 20:sg * 20 + 19, :35]] for sg in range(segs)]
+        scaled.append(TS._expected(frames, w, h, 8, table))
+    base = [{k: v for k, v in o.items() if not k.startswith("ref_")} for o in TC._run(ctx, av1mi, w, h, 8, q, gop, segs, scaled)]
+    s = av1mi.GopSession(ctx, w, h, 8, q, gop, segs, gpu_entropy=1, source=(tw, th), source_chroma=CR.C422, store_frames=segs * gop, deinterlace=1)
+    got = []
+    try:
+        for f0 in range(0, segs * gop, segs):
+            for dst, a in zip(s.input_planes(), clip):
+                dst[:] = a[f0:f0 + segs].reshape(dst.shape)
+            s.store_put(0, f0, segs)
+        for t in range(gop):
+            s.submit_stored(0, index[t], 0 if t == 0 else 1)
+            for p, a in enumerate(s.download_fed()):
+                assert a.shape == fed[t][p].shape and (a == fed[t][p]).all(), "batch %d plane %d: the fed buffer is not the reference's frame" % (t, p)
+        assert s.pending() == gop
+        for t in range(gop):
+            fr = s.collect()
+            got.append({k: v.copy() for k, v in fr.items() if isinstance(v, np.ndarray)})
+            got[-1]["frame_type"] = fr["frame_type"]
+        assert s.entropy_fallbacks() == 0
+    finally:
+        s.close()
+    TC._same(base, got, "stored 4:2:2, deinterlaced and scaled")
+
+
 def test_session_argument_rules(ctx, av1mi):
     for kw in (dict(deinterlace=1), dict(deinterlace=3, store_frames=4), dict(deinterlace=-1, store_frames=4)):
         with pytest.raises(av1mi.Av1miError) as e:
