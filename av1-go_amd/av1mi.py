@@ -91,7 +91,7 @@ class GopConfig(C.Structure):
                 ("segments", C.c_int), ("search_range", C.c_int), ("gpu_entropy", C.c_int), ("visible_width", C.c_int),
                 ("visible_height", C.c_int), ("coder_streams", C.c_int), ("key_block_size", C.c_int), ("input_format", C.c_int), ("source_width", C.c_int),
                 ("source_height", C.c_int), ("quality_stats", C.c_int), ("coarse_range", C.c_int), ("source_chroma", C.c_int),
-                ("source_bit_depth", C.c_int), ("store_frames", C.c_int), ("deinterlace", C.c_int)]
+                ("source_bit_depth", C.c_int), ("store_frames", C.c_int), ("deinterlace", C.c_int), ("denoise", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -105,7 +105,7 @@ class GopFrame(C.Structure):
                 ("uv_mode", C.c_void_p), ("mv", C.c_void_p), ("skip", C.c_void_p), ("lev_y", C.c_void_p), ("lev_u", C.c_void_p),
                 ("lev_v", C.c_void_p), ("tiles_per_frame", C.c_int), ("tile_size", C.c_void_p), ("tile_payload", C.c_void_p),
                 ("payload_bytes", C.c_uint64), ("lr_on", C.c_void_p), ("key_block_size", C.c_int), ("key_modes_stride", C.c_int),
-                ("key_modes_band", C.c_int), ("quality", C.c_void_p)]
+                ("key_modes_band", C.c_int), ("quality", C.c_void_p), ("grain", C.c_void_p)]
 
 
 def policy_frame_params(base_q_idx, bit_depth, frame_type):
@@ -119,6 +119,8 @@ def policy_frame_params(base_q_idx, bit_depth, frame_type):
 
 # av1mi_quality (include/av1mi.h): one record per (frame, plane)
 # av1mi_scene_record (include/av1mi.h "scene analysis"): one record per frame
+GRAIN_BINS = 16      # AV1MI_GRAIN_BINS; a record (av1mi_grain_record) is that many bins
+GRAIN_DTYPE = np.dtype([("sum_sq", "<u8"), ("count", "<u4"), ("reserved", "<u4")])      # av1mi_grain_bin
 SCENE_DTYPE = np.dtype([("inter_sad", "<u8"), ("intra_sad", "<u8"), ("blocks", "<u4"), ("reserved", "<u4")])
 assert SCENE_DTYPE.itemsize == 24
 QUALITY_DTYPE = np.dtype([("sse", "<u8"), ("ssim_sum", "<f8"), ("samples", "<u4"), ("windows", "<u4")])
@@ -227,7 +229,7 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
@@ -239,12 +241,16 @@ class GopSession:
         store_frames: the session owns two frame stores of that many fed frames (av1mi_gop_config.store_frames): store_put(),
         store_analyse() and submit_stored() feed it, submit() is refused;
         deinterlace: 0 none, 1 top field first, 2 bottom field first (av1mi_gop_config.deinterlace; needs store_frames): submit_stored()
-        gathers through the deinterlacer"""
+        gathers through the deinterlacer;
+        denoise: 1 .. 16, the strength of the temporal denoiser (av1mi_gop_config.denoise; needs store_frames, not with deinterlace):
+        submit_stored() gathers through it and collect()["grain"] holds the grain records.  None leaves the field unset (0 = none)"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
         sw, sh = source if source is not None else (0, 0)
         self.cfg = GopConfig(width, height, bit_depth, base_q_idx, gop_length, segments, search_range, gpu_entropy, vw, vh, coder_streams, key_block_size, input_format,
                              sw, sh, int(quality_stats), int(coarse_range), int(source_chroma), int(source_bit_depth), int(store_frames), int(deinterlace))
+        if denoise is not None:
+            self.cfg.denoise = int(denoise)
         self.g = C.c_void_p()
         ctx.lib.av1mi_gop_open.argtypes = [C.c_void_p, C.POINTER(GopConfig), C.POINTER(C.c_void_p)]
         ctx._chk(ctx.lib.av1mi_gop_open(ctx.h, C.byref(self.cfg), C.byref(self.g)))
@@ -324,6 +330,8 @@ class GopSession:
         out = dict(params=f.params, frame_type=f.params.frame_type, lr_on=_view(f.lr_on, (S, 3), np.uint8), raw=f)      # restoration on / off per segment and plane
         if f.quality:      # quality_stats: records [segment, plane] (QUALITY_DTYPE)
             out["quality"] = _view(f.quality, (S, 3), QUALITY_DTYPE)
+        if f.grain:        # denoise: records [segment, plane, bin] (GRAIN_DTYPE)
+            out["grain"] = _view(f.grain, (S, 3, GRAIN_BINS), GRAIN_DTYPE)
         if f.key_block_size == 32:
             out["key_block_size"] = 32
         if f.key_block_size == 32 and f.lev_y:
@@ -609,6 +617,17 @@ class Context:
         dst = (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_dst])
         self._chk(self.lib.av1mi_deinterlace_gather(self.h, int(bit_depth), arr([s[0] for s in plane_sizes]), arr([s[1] for s in plane_sizes]),
                                                     arr([s[0] for s in true_sizes]), arr([s[1] for s in true_sizes]), int(parity), int(segments), d_table.ptr, dst))
+
+    def denoise_gather(self, bit_depth, plane_sizes, true_sizes, strength, segments, d_table, d_dst, d_records=None):
+        """the gather with the denoiser in it (av1mi_denoise_gather): deinterlace_gather's arguments with a strength (1 .. 16) in place of
+        the parity; d_records: DevBuf of segments * 3 records (GRAIN_DTYPE [segments, 3, GRAIN_BINS]) or None = nothing is measured;
+        asynchronous"""
+        self.lib.av1mi_denoise_gather.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        arr = lambda v: (C.c_int * 3)(*[int(x) for x in v])
+        dst = (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_dst])
+        self._chk(self.lib.av1mi_denoise_gather(self.h, int(bit_depth), arr([s[0] for s in plane_sizes]), arr([s[1] for s in plane_sizes]),
+                                                arr([s[0] for s in true_sizes]), arr([s[1] for s in true_sizes]), int(strength), int(segments), d_table.ptr, dst,
+                                                d_records.ptr if d_records is not None else None))
 
     def prof_enable(self, on):
         self._chk(self.lib.av1mi_prof_enable(self.h, int(on)))

@@ -13,6 +13,23 @@ _HOST = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host", "libav1
 _lib = None
 
 
+class FilmGrain(C.Structure):
+    """av1mi_film_grain (include/av1mi_host.h): the film_grain_params a frame header carries"""
+    _fields_ = [("apply_grain", C.c_int32), ("grain_seed", C.c_int32), ("num_y_points", C.c_int32), ("point_y_value", C.c_uint8 * 14),
+                ("point_y_scaling", C.c_uint8 * 14), ("chroma_scaling_from_luma", C.c_int32), ("num_cb_points", C.c_int32), ("num_cr_points", C.c_int32),
+                ("point_cb_value", C.c_uint8 * 10), ("point_cb_scaling", C.c_uint8 * 10), ("point_cr_value", C.c_uint8 * 10), ("point_cr_scaling", C.c_uint8 * 10),
+                ("grain_scaling_minus_8", C.c_int32), ("ar_coeff_lag", C.c_int32), ("ar_coeffs_y_plus_128", C.c_uint8 * 24),
+                ("ar_coeffs_cb_plus_128", C.c_uint8 * 25), ("ar_coeffs_cr_plus_128", C.c_uint8 * 25), ("ar_coeff_shift_minus_6", C.c_int32),
+                ("grain_scale_shift", C.c_int32), ("cb_mult", C.c_int32), ("cb_luma_mult", C.c_int32), ("cb_offset", C.c_int32), ("cr_mult", C.c_int32),
+                ("cr_luma_mult", C.c_int32), ("cr_offset", C.c_int32), ("overlap_flag", C.c_int32), ("clip_to_restricted_range", C.c_int32)]
+
+
+def _set_film_grain(f, film_grain, film_grain_present):
+    """the two film grain fields of an ObuFrame; film_grain_present None = follows the pointer"""
+    f.film_grain_present = int(film_grain is not None if film_grain_present is None else film_grain_present)
+    f.film_grain = C.addressof(film_grain) if film_grain is not None else None
+
+
 class ObuFrame(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("bit_depth", C.c_int32), ("frame_type", C.c_int32),
                 ("base_q_idx", C.c_int32), ("lf_level", C.c_int32 * 4), ("lf_sharpness", C.c_int32), ("cdef_damping", C.c_int32),
@@ -22,7 +39,7 @@ class ObuFrame(C.Structure):
                 ("tile_rows_log2", C.c_int32), ("y_mode", C.c_void_p), ("angle_y", C.c_void_p), ("uv_mode", C.c_void_p),
                 ("angle_uv", C.c_void_p), ("cfl_alpha", C.c_void_p), ("skip", C.c_void_p), ("tx_type", C.c_void_p),
                 ("is_inter", C.c_void_p), ("mv", C.c_void_p), ("lev_y", C.c_void_p), ("lev_u", C.c_void_p), ("lev_v", C.c_void_p),
-                ("visible_width", C.c_int32), ("visible_height", C.c_int32)]
+                ("visible_width", C.c_int32), ("visible_height", C.c_int32), ("film_grain_present", C.c_int32), ("film_grain", C.c_void_p)]
 
 
 def lib():
@@ -46,11 +63,13 @@ _PTR_FIELDS = {"cdef_idx": np.uint8, "y_mode": np.uint8, "angle_y": np.int8, "uv
 def temporal_unit(width, height, bit_depth, base_q_idx, frame_type=0, with_sequence_header=True, threads=1, lf_level=(0, 0, 0, 0),
                   lf_sharpness=0, cdef_damping=3, cdef_bits=0, cdef_y=(0,), cdef_uv=(0,), lr_type=(0, 0, 0), lr_unit_shift=0, lr_uv_shift=0,
                   lr_units=(None, None, None), reduced_tx_set=0, disable_cdf_update=0, tile_cols_log2=-1, tile_rows_log2=-1, opstream=False,
-                  visible=None, key_rows32=0, **arrays):
+                  visible=None, key_rows32=0, film_grain=None, film_grain_present=None, **arrays):
     """arrays: y_mode, angle_y, uv_mode, angle_uv, cfl_alpha, skip, tx_type, is_inter, mv, lev_y, lev_u, lev_v, cdef_idx (numpy, raster
     order over 8x8 blocks; see av1_bitstream.hpp).  visible: (width, height) a decoder outputs when the coded size is the source's rounded up to 8.
+    film_grain: a FilmGrain the frame header carries; film_grain_present: the sequence's flag (None = set iff film_grain is given).
     Returns bytes."""
     f = ObuFrame()
+    _set_film_grain(f, film_grain, film_grain_present)
     f.width, f.height, f.bit_depth, f.frame_type, f.base_q_idx = width, height, bit_depth, frame_type, base_q_idx
     if visible is not None:
         f.visible_width, f.visible_height = int(visible[0]), int(visible[1])
@@ -155,6 +174,7 @@ def blocks_temporal_unit(width, height, bit_depth, base_q_idx, partition, blocks
 def assemble_temporal_unit(width, height, bit_depth, base_q_idx, payloads, sizes, with_sequence_header=True, **hdr):
     """temporal unit around tile payloads coded on the GPU (av1mi_obu_assemble_temporal_unit); hdr = header_from_params(...)"""
     f = ObuFrame()
+    _set_film_grain(f, hdr.get("film_grain"), hdr.get("film_grain_present"))
     f.width, f.height, f.bit_depth, f.base_q_idx = width, height, bit_depth, base_q_idx
     if hdr.get("visible") is not None:
         f.visible_width, f.visible_height = int(hdr["visible"][0]), int(hdr["visible"][1])
@@ -187,10 +207,11 @@ def assemble_temporal_unit(width, height, bit_depth, base_q_idx, payloads, sizes
     return out[:n].tobytes()
 
 
-def session_frame_unit_gpu(width, height, bit_depth, frame, seg, with_sequence_header=None, visible=None):
+def session_frame_unit_gpu(width, height, bit_depth, frame, seg, with_sequence_header=None, visible=None, film_grain=None, film_grain_present=None):
     """the temporal unit of segment `seg` of a collected batch whose tiles were entropy-coded on the GPU (gpu_entropy != 0)"""
     p = frame["params"]
     hdr = header_from_params(p, width, height, frame["lr_on"][seg], visible)
+    hdr.update(film_grain=film_grain, film_grain_present=film_grain_present)
     nt = frame["tiles_per_frame"]
     sizes = frame["tile_size"][seg * nt:(seg + 1) * nt]
     start = int(frame["tile_size"][:seg * nt].sum(dtype=np.uint64))
@@ -199,9 +220,30 @@ def session_frame_unit_gpu(width, height, bit_depth, frame, seg, with_sequence_h
     return assemble_temporal_unit(width, height, bit_depth, p.base_q_idx, pay, sizes, with_sequence_header=sh, **hdr)
 
 
-def session_temporal_unit(width, height, bit_depth, raw_frame, seg, with_sequence_header=True, threads=1, visible=None):
+def film_grain_from_records(records, bit_depth, frame_index):
+    """av1mi_film_grain_from_records: one frame's grain records (av1mi.GRAIN_DTYPE [3, GRAIN_BINS], e.g. collect()["grain"][seg]) -> FilmGrain"""
+    h = lib()
+    h.av1mi_film_grain_from_records.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(FilmGrain)]
+    rec = np.ascontiguousarray(records)
+    assert rec.shape == (3, 16) and rec.dtype.itemsize == 16
+    g = FilmGrain()
+    if h.av1mi_film_grain_from_records(rec.ctypes.data, int(bit_depth), int(frame_index), C.byref(g)):
+        raise ValueError("av1mi_film_grain_from_records: bad argument")
+    return g
+
+
+def film_grain_mid_grey(g):
+    h = lib()
+    h.av1mi_film_grain_mid_grey.argtypes = [C.POINTER(FilmGrain)]
+    return h.av1mi_film_grain_mid_grey(C.byref(g))
+
+
+def session_temporal_unit(width, height, bit_depth, raw_frame, seg, with_sequence_header=True, threads=1, visible=None, film_grain=None, film_grain_present=None):
     """av1mi_session_temporal_unit (include/av1mi_host.h): the temporal unit of segment `seg` of a collected batch, from the raw
-    av1mi_gop_frame (av1mi.GopSession.collect()["raw"]) — whichever coder produced it, whatever the key frames' block size"""
+    av1mi_gop_frame (av1mi.GopSession.collect()["raw"]) — whichever coder produced it, whatever the key frames' block size.  With
+    film_grain / film_grain_present: av1mi_session_temporal_unit_grain"""
+    if film_grain is not None or film_grain_present:
+        return _session_temporal_unit_grain(width, height, bit_depth, raw_frame, seg, with_sequence_header, threads, visible, film_grain, film_grain_present)
     h = lib()
     h.av1mi_session_temporal_unit.restype = C.c_longlong
     h.av1mi_session_temporal_unit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong,
@@ -214,6 +256,22 @@ def session_temporal_unit(width, height, bit_depth, raw_frame, seg, with_sequenc
                                       out.ctypes.data, cap, err, 256)
     if n < 0:
         raise ValueError("av1mi_session_temporal_unit: " + err.value.decode())
+    return out[:n].tobytes()
+
+
+def _session_temporal_unit_grain(width, height, bit_depth, raw_frame, seg, with_sequence_header, threads, visible, film_grain, film_grain_present):
+    h = lib()
+    h.av1mi_session_temporal_unit_grain.restype = C.c_longlong
+    h.av1mi_session_temporal_unit_grain.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p, C.c_void_p, C.c_longlong, C.c_char_p, C.c_int]
+    cap = width * height * 4 + (1 << 16)
+    out = np.empty(cap, np.uint8)
+    err = C.create_string_buffer(256)
+    vw, vh = visible if visible is not None else (0, 0)
+    present = int(film_grain is not None if film_grain_present is None else film_grain_present)
+    n = h.av1mi_session_temporal_unit_grain(C.addressof(raw_frame), int(seg), width, height, bit_depth, int(vw), int(vh), int(with_sequence_header), int(threads),
+                                            present, C.addressof(film_grain) if film_grain is not None else None, out.ctypes.data, cap, err, 256)
+    if n < 0:
+        raise ValueError("av1mi_session_temporal_unit_grain: " + err.value.decode())
     return out[:n].tobytes()
 
 
@@ -295,10 +353,11 @@ def header_from_params(p, width, height, lr_on=None, visible=None):
                 **({} if visible is None else {"visible": (int(vw), int(vh))}))
 
 
-def session_frame_unit(width, height, bit_depth, frame, seg, with_sequence_header=None, threads=1, visible=None):
+def session_frame_unit(width, height, bit_depth, frame, seg, with_sequence_header=None, threads=1, visible=None, film_grain=None, film_grain_present=None):
     """the temporal unit of segment `seg` of a collected GOP-session batch (av1mi.GopSession.collect())"""
     p = frame["params"]
     hdr = header_from_params(p, width, height, frame["lr_on"][seg], visible)
+    hdr.update(film_grain=film_grain, film_grain_present=film_grain_present)
     if p.frame_type == 0:
         sym = dict(y_mode=frame["y_mode"][seg], uv_mode=frame["uv_mode"][seg])
     else:

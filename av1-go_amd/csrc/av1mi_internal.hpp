@@ -196,6 +196,18 @@ struct DeintLaunch {
 };
 hipError_t launch_deint_gather(const DeintLaunch &L, hipStream_t s);
 
+// the denoising gather (grain_kernels.hip, include/av1mi.h "denoising" / "grain records"): launch_deint_gather's table and geometry with a
+// strength (1 .. 16) in place of the parity; bd 8 or 10.  records: segments * 3 records (device or pinned host memory), or null = nothing
+// is measured, ONE launch; else two, and scratch holds grain_scratch_bytes(L) bytes (8-byte aligned) of per-workgroup partials.
+struct DenoiseLaunch {
+  int bd, strength, segments;
+  int plane_w[3], plane_h[3], true_w[3], true_h[3];
+  const void *const *table; void *dst[3];
+  void *scratch; av1mi_grain_record *records;
+};
+size_t grain_scratch_bytes(const DenoiseLaunch &L);      // 0 for a geometry the launch refuses
+hipError_t launch_denoise_gather(const DenoiseLaunch &L, hipStream_t s);
+
 // side information that follows a batch's quantiser (levels_kernels.hip): up to three arrays of dwords patched in place in one launch,
 // word = (word & keep) | bits unless (word & hold) != 0
 struct LevelsLaunch {

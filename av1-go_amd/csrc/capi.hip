@@ -28,6 +28,8 @@ struct av1mi_ctx {
   size_t me_scratch_bytes = 0;
   void *scene_scratch = nullptr;          // av1mi_scene_analyse: quarter planes + block results (grown on demand)
   size_t scene_scratch_bytes = 0;
+  void *grain_scratch = nullptr;          // av1mi_denoise_gather: the workgroups' partial records (grown on demand)
+  size_t grain_scratch_bytes = 0;
   // per-kernel profile: one event pair per launch while enabled
   bool prof_on = false;
   struct ProfRec { int kind; hipEvent_t e0, e1; };
@@ -186,6 +188,7 @@ void av1mi_close(av1mi_ctx *ctx) {
   if (ctx->quality_scratch) (void)hipFree(ctx->quality_scratch);
   if (ctx->me_scratch) (void)hipFree(ctx->me_scratch);
   if (ctx->scene_scratch) (void)hipFree(ctx->scene_scratch);
+  if (ctx->grain_scratch) (void)hipFree(ctx->grain_scratch);
   if (ctx->av1ent) av1mi::av1ent_free(ctx->av1ent);
   av1mi::scale_plan_destroy(ctx->scale_plan);
   for (auto &r : ctx->prof_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -647,6 +650,47 @@ int av1mi_deinterlace_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3]
   }
   ProfScope ps(ctx, AV1MI_K_SCENE);
   HIP_TRY(ctx, av1mi::launch_deint_gather(L, ctx->stream));
+  return AV1MI_OK;
+}
+
+int av1mi_denoise_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int strength,
+                         int segments, const void *const *d_table, void *const d_dst[3], av1mi_grain_record *d_records) {
+  BIND(ctx);
+  if (!plane_w || !plane_h || !true_w || !true_h || !d_table || !d_dst || ((uintptr_t)d_table & 7) || ((uintptr_t)d_records & 7))
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: null pointer, or misaligned table or records");
+  if (bit_depth != 8 && bit_depth != 10) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: bit depth %d not supported (8 or 10)", bit_depth);
+  if (strength < 1 || strength > 16) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: strength %d out of range (1 .. 16)", strength);
+  if (segments < 1 || segments > 4096) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: segments %d out of range (1 .. 4096)", segments);
+  av1mi::DenoiseLaunch L;
+  L.bd = bit_depth; L.strength = strength; L.segments = segments; L.table = d_table; L.records = d_records; L.scratch = nullptr;
+  const int bps = bit_depth == 8 ? 1 : 2;
+  for (int p = 0; p < 3; p++) {
+    const bool have = plane_w[p] > 0 && plane_h[p] > 0;
+    if (plane_w[p] < 0 || plane_h[p] < 0 || plane_w[p] > 16384 || plane_h[p] > 16384 || ((size_t)plane_w[p] * bps & 3))
+      return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: plane %d of %dx%d samples (rows of whole dwords, up to 16384x16384)", p, plane_w[p], plane_h[p]);
+    if (have && (true_w[p] < 1 || true_h[p] < 1 || true_w[p] > plane_w[p] || true_h[p] > plane_h[p] || plane_w[p] - true_w[p] >= 8 || plane_h[p] - true_h[p] >= 8))
+      return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: plane %d: the true size %dx%d must lie within 7 samples below the buffer's %dx%d", p, true_w[p], true_h[p], plane_w[p], plane_h[p]);
+    if (have && (plane_w[p] * bps - 1) / 16 * (16 / bps) > true_w[p] - 1)
+      return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: plane %d: the last 16-byte cell of a row of %d samples starts beyond the true width %d", p, plane_w[p], true_w[p]);
+    if (have && (!d_dst[p] || ((uintptr_t)d_dst[p] & 15))) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: null or misaligned destination (plane %d)", p);
+    L.plane_w[p] = have ? plane_w[p] : 0; L.plane_h[p] = have ? plane_h[p] : 0; L.true_w[p] = true_w[p]; L.true_h[p] = true_h[p]; L.dst[p] = d_dst[p];
+  }
+  if (d_records) {
+    const size_t need = av1mi::grain_scratch_bytes(L);
+    if (ctx->grain_scratch_bytes < need) {      // (hipFree waits for the launches that still use the old one)
+      if (ctx->grain_scratch) (void)hipFree(ctx->grain_scratch);
+      ctx->grain_scratch = nullptr; ctx->grain_scratch_bytes = 0;
+      HIP_TRY(ctx, hipMalloc(&ctx->grain_scratch, need));
+      ctx->grain_scratch_bytes = need;
+    }
+    L.scratch = ctx->grain_scratch;
+    if (!L.scratch) {      // no plane at all: the records are still defined
+      HIP_TRY(ctx, hipMemsetAsync(d_records, 0, (size_t)segments * 3 * sizeof(av1mi_grain_record), ctx->stream));
+      return AV1MI_OK;
+    }
+  }
+  ProfScope ps(ctx, AV1MI_K_SCENE);
+  HIP_TRY(ctx, av1mi::launch_denoise_gather(L, ctx->stream));
   return AV1MI_OK;
 }
 

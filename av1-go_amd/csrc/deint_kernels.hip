@@ -17,6 +17,7 @@
 //             true row's: both by construction (a row y >= h is computed as row h - 1).  The input's padding is never used.
 // Arithmetic: include/av1mi.h; restated in numpy by tests/deinterlace_ref.py.  Reference tree: nothing (transcode.go:120).
 #include "av1mi_internal.hpp"
+#include "gather_cells.hpp"
 
 namespace av1mi {
 
@@ -41,29 +42,6 @@ template <typename Pix>
 __device__ __forceinline__ int elem(const uint32_t *d, int i) {
   if constexpr (sizeof(Pix) == 1) return (int)((d[i >> 2] >> (8 * (i & 3))) & 0xffu);
   else return (int)((d[i >> 1] >> (16 * (i & 1))) & 0xffffu);
-}
-
-// the cell at byte `off` of a row of rb bytes; dwords beyond the row, and all of an inactive lane's, are 0
-__device__ __forceinline__ void load_cell(const char *row, uint32_t off, uint32_t rb, bool whole, bool active, uint32_t c[4]) {
-  c[0] = c[1] = c[2] = c[3] = 0;
-  if (!active) return;
-  if (whole) {
-    const uint4 v = *reinterpret_cast<const uint4 *>(row + off);
-    c[0] = v.x; c[1] = v.y; c[2] = v.z; c[3] = v.w;
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-      if (off + 4u * q < rb) c[q] = *reinterpret_cast<const uint32_t *>(row + off + 4u * q);
-  }
-}
-__device__ __forceinline__ void store_cell(char *row, uint32_t off, uint32_t rb, bool whole, bool active, const uint32_t c[4]) {
-  if (!active) return;
-  if (whole) *reinterpret_cast<uint4 *>(row + off) = make_uint4(c[0], c[1], c[2], c[3]);
-  else {
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-      if (off + 4u * q < rb) *reinterpret_cast<uint32_t *>(row + off + 4u * q) = c[q];
-  }
 }
 
 // samples of a cell -> its dwords, the columns beyond the true width (sample index above `lastj`) repeating the last true one

@@ -121,6 +121,10 @@ struct Slot {
   hipEvent_t quality_done = nullptr;
   // store_frames: the gather's table of this slot's batch, [segment * 3 + plane] source pointers: pinned, and the device copy the kernel reads
   void *h_table = nullptr, *d_table = nullptr;
+  // denoise: the batch's grain records [segment * 3 + plane], pinned and written by the GPU (k_grain_sum); grain_done follows
+  void *h_grain = nullptr;
+  hipEvent_t grain_done = nullptr;
+  bool has_grain = false;             // this batch went through the denoising gather (a batch of av1mi_gop_submit_device does not)
 };
 
 // one frame store: a buffer per plane, store_frames frames of layout.plane[p].frame_bytes each
@@ -151,6 +155,7 @@ struct av1mi_gop {
   void *d_cdef_sb[2] = {}, *d_lr[2] = {}, *d_zero_skip = nullptr;
   void *d_lr_scratch = nullptr;                // the restoration decision's partial sums (three planes)
   void *d_me = nullptr;                        // coarse_range: the coarse search's quarter planes and centres of one batch (single: the chain is serial in t)
+  void *d_grain_scratch = nullptr;             // denoise: the workgroups' partial records of one batch (the main stream orders its users)
   void *d_quality_scratch = nullptr;           // quality_stats: the tiles' partial sums of one batch (the main stream orders its users)
   int vw = 0, vh = 0;                          // the true frame size (== the coded size unless cfg.visible_* say otherwise)
   int last = 0;                                // slot of the most recent batch (its d_lr_on selects the next batch's references)
@@ -203,6 +208,19 @@ enum Stage { kConvert, kChroma, kScale };      // the input stages (the chain of
 bool stage_writes(const av1mi_gop *g, int k, int p) { return !(g->chain[k] == kChroma && p == 0 && g->layout.bit_depth == g->cfg.bit_depth); }
 size_t fed_bytes(const av1mi_gop *g, int p) { return g->layout.plane[p].frame_bytes * (size_t)g->cfg.segments; }      // plane p of a batch as fed
 
+// the fed planes at their true sizes, for the filtering gathers (DeintLaunch / DenoiseLaunch): chroma subsampled where the layout's plane
+// is smaller than the luma buffer
+template <typename Launch>
+void fed_geometry(const av1mi_gop *g, const Slot &s, Launch &L) {
+  const av1mi_source_layout &Y = g->layout;
+  L.bd = Y.bit_depth; L.segments = g->cfg.segments; L.table = (const void *const *)s.d_table;
+  for (int p = 0; p < 3; p++) {
+    const int sx = Y.plane[p].width < Y.width, sy = Y.plane[p].height < Y.height;
+    L.plane_w[p] = Y.plane[p].width; L.plane_h[p] = Y.plane[p].height; L.dst[p] = s.d_in[p];
+    L.true_w[p] = (Y.true_width + sx) >> sx; L.true_h[p] = (Y.true_height + sy) >> sy;
+  }
+}
+
 int slot_buffers(av1mi_gop *g, Slot &s) {
   const av1mi_gop_config &c = g->cfg;
   const int S = c.segments;
@@ -237,10 +255,14 @@ int slot_buffers(av1mi_gop *g, Slot &s) {
     G_HIP(hipEventCreateWithFlags(&s.ent_done, hipEventDisableTiming));
   }
   if (c.store_frames) {
-    // (a session that deinterlaces keeps three pointers per segment and plane: the frames before, at and after the position)
-    const size_t entries = (size_t)S * 3 * (c.deinterlace ? 3 : 1);
+    // (a session that deinterlaces or denoises keeps three pointers per segment and plane: the frames before, at and after the position)
+    const size_t entries = (size_t)S * 3 * (c.deinterlace || c.denoise ? 3 : 1);
     G_TRY(host_alloc(g, &s.h_table, entries * sizeof(void *)));
     G_TRY(dev_alloc(g, &s.d_table, entries * sizeof(void *)));
+  }
+  if (c.denoise) {
+    G_TRY(host_alloc(g, &s.h_grain, (size_t)S * 3 * sizeof(av1mi_grain_record)));
+    G_HIP(hipEventCreateWithFlags(&s.grain_done, hipEventDisableTiming));
   }
   if (c.quality_stats) {
     G_TRY(host_alloc(g, &s.h_quality, (size_t)S * 3 * sizeof(av1mi_quality)));
@@ -346,6 +368,10 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
   if (c->store_frames && c->input_format != AV1MI_INPUT_PLANAR) return WHY("a frame store (store_frames %d) needs input_format 0 (planar), not %d", c->store_frames, c->input_format);
   if (c->deinterlace < 0 || c->deinterlace > 2) return WHY("deinterlace %d unknown (0 none, 1 top field first, 2 bottom field first)", c->deinterlace);
   if (c->deinterlace && !c->store_frames) return WHY("deinterlace %d needs a frame store (store_frames > 0): the filter reads the frames before and after each frame", c->deinterlace);
+  if (c->denoise < 0 || c->denoise > 16) return WHY("denoise %d out of range (0 none, 1 .. 16 the strength)", c->denoise);
+  if (c->denoise && !c->store_frames) return WHY("denoise %d needs a frame store (store_frames > 0): the filter reads the frames before and after each frame", c->denoise);
+  if (c->denoise && c->deinterlace) return WHY("denoise %d together with deinterlace %d is not built: the chain of the two needs a third copy of a group", c->denoise, c->deinterlace);
+  if (c->denoise && c->source_bit_depth == 12) return WHY("denoise %d takes fed samples of 8 or 10 bits, not source_bit_depth 12", c->denoise);
   return nullptr;
 #undef WHY
 }
@@ -390,6 +416,15 @@ int setup(av1mi_gop *g) {
   G_TRY(dev_alloc(g, &g->d_lr_scratch, av1mi_lr_yuv_decide_scratch_bytes(h, S)));
   if (c.coarse_range) G_TRY(dev_alloc(g, &g->d_me, av1mi::me_layout(w, h, S).bytes));
   if (c.quality_stats) G_TRY(dev_alloc(g, &g->d_quality_scratch, av1mi::quality_scratch_bytes(c.bit_depth, g->vw, g->vh, S)));
+  if (c.denoise) {
+    Slot probe; av1mi::DenoiseLaunch L;
+    fed_geometry(g, probe, L);
+    L.strength = c.denoise;
+    const size_t bytes = av1mi::grain_scratch_bytes(L);
+    if (!bytes) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "denoise %d: the fed layout %dx%d (true %dx%d) is not one the denoising gather takes", c.denoise, g->layout.width,
+                                      g->layout.height, g->layout.true_width, g->layout.true_height);
+    G_TRY(dev_alloc(g, &g->d_grain_scratch, bytes));
+  }
   if (c.store_frames) {
     for (Store &st : g->store) {
       for (int p = 0; p < 3; p++)
@@ -464,7 +499,7 @@ void av1mi_gop_close(av1mi_gop *g) {
   if (g->up) { (void)hipStreamSynchronize(g->up); (void)hipStreamDestroy(g->up); }
   if (g->down) { (void)hipStreamSynchronize(g->down); (void)hipStreamDestroy(g->down); }
   for (Slot &s : g->slot)
-    for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done, s.quality_done })
+    for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done, s.quality_done, s.grain_done })
       if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : { g->store[0].filled, g->store[0].read_done, g->store[1].filled, g->store[1].read_done, g->scene_done, g->put_done[0], g->put_done[1], g->put_done[2] })
     if (e) (void)hipEventDestroy(e);
@@ -497,8 +532,9 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
   hipStream_t main = av1mi::ctx_stream(g->ctx);
   const av1mi_gop_config &c = g->cfg;
   const av1mi_source_layout &Y = g->layout;
-  const int S = c.segments, dei = c.deinterlace;
+  const int S = c.segments, dei = c.deinterlace, three = dei || c.denoise;      // three: the table holds P, C, N
   for (int p = 0; p < 3; p++) src[p] = dev_src ? dev_src[p] : s.d_in[p];
+  s.has_grain = index && c.denoise;
   if (index) {
     Store &st = g->store[store];
     const void **table = (const void **)s.h_table;
@@ -507,7 +543,7 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
     for (int sg = 0; sg < S; sg++)
       for (int p = 0; p < 3; p++) {
         const bool flat = index[sg] < 0 || !frame_bytes[p];
-        if (!dei) table[sg * 3 + p] = flat ? nullptr : frame(p, index[sg]);
+        if (!three) table[sg * 3 + p] = flat ? nullptr : frame(p, index[sg]);
         else {      // P, C, N follow the POSITION in the store's run, clamped at its ends
           const void **e = table + (sg * 3 + p) * 3;
           e[0] = flat ? nullptr : frame(p, index[sg] > 0 ? index[sg] - 1 : 0);
@@ -515,22 +551,23 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
           e[2] = flat ? nullptr : frame(p, index[sg] + 1 < st.run ? index[sg] + 1 : st.run - 1);
         }
       }
-    G_HIP(hipMemcpyAsync(s.d_table, s.h_table, (size_t)S * 3 * (dei ? 3 : 1) * sizeof(void *), hipMemcpyHostToDevice, main));
+    G_HIP(hipMemcpyAsync(s.d_table, s.h_table, (size_t)S * 3 * (three ? 3 : 1) * sizeof(void *), hipMemcpyHostToDevice, main));
     G_HIP(hipStreamWaitEvent(main, st.filled, 0));
-    if (!dei) {
+    {
       av1mi::ProfScope ps(g->ctx, AV1MI_K_SCENE, main);
-      G_HIP(av1mi::launch_frames_gather(frame_bytes, S, (const void *const *)s.d_table, s.d_in, main));
-    } else {      // the fed planes at their true sizes: chroma subsampled where the layout's plane is smaller than the luma buffer
-      av1mi::ProfScope ps(g->ctx, AV1MI_K_SCENE, main);
-      av1mi::DeintLaunch L;
-      L.bd = Y.bit_depth; L.parity = dei - 1; L.segments = S; L.table = (const void *const *)s.d_table;
-      for (int p = 0; p < 3; p++) {
-        const int sx = Y.plane[p].width < Y.width, sy = Y.plane[p].height < Y.height;
-        L.plane_w[p] = Y.plane[p].width; L.plane_h[p] = Y.plane[p].height; L.dst[p] = s.d_in[p];
-        L.true_w[p] = (Y.true_width + sx) >> sx; L.true_h[p] = (Y.true_height + sy) >> sy;
-      }
-      G_HIP(av1mi::launch_deint_gather(L, main));
+      if (dei) {
+        av1mi::DeintLaunch L;
+        fed_geometry(g, s, L);
+        L.parity = dei - 1;
+        G_HIP(av1mi::launch_deint_gather(L, main));
+      } else if (c.denoise) {      // ... and the records of what it removed, straight into the slot's pinned memory
+        av1mi::DenoiseLaunch L;
+        fed_geometry(g, s, L);
+        L.strength = c.denoise; L.scratch = g->d_grain_scratch; L.records = (av1mi_grain_record *)s.h_grain;
+        G_HIP(av1mi::launch_denoise_gather(L, main));
+      } else G_HIP(av1mi::launch_frames_gather(frame_bytes, S, (const void *const *)s.d_table, s.d_in, main));
     }
+    if (c.denoise) G_HIP(hipEventRecord(s.grain_done, main));
     G_HIP(hipEventRecord(st.read_done, main));
     st.has_reader = true;
   } else if (!dev_src) {
@@ -908,9 +945,9 @@ int av1mi_gop_submit_stored(av1mi_gop *g, int store, const int32_t *index, int f
   if (frame_type != 0 && frame_type != 1) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: frame_type %d (0 key or 1 inter: the layout is the caller's)", frame_type);
   for (int s = 0; s < g->cfg.segments; s++)
     if (index[s] < -1 || index[s] >= g->cfg.store_frames) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: index[%d] = %d outside the store of %d frames", s, (int)index[s], g->cfg.store_frames);
-  for (int s = 0; g->cfg.deinterlace && s < g->cfg.segments; s++)
+  for (int s = 0; (g->cfg.deinterlace || g->cfg.denoise) && s < g->cfg.segments; s++)
     if (index[s] >= g->store[store].run)
-      return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: index[%d] = %d beyond the store's run of %d frames (deinterlacing reads the neighbours inside it)", s, (int)index[s], g->store[store].run);
+      return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: index[%d] = %d beyond the store's run of %d frames (the filter reads the neighbours inside it)", s, (int)index[s], g->store[store].run);
   return submit_batch(g, frame_type, nullptr, store, index);
 }
 
@@ -934,6 +971,7 @@ int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out) {
   out->params = s.params;
   out->lr_on = (const uint8_t *)s.h_lr_on;
   if (g->cfg.quality_stats) { G_HIP(hipEventSynchronize(s.quality_done)); out->quality = (const av1mi_quality *)s.h_quality; }
+  if (g->cfg.denoise && s.has_grain) { G_HIP(hipEventSynchronize(s.grain_done)); out->grain = (const av1mi_grain_record *)s.h_grain; }
   out->segments = g->cfg.segments;
   out->blocks_per_frame = g->nb / (size_t)g->cfg.segments;
   out->key_block_size = s.frame_type == 0 && g->key32 ? 32 : 8;

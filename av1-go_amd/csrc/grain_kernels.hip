@@ -1,0 +1,325 @@
+// grain_kernels.hip — the denoising gather behind av1mi_gop_config.denoise (include/av1mi.h "denoising", "grain records"): k_denoise_gather
+// stands where k_frames_gather / k_deint_gather stand, and measures what it removes on the way; k_grain_sum adds the measurements up.
+//
+//   work      k_deint_gather's: an item is (segment, plane, band of kBand output rows, group of 64 cells of 16 bytes), a wave owns an item
+//             and walks down its band, a workgroup holds four consecutive items of one (segment, plane).
+//   rows      per row and per neighbour frame F the wave computes A = |C - F| of its cell as PACKED 16-bit halves (v_pk_max / min / sub)
+//             and the horizontal 3-sums H = A(x - 1) + A(x) + A(x + 1), two samples per add (no half can carry: 3 x 4095).  H of three
+//             rows is held rolling (previous, current, next); D = their sum (<= 9 x 4095 < 2^16).  Inside a band every row of C, P and
+//             N is loaded once; a band re-reads one row above and one below it.
+//   columns   A(x0 - 1) and A(x0 + NS) are the neighbouring lanes': one dword (P's half, N's half) moved up and one moved down per row
+//             by ds_bpermute_b32.  Lanes 0 and 63, whose neighbour is another wave's, load that one dword of C, P and N.  At the
+//             true edge the last true column's A is replicated in registers; nothing beyond the true size is read into the result.
+//   samples   weights, output and the residual are per sample in 32 bits: num <= 48 x 4095 does not fit a half.  K[den] comes from a
+//             register of lane den - 16 (ds_bpermute_b32 again: no LDS memory for it).
+//   records   a lane adds r^2 and 1 into a (bin, sum, count) triple of its own while the bin stays the same, and flushes it into its
+//             wave's 16 bins in LDS (integer atomics: the order cannot matter) when the bin changes and at the end of the band; the
+//             workgroup's four sets become ONE partial in scratch; k_grain_sum adds the partials of a (segment, plane).  All integers,
+//             so every order of addition gives the same bytes.
+//   ends      a frame at an end of its run (P or N is C itself) and a flat slot (C null) are the gather alone: copied, resp. zeros,
+//             and their partials are zero.
+// Arithmetic: include/av1mi.h; restated in numpy by tests/denoise_ref.py.  Reference tree: nothing (it has no denoiser).
+#include "av1mi_internal.hpp"
+#include "gather_cells.hpp"
+
+namespace av1mi {
+
+namespace {
+constexpr int kBand = 16;      // output rows per item
+
+struct GrainGeom {
+  void *dst[3];
+  uint32_t plane_bytes[3];     // of one segment's plane in the destination (= a frame's plane in the store)
+  uint32_t row_bytes[3];       // multiples of 4
+  int32_t rows[3];             // buffer rows
+  int32_t w[3], h[3];          // true size in samples
+  uint32_t cells[3];           // 16-byte cells per row (the last one may be partial)
+  uint32_t groups[3];          // groups of 64 cells per row
+  uint32_t items[3];           // groups x bands
+  uint32_t wgs[3];             // workgroups per (segment, plane)
+  uint32_t per_seg;
+  uint32_t cut, recip;         // 27 T and floor(2^32 / (27 T)) + 1
+  int bin_shift;               // bit_depth - 4
+  av1mi_grain_bin *partials;   // per workgroup 16 bins, [blockIdx.x]; null = nothing is measured
+};
+
+// K[den - 16] = round(65536 / den), den = 16 .. 48 (include/av1mi.h prints it)
+__device__ const uint32_t kRecipDen[33] = { 4096, 3855, 3641, 3449, 3277, 3121, 2979, 2849, 2731, 2621, 2521, 2427, 2341, 2260, 2185, 2114, 2048,
+                                            1986, 1928, 1872, 1820, 1771, 1725, 1680, 1638, 1598, 1560, 1524, 1489, 1456, 1425, 1394, 1365 };
+
+typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+// |a - b| of both 16-bit halves
+__device__ __forceinline__ uint32_t pk_absdiff(uint32_t a, uint32_t b) {
+  const us2 x = __builtin_bit_cast(us2, a), y = __builtin_bit_cast(us2, b);
+  return __builtin_bit_cast(uint32_t, (us2)(__builtin_elementwise_max(x, y) - __builtin_elementwise_min(x, y)));
+}
+// the samples of a cell as 16-bit halves: NP dwords, sample 2 q in the low half of dword q
+template <typename Pix, int NP>
+__device__ __forceinline__ void halves(const uint32_t c[4], uint32_t o[NP]) {
+  if constexpr (sizeof(Pix) == 1) {
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      o[2 * q] = (c[q] & 0xffu) | ((c[q] & 0xff00u) << 8);
+      o[2 * q + 1] = ((c[q] >> 16) & 0xffu) | ((c[q] >> 24) << 16);
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; q++) o[q] = c[q];
+  }
+}
+__device__ __forceinline__ uint32_t half_of(const uint32_t *v, int j) { return (v[j >> 1] >> (16 * (j & 1))) & 0xffffu; }
+template <typename Pix>
+__device__ __forceinline__ uint32_t last_sample(uint32_t d) { return sizeof(Pix) == 1 ? d >> 24 : d >> 16; }
+template <typename Pix>
+__device__ __forceinline__ uint32_t first_sample(uint32_t d) { return sizeof(Pix) == 1 ? d & 0xffu : d & 0xffffu; }
+
+// the halves beyond sample lastj take the value of sample lastj (>= 0), without indexing registers by a variable
+template <int NP>
+__device__ __forceinline__ void replicate_halves(uint32_t v[NP], int lastj) {
+  uint32_t e = v[0] & 0xffffu;
+#pragma unroll
+  for (int j = 1; j < 2 * NP; j++) {
+    e = j <= lastj ? half_of(v, j) : e;
+    v[j >> 1] = (v[j >> 1] & ~(0xffffu << (16 * (j & 1)))) | e << (16 * (j & 1));
+  }
+}
+// samples of a cell -> its dwords, the columns beyond the true width (sample index above lastj) repeating the last true one
+template <typename Pix, int NS>
+__device__ __forceinline__ void pack_out(uint32_t o[NS], int lastj, uint32_t c[4]) {
+#pragma unroll
+  for (int j = 1; j < NS; j++) o[j] = j > lastj ? o[j - 1] : o[j];
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    if constexpr (sizeof(Pix) == 1) c[q] = o[4 * q] | o[4 * q + 1] << 8 | o[4 * q + 2] << 16 | o[4 * q + 3] << 24;
+    else c[q] = o[2 * q] | o[2 * q + 1] << 16;
+  }
+}
+
+template <int NP>
+struct GrainRow { uint32_t c[4], p[4], n[4], hp[NP], hn[NP]; };      // the cells of a row and its horizontal 3-sums against P and N
+
+}  // namespace
+
+// grid: per_seg x segments; 4 waves = 4 consecutive items of one (segment, plane)
+template <typename Pix>
+__global__ __launch_bounds__(256) void k_denoise_gather(GrainGeom G, const void *const *table) {
+  constexpr int NS = 16 / (int)sizeof(Pix);      // samples per cell
+  constexpr int NP = NS / 2;                     // dwords of packed halves per cell
+  __shared__ unsigned long long s_sum[4][16];
+  __shared__ uint32_t s_cnt[4][16];
+  const unsigned seg = blockIdx.x / G.per_seg;
+  unsigned wg = blockIdx.x - seg * G.per_seg;
+  int p = 0;
+  if (wg >= G.wgs[0]) { wg -= G.wgs[0]; p = 1; }
+  if (p == 1 && wg >= G.wgs[1]) { wg -= G.wgs[1]; p = 2; }
+#define PL(a) (p == 0 ? G.a[0] : p == 1 ? G.a[1] : G.a[2])
+  const uint32_t rb = PL(row_bytes), cells = PL(cells), groups = PL(groups), items = PL(items);
+  const int rows = PL(rows), w = PL(w), h = PL(h);
+  char *dst = (char *)PL(dst) + (size_t)seg * PL(plane_bytes);
+#undef PL
+  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  const bool measure = G.partials != nullptr;
+  if (measure) {
+    if (threadIdx.x < 64) { s_sum[threadIdx.x >> 4][threadIdx.x & 15] = 0; s_cnt[threadIdx.x >> 4][threadIdx.x & 15] = 0; }
+    __syncthreads();
+  }
+  const unsigned item = wg * 4u + wave;
+  if (item < items) {                            // (uniform in the wave)
+    const unsigned band = item / groups, grp = item - band * groups;
+    const uint32_t cx = grp * 64u + lane, off = cx * 16u;
+    const bool active = cx < cells, whole = !(rb & 15u);
+    const int r0 = (int)band * kBand, r1 = min(r0 + kBand, rows);
+    const char *const *tab = reinterpret_cast<const char *const *>(table) + ((size_t)seg * 3 + p) * 3;
+    const char *P = tab[0], *C = tab[1], *N = tab[2];
+    const int x0 = (int)cx * NS;                 // the cell's first sample; x0 <= w - 1 in every active lane (the launcher checks)
+    const int lastj = w - 1 - x0;                // sample of the cell that is the last true column (>= NS: the cell is all true)
+    if (!C) {                                    // a flat slot
+      const uint32_t z[4] = { 0, 0, 0, 0 };
+      for (int y = r0; y < r1; y++) store_cell(dst + (size_t)y * rb, off, rb, whole, active, z);
+    } else if (P == C || N == C) {               // an end of the run: the frame passes through, its padding replicating its edge
+      for (int y = r0; y < r1; y++) {
+        uint32_t c[4];
+        load_cell(C + (size_t)min(y, h - 1) * rb, off, rb, whole, active, c);
+        if (lastj < NS - 1) {
+          uint32_t hv[NP], o[NS];
+          halves<Pix, NP>(c, hv);
+#pragma unroll
+          for (int j = 0; j < NS; j++) o[j] = half_of(hv, j);
+          pack_out<Pix, NS>(o, lastj, c);
+        }
+        store_cell(dst + (size_t)y * rb, off, rb, whole, active, c);
+      }
+    } else {
+      const uint32_t kden = kRecipDen[lane < 33 ? lane : 32];
+      const bool left_edge = cx == 0, right_edge = lastj <= NS - 1;      // the neighbour column lies beyond the true width: clamped
+      // row r: its cells, and the horizontal 3-sums of |C - F| with the columns clamped to the true width
+      auto load_row = [&](GrainRow<NP> &R, int r) {
+        const size_t ro = (size_t)r * rb;
+        load_cell(C + ro, off, rb, whole, active, R.c);
+        load_cell(P + ro, off, rb, whole, active, R.p);
+        load_cell(N + ro, off, rb, whole, active, R.n);
+        uint32_t hc[NP], hf[NP], ap[NP], an[NP];
+        halves<Pix, NP>(R.c, hc);
+        halves<Pix, NP>(R.p, hf);
+#pragma unroll
+        for (int q = 0; q < NP; q++) ap[q] = pk_absdiff(hc[q], hf[q]);
+        halves<Pix, NP>(R.n, hf);
+#pragma unroll
+        for (int q = 0; q < NP; q++) an[q] = pk_absdiff(hc[q], hf[q]);
+        if (lastj < NS - 1) {                    // the cell reaches into the padding: the last true column's value goes on
+          replicate_halves<NP>(ap, lastj);
+          replicate_halves<NP>(an, lastj);
+        }
+        // the neighbours' columns: (P's, N's) in one dword each way.  Every lane of the wave is here
+        uint32_t lft = __shfl_up((ap[NP - 1] >> 16) | (an[NP - 1] & 0xffff0000u), 1);
+        uint32_t rgt = __shfl_down((ap[0] & 0xffffu) | (an[0] << 16), 1);
+        if (lane == 0 && active && cx > 0) {     // the neighbours are another wave's
+          const uint32_t c = last_sample<Pix>(*reinterpret_cast<const uint32_t *>(C + ro + off - 4u));
+          const uint32_t a = last_sample<Pix>(*reinterpret_cast<const uint32_t *>(P + ro + off - 4u)), b = last_sample<Pix>(*reinterpret_cast<const uint32_t *>(N + ro + off - 4u));
+          lft = (c > a ? c - a : a - c) | (c > b ? c - b : b - c) << 16;
+        }
+        if (lane == 63 && cx + 1 < cells) {
+          const uint32_t c = first_sample<Pix>(*reinterpret_cast<const uint32_t *>(C + ro + off + 16u));
+          const uint32_t a = first_sample<Pix>(*reinterpret_cast<const uint32_t *>(P + ro + off + 16u)), b = first_sample<Pix>(*reinterpret_cast<const uint32_t *>(N + ro + off + 16u));
+          rgt = (c > a ? c - a : a - c) | (c > b ? c - b : b - c) << 16;
+        }
+        if (left_edge) lft = (ap[0] & 0xffffu) | (an[0] << 16);
+        if (right_edge) rgt = (ap[NP - 1] >> 16) | (an[NP - 1] & 0xffff0000u);
+        const uint32_t lp = lft << 16, ln = lft & 0xffff0000u, rp = rgt & 0xffffu, rn = rgt >> 16;      // left: in the high half; right: in the low half
+#pragma unroll
+        for (int q = 0; q < NP; q++) {
+          R.hp[q] = ap[q] + __builtin_amdgcn_alignbit(ap[q], q ? ap[q - 1] : lp, 16) + __builtin_amdgcn_alignbit(q + 1 < NP ? ap[q + 1] : rp, ap[q], 16);
+          R.hn[q] = an[q] + __builtin_amdgcn_alignbit(an[q], q ? an[q - 1] : ln, 16) + __builtin_amdgcn_alignbit(q + 1 < NP ? an[q + 1] : rn, an[q], 16);
+        }
+      };
+
+      GrainRow<NP> cur, nxt;
+      uint32_t php[NP], phn[NP], out[4] = { 0, 0, 0, 0 };
+      int bin = -1;                              // the lane's open triple
+      unsigned long long acc = 0; uint32_t cnt = 0;
+      auto flush = [&]() {
+        if (bin >= 0) { atomicAdd(&s_sum[wave][bin], acc); atomicAdd(&s_cnt[wave][bin], cnt); }
+        acc = 0; cnt = 0;
+      };
+      int held = -1;
+#pragma unroll 1
+      for (int y = r0; y < r1; y++) {
+        const int ye = min(y, h - 1);
+        if (ye != held) {
+          if (held < 0) {                        // the band's first row: cur <- the row above it, nxt <- the row itself
+            load_row(cur, max(ye - 1, 0));
+            if (ye >= 1) load_row(nxt, ye); else nxt = cur;
+          }
+#pragma unroll
+          for (int q = 0; q < NP; q++) { php[q] = cur.hp[q]; phn[q] = cur.hn[q]; }
+          cur = nxt;
+          if (ye + 1 <= h - 1) load_row(nxt, ye + 1);      // (else the row below is the row itself: nxt stays)
+          held = ye;
+          uint32_t cc[NP], pp[NP], nn[NP], o[NS];
+          halves<Pix, NP>(cur.c, cc);
+          halves<Pix, NP>(cur.p, pp);
+          halves<Pix, NP>(cur.n, nn);
+#pragma unroll
+          for (int j = 0; j < NS; j++) {
+            const uint32_t dp = php[j >> 1] + cur.hp[j >> 1] + nxt.hp[j >> 1], dn = phn[j >> 1] + cur.hn[j >> 1] + nxt.hn[j >> 1];      // (both halves; no carry)
+            const uint32_t Dp = (dp >> (16 * (j & 1))) & 0xffffu, Dn = (dn >> (16 * (j & 1))) & 0xffffu;
+            const uint32_t wp = 16u - __umulhi(16u * min(Dp, G.cut), G.recip), wn = 16u - __umulhi(16u * min(Dn, G.cut), G.recip);
+            const uint32_t c = half_of(cc, j), num = 16u * c + wp * half_of(pp, j) + wn * half_of(nn, j);
+            const uint32_t k = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((wp + wn) << 2), (int)kden);
+            o[j] = (num * k + 32768u) >> 16;
+            if (measure && active && y < h && j <= lastj && wp + wn >= 24u) {
+              const int b = (int)(o[j] >> G.bin_shift);
+              if (b != bin) { flush(); bin = b; }
+              const int r = (int)c - (int)o[j];
+              acc += (uint32_t)(r * r); cnt++;
+            }
+          }
+          pack_out<Pix, NS>(o, lastj, out);
+        }
+        store_cell(dst + (size_t)y * rb, off, rb, whole, active, out);
+      }
+      if (measure) flush();
+    }
+  }
+  if (measure) {
+    __syncthreads();
+    if (threadIdx.x < 16) {
+      av1mi_grain_bin b;
+      b.sum_sq = s_sum[0][threadIdx.x] + s_sum[1][threadIdx.x] + s_sum[2][threadIdx.x] + s_sum[3][threadIdx.x];
+      b.count = s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
+      b.reserved = 0;
+      G.partials[(size_t)blockIdx.x * 16 + threadIdx.x] = b;
+    }
+  }
+}
+
+// grid: segments x 3; the partials of (segment, plane) are those of its workgroups, [first, first + n)
+__global__ __launch_bounds__(256) void k_grain_sum(GrainGeom G, av1mi_grain_record *out) {
+  __shared__ unsigned long long s_sum[16][16];
+  __shared__ uint32_t s_cnt[16][16];
+  const unsigned seg = blockIdx.x / 3, p = blockIdx.x - seg * 3;
+  const unsigned first = seg * G.per_seg + (p > 0 ? G.wgs[0] : 0) + (p > 1 ? G.wgs[1] : 0), n = G.wgs[p];
+  const unsigned b = threadIdx.x & 15u, part = threadIdx.x >> 4;
+  unsigned long long sum = 0; uint32_t cnt = 0;
+  for (unsigned i = part; i < n; i += 16) {
+    const av1mi_grain_bin v = G.partials[(size_t)(first + i) * 16 + b];
+    sum += v.sum_sq; cnt += v.count;
+  }
+  s_sum[part][b] = sum; s_cnt[part][b] = cnt;
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    av1mi_grain_bin o; o.sum_sq = 0; o.count = 0; o.reserved = 0;
+    for (int i = 0; i < 16; i++) { o.sum_sq += s_sum[i][b]; o.count += s_cnt[i][b]; }
+    out[blockIdx.x].bin[b] = o;
+  }
+}
+
+namespace {
+// the geometry of a launch; hipErrorInvalidValue for what the kernel cannot take
+hipError_t grain_geometry(const DenoiseLaunch &L, GrainGeom &G) {
+  const uint32_t bps = L.bd == 8 ? 1 : 2;
+  if (L.strength < 1 || L.strength > 16 || (L.bd != 8 && L.bd != 10)) return hipErrorInvalidValue;
+  G.per_seg = 0;
+  G.cut = 27u * ((uint32_t)L.strength << (L.bd - 8)); G.recip = (uint32_t)((1ull << 32) / G.cut) + 1u; G.bin_shift = L.bd - 4;
+  G.partials = nullptr;
+  for (int p = 0; p < 3; p++) {
+    const size_t rb = (size_t)L.plane_w[p] * bps, bytes = rb * (size_t)L.plane_h[p];
+    const bool have = L.plane_w[p] > 0 && L.plane_h[p] > 0;
+    if (bytes > 0x7FFFFFF0u || (rb & 3)) return hipErrorInvalidValue;
+    if (have && (L.true_w[p] < 1 || L.true_h[p] < 1 || L.true_w[p] > L.plane_w[p] || L.true_h[p] > L.plane_h[p] || L.plane_w[p] - L.true_w[p] >= 8 ||
+                 L.plane_h[p] - L.true_h[p] >= 8))
+      return hipErrorInvalidValue;
+    G.dst[p] = L.dst[p]; G.plane_bytes[p] = have ? (uint32_t)bytes : 0; G.row_bytes[p] = (uint32_t)rb; G.rows[p] = L.plane_h[p]; G.w[p] = L.true_w[p]; G.h[p] = L.true_h[p];
+    G.cells[p] = have ? (uint32_t)((rb + 15) >> 4) : 0;
+    if (have && (size_t)(G.cells[p] - 1) * (16 / bps) > (size_t)L.true_w[p] - 1) return hipErrorInvalidValue;      // the last cell starts inside the true width
+    G.groups[p] = (G.cells[p] + 63) / 64;
+    G.items[p] = have ? G.groups[p] * (uint32_t)((L.plane_h[p] + kBand - 1) / kBand) : 0;
+    G.wgs[p] = (G.items[p] + 3) / 4;
+    G.per_seg += G.wgs[p];
+  }
+  if (L.segments > 0 && (size_t)G.per_seg * L.segments > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  return hipSuccess;
+}
+}  // namespace
+
+size_t grain_scratch_bytes(const DenoiseLaunch &L) {
+  GrainGeom G;
+  if (grain_geometry(L, G) != hipSuccess || L.segments <= 0) return 0;
+  return (size_t)G.per_seg * L.segments * 16 * sizeof(av1mi_grain_bin);
+}
+
+hipError_t launch_denoise_gather(const DenoiseLaunch &L, hipStream_t s) {
+  GrainGeom G;
+  if (hipError_t e = grain_geometry(L, G)) return e;
+  if (L.segments <= 0 || !G.per_seg) return hipSuccess;
+  if (L.records && !L.scratch) return hipErrorInvalidValue;
+  G.partials = L.records ? (av1mi_grain_bin *)L.scratch : nullptr;
+  const dim3 grid(G.per_seg * (unsigned)L.segments);
+  if (L.bd == 8) hipLaunchKernelGGL(k_denoise_gather<uint8_t>, grid, dim3(256), 0, s, G, L.table);
+  else hipLaunchKernelGGL(k_denoise_gather<uint16_t>, grid, dim3(256), 0, s, G, L.table);
+  if (hipError_t e = hipGetLastError()) return e;
+  if (L.records) hipLaunchKernelGGL(k_grain_sum, dim3(3u * (unsigned)L.segments), dim3(256), 0, s, G, L.records);
+  return hipGetLastError();
+}
+
+}  // namespace av1mi

@@ -321,7 +321,7 @@ std::vector<uint8_t> sequence_header_obu(const SequenceParams &sp) {   // sequen
   w.put(1, 1);      // enable_cdef
   w.put(1, 1);      // enable_restoration
   write_color_config(w, sp.bit_depth);
-  w.put(0, 1);      // film_grain_params_present
+  w.put(sp.film_grain ? 1 : 0, 1);      // film_grain_params_present
   w.trailing_bits();
   return make_obu(1, w.b);
 }

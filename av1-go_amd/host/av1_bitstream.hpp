@@ -15,7 +15,8 @@
 // DCT/ADST/FLIPADST classes), single-reference inter blocks (LAST) with NEWMV coding against the spec's MV prediction
 // list, regular 8-tap interpolation, deblocking, CDEF (up to 8 strength sets, per-superblock index), loop restoration
 // (Wiener / self-guided / switchable per unit).  Not coded: other block sizes, compound / OBMC / warped motion, palette,
-// intra block copy, filter-intra, segmentation, delta q / lf, quantiser matrices, super-resolution, film grain.
+// intra block copy, filter-intra, segmentation, delta q / lf, quantiser matrices, super-resolution.  Film grain synthesis parameters are written when the frame
+// description carries them (av1mi_obu_frame.film_grain; update_grain = 1 always).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -29,14 +30,15 @@ namespace av1 {
 
 struct SequenceParams {
   int width = 0, height = 0, bit_depth = 8;
-  bool operator==(const SequenceParams &o) const { return width == o.width && height == o.height && bit_depth == o.bit_depth; }
+  bool film_grain = false;      // film_grain_params_present: every frame header of the stream then ends in film_grain_params
+  bool operator==(const SequenceParams &o) const { return width == o.width && height == o.height && bit_depth == o.bit_depth && film_grain == o.film_grain; }
 };
 
 // the size a decoder outputs (av1mi_obu_frame.visible_*: 0 = the coded size) and the sequence header that announces it
 inline int visible_width(const av1mi_obu_frame &f) { return f.visible_width ? f.visible_width : f.width; }
 inline int visible_height(const av1mi_obu_frame &f) { return f.visible_height ? f.visible_height : f.height; }
 inline SequenceParams sequence_params(const av1mi_obu_frame &f) {
-  SequenceParams sp; sp.width = visible_width(f); sp.height = visible_height(f); sp.bit_depth = f.bit_depth;
+  SequenceParams sp; sp.width = visible_width(f); sp.height = visible_height(f); sp.bit_depth = f.bit_depth; sp.film_grain = f.film_grain_present != 0;
   return sp;
 }
 // OBU_TEMPORAL_DELIMITER (spec 5.6)

@@ -289,6 +289,23 @@ inline bool check(const av1mi_obu_frame &f, std::string *err, bool need_symbols 
     if (f.lr_type[p] && !f.lr_units[p]) return bad("restoration units missing");
   }
   if (f.lr_unit_shift < 0 || f.lr_unit_shift > 2 || f.lr_uv_shift < 0 || f.lr_uv_shift > 1) return bad("restoration unit size out of range");
+  if (f.film_grain) {
+    const av1mi_film_grain &g = *f.film_grain;
+    if (!f.film_grain_present) return bad("film_grain given, but the sequence says film_grain_params_present = 0 (av1mi_obu_frame.film_grain_present)");
+    if (g.apply_grain) {
+      auto rising = [](const uint8_t *v, int n) { for (int i = 1; i < n; i++) if (v[i] <= v[i - 1]) return false; return true; };
+      if (g.grain_seed < 0 || g.grain_seed > 65535 || g.num_y_points < 0 || g.num_y_points > 14 || g.num_cb_points < 0 || g.num_cb_points > 10 || g.num_cr_points < 0 ||
+          g.num_cr_points > 10 || g.grain_scaling_minus_8 < 0 || g.grain_scaling_minus_8 > 3 || g.ar_coeff_lag < 0 || g.ar_coeff_lag > 3 || g.ar_coeff_shift_minus_6 < 0 ||
+          g.ar_coeff_shift_minus_6 > 3 || g.grain_scale_shift < 0 || g.grain_scale_shift > 3 || g.cb_mult < 0 || g.cb_mult > 255 || g.cb_luma_mult < 0 ||
+          g.cb_luma_mult > 255 || g.cb_offset < 0 || g.cb_offset > 511 || g.cr_mult < 0 || g.cr_mult > 255 || g.cr_luma_mult < 0 || g.cr_luma_mult > 255 || g.cr_offset < 0 ||
+          g.cr_offset > 511)
+        return bad("film grain parameter out of range");
+      if ((g.num_y_points == 0 || g.chroma_scaling_from_luma) && (g.num_cb_points || g.num_cr_points))
+        return bad("film grain: chroma points without luma points (4:2:0), or beside chroma_scaling_from_luma");
+      if (!rising(g.point_y_value, g.num_y_points) || !rising(g.point_cb_value, g.num_cb_points) || !rising(g.point_cr_value, g.num_cr_points))
+        return bad("film grain: the points of a scaling function must be strictly increasing");
+    }
+  }
   if (!need_symbols) return true;      // header + tile payloads coded elsewhere (frame_obu_from_tiles)
   if (!f.lev_y || !f.lev_u || !f.lev_v) return bad("levels missing");
   if (f.frame_type == 0 && (!f.y_mode || !f.uv_mode)) return bad("key frame without prediction modes");
@@ -333,6 +350,38 @@ inline void write_color_config(BitWriter &w, int bd) {   // color_config (5.5.2)
   w.put(0, 1);          // color_range: studio swing
   w.put(0, 2);          // chroma_sample_position: unknown
   w.put(0, 1);          // separate_uv_delta_q
+}
+
+// film_grain_params (5.9.30) of a shown frame in a 4:2:0 colour sequence; g null = apply_grain 0.  update_grain = 1 always: the
+// parameters are coded in full and no reference frame's are loaded
+inline void write_film_grain_params(BitWriter &w, const av1mi_film_grain *g, bool key) {
+  w.put(g && g->apply_grain ? 1 : 0, 1);          // apply_grain
+  if (!g || !g->apply_grain) return;
+  w.put((uint32_t)g->grain_seed, 16);
+  if (!key) w.put(1, 1);                          // update_grain (inter frames only; elsewhere inferred 1)
+  w.put((uint32_t)g->num_y_points, 4);
+  for (int i = 0; i < g->num_y_points; i++) { w.put(g->point_y_value[i], 8); w.put(g->point_y_scaling[i], 8); }
+  w.put(g->chroma_scaling_from_luma ? 1 : 0, 1);  // (not mono_chrome)
+  const bool chroma_points = !g->chroma_scaling_from_luma && g->num_y_points != 0;      // subsampling 1, 1: no chroma points without luma points
+  const int ncb = chroma_points ? g->num_cb_points : 0, ncr = chroma_points ? g->num_cr_points : 0;
+  if (chroma_points) {
+    w.put((uint32_t)ncb, 4);
+    for (int i = 0; i < ncb; i++) { w.put(g->point_cb_value[i], 8); w.put(g->point_cb_scaling[i], 8); }
+    w.put((uint32_t)ncr, 4);
+    for (int i = 0; i < ncr; i++) { w.put(g->point_cr_value[i], 8); w.put(g->point_cr_scaling[i], 8); }
+  }
+  w.put((uint32_t)g->grain_scaling_minus_8, 2);
+  w.put((uint32_t)g->ar_coeff_lag, 2);
+  const int pos_luma = 2 * g->ar_coeff_lag * (g->ar_coeff_lag + 1), pos_chroma = pos_luma + (g->num_y_points ? 1 : 0);
+  if (g->num_y_points) for (int i = 0; i < pos_luma; i++) w.put(g->ar_coeffs_y_plus_128[i], 8);
+  if (g->chroma_scaling_from_luma || ncb) for (int i = 0; i < pos_chroma; i++) w.put(g->ar_coeffs_cb_plus_128[i], 8);
+  if (g->chroma_scaling_from_luma || ncr) for (int i = 0; i < pos_chroma; i++) w.put(g->ar_coeffs_cr_plus_128[i], 8);
+  w.put((uint32_t)g->ar_coeff_shift_minus_6, 2);
+  w.put((uint32_t)g->grain_scale_shift, 2);
+  if (ncb) { w.put((uint32_t)g->cb_mult, 8); w.put((uint32_t)g->cb_luma_mult, 8); w.put((uint32_t)g->cb_offset, 9); }
+  if (ncr) { w.put((uint32_t)g->cr_mult, 8); w.put((uint32_t)g->cr_luma_mult, 8); w.put((uint32_t)g->cr_offset, 9); }
+  w.put(g->overlap_flag ? 1 : 0, 1);
+  w.put(g->clip_to_restricted_range ? 1 : 0, 1);
 }
 
 inline void write_frame_header(BitWriter &w, const FrameInfo &fi, int tile_size_bytes) {   // uncompressed_header (5.9.2)
@@ -418,7 +467,9 @@ inline void write_frame_header(BitWriter &w, const FrameInfo &fi, int tile_size_
   // skip_mode_params: not allowed without order hints.  allow_warped_motion: off in the sequence
   w.put((uint32_t)(f.reduced_tx_set ? 1 : 0), 1);
   if (!fi.key) for (int i = 0; i < 7; i++) w.put(0, 1);   // global_motion_params (5.9.24): is_global = 0 for LAST..ALTREF
-  // film_grain_params: not present in the sequence
+  // film_grain_params (5.9.30): present iff the sequence says so; show_frame = 1 in every frame this writer makes, so the
+  // (show_frame || showable_frame) condition always holds
+  if (f.film_grain_present) write_film_grain_params(w, f.film_grain, fi.key);
 }
 
 // OBU_FRAME from finished tile payloads (raster order): frame header, tile group with the size prefixes

@@ -18,6 +18,7 @@
 //
 // `segments` closed GOPs of the file are coded in lockstep (the session's batch dimension); while the host codes the
 // symbols of frame t the GPU already works on frames t + 1 and t + 2 (three batches in flight).
+#include "filmgrain.hpp"
 #include "backend.hpp"
 #include <sys/stat.h>
 #include <unistd.h>
@@ -131,9 +132,11 @@ static bool Key32TemporalUnit(const av1mi_gop_frame &fr, int seg, const SessionF
 }
 
 bool SessionTemporalUnit(const av1mi_gop_frame &fr, int seg, int width, int height, int bit_depth, int visible_width, int visible_height,
-                         bool with_sequence_header, int threads, std::vector<uint8_t> *out, std::string *err) {
+                         bool with_sequence_header, int threads, std::vector<uint8_t> *out, std::string *err, bool film_grain_present,
+                         const av1mi_film_grain *film_grain) {
   SessionFrameDesc desc;
   DescribeSessionFrame(fr, seg, width, height, bit_depth, &desc, visible_width, visible_height);
+  desc.f.film_grain_present = film_grain_present; desc.f.film_grain = film_grain;
   std::string werr;
   if (fr.tile_size) {      // tiles coded on the GPU: frame header + tile group around them
     const uint32_t *sz = fr.tile_size + (size_t)seg * fr.tiles_per_frame;
@@ -206,7 +209,10 @@ int RunBackend(const BackendJob &job, std::string *err) {
     }
     cfg.deinterlace = dei;
     // -av1mi_scenecut, or a job that deinterlaces: the frame store holds one group (the deinterlacer's run)
-    const bool analysed = job.scenecut > 0, stored = analysed || dei != 0;
+    // -av1mi_denoise: the same store, the denoiser in the gather; -av1mi_film_grain (1 unless told otherwise): parameters in every frame header
+    cfg.denoise = job.denoise;
+    const bool grainy = job.denoise > 0 && job.film_grain != 0;
+    const bool analysed = job.scenecut > 0, stored = analysed || dei != 0 || job.denoise > 0;
     if (stored) cfg.store_frames = S * G;
     // What the reader threads deliver, one segment's share of the pinned buffers: frames of the coded size (the source's edge replicated
     // into the padding) or, when the GPU scales, of the source size rounded up to 8; no chroma planes for a grey source.  (A config the
@@ -216,7 +222,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
     auto at = [&](void *plane, int p, int i) { return (unsigned char *)plane + fed.plane[p].frame_bytes * (size_t)i; };      // frame i of a pinned plane
     std::vector<std::vector<unsigned char>> scratch(packed ? (size_t)S : 0);          // per reader thread: one planar frame to pack from
     CHK(av1mi_gop_open(ctx, &cfg, &gop));
-    av1::SequenceParams sp; sp.width = tw; sp.height = th; sp.bit_depth = y.bd;
+    av1::SequenceParams sp; sp.width = tw; sp.height = th; sp.bit_depth = y.bd; sp.film_grain = grainy;
     // pixels that stay non-square: the track at least says at which shape to show them
     if (!square) sink.set_display_size((int)((long)tw * y.sar_n / y.sar_d), th);
     for (const std::string &side : job.tracks)
@@ -228,6 +234,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
     // A target (-b:v:0 / -av1mi_target_bpp): the controller lives across the groups.  It is asked at ONE point of the loop (before each
     // submit) and told at one (after each assemble), so the quantisers, and with them the output bytes, are a function of the input alone.
     std::unique_ptr<RateControl> rc;
+    std::vector<std::vector<int>> grains((size_t)S);                   // ... and, denoising, their luma scaling at mid grey (the stats file's grain:)
     std::vector<std::vector<int>> qs((size_t)S);                       // ... and, with a target, their quantisers (the stats file's q:)
     long long rc_bytes = 0, rc_frames = 0;
     if (job.bitrate || job.target_bpp_u) {
@@ -278,6 +285,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
       for (auto &u : units) u.clear();
       for (auto &r : records) r.clear();
       for (auto &v : qs) v.clear();
+      for (auto &v : grains) v.clear();
       // the next GROUP of S GOPs: a file is read in place, a stream one group ahead of the encoder (y4m.hpp)
       long have_frames;
       if (stored && next_frames >= 0) have_frames = next_frames;      // already in the store: it was put while the group before ran
@@ -319,7 +327,13 @@ int RunBackend(const BackendJob &job, std::string *err) {
         for (int s = 0; s < S; s++) {
           if (!exists(s, t)) continue;
           std::vector<uint8_t> tu;
-          if (!SessionTemporalUnit(fr, s, w, h, y.bd, cfg.visible_width, cfg.visible_height, t == 0, threads, &tu, err)) return false;
+          av1mi_film_grain fg;
+          if (job.denoise) {      // what the gather removed from this frame -> the parameters that put it back (none for the ends of a run)
+            if (!fr.grain) { *err = "the session returned no grain records"; return false; }
+            FilmGrainFromRecords(fr.grain + (size_t)s * 3, y.bd, (int)(g0 * G + start[(size_t)s] + t), &fg);
+            grains[(size_t)s].push_back(FilmGrainMidGrey(fg));
+          }
+          if (!SessionTemporalUnit(fr, s, w, h, y.bd, cfg.visible_width, cfg.visible_height, t == 0, threads, &tu, err, grainy, grainy ? &fg : nullptr)) return false;
           batch_bytes += (long long)tu.size();
           if (rc) qs[(size_t)s].push_back(fr.params.base_q_idx);
           units[(size_t)s].push_back(std::move(tu));
@@ -409,6 +423,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
             int n = snprintf(line, sizeof(line), "n:%ld type:%c bytes:%zu", summary.frames, t == 0 ? 'K' : 'P', units[(size_t)s][t].size());
             n += av1mi::quality::format_figures(av1mi::quality::frame_figures(records[(size_t)s][t].q, y.bd), line + n, sizeof(line) - (size_t)n);
             if (rc) n += snprintf(line + n, sizeof(line) - (size_t)n, " q:%d", qs[(size_t)s][t]);
+            if (job.denoise) n += snprintf(line + n, sizeof(line) - (size_t)n, " grain:%d", grains[(size_t)s][t]);
             if (analysed && cut[(size_t)start[(size_t)s] + t]) n += snprintf(line + n, sizeof(line) - (size_t)n, " cut:1");
             stats.append(line, (size_t)n); stats += '\n';
             summary.add(records[(size_t)s][t].q, y.bd);

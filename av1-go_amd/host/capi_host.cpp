@@ -1,6 +1,7 @@
 // capi_host.cpp — extern "C" hooks over the host mirror so that the CPU test-suite (ctypes) can pin it against
 // values read off the reference source.
 #include <cstring>
+#include "filmgrain.hpp"
 #include "daemon.hpp"
 #include "av1_bitstream.hpp"
 #include "mux.hpp"
@@ -246,6 +247,23 @@ long long av1mi_session_temporal_unit(const av1mi_gop_frame *fr, int seg, int wi
   if (err && errcap > 0) { strncpy(err, e.c_str(), errcap - 1); err[errcap - 1] = 0; }
   return -1;
 }
+long long av1mi_session_temporal_unit_grain(const av1mi_gop_frame *fr, int seg, int width, int height, int bit_depth, int visible_width, int visible_height,
+                                            int with_sequence_header, int threads, int film_grain_present, const av1mi_film_grain *film_grain, uint8_t *out,
+                                            long long cap, char *err, int errcap) {
+  std::vector<uint8_t> b; std::string e;
+  if (!fr || seg < 0 || seg >= fr->segments) e = "bad batch / segment";
+  else if (SessionTemporalUnit(*fr, seg, width, height, bit_depth, visible_width, visible_height, with_sequence_header != 0, threads, &b, &e, film_grain_present != 0,
+                               film_grain)) {
+    if ((long long)b.size() <= cap && out) memcpy(out, b.data(), b.size());
+    return (long long)b.size();
+  }
+  if (err && errcap > 0) { strncpy(err, e.c_str(), errcap - 1); err[errcap - 1] = 0; }
+  return -1;
+}
+int av1mi_film_grain_from_records(const av1mi_grain_record *records, int bit_depth, int frame_index, av1mi_film_grain *out) {
+  return FilmGrainFromRecords(records, bit_depth, frame_index, out) ? 0 : -1;
+}
+int av1mi_film_grain_mid_grey(const av1mi_film_grain *g) { return g ? FilmGrainMidGrey(*g) : 0; }
 // The general block description (av1_blockstream.cpp): any block / transform size, any partition
 long long av1mi_obu_write_blocks_temporal_unit(const av1mi_obu_blocks *f, int with_sequence_header, uint8_t *out, long long cap, char *err, int errcap) {
   std::vector<uint8_t> b; std::string e;

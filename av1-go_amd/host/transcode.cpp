@@ -149,6 +149,13 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
       else { if (err) *err = "Invalid argument: -av1mi_deinterlace takes off, auto, tff or bff, not " + v; return false; }
       deint_given = true;
     }
+    else if (args[i] == "-av1mi_denoise") {
+      if (!plain_int(args[i + 1], &job->denoise) || job->denoise > 16) { if (err) *err = "Invalid argument: -av1mi_denoise takes a strength 1 .. 16 (0 = off), not " + args[i + 1]; return false; }
+    }
+    else if (args[i] == "-av1mi_film_grain") {
+      if (args[i + 1] != "0" && args[i + 1] != "1") { if (err) *err = "Invalid argument: -av1mi_film_grain takes 0 or 1, not " + args[i + 1]; return false; }
+      job->film_grain = args[i + 1] == "1";
+    }
     else if (args[i] == "-av1mi_min_gop") {
       if (!plain_int(args[i + 1], &job->min_gop) || job->min_gop < 1 || job->min_gop > 256) { if (err) *err = "Invalid argument: -av1mi_min_gop takes a length in frames (1 .. gop - gop / 2), not " + args[i + 1]; return false; }
     }
@@ -205,6 +212,9 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
   if (job->qmin && job->qmax && job->qmin > job->qmax) { if (err) *err = "Invalid argument: -qmin " + std::to_string(job->qmin) + " above -qmax " + std::to_string(job->qmax); return false; }
   if (job->scenecut && job->pack10) { if (err) *err = "Invalid argument: -av1mi_scenecut keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
   if (job->deinterlace && job->pack10) { if (err) *err = "Invalid argument: -av1mi_deinterlace keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
+  if (job->denoise && job->pack10) { if (err) *err = "Invalid argument: -av1mi_denoise keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
+  if (job->denoise && job->deinterlace) { if (err) *err = "Invalid argument: -av1mi_denoise filters the group's frames on their way from the store, as -av1mi_deinterlace does: not together with -av1mi_deinterlace"; return false; }
+  if (job->film_grain >= 0 && !job->denoise) { if (err) *err = "Invalid argument: -av1mi_film_grain needs -av1mi_denoise"; return false; }
   if (job->min_gop && !job->scenecut) { if (err) *err = "Invalid argument: -av1mi_min_gop needs -av1mi_scenecut"; return false; }
   if (job->min_gop && job->gop >= 1 && job->min_gop > job->gop - job->gop / 2) { if (err) *err = "Invalid argument: -av1mi_min_gop " + std::to_string(job->min_gop) + " above gop - gop / 2 = " + std::to_string(job->gop - job->gop / 2); return false; }
   if (!have_in) { if (err) *err = "Invalid argument: no input (-i) given"; return false; }

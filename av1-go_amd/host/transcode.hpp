@@ -83,6 +83,11 @@ struct BackendJob {
                            // frame per frame), a progressive one is coded as ever, Im is refused (field-rate output and inverse telecine are not
                            // built).  tff / bff force a parity, for sources whose header lies.  A chain that names yadif, bwdif or deinterlace_vaapi
                            // (bare, mode=0 or mode=send_frame) means auto.  The job then runs through the frame store.  Not with -av1mi_pack10 1
+  int denoise = 0;         // -av1mi_denoise N: 0 (default) = off; 1 .. 16 = the strength of the temporal denoiser (include/av1mi.h "denoising",
+                           // av1mi_gop_config.denoise).  The job then runs through the frame store (one group), also without -av1mi_scenecut; the
+                           // first and last frame of a group pass through.  Not with -av1mi_pack10 1, not with -av1mi_deinterlace
+  int film_grain = -1;     // -av1mi_film_grain 0 | 1: with -av1mi_denoise, 1 (the default there) signals film grain synthesis parameters derived from
+                           // what the denoiser removed (host/filmgrain.hpp), 0 codes the clean frames alone; an error without -av1mi_denoise
   int min_gop = 0;         // -av1mi_min_gop M: the shortest GOP the planner makes, 1 .. gop - gop / 2; 0 = max(1, gop / 4).  Only with -av1mi_scenecut
   std::vector<std::string> tracks;   // -av1mi_tracks <file.mka> (repeatable): Matroska side files whose audio / subtitle tracks are copied
                                      // next to the video (the reference's `-c:a copy -c:s copy`, transcode.go:134-137, after an external demux)

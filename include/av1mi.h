@@ -538,6 +538,48 @@ int av1mi_frames_gather(av1mi_ctx *ctx, const size_t plane_bytes[3], int segment
 int av1mi_deinterlace_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int parity,
                              int segments, const void *const *d_table, void *const d_dst[3]);
 
+/* ---- denoising: a temporal filter inside the gather (av1-go_amd/csrc/grain_kernels.hip), the deinterlacer's sibling: it removes what
+ * changes from frame to frame while the picture stands still — film grain, sensor noise — so that the coder does not spend its bits on
+ * it; "grain records" below measure what was removed, and the bitstream asks the decoder to put statistically equal grain back (film
+ * grain synthesis; av1-go_amd/host/filmgrain.hpp).  Integer arithmetic, bit exact by definition; samples of 8 or 10 bits.
+ *   geometry  as "deinterlacing": every plane of the fed layout is filtered on its own at its true size w x h; a run is the frames
+ *             0 .. n - 1 of a store; for frame f: C = frame f, P = frame max(f - 1, 0), N = frame min(f + 1, n - 1).  All coordinates
+ *             clamp to [0, w - 1] x [0, h - 1].  The buffer's sample at (x, y) beyond the true size is the output at (min(x, w - 1),
+ *             min(y, h - 1)): the padding of the output replicates its own edge.  Nothing beyond the true size is read.
+ *   ends      a frame at an end of its run (f = 0 or f = n - 1: P or N is the frame itself) PASSES THROUGH: out = C, and it adds
+ *             nothing to the records.  (Averaging with one neighbour would leave 1/2 of the grain's variance where a middle frame
+ *             leaves 1/3, and the records' model below would not hold; a run of one or two frames is not filtered at all.)
+ *   measure   strength 1 .. 16 in 8-bit code values, T = strength << (bit_depth - 8).  For F in {P, N}:
+ *               D_F(x, y) = the sum over the 3x3 neighbourhood of |C - F|                                   (<= 9 x 1023)
+ *               w_F = max(0, 16 - floor(16 D_F / (27 T))), computed without a division as
+ *               w_F = 16 - ((16 min(D_F, 27 T) R) >> 32),  R = floor(2^32 / (27 T)) + 1                     (a 32 x 32 -> high 32 product)
+ *             which is the same number for every D_F and T (16 D R < 2^63; the error of R, below 16 x 27 T / 2^32, cannot reach the
+ *             next multiple of 1 / (27 T)).  A mean absolute difference of 3 T / 16 costs one step of weight; at 3 T the weight is 0.
+ *   output    den = 16 + w_P + w_N (16 .. 48), num = 16 C + w_P P + w_N N, out = (num K[den] + 2^15) >> 16 with K[den] = round(65536 / den):
+ *               K[16 .. 48] = 4096 3855 3641 3449 3277 3121 2979 2849 2731 2621 2521 2427 2341 2260 2185 2114 2048 1986 1928 1872 1820
+ *                             1771 1725 1680 1638 1598 1560 1524 1489 1456 1425 1394 1365
+ *             This IS the definition, not an approximation of a division.  |den K[den] - 65536| <= 20, so equal samples v <= 1023 give
+ *             v back (the error is below 1023 x 20 / 65536 < 1/2): a still, clean picture comes out unchanged, and a sample whose
+ *             neighbourhood moved (both weights 0) keeps C exactly.  With 12-bit samples neither would hold: not accepted.
+ * ---- grain records: what the filter removed, by intensity.  Per (segment, plane) of a batch a record of 16 bins; a sample of a middle
+ * frame of a run inside the true size is COUNTED iff w_P + w_N >= 24 (at least half of the possible weight: its neighbourhood stood
+ * still, so r is grain and not motion) and goes to bin out >> (bit_depth - 4), the OUTPUT sample's top four bits, with r = C - out:
+ *   sum_sq += r^2, count += 1.
+ * All integers: per-workgroup partials in scratch, then one sum per (segment, plane); no floating point, and integer addition gives the
+ * same bytes in any order, run to run.  A flat slot and the ends of a run have all-zero records. */
+#define AV1MI_GRAIN_BINS 16
+typedef struct av1mi_grain_bin { uint64_t sum_sq; uint32_t count, reserved; } av1mi_grain_bin;
+typedef struct av1mi_grain_record { av1mi_grain_bin bin[AV1MI_GRAIN_BINS]; } av1mi_grain_record;
+/* The gather with the denoiser in it: av1mi_deinterlace_gather's arguments and rules (the table of P, C, N per segment and plane with the
+ * run's clamping applied by whoever fills it — an entry P or N EQUAL to C marks an end of the run; a null C makes the slot flat), with
+ * strength 1 .. 16 in place of the parity, bit_depth 8 or 10, and the last 16-byte cell of every row starting inside the true width
+ * (true of every buffer that is its true size rounded up to 8 in luma terms).  d_records: segments * 3 records [segment * 3 + plane]
+ * in device memory (or pinned host memory), 8-byte aligned, written by a second launch (k_grain_sum); NULL = nothing is measured and
+ * only k_denoise_gather is launched.  The partials live in the context (grown on demand).  Asynchronous on the context's stream;
+ * AV1MI_K_SCENE in the profile, like the gathers it stands in for. */
+int av1mi_denoise_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int strength,
+                         int segments, const void *const *d_table, void *const d_dst[3], av1mi_grain_record *d_records);
+
 /* ---- GOP session: the encoder object a cgo replacement of RunTranscode drives (reference call site
  * internal/daemon/daemon.go:101 -> internal/ffmpeg/transcode.go:194; SURVEY.md §8b "av1mi_open(config) / av1mi_encode /
  * av1mi_flush").  It owns the closed-GOP orchestration and the encoder's filter-parameter POLICY, so that no caller
@@ -630,6 +672,14 @@ typedef struct av1mi_gop_config {
    * av1mi_gop_store_analyse keeps reading the frames AS FED: averaging 4x4 samples blends the two fields, so cuts are found as before.
    * av1mi_gop_submit_device does not deinterlace. */
   int deinterlace;
+  /* Denoising (0 = none: nothing new is allocated, launched or accepted; 1 .. 16 = the strength; "denoising" above).  Needs
+   * store_frames > 0, like deinterlace and for the same reason; fed samples of 8 or 10 bits; refused together with deinterlace (the
+   * chain of the two needs a third copy of a group: DESIGN section 7).  av1mi_gop_submit_stored then launches k_denoise_gather in place
+   * of k_frames_gather, with the deinterlacer's table of P, C, N and its run: the slot's fed buffers receive the filtered frames, the
+   * first and the last frame of a run pass through, and av1mi_gop_frame.grain carries the batch's grain records.  Everything behind the
+   * fed buffers is untouched (the quality records are measured against the denoised frame); av1mi_gop_store_analyse keeps reading the
+   * frames as fed; av1mi_gop_submit_device does not denoise. */
+  int denoise;
 } av1mi_gop_config;
 
 /* The source layout: what a session opened with a config is FED, as one description.  Everything a caller sizes or strides by — the
@@ -695,6 +745,9 @@ typedef struct av1mi_gop_frame {    /* one collected frame batch; host pointers 
   /* av1mi_gop_config.quality_stats: segments * 3 records [segment * 3 + plane] of this batch (source against the decoded picture, over
    * the true frame size), in pinned memory; NULL when the option is off */
   const av1mi_quality *quality;
+  /* av1mi_gop_config.denoise: segments * 3 grain records [segment * 3 + plane] of this batch ("grain records"), in pinned memory; NULL
+   * when the option is off (and for a batch of av1mi_gop_submit_device) */
+  const av1mi_grain_record *grain;
 } av1mi_gop_frame;
 
 typedef struct av1mi_gop av1mi_gop;

@@ -22,6 +22,26 @@
 extern "C" {
 #endif
 
+/* Film grain synthesis parameters of one frame: the fields of film_grain_params (AV1 spec 5.9.30, semantics 6.8.20) the writer codes,
+ * with update_grain = 1 always (no reference's parameters are loaded).  av1mi_film_grain_from_records (av1-go_amd/host/filmgrain.hpp)
+ * fills one from a frame's grain records (include/av1mi.h "grain records"); any legal set may be given. */
+typedef struct av1mi_film_grain {
+  int32_t apply_grain;             /* 0: the frame gets no grain, nothing else is coded */
+  int32_t grain_seed;              /* 0 .. 65535 */
+  int32_t num_y_points;            /* 0 .. 14 points of the luma scaling function, values strictly increasing */
+  uint8_t point_y_value[14], point_y_scaling[14];
+  int32_t chroma_scaling_from_luma;
+  int32_t num_cb_points, num_cr_points;      /* 0 .. 10; must be 0 when num_y_points is 0 (4:2:0) or chroma_scaling_from_luma is set */
+  uint8_t point_cb_value[10], point_cb_scaling[10], point_cr_value[10], point_cr_scaling[10];
+  int32_t grain_scaling_minus_8;   /* 0 .. 3 */
+  int32_t ar_coeff_lag;            /* 0 .. 3 */
+  uint8_t ar_coeffs_y_plus_128[24], ar_coeffs_cb_plus_128[25], ar_coeffs_cr_plus_128[25];
+  int32_t ar_coeff_shift_minus_6, grain_scale_shift;      /* 0 .. 3 each */
+  int32_t cb_mult, cb_luma_mult, cb_offset;               /* 8, 8 and 9 bits */
+  int32_t cr_mult, cr_luma_mult, cr_offset;
+  int32_t overlap_flag, clip_to_restricted_range;
+} av1mi_film_grain;
+
 /* Frame description for the bitstream writer.  All block arrays are raster order over the (width/8) x (height/8) grid of
  * 8x8 luma blocks; host pointers.  The tool set that can be described is listed in av1-go_amd/host/av1_bitstream.hpp. */
 /* Frame description (plain C: also bound from Python through libav1mi_host.so, and by the cgo shim of INTEGRATION.md). */
@@ -61,6 +81,12 @@ typedef struct av1mi_obu_frame {
    * header; coded - visible < 8.  0 = same as width / height.  What the encoder loop must do for such a frame so that a decoder
    * reconstructs the same pictures: av1mi.h, av1mi_gop_config.visible_width. */
   int32_t visible_width, visible_height;
+  /* Film grain.  film_grain_present says what the stream's SEQUENCE header says (film_grain_params_present; one value for all frames of a
+   * stream): when set, every frame header ends in film_grain_params, written from *film_grain, or as apply_grain = 0 where film_grain is
+   * NULL.  A film_grain pointer in a frame whose sequence flag is off is refused.  Both 0 / NULL (the default): every byte is what it
+   * was before the fields existed. */
+  int32_t film_grain_present;
+  const av1mi_film_grain *film_grain;
 } av1mi_obu_frame;
 
 /* One temporal unit: temporal delimiter [+ sequence header] + OBU_FRAME.  threads > 1 codes the tiles on that many host
@@ -83,6 +109,8 @@ long long av1mi_obu_assemble_temporal_unit(const av1mi_obu_frame *f, const uint8
 long long av1mi_session_temporal_unit(const av1mi_gop_frame *fr, int seg, int width, int height, int bit_depth, int visible_width,
                                       int visible_height, int with_sequence_header, int threads, uint8_t *out, long long cap, char *err,
                                       int errcap);
+
+/* av1mi_session_temporal_unit_grain (include/av1mi_filmgrain.h) is this entry with film grain parameters. */
 
 /* ---- general block structure: every AV1 block size 4x4 .. 64x64 (incl. the 1:2 / 2:1 / 1:4 / 4:1 shapes), every partition type,
  * every transform size (TX_MODE_LARGEST or TX_MODE_SELECT) and all 16 transform types, the four interpolation filters.  It is
@@ -135,6 +163,9 @@ long long av1mi_obu_write_blocks_temporal_unit(const av1mi_obu_blocks *f, int wi
  * "-i <input.y4m>", "-global_quality:v:0 <q>" and the output path (last argument), plus its own "-g", "-av1mi_device",
  * "-av1mi_segments", "-av1mi_gpu_entropy", "-av1mi_key_block_size", "-av1mi_tracks", "-threads", "-av1mi_scale WxH"; "-vf:v:0 <chain>"
  * is evaluated on the source (its scale filters are applied on the GPU, a filter that cannot be applied is an error: INTEGRATION.md §1);
+ * "-av1mi_denoise N" (0 = default: off; 1 .. 16 = the strength of the temporal denoiser in the gather, include/av1mi.h "denoising"; the job
+ * runs through the frame store; not with -av1mi_pack10 1 or -av1mi_deinterlace), "-av1mi_film_grain 0 | 1" (1 by default when denoising:
+ * film grain synthesis parameters from what was removed, av1mi_filmgrain.h; an error without -av1mi_denoise);
  * "-av1mi_deinterlace off | auto | tff | bff" (off = default; auto deinterlaces a source whose Y4M header says It / Ib on the GPU, at the
  * same frame rate, and refuses Im; a chain that names yadif, bwdif or deinterlace_vaapi — bare, mode=0 or mode=send_frame — means auto;
  * include/av1mi.h "deinterlacing", av1mi_gop_config.deinterlace);
