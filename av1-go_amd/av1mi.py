@@ -91,7 +91,8 @@ class GopConfig(C.Structure):
                 ("segments", C.c_int), ("search_range", C.c_int), ("gpu_entropy", C.c_int), ("visible_width", C.c_int),
                 ("visible_height", C.c_int), ("coder_streams", C.c_int), ("key_block_size", C.c_int), ("input_format", C.c_int), ("source_width", C.c_int),
                 ("source_height", C.c_int), ("quality_stats", C.c_int), ("coarse_range", C.c_int), ("source_chroma", C.c_int),
-                ("source_bit_depth", C.c_int), ("store_frames", C.c_int), ("deinterlace", C.c_int), ("denoise", C.c_int)]
+                ("source_bit_depth", C.c_int), ("store_frames", C.c_int), ("deinterlace", C.c_int), ("denoise", C.c_int),
+                ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int), ("crop_height", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -122,6 +123,7 @@ def policy_frame_params(base_q_idx, bit_depth, frame_type):
 GRAIN_BINS = 16      # AV1MI_GRAIN_BINS; a record (av1mi_grain_record) is that many bins
 GRAIN_DTYPE = np.dtype([("sum_sq", "<u8"), ("count", "<u4"), ("reserved", "<u4")])      # av1mi_grain_bin
 SCENE_DTYPE = np.dtype([("inter_sad", "<u8"), ("intra_sad", "<u8"), ("blocks", "<u4"), ("reserved", "<u4")])
+CROP_DTYPE = np.dtype([("top", "<u4"), ("bottom", "<u4"), ("left", "<u4"), ("right", "<u4")])      # av1mi_crop_record ("bar detection")
 assert SCENE_DTYPE.itemsize == 24
 QUALITY_DTYPE = np.dtype([("sse", "<u8"), ("ssim_sum", "<f8"), ("samples", "<u4"), ("windows", "<u4")])
 assert QUALITY_DTYPE.itemsize == 24
@@ -229,7 +231,7 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
@@ -243,7 +245,9 @@ class GopSession:
         deinterlace: 0 none, 1 top field first, 2 bottom field first (av1mi_gop_config.deinterlace; needs store_frames): submit_stored()
         gathers through the deinterlacer;
         denoise: 1 .. 16, the strength of the temporal denoiser (av1mi_gop_config.denoise; needs store_frames, not with deinterlace):
-        submit_stored() gathers through it and collect()["grain"] holds the grain records.  None leaves the field unset (0 = none)"""
+        submit_stored() gathers through it and collect()["grain"] holds the grain records.  None leaves the field unset (0 = none);
+        crop: (x, y, width, height), the window of the fed frames that is coded (av1mi_gop_config.crop_*; needs source, the fed frames'
+        true size): width x height (or visible) is the target the window is copied or scaled to"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
         sw, sh = source if source is not None else (0, 0)
@@ -251,6 +255,8 @@ class GopSession:
                              sw, sh, int(quality_stats), int(coarse_range), int(source_chroma), int(source_bit_depth), int(store_frames), int(deinterlace))
         if denoise is not None:
             self.cfg.denoise = int(denoise)
+        if crop is not None:
+            self.cfg.crop_x, self.cfg.crop_y, self.cfg.crop_width, self.cfg.crop_height = (int(v) for v in crop)
         self.g = C.c_void_p()
         ctx.lib.av1mi_gop_open.argtypes = [C.c_void_p, C.POINTER(GopConfig), C.POINTER(C.c_void_p)]
         ctx._chk(ctx.lib.av1mi_gop_open(ctx.h, C.byref(self.cfg), C.byref(self.g)))
@@ -617,6 +623,20 @@ class Context:
         dst = (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_dst])
         self._chk(self.lib.av1mi_deinterlace_gather(self.h, int(bit_depth), arr([s[0] for s in plane_sizes]), arr([s[1] for s in plane_sizes]),
                                                     arr([s[0] for s in true_sizes]), arr([s[1] for s in true_sizes]), int(parity), int(segments), d_table.ptr, dst))
+
+    def crop_analyse(self, Y, bit_depth, true_size, limit=24):
+        """the margins (CROP_DTYPE [frames]) of luma planes Y [frames, H8, W8], H8 and W8 multiples of 8, whose picture is true_size =
+        (width, height) (av1mi_crop_analyse): the dark rows / columns at every edge, `limit` the mean 8-bit level up to which a line is dark"""
+        Y = np.ascontiguousarray(Y, np.uint8 if bit_depth == 8 else np.uint16)
+        n, h, w = Y.shape
+        self.lib.av1mi_crop_analyse.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p]
+        d_y, d_out = self.to_device(Y), self.alloc(n * CROP_DTYPE.itemsize)
+        try:
+            self._chk(self.lib.av1mi_crop_analyse(self.h, int(bit_depth), w, h, int(true_size[0]), int(true_size[1]), n, d_y.ptr, int(limit), d_out.ptr))
+            return d_out.download((n,), CROP_DTYPE)
+        finally:
+            d_y.free()
+            d_out.free()
 
     def denoise_gather(self, bit_depth, plane_sizes, true_sizes, strength, segments, d_table, d_dst, d_records=None):
         """the gather with the denoiser in it (av1mi_denoise_gather): deinterlace_gather's arguments with a strength (1 .. 16) in place of

@@ -151,13 +151,32 @@ hipError_t launch_inter_pipe(const InterLaunch &L, hipStream_t s);
 
 // the resampler of the input stage (scale_kernels.hip): a plan holds the device tables of one geometry (true luma size of the source ->
 // target luma size, both buffers at their sizes rounded up to 8); one launch scales the three planes of `frames` stacked frames
+// A crop window (include/av1mi.h "crop window"): the rectangle (x, y, w, h), all even, of planar 4:2:0 frames of TRUE luma size frame_w x
+// frame_h (their buffers: that rounded up to 8).  The chroma planes' window is the half of every number.
+struct CropWindow { int x, y, w, h, frame_w, frame_h; };
 struct ScalePlan;
-hipError_t scale_plan_create(int bd, int sw, int sh, int dw, int dh, ScalePlan **out);      // synchronous (allocates, uploads)
+// window != null: sw x sh is the WINDOW's size and the source planes are the frames it lies in: the plan reads from the window's origin
+// with the frames' strides, and clamps at the window's edges
+hipError_t scale_plan_create(int bd, int sw, int sh, int dw, int dh, ScalePlan **out, const CropWindow *window = nullptr);      // synchronous (allocates, uploads)
 void scale_plan_destroy(ScalePlan *P);
 bool scale_plan_is(const ScalePlan *P, int bd, int sw, int sh, int dw, int dh);
 hipError_t launch_scale(const ScalePlan *P, int frames, const void *const *src, void *const *dst, hipStream_t s);
 // the argument rules shared by av1mi_scale_planes and the session: null = fine, else the reason
 const char *scale_geometry_error(int sw, int sh, int dw, int dh);
+
+// the window alone, nothing resampled (crop_kernels.hip, k_crop_copy): the window of `frames` stacked frames -> the coded planes of dst_w x
+// dst_h luma samples (the window's size rounded up to 8; the window's last column / row replicated into the padding).  ONE launch
+hipError_t launch_crop_copy(const CropWindow &W, int bd, int dst_w, int dst_h, int frames, const void *const *src, void *const *dst, hipStream_t s);
+// bar detection (crop_kernels.hip, include/av1mi.h "bar detection"): `frames` stacked luma planes of TRUE size w x h in buffers of stride x
+// rows samples -> one record of margins per frame, two launches.  scratch: crop_layout().bytes bytes, 4-byte aligned: a partial per
+// (row, tile column) at 0, a partial per (tile row, column) at off_cols
+struct CropLayout { int tiles_x, tiles_y; size_t off_cols, bytes; };
+CropLayout crop_layout(int bd, int w, int h, int frames);
+struct CropAnalyseLaunch {
+  int bd, stride, rows, w, h, frames, limit;
+  const void *luma; void *scratch; av1mi_crop_record *out;
+};
+hipError_t launch_crop_analyse(const CropAnalyseLaunch &A, hipStream_t s);
 
 // the quality records (quality_kernels.hip): source against the decoded picture, three planes of `frames` stacked frames of TRUE luma
 // size w x h in buffers of that size rounded up to 8; two launches (tiles, then a fixed-order sum per frame and plane).  dec1 / sel

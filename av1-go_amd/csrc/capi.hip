@@ -28,6 +28,8 @@ struct av1mi_ctx {
   size_t me_scratch_bytes = 0;
   void *scene_scratch = nullptr;          // av1mi_scene_analyse: quarter planes + block results (grown on demand)
   size_t scene_scratch_bytes = 0;
+  void *crop_scratch = nullptr;           // av1mi_crop_analyse: the partial row / column sums (grown on demand)
+  size_t crop_scratch_bytes = 0;
   void *grain_scratch = nullptr;          // av1mi_denoise_gather: the workgroups' partial records (grown on demand)
   size_t grain_scratch_bytes = 0;
   // per-kernel profile: one event pair per launch while enabled
@@ -188,6 +190,7 @@ void av1mi_close(av1mi_ctx *ctx) {
   if (ctx->quality_scratch) (void)hipFree(ctx->quality_scratch);
   if (ctx->me_scratch) (void)hipFree(ctx->me_scratch);
   if (ctx->scene_scratch) (void)hipFree(ctx->scene_scratch);
+  if (ctx->crop_scratch) (void)hipFree(ctx->crop_scratch);
   if (ctx->grain_scratch) (void)hipFree(ctx->grain_scratch);
   if (ctx->av1ent) av1mi::av1ent_free(ctx->av1ent);
   av1mi::scale_plan_destroy(ctx->scale_plan);
@@ -614,6 +617,32 @@ int av1mi_scene_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, in
   S.bd = bit_depth; S.w = width; S.h = height; S.frames = frames; S.luma = d_luma; S.scratch = ctx->scene_scratch; S.out = d_records;
   ProfScope ps(ctx, AV1MI_K_SCENE);
   HIP_TRY(ctx, av1mi::launch_scene(S, ctx->stream));
+  return AV1MI_OK;
+}
+
+int av1mi_crop_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int true_width, int true_height, int frames, const void *d_luma, int limit,
+                       av1mi_crop_record *d_records) {
+  BIND(ctx);
+  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return fail(ctx, AV1MI_E_INVAL, "av1mi_crop_analyse: bit depth %d not supported (8, 10 or 12)", bit_depth);
+  if (width < 8 || height < 8 || (width & 7) || (height & 7) || width > 16384 || height > 16384)
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_crop_analyse: the planes' size %dx%d must be a multiple of 8 (8 .. 16384)", width, height);
+  if (true_width < 1 || true_width > width || width - true_width >= 8 || true_height < 1 || true_height > height || height - true_height >= 8)
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_crop_analyse: the true size %dx%d must lie within 7 samples below the planes' size %dx%d", true_width, true_height, width, height);
+  if (frames < 1 || frames > 65535) return fail(ctx, AV1MI_E_INVAL, "av1mi_crop_analyse: frames %d out of range (1 .. 65535)", frames);
+  if (limit < 0 || limit > 255) return fail(ctx, AV1MI_E_INVAL, "av1mi_crop_analyse: limit %d out of range (0 .. 255)", limit);
+  if (!d_luma || !d_records || ((uintptr_t)d_luma & 15) || ((uintptr_t)d_records & 3)) return fail(ctx, AV1MI_E_INVAL, "av1mi_crop_analyse: null or misaligned device pointer (planes 16 bytes, records 4)");
+  const size_t need = av1mi::crop_layout(bit_depth, true_width, true_height, frames).bytes;
+  if (ctx->crop_scratch_bytes < need) {      // (hipFree waits for the launches that still read the old one)
+    if (ctx->crop_scratch) (void)hipFree(ctx->crop_scratch);
+    ctx->crop_scratch = nullptr; ctx->crop_scratch_bytes = 0;
+    HIP_TRY(ctx, hipMalloc(&ctx->crop_scratch, need));
+    ctx->crop_scratch_bytes = need;
+  }
+  av1mi::CropAnalyseLaunch A;
+  A.bd = bit_depth; A.stride = width; A.rows = height; A.w = true_width; A.h = true_height; A.frames = frames; A.limit = limit;
+  A.luma = d_luma; A.scratch = ctx->crop_scratch; A.out = d_records;
+  ProfScope ps(ctx, AV1MI_K_SCENE);
+  HIP_TRY(ctx, av1mi::launch_crop_analyse(A, ctx->stream));
   return AV1MI_OK;
 }
 

@@ -9,7 +9,7 @@
 //                     -> store.read_done, in place of the upload; the input stages follow as below.  A session that deinterlaces
 //                     (av1mi_gop_config.deinterlace) launches k_deint_gather in its place: same events, and the store is only read)
 //                     up:   wait slot.filters_done (the kernels that last read this slot's source) -> H2D of the fed buffers -> uploaded
-//                     main: wait uploaded -> [k_input_convert] -> [k_chroma_convert] -> [k_scale]
+//                     main: wait uploaded -> [k_input_convert] -> [k_chroma_convert] -> [k_scale | k_crop_copy]
 //   code_blocks       main: k_intra_pipe | [k_me_down + k_me_coarse] + k_me_int + k_inter_pipe -> kernel_done
 //   download_symbols  down: wait kernel_done -> D2H of the symbols into pinned memory
 //   loop_filters      main: deblock x3, CDEF, LR x3 + decision -> reference -> filters_done;  down: the decision -> downloaded
@@ -30,6 +30,11 @@
 //   chroma   a source that is not 4:2:0 at bit_depth (planar only): k_chroma_convert, fed layout -> planar 4:2:0 at the fed size.
 //            Where the depths are equal it passes the luma plane THROUGH: the plane stays in the buffer it is in;  then
 //   scale    source_width given: the resampler (scale_kernels.hip), fed size -> coded size.
+// The crop window (av1mi_gop_config.crop_*) is NOT a stage of its own and adds no plane: it is handed to the last stage as an origin
+// and the fed planes' stride.  Where the window is resampled that stage is `scale`, whose plan then reads from the window's origin and
+// clamps at the window's edges; where the window's size is the target, `crop` (k_crop_copy, crop_kernels.hip) takes scale's place and
+// copies the window, replicating its last column / row into the coded planes' padding.  Either way the chain stays at most two stages
+// (convert | chroma, then scale | crop) with d_pre between them, and a session without a window builds exactly the chain it always did.
 // slot_buffers() walks the chain once per slot and plane: the last stage that writes a plane writes d_src, a stage before it a plane
 // between (d_pre), and a plane that no stage writes IS d_src from the start (all planes with ZERO stages, the luma plane behind chroma
 // alone): the upload lands where the kernels read.  feed_source() walks it once per batch.
@@ -146,6 +151,8 @@ struct av1mi_gop {
   int stages = 0, chain[kMaxStages] = {};      // the input stages in launch order (Stage)
   uintptr_t fed_align = 8;                     // of the planes av1mi_gop_submit_device is given: 16 where convert or chroma reads them (16-byte loads)
   av1mi::ScalePlan *scale = nullptr;           // scaling sessions: the resampler's tables
+  bool cropping = false;                       // cfg.crop_*: the window, handed to the scale stage's plan or to the crop stage
+  av1mi::CropWindow window{};
   hipStream_t up = nullptr, down = nullptr;     // with the context's main and side streams: four, one hardware queue each
   Slot slot[kSlots];
   void *d_rec[3] = {}, *d_dbl[3] = {}, *d_cdef[3] = {}, *d_ref[3] = {};
@@ -203,7 +210,7 @@ int host_alloc(av1mi_gop *g, void **p, size_t bytes) {
   return AV1MI_OK;
 }
 
-enum Stage { kConvert, kChroma, kScale };      // the input stages (the chain of "The source path")
+enum Stage { kConvert, kChroma, kScale, kCrop };      // the input stages (the chain of "The source path"); kCrop stands where kScale would
 // Does stage k write plane p?  All do but chroma at equal depths, which passes the luma plane through
 bool stage_writes(const av1mi_gop *g, int k, int p) { return !(g->chain[k] == kChroma && p == 0 && g->layout.bit_depth == g->cfg.bit_depth); }
 size_t fed_bytes(const av1mi_gop *g, int p) { return g->layout.plane[p].frame_bytes * (size_t)g->cfg.segments; }      // plane p of a batch as fed
@@ -350,10 +357,23 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
                c->source_bit_depth, c->input_format);
   if ((c->source_width != 0) != (c->source_height != 0) || c->source_width < 0 || c->source_height < 0)
     return WHY("source size %dx%d: give both source_width and source_height, or neither", c->source_width, c->source_height);
-  if (c->source_width) {
+  const bool crop = c->crop_x || c->crop_y || c->crop_width || c->crop_height;
+  if (crop) {
+    const int x = c->crop_x, y = c->crop_y, cw = c->crop_width, ch = c->crop_height;
+    if (!c->source_width) return WHY("crop window %dx%d+%d+%d: a session with a window is fed whole frames, give their true size as source_width x source_height", cw, ch, x, y);
+    if (c->source_width < 16 || c->source_height < 16 || c->source_width > 16384 || c->source_height > 16384)
+      return WHY("crop window: source size %dx%d out of range (16 .. 16384)", c->source_width, c->source_height);
+    if (x < 0 || y < 0 || cw < 0 || ch < 0 || ((x | y | cw | ch) & 1)) return WHY("crop window %dx%d+%d+%d: the four numbers must be even and not negative", cw, ch, x, y);
+    if (cw < 16 || ch < 16) return WHY("crop window %dx%d+%d+%d: smaller than 16x16", cw, ch, x, y);
+    if (x > c->source_width - cw || y > c->source_height - ch)
+      return WHY("crop window %dx%d+%d+%d lies outside the source's true size %dx%d", cw, ch, x, y, c->source_width, c->source_height);
+  }
+  if (c->source_width) {      // what is resampled: the window, or the whole fed frame; a window of the target's size is copied
     const int tw = c->visible_width ? c->visible_width : c->width, th = c->visible_height ? c->visible_height : c->height;
-    if (const char *why = av1mi::scale_geometry_error(c->source_width, c->source_height, tw, th))
-      return WHY("source size %dx%d -> %dx%d: %s", c->source_width, c->source_height, tw, th, why);
+    const int sw = crop ? c->crop_width : c->source_width, sh = crop ? c->crop_height : c->source_height;
+    if (!(crop && sw == tw && sh == th))
+      if (const char *why = av1mi::scale_geometry_error(sw, sh, tw, th))
+        return WHY("%s %dx%d -> %dx%d: %s", crop ? "crop window" : "source size", sw, sh, tw, th, why);
   }
   if (c->key_block_size != 0 && c->key_block_size != 8 && c->key_block_size != 32) return WHY("key_block_size %d not supported (8 or 32)", c->key_block_size);
   if (c->key_block_size == 32 && (c->width & 31))
@@ -393,7 +413,10 @@ int setup(av1mi_gop *g) {
   // the chain (config_error: never convert AND chroma)
   if (c.input_format != AV1MI_INPUT_PLANAR) { g->chain[g->stages++] = kConvert; g->fed_align = 16; }
   if (c.source_chroma != AV1MI_CHROMA_420 || g->layout.bit_depth != c.bit_depth) { g->chain[g->stages++] = kChroma; g->fed_align = 16; }
-  if (c.source_width) g->chain[g->stages++] = kScale;
+  g->cropping = c.crop_width != 0;
+  if (g->cropping) g->window = { c.crop_x, c.crop_y, c.crop_width, c.crop_height, c.source_width, c.source_height };
+  const bool copy = g->cropping && c.crop_width == g->vw && c.crop_height == g->vh;      // a window of the target's size: nothing to resample
+  if (c.source_width) g->chain[g->stages++] = copy ? kCrop : kScale;
   if (c.gpu_entropy) {
     g->tiles = ((w + 63) / 64) * ((h + 63) / 64);
     // the size of the batch's frames as packed 4:2:0 samples: a frame codes to several times less at any sane quantiser, and to about
@@ -401,7 +424,9 @@ int setup(av1mi_gop *g) {
     g->ent_cap = (size_t)w * h * S * 3 * c.bit_depth / 16;
   }
   G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
-  if (c.source_width) G_HIP(av1mi::scale_plan_create(c.bit_depth, c.source_width, c.source_height, g->vw, g->vh, &g->scale));
+  if (c.source_width && !copy)
+    G_HIP(g->cropping ? av1mi::scale_plan_create(c.bit_depth, c.crop_width, c.crop_height, g->vw, g->vh, &g->scale, &g->window)
+                      : av1mi::scale_plan_create(c.bit_depth, c.source_width, c.source_height, g->vw, g->vh, &g->scale));
   G_HIP(hipStreamCreateWithFlags(&g->up, hipStreamNonBlocking));
   // (created in every mode, used only where symbols go to the host at submit time or a batch falls back.  HIP deals its four
   // default hardware queues to streams in creation order: main, up, down, side — and the coder's back stream, the fifth, shares
@@ -593,6 +618,8 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
       for (int p = 0; p < 3; p++) { L.in[p] = src[p]; L.out[p] = out[p]; }
       L.chroma = c.source_chroma; L.src_bd = Y.bit_depth; L.bd = c.bit_depth; L.frames = S; L.w = Y.true_width; L.h = Y.true_height;
       G_HIP(av1mi::launch_chroma_convert(L, main));
+    } else if (g->chain[k] == kCrop) {
+      G_HIP(av1mi::launch_crop_copy(g->window, c.bit_depth, c.width, c.height, S, src, out, main));
     } else G_HIP(av1mi::launch_scale(g->scale, S, src, out, main));
     for (int p = 0; p < 3; p++) if (out[p]) src[p] = out[p];      // (a plane that passes through stays where it was fed: the caller's, in a device batch)
   }

@@ -36,7 +36,8 @@ struct ScalePlaneDesc {      // 16 ints per plane at the head of the table
   int src_stride, src_rows;  // its buffer: samples per row, rows per frame
   int dst_w, dst_h;          // coded size of the destination plane (= its stride and rows per frame)
   int taps_h, taps_v;
-  int tiles_x, tiles_y, reserved[2];
+  int tiles_x, tiles_y;
+  int origin, reserved;      // a crop window: where it starts in the source plane (y * src_stride + x samples; src_w x src_h is then the window)
   int first_h, coef_h, first_v, coef_v;      // dword offsets into the table
 };
 static_assert(sizeof(ScalePlaneDesc) == 64, "table layout");
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(256) void k_scale(ScaleLaunch L) {
     const int ncx = (nx + 7) >> 3;
     for (int c = tid; c < ny * ncx; c += 256) {
       const int row = c / ncx, cx = c - row * ncx, sx = x0 + 8 * cx;
-      const Pix *rp = src + (size_t)(f * d.src_rows + min(max(y0 + row, 0), d.src_h - 1)) * d.src_stride;
+      const Pix *rp = src + d.origin + (size_t)(f * d.src_rows + min(max(y0 + row, 0), d.src_h - 1)) * d.src_stride;
       uint32_t o[4];
       if (sx >= 0 && sx + 7 < d.src_w) {
         widen8<Pix>(rp + sx, o);
@@ -255,12 +256,13 @@ void scale_plan_destroy(ScalePlan *P) {
 
 // sw x sh: the true luma size of the source (its buffers are that rounded up to 8); dw x dh: the target luma size (the destination
 // planes are that rounded up to 8).  Sizes and ratios are checked by the callers.
-hipError_t scale_plan_create(int bd, int sw, int sh, int dw, int dh, ScalePlan **out) {
+hipError_t scale_plan_create(int bd, int sw, int sh, int dw, int dh, ScalePlan **out, const CropWindow *window) {
   *out = nullptr;
   ScalePlan *P = new (std::nothrow) ScalePlan();
   if (!P) return hipErrorOutOfMemory;
   P->bd = bd; P->sw = sw; P->sh = sh; P->dw = dw; P->dh = dh;
-  const int sw8 = (sw + 7) & ~7, sh8 = (sh + 7) & ~7, cw = (dw + 7) & ~7, ch = (dh + 7) & ~7;
+  // (a window: the strides are those of the frames it lies in)
+  const int sw8 = ((window ? window->frame_w : sw) + 7) & ~7, sh8 = ((window ? window->frame_h : sh) + 7) & ~7, cw = (dw + 7) & ~7, ch = (dh + 7) & ~7;
   struct Dir { int n = 0, m = 0, coded = 0, taps = 0; std::vector<int32_t> first; std::vector<int16_t> coef; };
   Dir dir[3][2];
   int taps_all = -1;
@@ -312,6 +314,7 @@ hipError_t scale_plan_create(int bd, int sw, int sh, int dw, int dh, ScalePlan *
     const Dir &H = dir[p][0], &V = dir[p][1];
     ScalePlaneDesc &d = desc[p];
     d.src_w = H.n; d.src_h = V.n; d.src_stride = p ? sw8 / 2 : sw8; d.src_rows = p ? sh8 / 2 : sh8;
+    if (window) d.origin = (p ? window->y / 2 : window->y) * d.src_stride + (p ? window->x / 2 : window->x);
     d.dst_w = H.coded; d.dst_h = V.coded; d.taps_h = H.taps; d.taps_v = V.taps;
     d.tiles_x = (H.coded + (1 << twl) - 1) >> twl; d.tiles_y = (V.coded + th - 1) / th;
     P->tiles_per_frame[p] = d.tiles_x * d.tiles_y;

@@ -16,6 +16,11 @@
 // (sceneplan.hpp) lays the GOPs out, and every batch is gathered from the store (av1mi_gop_submit_stored).  The session has two stores:
 // the next group's frames are read and put while this group's batches run.
 //
+// A crop window — a crop= filter in front of the chain, -av1mi_crop W:H:X:Y, or the bars that -av1mi_crop auto finds — is settled BEFORE the
+// session is opened: auto reads up to 32 frames spread evenly over a seekable file, uploads their luma planes, runs av1mi_crop_analyse
+// and plans the window (cropplan.hpp).  The session is then opened with the window (av1mi_gop_config.crop_*) and fed whole frames; the
+// rest of the chain sees the window's size.  No window = the path below as it has always been.
+//
 // `segments` closed GOPs of the file are coded in lockstep (the session's batch dimension); while the host codes the
 // symbols of frame t the GPU already works on frames t + 1 and t + 2 (three batches in flight).
 #include "filmgrain.hpp"
@@ -30,6 +35,7 @@
 #include "../../include/av1mi.h"
 #include "../csrc/quality.hpp"
 #include "av1_bitstream.hpp"
+#include "cropplan.hpp"
 #include "mux.hpp"
 #include "ratecontrol.hpp"
 #include "sceneplan.hpp"
@@ -169,11 +175,48 @@ int RunBackend(const BackendJob &job, std::string *err) {
   if (!y.open(job.input, err, job.to_420)) { code = 1; goto done; }
   {
     // the target: what the argv's filter chain yields on this source (transcode.go:92-115), or -av1mi_scale; no chain = the source
-    int tw = y.w, th = y.h;
+    // the window first: -av1mi_crop stands in front of the chain, whose filters then see the window's size
+    CropRect win;
+    if (job.crop_mode == 2) {
+      win = job.crop;
+      if (win.w > y.w || win.h > y.h || win.x > y.w - win.w || win.y > y.h - win.h) {
+        *err = "Invalid argument: -av1mi_crop " + std::to_string(win.w) + ":" + std::to_string(win.h) + ":" + std::to_string(win.x) + ":" + std::to_string(win.y) +
+               " lies outside the " + std::to_string(y.w) + "x" + std::to_string(y.h) + " picture";
+        code = 1; goto done;
+      }
+    } else if (job.crop_mode == 1) {
+      // cropping by a stream's first frames would crop by its opening credits, and what is cropped is gone
+      if (!y.seekable()) { *err = "Invalid argument: -av1mi_crop auto needs a seekable file: it samples frames from all over the input, not from a pipe or FIFO"; code = 1; goto done; }
+      const long have = y.prepare(0, y.known_frames(), err);
+      if (have < 0) { code = 1; goto done; }
+      const int n = (int)std::min<long>(kCropSampleFrames, have), W8 = (y.w + 7) & ~7, H8 = (y.h + 7) & ~7;
+      const size_t plane = (size_t)W8 * H8 * (y.src_bd == 8 ? 1 : 2);
+      std::vector<unsigned char> luma(plane * (size_t)std::max(n, 1)), cu(plane), cv(plane);      // (the chroma planes are read and dropped)
+      for (int i = 0; i < n; i++)
+        if (!y.read((long)i * have / n, W8, H8, luma.data() + plane * (size_t)i, cu.data(), cv.data())) { *err = job.input + ": Invalid data found when processing input (truncated frame)"; code = 1; goto done; }
+      std::vector<av1mi_crop_record> rec((size_t)std::max(n, 1));
+      if (n > 0) {
+        void *d_luma = nullptr, *d_rec = nullptr;
+        int rc = av1mi_malloc(ctx, &d_luma, luma.size());
+        if (rc == AV1MI_OK) rc = av1mi_malloc(ctx, &d_rec, rec.size() * sizeof(av1mi_crop_record));
+        if (rc == AV1MI_OK) rc = av1mi_upload(ctx, d_luma, luma.data(), luma.size());
+        if (rc == AV1MI_OK) rc = av1mi_crop_analyse(ctx, y.src_bd, W8, H8, y.w, y.h, n, d_luma, job.crop_limit, (av1mi_crop_record *)d_rec);
+        if (rc == AV1MI_OK) rc = av1mi_download(ctx, rec.data(), d_rec, rec.size() * sizeof(av1mi_crop_record));
+        if (rc != AV1MI_OK) *err = std::string("av1mi_crop_analyse: ") + av1mi_last_error(ctx);
+        if (d_luma) (void)av1mi_free(ctx, d_luma);
+        if (d_rec) (void)av1mi_free(ctx, d_rec);
+        if (rc != AV1MI_OK) { code = 2; goto done; }
+      }
+      if (!PlanCrop(rec.data(), n, y.w, y.h, &win) || !win.trims(y.w, y.h)) win = CropRect();      // no bars: today's path, exactly
+    }
+    const int pw = win.w ? win.w : y.w, ph = win.w ? win.h : y.h;      // the picture the chain works on
+    int tw = pw, th = ph;
     bool square = y.sar_n == y.sar_d;
-    if (job.have_vf && !ScaleTarget(y.w, y.h, y.sar_n, y.sar_d, job.vf, &tw, &th, &square, err)) { code = 1; goto done; }
+    CropRect chain_crop;
+    if (job.have_vf && !ChainTarget(pw, ph, y.sar_n, y.sar_d, job.vf, &tw, &th, &square, err, nullptr, nullptr, &chain_crop)) { code = 1; goto done; }
+    if (chain_crop.w) win = chain_crop;      // (ParseBackendJob: never together with -av1mi_crop)
     if (job.scale_w) { tw = job.scale_w; th = job.scale_h; square = true; }
-    const bool scaling = tw != y.w || th != y.h || job.scale_w != 0;
+    const bool scaling = win.w != 0 || tw != y.w || th != y.h || job.scale_w != 0;      // a window is fed like a source to be scaled: whole frames
     const int G = job.gop, w = (tw + 7) & ~7, h = (th + 7) & ~7;       // the coded size; tw x th is what a decoder outputs
     int S = std::max(job.segments, 1);
     if (y.known_frames() >= 0) S = (int)std::max<long>(1, std::min<long>(S, (y.known_frames() + G - 1) / G));      // no more segments than the file has GOPs
@@ -183,6 +226,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
     memset(&cfg, 0, sizeof(cfg));
     if (w != tw || h != th) { cfg.visible_width = tw; cfg.visible_height = th; }
     if (scaling) { cfg.source_width = y.w; cfg.source_height = y.h; }
+    if (win.w) { cfg.crop_x = win.x; cfg.crop_y = win.y; cfg.crop_width = win.w; cfg.crop_height = win.h; }
     cfg.width = w; cfg.height = h; cfg.bit_depth = y.bd; cfg.base_q_idx = job.quality < 1 ? 1 : job.quality; cfg.gop_length = G; cfg.segments = S;
     cfg.search_range = 8;
     cfg.coarse_range = job.me_range;      // -av1mi_me_range: the coarse search in front of it
@@ -422,6 +466,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
             char line[512];
             int n = snprintf(line, sizeof(line), "n:%ld type:%c bytes:%zu", summary.frames, t == 0 ? 'K' : 'P', units[(size_t)s][t].size());
             n += av1mi::quality::format_figures(av1mi::quality::frame_figures(records[(size_t)s][t].q, y.bd), line + n, sizeof(line) - (size_t)n);
+            if (win.w && summary.frames == 0) n += snprintf(line + n, sizeof(line) - (size_t)n, " crop:%dx%d+%d+%d", win.w, win.h, win.x, win.y);
             if (rc) n += snprintf(line + n, sizeof(line) - (size_t)n, " q:%d", qs[(size_t)s][t]);
             if (job.denoise) n += snprintf(line + n, sizeof(line) - (size_t)n, " grain:%d", grains[(size_t)s][t]);
             if (analysed && cut[(size_t)start[(size_t)s] + t]) n += snprintf(line + n, sizeof(line) - (size_t)n, " cut:1");

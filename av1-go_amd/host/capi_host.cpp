@@ -127,6 +127,24 @@ int av1mi_host_scale_target(int iw, int ih, int sar_n, int sar_d, const char *ch
   bool square = false;
   return ScaleTarget(iw, ih, sar_n, sar_d, chain ? chain : "", w, h, &square, &e) ? 0 : -1;
 }
+// the chain with crop= accepted (ChainTarget): the size the chain yields in *w, *h and the window in win[4] = x, y, width, height (width 0: the
+// chain does not crop); -1 and the text in err (may be null) for a chain that is refused
+int av1mi_host_chain_target(int iw, int ih, int sar_n, int sar_d, const char *chain, int *w, int *h, int *win, char *err, int errcap) {
+  std::string e;
+  bool square = false;
+  CropRect c;
+  const bool ok = ChainTarget(iw, ih, sar_n, sar_d, chain ? chain : "", w, h, &square, &e, nullptr, nullptr, &c);
+  if (win) { win[0] = c.x; win[1] = c.y; win[2] = c.w; win[3] = c.h; }
+  if (err && errcap > 0) { strncpy(err, e.c_str(), (size_t)errcap - 1); err[errcap - 1] = 0; }
+  return ok ? 0 : -1;
+}
+// the crop plan (cropplan.hpp PlanCrop): n records of frames of true size w x h -> win[4] = x, y, width, height; 1 = a window, 0 = none (win zeroed)
+int av1mi_host_crop_plan(const av1mi_crop_record *rec, int n, int w, int h, int *win) {
+  CropRect c;
+  const bool ok = PlanCrop(rec, n, w, h, &c);
+  if (win) { win[0] = c.x; win[1] = c.y; win[2] = c.w; win[3] = c.h; }
+  return ok ? 1 : 0;
+}
 // StreamSink (mux.hpp) alone, for the CPU tests: n_units byte strings (unit i = bytes [off[i], off[i + 1]) of `units`, standing in for
 // temporal units; unit i is a key frame when i % gop == 0) muxed at fps_n / fps_d together with the tracks of the Matroska side files
 // `sides` (paths separated by '\n').  Returns 0, or -1 with the text in err.

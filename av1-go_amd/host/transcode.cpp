@@ -1,6 +1,7 @@
 // transcode.cpp — see transcode.hpp.  Argument vector and error strings follow internal/ffmpeg/transcode.go.
 #include "transcode.hpp"
 #include "backend.hpp"
+#include <sys/stat.h>
 #include <cmath>
 #include <cstdio>
 
@@ -63,10 +64,49 @@ static bool plain_int(const std::string &t, int *v) {
   return true;
 }
 
+// crop=...: the four values (-1 = not given) of FFmpeg's option order out_w, out_h, x, y, keep_aspect, exact; false + *why for what is not honoured
+static bool crop_arguments(const std::string &arg, int v[4], std::string *why) {
+  v[0] = v[1] = v[2] = v[3] = -1;
+  int pos = 0;
+  size_t p = 0;
+  while (p <= arg.size()) {
+    size_t q = arg.find(':', p);
+    if (q == std::string::npos) q = arg.size();
+    const std::string tok = arg.substr(p, q - p);
+    p = q + 1;
+    const size_t eq = tok.find('=');
+    std::string key = eq == std::string::npos ? "" : tok.substr(0, eq);
+    const std::string val = eq == std::string::npos ? tok : tok.substr(eq + 1);
+    if (key.empty()) {
+      static const char *const order[6] = { "w", "h", "x", "y", "keep_aspect", "exact" };
+      if (pos >= 6) { *why = "too many values"; return false; }
+      key = order[pos++];
+    }
+    int n = 0;
+    const int slot = key == "w" || key == "out_w" ? 0 : key == "h" || key == "out_h" ? 1 : key == "x" ? 2 : key == "y" ? 3 : -1;
+    if (slot >= 0) {
+      if (!plain_int(val, &n)) { *why = "plain integers only, no expressions"; return false; }
+      v[slot] = n;
+    } else if (key == "exact") {
+      if (val != "0") { *why = "exact=1 is not built: the window is rounded down to even"; return false; }
+    } else if (key == "keep_aspect") {
+      if (val != "0") { *why = "keep_aspect is not built"; return false; }
+    } else { *why = "unknown option " + key; return false; }
+  }
+  if (v[0] < 0 || v[1] < 0) { *why = "give the window's width and height"; return false; }
+  return true;
+}
+
 bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err, bool *to_420, bool *deint) {
+  return ChainTarget(iw, ih, sar_n, sar_d, chain, w, h, square, err, to_420, deint, nullptr);
+}
+
+bool ChainTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err, bool *to_420, bool *deint,
+                 CropRect *crop, bool geometry) {
   if (sar_n <= 0 || sar_d <= 0) sar_n = sar_d = 1;
   long cw = iw, ch = ih;
-  bool sq = sar_n == sar_d;
+  bool sq = sar_n == sar_d, scaled = false;
+  if (crop) *crop = CropRect();
   // split at commas outside quotes
   std::vector<std::string> parts;
   std::string cur;
@@ -78,11 +118,26 @@ bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain,
   parts.push_back(cur);
   for (const std::string &f : parts) {
     int a = 0, b = 0;
-    if (f == kSarScale) {
+    if (crop && f.compare(0, 5, "crop=") == 0) {
+      int v[4];
+      std::string why;
+      bool ok = crop_arguments(f.substr(5), v, &why);
+      if (ok && scaled) { ok = false; why = "a crop after a scale filter is not built: the window is cut from the source"; }
+      if (ok && geometry) {
+        const long W = v[0] & ~1, H = v[1] & ~1;
+        const long X = (v[2] >= 0 ? v[2] : (cw - W) / 2) & ~1L, Y = (v[3] >= 0 ? v[3] : (ch - H) / 2) & ~1L;
+        if (W < 16 || H < 16) { ok = false; why = "a window of at least 16x16"; }
+        else if (W > cw || H > ch || X < 0 || Y < 0 || X > cw - W || Y > ch - H) { ok = false; why = "the window lies outside the " + std::to_string(cw) + "x" + std::to_string(ch) + " picture"; }
+        else { crop->x += (int)X; crop->y += (int)Y; crop->w = (int)W; crop->h = (int)H; cw = W; ch = H; }
+      }
+      if (!ok) { if (err) *err = "Invalid argument: unsupported filter argument " + f + " (" + why + ")"; return false; }
+    } else if (f == kSarScale) {
+      scaled = true;
       if (sar_n < sar_d) ch = cw * sar_d / sar_n;      // gt(iw, iw * sar), i.e. sar < 1: (iw, iw / sar) — iw, as the expression is written
       else cw = cw * sar_n / sar_d;                    // else (iw * sar, ih)
       sar_n = sar_d = 1; sq = true;
     } else if (f == kEvenScale) {
+      scaled = true;
       cw = (cw + 1) / 2 * 2; ch = (ch + 1) / 2 * 2;
     } else if (f.empty() || f == "hwdownload" || f == "hwupload" || f == "setsar=1") {
     } else if (f.compare(0, 7, "format=") == 0) {      // the encoder is handed 4:2:0 whatever the decoder produced (transcode.go:99-110); nothing else can be honoured
@@ -102,10 +157,10 @@ bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain,
       if (deint) *deint = true;
     } else if (f.compare(0, 6, "scale=") == 0 && f.find(':') != std::string::npos && plain_int(f.substr(6, f.find(':') - 6), &a) &&
                plain_int(f.substr(f.find(':') + 1), &b)) {
-      cw = a; ch = b; sar_n = sar_d = 1; sq = true;
+      cw = a; ch = b; sar_n = sar_d = 1; sq = true; scaled = true;
     } else if (f.compare(0, 14, "scale_vaapi=w=") == 0 && f.find(":h=") != std::string::npos && plain_int(f.substr(14, f.find(":h=") - 14), &a) &&
                plain_int(f.substr(f.find(":h=") + 3), &b)) {
-      cw = a; ch = b; sar_n = sar_d = 1; sq = true;
+      cw = a; ch = b; sar_n = sar_d = 1; sq = true; scaled = true;
     } else {
       if (err) *err = "Invalid argument: unsupported filter " + f.substr(0, f.find('='));
       return false;
@@ -151,6 +206,18 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
     }
     else if (args[i] == "-av1mi_denoise") {
       if (!plain_int(args[i + 1], &job->denoise) || job->denoise > 16) { if (err) *err = "Invalid argument: -av1mi_denoise takes a strength 1 .. 16 (0 = off), not " + args[i + 1]; return false; }
+    }
+    else if (args[i] == "-av1mi_crop") {
+      const std::string &v = args[i + 1];
+      int n[4];
+      std::string why;
+      if (v == "off") job->crop_mode = 0; else if (v == "auto") job->crop_mode = 1;
+      else if (crop_arguments(v, n, &why) && n[2] >= 0 && n[3] >= 0 && v.find('=') == std::string::npos && (n[0] & ~1) >= 16 && (n[1] & ~1) >= 16) {
+        job->crop_mode = 2; job->crop.w = n[0] & ~1; job->crop.h = n[1] & ~1; job->crop.x = n[2] & ~1; job->crop.y = n[3] & ~1;
+      } else { if (err) *err = "Invalid argument: -av1mi_crop takes off, auto or W:H:X:Y (plain integers, at least 16x16), not " + v; return false; }
+    }
+    else if (args[i] == "-av1mi_crop_limit") {
+      if (!plain_int(args[i + 1], &job->crop_limit) || job->crop_limit > 255) { if (err) *err = "Invalid argument: -av1mi_crop_limit takes a mean 8-bit level 0 .. 255, not " + args[i + 1]; return false; }
     }
     else if (args[i] == "-av1mi_film_grain") {
       if (args[i + 1] != "0" && args[i + 1] != "1") { if (err) *err = "Invalid argument: -av1mi_film_grain takes 0 or 1, not " + args[i + 1]; return false; }
@@ -203,7 +270,12 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
   if (job->have_vf) {      // a filter that cannot be applied must not be skipped silently: the chain is checked before anything runs
     int w, h;
     bool to_420 = false, deint = false;
-    if (!ScaleTarget(16, 16, 1, 1, job->vf, &w, &h, nullptr, err, &to_420, &deint)) return false;
+    CropRect chain_crop;
+    if (!ChainTarget(16, 16, 1, 1, job->vf, &w, &h, nullptr, err, &to_420, &deint, &chain_crop, false)) return false;
+    if (job->crop_mode && job->vf.find("crop=") != std::string::npos) {
+      if (err) *err = "Invalid argument: -av1mi_crop together with a crop= filter in the chain: give one";
+      return false;
+    }
     if (to_420) job->to_420 = true;
     if (deint && !deint_given) job->deinterlace = 1;      // a deinterlacer in the chain means auto; an explicit option keeps its say
   }
@@ -212,6 +284,14 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
   if (job->qmin && job->qmax && job->qmin > job->qmax) { if (err) *err = "Invalid argument: -qmin " + std::to_string(job->qmin) + " above -qmax " + std::to_string(job->qmax); return false; }
   if (job->scenecut && job->pack10) { if (err) *err = "Invalid argument: -av1mi_scenecut keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
   if (job->deinterlace && job->pack10) { if (err) *err = "Invalid argument: -av1mi_deinterlace keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
+  if ((job->crop_mode || (job->have_vf && job->vf.find("crop=") != std::string::npos)) && job->pack10) { if (err) *err = "Invalid argument: a crop window is cut from planar planes on the GPU: not together with -av1mi_pack10 1"; return false; }
+  if (job->crop_mode == 1) {      // (a regular file whose frames cannot be addressed is refused when it is opened: backend.cpp)
+    struct stat st;
+    if (job->input == "-" || job->input == "pipe:0" || (!stat(job->input.c_str(), &st) && !S_ISREG(st.st_mode))) {
+      if (err) *err = "Invalid argument: -av1mi_crop auto needs a seekable file: it samples frames from all over the input, not from a pipe or FIFO";
+      return false;
+    }
+  }
   if (job->denoise && job->pack10) { if (err) *err = "Invalid argument: -av1mi_denoise keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
   if (job->denoise && job->deinterlace) { if (err) *err = "Invalid argument: -av1mi_denoise filters the group's frames on their way from the store, as -av1mi_deinterlace does: not together with -av1mi_deinterlace"; return false; }
   if (job->film_grain >= 0 && !job->denoise) { if (err) *err = "Invalid argument: -av1mi_film_grain needs -av1mi_denoise"; return false; }

@@ -10,6 +10,7 @@
 #pragma once
 #include <string>
 #include <vector>
+#include "cropplan.hpp"
 
 namespace av1mi_host {
 
@@ -89,6 +90,15 @@ struct BackendJob {
   int film_grain = -1;     // -av1mi_film_grain 0 | 1: with -av1mi_denoise, 1 (the default there) signals film grain synthesis parameters derived from
                            // what the denoiser removed (host/filmgrain.hpp), 0 codes the clean frames alone; an error without -av1mi_denoise
   int min_gop = 0;         // -av1mi_min_gop M: the shortest GOP the planner makes, 1 .. gop - gop / 2; 0 = max(1, gop / 4).  Only with -av1mi_scenecut
+  int crop_mode = 0;       // -av1mi_crop off | auto | W:H:X:Y (0, 1, 2).  off (default): only a crop= filter of the chain crops.  W:H:X:Y: that window of the
+                           // source (rounded down to even like the chain's crop=), in front of the chain.  auto: needs a seekable file; up to 32 frames
+                           // spread evenly over it are uploaded and analysed on the GPU (av1mi_crop_analyse at -av1mi_crop_limit, default 24:
+                           // FFmpeg cropdetect's), host/cropplan.hpp turns the margins into a window, and the session is opened with it
+                           // (av1mi_gop_config.crop_*); no bars found = the path without a window, exactly.  auto or W:H:X:Y together with a crop=
+                           // in the chain is refused.  Not with -av1mi_pack10 1 (the window is cut from planar planes; the packed upload would need
+                           // a second planar copy of the whole frame)
+  CropRect crop;           // -av1mi_crop W:H:X:Y as given
+  int crop_limit = kCropLimitDefault;   // -av1mi_crop_limit N (0 .. 255)
   std::vector<std::string> tracks;   // -av1mi_tracks <file.mka> (repeatable): Matroska side files whose audio / subtitle tracks are copied
                                      // next to the video (the reference's `-c:a copy -c:s copy`, transcode.go:134-137, after an external demux)
 };
@@ -106,6 +116,16 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
 // anything else.  *square: the chain leaves square pixels (it resampled by the SAR, or to an explicit size).
 bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err, bool *to_420 = nullptr,
                  bool *deint = nullptr);
+
+// The same evaluation with `crop=` accepted (ScaleTarget keeps refusing it: "unsupported filter crop").  Forms: positional crop=W:H[:X:Y] and
+// named w= / out_w= / h= / out_h= / x= / y=, plain integers only; x and y default to the centre, (iw - W) / 2 and (ih - H) / 2.  All four
+// values are rounded down to even: what FFmpeg's crop does on 4:2:0 frames without exact=1 [ext].  exact=0 and keep_aspect=0 (the defaults)
+// are accepted.  "Invalid argument: unsupported filter argument crop=... (reason)" for expressions, exact=1, keep_aspect, a crop after a
+// scale filter and a window outside the picture (or smaller than 16x16).  *crop receives the window in SOURCE samples (w == 0: the chain
+// does not crop; a second crop composes with the first), and every later filter of the chain sees the window's size.  geometry = false
+// checks the syntax alone, for a chain whose source size is not known yet: *w, *h and the window are then meaningless.
+bool ChainTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err, bool *to_420, bool *deint,
+                 CropRect *crop, bool geometry = true);
 
 // transcode.go:194-315 contract: (0, "") on success AND the output file exists; (code, text <= 800 chars) on failure;
 // (-1, text) when the backend could not run at all (no HIP device, library error before any frame).  Exit code 3 is the quality gate

@@ -507,6 +507,27 @@ int av1mi_scene_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, in
  * AV1MI_K_SCENE in the profile. */
 int av1mi_frames_gather(av1mi_ctx *ctx, const size_t plane_bytes[3], int segments, const void *const *d_src_table, void *const d_dst[3]);
 
+/* ---- bar detection: the black margins of every frame of a sample of frames (av1-go_amd/csrc/crop_kernels.hip), from which the host plans a
+ * crop window (av1-go_amd/host/cropplan.hpp).  Integer arithmetic, bit exact by definition; P_f = the luma plane of frame f, TRUE size w x h
+ * inside a buffer of W8 x H8 samples (the true size rounded up to 8); m8(v) = v >> (bit_depth - 8), as in "motion search".
+ *   sums           row(y) = the sum over x < w of m8(P_f[y][x]);  col(x) = the sum over y < h of m8(P_f[y][x]).  Both fit in 32 bits
+ *                  (16384 x 255).  Nothing at or beyond the true size is read: the buffer's padding may be undefined.
+ *   dark           a row is dark iff row(y) <= limit * w, a column iff col(x) <= limit * h; limit 0 .. 255 (a MEAN 8-bit level: FFmpeg's
+ *                  cropdetect compares the same way; its default is 24).  Column darkness is judged over the full height, bars included.
+ *   the record     top = the number of consecutive dark rows from y = 0, bottom = from y = h - 1; left / right the same over columns from
+ *                  x = 0 / x = w - 1.  A frame whose rows are all dark has top = bottom = h; all columns dark: left = right = w.
+ *   determinism    two stages like the quality and scene records: integer partials in scratch with ONE writer each (per row and tile
+ *                  column, per tile row and column), then one workgroup per frame adds them in an order fixed by geometry.  The only
+ *                  atomics are integer minima over the indices of the rows / columns that are not dark: the order changes nothing. */
+typedef struct av1mi_crop_record { uint32_t top, bottom, left, right; } av1mi_crop_record;
+/* The records of `frames` (1 .. 65535) frames whose luma planes are stacked in d_luma as for av1mi_scene_analyse: width x height samples
+ * each, both multiples of 8 (the buffers' size), uint8 at bit_depth 8, uint16 at 10 or 12; true_width x true_height the picture inside,
+ * less than 8 below the buffer's size.  d_records: `frames` records in device memory, 4-byte aligned; d_luma 16-byte aligned.  Two
+ * launches (k_crop_sums reads every sample once and makes both families of sums; k_crop_margins), asynchronous on the context's stream;
+ * the partials live in the context (grown on demand).  AV1MI_K_SCENE in the profile. */
+int av1mi_crop_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int true_width, int true_height, int frames, const void *d_luma, int limit,
+                       av1mi_crop_record *d_records);
+
 /* ---- deinterlacing: an interlaced source becomes progressive frames inside the gather (av1-go_amd/csrc/deint_kernels.hip).  AV1 has no
  * interlaced coding and no field signalling: combing that is coded stays in the picture.  The filter is SAME-RATE: one output frame per
  * input frame, at the time of the frame's FIRST field.  Integer arithmetic, bit exact by definition.
@@ -680,6 +701,29 @@ typedef struct av1mi_gop_config {
    * fed buffers is untouched (the quality records are measured against the denoised frame); av1mi_gop_store_analyse keeps reading the
    * frames as fed; av1mi_gop_submit_device does not denoise. */
   int denoise;
+  /* The crop window (0, 0, 0, 0 = none: same allocations, same launches, same bytes as ever).  Otherwise a rectangle (crop_x, crop_y,
+   * crop_width, crop_height) of the planar 4:2:0 frame at the fed TRUE size; it applies after "convert" / "chroma" and before "scale".
+   * Such a session is fed WHOLE source frames exactly as a scaling session is: source_width x source_height is their true size and is
+   * required, the buffers are that size rounded up to 8 (padding undefined, never read), and av1mi_gop_source_layout describes that.
+   * Rules: the four numbers are even, the window lies inside the true size and is at least 16 x 16.  The coded true size (visible_*, or
+   * width x height) is the target:
+   *   equal to the window's size   nothing is resampled: one launch per batch (k_crop_copy, crop_kernels.hip) copies the window to the
+   *                                coded planes and replicates the WINDOW's last column / row into their <= 7 padding columns / rows,
+   *                                which is what the block pipeline expects of a fed frame;
+   *   any other size               the scaler resamples the window to the target exactly as it would a fed frame that WAS the window
+   *                                ("scaling" with N = the window's size): its edge clamps sit at the window's edges, not the frame's.
+   * MECHANISM: no stage of its own and no plane between.  The window is handed to the last input stage as an origin (crop_y * stride +
+   * crop_x samples, the half of either for chroma) and the fed planes' stride: to k_scale, or where nothing is resampled to k_crop_copy,
+   * which takes k_scale's place in the chain.  Either way one launch per batch, and neither kernel assumes any alignment of the window's
+   * rows beyond the sample's own (an even crop_x starts 8-bit luma rows at any even byte, chroma rows at any byte).
+   * DEFINING PROPERTY: nothing outside the window influences anything the session produces.  Fed whole frames, it yields the same tile
+   * payloads, symbols, references, quality records and av1mi_gop_download_reference planes, byte for byte, as a session without a
+   * window fed the pre-cropped frames.  It composes with every input_format, with source_chroma / source_bit_depth (a 4:4:4 source is
+   * cropped after the conversion), the frame store, deinterlace and denoise (which run in the gather on the WHOLE fed frame, before
+   * the window), quality_stats (measured against the cropped frame), coarse_range and rate control.
+   * KNOWN LIMIT: av1mi_gop_store_analyse and the grain records keep reading whole fed frames, bars included: black bars count as still
+   * picture in the scene records and as clean samples in bin 0 of the grain records. */
+  int crop_x, crop_y, crop_width, crop_height;
 } av1mi_gop_config;
 
 /* The source layout: what a session opened with a config is FED, as one description.  Everything a caller sizes or strides by — the
@@ -689,8 +733,8 @@ typedef struct av1mi_gop_config {
  * frame s at byte s * frame_bytes.  (av1mi_input_plane_bytes / av1mi_source_plane_bytes give the same numbers for rows = segments *
  * height: both are linear in the rows.) */
 typedef struct av1mi_source_layout {
-  int width, height;            /* luma size of a fed frame's BUFFER: the coded size, or where the session scales the source size rounded up to 8 */
-  int true_width, true_height;  /* the picture inside it: source_width x source_height where the session scales, else the visible size */
+  int width, height;            /* luma size of a fed frame's BUFFER: the coded size, or where the session scales or crops the source size rounded up to 8 */
+  int true_width, true_height;  /* the picture inside it: source_width x source_height where the session scales or crops, else the visible size */
   int bit_depth;                /* of the fed samples: source_bit_depth, or bit_depth */
   struct {
     int width, height;          /* in samples; 0 x 0 = no such plane (the chroma of a grey source, the third plane of P010 / NV12).  The
