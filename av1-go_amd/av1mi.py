@@ -92,7 +92,7 @@ class GopConfig(C.Structure):
                 ("visible_height", C.c_int), ("coder_streams", C.c_int), ("key_block_size", C.c_int), ("input_format", C.c_int), ("source_width", C.c_int),
                 ("source_height", C.c_int), ("quality_stats", C.c_int), ("coarse_range", C.c_int), ("source_chroma", C.c_int),
                 ("source_bit_depth", C.c_int), ("store_frames", C.c_int), ("deinterlace", C.c_int), ("denoise", C.c_int),
-                ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int), ("crop_height", C.c_int)]
+                ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int), ("crop_height", C.c_int), ("denoise_range", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -122,6 +122,7 @@ def policy_frame_params(base_q_idx, bit_depth, frame_type):
 # av1mi_scene_record (include/av1mi.h "scene analysis"): one record per frame
 GRAIN_BINS = 16      # AV1MI_GRAIN_BINS; a record (av1mi_grain_record) is that many bins
 GRAIN_DTYPE = np.dtype([("sum_sq", "<u8"), ("count", "<u4"), ("reserved", "<u4")])      # av1mi_grain_bin
+DENOISE_VEC_DTYPE = np.dtype([("dx_p", "i1"), ("dy_p", "i1"), ("dx_n", "i1"), ("dy_n", "i1")])      # av1mi_denoise_vec: a block's vectors towards P and N
 SCENE_DTYPE = np.dtype([("inter_sad", "<u8"), ("intra_sad", "<u8"), ("blocks", "<u4"), ("reserved", "<u4")])
 CROP_DTYPE = np.dtype([("top", "<u4"), ("bottom", "<u4"), ("left", "<u4"), ("right", "<u4")])      # av1mi_crop_record ("bar detection")
 assert SCENE_DTYPE.itemsize == 24
@@ -231,7 +232,7 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
@@ -247,7 +248,9 @@ class GopSession:
         denoise: 1 .. 16, the strength of the temporal denoiser (av1mi_gop_config.denoise; needs store_frames, not with deinterlace):
         submit_stored() gathers through it and collect()["grain"] holds the grain records.  None leaves the field unset (0 = none);
         crop: (x, y, width, height), the window of the fed frames that is coded (av1mi_gop_config.crop_*; needs source, the fed frames'
-        true size): width x height (or visible) is the target the window is copied or scaled to"""
+        true size): width x height (or visible) is the target the window is copied or scaled to;
+        denoise_range: 4 or 8, the range of the denoiser's block search (av1mi_gop_config.denoise_range; needs denoise): submit_stored()
+        gathers through the motion-compensated filter.  None leaves the field unset (0 = none)"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
         sw, sh = source if source is not None else (0, 0)
@@ -255,6 +258,8 @@ class GopSession:
                              sw, sh, int(quality_stats), int(coarse_range), int(source_chroma), int(source_bit_depth), int(store_frames), int(deinterlace))
         if denoise is not None:
             self.cfg.denoise = int(denoise)
+        if denoise_range is not None:
+            self.cfg.denoise_range = int(denoise_range)
         if crop is not None:
             self.cfg.crop_x, self.cfg.crop_y, self.cfg.crop_width, self.cfg.crop_height = (int(v) for v in crop)
         self.g = C.c_void_p()
@@ -648,6 +653,17 @@ class Context:
         self._chk(self.lib.av1mi_denoise_gather(self.h, int(bit_depth), arr([s[0] for s in plane_sizes]), arr([s[1] for s in plane_sizes]),
                                                 arr([s[0] for s in true_sizes]), arr([s[1] for s in true_sizes]), int(strength), int(segments), d_table.ptr, dst,
                                                 d_records.ptr if d_records is not None else None))
+
+    def denoise_mc_gather(self, bit_depth, plane_sizes, true_sizes, strength, rng, segments, d_table, d_dst, d_records=None, d_vectors=None):
+        """the denoising gather behind a block search (av1mi_denoise_mc_gather): denoise_gather's arguments with rng (4 or 8) after the
+        strength; d_vectors: DevBuf of segments * blocks records (DENOISE_VEC_DTYPE [segments, blocks], blocks = ceil(w / 16) * ceil(h / 16)
+        of the luma plane's true size) or None = the vectors stay in the context; asynchronous"""
+        self.lib.av1mi_denoise_mc_gather.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4
+        arr = lambda v: (C.c_int * 3)(*[int(x) for x in v])
+        dst = (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_dst])
+        self._chk(self.lib.av1mi_denoise_mc_gather(self.h, int(bit_depth), arr([s[0] for s in plane_sizes]), arr([s[1] for s in plane_sizes]),
+                                                   arr([s[0] for s in true_sizes]), arr([s[1] for s in true_sizes]), int(strength), int(rng), int(segments), d_table.ptr, dst,
+                                                   d_records.ptr if d_records is not None else None, d_vectors.ptr if d_vectors is not None else None))
 
     def prof_enable(self, on):
         self._chk(self.lib.av1mi_prof_enable(self.h, int(on)))

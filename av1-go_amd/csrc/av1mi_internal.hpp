@@ -226,6 +226,16 @@ struct DenoiseLaunch {
 };
 size_t grain_scratch_bytes(const DenoiseLaunch &L);      // 0 for a geometry the launch refuses
 hipError_t launch_denoise_gather(const DenoiseLaunch &L, hipStream_t s);
+// the same with a block search in front (include/av1mi.h "motion-compensated denoising"): range 4 or 8; vectors: segments x blocks records
+// (denoise_mc_vector_bytes(L) bytes, 4-byte aligned, never null), written by k_denoise_search and read by k_denoise_mc_gather; scratch holds
+// denoise_mc_scratch_bytes(L) bytes where records are asked for.  Two launches, three with records.
+struct DenoiseMcLaunch : DenoiseLaunch {
+  int range;
+  av1mi_denoise_vec *vectors;
+};
+size_t denoise_mc_scratch_bytes(const DenoiseMcLaunch &L);      // 0 for a geometry the launch refuses
+size_t denoise_mc_vector_bytes(const DenoiseMcLaunch &L);       // likewise
+hipError_t launch_denoise_mc_gather(const DenoiseMcLaunch &L, hipStream_t s);
 
 // side information that follows a batch's quantiser (levels_kernels.hip): up to three arrays of dwords patched in place in one launch,
 // word = (word & keep) | bits unless (word & hold) != 0

@@ -32,6 +32,8 @@ struct av1mi_ctx {
   size_t crop_scratch_bytes = 0;
   void *grain_scratch = nullptr;          // av1mi_denoise_gather: the workgroups' partial records (grown on demand)
   size_t grain_scratch_bytes = 0;
+  void *denoise_vectors = nullptr;        // av1mi_denoise_mc_gather without d_vectors: the blocks' vectors (grown on demand)
+  size_t denoise_vectors_bytes = 0;
   // per-kernel profile: one event pair per launch while enabled
   bool prof_on = false;
   struct ProfRec { int kind; hipEvent_t e0, e1; };
@@ -192,6 +194,7 @@ void av1mi_close(av1mi_ctx *ctx) {
   if (ctx->scene_scratch) (void)hipFree(ctx->scene_scratch);
   if (ctx->crop_scratch) (void)hipFree(ctx->crop_scratch);
   if (ctx->grain_scratch) (void)hipFree(ctx->grain_scratch);
+  if (ctx->denoise_vectors) (void)hipFree(ctx->denoise_vectors);
   if (ctx->av1ent) av1mi::av1ent_free(ctx->av1ent);
   av1mi::scale_plan_destroy(ctx->scale_plan);
   for (auto &r : ctx->prof_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -720,6 +723,58 @@ int av1mi_denoise_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], co
   }
   ProfScope ps(ctx, AV1MI_K_SCENE);
   HIP_TRY(ctx, av1mi::launch_denoise_gather(L, ctx->stream));
+  return AV1MI_OK;
+}
+
+int av1mi_denoise_mc_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int strength,
+                            int range, int segments, const void *const *d_table, void *const d_dst[3], av1mi_grain_record *d_records, av1mi_denoise_vec *d_vectors) {
+  BIND(ctx);
+  if (!plane_w || !plane_h || !true_w || !true_h || !d_table || !d_dst || ((uintptr_t)d_table & 7) || ((uintptr_t)d_records & 7) || ((uintptr_t)d_vectors & 3))
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: null pointer, or misaligned table, records or vectors");
+  if (bit_depth != 8 && bit_depth != 10) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: bit depth %d not supported (8 or 10)", bit_depth);
+  if (strength < 1 || strength > 16) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: strength %d out of range (1 .. 16)", strength);
+  if (range != 4 && range != 8) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: range %d (4 or 8)", range);
+  if (segments < 1 || segments > 4096) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: segments %d out of range (1 .. 4096)", segments);
+  if (plane_w[0] <= 0 || plane_h[0] <= 0) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: no luma plane (%dx%d): it is what the search reads", plane_w[0], plane_h[0]);
+  av1mi::DenoiseMcLaunch L;
+  L.bd = bit_depth; L.strength = strength; L.range = range; L.segments = segments; L.table = d_table; L.records = d_records; L.scratch = nullptr; L.vectors = d_vectors;
+  const int bps = bit_depth == 8 ? 1 : 2;
+  for (int p = 0; p < 3; p++) {
+    const bool have = plane_w[p] > 0 && plane_h[p] > 0;
+    if (plane_w[p] < 0 || plane_h[p] < 0 || plane_w[p] > 16384 || plane_h[p] > 16384 || ((size_t)plane_w[p] * bps & 3))
+      return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: plane %d of %dx%d samples (rows of whole dwords, up to 16384x16384)", p, plane_w[p], plane_h[p]);
+    if (have && (true_w[p] < 1 || true_h[p] < 1 || true_w[p] > plane_w[p] || true_h[p] > plane_h[p] || plane_w[p] - true_w[p] >= 8 || plane_h[p] - true_h[p] >= 8))
+      return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: plane %d: the true size %dx%d must lie within 7 samples below the buffer's %dx%d", p, true_w[p], true_h[p], plane_w[p], plane_h[p]);
+    if (have && (plane_w[p] * bps - 1) / 16 * (16 / bps) > true_w[p] - 1)
+      return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: plane %d: the last 16-byte cell of a row of %d samples starts beyond the true width %d", p, plane_w[p], true_w[p]);
+    const int ssx = have && plane_w[p] < plane_w[0], ssy = have && plane_h[p] < plane_h[0];
+    if (have && (true_w[p] != (true_w[0] + ssx) >> ssx || true_h[p] != (true_h[0] + ssy) >> ssy))
+      return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: plane %d: the true size %dx%d is not the luma plane's %dx%d%s", p, true_w[p], true_h[p], true_w[0], true_h[0],
+                  ssx || ssy ? ", halved upwards where the plane is subsampled" : "");
+    if (have && (!d_dst[p] || ((uintptr_t)d_dst[p] & 15))) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: null or misaligned destination (plane %d)", p);
+    L.plane_w[p] = have ? plane_w[p] : 0; L.plane_h[p] = have ? plane_h[p] : 0; L.true_w[p] = true_w[p]; L.true_h[p] = true_h[p]; L.dst[p] = d_dst[p];
+  }
+  // (hipFree waits for the launches that still use the old scratch)
+  auto grow = [&](void **buf, size_t *have, size_t need) -> hipError_t {
+    if (*have >= need) return hipSuccess;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr; *have = 0;
+    if (hipError_t e = hipMalloc(buf, need)) return e;
+    *have = need;
+    return hipSuccess;
+  };
+  if (!d_vectors) {
+    const size_t need = av1mi::denoise_mc_vector_bytes(L);
+    if (!need) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: a geometry the launch does not take");
+    HIP_TRY(ctx, grow(&ctx->denoise_vectors, &ctx->denoise_vectors_bytes, need));
+    L.vectors = (av1mi_denoise_vec *)ctx->denoise_vectors;
+  }
+  if (d_records) {
+    HIP_TRY(ctx, grow(&ctx->grain_scratch, &ctx->grain_scratch_bytes, av1mi::denoise_mc_scratch_bytes(L)));
+    L.scratch = ctx->grain_scratch;
+  }
+  ProfScope ps(ctx, AV1MI_K_SCENE);
+  HIP_TRY(ctx, av1mi::launch_denoise_mc_gather(L, ctx->stream));
   return AV1MI_OK;
 }
 

@@ -162,6 +162,7 @@ struct av1mi_gop {
   void *d_cdef_sb[2] = {}, *d_lr[2] = {}, *d_zero_skip = nullptr;
   void *d_lr_scratch = nullptr;                // the restoration decision's partial sums (three planes)
   void *d_me = nullptr;                        // coarse_range: the coarse search's quarter planes and centres of one batch (single: the chain is serial in t)
+  void *d_denoise_vectors = nullptr;           // denoise_range: the blocks' vectors of one batch (the main stream orders its users)
   void *d_grain_scratch = nullptr;             // denoise: the workgroups' partial records of one batch (the main stream orders its users)
   void *d_quality_scratch = nullptr;           // quality_stats: the tiles' partial sums of one batch (the main stream orders its users)
   int vw = 0, vh = 0;                          // the true frame size (== the coded size unless cfg.visible_* say otherwise)
@@ -392,6 +393,8 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
   if (c->denoise && !c->store_frames) return WHY("denoise %d needs a frame store (store_frames > 0): the filter reads the frames before and after each frame", c->denoise);
   if (c->denoise && c->deinterlace) return WHY("denoise %d together with deinterlace %d is not built: the chain of the two needs a third copy of a group", c->denoise, c->deinterlace);
   if (c->denoise && c->source_bit_depth == 12) return WHY("denoise %d takes fed samples of 8 or 10 bits, not source_bit_depth 12", c->denoise);
+  if (c->denoise_range != 0 && c->denoise_range != 4 && c->denoise_range != 8) return WHY("denoise_range %d unknown (0 none, 4 or 8 the block search's range)", c->denoise_range);
+  if (c->denoise_range && !c->denoise) return WHY("denoise_range %d needs denoise (1 .. 16): it is the range of the denoiser's block search", c->denoise_range);
   return nullptr;
 #undef WHY
 }
@@ -442,13 +445,14 @@ int setup(av1mi_gop *g) {
   if (c.coarse_range) G_TRY(dev_alloc(g, &g->d_me, av1mi::me_layout(w, h, S).bytes));
   if (c.quality_stats) G_TRY(dev_alloc(g, &g->d_quality_scratch, av1mi::quality_scratch_bytes(c.bit_depth, g->vw, g->vh, S)));
   if (c.denoise) {
-    Slot probe; av1mi::DenoiseLaunch L;
+    Slot probe; av1mi::DenoiseMcLaunch L{};
     fed_geometry(g, probe, L);
-    L.strength = c.denoise;
-    const size_t bytes = av1mi::grain_scratch_bytes(L);
+    L.strength = c.denoise; L.range = c.denoise_range;
+    const size_t bytes = c.denoise_range ? av1mi::denoise_mc_scratch_bytes(L) : av1mi::grain_scratch_bytes(L);
     if (!bytes) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "denoise %d: the fed layout %dx%d (true %dx%d) is not one the denoising gather takes", c.denoise, g->layout.width,
                                       g->layout.height, g->layout.true_width, g->layout.true_height);
     G_TRY(dev_alloc(g, &g->d_grain_scratch, bytes));
+    if (c.denoise_range) G_TRY(dev_alloc(g, &g->d_denoise_vectors, av1mi::denoise_mc_vector_bytes(L)));
   }
   if (c.store_frames) {
     for (Store &st : g->store) {
@@ -585,6 +589,12 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
         fed_geometry(g, s, L);
         L.parity = dei - 1;
         G_HIP(av1mi::launch_deint_gather(L, main));
+      } else if (c.denoise_range) {      // the block search, the filter on displaced neighbours, the records as below
+        av1mi::DenoiseMcLaunch L;
+        fed_geometry(g, s, L);
+        L.strength = c.denoise; L.range = c.denoise_range; L.scratch = g->d_grain_scratch; L.records = (av1mi_grain_record *)s.h_grain;
+        L.vectors = (av1mi_denoise_vec *)g->d_denoise_vectors;
+        G_HIP(av1mi::launch_denoise_mc_gather(L, main));
       } else if (c.denoise) {      // ... and the records of what it removed, straight into the slot's pinned memory
         av1mi::DenoiseLaunch L;
         fed_geometry(g, s, L);

@@ -19,6 +19,7 @@
 //   ends      a frame at an end of its run (P or N is C itself) and a flat slot (C null) are the gather alone: copied, resp. zeros,
 //             and their partials are zero.
 // Arithmetic: include/av1mi.h; restated in numpy by tests/denoise_ref.py.  Reference tree: nothing (it has no denoiser).
+// Below them: k_denoise_search and k_denoise_mc_gather, the motion-compensated pair that av1mi_gop_config.denoise_range launches instead.
 #include "av1mi_internal.hpp"
 #include "gather_cells.hpp"
 
@@ -317,6 +318,305 @@ hipError_t launch_denoise_gather(const DenoiseLaunch &L, hipStream_t s) {
   const dim3 grid(G.per_seg * (unsigned)L.segments);
   if (L.bd == 8) hipLaunchKernelGGL(k_denoise_gather<uint8_t>, grid, dim3(256), 0, s, G, L.table);
   else hipLaunchKernelGGL(k_denoise_gather<uint16_t>, grid, dim3(256), 0, s, G, L.table);
+  if (hipError_t e = hipGetLastError()) return e;
+  if (L.records) hipLaunchKernelGGL(k_grain_sum, dim3(3u * (unsigned)L.segments), dim3(256), 0, s, G, L.records);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Motion-compensated denoising (include/av1mi.h "motion-compensated denoising"): k_denoise_search gives every 16x16 luma block a vector
+// towards P and one towards N; k_denoise_mc_gather stands in k_denoise_gather's place and compares every sample with its DISPLACED
+// neighbours.  The partial records and k_grain_sum are the plain gather's.
+//
+//   search    a wave owns (block, F): the block (zeros beyond its true part) and F's clamped window of (16 + 2 range)^2 samples lie in
+//             LDS as whole dwords.  A lane owns a candidate (dy, dx) at a time and walks down the block's rows: the window row's dwords
+//             from the candidate's first byte on come through v_alignbyte_b32, the columns beyond the true width are masked to zero on
+//             both sides, and v_sad_u8 (four samples) / v_sad_u16 (two) add into ONE 32-bit accumulator (256 x 1023 + the bias < 2^19).
+//             The key (cost << 11 | rank) goes through an LDS atomicMin; a workgroup holds two blocks and stores one dword per block.
+//   gather    a wave owns a block's samples in ONE plane (16 >> ssx by 16 >> ssy of them, plus the padding beyond the true size at the
+//             plane's right and bottom edge: at most 23 x 23), a workgroup four blocks side by side.  C and the displaced P and N of the
+//             block's 18 x 18 neighbourhood go to LDS once (coordinates clamped as the definition clamps them), |C - P| and |C - N| as the
+//             two halves of a dword, so that D_P and D_N of a sample are nine dword adds (9 x 1023 fits a half).  The output is
+//             assembled in LDS and leaves in 16-byte units where the block's row run allows them, in dwords elsewhere.
+// Arithmetic restated in numpy by tests/denoise_mc_ref.py.
+namespace {
+struct McGeom {
+  int w0, h0;                  // the luma plane's true size
+  int nbx, nby;                // blocks across and down
+  uint32_t rb0;                // bytes of a luma row
+  uint32_t pairs;              // the search's workgroups per segment: two blocks each
+  uint32_t strips;             // the gather's workgroups per block row: four blocks each
+  uint32_t t_luma;             // strength << (bit_depth - 8)
+  int ssx[3], ssy[3];          // the planes' subsampling against luma
+  uint32_t *vectors;           // [segment * blocks + block]: dx_p | dy_p << 8 | dx_n << 16 | dy_n << 24 (av1mi_denoise_vec)
+};
+
+template <typename Pix>
+__device__ __forceinline__ uint32_t sample_at(const char *plane, uint32_t rb, int x, int y) { return reinterpret_cast<const Pix *>(plane + (size_t)y * rb)[x]; }
+__device__ __forceinline__ int clampi(int v, int hi) { return min(max(v, 0), hi); }
+// idx / d for idx * d < 2^16, rcp = 65536 / d + 1 (the error of rcp, at most d / 65536 per unit, cannot reach the next integer)
+__device__ __forceinline__ uint32_t div_small(uint32_t idx, uint32_t rcp) { return (idx * rcp) >> 16; }
+}  // namespace
+
+// grid: pairs x segments; wave = (block pair * 2 + (wave >> 1), F = wave & 1 ? N : P)
+template <typename Pix, int RANGE>
+__global__ __launch_bounds__(256) void k_denoise_search(McGeom M, const void *const *table) {
+  constexpr int BPS = (int)sizeof(Pix), SPD = 4 / BPS;      // samples per dword
+  constexpr int WIN = 16 + 2 * RANGE;                       // the window's rows, and samples per row
+  constexpr int WDW = WIN / SPD + 1;                        // dwords of a window row in LDS (+ 1: the funnel's last high dword, zero)
+  constexpr int CDW = 16 / SPD;                             // dwords of a block row
+  constexpr int SIDE = 2 * RANGE + 1, CAND = SIDE * SIDE, CENTRE = RANGE * SIDE + RANGE;
+  __shared__ uint32_t s_win[4][WIN * WDW];
+  __shared__ uint32_t s_blk[4][16 * CDW];
+  __shared__ uint32_t s_key[4];
+  const unsigned seg = blockIdx.x / M.pairs, pair = blockIdx.x - seg * M.pairs;
+  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  const unsigned nblk = (unsigned)(M.nbx * M.nby);
+  const char *const *tab = reinterpret_cast<const char *const *>(table) + (size_t)seg * 9;      // the luma plane's P, C, N
+  const char *P = tab[0], *C = tab[1], *N = tab[2];
+  uint32_t *vec = M.vectors + (size_t)seg * nblk;
+  if (!C || P == C || N == C) {                  // a flat slot, an end of the run: not searched (uniform in the workgroup)
+    if (threadIdx.x < 2 && pair * 2 + threadIdx.x < nblk) vec[pair * 2 + threadIdx.x] = 0;
+    return;
+  }
+  const unsigned blk = pair * 2 + (wave >> 1);
+  const bool live = blk < nblk;
+  const char *F = (wave & 1) ? N : P;
+  const int by = live ? (int)blk / M.nbx : 0, bx = live ? (int)blk - by * M.nbx : 0;
+  const int bw = min(16, M.w0 - bx * 16), bh = min(16, M.h0 - by * 16);      // the block's true part
+  if (threadIdx.x < 4) s_key[threadIdx.x] = 0xffffffffu;
+  if (live) {
+    for (int i = (int)lane; i < 16 * CDW; i += 64) {
+      const int r = i / CDW, q = i - r * CDW;
+      uint32_t d = 0;
+      if (r < bh) {
+#pragma unroll
+        for (int k = 0; k < SPD; k++)
+          if (q * SPD + k < bw) d |= sample_at<Pix>(C, M.rb0, bx * 16 + q * SPD + k, by * 16 + r) << (8 * BPS * k);
+      }
+      s_blk[wave][i] = d;
+    }
+    for (int i = (int)lane; i < WIN * WDW; i += 64) {
+      const int r = i / WDW, q = i - r * WDW;
+      uint32_t d = 0;
+      if (q < WDW - 1) {
+        const int y = clampi(by * 16 - RANGE + r, M.h0 - 1), x = bx * 16 - RANGE + q * SPD;
+        if (x >= 0 && x + SPD - 1 <= M.w0 - 1) d = *reinterpret_cast<const uint32_t *>(F + (size_t)y * M.rb0 + (size_t)x * BPS);      // (x * BPS is a multiple of 4)
+        else {
+#pragma unroll
+          for (int k = 0; k < SPD; k++) d |= sample_at<Pix>(F, M.rb0, clampi(x + k, M.w0 - 1), y) << (8 * BPS * k);
+        }
+      }
+      s_win[wave][i] = d;
+    }
+  }
+  __syncthreads();
+  if (live) {
+    uint32_t mask[CDW];                          // the block's true columns
+#pragma unroll
+    for (int q = 0; q < CDW; q++) {
+      mask[q] = 0;
+#pragma unroll
+      for (int k = 0; k < SPD; k++)
+        if (q * SPD + k < bw) mask[q] |= (BPS == 1 ? 0xffu : 0xffffu) << (8 * BPS * k);
+    }
+    const uint32_t bias = ((uint32_t)(bw * bh) * M.t_luma) >> 2;
+    uint32_t best = 0xffffffffu;
+    for (int c = (int)lane; c < CAND; c += 64) {
+      const int dyi = c / SIDE, dxi = c - dyi * SIDE;      // dy + RANGE, dx + RANGE
+      const int q0 = (dxi * BPS) >> 2;
+      const uint32_t sh = (uint32_t)(dxi * BPS) & 3u;
+      uint32_t sad = 0;
+#pragma unroll 1
+      for (int r = 0; r < bh; r++) {
+        const uint32_t *wr = &s_win[wave][(dyi + r) * WDW + q0];
+        const uint32_t *br = &s_blk[wave][r * CDW];
+        uint32_t lo = wr[0];
+#pragma unroll
+        for (int q = 0; q < CDW; q++) {
+          const uint32_t hi = wr[q + 1];
+          const uint32_t f = __builtin_amdgcn_alignbyte(hi, lo, sh) & mask[q];
+          if constexpr (BPS == 1) sad = __builtin_amdgcn_sad_u8(br[q], f, sad);
+          else sad = __builtin_amdgcn_sad_u16(br[q], f, sad);
+          lo = hi;
+        }
+      }
+      const uint32_t rank = c < CENTRE ? (uint32_t)c + 1u : c > CENTRE ? (uint32_t)c : 0u;
+      best = min(best, ((sad + (rank ? bias : 0u)) << 11) | rank);
+    }
+    atomicMin(&s_key[wave], best);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 && pair * 2 + threadIdx.x < nblk) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int f = 0; f < 2; f++) {
+      const int rank = (int)(s_key[threadIdx.x * 2 + f] & 2047u);
+      const int c = rank == 0 ? CENTRE : rank <= CENTRE ? rank - 1 : rank;
+      const int dy = c / SIDE - RANGE, dx = c - (c / SIDE) * SIDE - RANGE;
+      v |= (((uint32_t)dx & 0xffu) | ((uint32_t)dy & 0xffu) << 8) << (16 * f);
+    }
+    vec[pair * 2 + threadIdx.x] = v;
+  }
+}
+
+// grid: per_seg x segments; workgroup = (segment, plane, block row, four blocks across), a wave per block
+template <typename Pix>
+__global__ __launch_bounds__(256) void k_denoise_mc_gather(GrainGeom G, McGeom M, const void *const *table) {
+  constexpr int BPS = (int)sizeof(Pix);
+  constexpr int TS = 18;                         // the neighbourhood tile's side
+  constexpr int RMAX = 23, RS = 32;              // the output region's rows at most, and its row stride in samples (whole 16-byte units)
+  __shared__ uint16_t s_c[4][TS * TS], s_p[4][TS * TS], s_n[4][TS * TS];
+  __shared__ uint32_t s_a[4][TS * TS];
+  __shared__ __attribute__((aligned(16))) Pix s_o[4][RMAX * RS];
+  __shared__ unsigned long long s_sum[4][16];
+  __shared__ uint32_t s_cnt[4][16];
+  const unsigned seg = blockIdx.x / G.per_seg;
+  unsigned wg = blockIdx.x - seg * G.per_seg;
+  int p = 0;
+  if (wg >= G.wgs[0]) { wg -= G.wgs[0]; p = 1; }
+  if (p == 1 && wg >= G.wgs[1]) { wg -= G.wgs[1]; p = 2; }
+#define PL(a) (p == 0 ? a[0] : p == 1 ? a[1] : a[2])
+  const uint32_t rb = PL(G.row_bytes);
+  const int rows = PL(G.rows), w = PL(G.w), h = PL(G.h), ssx = PL(M.ssx), ssy = PL(M.ssy);
+  char *dst = (char *)PL(G.dst) + (size_t)seg * PL(G.plane_bytes);
+#undef PL
+  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  const bool measure = G.partials != nullptr;
+  if (threadIdx.x < 64) { s_sum[threadIdx.x >> 4][threadIdx.x & 15] = 0; s_cnt[threadIdx.x >> 4][threadIdx.x & 15] = 0; }
+  const char *const *tab = reinterpret_cast<const char *const *>(table) + ((size_t)seg * 3 + p) * 3;
+  const char *P = tab[0], *C = tab[1], *N = tab[2];
+  const bool flat = !C, middle = C && P != C && N != C;      // (uniform in the workgroup)
+  const int brow = (int)(wg / M.strips), bx = (int)(wg - (unsigned)brow * M.strips) * 4 + (int)wave;
+  const bool live = bx < M.nbx;
+  const int bwp = 16 >> ssx, bhp = 16 >> ssy;
+  const int x0 = bx * bwp, y0 = brow * bhp;
+  // the true part tw x th (<= 16 x 16) and the region written rw x rh: the plane's last blocks take its padding with them
+  const int tw = live ? min(bwp, w - x0) : 0, th = live ? min(bhp, h - y0) : 0;
+  const int rw = live ? (bx == M.nbx - 1 ? (int)(rb / BPS) - x0 : bwp) : 0, rh = live ? (brow == M.nby - 1 ? rows - y0 : bhp) : 0;
+  if (live && middle) {
+    const uint32_t v = M.vectors[(size_t)seg * (unsigned)(M.nbx * M.nby) + (unsigned)(brow * M.nbx + bx)];
+    const int vxp = (int)(int8_t)(v & 0xffu) >> ssx, vyp = (int)(int8_t)((v >> 8) & 0xffu) >> ssy;      // (arithmetic shifts: floor)
+    const int vxn = (int)(int8_t)((v >> 16) & 0xffu) >> ssx, vyn = (int)(int8_t)(v >> 24) >> ssy;
+    const int ew = tw + 2, n = ew * (th + 2);
+    const uint32_t rcp = 65536u / (uint32_t)ew + 1u;
+    for (int e = (int)lane; e < n; e += 64) {
+      const int j = (int)div_small((uint32_t)e, rcp), i = e - j * ew;
+      const int cx = clampi(x0 - 1 + i, w - 1), cy = clampi(y0 - 1 + j, h - 1);
+      const uint32_t c = sample_at<Pix>(C, rb, cx, cy);
+      const uint32_t a = sample_at<Pix>(P, rb, clampi(cx + vxp, w - 1), clampi(cy + vyp, h - 1)), b = sample_at<Pix>(N, rb, clampi(cx + vxn, w - 1), clampi(cy + vyn, h - 1));
+      const int t = j * TS + i;
+      s_c[wave][t] = (uint16_t)c; s_p[wave][t] = (uint16_t)a; s_n[wave][t] = (uint16_t)b;
+      s_a[wave][t] = (c > a ? c - a : a - c) | (c > b ? c - b : b - c) << 16;
+    }
+  }
+  __syncthreads();
+  if (live) {
+    const uint32_t kden = kRecipDen[lane < 33 ? lane : 32];
+    const uint32_t rcp = 65536u / (uint32_t)rw + 1u;
+    const int n = rw * rh;
+    int bin = -1;                                // the lane's open triple, as in k_denoise_gather
+    unsigned long long acc = 0; uint32_t cnt = 0;
+    auto flush = [&]() {
+      if (bin >= 0) { atomicAdd(&s_sum[wave][bin], acc); atomicAdd(&s_cnt[wave][bin], cnt); }
+      acc = 0; cnt = 0;
+    };
+    for (int e0 = 0; e0 < n; e0 += 64) {         // (every lane of the wave walks the loop: ds_bpermute below reads lanes' registers)
+      const int e = min(e0 + (int)lane, n - 1);
+      const bool mine = e0 + (int)lane < n;
+      const int ry = (int)div_small((uint32_t)e, rcp), rx = e - ry * rw;
+      const int tx = min(rx, tw - 1), ty = min(ry, th - 1);      // the padding repeats the true part's edge
+      uint32_t o = 0;
+      if (middle) {
+        const uint32_t *a = &s_a[wave][ty * TS + tx];
+        const uint32_t d = a[0] + a[1] + a[2] + a[TS] + a[TS + 1] + a[TS + 2] + a[2 * TS] + a[2 * TS + 1] + a[2 * TS + 2];      // (both halves; no carry)
+        const uint32_t Dp = d & 0xffffu, Dn = d >> 16;
+        const uint32_t wp = 16u - __umulhi(16u * min(Dp, G.cut), G.recip), wn = 16u - __umulhi(16u * min(Dn, G.cut), G.recip);
+        const int t = (ty + 1) * TS + tx + 1;
+        const uint32_t c = s_c[wave][t], num = 16u * c + wp * s_p[wave][t] + wn * s_n[wave][t];
+        const uint32_t k = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((wp + wn) << 2), (int)kden);
+        o = (num * k + 32768u) >> 16;
+        if (measure && mine && rx < tw && ry < th && wp + wn >= 24u) {
+          const int b = (int)(o >> G.bin_shift);
+          if (b != bin) { flush(); bin = b; }
+          const int r = (int)c - (int)o;
+          acc += (uint32_t)(r * r); cnt++;
+        }
+      } else if (!flat) o = sample_at<Pix>(C, rb, x0 + tx, y0 + ty);      // an end of the run passes through
+      if (mine) s_o[wave][ry * RS + rx] = (Pix)o;
+    }
+    if (measure) flush();
+  }
+  __syncthreads();
+  if (live) {
+    const int rbytes = rw * BPS;                 // of the region's row: whole dwords, as the plane's rows and x0 * BPS are
+    const bool wide = !(rb & 15u) && !((x0 * BPS) & 15) && !(rbytes & 15);
+    const int units = wide ? rbytes >> 4 : rbytes >> 2, n = units * rh;
+    const uint32_t rcp = 65536u / (uint32_t)units + 1u;
+    char *at = dst + (size_t)y0 * rb + (size_t)x0 * BPS;
+    for (int e = (int)lane; e < n; e += 64) {
+      const int ry = (int)div_small((uint32_t)e, rcp), u = e - ry * units;
+      const char *from = reinterpret_cast<const char *>(&s_o[wave][ry * RS]);
+      if (wide) *reinterpret_cast<uint4 *>(at + (size_t)ry * rb + u * 16) = *reinterpret_cast<const uint4 *>(from + u * 16);
+      else *reinterpret_cast<uint32_t *>(at + (size_t)ry * rb + u * 4) = *reinterpret_cast<const uint32_t *>(from + u * 4);
+    }
+  }
+  if (measure && threadIdx.x < 16) {
+    av1mi_grain_bin b;
+    b.sum_sq = s_sum[0][threadIdx.x] + s_sum[1][threadIdx.x] + s_sum[2][threadIdx.x] + s_sum[3][threadIdx.x];
+    b.count = s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
+    b.reserved = 0;
+    G.partials[(size_t)blockIdx.x * 16 + threadIdx.x] = b;
+  }
+}
+
+namespace {
+// the geometry of the motion-compensated launches: the plain gather's checks, then blocks in place of bands
+hipError_t mc_geometry(const DenoiseMcLaunch &L, GrainGeom &G, McGeom &M) {
+  if (hipError_t e = grain_geometry(L, G)) return e;
+  if ((L.range != 4 && L.range != 8) || L.plane_w[0] <= 0 || L.plane_h[0] <= 0) return hipErrorInvalidValue;
+  M.w0 = L.true_w[0]; M.h0 = L.true_h[0]; M.nbx = (M.w0 + 15) / 16; M.nby = (M.h0 + 15) / 16;
+  M.rb0 = G.row_bytes[0]; M.pairs = ((uint32_t)(M.nbx * M.nby) + 1) / 2; M.strips = ((uint32_t)M.nbx + 3) / 4;
+  M.t_luma = (uint32_t)L.strength << (L.bd - 8); M.vectors = (uint32_t *)L.vectors;
+  G.per_seg = 0;
+  for (int p = 0; p < 3; p++) {
+    const bool have = L.plane_w[p] > 0 && L.plane_h[p] > 0;
+    M.ssx[p] = have && L.plane_w[p] < L.plane_w[0]; M.ssy[p] = have && L.plane_h[p] < L.plane_h[0];
+    // a chroma plane's true size is the luma plane's, halved upwards where it is subsampled: every block then has samples in it
+    if (have && (L.true_w[p] != (M.w0 + M.ssx[p]) >> M.ssx[p] || L.true_h[p] != (M.h0 + M.ssy[p]) >> M.ssy[p])) return hipErrorInvalidValue;
+    G.wgs[p] = have ? (uint32_t)M.nby * M.strips : 0;
+    G.per_seg += G.wgs[p];
+  }
+  if (L.segments > 0 && ((size_t)G.per_seg * L.segments > 0x7FFFFFFFu || (size_t)M.pairs * L.segments > 0x7FFFFFFFu)) return hipErrorInvalidValue;
+  return hipSuccess;
+}
+}  // namespace
+
+size_t denoise_mc_scratch_bytes(const DenoiseMcLaunch &L) {
+  GrainGeom G; McGeom M;
+  if (mc_geometry(L, G, M) != hipSuccess || L.segments <= 0) return 0;
+  return (size_t)G.per_seg * L.segments * 16 * sizeof(av1mi_grain_bin);
+}
+size_t denoise_mc_vector_bytes(const DenoiseMcLaunch &L) {
+  GrainGeom G; McGeom M;
+  if (mc_geometry(L, G, M) != hipSuccess || L.segments <= 0) return 0;
+  return (size_t)M.nbx * M.nby * L.segments * sizeof(av1mi_denoise_vec);
+}
+
+hipError_t launch_denoise_mc_gather(const DenoiseMcLaunch &L, hipStream_t s) {
+  GrainGeom G; McGeom M;
+  if (hipError_t e = mc_geometry(L, G, M)) return e;
+  if (L.segments <= 0) return hipSuccess;
+  if (!L.vectors || (L.records && !L.scratch)) return hipErrorInvalidValue;
+  G.partials = L.records ? (av1mi_grain_bin *)L.scratch : nullptr;
+  const dim3 search(M.pairs * (unsigned)L.segments), grid(G.per_seg * (unsigned)L.segments);
+  if (L.bd == 8 && L.range == 4) hipLaunchKernelGGL((k_denoise_search<uint8_t, 4>), search, dim3(256), 0, s, M, L.table);
+  else if (L.bd == 8) hipLaunchKernelGGL((k_denoise_search<uint8_t, 8>), search, dim3(256), 0, s, M, L.table);
+  else if (L.range == 4) hipLaunchKernelGGL((k_denoise_search<uint16_t, 4>), search, dim3(256), 0, s, M, L.table);
+  else hipLaunchKernelGGL((k_denoise_search<uint16_t, 8>), search, dim3(256), 0, s, M, L.table);
+  if (hipError_t e = hipGetLastError()) return e;
+  if (L.bd == 8) hipLaunchKernelGGL(k_denoise_mc_gather<uint8_t>, grid, dim3(256), 0, s, G, M, L.table);
+  else hipLaunchKernelGGL(k_denoise_mc_gather<uint16_t>, grid, dim3(256), 0, s, G, M, L.table);
   if (hipError_t e = hipGetLastError()) return e;
   if (L.records) hipLaunchKernelGGL(k_grain_sum, dim3(3u * (unsigned)L.segments), dim3(256), 0, s, G, L.records);
   return hipGetLastError();

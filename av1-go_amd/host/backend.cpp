@@ -255,6 +255,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
     // -av1mi_scenecut, or a job that deinterlaces: the frame store holds one group (the deinterlacer's run)
     // -av1mi_denoise: the same store, the denoiser in the gather; -av1mi_film_grain (1 unless told otherwise): parameters in every frame header
     cfg.denoise = job.denoise;
+    cfg.denoise_range = job.denoise_range;
     const bool grainy = job.denoise > 0 && job.film_grain != 0;
     const bool analysed = job.scenecut > 0, stored = analysed || dei != 0 || job.denoise > 0;
     if (stored) cfg.store_frames = S * G;

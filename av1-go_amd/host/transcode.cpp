@@ -207,6 +207,12 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
     else if (args[i] == "-av1mi_denoise") {
       if (!plain_int(args[i + 1], &job->denoise) || job->denoise > 16) { if (err) *err = "Invalid argument: -av1mi_denoise takes a strength 1 .. 16 (0 = off), not " + args[i + 1]; return false; }
     }
+    else if (args[i] == "-av1mi_denoise_range") {
+      if (!plain_int(args[i + 1], &job->denoise_range) || (job->denoise_range != 0 && job->denoise_range != 4 && job->denoise_range != 8)) {
+        if (err) *err = "Invalid argument: -av1mi_denoise_range takes 0 (off), 4 or 8, not " + args[i + 1];
+        return false;
+      }
+    }
     else if (args[i] == "-av1mi_crop") {
       const std::string &v = args[i + 1];
       int n[4];
@@ -294,6 +300,7 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
   }
   if (job->denoise && job->pack10) { if (err) *err = "Invalid argument: -av1mi_denoise keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
   if (job->denoise && job->deinterlace) { if (err) *err = "Invalid argument: -av1mi_denoise filters the group's frames on their way from the store, as -av1mi_deinterlace does: not together with -av1mi_deinterlace"; return false; }
+  if (job->denoise_range && !job->denoise) { if (err) *err = "Invalid argument: -av1mi_denoise_range needs -av1mi_denoise"; return false; }
   if (job->film_grain >= 0 && !job->denoise) { if (err) *err = "Invalid argument: -av1mi_film_grain needs -av1mi_denoise"; return false; }
   if (job->min_gop && !job->scenecut) { if (err) *err = "Invalid argument: -av1mi_min_gop needs -av1mi_scenecut"; return false; }
   if (job->min_gop && job->gop >= 1 && job->min_gop > job->gop - job->gop / 2) { if (err) *err = "Invalid argument: -av1mi_min_gop " + std::to_string(job->min_gop) + " above gop - gop / 2 = " + std::to_string(job->gop - job->gop / 2); return false; }

@@ -601,6 +601,42 @@ typedef struct av1mi_grain_record { av1mi_grain_bin bin[AV1MI_GRAIN_BINS]; } av1
 int av1mi_denoise_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int strength,
                          int segments, const void *const *d_table, void *const d_dst[3], av1mi_grain_record *d_records);
 
+/* ---- motion-compensated denoising: the temporal filter follows the picture.  "denoising" compares a sample with the sample at the same
+ * coordinates of P and N; where the picture moves both weights fall to 0 and nothing is removed.  Here a block search stands in front of
+ * the filter and the filter reads its neighbours DISPLACED.  Integers only, bit exact by definition.  Everything "denoising" says about
+ * geometry, the ends of a run, T, R, K[den], the output's padding and the records holds unchanged; with all vectors 0 this IS that filter.
+ *   blocks    the luma plane's true size w0 x h0 is tiled from (0, 0) in blocks of 16 x 16: ceil(w0 / 16) x ceil(h0 / 16) blocks; the last
+ *             block of a row or column may be partial, with n samples inside the true size.  A sample (x, y) of plane p, subsampled by
+ *             (ssx, ssy) in {0, 1}^2 against luma (from the fed layout's plane sizes: 4:2:0, 4:2:2, 4:4:4 and grey all occur), belongs to
+ *             block ((x << ssx) >> 4, (y << ssy) >> 4).
+ *   search    range 4 or 8.  For each F in {P, N} every block gets one integer vector (dx, dy), |dx|, |dy| <= range:
+ *               SAD(v)  = the sum over the block's n luma samples of |C(x, y) - F(clamp(x + dx), clamp(y + dy))|, full-depth samples,
+ *                         coordinates clamped to the true size: every one of the (2 range + 1)^2 candidates is valid at every block;
+ *               cost(v) = SAD(v) + (v != 0 ? (n T) >> 2 : 0), T the luma threshold strength << (bit_depth - 8);
+ *               the vector is the candidate with the smallest key (cost << 11 | rank); rank 0 is (0, 0), the others follow in raster
+ *               order of (dy, dx) from (-range, -range): the zero vector wins ties, then the earliest candidate.
+ *             cost <= 256 x 1023 + 256 x (16 << 2) / 4 < 2^19 and rank < 2^11: the key is a dword, and an integer minimum over it is the
+ *             same in any order.  The bias keeps still, grainy content at the zero vector: without it the minimum over 289 candidates
+ *             picks the neighbour whose noise happens to correlate with C's, and the filter keeps more grain than the records' model
+ *             assumes.  It costs real motion half a sigma per sample at T = 2 sigma.
+ *   filter    for a sample (x, y) of plane p, its block's vector for F scaled to the plane as (vx, vy) = (dx >> ssx, dy >> ssy)
+ *             (arithmetic shifts: floor):
+ *               D_F(x, y) = the sum over the 3x3 neighbourhood, (cx, cy) clamped, of |C(cx, cy) - F(clamp(cx + vx), clamp(cy + vy))|.
+ *             All nine terms use the vector of the block that holds (x, y), never a neighbouring block's.  The F that enters num is
+ *             F(clamp(x + vx), clamp(y + vy)).  Weights, den, K, out, the "counted" rule, the bins and r = C - out are "denoising"'s.
+ *             An end of a run passes through and is not searched; a flat slot is zeros.
+ *   vectors   one av1mi_denoise_vec per block in block raster order, per segment; an end of a run and a flat slot have zeros.
+ * Sub-sample vectors, overlapped blocks and a hierarchical search are not built. */
+typedef struct av1mi_denoise_vec { int8_t dx_p, dy_p, dx_n, dy_n; } av1mi_denoise_vec;
+/* av1mi_denoise_gather with the search in front of it: its arguments and rules, plus range (4 or 8), a luma plane (plane 0 must exist:
+ * it is what is searched), and chroma true sizes that are the luma plane's, halved upwards where the plane is subsampled.  d_vectors:
+ * segments * ceil(true_w[0] / 16) * ceil(true_h[0] / 16) records in device memory, 4-byte aligned, [segment * blocks + block]; NULL = the
+ * vectors live in the context (grown on demand).  Launches: k_denoise_search (luma, all segments, both neighbours), k_denoise_mc_gather
+ * (all planes and segments), and k_grain_sum where d_records is given.  Asynchronous on the context's stream; AV1MI_K_SCENE in the
+ * profile. */
+int av1mi_denoise_mc_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int strength,
+                            int range, int segments, const void *const *d_table, void *const d_dst[3], av1mi_grain_record *d_records, av1mi_denoise_vec *d_vectors);
+
 /* ---- GOP session: the encoder object a cgo replacement of RunTranscode drives (reference call site
  * internal/daemon/daemon.go:101 -> internal/ffmpeg/transcode.go:194; SURVEY.md §8b "av1mi_open(config) / av1mi_encode /
  * av1mi_flush").  It owns the closed-GOP orchestration and the encoder's filter-parameter POLICY, so that no caller
@@ -724,6 +760,12 @@ typedef struct av1mi_gop_config {
    * KNOWN LIMIT: av1mi_gop_store_analyse and the grain records keep reading whole fed frames, bars included: black bars count as still
    * picture in the scene records and as clean samples in bin 0 of the grain records. */
   int crop_x, crop_y, crop_width, crop_height;
+  /* The range of the denoiser's block search (0 = none: nothing new is allocated, launched or accepted; 4 or 8; "motion-compensated
+   * denoising" above).  Needs denoise.  av1mi_gop_submit_stored then launches k_denoise_search + k_denoise_mc_gather where it launches
+   * k_denoise_gather at range 0; the session owns one scratch of segments x blocks vectors, whose users the main stream orders.  Events,
+   * av1mi_gop_frame.grain and everything behind the fed buffers are as with denoise alone; av1mi_gop_submit_device still does not
+   * denoise. */
+  int denoise_range;
 } av1mi_gop_config;
 
 /* The source layout: what a session opened with a config is FED, as one description.  Everything a caller sizes or strides by — the

@@ -4,8 +4,10 @@
 1. k_denoise_gather + k_grain_sum beside k_frames_gather (the floor) and k_deint_gather on the same batch: 4K 10-bit x 12 segments and
    1080p 8-bit x 12, every leg alternated in one process, HIP events; bytes/s against 3.5 x bytes (the deinterlacer's row) and against the
    denoiser's own 4 x bytes (three reads, one write).
-2. av1mi_run_transcode at q 23 and 24 on tests/synth.py content with Gaussian grain of sigma 2, 4, 8 added per frame, with and without
-   -av1mi_denoise: coded bytes and frames per second, wall clock.
+   k_denoise_search + k_denoise_mc_gather + k_grain_sum (av1mi_denoise_mc_gather, range 4 and 8) are further legs of the same alternation.
+2. av1mi_run_transcode at q 23 and 24 on tests/synth.py content and on a translating clip (tests/denoise_mc_clips.py, 3 / -2 samples per
+   frame), with Gaussian grain of sigma 2, 4, 8 added per frame; without -av1mi_denoise, with it, and with -av1mi_denoise_range 4 and 8:
+   coded bytes and frames per second, wall clock.
 
     python tools/bench_grain.py --out profiles/grain.json
 """
@@ -24,6 +26,7 @@ sys.path[:0] = [os.path.join(ROOT, "av1-go_amd"), os.path.join(ROOT, "tests"), R
 import av1mi  # noqa: E402
 import av1stream  # noqa: E402
 import deint_clips  # noqa: E402
+import denoise_mc_clips  # noqa: E402
 import synth  # noqa: E402
 
 
@@ -45,6 +48,8 @@ def kernels(ctx, w, h, bd, segs, reps=7, launches=10):
     d_dst = [ctx.alloc(segs * b) for b in nbytes]
     d_rec = ctx.alloc(segs * 3 * 16 * 16)
     legs = dict(denoise=lambda: ctx.denoise_gather(bd, sizes, sizes, 4, segs, d_three, d_dst, d_rec),
+                denoise_mc_range4=lambda: ctx.denoise_mc_gather(bd, sizes, sizes, 4, 4, segs, d_three, d_dst, d_rec),
+                denoise_mc_range8=lambda: ctx.denoise_mc_gather(bd, sizes, sizes, 4, 8, segs, d_three, d_dst, d_rec),
                 denoise_no_records=lambda: ctx.denoise_gather(bd, sizes, sizes, 4, segs, d_three, d_dst, None),
                 deint=lambda: ctx.deinterlace_gather(bd, sizes, sizes, 0, segs, d_three, d_dst),
                 frames=lambda: ctx.frames_gather(nbytes, segs, d_one, d_dst))
@@ -76,15 +81,17 @@ def kernels(ctx, w, h, bd, segs, reps=7, launches=10):
 
 def transcodes(w, h, frames, runs=2):
     out = []
-    Y, U, V = synth.frames(w, h, frames, 8, 5)
+    clean = dict(synth=synth.frames(w, h, frames, 8, 5), pan=denoise_mc_clips.translating([(w, h), (w // 2, h // 2), (w // 2, h // 2)], frames, 8, 5, 0))
     with tempfile.TemporaryDirectory() as d:
-        for sigma in (2, 4, 8):
+        for content, sigma in ((c, s) for c in clean for s in (2, 4, 8)):
             rng = np.random.default_rng(sigma)
-            clip = [np.clip(a + np.rint(rng.normal(0, sigma, a.shape)), 0, 255).astype(np.uint8) for a in (Y, U, V)]
-            src = os.path.join(d, "s%d.y4m" % sigma)
+            clip = [np.clip(a + np.rint(rng.normal(0, sigma, a.shape)), 0, 255).astype(np.uint8) for a in clean[content]]
+            src = os.path.join(d, "%s%d.y4m" % (content, sigma))
             deint_clips.write_y4m(src, clip, 8, interlace="p")
+            den = ["-av1mi_denoise", max(sigma, 2) * 2]
             for q in (23, 24):
-                for name, extra in (("plain", []), ("denoise", ["-av1mi_denoise", max(sigma, 2) * 2]), ("denoise_no_film_grain", ["-av1mi_denoise", max(sigma, 2) * 2, "-av1mi_film_grain", 0])):
+                for name, extra in (("plain", []), ("denoise", den), ("denoise_no_film_grain", den + ["-av1mi_film_grain", 0]),
+                                    ("denoise_range4", den + ["-av1mi_denoise_range", 4]), ("denoise_range8", den + ["-av1mi_denoise_range", 8])):
                     fps = []
                     for _ in range(runs):
                         dst = os.path.join(d, "o.mkv")
@@ -92,7 +99,7 @@ def transcodes(w, h, frames, runs=2):
                         code, err = av1stream.run_transcode(["-i", src, "-global_quality:v:0", q, "-g", 30, "-av1mi_segments", 4] + extra + [dst])
                         fps.append(frames / (time.perf_counter() - t0))
                         assert code == 0, err
-                    out.append(dict(size="%dx%d" % (w, h), frames=frames, sigma=sigma, q=q, run=name, args=[str(x) for x in extra], bytes=os.path.getsize(dst), frames_per_s=spread(fps)))
+                    out.append(dict(size="%dx%d" % (w, h), frames=frames, content=content, sigma=sigma, q=q, run=name, args=[str(x) for x in extra], bytes=os.path.getsize(dst), frames_per_s=spread(fps)))
                     print(json.dumps(out[-1]), flush=True)
     return out
 
