@@ -53,6 +53,19 @@ class CdefJob(C.Structure):
                 ("d_skip8", C.c_void_p), ("skip_frame_stride", C.c_size_t)]
 
 
+class DeblockCdefJob(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("bit_depth", C.c_int), ("nframes", C.c_int), ("damping", C.c_int), ("sharpness", C.c_int),
+                ("rec_stride_y", C.c_int), ("rec_stride_uv", C.c_int), ("dbl_stride_y", C.c_int), ("dbl_stride_uv", C.c_int),
+                ("dst_stride_y", C.c_int), ("dst_stride_uv", C.c_int),
+                ("d_rec_y", C.c_void_p), ("d_rec_u", C.c_void_p), ("d_rec_v", C.c_void_p),
+                ("d_dbl_y", C.c_void_p), ("d_dbl_u", C.c_void_p), ("d_dbl_v", C.c_void_p),
+                ("d_dst_y", C.c_void_p), ("d_dst_u", C.c_void_p), ("d_dst_v", C.c_void_p),
+                ("d_mi_y", C.c_void_p), ("d_mi_uv", C.c_void_p), ("mi_stride_y", C.c_int), ("mi_stride_uv", C.c_int),
+                ("mi_frame_stride_y", C.c_size_t), ("mi_frame_stride_uv", C.c_size_t),
+                ("d_sb_strength", C.c_void_p), ("sb_frame_stride", C.c_size_t),
+                ("d_skip8", C.c_void_p), ("skip_frame_stride", C.c_size_t)]
+
+
 class IntraJob(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("bit_depth", C.c_int), ("nframes", C.c_int), ("qindex", C.c_int),
                 ("block_size", C.c_int), ("stride_y", C.c_int), ("stride_uv", C.c_int),
@@ -712,6 +725,11 @@ class Context:
         for b in bufs:
             b.free()
         return out
+
+    # ---- K5 + K6 in one launch
+    def deblock_cdef_frames(self, job):
+        """deblocking and CDEF of stacked 4:2:0 frames in one kernel (include/av1mi.h av1mi_deblock_cdef_frames; job: DeblockCdefJob)"""
+        self._chk(self.lib.av1mi_deblock_cdef_frames(self.h, C.byref(job)))
 
     # ---- K7
     def lr_frames(self, d_cdef, d_dbl, d_out, stride, w, h, bd, ss, unit_size, d_units, unit_frame_stride, nframes):

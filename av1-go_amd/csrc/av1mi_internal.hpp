@@ -93,6 +93,17 @@ struct CdefLaunch {
 };
 hipError_t launch_cdef(const CdefLaunch &L, hipStream_t s);
 
+// K5 + K6 in one kernel (deblock_cdef_kernel.hip): reconstruction -> CDEF output, and the rows of the deblocked planes that K7 reads
+struct DeblockCdefLaunch {
+  const void *rec[3]; void *dbl[3]; void *dst[3];
+  int w, h, rec_stride_y, rec_stride_uv, dbl_stride_y, dbl_stride_uv, dst_stride_y, dst_stride_uv, bd, damping, sharpness, nframes;
+  const uint32_t *mi_y, *mi_uv; int mi_stride_y, mi_stride_uv;   // deblocking mode info of the luma / chroma planes, as DeblockLaunch
+  size_t mi_frame_stride_y, mi_frame_stride_uv;
+  const uint8_t *sb_strength; size_t sb_frame_stride;            // as CdefLaunch
+  const uint8_t *skip8; size_t skip_frame_stride;
+};
+hipError_t launch_deblock_cdef(const DeblockCdefLaunch &L, hipStream_t s);
+
 // K7: loop restoration of one plane, frames stacked vertically
 struct LrLaunch {
   const void *cdef, *dbl; void *out;

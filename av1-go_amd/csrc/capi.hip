@@ -429,6 +429,40 @@ int av1mi_cdef_frames(av1mi_ctx *ctx, const av1mi_cdef_job *j) {
   return AV1MI_OK;
 }
 
+int av1mi_deblock_cdef_frames(av1mi_ctx *ctx, const av1mi_deblock_cdef_job *j) {
+  BIND(ctx);
+  if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
+  if (int rc = check_bd(ctx, j->bit_depth)) return rc;
+  if (j->width <= 0 || j->height <= 0 || (j->width & 7) || (j->height & 7)) return fail(ctx, AV1MI_E_INVAL, "frame %dx%d must be a multiple of 8", j->width, j->height);
+  if (j->damping < 3 || j->damping > 6) return fail(ctx, AV1MI_E_INVAL, "bad damping/nframes");
+  if (int rc = check_nframes(ctx, j->nframes)) return rc;
+  if (j->sharpness < 0 || j->sharpness > 7) return fail(ctx, AV1MI_E_INVAL, "sharpness %d out of range", j->sharpness);
+  const int sy[] = { j->rec_stride_y, j->dbl_stride_y, j->dst_stride_y }, suv[] = { j->rec_stride_uv, j->dbl_stride_uv, j->dst_stride_uv };
+  for (int i = 0; i < 3; i++)
+    if (sy[i] < j->width || suv[i] < j->width / 2 || (sy[i] & 3) || (suv[i] & 3)) return fail(ctx, AV1MI_E_INVAL, "bad strides");
+  if (j->mi_stride_y < j->width / 4 || j->mi_stride_uv < j->width / 8)
+    return fail(ctx, AV1MI_E_INVAL, "bad plane geometry %dx%d strides %d/%d/%d", j->width, j->height, j->rec_stride_y, j->mi_stride_y, j->mi_stride_uv);
+  const void *ptrs[] = { j->d_rec_y, j->d_rec_u, j->d_rec_v, j->d_dbl_y, j->d_dbl_u, j->d_dbl_v, j->d_dst_y, j->d_dst_u, j->d_dst_v };
+  for (const void *p : ptrs) if (!p || ((uintptr_t)p & 7)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned device pointer");
+  for (int a = 0; a < 9; a++)
+    for (int b = a + 1; b < 9; b++) if (ptrs[a] == ptrs[b]) return fail(ctx, AV1MI_E_INVAL, "null or aliased device pointer");
+  if (!j->d_mi_y || !j->d_mi_uv || !j->d_sb_strength || !j->d_skip8) return fail(ctx, AV1MI_E_INVAL, "null map pointer");
+  if (j->nframes == 0) return AV1MI_OK;
+  av1mi::DeblockCdefLaunch L;
+  L.rec[0] = j->d_rec_y; L.rec[1] = j->d_rec_u; L.rec[2] = j->d_rec_v;
+  L.dbl[0] = j->d_dbl_y; L.dbl[1] = j->d_dbl_u; L.dbl[2] = j->d_dbl_v;
+  L.dst[0] = j->d_dst_y; L.dst[1] = j->d_dst_u; L.dst[2] = j->d_dst_v;
+  L.w = j->width; L.h = j->height; L.rec_stride_y = j->rec_stride_y; L.rec_stride_uv = j->rec_stride_uv; L.dbl_stride_y = j->dbl_stride_y;
+  L.dbl_stride_uv = j->dbl_stride_uv; L.dst_stride_y = j->dst_stride_y; L.dst_stride_uv = j->dst_stride_uv;
+  L.bd = j->bit_depth; L.damping = j->damping; L.sharpness = j->sharpness; L.nframes = j->nframes;
+  L.mi_y = j->d_mi_y; L.mi_uv = j->d_mi_uv; L.mi_stride_y = j->mi_stride_y; L.mi_stride_uv = j->mi_stride_uv;
+  L.mi_frame_stride_y = j->mi_frame_stride_y; L.mi_frame_stride_uv = j->mi_frame_stride_uv;
+  L.sb_strength = j->d_sb_strength; L.sb_frame_stride = j->sb_frame_stride; L.skip8 = j->d_skip8; L.skip_frame_stride = j->skip_frame_stride;
+  // (the CDEF kind: the launch takes that kernel's place in every table)
+  { ProfScope ps(ctx, AV1MI_K_CDEF); HIP_TRY(ctx, av1mi::launch_deblock_cdef(L, ctx->stream)); }
+  return AV1MI_OK;
+}
+
 int av1mi_lr_frames(av1mi_ctx *ctx, const void *d_cdef, const void *d_deblocked, void *d_out, int stride, int w, int h,
                     int bd, int subsampled, int unit_size, const int8_t *d_units, size_t unit_frame_stride, int nframes) {
   BIND(ctx);

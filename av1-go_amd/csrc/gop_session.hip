@@ -12,7 +12,7 @@
 //                     main: wait uploaded -> [k_input_convert] -> [k_chroma_convert] -> [k_scale | k_crop_copy]
 //   code_blocks       main: k_intra_pipe | [k_me_down + k_me_coarse] + k_me_int + k_inter_pipe -> kernel_done
 //   download_symbols  down: wait kernel_done -> D2H of the symbols into pinned memory
-//   loop_filters      main: deblock x3, CDEF, LR x3 + decision -> reference -> filters_done;  down: the decision -> downloaded
+//   loop_filters      main: deblock + CDEF (one kernel), LR x3 + decision -> reference -> filters_done;  down: the decision -> downloaded
 //   measure_quality   main: (quality_stats) k_quality_tiles + k_quality_sum, the records written into the slot's pinned memory -> quality_done
 //   start_coder       side: (GPU entropy coding) wait filters_done -> k_av1_* -> payloads gathered into the slot's pinned buffer -> ent_done
 // Source and symbol buffers exist kSlots = 3 times (slot = batch % 3): batch t + 2 uploads while batch t + 1 is in the block
@@ -746,24 +746,43 @@ static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
   const int w = c.width, h = c.height, S = c.segments, bd = c.bit_depth, key = s.frame_type == 0;
   const av1mi_frame_params &P = s.params;
   G_TRY(follow_q(g, s));
-  for (int p = 0; p < 3; p++) {
-    const Plane &L = g->plane[p];
-    G_TRY(av1mi_deblock_frames(g->ctx, g->d_rec[p], L.w, g->d_dbl[p], L.w, L.w, L.h, bd, L.ss, (const uint32_t *)g->d_mi[key && g->key32 ? 2 : s.frame_type][L.ss], L.w / 4, 0,
-                               P.lf_sharpness, S));
-  }
-  av1mi_cdef_job cj;
-  memset(&cj, 0, sizeof(cj));
-  cj.width = w; cj.height = h; cj.bit_depth = bd; cj.nframes = S; cj.damping = P.cdef_damping; cj.stride_y = g->plane[0].w; cj.stride_uv = g->plane[1].w;
-  cj.d_src_y = g->d_dbl[0]; cj.d_src_u = g->d_dbl[1]; cj.d_src_v = g->d_dbl[2];
-  cj.d_dst_y = g->d_cdef[0]; cj.d_dst_u = g->d_cdef[1]; cj.d_dst_v = g->d_cdef[2];
-  cj.d_sb_strength = (const uint8_t *)g->d_cdef_sb[s.frame_type]; cj.sb_frame_stride = 0;
+  void *const *mi = g->d_mi[key && g->key32 ? 2 : s.frame_type];
   // key frames are coded with skip = 0 everywhere (no block is exempt from CDEF); P frames: the kernel's skip flags, per frame
   // (the slot's next inter kernel is kSlots batches away and ordered behind this CDEF on the main stream, nothing else writes them)
-  cj.d_skip8 = (const uint8_t *)(key ? g->d_zero_skip : s.d_skip); cj.skip_frame_stride = key ? 0 : (size_t)(w / 8) * (h / 8);
-  G_TRY(av1mi_cdef_frames(g->ctx, &cj));
-  // a true size that is not a multiple of 8: the decoder's restoration clamps at the true last column / row (CDEF above read the
-  // planes as they were: it works on the coded size in a decoder too)
+  const uint8_t *skip8 = (const uint8_t *)(key ? g->d_zero_skip : s.d_skip);
+  const size_t skip_frame_stride = key ? 0 : (size_t)(w / 8) * (h / 8);
+  // a true size that is not a multiple of 8: the decoder's restoration clamps at the true last column / row (CDEF reads the planes
+  // as they are: it works on the coded size in a decoder too)
   const bool padded = g->vw != w || g->vh != h;
+  if (!padded) {
+    // deblocking and CDEF in one kernel: the deblocked samples stay in LDS, and d_dbl receives only the rows restoration reads
+    av1mi_deblock_cdef_job fj;
+    memset(&fj, 0, sizeof(fj));
+    fj.width = w; fj.height = h; fj.bit_depth = bd; fj.nframes = S; fj.damping = P.cdef_damping; fj.sharpness = P.lf_sharpness;
+    fj.rec_stride_y = fj.dbl_stride_y = fj.dst_stride_y = g->plane[0].w; fj.rec_stride_uv = fj.dbl_stride_uv = fj.dst_stride_uv = g->plane[1].w;
+    fj.d_rec_y = g->d_rec[0]; fj.d_rec_u = g->d_rec[1]; fj.d_rec_v = g->d_rec[2];
+    fj.d_dbl_y = g->d_dbl[0]; fj.d_dbl_u = g->d_dbl[1]; fj.d_dbl_v = g->d_dbl[2];
+    fj.d_dst_y = g->d_cdef[0]; fj.d_dst_u = g->d_cdef[1]; fj.d_dst_v = g->d_cdef[2];
+    fj.d_mi_y = (const uint32_t *)mi[0]; fj.d_mi_uv = (const uint32_t *)mi[1]; fj.mi_stride_y = g->plane[0].w / 4; fj.mi_stride_uv = g->plane[1].w / 4;
+    fj.d_sb_strength = (const uint8_t *)g->d_cdef_sb[s.frame_type]; fj.sb_frame_stride = 0;
+    fj.d_skip8 = skip8; fj.skip_frame_stride = skip_frame_stride;
+    G_TRY(av1mi_deblock_cdef_frames(g->ctx, &fj));
+  } else {
+    // the two kernels on their own: extend_plane below replicates row vh - 1 and column vw - 1 of the WHOLE deblocked planes
+    // (restoration's boundary rows are clamped at the true size), and the fused kernel writes only four rows in 64 of them
+    for (int p = 0; p < 3; p++) {
+      const Plane &L = g->plane[p];
+      G_TRY(av1mi_deblock_frames(g->ctx, g->d_rec[p], L.w, g->d_dbl[p], L.w, L.w, L.h, bd, L.ss, (const uint32_t *)mi[L.ss], L.w / 4, 0, P.lf_sharpness, S));
+    }
+    av1mi_cdef_job cj;
+    memset(&cj, 0, sizeof(cj));
+    cj.width = w; cj.height = h; cj.bit_depth = bd; cj.nframes = S; cj.damping = P.cdef_damping; cj.stride_y = g->plane[0].w; cj.stride_uv = g->plane[1].w;
+    cj.d_src_y = g->d_dbl[0]; cj.d_src_u = g->d_dbl[1]; cj.d_src_v = g->d_dbl[2];
+    cj.d_dst_y = g->d_cdef[0]; cj.d_dst_u = g->d_cdef[1]; cj.d_dst_v = g->d_cdef[2];
+    cj.d_sb_strength = (const uint8_t *)g->d_cdef_sb[s.frame_type]; cj.sb_frame_stride = 0;
+    cj.d_skip8 = skip8; cj.skip_frame_stride = skip_frame_stride;
+    G_TRY(av1mi_cdef_frames(g->ctx, &cj));
+  }
   if (padded)
     for (int p = 0; p < 3; p++) { G_TRY(extend_plane(g, g->plane[p], g->d_dbl[p])); G_TRY(extend_plane(g, g->plane[p], g->d_cdef[p])); }
   // loop restoration of every frame, and the decision per segment and plane whether it stays ON (it must lower the squared error

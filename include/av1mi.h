@@ -199,6 +199,26 @@ typedef struct av1mi_cdef_job {
 } av1mi_cdef_job;
 int av1mi_cdef_frames(av1mi_ctx *ctx, const av1mi_cdef_job *job);
 
+/* ---- K5 + K6 in one launch: deblocking of the three planes and CDEF of nframes 4:2:0 frames stacked vertically, the deblocked
+ * samples never leaving the chip.  d_rec_*: the reconstruction (what av1mi_deblock_frames takes as d_src); d_dst_*: the CDEF output,
+ * bit for bit what av1mi_deblock_frames on each plane followed by av1mi_cdef_frames gives.  d_dbl_*: the deblocked planes, of which
+ * ONLY the rows loop restoration reads beyond its stripe boundaries are written (luma rows 64k - 10 .. 64k - 7, chroma rows
+ * 32k - 6 .. 32k - 3, for k >= 1 with 64k - 8 < height); every other sample keeps what it held.  So d_dbl_* serve av1mi_lr_frames /
+ * av1mi_lr_yuv_decide as d_deblocked and nothing else.  width/height: luma size, multiples of 8.  d_mi_y / d_mi_uv: the mode-info
+ * units of the luma plane and of a chroma plane (U and V share them), see av1mi_deblock_plane; mi_stride_* in units,
+ * mi_frame_stride_* units between frames, 0 = one shared map.  The other fields as in av1mi_cdef_job.  All nine planes distinct. */
+typedef struct av1mi_deblock_cdef_job {
+  int width, height, bit_depth, nframes, damping, sharpness;
+  int rec_stride_y, rec_stride_uv, dbl_stride_y, dbl_stride_uv, dst_stride_y, dst_stride_uv;
+  const void *d_rec_y, *d_rec_u, *d_rec_v;
+  void *d_dbl_y, *d_dbl_u, *d_dbl_v;
+  void *d_dst_y, *d_dst_u, *d_dst_v;
+  const uint32_t *d_mi_y, *d_mi_uv; int mi_stride_y, mi_stride_uv; size_t mi_frame_stride_y, mi_frame_stride_uv;
+  const uint8_t *d_sb_strength; size_t sb_frame_stride;
+  const uint8_t *d_skip8; size_t skip_frame_stride;
+} av1mi_deblock_cdef_job;
+int av1mi_deblock_cdef_frames(av1mi_ctx *ctx, const av1mi_deblock_cdef_job *job);
+
 /* ---- K7: loop restoration (AV1 spec §7.17) of one plane of nframes frames stacked vertically.  d_cdef: the CDEF
  * output, d_deblocked: the deblocked (pre-CDEF) plane used beyond stripe boundaries, d_out: the restored plane
  * (distinct from both).  subsampled = 1 for the chroma planes of 4:2:0 (32-row stripes offset by 4), 0 for luma.
