@@ -632,15 +632,20 @@ class Context:
         dst = (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_dst])
         self._chk(self.lib.av1mi_frames_gather(self.h, nb, int(segments), d_table.ptr, dst))
 
+    @staticmethod
+    def _gather_planes(plane_sizes, true_sizes, d_dst):
+        """the filtering gathers' plane_w, plane_h, true_w, true_h (int[3] each) and d_dst (void *[3], null for an absent plane)"""
+        arr = lambda v: (C.c_int * 3)(*[int(x) for x in v])
+        sizes = [arr([s[i] for s in v]) for v in (plane_sizes, true_sizes) for i in (0, 1)]
+        return sizes, (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_dst])
+
     def deinterlace_gather(self, bit_depth, plane_sizes, true_sizes, parity, segments, d_table, d_dst):
         """one launch: the gather with the deinterlacer in it (av1mi_deinterlace_gather).  plane_sizes / true_sizes: (w, h) in samples per
         plane, (0, 0) = no such plane; d_table: DevBuf of segments * 9 uint64, [(s * 3 + p) * 3 + i] = plane p of segment s's frame P, C, N
         (C 0 = zeros); d_dst[p]: DevBuf (None for an absent plane); asynchronous"""
         self.lib.av1mi_deinterlace_gather.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        arr = lambda v: (C.c_int * 3)(*[int(x) for x in v])
-        dst = (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_dst])
-        self._chk(self.lib.av1mi_deinterlace_gather(self.h, int(bit_depth), arr([s[0] for s in plane_sizes]), arr([s[1] for s in plane_sizes]),
-                                                    arr([s[0] for s in true_sizes]), arr([s[1] for s in true_sizes]), int(parity), int(segments), d_table.ptr, dst))
+        sizes, dst = self._gather_planes(plane_sizes, true_sizes, d_dst)
+        self._chk(self.lib.av1mi_deinterlace_gather(self.h, int(bit_depth), *sizes, int(parity), int(segments), d_table.ptr, dst))
 
     def crop_analyse(self, Y, bit_depth, true_size, limit=24):
         """the margins (CROP_DTYPE [frames]) of luma planes Y [frames, H8, W8], H8 and W8 multiples of 8, whose picture is true_size =
@@ -661,10 +666,8 @@ class Context:
         the parity; d_records: DevBuf of segments * 3 records (GRAIN_DTYPE [segments, 3, GRAIN_BINS]) or None = nothing is measured;
         asynchronous"""
         self.lib.av1mi_denoise_gather.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        arr = lambda v: (C.c_int * 3)(*[int(x) for x in v])
-        dst = (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_dst])
-        self._chk(self.lib.av1mi_denoise_gather(self.h, int(bit_depth), arr([s[0] for s in plane_sizes]), arr([s[1] for s in plane_sizes]),
-                                                arr([s[0] for s in true_sizes]), arr([s[1] for s in true_sizes]), int(strength), int(segments), d_table.ptr, dst,
+        sizes, dst = self._gather_planes(plane_sizes, true_sizes, d_dst)
+        self._chk(self.lib.av1mi_denoise_gather(self.h, int(bit_depth), *sizes, int(strength), int(segments), d_table.ptr, dst,
                                                 d_records.ptr if d_records is not None else None))
 
     def denoise_mc_gather(self, bit_depth, plane_sizes, true_sizes, strength, rng, segments, d_table, d_dst, d_records=None, d_vectors=None):
@@ -672,10 +675,8 @@ class Context:
         strength; d_vectors: DevBuf of segments * blocks records (DENOISE_VEC_DTYPE [segments, blocks], blocks = ceil(w / 16) * ceil(h / 16)
         of the luma plane's true size) or None = the vectors stay in the context; asynchronous"""
         self.lib.av1mi_denoise_mc_gather.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4
-        arr = lambda v: (C.c_int * 3)(*[int(x) for x in v])
-        dst = (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_dst])
-        self._chk(self.lib.av1mi_denoise_mc_gather(self.h, int(bit_depth), arr([s[0] for s in plane_sizes]), arr([s[1] for s in plane_sizes]),
-                                                   arr([s[0] for s in true_sizes]), arr([s[1] for s in true_sizes]), int(strength), int(rng), int(segments), d_table.ptr, dst,
+        sizes, dst = self._gather_planes(plane_sizes, true_sizes, d_dst)
+        self._chk(self.lib.av1mi_denoise_mc_gather(self.h, int(bit_depth), *sizes, int(strength), int(rng), int(segments), d_table.ptr, dst,
                                                    d_records.ptr if d_records is not None else None, d_vectors.ptr if d_vectors is not None else None))
 
     def prof_enable(self, on):

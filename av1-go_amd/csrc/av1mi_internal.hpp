@@ -215,24 +215,26 @@ hipError_t launch_scene(const SceneLaunch &S, hipStream_t s);
 // the gather (scene_kernels.hip): table[segment * 3 + plane] = where that segment's plane of plane_bytes[plane] bytes lies in device
 // memory (16-byte aligned), or null = zeros -> dst[plane] + segment * plane_bytes[plane]; ONE launch.  table is device memory.
 hipError_t launch_frames_gather(const size_t plane_bytes[3], int segments, const void *const *table, void *const dst[3], hipStream_t s);
-// the deinterlacing gather (deint_kernels.hip, include/av1mi.h "deinterlacing"): the gather above with the filter in it.  table[(segment *
-// 3 + plane) * 3 + {0, 1, 2}] = that segment's plane of frames P, C and N in device memory (the run's clamping applied by the caller;
-// C null = zeros); plane_w x plane_h: the buffers' size in samples (0 = no such plane), true_w x true_h the size the filter works at,
-// less than 8 below it; bd 8 = uint8 samples, else uint16; parity 0 = the even lines are kept.  ONE launch.
-struct DeintLaunch {
-  int bd, parity, segments;
+// the fed planes of a filtering gather (gather_cells.hpp): table[(segment * 3 + plane) * 3 + {0, 1, 2}] = that segment's plane of frames
+// P, C and N in device memory (the run's clamping applied by the caller; C null = zeros); plane_w x plane_h: the buffers' size in samples
+// (0 = no such plane), true_w x true_h the size the filter works at, less than 8 below it; bd 8 = uint8 samples, else uint16
+struct GatherPlanes {
+  int bd, segments;
   int plane_w[3], plane_h[3], true_w[3], true_h[3];
   const void *const *table; void *dst[3];
 };
+// the deinterlacing gather (deint_kernels.hip, include/av1mi.h "deinterlacing"): the gather above with the filter in it; parity 0 = the
+// even lines are kept.  ONE launch.
+struct DeintLaunch : GatherPlanes {
+  int parity;
+};
 hipError_t launch_deint_gather(const DeintLaunch &L, hipStream_t s);
 
-// the denoising gather (grain_kernels.hip, include/av1mi.h "denoising" / "grain records"): launch_deint_gather's table and geometry with a
-// strength (1 .. 16) in place of the parity; bd 8 or 10.  records: segments * 3 records (device or pinned host memory), or null = nothing
-// is measured, ONE launch; else two, and scratch holds grain_scratch_bytes(L) bytes (8-byte aligned) of per-workgroup partials.
-struct DenoiseLaunch {
-  int bd, strength, segments;
-  int plane_w[3], plane_h[3], true_w[3], true_h[3];
-  const void *const *table; void *dst[3];
+// the denoising gather (grain_kernels.hip, include/av1mi.h "denoising" / "grain records"): a strength (1 .. 16) in place of the parity; bd
+// 8 or 10.  records: segments * 3 records (device or pinned host memory), or null = nothing is measured, ONE launch; else two, and
+// scratch holds grain_scratch_bytes(L) bytes (8-byte aligned) of per-workgroup partials.
+struct DenoiseLaunch : GatherPlanes {
+  int strength;
   void *scratch; av1mi_grain_record *records;
 };
 size_t grain_scratch_bytes(const DenoiseLaunch &L);      // 0 for a geometry the launch refuses

@@ -90,12 +90,13 @@ bool tx_valid(int tx_size, int tx_type) {
   if (c == 3 && h > 32) return false;
   return true;
 }
-int ensure_scratch(av1mi_ctx *ctx, size_t bytes) {
-  if (ctx->scratch_bytes >= bytes) return AV1MI_OK;
-  if (ctx->scratch) (void)hipFree(ctx->scratch);
-  ctx->scratch = nullptr; ctx->scratch_bytes = 0;
-  HIP_TRY(ctx, hipMalloc(&ctx->scratch, bytes));
-  ctx->scratch_bytes = bytes;
+// one of the context's scratch areas, grown on demand to hold `need` bytes (hipFree waits for the launches that still read the old one)
+int grow(av1mi_ctx *ctx, void **buf, size_t *bytes, size_t need) {
+  if (*bytes >= need) return AV1MI_OK;
+  if (*buf) (void)hipFree(*buf);
+  *buf = nullptr; *bytes = 0;
+  HIP_TRY(ctx, hipMalloc(buf, need));
+  *bytes = need;
   return AV1MI_OK;
 }
 // the argument rules that every entry point states in the same words
@@ -111,6 +112,28 @@ int check_tx_launch(av1mi_ctx *ctx, int tx_size, const void *coef, const void *p
   if (nblocks < 0) return fail(ctx, AV1MI_E_INVAL, "nblocks %d < 0", nblocks);
   if (stride <= 0 || (stride & 3)) return fail(ctx, AV1MI_E_INVAL, "stride %d must be a positive multiple of 4", stride);
   if (((uintptr_t)coef & 15) || ((uintptr_t)plane & 7)) return fail(ctx, AV1MI_E_INVAL, "misaligned device pointer");
+  return AV1MI_OK;
+}
+// the fed planes of a filtering gather (av1mi_deinterlace_gather, av1mi_denoise_gather, av1mi_denoise_mc_gather: `name`), checked and
+// written into L: bit depth 8 .. max_bd, the segments, per plane the sizes, the destination and, under cell_rule, that the last 16-byte
+// cell of a row starts inside the true width
+int check_gather_planes(av1mi_ctx *ctx, const char *name, int max_bd, bool cell_rule, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3],
+                        const int true_h[3], int segments, const void *const *d_table, void *const d_dst[3], av1mi::GatherPlanes &L) {
+  if (bit_depth != 8 && bit_depth != 10 && (bit_depth != 12 || max_bd < 12)) return fail(ctx, AV1MI_E_INVAL, "%s: bit depth %d not supported (%s)", name, bit_depth, max_bd < 12 ? "8 or 10" : "8, 10 or 12");
+  if (segments < 1 || segments > 4096) return fail(ctx, AV1MI_E_INVAL, "%s: segments %d out of range (1 .. 4096)", name, segments);
+  L.bd = bit_depth; L.segments = segments; L.table = d_table;
+  const int bps = bit_depth == 8 ? 1 : 2;
+  for (int p = 0; p < 3; p++) {
+    const bool have = plane_w[p] > 0 && plane_h[p] > 0;
+    if (plane_w[p] < 0 || plane_h[p] < 0 || plane_w[p] > 16384 || plane_h[p] > 16384 || ((size_t)plane_w[p] * bps & 3))
+      return fail(ctx, AV1MI_E_INVAL, "%s: plane %d of %dx%d samples (rows of whole dwords, up to 16384x16384)", name, p, plane_w[p], plane_h[p]);
+    if (have && (true_w[p] < 1 || true_h[p] < 1 || true_w[p] > plane_w[p] || true_h[p] > plane_h[p] || plane_w[p] - true_w[p] >= 8 || plane_h[p] - true_h[p] >= 8))
+      return fail(ctx, AV1MI_E_INVAL, "%s: plane %d: the true size %dx%d must lie within 7 samples below the buffer's %dx%d", name, p, true_w[p], true_h[p], plane_w[p], plane_h[p]);
+    if (cell_rule && have && (plane_w[p] * bps - 1) / 16 * (16 / bps) > true_w[p] - 1)
+      return fail(ctx, AV1MI_E_INVAL, "%s: plane %d: the last 16-byte cell of a row of %d samples starts beyond the true width %d", name, p, plane_w[p], true_w[p]);
+    if (have && (!d_dst[p] || ((uintptr_t)d_dst[p] & 15))) return fail(ctx, AV1MI_E_INVAL, "%s: null or misaligned destination (plane %d)", name, p);
+    L.plane_w[p] = have ? plane_w[p] : 0; L.plane_h[p] = have ? plane_h[p] : 0; L.true_w[p] = true_w[p]; L.true_h[p] = true_h[p]; L.dst[p] = d_dst[p];
+  }
   return AV1MI_OK;
 }
 
@@ -621,13 +644,7 @@ int av1mi_quality_planes(av1mi_ctx *ctx, int bit_depth, int width, int height, i
     if ((((uintptr_t)d_src[p] | (uintptr_t)d_dec0[p] | (uintptr_t)(d_dec1 ? d_dec1[p] : nullptr)) & 15) || ((uintptr_t)d_out & 7))
       return fail(ctx, AV1MI_E_INVAL, "misaligned device pointer (planes 16 bytes, records 8)");
   }
-  const size_t need = av1mi::quality_scratch_bytes(bit_depth, width, height, frames);
-  if (ctx->quality_scratch_bytes < need) {      // (hipFree waits for the launches that still read the old one)
-    if (ctx->quality_scratch) (void)hipFree(ctx->quality_scratch);
-    ctx->quality_scratch = nullptr; ctx->quality_scratch_bytes = 0;
-    HIP_TRY(ctx, hipMalloc(&ctx->quality_scratch, need));
-    ctx->quality_scratch_bytes = need;
-  }
+  if (int rc = grow(ctx, &ctx->quality_scratch, &ctx->quality_scratch_bytes, av1mi::quality_scratch_bytes(bit_depth, width, height, frames))) return rc;
   av1mi::QualityLaunch Q;
   Q.bd = bit_depth; Q.w = width; Q.h = height; Q.frames = frames; Q.src = d_src; Q.dec0 = d_dec0; Q.dec1 = d_dec1; Q.sel = d_select;
   Q.scratch = ctx->quality_scratch; Q.out = d_out;
@@ -643,13 +660,7 @@ int av1mi_scene_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, in
     return fail(ctx, AV1MI_E_INVAL, "av1mi_scene_analyse: the planes' size %dx%d must be a multiple of 8 (8 .. 16384)", width, height);
   if (frames < 1 || frames > 65535) return fail(ctx, AV1MI_E_INVAL, "av1mi_scene_analyse: frames %d out of range (1 .. 65535)", frames);
   if (!d_luma || !d_records || ((uintptr_t)d_luma & 15) || ((uintptr_t)d_records & 7)) return fail(ctx, AV1MI_E_INVAL, "av1mi_scene_analyse: null or misaligned device pointer (planes 16 bytes, records 8)");
-  const size_t need = av1mi::scene_layout(width, height, frames).bytes;
-  if (ctx->scene_scratch_bytes < need) {      // (hipFree waits for the launches that still read the old one)
-    if (ctx->scene_scratch) (void)hipFree(ctx->scene_scratch);
-    ctx->scene_scratch = nullptr; ctx->scene_scratch_bytes = 0;
-    HIP_TRY(ctx, hipMalloc(&ctx->scene_scratch, need));
-    ctx->scene_scratch_bytes = need;
-  }
+  if (int rc = grow(ctx, &ctx->scene_scratch, &ctx->scene_scratch_bytes, av1mi::scene_layout(width, height, frames).bytes)) return rc;
   av1mi::SceneLaunch S;
   S.bd = bit_depth; S.w = width; S.h = height; S.frames = frames; S.luma = d_luma; S.scratch = ctx->scene_scratch; S.out = d_records;
   ProfScope ps(ctx, AV1MI_K_SCENE);
@@ -668,13 +679,7 @@ int av1mi_crop_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int
   if (frames < 1 || frames > 65535) return fail(ctx, AV1MI_E_INVAL, "av1mi_crop_analyse: frames %d out of range (1 .. 65535)", frames);
   if (limit < 0 || limit > 255) return fail(ctx, AV1MI_E_INVAL, "av1mi_crop_analyse: limit %d out of range (0 .. 255)", limit);
   if (!d_luma || !d_records || ((uintptr_t)d_luma & 15) || ((uintptr_t)d_records & 3)) return fail(ctx, AV1MI_E_INVAL, "av1mi_crop_analyse: null or misaligned device pointer (planes 16 bytes, records 4)");
-  const size_t need = av1mi::crop_layout(bit_depth, true_width, true_height, frames).bytes;
-  if (ctx->crop_scratch_bytes < need) {      // (hipFree waits for the launches that still read the old one)
-    if (ctx->crop_scratch) (void)hipFree(ctx->crop_scratch);
-    ctx->crop_scratch = nullptr; ctx->crop_scratch_bytes = 0;
-    HIP_TRY(ctx, hipMalloc(&ctx->crop_scratch, need));
-    ctx->crop_scratch_bytes = need;
-  }
+  if (int rc = grow(ctx, &ctx->crop_scratch, &ctx->crop_scratch_bytes, av1mi::crop_layout(bit_depth, true_width, true_height, frames).bytes)) return rc;
   av1mi::CropAnalyseLaunch A;
   A.bd = bit_depth; A.stride = width; A.rows = height; A.w = true_width; A.h = true_height; A.frames = frames; A.limit = limit;
   A.luma = d_luma; A.scratch = ctx->crop_scratch; A.out = d_records;
@@ -700,20 +705,10 @@ int av1mi_deinterlace_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3]
                              int segments, const void *const *d_table, void *const d_dst[3]) {
   BIND(ctx);
   if (!plane_w || !plane_h || !true_w || !true_h || !d_table || !d_dst || ((uintptr_t)d_table & 7)) return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: null pointer or misaligned table");
-  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: bit depth %d not supported (8, 10 or 12)", bit_depth);
   if (parity != 0 && parity != 1) return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: parity %d (0 = top field first, 1 = bottom field first)", parity);
-  if (segments < 1 || segments > 4096) return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: segments %d out of range (1 .. 4096)", segments);
   av1mi::DeintLaunch L;
-  L.bd = bit_depth; L.parity = parity; L.segments = segments; L.table = d_table;
-  for (int p = 0; p < 3; p++) {
-    const bool have = plane_w[p] > 0 && plane_h[p] > 0;
-    if (plane_w[p] < 0 || plane_h[p] < 0 || plane_w[p] > 16384 || plane_h[p] > 16384 || ((size_t)plane_w[p] * (bit_depth == 8 ? 1 : 2) & 3))
-      return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: plane %d of %dx%d samples (rows of whole dwords, up to 16384x16384)", p, plane_w[p], plane_h[p]);
-    if (have && (true_w[p] < 1 || true_h[p] < 1 || true_w[p] > plane_w[p] || true_h[p] > plane_h[p] || plane_w[p] - true_w[p] >= 8 || plane_h[p] - true_h[p] >= 8))
-      return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: plane %d: the true size %dx%d must lie within 7 samples below the buffer's %dx%d", p, true_w[p], true_h[p], plane_w[p], plane_h[p]);
-    if (have && (!d_dst[p] || ((uintptr_t)d_dst[p] & 15))) return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather: null or misaligned destination (plane %d)", p);
-    L.plane_w[p] = have ? plane_w[p] : 0; L.plane_h[p] = have ? plane_h[p] : 0; L.true_w[p] = true_w[p]; L.true_h[p] = true_h[p]; L.dst[p] = d_dst[p];
-  }
+  L.parity = parity;
+  if (int rc = check_gather_planes(ctx, "av1mi_deinterlace_gather", 12, false, bit_depth, plane_w, plane_h, true_w, true_h, segments, d_table, d_dst, L)) return rc;
   ProfScope ps(ctx, AV1MI_K_SCENE);
   HIP_TRY(ctx, av1mi::launch_deint_gather(L, ctx->stream));
   return AV1MI_OK;
@@ -724,31 +719,12 @@ int av1mi_denoise_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], co
   BIND(ctx);
   if (!plane_w || !plane_h || !true_w || !true_h || !d_table || !d_dst || ((uintptr_t)d_table & 7) || ((uintptr_t)d_records & 7))
     return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: null pointer, or misaligned table or records");
-  if (bit_depth != 8 && bit_depth != 10) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: bit depth %d not supported (8 or 10)", bit_depth);
   if (strength < 1 || strength > 16) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: strength %d out of range (1 .. 16)", strength);
-  if (segments < 1 || segments > 4096) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: segments %d out of range (1 .. 4096)", segments);
   av1mi::DenoiseLaunch L;
-  L.bd = bit_depth; L.strength = strength; L.segments = segments; L.table = d_table; L.records = d_records; L.scratch = nullptr;
-  const int bps = bit_depth == 8 ? 1 : 2;
-  for (int p = 0; p < 3; p++) {
-    const bool have = plane_w[p] > 0 && plane_h[p] > 0;
-    if (plane_w[p] < 0 || plane_h[p] < 0 || plane_w[p] > 16384 || plane_h[p] > 16384 || ((size_t)plane_w[p] * bps & 3))
-      return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: plane %d of %dx%d samples (rows of whole dwords, up to 16384x16384)", p, plane_w[p], plane_h[p]);
-    if (have && (true_w[p] < 1 || true_h[p] < 1 || true_w[p] > plane_w[p] || true_h[p] > plane_h[p] || plane_w[p] - true_w[p] >= 8 || plane_h[p] - true_h[p] >= 8))
-      return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: plane %d: the true size %dx%d must lie within 7 samples below the buffer's %dx%d", p, true_w[p], true_h[p], plane_w[p], plane_h[p]);
-    if (have && (plane_w[p] * bps - 1) / 16 * (16 / bps) > true_w[p] - 1)
-      return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: plane %d: the last 16-byte cell of a row of %d samples starts beyond the true width %d", p, plane_w[p], true_w[p]);
-    if (have && (!d_dst[p] || ((uintptr_t)d_dst[p] & 15))) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_gather: null or misaligned destination (plane %d)", p);
-    L.plane_w[p] = have ? plane_w[p] : 0; L.plane_h[p] = have ? plane_h[p] : 0; L.true_w[p] = true_w[p]; L.true_h[p] = true_h[p]; L.dst[p] = d_dst[p];
-  }
+  L.strength = strength; L.records = d_records; L.scratch = nullptr;
+  if (int rc = check_gather_planes(ctx, "av1mi_denoise_gather", 10, true, bit_depth, plane_w, plane_h, true_w, true_h, segments, d_table, d_dst, L)) return rc;
   if (d_records) {
-    const size_t need = av1mi::grain_scratch_bytes(L);
-    if (ctx->grain_scratch_bytes < need) {      // (hipFree waits for the launches that still use the old one)
-      if (ctx->grain_scratch) (void)hipFree(ctx->grain_scratch);
-      ctx->grain_scratch = nullptr; ctx->grain_scratch_bytes = 0;
-      HIP_TRY(ctx, hipMalloc(&ctx->grain_scratch, need));
-      ctx->grain_scratch_bytes = need;
-    }
+    if (int rc = grow(ctx, &ctx->grain_scratch, &ctx->grain_scratch_bytes, av1mi::grain_scratch_bytes(L))) return rc;
     L.scratch = ctx->grain_scratch;
     if (!L.scratch) {      // no plane at all: the records are still defined
       HIP_TRY(ctx, hipMemsetAsync(d_records, 0, (size_t)segments * 3 * sizeof(av1mi_grain_record), ctx->stream));
@@ -765,46 +741,26 @@ int av1mi_denoise_mc_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3],
   BIND(ctx);
   if (!plane_w || !plane_h || !true_w || !true_h || !d_table || !d_dst || ((uintptr_t)d_table & 7) || ((uintptr_t)d_records & 7) || ((uintptr_t)d_vectors & 3))
     return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: null pointer, or misaligned table, records or vectors");
-  if (bit_depth != 8 && bit_depth != 10) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: bit depth %d not supported (8 or 10)", bit_depth);
   if (strength < 1 || strength > 16) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: strength %d out of range (1 .. 16)", strength);
   if (range != 4 && range != 8) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: range %d (4 or 8)", range);
-  if (segments < 1 || segments > 4096) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: segments %d out of range (1 .. 4096)", segments);
-  if (plane_w[0] <= 0 || plane_h[0] <= 0) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: no luma plane (%dx%d): it is what the search reads", plane_w[0], plane_h[0]);
   av1mi::DenoiseMcLaunch L;
-  L.bd = bit_depth; L.strength = strength; L.range = range; L.segments = segments; L.table = d_table; L.records = d_records; L.scratch = nullptr; L.vectors = d_vectors;
-  const int bps = bit_depth == 8 ? 1 : 2;
-  for (int p = 0; p < 3; p++) {
-    const bool have = plane_w[p] > 0 && plane_h[p] > 0;
-    if (plane_w[p] < 0 || plane_h[p] < 0 || plane_w[p] > 16384 || plane_h[p] > 16384 || ((size_t)plane_w[p] * bps & 3))
-      return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: plane %d of %dx%d samples (rows of whole dwords, up to 16384x16384)", p, plane_w[p], plane_h[p]);
-    if (have && (true_w[p] < 1 || true_h[p] < 1 || true_w[p] > plane_w[p] || true_h[p] > plane_h[p] || plane_w[p] - true_w[p] >= 8 || plane_h[p] - true_h[p] >= 8))
-      return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: plane %d: the true size %dx%d must lie within 7 samples below the buffer's %dx%d", p, true_w[p], true_h[p], plane_w[p], plane_h[p]);
-    if (have && (plane_w[p] * bps - 1) / 16 * (16 / bps) > true_w[p] - 1)
-      return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: plane %d: the last 16-byte cell of a row of %d samples starts beyond the true width %d", p, plane_w[p], true_w[p]);
-    const int ssx = have && plane_w[p] < plane_w[0], ssy = have && plane_h[p] < plane_h[0];
-    if (have && (true_w[p] != (true_w[0] + ssx) >> ssx || true_h[p] != (true_h[0] + ssy) >> ssy))
+  L.strength = strength; L.range = range; L.records = d_records; L.scratch = nullptr; L.vectors = d_vectors;
+  if (int rc = check_gather_planes(ctx, "av1mi_denoise_mc_gather", 10, true, bit_depth, plane_w, plane_h, true_w, true_h, segments, d_table, d_dst, L)) return rc;
+  if (!L.plane_w[0]) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: no luma plane (%dx%d): it is what the search reads", plane_w[0], plane_h[0]);
+  for (int p = 1; p < 3; p++) {      // (an absent plane has the size 0 in L)
+    const int ssx = L.plane_w[p] && L.plane_w[p] < L.plane_w[0], ssy = L.plane_w[p] && L.plane_h[p] < L.plane_h[0];
+    if (L.plane_w[p] && (true_w[p] != (true_w[0] + ssx) >> ssx || true_h[p] != (true_h[0] + ssy) >> ssy))
       return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: plane %d: the true size %dx%d is not the luma plane's %dx%d%s", p, true_w[p], true_h[p], true_w[0], true_h[0],
                   ssx || ssy ? ", halved upwards where the plane is subsampled" : "");
-    if (have && (!d_dst[p] || ((uintptr_t)d_dst[p] & 15))) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: null or misaligned destination (plane %d)", p);
-    L.plane_w[p] = have ? plane_w[p] : 0; L.plane_h[p] = have ? plane_h[p] : 0; L.true_w[p] = true_w[p]; L.true_h[p] = true_h[p]; L.dst[p] = d_dst[p];
   }
-  // (hipFree waits for the launches that still use the old scratch)
-  auto grow = [&](void **buf, size_t *have, size_t need) -> hipError_t {
-    if (*have >= need) return hipSuccess;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr; *have = 0;
-    if (hipError_t e = hipMalloc(buf, need)) return e;
-    *have = need;
-    return hipSuccess;
-  };
   if (!d_vectors) {
     const size_t need = av1mi::denoise_mc_vector_bytes(L);
     if (!need) return fail(ctx, AV1MI_E_INVAL, "av1mi_denoise_mc_gather: a geometry the launch does not take");
-    HIP_TRY(ctx, grow(&ctx->denoise_vectors, &ctx->denoise_vectors_bytes, need));
+    if (int rc = grow(ctx, &ctx->denoise_vectors, &ctx->denoise_vectors_bytes, need)) return rc;
     L.vectors = (av1mi_denoise_vec *)ctx->denoise_vectors;
   }
   if (d_records) {
-    HIP_TRY(ctx, grow(&ctx->grain_scratch, &ctx->grain_scratch_bytes, av1mi::denoise_mc_scratch_bytes(L)));
+    if (int rc = grow(ctx, &ctx->grain_scratch, &ctx->grain_scratch_bytes, av1mi::denoise_mc_scratch_bytes(L))) return rc;
     L.scratch = ctx->grain_scratch;
   }
   ProfScope ps(ctx, AV1MI_K_SCENE);
@@ -883,15 +839,9 @@ static int inter_launch(av1mi_ctx *ctx, const av1mi_inter_job *j, bool search_on
   L.centres = nullptr;
   return AV1MI_OK;
 }
-// the context's own scratch area of the coarse search, large enough for L (hipFree waits for the launches that still read the old one)
+// the context's own scratch area of the coarse search, large enough for L
 static int ensure_me_scratch(av1mi_ctx *ctx, const av1mi::InterLaunch &L) {
-  const size_t need = av1mi::me_layout(L.w, L.h, L.nframes).bytes;
-  if (ctx->me_scratch_bytes >= need) return AV1MI_OK;
-  if (ctx->me_scratch) (void)hipFree(ctx->me_scratch);
-  ctx->me_scratch = nullptr; ctx->me_scratch_bytes = 0;
-  HIP_TRY(ctx, hipMalloc(&ctx->me_scratch, need));
-  ctx->me_scratch_bytes = need;
-  return AV1MI_OK;
+  return grow(ctx, &ctx->me_scratch, &ctx->me_scratch_bytes, av1mi::me_layout(L.w, L.h, L.nframes).bytes);
 }
 // coarse search (optional) + integer search of L; with a coarse search L.centres is set to the centres in d_me
 static int launch_search(av1mi_ctx *ctx, av1mi::InterLaunch &L, int coarse_range, void *d_me) {
@@ -988,7 +938,7 @@ int av1mi_inv_txfm2d_add(av1mi_ctx *ctx, const int32_t *coef, void *dst, int str
   if (stride < w) return fail(ctx, AV1MI_E_INVAL, "stride %d < width %d", stride, w);
   const int cw = w > 32 ? 32 : w, ch = h > 32 ? 32 : h, bps = bd == 8 ? 1 : 2;
   const size_t coef_bytes = (size_t)cw * ch * 4, pix_bytes = (size_t)w * h * bps;
-  if (int rc = ensure_scratch(ctx, coef_bytes + pix_bytes + 64)) return rc;
+  if (int rc = grow(ctx, &ctx->scratch, &ctx->scratch_bytes, coef_bytes + pix_bytes + 64)) return rc;
   char *d = (char *)ctx->scratch;
   int32_t *d_coef = (int32_t *)d;
   void *d_pix = d + coef_bytes;
@@ -1012,7 +962,7 @@ int av1mi_fwd_txfm2d(av1mi_ctx *ctx, const int16_t *resid, int stride, int32_t *
   if (stride < w) return fail(ctx, AV1MI_E_INVAL, "stride %d < width %d", stride, w);
   const int cw = w > 32 ? 32 : w, ch = h > 32 ? 32 : h;
   const size_t coef_bytes = (size_t)cw * ch * 4, pix_bytes = (size_t)w * h * 2;
-  if (int rc = ensure_scratch(ctx, coef_bytes + pix_bytes + 64)) return rc;
+  if (int rc = grow(ctx, &ctx->scratch, &ctx->scratch_bytes, coef_bytes + pix_bytes + 64)) return rc;
   char *d = (char *)ctx->scratch;
   int32_t *d_coef = (int32_t *)d;
   int16_t *d_res = (int16_t *)(d + coef_bytes);

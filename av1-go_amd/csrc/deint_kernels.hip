@@ -15,6 +15,8 @@
 //             the last cell of a row partly.
 //   padding   output columns beyond the true width repeat the last true column's OUTPUT, output rows beyond the true height the last
 //             true row's: both by construction (a row y >= h is computed as row h - 1).  The input's padding is never used.
+// The launch geometry, the decode of blockIdx.x and of an item, the cells and the padding rule are gather_cells.hpp's, shared with the
+// denoising gathers (grain_kernels.hip); here: the sets, the window and the filter.
 // Arithmetic: include/av1mi.h; restated in numpy by tests/deinterlace_ref.py.  Reference tree: nothing (transcode.go:120).
 #include "av1mi_internal.hpp"
 #include "gather_cells.hpp"
@@ -22,39 +24,7 @@
 namespace av1mi {
 
 namespace {
-constexpr int kBand = 16;      // output rows per item (even)
-
-struct DeintGeom {
-  void *dst[3];
-  uint32_t plane_bytes[3];     // of one segment's plane in the destination (= a frame's plane in the store)
-  uint32_t row_bytes[3];       // multiples of 4
-  int32_t rows[3];             // buffer rows
-  int32_t w[3], h[3];          // true size in samples
-  uint32_t cells[3];           // 16-byte cells per row (the last one may be partial)
-  uint32_t groups[3];          // groups of 64 cells per row
-  uint32_t items[3];           // groups x bands
-  uint32_t wgs[3];             // workgroups per (segment, plane)
-  uint32_t per_seg;
-  int parity, segments;
-};
-
-template <typename Pix>
-__device__ __forceinline__ int elem(const uint32_t *d, int i) {
-  if constexpr (sizeof(Pix) == 1) return (int)((d[i >> 2] >> (8 * (i & 3))) & 0xffu);
-  else return (int)((d[i >> 1] >> (16 * (i & 1))) & 0xffffu);
-}
-
-// samples of a cell -> its dwords, the columns beyond the true width (sample index above `lastj`) repeating the last true one
-template <typename Pix, int NS>
-__device__ __forceinline__ void pack_cell(int o[NS], int lastj, uint32_t c[4]) {
-#pragma unroll
-  for (int j = 1; j < NS; j++) o[j] = j > lastj ? o[j - 1] : o[j];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    if constexpr (sizeof(Pix) == 1) c[q] = (uint32_t)o[4 * q] | (uint32_t)o[4 * q + 1] << 8 | (uint32_t)o[4 * q + 2] << 16 | (uint32_t)o[4 * q + 3] << 24;
-    else c[q] = (uint32_t)o[2 * q] | (uint32_t)o[2 * q + 1] << 16;
-  }
-}
+struct DeintGeom : BandGeom { int parity; };
 
 // one kept row as the filter needs it: the C row's cell with HD dwords on either side (c[HD .. HD + 3] is the cell), and the cells of the
 // same row of P and N
@@ -72,32 +42,16 @@ __global__ __launch_bounds__(256) void k_deint_gather(DeintGeom G, const void *c
   constexpr int HD = (int)sizeof(Pix);           // dwords that hold 3 samples beside a cell (they hold 4)
   constexpr int ND = 4 + 2 * HD;
   constexpr int NW = NS + 6;                     // the window: samples x0 - 3 .. x0 + NS + 2
-  const unsigned seg = blockIdx.x / G.per_seg;
-  unsigned wg = blockIdx.x - seg * G.per_seg;
-  int p = 0;
-  if (wg >= G.wgs[0]) { wg -= G.wgs[0]; p = 1; }
-  if (p == 1 && wg >= G.wgs[1]) { wg -= G.wgs[1]; p = 2; }
-#define PL(a) (p == 0 ? G.a[0] : p == 1 ? G.a[1] : G.a[2])
-  const uint32_t rb = PL(row_bytes), cells = PL(cells), groups = PL(groups), items = PL(items);
-  const int rows = PL(rows), w = PL(w), h = PL(h), k = G.parity;
-  char *dst = (char *)PL(dst) + (size_t)seg * PL(plane_bytes);
-#undef PL
+  const GatherPlane W = gather_plane(G, table);
   const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  const unsigned item = wg * 4u + wave;
-  if (item >= items) return;                     // (uniform in the wave; the kernel has no barrier)
-  const unsigned band = item / groups, grp = item - band * groups;
-  const uint32_t cx = grp * 64u + lane, off = cx * 16u;
-  const bool active = cx < cells, whole = !(rb & 15u);
-  const int r0 = (int)band * kBand, r1 = min(r0 + kBand, rows);
-  const char *const *tab = reinterpret_cast<const char *const *>(table) + ((size_t)seg * 3 + p) * 3;
-  const char *P = tab[0], *C = tab[1], *N = tab[2];
-  if (!C) {                                      // a flat slot
-    const uint32_t z[4] = { 0, 0, 0, 0 };
-    for (int y = r0; y < r1; y++) store_cell(dst + (size_t)y * rb, off, rb, whole, active, z);
-    return;
-  }
-  const int x0 = (int)cx * NS;                   // the cell's first sample; x0 <= w - 1 in every active lane (the buffer is < 8 samples wider)
-  const int lastj = w - 1 - x0;                  // sample of the cell that is the last true column (>= NS: the cell is all true)
+  const unsigned item = W.wg * 4u + wave;
+  if (item >= W.items) return;                   // (uniform in the wave; the kernel has no barrier)
+  const GatherBand B = gather_band<NS>(W, item, lane);
+  if (!W.C) { zero_band(W, B); return; }
+  const uint32_t rb = W.rb, cells = W.cells, cx = B.cx, off = B.off;
+  const bool active = B.active, whole = B.whole;
+  const int h = W.h, k = G.parity, lastj = B.lastj;
+  const char *P = W.P, *C = W.C, *N = W.N;
   const bool first_cell = cx == 0, edge = first_cell || lastj < NS + 2;
 
   // the set of kept row r
@@ -137,19 +91,12 @@ __global__ __launch_bounds__(256) void k_deint_gather(DeintGeom G, const void *c
   RowSet<ND> up, dn;
   int held_up = -1, held_dn = -1;
 #pragma unroll 1
-  for (int y = r0; y < r1; y++) {
+  for (int y = B.r0; y < B.r1; y++) {
     const int ye = min(y, h - 1);
-    char *out_row = dst + (size_t)y * rb;
     if (h == 1 || (ye & 1) == k) {               // a kept row
       if (ye != held_dn) { load_set(dn, ye); held_dn = ye; }
       uint32_t c[4] = { dn.c[HD], dn.c[HD + 1], dn.c[HD + 2], dn.c[HD + 3] };
-      if (lastj < NS - 1) {                      // the cell reaches into the padding
-        int o[NS];
-#pragma unroll
-        for (int j = 0; j < NS; j++) o[j] = elem<Pix>(c, j);
-        pack_cell<Pix, NS>(o, lastj, c);
-      }
-      store_cell(out_row, off, rb, whole, active, c);
+      pass_cell<Pix>(W, B, y, c);
       continue;
     }
     const int ur = ye >= 1 ? ye - 1 : ye + 1, dr = ye + 1 <= h - 1 ? ye + 1 : ye - 1;
@@ -187,30 +134,15 @@ __global__ __launch_bounds__(256) void k_deint_gather(DeintGeom G, const void *c
     }
     uint32_t c[4];
     pack_cell<Pix, NS>(o, lastj, c);
-    store_cell(out_row, off, rb, whole, active, c);
+    store_cell(W.dst + (size_t)y * rb, off, rb, whole, active, c);
   }
 }
 
 hipError_t launch_deint_gather(const DeintLaunch &L, hipStream_t s) {
   DeintGeom G;
-  const uint32_t bps = L.bd == 8 ? 1 : 2;
-  G.per_seg = 0; G.segments = L.segments; G.parity = L.parity;
-  for (int p = 0; p < 3; p++) {
-    const size_t rb = (size_t)L.plane_w[p] * bps, bytes = rb * (size_t)L.plane_h[p];
-    const bool have = L.plane_w[p] > 0 && L.plane_h[p] > 0;
-    if (bytes > 0x7FFFFFF0u || (rb & 3)) return hipErrorInvalidValue;
-    if (have && (L.true_w[p] < 1 || L.true_h[p] < 1 || L.true_w[p] > L.plane_w[p] || L.true_h[p] > L.plane_h[p] || L.plane_w[p] - L.true_w[p] >= 8 ||
-                 L.plane_h[p] - L.true_h[p] >= 8))
-      return hipErrorInvalidValue;
-    G.dst[p] = L.dst[p]; G.plane_bytes[p] = have ? (uint32_t)bytes : 0; G.row_bytes[p] = (uint32_t)rb; G.rows[p] = L.plane_h[p]; G.w[p] = L.true_w[p]; G.h[p] = L.true_h[p];
-    G.cells[p] = have ? (uint32_t)((rb + 15) >> 4) : 0;
-    G.groups[p] = (G.cells[p] + 63) / 64;
-    G.items[p] = have ? G.groups[p] * (uint32_t)((L.plane_h[p] + kBand - 1) / kBand) : 0;
-    G.wgs[p] = (G.items[p] + 3) / 4;
-    G.per_seg += G.wgs[p];
-  }
+  G.parity = L.parity;
+  if (hipError_t e = band_geometry(L, false, G)) return e;
   if (L.segments <= 0 || !G.per_seg) return hipSuccess;
-  if ((size_t)G.per_seg * L.segments > 0x7FFFFFFFu) return hipErrorInvalidValue;
   const dim3 grid(G.per_seg * (unsigned)L.segments);
   if (L.bd == 8) hipLaunchKernelGGL(k_deint_gather<uint8_t>, grid, dim3(256), 0, s, G, L.table);
   else hipLaunchKernelGGL(k_deint_gather<uint16_t>, grid, dim3(256), 0, s, G, L.table);

@@ -216,15 +216,14 @@ enum Stage { kConvert, kChroma, kScale, kCrop };      // the input stages (the c
 bool stage_writes(const av1mi_gop *g, int k, int p) { return !(g->chain[k] == kChroma && p == 0 && g->layout.bit_depth == g->cfg.bit_depth); }
 size_t fed_bytes(const av1mi_gop *g, int p) { return g->layout.plane[p].frame_bytes * (size_t)g->cfg.segments; }      // plane p of a batch as fed
 
-// the fed planes at their true sizes, for the filtering gathers (DeintLaunch / DenoiseLaunch): chroma subsampled where the layout's plane
-// is smaller than the luma buffer
-template <typename Launch>
-void fed_geometry(const av1mi_gop *g, const Slot &s, Launch &L) {
+// the fed planes at their true sizes, for the filtering gathers: chroma subsampled where the layout's plane is smaller than the luma
+// buffer.  s: the slot whose table is read and whose fed buffers are written, or null where only the sizes are asked for
+void fed_geometry(const av1mi_gop *g, const Slot *s, av1mi::GatherPlanes &L) {
   const av1mi_source_layout &Y = g->layout;
-  L.bd = Y.bit_depth; L.segments = g->cfg.segments; L.table = (const void *const *)s.d_table;
+  L.bd = Y.bit_depth; L.segments = g->cfg.segments; L.table = s ? (const void *const *)s->d_table : nullptr;
   for (int p = 0; p < 3; p++) {
     const int sx = Y.plane[p].width < Y.width, sy = Y.plane[p].height < Y.height;
-    L.plane_w[p] = Y.plane[p].width; L.plane_h[p] = Y.plane[p].height; L.dst[p] = s.d_in[p];
+    L.plane_w[p] = Y.plane[p].width; L.plane_h[p] = Y.plane[p].height; L.dst[p] = s ? s->d_in[p] : nullptr;
     L.true_w[p] = (Y.true_width + sx) >> sx; L.true_h[p] = (Y.true_height + sy) >> sy;
   }
 }
@@ -445,8 +444,8 @@ int setup(av1mi_gop *g) {
   if (c.coarse_range) G_TRY(dev_alloc(g, &g->d_me, av1mi::me_layout(w, h, S).bytes));
   if (c.quality_stats) G_TRY(dev_alloc(g, &g->d_quality_scratch, av1mi::quality_scratch_bytes(c.bit_depth, g->vw, g->vh, S)));
   if (c.denoise) {
-    Slot probe; av1mi::DenoiseMcLaunch L{};
-    fed_geometry(g, probe, L);
+    av1mi::DenoiseMcLaunch L{};
+    fed_geometry(g, nullptr, L);
     L.strength = c.denoise; L.range = c.denoise_range;
     const size_t bytes = c.denoise_range ? av1mi::denoise_mc_scratch_bytes(L) : av1mi::grain_scratch_bytes(L);
     if (!bytes) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "denoise %d: the fed layout %dx%d (true %dx%d) is not one the denoising gather takes", c.denoise, g->layout.width,
@@ -586,18 +585,18 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
       av1mi::ProfScope ps(g->ctx, AV1MI_K_SCENE, main);
       if (dei) {
         av1mi::DeintLaunch L;
-        fed_geometry(g, s, L);
+        fed_geometry(g, &s, L);
         L.parity = dei - 1;
         G_HIP(av1mi::launch_deint_gather(L, main));
       } else if (c.denoise_range) {      // the block search, the filter on displaced neighbours, the records as below
         av1mi::DenoiseMcLaunch L;
-        fed_geometry(g, s, L);
+        fed_geometry(g, &s, L);
         L.strength = c.denoise; L.range = c.denoise_range; L.scratch = g->d_grain_scratch; L.records = (av1mi_grain_record *)s.h_grain;
         L.vectors = (av1mi_denoise_vec *)g->d_denoise_vectors;
         G_HIP(av1mi::launch_denoise_mc_gather(L, main));
       } else if (c.denoise) {      // ... and the records of what it removed, straight into the slot's pinned memory
         av1mi::DenoiseLaunch L;
-        fed_geometry(g, s, L);
+        fed_geometry(g, &s, L);
         L.strength = c.denoise; L.scratch = g->d_grain_scratch; L.records = (av1mi_grain_record *)s.h_grain;
         G_HIP(av1mi::launch_denoise_gather(L, main));
       } else G_HIP(av1mi::launch_frames_gather(frame_bytes, S, (const void *const *)s.d_table, s.d_in, main));

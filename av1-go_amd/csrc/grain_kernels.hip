@@ -1,8 +1,9 @@
 // grain_kernels.hip — the denoising gather behind av1mi_gop_config.denoise (include/av1mi.h "denoising", "grain records"): k_denoise_gather
 // stands where k_frames_gather / k_deint_gather stand, and measures what it removes on the way; k_grain_sum adds the measurements up.
 //
-//   work      k_deint_gather's: an item is (segment, plane, band of kBand output rows, group of 64 cells of 16 bytes), a wave owns an item
-//             and walks down its band, a workgroup holds four consecutive items of one (segment, plane).
+//   work      k_deint_gather's, from gather_cells.hpp (band_geometry, gather_plane, gather_band, the cells): an item is (segment, plane,
+//             band of kBand output rows, group of 64 cells of 16 bytes), a wave owns an item and walks down its band, a workgroup holds
+//             four consecutive items of one (segment, plane).
 //   rows      per row and per neighbour frame F the wave computes A = |C - F| of its cell as PACKED 16-bit halves (v_pk_max / min / sub)
 //             and the horizontal 3-sums H = A(x - 1) + A(x) + A(x + 1), two samples per add (no half can carry: 3 x 4095).  H of three
 //             rows is held rolling (previous, current, next); D = their sum (<= 9 x 4095 < 2^16).  Inside a band every row of C, P and
@@ -19,6 +20,7 @@
 //   ends      a frame at an end of its run (P or N is C itself) and a flat slot (C null) are the gather alone: copied, resp. zeros,
 //             and their partials are zero.
 // Arithmetic: include/av1mi.h; restated in numpy by tests/denoise_ref.py.  Reference tree: nothing (it has no denoiser).
+// GrainBins and GrainLane are the records' LDS bins and a lane's open triple, for both denoising gathers.
 // Below them: k_denoise_search and k_denoise_mc_gather, the motion-compensated pair that av1mi_gop_config.denoise_range launches instead.
 #include "av1mi_internal.hpp"
 #include "gather_cells.hpp"
@@ -26,22 +28,41 @@
 namespace av1mi {
 
 namespace {
-constexpr int kBand = 16;      // output rows per item
-
-struct GrainGeom {
-  void *dst[3];
-  uint32_t plane_bytes[3];     // of one segment's plane in the destination (= a frame's plane in the store)
-  uint32_t row_bytes[3];       // multiples of 4
-  int32_t rows[3];             // buffer rows
-  int32_t w[3], h[3];          // true size in samples
-  uint32_t cells[3];           // 16-byte cells per row (the last one may be partial)
-  uint32_t groups[3];          // groups of 64 cells per row
-  uint32_t items[3];           // groups x bands
-  uint32_t wgs[3];             // workgroups per (segment, plane)
-  uint32_t per_seg;
+struct GrainGeom : BandGeom {
   uint32_t cut, recip;         // 27 T and floor(2^32 / (27 T)) + 1
   int bin_shift;               // bit_depth - 4
   av1mi_grain_bin *partials;   // per workgroup 16 bins, [blockIdx.x]; null = nothing is measured
+};
+
+// the records of a workgroup of either denoising gather (in LDS): 16 bins per wave.  The barriers between clear(), the lanes' flushes and
+// store() are the kernel's
+struct GrainBins {
+  unsigned long long sum[4][16];
+  uint32_t cnt[4][16];
+  __device__ __forceinline__ void clear() {
+    if (threadIdx.x < 64) { sum[threadIdx.x >> 4][threadIdx.x & 15] = 0; cnt[threadIdx.x >> 4][threadIdx.x & 15] = 0; }
+  }
+  // the four waves' sets become ONE partial, the workgroup's
+  __device__ __forceinline__ void store(av1mi_grain_bin *partials) const {
+    if (threadIdx.x < 16) {
+      av1mi_grain_bin b;
+      b.sum_sq = sum[0][threadIdx.x] + sum[1][threadIdx.x] + sum[2][threadIdx.x] + sum[3][threadIdx.x];
+      b.count = cnt[0][threadIdx.x] + cnt[1][threadIdx.x] + cnt[2][threadIdx.x] + cnt[3][threadIdx.x];
+      b.reserved = 0;
+      partials[(size_t)blockIdx.x * 16 + threadIdx.x] = b;
+    }
+  }
+};
+// a lane's open (bin, sum, count) triple: the kernel adds residuals to it while the bin stays the same and flushes it into the wave's bins
+// when the bin changes and at the end.  (The update itself stays in the kernels' loops: as a member function it is optimised on its own
+// before it is inlined, and costs the plain gather three register moves per sample.)
+struct GrainLane {
+  int bin = -1;
+  unsigned long long acc = 0; uint32_t cnt = 0;
+  __device__ __forceinline__ void flush(GrainBins &S, unsigned wave) {
+    if (bin >= 0) { atomicAdd(&S.sum[wave][bin], acc); atomicAdd(&S.cnt[wave][bin], cnt); }
+    acc = 0; cnt = 0;
+  }
 };
 
 // K[den - 16] = round(65536 / den), den = 16 .. 48 (include/av1mi.h prints it)
@@ -84,18 +105,6 @@ __device__ __forceinline__ void replicate_halves(uint32_t v[NP], int lastj) {
     v[j >> 1] = (v[j >> 1] & ~(0xffffu << (16 * (j & 1)))) | e << (16 * (j & 1));
   }
 }
-// samples of a cell -> its dwords, the columns beyond the true width (sample index above lastj) repeating the last true one
-template <typename Pix, int NS>
-__device__ __forceinline__ void pack_out(uint32_t o[NS], int lastj, uint32_t c[4]) {
-#pragma unroll
-  for (int j = 1; j < NS; j++) o[j] = j > lastj ? o[j - 1] : o[j];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    if constexpr (sizeof(Pix) == 1) c[q] = o[4 * q] | o[4 * q + 1] << 8 | o[4 * q + 2] << 16 | o[4 * q + 3] << 24;
-    else c[q] = o[2 * q] | o[2 * q + 1] << 16;
-  }
-}
-
 template <int NP>
 struct GrainRow { uint32_t c[4], p[4], n[4], hp[NP], hn[NP]; };      // the cells of a row and its horizontal 3-sums against P and N
 
@@ -106,49 +115,27 @@ template <typename Pix>
 __global__ __launch_bounds__(256) void k_denoise_gather(GrainGeom G, const void *const *table) {
   constexpr int NS = 16 / (int)sizeof(Pix);      // samples per cell
   constexpr int NP = NS / 2;                     // dwords of packed halves per cell
-  __shared__ unsigned long long s_sum[4][16];
-  __shared__ uint32_t s_cnt[4][16];
-  const unsigned seg = blockIdx.x / G.per_seg;
-  unsigned wg = blockIdx.x - seg * G.per_seg;
-  int p = 0;
-  if (wg >= G.wgs[0]) { wg -= G.wgs[0]; p = 1; }
-  if (p == 1 && wg >= G.wgs[1]) { wg -= G.wgs[1]; p = 2; }
-#define PL(a) (p == 0 ? G.a[0] : p == 1 ? G.a[1] : G.a[2])
-  const uint32_t rb = PL(row_bytes), cells = PL(cells), groups = PL(groups), items = PL(items);
-  const int rows = PL(rows), w = PL(w), h = PL(h);
-  char *dst = (char *)PL(dst) + (size_t)seg * PL(plane_bytes);
-#undef PL
+  __shared__ GrainBins s_bins;
+  const GatherPlane W = gather_plane(G, table);
   const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
   const bool measure = G.partials != nullptr;
   if (measure) {
-    if (threadIdx.x < 64) { s_sum[threadIdx.x >> 4][threadIdx.x & 15] = 0; s_cnt[threadIdx.x >> 4][threadIdx.x & 15] = 0; }
+    s_bins.clear();
     __syncthreads();
   }
-  const unsigned item = wg * 4u + wave;
-  if (item < items) {                            // (uniform in the wave)
-    const unsigned band = item / groups, grp = item - band * groups;
-    const uint32_t cx = grp * 64u + lane, off = cx * 16u;
-    const bool active = cx < cells, whole = !(rb & 15u);
-    const int r0 = (int)band * kBand, r1 = min(r0 + kBand, rows);
-    const char *const *tab = reinterpret_cast<const char *const *>(table) + ((size_t)seg * 3 + p) * 3;
-    const char *P = tab[0], *C = tab[1], *N = tab[2];
-    const int x0 = (int)cx * NS;                 // the cell's first sample; x0 <= w - 1 in every active lane (the launcher checks)
-    const int lastj = w - 1 - x0;                // sample of the cell that is the last true column (>= NS: the cell is all true)
-    if (!C) {                                    // a flat slot
-      const uint32_t z[4] = { 0, 0, 0, 0 };
-      for (int y = r0; y < r1; y++) store_cell(dst + (size_t)y * rb, off, rb, whole, active, z);
-    } else if (P == C || N == C) {               // an end of the run: the frame passes through, its padding replicating its edge
-      for (int y = r0; y < r1; y++) {
+  const unsigned item = W.wg * 4u + wave;
+  if (item < W.items) {                          // (uniform in the wave)
+    const GatherBand B = gather_band<NS>(W, item, lane);
+    const uint32_t rb = W.rb, cells = W.cells, cx = B.cx, off = B.off;
+    const bool active = B.active, whole = B.whole;
+    const int h = W.h, lastj = B.lastj;          // (cx * NS <= w - 1 in every active lane: band_geometry's cell rule)
+    const char *P = W.P, *C = W.C, *N = W.N;
+    if (!C) zero_band(W, B);
+    else if (P == C || N == C) {                 // an end of the run: the frame passes through, its padding replicating its edge
+      for (int y = B.r0; y < B.r1; y++) {
         uint32_t c[4];
         load_cell(C + (size_t)min(y, h - 1) * rb, off, rb, whole, active, c);
-        if (lastj < NS - 1) {
-          uint32_t hv[NP], o[NS];
-          halves<Pix, NP>(c, hv);
-#pragma unroll
-          for (int j = 0; j < NS; j++) o[j] = half_of(hv, j);
-          pack_out<Pix, NS>(o, lastj, c);
-        }
-        store_cell(dst + (size_t)y * rb, off, rb, whole, active, c);
+        pass_cell<Pix>(W, B, y, c);
       }
     } else {
       const uint32_t kden = kRecipDen[lane < 33 ? lane : 32];
@@ -196,15 +183,10 @@ __global__ __launch_bounds__(256) void k_denoise_gather(GrainGeom G, const void 
 
       GrainRow<NP> cur, nxt;
       uint32_t php[NP], phn[NP], out[4] = { 0, 0, 0, 0 };
-      int bin = -1;                              // the lane's open triple
-      unsigned long long acc = 0; uint32_t cnt = 0;
-      auto flush = [&]() {
-        if (bin >= 0) { atomicAdd(&s_sum[wave][bin], acc); atomicAdd(&s_cnt[wave][bin], cnt); }
-        acc = 0; cnt = 0;
-      };
+      GrainLane open;
       int held = -1;
 #pragma unroll 1
-      for (int y = r0; y < r1; y++) {
+      for (int y = B.r0; y < B.r1; y++) {
         const int ye = min(y, h - 1);
         if (ye != held) {
           if (held < 0) {                        // the band's first row: cur <- the row above it, nxt <- the row itself
@@ -230,27 +212,21 @@ __global__ __launch_bounds__(256) void k_denoise_gather(GrainGeom G, const void 
             o[j] = (num * k + 32768u) >> 16;
             if (measure && active && y < h && j <= lastj && wp + wn >= 24u) {
               const int b = (int)(o[j] >> G.bin_shift);
-              if (b != bin) { flush(); bin = b; }
+              if (b != open.bin) { open.flush(s_bins, wave); open.bin = b; }
               const int r = (int)c - (int)o[j];
-              acc += (uint32_t)(r * r); cnt++;
+              open.acc += (uint32_t)(r * r); open.cnt++;
             }
           }
-          pack_out<Pix, NS>(o, lastj, out);
+          pack_cell<Pix, NS>(o, lastj, out);
         }
-        store_cell(dst + (size_t)y * rb, off, rb, whole, active, out);
+        store_cell(W.dst + (size_t)y * rb, off, rb, whole, active, out);
       }
-      if (measure) flush();
+      if (measure) open.flush(s_bins, wave);
     }
   }
   if (measure) {
     __syncthreads();
-    if (threadIdx.x < 16) {
-      av1mi_grain_bin b;
-      b.sum_sq = s_sum[0][threadIdx.x] + s_sum[1][threadIdx.x] + s_sum[2][threadIdx.x] + s_sum[3][threadIdx.x];
-      b.count = s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
-      b.reserved = 0;
-      G.partials[(size_t)blockIdx.x * 16 + threadIdx.x] = b;
-    }
+    s_bins.store(G.partials);
   }
 }
 
@@ -278,28 +254,10 @@ __global__ __launch_bounds__(256) void k_grain_sum(GrainGeom G, av1mi_grain_reco
 namespace {
 // the geometry of a launch; hipErrorInvalidValue for what the kernel cannot take
 hipError_t grain_geometry(const DenoiseLaunch &L, GrainGeom &G) {
-  const uint32_t bps = L.bd == 8 ? 1 : 2;
   if (L.strength < 1 || L.strength > 16 || (L.bd != 8 && L.bd != 10)) return hipErrorInvalidValue;
-  G.per_seg = 0;
   G.cut = 27u * ((uint32_t)L.strength << (L.bd - 8)); G.recip = (uint32_t)((1ull << 32) / G.cut) + 1u; G.bin_shift = L.bd - 4;
   G.partials = nullptr;
-  for (int p = 0; p < 3; p++) {
-    const size_t rb = (size_t)L.plane_w[p] * bps, bytes = rb * (size_t)L.plane_h[p];
-    const bool have = L.plane_w[p] > 0 && L.plane_h[p] > 0;
-    if (bytes > 0x7FFFFFF0u || (rb & 3)) return hipErrorInvalidValue;
-    if (have && (L.true_w[p] < 1 || L.true_h[p] < 1 || L.true_w[p] > L.plane_w[p] || L.true_h[p] > L.plane_h[p] || L.plane_w[p] - L.true_w[p] >= 8 ||
-                 L.plane_h[p] - L.true_h[p] >= 8))
-      return hipErrorInvalidValue;
-    G.dst[p] = L.dst[p]; G.plane_bytes[p] = have ? (uint32_t)bytes : 0; G.row_bytes[p] = (uint32_t)rb; G.rows[p] = L.plane_h[p]; G.w[p] = L.true_w[p]; G.h[p] = L.true_h[p];
-    G.cells[p] = have ? (uint32_t)((rb + 15) >> 4) : 0;
-    if (have && (size_t)(G.cells[p] - 1) * (16 / bps) > (size_t)L.true_w[p] - 1) return hipErrorInvalidValue;      // the last cell starts inside the true width
-    G.groups[p] = (G.cells[p] + 63) / 64;
-    G.items[p] = have ? G.groups[p] * (uint32_t)((L.plane_h[p] + kBand - 1) / kBand) : 0;
-    G.wgs[p] = (G.items[p] + 3) / 4;
-    G.per_seg += G.wgs[p];
-  }
-  if (L.segments > 0 && (size_t)G.per_seg * L.segments > 0x7FFFFFFFu) return hipErrorInvalidValue;
-  return hipSuccess;
+  return band_geometry(L, true, G);
 }
 }  // namespace
 
@@ -469,23 +427,17 @@ __global__ __launch_bounds__(256) void k_denoise_mc_gather(GrainGeom G, McGeom M
   __shared__ uint16_t s_c[4][TS * TS], s_p[4][TS * TS], s_n[4][TS * TS];
   __shared__ uint32_t s_a[4][TS * TS];
   __shared__ __attribute__((aligned(16))) Pix s_o[4][RMAX * RS];
-  __shared__ unsigned long long s_sum[4][16];
-  __shared__ uint32_t s_cnt[4][16];
-  const unsigned seg = blockIdx.x / G.per_seg;
-  unsigned wg = blockIdx.x - seg * G.per_seg;
-  int p = 0;
-  if (wg >= G.wgs[0]) { wg -= G.wgs[0]; p = 1; }
-  if (p == 1 && wg >= G.wgs[1]) { wg -= G.wgs[1]; p = 2; }
-#define PL(a) (p == 0 ? a[0] : p == 1 ? a[1] : a[2])
-  const uint32_t rb = PL(G.row_bytes);
-  const int rows = PL(G.rows), w = PL(G.w), h = PL(G.h), ssx = PL(M.ssx), ssy = PL(M.ssy);
-  char *dst = (char *)PL(G.dst) + (size_t)seg * PL(G.plane_bytes);
-#undef PL
+  __shared__ GrainBins s_bins;
+  const GatherPlane W = gather_plane(G, table);
+  const unsigned seg = W.seg, wg = W.wg;
+  const uint32_t rb = W.rb;
+  const int rows = W.rows, w = W.w, h = W.h;
+  const int ssx = W.p == 0 ? M.ssx[0] : W.p == 1 ? M.ssx[1] : M.ssx[2], ssy = W.p == 0 ? M.ssy[0] : W.p == 1 ? M.ssy[1] : M.ssy[2];
+  char *dst = W.dst;
+  const char *P = W.P, *C = W.C, *N = W.N;
   const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
   const bool measure = G.partials != nullptr;
-  if (threadIdx.x < 64) { s_sum[threadIdx.x >> 4][threadIdx.x & 15] = 0; s_cnt[threadIdx.x >> 4][threadIdx.x & 15] = 0; }
-  const char *const *tab = reinterpret_cast<const char *const *>(table) + ((size_t)seg * 3 + p) * 3;
-  const char *P = tab[0], *C = tab[1], *N = tab[2];
+  s_bins.clear();                                // (the barrier below stands before the first flush)
   const bool flat = !C, middle = C && P != C && N != C;      // (uniform in the workgroup)
   const int brow = (int)(wg / M.strips), bx = (int)(wg - (unsigned)brow * M.strips) * 4 + (int)wave;
   const bool live = bx < M.nbx;
@@ -515,12 +467,7 @@ __global__ __launch_bounds__(256) void k_denoise_mc_gather(GrainGeom G, McGeom M
     const uint32_t kden = kRecipDen[lane < 33 ? lane : 32];
     const uint32_t rcp = 65536u / (uint32_t)rw + 1u;
     const int n = rw * rh;
-    int bin = -1;                                // the lane's open triple, as in k_denoise_gather
-    unsigned long long acc = 0; uint32_t cnt = 0;
-    auto flush = [&]() {
-      if (bin >= 0) { atomicAdd(&s_sum[wave][bin], acc); atomicAdd(&s_cnt[wave][bin], cnt); }
-      acc = 0; cnt = 0;
-    };
+    GrainLane open;
     for (int e0 = 0; e0 < n; e0 += 64) {         // (every lane of the wave walks the loop: ds_bpermute below reads lanes' registers)
       const int e = min(e0 + (int)lane, n - 1);
       const bool mine = e0 + (int)lane < n;
@@ -538,14 +485,14 @@ __global__ __launch_bounds__(256) void k_denoise_mc_gather(GrainGeom G, McGeom M
         o = (num * k + 32768u) >> 16;
         if (measure && mine && rx < tw && ry < th && wp + wn >= 24u) {
           const int b = (int)(o >> G.bin_shift);
-          if (b != bin) { flush(); bin = b; }
+          if (b != open.bin) { open.flush(s_bins, wave); open.bin = b; }
           const int r = (int)c - (int)o;
-          acc += (uint32_t)(r * r); cnt++;
+          open.acc += (uint32_t)(r * r); open.cnt++;
         }
       } else if (!flat) o = sample_at<Pix>(C, rb, x0 + tx, y0 + ty);      // an end of the run passes through
       if (mine) s_o[wave][ry * RS + rx] = (Pix)o;
     }
-    if (measure) flush();
+    if (measure) open.flush(s_bins, wave);
   }
   __syncthreads();
   if (live) {
@@ -561,13 +508,7 @@ __global__ __launch_bounds__(256) void k_denoise_mc_gather(GrainGeom G, McGeom M
       else *reinterpret_cast<uint32_t *>(at + (size_t)ry * rb + u * 4) = *reinterpret_cast<const uint32_t *>(from + u * 4);
     }
   }
-  if (measure && threadIdx.x < 16) {
-    av1mi_grain_bin b;
-    b.sum_sq = s_sum[0][threadIdx.x] + s_sum[1][threadIdx.x] + s_sum[2][threadIdx.x] + s_sum[3][threadIdx.x];
-    b.count = s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
-    b.reserved = 0;
-    G.partials[(size_t)blockIdx.x * 16 + threadIdx.x] = b;
-  }
+  if (measure) s_bins.store(G.partials);
 }
 
 namespace {
@@ -606,7 +547,7 @@ size_t denoise_mc_vector_bytes(const DenoiseMcLaunch &L) {
 hipError_t launch_denoise_mc_gather(const DenoiseMcLaunch &L, hipStream_t s) {
   GrainGeom G; McGeom M;
   if (hipError_t e = mc_geometry(L, G, M)) return e;
-  if (L.segments <= 0) return hipSuccess;
+  if (L.segments <= 0) return hipSuccess;        // (per_seg > 0: mc_geometry asks for a luma plane)
   if (!L.vectors || (L.records && !L.scratch)) return hipErrorInvalidValue;
   G.partials = L.records ? (av1mi_grain_bin *)L.scratch : nullptr;
   const dim3 search(M.pairs * (unsigned)L.segments), grid(G.per_seg * (unsigned)L.segments);

@@ -1,5 +1,7 @@
 """GPU tests of the denoising option (av1mi_gop_config.denoise): k_denoise_gather + k_grain_sum against tests/denoise_ref.py bit for bit,
 in output and in records, and a session that gathers through them."""
+import types
+
 import numpy as np
 import pytest
 
@@ -128,6 +130,27 @@ def test_denoise_gather_refuses_bad_arguments(ctx, av1mi):
                 dict(plane_sizes=[(20, 8), (4, 4), (4, 4)], true_sizes=[(13, 8), (4, 4), (4, 4)])):
         with pytest.raises(av1mi.Av1miError):
             ctx.denoise_gather(**dict(ok, **bad))
+    ctx.sync()
+    d.free()
+
+
+def test_the_three_gathers_refuse_their_planes_in_the_same_words(ctx, av1mi):
+    """a true size above the buffer's, and a destination that is not 16-byte aligned: one sentence, under the called function's name"""
+    d = ctx.to_device(np.zeros(8192, np.uint8))
+    odd = types.SimpleNamespace(ptr=d.ptr + 4)      # the same memory, 4 bytes in
+    ok = dict(bit_depth=8, plane_sizes=[(8, 8), (4, 4), (4, 4)], true_sizes=[(8, 8), (4, 4), (4, 4)], segments=1, d_table=d, d_dst=[d, d, d])
+    calls = {"av1mi_deinterlace_gather": lambda **kw: ctx.deinterlace_gather(parity=0, **kw),
+             "av1mi_denoise_gather": lambda **kw: ctx.denoise_gather(strength=4, **kw),
+             "av1mi_denoise_mc_gather": lambda **kw: ctx.denoise_mc_gather(strength=4, rng=4, **kw)}
+    for bad in (dict(true_sizes=[(9, 8), (4, 4), (4, 4)]), dict(d_dst=[d, odd, d])):
+        said = {}
+        for name, call in calls.items():
+            with pytest.raises(av1mi.Av1miError) as e:
+                call(**dict(ok, **bad))
+            code = "av1mi error %d: " % e.value.code      # (Av1miError puts the return code in front of the library's text)
+            assert str(e.value).startswith(code + name + ": "), str(e.value)
+            said[name] = str(e.value)[len(code + name):]
+        assert len(set(said.values())) == 1, said
     ctx.sync()
     d.free()
 
