@@ -105,7 +105,8 @@ class GopConfig(C.Structure):
                 ("visible_height", C.c_int), ("coder_streams", C.c_int), ("key_block_size", C.c_int), ("input_format", C.c_int), ("source_width", C.c_int),
                 ("source_height", C.c_int), ("quality_stats", C.c_int), ("coarse_range", C.c_int), ("source_chroma", C.c_int),
                 ("source_bit_depth", C.c_int), ("store_frames", C.c_int), ("deinterlace", C.c_int), ("denoise", C.c_int),
-                ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int), ("crop_height", C.c_int), ("denoise_range", C.c_int)]
+                ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int), ("crop_height", C.c_int), ("denoise_range", C.c_int),
+                ("tone_map", C.c_int), ("tone_map_peak", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -245,7 +246,7 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None, tone_map=0, tone_map_peak=0):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
@@ -273,6 +274,8 @@ class GopSession:
             self.cfg.denoise = int(denoise)
         if denoise_range is not None:
             self.cfg.denoise_range = int(denoise_range)
+        # tone_map: 1 = every batch is tone-mapped (PQ / BT.2020 -> SDR / BT.709) in place behind the input stages; tone_map_peak: cd/m2, 0 = 1000
+        self.cfg.tone_map, self.cfg.tone_map_peak = int(tone_map), int(tone_map_peak)
         if crop is not None:
             self.cfg.crop_x, self.cfg.crop_y, self.cfg.crop_width, self.cfg.crop_height = (int(v) for v in crop)
         self.g = C.c_void_p()
@@ -434,6 +437,21 @@ def load():
     return _lib
 
 
+class ToneTables(C.Structure):      # av1mi_tone_tables ("tone mapping")
+    _fields_ = [("lin", C.c_uint32 * 1024), ("gain", C.c_uint32 * 1024), ("oetf_lo", C.c_uint32 * 512), ("oetf_hi", C.c_uint32 * 388),
+                ("to_rgb", C.c_int32 * 5), ("gamut", (C.c_int32 * 3) * 3), ("to_yuv", (C.c_int32 * 3) * 3), ("peak", C.c_int32)]
+
+
+def tone_map_tables(peak, lib=None):
+    """av1mi_tone_map_tables(peak): the ToneTables a tone mapping reads; host code, no device"""
+    lib = lib or load()
+    t = ToneTables()
+    lib.av1mi_tone_map_tables.argtypes = [C.c_int, C.c_void_p]
+    if lib.av1mi_tone_map_tables(int(peak), C.byref(t)) != 0:
+        raise ValueError("av1mi_tone_map_tables: peak %r out of range (100 .. 10000)" % (peak,))
+    return t
+
+
 def exported_symbols():
     """names declared in include/av1mi.h (parsed from the header)."""
     import re
@@ -588,6 +606,12 @@ class Context:
         self.lib.av1mi_chroma_convert.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 6
         ptr = [b.ptr if b is not None else None for b in list(d_in) + list(d_out)]
         self._chk(self.lib.av1mi_chroma_convert(self.h, int(chroma), int(source_bit_depth), int(bit_depth), int(width), int(height), int(frames), *ptr))
+
+    def tone_map(self, width, height, frames, d_y, d_u, d_v, d_tables):
+        """planar 4:2:0 10-bit planes (DevBuf) of `frames` stacked frames of luma size width x height tone-mapped in place with the tables in
+        d_tables (a DevBuf holding a ToneTables); one launch, asynchronous (av1mi_tone_map)"""
+        self.lib.av1mi_tone_map.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4
+        self._chk(self.lib.av1mi_tone_map(self.h, int(width), int(height), int(frames), d_y.ptr, d_u.ptr, d_v.ptr, d_tables.ptr))
 
     def scale_planes(self, bit_depth, src_w, src_h, dst_w, dst_h, frames, d_src, d_dst):
         """d_src: planar Y, U, V (DevBuf) of `frames` stacked frames of true size src_w x src_h in buffers of that size rounded up to 8;

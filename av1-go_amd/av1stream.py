@@ -39,7 +39,26 @@ class ObuFrame(C.Structure):
                 ("tile_rows_log2", C.c_int32), ("y_mode", C.c_void_p), ("angle_y", C.c_void_p), ("uv_mode", C.c_void_p),
                 ("angle_uv", C.c_void_p), ("cfl_alpha", C.c_void_p), ("skip", C.c_void_p), ("tx_type", C.c_void_p),
                 ("is_inter", C.c_void_p), ("mv", C.c_void_p), ("lev_y", C.c_void_p), ("lev_u", C.c_void_p), ("lev_v", C.c_void_p),
-                ("visible_width", C.c_int32), ("visible_height", C.c_int32), ("film_grain_present", C.c_int32), ("film_grain", C.c_void_p)]
+                ("visible_width", C.c_int32), ("visible_height", C.c_int32), ("film_grain_present", C.c_int32), ("film_grain", C.c_void_p), ("colour", C.c_void_p)]
+
+
+class Colour(C.Structure):
+    """av1mi_colour (include/av1mi_host.h): the colour description and HDR10 static metadata of a stream; Colour() is all-unspecified"""
+    _fields_ = [("primaries", C.c_int32), ("transfer", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32), ("have_mdcv", C.c_int32),
+                ("primary_x", C.c_uint16 * 3), ("primary_y", C.c_uint16 * 3), ("white_x", C.c_uint16), ("white_y", C.c_uint16),
+                ("luminance_max", C.c_uint32), ("luminance_min", C.c_uint32), ("have_cll", C.c_int32), ("max_cll", C.c_uint16), ("max_fall", C.c_uint16)]
+
+    def __init__(self, primaries=2, transfer=2, matrix=2, full_range=0, mdcv=None, cll=None):
+        """mdcv: ((rx, ry), (gx, gy), (bx, by), (wx, wy), luminance_max, luminance_min) in the record's fixed point; cll: (max_cll, max_fall)"""
+        super().__init__()
+        self.primaries, self.transfer, self.matrix, self.full_range = primaries, transfer, matrix, full_range
+        if mdcv is not None:
+            self.have_mdcv = 1
+            for i in range(3):
+                self.primary_x[i], self.primary_y[i] = mdcv[i]
+            (self.white_x, self.white_y), self.luminance_max, self.luminance_min = mdcv[3], mdcv[4], mdcv[5]
+        if cll is not None:
+            self.have_cll, self.max_cll, self.max_fall = 1, cll[0], cll[1]
 
 
 def lib():
@@ -63,13 +82,14 @@ _PTR_FIELDS = {"cdef_idx": np.uint8, "y_mode": np.uint8, "angle_y": np.int8, "uv
 def temporal_unit(width, height, bit_depth, base_q_idx, frame_type=0, with_sequence_header=True, threads=1, lf_level=(0, 0, 0, 0),
                   lf_sharpness=0, cdef_damping=3, cdef_bits=0, cdef_y=(0,), cdef_uv=(0,), lr_type=(0, 0, 0), lr_unit_shift=0, lr_uv_shift=0,
                   lr_units=(None, None, None), reduced_tx_set=0, disable_cdf_update=0, tile_cols_log2=-1, tile_rows_log2=-1, opstream=False,
-                  visible=None, key_rows32=0, film_grain=None, film_grain_present=None, **arrays):
+                  visible=None, key_rows32=0, film_grain=None, film_grain_present=None, colour=None, **arrays):
     """arrays: y_mode, angle_y, uv_mode, angle_uv, cfl_alpha, skip, tx_type, is_inter, mv, lev_y, lev_u, lev_v, cdef_idx (numpy, raster
     order over 8x8 blocks; see av1_bitstream.hpp).  visible: (width, height) a decoder outputs when the coded size is the source's rounded up to 8.
     film_grain: a FilmGrain the frame header carries; film_grain_present: the sequence's flag (None = set iff film_grain is given).
     Returns bytes."""
     f = ObuFrame()
     _set_film_grain(f, film_grain, film_grain_present)
+    f.colour = C.addressof(colour) if colour is not None else None      # (a Colour: the stream's description, read where a sequence header is written)
     f.width, f.height, f.bit_depth, f.frame_type, f.base_q_idx = width, height, bit_depth, frame_type, base_q_idx
     if visible is not None:
         f.visible_width, f.visible_height = int(visible[0]), int(visible[1])
@@ -129,12 +149,15 @@ class ObuBlocks(C.Structure):
 def blocks_temporal_unit(width, height, bit_depth, base_q_idx, partition, blocks, tx_type, levels, frame_type=0, with_sequence_header=True,
                          tx_mode_select=0, interp_filter=0, high_precision_mv=0, reduced_tx_set=0, disable_cdf_update=0, tile_cols_log2=-1,
                          tile_rows_log2=-1, lf_level=(0, 0, 0, 0), lf_sharpness=0, cdef_damping=3, cdef_bits=0, cdef_y=(0,), cdef_uv=(0,), cdef_idx=None,
-                         lr_type=(0, 0, 0), lr_units=(None, None, None), lr_unit_shift=0, lr_uv_shift=0):
+                         lr_type=(0, 0, 0), lr_units=(None, None, None), lr_unit_shift=0, lr_uv_shift=0, colour=None, visible=None):
     """the general block-structured writer (av1mi_obu_write_blocks_temporal_unit): partition = uint8 partition types in decoding order,
     blocks = array of BLOCK_DTYPE in decoding order, tx_type = uint8 per luma transform block, levels = int16 (see include/av1mi_host.h)"""
     d = ObuBlocks()
     f = d.hdr
     f.width, f.height, f.bit_depth, f.frame_type, f.base_q_idx = width, height, bit_depth, frame_type, base_q_idx
+    f.colour = C.addressof(colour) if colour is not None else None
+    if visible is not None:
+        f.visible_width, f.visible_height = int(visible[0]), int(visible[1])
     for i in range(4):
         f.lf_level[i] = int(lf_level[i])
     f.lf_sharpness, f.cdef_damping, f.cdef_bits = lf_sharpness, cdef_damping, cdef_bits

@@ -178,6 +178,9 @@ const char *scale_geometry_error(int sw, int sh, int dw, int dh);
 // the window alone, nothing resampled (crop_kernels.hip, k_crop_copy): the window of `frames` stacked frames -> the coded planes of dst_w x
 // dst_h luma samples (the window's size rounded up to 8; the window's last column / row replicated into the padding).  ONE launch
 hipError_t launch_crop_copy(const CropWindow &W, int bd, int dst_w, int dst_h, int frames, const void *const *src, void *const *dst, hipStream_t s);
+// tone mapping in place (tonemap_kernels.hip, include/av1mi.h "tone mapping"): `frames` stacked frames of planar 4:2:0 10-bit planes of luma size
+// w x h (w a multiple of 4, h even), tables = an av1mi_tone_tables in device memory (16-byte aligned); one launch
+hipError_t launch_tone_map(int w, int h, int frames, void *const planes[3], const void *tables, hipStream_t s);
 // bar detection (crop_kernels.hip, include/av1mi.h "bar detection"): `frames` stacked luma planes of TRUE size w x h in buffers of stride x
 // rows samples -> one record of margins per frame, two launches.  scratch: crop_layout().bytes bytes, 4-byte aligned: a partial per
 // (row, tile column) at 0, a partial per (tile row, column) at off_cols

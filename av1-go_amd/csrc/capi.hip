@@ -688,6 +688,19 @@ int av1mi_crop_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int
   return AV1MI_OK;
 }
 
+int av1mi_tone_map(av1mi_ctx *ctx, int width, int height, int frames, void *d_y, void *d_u, void *d_v, const av1mi_tone_tables *d_tables) {
+  BIND(ctx);
+  if (width < 4 || height < 2 || (width & 3) || (height & 1) || width > 16384 || height > 16384)
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_tone_map: the planes' size %dx%d must be a multiple of 4 x 2 (up to 16384)", width, height);
+  if (frames < 1 || frames > 65535) return fail(ctx, AV1MI_E_INVAL, "av1mi_tone_map: frames %d out of range (1 .. 65535)", frames);
+  if (!d_y || !d_u || !d_v || !d_tables || (((uintptr_t)d_y | (uintptr_t)d_u | (uintptr_t)d_v | (uintptr_t)d_tables) & 15))
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_tone_map: null or misaligned device pointer (planes and tables 16 bytes)");
+  void *const planes[3] = { d_y, d_u, d_v };
+  ProfScope ps(ctx, AV1MI_K_INPUT);
+  HIP_TRY(ctx, av1mi::launch_tone_map(width, height, frames, planes, d_tables, ctx->stream));
+  return AV1MI_OK;
+}
+
 int av1mi_frames_gather(av1mi_ctx *ctx, const size_t plane_bytes[3], int segments, const void *const *d_src_table, void *const d_dst[3]) {
   BIND(ctx);
   if (!plane_bytes || !d_src_table || !d_dst || ((uintptr_t)d_src_table & 7)) return fail(ctx, AV1MI_E_INVAL, "av1mi_frames_gather: null pointer or misaligned table");

@@ -164,6 +164,7 @@ struct av1mi_gop {
   void *d_me = nullptr;                        // coarse_range: the coarse search's quarter planes and centres of one batch (single: the chain is serial in t)
   void *d_denoise_vectors = nullptr;           // denoise_range: the blocks' vectors of one batch (the main stream orders its users)
   void *d_grain_scratch = nullptr;             // denoise: the workgroups' partial records of one batch (the main stream orders its users)
+  void *d_tone_tables = nullptr;               // tone_map: the tables (av1mi_tone_tables), uploaded at open
   void *d_quality_scratch = nullptr;           // quality_stats: the tiles' partial sums of one batch (the main stream orders its users)
   int vw = 0, vh = 0;                          // the true frame size (== the coded size unless cfg.visible_* say otherwise)
   int last = 0;                                // slot of the most recent batch (its d_lr_on selects the next batch's references)
@@ -394,6 +395,11 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
   if (c->denoise && c->source_bit_depth == 12) return WHY("denoise %d takes fed samples of 8 or 10 bits, not source_bit_depth 12", c->denoise);
   if (c->denoise_range != 0 && c->denoise_range != 4 && c->denoise_range != 8) return WHY("denoise_range %d unknown (0 none, 4 or 8 the block search's range)", c->denoise_range);
   if (c->denoise_range && !c->denoise) return WHY("denoise_range %d needs denoise (1 .. 16): it is the range of the denoiser's block search", c->denoise_range);
+  if (c->tone_map != 0 && c->tone_map != 1) return WHY("tone_map %d unknown (0 none, 1 BT.2390)", c->tone_map);
+  if (c->tone_map_peak && !c->tone_map) return WHY("tone_map_peak %d needs tone_map", c->tone_map_peak);
+  if (c->tone_map && c->bit_depth != 10) return WHY("tone_map needs bit_depth 10, not %d: an HDR10 source has 10 bits", c->bit_depth);
+  if (c->tone_map && c->tone_map_peak && (c->tone_map_peak < 100 || c->tone_map_peak > 10000)) return WHY("tone_map_peak %d out of range (100 .. 10000 cd/m2; 0 = 1000)", c->tone_map_peak);
+  if (c->tone_map && c->denoise) return WHY("tone_map together with denoise %d is not built: the grain records would be measured in the source's light, the grain synthesised in the output's", c->denoise);
   return nullptr;
 #undef WHY
 }
@@ -464,6 +470,12 @@ int setup(av1mi_gop *g) {
     G_TRY(host_alloc(g, &g->h_records, (size_t)c.store_frames * sizeof(av1mi_scene_record)));
     G_HIP(hipEventCreateWithFlags(&g->scene_done, hipEventDisableTiming));
     for (hipEvent_t &e : g->put_done) G_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  if (c.tone_map) {
+    av1mi_tone_tables tables;
+    if (av1mi_tone_map_tables(c.tone_map_peak ? c.tone_map_peak : 1000, &tables) != AV1MI_OK) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "tone_map_peak %d: no tables", c.tone_map_peak);
+    G_TRY(dev_alloc(g, &g->d_tone_tables, sizeof(tables)));
+    G_TRY(av1mi_upload(g->ctx, g->d_tone_tables, &tables, sizeof(tables)));
   }
   G_TRY(dev_alloc(g, &g->d_zero_skip, g->nb));
   G_TRY(av1mi_memset(g->ctx, g->d_zero_skip, 0, g->nb));
@@ -631,6 +643,11 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
       G_HIP(av1mi::launch_crop_copy(g->window, c.bit_depth, c.width, c.height, S, src, out, main));
     } else G_HIP(av1mi::launch_scale(g->scale, S, src, out, main));
     for (int p = 0; p < 3; p++) if (out[p]) src[p] = out[p];      // (a plane that passes through stays where it was fed: the caller's, in a device batch)
+  }
+  if (c.tone_map) {      // behind the last stage, in place: the planes are the slot's own (av1mi_gop_submit_device is refused)
+    av1mi::ProfScope ps(g->ctx, AV1MI_K_INPUT, main);
+    void *const planes[3] = { const_cast<void *>(src[0]), const_cast<void *>(src[1]), const_cast<void *>(src[2]) };
+    G_HIP(av1mi::launch_tone_map(c.width, c.height, S, planes, g->d_tone_tables, main));
   }
   return AV1MI_OK;
 }
@@ -1008,6 +1025,7 @@ int av1mi_gop_submit_stored(av1mi_gop *g, int store, const int32_t *index, int f
 
 int av1mi_gop_submit_device(av1mi_gop *g, const void *d_y, const void *d_u, const void *d_v, int frame_type) {
   if (!g) return AV1MI_E_INVAL;
+  if (g->cfg.tone_map) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "av1mi_gop_submit_device in a tone_map session is not built: the map runs in place and would overwrite the caller's planes");
   if (!g->layout.plane[2].frame_bytes) d_v = d_u;            // planes the layout does not have (semi-planar: the third; grey: both chroma
   if (!g->layout.plane[1].frame_bytes) d_u = d_v = d_y;      // planes) are not read
   if (!d_y || !d_u || !d_v || (((uintptr_t)d_y | (uintptr_t)d_u | (uintptr_t)d_v) & (g->fed_align - 1)))

@@ -320,12 +320,46 @@ std::vector<uint8_t> sequence_header_obu(const SequenceParams &sp) {   // sequen
   w.put(0, 1);      // enable_superres
   w.put(1, 1);      // enable_cdef
   w.put(1, 1);      // enable_restoration
-  write_color_config(w, sp.bit_depth);
+  write_color_config(w, sp);
   w.put(sp.film_grain ? 1 : 0, 1);      // film_grain_params_present
   w.trailing_bits();
   return make_obu(1, w.b);
 }
 
+
+const char *colour_error(const av1mi_colour &c) {
+  if (c.primaries < 0 || c.primaries > 255 || c.transfer < 0 || c.transfer > 255 || c.matrix < 0 || c.matrix > 255) return "colour: a code point does not fit in eight bits";
+  if (c.matrix == 0) return "colour: matrix_coefficients 0 (identity) implies 4:4:4 (the spec's sRGB case), which is not coded";
+  if (c.full_range != 0 && c.full_range != 1) return "colour: full_range must be 0 or 1";
+  return nullptr;
+}
+
+static std::vector<uint8_t> metadata_obu(int type, BitWriter &w) {   // metadata_obu (5.8.1): metadata_type leb128, the payload, trailing bits
+  w.trailing_bits();
+  std::vector<uint8_t> p;
+  put_leb128(p, (uint64_t)type);
+  p.insert(p.end(), w.b.begin(), w.b.end());
+  return make_obu(5, p);
+}
+std::vector<uint8_t> metadata_obu_hdr_cll(const av1mi_colour &c) {   // metadata_hdr_cll (5.8.3)
+  BitWriter w;
+  w.put(c.max_cll, 16); w.put(c.max_fall, 16);
+  return metadata_obu(1, w);
+}
+std::vector<uint8_t> metadata_obu_hdr_mdcv(const av1mi_colour &c) {  // metadata_hdr_mdcv (5.8.4)
+  BitWriter w;
+  for (int i = 0; i < 3; i++) { w.put(c.primary_x[i], 16); w.put(c.primary_y[i], 16); }
+  w.put(c.white_x, 16); w.put(c.white_y, 16);
+  w.put(c.luminance_max >> 16, 16); w.put(c.luminance_max & 0xFFFF, 16);      // (the writer's put takes up to 32 bits; two halves keep the shifts plain)
+  w.put(c.luminance_min >> 16, 16); w.put(c.luminance_min & 0xFFFF, 16);
+  return metadata_obu(2, w);
+}
+void append_sequence_obus(const SequenceParams &sp, std::vector<uint8_t> *out) {
+  const std::vector<uint8_t> sh = sequence_header_obu(sp);
+  out->insert(out->end(), sh.begin(), sh.end());
+  if (sp.colour.have_cll) { const std::vector<uint8_t> m = metadata_obu_hdr_cll(sp.colour); out->insert(out->end(), m.begin(), m.end()); }
+  if (sp.colour.have_mdcv) { const std::vector<uint8_t> m = metadata_obu_hdr_mdcv(sp.colour); out->insert(out->end(), m.begin(), m.end()); }
+}
 
 bool frame_obu_from_tiles(const av1mi_obu_frame &f, const uint8_t *payloads, const uint32_t *sizes, int ntiles, std::vector<uint8_t> *out,
                           std::string *err) {
@@ -374,11 +408,7 @@ bool temporal_unit(const av1mi_obu_frame &f, bool with_sequence_header, int thre
   std::vector<uint8_t> fr;
   if (!frame_obu(f, threads, &fr, err)) return false;
   *out = temporal_delimiter_obu();
-  if (with_sequence_header) {
-    const SequenceParams sp = sequence_params(f);
-    const std::vector<uint8_t> sh = sequence_header_obu(sp);
-    out->insert(out->end(), sh.begin(), sh.end());
-  }
+  if (with_sequence_header) append_sequence_obus(sequence_params(f), out);
   out->insert(out->end(), fr.begin(), fr.end());
   return true;
 }

@@ -28,23 +28,44 @@
 namespace av1mi_host {
 namespace av1 {
 
+inline av1mi_colour unspecified_colour() { av1mi_colour c = {}; c.primaries = c.transfer = c.matrix = 2; return c; }
+inline bool same_colour(const av1mi_colour &a, const av1mi_colour &b) {
+  if (a.primaries != b.primaries || a.transfer != b.transfer || a.matrix != b.matrix || a.full_range != b.full_range || !a.have_mdcv != !b.have_mdcv || !a.have_cll != !b.have_cll) return false;
+  if (a.have_cll && (a.max_cll != b.max_cll || a.max_fall != b.max_fall)) return false;
+  if (!a.have_mdcv) return true;
+  for (int i = 0; i < 3; i++) if (a.primary_x[i] != b.primary_x[i] || a.primary_y[i] != b.primary_y[i]) return false;
+  return a.white_x == b.white_x && a.white_y == b.white_y && a.luminance_max == b.luminance_max && a.luminance_min == b.luminance_min;
+}
 struct SequenceParams {
   int width = 0, height = 0, bit_depth = 8;
   bool film_grain = false;      // film_grain_params_present: every frame header of the stream then ends in film_grain_params
-  bool operator==(const SequenceParams &o) const { return width == o.width && height == o.height && bit_depth == o.bit_depth && film_grain == o.film_grain; }
+  av1mi_colour colour = unspecified_colour();      // color_config's description and range; the metadata OBUs that follow the sequence header
+  bool described() const { return colour.primaries != 2 || colour.transfer != 2 || colour.matrix != 2; }      // color_description_present_flag
+  bool has_colour() const { return described() || colour.full_range || colour.have_mdcv || colour.have_cll; }   // anything a container would note
+  bool operator==(const SequenceParams &o) const {
+    return width == o.width && height == o.height && bit_depth == o.bit_depth && film_grain == o.film_grain && same_colour(colour, o.colour);
+  }
 };
+// null = a record the writers take, else why not
+const char *colour_error(const av1mi_colour &c);
 
 // the size a decoder outputs (av1mi_obu_frame.visible_*: 0 = the coded size) and the sequence header that announces it
 inline int visible_width(const av1mi_obu_frame &f) { return f.visible_width ? f.visible_width : f.width; }
 inline int visible_height(const av1mi_obu_frame &f) { return f.visible_height ? f.visible_height : f.height; }
 inline SequenceParams sequence_params(const av1mi_obu_frame &f) {
   SequenceParams sp; sp.width = visible_width(f); sp.height = visible_height(f); sp.bit_depth = f.bit_depth; sp.film_grain = f.film_grain_present != 0;
+  if (f.colour) sp.colour = *f.colour;
   return sp;
 }
 // OBU_TEMPORAL_DELIMITER (spec 5.6)
 std::vector<uint8_t> temporal_delimiter_obu();
 // OBU_SEQUENCE_HEADER (spec 5.5)
 std::vector<uint8_t> sequence_header_obu(const SequenceParams &sp);
+// OBU_METADATA with metadata_type 1 (METADATA_TYPE_HDR_CLL, spec 5.8.3) and 2 (METADATA_TYPE_HDR_MDCV, spec 5.8.4), trailing bits included
+std::vector<uint8_t> metadata_obu_hdr_cll(const av1mi_colour &c);
+std::vector<uint8_t> metadata_obu_hdr_mdcv(const av1mi_colour &c);
+// what a temporal unit carries where it carries a sequence header: that header, then the metadata OBUs the record has
+void append_sequence_obus(const SequenceParams &sp, std::vector<uint8_t> *out);
 // OBU_FRAME (spec 5.10: frame header + tile group).  threads > 1 codes tiles on that many host threads.
 // Returns false and fills *err when the description cannot be coded with the tool set above.
 bool frame_obu(const av1mi_obu_frame &f, int threads, std::vector<uint8_t> *out, std::string *err);

@@ -289,6 +289,7 @@ inline bool check(const av1mi_obu_frame &f, std::string *err, bool need_symbols 
     if (f.lr_type[p] && !f.lr_units[p]) return bad("restoration units missing");
   }
   if (f.lr_unit_shift < 0 || f.lr_unit_shift > 2 || f.lr_uv_shift < 0 || f.lr_uv_shift > 1) return bad("restoration unit size out of range");
+  if (f.colour) if (const char *why = colour_error(*f.colour)) return bad(why);
   if (f.film_grain) {
     const av1mi_film_grain &g = *f.film_grain;
     if (!f.film_grain_present) return bad("film_grain given, but the sequence says film_grain_params_present = 0 (av1mi_obu_frame.film_grain_present)");
@@ -343,11 +344,13 @@ inline FrameInfo frame_info(const av1mi_obu_frame &f) {
 }
 
 // ------------------------------------------------------------------------------------------------ headers
-inline void write_color_config(BitWriter &w, int bd) {   // color_config (5.5.2), profile 0
-  w.put(bd == 10, 1);   // high_bitdepth
+inline void write_color_config(BitWriter &w, const SequenceParams &sp) {   // color_config (5.5.2), profile 0
+  const av1mi_colour &c = sp.colour;
+  w.put(sp.bit_depth == 10, 1);   // high_bitdepth
   w.put(0, 1);          // mono_chrome
-  w.put(0, 1);          // color_description_present_flag
-  w.put(0, 1);          // color_range: studio swing
+  w.put(sp.described(), 1);       // color_description_present_flag
+  if (sp.described()) { w.put((uint32_t)c.primaries, 8); w.put((uint32_t)c.transfer, 8); w.put((uint32_t)c.matrix, 8); }      // (never 1 / 13 / 0: matrix 0 is refused)
+  w.put(c.full_range ? 1 : 0, 1); // color_range
   w.put(0, 2);          // chroma_sample_position: unknown
   w.put(0, 1);          // separate_uv_delta_q
 }

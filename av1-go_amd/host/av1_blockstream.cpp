@@ -431,10 +431,7 @@ bool blocks_temporal_unit(const av1mi_obu_blocks &d, bool with_sequence_header, 
   std::vector<uint8_t> fr;
   if (!assemble_frame(bw.fi, data.data(), size.data(), &fr)) return false;
   *out = temporal_delimiter_obu();
-  if (with_sequence_header) {
-    const std::vector<uint8_t> sh = sequence_header_obu(sequence_params(d.hdr));
-    out->insert(out->end(), sh.begin(), sh.end());
-  }
+  if (with_sequence_header) append_sequence_obus(sequence_params(d.hdr), out);
   out->insert(out->end(), fr.begin(), fr.end());
   return true;
 }

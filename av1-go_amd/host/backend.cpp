@@ -139,10 +139,10 @@ static bool Key32TemporalUnit(const av1mi_gop_frame &fr, int seg, const SessionF
 
 bool SessionTemporalUnit(const av1mi_gop_frame &fr, int seg, int width, int height, int bit_depth, int visible_width, int visible_height,
                          bool with_sequence_header, int threads, std::vector<uint8_t> *out, std::string *err, bool film_grain_present,
-                         const av1mi_film_grain *film_grain) {
+                         const av1mi_film_grain *film_grain, const av1mi_colour *colour) {
   SessionFrameDesc desc;
   DescribeSessionFrame(fr, seg, width, height, bit_depth, &desc, visible_width, visible_height);
-  desc.f.film_grain_present = film_grain_present; desc.f.film_grain = film_grain;
+  desc.f.film_grain_present = film_grain_present; desc.f.film_grain = film_grain; desc.f.colour = colour;
   std::string werr;
   if (fr.tile_size) {      // tiles coded on the GPU: frame header + tile group around them
     const uint32_t *sz = fr.tile_size + (size_t)seg * fr.tiles_per_frame;
@@ -151,7 +151,7 @@ bool SessionTemporalUnit(const av1mi_gop_frame &fr, int seg, int width, int heig
     std::vector<uint8_t> frame;
     if (!av1::frame_obu_from_tiles(desc.f, fr.tile_payload + off, sz, fr.tiles_per_frame, &frame, &werr)) { if (err) *err = "bitstream assembly: " + werr; return false; }
     *out = av1::temporal_delimiter_obu();
-    if (with_sequence_header) { const std::vector<uint8_t> sh = av1::sequence_header_obu(av1::sequence_params(desc.f)); out->insert(out->end(), sh.begin(), sh.end()); }
+    if (with_sequence_header) av1::append_sequence_obus(av1::sequence_params(desc.f), out);
     out->insert(out->end(), frame.begin(), frame.end());
     return true;
   }
@@ -256,6 +256,15 @@ int RunBackend(const BackendJob &job, std::string *err) {
     // -av1mi_denoise: the same store, the denoiser in the gather; -av1mi_film_grain (1 unless told otherwise): parameters in every frame header
     cfg.denoise = job.denoise;
     cfg.denoise_range = job.denoise_range;
+    // the stream's colour record: the job's options, the header's range; a tone-mapped job says what the kernel makes
+    const av1mi_colour colour = JobColour(job, y.colour_range);
+    if (const char *why = av1::colour_error(colour)) { *err = std::string("Invalid argument: ") + why; code = 1; goto done; }
+    if (job.tonemap) {
+      if (y.bd != 10) { *err = "Invalid argument: tone mapping needs a 10-bit source (an 8-bit HDR10 source does not exist)"; code = 1; goto done; }
+      if (y.colour_range == 1) { *err = "Invalid argument: tone mapping takes a limited-range source; the Y4M header says XCOLORRANGE=FULL"; code = 1; goto done; }
+      cfg.tone_map = 1;
+      cfg.tone_map_peak = job.tonemap_peak ? job.tonemap_peak : job.hdr.have_mdcv ? (int)std::min<uint32_t>(std::max<uint32_t>(job.hdr.luminance_max >> 8, 100), 10000) : 0;
+    }
     const bool grainy = job.denoise > 0 && job.film_grain != 0;
     const bool analysed = job.scenecut > 0, stored = analysed || dei != 0 || job.denoise > 0;
     if (stored) cfg.store_frames = S * G;
@@ -267,7 +276,8 @@ int RunBackend(const BackendJob &job, std::string *err) {
     auto at = [&](void *plane, int p, int i) { return (unsigned char *)plane + fed.plane[p].frame_bytes * (size_t)i; };      // frame i of a pinned plane
     std::vector<std::vector<unsigned char>> scratch(packed ? (size_t)S : 0);          // per reader thread: one planar frame to pack from
     CHK(av1mi_gop_open(ctx, &cfg, &gop));
-    av1::SequenceParams sp; sp.width = tw; sp.height = th; sp.bit_depth = y.bd; sp.film_grain = grainy;
+    av1::SequenceParams sp; sp.width = tw; sp.height = th; sp.bit_depth = y.bd; sp.film_grain = grainy; sp.colour = colour;
+    const av1mi_colour *const stream_colour = sp.has_colour() ? &colour : nullptr;
     // pixels that stay non-square: the track at least says at which shape to show them
     if (!square) sink.set_display_size((int)((long)tw * y.sar_n / y.sar_d), th);
     for (const std::string &side : job.tracks)
@@ -378,7 +388,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
             FilmGrainFromRecords(fr.grain + (size_t)s * 3, y.bd, (int)(g0 * G + start[(size_t)s] + t), &fg);
             grains[(size_t)s].push_back(FilmGrainMidGrey(fg));
           }
-          if (!SessionTemporalUnit(fr, s, w, h, y.bd, cfg.visible_width, cfg.visible_height, t == 0, threads, &tu, err, grainy, grainy ? &fg : nullptr)) return false;
+          if (!SessionTemporalUnit(fr, s, w, h, y.bd, cfg.visible_width, cfg.visible_height, t == 0, threads, &tu, err, grainy, grainy ? &fg : nullptr, stream_colour)) return false;
           batch_bytes += (long long)tu.size();
           if (rc) qs[(size_t)s].push_back(fr.params.base_q_idx);
           units[(size_t)s].push_back(std::move(tu));
@@ -468,6 +478,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
             int n = snprintf(line, sizeof(line), "n:%ld type:%c bytes:%zu", summary.frames, t == 0 ? 'K' : 'P', units[(size_t)s][t].size());
             n += av1mi::quality::format_figures(av1mi::quality::frame_figures(records[(size_t)s][t].q, y.bd), line + n, sizeof(line) - (size_t)n);
             if (win.w && summary.frames == 0) n += snprintf(line + n, sizeof(line) - (size_t)n, " crop:%dx%d+%d+%d", win.w, win.h, win.x, win.y);
+            if (sp.described() && summary.frames == 0) n += snprintf(line + n, sizeof(line) - (size_t)n, " colour:%d/%d/%d/%d", colour.primaries, colour.transfer, colour.matrix, colour.full_range);
             if (rc) n += snprintf(line + n, sizeof(line) - (size_t)n, " q:%d", qs[(size_t)s][t]);
             if (job.denoise) n += snprintf(line + n, sizeof(line) - (size_t)n, " grain:%d", grains[(size_t)s][t]);
             if (analysed && cut[(size_t)start[(size_t)s] + t]) n += snprintf(line + n, sizeof(line) - (size_t)n, " cut:1");

@@ -17,5 +17,5 @@ void DescribeSessionFrame(const av1mi_gop_frame &fr, int seg, int width, int hei
 // the temporal unit of segment `seg` of a collected batch: GPU-coded tiles wrapped, or the symbols coded on `threads` host threads
 bool SessionTemporalUnit(const av1mi_gop_frame &fr, int seg, int width, int height, int bit_depth, int visible_width, int visible_height,
                          bool with_sequence_header, int threads, std::vector<uint8_t> *out, std::string *err, bool film_grain_present = false,
-                         const av1mi_film_grain *film_grain = nullptr);
+                         const av1mi_film_grain *film_grain = nullptr, const av1mi_colour *colour = nullptr);
 }

@@ -169,6 +169,41 @@ int av1mi_host_mux_selftest(const char *out_path, int width, int height, int bit
   if (!sink.close(&e)) return fail();
   return 0;
 }
+// StreamSink with a colour record, for the CPU tests: av1mi_host_mux_units with the sequence's colour (null = none)
+int av1mi_host_mux_units_colour(const char *path, int w, int h, int bd, int fps_n, int fps_d, const uint8_t *data, const long long *sizes, const uint8_t *keys, int n,
+                                const av1mi_colour *colour) {
+  StreamSink sink; std::string err;
+  av1::SequenceParams sp; sp.width = w; sp.height = h; sp.bit_depth = bd;
+  if (colour) sp.colour = *colour;
+  if (!sink.open(path, sp, fps_n, fps_d, &err)) return 1;
+  for (int i = 0; i < n; i++) {
+    std::vector<uint8_t> tu(data, data + sizes[i]);
+    data += sizes[i];
+    if (!sink.write(tu, keys[i] != 0, &err)) { sink.abort(); return 2; }
+  }
+  return sink.close(&err) ? 0 : 3;
+}
+// ParseBackendJob's view of the colour and tone mapping options for an argv joined with '\n': 0, *out = the record JobColour gives with the Y4M range
+// y4m_range, tone[2] = { tonemap, tonemap_peak }; or -1 with the text in err
+int av1mi_host_parse_colour_options(const char *joined, int y4m_range, av1mi_colour *out, int *tone, char *err, int cap) {
+  std::vector<std::string> a; std::string s = joined; size_t p = 0, q;
+  while ((q = s.find('\n', p)) != std::string::npos) { a.push_back(s.substr(p, q - p)); p = q + 1; }
+  a.push_back(s.substr(p));
+  BackendJob job; std::string e;
+  const bool ok = ParseBackendJob(a, &job, &e);
+  strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
+  if (!ok) return -1;
+  *out = JobColour(job, y4m_range);
+  tone[0] = job.tonemap; tone[1] = job.tonemap_peak;
+  return 0;
+}
+// the header's XCOLORRANGE as Y4mSource keeps it (-1 absent, 0 LIMITED, 1 FULL); -2 when the file does not open
+int av1mi_host_y4m_colour_range(const char *path) {
+  Y4mSource y;
+  std::string e;
+  if (!y.open(path, &e)) return -2;
+  return y.colour_range;
+}
 // The drop-in for internal/ffmpeg/transcode.go:194 `RunTranscode(ffmpegPath string, args []string) (int, error)`: what the cgo
 // shim of INTEGRATION.md binds.  Returns the exit code of the contract (0 = output written, -1 = could not run, else failed);
 // the error text (<= 800 chars + "...", transcode.go:295-297) goes to err.  Declared in include/av1mi_host.h.
@@ -304,11 +339,7 @@ long long av1mi_obu_assemble_temporal_unit(const av1mi_obu_frame *f, const uint8
     return -1;
   }
   std::vector<uint8_t> b = av1::temporal_delimiter_obu();
-  if (with_sequence_header) {
-    const av1::SequenceParams sp = av1::sequence_params(*f);
-    const std::vector<uint8_t> sh = av1::sequence_header_obu(sp);
-    b.insert(b.end(), sh.begin(), sh.end());
-  }
+  if (with_sequence_header) av1::append_sequence_obus(av1::sequence_params(*f), &b);
   b.insert(b.end(), fr.begin(), fr.end());
   if ((long long)b.size() <= cap && out) memcpy(out, b.data(), b.size());
   return (long long)b.size();
@@ -327,11 +358,7 @@ long long av1mi_host_opstream_key32_temporal_unit(const av1mi_obu_frame *f, int 
   std::vector<uint8_t> fr;
   if (!av1::frame_obu_from_tiles(*f, cat.data(), sizes.data(), (int)sizes.size(), &fr, &e)) return fail(-1);
   std::vector<uint8_t> b = av1::temporal_delimiter_obu();
-  if (with_sequence_header) {
-    const av1::SequenceParams sp = av1::sequence_params(*f);
-    const std::vector<uint8_t> sh = av1::sequence_header_obu(sp);
-    b.insert(b.end(), sh.begin(), sh.end());
-  }
+  if (with_sequence_header) av1::append_sequence_obus(av1::sequence_params(*f), &b);
   b.insert(b.end(), fr.begin(), fr.end());
   if ((long long)b.size() <= cap && out) memcpy(out, b.data(), b.size());
   return (long long)b.size();
@@ -367,15 +394,7 @@ double av1mi_host_gpu_usage(int device, const char *sysfs_root) { return GetGPUU
 // container hook for the CPU tests: writes `n` temporal units (concatenated in data, sizes[i] bytes each) to path; 0 = OK
 int av1mi_host_mux_units(const char *path, int w, int h, int bd, int fps_n, int fps_d, const uint8_t *data, const long long *sizes,
                          const uint8_t *keys, int n) {
-  StreamSink sink; std::string err;
-  av1::SequenceParams sp; sp.width = w; sp.height = h; sp.bit_depth = bd;
-  if (!sink.open(path, sp, fps_n, fps_d, &err)) return 1;
-  for (int i = 0; i < n; i++) {
-    std::vector<uint8_t> tu(data, data + sizes[i]);
-    data += sizes[i];
-    if (!sink.write(tu, keys[i] != 0, &err)) { sink.abort(); return 2; }
-  }
-  return sink.close(&err) ? 0 : 3;
+  return av1mi_host_mux_units_colour(path, w, h, bd, fps_n, fps_d, data, sizes, keys, n, nullptr);
 }
 // av1mi_host_mux_units with a display size on the video track (0, 0 = none)
 int av1mi_host_mux_units_display(const char *path, int w, int h, int bd, int fps_n, int fps_d, const uint8_t *data, const long long *sizes,

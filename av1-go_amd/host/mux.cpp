@@ -302,6 +302,23 @@ bool StreamSink::open(const std::string &path, const av1::SequenceParams &sp, in
     av1c.insert(av1c.end(), seq.begin(), seq.end());
     std::vector<uint8_t> video; el_uint(video, 0xB0, (uint64_t)sp.width); el_uint(video, 0xBA, (uint64_t)sp.height);
     if (display_w_ > 0 && display_h_ > 0) { el_uint(video, 0x54B0, (uint64_t)display_w_); el_uint(video, 0x54BA, (uint64_t)display_h_); }
+    if (sp.has_colour()) {      // Colour: the description in Matroska's terms (the code points are H.273's, as in the sequence header)
+      const av1mi_colour &c = sp.colour;
+      std::vector<uint8_t> col;
+      el_uint(col, 0x55B1, (uint64_t)c.matrix); el_uint(col, 0x55B2, (uint64_t)sp.bit_depth);      // MatrixCoefficients, BitsPerChannel
+      el_uint(col, 0x55B3, 1); el_uint(col, 0x55B4, 1);                                           // ChromaSubsamplingHorz / Vert: 4:2:0
+      el_uint(col, 0x55B9, c.full_range ? 2 : 1);                                                 // Range: 1 broadcast, 2 full
+      el_uint(col, 0x55BA, (uint64_t)c.transfer); el_uint(col, 0x55BB, (uint64_t)c.primaries);    // TransferCharacteristics, Primaries
+      if (c.have_cll) { el_uint(col, 0x55BC, c.max_cll); el_uint(col, 0x55BD, c.max_fall); }      // MaxCLL, MaxFALL
+      if (c.have_mdcv) {                                                                          // MasteringMetadata: R, G, B, white point, luminance
+        std::vector<uint8_t> mm;
+        for (int i = 0; i < 3; i++) { el_float(mm, 0x55D1 + 2 * (uint32_t)i, c.primary_x[i] / 65536.0); el_float(mm, 0x55D2 + 2 * (uint32_t)i, c.primary_y[i] / 65536.0); }
+        el_float(mm, 0x55D7, c.white_x / 65536.0); el_float(mm, 0x55D8, c.white_y / 65536.0);
+        el_float(mm, 0x55D9, c.luminance_max / 256.0); el_float(mm, 0x55DA, c.luminance_min / 16384.0);
+        el_master(col, 0x55D0, mm);
+      }
+      el_master(video, 0x55B0, col);
+    }
     std::vector<uint8_t> te;
     el_uint(te, 0xD7, 1); el_uint(te, 0x73C5, 1); el_uint(te, 0x83, 1); el_uint(te, 0x9C, 0);
     el_str(te, 0x86, "V_AV1"); el_bin(te, 0x63A2, av1c);

@@ -4,6 +4,8 @@
 #include <sys/stat.h>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
+#include <algorithm>
 
 namespace av1mi_host {
 
@@ -102,7 +104,7 @@ bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain,
 }
 
 bool ChainTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err, bool *to_420, bool *deint,
-                 CropRect *crop, bool geometry) {
+                 CropRect *crop, bool geometry, bool *tonemap) {
   if (sar_n <= 0 || sar_d <= 0) sar_n = sar_d = 1;
   long cw = iw, ch = ih;
   bool sq = sar_n == sar_d, scaled = false;
@@ -144,6 +146,19 @@ bool ChainTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain,
       const std::string name = f.substr(7);
       if (name != "nv12" && name != "p010" && name != "p010le" && name != "yuv420p" && name != "yuv420p10le") { if (err) *err = "Invalid argument: unsupported filter " + f; return false; }
       if (to_420) *to_420 = true;
+    } else if (f == "tonemap_vaapi" || f.compare(0, 14, "tonemap_vaapi=") == 0) {
+      // BT.2390 to BT.709 is what is built (include/av1mi.h "tone mapping"); the output stays 10-bit whatever format= names
+      std::string rest = f.size() > 14 ? f.substr(14) : "";
+      while (!rest.empty()) {
+        const size_t c = rest.find(':');
+        const std::string tok = rest.substr(0, c);
+        rest = c == std::string::npos ? "" : rest.substr(c + 1);
+        if (tok != "format=nv12" && tok != "format=p010" && tok != "t=bt709" && tok != "m=bt709" && tok != "p=bt709") {
+          if (err) *err = "Invalid argument: unsupported filter argument " + f + " (only format=nv12|p010 and t / m / p = bt709: the output is BT.709 SDR)";
+          return false;
+        }
+      }
+      if (tonemap) *tonemap = true;
     } else if (f == "yadif" || f == "bwdif" || f == "deinterlace_vaapi" || f.compare(0, 6, "yadif=") == 0 || f.compare(0, 6, "bwdif=") == 0 ||
                f.compare(0, 18, "deinterlace_vaapi=") == 0) {
       // same-rate deinterlacing is what is built (include/av1mi.h "deinterlacing"): one frame per frame.  Field-rate modes, a forced
@@ -172,10 +187,89 @@ bool ChainTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain,
   return true;
 }
 
+// FFmpeg's names of the H.273 code points it lets a job set (libavutil/pixdesc.c), or a plain number 0 .. 255
+static bool code_point(const std::string &v, const char *const (*names)[2], int *out) {
+  for (; (*names)[0]; names++) if (v == (*names)[0]) { *out = std::atoi((*names)[1]); return true; }
+  return plain_int(v, out) && *out <= 255;
+}
+static const char *const kPrimaries[][2] = { { "bt709", "1" }, { "unknown", "2" }, { "unspecified", "2" }, { "bt470m", "4" }, { "bt470bg", "5" }, { "smpte170m", "6" }, { "smpte240m", "7" }, { "film", "8" },
+                                             { "bt2020", "9" }, { "smpte428", "10" }, { "smpte431", "11" }, { "smpte432", "12" }, { nullptr, nullptr } };
+static const char *const kTransfer[][2] = { { "bt709", "1" }, { "unknown", "2" }, { "unspecified", "2" }, { "gamma22", "4" }, { "bt470m", "4" }, { "gamma28", "5" }, { "bt470bg", "5" }, { "smpte170m", "6" },
+                                            { "smpte240m", "7" }, { "linear", "8" }, { "iec61966-2-4", "11" }, { "bt1361e", "12" }, { "iec61966-2-1", "13" }, { "bt2020-10", "14" },
+                                            { "bt2020-12", "15" }, { "smpte2084", "16" }, { "smpte428", "17" }, { "arib-std-b67", "18" }, { nullptr, nullptr } };
+static const char *const kMatrix[][2] = { { "rgb", "0" }, { "gbr", "0" }, { "bt709", "1" }, { "unknown", "2" }, { "unspecified", "2" }, { "fcc", "4" }, { "bt470bg", "5" }, { "smpte170m", "6" },
+                                          { "smpte240m", "7" }, { "ycgco", "8" }, { "bt2020nc", "9" }, { "bt2020c", "10" }, { "smpte2085", "11" }, { nullptr, nullptr } };
+static const char *const kRange[][2] = { { "tv", "0" }, { "mpeg", "0" }, { "limited", "0" }, { "pc", "1" }, { "jpeg", "1" }, { "full", "1" }, { nullptr, nullptr } };
+
+// n numbers separated by commas between `open` and ')' at *p (which moves past them); each 0 .. limit
+static bool numbers(const std::string &s, size_t *p, const char *open, int n, long long limit, long long *out) {
+  if (s.compare(*p, strlen(open), open)) return false;
+  *p += strlen(open);
+  for (int i = 0; i < n; i++) {
+    size_t d = 0;
+    long long v = 0;
+    while (*p + d < s.size() && d < 12 && s[*p + d] >= '0' && s[*p + d] <= '9') v = v * 10 + (s[*p + d++] - '0');
+    if (!d || v > limit || *p + d >= s.size() || s[*p + d] != (i + 1 < n ? ',' : ')')) return false;
+    out[i] = v; *p += d + 1;
+  }
+  return true;
+}
+
+// one of the colour options (true: args[i] was one; *why is set where its value is refused)
+static bool colour_option(const std::string &name, const std::string &v, BackendJob *job, std::string *why) {
+  std::string base = name;
+  for (const char *suffix : { ":v:0", ":v" }) if (base.size() > strlen(suffix) && !base.compare(base.size() - strlen(suffix), strlen(suffix), suffix)) { base.resize(base.size() - strlen(suffix)); break; }
+  auto take = [&](const char *const (*names)[2], int *out) { if (!code_point(v, names, out)) *why = "Invalid argument: " + name + " takes one of FFmpeg's names or a number 0 .. 255, not " + v; };
+  if (base == "-color_primaries") take(kPrimaries, &job->color_primaries);
+  else if (base == "-color_trc") take(kTransfer, &job->color_trc);
+  else if (base == "-colorspace") {
+    take(kMatrix, &job->colorspace);
+    if (why->empty() && job->colorspace == 0) *why = "Invalid argument: " + name + " " + v + ": matrix 0 (identity / RGB) implies 4:4:4, which is not coded";
+  }
+  else if (base == "-color_range") { if (!code_point(v, kRange, &job->color_range) || job->color_range > 1) *why = "Invalid argument: " + name + " takes tv / mpeg / limited (0) or pc / jpeg / full (1), not " + v; }
+  else if (name == "-av1mi_master_display") {
+    long long g[2], b[2], r[2], wp[2], l[2];
+    size_t p = 0;
+    if (!numbers(v, &p, "G(", 2, 50000, g) || !numbers(v, &p, "B(", 2, 50000, b) || !numbers(v, &p, "R(", 2, 50000, r) || !numbers(v, &p, "WP(", 2, 50000, wp) ||
+        !numbers(v, &p, "L(", 2, 100000000, l) || p != v.size() || l[0] <= l[1]) {
+      *why = "Invalid argument: -av1mi_master_display takes G(x,y)B(x,y)R(x,y)WP(x,y)L(max,min): chromaticities 0 .. 50000 (units of 0.00002), luminance in 0.0001 cd/m2 up to 10000 cd/m2, max above min; not " + v;
+      return true;
+    }
+    av1mi_colour &c = job->hdr;
+    auto chroma = [](long long n) { return (uint16_t)std::min<long long>((n * 65536 + 25000) / 50000, 65535); };      // 0.00002 units -> 0.16, to nearest
+    c.have_mdcv = 1;
+    c.primary_x[0] = chroma(r[0]); c.primary_y[0] = chroma(r[1]); c.primary_x[1] = chroma(g[0]); c.primary_y[1] = chroma(g[1]); c.primary_x[2] = chroma(b[0]); c.primary_y[2] = chroma(b[1]);
+    c.white_x = chroma(wp[0]); c.white_y = chroma(wp[1]);
+    c.luminance_max = (uint32_t)((l[0] * 256 + 5000) / 10000); c.luminance_min = (uint32_t)((l[1] * 16384 + 5000) / 10000);      // 0.0001 cd/m2 -> 24.8 / 18.14
+  }
+  else if (name == "-av1mi_max_cll") {
+    long long n[2];
+    size_t p = 0;
+    const std::string wrapped = "(" + v + ")";
+    if (!numbers(wrapped, &p, "(", 2, 65535, n) || p != wrapped.size()) { *why = "Invalid argument: -av1mi_max_cll takes \"cll,fall\" in cd/m2 (0 .. 65535 each), not " + v; return true; }
+    job->hdr.have_cll = 1; job->hdr.max_cll = (uint16_t)n[0]; job->hdr.max_fall = (uint16_t)n[1];
+  }
+  else return false;
+  return true;
+}
+
+av1mi_colour JobColour(const BackendJob &job, int y4m_range) {
+  av1mi_colour c = job.hdr;
+  if (job.tonemap) {      // what the kernel makes: BT.709 limited, the display-referred metadata of the source no longer applies
+    c = av1mi_colour();
+    c.primaries = c.transfer = c.matrix = 1;
+    return c;
+  }
+  c.primaries = job.color_primaries < 0 ? 2 : job.color_primaries; c.transfer = job.color_trc < 0 ? 2 : job.color_trc; c.matrix = job.colorspace < 0 ? 2 : job.colorspace;
+  c.full_range = job.color_range >= 0 ? job.color_range : y4m_range > 0 ? 1 : 0;
+  return c;
+}
+
 bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std::string *err) {
   if (args.size() < 3) { if (err) *err = "Invalid argument: too few arguments"; return false; }
   job->output = args.back();
   bool have_in = false, deint_given = false;
+  std::string colour_err;
   for (size_t i = 0; i + 1 < args.size(); i++) {
     if (args[i] == "-i") { job->input = args[i + 1]; have_in = true; }
     else if (args[i] == "-global_quality:v:0") job->quality = std::atoi(args[i + 1].c_str());
@@ -262,6 +356,14 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
       if (!plain_int(args[i + 1], &v) || v < 1 || v > 255) { if (err) *err = "Invalid argument: " + args[i] + " takes a quantiser index 1 .. 255, not " + args[i + 1]; return false; }
       (args[i] == "-qmin" ? job->qmin : job->qmax) = v;
     }
+    else if (colour_option(args[i], args[i + 1], job, &colour_err)) { if (!colour_err.empty()) { if (err) *err = colour_err; return false; } }
+    else if (args[i] == "-av1mi_tonemap") {
+      if (args[i + 1] == "off") job->tonemap = 0; else if (args[i + 1] == "bt2390") job->tonemap = 1;
+      else { if (err) *err = "Invalid argument: -av1mi_tonemap takes off or bt2390, not " + args[i + 1]; return false; }
+    }
+    else if (args[i] == "-av1mi_tonemap_peak") {
+      if (!plain_int(args[i + 1], &job->tonemap_peak) || job->tonemap_peak < 100 || job->tonemap_peak > 10000) { if (err) *err = "Invalid argument: -av1mi_tonemap_peak takes cd/m2, 100 .. 10000, not " + args[i + 1]; return false; }
+    }
     else if (args[i] == "-vf:v:0" || args[i] == "-vf") { job->vf = args[i + 1]; job->have_vf = true; }
     else if (args[i] == "-av1mi_scale") {
       const std::string &v = args[i + 1];
@@ -277,13 +379,22 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
     int w, h;
     bool to_420 = false, deint = false;
     CropRect chain_crop;
-    if (!ChainTarget(16, 16, 1, 1, job->vf, &w, &h, nullptr, err, &to_420, &deint, &chain_crop, false)) return false;
+    bool tonemap = false;
+    if (!ChainTarget(16, 16, 1, 1, job->vf, &w, &h, nullptr, err, &to_420, &deint, &chain_crop, false, &tonemap)) return false;
+    if (tonemap) job->tonemap = 1;
     if (job->crop_mode && job->vf.find("crop=") != std::string::npos) {
       if (err) *err = "Invalid argument: -av1mi_crop together with a crop= filter in the chain: give one";
       return false;
     }
     if (to_420) job->to_420 = true;
     if (deint && !deint_given) job->deinterlace = 1;      // a deinterlacer in the chain means auto; an explicit option keeps its say
+  }
+  if (job->tonemap_peak && !job->tonemap) { if (err) *err = "Invalid argument: -av1mi_tonemap_peak needs -av1mi_tonemap bt2390 (or tonemap_vaapi in the chain)"; return false; }
+  if (job->tonemap) {
+    if (job->denoise) { if (err) *err = "Invalid argument: tone mapping together with -av1mi_denoise is not built: the grain would be measured in the source's light"; return false; }
+    const bool src_ok = (job->color_primaries < 0 || job->color_primaries == 2 || job->color_primaries == 9) && (job->color_trc < 0 || job->color_trc == 2 || job->color_trc == 16) &&
+                        (job->colorspace < 0 || job->colorspace == 2 || job->colorspace == 9) && job->color_range <= 0;
+    if (!src_ok) { if (err) *err = "Invalid argument: tone mapping takes a bt2020 / smpte2084 / bt2020nc / tv source: with it -color_* describe the source, and they say otherwise"; return false; }
   }
   if (job->bitrate && job->target_bpp_u) { if (err) *err = "Invalid argument: -b:v:0 and -av1mi_target_bpp are two forms of one target: give one"; return false; }
   if ((job->qmin || job->qmax) && !job->bitrate && !job->target_bpp_u) { if (err) *err = "Invalid argument: -qmin / -qmax need a target (-b:v:0 or -av1mi_target_bpp)"; return false; }

@@ -8,6 +8,7 @@
 //   internal/metadata/probe.go:14-46  ProbeResult / StreamInfo (the fields the path consumes)
 // RunTranscode here does not spawn ffmpeg: it drives libav1mi.so (include/av1mi.h) on raw frames.
 #pragma once
+#include "../../include/av1mi_host.h"
 #include <string>
 #include <vector>
 #include "cropplan.hpp"
@@ -101,10 +102,22 @@ struct BackendJob {
                            // a second planar copy of the whole frame)
   CropRect crop;           // -av1mi_crop W:H:X:Y as given
   int crop_limit = kCropLimitDefault;   // -av1mi_crop_limit N (0 .. 255)
+  // Colour.  -color_primaries / -color_trc / -colorspace / -color_range (FFmpeg's output options, bare or with a :v / :v:0 suffix; FFmpeg's
+  // names or plain numbers 0 .. 255): the description the stream carries (av1mi_colour: sequence header, Matroska Colour).  -1 = not given:
+  // unspecified (2); the range then follows the Y4M header's XCOLORRANGE.  -av1mi_master_display "G(x,y)B(x,y)R(x,y)WP(x,y)L(max,min)" (the
+  // x265 / FFmpeg string: chromaticities in 0.00002, luminance in 0.0001 cd/m2) and -av1mi_max_cll "cll,fall": HDR10 static metadata.
+  int color_primaries = -1, color_trc = -1, colorspace = -1, color_range = -1;
+  av1mi_colour hdr = {};   // have_mdcv / have_cll and their numbers; the four fields above fill the rest when the job runs
+  // -av1mi_tonemap off | bt2390 (a tonemap_vaapi in the chain means bt2390): the PQ / BT.2020 source becomes BT.709 SDR on the GPU
+  // (av1mi_gop_config.tone_map); -av1mi_tonemap_peak N: the source's peak in cd/m2 (else the mastering display's maximum, else 1000).  The
+  // output is then described as 1 / 1 / 1 limited without metadata, and -color_* describe the SOURCE (bt2020 / smpte2084 / bt2020nc / tv or nothing)
+  int tonemap = 0, tonemap_peak = 0;
   std::vector<std::string> tracks;   // -av1mi_tracks <file.mka> (repeatable): Matroska side files whose audio / subtitle tracks are copied
                                      // next to the video (the reference's `-c:a copy -c:s copy`, transcode.go:134-137, after an external demux)
 };
 bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std::string *err);
+// the colour record a job's stream carries: the options, the Y4M header's range (-1 = none) where -color_range is absent, and what tone mapping forces
+av1mi_colour JobColour(const BackendJob &job, int y4m_range);
 
 // The video filter chain of the argv (transcode.go:92-115), evaluated as it is written on a source of iw x ih samples with sample aspect
 // ratio sar_n : sar_d.  Recognised, literally: the reference's SAR scale (transcode.go:97: (w, h) = sar < 1 ? (iw, iw / sar) :
@@ -127,7 +140,9 @@ bool ScaleTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain,
 // does not crop; a second crop composes with the first), and every later filter of the chain sees the window's size.  geometry = false
 // checks the syntax alone, for a chain whose source size is not known yet: *w, *h and the window are then meaningless.
 bool ChainTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain, int *w, int *h, bool *square, std::string *err, bool *to_420, bool *deint,
-                 CropRect *crop, bool geometry = true);
+                 CropRect *crop, bool geometry = true, bool *tonemap = nullptr);
+// (`tonemap_vaapi`, bare or with format=nv12|p010 and t / m / p = bt709, sets *tonemap — BackendJob::tonemap; any other argument of it, and the
+// software filters tonemap= and zscale=, are refused)
 
 // transcode.go:194-315 contract: (0, "") on success AND the output file exists; (code, text <= 800 chars) on failure;
 // (-1, text) when the backend could not run at all (no HIP device, library error before any frame).  Exit code 3 is the quality gate

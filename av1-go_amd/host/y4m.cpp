@@ -70,6 +70,11 @@ bool Y4mSource::open(const std::string &path, std::string *err, bool any_layout)
     else if (t[0] == 'F') sscanf(t.c_str() + 1, "%d:%d", &fps_n, &fps_d);
     else if (t[0] == 'C') cs = t.substr(1);
     else if (t[0] == 'I') interlace = t.size() < 2 ? 0 : t[1] == 't' ? 1 : t[1] == 'b' ? 2 : t[1] == 'm' ? 3 : 0;
+    else if (t.compare(0, 12, "XCOLORRANGE=") == 0) {
+      const std::string v = t.substr(12);
+      if (v == "FULL") colour_range = 1; else if (v == "LIMITED") colour_range = 0;
+      else { *err = "Invalid argument: Y4M header XCOLORRANGE=" + v + " (FULL or LIMITED)"; return false; }
+    }
     else if (t[0] == 'A') { if (sscanf(t.c_str() + 1, "%d:%d", &sar_n, &sar_d) != 2 || sar_n <= 0 || sar_d <= 0) sar_n = sar_d = 1; }
   }
   if (any_layout) {

@@ -22,6 +22,7 @@ class Y4mSource {
   ~Y4mSource();
   int w = 0, h = 0, bd = 8, fps_n = 30, fps_d = 1;
   int sar_n = 1, sar_d = 1;      // the header's A<n>:<d> (sample aspect ratio); absent, A0:0 or malformed = 1:1
+  int colour_range = -1;         // the header's XCOLORRANGE=FULL (1) | LIMITED (0); absent = -1; anything else is refused
   int interlace = 0;             // the header's I<c>: 0 progressive (Ip, I? or absent), 1 top field first (It), 2 bottom field first (Ib), 3 mixed (Im)
   // the source's own layout and depth (include/av1mi.h enum av1mi_source_chroma: 0 4:2:0, 1 4:2:2, 2 4:4:4, 3 grey; 8, 10 or 12 bits);
   // bd above is the depth it is CODED at (12 -> 10).  Other than 4:2:0 at bd only after open(.., .., true)

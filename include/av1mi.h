@@ -657,6 +657,55 @@ typedef struct av1mi_denoise_vec { int8_t dx_p, dy_p, dx_n, dy_n; } av1mi_denois
 int av1mi_denoise_mc_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int strength,
                             int range, int segments, const void *const *d_table, void *const d_dst[3], av1mi_grain_record *d_records, av1mi_denoise_vec *d_vectors);
 
+/* ---- tone mapping: an HDR10 source (BT.2020 non-constant luminance, PQ, limited range, 10 bit) becomes BT.709 limited-range SDR at 10 bits
+ * (av1-go_amd/csrc/tonemap_kernels.hip, k_tone_map).  Pointwise per 2x2 luma QUAD of planar 4:2:0 planes (four luma samples, one U, one V, the
+ * chroma applied to all four), in place.  Integers throughout, bit exact by definition; restated in numpy in tests/tonemap_ref.py.  Every
+ * constant below is its formula times 16384, rounded to nearest.  >> is the arithmetic shift.  Per quad, u = U - 512, v = V - 512, and per pixel:
+ *   1. R'G'B' as 10-bit full-range PQ codes, from E = (Y - 64) / 876, Cb = u / 896, Cr = v / 896 with Kr = 0.2627, Kb = 0.0593, Kg = 1 - Kr - Kb:
+ *        y = TO_RGB_Y * (Y - 64) + 8192;  R' = (y + TO_RGB_RV * v) >> 14;  G' = (y - TO_RGB_GV * v - TO_RGB_GU * u) >> 14;  B' = (y + TO_RGB_BU * u) >> 14
+ *      each clamped to 0 .. 1023 (TO_RGB_Y = 1023 / 876, _RV = 2 (1 - Kr) 1023 / 896, _GV = 2 Kr (1 - Kr) / Kg 1023 / 896, _GU = 2 Kb (1 - Kb) / Kg
+ *      1023 / 896, _BU = 2 (1 - Kb) 1023 / 896).  Y, U, V outside 64 .. 940 / 64 .. 960 are legal input.
+ *   2. M = max(R', G', B').
+ *   3. r, g, b = lin[R'], lin[G'], lin[B']: the PQ EOTF (SMPTE ST 2084) of code / 1023 in units of 2^-8 cd/m2 (10000 cd/m2 = 2 560 000).
+ *   4. gamut: c_i = max((GAMUT[i][0] r + GAMUT[i][1] g + GAMUT[i][2] b + 8192) >> 14, 0) (64-bit sums).  GAMUT = inverse(RGB709 -> XYZ) *
+ *      (RGB2020 -> XYZ) from the primaries' chromaticities and D65 = (0.3127, 0.3290); the rounding remainder of a row goes to its entry of
+ *      largest magnitude: EVERY ROW SUMS TO EXACTLY 16384, so grey stays grey.
+ *   5. gain: c_i = min((c_i * gain[M] + 32768) >> 16, 25600): the curve, in Q16, then the clamp at 100 cd/m2.
+ *   6. BT.709 OETF (4.5 L below 0.018, else 1.099 L^0.45 - 0.099, L = c / 25600) to a code 0 .. 1023: c < 512: oetf_lo[c] (direct).  Otherwise
+ *      k = floor(log2 c) (9 .. 14), sh = k - 6, i = (k - 9) * 64 + (c >> sh) - 64, f = c & ((1 << sh) - 1): every octave has 64 intervals, the
+ *      nodes oetf_hi[] hold 64 * code (Q6), and the code is min((oetf_hi[i] * ((1 << sh) - f) + oetf_hi[i + 1] * f + (1 << (sh + 5))) >> (sh + 6), 1023).
+ *      The interpolation error is below 0.01 code (the curvature falls as fast as the intervals grow).
+ *   7. BT.709 Y'CbCr limited (Kr = 0.2126, Kb = 0.0722; scales 876 / 1023 and 896 / 1023): with d(k) = k[0] R + k[1] G + k[2] B over the codes of 6,
+ *        Y = 64 + ((d(TO_YUV[0]) + 8192) >> 14) per pixel;  U = 512 + ((sum over the quad of d(TO_YUV[1]) + 32768) >> 16), V with TO_YUV[2]:
+ *      the mean of the four pixels' Cb / Cr, rounded once.  The Cb and Cr rows SUM TO EXACTLY 0 (remainder to the entry of largest magnitude).
+ *      All three clamped to 0 .. 1023.
+ * A neutral quad (U = V = 512) comes out with U = V = 512 exactly, and on that axis Y out never falls as Y in rises.
+ * The curve is the BT.2390 EETF from a source of 0 .. peak cd/m2 to a display of 0 .. 100 cd/m2 (black level 0): on PQ signals, e1 = min(e /
+ * pq(peak), 1), maxLum = pq(100) / pq(peak), KS = 1.5 maxLum - 0.5, e2 = e1 below KS and the Hermite spline P(e1) of the Report above it, out =
+ * e2 pq(peak).  Only the host-built table knows it: gain[M] = round(65536 * eotf(out) / eotf(e)) for e = M / 1023 (65536 where the light is 0),
+ * then raised by single steps (at most 6 in all, 0.03 % of the light, for the peaks 400 .. 10000) wherever step 5's result for r = g = b = lin[M] would fall below that for M - 1 (rounding alone can do that where
+ * the curve is flat, at and above the peak; the clamp at 100 cd/m2 keeps the steps from adding up). */
+#define AV1MI_TONE_LO 512        /* direct OETF entries */
+#define AV1MI_TONE_HI 385        /* OETF nodes: 6 octaves of 64 intervals + the last node */
+#define AV1MI_TONE_TO_RGB_Y 19133
+#define AV1MI_TONE_TO_RGB_RV 27584
+#define AV1MI_TONE_TO_RGB_GV 10688
+#define AV1MI_TONE_TO_RGB_GU 3078
+#define AV1MI_TONE_TO_RGB_BU 35194
+#define AV1MI_TONE_GAMUT { { 27206, -9628, -1194 }, { -2041, 18562, -137 }, { -297, -1648, 18329 } }
+#define AV1MI_TONE_TO_YUV { { 2983, 10034, 1013 }, { -1644, -5531, 7175 }, { 7175, -6517, -658 } }
+typedef struct av1mi_tone_tables {
+  uint32_t lin[1024], gain[1024], oetf_lo[AV1MI_TONE_LO], oetf_hi[AV1MI_TONE_HI + 3];      /* what the kernel reads (the last three entries pad to 16 bytes) */
+  int32_t to_rgb[5], gamut[3][3], to_yuv[3][3];      /* the constants above, for callers that restate the arithmetic */
+  int32_t peak;
+} av1mi_tone_tables;
+/* all tables for a source peak of 100 .. 10000 cd/m2 (else AV1MI_E_INVAL).  Plain host code in double precision, no GPU needed. */
+int av1mi_tone_map_tables(int peak, av1mi_tone_tables *out);
+/* `frames` stacked frames of planar 4:2:0 10-bit planes (uint16; luma width x height, width a multiple of 4, height even, up to 16384 each) tone-mapped
+ * IN PLACE.  d_tables: an av1mi_tone_tables in device memory, 16-byte aligned; the planes 16-byte aligned.  One launch, asynchronous on the
+ * context's stream.  Counted under AV1MI_K_INPUT in the profile. */
+int av1mi_tone_map(av1mi_ctx *ctx, int width, int height, int frames, void *d_y, void *d_u, void *d_v, const av1mi_tone_tables *d_tables);
+
 /* ---- GOP session: the encoder object a cgo replacement of RunTranscode drives (reference call site
  * internal/daemon/daemon.go:101 -> internal/ffmpeg/transcode.go:194; SURVEY.md §8b "av1mi_open(config) / av1mi_encode /
  * av1mi_flush").  It owns the closed-GOP orchestration and the encoder's filter-parameter POLICY, so that no caller
@@ -786,6 +835,16 @@ typedef struct av1mi_gop_config {
    * av1mi_gop_frame.grain and everything behind the fed buffers are as with denoise alone; av1mi_gop_submit_device still does not
    * denoise. */
   int denoise_range;
+  /* Tone mapping (0 = none: nothing new is allocated, launched or accepted; 1 = BT.2390; "tone mapping" above).  Needs bit_depth 10.  The source
+   * is taken to be BT.2020 non-constant luminance, PQ, limited range; every batch becomes BT.709 limited-range SDR at 10 bits before the block
+   * pipeline sees it: ONE launch (k_tone_map) behind the last input stage, whatever the chain was, in place on the planar planes at the coded
+   * size, over all segments, padding included (the padding of a fed frame replicates its edge, and stays a replica: the map is pointwise per
+   * quad and the true size's odd last column / row shares its quad with its replica).  No stage of the chain and no plane of its own; the
+   * tables (av1mi_tone_map_tables) are built and uploaded at open.  tone_map_peak: the source's peak in cd/m2, 100 .. 10000; 0 = 1000.
+   * Refused with av1mi_gop_submit_device (it would overwrite the caller's planes) and with denoise (the grain records would be measured in the
+   * wrong light).  The scene analysis keeps reading the frames as fed; the quality records measure against the tone-mapped source, which is
+   * the source as coded; with zero input stages av1mi_gop_download_fed returns the tone-mapped planes (the fed buffer IS the coded plane). */
+  int tone_map, tone_map_peak;
 } av1mi_gop_config;
 
 /* The source layout: what a session opened with a config is FED, as one description.  Everything a caller sizes or strides by — the

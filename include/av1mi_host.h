@@ -42,6 +42,22 @@ typedef struct av1mi_film_grain {
   int32_t overlap_flag, clip_to_restricted_range;
 } av1mi_film_grain;
 
+/* Colour description and HDR10 static metadata of a stream: what its sequence header says in color_config (AV1 spec 5.5.2, code points of
+ * ITU-T H.273) and what the metadata OBUs behind every sequence header carry (spec 5.8.3 / 5.8.4).  A stream has one; give the same record
+ * with every frame.  primaries = transfer = matrix = 2 (unspecified), full_range = 0 and no metadata: every byte is what it is without a
+ * record.  matrix 0 (identity) is refused: the spec's sRGB special case implies 4:4:4, which is not coded; so are code points above 255. */
+typedef struct av1mi_colour {
+  int32_t primaries, transfer, matrix;   /* color_primaries, transfer_characteristics, matrix_coefficients; 2 = unspecified */
+  int32_t full_range;                    /* color_range: 0 studio swing, 1 full swing */
+  int32_t have_mdcv;                     /* the mastering display colour volume below is given (metadata_type 2) */
+  uint16_t primary_x[3], primary_y[3];   /* R, G, B chromaticities, 0.16 fixed point */
+  uint16_t white_x, white_y;             /* 0.16 fixed point */
+  uint32_t luminance_max;                /* cd/m2, 24.8 fixed point */
+  uint32_t luminance_min;                /* cd/m2, 18.14 fixed point */
+  int32_t have_cll;                      /* the content light level below is given (metadata_type 1) */
+  uint16_t max_cll, max_fall;            /* cd/m2 */
+} av1mi_colour;
+
 /* Frame description for the bitstream writer.  All block arrays are raster order over the (width/8) x (height/8) grid of
  * 8x8 luma blocks; host pointers.  The tool set that can be described is listed in av1-go_amd/host/av1_bitstream.hpp. */
 /* Frame description (plain C: also bound from Python through libav1mi_host.so, and by the cgo shim of INTEGRATION.md). */
@@ -87,6 +103,9 @@ typedef struct av1mi_obu_frame {
    * was before the fields existed. */
   int32_t film_grain_present;
   const av1mi_film_grain *film_grain;
+  /* Colour description + HDR10 static metadata (above).  Read only where a sequence header is written: it goes into color_config, and the
+   * metadata OBUs follow the sequence header directly.  NULL (the default): every byte is what it was before the field existed. */
+  const av1mi_colour *colour;
 } av1mi_obu_frame;
 
 /* One temporal unit: temporal delimiter [+ sequence header] + OBU_FRAME.  threads > 1 codes the tiles on that many host
