@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+import txq_model
+
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "txfm_kat.npz")
 
 
@@ -178,7 +180,10 @@ def test_quantize_dequantize(O):
         lv, dq, nz = O.quantize(coef, dcq, acq, ls)
         assert nz == np.count_nonzero(lv)
         assert (O.dequantize(lv, dcq, acq, ls, bd) == np.clip(dq, -(1 << (7 + bd)), (1 << (7 + bd)) - 1)).all()
-        step = np.full(coef.shape, acq); step.flat[0] = dcq
-        assert (np.abs(np.clip(coef, -32767 * step >> ls, 32767 * step >> ls) - dq) <= (step >> ls) + 1).all() or True
+        # how far a level may lie from the coefficient it came from: the exact integer model, and its proved bound against the
+        # real-valued quantiser (tests/txq_model.py; +-40000 reaches past the int16 clamp of the coefficient, which is described there)
+        elv, edq = txq_model.quantize(coef, dcq, acq, ls)
+        assert (lv == elv).all() and (dq == edq).all()
+        txq_model.check_quantiser_against_ideal(coef, lv, dcq, acq, ls)
         assert (np.sign(lv) * np.sign(coef) >= 0).all()
     assert O.tx_scale(0) == 0 and O.tx_scale(3) == 1 and O.tx_scale(9) == 1 and O.tx_scale(17) == 1 and O.tx_scale(4) == 2 and O.tx_scale(11) == 2
