@@ -19,6 +19,14 @@ __device__ __forceinline__ unsigned xcd_swizzle(unsigned bid, unsigned nwg) {
 // 16384), so it is ONE full-rate 24-bit multiply; written as (size_t)row * stride it is a 64-bit multiply-add, four passes.
 __device__ __forceinline__ size_t row_off(int row, int stride) { return (size_t)__umul24((unsigned)row, (unsigned)stride); }
 
+// The hand-off between lanes of one wave that share a block (a group): LDS traffic is in order per wave, this only stops the compiler
+// moving LDS accesses across the hand-off (and drains lgkmcnt).
+#define AV1MI_GROUP_SYNC()                                   \
+  do {                                                       \
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   \
+    __builtin_amdgcn_wave_barrier();                         \
+  } while (0)
+
 // raster tile index -> (x, y, z) of a gx x gy x gz grid
 struct Tile3 { int x, y, z; };
 __device__ __forceinline__ Tile3 xcd_tile(unsigned gx, unsigned gy, unsigned gz) {

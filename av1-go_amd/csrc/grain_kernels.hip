@@ -22,8 +22,8 @@
 // Arithmetic: include/av1mi.h; restated in numpy by tests/denoise_ref.py.  Reference tree: nothing (it has no denoiser).
 // GrainBins and GrainLane are the records' LDS bins and a lane's open triple, for both denoising gathers.
 // Below them: k_denoise_search and k_denoise_mc_gather, the motion-compensated pair that av1mi_gop_config.denoise_range launches instead.
-#include "av1mi_internal.hpp"
 #include "gather_cells.hpp"
+#include "motion_common.hpp"
 
 namespace av1mi {
 
@@ -359,11 +359,7 @@ __global__ __launch_bounds__(256) void k_denoise_search(McGeom M, const void *co
       uint32_t d = 0;
       if (q < WDW - 1) {
         const int y = clampi(by * 16 - RANGE + r, M.h0 - 1), x = bx * 16 - RANGE + q * SPD;
-        if (x >= 0 && x + SPD - 1 <= M.w0 - 1) d = *reinterpret_cast<const uint32_t *>(F + (size_t)y * M.rb0 + (size_t)x * BPS);      // (x * BPS is a multiple of 4)
-        else {
-#pragma unroll
-          for (int k = 0; k < SPD; k++) d |= sample_at<Pix>(F, M.rb0, clampi(x + k, M.w0 - 1), y) << (8 * BPS * k);
-        }
+        d = row_dword(reinterpret_cast<const Pix *>(F + (size_t)y * M.rb0), x, M.w0);
       }
       s_win[wave][i] = d;
     }

@@ -17,31 +17,9 @@
 // Arithmetic: AV1 spec §7.11.3.4 (see mc_kernels.hip) + §7.13.3 / §7.12.3; search policy is this project's own and
 // mirrored by oracle/av1o_pipeline.c:av1o_inter_encode_frame.  Reference tree: nothing (transcode.go:120).
 #include "block_code.hpp"
-#include "av1mi_internal.hpp"
+#include "motion_common.hpp"
 
 namespace av1mi {
-
-// regular 8-tap (Subpel_Filters[0]) and regular 4-tap (Subpel_Filters[4]) rows, the only ones this encoder policy uses
-__constant__ int16_t kRegular8[16][8] = {
-  { 0, 0, 0, 128, 0, 0, 0, 0 }, { 0, 2, -6, 126, 8, -2, 0, 0 }, { 0, 2, -10, 122, 18, -4, 0, 0 }, { 0, 2, -12, 116, 28, -8, 2, 0 },
-  { 0, 2, -14, 110, 38, -10, 2, 0 }, { 0, 2, -14, 102, 48, -12, 2, 0 }, { 0, 2, -16, 94, 58, -12, 2, 0 }, { 0, 2, -14, 84, 66, -12, 2, 0 },
-  { 0, 2, -14, 76, 76, -14, 2, 0 }, { 0, 2, -12, 66, 84, -14, 2, 0 }, { 0, 2, -12, 58, 94, -16, 2, 0 }, { 0, 2, -12, 48, 102, -14, 2, 0 },
-  { 0, 2, -10, 38, 110, -14, 2, 0 }, { 0, 2, -8, 28, 116, -12, 2, 0 }, { 0, 0, -4, 18, 122, -10, 2, 0 }, { 0, 0, -2, 8, 126, -6, 2, 0 } };
-__constant__ int16_t kRegular4[16][8] = {
-  { 0, 0, 0, 128, 0, 0, 0, 0 }, { 0, 0, -4, 126, 8, -2, 0, 0 }, { 0, 0, -8, 122, 18, -4, 0, 0 }, { 0, 0, -10, 116, 28, -6, 0, 0 },
-  { 0, 0, -12, 110, 38, -8, 0, 0 }, { 0, 0, -12, 102, 48, -10, 0, 0 }, { 0, 0, -14, 94, 58, -10, 0, 0 }, { 0, 0, -12, 84, 66, -10, 0, 0 },
-  { 0, 0, -12, 76, 76, -12, 0, 0 }, { 0, 0, -10, 66, 84, -12, 0, 0 }, { 0, 0, -10, 58, 94, -14, 0, 0 }, { 0, 0, -10, 48, 102, -12, 0, 0 },
-  { 0, 0, -8, 38, 110, -12, 0, 0 }, { 0, 0, -6, 28, 116, -10, 0, 0 }, { 0, 0, -4, 18, 122, -8, 0, 0 }, { 0, 0, -2, 8, 126, -4, 0, 0 } };
-
-// the plane frame f predicts from: the restored one, or (ref_sel given and 0 for this frame and plane) the CDEF output — the
-// restoration on / off decision of the previous frame (lr_kernel.hip k_lr_decide) without a copy
-// (the flag is read as the aligned dword that holds it: f is uniform in a workgroup, so this is a scalar load)
-__device__ __forceinline__ const void *ref_plane(const InterLaunch &L, int f, int p) {
-  if (!L.ref_sel) return L.ref[p];
-  const int i = f * 3 + p;
-  const uint32_t w = reinterpret_cast<const uint32_t *>(L.ref_sel)[i >> 2];
-  return ((w >> (8 * (i & 3))) & 0xffu) ? L.ref[p] : L.ref_alt[p];
-}
 
 // ------------------------------------------------------------------------------------------ integer search
 // The search runs on the 8 most significant bits of the samples (10-bit content is shifted down by 2: encoder policy,
@@ -79,38 +57,18 @@ __global__ __launch_bounds__(256) void k_me_int(InterLaunch L) {
   }
   const Pix *src = reinterpret_cast<const Pix *>(L.src[0]) + (size_t)f * L.h * L.stride_y;
   const Pix *ref = reinterpret_cast<const Pix *>(ref_plane(L, f, 0)) + (size_t)f * L.h * L.stride_y;
-  // staging, four samples per lane per step (the window starts on a 4-sample boundary and its width is a multiple of 4);
-  // groups that lie inside the plane are one vector load, the others clamp sample by sample (the spec's edge extension)
+  // staging, four samples per lane per step as one dword of their 8-bit views (the window starts on a 4-sample boundary and its width
+  // is a multiple of 4)
   const int wg = WDX >> 2;
   for (int i = tid; i < WDY * wg; i += 256) {
     const int r = i / wg, c = (i - r * wg) * 4;
     const int fy = min(max(sby * 64 - R + r + cy, 0), L.h - 1), fx = sbx * 64 - R4 + c + cx;
-    const Pix *row = ref + row_off(fy, L.stride_y);
-    uint32_t u;
-    if (fx >= 0 && fx + 3 < L.w) {
-      if constexpr (sizeof(Pix) == 1) u = *reinterpret_cast<const uint32_t *>(row + fx);
-      else { const uint2 v = *reinterpret_cast<const uint2 *>(row + fx); u = ((v.x >> sh) & 0xff) | (((v.x >> (16 + sh)) & 0xff) << 8) | (((v.y >> sh) & 0xff) << 16) | (((v.y >> (16 + sh)) & 0xff) << 24); }
-    } else {
-      u = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) u |= (uint32_t)((row[min(max(fx + k, 0), L.w - 1)] >> sh) & 0xff) << (8 * k);
-    }
-    *reinterpret_cast<uint32_t *>(win + r * WS + c) = u;
+    *reinterpret_cast<uint32_t *>(win + r * WS + c) = row_dword<Pix, 4>(ref + row_off(fy, L.stride_y), fx, L.w, sh);
   }
   for (int i = tid; i < 64 * 16; i += 256) {
     const int r = i >> 4, c = (i & 15) * 4;
     const int fy = min(sby * 64 + r, L.h - 1), fx = sbx * 64 + c;
-    const Pix *row = src + row_off(fy, L.stride_y);
-    uint32_t u;
-    if (fx + 3 < L.w) {
-      if constexpr (sizeof(Pix) == 1) u = *reinterpret_cast<const uint32_t *>(row + fx);
-      else { const uint2 v = *reinterpret_cast<const uint2 *>(row + fx); u = ((v.x >> sh) & 0xff) | (((v.x >> (16 + sh)) & 0xff) << 8) | (((v.y >> sh) & 0xff) << 16) | (((v.y >> (16 + sh)) & 0xff) << 24); }
-    } else {
-      u = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) u |= (uint32_t)((row[min(fx + k, L.w - 1)] >> sh) & 0xff) << (8 * k);
-    }
-    *reinterpret_cast<uint32_t *>(srct + r * 64 + c) = u;
+    *reinterpret_cast<uint32_t *>(srct + r * 64 + c) = row_dword<Pix, 4>(src + row_off(fy, L.stride_y), fx, L.w, sh);      // (fx >= 0: only the right side ever clamps)
   }
   if (tid < 64) s_best[tid] = 0xFFFFFFFFu;
   __syncthreads();
@@ -223,35 +181,6 @@ __global__ __launch_bounds__(256) void k_me_int(InterLaunch L) {
 // 2-D sub-pel prediction of row `lane` of a B x B block from a window in LDS (origin = integer position - 4, i.e. the
 // window starts 4 samples left of / above the integer-vector block): posx/posy = displacement from the window's block
 // origin in 1/16 samples, in [-16, 15].  im: (B+7) x B int16 scratch of the group.  NL = lanes of the block.
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-// The first v_dot2 of an accumulation with its start value as an operand.  The compiler always picks the two-address form
-// (v_dot2c: accumulator = destination) and initialises every accumulator with a v_mov first — one extra instruction per output
-// sample in loops that are nothing but dot products; the three-address VOP3P form takes the start value from an SGPR.
-__device__ __forceinline__ int dot2_start(uint32_t a, uint32_t b, int start_uniform) {
-  int d;
-  asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(start_uniform));
-  return d;
-}
-// One window row of N samples from plane row `row`, columns x0 .. x0 + N - 1, into the dword-aligned LDS row `dst`.
-// Inside the plane it is one unaligned vector load (the hardware takes any address) and N * sizeof(Pix) / 4 dword stores;
-// rows that stick out clamp sample by sample (the spec's edge extension).
-template <int N, typename Pix> __device__ __forceinline__ void stage_window_row(const Pix *row, int x0, int w, Pix *dst) {
-  constexpr int ND = N * (int)sizeof(Pix) / 4;
-  uint32_t u[ND];
-  if (x0 >= 0 && x0 + N <= w) __builtin_memcpy(u, row + x0, sizeof(u));
-  else {
-    constexpr int PER = 4 / (int)sizeof(Pix);
-#pragma unroll
-    for (int d = 0; d < ND; d++) {
-      u[d] = 0;
-#pragma unroll
-      for (int k = 0; k < PER; k++) u[d] |= (uint32_t)row[min(max(x0 + d * PER + k, 0), w - 1)] << (k * 8 * (int)sizeof(Pix));
-    }
-  }
-  uint32_t *q = reinterpret_cast<uint32_t *>(dst);
-#pragma unroll
-  for (int d = 0; d < ND; d++) q[d] = u[d];
-}
 // N consecutive samples starting `ox` samples into a dword-aligned LDS row: aligned dword reads + funnel shift, so that the
 // row costs (N * sizeof(ES)) / 4 + 1 LDS reads instead of N (k_inter_pipe is LDS-bound).  ox in [0, 4 / sizeof(ES)).
 template <int N, typename ES> __device__ __forceinline__ void row_samples(const ES *row, int ox, int *v) {
@@ -484,8 +413,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
   __shared__ __attribute__((aligned(16))) int16_t s_filt[3][16][8];   // regular 8-tap, regular 4-tap, regular 8-tap x 32 (mc_h16 at 10 bits, mc_v7)
   if (threadIdx.x < 128) {
     const int t = threadIdx.x;
-    reinterpret_cast<uint32_t *>(s_filt)[t] = t < 64 ? reinterpret_cast<const uint32_t *>(kRegular8)[t] : reinterpret_cast<const uint32_t *>(kRegular4)[t - 64];
-    s_filt[2][t >> 3][t & 7] = (int16_t)(kRegular8[t >> 3][t & 7] * 32);
+    reinterpret_cast<uint32_t *>(s_filt)[t] = reinterpret_cast<const uint32_t *>(kSubpel[t < 64 ? 0 : 4])[t & 63];
+    s_filt[2][t >> 3][t & 7] = (int16_t)(kSubpel[0][t >> 3][t & 7] * 32);
   }
   __syncthreads();
 
@@ -690,21 +619,11 @@ hipError_t launch_me_int(const InterLaunch &L, hipStream_t s) {
   if (L.nframes <= 0) return hipSuccess;
   const int sbs = ((L.w + 63) / 64) * ((L.h + 63) / 64);
   const dim3 g1((unsigned)(sbs * L.nframes));   // 1-D: the kernel orders the tiles (xcd_tile)
-  if (L.centres) {
-    if (L.range == 8) {
-      if (L.bd == 8) hipLaunchKernelGGL((k_me_int<uint8_t, 8, true>), g1, dim3(256), 0, s, L);
-      else hipLaunchKernelGGL((k_me_int<uint16_t, 8, true>), g1, dim3(256), 0, s, L);
-    } else {
-      if (L.bd == 8) hipLaunchKernelGGL((k_me_int<uint8_t, 0, true>), g1, dim3(256), 0, s, L);
-      else hipLaunchKernelGGL((k_me_int<uint16_t, 0, true>), g1, dim3(256), 0, s, L);
-    }
-  } else if (L.range == 8) {
-    if (L.bd == 8) hipLaunchKernelGGL((k_me_int<uint8_t, 8, false>), g1, dim3(256), 0, s, L);
-    else hipLaunchKernelGGL((k_me_int<uint16_t, 8, false>), g1, dim3(256), 0, s, L);
-  } else {
-    if (L.bd == 8) hipLaunchKernelGGL((k_me_int<uint8_t, 0, false>), g1, dim3(256), 0, s, L);
-    else hipLaunchKernelGGL((k_me_int<uint16_t, 0, false>), g1, dim3(256), 0, s, L);
-  }
+  // the instantiation by (bit depth, range known at compile time, centres given)
+  using Kernel = void (*)(InterLaunch);
+  static const Kernel kernels[2][2][2] = { { { k_me_int<uint8_t, 0, false>, k_me_int<uint8_t, 0, true> }, { k_me_int<uint8_t, 8, false>, k_me_int<uint8_t, 8, true> } },
+                                           { { k_me_int<uint16_t, 0, false>, k_me_int<uint16_t, 0, true> }, { k_me_int<uint16_t, 8, false>, k_me_int<uint16_t, 8, true> } } };
+  hipLaunchKernelGGL(kernels[L.bd != 8][L.range == 8][L.centres != nullptr], g1, dim3(256), 0, s, L);
   return hipGetLastError();
 }
 hipError_t launch_inter_pipe(const InterLaunch &L, hipStream_t s) {

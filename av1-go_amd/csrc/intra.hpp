@@ -7,21 +7,12 @@
 // av1_dr_prediction_z1/z2/z3_c / av1_filter_intra_edge_c / av1_upsample_intra_edge_c (SURVEY.md §8a
 // row K3); the reference tree has no counterpart (transcode.go:120).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "av1mi_internal.hpp"      // AV1MI_GROUP_SYNC
 
 namespace av1mi {
 
 enum { DC_PRED, V_PRED, H_PRED, D45_PRED, D135_PRED, D113_PRED, D157_PRED, D203_PRED, D67_PRED,
        SMOOTH_PRED, SMOOTH_V_PRED, SMOOTH_H_PRED, PAETH_PRED, INTRA_MODES };
-
-// lanes of one wave: LDS traffic is in order per wave, this only stops the compiler moving LDS
-// accesses across the hand-off (and drains lgkmcnt).
-#define AV1MI_GROUP_SYNC()                                   \
-  do {                                                       \
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   \
-    __builtin_amdgcn_wave_barrier();                         \
-  } while (0)
 
 // Sum over the G (4, 8, 16 or 32) consecutive lanes of a group with DPP cross-lane VALU moves (no LDS round trip, unlike
 // __shfl_xor's ds_bpermute): quad xor 1, quad xor 2, then half-row / row mirrors pair the quads.  Every lane gets the sum.

@@ -10,49 +10,9 @@
 //
 // Restates AV1 spec §7.11.3.4 == libaom av1_highbd_convolve_2d_sr_c; nothing to cite in the
 // reference tree (internal/ffmpeg/transcode.go:120 names the external encoder only).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "av1mi_internal.hpp"
+#include "motion_common.hpp"
 
 namespace av1mi {
-
-__constant__ int16_t kSubpel[6][16][8] = {
-  { { 0, 0, 0, 128, 0, 0, 0, 0 }, { 0, 2, -6, 126, 8, -2, 0, 0 }, { 0, 2, -10, 122, 18, -4, 0, 0 }, { 0, 2, -12, 116, 28, -8, 2, 0 },
-    { 0, 2, -14, 110, 38, -10, 2, 0 }, { 0, 2, -14, 102, 48, -12, 2, 0 }, { 0, 2, -16, 94, 58, -12, 2, 0 }, { 0, 2, -14, 84, 66, -12, 2, 0 },
-    { 0, 2, -14, 76, 76, -14, 2, 0 }, { 0, 2, -12, 66, 84, -14, 2, 0 }, { 0, 2, -12, 58, 94, -16, 2, 0 }, { 0, 2, -12, 48, 102, -14, 2, 0 },
-    { 0, 2, -10, 38, 110, -14, 2, 0 }, { 0, 2, -8, 28, 116, -12, 2, 0 }, { 0, 0, -4, 18, 122, -10, 2, 0 }, { 0, 0, -2, 8, 126, -6, 2, 0 } },
-  { { 0, 0, 0, 128, 0, 0, 0, 0 }, { 0, 2, 28, 62, 34, 2, 0, 0 }, { 0, 0, 26, 62, 36, 4, 0, 0 }, { 0, 0, 22, 62, 40, 4, 0, 0 },
-    { 0, 0, 20, 60, 42, 6, 0, 0 }, { 0, 0, 18, 58, 44, 8, 0, 0 }, { 0, 0, 16, 56, 46, 10, 0, 0 }, { 0, -2, 16, 54, 48, 12, 0, 0 },
-    { 0, -2, 14, 52, 52, 14, -2, 0 }, { 0, 0, 12, 48, 54, 16, -2, 0 }, { 0, 0, 10, 46, 56, 16, 0, 0 }, { 0, 0, 8, 44, 58, 18, 0, 0 },
-    { 0, 0, 6, 42, 60, 20, 0, 0 }, { 0, 0, 4, 40, 62, 22, 0, 0 }, { 0, 0, 4, 36, 62, 26, 0, 0 }, { 0, 0, 2, 34, 62, 28, 2, 0 } },
-  { { 0, 0, 0, 128, 0, 0, 0, 0 }, { -2, 2, -6, 126, 8, -2, 2, 0 }, { -2, 6, -12, 124, 16, -6, 4, -2 }, { -2, 8, -18, 120, 26, -10, 6, -2 },
-    { -4, 10, -22, 116, 38, -14, 6, -2 }, { -4, 10, -22, 108, 48, -18, 8, -2 }, { -4, 10, -24, 100, 60, -20, 8, -2 },
-    { -4, 10, -24, 90, 70, -22, 10, -2 }, { -4, 12, -24, 80, 80, -24, 12, -4 }, { -2, 10, -22, 70, 90, -24, 10, -4 },
-    { -2, 8, -20, 60, 100, -24, 10, -4 }, { -2, 8, -18, 48, 108, -22, 10, -4 }, { -2, 6, -14, 38, 116, -22, 10, -4 },
-    { -2, 6, -10, 26, 120, -18, 8, -2 }, { -2, 4, -6, 16, 124, -12, 6, -2 }, { 0, 2, -2, 8, 126, -6, 2, -2 } },
-  { { 0, 0, 0, 128, 0, 0, 0, 0 }, { 0, 0, 0, 120, 8, 0, 0, 0 }, { 0, 0, 0, 112, 16, 0, 0, 0 }, { 0, 0, 0, 104, 24, 0, 0, 0 },
-    { 0, 0, 0, 96, 32, 0, 0, 0 }, { 0, 0, 0, 88, 40, 0, 0, 0 }, { 0, 0, 0, 80, 48, 0, 0, 0 }, { 0, 0, 0, 72, 56, 0, 0, 0 },
-    { 0, 0, 0, 64, 64, 0, 0, 0 }, { 0, 0, 0, 56, 72, 0, 0, 0 }, { 0, 0, 0, 48, 80, 0, 0, 0 }, { 0, 0, 0, 40, 88, 0, 0, 0 },
-    { 0, 0, 0, 32, 96, 0, 0, 0 }, { 0, 0, 0, 24, 104, 0, 0, 0 }, { 0, 0, 0, 16, 112, 0, 0, 0 }, { 0, 0, 0, 8, 120, 0, 0, 0 } },
-  { { 0, 0, 0, 128, 0, 0, 0, 0 }, { 0, 0, -4, 126, 8, -2, 0, 0 }, { 0, 0, -8, 122, 18, -4, 0, 0 }, { 0, 0, -10, 116, 28, -6, 0, 0 },
-    { 0, 0, -12, 110, 38, -8, 0, 0 }, { 0, 0, -12, 102, 48, -10, 0, 0 }, { 0, 0, -14, 94, 58, -10, 0, 0 }, { 0, 0, -12, 84, 66, -10, 0, 0 },
-    { 0, 0, -12, 76, 76, -12, 0, 0 }, { 0, 0, -10, 66, 84, -12, 0, 0 }, { 0, 0, -10, 58, 94, -14, 0, 0 }, { 0, 0, -10, 48, 102, -12, 0, 0 },
-    { 0, 0, -8, 38, 110, -12, 0, 0 }, { 0, 0, -6, 28, 116, -10, 0, 0 }, { 0, 0, -4, 18, 122, -8, 0, 0 }, { 0, 0, -2, 8, 126, -4, 0, 0 } },
-  { { 0, 0, 0, 128, 0, 0, 0, 0 }, { 0, 0, 30, 62, 34, 2, 0, 0 }, { 0, 0, 26, 62, 36, 4, 0, 0 }, { 0, 0, 22, 62, 40, 4, 0, 0 },
-    { 0, 0, 20, 60, 42, 6, 0, 0 }, { 0, 0, 18, 58, 44, 8, 0, 0 }, { 0, 0, 16, 56, 46, 10, 0, 0 }, { 0, 0, 14, 54, 48, 12, 0, 0 },
-    { 0, 0, 12, 52, 52, 12, 0, 0 }, { 0, 0, 12, 48, 54, 14, 0, 0 }, { 0, 0, 10, 46, 56, 16, 0, 0 }, { 0, 0, 8, 44, 58, 18, 0, 0 },
-    { 0, 0, 6, 42, 60, 20, 0, 0 }, { 0, 0, 4, 40, 62, 22, 0, 0 }, { 0, 0, 4, 36, 62, 26, 0, 0 }, { 0, 0, 2, 34, 62, 30, 0, 0 } },
-};
-
-// the lanes of a block live in one wave: an LDS fence + wave barrier orders their hand-offs
-#define AV1MI_MC_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
-
-__device__ __forceinline__ int mc_filter_index(int type, int dim) {
-  if (dim <= 4) { if (type == 0 || type == 2) return 4; if (type == 1) return 5; }
-  return type;
-}
-
-typedef short s16x2 __attribute__((ext_vector_type(2)));
 
 // Block = BH lanes of one wave (64 / BH blocks per wave, 4 waves per workgroup); lane r owns window rows r, r + BH, ... in
 // the horizontal pass and output row r in the vertical pass.  What k_inter_pipe taught applies here:
@@ -84,6 +44,8 @@ __global__ __launch_bounds__(256) void k_mc(McLaunch L) {
   uint32_t *wn = win[wave * NBW + grp];
   int16_t *im = inter[wave * NBW + grp];
   // ---- stage the window: rows r, r + BH, ...
+  // (stage_window_row<(WD - 1) * PER, Pix> of motion_common.hpp is this loop's body, but through it k_mc<8, 4, uint8_t> takes six registers
+  // more and loses a wave per SIMD: the loop keeps its own copy, with the test hoisted out of it)
   const bool inside = x0 >= 0 && x0 + (WD - 1) * PER <= L.plane_w;
   for (int j = r; j < RH; j += BH) {
     const Pix *row = ref + (size_t)min(max(y0 + j, 0), L.plane_h - 1) * L.ref_stride;
@@ -100,7 +62,7 @@ __global__ __launch_bounds__(256) void k_mc(McLaunch L) {
 #pragma unroll
     for (int i = 0; i < WD - 1; i++) wn[j * WD + i] = u[i];
   }
-  AV1MI_MC_SYNC();
+  AV1MI_GROUP_SYNC();
   int fx[8], fy[8];
 #pragma unroll
   for (int t = 0; t < 8; t++) { fx[t] = fxp[t]; fy[t] = fyp[t]; }
@@ -155,7 +117,7 @@ __global__ __launch_bounds__(256) void k_mc(McLaunch L) {
       for (int i = 0; i < CH / 2; i++) q[i] = o[i];
     }
   }
-  AV1MI_MC_SYNC();
+  AV1MI_GROUP_SYNC();
   // ---- vertical pass: output row r (InterRound1 = 11, Clip1)
   Pix *dst = reinterpret_cast<Pix *>(L.dst) + (size_t)(d.y + r) * L.dst_stride + d.x;
   const int maxpix = (1 << L.bd) - 1;

@@ -14,7 +14,7 @@
 // The quarter planes live in a scratch area (me_layout) with rows padded to a multiple of 4 bytes, so that every store and
 // every aligned window group is a dword; the padding columns hold the replicated last column and are never scored.
 // Arithmetic and tie rules: include/av1mi.h; restated in numpy by tests/me_ref.py.  Reference tree: nothing (transcode.go:120).
-#include "av1mi_internal.hpp"
+#include "motion_common.hpp"
 
 namespace av1mi {
 
@@ -34,14 +34,6 @@ MeLayout me_layout(int w, int h, int nframes) {
   return M;
 }
 
-// the flag ref_plane() of inter_kernels.hip reads, here for the luma plane alone
-__device__ __forceinline__ const void *me_ref_luma(const InterLaunch &L, int f) {
-  if (!L.ref_sel) return L.ref[0];
-  const int i = f * 3;
-  const uint32_t w = reinterpret_cast<const uint32_t *>(L.ref_sel)[i >> 2];
-  return ((w >> (8 * (i & 3))) & 0xffu) ? L.ref[0] : L.ref_alt[0];
-}
-
 // ------------------------------------------------------------------------------------------ quarter planes
 // grid: (workgroups per plane) x 2 planes x nframes, in xcd_tile order: the frame and the plane are uniform in a workgroup
 template <typename Pix>
@@ -52,31 +44,9 @@ __global__ __launch_bounds__(256) void k_me_down(InterLaunch L, uint8_t *qsrc, u
   const int item = tl.x * 256 + (int)threadIdx.x;
   if (item >= ng * qh) return;
   const int y = item / ng, x0 = (item - y * ng) * 4;           // output samples (x0 .. x0 + 3, y)
-  const Pix *in = reinterpret_cast<const Pix *>(pl ? me_ref_luma(L, f) : L.src[0]) + (size_t)f * L.h * L.stride_y;
-  uint32_t sum[4] = { 8, 8, 8, 8 };
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int ix = 4 * x0;                                                        // first of the row's 16 input samples; ix < w
-    const Pix *row = in + row_off(4 * y + r, L.stride_y) + ix;                    // 4 y + r < h: qh = h / 4
-    if (ix + 15 < L.w) {
-      uint32_t d[4 * (int)sizeof(Pix)];
-      __builtin_memcpy(d, row, sizeof(d));
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        if constexpr (sizeof(Pix) == 1) sum[k] = __builtin_amdgcn_sad_u8(d[k], 0u, sum[k]);
-        else {
-          // two samples per dword: their 8-bit views side by side, added as packed halves (8 x 255 per half at most here)
-          const uint32_t t = ((d[2 * k] >> sh) & 0x00ff00ffu) + ((d[2 * k + 1] >> sh) & 0x00ff00ffu);
-          sum[k] += (t & 0xffffu) + (t >> 16);
-        }
-      }
-    } else {      // the last group of a row whose width is not a multiple of 16: the true last column replicated (the padding of the plane)
-#pragma unroll
-      for (int k = 0; k < 16; k++) sum[k >> 2] += (uint32_t)(row[min(k, L.w - 1 - ix)] >> sh) & 0xffu;
-    }
-  }
+  const Pix *in = reinterpret_cast<const Pix *>(pl ? ref_plane(L, f, 0) : L.src[0]) + (size_t)f * L.h * L.stride_y;
   uint8_t *out = (pl ? qref : qsrc) + (size_t)f * qs * qh + (size_t)y * qs + x0;
-  *reinterpret_cast<uint32_t *>(out) = (sum[0] >> 4) | ((sum[1] >> 4) << 8) | ((sum[2] >> 4) << 16) | ((sum[3] >> 4) << 24);
+  *reinterpret_cast<uint32_t *>(out) = quarter_dword<Pix>(in, L.stride_y, L.w, sh, x0, y);
 }
 
 // ------------------------------------------------------------------------------------------ coarse search
@@ -101,14 +71,8 @@ __global__ __launch_bounds__(256) void k_me_coarse(const uint8_t *qsrc, const ui
     const int r = is_blk ? j >> 2 : (j - 64) / WD, c = is_blk ? (j & 3) * 4 : ((j - 64) - r * WD) * 4;
     const int fy = min(max(16 * ty + r - (is_blk ? 0 : Rc), 0), qh - 1), fx = 16 * tx + c - (is_blk ? 0 : Rc);
     const uint8_t *row = (is_blk ? qsrc : qref) + (size_t)f * qs * qh + (size_t)fy * qs;
-    uint32_t u;
-    if (fx >= 0 && fx + 3 < qw && !(fx & 3)) u = *reinterpret_cast<const uint32_t *>(row + fx);
-    else {
-      u = 0;
-#pragma unroll
-      for (int b = 0; b < 4; b++) u |= (uint32_t)row[min(max(fx + b, 0), qw - 1)] << (8 * b);
-    }
-    *reinterpret_cast<uint32_t *>(is_blk ? blk[k] + r * 16 + c : win[k] + r * kWinStride + c) = u;
+    // (a window group starts at any byte, fx = 16 tx + c - Rc: inside the plane it is still one load of its four bytes)
+    *reinterpret_cast<uint32_t *>(is_blk ? blk[k] + r * 16 + c : win[k] + r * kWinStride + c) = row_dword(row, fx, qw);
   }
   if (tid < kTiles) s_best[tid] = 0xFFFFFFFFu;
   __syncthreads();

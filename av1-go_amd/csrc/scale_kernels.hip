@@ -342,15 +342,9 @@ hipError_t launch_scale(const ScalePlan *P, int frames, const void *const *src, 
   const unsigned total = (unsigned)(L.first_wg2 + P->tiles_per_frame[2] * frames);
   const dim3 grid(total), block(256);
   const size_t lds = P->lds_bytes;
-  if (P->bd == 8) {
-    if (P->taps == 6) hipLaunchKernelGGL((k_scale<uint8_t, 6>), grid, block, lds, s, L);
-    else if (P->taps == 12) hipLaunchKernelGGL((k_scale<uint8_t, 12>), grid, block, lds, s, L);
-    else hipLaunchKernelGGL((k_scale<uint8_t, 0>), grid, block, lds, s, L);
-  } else {
-    if (P->taps == 6) hipLaunchKernelGGL((k_scale<uint16_t, 6>), grid, block, lds, s, L);
-    else if (P->taps == 12) hipLaunchKernelGGL((k_scale<uint16_t, 12>), grid, block, lds, s, L);
-    else hipLaunchKernelGGL((k_scale<uint16_t, 0>), grid, block, lds, s, L);
-  }
+  using Kernel = void (*)(ScaleLaunch);
+  static const Kernel kernels[2][3] = { { k_scale<uint8_t, 0>, k_scale<uint8_t, 6>, k_scale<uint8_t, 12> }, { k_scale<uint16_t, 0>, k_scale<uint16_t, 6>, k_scale<uint16_t, 12> } };
+  hipLaunchKernelGGL(kernels[P->bd != 8][P->taps == 6 ? 1 : P->taps == 12 ? 2 : 0], grid, block, lds, s, L);
   return hipGetLastError();
 }
 

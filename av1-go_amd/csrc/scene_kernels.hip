@@ -16,7 +16,7 @@
 //   k_frames_gather the planes of a batch from a table of per-(segment, plane) source pointers into the stacked fed buffers, ONE
 //                   launch; a null pointer is a flat slot and is written as zeros.  A lane owns 16 bytes, a wave a contiguous run.
 // Arithmetic: include/av1mi.h; restated in numpy by tests/scene_ref.py.  Reference tree: nothing (transcode.go:120).
-#include "av1mi_internal.hpp"
+#include "motion_common.hpp"
 
 namespace av1mi {
 
@@ -46,43 +46,11 @@ __global__ __launch_bounds__(256) void k_scene_down(const Pix *luma, uint8_t *q,
   const int item = tl.x * 256 + (int)threadIdx.x;
   if (item >= ng * qh) return;
   const int y = item / ng, x0 = (item - y * ng) * 4;           // output samples (x0 .. x0 + 3, y)
-  const Pix *in = luma + (size_t)f * h * w;
-  uint32_t sum[4] = { 8, 8, 8, 8 };
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int ix = 4 * x0;                                     // first of the row's 16 input samples; ix < w
-    const Pix *row = in + row_off(4 * y + r, w) + ix;          // 4 y + r < h: qh = h / 4
-    if (ix + 15 < w) {
-      uint32_t d[4 * (int)sizeof(Pix)];
-      __builtin_memcpy(d, row, sizeof(d));
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        if constexpr (sizeof(Pix) == 1) sum[k] = __builtin_amdgcn_sad_u8(d[k], 0u, sum[k]);
-        else {
-          // two samples per dword: their 8-bit views side by side, added as packed halves (8 x 255 per half at most here)
-          const uint32_t t = ((d[2 * k] >> sh) & 0x00ff00ffu) + ((d[2 * k + 1] >> sh) & 0x00ff00ffu);
-          sum[k] += (t & 0xffffu) + (t >> 16);
-        }
-      }
-    } else {      // the last group of a row whose width is not a multiple of 16: the last column replicated (the padding of the plane)
-#pragma unroll
-      for (int k = 0; k < 16; k++) sum[k >> 2] += (uint32_t)(row[min(k, w - 1 - ix)] >> sh) & 0xffu;
-    }
-  }
   uint8_t *out = q + (size_t)f * qs * qh + (size_t)y * qs + x0;
-  *reinterpret_cast<uint32_t *>(out) = (sum[0] >> 4) | ((sum[1] >> 4) << 8) | ((sum[2] >> 4) << 16) | ((sum[3] >> 4) << 24);
+  *reinterpret_cast<uint32_t *>(out) = quarter_dword<Pix>(luma + (size_t)f * h * w, w, w, sh, x0, y);
 }
 
 // ------------------------------------------------------------------------------------------ blocks
-// the dword of quarter-plane row `row` that covers columns x .. x + 3 (x a multiple of 4, possibly outside [0, qw)), columns clamped
-__device__ __forceinline__ uint32_t scene_dword(const uint8_t *row, int x, int qw) {
-  if (x >= 0 && x + 3 < qw) return *reinterpret_cast<const uint32_t *>(row + x);
-  uint32_t u = 0;
-#pragma unroll
-  for (int b = 0; b < 4; b++) u |= (uint32_t)row[min(max(x + b, 0), qw - 1)] << (8 * b);
-  return u;
-}
-
 // grid: runs x block rows x frames
 __global__ __launch_bounds__(256) void k_scene_blocks(const uint8_t *q, uint2 *blocks, int qw, int qh, int qs, int nbx, int nby, int runs, int frames) {
   __shared__ __attribute__((aligned(16))) uint8_t cur[8 * kCurStride];
@@ -99,11 +67,11 @@ __global__ __launch_bounds__(256) void k_scene_blocks(const uint8_t *q, uint2 *b
     if (i < ncur) {
       const int r = i / cd, c = i - r * cd;
       const int y = min(8 * by + r, qh - 1);
-      *reinterpret_cast<uint32_t *>(cur + r * kCurStride + 4 * c) = scene_dword(qf + (size_t)y * qs, x0 + 4 * c, qw);
+      *reinterpret_cast<uint32_t *>(cur + r * kCurStride + 4 * c) = row_dword(qf + (size_t)y * qs, x0 + 4 * c, qw);
     } else {
       const int j = i - ncur, r = j / wd, c = j - r * wd;
       const int y = min(max(8 * by - 2 + r, 0), qh - 1);
-      *reinterpret_cast<uint32_t *>(win + r * kWinStride + 4 * c) = scene_dword(qf - (size_t)qs * qh + (size_t)y * qs, x0 - 4 + 4 * c, qw);
+      *reinterpret_cast<uint32_t *>(win + r * kWinStride + 4 * c) = row_dword(qf - (size_t)qs * qh + (size_t)y * qs, x0 - 4 + 4 * c, qw);
     }
   }
   if (tid < kRun) s_inter[tid] = f > 0 ? 0xFFFFFFFFu : 0u;

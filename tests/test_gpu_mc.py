@@ -57,3 +57,25 @@ def test_mc_every_phase_pair(ctx, O, av1mi):
             d_l.free(); d_dst.free()
             assert (got == O.mc_block(ref, 8, 24, 24, 8, 8, 16 + (p & 15), -32 + (p >> 4), filt, filt)).all(), (filt, p)
     d_ref.free()
+
+
+@pytest.mark.parametrize("sid", [0, 1])
+def test_mc_10_bit_windows_past_every_edge(ctx, O, av1mi, sid):
+    """a 64x64 plane of 16-bit samples, 4x4 and 8x8 blocks (two lengths of staged window row): windows that stick out at the left, the
+    right, the top and the bottom, two that lie far outside at a corner, one inside, and one whose samples all lie inside while the
+    whole dwords the kernel stages reach one column past the right edge"""
+    B = SIZES[sid][0]
+    rng = np.random.default_rng(90 + sid)
+    ref = rng.integers(0, 1024, (64, 64)).astype(np.uint16)
+    cases = [(0, 0, -40, 5), (64 - B, 16, 37, -3), (16, 0, 3, -50), (16, 64 - B, -7, 45), (0, 64 - B, -200, 700), (64 - B, 0, 900, -900),
+             (32, 32, 5, 9), (48, 32, 16 * (12 - B), 0)]
+    lst = np.zeros(len(cases), av1mi.MC_BLK_DTYPE)
+    for i, (x, y, mvx, mvy) in enumerate(cases):
+        lst[i] = (x, y, mvx, mvy, i % 4, (i + 1) % 4, 0)
+    d_ref, d_lst, d_dst = ctx.to_device(ref), ctx.to_device(lst), ctx.to_device(np.zeros((64, 64), np.uint16))
+    ctx.mc_list(sid, d_ref, 64, 64, 64, d_dst, 64, 10, d_lst, len(cases))
+    got = d_dst.download((64, 64), np.uint16)
+    d_ref.free(); d_lst.free(); d_dst.free()
+    for i, (x, y, mvx, mvy) in enumerate(cases):
+        exp = O.mc_block(ref, 10, x, y, B, B, mvx, mvy, i % 4, (i + 1) % 4)
+        assert (got[y:y + B, x:x + B] == exp).all(), (B, cases[i])
