@@ -28,8 +28,15 @@ struct Av1EntLaunch {
   FrameView fv;                 // pointers of frame 0; frame f adds f * per-frame strides
   int nframes, sbr_n, sbc_n;
   BlockInfo *info;              // nframes * blocks
-  op_t *ops; uint32_t ops_cap;  // per tile: the list (literal ops, tuples)
-  uint32_t *grouped; uint32_t grouped_cap;   // per tile: the entries of the adaptive symbols, grouped by slot
+  // The lists (literal ops, tuples) and the entries of the adaptive symbols, grouped by slot, are two POOLS of the size every tile at its
+  // capacity would need, handed out DENSELY: a tile's wave reserves whole 128-byte lines for the words and entries it has counted
+  // (PoolAreas), so what a batch touches lies at the pools' fronts, in the order the tiles arrive there, and no two tiles share a line
+  // (the tiles of different groups are completed on different XCDs, whose L2s know nothing of one another).  Every tile's range is at
+  // most its capacity rounded up to lines, which ops_cap and grouped_cap cover: a pool cannot run out before a tile does.
+  op_t *ops; uint32_t ops_cap;
+  uint32_t *grouped; uint32_t grouped_cap;
+  uint32_t *list_off, *grouped_off;          // per tile: where its list / its entries start, in lines of kPoolLine words
+  uint32_t *cursors;                         // [0] the lists' next free line, [1] the entries': zero at the start of a batch
   uint16_t *slot_total, *slot_base;          // per tile x S_MAX: entries of the slot, position of its first entry
   uint16_t *rec;                             // per tile of 8x8 blocks x 64 blocks x kBlockRecords: the tokenizer's records
   uint32_t *nops;               // per tile
@@ -59,6 +66,21 @@ template <int kKey = -1> __device__ __forceinline__ FrameView frame_view(const A
   if (L.lr_on_frame) for (int p = 0; p < 3; p++) v.lr_on[p] = v.lr_on[p] && L.lr_on_frame[f * 3 + p];
   return v;
 }
+
+// the areas of tile t (av1_ops32.hpp: the tile's areas) out of the launch's pools
+constexpr uint32_t kPoolLine = 32;      // words: 128 bytes
+struct PoolAreas {
+  const Av1EntLaunch &L; size_t t;
+  __device__ __forceinline__ void reserve(int words, int entries, int *a, int *b) const {
+    const uint32_t la = atomicAdd(L.cursors, ((uint32_t)words + kPoolLine - 1) / kPoolLine), lb = atomicAdd(L.cursors + 1, ((uint32_t)entries + kPoolLine - 1) / kPoolLine);
+    L.list_off[t] = la; L.grouped_off[t] = lb;
+    *a = (int)la; *b = (int)lb;
+  }
+  __device__ __forceinline__ op_t *list(int a) const { return L.ops + (size_t)(uint32_t)a * kPoolLine; }
+  __device__ __forceinline__ uint32_t *grouped(int b) const { return L.grouped + (size_t)(uint32_t)b * kPoolLine; }
+  __device__ __forceinline__ void slot(int sl, uint16_t total, uint16_t base) const { L.slot_total[t * S_MAX + sl] = total; L.slot_base[t * S_MAX + sl] = base; }
+  __device__ __forceinline__ void refuse(int sl) const { L.slot_total[t * S_MAX + sl] = 0; }
+};
 
 // inter frames only: the tokenizer of a key frame reads nothing of a block's info
 __global__ __launch_bounds__(256) void k_av1_info(Av1EntLaunch L) {
@@ -102,8 +124,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void
   const int below = tiles - L.sb_rows32 * L.sbc_n;      // the records are this band's alone: the frame's tiles below the 32x32 band
   uint16_t *rec = L.rec + ((size_t)f * below + (tt - (tiles - below))) * kBlocksPerTile * kBlockRecords;
   TileWave w;
-  const int n = tok_tile8(w, S, v, sbr, sbc, rec, L.ops + (size_t)t * L.ops_cap, L.ops_cap, L.grouped + (size_t)t * L.grouped_cap,
-                          L.slot_total + (size_t)t * S_MAX, L.slot_base + (size_t)t * S_MAX);
+  PoolAreas out = { L, (size_t)t };
+  const int n = tok_tile8(w, S, v, sbr, sbc, rec, L.ops_cap, out);
   if (threadIdx.x == 0) {
     if (n < 0) atomicOr(L.status, 1u);
     L.nops[t] = n < 0 ? 0u : (uint32_t)n;
@@ -120,7 +142,8 @@ __global__ __launch_bounds__(64) void k_av1_tokens32(Av1EntLaunch L) {
   const size_t t = (size_t)f * tiles + tt;          // (the band's tiles are a frame's first)
   const FrameView v = frame_view<1>(L, f);
   TileWave w;
-  const int n = tok_tile32(w, S, v, sbr, sbc, L.ops + t * L.ops_cap, L.ops_cap, L.grouped + t * L.grouped_cap, L.slot_total + t * S_MAX, L.slot_base + t * S_MAX);
+  PoolAreas out = { L, t };
+  const int n = tok_tile32(w, S, v, sbr, sbc, L.ops_cap, out);
   if (threadIdx.x == 0) {
     if (n < 0) atomicOr(L.status, 1u);
     L.nops[t] = n < 0 ? 0u : (uint32_t)n;
@@ -145,9 +168,9 @@ __global__ __launch_bounds__(64) void k_av1_chains(Av1EntLaunch L, int ntiles_al
   if (mine && L.band) { const int tiles = L.sbr_n * L.sbc_n, sbr = (t % tiles) / L.sbc_n; mine = (sbr < L.sb_rows32) == (L.band == 1); }
   if (mine) { cnt = L.slot_total[(size_t)t * S_MAX + sl]; base = L.slot_base[(size_t)t * S_MAX + sl]; }
   if (!__any(cnt > 0)) return;
-  const size_t tt = t < ntiles_all ? (size_t)t : 0;
-  op_t *list = L.ops + tt * L.ops_cap;
-  const uint32_t *grouped = L.grouped + tt * L.grouped_cap + base;
+  // (a tile without entries in the slot may be one that was refused and has no areas: its offsets are read by nobody)
+  op_t *list = L.ops + (cnt > 0 ? (size_t)L.list_off[t] * kPoolLine : 0);
+  const uint32_t *grouped = L.grouped + (cnt > 0 ? (size_t)L.grouped_off[t] * kPoolLine : 0) + base;
   if (n <= 4) {
     const uint32_t *iw = reinterpret_cast<const uint32_t *>(L.cdf_image) + (off >> 1);
     uint64_t cdf = (uint64_t)iw[0] | ((uint64_t)iw[1] << 32);
@@ -207,7 +230,7 @@ __global__ __launch_bounds__(64) void k_av1_code(Av1EntLaunch L, int ntiles_all)
   Coder c;
   c.init(L.slots + (size_t)(live ? t : 0) * L.slot_cap, (int)L.slot_cap, s_lane + lane * kLaneWords + kRingOps * 2);
   const int n = live ? (int)L.nops[t] : 0;
-  const uint4 *ops4 = reinterpret_cast<const uint4 *>(L.ops + (size_t)(live ? t : 0) * L.ops_cap);
+  const uint4 *ops4 = reinterpret_cast<const uint4 *>(L.ops + (n ? (size_t)L.list_off[t] * kPoolLine : 0));
   // words [w - 64, w) are in the ring; `pend`: words [w, w + 32) are on their way into r0..r7
   uint4 r0, r1, r2, r3, r4, r5, r6, r7;
   r0 = r1 = r2 = r3 = r4 = r5 = r6 = r7 = make_uint4(0, 0, 0, 0);
@@ -339,9 +362,9 @@ hipError_t launch_av1_back(av1mi_ctx *ctx, const Av1EntLaunch &L, hipStream_t s)
 
 // ------------------------------------------------------------------------------------------------ C ABI
 struct av1mi_av1ent_state {      // per-context scratch of the coder, grown on demand (owned through av1mi_av1_entropy_release)
-  void *info = nullptr, *ops[2] = { nullptr, nullptr }, *nops[2] = { nullptr, nullptr }, *grouped = nullptr, *slot_tb = nullptr, *rec = nullptr, *slots = nullptr, *tile_off = nullptr, *status = nullptr;
-  size_t info_b = 0, ops_b[2] = { 0, 0 }, nops_b[2] = { 0, 0 }, grouped_b = 0, slot_tb_b = 0, rec_b = 0, slots_b = 0, off_b = 0;
-  // the lists (ops, nops) exist twice: job k uses set k & 1, so the front half of job k + 1 may run beside the back half of job k
+  void *info = nullptr, *ops[2] = { nullptr, nullptr }, *nops[2] = { nullptr, nullptr }, *grouped = nullptr, *grouped_off = nullptr, *slot_tb = nullptr, *rec = nullptr, *slots = nullptr, *tile_off = nullptr, *status = nullptr;
+  size_t info_b = 0, ops_b[2] = { 0, 0 }, nops_b[2] = { 0, 0 }, grouped_b = 0, grouped_off_b = 0, slot_tb_b = 0, rec_b = 0, slots_b = 0, off_b = 0;
+  // the lists (ops; nops with the lists' offsets behind them) exist twice: job k uses set k & 1, so the front half of job k + 1 may run beside the back half of job k
   hipEvent_t lists_ready[2] = { nullptr, nullptr }, lists_free[2] = { nullptr, nullptr };
   bool free_recorded[2] = { false, false };
   unsigned long jobs = 0;
@@ -357,6 +380,7 @@ struct av1mi_av1ent_state {      // per-context scratch of the coder, grown on d
 };
 
 namespace {
+constexpr size_t kCursorBytes = 128;
 int grow(av1mi_ctx *ctx, void **p, size_t *have, size_t need) {
   if (*have >= need) return AV1MI_OK;
   if (*p) (void)hipFree(*p);
@@ -431,14 +455,16 @@ int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hip
   st->last_tiles = nt;
   int rc;
   if ((rc = grow(ctx, &st->info, &st->info_b, nb * sizeof(av1ops::BlockInfo))) ||
-      (rc = grow(ctx, &st->ops[par], &st->ops_b[par], nt * L.ops_cap * sizeof(av1ops::op_t))) || (rc = grow(ctx, &st->nops[par], &st->nops_b[par], nt * 4)) ||
-      (rc = grow(ctx, &st->grouped, &st->grouped_b, nt * L.grouped_cap * sizeof(uint32_t))) ||
-      (rc = grow(ctx, &st->slot_tb, &st->slot_tb_b, nt * av1ops::S_MAX * 4)) ||
+      (rc = grow(ctx, &st->ops[par], &st->ops_b[par], nt * L.ops_cap * sizeof(av1ops::op_t))) || (rc = grow(ctx, &st->nops[par], &st->nops_b[par], nt * 8)) ||
+      (rc = grow(ctx, &st->grouped, &st->grouped_b, nt * L.grouped_cap * sizeof(uint32_t))) || (rc = grow(ctx, &st->grouped_off, &st->grouped_off_b, nt * 4)) ||
+      (rc = grow(ctx, &st->slot_tb, &st->slot_tb_b, kCursorBytes + nt * av1ops::S_MAX * 4)) ||
       (rc = grow(ctx, &st->rec, &st->rec_b, (size_t)(L.sbr_n - L.sb_rows32) * L.sbc_n * j->nframes * av1ops::kBlocksPerTile * av1ops::kBlockRecords * sizeof(uint16_t))) ||
       (rc = grow(ctx, &st->slots, &st->slots_b, nt * L.slot_cap)) || (rc = grow(ctx, &st->tile_off, &st->off_b, (nt + 1) * 8)))
     return rc;
   L.info = (av1ops::BlockInfo *)st->info; L.ops = (av1ops::op_t *)st->ops[par]; L.nops = (uint32_t *)st->nops[par]; L.grouped = (uint32_t *)st->grouped;
-  L.slot_total = (uint16_t *)st->slot_tb; L.slot_base = L.slot_total + nt * av1ops::S_MAX; L.rec = (uint16_t *)st->rec; L.slots = (uint8_t *)st->slots;
+  L.list_off = L.nops + nt; L.grouped_off = (uint32_t *)st->grouped_off;
+  L.cursors = (uint32_t *)st->slot_tb;        // the pools' cursors: a line of their own in front of the slot tables
+  L.slot_total = (uint16_t *)((uint8_t *)st->slot_tb + kCursorBytes); L.slot_base = L.slot_total + nt * av1ops::S_MAX; L.rec = (uint16_t *)st->rec; L.slots = (uint8_t *)st->slots;
   L.tile_off = (uint64_t *)st->tile_off;
   L.tile_size = j->d_tile_size; L.out = j->d_out; L.out_cap = j->out_cap;
   L.status = (uint32_t *)(j->d_total + 1);
@@ -448,6 +474,7 @@ int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hip
   for (hipEvent_t *ev : { &st->lists_ready[par], &st->lists_free[par] }) if (!*ev) E_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
   if (st->free_recorded[par]) E_HIP(hipStreamWaitEvent(front, st->lists_free[par], 0));      // the coder of two jobs ago still reads this set of lists
   E_HIP(hipMemsetAsync(j->d_total, 0, 16, front));
+  E_HIP(hipMemsetAsync(L.cursors, 0, kCursorBytes, front));
   E_HIP(av1mi::launch_av1_front(ctx, L, front));
   E_HIP(hipEventRecord(st->lists_ready[par], front));
   st->pending[par] = L; st->pending_total[par] = j->d_total; st->pending_valid[par] = true;
@@ -505,7 +532,7 @@ int av1mi_av1_entropy_last_list_words(av1mi_ctx *ctx, uint64_t *words) {
 namespace av1mi {
 void av1ent_free(av1mi_av1ent_state *st) {
   if (!st) return;
-  for (void *p : { st->info, st->ops[0], st->ops[1], st->nops[0], st->nops[1], st->grouped, st->slot_tb, st->rec, st->slots, st->tile_off }) if (p) (void)hipFree(p);
+  for (void *p : { st->info, st->ops[0], st->ops[1], st->nops[0], st->nops[1], st->grouped, st->grouped_off, st->slot_tb, st->rec, st->slots, st->tile_off }) if (p) (void)hipFree(p);
   for (hipEvent_t ev : { st->lists_ready[0], st->lists_ready[1], st->lists_free[0], st->lists_free[1] }) if (ev) (void)hipEventDestroy(ev);
   for (auto &k : st->d_image) for (uint16_t *p : k) if (p) (void)hipFree(p);
   for (uint16_t *p : st->d_image32) if (p) (void)hipFree(p);

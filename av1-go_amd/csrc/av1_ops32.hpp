@@ -333,13 +333,30 @@ AV1_HD int tok_tb32_emit(W &w, Tile32Mem &S, const FrameView &f, int sbr, int sb
   return words + words2;
 }
 
+// THE TILE'S AREAS.  A tile tokenizer (tok_tile32 here, tok_tile8 of av1_ops8.hpp) knows the tile's list words and grouped entries after
+// its counting pass, before it writes one of them, and asks an object `out` for the places:
+//   out.reserve(words, entries, &a, &b)   one lane, once per tile that fits: two handles
+//   out.list(a) / out.grouped(b)          every lane: the areas behind the handles (>= words, >= entries; 16-byte aligned)
+//   out.slot(sl, total, base)             a slot's entries: `total` from grouped[base] on; called for every slot below S_MAX
+//   out.refuse(sl)                        the tile does not fit: slot sl has no entries
+// The GPU kernels reserve whole cache lines of a pool all tiles share (av1_entropy_kernels.hip); the CPU twin hands out the caller's
+// pointers:
+struct CallerAreas {
+  op_t *list_; uint32_t *grouped_; uint16_t *slot_total, *slot_base;
+  AV1_HD void reserve(int, int, int *a, int *b) const { *a = 0; *b = 0; }
+  AV1_HD op_t *list(int) const { return list_; }
+  AV1_HD uint32_t *grouped(int) const { return grouped_; }
+  AV1_HD void slot(int sl, uint16_t total, uint16_t base) const { slot_total[sl] = total; slot_base[sl] = base; }
+  AV1_HD void refuse(int sl) const { slot_total[sl] = 0; }
+};
+
 // THE TILE = superblock (sbr, sbc) of a key frame's 32x32 band: its literals into list[0 .. words), its adaptive symbols into `grouped`
-// (slot sl: slot_total[sl] entries from slot_base[sl] on, bases on multiples of kListAlign), totals and bases of all S_MAX slots.
-// Returns the list words, the same in every lane; -1 when the tile has more than ops_cap words or more than 65 535 entries: then all
-// totals are 0 and neither list nor grouped has been written.  (No other capacity: a lane's counts of a round fit their bytes.)
-template <class W>
-AV1_HD int tok_tile32(W &w, Tile32Mem &S, const FrameView &f, int sbr, int sbc, op_t *list, uint32_t ops_cap, uint32_t *grouped, uint16_t *slot_total,
-                      uint16_t *slot_base) {
+// (slot sl: total entries from base on, bases on multiples of kListAlign), totals and bases of all S_MAX slots to `out`, which also places
+// the list and the entries.  Returns the list words, the same in every lane; -1 when the tile has more than ops_cap words or more than
+// 65 535 entries: then all totals and bases are 0, nothing has been reserved and neither list nor grouped has been written.  (No other
+// capacity: a lane's counts of a round fit their bytes.)
+template <class W, class O>
+AV1_HD int tok_tile32(W &w, Tile32Mem &S, const FrameView &f, int sbr, int sbc, uint32_t ops_cap, O &out) {
   typedef typename W::template Var<int> LaneInt;
   const bool half = sbc * 8 + 4 >= f.w8;         // the frame ends after the superblock's left 32 columns (width % 64 == 32): blocks 1 and 3 are not coded
   w.each([&](int lane) {
@@ -394,13 +411,17 @@ AV1_HD int tok_tile32(W &w, Tile32Mem &S, const FrameView &f, int sbr, int sbc, 
       const int sl = lane * kOwn + q;
       if (sl >= K_END) break;
       const uint32_t tot = S.run[sl];
-      slot_total[sl] = (uint16_t)(fits ? tot : 0u); slot_base[sl] = (uint16_t)(fits ? run : 0u);
+      out.slot(sl, (uint16_t)(fits ? tot : 0u), (uint16_t)(fits ? run : 0u));
       S.run[sl] = run;
       run += (tot + kListAlign - 1) & ~(uint32_t)(kListAlign - 1);
     }
-    for (int sl = K_END + lane; sl < S_MAX; sl += kLanes32) { slot_total[sl] = 0; slot_base[sl] = 0; }
+    for (int sl = K_END + lane; sl < S_MAX; sl += kLanes32) out.slot(sl, 0, 0);
   });
   if (!fits) return -1;
+  LaneInt at_list, at_grouped;
+  w.each([&](int lane) { if (lane == 0) out.reserve(words, entries, &at_list[lane], &at_grouped[lane]); });
+  op_t *const list = out.list(w.first(at_list));
+  uint32_t *const grouped = out.grouped(w.first(at_grouped));
   // the emitting sweep, transform block by transform block in decoding order
   int at = 0;
   for (int b = 0; b < kBlocks32; b++) {

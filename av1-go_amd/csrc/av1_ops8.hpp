@@ -51,13 +51,13 @@ AV1_HD void replay_block8(const uint16_t *rec, int nrec, uint16_t *pos, const ui
 }
 
 // THE TILE = superblock (sbr, sbc) of 8x8 blocks: its literals into list[0 .. words), its adaptive symbols into `grouped` (slot sl:
-// slot_total[sl] entries from slot_base[sl] on, bases on multiples of kListAlign, slots in order), totals and bases of all S_MAX slots.
+// total entries from base on, bases on multiples of kListAlign, slots in order), totals and bases of all S_MAX slots to `out`.  The list
+// and the entries lie where `out` places them once the tile's word and entry counts are known (av1_ops32.hpp: the tile's areas).
 // rec: kBlocksPerTile * kBlockRecords records of scratch.  Returns the list words, the same in every lane; -1 when the tile has more
 // than ops_cap words or more than 65 535 entries, or a block more than kBlockRecords records or more than 255 symbols of one slot:
-// then all totals are 0 and nothing else has been written.
-template <class W>
-AV1_HD int tok_tile8(W &w, Tile8Mem &S, const FrameView &f, int sbr, int sbc, uint16_t *rec, op_t *list, uint32_t ops_cap, uint32_t *grouped,
-                     uint16_t *slot_total, uint16_t *slot_base) {
+// then every slot has been refused, nothing has been reserved and nothing else has been written.
+template <class W, class O>
+AV1_HD int tok_tile8(W &w, Tile8Mem &S, const FrameView &f, int sbr, int sbc, uint16_t *rec, uint32_t ops_cap, O &out) {
   typedef typename W::template Var<int> LaneInt;
   const int nslots = f.key ? S_KEY_END : S_INTER_END;
   w.each([&](int lane) {
@@ -113,9 +113,13 @@ AV1_HD int tok_tile8(W &w, Tile8Mem &S, const FrameView &f, int sbr, int sbc, ui
   const int entries = fits ? w.scan(ent) : 0, rows = fits ? w.scan(used) : 0;
   fits = fits && entries <= 65535;
   if (!fits) {
-    w.each([&](int lane) { for (int sl = lane; sl < S_MAX; sl += kLanes8) slot_total[sl] = 0; });
+    w.each([&](int lane) { for (int sl = lane; sl < S_MAX; sl += kLanes8) out.refuse(sl); });
     return -1;
   }
+  LaneInt at_list, at_grouped;
+  w.each([&](int lane) { if (lane == 0) out.reserve(words, entries, &at_list[lane], &at_grouped[lane]); });
+  op_t *const list = out.list(w.first(at_list));
+  uint32_t *const grouped = out.grouped(w.first(at_grouped));
   w.each([&](int lane) {
     int run = ent[lane], r = used[lane];
     for (int q = 0; q < 4; q++) {
@@ -136,7 +140,7 @@ AV1_HD int tok_tile8(W &w, Tile8Mem &S, const FrameView &f, int sbr, int sbc, ui
       for (int q = 0; q < kOwn8; q++) {
         const int sl = lane + kLanes8 * q;
         if (sl >= S_MAX) continue;
-        if (pass == 0) { const bool on = sl < nslots; slot_total[sl] = on ? S.total[sl] : (uint16_t)0; slot_base[sl] = on ? S.base[sl] : (uint16_t)0; }
+        if (pass == 0) { const bool on = sl < nslots; out.slot(sl, on ? S.total[sl] : (uint16_t)0, on ? S.base[sl] : (uint16_t)0); }
         if (sl >= nslots || !S.total[sl]) continue;
         const unsigned rw = (unsigned)S.row[sl] - (unsigned)row_lo;
         if (rw >= (unsigned)kReplaySlots) continue;

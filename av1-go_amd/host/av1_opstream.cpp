@@ -129,7 +129,8 @@ bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> 
         // a tile of the 32x32 band: the lanes of its wave over scan ranges (tok_tile32), then the same chains and the same range coder
         WaveLoop wave;
         uint16_t base[S_MAX], total[S_MAX];
-        const int words = tok_tile32(wave, mem32[0], v, sbr, sbc, list32.data(), ops_cap32, grouped32.data(), total, base);
+        CallerAreas out = { list32.data(), grouped32.data(), total, base };
+        const int words = tok_tile32(wave, mem32[0], v, sbr, sbc, ops_cap32, out);
         if (words < 0) { if (err) *err = "tile too large for 16-bit entry positions"; return false; }
         std::vector<op_t> list(list32.begin(), list32.begin() + words);
         if (!code_list(list, grouped32, K_END, total, base, tab32, image32.data(), &(*tiles)[(size_t)sbr * sbc_n + sbc], err)) return false;
@@ -138,7 +139,8 @@ bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> 
       // stage 1 (av1_ops8.hpp tok_tile8, the GPU: a lane per block): summaries, records + counts, place, replay
       WaveLoop wave;
       uint16_t base[S_MAX], total[S_MAX];
-      const int words = tok_tile8(wave, mem8[0], v, sbr, sbc, rec.data(), list8.data(), ops_cap8, grouped8.data(), total, base);
+      CallerAreas out = { list8.data(), grouped8.data(), total, base };
+      const int words = tok_tile8(wave, mem8[0], v, sbr, sbc, rec.data(), ops_cap8, out);
       if (stats) {       // the blocks once more, one by one, for what the tile's call does not tell
         std::vector<uint8_t> cnt((size_t)S_MAX * kBlocksPerTile, 0);
         const TokScratch ts = { mem8[0].p1.mag, &mem8[0].scan };
@@ -182,7 +184,8 @@ int opstream_tile8(const av1mi_obu_frame &f, int sbr, int sbc, uint32_t ops_cap,
   std::vector<Tile8Mem> mem(1);
   std::vector<uint16_t> rec((size_t)kBlocksPerTile * kBlockRecords);
   WaveLoop wave;
-  return tok_tile8(wave, mem[0], v, sbr, sbc, rec.data(), list, ops_cap, grouped, slot_total, slot_base);
+  CallerAreas out = { list, grouped, slot_total, slot_base };
+  return tok_tile8(wave, mem[0], v, sbr, sbc, rec.data(), ops_cap, out);
 }
 
 // One tile of a key frame's 32x32 band through tok_tile32 into the caller's areas, as the GPU kernel calls it (tests: the capacity of
@@ -197,7 +200,8 @@ int opstream_tile32(const av1mi_obu_frame &f, int sbr, int sbc, uint32_t ops_cap
   if (!lr_units_of(f, &v, err)) return -2;
   std::vector<Tile32Mem> mem(1);
   WaveLoop wave;
-  return tok_tile32(wave, mem[0], v, sbr, sbc, list, ops_cap, grouped, slot_total, slot_base);
+  CallerAreas out = { list, grouped, slot_total, slot_base };
+  return tok_tile32(wave, mem[0], v, sbr, sbc, ops_cap, out);
 }
 
 }  // namespace av1
