@@ -23,506 +23,442 @@
 //
 // `segments` closed GOPs of the file are coded in lockstep (the session's batch dimension); while the host codes the
 // symbols of frame t the GPU already works on frames t + 1 and t + 2 (three batches in flight).
+//
+// RunBackend is a list of steps, each a method of Run (the job's state; its destructor releases what the steps opened) that returns the
+// exit code, 0 = go on: settle_window, session_config (SessionConfig: the policy, a pure function), open_session, run_groups, finish.
 #include "filmgrain.hpp"
 #include "backend.hpp"
-#include <sys/stat.h>
-#include <unistd.h>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <thread>
 #include <vector>
-#include "../../include/av1mi.h"
-#include "../csrc/quality.hpp"
 #include "av1_bitstream.hpp"
 #include "cropplan.hpp"
-#include "mux.hpp"
 #include "ratecontrol.hpp"
 #include "sceneplan.hpp"
 #include "y4m.hpp"
 
 namespace av1mi_host {
 
-void DescribeSessionFrame(const av1mi_gop_frame &fr, int seg, int width, int height, int bit_depth, SessionFrameDesc *d, int visible_width, int visible_height) {
-  const av1mi_frame_params &p = fr.params;
-  av1mi_obu_frame &f = d->f;
-  memset(&f, 0, sizeof(f));
-  f.width = width; f.height = height; f.bit_depth = bit_depth; f.frame_type = p.frame_type; f.base_q_idx = p.base_q_idx;
-  f.visible_width = visible_width; f.visible_height = visible_height;
-  for (int i = 0; i < 4; i++) f.lf_level[i] = p.lf_level[i];
-  f.lf_sharpness = p.lf_sharpness; f.cdef_damping = p.cdef_damping; f.cdef_bits = 0; f.cdef_y[0] = p.cdef_y; f.cdef_uv[0] = p.cdef_uv;
-  auto units = [&](int n) { const int u = (n + p.lr_unit_size / 2) / p.lr_unit_size; return u > 1 ? u : 1; };
-  const int vw = visible_width ? visible_width : width, vh = visible_height ? visible_height : height;      // the units tile the TRUE frame
-  const size_t uy = (size_t)units(vh) * units(vw), uc = (size_t)units((vh + 1) / 2) * units((vw + 1) / 2);
-  d->lr_y.resize(uy * 8); d->lr_uv.resize(uc * 8);
-  for (size_t i = 0; i < uy; i++) memcpy(&d->lr_y[i * 8], p.lr_unit_y, 8);
-  for (size_t i = 0; i < uc; i++) memcpy(&d->lr_uv[i * 8], p.lr_unit_uv, 8);
-  // restoration per plane: the policy's type where the encoder kept it ON for this segment's frame (fr.lr_on), NONE elsewhere
-  const uint8_t *on = fr.lr_on ? fr.lr_on + (size_t)seg * 3 : nullptr;
-  f.lr_type[0] = (!on || on[0]) ? p.lr_unit_y[0] : 0;
-  f.lr_type[1] = (!on || on[1]) ? p.lr_unit_uv[0] : 0;
-  f.lr_type[2] = (!on || on[2]) ? p.lr_unit_uv[0] : 0;
-  f.lr_unit_shift = p.lr_unit_size == 64 ? 0 : p.lr_unit_size == 128 ? 1 : 2; f.lr_uv_shift = 0;
-  f.lr_units[0] = d->lr_y.data(); f.lr_units[1] = f.lr_units[2] = d->lr_uv.data();
-  f.tile_cols_log2 = f.tile_rows_log2 = -1;      // one superblock per tile: the independence the GPU pipeline's prediction assumes
-  const size_t nb = fr.blocks_per_frame, o = (size_t)seg * nb;
-  if (fr.y_mode) { f.y_mode = fr.y_mode + o; f.uv_mode = fr.uv_mode + o; }       // the symbols are absent when the tiles were coded on the GPU
-  if (fr.mv) { f.mv = fr.mv + o * 2; f.skip = fr.skip + o; }
-  if (fr.lev_y) { f.lev_y = fr.lev_y + o * 64; f.lev_u = fr.lev_u + o * 16; f.lev_v = fr.lev_v + o * 16; }     // absent when the tiles were coded on the GPU
+int ExplicitWindow(const BackendJob &job, int w, int h, CropRect *win, std::string *err) {
+  *win = job.crop;
+  if (win->w <= w && win->h <= h && win->x <= w - win->w && win->y <= h - win->h) return 0;
+  *err = "Invalid argument: -av1mi_crop " + std::to_string(win->w) + ":" + std::to_string(win->h) + ":" + std::to_string(win->x) + ":" + std::to_string(win->y) +
+         " lies outside the " + std::to_string(w) + "x" + std::to_string(h) + " picture";
+  return 1;
 }
 
-// A key frame of a key_block_size 32 session (av1mi_gop_frame.key_block_size == 32): 32x32 blocks over the complete superblock rows,
-// 8x8 blocks in a last partial row — written by the general block writer (av1_blockstream.cpp) from the session's symbols.
-static bool Key32TemporalUnit(const av1mi_gop_frame &fr, int seg, const SessionFrameDesc &desc, int width, int height, bool with_sequence_header, int threads,
-                              std::vector<uint8_t> *out, std::string *err) {
-  if (!fr.y_mode || !fr.lev_y) { if (err) *err = "a key frame in 32x32 blocks needs its symbols (gpu_entropy 0)"; return false; }
-  const int hA = (height / 64) * 64, mi_rows = height / 4, mi_cols = width / 4;
-  const size_t ny = (size_t)width * height, nc = ny / 4;
-  const uint8_t *my = fr.y_mode + (size_t)seg * fr.key_modes_stride, *muv = fr.uv_mode + (size_t)seg * fr.key_modes_stride;
-  std::vector<int16_t> lev(ny + 2 * nc);
-  memcpy(lev.data(), fr.lev_y + (size_t)seg * ny, ny * 2);
-  memcpy(lev.data() + ny, fr.lev_u + (size_t)seg * nc, nc * 2);
-  memcpy(lev.data() + ny + nc, fr.lev_v + (size_t)seg * nc, nc * 2);
-  std::vector<uint8_t> parts;
-  std::vector<av1mi_obu_block> blocks;
-  auto block = [&](int r, int c, int bsize, int mode_y, int mode_uv, size_t oy, size_t oc) {
-    av1mi_obu_block b;
-    memset(&b, 0, sizeof(b));
-    b.mi_row = (uint16_t)r; b.mi_col = (uint16_t)c; b.bsize = (uint8_t)bsize; b.y_mode = (uint8_t)mode_y; b.uv_mode = (uint8_t)mode_uv;
-    b.tx_type_off = 0;                                   // every luma transform is DCT_DCT: one shared entry
-    b.lev_off[0] = (uint32_t)oy; b.lev_off[1] = (uint32_t)(ny + oc); b.lev_off[2] = (uint32_t)(ny + nc + oc);
-    blocks.push_back(b);
-  };
-  const int w32 = width / 32, w8 = width / 8;
-  std::vector<size_t> starts;          // per tile (= superblock): its first block, its first partition symbol; the writer's threads start there
-  for (int sr = 0; sr * 16 < mi_rows; sr++)
-    for (int sc = 0; sc * 16 < mi_cols; sc++) {
-      starts.push_back(blocks.size()); starts.push_back(parts.size());
-      if (sr * 64 < hA) {                                // PARTITION_SPLIT at 64x64, four 32x32 blocks (two where the frame ends mid-superblock)
-        parts.push_back(3);
-        for (int k = 0; k < 4; k++) {
-          const int r32 = sr * 2 + (k >> 1), c32 = sc * 2 + (k & 1);
-          if (c32 >= w32) continue;
-          const size_t i = (size_t)r32 * w32 + c32;
-          parts.push_back(0);
-          block(r32 * 8, c32 * 8, 9 /* BLOCK_32X32 */, my[i], muv[i], i * 1024, i * 256);
-        }
-      } else {                                           // the last, partial superblock row: split down to 8x8 wherever the frame reaches
-        const size_t oyB = (size_t)hA * width, ocB = oyB / 4;
-        const uint8_t *myB = my + fr.key_modes_band, *muvB = muv + fr.key_modes_band;
-        for (int k = 0; k < 64; k++) {                   // z-order over the superblock's 8x8 blocks; a level's symbol precedes its first block
-          int bx = 0, by = 0;
-          for (int i = 0; i < 3; i++) { bx |= ((k >> (2 * i)) & 1) << i; by |= ((k >> (2 * i + 1)) & 1) << i; }
-          const int r = sr * 16 + by * 2, c = sc * 16 + bx * 2;
-          for (int n8 = 8; n8 >= 2; n8 >>= 1)            // 64, 32, 16: PARTITION_SPLIT at every level that starts here, inside the frame
-            if (!(bx & (n8 - 1)) && !(by & (n8 - 1)) && r < mi_rows && c < mi_cols) parts.push_back(3);
-          if (r >= mi_rows || c >= mi_cols) continue;
-          parts.push_back(0);
-          const size_t i = (size_t)(r / 2 - hA / 8) * w8 + c / 2;
-          block(r, c, 3 /* BLOCK_8X8 */, myB[i], muvB[i], oyB + i * 64, ocB + i * 16);
-        }
-      }
-    }
-  av1mi_obu_blocks d;
-  memset(&d, 0, sizeof(d));
-  d.hdr = desc.f;
-  const uint8_t dct = 0;
-  d.partition = parts.data(); d.n_partition = parts.size(); d.blocks = blocks.data(); d.n_blocks = blocks.size(); d.tx_type = &dct; d.levels = lev.data();
-  starts.push_back(blocks.size()); starts.push_back(parts.size());
-  std::string werr;
-  if (!av1::blocks_temporal_unit(d, with_sequence_header, out, &werr, threads, reinterpret_cast<const size_t (*)[2]>(starts.data()))) {
-    if (err) *err = "bitstream writer: " + werr;
-    return false;
+int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect &window, SessionPlan *plan, std::string *err) {
+  auto refuse = [&](const std::string &why) { *err = "Invalid argument: " + why; return 1; };
+  *plan = SessionPlan();      // (a refused job leaves a plan of zeros, never an indeterminate one)
+  // the target: what the argv's filter chain yields on this source (transcode.go:92-115), or -av1mi_scale; no chain = the source
+  // the window first: -av1mi_crop stands in front of the chain, whose filters then see the window's size
+  CropRect &win = plan->win = window;
+  const int pw = win.w ? win.w : src.w, ph = win.w ? win.h : src.h;      // the picture the chain works on
+  int &tw = plan->tw = pw, &th = plan->th = ph;
+  plan->square = src.sar_n == src.sar_d;
+  CropRect chain_crop;
+  if (job.have_vf && !ChainTarget(pw, ph, src.sar_n, src.sar_d, job.vf, &tw, &th, &plan->square, err, nullptr, nullptr, &chain_crop)) return 1;
+  if (chain_crop.w) win = chain_crop;      // (ParseBackendJob: never together with -av1mi_crop)
+  if (job.scale_w) { tw = job.scale_w; th = job.scale_h; plan->square = true; }
+  const bool scaling = win.w != 0 || tw != src.w || th != src.h || job.scale_w != 0;      // a window is fed like a source to be scaled: whole frames
+  const int G = job.gop, w = (tw + 7) & ~7, h = (th + 7) & ~7;       // the coded size; tw x th is what a decoder outputs
+  int S = std::max(job.segments, 1);
+  if (src.known_frames >= 0) S = (int)std::max<long>(1, std::min<long>(S, (src.known_frames + G - 1) / G));      // no more segments than the file has GOPs
+  av1mi_gop_config &cfg = plan->cfg;
+  if (w != tw || h != th) { cfg.visible_width = tw; cfg.visible_height = th; }
+  if (scaling) { cfg.source_width = src.w; cfg.source_height = src.h; }
+  if (win.w) { cfg.crop_x = win.x; cfg.crop_y = win.y; cfg.crop_width = win.w; cfg.crop_height = win.h; }
+  cfg.width = w; cfg.height = h; cfg.bit_depth = src.bd; cfg.base_q_idx = job.quality < 1 ? 1 : job.quality; cfg.gop_length = G; cfg.segments = S;
+  cfg.search_range = 8;
+  cfg.coarse_range = job.me_range;      // -av1mi_me_range: the coarse search in front of it
+  cfg.gpu_entropy = job.gpu_entropy ? 1 : 0;
+  // -av1mi_stats / -av1mi_min_psnr: the session measures every batch on the GPU; the records arrive with the collected batch
+  plan->measure = !job.stats_path.empty() || job.min_psnr > 0;
+  cfg.quality_stats = plan->measure ? 1 : 0;
+  // key frames in 32x32 blocks where the frame allows it (the coded width a multiple of 32)
+  cfg.key_block_size = (job.key_block_size == 32 && (w & 31) == 0) ? 32 : 8;
+  // A source that is not 4:2:0 at the coded depth (only a job that converts opens one): fed in its own layout, converted on the GPU
+  const bool convert = src.chroma != AV1MI_CHROMA_420 || src.src_bd != src.bd;
+  if (convert) { cfg.source_chroma = src.chroma; cfg.source_bit_depth = src.src_bd; }
+  // -av1mi_pack10 1: a 10-bit source crosses PCIe at 10 bits per sample; the session's pinned buffers are then three packed planes
+  plan->packed = job.pack10 && src.bd == 10 && !convert;      // (planar 4:2:0 10-bit only)
+  if (plan->packed) cfg.input_format = AV1MI_INPUT_PACKED10;
+  // -av1mi_deinterlace: auto follows the header's I parameter, tff / bff force a parity
+  int dei = job.deinterlace == 2 ? 1 : job.deinterlace == 3 ? 2 : 0;
+  if (job.deinterlace == 1) {
+    if (src.interlace == 3) return refuse("-av1mi_deinterlace auto: the source is mixed-mode interlaced (Im); field-rate output and inverse telecine are not built");
+    dei = src.interlace;
   }
-  return true;
-}
-
-bool SessionTemporalUnit(const av1mi_gop_frame &fr, int seg, int width, int height, int bit_depth, int visible_width, int visible_height,
-                         bool with_sequence_header, int threads, std::vector<uint8_t> *out, std::string *err, bool film_grain_present,
-                         const av1mi_film_grain *film_grain, const av1mi_colour *colour) {
-  SessionFrameDesc desc;
-  DescribeSessionFrame(fr, seg, width, height, bit_depth, &desc, visible_width, visible_height);
-  desc.f.film_grain_present = film_grain_present; desc.f.film_grain = film_grain; desc.f.colour = colour;
-  std::string werr;
-  if (fr.tile_size) {      // tiles coded on the GPU: frame header + tile group around them
-    const uint32_t *sz = fr.tile_size + (size_t)seg * fr.tiles_per_frame;
-    size_t off = 0;
-    for (size_t i = 0; i < (size_t)seg * fr.tiles_per_frame; i++) off += fr.tile_size[i];
-    std::vector<uint8_t> frame;
-    if (!av1::frame_obu_from_tiles(desc.f, fr.tile_payload + off, sz, fr.tiles_per_frame, &frame, &werr)) { if (err) *err = "bitstream assembly: " + werr; return false; }
-    *out = av1::temporal_delimiter_obu();
-    if (with_sequence_header) av1::append_sequence_obus(av1::sequence_params(desc.f), out);
-    out->insert(out->end(), frame.begin(), frame.end());
-    return true;
+  cfg.deinterlace = dei;
+  // -av1mi_scenecut, or a job that deinterlaces: the frame store holds one group (the deinterlacer's run)
+  // -av1mi_denoise: the same store, the denoiser in the gather; -av1mi_film_grain (1 unless told otherwise): parameters in every frame header
+  cfg.denoise = job.denoise;
+  cfg.denoise_range = job.denoise_range;
+  // the stream's colour record: the job's options, the header's range; a tone-mapped job says what the kernel makes
+  plan->colour = JobColour(job, src.colour_range);
+  if (const char *why = av1::colour_error(plan->colour)) return refuse(why);
+  if (job.tonemap) {
+    if (src.bd != 10) return refuse("tone mapping needs a 10-bit source (an 8-bit HDR10 source does not exist)");
+    if (src.colour_range == 1) return refuse("tone mapping takes a limited-range source; the Y4M header says XCOLORRANGE=FULL");
+    cfg.tone_map = 1;
+    cfg.tone_map_peak = job.tonemap_peak ? job.tonemap_peak : job.hdr.have_mdcv ? (int)std::min<uint32_t>(std::max<uint32_t>(job.hdr.luminance_max >> 8, 100), 10000) : 0;
   }
-  if (fr.key_block_size == 32) return Key32TemporalUnit(fr, seg, desc, width, height, with_sequence_header, threads, out, err);      // symbols of a key frame in 32x32 blocks
-  if (!av1::temporal_unit(desc.f, with_sequence_header, threads, out, &werr)) { if (err) *err = "bitstream writer: " + werr; return false; }
-  return true;
+  plan->grainy = job.denoise > 0 && job.film_grain != 0;
+  plan->analysed = job.scenecut > 0;
+  plan->stored = plan->analysed || dei != 0 || job.denoise > 0;
+  if (plan->stored) cfg.store_frames = S * G;
+  // What the reader threads deliver, one segment's share of the pinned buffers: frames of the coded size (the source's edge replicated
+  // into the padding) or, when the GPU scales, of the source size rounded up to 8; no chroma planes for a grey source.  (A config the
+  // layout refuses, av1mi_gop_open refuses, with the reason.)
+  (void)av1mi_gop_source_layout(&cfg, &plan->fed);
+  return 0;
 }
 
-int RunBackend(const BackendJob &job, std::string *err) {
+std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, const StatsTags &tags, bool cut) {
+  char line[512];
+  int k = snprintf(line, sizeof(line), "n:%ld type:%c bytes:%zu", n, key ? 'K' : 'P', f.unit.size());
+  k += av1mi::quality::format_figures(av1mi::quality::frame_figures(f.q, bit_depth), line + k, sizeof(line) - (size_t)k);
+  if (tags.win.w && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " crop:%dx%d+%d+%d", tags.win.w, tags.win.h, tags.win.x, tags.win.y);
+  if (tags.colour && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " colour:%d/%d/%d/%d", tags.colour->primaries, tags.colour->transfer, tags.colour->matrix, tags.colour->full_range);
+  if (tags.q) k += snprintf(line + k, sizeof(line) - (size_t)k, " q:%d", f.base_q_idx);
+  if (tags.grain) k += snprintf(line + k, sizeof(line) - (size_t)k, " grain:%d", f.grain);
+  if (cut) k += snprintf(line + k, sizeof(line) - (size_t)k, " cut:1");
+  return std::string(line, (size_t)k);
+}
+
+std::string StatsSummaryLine(const av1mi::quality::Summary &sum, long long bytes, int bit_depth) {
+  char line[512];
+  int k = snprintf(line, sizeof(line), "summary frames:%ld bytes:%lld", sum.frames, bytes);
+  k += av1mi::quality::format_figures(sum.figures(bit_depth), line + k, sizeof(line) - (size_t)k);
+  return std::string(line, (size_t)k);
+}
+
+namespace {
+
+// reader threads at work on the session's pinned planes; join() = all of them delivered their frame (false: a truncated one)
+struct Reads {
+  std::vector<std::thread> th; std::vector<char> ok;
+  bool join() { for (auto &x : th) if (x.joinable()) x.join(); th.clear(); for (char c : ok) if (!c) return false; return true; }
+  ~Reads() { for (auto &x : th) if (x.joinable()) x.join(); }
+};
+typedef std::vector<std::vector<FrameOut>> GroupOut;      // [segment][t]: the coded frames of the group in flight
+
+struct Run {
+  const BackendJob &job;
+  std::string *err;
   av1mi_ctx *ctx = nullptr;
-  if (av1mi_device_count() <= 0 || av1mi_open(job.device, &ctx) != AV1MI_OK) {
-    *err = "Error: no usable HIP device for the av1mi backend (device " + std::to_string(job.device) + ")";
-    return -1;
-  }
   Y4mSource y;
   av1mi_gop *gop = nullptr;
   StreamSink sink;
-  int code = 0;
-#define CHK(call)                                                                                   \
-  do { int rc_ = (call); if (rc_ != AV1MI_OK) { *err = std::string(#call) + ": " + av1mi_last_error(ctx); code = 2; goto done; } } while (0)
-  if (!y.open(job.input, err, job.to_420)) { code = 1; goto done; }
-  {
-    // the target: what the argv's filter chain yields on this source (transcode.go:92-115), or -av1mi_scale; no chain = the source
-    // the window first: -av1mi_crop stands in front of the chain, whose filters then see the window's size
-    CropRect win;
-    if (job.crop_mode == 2) {
-      win = job.crop;
-      if (win.w > y.w || win.h > y.h || win.x > y.w - win.w || win.y > y.h - win.h) {
-        *err = "Invalid argument: -av1mi_crop " + std::to_string(win.w) + ":" + std::to_string(win.h) + ":" + std::to_string(win.x) + ":" + std::to_string(win.y) +
-               " lies outside the " + std::to_string(y.w) + "x" + std::to_string(y.h) + " picture";
-        code = 1; goto done;
-      }
-    } else if (job.crop_mode == 1) {
-      // cropping by a stream's first frames would crop by its opening credits, and what is cropped is gone
-      if (!y.seekable()) { *err = "Invalid argument: -av1mi_crop auto needs a seekable file: it samples frames from all over the input, not from a pipe or FIFO"; code = 1; goto done; }
-      const long have = y.prepare(0, y.known_frames(), err);
-      if (have < 0) { code = 1; goto done; }
-      const int n = (int)std::min<long>(kCropSampleFrames, have), W8 = (y.w + 7) & ~7, H8 = (y.h + 7) & ~7;
-      const size_t plane = (size_t)W8 * H8 * (y.src_bd == 8 ? 1 : 2);
-      std::vector<unsigned char> luma(plane * (size_t)std::max(n, 1)), cu(plane), cv(plane);      // (the chroma planes are read and dropped)
-      for (int i = 0; i < n; i++)
-        if (!y.read((long)i * have / n, W8, H8, luma.data() + plane * (size_t)i, cu.data(), cv.data())) { *err = job.input + ": Invalid data found when processing input (truncated frame)"; code = 1; goto done; }
-      std::vector<av1mi_crop_record> rec((size_t)std::max(n, 1));
-      if (n > 0) {
-        void *d_luma = nullptr, *d_rec = nullptr;
-        int rc = av1mi_malloc(ctx, &d_luma, luma.size());
-        if (rc == AV1MI_OK) rc = av1mi_malloc(ctx, &d_rec, rec.size() * sizeof(av1mi_crop_record));
-        if (rc == AV1MI_OK) rc = av1mi_upload(ctx, d_luma, luma.data(), luma.size());
-        if (rc == AV1MI_OK) rc = av1mi_crop_analyse(ctx, y.src_bd, W8, H8, y.w, y.h, n, d_luma, job.crop_limit, (av1mi_crop_record *)d_rec);
-        if (rc == AV1MI_OK) rc = av1mi_download(ctx, rec.data(), d_rec, rec.size() * sizeof(av1mi_crop_record));
-        if (rc != AV1MI_OK) *err = std::string("av1mi_crop_analyse: ") + av1mi_last_error(ctx);
-        if (d_luma) (void)av1mi_free(ctx, d_luma);
-        if (d_rec) (void)av1mi_free(ctx, d_rec);
-        if (rc != AV1MI_OK) { code = 2; goto done; }
-      }
-      if (!PlanCrop(rec.data(), n, y.w, y.h, &win) || !win.trims(y.w, y.h)) win = CropRect();      // no bars: today's path, exactly
+  CropRect window;             // settle_window: -av1mi_crop's, given or found (w == 0: none)
+  SessionPlan plan = {};       // session_config
+  av1::SequenceParams sp;
+  int S = 0, G = 0, threads = 1, lag = 0;
+  std::vector<std::vector<unsigned char>> scratch;      // packed: per reader thread, one planar frame to pack from
+  // A target (-b:v:0 / -av1mi_target_bpp): the controller lives across the groups.  It is asked at ONE point of the loop (before each
+  // submit) and told at one (after each assemble), so the quantisers, and with them the output bytes, are a function of the input alone.
+  std::unique_ptr<RateControl> rc;
+  long long rc_bytes = 0, rc_frames = 0;
+  long g0 = 0, total_frames = 0;      // the group in flight starts at GOP g0 of the input
+  int cur_store = 0;
+  long next_frames = -1, next_put = 0;      // stored: frames of the group that goes into the other store (-1 = not asked yet), and those already put
+  av1mi_gop_frame oldest;      // the batch collected last, until it is assembled
+  std::string stats;           // the stats file's lines, in presentation order
+  av1mi::quality::Summary summary;
+  long long total_bytes = 0;
+
+  Run(const BackendJob &j, std::string *e) : job(j), err(e) {}
+  ~Run() {
+    if (!ctx) return;
+    sink.abort();
+    if (gop) av1mi_gop_close(gop);
+    y.close();
+    av1mi_close(ctx);
+  }
+  int fail(int code, const std::string &text) { *err = text; return code; }
+  int lib_error(const char *call) { return fail(2, std::string(call) + ": " + av1mi_last_error(ctx)); }
+  int truncated() { return fail(1, job.input + ": Invalid data found when processing input (truncated frame)"); }
+  unsigned char *at(void *plane, int p, int i) const { return (unsigned char *)plane + plan.fed.plane[p].frame_bytes * (size_t)i; }      // frame i of a pinned plane
+
+  // The crop window, settled before the session is opened: -av1mi_crop W:H:X:Y as given, or what auto finds in a sample of the file
+  int settle_window() {
+    if (job.crop_mode == 2) return ExplicitWindow(job, y.w, y.h, &window, err);
+    if (job.crop_mode != 1) return 0;
+    // cropping by a stream's first frames would crop by its opening credits, and what is cropped is gone
+    if (!y.seekable()) return fail(1, "Invalid argument: -av1mi_crop auto needs a seekable file: it samples frames from all over the input, not from a pipe or FIFO");
+    const long have = y.prepare(0, y.known_frames(), err);
+    if (have < 0) return 1;
+    const int n = (int)std::min<long>(kCropSampleFrames, have), W8 = (y.w + 7) & ~7, H8 = (y.h + 7) & ~7;
+    const size_t plane = (size_t)W8 * H8 * (y.src_bd == 8 ? 1 : 2);
+    std::vector<unsigned char> luma(plane * (size_t)std::max(n, 1)), cu(plane), cv(plane);      // (the chroma planes are read and dropped)
+    for (int i = 0; i < n; i++)
+      if (!y.read((long)i * have / n, W8, H8, luma.data() + plane * (size_t)i, cu.data(), cv.data())) return truncated();
+    std::vector<av1mi_crop_record> rec((size_t)std::max(n, 1));
+    if (n > 0) {
+      void *d_luma = nullptr, *d_rec = nullptr;
+      int rc = av1mi_malloc(ctx, &d_luma, luma.size());
+      if (rc == AV1MI_OK) rc = av1mi_malloc(ctx, &d_rec, rec.size() * sizeof(av1mi_crop_record));
+      if (rc == AV1MI_OK) rc = av1mi_upload(ctx, d_luma, luma.data(), luma.size());
+      if (rc == AV1MI_OK) rc = av1mi_crop_analyse(ctx, y.src_bd, W8, H8, y.w, y.h, n, d_luma, job.crop_limit, (av1mi_crop_record *)d_rec);
+      if (rc == AV1MI_OK) rc = av1mi_download(ctx, rec.data(), d_rec, rec.size() * sizeof(av1mi_crop_record));
+      if (rc != AV1MI_OK) lib_error("av1mi_crop_analyse");
+      if (d_luma) (void)av1mi_free(ctx, d_luma);
+      if (d_rec) (void)av1mi_free(ctx, d_rec);
+      if (rc != AV1MI_OK) return 2;
     }
-    const int pw = win.w ? win.w : y.w, ph = win.w ? win.h : y.h;      // the picture the chain works on
-    int tw = pw, th = ph;
-    bool square = y.sar_n == y.sar_d;
-    CropRect chain_crop;
-    if (job.have_vf && !ChainTarget(pw, ph, y.sar_n, y.sar_d, job.vf, &tw, &th, &square, err, nullptr, nullptr, &chain_crop)) { code = 1; goto done; }
-    if (chain_crop.w) win = chain_crop;      // (ParseBackendJob: never together with -av1mi_crop)
-    if (job.scale_w) { tw = job.scale_w; th = job.scale_h; square = true; }
-    const bool scaling = win.w != 0 || tw != y.w || th != y.h || job.scale_w != 0;      // a window is fed like a source to be scaled: whole frames
-    const int G = job.gop, w = (tw + 7) & ~7, h = (th + 7) & ~7;       // the coded size; tw x th is what a decoder outputs
-    int S = std::max(job.segments, 1);
-    if (y.known_frames() >= 0) S = (int)std::max<long>(1, std::min<long>(S, (y.known_frames() + G - 1) / G));      // no more segments than the file has GOPs
-    long total_frames = 0;
-    const int threads = job.threads > 0 ? job.threads : (int)std::max(1u, std::thread::hardware_concurrency());
-    av1mi_gop_config cfg;
-    memset(&cfg, 0, sizeof(cfg));
-    if (w != tw || h != th) { cfg.visible_width = tw; cfg.visible_height = th; }
-    if (scaling) { cfg.source_width = y.w; cfg.source_height = y.h; }
-    if (win.w) { cfg.crop_x = win.x; cfg.crop_y = win.y; cfg.crop_width = win.w; cfg.crop_height = win.h; }
-    cfg.width = w; cfg.height = h; cfg.bit_depth = y.bd; cfg.base_q_idx = job.quality < 1 ? 1 : job.quality; cfg.gop_length = G; cfg.segments = S;
-    cfg.search_range = 8;
-    cfg.coarse_range = job.me_range;      // -av1mi_me_range: the coarse search in front of it
-    cfg.gpu_entropy = job.gpu_entropy ? 1 : 0;
-    // -av1mi_stats / -av1mi_min_psnr: the session measures every batch on the GPU; the records arrive with the collected batch
-    const bool measure = !job.stats_path.empty() || job.min_psnr > 0;
-    cfg.quality_stats = measure ? 1 : 0;
-    std::string stats;                 // the stats file's lines, in presentation order
-    av1mi::quality::Summary summary;
-    long long total_bytes = 0;
-    // key frames in 32x32 blocks where the frame allows it (the coded width a multiple of 32)
-    cfg.key_block_size = (job.key_block_size == 32 && (w & 31) == 0) ? 32 : 8;
-    // -av1mi_pack10 1: a 10-bit source crosses PCIe at 10 bits per sample; the session's pinned buffers are then three packed planes
-    // A source that is not 4:2:0 at the coded depth (only a job that converts opens one): fed in its own layout, converted on the GPU
-    const bool convert = y.chroma != AV1MI_CHROMA_420 || y.src_bd != y.bd;
-    if (convert) { cfg.source_chroma = y.chroma; cfg.source_bit_depth = y.src_bd; }
-    const bool packed = job.pack10 && y.bd == 10 && !convert;      // (planar 4:2:0 10-bit only)
-    if (packed) cfg.input_format = AV1MI_INPUT_PACKED10;
-    // -av1mi_deinterlace: auto follows the header's I parameter, tff / bff force a parity
-    int dei = job.deinterlace == 2 ? 1 : job.deinterlace == 3 ? 2 : 0;
-    if (job.deinterlace == 1) {
-      if (y.interlace == 3) { *err = "Invalid argument: -av1mi_deinterlace auto: the source is mixed-mode interlaced (Im); field-rate output and inverse telecine are not built"; code = 1; goto done; }
-      dei = y.interlace;
-    }
-    cfg.deinterlace = dei;
-    // -av1mi_scenecut, or a job that deinterlaces: the frame store holds one group (the deinterlacer's run)
-    // -av1mi_denoise: the same store, the denoiser in the gather; -av1mi_film_grain (1 unless told otherwise): parameters in every frame header
-    cfg.denoise = job.denoise;
-    cfg.denoise_range = job.denoise_range;
-    // the stream's colour record: the job's options, the header's range; a tone-mapped job says what the kernel makes
-    const av1mi_colour colour = JobColour(job, y.colour_range);
-    if (const char *why = av1::colour_error(colour)) { *err = std::string("Invalid argument: ") + why; code = 1; goto done; }
-    if (job.tonemap) {
-      if (y.bd != 10) { *err = "Invalid argument: tone mapping needs a 10-bit source (an 8-bit HDR10 source does not exist)"; code = 1; goto done; }
-      if (y.colour_range == 1) { *err = "Invalid argument: tone mapping takes a limited-range source; the Y4M header says XCOLORRANGE=FULL"; code = 1; goto done; }
-      cfg.tone_map = 1;
-      cfg.tone_map_peak = job.tonemap_peak ? job.tonemap_peak : job.hdr.have_mdcv ? (int)std::min<uint32_t>(std::max<uint32_t>(job.hdr.luminance_max >> 8, 100), 10000) : 0;
-    }
-    const bool grainy = job.denoise > 0 && job.film_grain != 0;
-    const bool analysed = job.scenecut > 0, stored = analysed || dei != 0 || job.denoise > 0;
-    if (stored) cfg.store_frames = S * G;
-    // What the reader threads deliver, one segment's share of the pinned buffers: frames of the coded size (the source's edge replicated
-    // into the padding) or, when the GPU scales, of the source size rounded up to 8; no chroma planes for a grey source.  (A config the
-    // layout refuses, av1mi_gop_open refuses below, with the reason.)
-    av1mi_source_layout fed = {};
-    (void)av1mi_gop_source_layout(&cfg, &fed);
-    auto at = [&](void *plane, int p, int i) { return (unsigned char *)plane + fed.plane[p].frame_bytes * (size_t)i; };      // frame i of a pinned plane
-    std::vector<std::vector<unsigned char>> scratch(packed ? (size_t)S : 0);          // per reader thread: one planar frame to pack from
-    CHK(av1mi_gop_open(ctx, &cfg, &gop));
-    av1::SequenceParams sp; sp.width = tw; sp.height = th; sp.bit_depth = y.bd; sp.film_grain = grainy; sp.colour = colour;
-    const av1mi_colour *const stream_colour = sp.has_colour() ? &colour : nullptr;
+    if (!PlanCrop(rec.data(), n, y.w, y.h, &window) || !window.trims(y.w, y.h)) window = CropRect();      // no bars: the path without a window, exactly
+    return 0;
+  }
+
+  int session_config() {
+    const SourceFacts src = { y.w, y.h, y.bd, y.src_bd, y.chroma, y.sar_n, y.sar_d, y.fps_n, y.fps_d, y.interlace, y.colour_range, y.known_frames() };
+    if (const int code = SessionConfig(job, src, window, &plan, err)) return code;
+    S = plan.cfg.segments; G = plan.cfg.gop_length;
+    threads = job.threads > 0 ? job.threads : (int)std::max(1u, std::thread::hardware_concurrency());
+    scratch.resize(plan.packed ? (size_t)S : 0);
+    return 0;
+  }
+
+  // the session, the sink (display size, side tracks) and the rate controller
+  int open_session() {
+    if (av1mi_gop_open(ctx, &plan.cfg, &gop) != AV1MI_OK) return lib_error("av1mi_gop_open");
+    sp.width = plan.tw; sp.height = plan.th; sp.bit_depth = y.bd; sp.film_grain = plan.grainy; sp.colour = plan.colour;
     // pixels that stay non-square: the track at least says at which shape to show them
-    if (!square) sink.set_display_size((int)((long)tw * y.sar_n / y.sar_d), th);
+    if (!plan.square) sink.set_display_size((int)((long)plan.tw * y.sar_n / y.sar_d), plan.th);
     for (const std::string &side : job.tracks)
-      if (!sink.add_side_file(side, err)) { code = 1; goto done; }
-    if (!sink.open(job.output, sp, y.fps_n, y.fps_d, err)) { code = 1; goto done; }
-    std::vector<std::vector<std::vector<uint8_t>>> units((size_t)S);   // [segment][frame] temporal units of the batch in flight
-    struct Rec { av1mi_quality q[3]; };
-    std::vector<std::vector<Rec>> records((size_t)S);                  // ... and their quality records (measure)
-    // A target (-b:v:0 / -av1mi_target_bpp): the controller lives across the groups.  It is asked at ONE point of the loop (before each
-    // submit) and told at one (after each assemble), so the quantisers, and with them the output bytes, are a function of the input alone.
-    std::unique_ptr<RateControl> rc;
-    std::vector<std::vector<int>> grains((size_t)S);                   // ... and, denoising, their luma scaling at mid grey (the stats file's grain:)
-    std::vector<std::vector<int>> qs((size_t)S);                       // ... and, with a target, their quantisers (the stats file's q:)
-    long long rc_bytes = 0, rc_frames = 0;
+      if (!sink.add_side_file(side, err)) return 1;
+    if (!sink.open(job.output, sp, y.fps_n, y.fps_d, err)) return 1;
     if (job.bitrate || job.target_bpp_u) {
       av1mi_rc_params rp;
       memset(&rp, 0, sizeof(rp));
       av1mi_rc_defaults(&rp);
       if (job.bitrate) { rp.target_num = job.bitrate * y.fps_d; rp.target_den = 8ll * y.fps_n; }
-      else { rp.target_num = job.target_bpp_u * tw * th; rp.target_den = 8000000; }
+      else { rp.target_num = job.target_bpp_u * plan.tw * plan.th; rp.target_den = 8000000; }
       if (job.qmin) rp.qmin = job.qmin;
       if (job.qmax) rp.qmax = job.qmax;
       rp.gop_length = G; rp.bit_depth = y.bd;
-      rp.start_q = std::min(std::max(cfg.base_q_idx, rp.qmin), rp.qmax);
-      if (const char *why = RateControl::ParamError(rp)) { *err = std::string("Invalid argument: rate control: ") + why; code = 1; goto done; }
+      rp.start_q = std::min(std::max(plan.cfg.base_q_idx, rp.qmin), rp.qmax);
+      if (const char *why = RateControl::ParamError(rp)) return fail(1, std::string("Invalid argument: rate control: ") + why);
       rc.reset(new RateControl(rp));
     }
-    const int lag = av1mi_gop_max_in_flight() - 1;      // batches the GPU holds while the host works on the oldest
-    // the layout of the group in flight: GOP s holds frames start[s] .. start[s] + len[s] - 1 of the group.  Fixed (s G, up to G frames)
-    // unless the planner moves the boundaries onto cuts (stored)
-    std::vector<int32_t> start((size_t)S), len((size_t)S), index((size_t)S);
-    std::vector<uint8_t> cut;                           // stored: the frames of the group the analysis flagged
-    std::vector<av1mi_scene_record> scene;
-    int cur_store = 0;
-    long next_frames = -1;                              // stored: frames of the group that is (being) put into the other store; -1 = not asked yet
-    // One chunk of a group -> a store (stored): frames f0 .. f0 + n - 1 of the group the reader has prepared, read by one thread each into
-    // the session's pinned buffers IN FILE ORDER, then put.  begin starts the threads, end joins them and queues the copy.
-    struct Reads {
-      std::vector<std::thread> th; std::vector<char> ok;
-      bool join() { for (auto &x : th) if (x.joinable()) x.join(); th.clear(); for (char c : ok) if (!c) return false; return true; }
-      ~Reads() { for (auto &x : th) if (x.joinable()) x.join(); }
-    };
-    Reads puts;
-    auto put_begin = [&](long f0, int n) -> bool {
-      void *py, *pu, *pv;
-      if (av1mi_gop_acquire_input(gop, &py, &pu, &pv) != AV1MI_OK) { *err = std::string("av1mi_gop_acquire_input: ") + av1mi_last_error(ctx); return false; }
-      puts.ok.assign((size_t)n, 1);
-      for (int i = 0; i < n; i++)
-        puts.th.emplace_back([&, i, f0, py, pu, pv]() {
-          puts.ok[(size_t)i] = y.read(f0 + i, fed.width, fed.height, at(py, 0, i), at(pu, 1, i), at(pv, 2, i));
-        });
-      return true;
-    };
-    auto put_end = [&](int store, long f0, int n) -> int {      // 0, or the exit code
-      if (!puts.join()) { *err = job.input + ": Invalid data found when processing input (truncated frame)"; return 1; }
-      if (av1mi_gop_store_put(gop, store, (int)f0, n) != AV1MI_OK) { *err = std::string("av1mi_gop_store_put: ") + av1mi_last_error(ctx); return 2; }
-      return 0;
-    };
-    for (long g0 = 0;; g0 += S) {
-      for (auto &u : units) u.clear();
-      for (auto &r : records) r.clear();
-      for (auto &v : qs) v.clear();
-      for (auto &v : grains) v.clear();
-      // the next GROUP of S GOPs: a file is read in place, a stream one group ahead of the encoder (y4m.hpp)
-      long have_frames;
-      if (stored && next_frames >= 0) have_frames = next_frames;      // already in the store: it was put while the group before ran
-      else {
-        have_frames = y.prepare(g0 * G, (long)S * G, err);
-        if (have_frames < 0) { code = 1; goto done; }
-        for (long f0 = 0; stored && f0 < have_frames; f0 += S) {      // the first group: nothing runs beside it
-          const int n = (int)std::min<long>(S, have_frames - f0);
-          if (!put_begin(f0, n)) { code = 2; goto done; }
-          if ((code = put_end(cur_store, f0, n)) != 0) goto done;
-        }
+    lag = av1mi_gop_max_in_flight() - 1;      // batches the GPU holds while the host works on the oldest
+    return 0;
+  }
+
+  // THE reader of frames into the session's pinned planes: slot i of the next input buffers receives frame frame[i] of the group the
+  // reader has prepared, read (and, where the job packs, packed) by a thread of its own; -1 = a flat slot.  Every call is followed by
+  // exactly one submit or store_put.  0, or the exit code; reads->join() then tells whether every frame was whole.
+  int start_reads(const std::vector<int32_t> &frame, Reads *reads) {
+    void *py, *pu, *pv;
+    if (av1mi_gop_acquire_input(gop, &py, &pu, &pv) != AV1MI_OK) return lib_error("av1mi_gop_acquire_input");
+    const av1mi_source_layout &fed = plan.fed;
+    reads->ok.assign(frame.size(), 1);
+    for (int i = 0; i < (int)frame.size(); i++) {
+      if (frame[(size_t)i] < 0) {
+        // a shorter last GOP / fewer GOPs than segments: the slot is coded (the batch is one launch) and its output dropped.  Flat
+        // planes, not whatever the pinned buffer held: stale pixels could cost the GPU coder's tile capacity for the whole batch
+        // (zero samples pack to zero bytes)
+        void *const plane[3] = { py, pu, pv };
+        for (int p = 0; p < 3; p++) if (fed.plane[p].frame_bytes) memset(at(plane[p], p, i), 0, fed.plane[p].frame_bytes);
+        continue;
       }
-      if (have_frames == 0) break;
-      total_frames += have_frames;
-      for (int s = 0; s < S; s++) { start[(size_t)s] = s * G; len[(size_t)s] = (int32_t)std::max<long>(0, std::min<long>(G, have_frames - (long)s * G)); }
-      if (analysed) {
-        scene.resize((size_t)have_frames); cut.assign((size_t)have_frames, 0);
-        CHK(av1mi_gop_store_analyse(gop, cur_store, (int)have_frames, scene.data()));
-        for (long f = 0; f < have_frames; f++) cut[(size_t)f] = (uint8_t)av1mi_scene_is_cut(&scene[(size_t)f], job.scenecut);
-        if (av1mi_plan_gops((int)have_frames, G, S, job.min_gop, cut.data(), start.data(), len.data()) < 0) { *err = "Invalid argument: -av1mi_min_gop does not fit the GOP length"; code = 1; goto done; }
-      }
-      if (stored) {      // (a job that only deinterlaces keeps the nominal layout above)
-        // the group after this one: prepared now (this group's frames are all in the store), put chunk by chunk beside the batches below
-        next_frames = y.prepare((g0 + S) * G, (long)S * G, err);
-        if (next_frames < 0) { code = 1; goto done; }
-      }
-      long next_put = 0;                                  // stored: frames of the next group already put
-      // frames of this group that exist: segment s, position t -> frame start[s] + t of the group
-      auto exists = [&](int s, int t) { return t < len[(size_t)s]; };
-      int T = 0;
-      for (int s = 0; s < S; s++) T = std::max(T, (int)len[(size_t)s]);
-      av1mi_gop_frame fr;
-      auto collect_oldest = [&]() -> bool {
-        if (av1mi_gop_collect(gop, &fr) != AV1MI_OK) { *err = std::string("av1mi_gop_collect: ") + av1mi_last_error(ctx); return false; }
-        return true;
-      };
-      auto assemble = [&](int t) -> bool {         // the collected batch t -> temporal units (frame header + tile group, or the host coder)
-        long long batch_bytes = 0;
-        for (int s = 0; s < S; s++) {
-          if (!exists(s, t)) continue;
-          std::vector<uint8_t> tu;
-          av1mi_film_grain fg;
-          if (job.denoise) {      // what the gather removed from this frame -> the parameters that put it back (none for the ends of a run)
-            if (!fr.grain) { *err = "the session returned no grain records"; return false; }
-            FilmGrainFromRecords(fr.grain + (size_t)s * 3, y.bd, (int)(g0 * G + start[(size_t)s] + t), &fg);
-            grains[(size_t)s].push_back(FilmGrainMidGrey(fg));
-          }
-          if (!SessionTemporalUnit(fr, s, w, h, y.bd, cfg.visible_width, cfg.visible_height, t == 0, threads, &tu, err, grainy, grainy ? &fg : nullptr, stream_colour)) return false;
-          batch_bytes += (long long)tu.size();
-          if (rc) qs[(size_t)s].push_back(fr.params.base_q_idx);
-          units[(size_t)s].push_back(std::move(tu));
-          if (measure) {
-            if (!fr.quality) { *err = "the session returned no quality records"; return false; }
-            Rec r;
-            memcpy(r.q, fr.quality + (size_t)s * 3, sizeof(r.q));
-            records[(size_t)s].push_back(r);
-          }
-        }
-        if (rc) {      // the truth replaces the controller's prediction for this batch; segments that do not exist count nowhere
-          rc_bytes += batch_bytes;
-          if (rc->Collected(batch_bytes) != 0) { *err = "rate control: nothing in flight"; return false; }
-        }
-        return true;
-      };
-      // The frames of batch t + 1 are read (one thread per segment) WHILE the host assembles batch t - lag: the session hands out
-      // the next input buffers as soon as the oldest batch has been collected.
-      Reads reads;
-      auto start_reads = [&](int t) -> bool {
-        void *py, *pu, *pv;
-        if (av1mi_gop_acquire_input(gop, &py, &pu, &pv) != AV1MI_OK) { *err = std::string("av1mi_gop_acquire_input: ") + av1mi_last_error(ctx); return false; }
-        reads.ok.assign((size_t)S, 1);
-        for (int s = 0; s < S; s++) {
-          if (!exists(s, t)) {
-            // a shorter last GOP / fewer GOPs than segments: the slot is coded (the batch is one launch) and its output dropped.  Flat
-            // planes, not whatever the pinned buffer held: stale pixels could cost the GPU coder's tile capacity for the whole batch
-            // (zero samples pack to zero bytes)
-            void *const plane[3] = { py, pu, pv };
-            for (int p = 0; p < 3; p++) if (fed.plane[p].frame_bytes) memset(at(plane[p], p, s), 0, fed.plane[p].frame_bytes);
-            continue;
-          }
-          reads.th.emplace_back([&, s, t, py, pu, pv]() {
-            if (!packed) {
-              reads.ok[(size_t)s] = y.read((long)start[(size_t)s] + t, fed.width, fed.height, at(py, 0, s), at(pu, 1, s), at(pv, 2, s));
-              return;
-            }
-            // the frame (edge padding included) into this thread's scratch, then packed into the segment's byte range of the pinned planes
-            std::vector<unsigned char> &f = scratch[(size_t)s];
-            const size_t fy = (size_t)fed.width * fed.height * 2, fc = fy / 4;      // planar 10-bit planes
-            f.resize(fy + 2 * fc);
-            reads.ok[(size_t)s] = y.read((long)start[(size_t)s] + t, fed.width, fed.height, f.data(), f.data() + fy, f.data() + fy + fc) &&
-                                  av1mi_input_pack(AV1MI_INPUT_PACKED10, 10, fed.width, fed.height, f.data(), f.data() + fy, f.data() + fy + fc, at(py, 0, s), at(pu, 1, s), at(pv, 2, s)) == AV1MI_OK;
-          });
-        }
-        return true;
-      };
-      if (!stored && T > 0 && !start_reads(0)) { code = 2; goto done; }
-      for (int t = 0; t < T; t++) {
-        if (!stored && !reads.join()) { *err = job.input + ": Invalid data found when processing input (truncated frame)"; code = 1; goto done; }
-        if (rc) {
-          int frames = 0;
-          for (int s = 0; s < S; s++) frames += exists(s, t) ? 1 : 0;
-          rc_frames += frames;
-          const int q = rc->NextQ(t == 0 ? 0 : 1, frames);
-          if (q < 1) { *err = "rate control: no quantiser for the next batch"; code = 2; goto done; }
-          CHK(av1mi_gop_set_base_q_idx(gop, q));
-        }
-        if (stored) {
-          for (int s = 0; s < S; s++) index[(size_t)s] = exists(s, t) ? start[(size_t)s] + t : -1;      // (-1: a flat slot, its output dropped)
-          CHK(av1mi_gop_submit_stored(gop, cur_store, index.data(), t == 0 ? 0 : 1));
-        } else CHK(av1mi_gop_submit(gop, t == 0 ? 0 : 1));
-        const bool have = t >= lag;
-        if (have && !collect_oldest()) { code = 2; goto done; }            // the GPU works on the frames after it meanwhile
-        // what is read beside the host's work on the oldest batch: the next batch's frames, or (stored) the next chunk of the next group
-        const int chunk = stored ? (int)std::min<long>(S, next_frames - next_put) : 0;
-        if (!stored && t + 1 < T && !start_reads(t + 1)) { code = 2; goto done; }
-        if (chunk > 0 && !put_begin(next_put, chunk)) { code = 2; goto done; }
-        if (have && !assemble(t - lag)) { code = 2; goto done; }
-        if (chunk > 0) { if ((code = put_end(cur_store ^ 1, next_put, chunk)) != 0) goto done; next_put += chunk; }
-      }
-      for (int t = std::max(0, T - lag); t < T; t++)
-        if (!collect_oldest() || !assemble(t)) { code = 2; goto done; }
-      for (; stored && next_put < next_frames; ) {      // (a group of short GOPs has fewer batches than the next group has chunks)
-        const int n = (int)std::min<long>(S, next_frames - next_put);
-        if (!put_begin(next_put, n)) { code = 2; goto done; }
-        if ((code = put_end(cur_store ^ 1, next_put, n)) != 0) goto done;
-        next_put += n;
-      }
-      for (int s = 0; s < S; s++)
-        for (size_t t = 0; t < units[(size_t)s].size(); t++)
-          if (!sink.write(units[(size_t)s][t], t == 0, err)) { code = 1; goto done; }
-      if (measure)
-        for (int s = 0; s < S; s++)
-          for (size_t t = 0; t < units[(size_t)s].size(); t++) {
-            char line[512];
-            int n = snprintf(line, sizeof(line), "n:%ld type:%c bytes:%zu", summary.frames, t == 0 ? 'K' : 'P', units[(size_t)s][t].size());
-            n += av1mi::quality::format_figures(av1mi::quality::frame_figures(records[(size_t)s][t].q, y.bd), line + n, sizeof(line) - (size_t)n);
-            if (win.w && summary.frames == 0) n += snprintf(line + n, sizeof(line) - (size_t)n, " crop:%dx%d+%d+%d", win.w, win.h, win.x, win.y);
-            if (sp.described() && summary.frames == 0) n += snprintf(line + n, sizeof(line) - (size_t)n, " colour:%d/%d/%d/%d", colour.primaries, colour.transfer, colour.matrix, colour.full_range);
-            if (rc) n += snprintf(line + n, sizeof(line) - (size_t)n, " q:%d", qs[(size_t)s][t]);
-            if (job.denoise) n += snprintf(line + n, sizeof(line) - (size_t)n, " grain:%d", grains[(size_t)s][t]);
-            if (analysed && cut[(size_t)start[(size_t)s] + t]) n += snprintf(line + n, sizeof(line) - (size_t)n, " cut:1");
-            stats.append(line, (size_t)n); stats += '\n';
-            summary.add(records[(size_t)s][t].q, y.bd);
-            total_bytes += (long long)units[(size_t)s][t].size();
-          }
-      if (stored) cur_store ^= 1;
+      reads->th.emplace_back([this, reads, &fed, i, f = (long)frame[(size_t)i], py, pu, pv]() {
+        if (!plan.packed) { reads->ok[(size_t)i] = y.read(f, fed.width, fed.height, at(py, 0, i), at(pu, 1, i), at(pv, 2, i)); return; }
+        // the frame (edge padding included) into this thread's scratch, then packed into the slot's byte range of the pinned planes
+        std::vector<unsigned char> &b = scratch[(size_t)i];
+        const size_t fy = (size_t)fed.width * fed.height * 2, fc = fy / 4;      // planar 10-bit planes
+        b.resize(fy + 2 * fc);
+        reads->ok[(size_t)i] = y.read(f, fed.width, fed.height, b.data(), b.data() + fy, b.data() + fy + fc) &&
+                               av1mi_input_pack(AV1MI_INPUT_PACKED10, 10, fed.width, fed.height, b.data(), b.data() + fy, b.data() + fy + fc, at(py, 0, i), at(pu, 1, i), at(pv, 2, i)) == AV1MI_OK;
+      });
     }
-    if (total_frames == 0) { *err = job.input + ": Invalid data found when processing input (no frames)"; code = 1; goto done; }
-    if (!sink.close(err)) { code = 1; goto done; }
+    return 0;
+  }
+  // The next chunk (up to S frames, IN FILE ORDER) of the `frames` frames the reader has prepared -> a store; *put counts the frames
+  // put so far.  The chunk is read while `beside` (if any) runs; nothing left to put = `beside` alone.
+  int put_chunk(int store, long frames, long *put, const std::function<int()> &beside = nullptr) {
+    const int n = (int)std::min<long>(S, frames - *put);
+    Reads reads;
+    std::vector<int32_t> frame((size_t)std::max(n, 0));
+    for (int i = 0; i < n; i++) frame[(size_t)i] = (int32_t)*put + i;
+    int code = n > 0 ? start_reads(frame, &reads) : 0;
+    if (code || (beside && (code = beside())) || n <= 0) return code;
+    if (!reads.join()) return truncated();
+    if (av1mi_gop_store_put(gop, store, (int)*put, n) != AV1MI_OK) return lib_error("av1mi_gop_store_put");
+    *put += n;
+    return 0;
+  }
+  int put_all(int store, long frames, long *put) {
+    for (int code; *put < frames;) if ((code = put_chunk(store, frames, put))) return code;
+    return 0;
+  }
+
+  // THE place a group is laid out: the nominal layout (GOP s = frames s G .. of the group), or with -av1mi_scenecut the planner's, its
+  // boundaries moved onto the cuts the analysis of the store finds.  (A job that only deinterlaces or denoises keeps the nominal layout.)
+  int lay_out(long frames, Group *g) {
+    g->frames = frames; g->start.resize((size_t)S); g->len.resize((size_t)S);
+    for (int s = 0; s < S; s++) { g->start[(size_t)s] = s * G; g->len[(size_t)s] = (int32_t)std::max<long>(0, std::min<long>(G, frames - (long)s * G)); }
+    if (!plan.analysed) return 0;
+    std::vector<av1mi_scene_record> scene((size_t)frames);
+    g->cut.assign((size_t)frames, 0);
+    if (av1mi_gop_store_analyse(gop, cur_store, (int)frames, scene.data()) != AV1MI_OK) return lib_error("av1mi_gop_store_analyse");
+    for (long f = 0; f < frames; f++) g->cut[(size_t)f] = (uint8_t)av1mi_scene_is_cut(&scene[(size_t)f], job.scenecut);
+    if (av1mi_plan_gops((int)frames, G, S, job.min_gop, g->cut.data(), g->start.data(), g->len.data()) < 0) return fail(1, "Invalid argument: -av1mi_min_gop does not fit the GOP length");
+    return 0;
+  }
+
+  // ask the rate controller, then submit batch t
+  int submit(const Group &group, int t) {
+    if (rc) {
+      int frames = 0;
+      for (int s = 0; s < S; s++) frames += group.exists(s, t) ? 1 : 0;
+      rc_frames += frames;
+      const int q = rc->NextQ(t == 0 ? 0 : 1, frames);
+      if (q < 1) return fail(2, "rate control: no quantiser for the next batch");
+      if (av1mi_gop_set_base_q_idx(gop, q) != AV1MI_OK) return lib_error("av1mi_gop_set_base_q_idx");
+    }
+    if (!plan.stored) return av1mi_gop_submit(gop, t == 0 ? 0 : 1) == AV1MI_OK ? 0 : lib_error("av1mi_gop_submit");
+    return av1mi_gop_submit_stored(gop, cur_store, group.slots(t).data(), t == 0 ? 0 : 1) == AV1MI_OK ? 0 : lib_error("av1mi_gop_submit_stored");
+  }
+  int collect() { return av1mi_gop_collect(gop, &oldest) == AV1MI_OK ? 0 : lib_error("av1mi_gop_collect"); }
+  // the collected batch t -> one FrameOut per segment that exists (frame header + tile group, or the host coder); tells the controller
+  int assemble(const Group &group, int t, GroupOut *out) {
+    long long batch_bytes = 0;
+    for (int s = 0; s < S; s++) {
+      if (!group.exists(s, t)) continue;
+      FrameOut f = {};
+      av1mi_film_grain fg;
+      if (job.denoise) {      // what the gather removed from this frame -> the parameters that put it back (none for the ends of a run)
+        if (!oldest.grain) return fail(2, "the session returned no grain records");
+        FilmGrainFromRecords(oldest.grain + (size_t)s * 3, y.bd, (int)(g0 * G + group.start[(size_t)s] + t), &fg);
+        f.grain = FilmGrainMidGrey(fg);
+      }
+      if (!SessionTemporalUnit(oldest, s, plan.cfg.width, plan.cfg.height, y.bd, plan.cfg.visible_width, plan.cfg.visible_height, t == 0, threads, &f.unit, err, plan.grainy,
+                               plan.grainy ? &fg : nullptr, sp.has_colour() ? &plan.colour : nullptr)) return 2;
+      batch_bytes += (long long)f.unit.size();
+      f.base_q_idx = oldest.params.base_q_idx;
+      if (plan.measure) {
+        if (!oldest.quality) return fail(2, "the session returned no quality records");
+        memcpy(f.q, oldest.quality + (size_t)s * 3, sizeof(f.q));
+      }
+      (*out)[(size_t)s].push_back(std::move(f));
+    }
+    if (rc) {      // the truth replaces the controller's prediction for this batch; segments that do not exist count nowhere
+      rc_bytes += batch_bytes;
+      if (rc->Collected(batch_bytes) != 0) return fail(2, "rate control: nothing in flight");
+    }
+    return 0;
+  }
+
+  // The batches of a group.  The frames of batch t + 1 (stored: the next chunk of the next group) are read WHILE the host assembles batch
+  // t - lag: the session hands out the next input buffers as soon as the oldest batch has been collected.  The order inside a step is
+  // what overlaps the reads with the assembly and keeps the quantisers a function of the input alone.
+  int code_group(const Group &group, GroupOut *out) {
+    const int T = group.T();
+    const bool stored = plan.stored;
+    Reads reads;
+    int code = !stored && T > 0 ? start_reads(group.slots(0), &reads) : 0;
+    for (int t = 0; t < T && !code; t++) {
+      if (!stored && !reads.join()) return truncated();
+      if ((code = submit(group, t))) return code;
+      const bool have = t >= lag;
+      if (have && (code = collect())) return code;            // the GPU works on the frames after it meanwhile
+      if (!stored && t + 1 < T && (code = start_reads(group.slots(t + 1), &reads))) return code;
+      auto assemble_oldest = [&] { return have ? assemble(group, t - lag, out) : 0; };
+      code = stored ? put_chunk(cur_store ^ 1, next_frames, &next_put, assemble_oldest) : assemble_oldest();
+    }
+    for (int t = std::max(0, T - lag); t < T && !code; t++)
+      if (!(code = collect())) code = assemble(group, t, out);
+    if (code || !stored) return code;
+    return put_all(cur_store ^ 1, next_frames, &next_put);      // (a group of short GOPs has fewer batches than the next group has chunks)
+  }
+
+  // the group's frames in presentation order: each unit to the sink, its line to the stats
+  int write_group(const Group &group, const GroupOut &out) {
+    StatsTags tags;
+    tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0;
+    for (int s = 0; s < S; s++)
+      for (size_t t = 0; t < out[(size_t)s].size(); t++) {
+        const FrameOut &f = out[(size_t)s][t];
+        if (!sink.write(f.unit, t == 0, err)) return 1;
+        if (!plan.measure) continue;
+        stats += StatsFrameLine(summary.frames, t == 0, f, y.bd, tags, plan.analysed && group.cut[(size_t)group.index(s, (int)t)]) + '\n';
+        summary.add(f.q, y.bd);
+        total_bytes += (long long)f.unit.size();
+      }
+    return 0;
+  }
+
+  // The loop over GROUPS of S GOPs: a file is read in place, a stream one group ahead of the encoder (y4m.hpp).  Stored: the group's
+  // frames are in the current store before its batches run — the first group's are put here, nothing runs beside it; every later one was
+  // put into the other store while the group before ran (code_group) — and the stores swap per group.
+  int run_groups() {
+    for (int code;; g0 += S) {
+      long have = next_frames;
+      if (!plan.stored || have < 0) {
+        if ((have = y.prepare(g0 * G, (long)S * G, err)) < 0) return 1;
+        long put = 0;
+        if (plan.stored && (code = put_all(cur_store, have, &put))) return code;
+      }
+      if (have == 0) return 0;
+      total_frames += have;
+      Group group;
+      if ((code = lay_out(have, &group))) return code;
+      if (plan.stored) {
+        // the group after this one: prepared now (this group's frames are all in the store), put chunk by chunk beside the batches
+        if ((next_frames = y.prepare((g0 + S) * G, (long)S * G, err)) < 0) return 1;
+        next_put = 0;
+      }
+      GroupOut out((size_t)S);
+      if ((code = code_group(group, &out)) || (code = write_group(group, out))) return code;
+      if (plan.stored) cur_store ^= 1;
+    }
+  }
+
+  // the end of the job: the container, the rate-control report, the stats file and the quality gate
+  int finish() {
+    if (total_frames == 0) return fail(1, job.input + ": Invalid data found when processing input (no frames)");
+    if (!sink.close(err)) return 1;
     if (rc && rc_frames > 0) {
       const av1mi_rc_params &rp = rc->params();
-      const double fps = (double)y.fps_n / y.fps_d, px = (double)tw * th, want = 8.0 * rp.target_num / rp.target_den, got = 8.0 * rc_bytes / rc_frames;
+      const double fps = (double)y.fps_n / y.fps_d, px = (double)plan.tw * plan.th, want = 8.0 * rp.target_num / rp.target_den, got = 8.0 * rc_bytes / rc_frames;
       fprintf(stderr, "[av1mi] rate control: target %.0f bit/s (%.4f bit/pixel), achieved %.0f bit/s (%.4f bit/pixel) over %lld frames\n", want * fps, want / px,
               got * fps, got / px, rc_frames);
     }
-    if (measure) {
-      const av1mi::quality::Figures f = summary.figures(y.bd);
-      if (!job.stats_path.empty()) {
-        char line[512];
-        int n = snprintf(line, sizeof(line), "summary frames:%ld bytes:%lld", summary.frames, total_bytes);
-        n += av1mi::quality::format_figures(f, line + n, sizeof(line) - (size_t)n);
-        stats.append(line, (size_t)n); stats += '\n';
-        FILE *sf = fopen(job.stats_path.c_str(), "wb");
-        const bool ok = sf && fwrite(stats.data(), 1, stats.size(), sf) == stats.size();
-        if ((sf && fclose(sf)) || !ok) { *err = job.stats_path + ": could not write the stats file"; remove(job.output.c_str()); code = 1; goto done; }
-      }
-      if (job.min_psnr > 0 && f.psnr[0] < job.min_psnr) {      // the quality gate: the file is not good enough to stand in for its source
-        char why[160];
-        snprintf(why, sizeof(why), "quality gate: psnr_y %.6f dB below the bound %.6f dB", f.psnr[0], job.min_psnr);
-        *err = why;
-        remove(job.output.c_str());
-        code = 3; goto done;
-      }
+    if (!plan.measure) return 0;
+    if (!job.stats_path.empty()) {
+      stats += StatsSummaryLine(summary, total_bytes, y.bd) + '\n';
+      FILE *sf = fopen(job.stats_path.c_str(), "wb");
+      const bool ok = sf && fwrite(stats.data(), 1, stats.size(), sf) == stats.size();
+      if ((sf && fclose(sf)) || !ok) { remove(job.output.c_str()); return fail(1, job.stats_path + ": could not write the stats file"); }
     }
+    const av1mi::quality::Figures f = summary.figures(y.bd);
+    if (job.min_psnr > 0 && f.psnr[0] < job.min_psnr) {      // the quality gate: the file is not good enough to stand in for its source
+      char why[160];
+      snprintf(why, sizeof(why), "quality gate: psnr_y %.6f dB below the bound %.6f dB", f.psnr[0], job.min_psnr);
+      remove(job.output.c_str());
+      return fail(3, why);
+    }
+    return 0;
   }
-done:
-  sink.abort();
-  if (gop) av1mi_gop_close(gop);
-  y.close();
-  av1mi_close(ctx);
-  return code;
-#undef CHK
+};
+
+}  // namespace
+
+int RunBackend(const BackendJob &job, std::string *err) {
+  Run r(job, err);
+  if (av1mi_device_count() <= 0 || av1mi_open(job.device, &r.ctx) != AV1MI_OK) {
+    r.ctx = nullptr;
+    *err = "Error: no usable HIP device for the av1mi backend (device " + std::to_string(job.device) + ")";
+    return -1;
+  }
+  if (!r.y.open(job.input, err, job.to_420)) return 1;
+  int code;
+  if ((code = r.settle_window()) || (code = r.session_config()) || (code = r.open_session()) || (code = r.run_groups())) return code;
+  return r.finish();
 }
 
 }  // namespace av1mi_host

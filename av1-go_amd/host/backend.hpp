@@ -3,6 +3,7 @@
 #pragma once
 #include <string>
 #include "../../include/av1mi.h"
+#include "../csrc/quality.hpp"
 #include "mux.hpp"
 #include "transcode.hpp"
 
@@ -10,6 +11,47 @@ namespace av1mi_host {
 // 0 = OK and job.output written; > 0 = failed after starting (bad input, I/O, device error mid-run);
 // < 0 = could not run (no HIP device / library unusable).  *err carries the text.
 int RunBackend(const BackendJob &job, std::string *err);
+
+// What a job's session is opened with, as a pure function (SessionConfig): of the job, of the source's facts as plain values (the Y4M
+// header's, Y4mSource's fields of the same names; known_frames -1 = a stream) and of the settled crop window (w == 0: none).
+struct SourceFacts { int w, h, bd, src_bd, chroma, sar_n, sar_d, fps_n, fps_d, interlace, colour_range; long known_frames; };
+struct SessionPlan {
+  av1mi_gop_config cfg;
+  av1mi_source_layout fed;      // what the reader threads deliver, one segment's share of the pinned buffers (av1mi_gop_source_layout)
+  int tw, th;                   // the target: what a decoder outputs (cfg.width x cfg.height is it rounded up to 8)
+  bool square;                  // the target's pixels are square (else the track says at which shape to show them)
+  CropRect win;                 // the window the session cuts: the settled one, or the chain's crop=
+  av1mi_colour colour;          // the stream's colour record
+  // packed: the frames cross PCIe at 10 bits per sample; stored: the job runs through the frame store; analysed: its groups are laid out
+  // on scene cuts; grainy: film grain parameters in every frame header; measure: the session returns quality records
+  bool packed, stored, analysed, grainy, measure;
+};
+// -av1mi_crop W:H:X:Y against a w x h picture: 0 and *win, or 1 and the text
+int ExplicitWindow(const BackendJob &job, int w, int h, CropRect *win, std::string *err);
+// 0 and *plan, or the exit code 1 and "Invalid argument: ..." in *err.  Needs no device, no session and no sink.
+int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect &window, SessionPlan *plan, std::string *err);
+
+// one coded frame of a group: its temporal unit and what the stats file says about it (q: the session's records where the job measures;
+// grain: the luma scaling at mid grey where it denoises)
+struct FrameOut { std::vector<uint8_t> unit; av1mi_quality q[3]; int base_q_idx; int grain; };
+// the layout of a group of frames over the session's segments: GOP s holds frames start[s] .. start[s] + len[s] - 1 of the group; cut
+// (analysed jobs) flags the frames the scene analysis found
+struct Group {
+  std::vector<int32_t> start, len;
+  std::vector<uint8_t> cut;
+  long frames = 0;
+  int T() const { int t = 0; for (int32_t l : len) t = l > t ? l : t; return t; }      // batches: the longest GOP
+  bool exists(int s, int t) const { return t < len[(size_t)s]; }
+  int32_t index(int s, int t) const { return exists(s, t) ? start[(size_t)s] + t : -1; }      // -1: a flat slot, its output dropped
+  std::vector<int32_t> slots(int t) const { std::vector<int32_t> v(len.size()); for (size_t s = 0; s < v.size(); s++) v[s] = index((int)s, t); return v; }      // batch t: per segment
+};
+// The stats file: the line of frame n in presentation order, and the summary line.  tags: what a line says beyond the
+// figures — the window and the colour record (frame 0 only; w == 0 / null = none), q: (a job with a target), grain: (a job that denoises)
+struct StatsTags { CropRect win; const av1mi_colour *colour = nullptr; bool q = false, grain = false; };
+std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, const StatsTags &tags, bool cut);
+std::string StatsSummaryLine(const av1mi::quality::Summary &sum, long long bytes, int bit_depth);
+
+// session_unit.cpp:
 // the bitstream writer's frame description for segment `seg` of a collected session batch (pointers into the batch)
 // visible_*: the true frame size when width x height is it rounded up to 8 (0 = the coded size)
 void DescribeSessionFrame(const av1mi_gop_frame &fr, int seg, int width, int height, int bit_depth, SessionFrameDesc *d, int visible_width = 0,

@@ -11,6 +11,15 @@
 
 using namespace av1mi_host;
 
+// the test hooks' list convention: strings joined with '\n' (an argv, a list of paths)
+static std::vector<std::string> split_lines(const std::string &s) {
+  std::vector<std::string> a;
+  size_t p = 0, q;
+  while ((q = s.find('\n', p)) != std::string::npos) { a.push_back(s.substr(p, q - p)); p = q + 1; }
+  a.push_back(s.substr(p));
+  return a;
+}
+
 extern "C" {
 int av1mi_host_determine_quality(int height) { return DetermineQuality(height); }
 int av1mi_host_check_size_gate(long long orig, long long neu, double ratio) { return CheckSizeGate(orig, neu, ratio) ? 1 : 0; }
@@ -39,9 +48,7 @@ int av1mi_host_job_args(const char *in, const char *out, int height, int webrip,
 // ParseBackendJob's view of the rate options for an argv joined with '\n': 0 and out = { bits per second, millionths of a bit per pixel,
 // qmin, qmax, quality }, or -1 with the text in err
 int av1mi_host_parse_rate_options(const char *joined, long long *out, char *err, int cap) {
-  std::vector<std::string> a; std::string s = joined; size_t p = 0, q;
-  while ((q = s.find('\n', p)) != std::string::npos) { a.push_back(s.substr(p, q - p)); p = q + 1; }
-  a.push_back(s.substr(p));
+  const std::vector<std::string> a = split_lines(joined);
   BackendJob job; std::string e;
   const bool ok = ParseBackendJob(a, &job, &e);
   strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
@@ -87,9 +94,7 @@ int av1mi_host_y4m_layout(const char *path, int any_layout, int *geometry, unsig
 }
 // ParseBackendJob's view of the conversion to 4:2:0 (BackendJob::to_420) for an argv joined with '\n': 1 / 0, or -1 with the text in err
 int av1mi_host_parse_format_option(const char *joined, char *err, int cap) {
-  std::vector<std::string> a; std::string s = joined; size_t p = 0, q;
-  while ((q = s.find('\n', p)) != std::string::npos) { a.push_back(s.substr(p, q - p)); p = q + 1; }
-  a.push_back(s.substr(p));
+  const std::vector<std::string> a = split_lines(joined);
   BackendJob job; std::string e;
   const bool ok = ParseBackendJob(a, &job, &e);
   strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
@@ -113,9 +118,7 @@ int av1mi_host_y4m_interlace(const char *path) {
 // ParseBackendJob's view of -av1mi_deinterlace and the chain's deinterlacers for an argv joined with '\n': BackendJob::deinterlace (0 off,
 // 1 auto, 2 tff, 3 bff), or -1 with the text in err
 int av1mi_host_parse_deinterlace_option(const char *joined, char *err, int cap) {
-  std::vector<std::string> a; std::string s = joined; size_t p = 0, q;
-  while ((q = s.find('\n', p)) != std::string::npos) { a.push_back(s.substr(p, q - p)); p = q + 1; }
-  a.push_back(s.substr(p));
+  const std::vector<std::string> a = split_lines(joined);
   BackendJob job; std::string e;
   const bool ok = ParseBackendJob(a, &job, &e);
   strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
@@ -186,9 +189,7 @@ int av1mi_host_mux_units_colour(const char *path, int w, int h, int bd, int fps_
 // ParseBackendJob's view of the colour and tone mapping options for an argv joined with '\n': 0, *out = the record JobColour gives with the Y4M range
 // y4m_range, tone[2] = { tonemap, tonemap_peak }; or -1 with the text in err
 int av1mi_host_parse_colour_options(const char *joined, int y4m_range, av1mi_colour *out, int *tone, char *err, int cap) {
-  std::vector<std::string> a; std::string s = joined; size_t p = 0, q;
-  while ((q = s.find('\n', p)) != std::string::npos) { a.push_back(s.substr(p, q - p)); p = q + 1; }
-  a.push_back(s.substr(p));
+  const std::vector<std::string> a = split_lines(joined);
   BackendJob job; std::string e;
   const bool ok = ParseBackendJob(a, &job, &e);
   strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
@@ -216,9 +217,7 @@ int av1mi_run_transcode(int argc, const char *const *argv, char *err, size_t err
 }
 // runs the replacement RunTranscode on an argv joined with '\n'; error text into buf; returns the exit code
 int av1mi_host_run_transcode(const char *joined, char *buf, int cap) {
-  std::vector<std::string> a; std::string s = joined; size_t p = 0, q;
-  while ((q = s.find('\n', p)) != std::string::npos) { a.push_back(s.substr(p, q - p)); p = q + 1; }
-  a.push_back(s.substr(p));
+  const std::vector<std::string> a = split_lines(joined);
   const RunResult rr = RunTranscode("av1mi", a);
   strncpy(buf, rr.err.c_str(), cap - 1); buf[cap - 1] = 0;
   return rr.exitCode;
@@ -258,9 +257,7 @@ double av1mi_quality_ssim(const av1mi_quality *q) { return q->ssim_sum / (double
 // (q: n * 3 records; bytes: n temporal unit sizes); returns the line's length
 void av1mi_host_quality_constants(int bit_depth, long long *c1, long long *c2) { *c1 = av1mi::quality::ssim_c1(bit_depth); *c2 = av1mi::quality::ssim_c2(bit_depth); }
 int av1mi_host_parse_quality_options(const char *joined, char *stats_path, int cap, double *min_psnr, char *err, int errcap) {
-  std::vector<std::string> a; std::string s = joined; size_t p = 0, q;
-  while ((q = s.find('\n', p)) != std::string::npos) { a.push_back(s.substr(p, q - p)); p = q + 1; }
-  a.push_back(s.substr(p));
+  const std::vector<std::string> a = split_lines(joined);
   BackendJob job; std::string e;
   const bool ok = ParseBackendJob(a, &job, &e);
   strncpy(stats_path, job.stats_path.c_str(), cap - 1); stats_path[cap - 1] = 0;
@@ -272,9 +269,31 @@ int av1mi_host_quality_summary_line(const av1mi_quality *q, const long long *byt
   av1mi::quality::Summary sum;
   long long total = 0;
   for (int i = 0; i < n; i++) { sum.add(q + 3 * i, bit_depth); total += bytes[i]; }
-  int k = snprintf(buf, cap, "summary frames:%ld bytes:%lld", sum.frames, total);
-  if (k < 0 || k >= cap) return -1;
-  return k + av1mi::quality::format_figures(sum.figures(bit_depth), buf + k, (size_t)(cap - k));
+  const std::string line = StatsSummaryLine(sum, total, bit_depth);
+  if ((long long)line.size() >= cap) return -1;
+  memcpy(buf, line.c_str(), line.size() + 1);
+  return (int)line.size();
+}
+// SessionConfig (backend.hpp) for an argv joined with '\n' whose -i names a Y4M file (only its header is read): what RunBackend opens the
+// session with, found without a device.  auto_win (may be null) = x, y, width, height standing for what -av1mi_crop auto found; without it
+// the window is -av1mi_crop W:H:X:Y's, or none.  0 and *cfg, target[3] = the target's width, height and whether its pixels are square,
+// switches[5] = packed, stored, analysed, grainy, measure; or the exit code 1 with the text in err
+int av1mi_host_session_config(const char *joined, const int *auto_win, av1mi_gop_config *cfg, int *target, int *switches, char *err, int cap) {
+  BackendJob job; std::string e;
+  Y4mSource y;
+  CropRect win;
+  SessionPlan plan;
+  int code = ParseBackendJob(split_lines(joined), &job, &e) && y.open(job.input, &e, job.to_420) ? 0 : 1;
+  if (!code && auto_win) { win.x = auto_win[0]; win.y = auto_win[1]; win.w = auto_win[2]; win.h = auto_win[3]; }
+  else if (!code && job.crop_mode == 2) code = ExplicitWindow(job, y.w, y.h, &win, &e);
+  if (!code) code = SessionConfig(job, { y.w, y.h, y.bd, y.src_bd, y.chroma, y.sar_n, y.sar_d, y.fps_n, y.fps_d, y.interlace, y.colour_range, y.known_frames() }, win, &plan, &e);
+  strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
+  if (code) return code;
+  *cfg = plan.cfg;
+  target[0] = plan.tw; target[1] = plan.th; target[2] = plan.square;
+  const bool sw[5] = { plan.packed, plan.stored, plan.analysed, plan.grainy, plan.measure };
+  for (int i = 0; i < 5; i++) switches[i] = sw[i];
+  return 0;
 }
 // AV1 bitstream writer (av1_bitstream.hpp): one temporal unit (delimiter [+ sequence header] + frame) for a frame description.
 // Returns the size in bytes (copied into out when it fits in cap), -1 on a description the writer cannot code (text in err).
@@ -288,7 +307,7 @@ long long av1mi_obu_write_temporal_unit(const av1mi_obu_frame *f, int with_seque
   if ((long long)b.size() <= cap && out) memcpy(out, b.data(), b.size());
   return (long long)b.size();
 }
-// One segment of a collected session batch -> its temporal unit (include/av1mi_host.h; backend.cpp SessionTemporalUnit)
+// One segment of a collected session batch -> its temporal unit (include/av1mi_host.h; session_unit.cpp SessionTemporalUnit)
 long long av1mi_session_temporal_unit(const av1mi_gop_frame *fr, int seg, int width, int height, int bit_depth, int visible_width, int visible_height,
                                       int with_sequence_header, int threads, uint8_t *out, long long cap, char *err, int errcap) {
   std::vector<uint8_t> b; std::string e;
@@ -412,15 +431,13 @@ int av1mi_host_mux_units_display(const char *path, int w, int h, int bd, int fps
 }
 // RunJobPool over `n` source files joined with '\n'; statuses joined with '\n' into buf; returns the number of successes
 int av1mi_host_job_pool(const char *sources, int workers, int ngpus, double ratio, const char *state_dir, char *buf, int cap) {
-  std::vector<Job> jobs; std::string s = sources; size_t p = 0, q;
-  auto add = [&](const std::string &path) {
+  std::vector<Job> jobs;
+  for (const std::string &path : split_lines(sources)) {
     Job j; j.ID = "pool" + std::to_string(jobs.size()); j.SourcePath = path;
     FILE *f = fopen(path.c_str(), "rb");
     if (f) { fseek(f, 0, SEEK_END); j.OriginalSize = ftell(f); fclose(f); }
     jobs.push_back(j);
-  };
-  while ((q = s.find('\n', p)) != std::string::npos) { add(s.substr(p, q - p)); p = q + 1; }
-  add(s.substr(p));
+  }
   TranscodeConfig cfg; cfg.MaxSizeRatio = ratio; cfg.JobStateDir = state_dir ? state_dir : ""; cfg.StableWaitSeconds = 0;
   ProbeResult pr; pr.HasVideo = true; pr.has_video_stream = true; pr.VideoStream.Height = 720;
   std::vector<std::string> errs;

@@ -15,7 +15,7 @@
 
 namespace av1mi_host {
 
-// a frame description whose restoration-unit arrays are owned here (backend.cpp DescribeSessionFrame)
+// a frame description whose restoration-unit arrays are owned here (session_unit.cpp DescribeSessionFrame)
 struct SessionFrameDesc { av1mi_obu_frame f; std::vector<int8_t> lr_y, lr_uv; };
 
 // sequential reader of a Matroska file's tracks and blocks (side files of add_side_file; the file is read as the output advances,
