@@ -20,6 +20,7 @@
 #include "av1_ops_cdfs.hpp"
 #include "av1_ops8.hpp"
 #include "av1mi_internal.hpp"
+#include "chains_rank.hpp"
 
 namespace av1mi {
 using namespace av1ops;
@@ -155,12 +156,27 @@ __global__ __launch_bounds__(64) void k_av1_tokens32(Av1EntLaunch L) {
 // tile's own slots differ in length by three orders of magnitude.  Small alphabets keep the CDF in registers, large ones in LDS.
 // (Measured: a workgroup that walks several slots one after the other is slower — fewer, longer waves; about half of this
 // kernel's time is the 4-byte scatter of the tuples into the lists.)
-__global__ __launch_bounds__(64) void k_av1_chains(Av1EntLaunch L, int ntiles_all, int ngroups) {
+//
+// RESIDENCY is a launch parameter.  The 64 lists of a group are completed word by word by all the group's slots, and the traffic stays
+// near one read and one write per word only while their lines (about 1 MB per group, grouped entries included) stay in the XCD's 4 MB
+// L2.  Left alone, an XCD holds 1 024 of these waves: the short slots retire at once, so the resident set fills with the long slots of
+// many groups.  The launch asks for dynamic LDS nobody uses, sized so that `waves` workgroups fit a CU (nominally: the hardware rounds
+// an allocation up to its granule, which may make it one fewer).  Measured at 4K, q index 128 (DESIGN 5.0-quater,
+// profiles/chains_l2_parent_vs_change.json): 2.5 GB per launch uncapped, 1.8 GB at 12 waves, 0.95 GB at 4 — but below 12 the waves
+// that remain no longer hide the chains' latency beside the tokenizer and the range coder of the neighbouring batches, and the
+// session as a whole is fastest at 12.
+enum { kChainsInter = 0, kChainsKey8 = 1, kChainsKey32 = 2 };      // the launch flavours: each has its slot table and its rank
+constexpr int kChainsStaticLds = 64 * 16 * 2, kCuLds = 160 << 10, kChainsWavesPerCU = 12;
+static unsigned chains_dynamic_lds(int waves) { return waves > 0 && kCuLds / waves > kChainsStaticLds ? (unsigned)(kCuLds / waves - kChainsStaticLds) : 0u; }
+
+__global__ __launch_bounds__(64) void k_av1_chains(Av1EntLaunch L, int ntiles_all, int ngroups, int flavour) {
   // workgroups are dealt to the eight XCDs in turn (id % 8), each with its own L2: all slots of a tile group go to ONE XCD, one
   // after the other, so the 64 lists the group's chains complete word by word stay in that L2 as long as possible
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3, nslots = L.nslots;
-  const int g = (j / nslots) * 8 + xcd, sl = j - (j / nslots) * nslots, lane = threadIdx.x, t = g * 64 + lane;
+  const int g = (j / nslots) * 8 + xcd, k = j - (j / nslots) * nslots, lane = threadIdx.x, t = g * 64 + lane;
   if (g >= ngroups) return;
+  // the group's slots longest expected chain first (chains_rank.hpp)
+  const int sl = (flavour == kChainsInter ? kChainsRankInter : flavour == kChainsKey8 ? kChainsRankKey8 : kChainsRankKey32)[k];
   __shared__ __attribute__((aligned(16))) uint16_t s_big[64 * 16];
   const int n = L.tab.nsym[sl], off = L.tab.off[sl];
   int cnt = 0, base = 0;
@@ -338,10 +354,12 @@ hipError_t launch_av1_front(av1mi_ctx *ctx, const Av1EntLaunch &L, hipStream_t s
   t = ctx_prof_begin(ctx, AV1MI_K_ENTROPY_CHAINS, s);
   Av1EntLaunch C = L;
   C.nslots = L.fv.key ? S_KEY_END : S_INTER_END; C.band = L.sb_rows32 ? 2 : 0;
-  if (L.sb_rows32 < L.sbr_n) hipLaunchKernelGGL(k_av1_chains, dim3((unsigned)(((ngroups + 7) / 8) * 8 * C.nslots)), dim3(64), 0, s, C, ntiles_all, ngroups);
+  const unsigned lds = chains_dynamic_lds(kChainsWavesPerCU);
+  if (L.sb_rows32 < L.sbr_n)
+    hipLaunchKernelGGL(k_av1_chains, dim3((unsigned)(((ngroups + 7) / 8) * 8 * C.nslots)), dim3(64), lds, s, C, ntiles_all, ngroups, L.fv.key ? kChainsKey8 : kChainsInter);
   if (L.sb_rows32) {       // the 32x32 band's tiles: their slot table and default CDFs
     C.nslots = K_END; C.band = 1; C.tab = L.tab32; C.cdf_image = L.cdf_image32;
-    hipLaunchKernelGGL(k_av1_chains, dim3((unsigned)(((ngroups + 7) / 8) * 8 * C.nslots)), dim3(64), 0, s, C, ntiles_all, ngroups);
+    hipLaunchKernelGGL(k_av1_chains, dim3((unsigned)(((ngroups + 7) / 8) * 8 * C.nslots)), dim3(64), lds, s, C, ntiles_all, ngroups, kChainsKey32);
   }
   ctx_prof_end(ctx, t, s);
   return hipGetLastError();
