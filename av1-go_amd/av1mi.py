@@ -848,32 +848,51 @@ class Context:
             for b in list(bufs.values()) + q + [cen]:
                 b.free()
 
-    def inter_encode_arrays(self, src, ref, bd, qindex, search_range=8, coarse_range=0):
-        """tests: src / ref = (Y, U, V) with arrays [frames, h, w]; returns dict like the oracle's"""
+    def inter_encode_arrays(self, src, ref, bd, qindex, search_range=8, coarse_range=0, stride_y=None, stride_uv=None):
+        """tests: src / ref = (Y, U, V) with arrays [frames, h, w]; returns dict like the oracle's.  stride_y / stride_uv (samples;
+        default: the plane widths) lay the rows of every plane that far apart on the device: source and reference are uploaded into
+        padded rows, the reconstruction buffers are pre-filled with a sentinel (0xA5 bytes), rec_* are the w-wide views and
+        rec_pad_* the padding columns [frames, rows, stride - width] as the kernels left them (absent for a compact plane)."""
         dt = np.uint8 if bd == 8 else np.uint16
         S = [np.ascontiguousarray(a, dt) for a in src]
         R = [np.ascontiguousarray(a, dt) for a in ref]
         nf, h, w = S[0].shape
         nb = (h // 8) * (w // 8)
+        strides = [w if stride_y is None else int(stride_y)] + [w // 2 if stride_uv is None else int(stride_uv)] * 2
+
+        def padded(a, st):       # rows st samples apart; an impossible stride goes to the library as it is, which refuses the job
+            if st <= a.shape[2]:
+                return a
+            out = np.zeros(a.shape[:2] + (st,), dt)
+            out[:, :, :a.shape[2]] = a
+            return out
+
         bufs = {}
-        for i, p in enumerate("yuv"):
-            bufs["src_" + p], bufs["ref_" + p] = self.to_device(S[i]), self.to_device(R[i])
-            bufs["rec_" + p] = self.alloc(S[i].nbytes)
-            bufs["lev_" + p] = self.alloc(S[i].size * 2)
-        bufs["mvs"], bufs["skip"] = self.alloc(nf * nb * 4), self.alloc(nf * nb)
-        job = InterJob(w, h, bd, nf, qindex, search_range, w, w // 2)
-        job.coarse_range = coarse_range
-        for k, b in bufs.items():
-            setattr(job, "d_" + k, b.ptr)
-        self.inter_encode(job)
-        out = dict(mvs=bufs["mvs"].download((nf, nb, 2), np.int16), skip=bufs["skip"].download((nf, nb), np.uint8))
-        for i, p in enumerate("yuv"):
-            bs = 8 if i == 0 else 4
-            out["rec_" + p] = bufs["rec_" + p].download(S[i].shape, dt)
-            out["lev_" + p] = bufs["lev_" + p].download((nf, nb, bs, bs), np.int16)
-        for b in bufs.values():
-            b.free()
-        return out
+        try:
+            for i, p in enumerate("yuv"):
+                st = max(strides[i], S[i].shape[2])
+                bufs["src_" + p], bufs["ref_" + p] = self.to_device(padded(S[i], st)), self.to_device(padded(R[i], st))
+                bufs["rec_" + p] = self.alloc(nf * S[i].shape[1] * st * dt().itemsize)
+                self.memset(bufs["rec_" + p], 0xA5, bufs["rec_" + p].nbytes)
+                bufs["lev_" + p] = self.alloc(S[i].size * 2)
+            bufs["mvs"], bufs["skip"] = self.alloc(nf * nb * 4), self.alloc(nf * nb)
+            job = InterJob(w, h, bd, nf, qindex, search_range, strides[0], strides[1])
+            job.coarse_range = coarse_range
+            for k, b in bufs.items():
+                setattr(job, "d_" + k, b.ptr)
+            self.inter_encode(job)
+            out = dict(mvs=bufs["mvs"].download((nf, nb, 2), np.int16), skip=bufs["skip"].download((nf, nb), np.uint8))
+            for i, p in enumerate("yuv"):
+                bs = 8 if i == 0 else 4
+                rec = bufs["rec_" + p].download((nf, S[i].shape[1], strides[i]), dt)
+                out["rec_" + p] = np.ascontiguousarray(rec[:, :, :S[i].shape[2]])
+                if strides[i] > S[i].shape[2]:
+                    out["rec_pad_" + p] = np.ascontiguousarray(rec[:, :, S[i].shape[2]:])
+                out["lev_" + p] = bufs["lev_" + p].download((nf, nb, bs, bs), np.int16)
+            return out
+        finally:
+            for b in bufs.values():
+                b.free()
 
     # ---- host-pointer single-block forms
     def inv_txfm2d_add(self, coef, pred, tx_size, tx_type, bd):
