@@ -13,8 +13,10 @@
 //                  range coder needs.  The serial dependency of a tile drops from all its symbols (4000-8000) to its longest
 //                  chain (700-1300), and the chains of ALL tiles run side by side
 //   k_av1_code     ONE LANE PER TILE: the serial range coder over the finished list.  No CDFs: its state is five registers.
-//   k_av1_scan / k_av1_gather   tile payloads -> one contiguous buffer in tile order (the host adds the frame header and the
-//                  tile-size fields: they depend on the largest tile, host/av1_bitstream.cpp frame_obu_from_tiles)
+//                  Each workgroup also writes the sum of its 64 tiles' payload sizes.
+//   k_av1_gather   tile payloads -> one contiguous buffer in tile order (the host adds the frame header and the tile-size fields:
+//                  they depend on the largest tile, host/av1_bitstream.cpp frame_obu_from_tiles).  A tile's workgroup finds its
+//                  offset from the group sums; the last tile's writes the total and the status, and the caller's pinned mirrors
 #include <string.h>
 #include <vector>
 #include "av1_ops_cdfs.hpp"
@@ -43,7 +45,9 @@ struct Av1EntLaunch {
   uint32_t *nops;               // per tile
   uint8_t *slots; uint32_t slot_cap;   // per tile payload slot
   uint32_t *tile_size;          // per tile: payload bytes (0 = overflow)
-  uint64_t *tile_off;           // per tile + 1: exclusive scan of the sizes
+  uint64_t *group_sum;          // per workgroup of k_av1_code (64 tiles): the sum of its tiles' sizes
+  uint64_t *total;              // the job's d_total: [0] all tiles' bytes; the status is the word behind it
+  Av1EntMirrors mir;            // optional pinned mirrors of sizes, total + status and lr_on_frame (av1mi_internal.hpp)
   uint32_t *status;             // bit 0: a tile's op list overflowed, bit 1: a payload slot overflowed, bit 2: out_cap too small
   uint8_t *out; uint64_t out_cap;
   const uint16_t *cdf_image; int cdf_words;   // default slot image of this frame type / q category
@@ -297,39 +301,47 @@ __global__ __launch_bounds__(64) void k_av1_code(Av1EntLaunch L, int ntiles_all)
       }
     }
   }
-  if (!live) return;
-  int sz = n ? c.finish() : -1;          // n == 0: the list overflowed (k_av1_tokens), nothing to code
-  if (sz < 0) { if (n) atomicOr(L.status, 2u); sz = 0; }
-  L.tile_size[t] = (uint32_t)sz;
+  int sz = 0;
+  if (live) {
+    sz = n ? c.finish() : -1;          // n == 0: the list overflowed (k_av1_tokens), nothing to code
+    if (sz < 0) { if (n) atomicOr(L.status, 2u); sz = 0; }
+    L.tile_size[t] = (uint32_t)sz;
+  }
+  // the group's bytes (64 x slot_cap fits 32 bits), for the gather's offsets; a lane without a tile adds nothing
+  unsigned sum = (unsigned)sz;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) sum += __shfl_down(sum, d, 64);
+  if (lane == 0) L.group_sum[blockIdx.x] = sum;
 }
 
-// exclusive scan of all tile sizes (one workgroup; a batch has at most a few 10^4 tiles)
-__global__ __launch_bounds__(1024) void k_av1_scan(Av1EntLaunch L, int ntiles_all) {
-  __shared__ uint64_t part[1024];
-  const int tid = threadIdx.x, per = (ntiles_all + 1023) / 1024, i0 = tid * per, i1 = min(i0 + per, ntiles_all);
-  uint64_t s = 0;
-  for (int i = i0; i < i1; i++) s += L.tile_size[i];
-  part[tid] = s;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    const uint64_t y = tid >= d ? part[tid - d] : 0;
-    __syncthreads();
-    part[tid] += y;
-    __syncthreads();
-  }
-  uint64_t run = part[tid] - s;
-  for (int i = i0; i < i1; i++) { L.tile_off[i] = run; run += L.tile_size[i]; }
-  if (tid == 1023) {
-    L.tile_off[ntiles_all] = part[1023];
-    if (part[1023] > L.out_cap) atomicOr(L.status, 4u);
-  }
-}
 // one workgroup per tile; `out` may be pinned host memory (the GOP session hands the payloads straight to the host this way):
-// bytes up to the first 16-byte boundary of the destination, then aligned 16-byte stores, then the tail
-__global__ __launch_bounds__(64) void k_av1_gather(Av1EntLaunch L) {
-  const int t = blockIdx.x;
+// bytes up to the first 16-byte boundary of the destination, then aligned 16-byte stores, then the tail.
+// The tile's offset is the bytes of all tiles before it: the sums of the groups below its own (k_av1_code) plus the sizes of its own
+// group's tiles below it — at most groups / 64 + 1 coalesced loads per lane and one wave reduction, in 64 bits.  The last tile's
+// workgroup therefore knows the total: it sets status bit 2 where that exceeds out_cap (bits 0 and 1 were set by kernels that have
+// finished), and writes total and status to the job's d_total.  Where the caller gave pinned mirrors (Av1EntMirrors) every workgroup
+// stores its tile's size there and the last one total, status and the restoration flags: plain stores, ordered for the host by the
+// event behind this launch like the payloads themselves.
+__global__ __launch_bounds__(64) void k_av1_gather(Av1EntLaunch L, int ntiles_all) {
+  const int t = blockIdx.x, lane = threadIdx.x, g = t >> 6;
+  uint64_t off = 0;
+  for (int i = lane; i < g; i += 64) off += L.group_sum[i];
+  if (g * 64 + lane < t) off += L.tile_size[g * 64 + lane];
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) off += __shfl_xor(off, d, 64);
   const uint32_t n = L.tile_size[t];
-  const uint64_t off = L.tile_off[t];
+  if (lane == 0 && L.mir.h_tile_size) L.mir.h_tile_size[t] = n;
+  if (t == ntiles_all - 1) {
+    if (lane == 0) {
+      const uint64_t total = off + n;
+      uint32_t status = *L.status;
+      if (total > L.out_cap) status |= 4u;
+      L.total[0] = total; *L.status = status;
+      if (L.mir.h_total) { L.mir.h_total[0] = total; L.mir.h_total[1] = status; }
+    }
+    if (L.mir.h_lr_on && L.lr_on_frame)
+      for (uint32_t i = lane; i < L.mir.lr_on_bytes; i += 64) L.mir.h_lr_on[i] = L.lr_on_frame[i];
+  }
   if (off + n > L.out_cap) return;
   const uint8_t *src = L.slots + (size_t)t * L.slot_cap;
   uint8_t *dst = L.out + off;
@@ -370,8 +382,7 @@ hipError_t launch_av1_back(av1mi_ctx *ctx, const Av1EntLaunch &L, hipStream_t s)
   hipLaunchKernelGGL(k_av1_code, dim3((unsigned)((ntiles_all + 63) / 64)), dim3(64), 0, s, L, ntiles_all);
   ctx_prof_end(ctx, t, s);
   t = ctx_prof_begin(ctx, AV1MI_K_ENTROPY_PACK, s);
-  hipLaunchKernelGGL(k_av1_scan, dim3(1), dim3(1024), 0, s, L, ntiles_all);
-  hipLaunchKernelGGL(k_av1_gather, dim3((unsigned)ntiles_all), dim3(64), 0, s, L);
+  hipLaunchKernelGGL(k_av1_gather, dim3((unsigned)ntiles_all), dim3(64), 0, s, L, ntiles_all);
   ctx_prof_end(ctx, t, s);
   return hipGetLastError();
 }
@@ -380,14 +391,13 @@ hipError_t launch_av1_back(av1mi_ctx *ctx, const Av1EntLaunch &L, hipStream_t s)
 
 // ------------------------------------------------------------------------------------------------ C ABI
 struct av1mi_av1ent_state {      // per-context scratch of the coder, grown on demand (owned through av1mi_av1_entropy_release)
-  void *info = nullptr, *ops[2] = { nullptr, nullptr }, *nops[2] = { nullptr, nullptr }, *grouped = nullptr, *grouped_off = nullptr, *slot_tb = nullptr, *rec = nullptr, *slots = nullptr, *tile_off = nullptr, *status = nullptr;
-  size_t info_b = 0, ops_b[2] = { 0, 0 }, nops_b[2] = { 0, 0 }, grouped_b = 0, grouped_off_b = 0, slot_tb_b = 0, rec_b = 0, slots_b = 0, off_b = 0;
+  void *info = nullptr, *ops[2] = { nullptr, nullptr }, *nops[2] = { nullptr, nullptr }, *grouped = nullptr, *grouped_off = nullptr, *slot_tb = nullptr, *rec = nullptr, *slots = nullptr, *group_sum = nullptr, *status = nullptr;
+  size_t info_b = 0, ops_b[2] = { 0, 0 }, nops_b[2] = { 0, 0 }, grouped_b = 0, grouped_off_b = 0, slot_tb_b = 0, rec_b = 0, slots_b = 0, group_sum_b = 0;
   // the lists (ops; nops with the lists' offsets behind them) exist twice: job k uses set k & 1, so the front half of job k + 1 may run beside the back half of job k
   hipEvent_t lists_ready[2] = { nullptr, nullptr }, lists_free[2] = { nullptr, nullptr };
   bool free_recorded[2] = { false, false };
   unsigned long jobs = 0;
-  av1mi::Av1EntLaunch pending[2];             // a job whose back half (range coder, scan, gather) is still to be launched (av1_entropy_back)
-  uint64_t *pending_total[2] = { nullptr, nullptr };
+  av1mi::Av1EntLaunch pending[2];             // a job whose back half (range coder, gather) is still to be launched (av1_entropy_back)
   bool pending_valid[2] = { false, false };
   size_t last_tiles = 0;          // tiles of the most recent job (av1mi_av1_entropy_last_list_words)
   uint16_t *d_image[2][4] = {};   // [key][qcat] default CDF images
@@ -477,15 +487,15 @@ int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hip
       (rc = grow(ctx, &st->grouped, &st->grouped_b, nt * L.grouped_cap * sizeof(uint32_t))) || (rc = grow(ctx, &st->grouped_off, &st->grouped_off_b, nt * 4)) ||
       (rc = grow(ctx, &st->slot_tb, &st->slot_tb_b, kCursorBytes + nt * av1ops::S_MAX * 4)) ||
       (rc = grow(ctx, &st->rec, &st->rec_b, (size_t)(L.sbr_n - L.sb_rows32) * L.sbc_n * j->nframes * av1ops::kBlocksPerTile * av1ops::kBlockRecords * sizeof(uint16_t))) ||
-      (rc = grow(ctx, &st->slots, &st->slots_b, nt * L.slot_cap)) || (rc = grow(ctx, &st->tile_off, &st->off_b, (nt + 1) * 8)))
+      (rc = grow(ctx, &st->slots, &st->slots_b, nt * L.slot_cap)) || (rc = grow(ctx, &st->group_sum, &st->group_sum_b, ((nt + 63) / 64) * 8)))
     return rc;
   L.info = (av1ops::BlockInfo *)st->info; L.ops = (av1ops::op_t *)st->ops[par]; L.nops = (uint32_t *)st->nops[par]; L.grouped = (uint32_t *)st->grouped;
   L.list_off = L.nops + nt; L.grouped_off = (uint32_t *)st->grouped_off;
   L.cursors = (uint32_t *)st->slot_tb;        // the pools' cursors: a line of their own in front of the slot tables
   L.slot_total = (uint16_t *)((uint8_t *)st->slot_tb + kCursorBytes); L.slot_base = L.slot_total + nt * av1ops::S_MAX; L.rec = (uint16_t *)st->rec; L.slots = (uint8_t *)st->slots;
-  L.tile_off = (uint64_t *)st->tile_off;
+  L.group_sum = (uint64_t *)st->group_sum;
   L.tile_size = j->d_tile_size; L.out = j->d_out; L.out_cap = j->out_cap;
-  L.status = (uint32_t *)(j->d_total + 1);
+  L.total = j->d_total; L.status = (uint32_t *)(j->d_total + 1);
   L.cdf_image = st->d_image[key][qcat]; L.cdf_words = st->image_words[key]; L.tab = st->tab[key];
   L.lr_on_frame = j->d_lr_on;
 #define E_HIP(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return av1mi::ctx_fail(ctx, AV1MI_E_DEVICE, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
@@ -495,32 +505,32 @@ int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hip
   E_HIP(hipMemsetAsync(L.cursors, 0, kCursorBytes, front));
   E_HIP(av1mi::launch_av1_front(ctx, L, front));
   E_HIP(hipEventRecord(st->lists_ready[par], front));
-  st->pending[par] = L; st->pending_total[par] = j->d_total; st->pending_valid[par] = true;
+  st->pending[par] = L; st->pending_valid[par] = true;
   *ticket = par;
   return AV1MI_OK;
 }
 
-// the back half of the job `ticket` names (av1_entropy_front): the serial range coder, the scan of the tile sizes, the gather
-int av1mi::av1_entropy_back(av1mi_ctx *ctx, int ticket, hipStream_t back) {
+// the back half of the job `ticket` names (av1_entropy_front): the serial range coder and the gather, which also delivers sizes,
+// total and status (to the job's device arrays, and to the pinned mirrors where the caller gives them)
+int av1mi::av1_entropy_back(av1mi_ctx *ctx, int ticket, hipStream_t back, const Av1EntMirrors *mirrors) {
   if (!ctx || ticket < 0 || ticket > 1) return AV1MI_E_INVAL;
   av1mi_av1ent_state *st = av1mi::ctx_av1ent(ctx);
   if (!st || !st->pending_valid[ticket]) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "no entropy job pending under this ticket");
-  const av1mi::Av1EntLaunch &L = st->pending[ticket];
-  const size_t nt = (size_t)L.sbr_n * L.sbc_n * L.nframes;
+  av1mi::Av1EntLaunch L = st->pending[ticket];
+  if (mirrors) L.mir = *mirrors;
   E_HIP(hipStreamWaitEvent(back, st->lists_ready[ticket], 0));
   E_HIP(av1mi::launch_av1_back(ctx, L, back));
-  E_HIP(hipMemcpyAsync(st->pending_total[ticket], L.tile_off + nt, 8, hipMemcpyDeviceToDevice, back));      // total bytes next to the status: tile_off[nt]
   E_HIP(hipEventRecord(st->lists_free[ticket], back)); st->free_recorded[ticket] = true;
   st->pending_valid[ticket] = false;
 #undef E_HIP
   return AV1MI_OK;
 }
 
-int av1mi::av1_entropy_submit(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hipStream_t front, hipStream_t back) {
+int av1mi::av1_entropy_submit(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hipStream_t front, hipStream_t back, const Av1EntMirrors *mirrors) {
   int ticket = -1;
   const int rc = av1_entropy_front(ctx, j, front, &ticket);
   if (rc != AV1MI_OK || ticket < 0) return rc;      // (an empty job has no back half)
-  return av1_entropy_back(ctx, ticket, back);
+  return av1_entropy_back(ctx, ticket, back, mirrors);
 }
 
 extern "C" {
@@ -550,7 +560,7 @@ int av1mi_av1_entropy_last_list_words(av1mi_ctx *ctx, uint64_t *words) {
 namespace av1mi {
 void av1ent_free(av1mi_av1ent_state *st) {
   if (!st) return;
-  for (void *p : { st->info, st->ops[0], st->ops[1], st->nops[0], st->nops[1], st->grouped, st->grouped_off, st->slot_tb, st->rec, st->slots, st->tile_off }) if (p) (void)hipFree(p);
+  for (void *p : { st->info, st->ops[0], st->ops[1], st->nops[0], st->nops[1], st->grouped, st->grouped_off, st->slot_tb, st->rec, st->slots, st->group_sum }) if (p) (void)hipFree(p);
   for (hipEvent_t ev : { st->lists_ready[0], st->lists_ready[1], st->lists_free[0], st->lists_free[1] }) if (ev) (void)hipEventDestroy(ev);
   for (auto &k : st->d_image) for (uint16_t *p : k) if (p) (void)hipFree(p);
   for (uint16_t *p : st->d_image32) if (p) (void)hipFree(p);

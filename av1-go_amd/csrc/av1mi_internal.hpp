@@ -29,12 +29,14 @@ __device__ __forceinline__ size_t row_off(int row, int stride) { return (size_t)
 
 // raster tile index -> (x, y, z) of a gx x gy x gz grid
 struct Tile3 { int x, y, z; };
-__device__ __forceinline__ Tile3 xcd_tile(unsigned gx, unsigned gy, unsigned gz) {
-  (void)gz;   // the launch's 1-D grid is exactly gx * gy * gz workgroups (every launch_* computes it from the same expressions)
-  const unsigned t = xcd_swizzle(blockIdx.x, gridDim.x);
+// ... of workgroup `bid` out of the `nwg` that share the grid (a launch whose 1-D grid holds several such grids end to end)
+__device__ __forceinline__ Tile3 xcd_tile(unsigned gx, unsigned gy, unsigned gz, unsigned bid, unsigned nwg) {
+  (void)gz;   // the grid is exactly gx * gy * gz workgroups (every launch_* computes it from the same expressions)
+  const unsigned t = xcd_swizzle(bid, nwg);
   const unsigned z = t / (gx * gy), rem = t - z * gx * gy, y = rem / gx;
   return { (int)(rem - y * gx), (int)y, (int)z };
 }
+__device__ __forceinline__ Tile3 xcd_tile(unsigned gx, unsigned gy, unsigned gz) { return xcd_tile(gx, gy, gz, blockIdx.x, gridDim.x); }
 
 // One transform launch: either a block list or an implicit grid of equal blocks.
 struct TxLaunch {
@@ -126,9 +128,13 @@ struct LrLaunch {
   int no_sgr;       // the caller's promise that no unit is self-guided (type 2): the kernel without that path's LDS
 };
 hipError_t launch_lr(const LrLaunch &L, hipStream_t s);
+// the three planes of 4:2:0 frames in ONE launch: their grids end to end, a workgroup takes its plane from its index.  The planes
+// share bd, unit_size, nframes, pass and no_sgr; plane 0 is the luma plane (ss 0), planes 1 and 2 are subsampled (ss 1)
+struct LrYuvLaunch { LrLaunch plane[3]; unsigned first[3]; };      // first: filled in by launch_lr_yuv (plane p's first workgroup)
+hipError_t launch_lr_yuv(LrYuvLaunch &Y, hipStream_t s);
 int lr_stripes(int h, int ss);
 hipError_t launch_zero16(void *p, size_t bytes, hipStream_t s);
-hipError_t launch_lr_decide3(const unsigned long long *sse, int nframes, int stripes_y, int stripes_c, uint8_t *on, hipStream_t s);
+hipError_t launch_lr_decide3(unsigned long long *sse, int nframes, int stripes_y, int stripes_c, uint8_t *on, hipStream_t s);
 hipError_t launch_extend(void *plane, int stride, int w, int h, int vw, int vh, int bd, int nframes, hipStream_t s);
 hipError_t launch_lr_decide(const unsigned long long *sse, int nframes, int stripes, uint8_t *on, int on_stride, hipStream_t s);
 
@@ -288,14 +294,23 @@ void av1ent_free(av1mi_av1ent_state *st);
 av1mi_av1ent_state *ctx_av1ent(av1mi_ctx *ctx);
 hipStream_t ctx_side_stream(av1mi_ctx *ctx);      // these two are created at their first use; null = creation failed
 hipStream_t ctx_back_stream(av1mi_ctx *ctx);
+// Optional pinned host mirrors of a coder job's results.  The gather stores them itself, with plain stores, beside the payloads it
+// already writes into pinned memory: every tile's workgroup its size, the last tile's workgroup the total, the status and the job's
+// restoration flags (d_lr_on, lr_on_bytes of them).  They are valid where the payloads are: after an event recorded behind the back
+// half.  Null members are skipped; without the record a caller gets the job's device arrays and nothing else.
+struct Av1EntMirrors {
+  uint32_t *h_tile_size;
+  uint64_t *h_total;      // [0] total bytes, [1] status: the layout of av1mi_av1_entropy_job::d_total
+  uint8_t *h_lr_on; uint32_t lr_on_bytes;
+};
 // the AV1 tile coder of include/av1mi.h's av1mi_av1_entropy_job in two halves: info + tokens + chains on `front`, the serial range
-// coder + scan + gather on `back` (the same stream, or a second one: the lists are double-buffered, so the front half of the next
+// coder + gather on `back` (the same stream, or a second one: the lists are double-buffered, so the front half of the next
 // job runs beside the back half of this one)
-int av1_entropy_submit(av1mi_ctx *ctx, const struct av1mi_av1_entropy_job *j, hipStream_t front, hipStream_t back);
+int av1_entropy_submit(av1mi_ctx *ctx, const struct av1mi_av1_entropy_job *j, hipStream_t front, hipStream_t back, const Av1EntMirrors *mirrors = nullptr);
 // ... and the halves on their own: the back half of a job may be launched later (the session defers the range coder of batch t behind
 // the filters of batch t + 1 on the main stream); at most two jobs' back halves can be outstanding (the list sets)
 int av1_entropy_front(av1mi_ctx *ctx, const struct av1mi_av1_entropy_job *j, hipStream_t front, int *ticket);
-int av1_entropy_back(av1mi_ctx *ctx, int ticket, hipStream_t back);
+int av1_entropy_back(av1mi_ctx *ctx, int ticket, hipStream_t back, const Av1EntMirrors *mirrors = nullptr);
 // accessors of the opaque context for translation units other than capi.hip (gop_session.hip)
 hipStream_t ctx_stream(av1mi_ctx *ctx);
 int ctx_device(av1mi_ctx *ctx);
@@ -306,6 +321,8 @@ struct ProfToken { hipEvent_t e0 = nullptr; int kind = 0; };
 // av1mi_inter_encode with the coarse search's scratch area given by the caller (the GOP session owns one); d_me is unused, and may be
 // null, when the job's coarse_range is 0
 int inter_encode_with(av1mi_ctx *ctx, const struct av1mi_inter_job *j, void *d_me);
+// av1mi_lr_yuv_decide for a caller that owns its scratch: scratch_clean = the sums are known to be zero (capi.hip: the rule)
+int lr_yuv_decide_with(av1mi_ctx *ctx, const struct av1mi_lr_decide_job *j, bool scratch_clean);
 ProfToken ctx_prof_begin(av1mi_ctx *ctx, int kind, hipStream_t st);
 void ctx_prof_end(av1mi_ctx *ctx, const ProfToken &t, hipStream_t st);
 // ... and the same as a scope around the launch(es); st null = the context's stream

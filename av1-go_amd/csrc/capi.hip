@@ -527,7 +527,16 @@ int av1mi_lr_frames_decide(av1mi_ctx *ctx, const void *d_cdef, const void *d_deb
 size_t av1mi_lr_yuv_decide_scratch_bytes(int h, int nframes) {
   return av1mi_lr_decide_scratch_bytes(h, 0, nframes) + 2 * av1mi_lr_decide_scratch_bytes(h / 2, 1, nframes);
 }
-int av1mi_lr_yuv_decide(av1mi_ctx *ctx, const av1mi_lr_decide_job *j) {
+int av1mi_lr_yuv_decide(av1mi_ctx *ctx, const av1mi_lr_decide_job *j) { return av1mi::lr_yuv_decide_with(ctx, j, false); }
+
+}  // extern "C"
+
+// THE RULE OF THE SCRATCH'S ZEROES, in this one place.  Pass 1 adds into the sums, so they must be zero when it starts; the decision
+// kernel, their only reader, writes zero back over every sum it has read (k_lr_decide3), so a call leaves its scratch as clean as it
+// must find it.  scratch_clean is the caller's promise that the scratch is in that state: zeroed once when it was allocated and since
+// then written by calls of this function with the same height and frame count only (the GOP session).  Without the promise — the C
+// entry point, whose caller may hand over any memory — the zeroing launch runs first, as it always did.
+int av1mi::lr_yuv_decide_with(av1mi_ctx *ctx, const av1mi_lr_decide_job *j, bool scratch_clean) {
   BIND(ctx);
   if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
   const void *ptrs[] = { j->d_cdef_y, j->d_cdef_u, j->d_cdef_v, j->d_dbl_y, j->d_dbl_u, j->d_dbl_v, j->d_out_y, j->d_out_u, j->d_out_v,
@@ -542,24 +551,29 @@ int av1mi_lr_yuv_decide(av1mi_ctx *ctx, const av1mi_lr_decide_job *j) {
   if (j->nframes == 0) return AV1MI_OK;
   const int n = j->nframes, sy = av1mi::lr_stripes(j->height, 0), sc = av1mi::lr_stripes(j->height / 2, 1);
   unsigned long long *sse = (unsigned long long *)j->d_scratch;
-  HIP_TRY(ctx, av1mi::launch_zero16(sse, av1mi_lr_yuv_decide_scratch_bytes(j->height, n), ctx->stream));
+  if (!scratch_clean) HIP_TRY(ctx, av1mi::launch_zero16(sse, av1mi_lr_yuv_decide_scratch_bytes(j->height, n), ctx->stream));
   const void *cdef[3] = { j->d_cdef_y, j->d_cdef_u, j->d_cdef_v }, *dbl[3] = { j->d_dbl_y, j->d_dbl_u, j->d_dbl_v }, *orig[3] = { j->d_orig_y, j->d_orig_u, j->d_orig_v };
   void *out[3] = { j->d_out_y, j->d_out_u, j->d_out_v };
   for (int p = 0; p < 3; p++) if (out[p] == cdef[p] || out[p] == dbl[p]) return fail(ctx, AV1MI_E_INVAL, "aliased device pointer");
   // pass 1: the tiles the decision's sums run over (an eighth of a large plane); the decision; pass 2: the other tiles of the frames
-  // that keep their restoration — a plane that is switched off costs an eighth of its restoration
+  // that keep their restoration — a plane that is switched off costs an eighth of its restoration.  One launch per pass: the three
+  // planes' grids end to end (launch_lr_yuv)
   for (int pass = 1; pass <= 2; pass++) {
-    for (int p = 0; p < 3; p++) {
-      av1mi::LrLaunch L = { cdef[p], dbl[p], out[p], p ? j->stride_uv : j->stride_y, p ? j->width / 2 : j->width, p ? j->height / 2 : j->height, j->bit_depth, p ? 1 : 0,
-                            j->unit_size, n, p ? j->d_units_uv : j->d_units_y, p ? j->unit_frame_stride_uv : j->unit_frame_stride_y, orig[p],
-                            sse + 2 * ((size_t)(p ? n * sy + (p - 1) * n * sc : 0)), p ? sc : sy, pass, j->d_on + p, 3, j->no_self_guided_units != 0 };
+    av1mi::LrYuvLaunch Y;
+    for (int p = 0; p < 3; p++)
+      Y.plane[p] = { cdef[p], dbl[p], out[p], p ? j->stride_uv : j->stride_y, p ? j->width / 2 : j->width, p ? j->height / 2 : j->height, j->bit_depth, p ? 1 : 0,
+                     j->unit_size, n, p ? j->d_units_uv : j->d_units_y, p ? j->unit_frame_stride_uv : j->unit_frame_stride_y, orig[p],
+                     sse + 2 * ((size_t)(p ? n * sy + (p - 1) * n * sc : 0)), p ? sc : sy, pass, j->d_on + p, 3, j->no_self_guided_units != 0 };
+    {
       ProfScope ps(ctx, AV1MI_K_LR);
-      HIP_TRY(ctx, av1mi::launch_lr(L, ctx->stream));
+      HIP_TRY(ctx, av1mi::launch_lr_yuv(Y, ctx->stream));
     }
     if (pass == 1) HIP_TRY(ctx, av1mi::launch_lr_decide3(sse, n, sy, sc, j->d_on, ctx->stream));
   }
   return AV1MI_OK;
 }
+
+extern "C" {
 
 int av1mi_extend_frames(av1mi_ctx *ctx, void *d_plane, int stride, int w, int h, int visible_w, int visible_h, int bd, int nframes) {
   BIND(ctx);

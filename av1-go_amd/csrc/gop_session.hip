@@ -12,9 +12,11 @@
 //                     main: wait uploaded -> [k_input_convert] -> [k_chroma_convert] -> [k_scale | k_crop_copy]
 //   code_blocks       main: k_intra_pipe | [k_me_down + k_me_coarse] + k_me_int + k_inter_pipe -> kernel_done
 //   download_symbols  down: wait kernel_done -> D2H of the symbols into pinned memory
-//   loop_filters      main: deblock + CDEF (one kernel), LR x3 + decision -> reference -> filters_done;  down: the decision -> downloaded
+//   loop_filters      main: deblock + CDEF (one kernel), k_lr_yuv (the sampled tiles of the three planes) -> k_lr_decide3 -> k_lr_yuv (the rest where
+//                     restoration stays on) -> reference -> filters_done;  down: (symbols for the host) the decision -> downloaded
 //   measure_quality   main: (quality_stats) k_quality_tiles + k_quality_sum, the records written into the slot's pinned memory -> quality_done
-//   start_coder       side: (GPU entropy coding) wait filters_done -> k_av1_* -> payloads gathered into the slot's pinned buffer -> ent_done
+//   start_coder       side: (GPU entropy coding) wait filters_done -> two memsets, k_av1_info / tokens / chains;  back: k_av1_code -> k_av1_gather,
+//                     which stores payloads, tile sizes, total + status and the decision into the slot's pinned buffers -> ent_done (no copies)
 // Source and symbol buffers exist kSlots = 3 times (slot = batch % 3): batch t + 2 uploads while batch t + 1 is in the block
 // pipeline and the coder works on batch t, whose predecessor the host is still reading.  Four streams, one hardware queue each
 // (a fifth would share a queue with one of these and serialise behind it).
@@ -447,6 +449,8 @@ int setup(av1mi_gop *g) {
   for (int p = 0; p < 3; p++)      // reconstruction, deblocked, CDEF and reference planes: single (the chain is serial in t)
     for (void **d : { &g->d_rec[p], &g->d_dbl[p], &g->d_cdef[p], &g->d_ref[p] }) G_TRY(dev_alloc(g, d, g->plane[p].bytes));
   G_TRY(dev_alloc(g, &g->d_lr_scratch, av1mi_lr_yuv_decide_scratch_bytes(h, S)));
+  // the decision's sums, zeroed ONCE: every batch's decision leaves them zero behind it (capi.hip lr_yuv_decide_with: the rule)
+  G_HIP(hipMemset(g->d_lr_scratch, 0, av1mi_lr_yuv_decide_scratch_bytes(h, S)));
   if (c.coarse_range) G_TRY(dev_alloc(g, &g->d_me, av1mi::me_layout(w, h, S).bytes));
   if (c.quality_stats) G_TRY(dev_alloc(g, &g->d_quality_scratch, av1mi::quality_scratch_bytes(c.bit_depth, g->vw, g->vh, S)));
   if (c.denoise) {
@@ -813,7 +817,7 @@ static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
   lj.d_units_y = (const int8_t *)g->d_lr[0]; lj.d_units_uv = (const int8_t *)g->d_lr[1];
   lj.d_scratch = g->d_lr_scratch; lj.d_on = (uint8_t *)s.d_lr_on;
   lj.no_self_guided_units = P.lr_unit_y[0] != 2 && P.lr_unit_uv[0] != 2;
-  G_TRY(av1mi_lr_yuv_decide(g->ctx, &lj));
+  G_TRY(av1mi::lr_yuv_decide_with(g->ctx, &lj, true));
   if (padded)      // ... and so do its motion-compensation reads of this frame
     for (int p = 0; p < 3; p++) G_TRY(extend_plane(g, g->plane[p], g->d_ref[p]));
   G_HIP(hipEventRecord(s.filters_done, av1mi::ctx_stream(g->ctx)));
@@ -845,18 +849,20 @@ static int measure_quality(av1mi_gop *g, Slot &s, const void *const src[3]) {
   return AV1MI_OK;
 }
 
-// the coder's results of a slot -> its pinned mirrors, then ent_done (on the stream the range coder ran on)
+// The coder's results of a slot reach its pinned mirrors — tile sizes, total + status, the restoration flags — the way the payloads
+// do: the gather stores them (av1mi::Av1EntMirrors), and ent_done, recorded on the stream the range coder ran on, is what the host
+// waits for before it reads any of them.  No copies.
+static av1mi::Av1EntMirrors entropy_mirrors(av1mi_gop *g, Slot &s) {
+  return { (uint32_t *)s.h_tile_size, (uint64_t *)s.h_total, (uint8_t *)s.h_lr_on, (uint32_t)g->cfg.segments * 3u };
+}
 static int entropy_results(av1mi_gop *g, Slot &s, hipStream_t st) {
-  const int S = g->cfg.segments;
-  G_HIP(hipMemcpyAsync(s.h_tile_size, s.d_tile_size, (size_t)g->tiles * S * 4, hipMemcpyDeviceToHost, st));
-  G_HIP(hipMemcpyAsync(s.h_total, s.d_total, 16, hipMemcpyDeviceToHost, st));
-  G_HIP(hipMemcpyAsync(s.h_lr_on, s.d_lr_on, (size_t)S * 3, hipMemcpyDeviceToHost, st));
   G_HIP(hipEventRecord(s.ent_done, st));
   return AV1MI_OK;
 }
 // the deferred back half of a slot's entropy job (coder_streams 3)
 static int finish_entropy(av1mi_gop *g, Slot &s, hipStream_t st) {
-  G_TRY(av1mi::av1_entropy_back(g->ctx, s.ent_ticket, st));
+  const av1mi::Av1EntMirrors m = entropy_mirrors(g, s);
+  G_TRY(av1mi::av1_entropy_back(g->ctx, s.ent_ticket, st, &m));
   s.ent_ticket = -1;
   return entropy_results(g, s, st);
 }
@@ -892,7 +898,8 @@ static int start_coder(av1mi_gop *g, Slot &s) {
     Slot &prev = g->slot[(g->submitted + kSlots - 1) % kSlots];
     if (g->submitted > 0 && prev.ent_ticket >= 0) G_TRY(finish_entropy(g, prev, main));
   } else {
-    G_TRY(av1mi::av1_entropy_submit(g->ctx, &ej, side, back));
+    const av1mi::Av1EntMirrors m = entropy_mirrors(g, s);
+    G_TRY(av1mi::av1_entropy_submit(g->ctx, &ej, side, back, &m));
     G_TRY(entropy_results(g, s, back));
   }
   s.ent_pending = true;

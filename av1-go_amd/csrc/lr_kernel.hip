@@ -28,12 +28,24 @@ __device__ constexpr int kSgrParams[16][4] = {
 // SGR: the launch may hold self-guided units.  Without them (the encoder's policy: Wiener or none) the A / B planes of that path
 // are not allocated — 9 instead of 27 KB of scratch, 20 instead of 38 KB of LDS per workgroup, 8 instead of 4 workgroups per CU —
 // and a unit of type 2 would be copied unfiltered (the caller promises there is none: LrLaunch::no_sgr).
-template <typename Pix, int SUBY, bool SGR = true>
-__global__ __launch_bounds__(256) void k_lr(LrLaunch L) {
-  constexpr int MAXH = 64, MAXW = 64, SS = MAXW + 16;      // source tile row stride (u16): tile column 0 = X0 - 4
-  constexpr int AS = MAXW + 2 + 2;                         // A/B row stride
-  __shared__ __attribute__((aligned(16))) uint16_t src[(MAXH + 6) * SS];
-  __shared__ __attribute__((aligned(16))) unsigned char scratch[SGR ? (MAXH + 2) * AS * 2 + (MAXH + 2) * AS * 4 : (MAXH + 6) * MAXW * 2];
+//
+// The body is a device function over the workgroup's LDS, which the kernel declares: k_lr runs it for one plane, k_lr_yuv for the
+// three planes of 4:2:0 frames in one launch.  The buffers are sized by the 64 x 64 tile whatever SUBY is, so luma and chroma
+// workgroups of the merged launch use the same 20 KB (38 KB with self-guided units) and the occupancy of the luma launch stands.
+constexpr int kLrMaxH = 64, kLrMaxW = 64, kLrSS = kLrMaxW + 16, kLrAS = kLrMaxW + 2 + 2;
+template <bool SGR> struct LrLds {
+  __attribute__((aligned(16))) uint16_t src[(kLrMaxH + 6) * kLrSS];
+  __attribute__((aligned(16))) unsigned char scratch[SGR ? (kLrMaxH + 2) * kLrAS * 2 + (kLrMaxH + 2) * kLrAS * 4 : (kLrMaxH + 6) * kLrMaxW * 2];
+  unsigned long long sse[2][4];
+};
+// workgroup `bid` of the plane's `nwg`
+template <typename Pix, int SUBY, bool SGR>
+__device__ __forceinline__ void lr_tile(const LrLaunch &L, unsigned bid, unsigned nwg, LrLds<SGR> &lds) {
+  constexpr int MAXH = kLrMaxH, MAXW = kLrMaxW, SS = kLrSS;      // source tile row stride (u16): tile column 0 = X0 - 4
+  constexpr int AS = kLrAS;                                      // A/B row stride
+  uint16_t *src = lds.src;
+  unsigned char *scratch = lds.scratch;
+  unsigned long long (*s_sse)[4] = lds.sse;
   int16_t *inter = reinterpret_cast<int16_t *>(scratch);                       // Wiener: (SH+6) x tw
   uint16_t *Abuf = reinterpret_cast<uint16_t *>(scratch);                      // self-guided: (SH+2) x (tw+2)
   int32_t *Bbuf = reinterpret_cast<int32_t *>(scratch + (MAXH + 2) * AS * 2);
@@ -42,7 +54,7 @@ __global__ __launch_bounds__(256) void k_lr(LrLaunch L) {
   const int tid = threadIdx.x;
   constexpr int SH = 64 >> SUBY, off = 8 >> SUBY;
   const int tw = L.unit_size < 64 ? L.unit_size : 64;
-  const Tile3 tl = xcd_tile((L.w + tw - 1) / tw, (L.h + off + SH - 1) / SH, L.nframes);
+  const Tile3 tl = xcd_tile((L.w + tw - 1) / tw, (L.h + off + SH - 1) / SH, L.nframes, bid, nwg);
   const int X0 = tl.x * tw, stripe = tl.y, f = tl.z;
   const int sstart = stripe * SH - off, send = sstart + SH - 1;
   const int y0 = max(sstart, 0), y1 = min(send, L.h - 1);    // rows this workgroup writes
@@ -70,7 +82,6 @@ __global__ __launch_bounds__(256) void k_lr(LrLaunch L) {
   const Pix *orig = L.orig && sampled ? reinterpret_cast<const Pix *>(L.orig) + (size_t)f * L.h * L.stride : nullptr;
   unsigned e_lr = 0, e_cd = 0;
   auto lr_acc = [&](int o, int cd, int sv) { const int a = o - sv, b = cd - sv; e_lr += (unsigned)(a * a); e_cd += (unsigned)(b * b); };
-  __shared__ unsigned long long s_sse[2][4];
   auto lr_finish = [&]() {      // every thread of the workgroup comes here exactly once (uniform control flow up to the returns)
     if (!orig) return;       // (uniform: no decision asked for, or a tile outside the sample)
     unsigned long long a = e_lr, b = e_cd;
@@ -348,6 +359,21 @@ __global__ __launch_bounds__(256) void k_lr(LrLaunch L) {
   lr_finish();
 }
 
+template <typename Pix, int SUBY, bool SGR = true>
+__global__ __launch_bounds__(256) void k_lr(LrLaunch L) {
+  __shared__ LrLds<SGR> lds;
+  lr_tile<Pix, SUBY, SGR>(L, blockIdx.x, gridDim.x, lds);
+}
+// the three planes' grids end to end: the plane, and with it SUBY, from the workgroup's index (uniform per workgroup)
+template <typename Pix, bool SGR>
+__global__ __launch_bounds__(256) void k_lr_yuv(LrYuvLaunch Y) {
+  __shared__ LrLds<SGR> lds;
+  const unsigned b = blockIdx.x;
+  if (b < Y.first[1]) lr_tile<Pix, 0, SGR>(Y.plane[0], b, Y.first[1], lds);
+  else if (b < Y.first[2]) lr_tile<Pix, 1, SGR>(Y.plane[1], b - Y.first[1], Y.first[2] - Y.first[1], lds);
+  else lr_tile<Pix, 1, SGR>(Y.plane[2], b - Y.first[2], gridDim.x - Y.first[2], lds);
+}
+
 // restoration stays on for frame f of the plane when it lowered the squared error: on[f * on_stride] = sum over the stripes
 __global__ __launch_bounds__(64) void k_lr_decide(const unsigned long long *sse, int nframes, int stripes, uint8_t *on, int on_stride) {
   const int f = blockIdx.x * 64 + threadIdx.x;
@@ -384,15 +410,16 @@ hipError_t launch_extend(void *plane, int stride, int w, int h, int vw, int vh, 
   return hipGetLastError();
 }
 
-// the three planes of 4:2:0 frames at once: thread = (frame, plane); plane p's sums start at sse + off[p] pairs
-__global__ __launch_bounds__(64) void k_lr_decide3(const unsigned long long *sse, int nframes, int stripes_y, int stripes_c, uint8_t *on) {
+// the three planes of 4:2:0 frames at once: thread = (frame, plane); plane p's sums start at sse + off[p] pairs.  The sums a thread
+// has read it leaves ZERO, what the next call's pass 1 adds into (it is their only reader; capi.hip lr_yuv_decide_with: the rule)
+__global__ __launch_bounds__(64) void k_lr_decide3(unsigned long long *sse, int nframes, int stripes_y, int stripes_c, uint8_t *on) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= nframes * 3) return;
   const int f = i / 3, p = i - 3 * f;
   const int stripes = p ? stripes_c : stripes_y;
-  const unsigned long long *q = sse + 2 * ((size_t)(p ? nframes * stripes_y + (p - 1) * nframes * stripes_c : 0) + (size_t)f * stripes);
+  unsigned long long *q = sse + 2 * ((size_t)(p ? nframes * stripes_y + (p - 1) * nframes * stripes_c : 0) + (size_t)f * stripes);
   unsigned long long a = 0, b = 0;
-  for (int s = 0; s < stripes; s++) { a += q[2 * s]; b += q[2 * s + 1]; }
+  for (int s = 0; s < stripes; s++) { a += q[2 * s]; b += q[2 * s + 1]; q[2 * s] = 0; q[2 * s + 1] = 0; }
   on[i] = a < b;
 }
 __global__ __launch_bounds__(256) void k_zero16(uint4 *p, size_t n) {
@@ -404,7 +431,7 @@ hipError_t launch_zero16(void *p, size_t bytes, hipStream_t s) {      // bytes: 
   if (n) hipLaunchKernelGGL(k_zero16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (uint4 *)p, n);
   return hipGetLastError();
 }
-hipError_t launch_lr_decide3(const unsigned long long *sse, int nframes, int stripes_y, int stripes_c, uint8_t *on, hipStream_t s) {
+hipError_t launch_lr_decide3(unsigned long long *sse, int nframes, int stripes_y, int stripes_c, uint8_t *on, hipStream_t s) {
   hipLaunchKernelGGL(k_lr_decide3, dim3((unsigned)((nframes * 3 + 63) / 64)), dim3(64), 0, s, sse, nframes, stripes_y, stripes_c, on);
   return hipGetLastError();
 }
@@ -414,15 +441,30 @@ hipError_t launch_lr_decide(const unsigned long long *sse, int nframes, int stri
   hipLaunchKernelGGL(k_lr_decide, dim3((unsigned)((nframes + 63) / 64)), dim3(64), 0, s, sse, nframes, stripes, on, on_stride);
   return hipGetLastError();
 }
+// the plane's workgroups: column bands x stripes x frames
+static unsigned lr_grid(const LrLaunch &L) {
+  const int SH = 64 >> L.ss, off = 8 >> L.ss, tw = L.unit_size < 64 ? L.unit_size : 64;
+  return (unsigned)(((L.w + tw - 1) / tw) * ((L.h + off + SH - 1) / SH) * L.nframes);
+}
 hipError_t launch_lr(const LrLaunch &L, hipStream_t s) {
-  const int SH = 64 >> L.ss, off = 8 >> L.ss;
-  const int tw = L.unit_size < 64 ? L.unit_size : 64;
-  const dim3 grid((unsigned)(((L.w + tw - 1) / tw) * ((L.h + off + SH - 1) / SH) * L.nframes));   // 1-D: the kernel orders the tiles (xcd_tile)
+  const dim3 grid(lr_grid(L));   // 1-D: the kernel orders the tiles (xcd_tile)
 #define AV1MI_LR(PIX, SUBY) do { if (L.no_sgr) hipLaunchKernelGGL((k_lr<PIX, SUBY, false>), grid, dim3(256), 0, s, L); \
                                   else hipLaunchKernelGGL((k_lr<PIX, SUBY, true>), grid, dim3(256), 0, s, L); } while (0)
   if (L.ss) { if (L.bd == 8) AV1MI_LR(uint8_t, 1); else AV1MI_LR(uint16_t, 1); }
   else { if (L.bd == 8) AV1MI_LR(uint8_t, 0); else AV1MI_LR(uint16_t, 0); }
 #undef AV1MI_LR
+  return hipGetLastError();
+}
+hipError_t launch_lr_yuv(LrYuvLaunch &Y, hipStream_t s) {
+  if (Y.plane[0].ss != 0 || Y.plane[1].ss != 1 || Y.plane[2].ss != 1) return hipErrorInvalidValue;
+  unsigned n = 0;
+  for (int p = 0; p < 3; p++) { Y.first[p] = n; n += lr_grid(Y.plane[p]); }
+  const LrLaunch &L = Y.plane[0];
+  const dim3 grid(n);
+#define AV1MI_LR3(PIX) do { if (L.no_sgr) hipLaunchKernelGGL((k_lr_yuv<PIX, false>), grid, dim3(256), 0, s, Y); \
+                            else hipLaunchKernelGGL((k_lr_yuv<PIX, true>), grid, dim3(256), 0, s, Y); } while (0)
+  if (L.bd == 8) AV1MI_LR3(uint8_t); else AV1MI_LR3(uint16_t);
+#undef AV1MI_LR3
   return hipGetLastError();
 }
 
