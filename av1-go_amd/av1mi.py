@@ -106,7 +106,7 @@ class GopConfig(C.Structure):
                 ("source_height", C.c_int), ("quality_stats", C.c_int), ("coarse_range", C.c_int), ("source_chroma", C.c_int),
                 ("source_bit_depth", C.c_int), ("store_frames", C.c_int), ("deinterlace", C.c_int), ("denoise", C.c_int),
                 ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int), ("crop_height", C.c_int), ("denoise_range", C.c_int),
-                ("tone_map", C.c_int), ("tone_map_peak", C.c_int)]
+                ("tone_map", C.c_int), ("tone_map_peak", C.c_int), ("grain_cov", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -120,7 +120,7 @@ class GopFrame(C.Structure):
                 ("uv_mode", C.c_void_p), ("mv", C.c_void_p), ("skip", C.c_void_p), ("lev_y", C.c_void_p), ("lev_u", C.c_void_p),
                 ("lev_v", C.c_void_p), ("tiles_per_frame", C.c_int), ("tile_size", C.c_void_p), ("tile_payload", C.c_void_p),
                 ("payload_bytes", C.c_uint64), ("lr_on", C.c_void_p), ("key_block_size", C.c_int), ("key_modes_stride", C.c_int),
-                ("key_modes_band", C.c_int), ("quality", C.c_void_p), ("grain", C.c_void_p)]
+                ("key_modes_band", C.c_int), ("quality", C.c_void_p), ("grain", C.c_void_p), ("grain_cov", C.c_void_p)]
 
 
 def policy_frame_params(base_q_idx, bit_depth, frame_type):
@@ -136,6 +136,7 @@ def policy_frame_params(base_q_idx, bit_depth, frame_type):
 # av1mi_scene_record (include/av1mi.h "scene analysis"): one record per frame
 GRAIN_BINS = 16      # AV1MI_GRAIN_BINS; a record (av1mi_grain_record) is that many bins
 GRAIN_DTYPE = np.dtype([("sum_sq", "<u8"), ("count", "<u4"), ("reserved", "<u4")])      # av1mi_grain_bin
+GRAIN_COV_DTYPE = np.dtype([("sum", "<i8", (4, 13))])      # av1mi_grain_cov_record ("grain covariance"): sum[dy][dx + 6]
 DENOISE_VEC_DTYPE = np.dtype([("dx_p", "i1"), ("dy_p", "i1"), ("dx_n", "i1"), ("dy_n", "i1")])      # av1mi_denoise_vec: a block's vectors towards P and N
 SCENE_DTYPE = np.dtype([("inter_sad", "<u8"), ("intra_sad", "<u8"), ("blocks", "<u4"), ("reserved", "<u4")])
 CROP_DTYPE = np.dtype([("top", "<u4"), ("bottom", "<u4"), ("left", "<u4"), ("right", "<u4")])      # av1mi_crop_record ("bar detection")
@@ -246,7 +247,7 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None, tone_map=0, tone_map_peak=0):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None, tone_map=0, tone_map_peak=0, grain_cov=None):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
@@ -264,7 +265,9 @@ class GopSession:
         crop: (x, y, width, height), the window of the fed frames that is coded (av1mi_gop_config.crop_*; needs source, the fed frames'
         true size): width x height (or visible) is the target the window is copied or scaled to;
         denoise_range: 4 or 8, the range of the denoiser's block search (av1mi_gop_config.denoise_range; needs denoise): submit_stored()
-        gathers through the motion-compensated filter.  None leaves the field unset (0 = none)"""
+        gathers through the motion-compensated filter.  None leaves the field unset (0 = none);
+        grain_cov: 1 = the covariance of what the denoiser removed is measured behind the gather (av1mi_gop_config.grain_cov; needs
+        denoise): collect()["grain_cov"] holds the records.  None leaves the field unset (0 = none)"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
         sw, sh = source if source is not None else (0, 0)
@@ -274,6 +277,8 @@ class GopSession:
             self.cfg.denoise = int(denoise)
         if denoise_range is not None:
             self.cfg.denoise_range = int(denoise_range)
+        if grain_cov is not None:
+            self.cfg.grain_cov = int(grain_cov)
         # tone_map: 1 = every batch is tone-mapped (PQ / BT.2020 -> SDR / BT.709) in place behind the input stages; tone_map_peak: cd/m2, 0 = 1000
         self.cfg.tone_map, self.cfg.tone_map_peak = int(tone_map), int(tone_map_peak)
         if crop is not None:
@@ -359,6 +364,8 @@ class GopSession:
             out["quality"] = _view(f.quality, (S, 3), QUALITY_DTYPE)
         if f.grain:        # denoise: records [segment, plane, bin] (GRAIN_DTYPE)
             out["grain"] = _view(f.grain, (S, 3, GRAIN_BINS), GRAIN_DTYPE)
+        if f.grain_cov:    # grain_cov: records [segment, plane] (GRAIN_COV_DTYPE)
+            out["grain_cov"] = _view(f.grain_cov, (S, 3), GRAIN_COV_DTYPE)
         if f.key_block_size == 32:
             out["key_block_size"] = 32
         if f.key_block_size == 32 and f.lev_y:
@@ -702,6 +709,13 @@ class Context:
         sizes, dst = self._gather_planes(plane_sizes, true_sizes, d_dst)
         self._chk(self.lib.av1mi_denoise_mc_gather(self.h, int(bit_depth), *sizes, int(strength), int(rng), int(segments), d_table.ptr, dst,
                                                    d_records.ptr if d_records is not None else None, d_vectors.ptr if d_vectors is not None else None))
+
+    def grain_cov(self, bit_depth, plane_sizes, true_sizes, segments, d_table, d_out, d_cov):
+        """the grain covariance behind a denoising gather (av1mi_grain_cov): that gather's sizes, segments and table, d_out the planes it
+        wrote; d_cov: DevBuf of segments * 3 records (GRAIN_COV_DTYPE [segments, 3]); asynchronous"""
+        self.lib.av1mi_grain_cov.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        sizes, out = self._gather_planes(plane_sizes, true_sizes, d_out)
+        self._chk(self.lib.av1mi_grain_cov(self.h, int(bit_depth), *sizes, int(segments), d_table.ptr, out, d_cov.ptr if d_cov is not None else None))
 
     def prof_enable(self, on):
         self._chk(self.lib.av1mi_prof_enable(self.h, int(on)))

@@ -255,6 +255,22 @@ def film_grain_from_records(records, bit_depth, frame_index):
     return g
 
 
+def film_grain_from_records_ar(records, cov, bit_depth, frame_index, lag):
+    """av1mi_film_grain_from_records_ar: one frame's grain records and covariance records (int64 [3, 4, 13], or av1mi.GRAIN_COV_DTYPE [3],
+    e.g. collect()["grain_cov"][seg]) -> FilmGrain with autoregressive coefficients of up to `lag`"""
+    h = lib()
+    h.av1mi_film_grain_from_records_ar.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FilmGrain)]
+    rec = np.ascontiguousarray(records)
+    assert rec.shape == (3, 16) and rec.dtype.itemsize == 16
+    cv = np.ascontiguousarray(cov)
+    cv = np.ascontiguousarray(cv["sum"] if cv.dtype.names else cv, np.int64)
+    assert cv.shape == (3, 4, 13)
+    g = FilmGrain()
+    if h.av1mi_film_grain_from_records_ar(rec.ctypes.data, cv.ctypes.data, int(bit_depth), int(frame_index), int(lag), C.byref(g)):
+        raise ValueError("av1mi_film_grain_from_records_ar: bad argument")
+    return g
+
+
 def film_grain_mid_grey(g):
     h = lib()
     h.av1mi_film_grain_mid_grey.argtypes = [C.POINTER(FilmGrain)]

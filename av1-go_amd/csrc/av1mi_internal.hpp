@@ -266,6 +266,14 @@ struct DenoiseMcLaunch : DenoiseLaunch {
 size_t denoise_mc_scratch_bytes(const DenoiseMcLaunch &L);      // 0 for a geometry the launch refuses
 size_t denoise_mc_vector_bytes(const DenoiseMcLaunch &L);       // likewise
 hipError_t launch_denoise_mc_gather(const DenoiseMcLaunch &L, hipStream_t s);
+// the grain covariance (grain_cov_kernels.hip, include/av1mi.h "grain covariance"), launched BEHIND either gather above on the same planes:
+// of the table only the C entries are read, dst are the planes the gather wrote (only read here); bd 8 or 10.  cov: segments * 3 records
+// (device or pinned host memory); scratch holds grain_cov_scratch_bytes(L) bytes (8-byte aligned) of per-workgroup partials.  Two launches.
+struct GrainCovLaunch : GatherPlanes {
+  void *scratch; av1mi_grain_cov_record *cov;
+};
+size_t grain_cov_scratch_bytes(const GatherPlanes &L);      // 0 for a geometry the launch refuses
+hipError_t launch_grain_cov(const GrainCovLaunch &L, hipStream_t s);
 
 // side information that follows a batch's quantiser (levels_kernels.hip): up to three arrays of dwords patched in place in one launch,
 // word = (word & keep) | bits unless (word & hold) != 0

@@ -33,6 +33,8 @@ struct av1mi_ctx {
   void *grain_scratch = nullptr;          // av1mi_denoise_gather: the workgroups' partial records (grown on demand)
   size_t grain_scratch_bytes = 0;
   void *denoise_vectors = nullptr;        // av1mi_denoise_mc_gather without d_vectors: the blocks' vectors (grown on demand)
+  void *grain_cov_scratch = nullptr;      // av1mi_grain_cov: the workgroups' partial sums (grown on demand)
+  size_t grain_cov_scratch_bytes = 0;
   size_t denoise_vectors_bytes = 0;
   // per-kernel profile: one event pair per launch while enabled
   bool prof_on = false;
@@ -218,6 +220,7 @@ void av1mi_close(av1mi_ctx *ctx) {
   if (ctx->crop_scratch) (void)hipFree(ctx->crop_scratch);
   if (ctx->grain_scratch) (void)hipFree(ctx->grain_scratch);
   if (ctx->denoise_vectors) (void)hipFree(ctx->denoise_vectors);
+  if (ctx->grain_cov_scratch) (void)hipFree(ctx->grain_cov_scratch);
   if (ctx->av1ent) av1mi::av1ent_free(ctx->av1ent);
   av1mi::scale_plan_destroy(ctx->scale_plan);
   for (auto &r : ctx->prof_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -792,6 +795,21 @@ int av1mi_denoise_mc_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3],
   }
   ProfScope ps(ctx, AV1MI_K_SCENE);
   HIP_TRY(ctx, av1mi::launch_denoise_mc_gather(L, ctx->stream));
+  return AV1MI_OK;
+}
+
+int av1mi_grain_cov(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int segments,
+                    const void *const *d_table, void *const d_out[3], av1mi_grain_cov_record *d_cov) {
+  BIND(ctx);
+  if (!plane_w || !plane_h || !true_w || !true_h || !d_table || !d_out || !d_cov || ((uintptr_t)d_table & 7) || ((uintptr_t)d_cov & 7))
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_grain_cov: null pointer, or misaligned table or records");
+  av1mi::GrainCovLaunch L;
+  L.cov = d_cov; L.scratch = nullptr;
+  if (int rc = check_gather_planes(ctx, "av1mi_grain_cov", 10, true, bit_depth, plane_w, plane_h, true_w, true_h, segments, d_table, d_out, L)) return rc;
+  if (int rc = grow(ctx, &ctx->grain_cov_scratch, &ctx->grain_cov_scratch_bytes, av1mi::grain_cov_scratch_bytes(L))) return rc;
+  L.scratch = ctx->grain_cov_scratch;      // (null where there is no plane at all: the launch then only clears the records)
+  ProfScope ps(ctx, AV1MI_K_SCENE);
+  HIP_TRY(ctx, av1mi::launch_grain_cov(L, ctx->stream));
   return AV1MI_OK;
 }
 

@@ -130,6 +130,7 @@ struct Slot {
   void *h_table = nullptr, *d_table = nullptr;
   // denoise: the batch's grain records [segment * 3 + plane], pinned and written by the GPU (k_grain_sum); grain_done follows
   void *h_grain = nullptr;
+  void *h_grain_cov = nullptr;        // grain_cov: the batch's covariance records beside them (k_grain_cov_sum), in front of the same event
   hipEvent_t grain_done = nullptr;
   bool has_grain = false;             // this batch went through the denoising gather (a batch of av1mi_gop_submit_device does not)
 };
@@ -166,6 +167,7 @@ struct av1mi_gop {
   void *d_me = nullptr;                        // coarse_range: the coarse search's quarter planes and centres of one batch (single: the chain is serial in t)
   void *d_denoise_vectors = nullptr;           // denoise_range: the blocks' vectors of one batch (the main stream orders its users)
   void *d_grain_scratch = nullptr;             // denoise: the workgroups' partial records of one batch (the main stream orders its users)
+  void *d_grain_cov_scratch = nullptr;         // grain_cov: the workgroups' partial sums of one batch (likewise)
   void *d_tone_tables = nullptr;               // tone_map: the tables (av1mi_tone_tables), uploaded at open
   void *d_quality_scratch = nullptr;           // quality_stats: the tiles' partial sums of one batch (the main stream orders its users)
   int vw = 0, vh = 0;                          // the true frame size (== the coded size unless cfg.visible_* say otherwise)
@@ -273,6 +275,7 @@ int slot_buffers(av1mi_gop *g, Slot &s) {
   if (c.denoise) {
     G_TRY(host_alloc(g, &s.h_grain, (size_t)S * 3 * sizeof(av1mi_grain_record)));
     G_HIP(hipEventCreateWithFlags(&s.grain_done, hipEventDisableTiming));
+    if (c.grain_cov) G_TRY(host_alloc(g, &s.h_grain_cov, (size_t)S * 3 * sizeof(av1mi_grain_cov_record)));
   }
   if (c.quality_stats) {
     G_TRY(host_alloc(g, &s.h_quality, (size_t)S * 3 * sizeof(av1mi_quality)));
@@ -397,6 +400,8 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
   if (c->denoise && c->source_bit_depth == 12) return WHY("denoise %d takes fed samples of 8 or 10 bits, not source_bit_depth 12", c->denoise);
   if (c->denoise_range != 0 && c->denoise_range != 4 && c->denoise_range != 8) return WHY("denoise_range %d unknown (0 none, 4 or 8 the block search's range)", c->denoise_range);
   if (c->denoise_range && !c->denoise) return WHY("denoise_range %d needs denoise (1 .. 16): it is the range of the denoiser's block search", c->denoise_range);
+  if (c->grain_cov != 0 && c->grain_cov != 1) return WHY("grain_cov %d unknown (0 none, 1 the covariance of what the denoiser removed)", c->grain_cov);
+  if (c->grain_cov && !c->denoise) return WHY("grain_cov %d needs denoise (1 .. 16): it measures what the denoiser removed", c->grain_cov);
   if (c->tone_map != 0 && c->tone_map != 1) return WHY("tone_map %d unknown (0 none, 1 BT.2390)", c->tone_map);
   if (c->tone_map_peak && !c->tone_map) return WHY("tone_map_peak %d needs tone_map", c->tone_map_peak);
   if (c->tone_map && c->bit_depth != 10) return WHY("tone_map needs bit_depth 10, not %d: an HDR10 source has 10 bits", c->bit_depth);
@@ -462,6 +467,7 @@ int setup(av1mi_gop *g) {
                                       g->layout.height, g->layout.true_width, g->layout.true_height);
     G_TRY(dev_alloc(g, &g->d_grain_scratch, bytes));
     if (c.denoise_range) G_TRY(dev_alloc(g, &g->d_denoise_vectors, av1mi::denoise_mc_vector_bytes(L)));
+    if (c.grain_cov) G_TRY(dev_alloc(g, &g->d_grain_cov_scratch, av1mi::grain_cov_scratch_bytes(L)));      // (the gather's geometry: not 0 here)
   }
   if (c.store_frames) {
     for (Store &st : g->store) {
@@ -616,6 +622,12 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
         L.strength = c.denoise; L.scratch = g->d_grain_scratch; L.records = (av1mi_grain_record *)s.h_grain;
         G_HIP(av1mi::launch_denoise_gather(L, main));
       } else G_HIP(av1mi::launch_frames_gather(frame_bytes, S, (const void *const *)s.d_table, s.d_in, main));
+      if (c.grain_cov) {           // one more launch behind either denoising gather: C from the table, out from the fed buffers
+        av1mi::GrainCovLaunch L;
+        fed_geometry(g, &s, L);
+        L.scratch = g->d_grain_cov_scratch; L.cov = (av1mi_grain_cov_record *)s.h_grain_cov;
+        G_HIP(av1mi::launch_grain_cov(L, main));
+      }
     }
     if (c.denoise) G_HIP(hipEventRecord(s.grain_done, main));
     G_HIP(hipEventRecord(st.read_done, main));
@@ -1051,7 +1063,7 @@ int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out) {
   out->params = s.params;
   out->lr_on = (const uint8_t *)s.h_lr_on;
   if (g->cfg.quality_stats) { G_HIP(hipEventSynchronize(s.quality_done)); out->quality = (const av1mi_quality *)s.h_quality; }
-  if (g->cfg.denoise && s.has_grain) { G_HIP(hipEventSynchronize(s.grain_done)); out->grain = (const av1mi_grain_record *)s.h_grain; }
+  if (g->cfg.denoise && s.has_grain) { G_HIP(hipEventSynchronize(s.grain_done)); out->grain = (const av1mi_grain_record *)s.h_grain; out->grain_cov = (const av1mi_grain_cov_record *)s.h_grain_cov; }
   out->segments = g->cfg.segments;
   out->blocks_per_frame = g->nb / (size_t)g->cfg.segments;
   out->key_block_size = s.frame_type == 0 && g->key32 ? 32 : 8;

@@ -97,6 +97,7 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
   // -av1mi_denoise: the same store, the denoiser in the gather; -av1mi_film_grain (1 unless told otherwise): parameters in every frame header
   cfg.denoise = job.denoise;
   cfg.denoise_range = job.denoise_range;
+  cfg.grain_cov = job.grain_lag > 0;      // -av1mi_grain_lag: the covariance behind the gather, from which the AR coefficients follow
   // the stream's colour record: the job's options, the header's range; a tone-mapped job says what the kernel makes
   plan->colour = JobColour(job, src.colour_range);
   if (const char *why = av1::colour_error(plan->colour)) return refuse(why);
@@ -125,6 +126,7 @@ std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, c
   if (tags.colour && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " colour:%d/%d/%d/%d", tags.colour->primaries, tags.colour->transfer, tags.colour->matrix, tags.colour->full_range);
   if (tags.q) k += snprintf(line + k, sizeof(line) - (size_t)k, " q:%d", f.base_q_idx);
   if (tags.grain) k += snprintf(line + k, sizeof(line) - (size_t)k, " grain:%d", f.grain);
+  if (tags.ar) k += snprintf(line + k, sizeof(line) - (size_t)k, " ar:%d", f.ar);
   if (cut) k += snprintf(line + k, sizeof(line) - (size_t)k, " cut:1");
   return std::string(line, (size_t)k);
 }
@@ -333,7 +335,12 @@ struct Run {
       av1mi_film_grain fg;
       if (job.denoise) {      // what the gather removed from this frame -> the parameters that put it back (none for the ends of a run)
         if (!oldest.grain) return fail(2, "the session returned no grain records");
-        FilmGrainFromRecords(oldest.grain + (size_t)s * 3, y.bd, (int)(g0 * G + group.start[(size_t)s] + t), &fg);
+        const int index = (int)(g0 * G + group.start[(size_t)s] + t);
+        if (job.grain_lag > 0) {      // coloured grain: the covariance of the same residual shapes it
+          if (!oldest.grain_cov) return fail(2, "the session returned no grain covariance");
+          FilmGrainFromRecordsAr(oldest.grain + (size_t)s * 3, oldest.grain_cov + (size_t)s * 3, y.bd, index, job.grain_lag, &fg);
+          f.ar = fg.apply_grain ? fg.ar_coeff_lag : 0;
+        } else FilmGrainFromRecords(oldest.grain + (size_t)s * 3, y.bd, index, &fg);
         f.grain = FilmGrainMidGrey(fg);
       }
       if (!SessionTemporalUnit(oldest, s, plan.cfg.width, plan.cfg.height, y.bd, plan.cfg.visible_width, plan.cfg.visible_height, t == 0, threads, &f.unit, err, plan.grainy,
@@ -379,7 +386,7 @@ struct Run {
   // the group's frames in presentation order: each unit to the sink, its line to the stats
   int write_group(const Group &group, const GroupOut &out) {
     StatsTags tags;
-    tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0;
+    tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0; tags.ar = job.grain_lag > 0;
     for (int s = 0; s < S; s++)
       for (size_t t = 0; t < out[(size_t)s].size(); t++) {
         const FrameOut &f = out[(size_t)s][t];

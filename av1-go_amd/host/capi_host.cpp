@@ -335,6 +335,9 @@ long long av1mi_session_temporal_unit_grain(const av1mi_gop_frame *fr, int seg, 
 int av1mi_film_grain_from_records(const av1mi_grain_record *records, int bit_depth, int frame_index, av1mi_film_grain *out) {
   return FilmGrainFromRecords(records, bit_depth, frame_index, out) ? 0 : -1;
 }
+int av1mi_film_grain_from_records_ar(const av1mi_grain_record *records, const av1mi_grain_cov_record *cov, int bit_depth, int frame_index, int lag, av1mi_film_grain *out) {
+  return FilmGrainFromRecordsAr(records, cov, bit_depth, frame_index, lag, out) ? 0 : -1;
+}
 int av1mi_film_grain_mid_grey(const av1mi_film_grain *g) { return g ? FilmGrainMidGrey(*g) : 0; }
 // The general block description (av1_blockstream.cpp): any block / transform size, any partition
 long long av1mi_obu_write_blocks_temporal_unit(const av1mi_obu_blocks *f, int with_sequence_header, uint8_t *out, long long cap, char *err, int errcap) {

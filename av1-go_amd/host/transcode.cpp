@@ -268,7 +268,7 @@ av1mi_colour JobColour(const BackendJob &job, int y4m_range) {
 bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std::string *err) {
   if (args.size() < 3) { if (err) *err = "Invalid argument: too few arguments"; return false; }
   job->output = args.back();
-  bool have_in = false, deint_given = false;
+  bool have_in = false, deint_given = false, grain_lag_given = false;
   std::string colour_err;
   for (size_t i = 0; i + 1 < args.size(); i++) {
     if (args[i] == "-i") { job->input = args[i + 1]; have_in = true; }
@@ -306,6 +306,10 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
         if (err) *err = "Invalid argument: -av1mi_denoise_range takes 0 (off), 4 or 8, not " + args[i + 1];
         return false;
       }
+    }
+    else if (args[i] == "-av1mi_grain_lag") {
+      if (!plain_int(args[i + 1], &job->grain_lag) || job->grain_lag > 3) { if (err) *err = "Invalid argument: -av1mi_grain_lag takes 0 (white grain) .. 3, not " + args[i + 1]; return false; }
+      grain_lag_given = true;
     }
     else if (args[i] == "-av1mi_crop") {
       const std::string &v = args[i + 1];
@@ -413,6 +417,8 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
   if (job->denoise && job->deinterlace) { if (err) *err = "Invalid argument: -av1mi_denoise filters the group's frames on their way from the store, as -av1mi_deinterlace does: not together with -av1mi_deinterlace"; return false; }
   if (job->denoise_range && !job->denoise) { if (err) *err = "Invalid argument: -av1mi_denoise_range needs -av1mi_denoise"; return false; }
   if (job->film_grain >= 0 && !job->denoise) { if (err) *err = "Invalid argument: -av1mi_film_grain needs -av1mi_denoise"; return false; }
+  if (grain_lag_given && !job->denoise) { if (err) *err = "Invalid argument: -av1mi_grain_lag needs -av1mi_denoise"; return false; }
+  if (grain_lag_given && job->film_grain == 0) { if (err) *err = "Invalid argument: -av1mi_grain_lag shapes the film grain: not together with -av1mi_film_grain 0"; return false; }
   if (job->min_gop && !job->scenecut) { if (err) *err = "Invalid argument: -av1mi_min_gop needs -av1mi_scenecut"; return false; }
   if (job->min_gop && job->gop >= 1 && job->min_gop > job->gop - job->gop / 2) { if (err) *err = "Invalid argument: -av1mi_min_gop " + std::to_string(job->min_gop) + " above gop - gop / 2 = " + std::to_string(job->gop - job->gop / 2); return false; }
   if (!have_in) { if (err) *err = "Invalid argument: no input (-i) given"; return false; }

@@ -90,6 +90,9 @@ struct BackendJob {
                            // first and last frame of a group pass through.  Not with -av1mi_pack10 1, not with -av1mi_deinterlace
   int denoise_range = 0;   // -av1mi_denoise_range N: 0 (default), 4 or 8 = the range of the denoiser's block search (include/av1mi.h "motion-compensated
                            // denoising", av1mi_gop_config.denoise_range); an error without -av1mi_denoise
+  int grain_lag = 0;       // -av1mi_grain_lag N: 0 (default, white grain) .. 3 = the lag of the film grain's autoregressive filter, its coefficients from the
+                           // covariance of what the denoiser removed (host/filmgrain.hpp "coloured"; av1mi_gop_config.grain_cov); an error without
+                           // -av1mi_denoise or with -av1mi_film_grain 0
   int film_grain = -1;     // -av1mi_film_grain 0 | 1: with -av1mi_denoise, 1 (the default there) signals film grain synthesis parameters derived from
                            // what the denoiser removed (host/filmgrain.hpp), 0 codes the clean frames alone; an error without -av1mi_denoise
   int min_gop = 0;         // -av1mi_min_gop M: the shortest GOP the planner makes, 1 .. gop - gop / 2; 0 = max(1, gop / 4).  Only with -av1mi_scenecut

@@ -657,6 +657,31 @@ typedef struct av1mi_denoise_vec { int8_t dx_p, dy_p, dx_n, dy_n; } av1mi_denois
 int av1mi_denoise_mc_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int strength,
                             int range, int segments, const void *const *d_table, void *const d_dst[3], av1mi_grain_record *d_records, av1mi_denoise_vec *d_vectors);
 
+/* ---- grain covariance: how what the filter removed correlates with its neighbours (av1-go_amd/csrc/grain_cov_kernels.hip).  The grain
+ * records say how STRONG the grain was; white grain of that strength on a picture whose grain had a size looks like another, sharper
+ * noise.  For a plane of a frame, r(x, y) = C(x, y) - out(x, y) inside the true size w x h, C the fed sample and out what either
+ * denoising gather wrote.  For dy = 0 .. 3 and dx = -6 .. 6:
+ *   sum[dy][dx + 6] = the sum of r(x, y) r(x + dx, y + dy) over all (x, y) with 0 <= x, x + dx < w and 0 <= y, y + dy < h
+ * as signed 64-bit integers (|r| <= 1023, a product is below 2^20).  The entries with dy = 0, dx < 0 follow the same formula and equal
+ * their mirror images: one rule, no special case.  Nothing beyond the true size is read; a plane narrower or lower than an offset has no
+ * such pair and the entry is 0.  One record per (segment, plane), [segment * 3 + plane], like the grain records.  Integers only, bit
+ * exact by definition, and integer addition gives the same bytes in any order, run to run.
+ *   offsets   up to (+-6, 3) is what the Yule-Walker equations of AV1's lag-3 neighbourhood need: 24 causal neighbours with dy in -3 .. 0
+ *             and dx in -3 .. 3, whose differences reach (+-6, +-3); the covariance at (-dx, -dy) is the one at (dx, dy).
+ *   no mask   there is no "counted" rule here, and none is needed.  A sample whose neighbourhood moved keeps C exactly: r = 0, it adds
+ *             nothing to any sum, sum[0][6] (the sum of r^2) included.  An end of a run passes through (out = C) and a flat slot has no
+ *             C: both give all-zero records without a path of their own.  Only the ratios sum[d] / sum[0][6] are used downstream
+ *             (av1-go_amd/host/filmgrain.hpp), so samples that were filtered with part of the weight scale numerator and denominator alike.
+ *   limit     a slow change of the picture that the filter half removes is spatially correlated and enters the sums. */
+typedef struct av1mi_grain_cov { int64_t sum[4][13]; } av1mi_grain_cov_record;      /* (the plain name is the function's below) */
+/* Runs BEHIND av1mi_denoise_gather or av1mi_denoise_mc_gather, with their arguments and rules for the planes, the segments and the table
+ * (of which only the C entries are read; a null C means zeros were fed); d_out: the planes that gather wrote (its d_dst), only read here.
+ * d_cov: segments * 3 records [segment * 3 + plane] in device memory (or pinned host memory), 8-byte aligned.  Two launches: k_grain_cov
+ * (all planes and segments) and k_grain_cov_sum.  The partials live in the context (grown on demand).  Asynchronous on the context's
+ * stream; AV1MI_K_SCENE in the profile. */
+int av1mi_grain_cov(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int segments,
+                    const void *const *d_table, void *const d_out[3], av1mi_grain_cov_record *d_cov);
+
 /* ---- tone mapping: an HDR10 source (BT.2020 non-constant luminance, PQ, limited range, 10 bit) becomes BT.709 limited-range SDR at 10 bits
  * (av1-go_amd/csrc/tonemap_kernels.hip, k_tone_map).  Pointwise per 2x2 luma QUAD of planar 4:2:0 planes (four luma samples, one U, one V, the
  * chroma applied to all four), in place.  Integers throughout, bit exact by definition; restated in numpy in tests/tonemap_ref.py.  Every
@@ -845,6 +870,12 @@ typedef struct av1mi_gop_config {
    * wrong light).  The scene analysis keeps reading the frames as fed; the quality records measure against the tone-mapped source, which is
    * the source as coded; with zero input stages av1mi_gop_download_fed returns the tone-mapped planes (the fed buffer IS the coded plane). */
   int tone_map, tone_map_peak;
+  /* The grain covariance (0 = none: nothing new is allocated, launched or accepted, and the session produces the bytes it always did; 1 =
+   * on; "grain covariance" above).  Needs denoise; works with and without denoise_range.  av1mi_gop_submit_stored then makes one more
+   * pair of launches (k_grain_cov, k_grain_cov_sum) behind the batch's denoising gather, on the same stream and in front of the same
+   * event as the grain records; av1mi_gop_frame.grain_cov carries the batch's records.  The fed buffers and everything behind them are
+   * untouched: the coded bytes are those of the session without it. */
+  int grain_cov;
 } av1mi_gop_config;
 
 /* The source layout: what a session opened with a config is FED, as one description.  Everything a caller sizes or strides by — the
@@ -913,6 +944,9 @@ typedef struct av1mi_gop_frame {    /* one collected frame batch; host pointers 
   /* av1mi_gop_config.denoise: segments * 3 grain records [segment * 3 + plane] of this batch ("grain records"), in pinned memory; NULL
    * when the option is off (and for a batch of av1mi_gop_submit_device) */
   const av1mi_grain_record *grain;
+  /* av1mi_gop_config.grain_cov: segments * 3 covariance records [segment * 3 + plane] of this batch ("grain covariance"), in pinned
+   * memory, valid where `grain` is; NULL when the option is off (and for a batch of av1mi_gop_submit_device) */
+  const av1mi_grain_cov_record *grain_cov;
 } av1mi_gop_frame;
 
 typedef struct av1mi_gop av1mi_gop;

@@ -20,6 +20,15 @@ long long av1mi_session_temporal_unit_grain(const av1mi_gop_frame *fr, int seg, 
  * derived from frame_index; apply_grain = 0 where the luma record gives no point.  The model and the measured decoder gain are in
  * av1-go_amd/host/filmgrain.hpp.  bit_depth 8 or 10.  0 = OK, -1 = bad argument. */
 int av1mi_film_grain_from_records(const av1mi_grain_record *records, int bit_depth, int frame_index, av1mi_film_grain *out);
+/* The same with COLOURED grain: cov = the frame's three covariance records (include/av1mi.h "grain covariance": cov[plane], e.g.
+ * av1mi_gop_frame.grain_cov + segment * 3); lag 0 .. 3 = the largest ar_coeff_lag coded.  Per plane the autoregressive coefficients that
+ * give the synthesised grain the removed grain's normalised covariance (Yule-Walker over the spec's neighbour order), one
+ * ar_coeff_shift_minus_6 for the three planes, and the scaling points divided by the square root of the quantised filter's variance gain,
+ * so that the total variance stays what the records say; a plane falls back to a smaller lag and finally to white grain where its
+ * covariance is empty or the filter would be unstable.  lag 0 gives av1mi_film_grain_from_records' bytes.  The model is in
+ * av1-go_amd/host/filmgrain.hpp.  0 = OK, -1 = bad argument. */
+int av1mi_film_grain_from_records_ar(const av1mi_grain_record *records, const av1mi_grain_cov_record *cov, int bit_depth, int frame_index, int lag,
+                                     av1mi_film_grain *out);
 /* the luma scaling value at mid grey of a set of parameters (0 = no grain): the stats file's grain: field */
 int av1mi_film_grain_mid_grey(const av1mi_film_grain *g);
 

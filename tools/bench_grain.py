@@ -4,7 +4,9 @@
 1. k_denoise_gather + k_grain_sum beside k_frames_gather (the floor) and k_deint_gather on the same batch: 4K 10-bit x 12 segments and
    1080p 8-bit x 12, every leg alternated in one process, HIP events; bytes/s against 3.5 x bytes (the deinterlacer's row) and against the
    denoiser's own 4 x bytes (three reads, one write).
-   k_denoise_search + k_denoise_mc_gather + k_grain_sum (av1mi_denoise_mc_gather, range 4 and 8) are further legs of the same alternation.
+   k_denoise_search + k_denoise_mc_gather + k_grain_sum (av1mi_denoise_mc_gather, range 4 and 8) are further legs of the same alternation,
+   and so is k_grain_cov + k_grain_cov_sum (av1mi_grain_cov, "grain covariance") on the same planes: what -av1mi_grain_lag adds to a batch,
+   beside the gather it follows.
 2. av1mi_run_transcode at q 23 and 24 on tests/synth.py content and on a translating clip (tests/denoise_mc_clips.py, 3 / -2 samples per
    frame), with Gaussian grain of sigma 2, 4, 8 added per frame; without -av1mi_denoise, with it, and with -av1mi_denoise_range 4 and 8:
    coded bytes and frames per second, wall clock.
@@ -47,9 +49,11 @@ def kernels(ctx, w, h, bd, segs, reps=7, launches=10):
     d_three, d_one = ctx.to_device(three), ctx.to_device(one)
     d_dst = [ctx.alloc(segs * b) for b in nbytes]
     d_rec = ctx.alloc(segs * 3 * 16 * 16)
+    d_cov = ctx.alloc(segs * 3 * av1mi.GRAIN_COV_DTYPE.itemsize)
     legs = dict(denoise=lambda: ctx.denoise_gather(bd, sizes, sizes, 4, segs, d_three, d_dst, d_rec),
                 denoise_mc_range4=lambda: ctx.denoise_mc_gather(bd, sizes, sizes, 4, 4, segs, d_three, d_dst, d_rec),
                 denoise_mc_range8=lambda: ctx.denoise_mc_gather(bd, sizes, sizes, 4, 8, segs, d_three, d_dst, d_rec),
+                grain_cov=lambda: ctx.grain_cov(bd, sizes, sizes, segs, d_three, d_dst, d_cov),      # (no branch of it depends on the content)
                 denoise_no_records=lambda: ctx.denoise_gather(bd, sizes, sizes, 4, segs, d_three, d_dst, None),
                 deint=lambda: ctx.deinterlace_gather(bd, sizes, sizes, 0, segs, d_three, d_dst),
                 frames=lambda: ctx.frames_gather(nbytes, segs, d_one, d_dst))
@@ -74,7 +78,7 @@ def kernels(ctx, w, h, bd, segs, reps=7, launches=10):
     out["denoise_gb_per_s_at_4_x_bytes"] = 4 * frame / md / 1e6
     out["deint_gb_per_s_at_3.5_x_bytes"] = 3.5 * frame / statistics.median(times["deint"]) / 1e6
     out["frames_gb_per_s_at_2_x_bytes"] = 2 * frame / statistics.median(times["frames"]) / 1e6
-    for b in d_store + d_dst + [d_three, d_one, d_rec]:
+    for b in d_store + d_dst + [d_three, d_one, d_rec, d_cov]:
         b.free()
     return out
 
