@@ -116,27 +116,56 @@ hipError_t launch_deblock_cdef(const DeblockCdefLaunch &L, hipStream_t s);
 
 // K7: loop restoration of one plane, frames stacked vertically
 struct LrLaunch {
-  const void *cdef, *dbl; void *out;
-  int stride, w, h, bd, ss, unit_size, nframes;
-  const int8_t *units; size_t unit_frame_stride;   // 8 bytes per unit; units between frames (0 = shared)
+  const void *cdef = nullptr, *dbl = nullptr; void *out = nullptr;
+  int stride = 0, w = 0, h = 0, bd = 0, ss = 0, unit_size = 0, nframes = 0;
+  const int8_t *units = nullptr; size_t unit_frame_stride = 0;   // 8 bytes per unit; units between frames (0 = shared)
   // the on/off decision (orig != nullptr): the source plane, and per (frame, stripe) two 64-bit sums: squared error of the restored
-  // samples, of the CDEF samples (zeroed by the caller; sse_stripes = lr_stripes(h, ss))
-  const void *orig; unsigned long long *sse; int sse_stripes;
+  // samples, of the CDEF samples (zeroed by the caller; sse_stripes = LrGeom::stripes)
+  const void *orig = nullptr; unsigned long long *sse = nullptr; int sse_stripes = 0;
   // two-pass form of the decision (pass 0 = everything in one launch): pass 1 restores only the tiles the sums run over, pass 2 the
   // others, and only in the frames whose flag keep[f * keep_stride] (written by the decision between the two) is set
-  int pass; const uint8_t *keep; int keep_stride;
-  int no_sgr;       // the caller's promise that no unit is self-guided (type 2): the kernel without that path's LDS
+  int pass = 0; const uint8_t *keep = nullptr; int keep_stride = 0;
+  int no_sgr = 0;   // the caller's promise that no unit is self-guided (type 2): the kernel without that path's LDS
 };
+// K7's geometry, host and device: the ONE place it is computed (the launchers, the C ABI's scratch sizes and the kernels read it).  A
+// workgroup owns the intersection of a stripe (64 rows, 32 for 4:2:0 chroma, offset 8 luma rows upwards) with a column band no wider
+// than a unit or 64 samples; workgroups = bands x stripes x frames.
+struct LrGeom {
+  int w, h, unit_size, nframes, stripe_h, stripe_off, tile_w, bands, stripes, unit_rows, unit_cols;
+  __host__ __device__ static int stripes_of(int h, int ss) { return (h + (8 >> ss) + (64 >> ss) - 1) / (64 >> ss); }
+  __host__ __device__ LrGeom(int w_, int h_, int ss, int unit_size_, int nframes_) : w(w_), h(h_), unit_size(unit_size_), nframes(nframes_) {
+    stripe_h = 64 >> ss; stripe_off = 8 >> ss; tile_w = unit_size < 64 ? unit_size : 64;
+    bands = (w + tile_w - 1) / tile_w; stripes = stripes_of(h, ss);
+    unit_rows = (h + (unit_size >> 1)) / unit_size; unit_cols = (w + (unit_size >> 1)) / unit_size;
+    if (unit_rows < 1) unit_rows = 1;
+    if (unit_cols < 1) unit_cols = 1;
+  }
+  explicit LrGeom(const LrLaunch &L) : LrGeom(L.w, L.h, L.ss, L.unit_size, L.nframes) {}
+  __host__ __device__ unsigned workgroups() const { return (unsigned)(bands * stripes * nframes); }
+  // the stripe's first row (the first stripe starts above the picture); a tile writes the stripe's rows inside the picture
+  __host__ __device__ int first_row(int stripe) const { return stripe * stripe_h - stripe_off; }
+  // the unit of the tile whose first written sample is (x0, y0)
+  __host__ __device__ size_t unit_index(int x0, int y0) const {
+    const int ur = (y0 + stripe_off) / unit_size, uc = x0 / unit_size;
+    return (size_t)(ur < unit_rows - 1 ? ur : unit_rows - 1) * unit_cols + (uc < unit_cols - 1 ? uc : unit_cols - 1);
+  }
+  // The decision's sums run over an EIGHTH of the plane — the 64-column x stripe tiles with (column + stripe) % 8 == 0, a diagonal
+  // pattern over the whole picture (every tile when the plane has fewer than 32) — so the decision costs an eighth of a source read.
+  __host__ __device__ bool sampled(int x0, int stripe) const { return ((w + 63) >> 6) * stripes < 32 || (((x0 >> 6) + stripe) & 7) == 0; }
+  // the decision's scratch: per (frame, stripe) one pair of 64-bit sums
+  __host__ __device__ size_t sum_pairs() const { return (size_t)nframes * stripes; }
+};
+// the first pair of plane p in the scratch of a 4:2:0 frame's three planes (luma geometry y, chroma geometry c), end to end
+__host__ __device__ inline size_t lr_first_pair(const LrGeom &y, const LrGeom &c, int p) { return p ? y.sum_pairs() + (p - 1) * c.sum_pairs() : 0; }
 hipError_t launch_lr(const LrLaunch &L, hipStream_t s);
 // the three planes of 4:2:0 frames in ONE launch: their grids end to end, a workgroup takes its plane from its index.  The planes
 // share bd, unit_size, nframes, pass and no_sgr; plane 0 is the luma plane (ss 0), planes 1 and 2 are subsampled (ss 1)
 struct LrYuvLaunch { LrLaunch plane[3]; unsigned first[3]; };      // first: filled in by launch_lr_yuv (plane p's first workgroup)
 hipError_t launch_lr_yuv(LrYuvLaunch &Y, hipStream_t s);
-int lr_stripes(int h, int ss);
 hipError_t launch_zero16(void *p, size_t bytes, hipStream_t s);
-hipError_t launch_lr_decide3(unsigned long long *sse, int nframes, int stripes_y, int stripes_c, uint8_t *on, hipStream_t s);
 hipError_t launch_extend(void *plane, int stride, int w, int h, int vw, int vh, int bd, int nframes, hipStream_t s);
-hipError_t launch_lr_decide(const unsigned long long *sse, int nframes, int stripes, uint8_t *on, int on_stride, hipStream_t s);
+// the decision over the sums of nplanes = 1 plane (geometry y) or the 3 of 4:2:0 frames (y, c, c): lr_kernel.hip k_lr_decide
+hipError_t launch_lr_decide(unsigned long long *sse, const LrGeom &y, const LrGeom &c, int nplanes, uint8_t *on, int on_stride, bool clear, hipStream_t s);
 
 // inter (P-frame) pipeline over the t-th frames of a batch of segments, stacked like the intra job
 struct InterLaunch {

@@ -108,6 +108,12 @@ int check_lr_unit(av1mi_ctx *ctx, int unit_size, int subsampled) {      // 32 is
   if (unit_size == 64 || unit_size == 128 || unit_size == 256 || (unit_size == 32 && subsampled)) return AV1MI_OK;
   return fail(ctx, AV1MI_E_INVAL, "restoration unit size %d not allowed", unit_size);
 }
+int check_lr_plane(av1mi_ctx *ctx, const av1mi::LrLaunch &L) {      // ... of one plane's restoration (av1mi_lr_frames, av1mi_lr_frames_decide)
+  if (!L.cdef || !L.dbl || !L.out || !L.units || L.out == L.cdef || L.out == L.dbl) return fail(ctx, AV1MI_E_INVAL, "null or aliased device pointer");
+  if (int rc = check_bd(ctx, L.bd)) return rc;
+  if (L.w <= 0 || L.h <= 0 || L.stride < L.w) return fail(ctx, AV1MI_E_INVAL, "bad plane geometry %dx%d stride %d", L.w, L.h, L.stride);
+  return check_lr_unit(ctx, L.unit_size, L.ss);
+}
 int check_tx_launch(av1mi_ctx *ctx, int tx_size, const void *coef, const void *plane, int stride, int nblocks) {
   if (tx_size < 0 || tx_size >= AV1MI_TX_SIZES_ALL) return fail(ctx, AV1MI_E_INVAL, "tx_size %d out of range", tx_size);
   if (!coef || !plane) return fail(ctx, AV1MI_E_INVAL, "null device pointer");
@@ -492,44 +498,36 @@ int av1mi_deblock_cdef_frames(av1mi_ctx *ctx, const av1mi_deblock_cdef_job *j) {
 int av1mi_lr_frames(av1mi_ctx *ctx, const void *d_cdef, const void *d_deblocked, void *d_out, int stride, int w, int h,
                     int bd, int subsampled, int unit_size, const int8_t *d_units, size_t unit_frame_stride, int nframes) {
   BIND(ctx);
-  if (!d_cdef || !d_deblocked || !d_out || !d_units || d_out == d_cdef || d_out == d_deblocked)
-    return fail(ctx, AV1MI_E_INVAL, "null or aliased device pointer");
-  if (int rc = check_bd(ctx, bd)) return rc;
-  if (w <= 0 || h <= 0 || stride < w) return fail(ctx, AV1MI_E_INVAL, "bad plane geometry %dx%d stride %d", w, h, stride);
-  if (int rc = check_lr_unit(ctx, unit_size, subsampled)) return rc;
+  av1mi::LrLaunch L;      // (every member by name; the decision's and the two-pass form's stay null / 0)
+  L.cdef = d_cdef; L.dbl = d_deblocked; L.out = d_out; L.stride = stride; L.w = w; L.h = h; L.bd = bd; L.ss = subsampled ? 1 : 0;
+  L.unit_size = unit_size; L.units = d_units; L.unit_frame_stride = unit_frame_stride; L.nframes = nframes;
+  if (int rc = check_lr_plane(ctx, L)) return rc;
   if (int rc = check_nframes(ctx, nframes)) return rc;
   if (nframes == 0) return AV1MI_OK;
-  av1mi::LrLaunch L = { d_cdef, d_deblocked, d_out, stride, w, h, bd, subsampled ? 1 : 0, unit_size, nframes, d_units, unit_frame_stride, nullptr, nullptr, 0, 0, nullptr, 0, 0 };
   { ProfScope ps(ctx, AV1MI_K_LR); HIP_TRY(ctx, av1mi::launch_lr(L, ctx->stream)); }
   return AV1MI_OK;
 }
 
-size_t av1mi_lr_decide_scratch_bytes(int h, int subsampled, int nframes) {
-  return (size_t)(nframes > 0 ? nframes : 0) * (size_t)av1mi::lr_stripes(h, subsampled ? 1 : 0) * 16;
-}
+size_t av1mi_lr_decide_scratch_bytes(int h, int subsampled, int nframes) { return (size_t)(nframes > 0 ? nframes : 0) * av1mi::LrGeom::stripes_of(h, subsampled ? 1 : 0) * 16; }
 int av1mi_lr_frames_decide(av1mi_ctx *ctx, const void *d_cdef, const void *d_deblocked, void *d_out, int stride, int w, int h, int bd, int subsampled,
                            int unit_size, const int8_t *d_units, size_t unit_frame_stride, int nframes, const void *d_orig, void *d_scratch, uint8_t *d_on,
                            int on_stride) {
   BIND(ctx);
-  if (!d_cdef || !d_deblocked || !d_out || !d_units || !d_orig || !d_scratch || !d_on || d_out == d_cdef || d_out == d_deblocked)
-    return fail(ctx, AV1MI_E_INVAL, "null or aliased device pointer");
-  if (int rc = check_bd(ctx, bd)) return rc;
-  if (w <= 0 || h <= 0 || stride < w) return fail(ctx, AV1MI_E_INVAL, "bad plane geometry %dx%d stride %d", w, h, stride);
-  if (int rc = check_lr_unit(ctx, unit_size, subsampled)) return rc;
+  if (!d_orig || !d_scratch || !d_on) return fail(ctx, AV1MI_E_INVAL, "null or aliased device pointer");
+  av1mi::LrLaunch L;
+  L.cdef = d_cdef; L.dbl = d_deblocked; L.out = d_out; L.stride = stride; L.w = w; L.h = h; L.bd = bd; L.ss = subsampled ? 1 : 0;
+  L.unit_size = unit_size; L.units = d_units; L.unit_frame_stride = unit_frame_stride; L.nframes = nframes;
+  if (int rc = check_lr_plane(ctx, L)) return rc;
   if (nframes < 0 || nframes > 65535 || on_stride < 1) return fail(ctx, AV1MI_E_INVAL, "nframes %d / on_stride %d out of range", nframes, on_stride);
   if (nframes == 0) return AV1MI_OK;
-  const int stripes = av1mi::lr_stripes(h, subsampled ? 1 : 0);
   HIP_TRY(ctx, hipMemsetAsync(d_scratch, 0, av1mi_lr_decide_scratch_bytes(h, subsampled, nframes), ctx->stream));
-  av1mi::LrLaunch L = { d_cdef, d_deblocked, d_out, stride, w, h, bd, subsampled ? 1 : 0, unit_size, nframes, d_units, unit_frame_stride, d_orig,
-                        (unsigned long long *)d_scratch, stripes, 0, nullptr, 0, 0 };
+  L.orig = d_orig; L.sse = (unsigned long long *)d_scratch; L.sse_stripes = av1mi::LrGeom::stripes_of(h, L.ss);
   { ProfScope ps(ctx, AV1MI_K_LR); HIP_TRY(ctx, av1mi::launch_lr(L, ctx->stream)); }
-  HIP_TRY(ctx, av1mi::launch_lr_decide((const unsigned long long *)d_scratch, nframes, stripes, d_on, on_stride, ctx->stream));
+  HIP_TRY(ctx, av1mi::launch_lr_decide(L.sse, av1mi::LrGeom(L), av1mi::LrGeom(L), 1, d_on, on_stride, false, ctx->stream));      // (not cleared: the caller keeps the sums)
   return AV1MI_OK;
 }
 
-size_t av1mi_lr_yuv_decide_scratch_bytes(int h, int nframes) {
-  return av1mi_lr_decide_scratch_bytes(h, 0, nframes) + 2 * av1mi_lr_decide_scratch_bytes(h / 2, 1, nframes);
-}
+size_t av1mi_lr_yuv_decide_scratch_bytes(int h, int nframes) { return av1mi_lr_decide_scratch_bytes(h, 0, nframes) + 2 * av1mi_lr_decide_scratch_bytes(h / 2, 1, nframes); }
 int av1mi_lr_yuv_decide(av1mi_ctx *ctx, const av1mi_lr_decide_job *j) { return av1mi::lr_yuv_decide_with(ctx, j, false); }
 
 }  // extern "C"
@@ -542,9 +540,10 @@ int av1mi_lr_yuv_decide(av1mi_ctx *ctx, const av1mi_lr_decide_job *j) { return a
 int av1mi::lr_yuv_decide_with(av1mi_ctx *ctx, const av1mi_lr_decide_job *j, bool scratch_clean) {
   BIND(ctx);
   if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
-  const void *ptrs[] = { j->d_cdef_y, j->d_cdef_u, j->d_cdef_v, j->d_dbl_y, j->d_dbl_u, j->d_dbl_v, j->d_out_y, j->d_out_u, j->d_out_v,
-                         j->d_orig_y, j->d_orig_u, j->d_orig_v, j->d_units_y, j->d_units_uv, j->d_scratch, j->d_on };
-  for (const void *p : ptrs) if (!p) return fail(ctx, AV1MI_E_INVAL, "null device pointer");
+  const void *cdef[3] = { j->d_cdef_y, j->d_cdef_u, j->d_cdef_v }, *dbl[3] = { j->d_dbl_y, j->d_dbl_u, j->d_dbl_v }, *orig[3] = { j->d_orig_y, j->d_orig_u, j->d_orig_v };
+  void *out[3] = { j->d_out_y, j->d_out_u, j->d_out_v };
+  for (int p = 0; p < 3; p++) if (!cdef[p] || !dbl[p] || !out[p] || !orig[p]) return fail(ctx, AV1MI_E_INVAL, "null device pointer");
+  if (!j->d_units_y || !j->d_units_uv || !j->d_scratch || !j->d_on) return fail(ctx, AV1MI_E_INVAL, "null device pointer");
   if ((uintptr_t)j->d_scratch & 15) return fail(ctx, AV1MI_E_INVAL, "misaligned scratch");
   if (int rc = check_bd(ctx, j->bit_depth)) return rc;
   if (j->width <= 0 || j->height <= 0 || (j->width & 1) || (j->height & 1) || j->stride_y < j->width || j->stride_uv < j->width / 2)
@@ -552,26 +551,26 @@ int av1mi::lr_yuv_decide_with(av1mi_ctx *ctx, const av1mi_lr_decide_job *j, bool
   if (int rc = check_lr_unit(ctx, j->unit_size, 0)) return rc;
   if (int rc = check_nframes(ctx, j->nframes)) return rc;
   if (j->nframes == 0) return AV1MI_OK;
-  const int n = j->nframes, sy = av1mi::lr_stripes(j->height, 0), sc = av1mi::lr_stripes(j->height / 2, 1);
+  const int n = j->nframes;
   unsigned long long *sse = (unsigned long long *)j->d_scratch;
   if (!scratch_clean) HIP_TRY(ctx, av1mi::launch_zero16(sse, av1mi_lr_yuv_decide_scratch_bytes(j->height, n), ctx->stream));
-  const void *cdef[3] = { j->d_cdef_y, j->d_cdef_u, j->d_cdef_v }, *dbl[3] = { j->d_dbl_y, j->d_dbl_u, j->d_dbl_v }, *orig[3] = { j->d_orig_y, j->d_orig_u, j->d_orig_v };
-  void *out[3] = { j->d_out_y, j->d_out_u, j->d_out_v };
   for (int p = 0; p < 3; p++) if (out[p] == cdef[p] || out[p] == dbl[p]) return fail(ctx, AV1MI_E_INVAL, "aliased device pointer");
+  const av1mi::LrGeom gy(j->width, j->height, 0, j->unit_size, n), gc(j->width / 2, j->height / 2, 1, j->unit_size, n);
+  av1mi::LrYuvLaunch Y;
+  for (int p = 0; p < 3; p++) {
+    av1mi::LrLaunch &L = Y.plane[p];
+    L.cdef = cdef[p]; L.dbl = dbl[p]; L.out = out[p]; L.orig = orig[p]; L.bd = j->bit_depth; L.ss = p ? 1 : 0; L.unit_size = j->unit_size; L.nframes = n;
+    L.stride = p ? j->stride_uv : j->stride_y; L.w = (p ? gc : gy).w; L.h = (p ? gc : gy).h; L.sse_stripes = (p ? gc : gy).stripes;
+    L.units = p ? j->d_units_uv : j->d_units_y; L.unit_frame_stride = p ? j->unit_frame_stride_uv : j->unit_frame_stride_y;
+    L.sse = sse + 2 * av1mi::lr_first_pair(gy, gc, p); L.keep = j->d_on + p; L.keep_stride = 3; L.no_sgr = j->no_self_guided_units != 0;
+  }
   // pass 1: the tiles the decision's sums run over (an eighth of a large plane); the decision; pass 2: the other tiles of the frames
   // that keep their restoration — a plane that is switched off costs an eighth of its restoration.  One launch per pass: the three
   // planes' grids end to end (launch_lr_yuv)
   for (int pass = 1; pass <= 2; pass++) {
-    av1mi::LrYuvLaunch Y;
-    for (int p = 0; p < 3; p++)
-      Y.plane[p] = { cdef[p], dbl[p], out[p], p ? j->stride_uv : j->stride_y, p ? j->width / 2 : j->width, p ? j->height / 2 : j->height, j->bit_depth, p ? 1 : 0,
-                     j->unit_size, n, p ? j->d_units_uv : j->d_units_y, p ? j->unit_frame_stride_uv : j->unit_frame_stride_y, orig[p],
-                     sse + 2 * ((size_t)(p ? n * sy + (p - 1) * n * sc : 0)), p ? sc : sy, pass, j->d_on + p, 3, j->no_self_guided_units != 0 };
-    {
-      ProfScope ps(ctx, AV1MI_K_LR);
-      HIP_TRY(ctx, av1mi::launch_lr_yuv(Y, ctx->stream));
-    }
-    if (pass == 1) HIP_TRY(ctx, av1mi::launch_lr_decide3(sse, n, sy, sc, j->d_on, ctx->stream));
+    for (int p = 0; p < 3; p++) Y.plane[p].pass = pass;
+    { ProfScope ps(ctx, AV1MI_K_LR); HIP_TRY(ctx, av1mi::launch_lr_yuv(Y, ctx->stream)); }
+    if (pass == 1) HIP_TRY(ctx, av1mi::launch_lr_decide(sse, gy, gc, 3, j->d_on, 3, true, ctx->stream));
   }
   return AV1MI_OK;
 }

@@ -12,7 +12,7 @@
 //                     main: wait uploaded -> [k_input_convert] -> [k_chroma_convert] -> [k_scale | k_crop_copy]
 //   code_blocks       main: k_intra_pipe | [k_me_down + k_me_coarse] + k_me_int + k_inter_pipe -> kernel_done
 //   download_symbols  down: wait kernel_done -> D2H of the symbols into pinned memory
-//   loop_filters      main: deblock + CDEF (one kernel), k_lr_yuv (the sampled tiles of the three planes) -> k_lr_decide3 -> k_lr_yuv (the rest where
+//   loop_filters      main: deblock + CDEF (one kernel), k_lr_yuv (the sampled tiles of the three planes) -> k_lr_decide -> k_lr_yuv (the rest where
 //                     restoration stays on) -> reference -> filters_done;  down: (symbols for the host) the decision -> downloaded
 //   measure_quality   main: (quality_stats) k_quality_tiles + k_quality_sum, the records written into the slot's pinned memory -> quality_done
 //   start_coder       side: (GPU entropy coding) wait filters_done -> two memsets, k_av1_info / tokens / chains;  back: k_av1_code -> k_av1_gather,

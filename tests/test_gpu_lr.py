@@ -100,6 +100,71 @@ def test_lr_on_off_decision_equals_the_oracle(ctx, O, bd, ss):
         assert exp[1] == 0 and (exp[2] == 1 or (lr[2] == cdef[2]).mean() > 0.2)
 
 
+def _decide(ctx, cdef, dbl, src, bd, ss, unit, units, w=None):
+    """av1mi_lr_frames_decide on [frame, row, column] arrays whose rows may be longer than the plane's width w; the output buffer starts
+    out as 0xA5 bytes.  Returns the output buffer as it is, padding columns included, the flags, and the sums left in the scratch."""
+    nf, h, stride = cdef.shape
+    d_c, d_d, d_u, d_s = ctx.to_device(cdef), ctx.to_device(dbl), ctx.to_device(units), ctx.to_device(src)
+    d_o, d_on = ctx.to_device(np.full(cdef.shape, 0xA5A5 if cdef.itemsize == 2 else 0xA5, cdef.dtype)), ctx.to_device(np.full(nf, 7, np.uint8))
+    d_scr = ctx.alloc(ctx.lr_decide_scratch_bytes(h, ss, nf))
+    ctx.lr_frames_decide(d_c, d_d, d_o, stride, w or stride, h, bd, ss, unit, d_u, units.shape[1] * units.shape[2], nf, d_s, d_scr, d_on)
+    got, on = d_o.download(cdef.shape, cdef.dtype), d_on.download((nf,), np.uint8)
+    sums = d_scr.download((nf, ctx.lr_decide_scratch_bytes(h, ss, nf) // (16 * nf), 2), np.uint64)      # [frame, stripe, (restored, CDEF)]
+    for b in (d_c, d_d, d_u, d_s, d_o, d_on, d_scr):
+        b.free()
+    return got, on, sums
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("ss", [0, 1])
+@pytest.mark.parametrize("h,w", [(72, 70), (40, 23)])
+def test_lr_widths_that_are_no_multiple_of_4(ctx, O, bd, ss, h, w):
+    """the scalar Wiener path and the clamped staging (a column band whose width is no multiple of 4): at 72 x 70 a band of 64 columns
+    that touches the left edge and one of 6, two luma stripes (rows 0-55 and 56-71); 40 x 23 is one narrow band.  Every unit type,
+    with and without the decision, bit-exact against the oracle"""
+    rng = np.random.default_rng(h * 100 + w + bd + ss)
+    nf, unit = 2, 64
+    cdef = np.stack([make_image(rng, h, w, bd) for _ in range(nf)])
+    dbl = np.stack([make_image(rng, h, w, bd) for _ in range(nf)])
+    units = np.stack([_random_units(rng, O, unit, h, w) for _ in range(nf)])
+    lr = np.stack([O.lr_plane(cdef[f], dbl[f], bd, ss, unit, units[f]) for f in range(nf)])
+    got = _run(ctx, cdef, dbl, bd, ss, unit, units)
+    for f in range(nf):
+        assert (got[f] == lr[f]).all(), (f, np.argwhere(got[f] != lr[f])[:4])
+    # sources: frame 0 lies at the CDEF samples plus noise, frame 1 at the restored ones
+    src = np.stack([np.clip(cdef[0].astype(int) + rng.integers(-1, 2, cdef[0].shape), 0, (1 << bd) - 1), lr[1]]).astype(cdef.dtype)
+    got, on, _ = _decide(ctx, cdef, dbl, src, bd, ss, unit, units)
+    for f in range(nf):
+        assert (got[f] == lr[f]).all(), (f, np.argwhere(got[f] != lr[f])[:4])
+    assert on.tolist() == [O.lr_select((src[f],), (cdef[f],), (lr[f],), bd, ss)[1][0] for f in range(nf)]
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+def test_lr_row_stride_that_is_no_multiple_of_4(ctx, O, bd):
+    """a plane 136 wide in buffers of row stride 138: every second row of the packed Wiener path's four-sample stores and source loads
+    is unaligned.  Wiener units only, the decision on; the two padding columns of the output stay as they were"""
+    rng = np.random.default_rng(138 + bd)
+    nf, unit, h, w, stride = 2, 64, 72, 136, 138
+    cdef = np.stack([make_image(rng, h, stride, bd) for _ in range(nf)])
+    dbl = np.stack([make_image(rng, h, stride, bd) for _ in range(nf)])
+    units = np.zeros((nf, O.lr_units(unit, h), O.lr_units(unit, w), 8), np.int8)
+    for u in units.reshape(-1, 8):
+        u[:] = O.lr_unit_wiener((rng.integers(-5, 11), rng.integers(-23, 9), rng.integers(-17, 47)),
+                                (rng.integers(-5, 11), rng.integers(-23, 9), rng.integers(-17, 47)))
+    lr = np.stack([O.lr_plane(cdef[f, :, :w], dbl[f, :, :w], bd, 0, unit, units[f]) for f in range(nf)])
+    src = make_image(rng, nf * h, stride, bd).reshape(nf, h, stride)
+    src[0, :, :w] = np.clip(cdef[0, :, :w].astype(int) + rng.integers(-1, 2, (h, w)), 0, (1 << bd) - 1)
+    src[1, :, :w] = lr[1]
+    got, on, sums = _decide(ctx, cdef, dbl, src, bd, 0, unit, units, w=w)
+    assert (got[:, :, :w] == lr).all(), np.argwhere(got[:, :, :w] != lr)[:4]
+    assert (got[:, :, w:] == (0xA5 if bd == 8 else 0xA5A5)).all(), "the padding columns of the output were written"
+    assert on.tolist() == [O.lr_select((src[f, :, :w],), (cdef[f, :, :w],), (lr[f],), bd, 0)[1][0] for f in range(nf)]
+    # the sums stay in the caller's scratch: exact, per frame and luma stripe (rows 0-55, 56-71; six tiles, all in the decision's sample)
+    sq = lambda x, f, r: int(((x[f, r, :w].astype(np.int64) - src[f, r, :w].astype(np.int64)) ** 2).sum())
+    exp = [[[sq(lr, f, r), sq(cdef, f, r)] for r in (slice(0, 56), slice(56, 72))] for f in range(nf)]
+    assert sums.tolist() == exp
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("w,h,bd", [(200, 136, 8), (136, 72, 10), (576, 328, 10)])      # the last: luma has 54 tiles, sampled sparsely
 def test_three_plane_decide_equals_three_single_plane_calls(ctx, av1mi, O, w, h, bd):
