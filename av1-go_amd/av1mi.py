@@ -96,7 +96,18 @@ class LrDecideJob(C.Structure):
                 ("d_out_y", C.c_void_p), ("d_out_u", C.c_void_p), ("d_out_v", C.c_void_p),
                 ("d_orig_y", C.c_void_p), ("d_orig_u", C.c_void_p), ("d_orig_v", C.c_void_p),
                 ("d_units_y", C.c_void_p), ("d_units_uv", C.c_void_p), ("unit_frame_stride_y", C.c_size_t), ("unit_frame_stride_uv", C.c_size_t),
-                ("d_scratch", C.c_void_p), ("d_on", C.c_void_p), ("no_self_guided_units", C.c_int)]
+                ("d_scratch", C.c_void_p), ("d_on", C.c_void_p), ("no_self_guided_units", C.c_int),
+                ("d_units_v", C.c_void_p), ("unit_frame_stride_v", C.c_size_t)]
+
+
+class LrSearchJob(C.Structure):
+    """include/av1mi.h av1mi_lr_search_job"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("bit_depth", C.c_int), ("nframes", C.c_int), ("unit_size", C.c_int), ("qindex", C.c_int),
+                ("stride_y", C.c_int), ("stride_uv", C.c_int),
+                ("d_cdef_y", C.c_void_p), ("d_cdef_u", C.c_void_p), ("d_cdef_v", C.c_void_p),
+                ("d_dbl_y", C.c_void_p), ("d_dbl_u", C.c_void_p), ("d_dbl_v", C.c_void_p),
+                ("d_orig_y", C.c_void_p), ("d_orig_u", C.c_void_p), ("d_orig_v", C.c_void_p),
+                ("d_scratch", C.c_void_p), ("d_units_y", C.c_void_p), ("d_units_u", C.c_void_p), ("d_units_v", C.c_void_p), ("d_choice", C.c_void_p)]
 
 
 class GopConfig(C.Structure):
@@ -106,7 +117,7 @@ class GopConfig(C.Structure):
                 ("source_height", C.c_int), ("quality_stats", C.c_int), ("coarse_range", C.c_int), ("source_chroma", C.c_int),
                 ("source_bit_depth", C.c_int), ("store_frames", C.c_int), ("deinterlace", C.c_int), ("denoise", C.c_int),
                 ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int), ("crop_height", C.c_int), ("denoise_range", C.c_int),
-                ("tone_map", C.c_int), ("tone_map_peak", C.c_int), ("grain_cov", C.c_int)]
+                ("tone_map", C.c_int), ("tone_map_peak", C.c_int), ("grain_cov", C.c_int), ("lr_search", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -120,7 +131,8 @@ class GopFrame(C.Structure):
                 ("uv_mode", C.c_void_p), ("mv", C.c_void_p), ("skip", C.c_void_p), ("lev_y", C.c_void_p), ("lev_u", C.c_void_p),
                 ("lev_v", C.c_void_p), ("tiles_per_frame", C.c_int), ("tile_size", C.c_void_p), ("tile_payload", C.c_void_p),
                 ("payload_bytes", C.c_uint64), ("lr_on", C.c_void_p), ("key_block_size", C.c_int), ("key_modes_stride", C.c_int),
-                ("key_modes_band", C.c_int), ("quality", C.c_void_p), ("grain", C.c_void_p), ("grain_cov", C.c_void_p)]
+                ("key_modes_band", C.c_int), ("quality", C.c_void_p), ("grain", C.c_void_p), ("grain_cov", C.c_void_p),
+                ("lr_units", C.c_void_p * 3), ("lr_units_per_frame", C.c_int * 3), ("lr_choice", C.c_void_p)]
 
 
 def policy_frame_params(base_q_idx, bit_depth, frame_type):
@@ -247,7 +259,7 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None, tone_map=0, tone_map_peak=0, grain_cov=None):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None, tone_map=0, tone_map_peak=0, grain_cov=None, lr_search=None):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
@@ -279,6 +291,8 @@ class GopSession:
             self.cfg.denoise_range = int(denoise_range)
         if grain_cov is not None:
             self.cfg.grain_cov = int(grain_cov)
+        if lr_search is not None:       # 1 = a Wiener record or none chosen per restoration unit (av1mi_gop_config.lr_search)
+            self.cfg.lr_search = int(lr_search)
         # tone_map: 1 = every batch is tone-mapped (PQ / BT.2020 -> SDR / BT.709) in place behind the input stages; tone_map_peak: cd/m2, 0 = 1000
         self.cfg.tone_map, self.cfg.tone_map_peak = int(tone_map), int(tone_map_peak)
         if crop is not None:
@@ -364,6 +378,10 @@ class GopSession:
             out["quality"] = _view(f.quality, (S, 3), QUALITY_DTYPE)
         if f.grain:        # denoise: records [segment, plane, bin] (GRAIN_DTYPE)
             out["grain"] = _view(f.grain, (S, 3, GRAIN_BINS), GRAIN_DTYPE)
+        if f.lr_choice:    # lr_search: the chosen candidates [segment, unit of Y, U, V end to end] and the planes' records [segment, unit, 8]
+            per = list(f.lr_units_per_frame)
+            out["lr_choice"] = _view(f.lr_choice, (S, sum(per)), np.uint8)
+            out["lr_units"] = [_view(f.lr_units[p], (S, per[p], 8), np.int8) for p in range(3)]
         if f.grain_cov:    # grain_cov: records [segment, plane] (GRAIN_COV_DTYPE)
             out["grain_cov"] = _view(f.grain_cov, (S, 3), GRAIN_COV_DTYPE)
         if f.key_block_size == 32:
@@ -457,6 +475,38 @@ def tone_map_tables(peak, lib=None):
     if lib.av1mi_tone_map_tables(int(peak), C.byref(t)) != 0:
         raise ValueError("av1mi_tone_map_tables: peak %r out of range (100 .. 10000)" % (peak,))
     return t
+
+
+LR_SEARCH_CANDIDATES = 9      # AV1MI_LR_SEARCH_CANDIDATES
+
+
+def lr_search_units(width, height, unit_size=64):
+    """units of a frame's three planes together (av1mi_lr_search_units)"""
+    return int(load().av1mi_lr_search_units(int(width), int(height), int(unit_size)))
+
+
+def lr_search_scratch_bytes(width, height, nframes, unit_size=64):
+    lib = load()
+    lib.av1mi_lr_search_scratch_bytes.restype = C.c_size_t
+    return int(lib.av1mi_lr_search_scratch_bytes(int(width), int(height), int(unit_size), int(nframes)))
+
+
+def lr_search_candidate(chroma, c):
+    """candidate c's 8-byte unit record for a luma (chroma = 0) or chroma plane, as a list"""
+    rec = (C.c_int8 * 8)()
+    if load().av1mi_lr_search_candidate(int(chroma), int(c), rec):
+        raise ValueError("restoration search candidate %d out of range" % c)
+    return list(rec)
+
+
+def lr_search_bits(chroma, c):
+    return int(load().av1mi_lr_search_bits(int(chroma), int(c)))
+
+
+def lr_search_lambda(qindex, bd):
+    lib = load()
+    lib.av1mi_lr_search_lambda.restype = C.c_longlong
+    return int(lib.av1mi_lr_search_lambda(int(qindex), int(bd)))
 
 
 def exported_symbols():
@@ -793,6 +843,10 @@ class Context:
     def lr_yuv_decide(self, job):
         """the three planes' restoration + ON / OFF decisions in one call (include/av1mi.h av1mi_lr_yuv_decide)"""
         self._chk(self.lib.av1mi_lr_yuv_decide(self.h, C.byref(job)))
+
+    def lr_search(self, job):
+        """a Wiener record or none per restoration unit of the three planes (include/av1mi.h av1mi_lr_search; job: LrSearchJob)"""
+        self._chk(self.lib.av1mi_lr_search(self.h, C.byref(job)))
 
     # ---- fused intra-only segment pipeline
     def extend_frames(self, d_plane, stride, w, h, visible_w, visible_h, bd, nframes):

@@ -54,6 +54,7 @@ struct Av1EntLaunch {
   SlotTable tab;
   const uint16_t *cdf_image32; SlotTable tab32;   // the same for the tiles of a key frame's 32x32 band
   const uint8_t *lr_on_frame;   // optional: [frame * 3 + plane], 0 = restoration of the plane is off in that frame
+  size_t lr_units_stride[3];    // fv.lr_units[p] != null: units between the frames of plane p's records
   // key frames in 32x32 blocks (av1_ops32.hpp): the first sb_rows32 superblock rows of every frame are tiles of that kind, with their
   // own slot table and default CDFs; `band` selects which tiles a chains launch walks (0 all, 1 the 32x32 band, 2 the rows below)
   int sb_rows32, band, nslots;
@@ -69,6 +70,7 @@ template <int kKey = -1> __device__ __forceinline__ FrameView frame_view(const A
   v.lev_y += nb * 64 * f; v.lev_u += nb * 16 * f; v.lev_v += nb * 16 * f;
   v.info = L.info + nb * f;
   if (L.lr_on_frame) for (int p = 0; p < 3; p++) v.lr_on[p] = v.lr_on[p] && L.lr_on_frame[f * 3 + p];
+  for (int p = 0; p < 3; p++) if (v.lr_units[p]) v.lr_units[p] += L.lr_units_stride[p] * 8 * (size_t)f;
   return v;
 }
 
@@ -430,7 +432,7 @@ uint32_t av1mi_av1_entropy_slot_bytes(void) { return 16384; }
 
 }  // extern "C"
 
-int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hipStream_t front, int *ticket) {
+int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hipStream_t front, int *ticket, const av1mi_av1_entropy_units *units) {
   if (!ctx || !ticket) return AV1MI_E_INVAL;
   *ticket = -1;
   if (!j) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "null job");
@@ -441,6 +443,11 @@ int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hip
   const void *need[] = { j->d_lev_y, j->d_lev_u, j->d_lev_v, j->d_out, j->d_tile_size, j->d_total, j->key ? (const void *)j->d_modes_y : (const void *)j->d_mvs,
                          j->key ? (const void *)j->d_modes_uv : (const void *)j->d_skip };
   for (const void *p : need) if (!p) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "null device pointer");
+  if (units) {      // all three planes' records or none, each read as 64-bit words
+    const bool any = units->d_units[0] || units->d_units[1] || units->d_units[2], all = units->d_units[0] && units->d_units[1] && units->d_units[2];
+    if (any && !all) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "restoration units: the records of all three planes, or of none");
+    for (int p = 0; p < 3; p++) if ((uintptr_t)units->d_units[p] & 7) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "restoration units: misaligned device pointer (8 bytes)");
+  }
   if (j->nframes == 0) return AV1MI_OK;
   av1mi_av1ent_state *st = av1mi::ctx_av1ent(ctx);
   if (!st) return av1mi::ctx_fail(ctx, AV1MI_E_NOMEM, "AV1 entropy state");
@@ -498,6 +505,7 @@ int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hip
   L.total = j->d_total; L.status = (uint32_t *)(j->d_total + 1);
   L.cdf_image = st->d_image[key][qcat]; L.cdf_words = st->image_words[key]; L.tab = st->tab[key];
   L.lr_on_frame = j->d_lr_on;
+  if (units) for (int p = 0; p < 3; p++) { L.fv.lr_units[p] = units->d_units[p]; L.lr_units_stride[p] = units->frame_stride[p]; }
 #define E_HIP(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return av1mi::ctx_fail(ctx, AV1MI_E_DEVICE, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
   for (hipEvent_t *ev : { &st->lists_ready[par], &st->lists_free[par] }) if (!*ev) E_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
   if (st->free_recorded[par]) E_HIP(hipStreamWaitEvent(front, st->lists_free[par], 0));      // the coder of two jobs ago still reads this set of lists
@@ -526,15 +534,21 @@ int av1mi::av1_entropy_back(av1mi_ctx *ctx, int ticket, hipStream_t back, const 
   return AV1MI_OK;
 }
 
-int av1mi::av1_entropy_submit(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hipStream_t front, hipStream_t back, const Av1EntMirrors *mirrors) {
+int av1mi::av1_entropy_submit(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hipStream_t front, hipStream_t back, const Av1EntMirrors *mirrors,
+                              const av1mi_av1_entropy_units *units) {
   int ticket = -1;
-  const int rc = av1_entropy_front(ctx, j, front, &ticket);
+  const int rc = av1_entropy_front(ctx, j, front, &ticket, units);
   if (rc != AV1MI_OK || ticket < 0) return rc;      // (an empty job has no back half)
   return av1_entropy_back(ctx, ticket, back, mirrors);
 }
 
 extern "C" {
 
+int av1mi_av1_entropy_encode_units(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, const av1mi_av1_entropy_units *units, void *stream_handle) {
+  if (!ctx) return AV1MI_E_INVAL;
+  hipStream_t s = stream_handle ? (hipStream_t)stream_handle : av1mi::ctx_stream(ctx);
+  return av1mi::av1_entropy_submit(ctx, j, s, s, nullptr, units);
+}
 int av1mi_av1_entropy_encode_on(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, void *stream_handle) {
   if (!ctx) return AV1MI_E_INVAL;
   hipStream_t s = stream_handle ? (hipStream_t)stream_handle : av1mi::ctx_stream(ctx);

@@ -184,6 +184,8 @@ struct FrameView {
   int lr_on[3];                 // Wiener restoration per plane (unit size 64 in the plane's samples)
   int8_t lr_unit[2][8];         // the unit record (luma, chroma) every unit uses: type, v0 v1 v2, h0 h1 h2
   int lr_rows[3], lr_cols[3];   // units per plane
+  const int8_t *lr_units[3];    // optional, per plane: the frame's own records, lr_rows x lr_cols of 8 bytes in raster order (the
+                                // restoration search's choice; a record of type 0 = the unit is not filtered); null = lr_unit serves every unit
 };
 
 AV1_HD int iabs(int v) { return v < 0 ? -v : v; }
@@ -336,7 +338,33 @@ template <class K> AV1_HD void tok_signed_subexp_ref(K &k, int v, int low, int h
   v -= low; r -= low;
   tok_subexp(k, mx, kk, (r << 1) <= mx ? tok_recenter(r, v) : tok_recenter(mx - 1 - r, mx - 1 - v));
 }
-// read_lr for the superblock at (sbr, sbc): with one superblock per tile the reference taps are always the defaults
+// The Wiener taps' syntax (5.11.58): range, subexponential parameter and default reference of tap0, tap1, tap2 — the one table of
+// the coder and of the restoration search's bit count
+struct WienerTapSyntax { int lo, hi, k, ref; };
+AV1_HD WienerTapSyntax wiener_tap_syntax(int j) {
+  const WienerTapSyntax t[3] = { { -5, 10, 1, 3 }, { -23, 8, 2, -7 }, { -17, 46, 3, 15 } };
+  return t[j];
+}
+// A unit's 8-byte record (type, v0 v1 v2, h0 h1 h2, pad) as ONE 64-bit value, byte i in bits 8 i: a record is read whole and kept in
+// registers (a pointer that may aim into the FrameView or into memory put the whole view into scratch memory in the tokenizers)
+AV1_HD uint64_t lr_record_word(const int8_t *u) {
+  uint64_t w = 0;
+  for (int i = 0; i < 8; i++) w |= (uint64_t)(uint8_t)u[i] << (8 * i);
+  return w;
+}
+AV1_HD int lr_record_byte(uint64_t w, int i) { return (int)(int8_t)(w >> (8 * i)); }
+// the taps of one Wiener record as literals against the default reference taps; a chroma record codes no tap0
+template <class K> AV1_HD void tok_wiener_taps(K &k, uint64_t rec, bool chroma) {
+  for (int pass = 0; pass < 2; pass++)
+    for (int j = chroma ? 1 : 0; j < 3; j++) {
+      const WienerTapSyntax t = wiener_tap_syntax(j);
+      tok_signed_subexp_ref(k, lr_record_byte(rec, 1 + pass * 3 + j), t.lo, t.hi + 1, t.k, t.ref);
+    }
+}
+// read_lr for the superblock at (sbr, sbc): with one superblock per tile the reference taps are always the defaults.  A unit's record
+// is its own where the frame has per-unit records, else the plane class's shared one.  List capacity: a superblock opens at most one
+// unit per plane (units are 64 samples of the plane: a luma unit is a superblock, a chroma unit four); a unit is one symbol and six
+// taps of at most four literal words each (two "more" bits, then at most two words of the value): 25 words, 75 per tile of 32 768.
 template <const BandSlots &B, class K> AV1_HD void tok_lr(const FrameView &f, K &k, int sbr, int sbc) {
   const int mi_r = sbr * 16, mi_c = sbc * 16;
   for (int p = 0; p < 3; p++) {
@@ -344,14 +372,13 @@ template <const BandSlots &B, class K> AV1_HD void tok_lr(const FrameView &f, K 
     const int ss = p ? 1 : 0, us = 64;
     const int row0 = (mi_r * (4 >> ss) + us - 1) / us, row1 = imin(((mi_r + 16) * (4 >> ss) + us - 1) / us, f.lr_rows[p]);
     const int col0 = (mi_c * (4 >> ss) + us - 1) / us, col1 = imin(((mi_c + 16) * (4 >> ss) + us - 1) / us, f.lr_cols[p]);
-    const int8_t *u = f.lr_unit[p ? 1 : 0];
+    const uint64_t shared = lr_record_word(f.lr_unit[p ? 1 : 0]);
     for (int ur = row0; ur < row1; ur++)
       for (int uc = col0; uc < col1; uc++) {
-        k.sym(B.use_wiener, u[0] == 1);
-        if (u[0] != 1) continue;
-        const int kmin[3] = { -5, -23, -17 }, kmax[3] = { 10, 8, 46 }, kk[3] = { 1, 2, 3 }, mid[3] = { 3, -7, 15 };
-        for (int pass = 0; pass < 2; pass++)
-          for (int j = p ? 1 : 0; j < 3; j++) tok_signed_subexp_ref(k, u[1 + pass * 3 + j], kmin[j], kmax[j] + 1, kk[j], mid[j]);
+        const uint64_t rec = f.lr_units[p] ? *reinterpret_cast<const u64a *>(f.lr_units[p] + ((long)ur * f.lr_cols[p] + uc) * 8) : shared;
+        const bool wiener = lr_record_byte(rec, 0) == 1;
+        k.sym(B.use_wiener, wiener);
+        if (wiener) tok_wiener_taps(k, rec, p != 0);
       }
   }
 }

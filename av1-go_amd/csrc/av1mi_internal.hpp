@@ -167,6 +167,26 @@ hipError_t launch_extend(void *plane, int stride, int w, int h, int vw, int vh, 
 // the decision over the sums of nplanes = 1 plane (geometry y) or the 3 of 4:2:0 frames (y, c, c): lr_kernel.hip k_lr_decide
 hipError_t launch_lr_decide(unsigned long long *sse, const LrGeom &y, const LrGeom &c, int nplanes, uint8_t *on, int on_stride, bool clear, hipStream_t s);
 
+// The restoration search over the three planes of 4:2:0 frames (lr_kernel.hip k_lr_search, k_lr_pick; av1mi.h "restoration search").
+// The cost table holds 9 sums per unit, the units of a frame's planes end to end: [frame][unit_first[p] + unit][candidate].
+struct LrSearchLaunch {
+  const void *cdef[3], *dbl[3], *orig[3];
+  int stride[3], w[3], h[3], bd, unit_size, nframes;
+  unsigned long long *sums;                    // zeroed by the caller
+  unsigned unit_first[3], units_frame;         // plane p's first unit in a frame's run of units, and the run's length
+  unsigned first[3];                           // filled in by launch_lr_search (plane p's first workgroup)
+  int8_t taps[2][3][3];                        // [luma / chroma][filter][tap0 tap1 tap2]
+  // the pick: J = sum + lambda * bits[class][candidate]; the chosen record per unit, its index per unit
+  long long lambda; int bits[2][9];
+  int8_t *units[3]; uint8_t *choice;
+};
+hipError_t launch_lr_search(LrSearchLaunch &S, hipStream_t s);
+hipError_t launch_lr_pick(const LrSearchLaunch &S, hipStream_t s);
+// the search's tables, host side (lr_kernel.hip): candidate c's record for a luma / chroma plane, and the exact bits of that record
+void lr_search_record(int chroma, int c, int8_t rec[8]);
+int lr_search_bits(int chroma, int c);
+void lr_search_tables(LrSearchLaunch *S);      // the launch's taps (the table itself) and bits
+
 // inter (P-frame) pipeline over the t-th frames of a batch of segments, stacked like the intra job
 struct InterLaunch {
   const void *src[3]; const void *ref[3]; void *rec[3]; int16_t *lev[3];
@@ -343,10 +363,11 @@ struct Av1EntMirrors {
 // the AV1 tile coder of include/av1mi.h's av1mi_av1_entropy_job in two halves: info + tokens + chains on `front`, the serial range
 // coder + gather on `back` (the same stream, or a second one: the lists are double-buffered, so the front half of the next
 // job runs beside the back half of this one)
-int av1_entropy_submit(av1mi_ctx *ctx, const struct av1mi_av1_entropy_job *j, hipStream_t front, hipStream_t back, const Av1EntMirrors *mirrors = nullptr);
+int av1_entropy_submit(av1mi_ctx *ctx, const struct av1mi_av1_entropy_job *j, hipStream_t front, hipStream_t back, const Av1EntMirrors *mirrors = nullptr,
+                       const struct av1mi_av1_entropy_units *units = nullptr);
 // ... and the halves on their own: the back half of a job may be launched later (the session defers the range coder of batch t behind
 // the filters of batch t + 1 on the main stream); at most two jobs' back halves can be outstanding (the list sets)
-int av1_entropy_front(av1mi_ctx *ctx, const struct av1mi_av1_entropy_job *j, hipStream_t front, int *ticket);
+int av1_entropy_front(av1mi_ctx *ctx, const struct av1mi_av1_entropy_job *j, hipStream_t front, int *ticket, const struct av1mi_av1_entropy_units *units = nullptr);
 int av1_entropy_back(av1mi_ctx *ctx, int ticket, hipStream_t back, const Av1EntMirrors *mirrors = nullptr);
 // accessors of the opaque context for translation units other than capi.hip (gop_session.hip)
 hipStream_t ctx_stream(av1mi_ctx *ctx);

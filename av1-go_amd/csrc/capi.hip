@@ -530,6 +530,59 @@ int av1mi_lr_frames_decide(av1mi_ctx *ctx, const void *d_cdef, const void *d_deb
 size_t av1mi_lr_yuv_decide_scratch_bytes(int h, int nframes) { return av1mi_lr_decide_scratch_bytes(h, 0, nframes) + 2 * av1mi_lr_decide_scratch_bytes(h / 2, 1, nframes); }
 int av1mi_lr_yuv_decide(av1mi_ctx *ctx, const av1mi_lr_decide_job *j) { return av1mi::lr_yuv_decide_with(ctx, j, false); }
 
+// ---- restoration search
+int av1mi_lr_search_units(int width, int height, int unit_size) {
+  if (width <= 0 || height <= 0 || unit_size <= 0) return 0;
+  const av1mi::LrGeom gy(width, height, 0, unit_size, 1), gc(width / 2, height / 2, 1, unit_size, 1);
+  return gy.unit_rows * gy.unit_cols + 2 * gc.unit_rows * gc.unit_cols;
+}
+size_t av1mi_lr_search_scratch_bytes(int width, int height, int unit_size, int nframes) {
+  const size_t b = (size_t)(nframes > 0 ? nframes : 0) * av1mi_lr_search_units(width, height, unit_size) * AV1MI_LR_SEARCH_CANDIDATES * 8;
+  return (b + 15) & ~(size_t)15;
+}
+int av1mi_lr_search_candidate(int chroma, int c, int8_t record[8]) {
+  if (c < 0 || c >= AV1MI_LR_SEARCH_CANDIDATES || !record) return AV1MI_E_INVAL;
+  av1mi::lr_search_record(chroma, c, record);
+  return AV1MI_OK;
+}
+int av1mi_lr_search_bits(int chroma, int c) { return c < 0 || c >= AV1MI_LR_SEARCH_CANDIDATES ? -1 : av1mi::lr_search_bits(chroma, c); }
+long long av1mi_lr_search_lambda(int qindex, int bit_depth) {
+  const long long q = av1mi_dc_q(qindex, bit_depth);
+  return (3 * q * q) >> 7;
+}
+int av1mi_lr_search(av1mi_ctx *ctx, const av1mi_lr_search_job *j) {
+  BIND(ctx);
+  if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
+  const void *cdef[3] = { j->d_cdef_y, j->d_cdef_u, j->d_cdef_v }, *dbl[3] = { j->d_dbl_y, j->d_dbl_u, j->d_dbl_v }, *orig[3] = { j->d_orig_y, j->d_orig_u, j->d_orig_v };
+  int8_t *units[3] = { j->d_units_y, j->d_units_u, j->d_units_v };
+  for (int p = 0; p < 3; p++) if (!cdef[p] || !dbl[p] || !orig[p] || !units[p]) return fail(ctx, AV1MI_E_INVAL, "null device pointer");
+  if (!j->d_scratch || !j->d_choice) return fail(ctx, AV1MI_E_INVAL, "null device pointer");
+  if (((uintptr_t)j->d_scratch & 15) || ((uintptr_t)units[0] & 7) || ((uintptr_t)units[1] & 7) || ((uintptr_t)units[2] & 7)) return fail(ctx, AV1MI_E_INVAL, "misaligned device pointer");
+  if (int rc = check_bd(ctx, j->bit_depth)) return rc;
+  if (j->width <= 0 || j->height <= 0 || (j->width & 1) || (j->height & 1) || j->width > 16384 || j->height > 16384 || j->stride_y < j->width || j->stride_uv < j->width / 2)
+    return fail(ctx, AV1MI_E_INVAL, "bad frame geometry %dx%d strides %d/%d", j->width, j->height, j->stride_y, j->stride_uv);
+  if (j->unit_size != 64) return fail(ctx, AV1MI_E_INVAL, "restoration search: unit size %d not supported (64)", j->unit_size);
+  if (j->qindex < 0 || j->qindex > 255) return fail(ctx, AV1MI_E_INVAL, "qindex %d out of range", j->qindex);
+  if (int rc = check_nframes(ctx, j->nframes)) return rc;
+  if (j->nframes == 0) return AV1MI_OK;
+  const av1mi::LrGeom gy(j->width, j->height, 0, 64, j->nframes), gc(j->width / 2, j->height / 2, 1, 64, j->nframes);
+  av1mi::LrSearchLaunch S;
+  memset(&S, 0, sizeof(S));
+  for (int p = 0; p < 3; p++) {
+    S.cdef[p] = cdef[p]; S.dbl[p] = dbl[p]; S.orig[p] = orig[p]; S.units[p] = units[p];
+    S.stride[p] = p ? j->stride_uv : j->stride_y; S.w[p] = (p ? gc : gy).w; S.h[p] = (p ? gc : gy).h;
+  }
+  S.bd = j->bit_depth; S.unit_size = 64; S.nframes = j->nframes; S.sums = (unsigned long long *)j->d_scratch; S.choice = j->d_choice;
+  const unsigned ny = (unsigned)(gy.unit_rows * gy.unit_cols), nc = (unsigned)(gc.unit_rows * gc.unit_cols);
+  S.unit_first[0] = 0; S.unit_first[1] = ny; S.unit_first[2] = ny + nc; S.units_frame = ny + 2 * nc;
+  S.lambda = av1mi_lr_search_lambda(j->qindex, j->bit_depth);
+  av1mi::lr_search_tables(&S);
+  { ProfScope ps(ctx, AV1MI_K_LR); HIP_TRY(ctx, av1mi::launch_zero16(j->d_scratch, av1mi_lr_search_scratch_bytes(j->width, j->height, 64, j->nframes), ctx->stream)); }
+  { ProfScope ps(ctx, AV1MI_K_LR); HIP_TRY(ctx, av1mi::launch_lr_search(S, ctx->stream)); }
+  { ProfScope ps(ctx, AV1MI_K_LR); HIP_TRY(ctx, av1mi::launch_lr_pick(S, ctx->stream)); }
+  return AV1MI_OK;
+}
+
 }  // extern "C"
 
 // THE RULE OF THE SCRATCH'S ZEROES, in this one place.  Pass 1 adds into the sums, so they must be zero when it starts; the decision
@@ -562,6 +615,7 @@ int av1mi::lr_yuv_decide_with(av1mi_ctx *ctx, const av1mi_lr_decide_job *j, bool
     L.cdef = cdef[p]; L.dbl = dbl[p]; L.out = out[p]; L.orig = orig[p]; L.bd = j->bit_depth; L.ss = p ? 1 : 0; L.unit_size = j->unit_size; L.nframes = n;
     L.stride = p ? j->stride_uv : j->stride_y; L.w = (p ? gc : gy).w; L.h = (p ? gc : gy).h; L.sse_stripes = (p ? gc : gy).stripes;
     L.units = p ? j->d_units_uv : j->d_units_y; L.unit_frame_stride = p ? j->unit_frame_stride_uv : j->unit_frame_stride_y;
+    if (p == 2 && j->d_units_v) { L.units = j->d_units_v; L.unit_frame_stride = j->unit_frame_stride_v; }
     L.sse = sse + 2 * av1mi::lr_first_pair(gy, gc, p); L.keep = j->d_on + p; L.keep_stride = 3; L.no_sgr = j->no_self_guided_units != 0;
   }
   // pass 1: the tiles the decision's sums run over (an eighth of a large plane); the decision; pass 2: the other tiles of the frames

@@ -114,6 +114,10 @@ struct Slot {
   bool upload_pending = false, kernel_pending = false;
   // restoration on / off per (segment, plane), decided by the GPU against the source (k_lr + k_lr_decide): device + pinned mirror
   void *d_lr_on = nullptr, *h_lr_on = nullptr;
+  // lr_search: the batch's chosen unit records per plane, the cost table and the index bytes — per SLOT: the tokenizer of batch t reads
+  // the records while the filters of batch t + 1 run — and their pinned mirrors, copied behind the filters in front of lr_down
+  void *d_lr_units[3] = {}, *h_lr_units[3] = {}, *d_lr_cost = nullptr, *d_lr_choice = nullptr, *h_lr_choice = nullptr;
+  hipEvent_t lr_down = nullptr;
   int frame_type = 0;
   int q = 0;                          // the batch's quantiser (av1mi_gop_set_base_q_idx) and what the policy derives from it for its frame type
   av1mi_frame_params params{};
@@ -164,6 +168,7 @@ struct av1mi_gop {
   int key_modes_band = 0, key_modes_stride = 0;  // mode bytes per segment: the 32x32 blocks, then (from key_modes_band) the 8x8 blocks of the last rows
   void *d_cdef_sb[2] = {}, *d_lr[2] = {}, *d_zero_skip = nullptr;
   void *d_lr_scratch = nullptr;                // the restoration decision's partial sums (three planes)
+  int lr_units[3] = {};                        // lr_search: units per frame of Y, U, V
   void *d_me = nullptr;                        // coarse_range: the coarse search's quarter planes and centres of one batch (single: the chain is serial in t)
   void *d_denoise_vectors = nullptr;           // denoise_range: the blocks' vectors of one batch (the main stream orders its users)
   void *d_grain_scratch = nullptr;             // denoise: the workgroups' partial records of one batch (the main stream orders its users)
@@ -276,6 +281,13 @@ int slot_buffers(av1mi_gop *g, Slot &s) {
     G_TRY(host_alloc(g, &s.h_grain, (size_t)S * 3 * sizeof(av1mi_grain_record)));
     G_HIP(hipEventCreateWithFlags(&s.grain_done, hipEventDisableTiming));
     if (c.grain_cov) G_TRY(host_alloc(g, &s.h_grain_cov, (size_t)S * 3 * sizeof(av1mi_grain_cov_record)));
+  }
+  if (c.lr_search) {
+    for (int p = 0; p < 3; p++) { G_TRY(dev_alloc(g, &s.d_lr_units[p], (size_t)S * g->lr_units[p] * 8)); G_TRY(host_alloc(g, &s.h_lr_units[p], (size_t)S * g->lr_units[p] * 8)); }
+    const size_t n = (size_t)S * (g->lr_units[0] + g->lr_units[1] + g->lr_units[2]);
+    G_TRY(dev_alloc(g, &s.d_lr_cost, av1mi_lr_search_scratch_bytes(c.width, c.height, 64, S)));
+    G_TRY(dev_alloc(g, &s.d_lr_choice, n)); G_TRY(host_alloc(g, &s.h_lr_choice, n));
+    G_HIP(hipEventCreateWithFlags(&s.lr_down, hipEventDisableTiming));
   }
   if (c.quality_stats) {
     G_TRY(host_alloc(g, &s.h_quality, (size_t)S * 3 * sizeof(av1mi_quality)));
@@ -402,6 +414,13 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
   if (c->denoise_range && !c->denoise) return WHY("denoise_range %d needs denoise (1 .. 16): it is the range of the denoiser's block search", c->denoise_range);
   if (c->grain_cov != 0 && c->grain_cov != 1) return WHY("grain_cov %d unknown (0 none, 1 the covariance of what the denoiser removed)", c->grain_cov);
   if (c->grain_cov && !c->denoise) return WHY("grain_cov %d needs denoise (1 .. 16): it measures what the denoiser removed", c->grain_cov);
+  if (c->lr_search != 0 && c->lr_search != 1) return WHY("lr_search %d unknown (0 the policy's record in every unit, 1 a record chosen per unit)", c->lr_search);
+  if (c->lr_search) {      // the filters' units tile the coded size, the syntax's the true size: the search needs the two grids to be one
+    const int vw = c->visible_width ? c->visible_width : c->width, vh = c->visible_height ? c->visible_height : c->height;
+    auto units = [](int n) { const int u = (n + 32) / 64; return u > 1 ? u : 1; };
+    if (units(vw) != units(c->width) || units(vh) != units(c->height) || units((vw + 1) / 2) != units(c->width / 2) || units((vh + 1) / 2) != units(c->height / 2))
+      return WHY("lr_search at a true size %dx%d whose restoration units differ from those of the coded size %dx%d is not built", vw, vh, c->width, c->height);
+  }
   if (c->tone_map != 0 && c->tone_map != 1) return WHY("tone_map %d unknown (0 none, 1 BT.2390)", c->tone_map);
   if (c->tone_map_peak && !c->tone_map) return WHY("tone_map_peak %d needs tone_map", c->tone_map_peak);
   if (c->tone_map && c->bit_depth != 10) return WHY("tone_map needs bit_depth 10, not %d: an HDR10 source has 10 bits", c->bit_depth);
@@ -423,6 +442,7 @@ int setup(av1mi_gop *g) {
     P.n = (size_t)P.w * P.h * S; P.bytes = P.n * g->bps;
   }
   g->nb = g->plane[0].n / 64;
+  for (int p = 0; p < 3; p++) { const av1mi::LrGeom lg(g->plane[p].w, g->plane[p].h, p ? 1 : 0, 64, 1); g->lr_units[p] = lg.unit_rows * lg.unit_cols; }
   g->next_q = c.base_q_idx;
   G_TRY(av1mi_gop_source_layout(&c, &g->layout));
   // the chain (config_error: never convert AND chroma)
@@ -549,7 +569,7 @@ void av1mi_gop_close(av1mi_gop *g) {
   if (g->up) { (void)hipStreamSynchronize(g->up); (void)hipStreamDestroy(g->up); }
   if (g->down) { (void)hipStreamSynchronize(g->down); (void)hipStreamDestroy(g->down); }
   for (Slot &s : g->slot)
-    for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done, s.quality_done, s.grain_done })
+    for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done, s.quality_done, s.grain_done, s.lr_down })
       if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : { g->store[0].filled, g->store[0].read_done, g->store[1].filled, g->store[1].read_done, g->scene_done, g->put_done[0], g->put_done[1], g->put_done[2] })
     if (e) (void)hipEventDestroy(e);
@@ -828,11 +848,29 @@ static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
   lj.d_orig_y = src[0]; lj.d_orig_u = src[1]; lj.d_orig_v = src[2];
   lj.d_units_y = (const int8_t *)g->d_lr[0]; lj.d_units_uv = (const int8_t *)g->d_lr[1];
   lj.d_scratch = g->d_lr_scratch; lj.d_on = (uint8_t *)s.d_lr_on;
+  if (c.lr_search) {      // zero the cost table, search, pick; then the restoration and its decision with the batch's own units
+    av1mi_lr_search_job sj;
+    memset(&sj, 0, sizeof(sj));
+    sj.width = w; sj.height = h; sj.bit_depth = bd; sj.nframes = S; sj.unit_size = 64; sj.qindex = s.q; sj.stride_y = lj.stride_y; sj.stride_uv = lj.stride_uv;
+    sj.d_cdef_y = lj.d_cdef_y; sj.d_cdef_u = lj.d_cdef_u; sj.d_cdef_v = lj.d_cdef_v; sj.d_dbl_y = lj.d_dbl_y; sj.d_dbl_u = lj.d_dbl_u; sj.d_dbl_v = lj.d_dbl_v;
+    sj.d_orig_y = src[0]; sj.d_orig_u = src[1]; sj.d_orig_v = src[2];
+    sj.d_scratch = s.d_lr_cost; sj.d_units_y = (int8_t *)s.d_lr_units[0]; sj.d_units_u = (int8_t *)s.d_lr_units[1]; sj.d_units_v = (int8_t *)s.d_lr_units[2];
+    sj.d_choice = (uint8_t *)s.d_lr_choice;
+    G_TRY(av1mi_lr_search(g->ctx, &sj));
+    lj.d_units_y = sj.d_units_y; lj.d_units_uv = sj.d_units_u; lj.d_units_v = sj.d_units_v;
+    lj.unit_frame_stride_y = g->lr_units[0]; lj.unit_frame_stride_uv = g->lr_units[1]; lj.unit_frame_stride_v = g->lr_units[2];
+  }
   lj.no_self_guided_units = P.lr_unit_y[0] != 2 && P.lr_unit_uv[0] != 2;
   G_TRY(av1mi::lr_yuv_decide_with(g->ctx, &lj, true));
   if (padded)      // ... and so do its motion-compensation reads of this frame
     for (int p = 0; p < 3; p++) G_TRY(extend_plane(g, g->plane[p], g->d_ref[p]));
   G_HIP(hipEventRecord(s.filters_done, av1mi::ctx_stream(g->ctx)));
+  if (c.lr_search) {      // the records and indices to the host with every batch: a few KB, for the host writer and the statistics
+    G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
+    for (int p = 0; p < 3; p++) G_HIP(hipMemcpyAsync(s.h_lr_units[p], s.d_lr_units[p], (size_t)S * g->lr_units[p] * 8, hipMemcpyDeviceToHost, g->down));
+    G_HIP(hipMemcpyAsync(s.h_lr_choice, s.d_lr_choice, (size_t)S * (g->lr_units[0] + g->lr_units[1] + g->lr_units[2]), hipMemcpyDeviceToHost, g->down));
+    G_HIP(hipEventRecord(s.lr_down, g->down));
+  }
   if (s.symbols_down) {
     G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
     G_HIP(hipMemcpyAsync(s.h_lr_on, s.d_lr_on, (size_t)S * 3, hipMemcpyDeviceToHost, g->down));
@@ -898,6 +936,8 @@ static int start_coder(av1mi_gop *g, Slot &s) {
   ej.d_mvs = (const int16_t *)s.d_mv; ej.d_skip = (const uint8_t *)s.d_skip;
   ej.lr_on[0] = P.lr_unit_y[0] == 1; ej.lr_on[1] = ej.lr_on[2] = P.lr_unit_uv[0] == 1;
   ej.d_lr_on = (const uint8_t *)s.d_lr_on;
+  av1mi_av1_entropy_units eu;
+  if (c.lr_search) for (int p = 0; p < 3; p++) { eu.d_units[p] = (const int8_t *)s.d_lr_units[p]; eu.frame_stride[p] = (size_t)g->lr_units[p]; }
   ej.visible_width = g->vw; ej.visible_height = g->vh;
   ej.key_rows32 = s.frame_type == 0 && g->key32 ? g->key_rows32 : 0;
   memcpy(ej.lr_unit_y, P.lr_unit_y, 8); memcpy(ej.lr_unit_uv, P.lr_unit_uv, 8);
@@ -906,12 +946,12 @@ static int start_coder(av1mi_gop *g, Slot &s) {
     // tokenizer + chains of THIS batch on the side stream; the range coder of the PREVIOUS batch on the main stream, behind this
     // batch's filters: two queues that are both busy all the time ((pipeline + filters + coder) beside (tokenizer + chains)) instead of
     // a short one and a long one
-    G_TRY(av1mi::av1_entropy_front(g->ctx, &ej, side, &s.ent_ticket));
+    G_TRY(av1mi::av1_entropy_front(g->ctx, &ej, side, &s.ent_ticket, c.lr_search ? &eu : nullptr));
     Slot &prev = g->slot[(g->submitted + kSlots - 1) % kSlots];
     if (g->submitted > 0 && prev.ent_ticket >= 0) G_TRY(finish_entropy(g, prev, main));
   } else {
     const av1mi::Av1EntMirrors m = entropy_mirrors(g, s);
-    G_TRY(av1mi::av1_entropy_submit(g->ctx, &ej, side, back, &m));
+    G_TRY(av1mi::av1_entropy_submit(g->ctx, &ej, side, back, &m, c.lr_search ? &eu : nullptr));
     G_TRY(entropy_results(g, s, back));
   }
   s.ent_pending = true;
@@ -1062,6 +1102,11 @@ int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out) {
   memset(out, 0, sizeof(*out));
   out->params = s.params;
   out->lr_on = (const uint8_t *)s.h_lr_on;
+  if (g->cfg.lr_search) {
+    G_HIP(hipEventSynchronize(s.lr_down));
+    for (int p = 0; p < 3; p++) { out->lr_units[p] = (const int8_t *)s.h_lr_units[p]; out->lr_units_per_frame[p] = g->lr_units[p]; }
+    out->lr_choice = (const uint8_t *)s.h_lr_choice;
+  }
   if (g->cfg.quality_stats) { G_HIP(hipEventSynchronize(s.quality_done)); out->quality = (const av1mi_quality *)s.h_quality; }
   if (g->cfg.denoise && s.has_grain) { G_HIP(hipEventSynchronize(s.grain_done)); out->grain = (const av1mi_grain_record *)s.h_grain; out->grain_cov = (const av1mi_grain_cov_record *)s.h_grain_cov; }
   out->segments = g->cfg.segments;

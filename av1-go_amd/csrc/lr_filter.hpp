@@ -171,14 +171,14 @@ __device__ __forceinline__ s16x2 lr_pk(int a, int b) { return __builtin_bit_cast
 // int16, the sums are exact in int32).  Horizontal: four outputs per lane from six aligned dwords of the source row (window columns
 // c .. c + 11, the taps of output k start at column c + 1 + k): outputs 1 and 3 use the dwords as they are, outputs 0 and 2 the
 // same dwords funnel-shifted by one sample.  Tap pairs (h0,h1) (h2,h3) (h4,h5) (h6,0).
-template <typename Pix, int BD, bool SGR> __device__ __forceinline__ void lr_wiener_packed(const LrTile<Pix> &T, LrLds<SGR> &lds, LrErr &err, const LrUnit &U) {
+// The horizontal pass of that route on its own (the restoration search runs it once per horizontal filter): the (bh + 6) x bw
+// intermediate of the staged tile under the taps hf
+template <int BD> __device__ __forceinline__ void lr_wiener_h_packed(const uint16_t *src, int16_t *inter, int bw, int bh, const int (&hf)[7]) {
   constexpr int offset = 1 << (BD + 3), limit = (1 << (BD + 5)) - 1;
-  const uint16_t *src = lds.src;
-  int16_t *inter = lds.inter();
-  const s16x2 H0 = lr_pk(U.hf[0], U.hf[1]), H1 = lr_pk(U.hf[2], U.hf[3]), H2 = lr_pk(U.hf[4], U.hf[5]), H3 = lr_pk(U.hf[6], 0);
-  const int q4 = T.bw / 4, hp = (T.bh + 1) >> 1;
+  const s16x2 H0 = lr_pk(hf[0], hf[1]), H1 = lr_pk(hf[2], hf[3]), H2 = lr_pk(hf[4], hf[5]), H3 = lr_pk(hf[6], 0);
+  const int q4 = bw / 4;
   const float inv_q4 = 1.0f / (float)q4;
-  for (int i = threadIdx.x; i < (T.bh + 6) * q4; i += 256) {
+  for (int i = threadIdx.x; i < (bh + 6) * q4; i += 256) {
     const int r = (int)(((float)i + 0.5f) * inv_q4), c = (i - r * q4) * 4;
     const uint2 *p = reinterpret_cast<const uint2 *>(src + __mul24(r, kLrSS) + c);   // (r * SS became a 64-bit multiply-add)
     const uint2 a = p[0], b = p[1], e = p[2];
@@ -201,6 +201,13 @@ template <typename Pix, int BD, bool SGR> __device__ __forceinline__ void lr_wie
     uint2 w; w.x = (uint32_t)(o[0] & 0xffff) | ((uint32_t)o[1] << 16); w.y = (uint32_t)(o[2] & 0xffff) | ((uint32_t)o[3] << 16);
     *reinterpret_cast<uint2 *>(inter + r * kLrMaxW + c) = w;
   }
+}
+template <typename Pix, int BD, bool SGR> __device__ __forceinline__ void lr_wiener_packed(const LrTile<Pix> &T, LrLds<SGR> &lds, LrErr &err, const LrUnit &U) {
+  const uint16_t *src = lds.src;
+  int16_t *inter = lds.inter();
+  const int q4 = T.bw / 4, hp = (T.bh + 1) >> 1;
+  const float inv_q4 = 1.0f / (float)q4;
+  lr_wiener_h_packed<BD>(src, inter, T.bw, T.bh, U.hf);
   __syncthreads();
   // Vertical: a lane produces rows 2 rp and 2 rp + 1 of four columns from intermediate rows 2 rp .. 2 rp + 7, interleaved once into
   // row pairs per column; the even row pairs its taps (v0,v1) (v2,v3) (v4,v5) (v6,0), the odd row the same row pairs with the taps
@@ -235,18 +242,21 @@ template <typename Pix, int BD, bool SGR> __device__ __forceinline__ void lr_wie
   }
 }
 // the scalar route: any width
-template <typename Pix, int BD, bool SGR> __device__ __forceinline__ void lr_wiener_scalar(const LrTile<Pix> &T, LrLds<SGR> &lds, LrErr &err, const LrUnit &U) {
+template <int BD> __device__ __forceinline__ void lr_wiener_h_scalar(const uint16_t *src, int16_t *inter, int bw, int bh, const int (&hf)[7]) {
   constexpr int offset = 1 << (BD + 3), limit = (1 << (BD + 5)) - 1;
-  const int tid = threadIdx.x, bw = T.bw, bh = T.bh;
-  int16_t *inter = lds.inter();
-  for (int i = tid; i < (bh + 6) * bw; i += 256) {
+  for (int i = threadIdx.x; i < (bh + 6) * bw; i += 256) {
     const int r = i / bw, c = i - r * bw;
-    const uint16_t *p = lds.src + r * kLrSS + c + 1;
+    const uint16_t *p = src + r * kLrSS + c + 1;
     int sum = 0;
 #pragma unroll
-    for (int t = 0; t < 7; t++) sum += U.hf[t] * p[t];
+    for (int t = 0; t < 7; t++) sum += hf[t] * p[t];
     inter[r * kLrMaxW + c] = (int16_t)min(max((sum + 4) >> 3, -offset), limit - offset);
   }
+}
+template <typename Pix, int BD, bool SGR> __device__ __forceinline__ void lr_wiener_scalar(const LrTile<Pix> &T, LrLds<SGR> &lds, LrErr &err, const LrUnit &U) {
+  const int tid = threadIdx.x, bw = T.bw, bh = T.bh;
+  int16_t *inter = lds.inter();
+  lr_wiener_h_scalar<BD>(lds.src, inter, bw, bh, U.hf);
   __syncthreads();
   for (int i = tid; i < bh * bw; i += 256) {
     const int r = i / bw, c = i - r * bw;
@@ -255,6 +265,158 @@ template <typename Pix, int BD, bool SGR> __device__ __forceinline__ void lr_wie
     for (int t = 0; t < 7; t++) sum += U.vf[t] * inter[(r + t) * kLrMaxW + c];
     lr_put1(T, err, r, c, min(max((sum + 1024) >> 11, 0), (1 << BD) - 1), lds.src[(r + 3) * kLrSS + c + 4]);
   }
+}
+
+// ---- The restoration search (av1mi.h "restoration search"): the squared error of every candidate over one staged tile against the
+// source, nothing stored.  A candidate above 0 is a (vertical, horizontal) pair of the plane class's three 1-D filters: pair (v, h) is
+// candidate 3 v + h.  Pair (0, 0) would be the identity; its place, candidate 0, holds "none": the CDEF samples' own error.
+// One horizontal pass per horizontal filter (lr_wiener_h_packed / _scalar), then ONE vertical pass that runs the vertical filters
+// over the same loads of the intermediate, into error sums only.  Per lane the sums are 32 bits: at most 16 samples x 2^20.
+constexpr int kLrFilters = 3, kLrCands = 9;
+struct LrSearchTaps { int f[kLrFilters][7]; };      // the symmetric 7-tap form of the class's filters
+__device__ __forceinline__ LrSearchTaps lr_search_taps(const int8_t (&t)[kLrFilters][3]) {
+  LrSearchTaps F;
+#pragma unroll
+  for (int k = 0; k < kLrFilters; k++) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) F.f[k][i] = F.f[k][6 - i] = t[k][i];
+    F.f[k][3] = 128 - 2 * (t[k][0] + t[k][1] + t[k][2]);
+  }
+  return F;
+}
+// The packed route's source samples, loaded once and kept for the three vertical passes: item i = tid + 256 k of the vertical pass
+// (k < 2: a tile has at most 32 row pairs x 16 column groups) is rows 2 rp, 2 rp + 1 of four columns; sv[k][half] = those four samples
+// of the source as 16-bit halves, where the row exists
+template <typename Pix> __device__ __forceinline__ void lr_search_source(const LrTile<Pix> &T, uint2 (&sv)[2][2]) {
+  typedef Pix Pix4 __attribute__((ext_vector_type(4)));
+  const int q4 = T.bw / 4, hp = (T.bh + 1) >> 1;
+  const float inv_q4 = 1.0f / (float)q4;
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const int i = threadIdx.x + 256 * k;
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+      sv[k][half] = make_uint2(0, 0);
+      if (i >= hp * q4) continue;
+      const int rp = (int)(((float)i + 0.5f) * inv_q4), c = (i - rp * q4) * 4, r = 2 * rp + half;
+      if (r >= T.bh) continue;
+      const Pix *sp = T.orig + T.at(r, c);
+      Pix4 v;
+      if (((uintptr_t)sp & (sizeof(Pix4) - 1)) == 0) v = *reinterpret_cast<const Pix4 *>(sp);
+      else v = Pix4{ sp[0], sp[1], sp[2], sp[3] };
+      sv[k][half] = make_uint2((uint32_t)v[0] | ((uint32_t)v[1] << 16), (uint32_t)v[2] | ((uint32_t)v[3] << 16));
+    }
+  }
+}
+__device__ __forceinline__ int lr_search_sample(const uint2 &s, int k) { return (int)(((k & 2) ? s.y : s.x) >> ((k & 1) * 16) & 0xffffu); }
+// candidate 0 over the lane's items: the staged CDEF samples against the source
+__device__ __forceinline__ unsigned lr_search_none_packed(const uint16_t *src, int bw, int bh, const uint2 (&sv)[2][2]) {
+  const int q4 = bw / 4, hp = (bh + 1) >> 1;
+  const float inv_q4 = 1.0f / (float)q4;
+  unsigned e = 0;
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const int i = threadIdx.x + 256 * k;
+    if (i >= hp * q4) continue;
+    const int rp = (int)(((float)i + 0.5f) * inv_q4), c = (i - rp * q4) * 4;
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+      const int r = 2 * rp + half;
+      if (r >= bh) continue;
+      const uint2 cd = *reinterpret_cast<const uint2 *>(src + (r + 3) * kLrSS + c + 4);
+#pragma unroll
+      for (int m = 0; m < 4; m++) { const int d = lr_search_sample(cd, m) - lr_search_sample(sv[k][half], m); e += (unsigned)(d * d); }
+    }
+  }
+  return e;
+}
+// The vertical pass of the search, packed: lr_wiener_packed's row pairs and tap pairs, the vertical filters FIRST .. 2 over one set of
+// loads, err[v] += the squared error of filter v's output.  (The last pair of an odd-height block: see lr_wiener_packed; its odd row
+// is not counted.)
+template <int BD, int FIRST> __device__ __forceinline__ void lr_search_v_packed(const int16_t *inter, int bw, int bh, const LrSearchTaps &F, const uint2 (&sv)[2][2],
+                                                                               unsigned (&err)[kLrFilters]) {
+  const int q4 = bw / 4, hp = (bh + 1) >> 1;
+  const float inv_q4 = 1.0f / (float)q4;
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const int i = threadIdx.x + 256 * k;
+    if (i >= hp * q4) continue;
+    const int rp = (int)(((float)i + 0.5f) * inv_q4), c = (i - rp * q4) * 4, r = 2 * rp;
+    uint32_t pr[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint2 x = *reinterpret_cast<const uint2 *>(inter + (r + 2 * j) * kLrMaxW + c);
+      const uint2 y = *reinterpret_cast<const uint2 *>(inter + (r + 2 * j + 1) * kLrMaxW + c);
+      pr[j][0] = __builtin_amdgcn_perm(y.x, x.x, 0x05040100u); pr[j][1] = __builtin_amdgcn_perm(y.x, x.x, 0x07060302u);
+      pr[j][2] = __builtin_amdgcn_perm(y.y, x.y, 0x05040100u); pr[j][3] = __builtin_amdgcn_perm(y.y, x.y, 0x07060302u);
+    }
+#pragma unroll
+    for (int v = FIRST; v < kLrFilters; v++) {
+      const int (&vf)[7] = F.f[v];
+      const s16x2 VE[4] = { lr_pk(vf[0], vf[1]), lr_pk(vf[2], vf[3]), lr_pk(vf[4], vf[5]), lr_pk(vf[6], 0) };
+      const s16x2 VO[4] = { lr_pk(0, vf[0]), lr_pk(vf[1], vf[2]), lr_pk(vf[3], vf[4]), lr_pk(vf[5], vf[6]) };
+      int se[4] = { 1024, 1024, 1024, 1024 }, so[4] = { 1024, 1024, 1024, 1024 };
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int m = 0; m < 4; m++) {
+          se[m] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, pr[j][m]), VE[j], se[m], false);
+          so[m] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, pr[j][m]), VO[j], so[m], false);
+        }
+#pragma unroll
+      for (int half = 0; half < 2; half++) {
+        if (r + half >= bh) continue;
+#pragma unroll
+        for (int m = 0; m < 4; m++) {
+          const int d = min(max((half ? so[m] : se[m]) >> 11, 0), (1 << BD) - 1) - lr_search_sample(sv[k][half], m);
+          err[v] += (unsigned)(d * d);
+        }
+      }
+    }
+  }
+}
+// ... and the scalar route, any width: the source sample by sample from memory
+template <typename Pix> __device__ __forceinline__ unsigned lr_search_none_scalar(const LrTile<Pix> &T, const uint16_t *src) {
+  unsigned e = 0;
+  for (int i = threadIdx.x; i < T.bh * T.bw; i += 256) {
+    const int r = i / T.bw, c = i - r * T.bw, d = (int)src[(r + 3) * kLrSS + c + 4] - (int)T.orig[T.at(r, c)];
+    e += (unsigned)(d * d);
+  }
+  return e;
+}
+template <typename Pix, int BD, int FIRST> __device__ __forceinline__ void lr_search_v_scalar(const LrTile<Pix> &T, const int16_t *inter, const LrSearchTaps &F,
+                                                                                             unsigned (&err)[kLrFilters]) {
+  for (int i = threadIdx.x; i < T.bh * T.bw; i += 256) {
+    const int r = i / T.bw, c = i - r * T.bw, sv = T.orig[T.at(r, c)];
+    int x[7];
+#pragma unroll
+    for (int t = 0; t < 7; t++) x[t] = inter[(r + t) * kLrMaxW + c];
+#pragma unroll
+    for (int v = FIRST; v < kLrFilters; v++) {
+      int sum = 0;
+#pragma unroll
+      for (int t = 0; t < 7; t++) sum += F.f[v][t] * x[t];
+      const int d = min(max((sum + 1024) >> 11, 0), (1 << BD) - 1) - sv;
+      err[v] += (unsigned)(d * d);
+    }
+  }
+}
+// The workgroup's nine sums into the unit's entry of the cost table: per wave in 32 bits (64 lanes x 2^24), the four waves and the
+// tiles of a unit in 64 — integer adds, so the table does not depend on the order the tiles finish in.  Uses the intermediate's LDS,
+// which every lane has left (the barrier).
+__device__ __forceinline__ void lr_search_finish(LrLds<false> &lds, const unsigned (&err)[kLrCands], unsigned long long *dst) {
+  const int tid = threadIdx.x;
+  unsigned *red = reinterpret_cast<unsigned *>(lds.scratch);      // [candidate][wave]
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < kLrCands; c++) {
+    unsigned a = err[c];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) a += __shfl_down(a, d, 64);
+    if ((tid & 63) == 0) red[c * 4 + (tid >> 6)] = a;
+  }
+  __syncthreads();
+  if (tid < kLrCands) atomicAdd(dst + tid, (unsigned long long)red[tid * 4] + red[tid * 4 + 1] + red[tid * 4 + 2] + red[tid * 4 + 3]);
 }
 
 // Self-guided (spec 7.17.3): box sums (r = 2 on odd rows, then r = 1) -> A (u16) / B (i32) in LDS -> 3x3 weighted a*x + b, both

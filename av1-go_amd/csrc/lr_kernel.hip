@@ -11,6 +11,8 @@
 // av1_selfguided_restoration_c; the reference has no counterpart (internal/ffmpeg/transcode.go:120).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
+#include "av1_ops.hpp"
 #include "lr_filter.hpp"
 
 namespace av1mi {
@@ -85,6 +87,127 @@ __global__ __launch_bounds__(64) void k_lr_decide(unsigned long long *sse, LrGeo
 hipError_t launch_lr_decide(unsigned long long *sse, const LrGeom &y, const LrGeom &c, int nplanes, uint8_t *on, int on_stride, bool clear, hipStream_t s) {
   hipLaunchKernelGGL(k_lr_decide, dim3((unsigned)((y.nframes * nplanes + 63) / 64)), dim3(64), 0, s, sse, y, c, nplanes, on, on_stride, clear);
   return hipGetLastError();
+}
+
+// ---- The restoration search (av1mi.h "restoration search").  k_lr_search: k_lr_yuv's tiles — a stripe x a band of 64 columns, the
+// three planes' grids end to end — each staged once through the get_source_sample rule, then per horizontal filter the int16
+// intermediate and one vertical pass over it that sums the squared error of every vertical filter's output against the source.  No
+// sample is stored: a workgroup's nine sums go by 64-bit integer atomic adds into its unit's entry of the cost table (a unit spans
+// several tiles: the stripes split it at rows 64 k - 8, and edge units are up to 1.5 units long).
+template <typename Pix, int SUBY>
+__device__ __forceinline__ void lr_search_tile(const LrSearchLaunch &S, int p, unsigned bid, unsigned nwg, LrLds<false> &lds) {
+  constexpr int bd = sizeof(Pix) == 1 ? 8 : 10;
+  const LrGeom G(S.w[p], S.h[p], SUBY, S.unit_size, S.nframes);
+  const Tile3 tl = xcd_tile(G.bands, G.stripes, S.nframes, bid, nwg);
+  const int X0 = tl.x * G.tile_w, f = tl.z;
+  LrTile<Pix> T;
+  T.stride = S.stride[p]; T.w = G.w; T.h = G.h; T.X0 = X0; T.sstart = G.first_row(tl.y); T.send = T.sstart + G.stripe_h - 1;
+  T.y0 = max(T.sstart, 0); T.y1 = min(T.send, G.h - 1);
+  if (T.y0 > T.y1 || X0 >= G.w) return;      // (uniform per workgroup, before any barrier)
+  T.bw = min(G.tile_w, G.w - X0); T.bh = T.y1 - T.y0 + 1;
+  const size_t frame = (size_t)f * G.h * T.stride;
+  T.cdef = reinterpret_cast<const Pix *>(S.cdef[p]) + frame; T.dbl = reinterpret_cast<const Pix *>(S.dbl[p]) + frame;
+  T.orig = reinterpret_cast<const Pix *>(S.orig[p]) + frame; T.out = nullptr;
+  if (X0 >= 4 && X0 + T.bw + 4 <= G.w && !(T.bw & 3)) lr_stage_aligned(T, lds.src);
+  else lr_stage_clamped(T, lds.src);
+  __syncthreads();
+  const LrSearchTaps F = lr_search_taps(S.taps[p ? 1 : 0]);
+  unsigned err[kLrCands] = {};
+  // candidate 3 v + h: the horizontal filters one after the other, under each the vertical ones (the pair (0, 0) is left out)
+  auto passes = [&](auto &&horizontal, auto &&vertical_all, auto &&vertical_from1) __attribute__((always_inline)) {
+#pragma unroll
+    for (int h = 0; h < kLrFilters; h++) {
+      if (h) __syncthreads();      // the last vertical pass has read the intermediate
+      horizontal(F.f[h]);
+      __syncthreads();
+      unsigned e[kLrFilters] = {};
+      if (h) vertical_all(e); else vertical_from1(e);
+#pragma unroll
+      for (int v = 0; v < kLrFilters; v++) err[3 * v + h] += e[v];
+    }
+  };
+  if (!(T.bw & 3)) {
+    uint2 sv[2][2];
+    lr_search_source(T, sv);
+    err[0] = lr_search_none_packed(lds.src, T.bw, T.bh, sv);
+    passes([&](const int (&hf)[7]) __attribute__((always_inline)) { lr_wiener_h_packed<bd>(lds.src, lds.inter(), T.bw, T.bh, hf); },
+           [&](unsigned (&e)[kLrFilters]) __attribute__((always_inline)) { lr_search_v_packed<bd, 0>(lds.inter(), T.bw, T.bh, F, sv, e); },
+           [&](unsigned (&e)[kLrFilters]) __attribute__((always_inline)) { lr_search_v_packed<bd, 1>(lds.inter(), T.bw, T.bh, F, sv, e); });
+  } else {
+    err[0] = lr_search_none_scalar(T, lds.src);
+    passes([&](const int (&hf)[7]) __attribute__((always_inline)) { lr_wiener_h_scalar<bd>(lds.src, lds.inter(), T.bw, T.bh, hf); },
+           [&](unsigned (&e)[kLrFilters]) __attribute__((always_inline)) { lr_search_v_scalar<Pix, bd, 0>(T, lds.inter(), F, e); },
+           [&](unsigned (&e)[kLrFilters]) __attribute__((always_inline)) { lr_search_v_scalar<Pix, bd, 1>(T, lds.inter(), F, e); });
+  }
+  lr_search_finish(lds, err, S.sums + ((size_t)f * S.units_frame + S.unit_first[p] + G.unit_index(X0, T.y0)) * kLrCands);
+}
+template <typename Pix>
+__global__ __launch_bounds__(256) void k_lr_search(LrSearchLaunch S) {
+  __shared__ LrLds<false> lds;
+  const unsigned b = blockIdx.x;
+  if (b < S.first[1]) lr_search_tile<Pix, 0>(S, 0, b, S.first[1], lds);
+  else if (b < S.first[2]) lr_search_tile<Pix, 1>(S, 1, b - S.first[1], S.first[2] - S.first[1], lds);
+  else lr_search_tile<Pix, 1>(S, 2, b - S.first[2], gridDim.x - S.first[2], lds);
+}
+// k_lr_pick: one lane per unit of a frame's three planes.  J_c = SSE_c + lambda * bits_c in 64-bit integers, the lowest J wins, the
+// lowest index on a tie; the unit's 8-byte record into its plane's array, the chosen index into choice
+__global__ __launch_bounds__(64) void k_lr_pick(LrSearchLaunch S) {
+  const unsigned i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= (unsigned)S.nframes * S.units_frame) return;
+  const unsigned f = i / S.units_frame, u = i - f * S.units_frame;
+  const int p = u < S.unit_first[1] ? 0 : u < S.unit_first[2] ? 1 : 2, cls = p ? 1 : 0;
+  const unsigned nunits = (p == 2 ? S.units_frame : S.unit_first[p + 1]) - S.unit_first[p];
+  const unsigned long long *sse = S.sums + (size_t)i * kLrCands;
+  int best = 0;
+  long long bestj = 0;
+  for (int c = 0; c < kLrCands; c++) {
+    const long long j = (long long)sse[c] + S.lambda * S.bits[cls][c];
+    if (c == 0 || j < bestj) { best = c; bestj = j; }
+  }
+  typedef signed char i8x8 __attribute__((ext_vector_type(8)));
+  i8x8 rec = { 0, 0, 0, 0, 0, 0, 0, 0 };
+  if (best) {
+    const int8_t *v = S.taps[cls][best / 3], *h = S.taps[cls][best % 3];
+    rec = i8x8{ 1, v[0], v[1], v[2], h[0], h[1], h[2], 0 };
+  }
+  *reinterpret_cast<i8x8 *>(S.units[p] + ((size_t)f * nunits + (u - S.unit_first[p])) * 8) = rec;
+  S.choice[i] = (uint8_t)best;
+}
+hipError_t launch_lr_search(LrSearchLaunch &S, hipStream_t s) {
+  unsigned n = 0;
+  for (int p = 0; p < 3; p++) { S.first[p] = n; n += LrGeom(S.w[p], S.h[p], p ? 1 : 0, S.unit_size, S.nframes).workgroups(); }
+  if (S.bd == 8) hipLaunchKernelGGL(k_lr_search<uint8_t>, dim3(n), dim3(256), 0, s, S);
+  else hipLaunchKernelGGL(k_lr_search<uint16_t>, dim3(n), dim3(256), 0, s, S);
+  return hipGetLastError();
+}
+hipError_t launch_lr_pick(const LrSearchLaunch &S, hipStream_t s) {
+  const unsigned n = (unsigned)S.nframes * S.units_frame;
+  hipLaunchKernelGGL(k_lr_pick, dim3((n + 63) / 64), dim3(64), 0, s, S);
+  return hipGetLastError();
+}
+// The candidates (av1mi.h states the table): the 1-D filters I, D, L per plane class as (tap0, tap1, tap2)
+static const int8_t kLrSearchTaps[2][3][3] = { { { 0, 0, 0 }, { 3, -7, 15 }, { 0, 2, 14 } }, { { 0, 0, 0 }, { 0, -7, 15 }, { 0, 2, 14 } } };
+void lr_search_tables(LrSearchLaunch *S) {
+  memcpy(S->taps, kLrSearchTaps, sizeof(kLrSearchTaps));
+  for (int cls = 0; cls < 2; cls++)
+    for (int c = 0; c < kLrCands; c++) S->bits[cls][c] = lr_search_bits(cls, c);
+}
+void lr_search_record(int chroma, int c, int8_t rec[8]) {
+  memset(rec, 0, 8);
+  if (c < 1 || c >= kLrCands) return;
+  const int8_t *v = kLrSearchTaps[chroma ? 1 : 0][c / 3], *h = kLrSearchTaps[chroma ? 1 : 0][c % 3];
+  rec[0] = 1;
+  for (int i = 0; i < 3; i++) { rec[1 + i] = v[i]; rec[4 + i] = h[i]; }
+}
+// bits_c: one for the use_wiener symbol, and the literal bits the coder's own syntax function (av1_ops.hpp tok_signed_subexp_ref)
+// emits for the record's taps against the default reference taps — what tok_lr codes with one superblock per tile
+namespace { struct BitCounter { int n = 0; void lit(unsigned, int nbits) { n += nbits; } }; }
+int lr_search_bits(int chroma, int c) {
+  int8_t u[8];
+  lr_search_record(chroma, c, u);
+  BitCounter k;
+  if (u[0] == 1) av1ops::tok_wiener_taps(k, av1ops::lr_record_word(u), chroma != 0);
+  return 1 + k.n;
 }
 
 // A frame whose true size (vw x vh) is not a multiple of 8 is coded at the size rounded up (w x h, at most 7 more columns / rows).

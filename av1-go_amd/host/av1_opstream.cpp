@@ -68,15 +68,25 @@ void frame_view_of(const av1mi_obu_frame &f, av1ops::FrameView *v) {
     v->lr_rows[p] = std::max((ph + 32) / 64, 1); v->lr_cols[p] = std::max((pw + 32) / 64, 1);
   }
 }
-// the op-stream coder takes ONE unit record per plane class (what the session's policy produces): check and copy it
+// the op-stream coder reads a unit's own record where the plane's records differ (FrameView::lr_units: the restoration search's
+// choice, Wiener or none), and the one shared record per plane class where they are all alike (what the session's policy produces:
+// the path the GPU coder takes with null arrays, so the two are compared on every frame of that kind)
 bool lr_units_of(const av1mi_obu_frame &f, av1ops::FrameView *v, std::string *err) {
+  bool shared = true;
   for (int p = 0; p < 3; p++) {
     if (!v->lr_on[p]) continue;
     const int8_t *u = f.lr_units[p];
     const size_t n = (size_t)v->lr_rows[p] * v->lr_cols[p];
-    for (size_t i = 1; i < n; i++) if (memcmp(u, u + i * 8, 8)) { if (err) *err = "restoration units must be uniform per plane"; return false; }
-    if (p == 2 && v->lr_on[1] && memcmp(u, f.lr_units[1], 8)) { if (err) *err = "U and V restoration units must be equal"; return false; }
-    memcpy(v->lr_unit[p ? 1 : 0], u, 8);
+    for (size_t i = 0; i < n; i++) {
+      if (u[i * 8] != 0 && u[i * 8] != 1) { if (err) *err = "Wiener restoration units only"; return false; }
+      if (memcmp(u, u + i * 8, 8)) shared = false;
+    }
+    if (p == 2 && v->lr_on[1] && memcmp(u, f.lr_units[1], 8)) shared = false;
+  }
+  for (int p = 0; p < 3; p++) {
+    if (!v->lr_on[p]) continue;
+    if (shared) memcpy(v->lr_unit[p ? 1 : 0], f.lr_units[p], 8);
+    else v->lr_units[p] = f.lr_units[p];
   }
   return true;
 }

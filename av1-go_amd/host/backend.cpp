@@ -75,6 +75,7 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
   cfg.search_range = 8;
   cfg.coarse_range = job.me_range;      // -av1mi_me_range: the coarse search in front of it
   cfg.gpu_entropy = job.gpu_entropy ? 1 : 0;
+  cfg.lr_search = job.lr_search;        // -av1mi_lr_search: a restoration record chosen per unit
   // -av1mi_stats / -av1mi_min_psnr: the session measures every batch on the GPU; the records arrive with the collected batch
   plan->measure = !job.stats_path.empty() || job.min_psnr > 0;
   cfg.quality_stats = plan->measure ? 1 : 0;
@@ -127,6 +128,7 @@ std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, c
   if (tags.q) k += snprintf(line + k, sizeof(line) - (size_t)k, " q:%d", f.base_q_idx);
   if (tags.grain) k += snprintf(line + k, sizeof(line) - (size_t)k, " grain:%d", f.grain);
   if (tags.ar) k += snprintf(line + k, sizeof(line) - (size_t)k, " ar:%d", f.ar);
+  if (tags.lr) k += snprintf(line + k, sizeof(line) - (size_t)k, " lr:%d/%d", f.lr_filtered, f.lr_units);
   if (cut) k += snprintf(line + k, sizeof(line) - (size_t)k, " cut:1");
   return std::string(line, (size_t)k);
 }
@@ -347,6 +349,14 @@ struct Run {
                                plan.grainy ? &fg : nullptr, sp.has_colour() ? &plan.colour : nullptr)) return 2;
       batch_bytes += (long long)f.unit.size();
       f.base_q_idx = oldest.params.base_q_idx;
+      if (job.lr_search) {      // the units of the three planes that are filtered: a Wiener record chosen, in a plane whose restoration stayed ON
+        if (!oldest.lr_choice) return fail(2, "the session returned no restoration choices");
+        const int per[3] = { oldest.lr_units_per_frame[0], oldest.lr_units_per_frame[1], oldest.lr_units_per_frame[2] }, all = per[0] + per[1] + per[2];
+        const uint8_t *choice = oldest.lr_choice + (size_t)s * all, *on = oldest.lr_on ? oldest.lr_on + (size_t)s * 3 : nullptr;
+        for (int p = 0, u = 0; p < 3; p++)
+          for (int i = 0; i < per[p]; i++, u++) f.lr_filtered += choice[u] != 0 && (!on || on[p]);
+        f.lr_units = all;
+      }
       if (plan.measure) {
         if (!oldest.quality) return fail(2, "the session returned no quality records");
         memcpy(f.q, oldest.quality + (size_t)s * 3, sizeof(f.q));
@@ -386,7 +396,7 @@ struct Run {
   // the group's frames in presentation order: each unit to the sink, its line to the stats
   int write_group(const Group &group, const GroupOut &out) {
     StatsTags tags;
-    tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0; tags.ar = job.grain_lag > 0;
+    tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0; tags.ar = job.grain_lag > 0; tags.lr = job.lr_search != 0;
     for (int s = 0; s < S; s++)
       for (size_t t = 0; t < out[(size_t)s].size(); t++) {
         const FrameOut &f = out[(size_t)s][t];

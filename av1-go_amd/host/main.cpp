@@ -6,6 +6,8 @@
 //                   (-av1mi_format 420, or a format= filter naming a 4:2:0 format in CHAIN: 4:2:2 / 4:4:4 / grey and 12-bit sources are
 //                   accepted and converted to 4:2:0 on the GPU)
 //                   (-av1mi_stats: per-frame PSNR / SSIM measured on the GPU; -av1mi_min_psnr: fail with exit code 3 below that luma PSNR)
+//                   (-av1mi_lr_search 0 | 1: 1 = a Wiener restoration record or none chosen per 64x64 unit on the GPU; the stats file's frame
+//                   lines gain " lr:<units filtered>/<units>")
 //                   (-av1mi_me_range: 0, or a multiple of 4 up to 64: the P frames' motion search follows N + 8 samples per frame)
 //                   (CHAIN: the reference's scale filters, evaluated on the source's size and sample aspect ratio and applied on the GPU;
 //                   -av1mi_scale: an explicit output size, wins over the chain; any other filter is refused)

@@ -31,6 +31,9 @@ void DescribeSessionFrame(const av1mi_gop_frame &fr, int seg, int width, int hei
   f.lr_type[2] = (!on || on[2]) ? p.lr_unit_uv[0] : 0;
   f.lr_unit_shift = p.lr_unit_size == 64 ? 0 : p.lr_unit_size == 128 ? 1 : 2; f.lr_uv_shift = 0;
   f.lr_units[0] = d->lr_y.data(); f.lr_units[1] = f.lr_units[2] = d->lr_uv.data();
+  // a session with the restoration search: the segment's own records per plane (the session keeps the true size's grid of units)
+  for (int q = 0; q < 3; q++)
+    if (fr.lr_units[q] && (size_t)fr.lr_units_per_frame[q] == (q ? uc : uy)) f.lr_units[q] = fr.lr_units[q] + (size_t)seg * fr.lr_units_per_frame[q] * 8;
   f.tile_cols_log2 = f.tile_rows_log2 = -1;      // one superblock per tile: the independence the GPU pipeline's prediction assumes
   const size_t nb = fr.blocks_per_frame, o = (size_t)seg * nb;
   if (fr.y_mode) { f.y_mode = fr.y_mode + o; f.uv_mode = fr.uv_mode + o; }       // the symbols are absent when the tiles were coded on the GPU

@@ -286,6 +286,9 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
       if (args[i + 1] != "420") { if (err) *err = "Invalid argument: -av1mi_format takes 420 (the only layout that is coded), not " + args[i + 1]; return false; }
       job->to_420 = true;
     }
+    else if (args[i] == "-av1mi_lr_search") {
+      if (!plain_int(args[i + 1], &job->lr_search) || job->lr_search > 1) { if (err) *err = "Invalid argument: -av1mi_lr_search takes 0 or 1, not " + args[i + 1]; return false; }
+    }
     else if (args[i] == "-av1mi_me_range") {
       if (!plain_int(args[i + 1], &job->me_range) || job->me_range > 64 || (job->me_range & 3)) { if (err) *err = "Invalid argument: -av1mi_me_range takes 0 or a multiple of 4 up to 64, not " + args[i + 1]; return false; }
     }

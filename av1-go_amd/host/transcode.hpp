@@ -63,6 +63,8 @@ struct BackendJob {
                            // (av1mi_gop_config.quality_stats), one line per frame in presentation order + a summary line
   double min_psnr = 0;     // -av1mi_min_psnr <dB>: the quality gate on the summary's psnr_y (0 = off), with or without a stats file: below it the
                            // transcode fails with exit code 3, "quality gate: psnr_y ...", and the output is removed
+  int lr_search = 0;       // -av1mi_lr_search 0 | 1: 1 = a Wiener record or none chosen per restoration unit on the GPU (av1mi_gop_config.lr_search); the
+                           // stats file's frame lines gain " lr:<units filtered>/<units>"
   int me_range = 0;        // -av1mi_me_range N: 0 (default), or a multiple of 4 up to 64: P frames search around a coarse centre per 64x64 tile
                            // (av1mi_gop_config.coarse_range): vectors reach N + 8 samples per frame instead of 8
   // A target instead of the fixed quantiser (host/ratecontrol.hpp: one quantiser per batch, chosen from the bytes of the batches before).

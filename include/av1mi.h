@@ -251,6 +251,8 @@ typedef struct av1mi_lr_decide_job {
   int no_self_guided_units;                      /* != 0: the caller promises that no unit record has type 2 (the session's policy:
                                                     Wiener or none) — the kernel then runs without the self-guided path's 18 KB of LDS, at
                                                     twice the occupancy; a type-2 unit would be left unfiltered */
+  const int8_t *d_units_v; size_t unit_frame_stride_v;   /* optional: the V plane's own units (what av1mi_lr_search writes); null:
+                                                    d_units_uv / unit_frame_stride_uv serve U and V */
 } av1mi_lr_decide_job;
 size_t av1mi_lr_yuv_decide_scratch_bytes(int height, int nframes);
 int av1mi_lr_yuv_decide(av1mi_ctx *ctx, const av1mi_lr_decide_job *job);
@@ -262,6 +264,54 @@ size_t av1mi_lr_decide_scratch_bytes(int h, int subsampled, int nframes);
 int av1mi_lr_frames_decide(av1mi_ctx *ctx, const void *d_cdef, const void *d_deblocked, void *d_out, int stride, int w, int h, int bd, int subsampled,
                            int unit_size, const int8_t *d_units, size_t unit_frame_stride, int nframes, const void *d_orig, void *d_scratch, uint8_t *d_on,
                            int on_stride);
+
+/* ---- restoration search (policy, non-normative): a Wiener filter chosen per 64 x 64 restoration unit, or none, by squared error
+ * against the source plus the exact cost of the unit's record.
+ *
+ * The candidates.  Three 1-D filters per plane class, written (tap0, tap1, tap2) of the symmetric 7-tap form (layout of
+ * av1mi_lr_frames; chroma filters have tap0 = 0, as the syntax demands):
+ *                filter 0  I (identity)   filter 1  D (the policy's, libaom's mid-range taps)   filter 2  L (a low-pass)
+ *     luma       ( 0,  0,  0)             ( 3, -7, 15)                                           ( 0,  2, 14)
+ *     chroma     ( 0,  0,  0)             ( 0, -7, 15)                                           ( 0,  2, 14)
+ * Candidate 0 is "none": the unit is not filtered (record type 0).  Candidate c = 1 .. 8 is the Wiener record with the VERTICAL
+ * filter c / 3 and the HORIZONTAL filter c % 3:
+ *     c       1      2      3      4      5      6      7      8
+ *     v, h    I, D   I, L   D, I   D, D   D, L   L, I   L, D   L, L
+ * The pair (I, I) is exactly the identity and is left out; candidate 4 is the record of av1mi_frame_params.
+ *
+ * The cost of candidate c for a unit, in 64-bit integers:  J_c = SSE_c + lambda * bits_c.  SSE_c: the squared error against the
+ * source over the unit's samples of the plane after restoration with c (c = 0: of the CDEF samples).  bits_c
+ * (av1mi_lr_search_bits): 1 for the use_wiener symbol plus the literal bits the tile syntax spends on the record's taps, each coded
+ * against the default reference taps (3, -7, 15) — exact for this encoder's one superblock per tile, where every tile resets the
+ * reference.  lambda (av1mi_lr_search_lambda) = (3 * av1mi_dc_q(qindex, bit_depth)^2) >> 7.  The lowest J wins; on a tie the
+ * lowest index.
+ *
+ * av1mi_lr_search runs the search for the three planes of nframes 4:2:0 frames stacked vertically (geometry, d_cdef_*, d_dbl_*,
+ * d_orig_* as in av1mi_lr_decide_job; unit_size must be 64).  Outputs, all device memory:
+ *   d_scratch  the cost table, av1mi_lr_search_scratch_bytes() bytes, 16-byte aligned; the call zeroes it.  Afterwards it holds
+ *              uint64 SSE[frame][unit][candidate], a frame's units being those of Y, then U, then V, each plane's in raster order
+ *              (rows x cols as in av1mi_lr_frames): av1mi_lr_search_units(width, height, 64) of them per frame.
+ *   d_units_y / d_units_u / d_units_v   the chosen 8-byte record of every unit, [frame][unit of the plane]: what av1mi_lr_frames
+ *              and av1mi_lr_yuv_decide (d_units_y, d_units_uv, d_units_v) take, with the plane's unit count as the frame stride.
+ *   d_choice   one byte per unit, [frame][unit] in the cost table's order: the chosen candidate's index.
+ * Three launches (the zeroing one, k_lr_search, k_lr_pick), asynchronous on the context's stream; all under AV1MI_K_LR in the profile. */
+#define AV1MI_LR_SEARCH_CANDIDATES 9
+typedef struct av1mi_lr_search_job {
+  int width, height, bit_depth, nframes, unit_size, qindex;
+  int stride_y, stride_uv;
+  const void *d_cdef_y, *d_cdef_u, *d_cdef_v;
+  const void *d_dbl_y, *d_dbl_u, *d_dbl_v;
+  const void *d_orig_y, *d_orig_u, *d_orig_v;
+  void *d_scratch;
+  int8_t *d_units_y, *d_units_u, *d_units_v;
+  uint8_t *d_choice;
+} av1mi_lr_search_job;
+int av1mi_lr_search_units(int width, int height, int unit_size);       /* units of a frame's three planes together */
+size_t av1mi_lr_search_scratch_bytes(int width, int height, int unit_size, int nframes);
+int av1mi_lr_search_candidate(int chroma, int c, int8_t record[8]);    /* candidate c's record; AV1MI_E_INVAL outside 0 .. 8 */
+int av1mi_lr_search_bits(int chroma, int c);                           /* bits_c; -1 outside 0 .. 8 */
+long long av1mi_lr_search_lambda(int qindex, int bit_depth);
+int av1mi_lr_search(av1mi_ctx *ctx, const av1mi_lr_search_job *job);
 
 /* ---- the intra-only segment pipeline (BASELINE config 2): what stands in for the encode the reference delegates
  * to `ffmpeg -c:v:0 av1_vaapi` (transcode.go:120) for key frames.  One launch codes `nframes` frames that are
@@ -366,6 +416,14 @@ typedef struct av1mi_av1_entropy_job {
                                                   32x32 blocks: their modes one per 32x32 block from entry 0 of d_modes_*, their levels
                                                   block-contiguous over the 32x32 grid; the rows below in 8x8 blocks at their usual places */
 } av1mi_av1_entropy_job;
+/* The restoration units' own records for a job (the restoration search's choice), beside the job and not inside it: callers built
+ * against the job as it stands hand over a struct that ends at key_rows32, and a field behind it would be read from their memory.
+ * d_units[p] (Y, U, V): 8-byte records (type 0 none / 1 Wiener), per frame rows x cols in raster order as the units tile the TRUE
+ * frame — what av1mi_lr_search writes; null = lr_unit_y / lr_unit_uv serve every unit of the plane.  frame_stride[p]: units between
+ * the frames of d_units[p], 0 = one frame's records serve all.  The three pointers are all given or all null, and 8-byte aligned (a
+ * record is read as one word); anything else is AV1MI_E_INVAL.  units = NULL: av1mi_av1_entropy_encode_on. */
+typedef struct av1mi_av1_entropy_units { const int8_t *d_units[3]; size_t frame_stride[3]; } av1mi_av1_entropy_units;
+int av1mi_av1_entropy_encode_units(av1mi_ctx *ctx, const av1mi_av1_entropy_job *job, const av1mi_av1_entropy_units *units, void *stream);
 int av1mi_av1_entropy_encode(av1mi_ctx *ctx, const av1mi_av1_entropy_job *job);
 /* the same on another HIP stream of the caller's (hipStream_t passed as void *; NULL = the context's stream) */
 int av1mi_av1_entropy_encode_on(av1mi_ctx *ctx, const av1mi_av1_entropy_job *job, void *stream);
@@ -876,6 +934,12 @@ typedef struct av1mi_gop_config {
    * event as the grain records; av1mi_gop_frame.grain_cov carries the batch's records.  The fed buffers and everything behind them are
    * untouched: the coded bytes are those of the session without it. */
   int grain_cov;
+  /* restoration search ("restoration search"): 0 = every unit of a plane is filtered with the policy's one record, as ever; 1 = a
+   * Wiener record or none is chosen per 64 x 64 unit and frame (k_lr_search, k_lr_pick in front of the restoration, on the same
+   * stream), the restoration and its per-plane ON / OFF decision run with the chosen units, the GPU coder codes them, and
+   * av1mi_gop_frame.lr_units carries them.  Per slot: the three unit arrays, the cost table and the index bytes.  Refused where the
+   * units of the coded size and of the true size form different grids.  With 0 nothing of this is allocated or launched. */
+  int lr_search;
 } av1mi_gop_config;
 
 /* The source layout: what a session opened with a config is FED, as one description.  Everything a caller sizes or strides by — the
@@ -947,6 +1011,12 @@ typedef struct av1mi_gop_frame {    /* one collected frame batch; host pointers 
   /* av1mi_gop_config.grain_cov: segments * 3 covariance records [segment * 3 + plane] of this batch ("grain covariance"), in pinned
    * memory, valid where `grain` is; NULL when the option is off (and for a batch of av1mi_gop_submit_device) */
   const av1mi_grain_cov_record *grain_cov;
+  /* av1mi_gop_config.lr_search: the chosen unit records of this batch per plane (Y, U, V), [segment][unit of the plane][8], in pinned
+   * memory (what av1mi_obu_frame.lr_units takes for a segment), lr_units_per_frame[p] units per segment; lr_choice: the chosen
+   * candidates' indices, [segment][units of Y, U, V end to end].  NULL / 0 when the option is off */
+  const int8_t *lr_units[3];
+  int lr_units_per_frame[3];
+  const uint8_t *lr_choice;
 } av1mi_gop_frame;
 
 typedef struct av1mi_gop av1mi_gop;
