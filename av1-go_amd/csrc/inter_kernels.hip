@@ -4,20 +4,20 @@
 //                (tile + search range, coordinates clamped = the spec's edge extension) staged in LDS; one 8x8 block
 //                per wave at a time, ONE CANDIDATE VECTOR PER LANE, the 64 source samples broadcast from LDS;
 //                (SAD, raster rank) packed into one integer and min-reduced across the wave with xor-shuffles.
-//   k_inter_pipe per block, 8 lanes of one wave (8 blocks per wave, no dependency between blocks): half-pel refinement scored
-//                with the bilinear filter (= rounded averages, no filter passes), quarter-pel refinement with the real 8-tap
-//                sub-pel filter (K4 arithmetic, window in LDS), final
-//                luma + chroma motion compensation, then the shared residual tail (K1 + K8 + K2, block_code.hpp),
-//                skip flag and final vector.
+//   k_inter_pipe per block, 8 lanes of one wave (8 blocks per wave, no dependency between blocks), seven phases, a function each:
+//                1 the block of this group; 2 luma window into LDS; 3 score of the integer vector; 4 half-pel refinement scored
+//                with the bilinear filter (= rounded averages, no filter passes); 5 quarter-pel refinement with the real 8-tap
+//                sub-pel filter (K4 arithmetic, subpel.hpp); 6 luma and 7 chroma motion compensation + the shared residual tail
+//                (K1 + K8 + K2, block_code.hpp), skip flag and final vector.
 // Inter blocks only depend on the PREVIOUS frame, so a P frame is embarrassingly parallel; the serial dependency is
 // frame-to-frame inside a GOP and the pipeline batches the t-th frames of many segments into one launch.
 // HBM traffic per sample (k_inter_pipe): source b + reference window (L2-served after first touch) ~b + reconstruction
 // b + levels 2.
 //
-// Arithmetic: AV1 spec §7.11.3.4 (see mc_kernels.hip) + §7.13.3 / §7.12.3; search policy is this project's own and
+// Arithmetic: AV1 spec §7.11.3.4 (subpel.hpp, shared with mc_kernels.hip) + §7.13.3 / §7.12.3; search policy is this project's own and
 // mirrored by oracle/av1o_pipeline.c:av1o_inter_encode_frame.  Reference tree: nothing (transcode.go:120).
 #include "block_code.hpp"
-#include "motion_common.hpp"
+#include "subpel.hpp"
 
 namespace av1mi {
 
@@ -178,236 +178,279 @@ __global__ __launch_bounds__(256) void k_me_int(InterLaunch L) {
 }
 
 // ------------------------------------------------------------------------------------------ refinement + coding
-// 2-D sub-pel prediction of row `lane` of a B x B block from a window in LDS (origin = integer position - 4, i.e. the
-// window starts 4 samples left of / above the integer-vector block): posx/posy = displacement from the window's block
-// origin in 1/16 samples, in [-16, 15].  im: (B+7) x B int16 scratch of the group.  NL = lanes of the block.
-// N consecutive samples starting `ox` samples into a dword-aligned LDS row: aligned dword reads + funnel shift, so that the
-// row costs (N * sizeof(ES)) / 4 + 1 LDS reads instead of N (k_inter_pipe is LDS-bound).  ox in [0, 4 / sizeof(ES)).
-template <int N, typename ES> __device__ __forceinline__ void row_samples(const ES *row, int ox, int *v) {
-  const uint32_t *q = reinterpret_cast<const uint32_t *>(row);
-  constexpr int PER = 4 / (int)sizeof(ES), ND = (N + PER - 1) / PER;
-  uint32_t w[ND + 1], a[ND];
-#pragma unroll
-  for (int i = 0; i <= ND; i++) w[i] = q[i];
-#pragma unroll
-  for (int i = 0; i < ND; i++) {
-    if constexpr (sizeof(ES) == 1) a[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], ox);
-    else a[i] = __builtin_amdgcn_alignbit(w[i + 1], w[i], ox * 16);
-  }
-#pragma unroll
-  for (int i = 0; i < N; i++) v[i] = (a[i / PER] >> ((i % PER) * 8 * (int)sizeof(ES))) & (sizeof(ES) == 1 ? 255u : 0xffffu);
-}
-
-// T0, T1: the filter family's non-zero taps are T0 .. T1 - 1 (the 4-tap families of blocks <= 4 wide: 2 .. 5; the other taps
-// are exactly 0, so leaving them out changes nothing but the work: 7 intermediate rows of 4 taps instead of 11 of 8).
-template <int B, typename ES, int T0 = 0, int T1 = 8>
-__device__ __forceinline__ void mc_row(const ES *win, int ws, int16_t *im, int lane, int posx, int posy, const int16_t (*filt)[8], int bd,
-                                       int *out) {
-  const int ox = 4 + (posx >> 4) - 3, oy = 4 + (posy >> 4) - 3;   // window column / row of tap 0 of sample (0,0)
-  constexpr int NT = T1 - T0, NR = B + NT - 1, PER = 4 / (int)sizeof(ES);
-  int fx[NT], fy[NT];
-#pragma unroll
-  for (int t = 0; t < NT; t++) { fx[t] = filt[posx & 15][T0 + t]; fy[t] = filt[posy & 15][T0 + t]; }
-#pragma unroll
-  for (int it = 0; it < (NR + B - 1) / B; it++) {   // intermediate rows T0 .. T0 + NR - 1 over B lanes
-    const int j = T0 + lane + it * B;
-    if (j < T0 + NR) {
-      int v[NR];
-      const int o = ox + T0;                        // first sample of the row that a non-zero tap touches
-      row_samples<NR, ES>(win + (oy + j) * ws + (o & ~(PER - 1)), o & (PER - 1), v);
-#pragma unroll
-      for (int c = 0; c < B; c++) {
-        int s = 0;
-#pragma unroll
-        for (int t = 0; t < NT; t++) s += fx[t] * v[c + t];
-        im[j * B + c] = (int16_t)((s + 4) >> 3);
-      }
-    }
-  }
-  AV1MI_GROUP_SYNC();
-  const int maxpix = (1 << bd) - 1;
-#pragma unroll
-  for (int c = 0; c < B; c++) {
-    int s = 0;
-#pragma unroll
-    for (int t = 0; t < NT; t++) s += fy[t] * (int)im[(lane + T0 + t) * B + c];
-    out[c] = min(max((s + 1024) >> 11, 0), maxpix);
-  }
-  AV1MI_GROUP_SYNC();
-}
-
-// The same filter split in two, so that the candidates of a refinement round that share a horizontal phase share its
-// (more expensive) horizontal pass: mc_h16 filters all 16 rows of the luma window for one horizontal displacement,
-// mc_rows7 + mc_v7 produce row `lane` of the prediction for the vertical displacements from that intermediate.
-template <typename ES>
-__device__ __forceinline__ void mc_h16(const ES *win, int ws, int16_t *im, int lane, int posx, const int16_t (*filt)[8]) {
-  const int ox = 4 + (posx >> 4) - 3;            // 0 or 1
-  int fx[8];
-  if constexpr (sizeof(ES) == 1) {
-#pragma unroll
-    for (int t = 0; t < 8; t++) fx[t] = filt[posx & 15][t];
-  }
-  constexpr int PER = 4 / (int)sizeof(ES), ND = 16 / PER;
-#pragma unroll
-  for (int it = 0; it < 2; it++) {
-    const int j = lane + it * 8;
-    // the row's 16 samples from ox on, as aligned dwords funnel-shifted by ox samples
-    const uint32_t *q = reinterpret_cast<const uint32_t *>(win + j * ws);
-    uint32_t w[ND + 1], a[ND];
-#pragma unroll
-    for (int i = 0; i <= ND; i++) w[i] = q[i];
-#pragma unroll
-    for (int i = 0; i < ND; i++) {
-      if constexpr (sizeof(ES) == 1) a[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], ox);
-      else a[i] = __builtin_amdgcn_alignbit(w[i + 1], w[i], ox * 16);
-    }
-    int sum[8];
-    if constexpr (sizeof(ES) == 1) {
-      // 8 taps = two v_dot4_i32_i8 on the samples biased to signed bytes (p - 128), except tap 3 (it reaches 128, one more
-      // than a signed byte holds), which is a separate multiply-add on the unbiased sample.  The bias is paid back in the
-      // accumulator: sum over t != 3 of f_t * 128 = 128 * (128 - f_3).
-      uint32_t b[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) b[i] = a[i] ^ 0x80808080u;
-      const int F0 = (fx[0] & 255) | ((fx[1] & 255) << 8) | ((fx[2] & 255) << 16);
-      const int F1 = (fx[4] & 255) | ((fx[5] & 255) << 8) | ((fx[6] & 255) << 16) | ((fx[7] & 255) << 24);
-      const int acc0 = 4 + 128 * (128 - fx[3]);
-      uint32_t d[12];
-#pragma unroll
-      for (int c = 0; c < 12; c++) d[c] = (c & 3) ? __builtin_amdgcn_alignbyte(b[(c >> 2) + 1], b[c >> 2], c & 3) : b[c >> 2];
-#pragma unroll
-      for (int c = 0; c < 8; c++) {
-        const int p3 = (int)((a[(c + 3) >> 2] >> (((c + 3) & 3) * 8)) & 255);
-        sum[c] = __builtin_amdgcn_sdot4(F0, (int)d[c], __builtin_amdgcn_sdot4(F1, (int)d[c + 4], acc0 + fx[3] * p3, false), false);
-      }
-    } else {
-      // 10-bit: the regular filter has SIX taps (taps 0 and 7 are 0 at every phase): sample pairs (m, m + 1) for m = 1..12 (odd
-      // m by funnel shift) against the tap pairs (t1, t2) (t3, t4) (t5, t6) = three v_dot2_i32_i16 per sample
-      uint32_t pm[13];
-#pragma unroll
-      for (int m = 1; m < 13; m++) pm[m] = (m & 1) ? __builtin_amdgcn_alignbit(a[(m + 1) >> 1], a[m >> 1], 16) : a[m >> 1];
-      // the tap row is 8 int16 = (t0, t1) (t2, t3) (t4, t5) (t6, t7) as they lie in memory: the pairs one tap further by funnel shift
-      const uint4 fq = *reinterpret_cast<const uint4 *>(filt[posx & 15]);
-      const uint32_t g1 = __builtin_amdgcn_alignbit(fq.y, fq.x, 16), g2 = __builtin_amdgcn_alignbit(fq.z, fq.y, 16), g3 = __builtin_amdgcn_alignbit(fq.w, fq.z, 16);
-#pragma unroll
-      for (int c = 0; c < 8; c++) {
-        int acc = dot2_start(pm[c + 1], g1, 128);   // taps x 32 (see below): the rounding constant 4 x 32
-        acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, pm[c + 3]), __builtin_bit_cast(s16x2, g2), acc, false);
-        acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, pm[c + 5]), __builtin_bit_cast(s16x2, g3), acc, false);
-        sum[c] = acc;
-      }
-    }
-    uint32_t o[4];
-    if constexpr (sizeof(ES) == 1) {
-#pragma unroll
-      for (int c = 0; c < 8; c++) {
-        const uint32_t h = (uint32_t)(sum[c] >> 3) & 0xffff;
-        o[c >> 1] = (c & 1) ? (o[c >> 1] | (h << 16)) : h;
-      }
-    } else {
-      // 10-bit: `filt` is the x 32 table, (32 s + 128) >> 8 == (s + 4) >> 3: the int16 result is bytes 1..2 of the accumulator, and
-      // one v_perm shifts and packs two of them (|32 s| < 2^23: no overflow)
-#pragma unroll
-      for (int j = 0; j < 4; j++) o[j] = __builtin_amdgcn_perm((uint32_t)sum[2 * j + 1], (uint32_t)sum[2 * j], 0x06050201u);
-    }
-    *reinterpret_cast<uint4 *>(im + j * 8) = make_uint4(o[0], o[1], o[2], o[3]);
-  }
-}
-// mc_h16 for a whole-sample horizontal position (posx = 0): phase 0 is the identity, (128 p + 4) >> 3 = 16 p exactly.
-template <typename ES>
-__device__ __forceinline__ void mc_h16_copy(const ES *win, int ws, int16_t *im, int lane) {
-#pragma unroll
-  for (int it = 0; it < 2; it++) {
-    const int j = lane + it * 8;
-    uint32_t o[4];
-    if constexpr (sizeof(ES) == 2) {
-      const uint4 a = *reinterpret_cast<const uint4 *>(win + j * ws + 4);        // samples 4 .. 11 of the row, two per dword
-      o[0] = a.x << 4; o[1] = a.y << 4; o[2] = a.z << 4; o[3] = a.w << 4;         // p < 2^12: no carry between the halves
-    } else {
-      const uint2 a = *reinterpret_cast<const uint2 *>(win + j * ws + 4);
-      o[0] = __builtin_amdgcn_perm(0u, a.x, 0x0c010c00u) << 4; o[1] = __builtin_amdgcn_perm(0u, a.x, 0x0c030c02u) << 4;
-      o[2] = __builtin_amdgcn_perm(0u, a.y, 0x0c010c00u) << 4; o[3] = __builtin_amdgcn_perm(0u, a.y, 0x0c030c02u) << 4;
-    }
-    *reinterpret_cast<uint4 *>(im + j * 8) = make_uint4(o[0], o[1], o[2], o[3]);
-  }
-}
-// The vertical displacements of one refinement round differ by less than a sample and the regular filter has six taps (1..6),
-// so row `lane` of all of them reads intermediate rows lane + 1 .. lane + 7: those seven rows (16 bytes each) are loaded ONCE
-// per horizontal position (mc_rows7) and every vertical candidate is a 7-tap sum over them — the six taps of its phase shifted
-// by its integer part, a zero at the other end (mc_v7).  The first version of k_inter_pipe was LDS-bound (LDS busy 85 % of the
-// kernel by PMC); this cut the reads of the vertical pass from 8 per candidate to 7 per three candidates.
-// After the LDS diet the kernel is VALU-bound, so the vertical sums run on v_dot2_i32_i16: the rows are interleaved once per
-// horizontal position into row PAIRS per column, pr[kp][c] = (row 2kp + 1, row 2kp + 2) of column c ("row 8" = a constant), and
-// a candidate is 4 dot2 per sample instead of 7 multiply-adds + 7 extracts (exact: int16 x int16 into int32).
-__device__ __forceinline__ void mc_rows7(const int16_t *im, int lane, uint32_t (*pr)[8]) {
-  uint4 rw[8];
-#pragma unroll
-  for (int k = 0; k < 7; k++) rw[k] = *reinterpret_cast<const uint4 *>(im + (lane + 1 + k) * 8);
-  rw[7] = make_uint4(0x00020002u, 0x00020002u, 0x00020002u, 0x00020002u);   // "row 8" = the constant 2: carries mc_v7's rounding term
-#pragma unroll
-  for (int kp = 0; kp < 4; kp++) {
-    const uint32_t x[4] = { rw[2 * kp].x, rw[2 * kp].y, rw[2 * kp].z, rw[2 * kp].w };
-    const uint32_t y[4] = { rw[2 * kp + 1].x, rw[2 * kp + 1].y, rw[2 * kp + 1].z, rw[2 * kp + 1].w };
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-      pr[kp][2 * d] = __builtin_amdgcn_perm(y[d], x[d], 0x05040100u);       // (x.lo, y.lo)
-      pr[kp][2 * d + 1] = __builtin_amdgcn_perm(y[d], x[d], 0x07060302u);   // (x.hi, y.hi)
-    }
-  }
-}
-// `filt32` holds the taps times 32: (32 s + 32768) >> 16 == (s + 1024) >> 11 exactly, and the result is then the high half of
-// the accumulator — one v_perm takes the high halves of two sums, shift and pack in one instruction (the products stay far
-// inside int32: |intermediate| < 2^15, sum of |taps| x 32 < 2^13).  Returns row `lane` of the prediction as four packed pairs.
-__device__ __forceinline__ void mc_v7(const uint32_t (*pr)[8], int posy, const int16_t (*filt32)[8], int bd, uint32_t *ow) {
-  const int oy = 4 + (posy >> 4) - 3;            // 0 or 1
-  // the taps over rows lane + 1 .. lane + 7 as pairs.  The tap row lies in memory as (t0, t1) (t2, t3) (t4, t5) (t6, t7), t0 = t7 = 0:
-  //   oy = 1 (rows 2 .. 7 carry t1 .. t6): (0, t1) (t2, t3) (t4, t5) (t6, .)   = the row as it lies;
-  //   oy = 0 (rows 1 .. 6 carry t1 .. t6): (t1, t2) (t3, t4) (t5, t6) (0, .)   = one funnel shift per pair.
-  // The last pair's second row is the constant 2 (mc_rows7) and its tap 16384: 2 x 16384 = 32768 is the rounding term, so the
-  // accumulators start at 0 — an inline constant of the first dot2 instead of a v_mov of a literal per column.
-  const uint4 fq = *reinterpret_cast<const uint4 *>(filt32[posy & 15]);
-  const uint32_t g[4] = { oy ? fq.x : __builtin_amdgcn_alignbit(fq.y, fq.x, 16), oy ? fq.y : __builtin_amdgcn_alignbit(fq.z, fq.y, 16),
-                          oy ? fq.z : __builtin_amdgcn_alignbit(fq.w, fq.z, 16), (oy ? (fq.w & 0xFFFFu) : 0u) | 0x40000000u };
-  int s[8];
-#pragma unroll
-  for (int kp = 0; kp < 4; kp++) {
-    const s16x2 gp = __builtin_bit_cast(s16x2, g[kp]);
-#pragma unroll
-    for (int c = 0; c < 8; c++)
-      s[c] = kp == 0 ? dot2_start(pr[kp][c], g[kp], 0) : __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, pr[kp][c]), gp, s[c], false);
-  }
-  const s16x2 zero = { 0, 0 }, top = { (short)((1 << bd) - 1), (short)((1 << bd) - 1) };
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const s16x2 v = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm((uint32_t)s[2 * j + 1], (uint32_t)s[2 * j], 0x07060302u));
-    ow[j] = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_elementwise_max(v, zero), top));
-  }
-}
-
 __host__ __device__ constexpr int cmax3(int a, int b, int c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
+constexpr int kInterGroups = 32;                 // groups (blocks) per workgroup of k_inter_pipe
+
+// ONE LDS region per group, reused by the phases of a block (each ends with a group sync before the next one writes):
+//   luma search     window (YW x YWS samples) | intermediate (16 x 8 int16)
+//   luma residual   transpose buffer (8 x 12 int32) over the dead window / intermediate
+//   chroma          two windows (CWR x CWS samples) | intermediates (2 x (11 x 4 + 4) int16); then the two transpose buffers
+//                   (2 x 32 int32) over the dead windows
+// Separate arrays cost 66 KB per workgroup at 10 bits = 2 waves per SIMD; the shared region is 29 KB (912 bytes per block: the luma
+// phase sets it since the chroma windows hold 7 rows instead of 12) = the 5 waves per SIMD the VGPRs allow.
+template <typename ES> struct InterRegion {
+  static constexpr int YW = 16, YWS = 20;        // luma window 16 x 16 (integer vector -4 .. +11); rows are whole dwords
+  static constexpr int CW = 12, CWS = 16;        // chroma window columns: chroma integer position -4 .. +7; rows are whole dwords
+  static constexpr int CWR0 = 3, CWR = 7;        // ... of which the 4-tap family reads rows 3 .. 9 only: those are stored
+  static constexpr int YWIN_BYTES = YW * YWS * (int)sizeof(ES), CWIN_BYTES = 2 * CWR * CWS * (int)sizeof(ES);
+  static constexpr int IMY_BYTES = 16 * 8 * 2, IMC_BYTES = 2 * (11 * 4 + 4) * 2, TY_BYTES = 8 * 12 * 4, TC_BYTES = 2 * 32 * 4;
+  static constexpr int REG_RAW = cmax3(YWIN_BYTES + IMY_BYTES, CWIN_BYTES + IMC_BYTES, TY_BYTES > TC_BYTES ? TY_BYTES : TC_BYTES);
+  // per-group stride = 16 bytes past a multiple of 128: the groups of a wave run in lockstep at equal offsets and so start 4 banks apart
+  static constexpr int REG_BYTES = ((REG_RAW + 127) / 128) * 128 + 16;
+  static_assert(YWIN_BYTES % 16 == 0 && CWIN_BYTES % 16 == 0, "intermediates and transpose buffers need 16-byte alignment");
+  unsigned char *base;                           // of this group's region: 16-byte aligned, which the compiler is told at every use
+  __device__ __forceinline__ unsigned char *at(int off) const { return static_cast<unsigned char *>(__builtin_assume_aligned(base, 16)) + off; }
+  __device__ __forceinline__ ES *luma_win() const { return reinterpret_cast<ES *>(at(0)); }
+  __device__ __forceinline__ int16_t *luma_im() const { return reinterpret_cast<int16_t *>(at(YWIN_BYTES)); }
+  __device__ __forceinline__ int32_t *luma_T() const { return reinterpret_cast<int32_t *>(at(0)); }
+  // window of chroma plane pl (0 U, 1 V): row r at chroma_win(pl) + r * CWS, rows CWR0 .. CWR0 + CWR - 1 exist
+  __device__ __forceinline__ ES *chroma_win(int pl) const { return reinterpret_cast<ES *>(at(0)) + pl * CWR * CWS - CWR0 * CWS; }
+  __device__ __forceinline__ int16_t *chroma_im(int pl) const { return reinterpret_cast<int16_t *>(at(CWIN_BYTES)) + pl * (11 * 4 + 4); }
+  __device__ __forceinline__ int32_t *chroma_T(int pl) const { return reinterpret_cast<int32_t *>(at(0)) + pl * 32; }
+};
+
+// What the phases of one block share.  The chroma planes are not here: lanes 0-3 of a group work on U and 4-7 on V, so their pointers
+// are per lane and phase 7 makes them — held from the start they would be six registers through the whole search.
+template <typename Pix> struct InterBlock {
+  int f, blk, x, y, lane;                        // frame, block of the frame in raster order, its luma origin, lane of the block's 8
+  const Pix *src_y, *ref_y;                      // luma planes of frame f
+  Pix *rec_y;
+  InterRegion<Pix> reg;
+  // the block among the blocks of all frames: where its vector and its skip flag are
+  __device__ __forceinline__ bool present(const InterLaunch &L) const { return blk < (L.w / 8) * (L.h / 8); }
+  __device__ __forceinline__ size_t index(const InterLaunch &L) const { return (size_t)f * (L.w / 8) * (L.h / 8) + blk; }
+};
+
+// rows are compared as packed pairs (v_sad_u16: two samples per instruction, both bit depths) and the running best
+// prediction is kept packed: four selects per candidate; it is unpacked once after the search
+__device__ __forceinline__ void pack_pairs(const int *o, uint32_t *w) {
+#pragma unroll
+  for (int j = 0; j < 4; j++) w[j] = (uint32_t)o[2 * j] | ((uint32_t)o[2 * j + 1] << 16);
+}
+__device__ __forceinline__ int block_sad(const uint32_t *sp, const uint32_t *w) {
+  uint32_t v = 0;
+#pragma unroll
+  for (int j = 0; j < 4; j++) v = __builtin_amdgcn_sad_u16(sp[j], w[j], v);
+  return group_sum<8>((int)v);
+}
+// A 3x3 refinement round picks the minimum of (SAD, rank): candidate k = iy * 3 + ix has rank k + 1, except the centre (k = 4), which
+// has rank 0 and so keeps ties — the oracle's raster-order visit with strict improvement.  round_winner: the winning key's offset
+// from the centre, each of -1, 0, 1 times `step`.
+__device__ __forceinline__ unsigned round_key(int sad, int k) { return ((unsigned)sad << 4) | (unsigned)(k == 4 ? 0 : k + 1); }
+__device__ __forceinline__ void round_winner(unsigned key, int step, int &dx, int &dy) {
+  const int rk = (int)(key & 15u), kk = rk - 1, wy = (kk * 11) >> 5, wx = kk - 3 * wy;   // kk / 3 for kk in 0..8
+  dx = rk ? (wx - 1) * step : 0;
+  dy = rk ? (wy - 1) * step : 0;
+}
+
+// Phase 1, the block of this group.  No LDS, no memory access but the kernel's arguments; the kernel leaves right after it when
+// B.present(L) is false (the groups past the last block in a frame's last workgroup).  The context is filled whole before that test:
+// filled on one path only, its members reach the phases merged with "undefined" and the compiler forgets the region's alignment
+// (64-bit LDS accesses of the window became pairs of 32-bit ones, 110 instructions more).
+// workgroups in XCD-aware order: vertically adjacent block rows (their windows overlap by 8 of 16 rows) share an L2
+// frame = a whole number of workgroups (launch_inter_pipe): the frame index is a 32-bit division of the workgroup id — scalar
+// code — and the block row a reciprocal multiplication with a one-step correction.  (As blk_all / (bw * bh) in 64 bits and two
+// more integer divisions per lane this line was 117 vector instructions, 5 % of the kernel.)
+template <typename Pix> __device__ __forceinline__ void inter_block_of_group(const InterLaunch &L, unsigned char *regions, InterBlock<Pix> &B) {
+  const int grp = threadIdx.x >> 3, bw = L.w / 8, bh = L.h / 8;
+  const unsigned wpf = (unsigned)(bw * bh + kInterGroups - 1) / kInterGroups, wg = xcd_swizzle(blockIdx.x, gridDim.x);
+  B.lane = threadIdx.x & 7;
+  B.f = (int)(wg / wpf); B.blk = (int)(wg - (unsigned)B.f * wpf) * kInterGroups + grp;
+  int by = (int)((float)B.blk * __builtin_amdgcn_rcpf((float)bw)), bx = B.blk - by * bw;       // blk < 2^22: the estimate is within 1
+  if (bx < 0) { by--; bx += bw; } else if (bx >= bw) { by++; bx -= bw; }
+  B.x = bx * 8; B.y = by * 8;
+  B.reg.base = regions + grp * InterRegion<Pix>::REG_BYTES;
+  B.src_y = reinterpret_cast<const Pix *>(L.src[0]) + (size_t)B.f * L.h * L.stride_y;
+  B.ref_y = reinterpret_cast<const Pix *>(ref_plane(L, B.f, 0)) + (size_t)B.f * L.h * L.stride_y;
+  B.rec_y = reinterpret_cast<Pix *>(L.rec[0]) + (size_t)B.f * L.h * L.stride_y;
+}
+
+// Phase 2, the luma window: samples (x + imx - 4 .. +11, y + imy - 4 .. +11) around the integer vector (imx, imy) from k_me_int
+// (multiples of 8), clamped into the plane; and the block's source row as samples s[] and as pairs sp[].
+// Enters with the region free; leaves with the window written and synced.
+template <typename Pix>
+__device__ __forceinline__ void inter_stage_luma(const InterLaunch &L, const InterBlock<Pix> &B, int &imx, int &imy, int *s, uint32_t *sp) {
+  using Reg = InterRegion<Pix>;
+  const int16_t *mvs = L.mvs + B.index(L) * 2;
+  imx = mvs[0] >> 3; imy = mvs[1] >> 3;
+#pragma unroll
+  for (int it = 0; it < 2; it++) {
+    const int r = B.lane + it * 8;
+    const int fy = min(max(B.y + imy - 4 + r, 0), L.h - 1);
+    stage_window_row<Reg::YW, Pix>(B.ref_y + row_off(fy, L.stride_y), B.x + imx - 4, L.w, B.reg.luma_win() + r * Reg::YWS);
+  }
+  load_row<8>(B.src_y + row_off(B.y + B.lane, L.stride_y) + B.x, s);
+  AV1MI_GROUP_SYNC();
+  pack_pairs(s, sp);
+}
+
+// Phase 3, candidate 0, the integer vector itself: returns its SAD.  Window synced on entry, only read.
+// (phase 0 of the 8-tap filter is the identity: taps 0 0 0 128 0 0 0 0, and (128 p + 4) >> 3 = 16 p, (128 * 16 p + 1024) >> 11
+// = p exactly — so the integer position is a copy of the window's centre)
+template <typename Pix> __device__ __forceinline__ int inter_score_integer(const InterBlock<Pix> &B, const uint32_t *sp) {
+  int bp[8];
+  uint32_t w[4];
+  row_samples<8, Pix>(B.reg.luma_win() + (B.lane + 4) * InterRegion<Pix>::YWS + 4, 0, bp);
+  pack_pairs(bp, w);
+  return block_sad(sp, w);
+}
+
+// Phase 4, the half-sample round, scored with the BILINEAR filter (encoder policy, mirrored by the oracle; libaom's USE_2_TAPS search):
+// at phase 8 its taps are (64, 64), and through the spec's two rounding stages ((s + 4) >> 3, then (s + 1024) >> 11) the
+// prediction is EXACTLY the rounded average of the 2 (one direction) or 4 (both) samples around the position.  So this round
+// needs no filter passes at all: three window rows of ten samples per lane and adds.  Which half-sample neighbourhood a
+// block lies in is decided as well this way as with the 8-tap filter (coded bytes and PSNR unchanged); the
+// quarter-sample round scores every position, its centre included, with the real filter.
+// centre_sad: phase 3's; (bfx, bfy): the winner in 1/8 samples relative to the integer vector.  Window synced on entry, only read.
+template <typename Pix>
+__device__ __forceinline__ void inter_half_round(const InterBlock<Pix> &B, const uint32_t *sp, int centre_sad, int &bfx, int &bfy) {
+  // packed 16-bit arithmetic (v_pk_add_u16 / v_pk_lshrrev_b16: two samples per lane-op; sums of four 10-bit samples fit):
+  // P[j][k][i] = the sample pair at columns 3 + k + 2 i, 4 + k + 2 i of window row lane + 3 + j (block row -1 .. +1, columns
+  // -1 + k ..), straight from the window's dwords — the sample-by-sample form unpacked 30 samples, averaged in 32 bits and packed
+  // every candidate again for the SAD
+  typedef unsigned short v2u __attribute__((ext_vector_type(2)));
+  v2u P[3][3][4];
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const uint32_t *r32 = reinterpret_cast<const uint32_t *>(B.reg.luma_win() + (B.lane + 3 + j) * InterRegion<Pix>::YWS);
+    uint32_t w[3][4];
+    if constexpr (sizeof(Pix) == 2) {
+      uint32_t D[6];                               // columns 2 .. 13
+#pragma unroll
+      for (int i = 0; i < 6; i++) D[i] = r32[1 + i];
+#pragma unroll
+      for (int i = 0; i < 4; i++) { w[0][i] = __builtin_amdgcn_alignbit(D[i + 1], D[i], 16); w[1][i] = D[i + 1]; w[2][i] = __builtin_amdgcn_alignbit(D[i + 2], D[i + 1], 16); }
+    } else {
+      const uint32_t B0 = r32[0], B1 = r32[1], B2 = r32[2], B3 = r32[3];     // columns 0 .. 15, one byte each
+      w[0][0] = __builtin_amdgcn_perm(B1, B0, 0x0c040c03u); w[0][1] = __builtin_amdgcn_perm(0u, B1, 0x0c020c01u);
+      w[0][2] = __builtin_amdgcn_perm(B2, B1, 0x0c040c03u); w[0][3] = __builtin_amdgcn_perm(0u, B2, 0x0c020c01u);
+      w[1][0] = __builtin_amdgcn_perm(0u, B1, 0x0c010c00u); w[1][1] = __builtin_amdgcn_perm(0u, B1, 0x0c030c02u);
+      w[1][2] = __builtin_amdgcn_perm(0u, B2, 0x0c010c00u); w[1][3] = __builtin_amdgcn_perm(0u, B2, 0x0c030c02u);
+      w[2][0] = w[0][1]; w[2][1] = w[0][2]; w[2][2] = w[0][3]; w[2][3] = __builtin_amdgcn_perm(B3, B2, 0x0c040c03u);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+      for (int i = 0; i < 4; i++) P[j][k][i] = __builtin_bit_cast(v2u, w[k][i]);
+  }
+  v2u H[3][2][4];                                // horizontal pair sums: columns (k, k + 1) of row j
+#pragma unroll
+  for (int j = 0; j < 3; j++)
+#pragma unroll
+    for (int k = 0; k < 2; k++)
+#pragma unroll
+      for (int i = 0; i < 4; i++) H[j][k][i] = P[j][k][i] + P[j][k + 1][i];
+  const v2u one = { 1, 1 }, two = { 2, 2 };
+  unsigned bestkey = round_key(centre_sad, 4);
+#pragma unroll
+  for (int iy = 0; iy < 3; iy++) {
+#pragma unroll
+    for (int ix = 0; ix < 3; ix++) {
+      if (ix == 1 && iy == 1) continue;
+      const int r0 = iy == 0 ? 0 : 1, r1 = iy == 2 ? 2 : 1, k = ix == 0 ? 0 : 1;   // the 1, 2 or 4 samples averaged
+      uint32_t ow[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        v2u o;
+        if (iy == 1) o = (H[1][k][i] + one) >> one;
+        else if (ix == 1) o = (P[r0][1][i] + P[r1][1][i] + one) >> one;
+        else o = (H[r0][k][i] + H[r1][k][i] + two) >> two;
+        ow[i] = __builtin_bit_cast(uint32_t, o);
+      }
+      bestkey = min(bestkey, round_key(block_sad(sp, ow), iy * 3 + ix));
+    }
+  }
+  round_winner(bestkey, 4, bfx, bfy);
+}
+
+// Phase 5, the quarter-sample round with the real 8-tap filter: the centre (bfx, bfy) (re-scored: rank 0) and its 8 neighbours, column
+// by column, one horizontal pass per column.  Every position goes through the same (key, prediction) update, so the order of
+// evaluation does not matter.  (bfx, bfy) becomes the winner and bpp its prediction row, packed.  filt: the kernel's tables in LDS.
+// Enters with the window synced and the intermediate free; a column is pass, sync, reads, sync, so it leaves the region free.
+template <typename Pix>
+__device__ __forceinline__ void inter_quarter_round(const InterBlock<Pix> &B, const int16_t (*filt)[16][8], const uint32_t *sp, int &bfx, int &bfy,
+                                                    uint32_t *bpp) {
+  constexpr int step = 2, bd = sizeof(Pix) == 1 ? 8 : 10;
+  const int cx = bfx, cy = bfy;
+  int16_t *im = B.reg.luma_im();
+  unsigned bestkey = 0xFFFFFFFFu;
+#pragma unroll 1
+  for (int ix = 0; ix < 3; ix++) {
+    const int fx = cx + (ix - 1) * step;
+    mc_h16<Pix>(B.reg.luma_win(), InterRegion<Pix>::YWS, im, B.lane, fx * 2, sizeof(Pix) == 2 ? filt[2] : filt[0]);
+    AV1MI_GROUP_SYNC();
+    uint32_t pr[4][8];
+    mc_rows7(im, B.lane, pr);
+#pragma unroll
+    for (int iy = 0; iy < 3; iy++) {     // unrolled: the three vertical candidates of a column overlap
+      const int fy = cy + (iy - 1) * step;
+      uint32_t ow[4];
+      mc_v7(pr, fy * 2, filt[2], bd, ow);
+      const unsigned key = round_key(block_sad(sp, ow), iy * 3 + ix);
+      const bool better = key < bestkey;
+      bestkey = min(bestkey, key);
+#pragma unroll
+      for (int j = 0; j < 4; j++) bpp[j] = better ? ow[j] : bpp[j];
+    }
+    AV1MI_GROUP_SYNC();
+  }
+  round_winner(bestkey, step, bfx, bfy);
+  bfx += cx; bfy += cy;
+}
+
+// Phase 6, luma: the final vector (1/8 luma samples) written, the residual of source row s[] against prediction row bpp coded
+// (levels, reconstruction stored).  Returns non-zero when the row holds a level.  The transpose buffer lies over window and
+// intermediate: enters with the region free, leaves it read but NOT synced.
+template <typename Pix>
+__device__ __forceinline__ int inter_code_luma(const InterLaunch &L, const InterBlock<Pix> &B, const int *s, const uint32_t *bpp, int mvx, int mvy) {
+  int bp[8], rec[8];
+#pragma unroll
+  for (int j = 0; j < 4; j++) { bp[2 * j] = bpp[j] & 0xffff; bp[2 * j + 1] = bpp[j] >> 16; }
+  int16_t *mvs = L.mvs + B.index(L) * 2;
+  if (B.lane == 0) { mvs[0] = (int16_t)mvx; mvs[1] = (int16_t)mvy; }
+  const int nz = code_residual<8, Pix, false, kAcRoundInter>(B.reg.luma_T(), B.lane, s, bp, L.dc_q, L.ac_q, L.dc_quant, L.ac_quant,
+                                                             L.lev[0] + (size_t)B.f * L.w * L.h + (size_t)B.blk * 64 + B.lane * 8, rec);
+  store_row<8>(B.rec_y + row_off(B.y + B.lane, L.stride_y) + B.x, rec);
+  return nz;
+}
+
+// Phase 7, chroma: lanes 0-3 code the U block, lanes 4-7 the V block (4x4 each, 4-tap regular filter rows `filt4`): two 7-row windows
+// staged, mc_row, residual, store.  The vector in 1/16 chroma samples is the luma vector in 1/8 luma samples.
+// Enters with the luma transpose buffer read but not synced (its first act is that sync); leaves the chroma buffers read.
+template <typename Pix>
+__device__ __forceinline__ int inter_code_chroma(const InterLaunch &L, const InterBlock<Pix> &B, const int16_t (*filt4)[8], int mvx, int mvy) {
+  using Reg = InterRegion<Pix>;
+  constexpr int bd = sizeof(Pix) == 1 ? 8 : 10;
+  const int pl = B.lane >> 2, cl = B.lane & 3;
+  const int cw = L.w / 2, chh = L.h / 2, cx0 = B.x / 2, cy0 = B.y / 2;
+  const Pix *src_c = reinterpret_cast<const Pix *>(L.src[1 + pl]) + (size_t)B.f * chh * L.stride_uv;
+  const Pix *ref_c = reinterpret_cast<const Pix *>(ref_plane(L, B.f, 1 + pl)) + (size_t)B.f * chh * L.stride_uv;
+  Pix *rec_c = reinterpret_cast<Pix *>(L.rec[1 + pl]) + (size_t)B.f * chh * L.stride_uv;
+  const int cix = mvx >> 4, ciy = mvy >> 4;         // integer chroma displacement (floor)
+  Pix *wc = B.reg.chroma_win(pl);
+  AV1MI_GROUP_SYNC();                               // the luma transpose buffer has been read: the region is free
+  // the 4-tap family reads window rows 3 .. 9 only (mc_row<4, ES, 2, 6>: taps 2 .. 5 of rows -1 .. +5 around the block)
+#pragma unroll
+  for (int it = 0; it < 2; it++) {
+    const int r = 3 + cl + it * 4;
+    if (r <= 9) {
+      const int fy = min(max(cy0 + ciy - 4 + r, 0), chh - 1);
+      stage_window_row<Reg::CW, Pix>(ref_c + row_off(fy, L.stride_uv), cx0 + cix - 4, cw, wc + r * Reg::CWS);
+    }
+  }
+  int sc[4], pc[4], rc[4];
+  load_row<4>(src_c + row_off(cy0 + cl, L.stride_uv) + cx0, sc);
+  AV1MI_GROUP_SYNC();
+  mc_row<4, Pix, 2, 6>(wc, Reg::CWS, B.reg.chroma_im(pl), cl, mvx & 15, mvy & 15, filt4, bd, pc);
+  const int nz = code_residual<4, Pix, false, kAcRoundInter>(B.reg.chroma_T(pl), cl, sc, pc, L.dc_q, L.ac_q, L.dc_quant, L.ac_quant,
+                                                             L.lev[1 + pl] + (size_t)B.f * cw * chh + (size_t)B.blk * 16 + cl * 4, rc);
+  store_row<4>(rec_c + row_off(cy0 + cl, L.stride_uv) + cx0, rc);
+  return nz;
+}
 
 template <typename Pix>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_inter_pipe(InterLaunch L) {
-  using ES = Pix;
-  constexpr int bd = sizeof(Pix) == 1 ? 8 : 10;
-  constexpr int GPW = 32;                        // groups (blocks) per workgroup
-  constexpr int YW = 16, YWS = 20;               // luma window 16 x 16 (integer vector -4 .. +11); rows are whole dwords
-  constexpr int CW = 12, CWS = 16;               // chroma window columns: chroma integer position -4 .. +7; rows are whole dwords
-  constexpr int CWR0 = 3, CWR = 7;               // ... of which the 4-tap family reads rows 3 .. 9 only: those are stored
-  // ONE LDS region per group, reused by the phases of a block (each ends with a group sync before the next one writes):
-  //   luma search     window (YW x YWS samples) | intermediate (16 x 8 int16)
-  //   luma residual   transpose buffer (8 x 12 int32) over the dead window / intermediate
-  //   chroma          two windows (CWR x CWS samples) | intermediates (2 x (11 x 4 + 4) int16); then the two transpose buffers
-  //                   (2 x 32 int32) over the dead windows
-  // Separate arrays cost 66 KB per workgroup at 10 bits = 2 waves per SIMD; the shared region is 29 KB (912 bytes per block: the luma
-  // phase sets it since the chroma windows hold 7 rows instead of 12) = the 5 waves per SIMD the VGPRs allow.
-  constexpr int YWIN_BYTES = YW * YWS * (int)sizeof(ES), CWIN_BYTES = 2 * CWR * CWS * (int)sizeof(ES);
-  constexpr int IMY_BYTES = 16 * 8 * 2, IMC_BYTES = 2 * (11 * 4 + 4) * 2, TY_BYTES = 8 * 12 * 4, TC_BYTES = 2 * 32 * 4;
-  constexpr int REG_RAW = cmax3(YWIN_BYTES + IMY_BYTES, CWIN_BYTES + IMC_BYTES, TY_BYTES > TC_BYTES ? TY_BYTES : TC_BYTES);
-  // per-group stride = 16 bytes past a multiple of 128: the groups of a wave run in lockstep at equal offsets and so start 4 banks apart
-  constexpr int REG_BYTES = ((REG_RAW + 127) / 128) * 128 + 16;
-  static_assert(YWIN_BYTES % 16 == 0 && CWIN_BYTES % 16 == 0, "intermediates and transpose buffers need 16-byte alignment");
-  __shared__ __attribute__((aligned(16))) unsigned char regb[GPW * REG_BYTES];
+  __shared__ __attribute__((aligned(16))) unsigned char regions[kInterGroups * InterRegion<Pix>::REG_BYTES];
   // the two filter families this policy uses, copied next to the windows: a lane's taps depend on its block's vector, and a
   // per-lane indexed read of __constant__ memory is a vector memory load (hundreds of cycles) in front of every candidate
   __shared__ __attribute__((aligned(16))) int16_t s_filt[3][16][8];   // regular 8-tap, regular 4-tap, regular 8-tap x 32 (mc_h16 at 10 bits, mc_v7)
@@ -417,201 +460,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
     s_filt[2][t >> 3][t & 7] = (int16_t)(kSubpel[0][t >> 3][t & 7] * 32);
   }
   __syncthreads();
-
-  const int grp = threadIdx.x >> 3, lane = threadIdx.x & 7;
-  const int bw = L.w / 8, bh = L.h / 8;
-  // workgroups in XCD-aware order: vertically adjacent block rows (their windows overlap by 8 of 16 rows) share an L2
-  // frame = a whole number of workgroups (launch_inter_pipe): the frame index is a 32-bit division of the workgroup id — scalar
-  // code — and the block row a reciprocal multiplication with a one-step correction.  (As blk_all / (bw * bh) in 64 bits and two
-  // more integer divisions per lane this line was 117 vector instructions, 5 % of the kernel.)
-  const unsigned wpf = (unsigned)(bw * bh + GPW - 1) / GPW, wg = xcd_swizzle(blockIdx.x, gridDim.x);
-  const int f = (int)(wg / wpf), blk = (int)(wg - (unsigned)f * wpf) * GPW + grp;
-  if (blk >= bw * bh) return;
-  int by = (int)((float)blk * __builtin_amdgcn_rcpf((float)bw)), bx = blk - by * bw;       // blk < 2^22: the estimate is within 1
-  if (bx < 0) { by--; bx += bw; } else if (bx >= bw) { by++; bx -= bw; }
-  const int x = bx * 8, y = by * 8;
-  unsigned char *reg = regb + grp * REG_BYTES;
-  ES *wy = reinterpret_cast<ES *>(reg);
-  int16_t *im = reinterpret_cast<int16_t *>(reg + YWIN_BYTES);
-  int32_t *T = reinterpret_cast<int32_t *>(reg);
-
-  const Pix *src_y = reinterpret_cast<const Pix *>(L.src[0]) + (size_t)f * L.h * L.stride_y;
-  const Pix *ref_y = reinterpret_cast<const Pix *>(ref_plane(L, f, 0)) + (size_t)f * L.h * L.stride_y;
-  Pix *rec_y = reinterpret_cast<Pix *>(L.rec[0]) + (size_t)f * L.h * L.stride_y;
-  int16_t *mvs = L.mvs + ((size_t)f * bw * bh + blk) * 2;
-  const int imx = mvs[0] >> 3, imy = mvs[1] >> 3;   // integer vector from k_me_int (multiples of 8)
-
-  // luma window: samples (x + imx - 4 .. +11, y + imy - 4 .. +11), clamped into the plane
-#pragma unroll
-  for (int it = 0; it < 2; it++) {
-    const int r = lane + it * 8;
-    const int fy = min(max(y + imy - 4 + r, 0), L.h - 1);
-    const Pix *row = ref_y + row_off(fy, L.stride_y);
-    stage_window_row<YW, Pix>(row, x + imx - 4, L.w, wy + r * YWS);
-  }
-  int s[8], bp[8];
-  load_row<8>(src_y + row_off(y + lane, L.stride_y) + x, s);
-  AV1MI_GROUP_SYNC();
-  // rows are compared as packed pairs (v_sad_u16: two samples per instruction, both bit depths) and the running best
-  // prediction is kept packed: four selects per candidate; it is unpacked once after the search
+  InterBlock<Pix> B;
+  inter_block_of_group(L, regions, B);                               // 1
+  if (!B.present(L)) return;
+  int s[8], imx, imy, bfx, bfy;
   uint32_t sp[4], bpp[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) sp[j] = (uint32_t)s[2 * j] | ((uint32_t)s[2 * j + 1] << 16);
-  auto pack4 = [&](const int *o, uint32_t *w) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) w[j] = (uint32_t)o[2 * j] | ((uint32_t)o[2 * j + 1] << 16);
-  };
-  auto sad_of = [&](const uint32_t *w) {
-    uint32_t v = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) v = __builtin_amdgcn_sad_u16(sp[j], w[j], v);
-    return group_sum<8>((int)v);
-  };
-  // candidate 0: the integer vector itself
-  // (phase 0 of the 8-tap filter is the identity: taps 0 0 0 128 0 0 0 0, and (128 p + 4) >> 3 = 16 p, (128 * 16 p + 1024) >> 11
-  // = p exactly — so the integer position is a copy of the window's centre)
-  row_samples<8, ES>(wy + (lane + 4) * YWS + 4, 0, bp);
-  pack4(bp, bpp);
-  int best = sad_of(bpp), bfx = 0, bfy = 0;     // fractional part in 1/8 samples relative to the integer vector
-  // ---- half-sample round, scored with the BILINEAR filter (encoder policy, mirrored by the oracle; libaom's USE_2_TAPS search):
-  // at phase 8 its taps are (64, 64), and through the spec's two rounding stages ((s + 4) >> 3, then (s + 1024) >> 11) the
-  // prediction is EXACTLY the rounded average of the 2 (one direction) or 4 (both) samples around the position.  So this round
-  // needs no filter passes at all: three window rows of ten samples per lane and adds.  Which half-sample neighbourhood a
-  // block lies in is decided as well this way as with the 8-tap filter (coded bytes and PSNR unchanged); the
-  // quarter-sample round below scores every position, its centre included, with the real filter.
-  {
-    // packed 16-bit arithmetic (v_pk_add_u16 / v_pk_lshrrev_b16: two samples per lane-op; sums of four 10-bit samples fit):
-    // P[j][k][i] = the sample pair at columns 3 + k + 2 i, 4 + k + 2 i of window row lane + 3 + j (block row -1 .. +1, columns
-    // -1 + k ..), straight from the window's dwords — the sample-by-sample form unpacked 30 samples, averaged in 32 bits and packed
-    // every candidate again for the SAD
-    typedef unsigned short v2u __attribute__((ext_vector_type(2)));
-    v2u P[3][3][4];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      const uint32_t *r32 = reinterpret_cast<const uint32_t *>(wy + (lane + 3 + j) * YWS);
-      uint32_t w[3][4];
-      if constexpr (sizeof(ES) == 2) {
-        uint32_t D[6];                               // columns 2 .. 13
-#pragma unroll
-        for (int i = 0; i < 6; i++) D[i] = r32[1 + i];
-#pragma unroll
-        for (int i = 0; i < 4; i++) { w[0][i] = __builtin_amdgcn_alignbit(D[i + 1], D[i], 16); w[1][i] = D[i + 1]; w[2][i] = __builtin_amdgcn_alignbit(D[i + 2], D[i + 1], 16); }
-      } else {
-        const uint32_t B0 = r32[0], B1 = r32[1], B2 = r32[2], B3 = r32[3];     // columns 0 .. 15, one byte each
-        w[0][0] = __builtin_amdgcn_perm(B1, B0, 0x0c040c03u); w[0][1] = __builtin_amdgcn_perm(0u, B1, 0x0c020c01u);
-        w[0][2] = __builtin_amdgcn_perm(B2, B1, 0x0c040c03u); w[0][3] = __builtin_amdgcn_perm(0u, B2, 0x0c020c01u);
-        w[1][0] = __builtin_amdgcn_perm(0u, B1, 0x0c010c00u); w[1][1] = __builtin_amdgcn_perm(0u, B1, 0x0c030c02u);
-        w[1][2] = __builtin_amdgcn_perm(0u, B2, 0x0c010c00u); w[1][3] = __builtin_amdgcn_perm(0u, B2, 0x0c030c02u);
-        w[2][0] = w[0][1]; w[2][1] = w[0][2]; w[2][2] = w[0][3]; w[2][3] = __builtin_amdgcn_perm(B3, B2, 0x0c040c03u);
-      }
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int i = 0; i < 4; i++) P[j][k][i] = __builtin_bit_cast(v2u, w[k][i]);
-    }
-    v2u H[3][2][4];                                // horizontal pair sums: columns (k, k + 1) of row j
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-#pragma unroll
-      for (int k = 0; k < 2; k++)
-#pragma unroll
-        for (int i = 0; i < 4; i++) H[j][k][i] = P[j][k][i] + P[j][k + 1][i];
-    const v2u one = { 1, 1 }, two = { 2, 2 };
-    unsigned bestkey = (unsigned)best << 4;        // (SAD, rank): rank 0 = the centre (keeps ties), k + 1 = the neighbour visited k-th
-#pragma unroll
-    for (int iy = 0; iy < 3; iy++) {
-#pragma unroll
-      for (int ix = 0; ix < 3; ix++) {
-        if (ix == 1 && iy == 1) continue;
-        const int r0 = iy == 0 ? 0 : 1, r1 = iy == 2 ? 2 : 1, k = ix == 0 ? 0 : 1;   // the 1, 2 or 4 samples averaged
-        uint32_t ow[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          v2u o;
-          if (iy == 1) o = (H[1][k][i] + one) >> one;
-          else if (ix == 1) o = (P[r0][1][i] + P[r1][1][i] + one) >> one;
-          else o = (H[r0][k][i] + H[r1][k][i] + two) >> two;
-          ow[i] = __builtin_bit_cast(uint32_t, o);
-        }
-        bestkey = min(bestkey, ((unsigned)sad_of(ow) << 4) | (unsigned)(iy * 3 + ix + 1));
-      }
-    }
-    const int rk = (int)(bestkey & 15u), kk = rk - 1, wy_ = (kk * 11) >> 5, wx_ = kk - 3 * wy_;   // kk / 3 for kk in 0..8
-    bfx = rk ? (wx_ - 1) * 4 : 0;
-    bfy = rk ? (wy_ - 1) * 4 : 0;
-  }
-  // ---- quarter-sample round with the real 8-tap filter: the centre (re-scored: rank 0) and its 8 neighbours, column by column,
-  // one horizontal pass per column.  The oracle visits the neighbours in raster order with strict improvement, i.e. the winner
-  // is the minimum of (SAD, rank) and the centre keeps ties; every position goes through the same (key, prediction) update, so
-  // the order of evaluation does not matter.
-  {
-    const int step = 2, cx = bfx, cy = bfy;
-    unsigned bestkey = 0xFFFFFFFFu;
-#pragma unroll 1
-    for (int ix = 0; ix < 3; ix++) {
-      const int fx = cx + (ix - 1) * step;
-      mc_h16<ES>(wy, YWS, im, lane, fx * 2, sizeof(ES) == 2 ? s_filt[2] : s_filt[0]);
-      AV1MI_GROUP_SYNC();
-      uint32_t pr[4][8];
-      mc_rows7(im, lane, pr);
-#pragma unroll
-      for (int iy = 0; iy < 3; iy++) {     // unrolled: the three vertical candidates of a column overlap
-        const int fy = cy + (iy - 1) * step, k = iy * 3 + ix;
-        uint32_t ow[4];
-        mc_v7(pr, fy * 2, s_filt[2], bd, ow);
-        const unsigned key = ((unsigned)sad_of(ow) << 4) | (unsigned)(k == 4 ? 0 : k + 1);
-        const bool better = key < bestkey;
-        bestkey = min(bestkey, key);
-#pragma unroll
-        for (int j = 0; j < 4; j++) bpp[j] = better ? ow[j] : bpp[j];
-      }
-      AV1MI_GROUP_SYNC();
-    }
-    const int rk = (int)(bestkey & 15u), kk = rk - 1, wy_ = (kk * 11) >> 5, wx_ = kk - 3 * wy_;
-    best = (int)(bestkey >> 4);
-    bfx = rk ? cx + (wx_ - 1) * step : cx;
-    bfy = rk ? cy + (wy_ - 1) * step : cy;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; j++) { bp[2 * j] = bpp[j] & 0xffff; bp[2 * j + 1] = bpp[j] >> 16; }
-  const int mvx = imx * 8 + bfx, mvy = imy * 8 + bfy;   // final vector, 1/8 luma samples
-  if (lane == 0) { mvs[0] = (int16_t)mvx; mvs[1] = (int16_t)mvy; }
-  int rec[8];
-  int nz = code_residual<8, Pix, false, kAcRoundInter>(T, lane, s, bp, L.dc_q, L.ac_q, L.dc_quant, L.ac_quant, L.lev[0] + (size_t)f * L.w * L.h + (size_t)blk * 64 + lane * 8, rec);
-  store_row<8>(rec_y + row_off(y + lane, L.stride_y) + x, rec);
-
-  // chroma: lanes 0-3 code the U block, lanes 4-7 the V block (4x4 each, 4-tap regular filter rows)
-  {
-    const int pl = lane >> 2, cl = lane & 3;
-    const int cw = L.w / 2, chh = L.h / 2, cx0 = x / 2, cy0 = y / 2;
-    const Pix *src_c = reinterpret_cast<const Pix *>(L.src[1 + pl]) + (size_t)f * chh * L.stride_uv;
-    const Pix *ref_c = reinterpret_cast<const Pix *>(ref_plane(L, f, 1 + pl)) + (size_t)f * chh * L.stride_uv;
-    Pix *rec_c = reinterpret_cast<Pix *>(L.rec[1 + pl]) + (size_t)f * chh * L.stride_uv;
-    // the vector in 1/16 chroma samples is the luma vector in 1/8 luma samples
-    const int cix = mvx >> 4, ciy = mvy >> 4;         // integer chroma displacement (floor)
-    ES *wc = wy + pl * CWR * CWS - CWR0 * CWS;       // row r of the window at wc + r * CWS, rows CWR0 .. CWR0 + CWR - 1 exist
-    int16_t *imc = reinterpret_cast<int16_t *>(reg + CWIN_BYTES) + pl * (11 * 4 + 4);
-    AV1MI_GROUP_SYNC();                               // the luma transpose buffer has been read: the region is free
-    // the 4-tap family reads window rows 3 .. 9 only (mc_row<4, ES, 2, 6>: taps 2 .. 5 of rows -1 .. +5 around the block)
-#pragma unroll
-    for (int it = 0; it < 2; it++) {
-      const int r = 3 + cl + it * 4;
-      if (r <= 9) {
-        const int fy = min(max(cy0 + ciy - 4 + r, 0), chh - 1);
-        const Pix *row = ref_c + row_off(fy, L.stride_uv);
-        stage_window_row<CW, Pix>(row, cx0 + cix - 4, cw, wc + r * CWS);
-      }
-    }
-    int sc[4], pc[4], rc[4];
-    load_row<4>(src_c + row_off(cy0 + cl, L.stride_uv) + cx0, sc);
-    AV1MI_GROUP_SYNC();
-    mc_row<4, ES, 2, 6>(wc, CWS, imc, cl, mvx & 15, mvy & 15, s_filt[1], bd, pc);
-    nz |= code_residual<4, Pix, false, kAcRoundInter>(T + pl * 32, cl, sc, pc, L.dc_q, L.ac_q, L.dc_quant, L.ac_quant,
-                                L.lev[1 + pl] + (size_t)f * cw * chh + (size_t)blk * 16 + cl * 4, rc);
-    store_row<4>(rec_c + row_off(cy0 + cl, L.stride_uv) + cx0, rc);
-  }
+  inter_stage_luma(L, B, imx, imy, s, sp);                           // 2
+  const int sad0 = inter_score_integer(B, sp);                       // 3
+  inter_half_round(B, sp, sad0, bfx, bfy);                           // 4
+  inter_quarter_round(B, s_filt, sp, bfx, bfy, bpp);                 // 5
+  const int mvx = imx * 8 + bfx, mvy = imy * 8 + bfy;                // final vector, 1/8 luma samples
+  int nz = inter_code_luma(L, B, s, bpp, mvx, mvy);                  // 6
+  nz |= inter_code_chroma(L, B, s_filt[1], mvx, mvy);                // 7
   nz = group_or<8>(nz);
-  if (lane == 0) L.skip[(size_t)f * bw * bh + blk] = nz == 0;
+  if (B.lane == 0) L.skip[B.index(L)] = nz == 0;
 }
 
 // integer search: writes L.mvs (whole-sample vectors), which k_inter_pipe then refines

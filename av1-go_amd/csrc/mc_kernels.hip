@@ -8,9 +8,11 @@
 // is an 8-tap row with zero outer taps, so every block takes the same path.  Traffic: reference window read
 // ~ b*S*(1+7/BW)(1+7/BH) out of L2, prediction written b*S.
 //
+// The 8-bit horizontal pass, the packing of the intermediate and the row-pair interleave are subpel.hpp's, shared with k_inter_pipe.
+//
 // Restates AV1 spec §7.11.3.4 == libaom av1_highbd_convolve_2d_sr_c; nothing to cite in the
 // reference tree (internal/ffmpeg/transcode.go:120 names the external encoder only).
-#include "motion_common.hpp"
+#include "subpel.hpp"
 
 namespace av1mi {
 
@@ -73,21 +75,13 @@ __global__ __launch_bounds__(256) void k_mc(McLaunch L) {
       int sum[CH];
       if constexpr (sizeof(Pix) == 1) {
         const int D0 = c0 / 4;                                // c0 is a multiple of 4 for every BW (unrolled: a constant)
-        uint32_t a[4], bb[4];
+        uint32_t a[4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) { a[i] = (D0 + i < WD) ? wn[j * WD + D0 + i] : 0u; bb[i] = a[i] ^ 0x80808080u; }
-        const int F0 = (fx[0] & 255) | ((fx[1] & 255) << 8) | ((fx[2] & 255) << 16);
-        const int F1 = (fx[4] & 255) | ((fx[5] & 255) << 8) | ((fx[6] & 255) << 16) | ((fx[7] & 255) << 24);
-        const int acc0 = 4 + 128 * (128 - fx[3]);             // pays the bias back: sum over t != 3 of 128 f_t
-        uint32_t dd[CH + 4];
-#pragma unroll
-        for (int c = 0; c < CH + 4; c++) dd[c] = (c & 3) ? __builtin_amdgcn_alignbyte(bb[(c >> 2) + 1 < 4 ? (c >> 2) + 1 : 3], bb[c >> 2], c & 3) : bb[c >> 2];
-#pragma unroll
-        for (int c = 0; c < CH; c++) {
-          const int p3 = (int)((a[(c + 3) >> 2] >> (((c + 3) & 3) * 8)) & 255);
-          sum[c] = __builtin_amdgcn_sdot4(F0, (int)dd[c], __builtin_amdgcn_sdot4(F1, (int)dd[c + 4], acc0 + fx[3] * p3, false), false);
-        }
+        for (int i = 0; i < 4; i++) a[i] = (D0 + i < WD) ? wn[j * WD + D0 + i] : 0u;
+        fir8_u8<CH>(a, fx, sum);
       } else {
+        // 10-bit, this kernel's own: any filter family may come, so all eight taps count, four v_dot2_i32_i16 per sample
+        // (k_inter_pipe's mc_h16 only ever takes the regular family, six taps, and gets by with three)
         const int D0 = c0 / 2;
         uint32_t a[8];
 #pragma unroll
@@ -107,11 +101,7 @@ __global__ __launch_bounds__(256) void k_mc(McLaunch L) {
         }
       }
       uint32_t o[CH / 2];
-#pragma unroll
-      for (int c = 0; c < CH; c++) {
-        const uint32_t hh = (uint32_t)(sum[c] >> 3) & 0xffff;   // |value| < 2^15 for bd <= 10
-        o[c >> 1] = (c & 1) ? (o[c >> 1] | (hh << 16)) : hh;
-      }
+      pack_intermediate<CH>(sum, o);
       uint32_t *q = reinterpret_cast<uint32_t *>(im + j * IMS + c0);
 #pragma unroll
       for (int i = 0; i < CH / 2; i++) q[i] = o[i];
@@ -135,9 +125,10 @@ __global__ __launch_bounds__(256) void k_mc(McLaunch L) {
       const uint32_t *qb = reinterpret_cast<const uint32_t *>(im + (r + 2 * kp + 1) * IMS + c0);
 #pragma unroll
       for (int i = 0; i < CH / 2; i++) {
-        const uint32_t x = qa[i], y = qb[i];
-        sum[2 * i] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, __builtin_amdgcn_perm(y, x, 0x05040100u)), gp[kp], sum[2 * i], false);
-        sum[2 * i + 1] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, __builtin_amdgcn_perm(y, x, 0x07060302u)), gp[kp], sum[2 * i + 1], false);
+        uint32_t lo, hi;
+        row_pair(qa[i], qb[i], lo, hi);
+        sum[2 * i] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, lo), gp[kp], sum[2 * i], false);
+        sum[2 * i + 1] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, hi), gp[kp], sum[2 * i + 1], false);
       }
     }
     int o[CH];

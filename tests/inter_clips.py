@@ -115,6 +115,34 @@ def low_bits(w, h, bd=10, seed=4):
     return src, ref
 
 
+HALF_W, HALF_H, HALF_Q = 72, 40, 255      # half_sample_frames as the tests run them: 45 blocks a frame, the coarsest quantiser
+
+
+def transposed(clip):
+    """a clip of the transposed size with every plane transposed: what a generator does along x happens along y"""
+    return tuple(tuple(np.ascontiguousarray(a.T) for a in t) for t in clip)
+
+
+def half_sample_frames(w, h, bd):
+    """three frames whose best vectors are half-sample ones along x only, along y only and along both, on content that a coarse
+    quantiser leaves without a residual: checker_half along x, the same transposed, and checker_half both ways at half the
+    amplitude (at the full one the 8-tap overshoot is a residual that no quantiser drops)"""
+    both = tuple(tuple(a >> 1 for a in t) for t in checker_half(w, h, bd, True))
+    return [checker_half(w, h, bd, False), transposed(checker_half(h, w, bd, False)), both]
+
+
+def vector_classes(mvs, skip, w, h):
+    """of the 8x8 blocks of a w x h frame with vectors mvs [n, 2] (1/8 luma samples) and flags skip [n]: boolean arrays for 'skipped
+    and the vector has a fraction along x only', '... along y only', '... along both', and 'skipped and the 15 x 15 samples an 8-tap
+    filter reads around the displaced block reach outside the plane'"""
+    mv, sk = np.asarray(mvs).astype(int), np.asarray(skip).astype(bool)
+    fx, fy = (mv[:, 0] & 7) != 0, (mv[:, 1] & 7) != 0
+    b = np.arange(len(mv))
+    x0, y0 = (b % (w // 8)) * 8 + (mv[:, 0] >> 3) - 3, (b // (w // 8)) * 8 + (mv[:, 1] >> 3) - 3
+    outside = (x0 < 0) | (y0 < 0) | (x0 + 15 > w) | (y0 + 15 > h)
+    return dict(x_only=sk & fx & ~fy, y_only=sk & ~fx & fy, both=sk & fx & fy, outside=sk & outside)
+
+
 def stack(clips):
     """clips [(src, ref), ...] of one size -> (src, ref) with [frames, h, w] arrays, the layout of inter_encode_arrays"""
     return (tuple(np.stack([c[0][i] for c in clips]) for i in range(3)),

@@ -153,6 +153,21 @@ def test_low_bits_leaves_the_refinement_alone():
     assert o["fractional"] >= 0.9 * NB and o["distinct_vectors"] >= 20, o
 
 
+@pytest.mark.parametrize("bd", DEPTHS)
+def test_half_sample_frames_fill_every_class_of_vector(bd):
+    """what tests/test_gpu_inter_vs_mc.py compares must be there by the oracle alone: per depth at least 16 skipped blocks whose final
+    vector has a fraction along x only, 16 along y only, 16 along both, and one whose filter window reaches outside the plane.  (72 x 40
+    is 45 blocks, so the three times 16 take three frames.)"""
+    O = _oracle()
+    w, h, q = IC.HALF_W, IC.HALF_H, IC.HALF_Q
+    n = dict(x_only=0, y_only=0, both=0, outside=0)
+    for src, ref in IC.half_sample_frames(w, h, bd):
+        r = O.inter_encode_frame(src, ref, bd, q, 8)
+        for k, m in IC.vector_classes(r["mvs"], r["skip"], w, h).items():
+            n[k] += int(m.sum())
+    assert n["x_only"] >= 16 and n["y_only"] >= 16 and n["both"] >= 16 and n["outside"] >= 1, n
+
+
 def test_observed_counts_are_recorded():
     rec = json.load(open(GOLD))
     now = {str(bd): observe(bd) for bd in DEPTHS}
