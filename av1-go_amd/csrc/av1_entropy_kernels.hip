@@ -17,6 +17,7 @@
 //   k_av1_gather   tile payloads -> one contiguous buffer in tile order (the host adds the frame header and the tile-size fields:
 //                  they depend on the largest tile, host/av1_bitstream.cpp frame_obu_from_tiles).  A tile's workgroup finds its
 //                  offset from the group sums; the last tile's writes the total and the status, and the caller's pinned mirrors
+#include <stdlib.h>
 #include <string.h>
 #include <vector>
 #include "av1_ops_cdfs.hpp"
@@ -39,7 +40,7 @@ struct Av1EntLaunch {
   op_t *ops; uint32_t ops_cap;
   uint32_t *grouped; uint32_t grouped_cap;
   uint32_t *list_off, *grouped_off;          // per tile: where its list / its entries start, in lines of kPoolLine words
-  uint32_t *cursors;                         // [0] the lists' next free line, [1] the entries': zero at the start of a batch
+  uint32_t *cursors;                         // [0] the lists' next free line, [1] the entries'; from [kTicketRowFirst] the chains' tickets: all zero at the start of a batch
   uint16_t *slot_total, *slot_base;          // per tile x S_MAX: entries of the slot, position of its first entry
   uint16_t *rec;                             // per tile of 8x8 blocks x 64 blocks x kBlockRecords: the tokenizer's records
   uint32_t *nops;               // per tile
@@ -58,6 +59,7 @@ struct Av1EntLaunch {
   // key frames in 32x32 blocks (av1_ops32.hpp): the first sb_rows32 superblock rows of every frame are tiles of that kind, with their
   // own slot table and default CDFs; `band` selects which tiles a chains launch walks (0 all, 1 the 32x32 band, 2 the rows below)
   int sb_rows32, band, nslots;
+  int chains_cap, chains_waves; // how k_av1_chains' residency is limited (kChainsCap*), and to how many workgroups per CU
 };
 
 // frame f of the launch; kKey: 1 / 0 = the launch is known to hold key / inter frames (the choice at run time between the two sets of
@@ -163,27 +165,38 @@ __global__ __launch_bounds__(64) void k_av1_tokens32(Av1EntLaunch L) {
 // (Measured: a workgroup that walks several slots one after the other is slower — fewer, longer waves; about half of this
 // kernel's time is the 4-byte scatter of the tuples into the lists.)
 //
-// RESIDENCY is a launch parameter.  The 64 lists of a group are completed word by word by all the group's slots, and the traffic stays
+// RESIDENCY is bounded by the GRID.  The 64 lists of a group are completed word by word by all the group's slots, and the traffic stays
 // near one read and one write per word only while their lines (about 1 MB per group, grouped entries included) stay in the XCD's 4 MB
 // L2.  Left alone, an XCD holds 1 024 of these waves: the short slots retire at once, so the resident set fills with the long slots of
-// many groups.  The launch asks for dynamic LDS nobody uses, sized so that `waves` workgroups fit a CU (nominally: the hardware rounds
-// an allocation up to its granule, which may make it one fewer).  Measured at 4K, q index 128 (DESIGN 5.0-quater,
-// profiles/chains_l2_parent_vs_change.json): 2.5 GB per launch uncapped, 1.8 GB at 12 waves, 0.95 GB at 4 — but below 12 the waves
-// that remain no longer hide the chains' latency beside the tokenizer and the range coder of the neighbouring batches, and the
-// session as a whole is fastest at 12.
+// many groups.  Two limiters, chosen per context (AV1MI_CHAINS_CAP, AV1MI_CHAINS_WAVES = W workgroups per CU):
+//   tickets  a fixed grid of 8 XCDs x 32 CUs x W workgroups; each takes (group, slot) items of its XCD from a counter until the XCD's
+//            groups are used up.  An XCD never has more than 32 W items open, and the kernel holds its 2 KB of LDS per workgroup and
+//            nothing else: the LDS-using kernels of the other streams can start beside it.  NO WORKGROUP WAITS FOR ANOTHER: the counter
+//            is a work queue, a workgroup that is never scheduled costs nothing, one that comes late finds the queue empty and leaves.
+//   lds      one workgroup per item, and dynamic LDS nobody uses, sized so that W workgroups fit a CU (nominally: the hardware rounds
+//            an allocation up to its granule, which may make it one fewer).  At W = 12 that is the CU's whole LDS: while chains waves
+//            sit on a CU no workgroup of a kernel that uses LDS starts there.
+// Either way an XCD opens its groups in turn and a group's slots longest first, and every (group, slot) is walked exactly once, so the
+// bytes are the same.  Measured at 4K, q index 128: DESIGN 5.0-quater (lds: 2.5 GB per launch uncapped, 1.8 GB at 12 waves, 0.95 GB at
+// 4) and 5.0-septies (tickets, profiles/chains_tickets_parent_vs_change.json): under lds the session is fastest at 12, because fewer
+// waves still lock the CUs; under tickets the kernel alone is fastest at 6 (0.65 ms against 0.77) and the SESSION at 2, where the
+// chains take twice as long beside the other kernels and the block pipeline, which is the longer queue, gets the CUs.  At 1 the
+// chains become the longer queue.  Default: tickets, W = 2.
 enum { kChainsInter = 0, kChainsKey8 = 1, kChainsKey32 = 2 };      // the launch flavours: each has its slot table and its rank
-constexpr int kChainsStaticLds = 64 * 16 * 2, kCuLds = 160 << 10, kChainsWavesPerCU = 12;
+enum { kChainsCapLds = 0, kChainsCapTickets = 1 };
+constexpr int kChainsStaticLds = 64 * 16 * 2, kCuLds = 160 << 10, kChainsXcds = 8, kChainsCusPerXcd = 32;
+constexpr int kChainsDefaultCap = kChainsCapTickets, kChainsDefaultWaves = 2;
+// the tickets live behind the batch's cursor line and are zeroed with it, by the one memset per batch: a row of eight counters, one per
+// XCD, for each of a batch's two launches, EVERY COUNTER ON A 128-BYTE LINE OF ITS OWN.  (Measured: with the eight counters of a row in
+// one line the 76 000 draws of a launch queue up behind one another at the memory side and the kernel alone takes 0.4 ms longer.)
+constexpr int kTicketStride = 32, kTicketRowFirst = kTicketStride, kTicketRowBand32 = kTicketRowFirst + kChainsXcds * kTicketStride;
 static unsigned chains_dynamic_lds(int waves) { return waves > 0 && kCuLds / waves > kChainsStaticLds ? (unsigned)(kCuLds / waves - kChainsStaticLds) : 0u; }
 
-__global__ __launch_bounds__(64) void k_av1_chains(Av1EntLaunch L, int ntiles_all, int ngroups, int flavour) {
-  // workgroups are dealt to the eight XCDs in turn (id % 8), each with its own L2: all slots of a tile group go to ONE XCD, one
-  // after the other, so the 64 lists the group's chains complete word by word stay in that L2 as long as possible
-  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3, nslots = L.nslots;
-  const int g = (j / nslots) * 8 + xcd, k = j - (j / nslots) * nslots, lane = threadIdx.x, t = g * 64 + lane;
-  if (g >= ngroups) return;
+// one item: slot rank[k] of tile group g, a lane per tile
+__device__ __forceinline__ void chains_item(const Av1EntLaunch &L, int ntiles_all, int flavour, int g, int k, uint16_t *s_big) {
+  const int lane = threadIdx.x, t = g * 64 + lane;
   // the group's slots longest expected chain first (chains_rank.hpp)
   const int sl = (flavour == kChainsInter ? kChainsRankInter : flavour == kChainsKey8 ? kChainsRankKey8 : kChainsRankKey32)[k];
-  __shared__ __attribute__((aligned(16))) uint16_t s_big[64 * 16];
   const int n = L.tab.nsym[sl], off = L.tab.off[sl];
   int cnt = 0, base = 0;
   bool mine = t < ntiles_all;
@@ -228,6 +241,28 @@ __global__ __launch_bounds__(64) void k_av1_chains(Av1EntLaunch L, int ntiles_al
       const int s = (int)(v & 15);
       list[v >> 4] = s >= kSplitHorz ? split_tuple(cdf, s) : big_step(cdf, s, n);
     }
+  }
+}
+
+// tickets: one row of kChainsXcds counters, zero at the start of the batch (the fixed grid takes items from them), or null (one
+// workgroup per item: a grid of ((ngroups + 7) / 8) * 8 * nslots workgroups)
+__global__ __launch_bounds__(64) void k_av1_chains(Av1EntLaunch L, int ntiles_all, int ngroups, int flavour, uint32_t *tickets) {
+  // workgroups are dealt to the eight XCDs in turn (id % 8), each with its own L2: all slots of a tile group go to ONE XCD, one
+  // after the other, so the 64 lists the group's chains complete word by word stay in that L2 as long as possible.  (Were they dealt
+  // otherwise, the items would still be walked exactly once each, only on other L2s.)
+  const int xcd = blockIdx.x & (kChainsXcds - 1), nslots = L.nslots;
+  __shared__ __attribute__((aligned(16))) uint16_t s_big[64 * 16];      // a lane's own 16 words, written afresh by every item that uses them
+  uint32_t j = blockIdx.x >> 3;
+  for (;;) {
+    if (tickets) {       // the workgroup is one wave: lane 0 draws, the wave reads its lane — no barrier, and nothing to wait for
+      uint32_t drawn = 0;
+      if (threadIdx.x == 0) drawn = atomicAdd(tickets + xcd * kTicketStride, 1u);
+      j = (uint32_t)__shfl((int)drawn, 0, 64);
+    }
+    const int g = (int)(j / (uint32_t)nslots) * kChainsXcds + xcd, k = (int)(j % (uint32_t)nslots);
+    if (g >= ngroups) return;
+    chains_item(L, ntiles_all, flavour, g, k, s_big);
+    if (!tickets) return;
   }
 }
 
@@ -368,12 +403,16 @@ hipError_t launch_av1_front(av1mi_ctx *ctx, const Av1EntLaunch &L, hipStream_t s
   t = ctx_prof_begin(ctx, AV1MI_K_ENTROPY_CHAINS, s);
   Av1EntLaunch C = L;
   C.nslots = L.fv.key ? S_KEY_END : S_INTER_END; C.band = L.sb_rows32 ? 2 : 0;
-  const unsigned lds = chains_dynamic_lds(kChainsWavesPerCU);
-  if (L.sb_rows32 < L.sbr_n)
-    hipLaunchKernelGGL(k_av1_chains, dim3((unsigned)(((ngroups + 7) / 8) * 8 * C.nslots)), dim3(64), lds, s, C, ntiles_all, ngroups, L.fv.key ? kChainsKey8 : kChainsInter);
+  const bool by_tickets = L.chains_cap == kChainsCapTickets;
+  const unsigned lds = by_tickets ? 0u : chains_dynamic_lds(L.chains_waves);
+  auto chains = [&](int flavour, int ticket_row) {
+    const unsigned grid = by_tickets ? (unsigned)(kChainsXcds * kChainsCusPerXcd * L.chains_waves) : (unsigned)(((ngroups + 7) / 8) * 8 * C.nslots);
+    hipLaunchKernelGGL(k_av1_chains, dim3(grid), dim3(64), lds, s, C, ntiles_all, ngroups, flavour, by_tickets ? L.cursors + ticket_row : nullptr);
+  };
+  if (L.sb_rows32 < L.sbr_n) chains(L.fv.key ? kChainsKey8 : kChainsInter, kTicketRowFirst);
   if (L.sb_rows32) {       // the 32x32 band's tiles: their slot table and default CDFs
     C.nslots = K_END; C.band = 1; C.tab = L.tab32; C.cdf_image = L.cdf_image32;
-    hipLaunchKernelGGL(k_av1_chains, dim3((unsigned)(((ngroups + 7) / 8) * 8 * C.nslots)), dim3(64), lds, s, C, ntiles_all, ngroups, kChainsKey32);
+    chains(kChainsKey32, kTicketRowBand32);
   }
   ctx_prof_end(ctx, t, s);
   return hipGetLastError();
@@ -407,10 +446,14 @@ struct av1mi_av1ent_state {      // per-context scratch of the coder, grown on d
   av1ops::SlotTable tab32;        // the 32x32 band's slot table (the same for every q category)
   int image_words[2] = { 0, 0 };
   av1ops::SlotTable tab[2];
+  // k_av1_chains' residency limiter, read once when the context's coder state is made.  Diagnostics, like AV1MI_CODER_STREAMS:
+  // AV1MI_CHAINS_CAP = lds | tickets, AV1MI_CHAINS_WAVES = workgroups per CU (1..32); anything else leaves the default
+  int chains_cap = av1mi::kChainsDefaultCap, chains_waves = av1mi::kChainsDefaultWaves;
 };
 
 namespace {
-constexpr size_t kCursorBytes = 128;
+constexpr size_t kCursorBytes = 128 * (1 + 2 * av1mi::kChainsXcds);      // the pools' cursor line, then a line per ticket counter
+static_assert((av1mi::kTicketRowBand32 + av1mi::kChainsXcds * av1mi::kTicketStride) * sizeof(uint32_t) <= kCursorBytes && av1mi::kTicketRowFirst >= 2, "the tickets lie in the zeroed area, behind the pool cursors");
 int grow(av1mi_ctx *ctx, void **p, size_t *have, size_t need) {
   if (*have >= need) return AV1MI_OK;
   if (*p) (void)hipFree(*p);
@@ -505,6 +548,7 @@ int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hip
   L.total = j->d_total; L.status = (uint32_t *)(j->d_total + 1);
   L.cdf_image = st->d_image[key][qcat]; L.cdf_words = st->image_words[key]; L.tab = st->tab[key];
   L.lr_on_frame = j->d_lr_on;
+  L.chains_cap = st->chains_cap; L.chains_waves = st->chains_waves;
   if (units) for (int p = 0; p < 3; p++) { L.fv.lr_units[p] = units->d_units[p]; L.lr_units_stride[p] = units->frame_stride[p]; }
 #define E_HIP(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return av1mi::ctx_fail(ctx, AV1MI_E_DEVICE, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
   for (hipEvent_t *ev : { &st->lists_ready[par], &st->lists_free[par] }) if (!*ev) E_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
@@ -580,5 +624,11 @@ void av1ent_free(av1mi_av1ent_state *st) {
   for (uint16_t *p : st->d_image32) if (p) (void)hipFree(p);
   delete st;
 }
-av1mi_av1ent_state *av1ent_new() { return new (std::nothrow) av1mi_av1ent_state(); }
+av1mi_av1ent_state *av1ent_new() {
+  av1mi_av1ent_state *st = new (std::nothrow) av1mi_av1ent_state();
+  if (!st) return st;
+  if (const char *e = getenv("AV1MI_CHAINS_CAP")) st->chains_cap = !strcmp(e, "tickets") ? kChainsCapTickets : !strcmp(e, "lds") ? kChainsCapLds : st->chains_cap;
+  if (const char *e = getenv("AV1MI_CHAINS_WAVES")) { const int w = atoi(e); if (w >= 1 && w <= 32) st->chains_waves = w; }
+  return st;
+}
 }  // namespace av1mi
