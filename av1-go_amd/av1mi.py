@@ -110,6 +110,20 @@ class LrSearchJob(C.Structure):
                 ("d_scratch", C.c_void_p), ("d_units_y", C.c_void_p), ("d_units_u", C.c_void_p), ("d_units_v", C.c_void_p), ("d_choice", C.c_void_p)]
 
 
+class CdefSearchJob(C.Structure):
+    """include/av1mi.h av1mi_cdef_search_job"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("bit_depth", C.c_int), ("nframes", C.c_int), ("stride_y", C.c_int), ("stride_uv", C.c_int),
+                ("d_src_y", C.c_void_p), ("d_src_u", C.c_void_p), ("d_src_v", C.c_void_p),
+                ("d_orig_y", C.c_void_p), ("d_orig_u", C.c_void_p), ("d_orig_v", C.c_void_p),
+                ("d_skip8", C.c_void_p), ("skip_frame_stride", C.c_size_t), ("true_width", C.c_int), ("true_height", C.c_int), ("bits", C.c_int),
+                ("params", C.c_void_p), ("d_sse", C.c_void_p), ("d_strength", C.c_void_p), ("d_idx", C.c_void_p)]
+
+
+class EntropyCdef(C.Structure):
+    """include/av1mi.h av1mi_av1_entropy_cdef"""
+    _fields_ = [("cdef_bits", C.c_int), ("d_idx", C.c_void_p), ("frame_stride", C.c_size_t)]
+
+
 class GopConfig(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("bit_depth", C.c_int), ("base_q_idx", C.c_int), ("gop_length", C.c_int),
                 ("segments", C.c_int), ("search_range", C.c_int), ("gpu_entropy", C.c_int), ("visible_width", C.c_int),
@@ -117,7 +131,8 @@ class GopConfig(C.Structure):
                 ("source_height", C.c_int), ("quality_stats", C.c_int), ("coarse_range", C.c_int), ("source_chroma", C.c_int),
                 ("source_bit_depth", C.c_int), ("store_frames", C.c_int), ("deinterlace", C.c_int), ("denoise", C.c_int),
                 ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int), ("crop_height", C.c_int), ("denoise_range", C.c_int),
-                ("tone_map", C.c_int), ("tone_map_peak", C.c_int), ("grain_cov", C.c_int), ("lr_search", C.c_int)]
+                ("tone_map", C.c_int), ("tone_map_peak", C.c_int), ("grain_cov", C.c_int), ("lr_search", C.c_int),
+                ("cdef_search", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -132,7 +147,8 @@ class GopFrame(C.Structure):
                 ("lev_v", C.c_void_p), ("tiles_per_frame", C.c_int), ("tile_size", C.c_void_p), ("tile_payload", C.c_void_p),
                 ("payload_bytes", C.c_uint64), ("lr_on", C.c_void_p), ("key_block_size", C.c_int), ("key_modes_stride", C.c_int),
                 ("key_modes_band", C.c_int), ("quality", C.c_void_p), ("grain", C.c_void_p), ("grain_cov", C.c_void_p),
-                ("lr_units", C.c_void_p * 3), ("lr_units_per_frame", C.c_int * 3), ("lr_choice", C.c_void_p)]
+                ("lr_units", C.c_void_p * 3), ("lr_units_per_frame", C.c_int * 3), ("lr_choice", C.c_void_p),
+                ("cdef_bits", C.c_int), ("cdef_y", C.c_uint8 * 8), ("cdef_uv", C.c_uint8 * 8), ("cdef_idx", C.c_void_p)]
 
 
 def policy_frame_params(base_q_idx, bit_depth, frame_type):
@@ -259,7 +275,7 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None, tone_map=0, tone_map_peak=0, grain_cov=None, lr_search=None):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None, tone_map=0, tone_map_peak=0, grain_cov=None, lr_search=None, cdef_search=None):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
@@ -293,6 +309,8 @@ class GopSession:
             self.cfg.grain_cov = int(grain_cov)
         if lr_search is not None:       # 1 = a Wiener record or none chosen per restoration unit (av1mi_gop_config.lr_search)
             self.cfg.lr_search = int(lr_search)
+        if cdef_search is not None:     # 1 .. 3 = cdef_bits: a CDEF strength set chosen per superblock (av1mi_gop_config.cdef_search)
+            self.cfg.cdef_search = int(cdef_search)
         # tone_map: 1 = every batch is tone-mapped (PQ / BT.2020 -> SDR / BT.709) in place behind the input stages; tone_map_peak: cd/m2, 0 = 1000
         self.cfg.tone_map, self.cfg.tone_map_peak = int(tone_map), int(tone_map_peak)
         if crop is not None:
@@ -382,6 +400,9 @@ class GopSession:
             per = list(f.lr_units_per_frame)
             out["lr_choice"] = _view(f.lr_choice, (S, sum(per)), np.uint8)
             out["lr_units"] = [_view(f.lr_units[p], (S, per[p], 8), np.int8) for p in range(3)]
+        if f.cdef_bits:    # cdef_search: the frame header's sets and the chosen index per [segment, superblock]
+            out["cdef_bits"], out["cdef_y"], out["cdef_uv"] = int(f.cdef_bits), list(f.cdef_y), list(f.cdef_uv)
+            out["cdef_idx"] = _view(f.cdef_idx, (S, ((self.w + 63) // 64) * ((self.h + 63) // 64)), np.uint8)
         if f.grain_cov:    # grain_cov: records [segment, plane] (GRAIN_COV_DTYPE)
             out["grain_cov"] = _view(f.grain_cov, (S, 3), GRAIN_COV_DTYPE)
         if f.key_block_size == 32:
@@ -475,6 +496,20 @@ def tone_map_tables(peak, lib=None):
     if lib.av1mi_tone_map_tables(int(peak), C.byref(t)) != 0:
         raise ValueError("av1mi_tone_map_tables: peak %r out of range (100 .. 10000)" % (peak,))
     return t
+
+
+def cdef_search_sets(params, bits):
+    """the candidate strength sets of a frame (av1mi_cdef_search_sets): two lists of 8 bytes, (primary << 2) | secondary, luma and chroma"""
+    y, uv = (C.c_uint8 * 8)(), (C.c_uint8 * 8)()
+    if load().av1mi_cdef_search_sets(C.byref(params), int(bits), y, uv):
+        raise ValueError("CDEF search: bits %d outside 1 .. 3" % bits)
+    return list(y), list(uv)
+
+
+def cdef_search_table_bytes(width, height, nframes):
+    lib = load()
+    lib.av1mi_cdef_search_table_bytes.restype = C.c_size_t
+    return int(lib.av1mi_cdef_search_table_bytes(int(width), int(height), int(nframes)))
 
 
 LR_SEARCH_CANDIDATES = 9      # AV1MI_LR_SEARCH_CANDIDATES
@@ -843,6 +878,10 @@ class Context:
     def lr_yuv_decide(self, job):
         """the three planes' restoration + ON / OFF decisions in one call (include/av1mi.h av1mi_lr_yuv_decide)"""
         self._chk(self.lib.av1mi_lr_yuv_decide(self.h, C.byref(job)))
+
+    def cdef_search(self, job):
+        """a CDEF strength set per superblock against the source (include/av1mi.h av1mi_cdef_search; job: CdefSearchJob)"""
+        self._chk(self.lib.av1mi_cdef_search(self.h, C.byref(job)))
 
     def lr_search(self, job):
         """a Wiener record or none per restoration unit of the three planes (include/av1mi.h av1mi_lr_search; job: LrSearchJob)"""

@@ -204,8 +204,11 @@ def assemble_temporal_unit(width, height, bit_depth, base_q_idx, payloads, sizes
     f.frame_type = hdr.get("frame_type", 0)
     for i in range(4):
         f.lf_level[i] = int(hdr.get("lf_level", (0,) * 4)[i])
-    f.lf_sharpness, f.cdef_damping, f.cdef_bits = hdr.get("lf_sharpness", 0), hdr.get("cdef_damping", 3), 0
-    f.cdef_y[0], f.cdef_uv[0] = int(hdr.get("cdef_y", (0,))[0]), int(hdr.get("cdef_uv", (0,))[0])
+    f.lf_sharpness, f.cdef_damping, f.cdef_bits = hdr.get("lf_sharpness", 0), hdr.get("cdef_damping", 3), int(hdr.get("cdef_bits", 0))
+    for i, v in enumerate(hdr.get("cdef_y", (0,))):      # (the header lists the sets; the tiles carry the indices)
+        f.cdef_y[i] = int(v)
+    for i, v in enumerate(hdr.get("cdef_uv", (0,))):
+        f.cdef_uv[i] = int(v)
     keep = []
     for p in range(3):
         f.lr_type[p] = int(hdr.get("lr_type", (0, 0, 0))[p])
@@ -230,10 +233,22 @@ def assemble_temporal_unit(width, height, bit_depth, base_q_idx, payloads, sizes
     return out[:n].tobytes()
 
 
+def _session_cdef(frame, seg, with_indices):
+    """a CDEF-search session's part of the header: cdef_bits and the batch's strength sets, and (host writer) the segment's indices"""
+    if not frame.get("cdef_bits"):
+        return {}
+    n = 1 << frame["cdef_bits"]
+    hdr = dict(cdef_bits=frame["cdef_bits"], cdef_y=tuple(frame["cdef_y"][:n]), cdef_uv=tuple(frame["cdef_uv"][:n]))
+    if with_indices:
+        hdr["cdef_idx"] = frame["cdef_idx"][seg]
+    return hdr
+
+
 def session_frame_unit_gpu(width, height, bit_depth, frame, seg, with_sequence_header=None, visible=None, film_grain=None, film_grain_present=None):
     """the temporal unit of segment `seg` of a collected batch whose tiles were entropy-coded on the GPU (gpu_entropy != 0)"""
     p = frame["params"]
     hdr = header_from_params(p, width, height, frame["lr_on"][seg], visible)
+    hdr.update(_session_cdef(frame, seg, False))
     hdr.update(film_grain=film_grain, film_grain_present=film_grain_present)
     nt = frame["tiles_per_frame"]
     sizes = frame["tile_size"][seg * nt:(seg + 1) * nt]
@@ -397,6 +412,7 @@ def session_frame_unit(width, height, bit_depth, frame, seg, with_sequence_heade
     p = frame["params"]
     hdr = header_from_params(p, width, height, frame["lr_on"][seg], visible)
     hdr.update(film_grain=film_grain, film_grain_present=film_grain_present)
+    hdr.update(_session_cdef(frame, seg, True))
     if p.frame_type == 0:
         sym = dict(y_mode=frame["y_mode"][seg], uv_mode=frame["uv_mode"][seg])
     else:

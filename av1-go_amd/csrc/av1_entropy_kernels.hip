@@ -56,6 +56,7 @@ struct Av1EntLaunch {
   const uint16_t *cdf_image32; SlotTable tab32;   // the same for the tiles of a key frame's 32x32 band
   const uint8_t *lr_on_frame;   // optional: [frame * 3 + plane], 0 = restoration of the plane is off in that frame
   size_t lr_units_stride[3];    // fv.lr_units[p] != null: units between the frames of plane p's records
+  size_t cdef_idx_stride;       // fv.cdef_idx != null: bytes between the frames' CDEF indices
   // key frames in 32x32 blocks (av1_ops32.hpp): the first sb_rows32 superblock rows of every frame are tiles of that kind, with their
   // own slot table and default CDFs; `band` selects which tiles a chains launch walks (0 all, 1 the 32x32 band, 2 the rows below)
   int sb_rows32, band, nslots;
@@ -73,6 +74,7 @@ template <int kKey = -1> __device__ __forceinline__ FrameView frame_view(const A
   v.info = L.info + nb * f;
   if (L.lr_on_frame) for (int p = 0; p < 3; p++) v.lr_on[p] = v.lr_on[p] && L.lr_on_frame[f * 3 + p];
   for (int p = 0; p < 3; p++) if (v.lr_units[p]) v.lr_units[p] += L.lr_units_stride[p] * 8 * (size_t)f;
+  if (v.cdef_idx) v.cdef_idx += L.cdef_idx_stride * (size_t)f;
   return v;
 }
 
@@ -118,6 +120,7 @@ struct TileWave {
     return __shfl(inc, 63, 64);
   }
   __device__ __forceinline__ int first(Var<int> &v) { return __shfl(v.v[0], 0, 64); }
+  __device__ __forceinline__ uint64_t ballot(Var<int> &v) { return __ballot(v.v[0] != 0); }
 };
 
 // The tiles of 8x8 blocks: ONE WAVE PER TILE, a lane per block in z-order (av1_ops8.hpp tok_tile8): the neighbours' level summaries into
@@ -475,7 +478,8 @@ uint32_t av1mi_av1_entropy_slot_bytes(void) { return 16384; }
 
 }  // extern "C"
 
-int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hipStream_t front, int *ticket, const av1mi_av1_entropy_units *units) {
+int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hipStream_t front, int *ticket, const av1mi_av1_entropy_units *units,
+                             const av1mi_av1_entropy_cdef *cdef) {
   if (!ctx || !ticket) return AV1MI_E_INVAL;
   *ticket = -1;
   if (!j) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "null job");
@@ -491,6 +495,7 @@ int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hip
     if (any && !all) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "restoration units: the records of all three planes, or of none");
     for (int p = 0; p < 3; p++) if ((uintptr_t)units->d_units[p] & 7) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "restoration units: misaligned device pointer (8 bytes)");
   }
+  if (cdef && (cdef->cdef_bits < 0 || cdef->cdef_bits > 3)) return av1mi::ctx_fail(ctx, AV1MI_E_INVAL, "CDEF indices: cdef_bits %d outside 0 .. 3", cdef->cdef_bits);
   if (j->nframes == 0) return AV1MI_OK;
   av1mi_av1ent_state *st = av1mi::ctx_av1ent(ctx);
   if (!st) return av1mi::ctx_fail(ctx, AV1MI_E_NOMEM, "AV1 entropy state");
@@ -550,6 +555,7 @@ int av1mi::av1_entropy_front(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hip
   L.lr_on_frame = j->d_lr_on;
   L.chains_cap = st->chains_cap; L.chains_waves = st->chains_waves;
   if (units) for (int p = 0; p < 3; p++) { L.fv.lr_units[p] = units->d_units[p]; L.lr_units_stride[p] = units->frame_stride[p]; }
+  if (cdef && cdef->cdef_bits) { L.fv.cdef_bits = cdef->cdef_bits; L.fv.cdef_idx = cdef->d_idx; L.cdef_idx_stride = cdef->frame_stride; }
 #define E_HIP(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return av1mi::ctx_fail(ctx, AV1MI_E_DEVICE, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
   for (hipEvent_t *ev : { &st->lists_ready[par], &st->lists_free[par] }) if (!*ev) E_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
   if (st->free_recorded[par]) E_HIP(hipStreamWaitEvent(front, st->lists_free[par], 0));      // the coder of two jobs ago still reads this set of lists
@@ -579,15 +585,21 @@ int av1mi::av1_entropy_back(av1mi_ctx *ctx, int ticket, hipStream_t back, const 
 }
 
 int av1mi::av1_entropy_submit(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, hipStream_t front, hipStream_t back, const Av1EntMirrors *mirrors,
-                              const av1mi_av1_entropy_units *units) {
+                              const av1mi_av1_entropy_units *units, const av1mi_av1_entropy_cdef *cdef) {
   int ticket = -1;
-  const int rc = av1_entropy_front(ctx, j, front, &ticket, units);
+  const int rc = av1_entropy_front(ctx, j, front, &ticket, units, cdef);
   if (rc != AV1MI_OK || ticket < 0) return rc;      // (an empty job has no back half)
   return av1_entropy_back(ctx, ticket, back, mirrors);
 }
 
 extern "C" {
 
+int av1mi_av1_entropy_encode_sides(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, const av1mi_av1_entropy_units *units, const av1mi_av1_entropy_cdef *cdef,
+                                   void *stream_handle) {
+  if (!ctx) return AV1MI_E_INVAL;
+  hipStream_t s = stream_handle ? (hipStream_t)stream_handle : av1mi::ctx_stream(ctx);
+  return av1mi::av1_entropy_submit(ctx, j, s, s, nullptr, units, cdef);
+}
 int av1mi_av1_entropy_encode_units(av1mi_ctx *ctx, const av1mi_av1_entropy_job *j, const av1mi_av1_entropy_units *units, void *stream_handle) {
   if (!ctx) return AV1MI_E_INVAL;
   hipStream_t s = stream_handle ? (hipStream_t)stream_handle : av1mi::ctx_stream(ctx);

@@ -186,7 +186,11 @@ struct FrameView {
   int lr_rows[3], lr_cols[3];   // units per plane
   const int8_t *lr_units[3];    // optional, per plane: the frame's own records, lr_rows x lr_cols of 8 bytes in raster order (the
                                 // restoration search's choice; a record of type 0 = the unit is not filtered); null = lr_unit serves every unit
+  int cdef_bits;                // read_cdef (5.11.56): a superblock's CDEF index is cdef_bits literal bits (0: nothing is coded) ...
+  const uint8_t *cdef_idx;      // ... the frame's indices, one byte per superblock in raster order (the CDEF search's choice); null = 0
 };
+// the CDEF index of the tile = superblock (sbr, sbc)
+AV1_HD unsigned cdef_index(const FrameView &f, int sbr, int sbc) { return f.cdef_idx ? f.cdef_idx[sbr * ((f.w8 + 7) / 8) + sbc] : 0u; }
 
 AV1_HD int iabs(int v) { return v < 0 ? -v : v; }
 AV1_HD int imin(int a, int b) { return a < b ? a : b; }
@@ -562,8 +566,9 @@ AV1_HD void tok_mv_comp(Sink &k, int comp, int diff) {            // read_mv_com
 }
 
 // all ops of the block with z-order index `zi` of superblock (sbr, sbc); returns without ops for blocks outside the frame.
-// sums[by * 8 + bx]: block_levels_summary of the tile's blocks
-AV1_HD void tok_block(const FrameView &f, Sink &k, const TokScratch &ts, int sbr, int sbc, int zi, const uint8_t *sums) {
+// sums[by * 8 + bx]: block_levels_summary of the tile's blocks; cdef_zi: the z-order index of the tile's first block that is not
+// skipped, which carries the superblock's CDEF index behind its skip symbol (anything else, -1 for instance: no block of this tile does)
+AV1_HD void tok_block(const FrameView &f, Sink &k, const TokScratch &ts, int sbr, int sbc, int zi, const uint8_t *sums, int cdef_zi) {
   int bx, by;
   demorton8((unsigned)zi, &bx, &by);
   const int r8 = sbr * 8 + by, c8 = sbc * 8 + bx;
@@ -575,6 +580,7 @@ AV1_HD void tok_block(const FrameView &f, Sink &k, const TokScratch &ts, int sbr
   const unsigned sa = au ? sums[(by - 1) * 8 + bx] : 0u, sl = al ? sums[by * 8 + bx - 1] : 0u;
   const int skip = f.key ? 0 : f.skip[b];
   k.sym(S_SKIP + (au && !f.key ? f.skip[b - f.w8] : 0) + (al && !f.key ? f.skip[b - 1] : 0), skip);
+  if (zi == cdef_zi) k.lit(cdef_index(f, sbr, sbc), f.cdef_bits);
   int ym = 0;
   if (f.key) {
     ym = f.y_mode[b];

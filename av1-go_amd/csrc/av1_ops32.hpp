@@ -122,6 +122,7 @@ template <int N> struct MagMap<N, false> {
 //   w.each(f)            f(lane) for every lane, then a barrier: what a phase wrote to the tile's memory is visible to the next
 //   w.scan(v) -> total   v[lane] becomes the sum of the lanes before it
 //   w.first(v)           lane 0's value, to all
+//   w.ballot(v) -> mask  bit `lane` = v[lane] != 0 (64 bits)
 // Values that are the same in every lane (what scan and first return, what is read from the tile's memory after a barrier) are
 // plain variables.
 enum { kLanes32 = 64, kBlocks32 = 4, kTile32MagBytes = kBlocks32 * (Mag32<32>::kBytes + 2 * Mag32<16>::kBytes) };
@@ -205,6 +206,7 @@ template <class K> AV1_HD void tok_block32_head(const FrameView &f, K &k, int sb
   }
   k.sym(K_PART32, 0);                            // PARTITION_NONE
   k.sym(K_SKIP, 0);
+  if (b == 0 && f.cdef_bits) k.lit(cdef_index(f, sbr, sbc), f.cdef_bits);      // read_cdef: with the tile's first block (key frames: skip = 0)
   tok_kf_modes<kSlots32>(k, f.y_mode[i], f.uv_mode[i], by ? f.y_mode[i - w32] : 0, bx ? f.y_mode[i - 1] : 0);
 }
 // what the neighbours of a transform block read of it: min(63, sum |level|) and the DC's sign class (0 none / 1 negative / 2 positive)

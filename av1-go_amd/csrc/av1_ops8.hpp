@@ -68,12 +68,29 @@ AV1_HD int tok_tile8(W &w, Tile8Mem &S, const FrameView &f, int sbr, int sbc, ui
     const int r8 = sbr * 8 + by, c8 = sbc * 8 + bx;
     S.sums[by * 8 + bx] = (uint8_t)(r8 < f.h8 && c8 < f.w8 ? block_levels_summary(f, r8 * f.w8 + c8) : 0u);
   });
+  // read_cdef: the superblock's index goes with the tile's first block in coding order (= lane order) that is not skipped — block 0 of
+  // a key frame; in a P frame a ballot over the lanes' "inside the frame and coded" says which, and none when the tile is all skipped
+  int cdef_zi = -1;
+  if (f.cdef_bits) {
+    if (f.key) cdef_zi = 0;
+    else {
+      LaneInt coded;
+      w.each([&](int lane) {
+        int bx, by;
+        demorton8((unsigned)lane, &bx, &by);
+        const int r8 = sbr * 8 + by, c8 = sbc * 8 + bx;
+        coded[lane] = r8 < f.h8 && c8 < f.w8 && !f.skip[r8 * f.w8 + c8];
+      });
+      const uint64_t m = w.ballot(coded);
+      cdef_zi = m ? __builtin_ctzll(m) : -1;
+    }
+  }
   // tokenize: records, counts; a lane's list words, and "a block overflowed" above them
   LaneInt nrec, first;
   w.each([&](int lane) {
     const TokScratch ts = { S.p1.mag + lane * kMagBytes, &S.scan };
     Sink k = { rec + (size_t)lane * kBlockRecords, S.p1.cnt, lane, 0, 0, false };
-    tok_block(f, k, ts, sbr, sbc, lane, S.sums);
+    tok_block(f, k, ts, sbr, sbc, lane, S.sums, cdef_zi);
     nrec[lane] = k.nrec;
     first[lane] = k.n | (k.overflow ? 1 << 24 : 0);       // (a block has fewer than 2^16 words)
   });

@@ -103,6 +103,18 @@ struct CdefLaunch {
 };
 hipError_t launch_cdef(const CdefLaunch &L, hipStream_t s);
 
+// The CDEF search (cdef_search_kernel.hip k_cdef_search; av1mi.h "CDEF search"): per superblock the squared error of ncand candidate
+// strength sets against the source over the true size (tw x th), and the arg-min
+struct CdefSearchLaunch {
+  const void *src[3], *orig[3];                         // deblocked planes, source planes: the same geometry
+  int w, h, tw, th, stride_y, stride_uv, bd, damping, nframes, ncand;
+  const uint8_t *skip8; size_t skip_frame_stride;       // as CdefLaunch
+  uint32_t sets[8];                                     // candidate c as a CdefLaunch strength record: y_pri | y_sec << 8 | uv_pri << 16 | uv_sec << 24
+  unsigned long long *sse;                              // [frame][sb][8]
+  uint8_t *strength, *idx;                              // [frame][sb][4], [frame][sb]
+};
+hipError_t launch_cdef_search(const CdefSearchLaunch &L, hipStream_t s);
+
 // K5 + K6 in one kernel (deblock_cdef_kernel.hip): reconstruction -> CDEF output, and the rows of the deblocked planes that K7 reads
 struct DeblockCdefLaunch {
   const void *rec[3]; void *dbl[3]; void *dst[3];
@@ -364,10 +376,11 @@ struct Av1EntMirrors {
 // coder + gather on `back` (the same stream, or a second one: the lists are double-buffered, so the front half of the next
 // job runs beside the back half of this one)
 int av1_entropy_submit(av1mi_ctx *ctx, const struct av1mi_av1_entropy_job *j, hipStream_t front, hipStream_t back, const Av1EntMirrors *mirrors = nullptr,
-                       const struct av1mi_av1_entropy_units *units = nullptr);
+                       const struct av1mi_av1_entropy_units *units = nullptr, const struct av1mi_av1_entropy_cdef *cdef = nullptr);
 // ... and the halves on their own: the back half of a job may be launched later (the session defers the range coder of batch t behind
 // the filters of batch t + 1 on the main stream); at most two jobs' back halves can be outstanding (the list sets)
-int av1_entropy_front(av1mi_ctx *ctx, const struct av1mi_av1_entropy_job *j, hipStream_t front, int *ticket, const struct av1mi_av1_entropy_units *units = nullptr);
+int av1_entropy_front(av1mi_ctx *ctx, const struct av1mi_av1_entropy_job *j, hipStream_t front, int *ticket, const struct av1mi_av1_entropy_units *units = nullptr,
+                      const struct av1mi_av1_entropy_cdef *cdef = nullptr);
 int av1_entropy_back(av1mi_ctx *ctx, int ticket, hipStream_t back, const Av1EntMirrors *mirrors = nullptr);
 // accessors of the opaque context for translation units other than capi.hip (gop_session.hip)
 hipStream_t ctx_stream(av1mi_ctx *ctx);

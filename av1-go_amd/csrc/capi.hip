@@ -461,6 +461,53 @@ int av1mi_cdef_frames(av1mi_ctx *ctx, const av1mi_cdef_job *j) {
   return AV1MI_OK;
 }
 
+// ---- CDEF search
+int av1mi_cdef_search_sets(const av1mi_frame_params *p, int bits, uint8_t y[8], uint8_t uv[8]) {
+  if (!p || !y || !uv || bits < 1 || bits > 3) return AV1MI_E_INVAL;
+  auto dbl = [](int x) { return std::min(15, std::max(1, 2 * x)); };
+  auto up = [](int x) { return std::min(3, x + 1); };
+  auto sets = [&](int v, uint8_t out[8]) {
+    const int P = v >> 2, S = v & 3;
+    const int pri[8] = { P, 0, P >> 1, dbl(P), P, P, dbl(P), dbl(dbl(P)) }, sec[8] = { S, 0, S, S, up(S), 0, up(S), up(S) };
+    for (int c = 0; c < 8; c++) out[c] = c < (1 << bits) ? (uint8_t)((pri[c] << 2) | sec[c]) : (uint8_t)0;
+  };
+  sets(p->cdef_y, y); sets(p->cdef_uv, uv);
+  return AV1MI_OK;
+}
+size_t av1mi_cdef_search_table_bytes(int width, int height, int nframes) {
+  if (width <= 0 || height <= 0 || nframes <= 0) return 0;
+  return (size_t)nframes * ((width + 63) / 64) * ((height + 63) / 64) * 8 * sizeof(uint64_t);
+}
+int av1mi_cdef_search(av1mi_ctx *ctx, const av1mi_cdef_search_job *j) {
+  BIND(ctx);
+  if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
+  if (int rc = check_bd(ctx, j->bit_depth)) return rc;
+  if (j->width <= 0 || j->height <= 0 || (j->width & 7) || (j->height & 7) || j->width > 16384 || j->height > 16384)
+    return fail(ctx, AV1MI_E_INVAL, "frame %dx%d must be a multiple of 8", j->width, j->height);
+  if (int rc = check_nframes(ctx, j->nframes)) return rc;
+  if (j->stride_y < j->width || j->stride_uv < j->width / 2 || (j->stride_y & 3) || (j->stride_uv & 3)) return fail(ctx, AV1MI_E_INVAL, "bad strides");
+  const int tw = j->true_width ? j->true_width : j->width, th = j->true_height ? j->true_height : j->height;
+  if (tw > j->width || th > j->height || tw <= j->width - 8 || th <= j->height - 8) return fail(ctx, AV1MI_E_INVAL, "true size %dx%d does not round up to %dx%d", tw, th, j->width, j->height);
+  if (!j->params || j->bits < 1 || j->bits > 3) return fail(ctx, AV1MI_E_INVAL, "CDEF search: bits %d outside 1 .. 3, or no frame parameters", j->bits);
+  if (j->params->cdef_damping < 3 || j->params->cdef_damping > 6) return fail(ctx, AV1MI_E_INVAL, "bad damping/nframes");
+  const void *ptrs[] = { j->d_src_y, j->d_src_u, j->d_src_v, j->d_orig_y, j->d_orig_u, j->d_orig_v, j->d_sse };
+  for (const void *p : ptrs) if (!p || ((uintptr_t)p & 7)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned device pointer");
+  if (!j->d_skip8 || !j->d_strength || !j->d_idx || ((uintptr_t)j->d_strength & 3)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned map pointer");
+  if (j->nframes == 0) return AV1MI_OK;
+  av1mi::CdefSearchLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.src[0] = j->d_src_y; L.src[1] = j->d_src_u; L.src[2] = j->d_src_v; L.orig[0] = j->d_orig_y; L.orig[1] = j->d_orig_u; L.orig[2] = j->d_orig_v;
+  L.w = j->width; L.h = j->height; L.tw = tw; L.th = th; L.stride_y = j->stride_y; L.stride_uv = j->stride_uv; L.bd = j->bit_depth;
+  L.damping = j->params->cdef_damping; L.nframes = j->nframes; L.ncand = 1 << j->bits;
+  L.skip8 = j->d_skip8; L.skip_frame_stride = j->skip_frame_stride;
+  uint8_t y[8], uv[8];
+  av1mi_cdef_search_sets(j->params, j->bits, y, uv);
+  for (int c = 0; c < 8; c++) L.sets[c] = (uint32_t)(y[c] >> 2) | (uint32_t)(y[c] & 3) << 8 | (uint32_t)(uv[c] >> 2) << 16 | (uint32_t)(uv[c] & 3) << 24;
+  L.sse = (unsigned long long *)j->d_sse; L.strength = j->d_strength; L.idx = j->d_idx;
+  { ProfScope ps(ctx, AV1MI_K_CDEF); HIP_TRY(ctx, av1mi::launch_cdef_search(L, ctx->stream)); }
+  return AV1MI_OK;
+}
+
 int av1mi_deblock_cdef_frames(av1mi_ctx *ctx, const av1mi_deblock_cdef_job *j) {
   BIND(ctx);
   if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");

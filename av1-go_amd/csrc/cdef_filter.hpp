@@ -1,7 +1,8 @@
 // cdef_filter.hpp — CDEF (AV1 spec §7.15) of one 64x64 luma superblock and its two 32x32 chroma blocks on tiles staged in LDS: the
-// direction search, the tap tables, the packed filter, and the filter loops of a 256-lane workgroup.  Shared by k_cdef
-// (cdef_kernel.hip: deblocked planes from HBM) and k_deblock_cdef (deblock_cdef_kernel.hip: the tile deblocked in place), so both
-// run the same source.  A tile holds 0xFFFF where a sample lies outside the picture.
+// direction search, the tap tables, the packed filter, and the filter items of a 256-lane workgroup with a sink for their output.
+// Shared by k_cdef (cdef_kernel.hip: deblocked planes from HBM), k_deblock_cdef (deblock_cdef_kernel.hip: the tile deblocked in
+// place) and k_cdef_search (cdef_search_kernel.hip: squared error against the source per candidate strength set), so all three run
+// the same source.  A tile holds 0xFFFF where a sample lies outside the picture.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -120,11 +121,10 @@ __device__ __forceinline__ CdefSb cdef_sb_params(uint32_t st32, int damping, int
   return s;
 }
 
-// Direction search of the 8x8 luma block at p (rows YS apart), every bin index a compile-time constant.  Returns everything a
-// quad of this block needs, once per block instead of once per quad (16 luma + 8 chroma quads per block): luma primary strength
-// after the variance adjustment (bits 0-7), its damping shift (8-11), the luma filter direction (12-14), the primary tap parity
-// (15), the block's direction itself (16-18: chroma)
-template <int YS> __device__ __forceinline__ uint32_t cdef_block_params(const uint16_t *p, int cs, int ypri0, int dampy) {
+// Direction search of the 8x8 luma block at p (rows YS apart), every bin index a compile-time constant: the block's direction
+// (bits 0-2) and its variance (from bit 3).  Neither depends on the strengths, so the CDEF search runs this once per block for all of
+// its candidate sets; cdef_block_pack adds what a strength set makes of them.
+template <int YS> __device__ __forceinline__ uint32_t cdef_block_dirvar(const uint16_t *p, int cs) {
   // squares of sums of at most 8 values in [-128, 127] (<= 2^20) times weights <= 840: 24-bit multiplies (a 32-bit integer
   // multiply is four passes)
   constexpr int div_table[9] = { 0, 840, 420, 280, 210, 168, 140, 120, 105 };
@@ -181,12 +181,21 @@ template <int YS> __device__ __forceinline__ uint32_t cdef_block_params(const ui
   int opp = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) if (i == ((best + 4) & 7)) opp = cost[i];
-  const int var = (best_cost - opp) >> 10;
+  return (uint32_t)best | ((uint32_t)((best_cost - opp) >> 10) << 3);
+}
+// Everything a quad of the block needs, once per block instead of once per quad (16 luma + 8 chroma quads per block): luma primary
+// strength after the variance adjustment (bits 0-7), its damping shift (8-11), the luma filter direction (12-14), the primary tap
+// parity (15), the block's direction itself (16-18: chroma)
+__device__ __forceinline__ uint32_t cdef_block_pack(uint32_t dirvar, int cs, int ypri0, int dampy) {
+  const int best = (int)(dirvar & 7), var = (int)(dirvar >> 3);
   const int vs = (var >> 6) ? min(msb((unsigned)(var >> 6)), 12) : 0;
   const int pri = var ? (ypri0 * (4 + vs) + 8) >> 4 : 0;             // spec 7.15.2: luma primary strength adjusted by the variance
   const int pshift = pri ? max(0, dampy - msb((unsigned)pri)) : 0;
   const int ydir = ypri0 == 0 ? 0 : best;
   return (uint32_t)pri | ((uint32_t)pshift << 8) | ((uint32_t)ydir << 12) | ((uint32_t)((pri >> cs) & 1) << 15) | ((uint32_t)best << 16);
+}
+template <int YS> __device__ __forceinline__ uint32_t cdef_block_params(const uint16_t *p, int cs, int ypri0, int dampy) {
+  return cdef_block_pack(cdef_block_dirvar<YS>(p, cs), cs, ypri0, dampy);
 }
 
 template <typename Pix> __device__ __forceinline__ void cdef_store4(Pix *d, const int (&o)[4]) {
@@ -194,57 +203,151 @@ template <typename Pix> __device__ __forceinline__ void cdef_store4(Pix *d, cons
   else { uint2 u; u.x = (uint32_t)o[0] | ((uint32_t)o[1] << 16); u.y = (uint32_t)o[2] | ((uint32_t)o[3] << 16); *reinterpret_cast<uint2 *>(d) = u; }
 }
 
-// The filter loops of a 256-lane workgroup.  ty0 / tc0: the tile sample of the block's top-left corner (4-byte aligned, rows YS / CS
-// apart, both even); (sbx, sby): the superblock; w, h: the luma picture; dy / dc: frame f's output planes.  interior: the tiles hold
-// no 0xFFFF mark.  bskip: skip flag of each 8x8 block of the superblock (1 also for blocks outside the picture); bpar: see
-// cdef_block_params; offy / offc: the tap tables of the two tile strides (cdef_fill_offsets).
+// THE FILTER, stated once: item q of a 256-lane workgroup's superblock is four horizontally adjacent samples, and what becomes of the
+// four filtered samples is the SINK's business — k_cdef and k_deblock_cdef store them to the output planes (CdefStore), k_cdef_search
+// adds their squared difference to the source into a register.  ty0 / tu0, tv0: the tile sample of the block's top-left corner (4-byte
+// aligned, rows YS / CS apart, both even); (sbx, sby): the superblock; w, h: the luma picture.  interior: the tiles hold no 0xFFFF
+// mark.  bskip: skip flag of each 8x8 block of the superblock (1 also for blocks outside the picture); bpar: see cdef_block_pack;
+// offy / offc: the tap tables of the two tile strides (cdef_fill_offsets).  An item outside the picture reaches no sink.
+// luma 64x64: q in [0, 64 * 16) -> (row, group of 4 columns); sink(fy, fx, o)
+template <int YS, class Sink>
+__device__ __forceinline__ void cdef_luma_item(int q, const uint16_t *ty0, int sbx, int sby, int w, int h, const CdefSb &S, bool interior,
+                                               const uint8_t *bskip, const uint32_t *bpar, const int32_t *offy, Sink &&sink) {
+  const int r = q >> 4, c = (q & 15) * 4;
+  const int fy = sby * 64 + r, fx = sbx * 64 + c;
+  if (fy >= h || fx >= w) return;
+  const int b = (r >> 3) * 8 + (c >> 3);
+  const bool skip = !S.enabled || bskip[b];
+  const uint16_t *p = ty0 + r * YS + c;
+  int o[4];
+  if (skip) { o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; o[3] = p[3]; }
+  else {
+    const uint32_t bp = bpar[b];
+    const int pri = bp & 255, pshift = (bp >> 8) & 15, par = (bp >> 15) & 1;
+    const int32_t *ot = offy + ((bp >> 12) & 7) * kTapEntries;
+    v2s r[2];
+    if (interior) cdef_quad_packed<false>(p, ot, pri, S.ysec, pshift, S.ysshift, par ? 3 : 4, par ? 3 : 2, r);
+    else cdef_quad_packed<true>(p, ot, pri, S.ysec, pshift, S.ysshift, par ? 3 : 4, par ? 3 : 2, r);
+    o[0] = r[0].x; o[1] = r[0].y; o[2] = r[1].x; o[3] = r[1].y;
+  }
+  sink(fy, fx, o);
+}
+// chroma 2 x 32x32: q in [0, 2 * 32 * 8) -> (plane, row, group of 4 columns); sink(pl, fy, fx, o)
+template <int CS, class Sink>
+__device__ __forceinline__ void cdef_chroma_item(int q, const uint16_t *tu0, const uint16_t *tv0, int sbx, int sby, int w, int h, const CdefSb &S, bool interior,
+                                                 const uint8_t *bskip, const uint32_t *bpar, const int32_t *offc, Sink &&sink) {
+  const int cw = w / 2, chh = h / 2;
+  const int pl = q >> 8, r = (q >> 3) & 31, c = (q & 7) * 4;
+  const int fy = sby * 32 + r, fx = sbx * 32 + c;
+  if (fy >= chh || fx >= cw) return;
+  const int b = (r >> 2) * 8 + (c >> 2);
+  const bool skip = !S.enabled || bskip[b];
+  const uint16_t *p = (pl ? tv0 : tu0) + r * CS + c;
+  int o[4];
+  if (skip) { o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; o[3] = p[3]; }
+  else {
+    const int32_t *ot = offc + (S.upri == 0 ? 0 : (int)((bpar[b] >> 16) & 7)) * kTapEntries;
+    v2s r[2];
+    if (interior) cdef_quad_packed<false>(p, ot, S.upri, S.usec, S.upshift, S.usshift, S.upar ? 3 : 4, S.upar ? 3 : 2, r);
+    else cdef_quad_packed<true>(p, ot, S.upri, S.usec, S.upshift, S.usshift, S.upar ? 3 : 4, S.upar ? 3 : 2, r);
+    o[0] = r[0].x; o[1] = r[0].y; o[2] = r[1].x; o[3] = r[1].y;
+  }
+  sink(pl, fy, fx, o);
+}
+
+// The filter loops of the two kernels that store: dy / du, dv: frame f's output planes.
 // luma 64x64 -> 16 samples per lane (4 rows x 4 columns)
 template <typename Pix, int YS>
 __device__ __forceinline__ void cdef_filter_luma(const uint16_t *ty0, Pix *dy, int stride_y, int sbx, int sby, int w, int h, const CdefSb &S, bool interior,
                                                  const uint8_t *bskip, const uint32_t *bpar, const int32_t *offy, int tid) {
-  for (int q = tid; q < 64 * 16; q += 256) {         // q -> (row, group of 4 columns)
-    const int r = q >> 4, c = (q & 15) * 4;
-    const int fy = sby * 64 + r, fx = sbx * 64 + c;
-    if (fy >= h || fx >= w) continue;
-    const int b = (r >> 3) * 8 + (c >> 3);
-    const bool skip = !S.enabled || bskip[b];
-    const uint16_t *p = ty0 + r * YS + c;
-    int o[4];
-    if (skip) { o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; o[3] = p[3]; }
-    else {
-      const uint32_t bp = bpar[b];
-      const int pri = bp & 255, pshift = (bp >> 8) & 15, par = (bp >> 15) & 1;
-      const int32_t *ot = offy + ((bp >> 12) & 7) * kTapEntries;
-      v2s r[2];
-      if (interior) cdef_quad_packed<false>(p, ot, pri, S.ysec, pshift, S.ysshift, par ? 3 : 4, par ? 3 : 2, r);
-      else cdef_quad_packed<true>(p, ot, pri, S.ysec, pshift, S.ysshift, par ? 3 : 4, par ? 3 : 2, r);
-      o[0] = r[0].x; o[1] = r[0].y; o[2] = r[1].x; o[3] = r[1].y;
-    }
-    cdef_store4<Pix>(dy + row_off(fy, stride_y) + fx, o);
-  }
+  for (int q = tid; q < 64 * 16; q += 256)
+    cdef_luma_item<YS>(q, ty0, sbx, sby, w, h, S, interior, bskip, bpar, offy,
+                       [&](int fy, int fx, const int (&o)[4]) { cdef_store4<Pix>(dy + row_off(fy, stride_y) + fx, o); });
 }
 // chroma 2 x 32x32 -> 2 x 4 samples per lane
 template <typename Pix, int CS>
 __device__ __forceinline__ void cdef_filter_chroma(const uint16_t *tu0, const uint16_t *tv0, Pix *du, Pix *dv, int stride_uv, int sbx, int sby, int w, int h, const CdefSb &S,
                                                    bool interior, const uint8_t *bskip, const uint32_t *bpar, const int32_t *offc, int tid) {
+  for (int q = tid; q < 2 * 32 * 8; q += 256)
+    cdef_chroma_item<CS>(q, tu0, tv0, sbx, sby, w, h, S, interior, bskip, bpar, offc,
+                         [&](int pl, int fy, int fx, const int (&o)[4]) { cdef_store4<Pix>((pl ? dv : du) + row_off(fy, stride_uv) + fx, o); });
+}
+
+// Staging of a superblock from whole planes in memory (k_cdef, k_cdef_search): luma 68x68 into ty (rows YS apart) and chroma 36x36 x 2
+// into tc (rows CSZ apart), local (0, 0) = picture (sb * 64 - 2, sb * 64 - 2) (chroma: sb * 32 - 2); sy / su / sv: frame f's planes.
+// interior: every tap of the superblock lies inside the picture; otherwise what lies outside is stored as 0xFFFF.
+template <typename Pix, int YS, int CSZ, int TCN>
+__device__ __forceinline__ void cdef_stage_tiles(uint16_t *ty, uint16_t (*tc)[TCN], const Pix *sy, const Pix *su, const Pix *sv, int stride_y, int stride_uv, int sbx, int sby,
+                                                 int w, int h, bool interior, int tid) {
   const int cw = w / 2, chh = h / 2;
-  for (int q = tid; q < 2 * 32 * 8; q += 256) {
-    const int pl = q >> 8, r = (q >> 3) & 31, c = (q & 7) * 4;
-    const int fy = sby * 32 + r, fx = sbx * 32 + c;
-    if (fy >= chh || fx >= cw) continue;
-    const int b = (r >> 2) * 8 + (c >> 2);
-    const bool skip = !S.enabled || bskip[b];
-    const uint16_t *p = (pl ? tv0 : tu0) + r * CS + c;
-    int o[4];
-    if (skip) { o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; o[3] = p[3]; }
-    else {
-      const int32_t *ot = offc + (S.upri == 0 ? 0 : (int)((bpar[b] >> 16) & 7)) * kTapEntries;
-      v2s r[2];
-      if (interior) cdef_quad_packed<false>(p, ot, S.upri, S.usec, S.upshift, S.usshift, S.upar ? 3 : 4, S.upar ? 3 : 2, r);
-      else cdef_quad_packed<true>(p, ot, S.upri, S.usec, S.upshift, S.usshift, S.upar ? 3 : 4, S.upar ? 3 : 2, r);
-      o[0] = r[0].x; o[1] = r[0].y; o[2] = r[1].x; o[3] = r[1].y;
+  if (interior) {
+    // no bounds to check: 4-sample aligned loads starting 4 samples left of the block (18 per row luma, 10 chroma); the tile
+    // keeps only the 2-sample halo, so local column = aligned column - 2.  The four samples are two uint16 pairs = two dword
+    // stores: samples 0,1 go to tile columns 4g - 2, 4g - 1 and samples 2,3 to 4g, 4g + 1 (even columns, even row stride);
+    // the first pair of a row and the last lie outside.  All of a lane's loads (5 luma + 3 chroma items) are issued before
+    // its first LDS store, so their latencies overlap instead of adding up.
+    constexpr int NY = 68 * 18, NC = 2 * 36 * 10, KY = (NY + 255) / 256, KC = (NC + 255) / 256;
+    uint2 vy[KY], vc[KC];
+#pragma unroll
+    for (int k = 0; k < KY; k++) {
+      const int i = tid + 256 * k;
+      if (i < NY) {
+        const int r = i / 18, g = i - r * 18;
+        const Pix *q = sy + row_off(sby * 64 - 2 + r, stride_y) + sbx * 64 - 4 + g * 4;
+        if constexpr (sizeof(Pix) == 1) vy[k].x = *reinterpret_cast<const uint32_t *>(q);
+        else vy[k] = *reinterpret_cast<const uint2 *>(q);
+      }
     }
-    cdef_store4<Pix>((pl ? dv : du) + row_off(fy, stride_uv) + fx, o);
+#pragma unroll
+    for (int k = 0; k < KC; k++) {
+      const int i = tid + 256 * k;
+      if (i < NC) {
+        const int pl = i / 360, j = i - pl * 360, r = j / 10, g = j - r * 10;
+        const Pix *q = (pl ? sv : su) + row_off(sby * 32 - 2 + r, stride_uv) + sbx * 32 - 4 + g * 4;
+        if constexpr (sizeof(Pix) == 1) vc[k].x = *reinterpret_cast<const uint32_t *>(q);
+        else vc[k] = *reinterpret_cast<const uint2 *>(q);
+      }
+    }
+    auto pairs = [](uint2 v, uint32_t &lo, uint32_t &hi) {
+      if constexpr (sizeof(Pix) == 1) { lo = __builtin_amdgcn_perm(0u, v.x, 0x0c010c00u); hi = __builtin_amdgcn_perm(0u, v.x, 0x0c030c02u); }
+      else { lo = v.x; hi = v.y; }
+    };
+#pragma unroll
+    for (int k = 0; k < KY; k++) {
+      const int i = tid + 256 * k;
+      if (i < NY) {
+        const int r = i / 18, g = i - r * 18;
+        uint32_t lo, hi;
+        pairs(vy[k], lo, hi);
+        uint32_t *d = reinterpret_cast<uint32_t *>(ty + r * YS + g * 4 - 2);
+        if (g > 0) d[0] = lo;
+        if (g < 17) d[1] = hi;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < KC; k++) {
+      const int i = tid + 256 * k;
+      if (i < NC) {
+        const int pl = i / 360, j = i - pl * 360, r = j / 10, g = j - r * 10;
+        uint32_t lo, hi;
+        pairs(vc[k], lo, hi);
+        uint32_t *d = reinterpret_cast<uint32_t *>(tc[pl] + r * CSZ + g * 4 - 2);
+        if (g > 0) d[0] = lo;
+        if (g < 9) d[1] = hi;
+      }
+    }
+  } else {
+    for (int i = tid; i < 68 * 68; i += 256) {
+      const int r = i / 68, c = i - r * 68;
+      const int fy = sby * 64 - 2 + r, fx = sbx * 64 - 2 + c;
+      ty[r * YS + c] = (fy >= 0 && fy < h && fx >= 0 && fx < w) ? (uint16_t)sy[row_off(fy, stride_y) + fx] : (uint16_t)0xFFFF;
+    }
+    for (int i = tid; i < 2 * 36 * 36; i += 256) {
+      const int pl = i / (36 * 36), j = i - pl * 36 * 36, r = j / 36, c = j - r * 36;
+      const int fy = sby * 32 - 2 + r, fx = sbx * 32 - 2 + c;
+      const Pix *sc = pl ? sv : su;
+      tc[pl][r * CSZ + c] = (fy >= 0 && fy < chh && fx >= 0 && fx < cw) ? (uint16_t)sc[row_off(fy, stride_uv) + fx] : (uint16_t)0xFFFF;
+    }
   }
 }
 

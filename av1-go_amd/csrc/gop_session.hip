@@ -118,6 +118,10 @@ struct Slot {
   // the records while the filters of batch t + 1 run — and their pinned mirrors, copied behind the filters in front of lr_down
   void *d_lr_units[3] = {}, *h_lr_units[3] = {}, *d_lr_cost = nullptr, *d_lr_choice = nullptr, *h_lr_choice = nullptr;
   hipEvent_t lr_down = nullptr;
+  // cdef_search: the batch's cost table, the chosen strength records and index bytes — per SLOT for the same reason — the indices'
+  // pinned mirror, copied behind the filters in front of cdef_down
+  void *d_cdef_cost = nullptr, *d_cdef_rec = nullptr, *d_cdef_idx = nullptr, *h_cdef_idx = nullptr;
+  hipEvent_t cdef_down = nullptr;
   int frame_type = 0;
   int q = 0;                          // the batch's quantiser (av1mi_gop_set_base_q_idx) and what the policy derives from it for its frame type
   av1mi_frame_params params{};
@@ -289,6 +293,12 @@ int slot_buffers(av1mi_gop *g, Slot &s) {
     G_TRY(dev_alloc(g, &s.d_lr_choice, n)); G_TRY(host_alloc(g, &s.h_lr_choice, n));
     G_HIP(hipEventCreateWithFlags(&s.lr_down, hipEventDisableTiming));
   }
+  if (c.cdef_search) {
+    const size_t nsb = (size_t)S * ((c.width + 63) / 64) * ((c.height + 63) / 64);
+    G_TRY(dev_alloc(g, &s.d_cdef_cost, av1mi_cdef_search_table_bytes(c.width, c.height, S)));
+    G_TRY(dev_alloc(g, &s.d_cdef_rec, nsb * 4)); G_TRY(dev_alloc(g, &s.d_cdef_idx, nsb)); G_TRY(host_alloc(g, &s.h_cdef_idx, nsb));
+    G_HIP(hipEventCreateWithFlags(&s.cdef_down, hipEventDisableTiming));
+  }
   if (c.quality_stats) {
     G_TRY(host_alloc(g, &s.h_quality, (size_t)S * 3 * sizeof(av1mi_quality)));
     G_HIP(hipEventCreateWithFlags(&s.quality_done, hipEventDisableTiming));
@@ -421,6 +431,7 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
     if (units(vw) != units(c->width) || units(vh) != units(c->height) || units((vw + 1) / 2) != units(c->width / 2) || units((vh + 1) / 2) != units(c->height / 2))
       return WHY("lr_search at a true size %dx%d whose restoration units differ from those of the coded size %dx%d is not built", vw, vh, c->width, c->height);
   }
+  if (c->cdef_search < 0 || c->cdef_search > 3) return WHY("cdef_search %d unknown (0 the policy's strength set in every superblock, 1 .. 3 = cdef_bits: one of 2, 4, 8 sets chosen per superblock)", c->cdef_search);
   if (c->tone_map != 0 && c->tone_map != 1) return WHY("tone_map %d unknown (0 none, 1 BT.2390)", c->tone_map);
   if (c->tone_map_peak && !c->tone_map) return WHY("tone_map_peak %d needs tone_map", c->tone_map_peak);
   if (c->tone_map && c->bit_depth != 10) return WHY("tone_map needs bit_depth 10, not %d: an HDR10 source has 10 bits", c->bit_depth);
@@ -569,7 +580,7 @@ void av1mi_gop_close(av1mi_gop *g) {
   if (g->up) { (void)hipStreamSynchronize(g->up); (void)hipStreamDestroy(g->up); }
   if (g->down) { (void)hipStreamSynchronize(g->down); (void)hipStreamDestroy(g->down); }
   for (Slot &s : g->slot)
-    for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done, s.quality_done, s.grain_done, s.lr_down })
+    for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done, s.quality_done, s.grain_done, s.lr_down, s.cdef_down })
       if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : { g->store[0].filled, g->store[0].read_done, g->store[1].filled, g->store[1].read_done, g->scene_done, g->put_done[0], g->put_done[1], g->put_done[2] })
     if (e) (void)hipEventDestroy(e);
@@ -806,7 +817,8 @@ static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
   // a true size that is not a multiple of 8: the decoder's restoration clamps at the true last column / row (CDEF reads the planes
   // as they are: it works on the coded size in a decoder too)
   const bool padded = g->vw != w || g->vh != h;
-  if (!padded) {
+  // cdef_search: the search reads WHOLE deblocked planes, so every size takes the kernels one by one
+  if (!padded && !c.cdef_search) {
     // deblocking and CDEF in one kernel: the deblocked samples stay in LDS, and d_dbl receives only the rows restoration reads
     av1mi_deblock_cdef_job fj;
     memset(&fj, 0, sizeof(fj));
@@ -833,6 +845,16 @@ static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
     cj.d_dst_y = g->d_cdef[0]; cj.d_dst_u = g->d_cdef[1]; cj.d_dst_v = g->d_cdef[2];
     cj.d_sb_strength = (const uint8_t *)g->d_cdef_sb[s.frame_type]; cj.sb_frame_stride = 0;
     cj.d_skip8 = skip8; cj.skip_frame_stride = skip_frame_stride;
+    if (c.cdef_search) {      // a strength set per superblock and frame against the source; CDEF then runs with the chosen records
+      av1mi_cdef_search_job sj;
+      memset(&sj, 0, sizeof(sj));
+      sj.width = w; sj.height = h; sj.bit_depth = bd; sj.nframes = S; sj.stride_y = cj.stride_y; sj.stride_uv = cj.stride_uv;
+      sj.d_src_y = cj.d_src_y; sj.d_src_u = cj.d_src_u; sj.d_src_v = cj.d_src_v; sj.d_orig_y = src[0]; sj.d_orig_u = src[1]; sj.d_orig_v = src[2];
+      sj.d_skip8 = skip8; sj.skip_frame_stride = skip_frame_stride; sj.true_width = g->vw; sj.true_height = g->vh; sj.bits = c.cdef_search; sj.params = &P;
+      sj.d_sse = (uint64_t *)s.d_cdef_cost; sj.d_strength = (uint8_t *)s.d_cdef_rec; sj.d_idx = (uint8_t *)s.d_cdef_idx;
+      G_TRY(av1mi_cdef_search(g->ctx, &sj));
+      cj.d_sb_strength = sj.d_strength; cj.sb_frame_stride = (size_t)((w + 63) / 64) * ((h + 63) / 64);
+    }
     G_TRY(av1mi_cdef_frames(g->ctx, &cj));
   }
   if (padded)
@@ -870,6 +892,11 @@ static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
     for (int p = 0; p < 3; p++) G_HIP(hipMemcpyAsync(s.h_lr_units[p], s.d_lr_units[p], (size_t)S * g->lr_units[p] * 8, hipMemcpyDeviceToHost, g->down));
     G_HIP(hipMemcpyAsync(s.h_lr_choice, s.d_lr_choice, (size_t)S * (g->lr_units[0] + g->lr_units[1] + g->lr_units[2]), hipMemcpyDeviceToHost, g->down));
     G_HIP(hipEventRecord(s.lr_down, g->down));
+  }
+  if (c.cdef_search) {    // the indices to the host with every batch: a byte per superblock, for the host writer and the statistics
+    G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
+    G_HIP(hipMemcpyAsync(s.h_cdef_idx, s.d_cdef_idx, (size_t)S * ((w + 63) / 64) * ((h + 63) / 64), hipMemcpyDeviceToHost, g->down));
+    G_HIP(hipEventRecord(s.cdef_down, g->down));
   }
   if (s.symbols_down) {
     G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
@@ -938,6 +965,7 @@ static int start_coder(av1mi_gop *g, Slot &s) {
   ej.d_lr_on = (const uint8_t *)s.d_lr_on;
   av1mi_av1_entropy_units eu;
   if (c.lr_search) for (int p = 0; p < 3; p++) { eu.d_units[p] = (const int8_t *)s.d_lr_units[p]; eu.frame_stride[p] = (size_t)g->lr_units[p]; }
+  const av1mi_av1_entropy_cdef ec = { c.cdef_search, (const uint8_t *)s.d_cdef_idx, (size_t)((c.width + 63) / 64) * ((c.height + 63) / 64) };
   ej.visible_width = g->vw; ej.visible_height = g->vh;
   ej.key_rows32 = s.frame_type == 0 && g->key32 ? g->key_rows32 : 0;
   memcpy(ej.lr_unit_y, P.lr_unit_y, 8); memcpy(ej.lr_unit_uv, P.lr_unit_uv, 8);
@@ -946,12 +974,12 @@ static int start_coder(av1mi_gop *g, Slot &s) {
     // tokenizer + chains of THIS batch on the side stream; the range coder of the PREVIOUS batch on the main stream, behind this
     // batch's filters: two queues that are both busy all the time ((pipeline + filters + coder) beside (tokenizer + chains)) instead of
     // a short one and a long one
-    G_TRY(av1mi::av1_entropy_front(g->ctx, &ej, side, &s.ent_ticket, c.lr_search ? &eu : nullptr));
+    G_TRY(av1mi::av1_entropy_front(g->ctx, &ej, side, &s.ent_ticket, c.lr_search ? &eu : nullptr, c.cdef_search ? &ec : nullptr));
     Slot &prev = g->slot[(g->submitted + kSlots - 1) % kSlots];
     if (g->submitted > 0 && prev.ent_ticket >= 0) G_TRY(finish_entropy(g, prev, main));
   } else {
     const av1mi::Av1EntMirrors m = entropy_mirrors(g, s);
-    G_TRY(av1mi::av1_entropy_submit(g->ctx, &ej, side, back, &m, c.lr_search ? &eu : nullptr));
+    G_TRY(av1mi::av1_entropy_submit(g->ctx, &ej, side, back, &m, c.lr_search ? &eu : nullptr, c.cdef_search ? &ec : nullptr));
     G_TRY(entropy_results(g, s, back));
   }
   s.ent_pending = true;
@@ -1106,6 +1134,11 @@ int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out) {
     G_HIP(hipEventSynchronize(s.lr_down));
     for (int p = 0; p < 3; p++) { out->lr_units[p] = (const int8_t *)s.h_lr_units[p]; out->lr_units_per_frame[p] = g->lr_units[p]; }
     out->lr_choice = (const uint8_t *)s.h_lr_choice;
+  }
+  if (g->cfg.cdef_search) {
+    G_HIP(hipEventSynchronize(s.cdef_down));
+    out->cdef_bits = g->cfg.cdef_search; out->cdef_idx = (const uint8_t *)s.h_cdef_idx;
+    av1mi_cdef_search_sets(&s.params, out->cdef_bits, out->cdef_y, out->cdef_uv);
   }
   if (g->cfg.quality_stats) { G_HIP(hipEventSynchronize(s.quality_done)); out->quality = (const av1mi_quality *)s.h_quality; }
   if (g->cfg.denoise && s.has_grain) { G_HIP(hipEventSynchronize(s.grain_done)); out->grain = (const av1mi_grain_record *)s.h_grain; out->grain_cov = (const av1mi_grain_cov_record *)s.h_grain_cov; }

@@ -18,7 +18,8 @@ namespace av1 {
 // true when the description stays inside the GPU coder's tool set (what the GPU block pipeline produces)
 bool opstream_supported(const av1mi_obu_frame &f, std::string *why) {
   auto no = [&](const char *m) { if (why) *why = m; return false; };
-  if (f.cdef_bits || f.reduced_tx_set || f.disable_cdf_update) return no("cdef_bits / reduced_tx_set / disable_cdf_update must be 0");
+  if (f.cdef_bits < 0 || f.cdef_bits > 3) return no("cdef_bits outside 0 .. 3");      // (a null cdef_idx is index 0 everywhere, as in the host writers)
+  if (f.reduced_tx_set || f.disable_cdf_update) return no("reduced_tx_set / disable_cdf_update must be 0");
   if (f.tile_cols_log2 >= 0 || f.tile_rows_log2 >= 0) return no("one superblock per tile only");
   if (f.angle_y || f.angle_uv || f.cfl_alpha || f.tx_type || f.is_inter) return no("angle deltas, chroma from luma, transform types and intra blocks in inter frames are host-writer only");
   if (f.frame_type == 0 && f.skip) return no("key frames are coded with skip = 0");
@@ -57,11 +58,17 @@ struct WaveLoop {
     return run;
   }
   int first(Var<int> &v) { return v.v[0]; }
+  uint64_t ballot(Var<int> &v) {
+    uint64_t m = 0;
+    for (int lane = 0; lane < av1ops::kLanes32; lane++) m |= (uint64_t)(v.v[lane] != 0) << lane;
+    return m;
+  }
 };
 void frame_view_of(const av1mi_obu_frame &f, av1ops::FrameView *v) {
   memset(v, 0, sizeof(*v));
   v->w8 = f.width / 8; v->h8 = f.height / 8; v->key = f.frame_type == 0;
   v->y_mode = f.y_mode; v->uv_mode = f.uv_mode; v->mv = f.mv; v->skip = f.skip; v->lev_y = f.lev_y; v->lev_u = f.lev_u; v->lev_v = f.lev_v;
+  v->cdef_bits = f.cdef_bits; v->cdef_idx = f.cdef_bits ? f.cdef_idx : nullptr;
   for (int p = 0; p < 3; p++) {
     v->lr_on[p] = f.lr_type[p] == 1;
     const int ph = p ? (visible_height(f) + 1) >> 1 : visible_height(f), pw = p ? (visible_width(f) + 1) >> 1 : visible_width(f);
@@ -157,7 +164,7 @@ bool opstream_tiles(const av1mi_obu_frame &f, std::vector<std::vector<uint8_t>> 
         int ops = 0;
         for (int zi = 0; zi < kBlocksPerTile; zi++) {
           Sink k = { rec.data(), cnt.data(), zi, 0, 0, false };
-          tok_block(v, k, ts, sbr, sbc, zi, mem8[0].sums);
+          tok_block(v, k, ts, sbr, sbc, zi, mem8[0].sums, -1);
           st_rec = std::max(st_rec, k.nrec); ops += k.n;
         }
         for (uint8_t c : cnt) st_cnt = std::max(st_cnt, (int)c);

@@ -18,6 +18,11 @@ void DescribeSessionFrame(const av1mi_gop_frame &fr, int seg, int width, int hei
   f.visible_width = visible_width; f.visible_height = visible_height;
   for (int i = 0; i < 4; i++) f.lf_level[i] = p.lf_level[i];
   f.lf_sharpness = p.lf_sharpness; f.cdef_damping = p.cdef_damping; f.cdef_bits = 0; f.cdef_y[0] = p.cdef_y; f.cdef_uv[0] = p.cdef_uv;
+  if (fr.cdef_bits) {      // a session with the CDEF search: the batch's strength sets and the segment's index per superblock
+    f.cdef_bits = fr.cdef_bits;
+    memcpy(f.cdef_y, fr.cdef_y, 8); memcpy(f.cdef_uv, fr.cdef_uv, 8);
+    if (fr.cdef_idx) f.cdef_idx = fr.cdef_idx + (size_t)seg * ((width + 63) / 64) * ((height + 63) / 64);
+  }
   auto units = [&](int n) { const int u = (n + p.lr_unit_size / 2) / p.lr_unit_size; return u > 1 ? u : 1; };
   const int vw = visible_width ? visible_width : width, vh = visible_height ? visible_height : height;      // the units tile the TRUE frame
   const size_t uy = (size_t)units(vh) * units(vw), uc = (size_t)units((vh + 1) / 2) * units((vw + 1) / 2);

@@ -219,6 +219,58 @@ typedef struct av1mi_deblock_cdef_job {
 } av1mi_deblock_cdef_job;
 int av1mi_deblock_cdef_frames(av1mi_ctx *ctx, const av1mi_deblock_cdef_job *job);
 
+/* ---- CDEF search (policy, non-normative): one of 2, 4 or 8 CDEF strength sets chosen per 64 x 64 superblock by squared error
+ * against the source.  The frame header lists the sets (cdef_bits = bits), a superblock's index is `bits` literal bits.
+ *
+ * The candidates.  From the frame's policy set (av1mi_frame_params.cdef_y / cdef_uv): luma (P, S), chroma (p, s); a primary strength
+ * is 0 .. 15, a secondary value the 2-bit code (3 means strength 4).  With dbl(x) = min(15, max(1, 2 x)) and up(x) = min(3, x + 1):
+ *     c   luma                    chroma
+ *     0   (P, S)                  (p, s)                    the policy's set
+ *     1   (0, 0)                  (0, 0)                    unfiltered
+ *     2   (P >> 1, S)             (p >> 1, s)
+ *     3   (dbl(P), S)             (dbl(p), s)
+ *     4   (P, up(S))              (p, up(s))
+ *     5   (P, 0)                  (p, 0)
+ *     6   (dbl(P), up(S))         (dbl(p), up(s))
+ *     7   (dbl(dbl(P)), up(S))    (dbl(dbl(p)), up(s))
+ * bits = 1, 2, 3 takes the first 1 << bits sets.  Sets that come out equal are legal and stay where they are; they never win a tie.
+ * The damping is the policy's.  av1mi_cdef_search_sets writes the sets in the (primary << 2) | secondary form of
+ * av1mi_frame_params.cdef_y (entries from 1 << bits on: 0): plain host code, no device; AV1MI_E_INVAL for a null pointer or bits
+ * outside 1 .. 3.
+ *
+ * The cost of candidate c for a superblock: SSE_c, the 64-bit sum over the three planes of the squared difference between the source
+ * and the CDEF output with set c, over the superblock's samples INSIDE THE TRUE FRAME SIZE (chroma: the true size halved, rounded up).
+ * Skipped 8 x 8 blocks are left unfiltered, as the filter leaves them: they count the same for every c.  The index costs the same
+ * literal bits whatever its value, so there is no lambda: the lowest SSE_c wins, on a tie the lowest c.  A superblock whose blocks
+ * are all skipped therefore gets 0 (the syntax codes no index for it).
+ *
+ * av1mi_cdef_search: geometry, d_src_* (the deblocked planes), d_skip8 and skip_frame_stride as in av1mi_cdef_job; d_orig_*: the
+ * source planes, same geometry; true_width / true_height: the true frame size (0 = width / height; at most width / height, and more
+ * than width - 8 / height - 8); params: the frame's policy numbers (cdef_y, cdef_uv, cdef_damping are read).  Outputs, device memory:
+ *   d_sse        uint64 SSE[frame][sb][8], av1mi_cdef_search_table_bytes() bytes, 8-byte aligned; columns from 1 << bits on hold 0
+ *   d_strength   the chosen set's four bytes { y_pri, y_sec, uv_pri, uv_sec } per [frame][sb], 4-byte aligned: what
+ *                av1mi_cdef_job.d_sb_strength takes with sb_frame_stride = the superblocks of a frame
+ *   d_idx        the chosen index, one byte per [frame][sb]
+ * One launch (k_cdef_search, a workgroup per superblock: no atomics, no zeroing), asynchronous on the context's stream, under
+ * AV1MI_K_CDEF in the profile. */
+struct av1mi_frame_params;      /* below: the session's policy numbers for one frame */
+typedef struct av1mi_cdef_search_job {
+  int width, height, bit_depth, nframes;
+  int stride_y, stride_uv;
+  const void *d_src_y, *d_src_u, *d_src_v;
+  const void *d_orig_y, *d_orig_u, *d_orig_v;
+  const uint8_t *d_skip8; size_t skip_frame_stride;
+  int true_width, true_height;
+  int bits;
+  const struct av1mi_frame_params *params;
+  uint64_t *d_sse;
+  uint8_t *d_strength;
+  uint8_t *d_idx;
+} av1mi_cdef_search_job;
+int av1mi_cdef_search_sets(const struct av1mi_frame_params *params, int bits, uint8_t y[8], uint8_t uv[8]);
+size_t av1mi_cdef_search_table_bytes(int width, int height, int nframes);
+int av1mi_cdef_search(av1mi_ctx *ctx, const av1mi_cdef_search_job *job);
+
 /* ---- K7: loop restoration (AV1 spec §7.17) of one plane of nframes frames stacked vertically.  d_cdef: the CDEF
  * output, d_deblocked: the deblocked (pre-CDEF) plane used beyond stripe boundaries, d_out: the restored plane
  * (distinct from both).  subsampled = 1 for the chroma planes of 4:2:0 (32-row stripes offset by 4), 0 for luma.
@@ -424,6 +476,13 @@ typedef struct av1mi_av1_entropy_job {
  * record is read as one word); anything else is AV1MI_E_INVAL.  units = NULL: av1mi_av1_entropy_encode_on. */
 typedef struct av1mi_av1_entropy_units { const int8_t *d_units[3]; size_t frame_stride[3]; } av1mi_av1_entropy_units;
 int av1mi_av1_entropy_encode_units(av1mi_ctx *ctx, const av1mi_av1_entropy_job *job, const av1mi_av1_entropy_units *units, void *stream);
+/* The superblocks' CDEF indices for a job (the CDEF search's choice), beside the job for the same reason.  cdef_bits 1 .. 3: every
+ * tile codes its superblock's index d_idx[frame * frame_stride + sb] (sb in raster order) as cdef_bits literal bits behind the skip
+ * symbol of its first block that is not skipped; d_idx null = index 0 everywhere.  cdef_bits 0 (or cdef = NULL): nothing is coded.
+ * Anything else is AV1MI_E_INVAL.  Either side struct may be NULL. */
+typedef struct av1mi_av1_entropy_cdef { int cdef_bits; const uint8_t *d_idx; size_t frame_stride; } av1mi_av1_entropy_cdef;
+int av1mi_av1_entropy_encode_sides(av1mi_ctx *ctx, const av1mi_av1_entropy_job *job, const av1mi_av1_entropy_units *units,
+                                   const av1mi_av1_entropy_cdef *cdef, void *stream);
 int av1mi_av1_entropy_encode(av1mi_ctx *ctx, const av1mi_av1_entropy_job *job);
 /* the same on another HIP stream of the caller's (hipStream_t passed as void *; NULL = the context's stream) */
 int av1mi_av1_entropy_encode_on(av1mi_ctx *ctx, const av1mi_av1_entropy_job *job, void *stream);
@@ -940,6 +999,14 @@ typedef struct av1mi_gop_config {
    * av1mi_gop_frame.lr_units carries them.  Per slot: the three unit arrays, the cost table and the index bytes.  Refused where the
    * units of the coded size and of the true size form different grids.  With 0 nothing of this is allocated or launched. */
   int lr_search;
+  /* CDEF search ("CDEF search"): 0 = every superblock is filtered with the policy's one strength set and the stream carries
+   * cdef_bits = 0, as ever; N = 1, 2, 3 = cdef_bits = N: one of the first 1 << N sets of av1mi_cdef_search_sets is chosen per 64 x 64
+   * superblock and frame against the source.  Every frame size then takes the filters one by one on the main stream —
+   * av1mi_deblock_frames per plane, av1mi_cdef_search (k_cdef_search), av1mi_cdef_frames with the chosen records — because the search
+   * reads whole deblocked planes; the GPU coder codes the indices, and av1mi_gop_frame.cdef_bits / cdef_y / cdef_uv / cdef_idx carry
+   * what the frame header and the host writer need.  Per slot: the cost table, the strength records, the index bytes and their pinned
+   * mirror, an event.  Anything outside 0 .. 3 is refused.  With 0 nothing of this is allocated or launched. */
+  int cdef_search;
 } av1mi_gop_config;
 
 /* The source layout: what a session opened with a config is FED, as one description.  Everything a caller sizes or strides by — the
@@ -1017,6 +1084,12 @@ typedef struct av1mi_gop_frame {    /* one collected frame batch; host pointers 
   const int8_t *lr_units[3];
   int lr_units_per_frame[3];
   const uint8_t *lr_choice;
+  /* av1mi_gop_config.cdef_search: cdef_bits of this batch's frames, their 1 << cdef_bits strength sets (av1mi_cdef_search_sets of
+   * `params`: the batch's frame type and quantiser) and the chosen indices [segment][superblock in raster order] in pinned memory: what
+   * av1mi_obu_frame.cdef_bits / cdef_y / cdef_uv / cdef_idx take for a segment.  0 / NULL when the option is off */
+  int cdef_bits;
+  uint8_t cdef_y[8], cdef_uv[8];
+  const uint8_t *cdef_idx;
 } av1mi_gop_frame;
 
 typedef struct av1mi_gop av1mi_gop;
