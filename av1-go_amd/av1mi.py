@@ -894,32 +894,67 @@ class Context:
     def intra_encode(self, job):
         self._chk(self.lib.av1mi_intra_encode(self.h, C.byref(job)))
 
-    def intra_encode_arrays(self, Y, U, V, bd, bs, qindex, open_loop=False):
-        """convenience for tests: Y/U/V are [frames, h, w] arrays; returns dict of outputs like the oracle's"""
+    def intra_encode_arrays(self, Y, U, V, bd, bs, qindex, open_loop=False, stride_y=None, stride_uv=None, frame_rows=None,
+                            modes_frame_stride=None):
+        """convenience for tests: Y/U/V are [frames, h, w] arrays; returns dict of outputs like the oracle's.  The job's geometry
+        (av1mi_intra_job; defaults: compact): stride_y / stride_uv lay the rows of every plane that many samples apart, frame_rows
+        makes the job the top band of frames that many luma rows tall (the levels of consecutive frames lie as far apart as those
+        frames' samples), modes_frame_stride lays the frames' mode bytes that far apart.  The sources are uploaded into that layout
+        and every output buffer is pre-filled with a sentinel (0xA5 bytes, which no mode takes).  rec_*, lev_* and modes_* are the
+        compact views; what lies outside them comes back as the kernels left it, each key only where the layout has such bytes:
+        rec_pad_* [frames, rows, stride - width] the row padding of the band, rec_gap_* [frames, frame rows - rows, stride] the rows
+        between bands, lev_gap_* [frames, n] the levels between the frames' blocks, modes_gap_y / _uv [frames, stride - blocks]."""
         dt = np.uint8 if bd == 8 else np.uint16
-        Y, U, V = (np.ascontiguousarray(a, dt) for a in (Y, U, V))
-        nf, h, w = Y.shape
-        nb = (h // bs) * (w // bs)
-        bufs = {}
-        job = IntraJob(w, h, bd, nf, qindex, bs, w, w // 2)
+        P = [np.ascontiguousarray(a, dt) for a in (Y, U, V)]
+        nf, h, w = P[0].shape
+        nb, cs = (h // bs) * (w // bs), bs // 2
+        strides = [w if stride_y is None else int(stride_y)] + [w // 2 if stride_uv is None else int(stride_uv)] * 2
+        job = IntraJob(w, h, bd, nf, qindex, bs, strides[0], strides[1])
         job.open_loop = 1 if open_loop else 0
-        for name, arr in (("src_y", Y), ("src_u", U), ("src_v", V)):
-            bufs[name] = self.to_device(arr)
-        for name, n in (("rec_y", Y.nbytes), ("rec_u", U.nbytes), ("rec_v", V.nbytes), ("lev_y", Y.size * 2), ("lev_u", U.size * 2),
-                        ("lev_v", V.size * 2), ("modes_y", nf * nb), ("modes_uv", nf * nb)):
-            bufs[name] = self.alloc(n)
-            self.memset(bufs[name], 0, n)
-        for name, b in bufs.items():
-            setattr(job, "d_" + name, b.ptr)
-        self.intra_encode(job)
-        cs = bs // 2
-        out = dict(rec_y=bufs["rec_y"].download(Y.shape, dt), rec_u=bufs["rec_u"].download(U.shape, dt),
-                   rec_v=bufs["rec_v"].download(V.shape, dt), lev_y=bufs["lev_y"].download((nf, nb, bs, bs), np.int16),
-                   lev_u=bufs["lev_u"].download((nf, nb, cs, cs), np.int16), lev_v=bufs["lev_v"].download((nf, nb, cs, cs), np.int16),
-                   modes_y=bufs["modes_y"].download((nf, nb), np.uint8), modes_uv=bufs["modes_uv"].download((nf, nb), np.uint8))
-        for b in bufs.values():
-            b.free()
-        return out
+        job.frame_rows = 0 if frame_rows is None else int(frame_rows)
+        job.modes_frame_stride = 0 if modes_frame_stride is None else int(modes_frame_stride)
+        # the buffers' own geometry; an impossible value goes to the library as it is, which refuses the job before anything runs
+        fr = max(job.frame_rows, h)
+        ms = max(job.modes_frame_stride, nb)
+        bufs, shape = {}, {}
+        try:
+            for i, p in enumerate("yuv"):
+                rows, width = P[i].shape[1:]
+                shape[p] = (nf, fr if i == 0 else fr // 2, max(strides[i], width))
+                src = np.zeros(shape[p], dt)
+                src[:, :rows, :width] = P[i]
+                bufs["src_" + p] = self.to_device(src)
+                bufs["rec_" + p] = self.alloc(src.nbytes)
+                bufs["lev_" + p] = self.alloc(nf * shape[p][1] * width * 2)
+            bufs["modes_y"], bufs["modes_uv"] = self.alloc(nf * ms), self.alloc(nf * ms)
+            for name, b in bufs.items():
+                if not name.startswith("src_"):
+                    self.memset(b, 0xA5, b.nbytes)
+                setattr(job, "d_" + name, b.ptr)
+            self.intra_encode(job)
+            out = {}
+            for i, p in enumerate("yuv"):
+                rows, width = P[i].shape[1:]
+                b = bs if i == 0 else cs
+                rec = bufs["rec_" + p].download(shape[p], dt)
+                out["rec_" + p] = np.ascontiguousarray(rec[:, :rows, :width])
+                if shape[p][2] > width:
+                    out["rec_pad_" + p] = np.ascontiguousarray(rec[:, :rows, width:])
+                if shape[p][1] > rows:
+                    out["rec_gap_" + p] = np.ascontiguousarray(rec[:, rows:])
+                lev = bufs["lev_" + p].download((nf, shape[p][1] * width), np.int16)
+                out["lev_" + p] = np.ascontiguousarray(lev[:, :rows * width]).reshape(nf, nb, b, b)
+                if shape[p][1] > rows:
+                    out["lev_gap_" + p] = np.ascontiguousarray(lev[:, rows * width:])
+            for k in ("modes_y", "modes_uv"):
+                m = bufs[k].download((nf, ms), np.uint8)
+                out[k] = np.ascontiguousarray(m[:, :nb])
+                if ms > nb:
+                    out[k.replace("modes_", "modes_gap_")] = np.ascontiguousarray(m[:, nb:])
+            return out
+        finally:
+            for b in bufs.values():
+                b.free()
 
     # ---- inter (P-frame) pipeline
     def inter_encode(self, job):
