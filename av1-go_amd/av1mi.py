@@ -119,6 +119,18 @@ class CdefSearchJob(C.Structure):
                 ("params", C.c_void_p), ("d_sse", C.c_void_p), ("d_strength", C.c_void_p), ("d_idx", C.c_void_p)]
 
 
+class LfSearchJob(C.Structure):
+    """include/av1mi.h av1mi_lf_search_job"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("bit_depth", C.c_int), ("nframes", C.c_int), ("stride_y", C.c_int), ("stride_uv", C.c_int),
+                ("d_rec_y", C.c_void_p), ("d_rec_u", C.c_void_p), ("d_rec_v", C.c_void_p),
+                ("d_orig_y", C.c_void_p), ("d_orig_u", C.c_void_p), ("d_orig_v", C.c_void_p),
+                ("true_width", C.c_int), ("true_height", C.c_int),
+                ("d_mi_y", C.c_void_p), ("d_mi_uv", C.c_void_p), ("mi_stride_y", C.c_int), ("mi_stride_uv", C.c_int),
+                ("mi_frame_stride_y", C.c_size_t), ("mi_frame_stride_uv", C.c_size_t),
+                ("params", C.c_void_p), ("d_scratch", C.c_void_p), ("d_sse", C.c_void_p), ("d_choice", C.c_void_p), ("d_levels", C.c_void_p),
+                ("d_mi_y_out", C.c_void_p), ("d_mi_uv_out", C.c_void_p)]
+
+
 class EntropyCdef(C.Structure):
     """include/av1mi.h av1mi_av1_entropy_cdef"""
     _fields_ = [("cdef_bits", C.c_int), ("d_idx", C.c_void_p), ("frame_stride", C.c_size_t)]
@@ -132,7 +144,7 @@ class GopConfig(C.Structure):
                 ("source_bit_depth", C.c_int), ("store_frames", C.c_int), ("deinterlace", C.c_int), ("denoise", C.c_int),
                 ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int), ("crop_height", C.c_int), ("denoise_range", C.c_int),
                 ("tone_map", C.c_int), ("tone_map_peak", C.c_int), ("grain_cov", C.c_int), ("lr_search", C.c_int),
-                ("cdef_search", C.c_int)]
+                ("cdef_search", C.c_int), ("lf_search", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -148,7 +160,8 @@ class GopFrame(C.Structure):
                 ("payload_bytes", C.c_uint64), ("lr_on", C.c_void_p), ("key_block_size", C.c_int), ("key_modes_stride", C.c_int),
                 ("key_modes_band", C.c_int), ("quality", C.c_void_p), ("grain", C.c_void_p), ("grain_cov", C.c_void_p),
                 ("lr_units", C.c_void_p * 3), ("lr_units_per_frame", C.c_int * 3), ("lr_choice", C.c_void_p),
-                ("cdef_bits", C.c_int), ("cdef_y", C.c_uint8 * 8), ("cdef_uv", C.c_uint8 * 8), ("cdef_idx", C.c_void_p)]
+                ("cdef_bits", C.c_int), ("cdef_y", C.c_uint8 * 8), ("cdef_uv", C.c_uint8 * 8), ("cdef_idx", C.c_void_p),
+                ("lf_levels", C.c_void_p), ("lf_choice", C.c_void_p)]
 
 
 def policy_frame_params(base_q_idx, bit_depth, frame_type):
@@ -275,7 +288,7 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None, tone_map=0, tone_map_peak=0, grain_cov=None, lr_search=None, cdef_search=None):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None, tone_map=0, tone_map_peak=0, grain_cov=None, lr_search=None, cdef_search=None, lf_search=None):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
@@ -311,6 +324,8 @@ class GopSession:
             self.cfg.lr_search = int(lr_search)
         if cdef_search is not None:     # 1 .. 3 = cdef_bits: a CDEF strength set chosen per superblock (av1mi_gop_config.cdef_search)
             self.cfg.cdef_search = int(cdef_search)
+        if lf_search is not None:       # 1 = the deblocking levels chosen per frame against the source (av1mi_gop_config.lf_search)
+            self.cfg.lf_search = int(lf_search)
         # tone_map: 1 = every batch is tone-mapped (PQ / BT.2020 -> SDR / BT.709) in place behind the input stages; tone_map_peak: cd/m2, 0 = 1000
         self.cfg.tone_map, self.cfg.tone_map_peak = int(tone_map), int(tone_map_peak)
         if crop is not None:
@@ -403,6 +418,8 @@ class GopSession:
         if f.cdef_bits:    # cdef_search: the frame header's sets and the chosen index per [segment, superblock]
             out["cdef_bits"], out["cdef_y"], out["cdef_uv"] = int(f.cdef_bits), list(f.cdef_y), list(f.cdef_uv)
             out["cdef_idx"] = _view(f.cdef_idx, (S, ((self.w + 63) // 64) * ((self.h + 63) // 64)), np.uint8)
+        if f.lf_levels:    # lf_search: the header levels [segment, 4] and the chosen candidates [segment, 2] (luma, chroma)
+            out["lf_levels"], out["lf_choice"] = _view(f.lf_levels, (S, 4), np.uint8), _view(f.lf_choice, (S, 2), np.uint8)
         if f.grain_cov:    # grain_cov: records [segment, plane] (GRAIN_COV_DTYPE)
             out["grain_cov"] = _view(f.grain_cov, (S, 3), GRAIN_COV_DTYPE)
         if f.key_block_size == 32:
@@ -510,6 +527,23 @@ def cdef_search_table_bytes(width, height, nframes):
     lib = load()
     lib.av1mi_cdef_search_table_bytes.restype = C.c_size_t
     return int(lib.av1mi_cdef_search_table_bytes(int(width), int(height), int(nframes)))
+
+
+LF_SEARCH_CANDIDATES = 8      # AV1MI_LF_SEARCH_CANDIDATES
+
+
+def lf_search_levels(params, c):
+    """the four header levels of candidate c of a frame (av1mi_lf_search_levels): luma vertical, luma horizontal, U, V"""
+    out = (C.c_int * 4)()
+    if load().av1mi_lf_search_levels(C.byref(params), int(c), out):
+        raise ValueError("deblocking search: candidate %d outside 0 .. 7, or policy levels the search refuses" % c)
+    return list(out)
+
+
+def lf_search_scratch_bytes(width, height, nframes):
+    lib = load()
+    lib.av1mi_lf_search_scratch_bytes.restype = C.c_size_t
+    return int(lib.av1mi_lf_search_scratch_bytes(int(width), int(height), int(nframes)))
 
 
 LR_SEARCH_CANDIDATES = 9      # AV1MI_LR_SEARCH_CANDIDATES
@@ -882,6 +916,10 @@ class Context:
     def cdef_search(self, job):
         """a CDEF strength set per superblock against the source (include/av1mi.h av1mi_cdef_search; job: CdefSearchJob)"""
         self._chk(self.lib.av1mi_cdef_search(self.h, C.byref(job)))
+
+    def lf_search(self, job):
+        """the deblocking levels per frame against the source, and a map per frame (include/av1mi.h av1mi_lf_search; job: LfSearchJob)"""
+        self._chk(self.lib.av1mi_lf_search(self.h, C.byref(job)))
 
     def lr_search(self, job):
         """a Wiener record or none per restoration unit of the three planes (include/av1mi.h av1mi_lr_search; job: LrSearchJob)"""

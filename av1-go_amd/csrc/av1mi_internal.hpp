@@ -343,6 +343,32 @@ struct LevelsLaunch {
   int arrays;
 };
 hipError_t launch_mi_levels(const LevelsLaunch &L, hipStream_t s);
+// ... and its grid-wide sibling (k_mi_levels_frames): the level bytes come from levels[frame][4] in DEVICE memory (the deblocking search's
+// pick: luma vertical, luma horizontal, U, V) and the patched words go to a map of their own per frame, dense (w / 4 units a row, h / 4
+// rows a frame; chroma: of the chroma plane), read from base maps with their strides (frame stride 0 = shared).  The hold rule as above
+struct LevelsFramesLaunch {
+  const uint8_t *levels;
+  const uint32_t *base[2]; uint32_t *out[2];              // luma, chroma; a null out[k] is skipped
+  int cols[2], rows[2], stride[2]; size_t frame_stride[2];
+  int nframes;
+};
+hipError_t launch_mi_levels_frames(const LevelsFramesLaunch &L, hipStream_t s);
+
+// The deblocking search (lf_search_kernel.hip k_lf_search, k_lf_pick; av1mi.h "deblocking search"): per (frame, superblock) the squared
+// error against the source of the planes deblocked at each of 8 candidate levels, luma and chroma apart, over the true size (tw x th);
+// then per frame the sums over the superblocks, the two arg-mins and the four header levels
+struct LfSearchLaunch {
+  const void *rec[3], *orig[3];                            // reconstruction, source: the same geometry
+  int w, h, tw, th, stride_y, stride_uv, bd, sharpness, nframes;
+  const uint32_t *mi_y, *mi_uv; int mi_stride_y, mi_stride_uv;      // the base maps, as DeblockCdefLaunch
+  size_t mi_frame_stride_y, mi_frame_stride_uv;
+  uint8_t lvl[8][4];                                       // candidate c: luma vertical, luma horizontal, chroma, chroma
+  uint8_t first[2][8];                                     // [luma / chroma][c]: the lowest candidate with c's levels (c itself: not a twin)
+  unsigned long long *table;                               // scratch: [frame][sb][2][8]
+  unsigned long long *sse; uint8_t *choice, *levels;       // [frame][2][8], [frame][2], [frame][4]
+};
+hipError_t launch_lf_search(const LfSearchLaunch &L, hipStream_t s);
+hipError_t launch_lf_pick(const LfSearchLaunch &L, hipStream_t s);
 
 int tx_width(int tx_size);
 int tx_height(int tx_size);

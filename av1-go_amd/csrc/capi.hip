@@ -508,6 +508,81 @@ int av1mi_cdef_search(av1mi_ctx *ctx, const av1mi_cdef_search_job *j) {
   return AV1MI_OK;
 }
 
+// ---- deblocking search
+// null = fine, else why the policy levels P cannot be searched
+static const char *lf_search_error(const av1mi_frame_params *p) {
+  if (!p) return "no frame parameters";
+  for (int i = 0; i < 4; i++) if (p->lf_level[i] < 0 || p->lf_level[i] > 63) return "a policy level outside 0 .. 63";
+  if (p->lf_level[2] != p->lf_level[3]) return "the policy's U and V levels differ (the search gives both chroma planes one level)";
+  if (p->lf_level[0] == 0 && p->lf_level[1] == 0 && p->lf_level[2] != 0) return "policy luma levels 0 with a chroma level: the frame header could not carry the chroma level";
+  return nullptr;
+}
+int av1mi_lf_search_levels(const av1mi_frame_params *p, int c, int out[4]) {
+  if (!out || c < 0 || c >= AV1MI_LF_SEARCH_CANDIDATES || lf_search_error(p)) return AV1MI_E_INVAL;
+  static const int m[AV1MI_LF_SEARCH_CANDIDATES] = { 4, 0, 2, 3, 5, 6, 8, 12 };
+  for (int i = 0; i < 4; i++) {
+    const int L = p->lf_level[i], lo = i < 2 ? 1 : 0;
+    out[i] = c == 0 ? L : std::min(63, std::max(lo, (L * m[c] + 2) >> 2));
+  }
+  return AV1MI_OK;
+}
+size_t av1mi_lf_search_scratch_bytes(int width, int height, int nframes) {
+  if (width <= 0 || height <= 0 || nframes <= 0) return 0;
+  return (size_t)nframes * ((width + 63) / 64) * ((height + 63) / 64) * 2 * AV1MI_LF_SEARCH_CANDIDATES * sizeof(uint64_t);
+}
+int av1mi_lf_search(av1mi_ctx *ctx, const av1mi_lf_search_job *j) {
+  BIND(ctx);
+  if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
+  if (int rc = check_bd(ctx, j->bit_depth)) return rc;
+  if (j->width <= 0 || j->height <= 0 || (j->width & 7) || (j->height & 7) || j->width > 16384 || j->height > 16384)
+    return fail(ctx, AV1MI_E_INVAL, "frame %dx%d must be a multiple of 8", j->width, j->height);
+  if (int rc = check_nframes(ctx, j->nframes)) return rc;
+  if (j->stride_y < j->width || j->stride_uv < j->width / 2 || (j->stride_y & 3) || (j->stride_uv & 3)) return fail(ctx, AV1MI_E_INVAL, "bad strides");
+  if (j->mi_stride_y < j->width / 4 || j->mi_stride_uv < j->width / 8)
+    return fail(ctx, AV1MI_E_INVAL, "bad plane geometry %dx%d strides %d/%d/%d", j->width, j->height, j->stride_y, j->mi_stride_y, j->mi_stride_uv);
+  const int tw = j->true_width ? j->true_width : j->width, th = j->true_height ? j->true_height : j->height;
+  if (tw > j->width || th > j->height || tw <= j->width - 8 || th <= j->height - 8) return fail(ctx, AV1MI_E_INVAL, "true size %dx%d does not round up to %dx%d", tw, th, j->width, j->height);
+  if (const char *why = lf_search_error(j->params)) return fail(ctx, AV1MI_E_INVAL, "deblocking search: %s", why);
+  if (j->params->lf_sharpness < 0 || j->params->lf_sharpness > 7) return fail(ctx, AV1MI_E_INVAL, "sharpness %d out of range", j->params->lf_sharpness);
+  const void *ptrs[] = { j->d_rec_y, j->d_rec_u, j->d_rec_v, j->d_orig_y, j->d_orig_u, j->d_orig_v, j->d_scratch, j->d_sse };
+  for (const void *p : ptrs) if (!p || ((uintptr_t)p & 7)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned device pointer");
+  if (!j->d_mi_y || !j->d_mi_uv || !j->d_choice || !j->d_levels || ((uintptr_t)j->d_levels & 3)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned map pointer");
+  if (!j->d_mi_y_out != !j->d_mi_uv_out) return fail(ctx, AV1MI_E_INVAL, "deblocking search: give both output maps or neither");
+  if (j->d_mi_y_out == j->d_mi_y || j->d_mi_uv_out == j->d_mi_uv) return fail(ctx, AV1MI_E_INVAL, "null or aliased device pointer");
+  if (j->nframes == 0) return AV1MI_OK;
+  av1mi::LfSearchLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.rec[0] = j->d_rec_y; L.rec[1] = j->d_rec_u; L.rec[2] = j->d_rec_v; L.orig[0] = j->d_orig_y; L.orig[1] = j->d_orig_u; L.orig[2] = j->d_orig_v;
+  L.w = j->width; L.h = j->height; L.tw = tw; L.th = th; L.stride_y = j->stride_y; L.stride_uv = j->stride_uv; L.bd = j->bit_depth;
+  L.sharpness = j->params->lf_sharpness; L.nframes = j->nframes;
+  L.mi_y = j->d_mi_y; L.mi_uv = j->d_mi_uv; L.mi_stride_y = j->mi_stride_y; L.mi_stride_uv = j->mi_stride_uv;
+  L.mi_frame_stride_y = j->mi_frame_stride_y; L.mi_frame_stride_uv = j->mi_frame_stride_uv;
+  for (int c = 0; c < AV1MI_LF_SEARCH_CANDIDATES; c++) {
+    int lv[4];
+    av1mi_lf_search_levels(j->params, c, lv);
+    for (int i = 0; i < 4; i++) L.lvl[c][i] = (uint8_t)lv[i];
+    // the lowest candidate with the same levels: luma = the pair (vertical, horizontal), chroma = the one level
+    for (int g = 0; g < 2; g++) {
+      int first = c;
+      for (int e = c - 1; e >= 0; e--) if (g == 0 ? (L.lvl[e][0] == L.lvl[c][0] && L.lvl[e][1] == L.lvl[c][1]) : L.lvl[e][2] == L.lvl[c][2]) first = e;
+      L.first[g][c] = (uint8_t)first;
+    }
+  }
+  L.table = (unsigned long long *)j->d_scratch; L.sse = (unsigned long long *)j->d_sse; L.choice = j->d_choice; L.levels = j->d_levels;
+  ProfScope ps(ctx, AV1MI_K_DEBLOCK);
+  HIP_TRY(ctx, av1mi::launch_lf_search(L, ctx->stream));
+  HIP_TRY(ctx, av1mi::launch_lf_pick(L, ctx->stream));
+  if (j->d_mi_y_out) {
+    av1mi::LevelsFramesLaunch M;
+    memset(&M, 0, sizeof(M));
+    M.levels = j->d_levels; M.nframes = j->nframes;
+    M.base[0] = j->d_mi_y; M.out[0] = j->d_mi_y_out; M.cols[0] = j->width / 4; M.rows[0] = j->height / 4; M.stride[0] = j->mi_stride_y; M.frame_stride[0] = j->mi_frame_stride_y;
+    M.base[1] = j->d_mi_uv; M.out[1] = j->d_mi_uv_out; M.cols[1] = j->width / 8; M.rows[1] = j->height / 8; M.stride[1] = j->mi_stride_uv; M.frame_stride[1] = j->mi_frame_stride_uv;
+    HIP_TRY(ctx, av1mi::launch_mi_levels_frames(M, ctx->stream));
+  }
+  return AV1MI_OK;
+}
+
 int av1mi_deblock_cdef_frames(av1mi_ctx *ctx, const av1mi_deblock_cdef_job *j) {
   BIND(ctx);
   if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");

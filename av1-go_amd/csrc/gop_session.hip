@@ -122,6 +122,10 @@ struct Slot {
   // pinned mirror, copied behind the filters in front of cdef_down
   void *d_cdef_cost = nullptr, *d_cdef_rec = nullptr, *d_cdef_idx = nullptr, *h_cdef_idx = nullptr;
   hipEvent_t cdef_down = nullptr;
+  // lf_search: the batch's header levels [segment][4] and chosen candidates [segment][2] — per SLOT: the host reads them while later
+  // batches search — their pinned mirrors, copied behind the filters in front of lf_down
+  void *d_lf_levels = nullptr, *h_lf_levels = nullptr, *d_lf_choice = nullptr, *h_lf_choice = nullptr;
+  hipEvent_t lf_down = nullptr;
   int frame_type = 0;
   int q = 0;                          // the batch's quantiser (av1mi_gop_set_base_q_idx) and what the policy derives from it for its frame type
   av1mi_frame_params params{};
@@ -168,6 +172,9 @@ struct av1mi_gop {
   Slot slot[kSlots];
   void *d_rec[3] = {}, *d_dbl[3] = {}, *d_cdef[3] = {}, *d_ref[3] = {};
   void *d_mi[3][2] = {};                       // [key / inter / key in 32x32 blocks][luma / chroma] deblocking mode-info maps (one frame, shared by the batch)
+  // lf_search: a map per frame of a batch [luma / chroma] (k_mi_levels_frames writes them from d_mi in front of the batch's deblocking),
+  // the search's scratch table and its sums — once per session: the batches are serial on the main stream
+  void *d_mi_frames[2] = {}, *d_lf_table = nullptr, *d_lf_sse = nullptr;
   int key32 = 0, key_rows32 = 0;               // key frames in 32x32 blocks over the first key_rows32 luma rows (the complete superblock rows)
   int key_modes_band = 0, key_modes_stride = 0;  // mode bytes per segment: the 32x32 blocks, then (from key_modes_band) the 8x8 blocks of the last rows
   void *d_cdef_sb[2] = {}, *d_lr[2] = {}, *d_zero_skip = nullptr;
@@ -299,6 +306,11 @@ int slot_buffers(av1mi_gop *g, Slot &s) {
     G_TRY(dev_alloc(g, &s.d_cdef_rec, nsb * 4)); G_TRY(dev_alloc(g, &s.d_cdef_idx, nsb)); G_TRY(host_alloc(g, &s.h_cdef_idx, nsb));
     G_HIP(hipEventCreateWithFlags(&s.cdef_down, hipEventDisableTiming));
   }
+  if (c.lf_search) {
+    G_TRY(dev_alloc(g, &s.d_lf_levels, (size_t)S * 4)); G_TRY(host_alloc(g, &s.h_lf_levels, (size_t)S * 4));
+    G_TRY(dev_alloc(g, &s.d_lf_choice, (size_t)S * 2)); G_TRY(host_alloc(g, &s.h_lf_choice, (size_t)S * 2));
+    G_HIP(hipEventCreateWithFlags(&s.lf_down, hipEventDisableTiming));
+  }
   if (c.quality_stats) {
     G_TRY(host_alloc(g, &s.h_quality, (size_t)S * 3 * sizeof(av1mi_quality)));
     G_HIP(hipEventCreateWithFlags(&s.quality_done, hipEventDisableTiming));
@@ -352,6 +364,11 @@ int side_information(av1mi_gop *g) {
     G_TRY(dev_alloc(g, &g->d_lr[0], uy * 8)); G_TRY(av1mi_upload(g->ctx, g->d_lr[0], lr.data(), uy * 8));
     for (size_t i = 0; i < uc; i++) memcpy(&lr[i * 8], P.lr_unit_uv, 8);
     G_TRY(dev_alloc(g, &g->d_lr[1], uc * 8)); G_TRY(av1mi_upload(g->ctx, g->d_lr[1], lr.data(), uc * 8));
+  }
+  if (c.lf_search) {      // a map per frame of a batch, the scratch table [segment][superblock][2][8] and the sums [segment][2][8]
+    G_TRY(dev_alloc(g, &g->d_mi_frames[0], (size_t)c.segments * (fy / 16) * 4)); G_TRY(dev_alloc(g, &g->d_mi_frames[1], (size_t)c.segments * (fc / 16) * 4));
+    G_TRY(dev_alloc(g, &g->d_lf_table, av1mi_lf_search_scratch_bytes(w, h, c.segments)));
+    G_TRY(dev_alloc(g, &g->d_lf_sse, (size_t)c.segments * 2 * AV1MI_LF_SEARCH_CANDIDATES * sizeof(uint64_t)));
   }
   return AV1MI_OK;
 }
@@ -432,6 +449,7 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
       return WHY("lr_search at a true size %dx%d whose restoration units differ from those of the coded size %dx%d is not built", vw, vh, c->width, c->height);
   }
   if (c->cdef_search < 0 || c->cdef_search > 3) return WHY("cdef_search %d unknown (0 the policy's strength set in every superblock, 1 .. 3 = cdef_bits: one of 2, 4, 8 sets chosen per superblock)", c->cdef_search);
+  if (c->lf_search != 0 && c->lf_search != 1) return WHY("lf_search %d unknown (0 the policy's deblocking levels in every frame, 1 levels chosen per frame against the source)", c->lf_search);
   if (c->tone_map != 0 && c->tone_map != 1) return WHY("tone_map %d unknown (0 none, 1 BT.2390)", c->tone_map);
   if (c->tone_map_peak && !c->tone_map) return WHY("tone_map_peak %d needs tone_map", c->tone_map_peak);
   if (c->tone_map && c->bit_depth != 10) return WHY("tone_map needs bit_depth 10, not %d: an HDR10 source has 10 bits", c->bit_depth);
@@ -580,7 +598,7 @@ void av1mi_gop_close(av1mi_gop *g) {
   if (g->up) { (void)hipStreamSynchronize(g->up); (void)hipStreamDestroy(g->up); }
   if (g->down) { (void)hipStreamSynchronize(g->down); (void)hipStreamDestroy(g->down); }
   for (Slot &s : g->slot)
-    for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done, s.quality_done, s.grain_done, s.lr_down, s.cdef_down })
+    for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done, s.quality_done, s.grain_done, s.lr_down, s.cdef_down, s.lf_down })
       if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : { g->store[0].filled, g->store[0].read_done, g->store[1].filled, g->store[1].read_done, g->scene_done, g->put_done[0], g->put_done[1], g->put_done[2] })
     if (e) (void)hipEventDestroy(e);
@@ -810,6 +828,20 @@ static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
   const av1mi_frame_params &P = s.params;
   G_TRY(follow_q(g, s));
   void *const *mi = g->d_mi[key && g->key32 ? 2 : s.frame_type];
+  size_t mi_frame_stride[2] = { 0, 0 };      // units between the frames' maps: 0 = the one shared map
+  if (c.lf_search) {      // the levels of every frame against the source, and a map per frame with them: what every deblocking launch below reads
+    av1mi_lf_search_job sj;
+    memset(&sj, 0, sizeof(sj));
+    sj.width = w; sj.height = h; sj.bit_depth = bd; sj.nframes = S; sj.stride_y = g->plane[0].w; sj.stride_uv = g->plane[1].w;
+    sj.d_rec_y = g->d_rec[0]; sj.d_rec_u = g->d_rec[1]; sj.d_rec_v = g->d_rec[2]; sj.d_orig_y = src[0]; sj.d_orig_u = src[1]; sj.d_orig_v = src[2];
+    sj.true_width = g->vw; sj.true_height = g->vh; sj.params = &P;
+    sj.d_mi_y = (const uint32_t *)mi[0]; sj.d_mi_uv = (const uint32_t *)mi[1]; sj.mi_stride_y = g->plane[0].w / 4; sj.mi_stride_uv = g->plane[1].w / 4;
+    sj.d_scratch = g->d_lf_table; sj.d_sse = (uint64_t *)g->d_lf_sse; sj.d_choice = (uint8_t *)s.d_lf_choice; sj.d_levels = (uint8_t *)s.d_lf_levels;
+    sj.d_mi_y_out = (uint32_t *)g->d_mi_frames[0]; sj.d_mi_uv_out = (uint32_t *)g->d_mi_frames[1];
+    G_TRY(av1mi_lf_search(g->ctx, &sj));
+    mi = g->d_mi_frames;
+    mi_frame_stride[0] = (size_t)(w / 4) * (h / 4); mi_frame_stride[1] = (size_t)(w / 8) * (h / 8);
+  }
   // key frames are coded with skip = 0 everywhere (no block is exempt from CDEF); P frames: the kernel's skip flags, per frame
   // (the slot's next inter kernel is kSlots batches away and ordered behind this CDEF on the main stream, nothing else writes them)
   const uint8_t *skip8 = (const uint8_t *)(key ? g->d_zero_skip : s.d_skip);
@@ -828,6 +860,7 @@ static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
     fj.d_dbl_y = g->d_dbl[0]; fj.d_dbl_u = g->d_dbl[1]; fj.d_dbl_v = g->d_dbl[2];
     fj.d_dst_y = g->d_cdef[0]; fj.d_dst_u = g->d_cdef[1]; fj.d_dst_v = g->d_cdef[2];
     fj.d_mi_y = (const uint32_t *)mi[0]; fj.d_mi_uv = (const uint32_t *)mi[1]; fj.mi_stride_y = g->plane[0].w / 4; fj.mi_stride_uv = g->plane[1].w / 4;
+    fj.mi_frame_stride_y = mi_frame_stride[0]; fj.mi_frame_stride_uv = mi_frame_stride[1];
     fj.d_sb_strength = (const uint8_t *)g->d_cdef_sb[s.frame_type]; fj.sb_frame_stride = 0;
     fj.d_skip8 = skip8; fj.skip_frame_stride = skip_frame_stride;
     G_TRY(av1mi_deblock_cdef_frames(g->ctx, &fj));
@@ -836,7 +869,7 @@ static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
     // (restoration's boundary rows are clamped at the true size), and the fused kernel writes only four rows in 64 of them
     for (int p = 0; p < 3; p++) {
       const Plane &L = g->plane[p];
-      G_TRY(av1mi_deblock_frames(g->ctx, g->d_rec[p], L.w, g->d_dbl[p], L.w, L.w, L.h, bd, L.ss, (const uint32_t *)mi[L.ss], L.w / 4, 0, P.lf_sharpness, S));
+      G_TRY(av1mi_deblock_frames(g->ctx, g->d_rec[p], L.w, g->d_dbl[p], L.w, L.w, L.h, bd, L.ss, (const uint32_t *)mi[L.ss], L.w / 4, mi_frame_stride[L.ss], P.lf_sharpness, S));
     }
     av1mi_cdef_job cj;
     memset(&cj, 0, sizeof(cj));
@@ -897,6 +930,12 @@ static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
     G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
     G_HIP(hipMemcpyAsync(s.h_cdef_idx, s.d_cdef_idx, (size_t)S * ((w + 63) / 64) * ((h + 63) / 64), hipMemcpyDeviceToHost, g->down));
     G_HIP(hipEventRecord(s.cdef_down, g->down));
+  }
+  if (c.lf_search) {      // the levels and the choice to the host with every batch: six bytes per segment, for the frame header and the statistics
+    G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
+    G_HIP(hipMemcpyAsync(s.h_lf_levels, s.d_lf_levels, (size_t)S * 4, hipMemcpyDeviceToHost, g->down));
+    G_HIP(hipMemcpyAsync(s.h_lf_choice, s.d_lf_choice, (size_t)S * 2, hipMemcpyDeviceToHost, g->down));
+    G_HIP(hipEventRecord(s.lf_down, g->down));
   }
   if (s.symbols_down) {
     G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
@@ -1139,6 +1178,10 @@ int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out) {
     G_HIP(hipEventSynchronize(s.cdef_down));
     out->cdef_bits = g->cfg.cdef_search; out->cdef_idx = (const uint8_t *)s.h_cdef_idx;
     av1mi_cdef_search_sets(&s.params, out->cdef_bits, out->cdef_y, out->cdef_uv);
+  }
+  if (g->cfg.lf_search) {
+    G_HIP(hipEventSynchronize(s.lf_down));
+    out->lf_levels = (const uint8_t *)s.h_lf_levels; out->lf_choice = (const uint8_t *)s.h_lf_choice;
   }
   if (g->cfg.quality_stats) { G_HIP(hipEventSynchronize(s.quality_done)); out->quality = (const av1mi_quality *)s.h_quality; }
   if (g->cfg.denoise && s.has_grain) { G_HIP(hipEventSynchronize(s.grain_done)); out->grain = (const av1mi_grain_record *)s.h_grain; out->grain_cov = (const av1mi_grain_cov_record *)s.h_grain_cov; }

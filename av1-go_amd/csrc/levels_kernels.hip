@@ -46,4 +46,39 @@ hipError_t launch_mi_levels(const LevelsLaunch &L, hipStream_t s) {
   return hipGetLastError();
 }
 
+// The grid-wide sibling for the deblocking search (lf_search_kernel.hip): every frame of a batch gets a map of its own, the base map's
+// words with the level bytes the search picked for THAT frame.  The bytes are read from levels[frame] in device memory (k_lf_pick wrote
+// them on the same stream: no host round trip), the words from the base maps with their strides, and written densely.  blockIdx.y: luma
+// / chroma map, blockIdx.z: the frame; a dword per lane and trip.
+__global__ __launch_bounds__(256) void k_mi_levels_frames(LevelsFramesLaunch L) {
+  const int k = blockIdx.y, f = blockIdx.z;
+  if (!L.out[k]) return;
+  const uint32_t lv = *reinterpret_cast<const uint32_t *>(L.levels + (size_t)f * 4);      // luma vertical, luma horizontal, U, V
+  const uint32_t bits = k == 0 ? (lv & 0xFFFFu) << 8 : ((lv >> 16) & 255u) << 8 | ((lv >> 16) & 255u) << 16;      // (U and V share the chroma map: U's level)
+  const uint32_t keep = ~0x00FFFF00u, hold = 1u << 24;
+  const int cols = L.cols[k];
+  const size_t n = (size_t)L.rows[k] * cols, step = (size_t)gridDim.x * blockDim.x;
+  const uint32_t *base = L.base[k] + (size_t)f * L.frame_stride[k];
+  uint32_t *out = L.out[k] + (size_t)f * n;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+    const size_t r = i / cols;
+    const uint32_t v = base[r * L.stride[k] + (i - r * cols)];
+    out[i] = (v & hold) ? v : ((v & keep) | bits);
+  }
+}
+
+hipError_t launch_mi_levels_frames(const LevelsFramesLaunch &L, hipStream_t s) {
+  if (!L.levels || L.nframes < 1 || L.nframes > 65535 || (!L.out[0] && !L.out[1])) return hipErrorInvalidValue;
+  size_t most = 0;
+  for (int k = 0; k < 2; k++) {
+    if (L.out[k] && (!L.base[k] || L.cols[k] < 1 || L.rows[k] < 1 || L.stride[k] < L.cols[k])) return hipErrorInvalidValue;
+    const size_t n = L.out[k] ? (size_t)L.rows[k] * L.cols[k] : 0;
+    most = n > most ? n : most;
+  }
+  size_t blocks = (most + 255) / 256;      // a lane per dword of the larger map, at most 256 workgroups a frame (the loop strides over the rest)
+  blocks = blocks < 1 ? 1 : blocks > 256 ? 256 : blocks;
+  hipLaunchKernelGGL(k_mi_levels_frames, dim3((unsigned)blocks, 2u, (unsigned)L.nframes), dim3(256), 0, s, L);
+  return hipGetLastError();
+}
+
 }  // namespace av1mi

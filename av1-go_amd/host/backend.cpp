@@ -77,6 +77,7 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
   cfg.gpu_entropy = job.gpu_entropy ? 1 : 0;
   cfg.lr_search = job.lr_search;        // -av1mi_lr_search: a restoration record chosen per unit
   cfg.cdef_search = job.cdef_search;    // -av1mi_cdef_search: cdef_bits, a CDEF strength set chosen per superblock
+  cfg.lf_search = job.lf_search;        // -av1mi_lf_search: the deblocking levels chosen per frame
   // -av1mi_stats / -av1mi_min_psnr: the session measures every batch on the GPU; the records arrive with the collected batch
   plan->measure = !job.stats_path.empty() || job.min_psnr > 0;
   cfg.quality_stats = plan->measure ? 1 : 0;
@@ -131,6 +132,7 @@ std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, c
   if (tags.ar) k += snprintf(line + k, sizeof(line) - (size_t)k, " ar:%d", f.ar);
   if (tags.lr) k += snprintf(line + k, sizeof(line) - (size_t)k, " lr:%d/%d", f.lr_filtered, f.lr_units);
   if (tags.cdef) k += snprintf(line + k, sizeof(line) - (size_t)k, " cdef:%d/%d", f.cdef_moved, f.cdef_sbs);
+  if (tags.lf) k += snprintf(line + k, sizeof(line) - (size_t)k, " lf:%d/%d", f.lf_y, f.lf_uv);
   if (cut) k += snprintf(line + k, sizeof(line) - (size_t)k, " cut:1");
   return std::string(line, (size_t)k);
 }
@@ -364,6 +366,10 @@ struct Run {
         f.cdef_sbs = ((plan.cfg.width + 63) / 64) * ((plan.cfg.height + 63) / 64);
         for (int i = 0; i < f.cdef_sbs; i++) f.cdef_moved += oldest.cdef_idx[(size_t)s * f.cdef_sbs + i] != 0;
       }
+      if (job.lf_search) {      // the frame's chosen levels: luma vertical, chroma
+        if (!oldest.lf_levels) return fail(2, "the session returned no deblocking levels");
+        f.lf_y = oldest.lf_levels[(size_t)s * 4]; f.lf_uv = oldest.lf_levels[(size_t)s * 4 + 2];
+      }
       if (plan.measure) {
         if (!oldest.quality) return fail(2, "the session returned no quality records");
         memcpy(f.q, oldest.quality + (size_t)s * 3, sizeof(f.q));
@@ -403,7 +409,7 @@ struct Run {
   // the group's frames in presentation order: each unit to the sink, its line to the stats
   int write_group(const Group &group, const GroupOut &out) {
     StatsTags tags;
-    tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0; tags.ar = job.grain_lag > 0; tags.lr = job.lr_search != 0; tags.cdef = job.cdef_search != 0;
+    tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0; tags.ar = job.grain_lag > 0; tags.lr = job.lr_search != 0; tags.cdef = job.cdef_search != 0; tags.lf = job.lf_search != 0;
     for (int s = 0; s < S; s++)
       for (size_t t = 0; t < out[(size_t)s].size(); t++) {
         const FrameOut &f = out[(size_t)s][t];

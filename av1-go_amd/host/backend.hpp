@@ -33,7 +33,7 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
 
 // one coded frame of a group: its temporal unit and what the stats file says about it (q: the session's records where the job measures;
 // grain: the luma scaling at mid grey where it denoises)
-struct FrameOut { std::vector<uint8_t> unit; av1mi_quality q[3]; int base_q_idx; int grain; int ar; int lr_filtered, lr_units; int cdef_moved, cdef_sbs; };      // ar: the ar_coeff_lag coded (-av1mi_grain_lag)
+struct FrameOut { std::vector<uint8_t> unit; av1mi_quality q[3]; int base_q_idx; int grain; int ar; int lr_filtered, lr_units; int cdef_moved, cdef_sbs; int lf_y, lf_uv; };      // ar: the ar_coeff_lag coded (-av1mi_grain_lag)
 // the layout of a group of frames over the session's segments: GOP s holds frames start[s] .. start[s] + len[s] - 1 of the group; cut
 // (analysed jobs) flags the frames the scene analysis found
 struct Group {
@@ -47,7 +47,7 @@ struct Group {
 };
 // The stats file: the line of frame n in presentation order, and the summary line.  tags: what a line says beyond the
 // figures — the window and the colour record (frame 0 only; w == 0 / null = none), q: (a job with a target), grain: (a job that denoises)
-struct StatsTags { CropRect win; const av1mi_colour *colour = nullptr; bool q = false, grain = false, ar = false, lr = false, cdef = false; };
+struct StatsTags { CropRect win; const av1mi_colour *colour = nullptr; bool q = false, grain = false, ar = false, lr = false, cdef = false, lf = false; };
 std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, const StatsTags &tags, bool cut);
 std::string StatsSummaryLine(const av1mi::quality::Summary &sum, long long bytes, int bit_depth);
 

@@ -10,6 +10,8 @@
 //                   lines gain " lr:<units filtered>/<units>")
 //                   (-av1mi_cdef_search 0 .. 3: N > 0 = one of 1 << N CDEF strength sets chosen per 64x64 superblock on the GPU, cdef_bits = N;
 //                   the stats file's frame lines gain " cdef:<superblocks not on set 0>/<superblocks>")
+//                   (-av1mi_lf_search 0 | 1: 1 = the deblocking levels of every frame chosen among 8 candidates on the GPU against the source;
+//                   the stats file's frame lines gain " lf:<luma vertical level>/<chroma level>")
 //                   (-av1mi_me_range: 0, or a multiple of 4 up to 64: the P frames' motion search follows N + 8 samples per frame)
 //                   (CHAIN: the reference's scale filters, evaluated on the source's size and sample aspect ratio and applied on the GPU;
 //                   -av1mi_scale: an explicit output size, wins over the chain; any other filter is refused)

@@ -16,7 +16,7 @@ void DescribeSessionFrame(const av1mi_gop_frame &fr, int seg, int width, int hei
   memset(&f, 0, sizeof(f));
   f.width = width; f.height = height; f.bit_depth = bit_depth; f.frame_type = p.frame_type; f.base_q_idx = p.base_q_idx;
   f.visible_width = visible_width; f.visible_height = visible_height;
-  for (int i = 0; i < 4; i++) f.lf_level[i] = p.lf_level[i];
+  for (int i = 0; i < 4; i++) f.lf_level[i] = fr.lf_levels ? fr.lf_levels[(size_t)seg * 4 + i] : p.lf_level[i];      // (lf_levels: a session with the deblocking search)
   f.lf_sharpness = p.lf_sharpness; f.cdef_damping = p.cdef_damping; f.cdef_bits = 0; f.cdef_y[0] = p.cdef_y; f.cdef_uv[0] = p.cdef_uv;
   if (fr.cdef_bits) {      // a session with the CDEF search: the batch's strength sets and the segment's index per superblock
     f.cdef_bits = fr.cdef_bits;

@@ -292,6 +292,9 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
     else if (args[i] == "-av1mi_cdef_search") {
       if (!plain_int(args[i + 1], &job->cdef_search) || job->cdef_search > 3) { if (err) *err = "Invalid argument: -av1mi_cdef_search takes 0, 1, 2 or 3, not " + args[i + 1]; return false; }
     }
+    else if (args[i] == "-av1mi_lf_search") {
+      if (!plain_int(args[i + 1], &job->lf_search) || job->lf_search > 1) { if (err) *err = "Invalid argument: -av1mi_lf_search takes 0 or 1, not " + args[i + 1]; return false; }
+    }
     else if (args[i] == "-av1mi_me_range") {
       if (!plain_int(args[i + 1], &job->me_range) || job->me_range > 64 || (job->me_range & 3)) { if (err) *err = "Invalid argument: -av1mi_me_range takes 0 or a multiple of 4 up to 64, not " + args[i + 1]; return false; }
     }

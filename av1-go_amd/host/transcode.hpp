@@ -67,6 +67,8 @@ struct BackendJob {
                            // stats file's frame lines gain " lr:<units filtered>/<units>"
   int cdef_search = 0;     // -av1mi_cdef_search 0 .. 3: N > 0 = cdef_bits N: one of 1 << N CDEF strength sets chosen per 64x64 superblock on the GPU
                            // (av1mi_gop_config.cdef_search); the stats file's frame lines gain " cdef:<superblocks not on set 0>/<superblocks>"
+  int lf_search = 0;       // -av1mi_lf_search 0 | 1: 1 = the deblocking levels chosen per frame on the GPU against the source (av1mi_gop_config.lf_search);
+                           // the stats file's frame lines gain " lf:<luma vertical level>/<chroma level>"
   int me_range = 0;        // -av1mi_me_range N: 0 (default), or a multiple of 4 up to 64: P frames search around a coarse centre per 64x64 tile
                            // (av1mi_gop_config.coarse_range): vectors reach N + 8 samples per frame instead of 8
   // A target instead of the fixed quantiser (host/ratecontrol.hpp: one quantiser per batch, chosen from the bytes of the batches before).

@@ -271,6 +271,58 @@ int av1mi_cdef_search_sets(const struct av1mi_frame_params *params, int bits, ui
 size_t av1mi_cdef_search_table_bytes(int width, int height, int nframes);
 int av1mi_cdef_search(av1mi_ctx *ctx, const av1mi_cdef_search_job *job);
 
+/* ---- deblocking search (policy, non-normative): the deblocking levels of a frame chosen among 8 candidates around the policy's by
+ * squared error against the source, luma and chroma apart.  The levels are fixed-length bits of the frame header and nothing else.
+ *
+ * The candidates.  For a frame with policy levels P = av1mi_frame_params.lf_level[0..3] and m[8] = { 4, 0, 2, 3, 5, 6, 8, 12 }:
+ *     level(L, 0) = L                                           the policy's level untouched
+ *     level(L, c) = min(63, max(lo, (L * m[c] + 2) >> 2))       c = 1 .. 7; lo = 1 for luma, 0 for chroma
+ * Luma candidate c filters vertical edges at level(P[0], c) and horizontal edges at level(P[1], c); chroma candidate c filters U and
+ * V both at level(P[2], c).  A stated limit: U and V share one level, because the fused kernel (av1mi_deblock_cdef_frames) reads one
+ * chroma map for both; P[2] != P[3] is refused.  So is P[0] == P[1] == 0 with P[2] != 0: the frame header carries the chroma levels
+ * only behind a non-zero luma level.  Candidates that come out equal are legal and stay where they are; they never win a tie.
+ * av1mi_lf_search_levels writes the four header levels of candidate c (luma's and chroma's c alike) to out: plain host code, no
+ * device; AV1MI_E_INVAL for a null pointer, c outside 0 .. 7, a level outside 0 .. 63 and the two refusals.
+ *
+ * The cost.  SSE_y[c]: the 64-bit sum over the luma plane, over the samples INSIDE THE TRUE FRAME SIZE, of the squared difference
+ * between the source and the plane deblocked WHOLE at candidate c — both passes, the policy's sharpness.  SSE_uv[c]: the same over U
+ * plus V, the true size halved and rounded up.  "Deblocked at candidate c": with the frame's mode-info map in which the two level
+ * bytes (bits 8 .. 23) are replaced in every word that does not carry bit 24 — k_mi_levels' hold rule, by which the session marks
+ * off-screen units — and everything else of a word stays.  The levels cost the same bits whatever their value, so there is no lambda:
+ * per group (luma, chroma) the lowest sum wins, on a tie the lowest c.  The groups are independent: deblocking does not cross planes.
+ *
+ * av1mi_lf_search: d_rec_* the reconstruction (what av1mi_deblock_frames takes as d_src) and d_orig_* the source of nframes stacked
+ * 4:2:0 frames, the same geometry (width / height multiples of 8, strides in samples, multiples of 4, 8-byte aligned planes);
+ * true_width / true_height as in av1mi_cdef_search_job; d_mi_y / d_mi_uv: the base maps as in av1mi_deblock_cdef_job (their level
+ * bytes are not read); params: the frame's policy numbers (lf_level, lf_sharpness are read).  Device memory:
+ *   d_scratch    av1mi_lf_search_scratch_bytes() bytes, 8-byte aligned: uint64 [frame][superblock][2][8], every entry written
+ *   d_sse        uint64 SSE[frame][2][8] (luma, chroma), 8-byte aligned
+ *   d_choice     uint8 [frame][2]: the chosen luma and chroma candidate
+ *   d_levels     uint8 [frame][4], 4-byte aligned: the four header levels (luma vertical, luma horizontal, U, V)
+ *   d_mi_y_out / d_mi_uv_out   one patched map per frame, dense: (height / 4) x (width / 4) words a frame (chroma: (height / 8) x
+ *                (width / 8)), what av1mi_deblock_frames and av1mi_deblock_cdef_frames take with that row stride and that many units
+ *                as mi_frame_stride.  Both null: no maps are wanted; one null is refused.
+ * Three launches (k_lf_search: a workgroup per superblock, no atomics, no zeroing; k_lf_pick: a workgroup per frame; k_mi_levels_frames),
+ * asynchronous on the context's stream, under AV1MI_K_DEBLOCK in the profile. */
+typedef struct av1mi_lf_search_job {
+  int width, height, bit_depth, nframes;
+  int stride_y, stride_uv;
+  const void *d_rec_y, *d_rec_u, *d_rec_v;
+  const void *d_orig_y, *d_orig_u, *d_orig_v;
+  int true_width, true_height;
+  const uint32_t *d_mi_y, *d_mi_uv; int mi_stride_y, mi_stride_uv; size_t mi_frame_stride_y, mi_frame_stride_uv;
+  const struct av1mi_frame_params *params;
+  void *d_scratch;
+  uint64_t *d_sse;
+  uint8_t *d_choice;
+  uint8_t *d_levels;
+  uint32_t *d_mi_y_out, *d_mi_uv_out;
+} av1mi_lf_search_job;
+#define AV1MI_LF_SEARCH_CANDIDATES 8
+int av1mi_lf_search_levels(const struct av1mi_frame_params *params, int c, int out[4]);
+size_t av1mi_lf_search_scratch_bytes(int width, int height, int nframes);
+int av1mi_lf_search(av1mi_ctx *ctx, const av1mi_lf_search_job *job);
+
 /* ---- K7: loop restoration (AV1 spec §7.17) of one plane of nframes frames stacked vertically.  d_cdef: the CDEF
  * output, d_deblocked: the deblocked (pre-CDEF) plane used beyond stripe boundaries, d_out: the restored plane
  * (distinct from both).  subsampled = 1 for the chroma planes of 4:2:0 (32-row stripes offset by 4), 0 for luma.
@@ -1007,6 +1059,14 @@ typedef struct av1mi_gop_config {
    * what the frame header and the host writer need.  Per slot: the cost table, the strength records, the index bytes and their pinned
    * mirror, an event.  Anything outside 0 .. 3 is refused.  With 0 nothing of this is allocated or launched. */
   int cdef_search;
+  /* deblocking search ("deblocking search"): 0 = every frame of a batch is deblocked at the policy's levels from one shared map, as
+   * ever; 1 = in front of the first deblocking launch of a batch, on the main stream, av1mi_lf_search (k_lf_search, k_lf_pick,
+   * k_mi_levels_frames) chooses the levels of every segment's frame against the source and writes a map per frame, which all three
+   * deblocking paths (the fused kernel, the unfused path of padded sizes and of cdef_search) then read with a frame stride;
+   * av1mi_gop_frame.lf_levels / lf_choice carry the choice and av1mi_session_temporal_unit writes it into the frame header.  Per
+   * session: the per-frame maps (the batches are serial on the main stream), the scratch table and the sums; per slot: the level and
+   * choice bytes with pinned mirrors, an event.  Anything outside 0 / 1 is refused.  With 0 nothing of this is allocated or launched. */
+  int lf_search;
 } av1mi_gop_config;
 
 /* The source layout: what a session opened with a config is FED, as one description.  Everything a caller sizes or strides by — the
@@ -1090,6 +1150,11 @@ typedef struct av1mi_gop_frame {    /* one collected frame batch; host pointers 
   int cdef_bits;
   uint8_t cdef_y[8], cdef_uv[8];
   const uint8_t *cdef_idx;
+  /* av1mi_gop_config.lf_search: the deblocking levels of this batch's frames, [segment][4] (luma vertical, luma horizontal, U, V: what
+   * av1mi_obu_frame.lf_level takes for a segment, in place of params.lf_level), and the chosen candidates [segment][2] (luma, chroma),
+   * in pinned memory.  NULL when the option is off */
+  const uint8_t *lf_levels;
+  const uint8_t *lf_choice;
 } av1mi_gop_frame;
 
 typedef struct av1mi_gop av1mi_gop;
