@@ -18,6 +18,8 @@ __device__ __forceinline__ unsigned xcd_swizzle(unsigned bid, unsigned nwg) {
 // row * stride of a plane row: both operands are below 2^24 and the product below 2^32 (the C ABI admits frames up to 16384 x
 // 16384), so it is ONE full-rate 24-bit multiply; written as (size_t)row * stride it is a 64-bit multiply-add, four passes.
 __device__ __forceinline__ size_t row_off(int row, int stride) { return (size_t)__umul24((unsigned)row, (unsigned)stride); }
+// the 64x64 superblocks of a w x h frame (at most 256 x 256 of them)
+__host__ __device__ inline int sb_count(int w, int h) { return ((w + 63) / 64) * ((h + 63) / 64); }
 
 // The hand-off between lanes of one wave that share a block (a group): LDS traffic is in order per wave, this only stops the compiler
 // moving LDS accesses across the hand-off (and drains lgkmcnt).

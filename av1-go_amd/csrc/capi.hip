@@ -104,6 +104,24 @@ int grow(av1mi_ctx *ctx, void **buf, size_t *bytes, size_t need) {
 // the argument rules that every entry point states in the same words
 int check_bd(av1mi_ctx *ctx, int bd) { return bd != 8 && bd != 10 ? fail(ctx, AV1MI_E_INVAL, "bit depth %d not supported (8 or 10)", bd) : AV1MI_OK; }
 int check_nframes(av1mi_ctx *ctx, int nframes) { return nframes < 0 || nframes > 65535 ? fail(ctx, AV1MI_E_INVAL, "nframes %d out of range", nframes) : AV1MI_OK; }
+// ... of a 4:2:0 filter job (CDEF, its search, the deblocking search, deblock + CDEF): the frame and one pair of strides; cap: up to 16384 x 16384 only
+int check_frame420(av1mi_ctx *ctx, int w, int h, int stride_y, int stride_uv, bool cap) {
+  if (w <= 0 || h <= 0 || (w & 7) || (h & 7) || (cap && (w > 16384 || h > 16384))) return fail(ctx, AV1MI_E_INVAL, "frame %dx%d must be a multiple of 8", w, h);
+  if (stride_y < w || stride_uv < w / 2 || (stride_y & 3) || (stride_uv & 3)) return fail(ctx, AV1MI_E_INVAL, "bad strides");
+  return AV1MI_OK;
+}
+// the true size a job's sums run over: 0 = the coded size, else within 7 samples below it
+int check_true_size(av1mi_ctx *ctx, int w, int h, int true_w, int true_h, int *tw, int *th) {
+  *tw = true_w ? true_w : w; *th = true_h ? true_h : h;
+  return *tw > w || *th > h || *tw <= w - 8 || *th <= h - 8 ? fail(ctx, AV1MI_E_INVAL, "true size %dx%d does not round up to %dx%d", *tw, *th, w, h) : AV1MI_OK;
+}
+// every pointer of a list there and aligned to `align` bytes (a power of two); what: "device", "map"
+template <size_t N> int check_pointers(av1mi_ctx *ctx, const char *what, uintptr_t align, const void *const (&ptrs)[N]) {
+  for (const void *p : ptrs) if (!p || ((uintptr_t)p & (align - 1))) return fail(ctx, AV1MI_E_INVAL, "null or misaligned %s pointer", what);
+  return AV1MI_OK;
+}
+// a job's _y / _u / _v fields as a launch's planes
+template <typename T, typename U> void planes3(T (&dst)[3], U y, U u, U v) { dst[0] = y; dst[1] = u; dst[2] = v; }
 int check_lr_unit(av1mi_ctx *ctx, int unit_size, int subsampled) {      // 32 is a chroma unit size only
   if (unit_size == 64 || unit_size == 128 || unit_size == 256 || (unit_size == 32 && subsampled)) return AV1MI_OK;
   return fail(ctx, AV1MI_E_INVAL, "restoration unit size %d not allowed", unit_size);
@@ -443,17 +461,14 @@ int av1mi_cdef_frames(av1mi_ctx *ctx, const av1mi_cdef_job *j) {
   BIND(ctx);
   if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
   if (int rc = check_bd(ctx, j->bit_depth)) return rc;
-  if (j->width <= 0 || j->height <= 0 || (j->width & 7) || (j->height & 7)) return fail(ctx, AV1MI_E_INVAL, "frame %dx%d must be a multiple of 8", j->width, j->height);
+  if (int rc = check_frame420(ctx, j->width, j->height, j->stride_y, j->stride_uv, false)) return rc;
   if (j->damping < 3 || j->damping > 6 || j->nframes < 0 || j->nframes > 65535) return fail(ctx, AV1MI_E_INVAL, "bad damping/nframes");
-  if (j->stride_y < j->width || j->stride_uv < j->width / 2 || (j->stride_y & 3) || (j->stride_uv & 3)) return fail(ctx, AV1MI_E_INVAL, "bad strides");
-  const void *ptrs[] = { j->d_src_y, j->d_src_u, j->d_src_v, j->d_dst_y, j->d_dst_u, j->d_dst_v };
-  for (const void *p : ptrs) if (!p || ((uintptr_t)p & 7)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned device pointer");
-  if (!j->d_sb_strength || !j->d_skip8) return fail(ctx, AV1MI_E_INVAL, "null map pointer");
+  if (int rc = check_pointers(ctx, "device", 8, { j->d_src_y, j->d_src_u, j->d_src_v, j->d_dst_y, j->d_dst_u, j->d_dst_v })) return rc;
+  if (int rc = check_pointers(ctx, "map", 1, { j->d_sb_strength, j->d_skip8 })) return rc;
   if (j->d_src_y == j->d_dst_y || j->d_src_u == j->d_dst_u || j->d_src_v == j->d_dst_v) return fail(ctx, AV1MI_E_INVAL, "CDEF cannot run in place");
   if (j->nframes == 0) return AV1MI_OK;
   av1mi::CdefLaunch L;
-  L.src[0] = j->d_src_y; L.src[1] = j->d_src_u; L.src[2] = j->d_src_v;
-  L.dst[0] = j->d_dst_y; L.dst[1] = j->d_dst_u; L.dst[2] = j->d_dst_v;
+  planes3(L.src, j->d_src_y, j->d_src_u, j->d_src_v); planes3(L.dst, j->d_dst_y, j->d_dst_u, j->d_dst_v);
   L.w = j->width; L.h = j->height; L.stride_y = j->stride_y; L.stride_uv = j->stride_uv; L.bd = j->bit_depth; L.damping = j->damping;
   L.nframes = j->nframes; L.sb_strength = j->d_sb_strength; L.sb_frame_stride = j->sb_frame_stride;
   L.skip8 = j->d_skip8; L.skip_frame_stride = j->skip_frame_stride;
@@ -476,27 +491,25 @@ int av1mi_cdef_search_sets(const av1mi_frame_params *p, int bits, uint8_t y[8], 
 }
 size_t av1mi_cdef_search_table_bytes(int width, int height, int nframes) {
   if (width <= 0 || height <= 0 || nframes <= 0) return 0;
-  return (size_t)nframes * ((width + 63) / 64) * ((height + 63) / 64) * 8 * sizeof(uint64_t);
+  return (size_t)nframes * av1mi::sb_count(width, height) * 8 * sizeof(uint64_t);
 }
 int av1mi_cdef_search(av1mi_ctx *ctx, const av1mi_cdef_search_job *j) {
   BIND(ctx);
   if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
   if (int rc = check_bd(ctx, j->bit_depth)) return rc;
-  if (j->width <= 0 || j->height <= 0 || (j->width & 7) || (j->height & 7) || j->width > 16384 || j->height > 16384)
-    return fail(ctx, AV1MI_E_INVAL, "frame %dx%d must be a multiple of 8", j->width, j->height);
+  if (int rc = check_frame420(ctx, j->width, j->height, j->stride_y, j->stride_uv, true)) return rc;
   if (int rc = check_nframes(ctx, j->nframes)) return rc;
-  if (j->stride_y < j->width || j->stride_uv < j->width / 2 || (j->stride_y & 3) || (j->stride_uv & 3)) return fail(ctx, AV1MI_E_INVAL, "bad strides");
-  const int tw = j->true_width ? j->true_width : j->width, th = j->true_height ? j->true_height : j->height;
-  if (tw > j->width || th > j->height || tw <= j->width - 8 || th <= j->height - 8) return fail(ctx, AV1MI_E_INVAL, "true size %dx%d does not round up to %dx%d", tw, th, j->width, j->height);
+  int tw, th;
+  if (int rc = check_true_size(ctx, j->width, j->height, j->true_width, j->true_height, &tw, &th)) return rc;
   if (!j->params || j->bits < 1 || j->bits > 3) return fail(ctx, AV1MI_E_INVAL, "CDEF search: bits %d outside 1 .. 3, or no frame parameters", j->bits);
   if (j->params->cdef_damping < 3 || j->params->cdef_damping > 6) return fail(ctx, AV1MI_E_INVAL, "bad damping/nframes");
-  const void *ptrs[] = { j->d_src_y, j->d_src_u, j->d_src_v, j->d_orig_y, j->d_orig_u, j->d_orig_v, j->d_sse };
-  for (const void *p : ptrs) if (!p || ((uintptr_t)p & 7)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned device pointer");
-  if (!j->d_skip8 || !j->d_strength || !j->d_idx || ((uintptr_t)j->d_strength & 3)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned map pointer");
+  if (int rc = check_pointers(ctx, "device", 8, { j->d_src_y, j->d_src_u, j->d_src_v, j->d_orig_y, j->d_orig_u, j->d_orig_v, j->d_sse })) return rc;
+  if (int rc = check_pointers(ctx, "map", 1, { j->d_skip8, j->d_idx })) return rc;
+  if (int rc = check_pointers(ctx, "map", 4, { j->d_strength })) return rc;
   if (j->nframes == 0) return AV1MI_OK;
   av1mi::CdefSearchLaunch L;
   memset(&L, 0, sizeof(L));
-  L.src[0] = j->d_src_y; L.src[1] = j->d_src_u; L.src[2] = j->d_src_v; L.orig[0] = j->d_orig_y; L.orig[1] = j->d_orig_u; L.orig[2] = j->d_orig_v;
+  planes3(L.src, j->d_src_y, j->d_src_u, j->d_src_v); planes3(L.orig, j->d_orig_y, j->d_orig_u, j->d_orig_v);
   L.w = j->width; L.h = j->height; L.tw = tw; L.th = th; L.stride_y = j->stride_y; L.stride_uv = j->stride_uv; L.bd = j->bit_depth;
   L.damping = j->params->cdef_damping; L.nframes = j->nframes; L.ncand = 1 << j->bits;
   L.skip8 = j->d_skip8; L.skip_frame_stride = j->skip_frame_stride;
@@ -528,31 +541,29 @@ int av1mi_lf_search_levels(const av1mi_frame_params *p, int c, int out[4]) {
 }
 size_t av1mi_lf_search_scratch_bytes(int width, int height, int nframes) {
   if (width <= 0 || height <= 0 || nframes <= 0) return 0;
-  return (size_t)nframes * ((width + 63) / 64) * ((height + 63) / 64) * 2 * AV1MI_LF_SEARCH_CANDIDATES * sizeof(uint64_t);
+  return (size_t)nframes * av1mi::sb_count(width, height) * 2 * AV1MI_LF_SEARCH_CANDIDATES * sizeof(uint64_t);
 }
 int av1mi_lf_search(av1mi_ctx *ctx, const av1mi_lf_search_job *j) {
   BIND(ctx);
   if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
   if (int rc = check_bd(ctx, j->bit_depth)) return rc;
-  if (j->width <= 0 || j->height <= 0 || (j->width & 7) || (j->height & 7) || j->width > 16384 || j->height > 16384)
-    return fail(ctx, AV1MI_E_INVAL, "frame %dx%d must be a multiple of 8", j->width, j->height);
+  if (int rc = check_frame420(ctx, j->width, j->height, j->stride_y, j->stride_uv, true)) return rc;
   if (int rc = check_nframes(ctx, j->nframes)) return rc;
-  if (j->stride_y < j->width || j->stride_uv < j->width / 2 || (j->stride_y & 3) || (j->stride_uv & 3)) return fail(ctx, AV1MI_E_INVAL, "bad strides");
   if (j->mi_stride_y < j->width / 4 || j->mi_stride_uv < j->width / 8)
     return fail(ctx, AV1MI_E_INVAL, "bad plane geometry %dx%d strides %d/%d/%d", j->width, j->height, j->stride_y, j->mi_stride_y, j->mi_stride_uv);
-  const int tw = j->true_width ? j->true_width : j->width, th = j->true_height ? j->true_height : j->height;
-  if (tw > j->width || th > j->height || tw <= j->width - 8 || th <= j->height - 8) return fail(ctx, AV1MI_E_INVAL, "true size %dx%d does not round up to %dx%d", tw, th, j->width, j->height);
+  int tw, th;
+  if (int rc = check_true_size(ctx, j->width, j->height, j->true_width, j->true_height, &tw, &th)) return rc;
   if (const char *why = lf_search_error(j->params)) return fail(ctx, AV1MI_E_INVAL, "deblocking search: %s", why);
   if (j->params->lf_sharpness < 0 || j->params->lf_sharpness > 7) return fail(ctx, AV1MI_E_INVAL, "sharpness %d out of range", j->params->lf_sharpness);
-  const void *ptrs[] = { j->d_rec_y, j->d_rec_u, j->d_rec_v, j->d_orig_y, j->d_orig_u, j->d_orig_v, j->d_scratch, j->d_sse };
-  for (const void *p : ptrs) if (!p || ((uintptr_t)p & 7)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned device pointer");
-  if (!j->d_mi_y || !j->d_mi_uv || !j->d_choice || !j->d_levels || ((uintptr_t)j->d_levels & 3)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned map pointer");
+  if (int rc = check_pointers(ctx, "device", 8, { j->d_rec_y, j->d_rec_u, j->d_rec_v, j->d_orig_y, j->d_orig_u, j->d_orig_v, j->d_scratch, j->d_sse })) return rc;
+  if (int rc = check_pointers(ctx, "map", 1, { j->d_mi_y, j->d_mi_uv, j->d_choice })) return rc;
+  if (int rc = check_pointers(ctx, "map", 4, { j->d_levels })) return rc;
   if (!j->d_mi_y_out != !j->d_mi_uv_out) return fail(ctx, AV1MI_E_INVAL, "deblocking search: give both output maps or neither");
   if (j->d_mi_y_out == j->d_mi_y || j->d_mi_uv_out == j->d_mi_uv) return fail(ctx, AV1MI_E_INVAL, "null or aliased device pointer");
   if (j->nframes == 0) return AV1MI_OK;
   av1mi::LfSearchLaunch L;
   memset(&L, 0, sizeof(L));
-  L.rec[0] = j->d_rec_y; L.rec[1] = j->d_rec_u; L.rec[2] = j->d_rec_v; L.orig[0] = j->d_orig_y; L.orig[1] = j->d_orig_u; L.orig[2] = j->d_orig_v;
+  planes3(L.rec, j->d_rec_y, j->d_rec_u, j->d_rec_v); planes3(L.orig, j->d_orig_y, j->d_orig_u, j->d_orig_v);
   L.w = j->width; L.h = j->height; L.tw = tw; L.th = th; L.stride_y = j->stride_y; L.stride_uv = j->stride_uv; L.bd = j->bit_depth;
   L.sharpness = j->params->lf_sharpness; L.nframes = j->nframes;
   L.mi_y = j->d_mi_y; L.mi_uv = j->d_mi_uv; L.mi_stride_y = j->mi_stride_y; L.mi_stride_uv = j->mi_stride_uv;
@@ -587,25 +598,22 @@ int av1mi_deblock_cdef_frames(av1mi_ctx *ctx, const av1mi_deblock_cdef_job *j) {
   BIND(ctx);
   if (!j) return fail(ctx, AV1MI_E_INVAL, "null job");
   if (int rc = check_bd(ctx, j->bit_depth)) return rc;
-  if (j->width <= 0 || j->height <= 0 || (j->width & 7) || (j->height & 7)) return fail(ctx, AV1MI_E_INVAL, "frame %dx%d must be a multiple of 8", j->width, j->height);
+  if (int rc = check_frame420(ctx, j->width, j->height, j->rec_stride_y, j->rec_stride_uv, false)) return rc;
+  if (int rc = check_frame420(ctx, j->width, j->height, j->dbl_stride_y, j->dbl_stride_uv, false)) return rc;
+  if (int rc = check_frame420(ctx, j->width, j->height, j->dst_stride_y, j->dst_stride_uv, false)) return rc;
   if (j->damping < 3 || j->damping > 6) return fail(ctx, AV1MI_E_INVAL, "bad damping/nframes");
   if (int rc = check_nframes(ctx, j->nframes)) return rc;
   if (j->sharpness < 0 || j->sharpness > 7) return fail(ctx, AV1MI_E_INVAL, "sharpness %d out of range", j->sharpness);
-  const int sy[] = { j->rec_stride_y, j->dbl_stride_y, j->dst_stride_y }, suv[] = { j->rec_stride_uv, j->dbl_stride_uv, j->dst_stride_uv };
-  for (int i = 0; i < 3; i++)
-    if (sy[i] < j->width || suv[i] < j->width / 2 || (sy[i] & 3) || (suv[i] & 3)) return fail(ctx, AV1MI_E_INVAL, "bad strides");
   if (j->mi_stride_y < j->width / 4 || j->mi_stride_uv < j->width / 8)
     return fail(ctx, AV1MI_E_INVAL, "bad plane geometry %dx%d strides %d/%d/%d", j->width, j->height, j->rec_stride_y, j->mi_stride_y, j->mi_stride_uv);
   const void *ptrs[] = { j->d_rec_y, j->d_rec_u, j->d_rec_v, j->d_dbl_y, j->d_dbl_u, j->d_dbl_v, j->d_dst_y, j->d_dst_u, j->d_dst_v };
-  for (const void *p : ptrs) if (!p || ((uintptr_t)p & 7)) return fail(ctx, AV1MI_E_INVAL, "null or misaligned device pointer");
+  if (int rc = check_pointers(ctx, "device", 8, ptrs)) return rc;
   for (int a = 0; a < 9; a++)
     for (int b = a + 1; b < 9; b++) if (ptrs[a] == ptrs[b]) return fail(ctx, AV1MI_E_INVAL, "null or aliased device pointer");
-  if (!j->d_mi_y || !j->d_mi_uv || !j->d_sb_strength || !j->d_skip8) return fail(ctx, AV1MI_E_INVAL, "null map pointer");
+  if (int rc = check_pointers(ctx, "map", 1, { j->d_mi_y, j->d_mi_uv, j->d_sb_strength, j->d_skip8 })) return rc;
   if (j->nframes == 0) return AV1MI_OK;
   av1mi::DeblockCdefLaunch L;
-  L.rec[0] = j->d_rec_y; L.rec[1] = j->d_rec_u; L.rec[2] = j->d_rec_v;
-  L.dbl[0] = j->d_dbl_y; L.dbl[1] = j->d_dbl_u; L.dbl[2] = j->d_dbl_v;
-  L.dst[0] = j->d_dst_y; L.dst[1] = j->d_dst_u; L.dst[2] = j->d_dst_v;
+  planes3(L.rec, j->d_rec_y, j->d_rec_u, j->d_rec_v); planes3(L.dbl, j->d_dbl_y, j->d_dbl_u, j->d_dbl_v); planes3(L.dst, j->d_dst_y, j->d_dst_u, j->d_dst_v);
   L.w = j->width; L.h = j->height; L.rec_stride_y = j->rec_stride_y; L.rec_stride_uv = j->rec_stride_uv; L.dbl_stride_y = j->dbl_stride_y;
   L.dbl_stride_uv = j->dbl_stride_uv; L.dst_stride_y = j->dst_stride_y; L.dst_stride_uv = j->dst_stride_uv;
   L.bd = j->bit_depth; L.damping = j->damping; L.sharpness = j->sharpness; L.nframes = j->nframes;

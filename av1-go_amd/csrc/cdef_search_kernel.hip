@@ -6,7 +6,7 @@
 //   PARAMETERS  direction and variance of every 8x8 block, once (wave 0, a block per lane: cdef_block_dirvar) — they do not depend on
 //               the strengths — and from them every candidate's per-block record (cdef_block_pack: 2 per lane at 8 candidates);
 //   SOURCE      each lane's 16 luma + 8 chroma source samples into registers, once, with how many of each four lie inside the TRUE
-//               frame size;
+//               frame size (search_sse.hpp: SbSource, and the error and the sums below);
 //   CANDIDATES  per candidate the filter items of cdef_filter.hpp, whose sink adds the squared difference to the source into a
 //               register (a lane's 24 samples: below 2^25), reduced over the wave (below 2^31) into LDS;
 //   PICK        the workgroup owns its superblock: thread 0 adds the four waves' sums in 64 bits, takes the arg-min (lowest sum, then
@@ -17,31 +17,9 @@
 #include <stdint.h>
 #include "av1mi_internal.hpp"
 #include "cdef_filter.hpp"
+#include "search_sse.hpp"
 
 namespace av1mi {
-
-// four source samples as they lie in memory
-template <typename Pix> struct CdefSrc4 { uint32_t w[sizeof(Pix) == 1 ? 1 : 2]; };
-template <typename Pix> __device__ __forceinline__ CdefSrc4<Pix> cdef_load4(const Pix *p) {
-  CdefSrc4<Pix> v;
-  if constexpr (sizeof(Pix) == 1) v.w[0] = *reinterpret_cast<const uint32_t *>(p);
-  else { const uint2 u = *reinterpret_cast<const uint2 *>(p); v.w[0] = u.x; v.w[1] = u.y; }
-  return v;
-}
-template <typename Pix> __device__ __forceinline__ int cdef_src_at(const CdefSrc4<Pix> &v, int i) {
-  if constexpr (sizeof(Pix) == 1) return (int)((v.w[0] >> (8 * i)) & 255u);
-  else return (int)((v.w[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
-}
-// the squared difference of the first n of four samples
-template <typename Pix> __device__ __forceinline__ uint32_t cdef_sq4(const int (&o)[4], const CdefSrc4<Pix> &s, int n) {
-  uint32_t e = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int d = o[i] - cdef_src_at<Pix>(s, i);
-    e += i < n ? (uint32_t)(d * d) : 0u;
-  }
-  return e;
-}
 
 template <typename Pix>
 __global__ __launch_bounds__(256) void k_cdef_search(CdefSearchLaunch L) {
@@ -58,8 +36,7 @@ __global__ __launch_bounds__(256) void k_cdef_search(CdefSearchLaunch L) {
   const Tile3 tl = xcd_tile(sbw, sbh, L.nframes);
   const int sbx = tl.x, sby = tl.y, f = tl.z;
   constexpr int bd = sizeof(Pix) == 1 ? 8 : 10, cs = bd - 8;
-  const int cw = L.w / 2, chh = L.h / 2;
-  const size_t oy = (size_t)f * L.h * L.stride_y, oc = (size_t)f * chh * L.stride_uv;
+  const size_t oy = (size_t)f * L.h * L.stride_y, oc = (size_t)f * (L.h / 2) * L.stride_uv;
   if (tid >= 192) {
     const int b = tid - 192, fy8 = sby * 8 + (b >> 3), fx8 = sbx * 8 + (b & 7);
     bskip[b] = (fy8 < (L.h >> 3) && fx8 < (L.w >> 3)) ? L.skip8[(size_t)f * L.skip_frame_stride + (size_t)fy8 * (L.w >> 3) + fx8] : (uint8_t)1;
@@ -67,23 +44,8 @@ __global__ __launch_bounds__(256) void k_cdef_search(CdefSearchLaunch L) {
   const bool interior = sbx > 0 && sby > 0 && sbx * 64 + 66 <= L.w && sby * 64 + 66 <= L.h;
   cdef_stage_tiles<Pix, YS, CSZ>(ty, tc, reinterpret_cast<const Pix *>(L.src[0]) + oy, reinterpret_cast<const Pix *>(L.src[1]) + oc,
                                  reinterpret_cast<const Pix *>(L.src[2]) + oc, L.stride_y, L.stride_uv, sbx, sby, L.w, L.h, interior, tid);
-  // the lane's source samples, and how many of each four count: those inside the true size
-  CdefSrc4<Pix> sy[4], sc[2];
-  int ny[4], nc[2];
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const int q = tid + 256 * k, fy = sby * 64 + (q >> 4), fx = sbx * 64 + (q & 15) * 4;
-    sy[k] = CdefSrc4<Pix>{};
-    ny[k] = fy < L.th ? min(max(L.tw - fx, 0), 4) : 0;
-    if (fy < L.h && fx < L.w) sy[k] = cdef_load4(reinterpret_cast<const Pix *>(L.orig[0]) + oy + row_off(fy, L.stride_y) + fx);
-  }
-#pragma unroll
-  for (int k = 0; k < 2; k++) {      // (item tid + 256 k is plane k's)
-    const int fy = sby * 32 + ((tid >> 3) & 31), fx = sbx * 32 + (tid & 7) * 4;
-    sc[k] = CdefSrc4<Pix>{};
-    nc[k] = fy < (L.th + 1) / 2 ? min(max((L.tw + 1) / 2 - fx, 0), 4) : 0;
-    if (fy < chh && fx < cw) sc[k] = cdef_load4(reinterpret_cast<const Pix *>(L.orig[1 + k]) + oc + row_off(fy, L.stride_uv) + fx);
-  }
+  SbSource<Pix> src;      // SOURCE: the lane's samples, and how many of each four count
+  src.load(L.orig, oy, oc, L.stride_y, L.stride_uv, sbx, sby, L.w, L.h, L.tw, L.th, tid);
   __syncthreads();
   // direction and variance: lane b of wave 0 owns 8x8 block b (raster within the superblock); 0 for a block outside the picture
   if (tid < 64) {
@@ -100,22 +62,21 @@ __global__ __launch_bounds__(256) void k_cdef_search(CdefSearchLaunch L) {
 #pragma unroll
     for (int k = 0; k < 4; k++)
       cdef_luma_item<YS>(tid + 256 * k, ty + 2 * YS + 2, sbx, sby, L.w, L.h, S, interior, bskip, bpar[c], offy,
-                         [&](int, int, const int (&o)[4]) { e += cdef_sq4<Pix>(o, sy[k], ny[k]); });
+                         [&](int, int, const int (&o)[4]) { e += sq_diff4<Pix>(o, src.sy[k], src.ny[k]); });
 #pragma unroll
     for (int k = 0; k < 2; k++)
       cdef_chroma_item<CSZ>(tid + 256 * k, tc[0] + 2 * CSZ + 2, tc[1] + 2 * CSZ + 2, sbx, sby, L.w, L.h, S, interior, bskip, bpar[c], offc,
-                            [&](int, int, int, const int (&o)[4]) { e += cdef_sq4<Pix>(o, sc[k], nc[k]); });
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) e += __shfl_xor(e, d, 64);
+                            [&](int, int, int, const int (&o)[4]) { e += sq_diff4<Pix>(o, src.sc[k], src.nc[k]); });
+    e = wave_sum(e);
     if ((tid & 63) == 0) wsum[c][tid >> 6] = e;
   }
   __syncthreads();
   if (tid == 0) {
-    const size_t sb = (size_t)f * sbw * sbh + (size_t)sby * sbw + sbx;
+    const size_t sb = (size_t)f * sb_count(L.w, L.h) + (size_t)sby * sbw + sbx;
     unsigned long long best = 0;
     int pick = 0;
     for (int c = 0; c < 8; c++) {
-      const unsigned long long s = c < L.ncand ? (unsigned long long)wsum[c][0] + wsum[c][1] + wsum[c][2] + wsum[c][3] : 0ull;
+      const unsigned long long s = c < L.ncand ? wave_sums_total(wsum[c]) : 0ull;
       L.sse[sb * 8 + c] = s;
       if (c < L.ncand && (c == 0 || s < best)) { best = s; pick = c; }
     }
@@ -125,7 +86,7 @@ __global__ __launch_bounds__(256) void k_cdef_search(CdefSearchLaunch L) {
 }
 
 hipError_t launch_cdef_search(const CdefSearchLaunch &L, hipStream_t s) {
-  const dim3 grid((unsigned)(((L.w + 63) / 64) * ((L.h + 63) / 64) * L.nframes));   // 1-D: the kernel orders the tiles itself (xcd_tile)
+  const dim3 grid((unsigned)(sb_count(L.w, L.h) * L.nframes));   // 1-D: the kernel orders the tiles itself (xcd_tile)
   if (L.bd == 8) hipLaunchKernelGGL(k_cdef_search<uint8_t>, grid, dim3(256), 0, s, L);
   else hipLaunchKernelGGL(k_cdef_search<uint16_t>, grid, dim3(256), 0, s, L);
   return hipGetLastError();

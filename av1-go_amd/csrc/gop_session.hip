@@ -12,8 +12,10 @@
 //                     main: wait uploaded -> [k_input_convert] -> [k_chroma_convert] -> [k_scale | k_crop_copy]
 //   code_blocks       main: k_intra_pipe | [k_me_down + k_me_coarse] + k_me_int + k_inter_pipe -> kernel_done
 //   download_symbols  down: wait kernel_done -> D2H of the symbols into pinned memory
-//   loop_filters      main: deblock + CDEF (one kernel), k_lr_yuv (the sampled tiles of the three planes) -> k_lr_decide -> k_lr_yuv (the rest where
-//                     restoration stays on) -> reference -> filters_done;  down: (symbols for the host) the decision -> downloaded
+//   loop_filters      main: deblock_search ([lf_search]: levels and a map per frame), deblock_cdef (one kernel; at a padded size or with [cdef_search]
+//                     the two on their own, the search between them), restore ([lr_search], k_lr_yuv (the sampled tiles of the three planes) ->
+//                     k_lr_decide -> k_lr_yuv (the rest where restoration stays on) -> reference) -> filters_done;  down: download_search_results
+//                     (the searches' mirrors -> search_down), (symbols for the host) the decision -> downloaded
 //   measure_quality   main: (quality_stats) k_quality_tiles + k_quality_sum, the records written into the slot's pinned memory -> quality_done
 //   start_coder       side: (GPU entropy coding) wait filters_done -> two memsets, k_av1_info / tokens / chains;  back: k_av1_code -> k_av1_gather,
 //                     which stores payloads, tile sizes, total + status and the decision into the slot's pinned buffers -> ent_done (no copies)
@@ -115,17 +117,17 @@ struct Slot {
   // restoration on / off per (segment, plane), decided by the GPU against the source (k_lr + k_lr_decide): device + pinned mirror
   void *d_lr_on = nullptr, *h_lr_on = nullptr;
   // lr_search: the batch's chosen unit records per plane, the cost table and the index bytes — per SLOT: the tokenizer of batch t reads
-  // the records while the filters of batch t + 1 run — and their pinned mirrors, copied behind the filters in front of lr_down
+  // the records while the filters of batch t + 1 run — and their pinned mirrors
   void *d_lr_units[3] = {}, *h_lr_units[3] = {}, *d_lr_cost = nullptr, *d_lr_choice = nullptr, *h_lr_choice = nullptr;
-  hipEvent_t lr_down = nullptr;
-  // cdef_search: the batch's cost table, the chosen strength records and index bytes — per SLOT for the same reason — the indices'
-  // pinned mirror, copied behind the filters in front of cdef_down
+  // cdef_search: the batch's cost table, the chosen strength records and index bytes — per SLOT for the same reason — the indices' mirror
   void *d_cdef_cost = nullptr, *d_cdef_rec = nullptr, *d_cdef_idx = nullptr, *h_cdef_idx = nullptr;
-  hipEvent_t cdef_down = nullptr;
   // lf_search: the batch's header levels [segment][4] and chosen candidates [segment][2] — per SLOT: the host reads them while later
-  // batches search — their pinned mirrors, copied behind the filters in front of lf_down
+  // batches search — and their pinned mirrors
   void *d_lf_levels = nullptr, *h_lf_levels = nullptr, *d_lf_choice = nullptr, *h_lf_choice = nullptr;
-  hipEvent_t lf_down = nullptr;
+  // the searches' results path: what the enabled searches send to the host with every batch, in the order slot_buffers() allocated it (lr
+  // units x 3, lr choice, cdef idx, lf levels, lf choice), copied behind the filters on the download stream in front of search_down
+  struct Mirror { const void *device; void *pinned; size_t bytes; } mirror[7] = {}; int mirrors = 0;
+  hipEvent_t search_down = nullptr;
   int frame_type = 0;
   int q = 0;                          // the batch's quantiser (av1mi_gop_set_base_q_idx) and what the policy derives from it for its frame type
   av1mi_frame_params params{};
@@ -293,24 +295,22 @@ int slot_buffers(av1mi_gop *g, Slot &s) {
     G_HIP(hipEventCreateWithFlags(&s.grain_done, hipEventDisableTiming));
     if (c.grain_cov) G_TRY(host_alloc(g, &s.h_grain_cov, (size_t)S * 3 * sizeof(av1mi_grain_cov_record)));
   }
+  auto mirrored = [&](void **d, void **h, size_t bytes) {      // a search's result the host gets: device array + pinned mirror, entered into the slot's table
+    G_TRY(dev_alloc(g, d, bytes)); G_TRY(host_alloc(g, h, bytes));
+    s.mirror[s.mirrors++] = { *d, *h, bytes }; return (int)AV1MI_OK;
+  };
   if (c.lr_search) {
-    for (int p = 0; p < 3; p++) { G_TRY(dev_alloc(g, &s.d_lr_units[p], (size_t)S * g->lr_units[p] * 8)); G_TRY(host_alloc(g, &s.h_lr_units[p], (size_t)S * g->lr_units[p] * 8)); }
-    const size_t n = (size_t)S * (g->lr_units[0] + g->lr_units[1] + g->lr_units[2]);
+    for (int p = 0; p < 3; p++) G_TRY(mirrored(&s.d_lr_units[p], &s.h_lr_units[p], (size_t)S * g->lr_units[p] * 8));
     G_TRY(dev_alloc(g, &s.d_lr_cost, av1mi_lr_search_scratch_bytes(c.width, c.height, 64, S)));
-    G_TRY(dev_alloc(g, &s.d_lr_choice, n)); G_TRY(host_alloc(g, &s.h_lr_choice, n));
-    G_HIP(hipEventCreateWithFlags(&s.lr_down, hipEventDisableTiming));
+    G_TRY(mirrored(&s.d_lr_choice, &s.h_lr_choice, (size_t)S * (g->lr_units[0] + g->lr_units[1] + g->lr_units[2])));
   }
   if (c.cdef_search) {
-    const size_t nsb = (size_t)S * ((c.width + 63) / 64) * ((c.height + 63) / 64);
+    const size_t nsb = (size_t)S * av1mi::sb_count(c.width, c.height);
     G_TRY(dev_alloc(g, &s.d_cdef_cost, av1mi_cdef_search_table_bytes(c.width, c.height, S)));
-    G_TRY(dev_alloc(g, &s.d_cdef_rec, nsb * 4)); G_TRY(dev_alloc(g, &s.d_cdef_idx, nsb)); G_TRY(host_alloc(g, &s.h_cdef_idx, nsb));
-    G_HIP(hipEventCreateWithFlags(&s.cdef_down, hipEventDisableTiming));
+    G_TRY(dev_alloc(g, &s.d_cdef_rec, nsb * 4)); G_TRY(mirrored(&s.d_cdef_idx, &s.h_cdef_idx, nsb));
   }
-  if (c.lf_search) {
-    G_TRY(dev_alloc(g, &s.d_lf_levels, (size_t)S * 4)); G_TRY(host_alloc(g, &s.h_lf_levels, (size_t)S * 4));
-    G_TRY(dev_alloc(g, &s.d_lf_choice, (size_t)S * 2)); G_TRY(host_alloc(g, &s.h_lf_choice, (size_t)S * 2));
-    G_HIP(hipEventCreateWithFlags(&s.lf_down, hipEventDisableTiming));
-  }
+  if (c.lf_search) { G_TRY(mirrored(&s.d_lf_levels, &s.h_lf_levels, (size_t)S * 4)); G_TRY(mirrored(&s.d_lf_choice, &s.h_lf_choice, (size_t)S * 2)); }
+  if (s.mirrors) G_HIP(hipEventCreateWithFlags(&s.search_down, hipEventDisableTiming));
   if (c.quality_stats) {
     G_TRY(host_alloc(g, &s.h_quality, (size_t)S * 3 * sizeof(av1mi_quality)));
     G_HIP(hipEventCreateWithFlags(&s.quality_done, hipEventDisableTiming));
@@ -323,7 +323,7 @@ int side_information(av1mi_gop *g) {
   const av1mi_gop_config &c = g->cfg;
   const int w = c.width, h = c.height;
   const size_t fy = (size_t)w * h, fc = fy / 4;
-  const int nsb = ((w + 63) / 64) * ((h + 63) / 64);
+  const int nsb = av1mi::sb_count(w, h);
   auto units = [](int n) { const int u = (n + 32) / 64; return u > 1 ? u : 1; };
   const size_t uy = (size_t)units(h) * units(w), uc = (size_t)units(h / 2) * units(w / 2);
   if (c.key_block_size == 32) {
@@ -482,7 +482,7 @@ int setup(av1mi_gop *g) {
   const bool copy = g->cropping && c.crop_width == g->vw && c.crop_height == g->vh;      // a window of the target's size: nothing to resample
   if (c.source_width) g->chain[g->stages++] = copy ? kCrop : kScale;
   if (c.gpu_entropy) {
-    g->tiles = ((w + 63) / 64) * ((h + 63) / 64);
+    g->tiles = av1mi::sb_count(w, h);
     // the size of the batch's frames as packed 4:2:0 samples: a frame codes to several times less at any sane quantiser, and to about
     // that at the finest one (one byte per luma sample, the capacity before, gave an 8-bit key frame at base_q_idx 1 back to the host)
     g->ent_cap = (size_t)w * h * S * 3 * c.bit_depth / 16;
@@ -598,7 +598,7 @@ void av1mi_gop_close(av1mi_gop *g) {
   if (g->up) { (void)hipStreamSynchronize(g->up); (void)hipStreamDestroy(g->up); }
   if (g->down) { (void)hipStreamSynchronize(g->down); (void)hipStreamDestroy(g->down); }
   for (Slot &s : g->slot)
-    for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done, s.quality_done, s.grain_done, s.lr_down, s.cdef_down, s.lf_down })
+    for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done, s.quality_done, s.grain_done, s.search_down })
       if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : { g->store[0].filled, g->store[0].read_done, g->store[1].filled, g->store[1].read_done, g->scene_done, g->put_done[0], g->put_done[1], g->put_done[2] })
     if (e) (void)hipEventDestroy(e);
@@ -809,7 +809,7 @@ static int follow_q(av1mi_gop *g, const Slot &s) {
     g->mi_q[m] = s.q;
   }
   if (g->cdef_q[t] != s.q) {      // one dword per superblock: primary / secondary strength of luma, then of chroma
-    const size_t nsb = (size_t)((g->cfg.width + 63) / 64) * ((g->cfg.height + 63) / 64);
+    const size_t nsb = (size_t)av1mi::sb_count(g->cfg.width, g->cfg.height);
     L.a[L.arrays++] = { (uint32_t *)g->d_cdef_sb[t], nsb, 0u,
                         (uint32_t)(P.cdef_y >> 2) | (uint32_t)(P.cdef_y & 3) << 8 | (uint32_t)(P.cdef_uv >> 2) << 16 | (uint32_t)(P.cdef_uv & 3) << 24, 0u };
     g->cdef_q[t] = s.q;
@@ -821,94 +821,101 @@ static int follow_q(av1mi_gop *g, const Slot &s) {
   return AV1MI_OK;
 }
 
-// in-loop filters: reconstruction -> what the next frame predicts from; then filters_done and (symbols_down) the decision -> downloaded
-static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
+// The stages of loop_filters.  A job's _y / _u / _v fields from a triple of planes
+template <typename T, typename P> static void yuv(T &y, T &u, T &v, const P &planes) { y = planes[0]; u = planes[1]; v = planes[2]; }
+// a true size that is not a multiple of 8: the decoder's restoration clamps at the true last column / row, so the planes it reads are
+// extended from the true size (CDEF reads the planes as they are: it works on the coded size in a decoder too)
+static bool padded(const av1mi_gop *g) { return g->vw != g->cfg.width || g->vh != g->cfg.height; }
+// the deblocking maps a batch's launches read [luma / chroma], and the units between the frames' maps (0 = the one shared map)
+struct LfMaps { void *const *mi; size_t frame_stride[2]; };
+
+// The batch's deblocking maps: the frame type's shared pair at the policy's levels, or (lf_search) the levels of every frame chosen
+// against the source and a map per frame with them
+static int deblock_search(av1mi_gop *g, Slot &s, const void *const src[3], LfMaps &M) {
+  const av1mi_gop_config &c = g->cfg;
+  const int w = c.width, h = c.height;
+  M = { g->d_mi[s.frame_type == 0 && g->key32 ? 2 : s.frame_type], { 0, 0 } };
+  if (!c.lf_search) return AV1MI_OK;
+  av1mi_lf_search_job sj;
+  memset(&sj, 0, sizeof(sj));
+  sj.width = w; sj.height = h; sj.bit_depth = c.bit_depth; sj.nframes = c.segments; sj.stride_y = g->plane[0].w; sj.stride_uv = g->plane[1].w;
+  yuv(sj.d_rec_y, sj.d_rec_u, sj.d_rec_v, g->d_rec); yuv(sj.d_orig_y, sj.d_orig_u, sj.d_orig_v, src);
+  sj.true_width = g->vw; sj.true_height = g->vh; sj.params = &s.params; sj.d_mi_y_out = (uint32_t *)g->d_mi_frames[0]; sj.d_mi_uv_out = (uint32_t *)g->d_mi_frames[1];
+  sj.d_mi_y = (const uint32_t *)M.mi[0]; sj.d_mi_uv = (const uint32_t *)M.mi[1]; sj.mi_stride_y = g->plane[0].w / 4; sj.mi_stride_uv = g->plane[1].w / 4;
+  sj.d_scratch = g->d_lf_table; sj.d_sse = (uint64_t *)g->d_lf_sse; sj.d_choice = (uint8_t *)s.d_lf_choice; sj.d_levels = (uint8_t *)s.d_lf_levels;
+  G_TRY(av1mi_lf_search(g->ctx, &sj));
+  M = { g->d_mi_frames, { (size_t)(w / 4) * (h / 4), (size_t)(w / 8) * (h / 8) } };
+  return AV1MI_OK;
+}
+
+// reconstruction -> deblocked planes (d_dbl) -> CDEF output (d_cdef), with the maps of deblock_search
+static int deblock_cdef(av1mi_gop *g, Slot &s, const void *const src[3], const LfMaps &M) {
   const av1mi_gop_config &c = g->cfg;
   const int w = c.width, h = c.height, S = c.segments, bd = c.bit_depth, key = s.frame_type == 0;
   const av1mi_frame_params &P = s.params;
-  G_TRY(follow_q(g, s));
-  void *const *mi = g->d_mi[key && g->key32 ? 2 : s.frame_type];
-  size_t mi_frame_stride[2] = { 0, 0 };      // units between the frames' maps: 0 = the one shared map
-  if (c.lf_search) {      // the levels of every frame against the source, and a map per frame with them: what every deblocking launch below reads
-    av1mi_lf_search_job sj;
-    memset(&sj, 0, sizeof(sj));
-    sj.width = w; sj.height = h; sj.bit_depth = bd; sj.nframes = S; sj.stride_y = g->plane[0].w; sj.stride_uv = g->plane[1].w;
-    sj.d_rec_y = g->d_rec[0]; sj.d_rec_u = g->d_rec[1]; sj.d_rec_v = g->d_rec[2]; sj.d_orig_y = src[0]; sj.d_orig_u = src[1]; sj.d_orig_v = src[2];
-    sj.true_width = g->vw; sj.true_height = g->vh; sj.params = &P;
-    sj.d_mi_y = (const uint32_t *)mi[0]; sj.d_mi_uv = (const uint32_t *)mi[1]; sj.mi_stride_y = g->plane[0].w / 4; sj.mi_stride_uv = g->plane[1].w / 4;
-    sj.d_scratch = g->d_lf_table; sj.d_sse = (uint64_t *)g->d_lf_sse; sj.d_choice = (uint8_t *)s.d_lf_choice; sj.d_levels = (uint8_t *)s.d_lf_levels;
-    sj.d_mi_y_out = (uint32_t *)g->d_mi_frames[0]; sj.d_mi_uv_out = (uint32_t *)g->d_mi_frames[1];
-    G_TRY(av1mi_lf_search(g->ctx, &sj));
-    mi = g->d_mi_frames;
-    mi_frame_stride[0] = (size_t)(w / 4) * (h / 4); mi_frame_stride[1] = (size_t)(w / 8) * (h / 8);
-  }
   // key frames are coded with skip = 0 everywhere (no block is exempt from CDEF); P frames: the kernel's skip flags, per frame
   // (the slot's next inter kernel is kSlots batches away and ordered behind this CDEF on the main stream, nothing else writes them)
   const uint8_t *skip8 = (const uint8_t *)(key ? g->d_zero_skip : s.d_skip);
   const size_t skip_frame_stride = key ? 0 : (size_t)(w / 8) * (h / 8);
-  // a true size that is not a multiple of 8: the decoder's restoration clamps at the true last column / row (CDEF reads the planes
-  // as they are: it works on the coded size in a decoder too)
-  const bool padded = g->vw != w || g->vh != h;
   // cdef_search: the search reads WHOLE deblocked planes, so every size takes the kernels one by one
-  if (!padded && !c.cdef_search) {
+  if (!padded(g) && !c.cdef_search) {
     // deblocking and CDEF in one kernel: the deblocked samples stay in LDS, and d_dbl receives only the rows restoration reads
     av1mi_deblock_cdef_job fj;
     memset(&fj, 0, sizeof(fj));
     fj.width = w; fj.height = h; fj.bit_depth = bd; fj.nframes = S; fj.damping = P.cdef_damping; fj.sharpness = P.lf_sharpness;
     fj.rec_stride_y = fj.dbl_stride_y = fj.dst_stride_y = g->plane[0].w; fj.rec_stride_uv = fj.dbl_stride_uv = fj.dst_stride_uv = g->plane[1].w;
-    fj.d_rec_y = g->d_rec[0]; fj.d_rec_u = g->d_rec[1]; fj.d_rec_v = g->d_rec[2];
-    fj.d_dbl_y = g->d_dbl[0]; fj.d_dbl_u = g->d_dbl[1]; fj.d_dbl_v = g->d_dbl[2];
-    fj.d_dst_y = g->d_cdef[0]; fj.d_dst_u = g->d_cdef[1]; fj.d_dst_v = g->d_cdef[2];
-    fj.d_mi_y = (const uint32_t *)mi[0]; fj.d_mi_uv = (const uint32_t *)mi[1]; fj.mi_stride_y = g->plane[0].w / 4; fj.mi_stride_uv = g->plane[1].w / 4;
-    fj.mi_frame_stride_y = mi_frame_stride[0]; fj.mi_frame_stride_uv = mi_frame_stride[1];
-    fj.d_sb_strength = (const uint8_t *)g->d_cdef_sb[s.frame_type]; fj.sb_frame_stride = 0;
-    fj.d_skip8 = skip8; fj.skip_frame_stride = skip_frame_stride;
+    yuv(fj.d_rec_y, fj.d_rec_u, fj.d_rec_v, g->d_rec); yuv(fj.d_dbl_y, fj.d_dbl_u, fj.d_dbl_v, g->d_dbl); yuv(fj.d_dst_y, fj.d_dst_u, fj.d_dst_v, g->d_cdef);
+    fj.d_mi_y = (const uint32_t *)M.mi[0]; fj.d_mi_uv = (const uint32_t *)M.mi[1]; fj.mi_stride_y = g->plane[0].w / 4; fj.mi_stride_uv = g->plane[1].w / 4;
+    fj.mi_frame_stride_y = M.frame_stride[0]; fj.mi_frame_stride_uv = M.frame_stride[1];
+    fj.d_sb_strength = (const uint8_t *)g->d_cdef_sb[s.frame_type]; fj.sb_frame_stride = 0; fj.d_skip8 = skip8; fj.skip_frame_stride = skip_frame_stride;
     G_TRY(av1mi_deblock_cdef_frames(g->ctx, &fj));
   } else {
     // the two kernels on their own: extend_plane below replicates row vh - 1 and column vw - 1 of the WHOLE deblocked planes
     // (restoration's boundary rows are clamped at the true size), and the fused kernel writes only four rows in 64 of them
     for (int p = 0; p < 3; p++) {
       const Plane &L = g->plane[p];
-      G_TRY(av1mi_deblock_frames(g->ctx, g->d_rec[p], L.w, g->d_dbl[p], L.w, L.w, L.h, bd, L.ss, (const uint32_t *)mi[L.ss], L.w / 4, mi_frame_stride[L.ss], P.lf_sharpness, S));
+      G_TRY(av1mi_deblock_frames(g->ctx, g->d_rec[p], L.w, g->d_dbl[p], L.w, L.w, L.h, bd, L.ss, (const uint32_t *)M.mi[L.ss], L.w / 4, M.frame_stride[L.ss], P.lf_sharpness, S));
     }
     av1mi_cdef_job cj;
     memset(&cj, 0, sizeof(cj));
     cj.width = w; cj.height = h; cj.bit_depth = bd; cj.nframes = S; cj.damping = P.cdef_damping; cj.stride_y = g->plane[0].w; cj.stride_uv = g->plane[1].w;
-    cj.d_src_y = g->d_dbl[0]; cj.d_src_u = g->d_dbl[1]; cj.d_src_v = g->d_dbl[2];
-    cj.d_dst_y = g->d_cdef[0]; cj.d_dst_u = g->d_cdef[1]; cj.d_dst_v = g->d_cdef[2];
-    cj.d_sb_strength = (const uint8_t *)g->d_cdef_sb[s.frame_type]; cj.sb_frame_stride = 0;
-    cj.d_skip8 = skip8; cj.skip_frame_stride = skip_frame_stride;
+    yuv(cj.d_src_y, cj.d_src_u, cj.d_src_v, g->d_dbl); yuv(cj.d_dst_y, cj.d_dst_u, cj.d_dst_v, g->d_cdef);
+    cj.d_sb_strength = (const uint8_t *)g->d_cdef_sb[s.frame_type]; cj.sb_frame_stride = 0; cj.d_skip8 = skip8; cj.skip_frame_stride = skip_frame_stride;
     if (c.cdef_search) {      // a strength set per superblock and frame against the source; CDEF then runs with the chosen records
       av1mi_cdef_search_job sj;
       memset(&sj, 0, sizeof(sj));
       sj.width = w; sj.height = h; sj.bit_depth = bd; sj.nframes = S; sj.stride_y = cj.stride_y; sj.stride_uv = cj.stride_uv;
-      sj.d_src_y = cj.d_src_y; sj.d_src_u = cj.d_src_u; sj.d_src_v = cj.d_src_v; sj.d_orig_y = src[0]; sj.d_orig_u = src[1]; sj.d_orig_v = src[2];
+      yuv(sj.d_src_y, sj.d_src_u, sj.d_src_v, g->d_dbl); yuv(sj.d_orig_y, sj.d_orig_u, sj.d_orig_v, src);
       sj.d_skip8 = skip8; sj.skip_frame_stride = skip_frame_stride; sj.true_width = g->vw; sj.true_height = g->vh; sj.bits = c.cdef_search; sj.params = &P;
       sj.d_sse = (uint64_t *)s.d_cdef_cost; sj.d_strength = (uint8_t *)s.d_cdef_rec; sj.d_idx = (uint8_t *)s.d_cdef_idx;
       G_TRY(av1mi_cdef_search(g->ctx, &sj));
-      cj.d_sb_strength = sj.d_strength; cj.sb_frame_stride = (size_t)((w + 63) / 64) * ((h + 63) / 64);
+      cj.d_sb_strength = sj.d_strength; cj.sb_frame_stride = (size_t)av1mi::sb_count(w, h);
     }
     G_TRY(av1mi_cdef_frames(g->ctx, &cj));
   }
-  if (padded)
+  if (padded(g))
     for (int p = 0; p < 3; p++) { G_TRY(extend_plane(g, g->plane[p], g->d_dbl[p])); G_TRY(extend_plane(g, g->plane[p], g->d_cdef[p])); }
-  // loop restoration of every frame, and the decision per segment and plane whether it stays ON (it must lower the squared error
-  // against the source): d_ref always receives the restored planes, the next batch's kernels choose between d_ref and d_cdef
+  return AV1MI_OK;
+}
+
+// loop restoration of every frame, and the decision per segment and plane whether it stays ON (it must lower the squared error
+// against the source): d_ref always receives the restored planes, the next batch's kernels choose between d_ref and d_cdef
+static int restore(av1mi_gop *g, Slot &s, const void *const src[3]) {
+  const av1mi_gop_config &c = g->cfg;
+  const int w = c.width, h = c.height, S = c.segments, bd = c.bit_depth;
+  const av1mi_frame_params &P = s.params;
   av1mi_lr_decide_job lj;
   memset(&lj, 0, sizeof(lj));
   lj.width = w; lj.height = h; lj.bit_depth = bd; lj.nframes = S; lj.unit_size = P.lr_unit_size; lj.stride_y = g->plane[0].w; lj.stride_uv = g->plane[1].w;
-  lj.d_cdef_y = g->d_cdef[0]; lj.d_cdef_u = g->d_cdef[1]; lj.d_cdef_v = g->d_cdef[2];
-  lj.d_dbl_y = g->d_dbl[0]; lj.d_dbl_u = g->d_dbl[1]; lj.d_dbl_v = g->d_dbl[2];
-  lj.d_out_y = g->d_ref[0]; lj.d_out_u = g->d_ref[1]; lj.d_out_v = g->d_ref[2];
-  lj.d_orig_y = src[0]; lj.d_orig_u = src[1]; lj.d_orig_v = src[2];
+  yuv(lj.d_cdef_y, lj.d_cdef_u, lj.d_cdef_v, g->d_cdef); yuv(lj.d_dbl_y, lj.d_dbl_u, lj.d_dbl_v, g->d_dbl);
+  yuv(lj.d_out_y, lj.d_out_u, lj.d_out_v, g->d_ref); yuv(lj.d_orig_y, lj.d_orig_u, lj.d_orig_v, src);
   lj.d_units_y = (const int8_t *)g->d_lr[0]; lj.d_units_uv = (const int8_t *)g->d_lr[1];
   lj.d_scratch = g->d_lr_scratch; lj.d_on = (uint8_t *)s.d_lr_on;
   if (c.lr_search) {      // zero the cost table, search, pick; then the restoration and its decision with the batch's own units
     av1mi_lr_search_job sj;
     memset(&sj, 0, sizeof(sj));
     sj.width = w; sj.height = h; sj.bit_depth = bd; sj.nframes = S; sj.unit_size = 64; sj.qindex = s.q; sj.stride_y = lj.stride_y; sj.stride_uv = lj.stride_uv;
-    sj.d_cdef_y = lj.d_cdef_y; sj.d_cdef_u = lj.d_cdef_u; sj.d_cdef_v = lj.d_cdef_v; sj.d_dbl_y = lj.d_dbl_y; sj.d_dbl_u = lj.d_dbl_u; sj.d_dbl_v = lj.d_dbl_v;
-    sj.d_orig_y = src[0]; sj.d_orig_u = src[1]; sj.d_orig_v = src[2];
+    yuv(sj.d_cdef_y, sj.d_cdef_u, sj.d_cdef_v, g->d_cdef); yuv(sj.d_dbl_y, sj.d_dbl_u, sj.d_dbl_v, g->d_dbl); yuv(sj.d_orig_y, sj.d_orig_u, sj.d_orig_v, src);
     sj.d_scratch = s.d_lr_cost; sj.d_units_y = (int8_t *)s.d_lr_units[0]; sj.d_units_u = (int8_t *)s.d_lr_units[1]; sj.d_units_v = (int8_t *)s.d_lr_units[2];
     sj.d_choice = (uint8_t *)s.d_lr_choice;
     G_TRY(av1mi_lr_search(g->ctx, &sj));
@@ -917,29 +924,33 @@ static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
   }
   lj.no_self_guided_units = P.lr_unit_y[0] != 2 && P.lr_unit_uv[0] != 2;
   G_TRY(av1mi::lr_yuv_decide_with(g->ctx, &lj, true));
-  if (padded)      // ... and so do its motion-compensation reads of this frame
+  if (padded(g))      // the next batch's motion compensation reads this frame beyond the true size
     for (int p = 0; p < 3; p++) G_TRY(extend_plane(g, g->plane[p], g->d_ref[p]));
+  return AV1MI_OK;
+}
+
+// The searches' results to the host with every batch (a few KB, for the host writer, the frame header and the statistics): the slot's
+// mirrors in table order on the download stream behind filters_done, then search_down, which av1mi_gop_collect waits for
+static int download_search_results(av1mi_gop *g, Slot &s) {
+  if (!s.mirrors) return AV1MI_OK;
+  G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
+  for (int i = 0; i < s.mirrors; i++) G_HIP(hipMemcpyAsync(s.mirror[i].pinned, s.mirror[i].device, s.mirror[i].bytes, hipMemcpyDeviceToHost, g->down));
+  G_HIP(hipEventRecord(s.search_down, g->down));
+  return AV1MI_OK;
+}
+
+// in-loop filters: reconstruction -> what the next frame predicts from; then filters_done and (symbols_down) the decision -> downloaded
+static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
+  LfMaps maps;
+  G_TRY(follow_q(g, s));
+  G_TRY(deblock_search(g, s, src, maps));
+  G_TRY(deblock_cdef(g, s, src, maps));
+  G_TRY(restore(g, s, src));
   G_HIP(hipEventRecord(s.filters_done, av1mi::ctx_stream(g->ctx)));
-  if (c.lr_search) {      // the records and indices to the host with every batch: a few KB, for the host writer and the statistics
-    G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
-    for (int p = 0; p < 3; p++) G_HIP(hipMemcpyAsync(s.h_lr_units[p], s.d_lr_units[p], (size_t)S * g->lr_units[p] * 8, hipMemcpyDeviceToHost, g->down));
-    G_HIP(hipMemcpyAsync(s.h_lr_choice, s.d_lr_choice, (size_t)S * (g->lr_units[0] + g->lr_units[1] + g->lr_units[2]), hipMemcpyDeviceToHost, g->down));
-    G_HIP(hipEventRecord(s.lr_down, g->down));
-  }
-  if (c.cdef_search) {    // the indices to the host with every batch: a byte per superblock, for the host writer and the statistics
-    G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
-    G_HIP(hipMemcpyAsync(s.h_cdef_idx, s.d_cdef_idx, (size_t)S * ((w + 63) / 64) * ((h + 63) / 64), hipMemcpyDeviceToHost, g->down));
-    G_HIP(hipEventRecord(s.cdef_down, g->down));
-  }
-  if (c.lf_search) {      // the levels and the choice to the host with every batch: six bytes per segment, for the frame header and the statistics
-    G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
-    G_HIP(hipMemcpyAsync(s.h_lf_levels, s.d_lf_levels, (size_t)S * 4, hipMemcpyDeviceToHost, g->down));
-    G_HIP(hipMemcpyAsync(s.h_lf_choice, s.d_lf_choice, (size_t)S * 2, hipMemcpyDeviceToHost, g->down));
-    G_HIP(hipEventRecord(s.lf_down, g->down));
-  }
+  G_TRY(download_search_results(g, s));
   if (s.symbols_down) {
     G_HIP(hipStreamWaitEvent(g->down, s.filters_done, 0));
-    G_HIP(hipMemcpyAsync(s.h_lr_on, s.d_lr_on, (size_t)S * 3, hipMemcpyDeviceToHost, g->down));
+    G_HIP(hipMemcpyAsync(s.h_lr_on, s.d_lr_on, (size_t)g->cfg.segments * 3, hipMemcpyDeviceToHost, g->down));
     G_HIP(hipEventRecord(s.downloaded, g->down));
   }
   return AV1MI_OK;
@@ -1004,7 +1015,7 @@ static int start_coder(av1mi_gop *g, Slot &s) {
   ej.d_lr_on = (const uint8_t *)s.d_lr_on;
   av1mi_av1_entropy_units eu;
   if (c.lr_search) for (int p = 0; p < 3; p++) { eu.d_units[p] = (const int8_t *)s.d_lr_units[p]; eu.frame_stride[p] = (size_t)g->lr_units[p]; }
-  const av1mi_av1_entropy_cdef ec = { c.cdef_search, (const uint8_t *)s.d_cdef_idx, (size_t)((c.width + 63) / 64) * ((c.height + 63) / 64) };
+  const av1mi_av1_entropy_cdef ec = { c.cdef_search, (const uint8_t *)s.d_cdef_idx, (size_t)av1mi::sb_count(c.width, c.height) };
   ej.visible_width = g->vw; ej.visible_height = g->vh;
   ej.key_rows32 = s.frame_type == 0 && g->key32 ? g->key_rows32 : 0;
   memcpy(ej.lr_unit_y, P.lr_unit_y, 8); memcpy(ej.lr_unit_uv, P.lr_unit_uv, 8);
@@ -1169,20 +1180,16 @@ int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out) {
   memset(out, 0, sizeof(*out));
   out->params = s.params;
   out->lr_on = (const uint8_t *)s.h_lr_on;
+  if (s.mirrors) G_HIP(hipEventSynchronize(s.search_down));      // the searches' results, all of them (download_search_results)
   if (g->cfg.lr_search) {
-    G_HIP(hipEventSynchronize(s.lr_down));
     for (int p = 0; p < 3; p++) { out->lr_units[p] = (const int8_t *)s.h_lr_units[p]; out->lr_units_per_frame[p] = g->lr_units[p]; }
     out->lr_choice = (const uint8_t *)s.h_lr_choice;
   }
   if (g->cfg.cdef_search) {
-    G_HIP(hipEventSynchronize(s.cdef_down));
     out->cdef_bits = g->cfg.cdef_search; out->cdef_idx = (const uint8_t *)s.h_cdef_idx;
     av1mi_cdef_search_sets(&s.params, out->cdef_bits, out->cdef_y, out->cdef_uv);
   }
-  if (g->cfg.lf_search) {
-    G_HIP(hipEventSynchronize(s.lf_down));
-    out->lf_levels = (const uint8_t *)s.h_lf_levels; out->lf_choice = (const uint8_t *)s.h_lf_choice;
-  }
+  if (g->cfg.lf_search) { out->lf_levels = (const uint8_t *)s.h_lf_levels; out->lf_choice = (const uint8_t *)s.h_lf_choice; }
   if (g->cfg.quality_stats) { G_HIP(hipEventSynchronize(s.quality_done)); out->quality = (const av1mi_quality *)s.h_quality; }
   if (g->cfg.denoise && s.has_grain) { G_HIP(hipEventSynchronize(s.grain_done)); out->grain = (const av1mi_grain_record *)s.h_grain; out->grain_cov = (const av1mi_grain_cov_record *)s.h_grain_cov; }
   out->segments = g->cfg.segments;

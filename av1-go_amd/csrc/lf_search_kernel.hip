@@ -5,7 +5,7 @@
 //   STAGE       the UNFILTERED 80 x 80 luma tile, the two 40 x 40 chroma tiles and the mode-info words under them into LDS, once, by
 //               deblock_filter.hpp's own staging (lf_stage_load / store, lf_mi_load / store: the calls of k_deblock_cdef);
 //   SOURCE      each lane's 16 luma + 8 chroma source samples of the inner 64 x 64 / 2 x 32 x 32 into registers, once, with how many of
-//               each four lie inside the TRUE frame size;
+//               each four lie inside the TRUE frame size (search_sse.hpp: SbSource, and the error and the sums below);
 //   CANDIDATES  per candidate: the pristine tiles copied to work tiles (LDS to LDS, 16 bytes a lane and trip), the two level bytes of
 //               the LDS mode-info words replaced (k_mi_levels' rule: a word that carries bit 24 is held; so is the 0xFFFFFFFF of a unit
 //               outside the plane), lf_pass0 / lf_pass1 as k_deblock runs them (window only: EXT 0), then the lane's squared
@@ -25,34 +25,10 @@
 #include <stdint.h>
 #include "av1mi_internal.hpp"
 #include "deblock_filter.hpp"
+#include "search_sse.hpp"
 
 namespace av1mi {
 
-// four samples as they lie in memory (the source) ...
-template <typename Pix> struct LfSrc4 { uint32_t w[sizeof(Pix) == 1 ? 1 : 2]; };
-template <typename Pix> __device__ __forceinline__ LfSrc4<Pix> lf_src_load4(const Pix *p) {
-  LfSrc4<Pix> v;
-  if constexpr (sizeof(Pix) == 1) v.w[0] = *reinterpret_cast<const uint32_t *>(p);
-  else { const uint2 u = *reinterpret_cast<const uint2 *>(p); v.w[0] = u.x; v.w[1] = u.y; }
-  return v;
-}
-template <typename Pix> __device__ __forceinline__ int lf_src_at(const LfSrc4<Pix> &v, int i) {
-  if constexpr (sizeof(Pix) == 1) return (int)((v.w[0] >> (8 * i)) & 255u);
-  else return (int)((v.w[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
-}
-// ... against four samples of a tile (uint16, the first at an even index): the squared difference of the first n
-template <typename Pix> __device__ __forceinline__ uint32_t lf_sq4(const uint16_t *t, const LfSrc4<Pix> &s, int n) {
-  const uint32_t *t32 = reinterpret_cast<const uint32_t *>(t);      // (two dwords: the rows are an odd number of dwords apart)
-  const uint2 u = { t32[0], t32[1] };
-  const int o[4] = { (int)(u.x & 0xFFFFu), (int)(u.x >> 16), (int)(u.y & 0xFFFFu), (int)(u.y >> 16) };
-  uint32_t e = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int d = o[i] - lf_src_at<Pix>(s, i);
-    e += i < n ? (uint32_t)(d * d) : 0u;
-  }
-  return e;
-}
 // N16 x 16 bytes LDS to LDS, and the level bytes of N mode-info words
 template <int N16> __device__ __forceinline__ void lf_copy16(uint16_t *dst, const uint16_t *src, int tid) {
   for (int i = tid; i < N16; i += 256) reinterpret_cast<uint4 *>(dst)[i] = reinterpret_cast<const uint4 *>(src)[i];
@@ -101,23 +77,8 @@ __global__ __launch_bounds__(256) void k_lf_search(LfSearchLaunch L) {
     lf_stage_store<Pix, GC>(pc, vu, du_, tid);
     lf_stage_store<Pix, GC>(pc + NC, vv, dv_, tid);
   }
-  // SOURCE: the lane's samples, and how many of each four count: those inside the true size
-  LfSrc4<Pix> sy[4], sc[2];
-  int ny[4], nc[2];
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const int q = tid + 256 * k, fy = sby * 64 + (q >> 4), fx = sbx * 64 + (q & 15) * 4;
-    sy[k] = LfSrc4<Pix>{};
-    ny[k] = fy < L.th ? min(max(L.tw - fx, 0), 4) : 0;
-    if (fy < L.h && fx < L.w) sy[k] = lf_src_load4(reinterpret_cast<const Pix *>(L.orig[0]) + oy + row_off(fy, L.stride_y) + fx);
-  }
-#pragma unroll
-  for (int k = 0; k < 2; k++) {      // (item tid + 256 k is plane k's)
-    const int fy = sby * 32 + ((tid >> 3) & 31), fx = sbx * 32 + (tid & 7) * 4;
-    sc[k] = LfSrc4<Pix>{};
-    nc[k] = fy < (L.th + 1) / 2 ? min(max((L.tw + 1) / 2 - fx, 0), 4) : 0;
-    if (fy < chh && fx < cw) sc[k] = lf_src_load4(reinterpret_cast<const Pix *>(L.orig[1 + k]) + oc + row_off(fy, L.stride_uv) + fx);
-  }
+  SbSource<Pix> src;      // SOURCE: the lane's samples, and how many of each four count
+  src.load(L.orig, oy, oc, L.stride_y, L.stride_uv, sbx, sby, L.w, L.h, L.tw, L.th, tid);
   __syncthreads();
   // CANDIDATES (every condition on c is the launch's: the whole workgroup takes the same way to every barrier)
   const int tid2 = (tid + 128) & 255;      // V's lines start half a workgroup further on than U's (k_deblock_cdef)
@@ -149,17 +110,13 @@ __global__ __launch_bounds__(256) void k_lf_search(LfSearchLaunch L) {
     uint32_t ey = 0, ec = 0;
     if (luma) {
 #pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int q = tid + 256 * k;
-        ey += lf_sq4<Pix>(wy + (GY::HALO + (q >> 4)) * YS + GY::HALO + (q & 15) * 4, sy[k], ny[k]);
-      }
+      for (int k = 0; k < 4; k++) ey += sq_diff4<Pix>(wy + (GY::HALO + sb_luma_row(tid + 256 * k)) * YS + GY::HALO + sb_luma_col(tid + 256 * k), src.sy[k], src.ny[k]);
     }
     if (chroma) {
 #pragma unroll
-      for (int k = 0; k < 2; k++) ec += lf_sq4<Pix>(wc + k * NC + (GC::HALO + ((tid >> 3) & 31)) * CS + GC::HALO + (tid & 7) * 4, sc[k], nc[k]);
+      for (int k = 0; k < 2; k++) ec += sq_diff4<Pix>(wc + k * NC + (GC::HALO + sb_chroma_row(tid)) * CS + GC::HALO + sb_chroma_col(tid), src.sc[k], src.nc[k]);
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { ey += __shfl_xor(ey, d, 64); ec += __shfl_xor(ec, d, 64); }
+    ey = wave_sum(ey); ec = wave_sum(ec);
     if ((tid & 63) == 0) {
       if (luma) wsum[0][c][tid >> 6] = ey;
       if (chroma) wsum[1][c][tid >> 6] = ec;
@@ -168,16 +125,16 @@ __global__ __launch_bounds__(256) void k_lf_search(LfSearchLaunch L) {
   }
   // TABLE: a lane per entry; a twin's entry is the sum of the candidate it repeats
   if (tid < 16) {
-    const int g = tid >> 3, c = tid & 7, src = L.first[g][c];
-    const size_t sb = (size_t)f * sbw * sbh + (size_t)sby * sbw + sbx;
-    L.table[sb * 16 + tid] = (unsigned long long)wsum[g][src][0] + wsum[g][src][1] + wsum[g][src][2] + wsum[g][src][3];
+    const int g = tid >> 3, c = tid & 7, first = L.first[g][c];
+    const size_t sb = (size_t)f * sb_count(L.w, L.h) + (size_t)sby * sbw + sbx;
+    L.table[sb * 16 + tid] = wave_sums_total(wsum[g][first]);
   }
 }
 
 __global__ __launch_bounds__(256) void k_lf_pick(LfSearchLaunch L) {
   __shared__ unsigned long long part[16][16], total[16];
   const int tid = threadIdx.x, f = blockIdx.x, col = tid & 15, stripe = tid >> 4;
-  const size_t nsb = (size_t)((L.w + 63) / 64) * ((L.h + 63) / 64);
+  const size_t nsb = (size_t)sb_count(L.w, L.h);
   const unsigned long long *t = L.table + (size_t)f * nsb * 16;
   unsigned long long s = 0;
   for (size_t sb = stripe; sb < nsb; sb += 16) s += t[sb * 16 + col];
@@ -204,7 +161,7 @@ __global__ __launch_bounds__(256) void k_lf_pick(LfSearchLaunch L) {
 }
 
 hipError_t launch_lf_search(const LfSearchLaunch &L, hipStream_t s) {
-  const dim3 grid((unsigned)(((L.w + 63) / 64) * ((L.h + 63) / 64) * L.nframes));   // 1-D: the kernel orders the tiles itself (xcd_tile)
+  const dim3 grid((unsigned)(sb_count(L.w, L.h) * L.nframes));   // 1-D: the kernel orders the tiles itself (xcd_tile)
   const bool s0 = L.sharpness == 0;
   if (L.bd == 8) { if (s0) hipLaunchKernelGGL((k_lf_search<uint8_t, true>), grid, dim3(256), 0, s, L); else hipLaunchKernelGGL((k_lf_search<uint8_t, false>), grid, dim3(256), 0, s, L); }
   else           { if (s0) hipLaunchKernelGGL((k_lf_search<uint16_t, true>), grid, dim3(256), 0, s, L); else hipLaunchKernelGGL((k_lf_search<uint16_t, false>), grid, dim3(256), 0, s, L); }
