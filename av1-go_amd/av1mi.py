@@ -144,7 +144,7 @@ class GopConfig(C.Structure):
                 ("source_bit_depth", C.c_int), ("store_frames", C.c_int), ("deinterlace", C.c_int), ("denoise", C.c_int),
                 ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int), ("crop_height", C.c_int), ("denoise_range", C.c_int),
                 ("tone_map", C.c_int), ("tone_map_peak", C.c_int), ("grain_cov", C.c_int), ("lr_search", C.c_int),
-                ("cdef_search", C.c_int), ("lf_search", C.c_int)]
+                ("cdef_search", C.c_int), ("lf_search", C.c_int), ("coded_bit_depth", C.c_int), ("depth_dither", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -161,7 +161,7 @@ class GopFrame(C.Structure):
                 ("key_modes_band", C.c_int), ("quality", C.c_void_p), ("grain", C.c_void_p), ("grain_cov", C.c_void_p),
                 ("lr_units", C.c_void_p * 3), ("lr_units_per_frame", C.c_int * 3), ("lr_choice", C.c_void_p),
                 ("cdef_bits", C.c_int), ("cdef_y", C.c_uint8 * 8), ("cdef_uv", C.c_uint8 * 8), ("cdef_idx", C.c_void_p),
-                ("lf_levels", C.c_void_p), ("lf_choice", C.c_void_p)]
+                ("lf_levels", C.c_void_p), ("lf_choice", C.c_void_p), ("bit_depth", C.c_int)]
 
 
 def policy_frame_params(base_q_idx, bit_depth, frame_type):
@@ -210,6 +210,7 @@ def input_plane_bytes(fmt, bit_depth, plane, width, rows):
 
 
 CHROMA_420, CHROMA_422, CHROMA_444, CHROMA_400 = 0, 1, 2, 3      # enum av1mi_source_chroma
+DEPTH_ROUND, DEPTH_ORDERED = 0, 1      # enum av1mi_depth_mode
 
 
 def source_plane_bytes(chroma, source_bit_depth, plane, width, rows):
@@ -288,7 +289,8 @@ class GopSession:
     """av1mi_gop_* (include/av1mi.h): closed GOPs in lockstep, policy and PCIe plumbing inside the library."""
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
-                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None, tone_map=0, tone_map_peak=0, grain_cov=None, lr_search=None, cdef_search=None, lf_search=None):
+                 key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None, tone_map=0, tone_map_peak=0, grain_cov=None, lr_search=None, cdef_search=None, lf_search=None, coded_bit_depth=None,
+                 depth_dither=None):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
@@ -308,7 +310,9 @@ class GopSession:
         denoise_range: 4 or 8, the range of the denoiser's block search (av1mi_gop_config.denoise_range; needs denoise): submit_stored()
         gathers through the motion-compensated filter.  None leaves the field unset (0 = none);
         grain_cov: 1 = the covariance of what the denoiser removed is measured behind the gather (av1mi_gop_config.grain_cov; needs
-        denoise): collect()["grain_cov"] holds the records.  None leaves the field unset (0 = none)"""
+        denoise): collect()["grain_cov"] holds the records.  None leaves the field unset (0 = none);
+        coded_bit_depth: 8 in a bit_depth 10 session = the depth reduction at the end of the input chain: everything behind it is an 8-bit
+        session (av1mi_gop_config.coded_bit_depth); depth_dither: DEPTH_ROUND or DEPTH_ORDERED.  None leaves a field unset (0)"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
         sw, sh = source if source is not None else (0, 0)
@@ -328,6 +332,10 @@ class GopSession:
             self.cfg.lf_search = int(lf_search)
         # tone_map: 1 = every batch is tone-mapped (PQ / BT.2020 -> SDR / BT.709) in place behind the input stages; tone_map_peak: cd/m2, 0 = 1000
         self.cfg.tone_map, self.cfg.tone_map_peak = int(tone_map), int(tone_map_peak)
+        if coded_bit_depth is not None:
+            self.cfg.coded_bit_depth = int(coded_bit_depth)
+        if depth_dither is not None:
+            self.cfg.depth_dither = int(depth_dither)
         if crop is not None:
             self.cfg.crop_x, self.cfg.crop_y, self.cfg.crop_width, self.cfg.crop_height = (int(v) for v in crop)
         self.g = C.c_void_p()
@@ -338,7 +346,8 @@ class GopSession:
                      "av1mi_gop_download_reference"):
             getattr(ctx.lib, name).argtypes = None
         ctx.lib.av1mi_gop_close.restype = None
-        self.dt = np.uint8 if bit_depth == 8 else np.uint16
+        self.coded_bd = self.cfg.coded_bit_depth or bit_depth      # the depth of the reference planes and of the stream
+        self.dt = np.uint8 if self.coded_bd == 8 else np.uint16
 
     def fed_planes(self):
         """(shape, dtype) of the planes of a batch as the session is fed them, from the layout: the planes it has, segments stacked; a
@@ -738,6 +747,14 @@ class Context:
         d_tables (a DevBuf holding a ToneTables); one launch, asynchronous (av1mi_tone_map)"""
         self.lib.av1mi_tone_map.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4
         self._chk(self.lib.av1mi_tone_map(self.h, int(width), int(height), int(frames), d_y.ptr, d_u.ptr, d_v.ptr, d_tables.ptr))
+
+    def depth_reduce(self, mode, width, height, frames, d_in, d_out):
+        """d_in: planar 4:2:0 uint16 planes Y, U, V (DevBuf) of `frames` stacked frames of luma buffer size width x height, d_out: the uint8
+        planes they are reduced to, mode DEPTH_ROUND / DEPTH_ORDERED; one launch, asynchronous (av1mi_depth_reduce)"""
+        self.lib.av1mi_depth_reduce.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2
+        src = (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_in])
+        dst = (C.c_void_p * 3)(*[b.ptr if b is not None else None for b in d_out])
+        self._chk(self.lib.av1mi_depth_reduce(self.h, int(mode), int(width), int(height), int(frames), src, dst))
 
     def scale_planes(self, bit_depth, src_w, src_h, dst_w, dst_h, frames, d_src, d_dst):
         """d_src: planar Y, U, V (DevBuf) of `frames` stacked frames of true size src_w x src_h in buffers of that size rounded up to 8;

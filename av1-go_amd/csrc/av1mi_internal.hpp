@@ -258,6 +258,9 @@ hipError_t launch_crop_copy(const CropWindow &W, int bd, int dst_w, int dst_h, i
 // tone mapping in place (tonemap_kernels.hip, include/av1mi.h "tone mapping"): `frames` stacked frames of planar 4:2:0 10-bit planes of luma size
 // w x h (w a multiple of 4, h even), tables = an av1mi_tone_tables in device memory (16-byte aligned); one launch
 hipError_t launch_tone_map(int w, int h, int frames, void *const planes[3], const void *tables, hipStream_t s);
+// depth reduction (depth_kernels.hip, include/av1mi.h "depth reduction"): `frames` stacked frames of planar 4:2:0 uint16 planes of luma BUFFER size
+// w x h (multiples of 8) -> uint8 planes of the same sizes, mode = enum av1mi_depth_mode; all planes 4-byte aligned; one launch
+hipError_t launch_depth_reduce(int mode, int w, int h, int frames, const void *const in[3], void *const out[3], hipStream_t s);
 // bar detection (crop_kernels.hip, include/av1mi.h "bar detection"): `frames` stacked luma planes of TRUE size w x h in buffers of stride x
 // rows samples -> one record of margins per frame, two launches.  scratch: crop_layout().bytes bytes, 4-byte aligned: a partial per
 // (row, tile column) at 0, a partial per (tile row, column) at off_cols

@@ -901,6 +901,20 @@ int av1mi_tone_map(av1mi_ctx *ctx, int width, int height, int frames, void *d_y,
   return AV1MI_OK;
 }
 
+int av1mi_depth_reduce(av1mi_ctx *ctx, int mode, int width, int height, int frames, const void *const d_in[3], void *const d_out[3]) {
+  BIND(ctx);
+  if (mode != AV1MI_DEPTH_ROUND && mode != AV1MI_DEPTH_ORDERED) return fail(ctx, AV1MI_E_INVAL, "av1mi_depth_reduce: mode %d unknown (0 round, 1 ordered)", mode);
+  if (width < 8 || height < 8 || (width & 7) || (height & 7) || width > 16384 || height > 16384)
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_depth_reduce: the planes' size %dx%d must be a multiple of 8 (8 .. 16384)", width, height);
+  if (frames < 1 || (size_t)frames * (size_t)height > 65535u * 32u) return fail(ctx, AV1MI_E_INVAL, "av1mi_depth_reduce: frames %d out of range", frames);
+  if (!d_in || !d_out) return fail(ctx, AV1MI_E_INVAL, "av1mi_depth_reduce: null plane array");
+  for (int p = 0; p < 3; p++)
+    if (!d_in[p] || !d_out[p] || (((uintptr_t)d_in[p] | (uintptr_t)d_out[p]) & 3)) return fail(ctx, AV1MI_E_INVAL, "av1mi_depth_reduce: null or misaligned device pointer (4 bytes)");
+  ProfScope ps(ctx, AV1MI_K_INPUT);
+  HIP_TRY(ctx, av1mi::launch_depth_reduce(mode, width, height, frames, d_in, d_out, ctx->stream));
+  return AV1MI_OK;
+}
+
 int av1mi_frames_gather(av1mi_ctx *ctx, const size_t plane_bytes[3], int segments, const void *const *d_src_table, void *const d_dst[3]) {
   BIND(ctx);
   if (!plane_bytes || !d_src_table || !d_dst || ((uintptr_t)d_src_table & 7)) return fail(ctx, AV1MI_E_INVAL, "av1mi_frames_gather: null pointer or misaligned table");

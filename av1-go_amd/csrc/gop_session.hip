@@ -9,7 +9,7 @@
 //                     -> store.read_done, in place of the upload; the input stages follow as below.  A session that deinterlaces
 //                     (av1mi_gop_config.deinterlace) launches k_deint_gather in its place: same events, and the store is only read)
 //                     up:   wait slot.filters_done (the kernels that last read this slot's source) -> H2D of the fed buffers -> uploaded
-//                     main: wait uploaded -> [k_input_convert] -> [k_chroma_convert] -> [k_scale | k_crop_copy]
+//                     main: wait uploaded -> [k_input_convert] -> [k_chroma_convert] -> [k_scale | k_crop_copy] -> [k_tone_map] -> [k_depth_reduce]
 //   code_blocks       main: k_intra_pipe | [k_me_down + k_me_coarse] + k_me_int + k_inter_pipe -> kernel_done
 //   download_symbols  down: wait kernel_done -> D2H of the symbols into pinned memory
 //   loop_filters      main: deblock_search ([lf_search]: levels and a map per frame), deblock_cdef (one kernel; at a padded size or with [cdef_search]
@@ -42,6 +42,13 @@
 // slot_buffers() walks the chain once per slot and plane: the last stage that writes a plane writes d_src, a stage before it a plane
 // between (d_pre), and a plane that no stage writes IS d_src from the start (all planes with ZERO stages, the luma plane behind chroma
 // alone): the upload lands where the kernels read.  feed_source() walks it once per batch.
+//
+// The coded depth.  cfg.bit_depth is the depth of the INPUT side: the fed layout, the chain, the tone map.  What everything from
+// code_blocks on works at — planes, policy, pipelines, filters, searches, coder, quality records — is coded_depth(cfg), kept as g->bd, and
+// nothing behind the chain reads cfg.bit_depth.  Where the two differ (cfg.coded_bit_depth 8 in a 10-bit session) the chain ends in d_work,
+// the slot's planar planes at bit_depth and the coded size, instead of d_src, and ONE more launch at the end of feed_source (k_depth_reduce,
+// depth_kernels.hip) writes the 8-bit d_src from wherever the planes are then: d_work, or in a device batch the caller's planes, which it
+// only reads.  A session without the option has no d_work and launches what it always did.
 //
 // The frame store (av1mi_gop_config.store_frames; nothing of it exists at 0).  Two stores of store_frames fed frames, a plane per
 // buffer, frames in file order.  The upload stream carries everything that fills and reads a store for the analysis: the puts (pinned
@@ -107,7 +114,8 @@ struct Slot {
   void *h_in[3] = { nullptr, nullptr, nullptr }, *d_in[3] = { nullptr, nullptr, nullptr };
   void *d_pre[3] = { nullptr, nullptr, nullptr };       // two stages: the planar planes at the fed size that the first one writes
   void *stage_out[kMaxStages][3] = {};                  // where stage k writes plane p, resolved at open; null = the plane passes through
-  void *d_src[3] = { nullptr, nullptr, nullptr };       // planar, coded size: what the block pipeline and the restoration decision read
+  void *d_src[3] = { nullptr, nullptr, nullptr };       // planar, coded size, coded depth: what the block pipeline and the restoration decision read
+  void *d_work[3] = { nullptr, nullptr, nullptr };      // depth reduction: planar, coded size, at bit_depth: where the chain ends; the stage writes d_src
   // symbols: device + pinned host mirror
   void *d_lev[3] = { nullptr, nullptr, nullptr }, *h_lev[3] = { nullptr, nullptr, nullptr };
   void *d_modes[2] = { nullptr, nullptr }, *h_modes[2] = { nullptr, nullptr };
@@ -163,7 +171,8 @@ struct av1mi_gop {
   av1mi_ctx *ctx = nullptr;
   av1mi_gop_config cfg{};
   Plane plane[3];                              // the coded planes
-  size_t nb = 0, bps = 1;                      // blocks of a BATCH (segments stacked), bytes per sample
+  int bd = 8;                                  // the CODED depth (coded_depth(cfg)): what everything behind the input chain works at
+  size_t nb = 0, bps = 1;                      // blocks of a BATCH (segments stacked), bytes per sample of the coded planes
   av1mi_source_layout layout{};                // what the session is fed (av1mi_gop_source_layout(cfg)): the fed side's only geometry
   int stages = 0, chain[kMaxStages] = {};      // the input stages in launch order (Stage)
   uintptr_t fed_align = 8;                     // of the planes av1mi_gop_submit_device is given: 16 where convert or chroma reads them (16-byte loads)
@@ -234,6 +243,10 @@ int host_alloc(av1mi_gop *g, void **p, size_t bytes) {
   return AV1MI_OK;
 }
 
+// THE place that says what depth is coded: the input side's, unless the config asks for the reduction
+int coded_depth(const av1mi_gop_config &c) { return c.coded_bit_depth ? c.coded_bit_depth : c.bit_depth; }
+bool reducing(const av1mi_gop *g) { return g->bd != g->cfg.bit_depth; }
+
 enum Stage { kConvert, kChroma, kScale, kCrop };      // the input stages (the chain of "The source path"); kCrop stands where kScale would
 // Does stage k write plane p?  All do but chroma at equal depths, which passes the luma plane through
 bool stage_writes(const av1mi_gop *g, int k, int p) { return !(g->chain[k] == kChroma && p == 0 && g->layout.bit_depth == g->cfg.bit_depth); }
@@ -259,14 +272,16 @@ int slot_buffers(av1mi_gop *g, Slot &s) {
     // the source: pinned + device as fed, then the chain's planes (a plane that no stage writes is fed straight into d_src)
     if (fed_bytes(g, p)) G_TRY(host_alloc(g, &s.h_in[p], fed_bytes(g, p)));
     G_TRY(dev_alloc(g, &s.d_src[p], P.bytes));
+    void *end = s.d_src[p];      // where the chain leaves the plane: d_src, or in front of the depth reduction d_work
+    if (reducing(g)) { G_TRY(dev_alloc(g, &s.d_work[p], P.n * 2)); end = s.d_work[p]; }
     int last = -1;
     for (int k = 0; k < g->stages; k++) if (stage_writes(g, k, p)) last = k;
-    if (last < 0) s.d_in[p] = s.d_src[p];
+    if (last < 0) s.d_in[p] = end;
     else if (fed_bytes(g, p)) G_TRY(dev_alloc(g, &s.d_in[p], fed_bytes(g, p)));
     for (int k = 0; k <= last; k++) {
       if (!stage_writes(g, k, p)) continue;
       if (k < last) G_TRY(dev_alloc(g, &s.d_pre[p], av1mi_input_plane_bytes(AV1MI_INPUT_PLANAR, c.bit_depth, p, g->layout.width, g->layout.height * S)));
-      s.stage_out[k][p] = k < last ? s.d_pre[p] : s.d_src[p];
+      s.stage_out[k][p] = k < last ? s.d_pre[p] : end;
     }
     // the pinned mirror of the levels (as large as the source) is needed when the symbols go to the host; with the GPU coder
     // only a batch the coder gives back needs it, and it is allocated then (pinning memory is a good part of the start-up time)
@@ -333,7 +348,7 @@ int side_information(av1mi_gop *g) {
     g->key_modes_stride = (h / 8) * (w / 8);
   }
   for (int t = 0; t < 2 + g->key32; t++) {
-    if (t < 2) frame_params(c.base_q_idx, c.bit_depth, t, &g->params[t]);
+    if (t < 2) frame_params(c.base_q_idx, g->bd, t, &g->params[t]);
     const av1mi_frame_params &P = g->params[t == 2 ? 0 : t];
     // deblocking mode-info words (av1mi_deblock_plane): 8x8 luma / 4x4 chroma transforms, every block edge a prediction edge
     std::vector<uint32_t> mi(fy / 16, 3u | (3u << 4) | ((uint32_t)P.lf_level[0] << 8) | ((uint32_t)P.lf_level[1] << 16) | (3u << 25));
@@ -455,6 +470,14 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
   if (c->tone_map && c->bit_depth != 10) return WHY("tone_map needs bit_depth 10, not %d: an HDR10 source has 10 bits", c->bit_depth);
   if (c->tone_map && c->tone_map_peak && (c->tone_map_peak < 100 || c->tone_map_peak > 10000)) return WHY("tone_map_peak %d out of range (100 .. 10000 cd/m2; 0 = 1000)", c->tone_map_peak);
   if (c->tone_map && c->denoise) return WHY("tone_map together with denoise %d is not built: the grain records would be measured in the source's light, the grain synthesised in the output's", c->denoise);
+  if (c->coded_bit_depth != 0 && c->coded_bit_depth != 8 && c->coded_bit_depth != c->bit_depth)
+    return WHY("coded_bit_depth %d not supported with bit_depth %d (0 = bit_depth; 8: a 10-bit session coded at 8 bits)", c->coded_bit_depth, c->bit_depth);
+  if (c->coded_bit_depth == 8 && c->bit_depth == 8) return WHY("coded_bit_depth 8 with bit_depth 8: there is nothing to reduce, leave it 0");
+  if (c->depth_dither < 0 || c->depth_dither > 1) return WHY("depth_dither %d unknown (0 round, 1 ordered)", c->depth_dither);
+  if (c->depth_dither && c->coded_bit_depth != 8) return WHY("depth_dither %d needs coded_bit_depth 8: it is the dither of the depth reduction", c->depth_dither);
+  if (c->coded_bit_depth && c->coded_bit_depth != c->bit_depth && c->denoise)
+    return WHY("coded_bit_depth %d together with denoise %d is not built: the grain records are measured in %d-bit codes and the grain would be synthesised into an 8-bit stream",
+               c->coded_bit_depth, c->denoise, c->bit_depth);
   return nullptr;
 #undef WHY
 }
@@ -462,7 +485,8 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
 int setup(av1mi_gop *g) {
   const av1mi_gop_config &c = g->cfg;
   const int w = c.width, h = c.height, S = c.segments;
-  g->bps = c.bit_depth == 8 ? 1 : 2;
+  g->bd = coded_depth(c);
+  g->bps = g->bd == 8 ? 1 : 2;
   g->vw = c.visible_width ? c.visible_width : w; g->vh = c.visible_height ? c.visible_height : h;
   for (int p = 0; p < 3; p++) {
     Plane &P = g->plane[p];
@@ -485,7 +509,7 @@ int setup(av1mi_gop *g) {
     g->tiles = av1mi::sb_count(w, h);
     // the size of the batch's frames as packed 4:2:0 samples: a frame codes to several times less at any sane quantiser, and to about
     // that at the finest one (one byte per luma sample, the capacity before, gave an 8-bit key frame at base_q_idx 1 back to the host)
-    g->ent_cap = (size_t)w * h * S * 3 * c.bit_depth / 16;
+    g->ent_cap = (size_t)w * h * S * 3 * g->bd / 16;
   }
   G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
   if (c.source_width && !copy)
@@ -506,7 +530,7 @@ int setup(av1mi_gop *g) {
   // the decision's sums, zeroed ONCE: every batch's decision leaves them zero behind it (capi.hip lr_yuv_decide_with: the rule)
   G_HIP(hipMemset(g->d_lr_scratch, 0, av1mi_lr_yuv_decide_scratch_bytes(h, S)));
   if (c.coarse_range) G_TRY(dev_alloc(g, &g->d_me, av1mi::me_layout(w, h, S).bytes));
-  if (c.quality_stats) G_TRY(dev_alloc(g, &g->d_quality_scratch, av1mi::quality_scratch_bytes(c.bit_depth, g->vw, g->vh, S)));
+  if (c.quality_stats) G_TRY(dev_alloc(g, &g->d_quality_scratch, av1mi::quality_scratch_bytes(g->bd, g->vw, g->vh, S)));
   if (c.denoise) {
     av1mi::DenoiseMcLaunch L{};
     fed_geometry(g, nullptr, L);
@@ -714,6 +738,11 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
     void *const planes[3] = { const_cast<void *>(src[0]), const_cast<void *>(src[1]), const_cast<void *>(src[2]) };
     G_HIP(av1mi::launch_tone_map(c.width, c.height, S, planes, g->d_tone_tables, main));
   }
+  if (reducing(g)) {      // the last word of the input side: the planes at bit_depth, wherever they are now (read only) -> the slot's coded planes
+    av1mi::ProfScope ps(g->ctx, AV1MI_K_INPUT, main);
+    G_HIP(av1mi::launch_depth_reduce(c.depth_dither, c.width, c.height, S, src, s.d_src, main));
+    for (int p = 0; p < 3; p++) src[p] = s.d_src[p];
+  }
   return AV1MI_OK;
 }
 
@@ -725,7 +754,7 @@ static int code_blocks(av1mi_gop *g, Slot &s, int frame_type, const void *const 
   if (frame_type == 0) {
     av1mi_intra_job j;
     memset(&j, 0, sizeof(j));
-    j.width = w; j.height = h; j.bit_depth = c.bit_depth; j.nframes = c.segments; j.qindex = s.q; j.block_size = 8; j.stride_y = g->plane[0].w; j.stride_uv = g->plane[1].w;
+    j.width = w; j.height = h; j.bit_depth = g->bd; j.nframes = c.segments; j.qindex = s.q; j.block_size = 8; j.stride_y = g->plane[0].w; j.stride_uv = g->plane[1].w;
     j.d_src_y = src[0]; j.d_src_u = src[1]; j.d_src_v = src[2];
     j.d_rec_y = g->d_rec[0]; j.d_rec_u = g->d_rec[1]; j.d_rec_v = g->d_rec[2];
     j.d_lev_y = (int16_t *)s.d_lev[0]; j.d_lev_u = (int16_t *)s.d_lev[1]; j.d_lev_v = (int16_t *)s.d_lev[2];
@@ -753,7 +782,7 @@ static int code_blocks(av1mi_gop *g, Slot &s, int frame_type, const void *const 
   } else {
     av1mi_inter_job j;
     memset(&j, 0, sizeof(j));
-    j.width = w; j.height = h; j.bit_depth = c.bit_depth; j.nframes = c.segments; j.qindex = s.q; j.search_range = c.search_range; j.stride_y = g->plane[0].w; j.stride_uv = g->plane[1].w;
+    j.width = w; j.height = h; j.bit_depth = g->bd; j.nframes = c.segments; j.qindex = s.q; j.search_range = c.search_range; j.stride_y = g->plane[0].w; j.stride_uv = g->plane[1].w;
     j.d_src_y = src[0]; j.d_src_u = src[1]; j.d_src_v = src[2];
     j.d_ref_y = g->d_ref[0]; j.d_ref_u = g->d_ref[1]; j.d_ref_v = g->d_ref[2];
     j.d_rec_y = g->d_rec[0]; j.d_rec_u = g->d_rec[1]; j.d_rec_v = g->d_rec[2];
@@ -787,7 +816,7 @@ static int download_symbols(av1mi_gop *g, Slot &s) {
 }
 
 static int extend_plane(av1mi_gop *g, const Plane &P, void *d) {
-  return av1mi_extend_frames(g->ctx, d, P.w, P.w, P.h, P.vw, P.vh, g->cfg.bit_depth, g->cfg.segments);
+  return av1mi_extend_frames(g->ctx, d, P.w, P.w, P.h, P.vw, P.vh, g->bd, g->cfg.segments);
 }
 
 // The device state derived from the quantiser follows the batch: the deblocking map pair this batch's filters read (key / inter / key in
@@ -838,7 +867,7 @@ static int deblock_search(av1mi_gop *g, Slot &s, const void *const src[3], LfMap
   if (!c.lf_search) return AV1MI_OK;
   av1mi_lf_search_job sj;
   memset(&sj, 0, sizeof(sj));
-  sj.width = w; sj.height = h; sj.bit_depth = c.bit_depth; sj.nframes = c.segments; sj.stride_y = g->plane[0].w; sj.stride_uv = g->plane[1].w;
+  sj.width = w; sj.height = h; sj.bit_depth = g->bd; sj.nframes = c.segments; sj.stride_y = g->plane[0].w; sj.stride_uv = g->plane[1].w;
   yuv(sj.d_rec_y, sj.d_rec_u, sj.d_rec_v, g->d_rec); yuv(sj.d_orig_y, sj.d_orig_u, sj.d_orig_v, src);
   sj.true_width = g->vw; sj.true_height = g->vh; sj.params = &s.params; sj.d_mi_y_out = (uint32_t *)g->d_mi_frames[0]; sj.d_mi_uv_out = (uint32_t *)g->d_mi_frames[1];
   sj.d_mi_y = (const uint32_t *)M.mi[0]; sj.d_mi_uv = (const uint32_t *)M.mi[1]; sj.mi_stride_y = g->plane[0].w / 4; sj.mi_stride_uv = g->plane[1].w / 4;
@@ -851,7 +880,7 @@ static int deblock_search(av1mi_gop *g, Slot &s, const void *const src[3], LfMap
 // reconstruction -> deblocked planes (d_dbl) -> CDEF output (d_cdef), with the maps of deblock_search
 static int deblock_cdef(av1mi_gop *g, Slot &s, const void *const src[3], const LfMaps &M) {
   const av1mi_gop_config &c = g->cfg;
-  const int w = c.width, h = c.height, S = c.segments, bd = c.bit_depth, key = s.frame_type == 0;
+  const int w = c.width, h = c.height, S = c.segments, bd = g->bd, key = s.frame_type == 0;
   const av1mi_frame_params &P = s.params;
   // key frames are coded with skip = 0 everywhere (no block is exempt from CDEF); P frames: the kernel's skip flags, per frame
   // (the slot's next inter kernel is kSlots batches away and ordered behind this CDEF on the main stream, nothing else writes them)
@@ -902,7 +931,7 @@ static int deblock_cdef(av1mi_gop *g, Slot &s, const void *const src[3], const L
 // against the source): d_ref always receives the restored planes, the next batch's kernels choose between d_ref and d_cdef
 static int restore(av1mi_gop *g, Slot &s, const void *const src[3]) {
   const av1mi_gop_config &c = g->cfg;
-  const int w = c.width, h = c.height, S = c.segments, bd = c.bit_depth;
+  const int w = c.width, h = c.height, S = c.segments, bd = g->bd;
   const av1mi_frame_params &P = s.params;
   av1mi_lr_decide_job lj;
   memset(&lj, 0, sizeof(lj));
@@ -965,7 +994,7 @@ static int loop_filters(av1mi_gop *g, Slot &s, const void *const src[3]) {
 static int measure_quality(av1mi_gop *g, Slot &s, const void *const src[3]) {
   hipStream_t main = av1mi::ctx_stream(g->ctx);
   av1mi::QualityLaunch Q;
-  Q.bd = g->cfg.bit_depth; Q.w = g->vw; Q.h = g->vh; Q.frames = g->cfg.segments;
+  Q.bd = g->bd; Q.w = g->vw; Q.h = g->vh; Q.frames = g->cfg.segments;
   Q.src = src; Q.dec0 = g->d_ref; Q.dec1 = g->d_cdef; Q.sel = (const uint8_t *)s.d_lr_on;
   Q.scratch = g->d_quality_scratch; Q.out = (av1mi_quality *)s.h_quality;
   {
@@ -1047,7 +1076,7 @@ static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src
   // the batch's quantiser: fixed here, whatever av1mi_gop_set_base_q_idx is told while the batch is in flight
   s.q = g->next_q;
   if (s.q == g->cfg.base_q_idx) s.params = g->params[frame_type];
-  else frame_params(s.q, g->cfg.bit_depth, frame_type, &s.params);
+  else frame_params(s.q, g->bd, frame_type, &s.params);
   const void *src[3];
   G_TRY(feed_source(g, s, dev_src, src, store, index));
   if (s.ent_pending) G_HIP(hipStreamWaitEvent(av1mi::ctx_stream(g->ctx), s.ent_done, 0));      // the GPU coder of the slot's previous batch still reads its symbols
@@ -1193,6 +1222,7 @@ int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out) {
   if (g->cfg.quality_stats) { G_HIP(hipEventSynchronize(s.quality_done)); out->quality = (const av1mi_quality *)s.h_quality; }
   if (g->cfg.denoise && s.has_grain) { G_HIP(hipEventSynchronize(s.grain_done)); out->grain = (const av1mi_grain_record *)s.h_grain; out->grain_cov = (const av1mi_grain_cov_record *)s.h_grain_cov; }
   out->segments = g->cfg.segments;
+  out->bit_depth = g->bd;
   out->blocks_per_frame = g->nb / (size_t)g->cfg.segments;
   out->key_block_size = s.frame_type == 0 && g->key32 ? 32 : 8;
   out->key_modes_stride = g->key_modes_stride; out->key_modes_band = g->key_modes_band;

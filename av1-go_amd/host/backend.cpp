@@ -110,6 +110,16 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
     cfg.tone_map = 1;
     cfg.tone_map_peak = job.tonemap_peak ? job.tonemap_peak : job.hdr.have_mdcv ? (int)std::min<uint32_t>(std::max<uint32_t>(job.hdr.luminance_max >> 8, 100), 10000) : 0;
   }
+  // -av1mi_depth: the depth that is coded.  The session's bit_depth stays the depth its input stages work at
+  const int want = job.depth == -1 ? job.chain_depth : job.depth;      // 0 = the source's
+  plan->coded_bd = src.bd;
+  if (want == 10 && src.bd == 8)
+    return refuse(std::string(job.depth == -1 ? "-av1mi_depth chain: the chain's last format= names a 10-bit format" : "-av1mi_depth 10") + " and the source has 8 bits: 8 -> 10 bits is not built");
+  if (want == 8 && src.bd == 10) {
+    if (job.denoise) return refuse("a depth reduction together with -av1mi_denoise is not built: the grain records are measured in 10-bit codes and the grain would be synthesised into an 8-bit stream");
+    cfg.coded_bit_depth = 8; cfg.depth_dither = job.dither != 0;      // (ordered unless -av1mi_dither round)
+    plan->coded_bd = 8; plan->reduced_from = src.src_bd;
+  }
   plan->grainy = job.denoise > 0 && job.film_grain != 0;
   plan->analysed = job.scenecut > 0;
   plan->stored = plan->analysed || dei != 0 || job.denoise > 0;
@@ -126,6 +136,7 @@ std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, c
   int k = snprintf(line, sizeof(line), "n:%ld type:%c bytes:%zu", n, key ? 'K' : 'P', f.unit.size());
   k += av1mi::quality::format_figures(av1mi::quality::frame_figures(f.q, bit_depth), line + k, sizeof(line) - (size_t)k);
   if (tags.win.w && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " crop:%dx%d+%d+%d", tags.win.w, tags.win.h, tags.win.x, tags.win.y);
+  if (tags.depth_from && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " depth:%d>%d", tags.depth_from, tags.depth_to);
   if (tags.colour && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " colour:%d/%d/%d/%d", tags.colour->primaries, tags.colour->transfer, tags.colour->matrix, tags.colour->full_range);
   if (tags.q) k += snprintf(line + k, sizeof(line) - (size_t)k, " q:%d", f.base_q_idx);
   if (tags.grain) k += snprintf(line + k, sizeof(line) - (size_t)k, " grain:%d", f.grain);
@@ -233,7 +244,7 @@ struct Run {
   // the session, the sink (display size, side tracks) and the rate controller
   int open_session() {
     if (av1mi_gop_open(ctx, &plan.cfg, &gop) != AV1MI_OK) return lib_error("av1mi_gop_open");
-    sp.width = plan.tw; sp.height = plan.th; sp.bit_depth = y.bd; sp.film_grain = plan.grainy; sp.colour = plan.colour;
+    sp.width = plan.tw; sp.height = plan.th; sp.bit_depth = plan.coded_bd; sp.film_grain = plan.grainy; sp.colour = plan.colour;
     // pixels that stay non-square: the track at least says at which shape to show them
     if (!plan.square) sink.set_display_size((int)((long)plan.tw * y.sar_n / y.sar_d), plan.th);
     for (const std::string &side : job.tracks)
@@ -247,7 +258,7 @@ struct Run {
       else { rp.target_num = job.target_bpp_u * plan.tw * plan.th; rp.target_den = 8000000; }
       if (job.qmin) rp.qmin = job.qmin;
       if (job.qmax) rp.qmax = job.qmax;
-      rp.gop_length = G; rp.bit_depth = y.bd;
+      rp.gop_length = G; rp.bit_depth = plan.coded_bd;
       rp.start_q = std::min(std::max(plan.cfg.base_q_idx, rp.qmin), rp.qmax);
       if (const char *why = RateControl::ParamError(rp)) return fail(1, std::string("Invalid argument: rate control: ") + why);
       rc.reset(new RateControl(rp));
@@ -349,7 +360,7 @@ struct Run {
         } else FilmGrainFromRecords(oldest.grain + (size_t)s * 3, y.bd, index, &fg);
         f.grain = FilmGrainMidGrey(fg);
       }
-      if (!SessionTemporalUnit(oldest, s, plan.cfg.width, plan.cfg.height, y.bd, plan.cfg.visible_width, plan.cfg.visible_height, t == 0, threads, &f.unit, err, plan.grainy,
+      if (!SessionTemporalUnit(oldest, s, plan.cfg.width, plan.cfg.height, plan.coded_bd, plan.cfg.visible_width, plan.cfg.visible_height, t == 0, threads, &f.unit, err, plan.grainy,
                                plan.grainy ? &fg : nullptr, sp.has_colour() ? &plan.colour : nullptr)) return 2;
       batch_bytes += (long long)f.unit.size();
       f.base_q_idx = oldest.params.base_q_idx;
@@ -409,14 +420,15 @@ struct Run {
   // the group's frames in presentation order: each unit to the sink, its line to the stats
   int write_group(const Group &group, const GroupOut &out) {
     StatsTags tags;
+    tags.depth_from = plan.reduced_from; tags.depth_to = plan.coded_bd;
     tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0; tags.ar = job.grain_lag > 0; tags.lr = job.lr_search != 0; tags.cdef = job.cdef_search != 0; tags.lf = job.lf_search != 0;
     for (int s = 0; s < S; s++)
       for (size_t t = 0; t < out[(size_t)s].size(); t++) {
         const FrameOut &f = out[(size_t)s][t];
         if (!sink.write(f.unit, t == 0, err)) return 1;
         if (!plan.measure) continue;
-        stats += StatsFrameLine(summary.frames, t == 0, f, y.bd, tags, plan.analysed && group.cut[(size_t)group.index(s, (int)t)]) + '\n';
-        summary.add(f.q, y.bd);
+        stats += StatsFrameLine(summary.frames, t == 0, f, plan.coded_bd, tags, plan.analysed && group.cut[(size_t)group.index(s, (int)t)]) + '\n';
+        summary.add(f.q, plan.coded_bd);
         total_bytes += (long long)f.unit.size();
       }
     return 0;
@@ -460,12 +472,12 @@ struct Run {
     }
     if (!plan.measure) return 0;
     if (!job.stats_path.empty()) {
-      stats += StatsSummaryLine(summary, total_bytes, y.bd) + '\n';
+      stats += StatsSummaryLine(summary, total_bytes, plan.coded_bd) + '\n';
       FILE *sf = fopen(job.stats_path.c_str(), "wb");
       const bool ok = sf && fwrite(stats.data(), 1, stats.size(), sf) == stats.size();
       if ((sf && fclose(sf)) || !ok) { remove(job.output.c_str()); return fail(1, job.stats_path + ": could not write the stats file"); }
     }
-    const av1mi::quality::Figures f = summary.figures(y.bd);
+    const av1mi::quality::Figures f = summary.figures(plan.coded_bd);
     if (job.min_psnr > 0 && f.psnr[0] < job.min_psnr) {      // the quality gate: the file is not good enough to stand in for its source
       char why[160];
       snprintf(why, sizeof(why), "quality gate: psnr_y %.6f dB below the bound %.6f dB", f.psnr[0], job.min_psnr);

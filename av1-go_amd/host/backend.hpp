@@ -25,6 +25,8 @@ struct SessionPlan {
   // packed: the frames cross PCIe at 10 bits per sample; stored: the job runs through the frame store; analysed: its groups are laid out
   // on scene cuts; grainy: film grain parameters in every frame header; measure: the session returns quality records
   bool packed, stored, analysed, grainy, measure;
+  int coded_bd;                 // the depth of the stream (-av1mi_depth): what the sequence header, the sink, the rate controller and the figures take
+  int reduced_from;             // the source's depth where the job reduces it (10 or 12), else 0
 };
 // -av1mi_crop W:H:X:Y against a w x h picture: 0 and *win, or 1 and the text
 int ExplicitWindow(const BackendJob &job, int w, int h, CropRect *win, std::string *err);
@@ -46,8 +48,8 @@ struct Group {
   std::vector<int32_t> slots(int t) const { std::vector<int32_t> v(len.size()); for (size_t s = 0; s < v.size(); s++) v[s] = index((int)s, t); return v; }      // batch t: per segment
 };
 // The stats file: the line of frame n in presentation order, and the summary line.  tags: what a line says beyond the
-// figures — the window and the colour record (frame 0 only; w == 0 / null = none), q: (a job with a target), grain: (a job that denoises)
-struct StatsTags { CropRect win; const av1mi_colour *colour = nullptr; bool q = false, grain = false, ar = false, lr = false, cdef = false, lf = false; };
+// figures — the window, the colour record and the depth reduction " depth:10>8" (frame 0 only; w == 0 / null / depth_from 0 = none), q: (a job with a target), grain: (a job that denoises)
+struct StatsTags { CropRect win; const av1mi_colour *colour = nullptr; int depth_from = 0, depth_to = 0; bool q = false, grain = false, ar = false, lr = false, cdef = false, lf = false; };
 std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, const StatsTags &tags, bool cut);
 std::string StatsSummaryLine(const av1mi::quality::Summary &sum, long long bytes, int bit_depth);
 

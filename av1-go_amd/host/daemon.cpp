@@ -116,6 +116,8 @@ void AppendConfigArgs(const TranscodeConfig &cfg, std::vector<std::string> *a) {
   if (cfg.Device) { const std::string out = args.back(); args.back() = "-av1mi_device"; args.push_back(std::to_string(cfg.Device)); args.push_back(out); }
   if (cfg.MeRange) { const std::string out = args.back(); args.back() = "-av1mi_me_range"; args.push_back(std::to_string(cfg.MeRange)); args.push_back(out); }
   if (cfg.Format420) { const std::string out = args.back(); args.back() = "-av1mi_format"; args.push_back("420"); args.push_back(out); }
+  if (!cfg.Depth.empty()) { const std::string out = args.back(); args.back() = "-av1mi_depth"; args.push_back(cfg.Depth); args.push_back(out); }
+  if (!cfg.Dither.empty()) { const std::string out = args.back(); args.back() = "-av1mi_dither"; args.push_back(cfg.Dither); args.push_back(out); }
   if (cfg.MinPSNR > 0) {
     char bound[32];
     snprintf(bound, sizeof(bound), "%.6f", cfg.MinPSNR);

@@ -47,6 +47,9 @@ struct TranscodeConfig {           // daemon.go:185-188; Device is this backend'
   // -av1mi_format 420 on every job (BackendJob::to_420).  The reference's chain, which ProcessJob always passes, already says so with
   // its format=nv12; the option states it for callers that build their own argv without a chain.
   bool Format420 = false;
+  // -av1mi_depth / -av1mi_dither on every job (BackendJob::depth, ::dither), carried as their values: "" = not given.  "chain" makes the
+  // reference's format=nv12 mean what it says: 10-bit sources are coded at 8 bits.
+  std::string Depth, Dither;
   // A target size instead of the fixed quantiser: bits per pixel per frame (-av1mi_target_bpp; 0 = off, the default: the argv is then the
   // reference's, and -global_quality maps 1:1 to the quantiser).  The reference's own estimate expects 0.15 / 0.12 / 0.10 at quality
   // 23 / 24 / 25 (cmd/av1d/main.go:413-427): a caller that wants the size gate to pass asks for that here.

@@ -41,6 +41,8 @@ int main(int argc, char **argv) {
       else if (!strcmp(argv[i], "--min-psnr")) cfg.MinPSNR = atof(argv[i + 1]);
       else if (!strcmp(argv[i], "--me-range")) cfg.MeRange = atoi(argv[i + 1]);
       else if (!strcmp(argv[i], "--format")) cfg.Format420 = !strcmp(argv[i + 1], "420");
+      else if (!strcmp(argv[i], "--depth")) cfg.Depth = argv[i + 1];
+      else if (!strcmp(argv[i], "--dither")) cfg.Dither = argv[i + 1];
       else if (!strcmp(argv[i], "--target-bpp")) cfg.TargetBitsPerPixel = atof(argv[i + 1]);
     }
     struct stat st;
@@ -62,6 +64,8 @@ int main(int argc, char **argv) {
       else if (!strcmp(argv[i], "--min-psnr") && i + 1 < argc) cfg.MinPSNR = atof(argv[++i]);
       else if (!strcmp(argv[i], "--me-range") && i + 1 < argc) cfg.MeRange = atoi(argv[++i]);
       else if (!strcmp(argv[i], "--format") && i + 1 < argc) cfg.Format420 = !strcmp(argv[++i], "420");
+      else if (!strcmp(argv[i], "--depth") && i + 1 < argc) cfg.Depth = argv[++i];
+      else if (!strcmp(argv[i], "--dither") && i + 1 < argc) cfg.Dither = argv[++i];
       else if (!strcmp(argv[i], "--target-bpp") && i + 1 < argc) cfg.TargetBitsPerPixel = atof(argv[++i]);
       else {
         Job j; j.ID = "job" + std::to_string(jobs.size()); j.SourcePath = argv[i];

@@ -147,7 +147,7 @@ bool ChainTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain,
       if (name != "nv12" && name != "p010" && name != "p010le" && name != "yuv420p" && name != "yuv420p10le") { if (err) *err = "Invalid argument: unsupported filter " + f; return false; }
       if (to_420) *to_420 = true;
     } else if (f == "tonemap_vaapi" || f.compare(0, 14, "tonemap_vaapi=") == 0) {
-      // BT.2390 to BT.709 is what is built (include/av1mi.h "tone mapping"); the output stays 10-bit whatever format= names
+      // BT.2390 to BT.709 is what is built (include/av1mi.h "tone mapping"); the output's depth is -av1mi_depth's business, not this filter's format=
       std::string rest = f.size() > 14 ? f.substr(14) : "";
       while (!rest.empty()) {
         const size_t c = rest.find(':');
@@ -268,7 +268,7 @@ av1mi_colour JobColour(const BackendJob &job, int y4m_range) {
 bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std::string *err) {
   if (args.size() < 3) { if (err) *err = "Invalid argument: too few arguments"; return false; }
   job->output = args.back();
-  bool have_in = false, deint_given = false, grain_lag_given = false;
+  bool have_in = false, deint_given = false, grain_lag_given = false, depth_given = false;
   std::string colour_err;
   for (size_t i = 0; i + 1 < args.size(); i++) {
     if (args[i] == "-i") { job->input = args[i + 1]; have_in = true; }
@@ -374,6 +374,16 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
       if (args[i + 1] == "off") job->tonemap = 0; else if (args[i + 1] == "bt2390") job->tonemap = 1;
       else { if (err) *err = "Invalid argument: -av1mi_tonemap takes off or bt2390, not " + args[i + 1]; return false; }
     }
+    else if (args[i] == "-av1mi_depth") {
+      const std::string &v = args[i + 1];
+      if (v == "8") job->depth = 8; else if (v == "10") job->depth = 10; else if (v == "source") job->depth = 0; else if (v == "chain") job->depth = -1;
+      else { if (err) *err = "Invalid argument: -av1mi_depth takes 8, 10, source or chain, not " + v; return false; }
+      depth_given = true;
+    }
+    else if (args[i] == "-av1mi_dither") {
+      if (args[i + 1] == "ordered") job->dither = 1; else if (args[i + 1] == "round") job->dither = 0;
+      else { if (err) *err = "Invalid argument: -av1mi_dither takes ordered or round, not " + args[i + 1]; return false; }
+    }
     else if (args[i] == "-av1mi_tonemap_peak") {
       if (!plain_int(args[i + 1], &job->tonemap_peak) || job->tonemap_peak < 100 || job->tonemap_peak > 10000) { if (err) *err = "Invalid argument: -av1mi_tonemap_peak takes cd/m2, 100 .. 10000, not " + args[i + 1]; return false; }
     }
@@ -401,7 +411,18 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
     }
     if (to_420) job->to_420 = true;
     if (deint && !deint_given) job->deinterlace = 1;      // a deinterlacer in the chain means auto; an explicit option keeps its say
+    // what the chain's LAST format= names (ChainTarget has refused every name but these five): -av1mi_depth chain reads it
+    std::string part;
+    bool quoted = false;
+    for (size_t k = 0; k <= job->vf.size(); k++) {
+      const char c = k < job->vf.size() ? job->vf[k] : ',';
+      if (c == '\'') quoted = !quoted;
+      if (c != ',' || quoted) { part.push_back(c); continue; }
+      if (part.compare(0, 7, "format=") == 0) job->chain_depth = part == "format=nv12" || part == "format=yuv420p" ? 8 : 10;
+      part.clear();
+    }
   }
+  if (job->dither >= 0 && !depth_given) { if (err) *err = "Invalid argument: -av1mi_dither needs -av1mi_depth: it is the rounding of the depth reduction"; return false; }
   if (job->tonemap_peak && !job->tonemap) { if (err) *err = "Invalid argument: -av1mi_tonemap_peak needs -av1mi_tonemap bt2390 (or tonemap_vaapi in the chain)"; return false; }
   if (job->tonemap) {
     if (job->denoise) { if (err) *err = "Invalid argument: tone mapping together with -av1mi_denoise is not built: the grain would be measured in the source's light"; return false; }

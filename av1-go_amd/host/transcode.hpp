@@ -81,7 +81,7 @@ struct BackendJob {
   bool to_420 = false;     // the job converts its source to 4:2:0: the chain has a format= filter naming a 4:2:0 format (nv12, p010, p010le, yuv420p,
                            // yuv420p10le — the reference's chain always does, transcode.go:99-110), or -av1mi_format 420 was given.  The source may then be
                            // 4:2:2, 4:4:4 or grey, at 8, 10 or 12 bits (Y4mSource::open's any_layout); it is converted on the GPU (av1mi.h "chroma formats").
-                           // The coded depth follows the SOURCE (8 -> 8, 10 -> 10, 12 -> 10), not the format's name.  Without it such a source is refused
+                           // The coded depth follows the SOURCE (8 -> 8, 10 -> 10, 12 -> 10) unless -av1mi_depth says otherwise.  Without it such a source is refused
   int scenecut = 0;        // -av1mi_scenecut N: 0 (default) = off; 1 .. 99 = the sensitivity of the scene-cut rule (include/av1mi.h "scene analysis";
                            // host/sceneplan.hpp AV1MI_SCENECUT_DEFAULT is the measured middle).  Every group of segments x gop frames is put into the
                            // session's frame store in file order, analysed on the GPU, and its GOP boundaries are moved onto the cuts found
@@ -121,6 +121,13 @@ struct BackendJob {
   // (av1mi_gop_config.tone_map); -av1mi_tonemap_peak N: the source's peak in cd/m2 (else the mastering display's maximum, else 1000).  The
   // output is then described as 1 / 1 / 1 limited without metadata, and -color_* describe the SOURCE (bt2020 / smpte2084 / bt2020nc / tv or nothing)
   int tonemap = 0, tonemap_peak = 0;
+  // -av1mi_depth 8 | 10 | source | chain: the depth that is CODED (av1mi_gop_config.coded_bit_depth).  source (0, the default): the source's, as
+  // ever (8 -> 8, 10 -> 10, 12 -> 10).  8: a 10- or 12-bit source is reduced to 8 bits on the GPU at the end of the input chain, behind the
+  // scaler and the tone map; nothing happens to an 8-bit source.  chain (-1): the LAST format= of the chain decides (chain_depth: nv12, yuv420p = 8;
+  // p010, p010le, yuv420p10le = 10; none = source): what the reference's argv means by format=nv12.  10, or a chain asking for 10, with an 8-bit
+  // source is refused when the source is known: 8 -> 10 bits is not built.  -av1mi_dither ordered | round (1, 0; -1 = not given: ordered): the
+  // reduction's rounding (include/av1mi.h "depth reduction"); an error without -av1mi_depth.  Not together with -av1mi_denoise
+  int depth = 0, dither = -1, chain_depth = 0;
   std::vector<std::string> tracks;   // -av1mi_tracks <file.mka> (repeatable): Matroska side files whose audio / subtitle tracks are copied
                                      // next to the video (the reference's `-c:a copy -c:s copy`, transcode.go:134-137, after an external demux)
 };

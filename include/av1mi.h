@@ -900,6 +900,26 @@ int av1mi_tone_map_tables(int peak, av1mi_tone_tables *out);
  * context's stream.  Counted under AV1MI_K_INPUT in the profile. */
 int av1mi_tone_map(av1mi_ctx *ctx, int width, int height, int frames, void *d_y, void *d_u, void *d_v, const av1mi_tone_tables *d_tables);
 
+/* ---- depth reduction: 10-bit planar 4:2:0 planes become the 8-bit planes that are coded (av1-go_amd/csrc/depth_kernels.hip, k_depth_reduce;
+ * numpy twin: tests/depth_ref.py).  Pointwise, out of place, integer arithmetic, bit exact by definition.  Input: the three planes of `frames`
+ * stacked frames, uint16 samples v (0 .. 1023 is what a 10-bit picture holds; the arithmetic below is defined, and computed exactly, for every
+ * uint16), at their BUFFER size: W8 x H8 luma, W8 / 2 x H8 / 2 chroma, both multiples of 8.  Output: uint8 planes of the same sizes.  Every
+ * sample of the buffers is processed, padding included.  With (x, y) the sample's position in its own plane and p = 0, 1, 2 for Y, U, V:
+ *   mode 0 (round)     out = min((v + 2) >> 2, 255)
+ *   mode 1 (ordered)   out = min((v + t_p(x, y)) >> 2, 255),  t_p(x, y) = T[y & 1][(x + p) & 1],  T = { { 0, 2 }, { 3, 1 } }
+ * The pattern depends on the position only, never on the frame: a still picture stays still, and a P frame does not code the dither again.
+ * Over any aligned 2x2 cell of constant v the thresholds are 0, 1, 2, 3 once each, so the four outputs sum to exactly v (where no clamp is
+ * hit: v <= 1020): the dither preserves the mean, and a larger (Bayer 8x8) matrix could add nothing to a reduction by two bits.  Plane p's
+ * pattern is plane 0's shifted by p columns, so U and V do not dither in step.  Limited range maps onto limited range in both modes: 64 -> 16,
+ * 940 -> 235 (multiples of 4 pass every threshold unchanged).  H8 and H8 / 2 are even, so a row's parity inside a batch plane of frames x
+ * height rows is its parity inside its frame: the kernel treats the batch as one plane. */
+enum av1mi_depth_mode { AV1MI_DEPTH_ROUND = 0, AV1MI_DEPTH_ORDERED = 1 };
+/* d_in[p] -> d_out[p], p = Y, U, V: `frames` stacked frames of width x height luma samples (multiples of 8, 8 .. 16384: the buffers' size) and
+ * the half-size chroma planes; uint16 in, uint8 out, all six 4-byte aligned, no output overlapping an input.  One launch, asynchronous on the
+ * context's stream; counted under AV1MI_K_INPUT in the profile.  AV1MI_E_INVAL for an unknown mode, a size that is not a multiple of 8 or
+ * outside 8 .. 16384, frames < 1 (or frames x height beyond 65535 x 32 rows), a null or misaligned plane. */
+int av1mi_depth_reduce(av1mi_ctx *ctx, int mode, int width, int height, int frames, const void *const d_in[3], void *const d_out[3]);
+
 /* ---- GOP session: the encoder object a cgo replacement of RunTranscode drives (reference call site
  * internal/daemon/daemon.go:101 -> internal/ffmpeg/transcode.go:194; SURVEY.md §8b "av1mi_open(config) / av1mi_encode /
  * av1mi_flush").  It owns the closed-GOP orchestration and the encoder's filter-parameter POLICY, so that no caller
@@ -1067,6 +1087,20 @@ typedef struct av1mi_gop_config {
    * session: the per-frame maps (the batches are serial on the main stream), the scratch table and the sums; per slot: the level and
    * choice bytes with pinned mirrors, an event.  Anything outside 0 / 1 is refused.  With 0 nothing of this is allocated or launched. */
   int lf_search;
+  /* Depth reduction ("depth reduction"; 0, 0 = none: the session codes at bit_depth as it always has — same allocations, same launches, same
+   * bytes).  coded_bit_depth: 0 = bit_depth; 8 is valid with bit_depth 10 only (with bit_depth 8 there is nothing to do, and it is refused; 10 with bit_depth 10 means 0).  bit_depth KEEPS
+   * its meaning for everything in front of the stage — wire formats, source_bit_depth, chroma conversion, crop, scaler, tone map, frame store,
+   * scene analysis, deinterlacing: the depth the input stages work at — and the stage runs at the end of the input chain, BEHIND the tone
+   * map: one launch per batch (k_depth_reduce, under AV1MI_K_INPUT) reads the planar planes at the coded size where the chain left them and
+   * writes the slot's own uint8 planes.  Per slot: those 10-bit planes (in a session without input stages they are the fed buffers).  In a
+   * batch of av1mi_gop_submit_device the stage may read the caller's planes and never writes them (a tone_map session still refuses device
+   * batches: the MAP runs in place on the planes it is given).  Everything from the block pipeline on
+   * is an 8-bit session: planes and strides, av1mi_policy_frame_params, both intra pipelines and the inter pipeline, motion search, the loop
+   * filters and their three searches (against the 8-bit source), tokenizers and coder, the quantiser tables, av1mi_gop_frame.bit_depth, and
+   * the quality records (against the source AS CODED, the 8-bit planes: L = 255).  It yields, byte for byte, what a bit_depth 8 session
+   * fed the reduced planes yields.  depth_dither: 0 = round, 1 = ordered (enum av1mi_depth_mode); needs coded_bit_depth 8.  Refused with
+   * denoise: the grain records are measured in 10-bit codes and the grain would be synthesised into an 8-bit stream. */
+  int coded_bit_depth, depth_dither;
 } av1mi_gop_config;
 
 /* The source layout: what a session opened with a config is FED, as one description.  Everything a caller sizes or strides by — the
@@ -1155,6 +1189,8 @@ typedef struct av1mi_gop_frame {    /* one collected frame batch; host pointers 
    * in pinned memory.  NULL when the option is off */
   const uint8_t *lf_levels;
   const uint8_t *lf_choice;
+  int bit_depth;                    /* of what was coded: av1mi_gop_config.coded_bit_depth, or bit_depth.  What the sequence header and every
+                                       writer of this batch's frames take */
 } av1mi_gop_frame;
 
 typedef struct av1mi_gop av1mi_gop;
