@@ -144,7 +144,8 @@ class GopConfig(C.Structure):
                 ("source_bit_depth", C.c_int), ("store_frames", C.c_int), ("deinterlace", C.c_int), ("denoise", C.c_int),
                 ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int), ("crop_height", C.c_int), ("denoise_range", C.c_int),
                 ("tone_map", C.c_int), ("tone_map_peak", C.c_int), ("grain_cov", C.c_int), ("lr_search", C.c_int),
-                ("cdef_search", C.c_int), ("lf_search", C.c_int), ("coded_bit_depth", C.c_int), ("depth_dither", C.c_int)]
+                ("cdef_search", C.c_int), ("lf_search", C.c_int), ("coded_bit_depth", C.c_int), ("depth_dither", C.c_int),
+                ("deinterlace_fields", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -290,7 +291,7 @@ class GopSession:
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
                  key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None, tone_map=0, tone_map_peak=0, grain_cov=None, lr_search=None, cdef_search=None, lf_search=None, coded_bit_depth=None,
-                 depth_dither=None):
+                 depth_dither=None, deinterlace_fields=None):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
@@ -312,7 +313,9 @@ class GopSession:
         grain_cov: 1 = the covariance of what the denoiser removed is measured behind the gather (av1mi_gop_config.grain_cov; needs
         denoise): collect()["grain_cov"] holds the records.  None leaves the field unset (0 = none);
         coded_bit_depth: 8 in a bit_depth 10 session = the depth reduction at the end of the input chain: everything behind it is an 8-bit
-        session (av1mi_gop_config.coded_bit_depth); depth_dither: DEPTH_ROUND or DEPTH_ORDERED.  None leaves a field unset (0)"""
+        session (av1mi_gop_config.coded_bit_depth); depth_dither: DEPTH_ROUND or DEPTH_ORDERED.  None leaves a field unset (0);
+        deinterlace_fields: 1 = one output frame per field (av1mi_gop_config.deinterlace_fields; needs deinterlace): submit_stored() then
+        takes OUTPUT positions, source position * 2 + phase.  None leaves the field unset (0)"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
         sw, sh = source if source is not None else (0, 0)
@@ -336,6 +339,8 @@ class GopSession:
             self.cfg.coded_bit_depth = int(coded_bit_depth)
         if depth_dither is not None:
             self.cfg.depth_dither = int(depth_dither)
+        if deinterlace_fields is not None:
+            self.cfg.deinterlace_fields = int(deinterlace_fields)
         if crop is not None:
             self.cfg.crop_x, self.cfg.crop_y, self.cfg.crop_width, self.cfg.crop_height = (int(v) for v in crop)
         self.g = C.c_void_p()
@@ -813,6 +818,13 @@ class Context:
         self.lib.av1mi_deinterlace_gather.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         sizes, dst = self._gather_planes(plane_sizes, true_sizes, d_dst)
         self._chk(self.lib.av1mi_deinterlace_gather(self.h, int(bit_depth), *sizes, int(parity), int(segments), d_table.ptr, dst))
+
+    def deinterlace_gather_fields(self, bit_depth, plane_sizes, true_sizes, parity, segments, d_table, d_phase, d_dst):
+        """the same at field rate (av1mi_deinterlace_gather_fields): d_phase: DevBuf of `segments` bytes, 0 = the first field of the
+        segment's frame, 1 = its second (only the low bit is read); the table holds P, C, N of the SOURCE frame"""
+        self.lib.av1mi_deinterlace_gather_fields.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        sizes, dst = self._gather_planes(plane_sizes, true_sizes, d_dst)
+        self._chk(self.lib.av1mi_deinterlace_gather_fields(self.h, int(bit_depth), *sizes, int(parity), int(segments), d_table.ptr, d_phase.ptr if d_phase is not None else None, dst))
 
     def crop_analyse(self, Y, bit_depth, true_size, limit=24):
         """the margins (CROP_DTYPE [frames]) of luma planes Y [frames, H8, W8], H8 and W8 multiples of 8, whose picture is true_size =

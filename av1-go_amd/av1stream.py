@@ -380,6 +380,43 @@ def parse_deinterlace_option(argv):
     return DEINTERLACE_MODES[k]
 
 
+DEINTERLACE_RATES = ("frame", "field")      # BackendJob::deint_rate, -av1mi_deinterlace_rate
+
+
+def parse_deinterlace_rate(argv):
+    """what an argument vector asks of -av1mi_deinterlace_rate: one of DEINTERLACE_RATES; ValueError with the host's text where the vector
+    is refused"""
+    h = lib()
+    h.av1mi_host_parse_deinterlace_rate.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
+    err = C.create_string_buffer(1024)
+    k = h.av1mi_host_parse_deinterlace_rate("\n".join(str(x) for x in argv).encode(), err, 1024)
+    if k < 0:
+        raise ValueError(err.value.decode())
+    return DEINTERLACE_RATES[k]
+
+
+def job_output(argv, interlace, fps, frames):
+    """the output of the job of an argument vector (host/fieldrate.hpp JobOutputOf) on a source with the Y4M I parameter `interlace` ("p",
+    "t", "b", "m"), the rate fps = (n, d) and `frames` frames (-1 = a stream): (output frames per source frame, (fps_n, fps_d), frames)"""
+    h = lib()
+    h.av1mi_host_job_output.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_longlong), C.c_char_p, C.c_int]
+    err, out = C.create_string_buffer(1024), (C.c_longlong * 4)()
+    if h.av1mi_host_job_output("\n".join(str(x) for x in argv).encode(), "ptbm".index(interlace), int(fps[0]), int(fps[1]), int(frames), out, err, 1024) < 0:
+        raise ValueError(err.value.decode())
+    return int(out[0]), (int(out[1]), int(out[2])), int(out[3])
+
+
+def field_rate_cuts(cut):
+    """the cut flags of n source frames as the 2 n output frames of a field-rate job carry them (host/fieldrate.hpp FieldRateCuts)"""
+    h = lib()
+    h.av1mi_host_field_rate_cuts.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    h.av1mi_host_field_rate_cuts.restype = None
+    c = np.ascontiguousarray(cut, np.uint8)
+    out = np.full(2 * c.size, 7, np.uint8)
+    h.av1mi_host_field_rate_cuts(c.ctypes.data, int(c.size), out.ctypes.data)
+    return out
+
+
 def run_transcode(argv):
     """av1mi_run_transcode (include/av1mi_host.h) on an argument vector: (exit code, error text)"""
     h = lib()

@@ -312,6 +312,12 @@ struct DeintLaunch : GatherPlanes {
   int parity;
 };
 hipError_t launch_deint_gather(const DeintLaunch &L, hipStream_t s);
+// the same at field rate (include/av1mi.h "field-rate output"): phase[segment] in device memory, low bit 0 = the frame's first field
+// (the launch above, exactly), 1 = its second: the opposite parity is kept and the temporal pair is (C, N).  ONE launch.
+struct DeintFieldsLaunch : DeintLaunch {
+  const uint8_t *phase;
+};
+hipError_t launch_deint_gather_fields(const DeintFieldsLaunch &L, hipStream_t s);
 
 // the denoising gather (grain_kernels.hip, include/av1mi.h "denoising" / "grain records"): a strength (1 .. 16) in place of the parity; bd
 // 8 or 10.  records: segments * 3 records (device or pinned host memory), or null = nothing is measured, ONE launch; else two, and

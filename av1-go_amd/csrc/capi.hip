@@ -941,6 +941,20 @@ int av1mi_deinterlace_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3]
   return AV1MI_OK;
 }
 
+int av1mi_deinterlace_gather_fields(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int parity,
+                                    int segments, const void *const *d_table, const uint8_t *d_phase, void *const d_dst[3]) {
+  BIND(ctx);
+  if (!plane_w || !plane_h || !true_w || !true_h || !d_table || !d_phase || !d_dst || ((uintptr_t)d_table & 7))
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather_fields: null pointer or misaligned table");
+  if (parity != 0 && parity != 1) return fail(ctx, AV1MI_E_INVAL, "av1mi_deinterlace_gather_fields: parity %d (0 = top field first, 1 = bottom field first)", parity);
+  av1mi::DeintFieldsLaunch L;
+  L.parity = parity; L.phase = d_phase;
+  if (int rc = check_gather_planes(ctx, "av1mi_deinterlace_gather_fields", 12, false, bit_depth, plane_w, plane_h, true_w, true_h, segments, d_table, d_dst, L)) return rc;
+  ProfScope ps(ctx, AV1MI_K_SCENE);
+  HIP_TRY(ctx, av1mi::launch_deint_gather_fields(L, ctx->stream));
+  return AV1MI_OK;
+}
+
 int av1mi_denoise_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int strength,
                          int segments, const void *const *d_table, void *const d_dst[3], av1mi_grain_record *d_records) {
   BIND(ctx);

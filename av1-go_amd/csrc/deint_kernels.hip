@@ -15,9 +15,13 @@
 //             the last cell of a row partly.
 //   padding   output columns beyond the true width repeat the last true column's OUTPUT, output rows beyond the true height the last
 //             true row's: both by construction (a row y >= h is computed as row h - 1).  The input's padding is never used.
+//   fields    k_deint_gather<Pix, true> is the field-rate launch (av1mi_gop_config.deinterlace_fields): a phase per segment, 0 = the frame's
+//             first field (the same-rate filter), 1 = its second (the opposite parity kept, t0 / t1 from C / N).  The phase is read once
+//             per workgroup and only picks a parity and two row pointers: the row loop, its loads and its arithmetic are shared.
 // The launch geometry, the decode of blockIdx.x and of an item, the cells and the padding rule are gather_cells.hpp's, shared with the
 // denoising gathers (grain_kernels.hip); here: the sets, the window and the filter.
 // Arithmetic: include/av1mi.h; restated in numpy by tests/deinterlace_ref.py.  Reference tree: nothing (transcode.go:120).
+#include <type_traits>
 #include "av1mi_internal.hpp"
 #include "gather_cells.hpp"
 
@@ -25,6 +29,8 @@ namespace av1mi {
 
 namespace {
 struct DeintGeom : BandGeom { int parity; };
+// the field-rate launch (include/av1mi.h "field-rate output"): a phase per segment beside the session's parity; only its low bit is read
+struct DeintFieldsGeom : DeintGeom { const uint8_t *phase; };
 
 // one kept row as the filter needs it: the C row's cell with HD dwords on either side (c[HD .. HD + 3] is the cell), and the cells of the
 // same row of P and N
@@ -35,9 +41,10 @@ __device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
 
 }  // namespace
 
-// grid: per_seg x segments; 4 waves = 4 consecutive items of one (segment, plane)
-template <typename Pix>
-__global__ __launch_bounds__(256) void k_deint_gather(DeintGeom G, const void *const *table) {
+// grid: per_seg x segments; 4 waves = 4 consecutive items of one (segment, plane).  FIELDS: the segment's phase (uniform in the workgroup)
+// picks the kept parity and the temporal pair (P, C) or (C, N) once, in front of the row loop; the loop itself is the same-rate one
+template <typename Pix, bool FIELDS>
+__global__ __launch_bounds__(256) void k_deint_gather(typename std::conditional<FIELDS, DeintFieldsGeom, DeintGeom>::type G, const void *const *table) {
   constexpr int NS = 16 / (int)sizeof(Pix);      // samples per cell
   constexpr int HD = (int)sizeof(Pix);           // dwords that hold 3 samples beside a cell (they hold 4)
   constexpr int ND = 4 + 2 * HD;
@@ -50,8 +57,15 @@ __global__ __launch_bounds__(256) void k_deint_gather(DeintGeom G, const void *c
   if (!W.C) { zero_band(W, B); return; }
   const uint32_t rb = W.rb, cells = W.cells, cx = B.cx, off = B.off;
   const bool active = B.active, whole = B.whole;
-  const int h = W.h, k = G.parity, lastj = B.lastj;
   const char *P = W.P, *C = W.C, *N = W.N;
+  int k = G.parity;
+  const char *T0 = P, *T1 = C;                   // the rows of t0 and t1: one field before and one field after the missing one
+  if constexpr (FIELDS) {
+    const int phi = __builtin_amdgcn_readfirstlane(G.phase[W.seg] & 1);
+    k ^= phi;
+    T0 = phi ? C : P; T1 = phi ? N : C;
+  }
+  const int h = W.h, lastj = B.lastj;
   const bool first_cell = cx == 0, edge = first_cell || lastj < NS + 2;
 
   // the set of kept row r
@@ -109,8 +123,8 @@ __global__ __launch_bounds__(256) void k_deint_gather(DeintGeom G, const void *c
       held_dn = dr;
     }
     uint32_t py[4], cy[4];
-    load_cell(P + (size_t)ye * rb, off, rb, whole, active, py);
-    load_cell(C + (size_t)ye * rb, off, rb, whole, active, cy);
+    load_cell(T0 + (size_t)ye * rb, off, rb, whole, active, py);
+    load_cell(T1 + (size_t)ye * rb, off, rb, whole, active, cy);
     int A[NW], B[NW], o[NS];
     window(up, A);
     window(dn, B);
@@ -144,8 +158,19 @@ hipError_t launch_deint_gather(const DeintLaunch &L, hipStream_t s) {
   if (hipError_t e = band_geometry(L, false, G)) return e;
   if (L.segments <= 0 || !G.per_seg) return hipSuccess;
   const dim3 grid(G.per_seg * (unsigned)L.segments);
-  if (L.bd == 8) hipLaunchKernelGGL(k_deint_gather<uint8_t>, grid, dim3(256), 0, s, G, L.table);
-  else hipLaunchKernelGGL(k_deint_gather<uint16_t>, grid, dim3(256), 0, s, G, L.table);
+  if (L.bd == 8) hipLaunchKernelGGL((k_deint_gather<uint8_t, false>), grid, dim3(256), 0, s, G, L.table);
+  else hipLaunchKernelGGL((k_deint_gather<uint16_t, false>), grid, dim3(256), 0, s, G, L.table);
+  return hipGetLastError();
+}
+
+hipError_t launch_deint_gather_fields(const DeintFieldsLaunch &L, hipStream_t s) {
+  DeintFieldsGeom G;
+  G.parity = L.parity; G.phase = L.phase;
+  if (hipError_t e = band_geometry(L, false, G)) return e;
+  if (L.segments <= 0 || !G.per_seg) return hipSuccess;
+  const dim3 grid(G.per_seg * (unsigned)L.segments);
+  if (L.bd == 8) hipLaunchKernelGGL((k_deint_gather<uint8_t, true>), grid, dim3(256), 0, s, G, L.table);
+  else hipLaunchKernelGGL((k_deint_gather<uint16_t, true>), grid, dim3(256), 0, s, G, L.table);
   return hipGetLastError();
 }
 

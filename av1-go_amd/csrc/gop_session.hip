@@ -302,8 +302,10 @@ int slot_buffers(av1mi_gop *g, Slot &s) {
   if (c.store_frames) {
     // (a session that deinterlaces or denoises keeps three pointers per segment and plane: the frames before, at and after the position)
     const size_t entries = (size_t)S * 3 * (c.deinterlace || c.denoise ? 3 : 1);
-    G_TRY(host_alloc(g, &s.h_table, entries * sizeof(void *)));
-    G_TRY(dev_alloc(g, &s.d_table, entries * sizeof(void *)));
+    // (at field rate a phase byte per segment rides behind the pointers, in the same copy)
+    const size_t phases = c.deinterlace_fields ? (size_t)S : 0;
+    G_TRY(host_alloc(g, &s.h_table, entries * sizeof(void *) + phases));
+    G_TRY(dev_alloc(g, &s.d_table, entries * sizeof(void *) + phases));
   }
   if (c.denoise) {
     G_TRY(host_alloc(g, &s.h_grain, (size_t)S * 3 * sizeof(av1mi_grain_record)));
@@ -448,6 +450,8 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
   if (c->store_frames && c->input_format != AV1MI_INPUT_PLANAR) return WHY("a frame store (store_frames %d) needs input_format 0 (planar), not %d", c->store_frames, c->input_format);
   if (c->deinterlace < 0 || c->deinterlace > 2) return WHY("deinterlace %d unknown (0 none, 1 top field first, 2 bottom field first)", c->deinterlace);
   if (c->deinterlace && !c->store_frames) return WHY("deinterlace %d needs a frame store (store_frames > 0): the filter reads the frames before and after each frame", c->deinterlace);
+  if (c->deinterlace_fields != 0 && c->deinterlace_fields != 1) return WHY("deinterlace_fields %d unknown (0 one frame per frame, 1 one frame per field)", c->deinterlace_fields);
+  if (c->deinterlace_fields && !c->deinterlace) return WHY("deinterlace_fields %d needs deinterlace (1 top field first, 2 bottom field first): it is that filter's output rate", c->deinterlace_fields);
   if (c->denoise < 0 || c->denoise > 16) return WHY("denoise %d out of range (0 none, 1 .. 16 the strength)", c->denoise);
   if (c->denoise && !c->store_frames) return WHY("denoise %d needs a frame store (store_frames > 0): the filter reads the frames before and after each frame", c->denoise);
   if (c->denoise && c->deinterlace) return WHY("denoise %d together with deinterlace %d is not built: the chain of the two needs a third copy of a group", c->denoise, c->deinterlace);
@@ -656,6 +660,7 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
   const av1mi_gop_config &c = g->cfg;
   const av1mi_source_layout &Y = g->layout;
   const int S = c.segments, dei = c.deinterlace, three = dei || c.denoise;      // three: the table holds P, C, N
+  const int fields = c.deinterlace_fields;      // index[] holds OUTPUT positions: source frame o >> 1, phase o & 1
   for (int p = 0; p < 3; p++) src[p] = dev_src ? dev_src[p] : s.d_in[p];
   s.has_grain = index && c.denoise;
   if (index) {
@@ -663,22 +668,32 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
     const void **table = (const void **)s.h_table;
     const size_t frame_bytes[3] = { Y.plane[0].frame_bytes, Y.plane[1].frame_bytes, Y.plane[2].frame_bytes };
     auto frame = [&](int p, int pos) { return (const void *)((const char *)st.d[p] + frame_bytes[p] * (size_t)pos); };
-    for (int sg = 0; sg < S; sg++)
+    const size_t table_bytes = (size_t)S * 3 * (three ? 3 : 1) * sizeof(void *);
+    uint8_t *phase = (uint8_t *)s.h_table + table_bytes;      // (field rate only: the slot's table was allocated with S bytes more)
+    for (int sg = 0; sg < S; sg++) {
+      const int pos = fields && index[sg] >= 0 ? index[sg] >> 1 : index[sg];
+      if (fields) phase[sg] = index[sg] >= 0 ? (uint8_t)(index[sg] & 1) : 0;
       for (int p = 0; p < 3; p++) {
-        const bool flat = index[sg] < 0 || !frame_bytes[p];
-        if (!three) table[sg * 3 + p] = flat ? nullptr : frame(p, index[sg]);
+        const bool flat = pos < 0 || !frame_bytes[p];
+        if (!three) table[sg * 3 + p] = flat ? nullptr : frame(p, pos);
         else {      // P, C, N follow the POSITION in the store's run, clamped at its ends
           const void **e = table + (sg * 3 + p) * 3;
-          e[0] = flat ? nullptr : frame(p, index[sg] > 0 ? index[sg] - 1 : 0);
-          e[1] = flat ? nullptr : frame(p, index[sg]);
-          e[2] = flat ? nullptr : frame(p, index[sg] + 1 < st.run ? index[sg] + 1 : st.run - 1);
+          e[0] = flat ? nullptr : frame(p, pos > 0 ? pos - 1 : 0);
+          e[1] = flat ? nullptr : frame(p, pos);
+          e[2] = flat ? nullptr : frame(p, pos + 1 < st.run ? pos + 1 : st.run - 1);
         }
       }
-    G_HIP(hipMemcpyAsync(s.d_table, s.h_table, (size_t)S * 3 * (three ? 3 : 1) * sizeof(void *), hipMemcpyHostToDevice, main));
+    }
+    G_HIP(hipMemcpyAsync(s.d_table, s.h_table, table_bytes + (fields ? (size_t)S : 0), hipMemcpyHostToDevice, main));
     G_HIP(hipStreamWaitEvent(main, st.filled, 0));
     {
       av1mi::ProfScope ps(g->ctx, AV1MI_K_SCENE, main);
-      if (dei) {
+      if (fields) {
+        av1mi::DeintFieldsLaunch L;
+        fed_geometry(g, &s, L);
+        L.parity = dei - 1; L.phase = (const uint8_t *)s.d_table + table_bytes;
+        G_HIP(av1mi::launch_deint_gather_fields(L, main));
+      } else if (dei) {
         av1mi::DeintLaunch L;
         fed_geometry(g, &s, L);
         L.parity = dei - 1;
@@ -1181,11 +1196,13 @@ int av1mi_gop_submit_stored(av1mi_gop *g, int store, const int32_t *index, int f
   if (!g->cfg.store_frames) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "the session has no frame store (store_frames 0)");
   if (store < 0 || store > 1 || !index || !g->store[store].has_fill) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: store %d holds nothing, or no index", store);
   if (frame_type != 0 && frame_type != 1) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: frame_type %d (0 key or 1 inter: the layout is the caller's)", frame_type);
+  const int per = g->cfg.deinterlace_fields ? 2 : 1;      // output positions per source frame
   for (int s = 0; s < g->cfg.segments; s++)
-    if (index[s] < -1 || index[s] >= g->cfg.store_frames) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: index[%d] = %d outside the store of %d frames", s, (int)index[s], g->cfg.store_frames);
+    if (index[s] < -1 || index[s] >= per * g->cfg.store_frames)
+      return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: index[%d] = %d outside the store of %d frames%s", s, (int)index[s], g->cfg.store_frames, per == 2 ? " (two output positions each)" : "");
   for (int s = 0; (g->cfg.deinterlace || g->cfg.denoise) && s < g->cfg.segments; s++)
-    if (index[s] >= g->store[store].run)
-      return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: index[%d] = %d beyond the store's run of %d frames (the filter reads the neighbours inside it)", s, (int)index[s], g->store[store].run);
+    if (index[s] >= per * g->store[store].run)
+      return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: index[%d] = %d beyond the store's run of %d frames%s (the filter reads the neighbours inside it)", s, (int)index[s], g->store[store].run, per == 2 ? " (two output positions each)" : "");
   return submit_batch(g, frame_type, nullptr, store, index);
 }
 

@@ -11,6 +11,8 @@
 //
 // With -av1mi_deinterlace (or a deinterlacer in the chain) an interlaced source takes the same stored path, without the analysis unless
 // -av1mi_scenecut asks for it: the session's gather deinterlaces every frame on its way from the store (av1mi_gop_config.deinterlace).
+// With -av1mi_deinterlace_rate field it makes two output frames of every stored frame: the groups, their layouts and the stored batches'
+// indices then count OUTPUT frames, the reader and the store source frames (SessionPlan::out_per_src; fieldrate.hpp).
 // With -av1mi_scenecut the GOPs of a group do not start every `gop` frames but where the scene analysis finds cuts: the group's frames go
 // into the session's frame store in file order (av1mi_gop_store_put), are analysed there (av1mi_gop_store_analyse), the planner
 // (sceneplan.hpp) lays the GOPs out, and every batch is gathered from the store (av1mi_gop_submit_stored).  The session has two stores:
@@ -36,6 +38,7 @@
 #include <vector>
 #include "av1_bitstream.hpp"
 #include "cropplan.hpp"
+#include "fieldrate.hpp"
 #include "ratecontrol.hpp"
 #include "sceneplan.hpp"
 #include "y4m.hpp"
@@ -66,7 +69,11 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
   const bool scaling = win.w != 0 || tw != src.w || th != src.h || job.scale_w != 0;      // a window is fed like a source to be scaled: whole frames
   const int G = job.gop, w = (tw + 7) & ~7, h = (th + 7) & ~7;       // the coded size; tw x th is what a decoder outputs
   int S = std::max(job.segments, 1);
-  if (src.known_frames >= 0) S = (int)std::max<long>(1, std::min<long>(S, (src.known_frames + G - 1) / G));      // no more segments than the file has GOPs
+  // the output: -av1mi_deinterlace_rate field makes two frames of each source frame, at twice the rate; G counts OUTPUT frames
+  const JobOutput output = JobOutputOf(job, src.interlace, src.fps_n, src.fps_d, src.known_frames);
+  plan->out_per_src = output.per_source; plan->fps_n = output.fps_n; plan->fps_d = output.fps_d;
+  if (output.per_source == 2 && (G & 1)) return refuse("with -av1mi_deinterlace_rate field -g counts output frames, two per source frame, and must be even: not -g " + std::to_string(G));
+  if (output.frames >= 0) S = (int)std::max<long>(1, std::min<long>(S, (output.frames + G - 1) / G));      // no more segments than the file has GOPs
   av1mi_gop_config &cfg = plan->cfg;
   if (w != tw || h != th) { cfg.visible_width = tw; cfg.visible_height = th; }
   if (scaling) { cfg.source_width = src.w; cfg.source_height = src.h; }
@@ -96,6 +103,7 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
     dei = src.interlace;
   }
   cfg.deinterlace = dei;
+  cfg.deinterlace_fields = output.per_source == 2;
   // -av1mi_scenecut, or a job that deinterlaces: the frame store holds one group (the deinterlacer's run)
   // -av1mi_denoise: the same store, the denoiser in the gather; -av1mi_film_grain (1 unless told otherwise): parameters in every frame header
   cfg.denoise = job.denoise;
@@ -123,7 +131,7 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
   plan->grainy = job.denoise > 0 && job.film_grain != 0;
   plan->analysed = job.scenecut > 0;
   plan->stored = plan->analysed || dei != 0 || job.denoise > 0;
-  if (plan->stored) cfg.store_frames = S * G;
+  if (plan->stored) cfg.store_frames = S * G / output.per_source;      // SOURCE frames: a group of S G output frames
   // What the reader threads deliver, one segment's share of the pinned buffers: frames of the coded size (the source's edge replicated
   // into the padding) or, when the GPU scales, of the source size rounded up to 8; no chroma planes for a grey source.  (A config the
   // layout refuses, av1mi_gop_open refuses, with the reason.)
@@ -249,12 +257,12 @@ struct Run {
     if (!plan.square) sink.set_display_size((int)((long)plan.tw * y.sar_n / y.sar_d), plan.th);
     for (const std::string &side : job.tracks)
       if (!sink.add_side_file(side, err)) return 1;
-    if (!sink.open(job.output, sp, y.fps_n, y.fps_d, err)) return 1;
+    if (!sink.open(job.output, sp, plan.fps_n, plan.fps_d, err)) return 1;
     if (job.bitrate || job.target_bpp_u) {
       av1mi_rc_params rp;
       memset(&rp, 0, sizeof(rp));
       av1mi_rc_defaults(&rp);
-      if (job.bitrate) { rp.target_num = job.bitrate * y.fps_d; rp.target_den = 8ll * y.fps_n; }
+      if (job.bitrate) { rp.target_num = job.bitrate * plan.fps_d; rp.target_den = 8ll * plan.fps_n; }      // bytes per OUTPUT frame
       else { rp.target_num = job.target_bpp_u * plan.tw * plan.th; rp.target_den = 8000000; }
       if (job.qmin) rp.qmin = job.qmin;
       if (job.qmax) rp.qmax = job.qmax;
@@ -317,14 +325,20 @@ struct Run {
 
   // THE place a group is laid out: the nominal layout (GOP s = frames s G .. of the group), or with -av1mi_scenecut the planner's, its
   // boundaries moved onto the cuts the analysis of the store finds.  (A job that only deinterlaces or denoises keeps the nominal layout.)
+  // frames: the group's OUTPUT frames.  At field rate the analysis still reads the source frames, and FieldRateCuts places their cuts.
   int lay_out(long frames, Group *g) {
     g->frames = frames; g->start.resize((size_t)S); g->len.resize((size_t)S);
     for (int s = 0; s < S; s++) { g->start[(size_t)s] = s * G; g->len[(size_t)s] = (int32_t)std::max<long>(0, std::min<long>(G, frames - (long)s * G)); }
     if (!plan.analysed) return 0;
-    std::vector<av1mi_scene_record> scene((size_t)frames);
+    const long n = frames / plan.out_per_src;      // source frames
+    std::vector<av1mi_scene_record> scene((size_t)n);
     g->cut.assign((size_t)frames, 0);
-    if (av1mi_gop_store_analyse(gop, cur_store, (int)frames, scene.data()) != AV1MI_OK) return lib_error("av1mi_gop_store_analyse");
-    for (long f = 0; f < frames; f++) g->cut[(size_t)f] = (uint8_t)av1mi_scene_is_cut(&scene[(size_t)f], job.scenecut);
+    if (av1mi_gop_store_analyse(gop, cur_store, (int)n, scene.data()) != AV1MI_OK) return lib_error("av1mi_gop_store_analyse");
+    for (long f = 0; f < n; f++) g->cut[(size_t)f] = (uint8_t)av1mi_scene_is_cut(&scene[(size_t)f], job.scenecut);
+    if (plan.out_per_src == 2) {
+      const std::vector<uint8_t> source_cut(g->cut.begin(), g->cut.begin() + n);
+      FieldRateCuts(source_cut.data(), n, g->cut.data());
+    }
     if (av1mi_plan_gops((int)frames, G, S, job.min_gop, g->cut.data(), g->start.data(), g->len.data()) < 0) return fail(1, "Invalid argument: -av1mi_min_gop does not fit the GOP length");
     return 0;
   }
@@ -440,18 +454,19 @@ struct Run {
   int run_groups() {
     for (int code;; g0 += S) {
       long have = next_frames;
+      const int F = plan.out_per_src;      // g0 and G count OUTPUT frames; the reader and the store count source frames (G is even where F is 2)
       if (!plan.stored || have < 0) {
-        if ((have = y.prepare(g0 * G, (long)S * G, err)) < 0) return 1;
+        if ((have = y.prepare(g0 * G / F, (long)S * G / F, err)) < 0) return 1;
         long put = 0;
         if (plan.stored && (code = put_all(cur_store, have, &put))) return code;
       }
       if (have == 0) return 0;
       total_frames += have;
       Group group;
-      if ((code = lay_out(have, &group))) return code;
+      if ((code = lay_out(have * F, &group))) return code;
       if (plan.stored) {
         // the group after this one: prepared now (this group's frames are all in the store), put chunk by chunk beside the batches
-        if ((next_frames = y.prepare((g0 + S) * G, (long)S * G, err)) < 0) return 1;
+        if ((next_frames = y.prepare((g0 + S) * G / F, (long)S * G / F, err)) < 0) return 1;
         next_put = 0;
       }
       GroupOut out((size_t)S);
@@ -466,7 +481,7 @@ struct Run {
     if (!sink.close(err)) return 1;
     if (rc && rc_frames > 0) {
       const av1mi_rc_params &rp = rc->params();
-      const double fps = (double)y.fps_n / y.fps_d, px = (double)plan.tw * plan.th, want = 8.0 * rp.target_num / rp.target_den, got = 8.0 * rc_bytes / rc_frames;
+      const double fps = (double)plan.fps_n / plan.fps_d, px = (double)plan.tw * plan.th, want = 8.0 * rp.target_num / rp.target_den, got = 8.0 * rc_bytes / rc_frames;
       fprintf(stderr, "[av1mi] rate control: target %.0f bit/s (%.4f bit/pixel), achieved %.0f bit/s (%.4f bit/pixel) over %lld frames\n", want * fps, want / px,
               got * fps, got / px, rc_frames);
     }

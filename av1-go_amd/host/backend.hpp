@@ -27,6 +27,10 @@ struct SessionPlan {
   bool packed, stored, analysed, grainy, measure;
   int coded_bd;                 // the depth of the stream (-av1mi_depth): what the sequence header, the sink, the rate controller and the figures take
   int reduced_from;             // the source's depth where the job reduces it (10 or 12), else 0
+  // the job's OUTPUT (fieldrate.hpp JobOutputOf): output frames per source frame (2 = field rate: -g, the groups' layouts and the
+  // indices of av1mi_gop_submit_stored count output frames, the reader and the store source frames) and the rate the sink, the rate
+  // controller and the report take
+  int out_per_src, fps_n, fps_d;
 };
 // -av1mi_crop W:H:X:Y against a w x h picture: 0 and *win, or 1 and the text
 int ExplicitWindow(const BackendJob &job, int w, int h, CropRect *win, std::string *err);
@@ -37,7 +41,7 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
 // grain: the luma scaling at mid grey where it denoises)
 struct FrameOut { std::vector<uint8_t> unit; av1mi_quality q[3]; int base_q_idx; int grain; int ar; int lr_filtered, lr_units; int cdef_moved, cdef_sbs; int lf_y, lf_uv; };      // ar: the ar_coeff_lag coded (-av1mi_grain_lag)
 // the layout of a group of frames over the session's segments: GOP s holds frames start[s] .. start[s] + len[s] - 1 of the group; cut
-// (analysed jobs) flags the frames the scene analysis found
+// (analysed jobs) flags the frames the scene analysis found.  At field rate the frames of a group are OUTPUT frames (two per source frame).
 struct Group {
   std::vector<int32_t> start, len;
   std::vector<uint8_t> cut;

@@ -7,6 +7,7 @@
 #include "mux.hpp"
 #include "y4m.hpp"
 #include "backend.hpp"
+#include "fieldrate.hpp"
 #include "../csrc/quality.hpp"
 
 using namespace av1mi_host;
@@ -124,6 +125,30 @@ int av1mi_host_parse_deinterlace_option(const char *joined, char *err, int cap) 
   strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
   return ok ? job.deinterlace : -1;
 }
+// ParseBackendJob's view of -av1mi_deinterlace_rate for an argv joined with '\n': BackendJob::deint_rate (0 frame, 1 field), or -1 with the
+// text in err
+int av1mi_host_parse_deinterlace_rate(const char *joined, char *err, int cap) {
+  const std::vector<std::string> a = split_lines(joined);
+  BackendJob job; std::string e;
+  const bool ok = ParseBackendJob(a, &job, &e);
+  strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
+  return ok ? job.deint_rate : -1;
+}
+// JobOutputOf (fieldrate.hpp) for an argv joined with '\n' on a source with the header's I parameter `interlace` (0 progressive, 1 It, 2 Ib,
+// 3 Im), fps_n / fps_d and `frames` frames (-1 = a stream): 0 and out = { output frames per source frame, fps_n, fps_d, frames }, or -1
+// with the text in err
+int av1mi_host_job_output(const char *joined, int interlace, int fps_n, int fps_d, long long frames, long long *out, char *err, int cap) {
+  const std::vector<std::string> a = split_lines(joined);
+  BackendJob job; std::string e;
+  const bool ok = ParseBackendJob(a, &job, &e);
+  strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
+  if (!ok) return -1;
+  const JobOutput o = JobOutputOf(job, interlace, fps_n, fps_d, (long)frames);
+  out[0] = o.per_source; out[1] = o.fps_n; out[2] = o.fps_d; out[3] = o.frames;
+  return 0;
+}
+// FieldRateCuts (fieldrate.hpp): n source frames' cut flags -> 2 n output frames'
+void av1mi_host_field_rate_cuts(const uint8_t *cut, int n, uint8_t *out) { FieldRateCuts(cut, n, out); }
 // ScaleTarget (transcode.hpp): the size a filter chain yields on a source; 0, or -1 for a chain with an unsupported filter
 int av1mi_host_scale_target(int iw, int ih, int sar_n, int sar_d, const char *chain, int *w, int *h) {
   std::string e;

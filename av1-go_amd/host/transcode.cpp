@@ -307,6 +307,11 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
       else { if (err) *err = "Invalid argument: -av1mi_deinterlace takes off, auto, tff or bff, not " + v; return false; }
       deint_given = true;
     }
+    else if (args[i] == "-av1mi_deinterlace_rate") {
+      const std::string &v = args[i + 1];
+      if (v == "frame") job->deint_rate = 0; else if (v == "field") job->deint_rate = 1;
+      else { if (err) *err = "Invalid argument: -av1mi_deinterlace_rate takes frame or field, not " + v; return false; }
+    }
     else if (args[i] == "-av1mi_denoise") {
       if (!plain_int(args[i + 1], &job->denoise) || job->denoise > 16) { if (err) *err = "Invalid argument: -av1mi_denoise takes a strength 1 .. 16 (0 = off), not " + args[i + 1]; return false; }
     }
@@ -435,6 +440,10 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
   if (job->qmin && job->qmax && job->qmin > job->qmax) { if (err) *err = "Invalid argument: -qmin " + std::to_string(job->qmin) + " above -qmax " + std::to_string(job->qmax); return false; }
   if (job->scenecut && job->pack10) { if (err) *err = "Invalid argument: -av1mi_scenecut keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
   if (job->deinterlace && job->pack10) { if (err) *err = "Invalid argument: -av1mi_deinterlace keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
+  if (job->deint_rate && job->deinterlace && job->gop >= 1 && (job->gop & 1)) {
+    if (err) *err = "Invalid argument: with -av1mi_deinterlace_rate field -g counts output frames, two per source frame, and must be even: not -g " + std::to_string(job->gop);
+    return false;
+  }
   if ((job->crop_mode || (job->have_vf && job->vf.find("crop=") != std::string::npos)) && job->pack10) { if (err) *err = "Invalid argument: a crop window is cut from planar planes on the GPU: not together with -av1mi_pack10 1"; return false; }
   if (job->crop_mode == 1) {      // (a regular file whose frames cannot be addressed is refused when it is opened: backend.cpp)
     struct stat st;

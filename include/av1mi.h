@@ -737,7 +737,20 @@ int av1mi_crop_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int
  *             value.  The buffer's sample at (x, y) beyond the true size is the filter's value at (min(x, w - 1), min(y, h - 1)): the
  *             padding of the output replicates its own edge, which is what the analysis and the block pipeline expect of a fed frame.
  *             Nothing beyond the true size is read: the input's padding may be undefined.
- * Field-rate output, inverse telecine and neighbours across the boundaries of a run are not built. */
+ * FIELD-RATE OUTPUT ("bob": one progressive frame per FIELD, 25i -> 50p).  A run of n source frames gives 2 n output frames; output
+ * o = 2 f + phi comes from source frame f with phase phi in {0, 1}, at the time of that frame's first (phi = 0) or second (phi = 1)
+ * field.  With k the parity above:
+ *   phi = 0   exactly the filter above for frame f: the kept parity is k, t0 = P[y][x], t1 = C[y][x].
+ *   phi = 1   the kept lines are those with y mod 2 == 1 - k: up, dn, spatial and output are defined as above on C's lines of THAT
+ *             parity.  temporal changes: t0 = C[y][x] (the first field of this frame, one field earlier), t1 = N[y][x] (the first field
+ *             of the next frame, one field later).  bound is unchanged: P[up] / P[dn] and N[up] / N[dn] are the fields of the kept
+ *             parity before and after.
+ *   ends      P and N clamp at the ends of the run as above, so the last frame's second field sees t0 = t1 (and the first frame's first
+ *             field, as ever, too).
+ * A still picture gives the weave in both phases, exactly; the padding rule is unchanged.  CONSEQUENCE: output (f, phi = 1) is the
+ * same-rate filter applied to the time-reversed triple with the opposite parity — filter(P = N, C = C, N = P, parity 1 - k) — because t,
+ * the first term of m and the pair of bound terms are symmetric in P and N.
+ * Inverse telecine and neighbours across the boundaries of a run are not built. */
 /* The gather with the filter in it, ONE launch for all planes and segments.  d_table: segments * 9 device pointers IN DEVICE MEMORY,
  * [(s * 3 + p) * 3 + i] = plane p of segment s's frame P (i = 0), C (1) and N (2), the run's clamping applied by whoever fills it; a null
  * C makes the slot flat (zeros).  Planes whose rows are whole 16-byte units must be 16-byte aligned, any other 4-byte.  plane_w x
@@ -747,6 +760,13 @@ int av1mi_crop_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int
  * gather it stands in for. */
 int av1mi_deinterlace_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int parity,
                              int segments, const void *const *d_table, void *const d_dst[3]);
+/* The same at field rate ("FIELD-RATE OUTPUT" above), ONE launch (k_deint_gather's field-rate instantiation): av1mi_deinterlace_gather's
+ * arguments and rules, plus d_phase: `segments` bytes IN DEVICE MEMORY, the phase of each segment's output.  Phases may differ from
+ * segment to segment inside one launch.  A value outside 0 .. 1 cannot be checked on the device: only the low bit is read.  A launch
+ * whose phases are all 0 writes the bytes av1mi_deinterlace_gather writes.  parity stays the SOURCE's (0 = top field first); the table
+ * holds P, C, N of the SOURCE frame o >> 1 of output o. */
+int av1mi_deinterlace_gather_fields(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int parity,
+                                    int segments, const void *const *d_table, const uint8_t *d_phase, void *const d_dst[3]);
 
 /* ---- denoising: a temporal filter inside the gather (av1-go_amd/csrc/grain_kernels.hip), the deinterlacer's sibling: it removes what
  * changes from frame to frame while the picture stands still — film grain, sensor noise — so that the coder does not spend its bits on
@@ -1101,6 +1121,13 @@ typedef struct av1mi_gop_config {
    * fed the reduced planes yields.  depth_dither: 0 = round, 1 = ordered (enum av1mi_depth_mode); needs coded_bit_depth 8.  Refused with
    * denoise: the grain records are measured in 10-bit codes and the grain would be synthesised into an 8-bit stream. */
   int coded_bit_depth, depth_dither;
+  /* Field-rate deinterlacing ("FIELD-RATE OUTPUT" under "deinterlacing"; 0 = none: nothing new is allocated, launched or accepted; 1 =
+   * one output frame per field).  Needs deinterlace 1 / 2 and is refused without it.  A store's run of n source frames then stands for
+   * 2 n OUTPUT frames, and the index[s] of av1mi_gop_submit_stored is an output position o in 0 .. 2 run - 1 (source frame o >> 1,
+   * phase o & 1; -1 stays a flat slot); the gather is k_deint_gather's field-rate instantiation, and the slot's table carries one phase
+   * byte per segment behind its pointers, in the same copy.  av1mi_gop_store_put / av1mi_gop_store_analyse keep SOURCE positions and
+   * store_frames keeps counting source frames.  Everything behind the gather is unchanged. */
+  int deinterlace_fields;
 } av1mi_gop_config;
 
 /* The source layout: what a session opened with a config is FED, as one description.  Everything a caller sizes or strides by — the
@@ -1238,7 +1265,7 @@ int av1mi_gop_store_analyse(av1mi_gop *g, int store, int frames, av1mi_scene_rec
 /* A batch from the store: index[s] (segments entries) = the store position of segment s's frame, or -1 for a flat slot (zeros, as the
  * product feeds a segment that has no frame; its output is to be dropped).  The gather stands in for the upload, the stages follow as
  * ever.  frame_type must be 0 or 1: the layout is the caller's.  A later av1mi_gop_store_put into the same store is ordered behind this
- * batch's gather by an event. */
+ * batch's gather by an event.  In a session with deinterlace_fields index[s] is an OUTPUT position (source position * 2 + phase). */
 int av1mi_gop_submit_stored(av1mi_gop *g, int store, const int32_t *index, int frame_type);
 /* wait for the oldest batch in flight and describe its symbols; AV1MI_E_INVAL when nothing is in flight */
 int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out);

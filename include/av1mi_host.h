@@ -189,7 +189,9 @@ long long av1mi_obu_write_blocks_temporal_unit(const av1mi_obu_blocks *f, int wi
  * film grain synthesis parameters from what was removed, av1mi_filmgrain.h; an error without -av1mi_denoise);
  * "-av1mi_deinterlace off | auto | tff | bff" (off = default; auto deinterlaces a source whose Y4M header says It / Ib on the GPU, at the
  * same frame rate, and refuses Im; a chain that names yadif, bwdif or deinterlace_vaapi — bare, mode=0 or mode=send_frame — means auto;
- * include/av1mi.h "deinterlacing", av1mi_gop_config.deinterlace);
+ * include/av1mi.h "deinterlacing", av1mi_gop_config.deinterlace); "-av1mi_deinterlace_rate frame | field" (frame = default; field = one
+ * output frame per FIELD where the job deinterlaces, at twice the source's frame rate: "-g" then counts output frames and must be even;
+ * av1mi_gop_config.deinterlace_fields; the chain's own field-rate spellings stay refused);
  * everything else is accepted and ignored.  Returns 0 and leaves the output file in place on
  * success; -1 when the backend could not run at all (no HIP device: transcode.go:311); another non-zero code on failure.
  * err receives the reference-shaped text ("av1mi failed with exit code N: ...", at most 800 characters + "..."). */

@@ -6,6 +6,9 @@ measured against, in the same process, legs alternated, `--reps` repetitions wit
    1080p 8-bit x 12, every segment with its own P, C and N frames in a store past the Infinity Cache; HIP events around `--launches`
    launches.  Rates against the algorithmic bytes (one read of C plus one write) and against three reads plus one write.
 2. av1mi_run_transcode on an interlaced 1080p clip, -av1mi_deinterlace auto against off, wall clock, frames per second.
+3. Field rate (include/av1mi.h "FIELD-RATE OUTPUT"): the field-rate launch (av1mi_deinterlace_gather_fields; phases alternating over the
+   segments, and all second fields) beside the same-rate launch in leg 1's loop, on the same batch; and the transcode with
+   -av1mi_deinterlace_rate field beside frame, in OUTPUT frames per second (field rate makes two of every source frame).
 
     python tools/bench_deinterlace.py --out profiles/deinterlace.json
 """
@@ -51,8 +54,9 @@ def kernel_leg(ctx, W, H, bd, segs, reps, launches):
     plain = np.array([[d_store[p].ptr + (3 * s + 1) * nbytes[p] for p in range(3)] for s in range(segs)], np.uint64)
     three = np.array([[[d_store[p].ptr + (3 * s + i) * nbytes[p] for i in range(3)] for p in range(3)] for s in range(segs)], np.uint64)
     d_plain, d_three = ctx.to_device(plain), ctx.to_device(three)
+    d_mixed, d_second = ctx.to_device(np.arange(segs, dtype=np.uint8) & 1), ctx.to_device(np.ones(segs, np.uint8))      # the phases
     d_dst = [ctx.alloc(segs * b) for b in nbytes]
-    t_deint, t_plain = [], []
+    t_deint, t_plain, t_mixed, t_second = [], [], [], []
     for rep in range(reps + 1):      # the first repetition warms up
         ctx.timer_begin()
         for _ in range(launches):
@@ -62,16 +66,26 @@ def kernel_leg(ctx, W, H, bd, segs, reps, launches):
         for _ in range(launches):
             ctx.frames_gather(nbytes, segs, d_plain, d_dst)
         b = ctx.timer_end() / launches
+        fields = []
+        for d_phase in (d_mixed, d_second):
+            ctx.timer_begin()
+            for _ in range(launches):
+                ctx.deinterlace_gather_fields(bd, sizes, sizes, 0, segs, d_three, d_phase, d_dst)
+            fields.append(ctx.timer_end() / launches)
         if rep:
             t_deint.append(a)
             t_plain.append(b)
-    for b in d_store + d_dst + [d_plain, d_three]:
+            t_mixed.append(fields[0])
+            t_second.append(fields[1])
+    for b in d_store + d_dst + [d_plain, d_three, d_mixed, d_second]:
         b.free()
     frame = sum(nbytes) * segs
     md, mp = statistics.median(t_deint), statistics.median(t_plain)
     gbs = lambda n, ms: n / (ms * 1e-3) / 1e9
     return {"width": W, "height": H, "bit_depth": bd, "segments": segs, "batch_bytes": frame,
             "deint_gather_ms": spread(t_deint), "frames_gather_ms": spread(t_plain), "ratio_to_the_plain_gather": md / mp,
+            "fields_gather_mixed_phases_ms": spread(t_mixed), "fields_gather_second_fields_ms": spread(t_second),
+            "fields_mixed_over_same_rate": statistics.median(t_mixed) / md, "fields_second_over_same_rate": statistics.median(t_second) / md,
             "deint_gb_per_s_one_read_one_write": gbs(2 * frame, md), "deint_gb_per_s_three_reads_one_write": gbs(4 * frame, md),
             "frames_gather_gb_per_s": gbs(2 * frame, mp)}
 
@@ -82,20 +96,24 @@ def transcode_leg(reps, frames):
     with tempfile.TemporaryDirectory() as d:
         src = os.path.join(d, "it.y4m")
         deint_clips.write_y4m(src, deint_clips.pan_clip(W, H, frames, 8, 0), 8, interlace="t")
-        t = {"auto": [], "off": []}
+        # field: -g counts output frames, so -g 60 keeps a GOP the 30 source frames long that the other two legs code
+        legs = {"auto": ["-g", 30, "-av1mi_deinterlace", "auto"], "off": ["-g", 30, "-av1mi_deinterlace", "off"],
+                "field": ["-g", 60, "-av1mi_deinterlace", "auto", "-av1mi_deinterlace_rate", "field"]}
+        t = {mode: [] for mode in legs}
         for rep in range(reps + 1):
-            for mode in ("auto", "off"):
+            for mode, extra in legs.items():
                 t0 = time.perf_counter()
-                code, err = av1stream.run_transcode(["-i", src, "-g", 30, "-av1mi_segments", 4, "-av1mi_deinterlace", mode, os.path.join(d, mode + ".ivf")])
+                code, err = av1stream.run_transcode(["-i", src, "-av1mi_segments", 4] + extra + [os.path.join(d, mode + ".ivf")])
                 dt = time.perf_counter() - t0
                 if code:
                     raise RuntimeError(err)
                 if rep:
-                    t[mode].append(frames / dt)
+                    t[mode].append((2 if mode == "field" else 1) * frames / dt)      # OUTPUT frames per second
         for mode in t:
             out[mode + "_frames_per_s"] = spread(t[mode])
             out[mode + "_bytes"] = os.path.getsize(os.path.join(d, mode + ".ivf"))
     out["auto_over_off"] = out["auto_frames_per_s"]["median"] / out["off_frames_per_s"]["median"]
+    out["field_over_auto_in_output_frames"] = out["field_frames_per_s"]["median"] / out["auto_frames_per_s"]["median"]
     return out
 
 
