@@ -145,7 +145,7 @@ class GopConfig(C.Structure):
                 ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int), ("crop_height", C.c_int), ("denoise_range", C.c_int),
                 ("tone_map", C.c_int), ("tone_map_peak", C.c_int), ("grain_cov", C.c_int), ("lr_search", C.c_int),
                 ("cdef_search", C.c_int), ("lf_search", C.c_int), ("coded_bit_depth", C.c_int), ("depth_dither", C.c_int),
-                ("deinterlace_fields", C.c_int)]
+                ("deinterlace_fields", C.c_int), ("telecine", C.c_int)]
 
 
 class FrameParams(C.Structure):
@@ -182,6 +182,8 @@ GRAIN_COV_DTYPE = np.dtype([("sum", "<i8", (4, 13))])      # av1mi_grain_cov_rec
 DENOISE_VEC_DTYPE = np.dtype([("dx_p", "i1"), ("dy_p", "i1"), ("dx_n", "i1"), ("dy_n", "i1")])      # av1mi_denoise_vec: a block's vectors towards P and N
 SCENE_DTYPE = np.dtype([("inter_sad", "<u8"), ("intra_sad", "<u8"), ("blocks", "<u4"), ("reserved", "<u4")])
 CROP_DTYPE = np.dtype([("top", "<u4"), ("bottom", "<u4"), ("left", "<u4"), ("right", "<u4")])      # av1mi_crop_record ("bar detection")
+# av1mi_telecine_record ("inverse telecine"): comb of the candidates p, c, n; bdiff
+TELECINE_DTYPE = np.dtype([("comb", "<u8", 3), ("bdiff", "<u8")])
 assert SCENE_DTYPE.itemsize == 24
 QUALITY_DTYPE = np.dtype([("sse", "<u8"), ("ssim_sum", "<f8"), ("samples", "<u4"), ("windows", "<u4")])
 assert QUALITY_DTYPE.itemsize == 24
@@ -291,7 +293,7 @@ class GopSession:
 
     def __init__(self, ctx, width, height, bit_depth, base_q_idx, gop_length, segments=1, search_range=8, gpu_entropy=0, visible=None, coder_streams=0,
                  key_block_size=0, input_format=0, source=None, quality_stats=0, coarse_range=0, source_chroma=0, source_bit_depth=0, store_frames=0, deinterlace=0, denoise=None, crop=None, denoise_range=None, tone_map=0, tone_map_peak=0, grain_cov=None, lr_search=None, cdef_search=None, lf_search=None, coded_bit_depth=None,
-                 depth_dither=None, deinterlace_fields=None):
+                 depth_dither=None, deinterlace_fields=None, telecine=None):
         """visible: the true (width, height) when width x height is it rounded up to 8 (the caller replicates the source edge);
         key_block_size 32: key frames in 32x32 blocks (av1mi_gop_config.key_block_size); input_format: INPUT_* (the layout of the
         source handed to input_planes() / submit_device()); source: the true (width, height) of the frames the session is fed when
@@ -315,7 +317,10 @@ class GopSession:
         coded_bit_depth: 8 in a bit_depth 10 session = the depth reduction at the end of the input chain: everything behind it is an 8-bit
         session (av1mi_gop_config.coded_bit_depth); depth_dither: DEPTH_ROUND or DEPTH_ORDERED.  None leaves a field unset (0);
         deinterlace_fields: 1 = one output frame per field (av1mi_gop_config.deinterlace_fields; needs deinterlace): submit_stored() then
-        takes OUTPUT positions, source position * 2 + phase.  None leaves the field unset (0)"""
+        takes OUTPUT positions, source position * 2 + phase.  None leaves the field unset (0);
+        telecine: 1 = inverse telecine (av1mi_gop_config.telecine; needs store_frames): the stores hold store_frames + 2 frames,
+        store_telecine() gives the field-match records and submit_woven() weaves a batch from two positions per segment.  None leaves
+        the field unset (0)"""
         self.ctx, self.w, self.h, self.bd, self.segments = ctx, width, height, bit_depth, segments
         vw, vh = visible if visible is not None else (0, 0)
         sw, sh = source if source is not None else (0, 0)
@@ -341,6 +346,8 @@ class GopSession:
             self.cfg.depth_dither = int(depth_dither)
         if deinterlace_fields is not None:
             self.cfg.deinterlace_fields = int(deinterlace_fields)
+        if telecine is not None:
+            self.cfg.telecine = int(telecine)
         if crop is not None:
             self.cfg.crop_x, self.cfg.crop_y, self.cfg.crop_width, self.cfg.crop_height = (int(v) for v in crop)
         self.g = C.c_void_p()
@@ -395,6 +402,21 @@ class GopSession:
         assert idx.size == self.segments
         self.ctx.lib.av1mi_gop_submit_stored.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         self.ctx._chk(self.ctx.lib.av1mi_gop_submit_stored(self.g, int(store), idx.ctypes.data, int(frame_type)))
+
+    def store_telecine(self, store, frames):
+        """the field-match records (TELECINE_DTYPE [frames]) of the run of frames 0 .. frames - 1 of a store (av1mi_gop_store_telecine)"""
+        out = np.zeros(frames, TELECINE_DTYPE)
+        self.ctx.lib.av1mi_gop_store_telecine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        self.ctx._chk(self.ctx.lib.av1mi_gop_store_telecine(self.g, int(store), int(frames), out.ctypes.data))
+        return out
+
+    def submit_woven(self, store, top, bottom, frame_type):
+        """a batch woven from a store: segment s's frame takes its even lines from position top[s] and its odd lines from bottom[s];
+        top[s] = -1 = a flat slot (av1mi_gop_submit_woven)"""
+        t, b = np.ascontiguousarray(top, np.int32), np.ascontiguousarray(bottom, np.int32)
+        assert t.size == self.segments and b.size == self.segments
+        self.ctx.lib.av1mi_gop_submit_woven.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        self.ctx._chk(self.ctx.lib.av1mi_gop_submit_woven(self.g, int(store), t.ctypes.data, b.ctypes.data, int(frame_type)))
 
     def set_q(self, base_q_idx):
         """the quantiser (1..255) of every batch submitted from now on; batches in flight keep theirs (av1mi_gop_set_base_q_idx)"""
@@ -825,6 +847,28 @@ class Context:
         self.lib.av1mi_deinterlace_gather_fields.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         sizes, dst = self._gather_planes(plane_sizes, true_sizes, d_dst)
         self._chk(self.lib.av1mi_deinterlace_gather_fields(self.h, int(bit_depth), *sizes, int(parity), int(segments), d_table.ptr, d_phase.ptr if d_phase is not None else None, dst))
+
+    def telecine_analyse(self, Y, bit_depth, true_size):
+        """the field-match records (TELECINE_DTYPE [frames]) of a run of luma planes Y [frames, H8, W8], H8 and W8 multiples of 8, whose
+        picture is true_size = (width, height) (av1mi_telecine_analyse)"""
+        Y = np.ascontiguousarray(Y, np.uint8 if bit_depth == 8 else np.uint16)
+        n, h, w = Y.shape
+        self.lib.av1mi_telecine_analyse.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]
+        d_y, d_out = self.to_device(Y), self.alloc(n * TELECINE_DTYPE.itemsize)
+        try:
+            self._chk(self.lib.av1mi_telecine_analyse(self.h, int(bit_depth), w, h, int(true_size[0]), int(true_size[1]), n, d_y.ptr, d_out.ptr))
+            return d_out.download((n,), TELECINE_DTYPE)
+        finally:
+            d_y.free()
+            d_out.free()
+
+    def telecine_gather(self, bit_depth, plane_sizes, true_sizes, segments, d_table, d_dst):
+        """one launch: the weave gather (av1mi_telecine_gather).  plane_sizes / true_sizes / d_dst as deinterlace_gather's; d_table: DevBuf
+        of segments * 6 uint64, [(s * 3 + p) * 2 + i] = plane p of segment s's top (i = 0) and bottom (1) source (top 0 = zeros);
+        asynchronous"""
+        self.lib.av1mi_telecine_gather.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
+        sizes, dst = self._gather_planes(plane_sizes, true_sizes, d_dst)
+        self._chk(self.lib.av1mi_telecine_gather(self.h, int(bit_depth), *sizes, int(segments), d_table.ptr, dst))
 
     def crop_analyse(self, Y, bit_depth, true_size, limit=24):
         """the margins (CROP_DTYPE [frames]) of luma planes Y [frames, H8, W8], H8 and W8 multiples of 8, whose picture is true_size =

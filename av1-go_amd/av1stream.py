@@ -417,6 +417,44 @@ def field_rate_cuts(cut):
     return out
 
 
+def job_output_ratio(argv, interlace, fps, frames):
+    """job_output() with the ratio: (output frames per source frame, (fps_n, fps_d), frames, (num, den)): num output frames per den source
+    frames, 4 / 5 for a job with -av1mi_ivtc 1"""
+    h = lib()
+    h.av1mi_host_job_output_ratio.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_longlong), C.c_char_p, C.c_int]
+    err, out = C.create_string_buffer(1024), (C.c_longlong * 6)()
+    if h.av1mi_host_job_output_ratio("\n".join(str(x) for x in argv).encode(), "ptbm".index(interlace), int(fps[0]), int(fps[1]), int(frames), out, err, 1024) < 0:
+        raise ValueError(err.value.decode())
+    return int(out[0]), (int(out[1]), int(out[2])), int(out[3]), (int(out[4]), int(out[5]))
+
+
+def parse_ivtc_option(argv):
+    """what an argument vector asks of -av1mi_ivtc: 0 or 1; ValueError with the host's text where the vector is refused"""
+    h = lib()
+    h.av1mi_host_parse_ivtc_option.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
+    err = C.create_string_buffer(1024)
+    k = h.av1mi_host_parse_ivtc_option("\n".join(str(x) for x in argv).encode(), err, 1024)
+    if k < 0:
+        raise ValueError(err.value.decode())
+    return k
+
+
+def plan_telecine(records, front=0, back=0):
+    """av1mi_plan_telecine (host/telecineplan.hpp): the records of a run (av1mi.TELECINE_DTYPE layout: comb [3], bdiff, uint64) whose first
+    `front` and last `back` frames are context -> (top, bottom): the run positions every output frame is woven from; ValueError where the
+    planner refuses its arguments"""
+    h = lib()
+    h.av1mi_plan_telecine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    r = np.ascontiguousarray(records)
+    assert r.dtype.itemsize == 32
+    n = len(r) - int(front) - int(back)
+    top, bottom = np.full(max(n, 1), -7, np.int32), np.full(max(n, 1), -7, np.int32)
+    k = h.av1mi_plan_telecine(r.ctypes.data, len(r), int(front), int(back), top.ctypes.data, bottom.ctypes.data)
+    if k < 0:
+        raise ValueError("av1mi_plan_telecine(%d frames, front %d, back %d) refused" % (len(r), front, back))
+    return top[:k].copy(), bottom[:k].copy()
+
+
 def run_transcode(argv):
     """av1mi_run_transcode (include/av1mi_host.h) on an argument vector: (exit code, error text)"""
     h = lib()

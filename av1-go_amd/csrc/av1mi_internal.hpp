@@ -319,6 +319,20 @@ struct DeintFieldsLaunch : DeintLaunch {
 };
 hipError_t launch_deint_gather_fields(const DeintFieldsLaunch &L, hipStream_t s);
 
+// inverse telecine (telecine_kernels.hip, include/av1mi.h "inverse telecine").  The records of a run of `frames` stacked luma planes of TRUE
+// size w x h in buffers of stride x rows samples: two launches.  scratch: telecine_layout().bytes bytes, 16-byte aligned: per (frame,
+// tile, wave) four 32-bit partials; out: `frames` records (device memory or pinned host memory)
+struct TelecineLayout { int tiles_x, tiles_y, chunks; size_t per_frame, bytes; };
+TelecineLayout telecine_layout(int bd, int w, int h, int frames);
+struct TelecineLaunch {
+  int bd, stride, rows, w, h, frames;
+  const void *luma; void *scratch; av1mi_telecine_record *out;
+};
+hipError_t launch_telecine_analyse(const TelecineLaunch &A, hipStream_t s);
+// the weave gather: a GatherPlanes whose table holds TWO pointers per (segment, plane), [(segment * 3 + plane) * 2 + {0, 1}] = the top and
+// the bottom source (top null = zeros).  ONE launch.
+hipError_t launch_telecine_gather(const GatherPlanes &L, hipStream_t s);
+
 // the denoising gather (grain_kernels.hip, include/av1mi.h "denoising" / "grain records"): a strength (1 .. 16) in place of the parity; bd
 // 8 or 10.  records: segments * 3 records (device or pinned host memory), or null = nothing is measured, ONE launch; else two, and
 // scratch holds grain_scratch_bytes(L) bytes (8-byte aligned) of per-workgroup partials.

@@ -30,6 +30,8 @@ struct av1mi_ctx {
   size_t scene_scratch_bytes = 0;
   void *crop_scratch = nullptr;           // av1mi_crop_analyse: the partial row / column sums (grown on demand)
   size_t crop_scratch_bytes = 0;
+  void *telecine_scratch = nullptr;       // av1mi_telecine_analyse: the waves' partial sums (grown on demand)
+  size_t telecine_scratch_bytes = 0;
   void *grain_scratch = nullptr;          // av1mi_denoise_gather: the workgroups' partial records (grown on demand)
   size_t grain_scratch_bytes = 0;
   void *denoise_vectors = nullptr;        // av1mi_denoise_mc_gather without d_vectors: the blocks' vectors (grown on demand)
@@ -242,6 +244,7 @@ void av1mi_close(av1mi_ctx *ctx) {
   if (ctx->me_scratch) (void)hipFree(ctx->me_scratch);
   if (ctx->scene_scratch) (void)hipFree(ctx->scene_scratch);
   if (ctx->crop_scratch) (void)hipFree(ctx->crop_scratch);
+  if (ctx->telecine_scratch) (void)hipFree(ctx->telecine_scratch);
   if (ctx->grain_scratch) (void)hipFree(ctx->grain_scratch);
   if (ctx->denoise_vectors) (void)hipFree(ctx->denoise_vectors);
   if (ctx->grain_cov_scratch) (void)hipFree(ctx->grain_cov_scratch);
@@ -885,6 +888,36 @@ int av1mi_crop_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int
   A.luma = d_luma; A.scratch = ctx->crop_scratch; A.out = d_records;
   ProfScope ps(ctx, AV1MI_K_SCENE);
   HIP_TRY(ctx, av1mi::launch_crop_analyse(A, ctx->stream));
+  return AV1MI_OK;
+}
+
+int av1mi_telecine_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int true_width, int true_height, int frames, const void *d_luma,
+                           av1mi_telecine_record *d_records) {
+  BIND(ctx);
+  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return fail(ctx, AV1MI_E_INVAL, "av1mi_telecine_analyse: bit depth %d not supported (8, 10 or 12)", bit_depth);
+  if (width < 8 || height < 8 || (width & 7) || (height & 7) || width > 16384 || height > 16384)
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_telecine_analyse: the planes' size %dx%d must be a multiple of 8 (8 .. 16384)", width, height);
+  if (true_width < 1 || true_width > width || width - true_width >= 8 || true_height < 1 || true_height > height || height - true_height >= 8)
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_telecine_analyse: the true size %dx%d must lie within 7 samples below the planes' size %dx%d", true_width, true_height, width, height);
+  if (frames < 1 || frames > 65535) return fail(ctx, AV1MI_E_INVAL, "av1mi_telecine_analyse: frames %d out of range (1 .. 65535)", frames);
+  if (!d_luma || !d_records || ((uintptr_t)d_luma & 15) || ((uintptr_t)d_records & 7)) return fail(ctx, AV1MI_E_INVAL, "av1mi_telecine_analyse: null or misaligned device pointer (planes 16 bytes, records 8)");
+  if (int rc = grow(ctx, &ctx->telecine_scratch, &ctx->telecine_scratch_bytes, av1mi::telecine_layout(bit_depth, true_width, true_height, frames).bytes)) return rc;
+  av1mi::TelecineLaunch A;
+  A.bd = bit_depth; A.stride = width; A.rows = height; A.w = true_width; A.h = true_height; A.frames = frames;
+  A.luma = d_luma; A.scratch = ctx->telecine_scratch; A.out = d_records;
+  ProfScope ps(ctx, AV1MI_K_SCENE);
+  HIP_TRY(ctx, av1mi::launch_telecine_analyse(A, ctx->stream));
+  return AV1MI_OK;
+}
+
+int av1mi_telecine_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int segments,
+                          const void *const *d_table, void *const d_dst[3]) {
+  BIND(ctx);
+  if (!plane_w || !plane_h || !true_w || !true_h || !d_table || !d_dst || ((uintptr_t)d_table & 7)) return fail(ctx, AV1MI_E_INVAL, "av1mi_telecine_gather: null pointer or misaligned table");
+  av1mi::GatherPlanes L;
+  if (int rc = check_gather_planes(ctx, "av1mi_telecine_gather", 12, false, bit_depth, plane_w, plane_h, true_w, true_h, segments, d_table, d_dst, L)) return rc;
+  ProfScope ps(ctx, AV1MI_K_SCENE);
+  HIP_TRY(ctx, av1mi::launch_telecine_gather(L, ctx->stream));
   return AV1MI_OK;
 }
 

@@ -213,6 +213,8 @@ struct av1mi_gop {
   Store store[2];                              // the frame store (cfg.store_frames != 0)
   void *d_scene = nullptr, *h_records = nullptr;      // the analysis' scratch area (one store's) and its records, pinned
   hipEvent_t scene_done = nullptr;
+  void *d_telecine = nullptr, *h_telecine = nullptr;  // telecine: the field-match records' partials (one store's) and the records, pinned
+  hipEvent_t telecine_done = nullptr;                 // ... and the event behind them: its own, so the scene analysis and this never wait for each other's records
   long puts = 0;                               // av1mi_gop_store_put calls: the pinned buffers of slot puts % kSlots are handed out next
   hipEvent_t put_done[kSlots] = {};            // the copy that last read those pinned buffers
   bool put_pending[kSlots] = {};
@@ -246,6 +248,8 @@ int host_alloc(av1mi_gop *g, void **p, size_t bytes) {
 // THE place that says what depth is coded: the input side's, unless the config asks for the reduction
 int coded_depth(const av1mi_gop_config &c) { return c.coded_bit_depth ? c.coded_bit_depth : c.bit_depth; }
 bool reducing(const av1mi_gop *g) { return g->bd != g->cfg.bit_depth; }
+// the frames a store holds: store_frames, and in a session that weaves room for one context frame in front of a group and one behind it
+int store_capacity(const av1mi_gop_config &c) { return c.store_frames + (c.telecine ? 2 : 0); }
 
 enum Stage { kConvert, kChroma, kScale, kCrop };      // the input stages (the chain of "The source path"); kCrop stands where kScale would
 // Does stage k write plane p?  All do but chroma at equal depths, which passes the luma plane through
@@ -301,7 +305,8 @@ int slot_buffers(av1mi_gop *g, Slot &s) {
   }
   if (c.store_frames) {
     // (a session that deinterlaces or denoises keeps three pointers per segment and plane: the frames before, at and after the position)
-    const size_t entries = (size_t)S * 3 * (c.deinterlace || c.denoise ? 3 : 1);
+    // (a session that weaves two: the top and the bottom source)
+    const size_t entries = (size_t)S * 3 * (c.deinterlace || c.denoise ? 3 : c.telecine ? 2 : 1);
     // (at field rate a phase byte per segment rides behind the pointers, in the same copy)
     const size_t phases = c.deinterlace_fields ? (size_t)S : 0;
     G_TRY(host_alloc(g, &s.h_table, entries * sizeof(void *) + phases));
@@ -447,6 +452,8 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
   if (c->quality_stats && ((c->visible_width ? c->visible_width : c->width) < 16 || (c->visible_height ? c->visible_height : c->height) < 16))
     return WHY("quality_stats needs a true luma size of at least 16x16");
   if (c->store_frames < 0 || c->store_frames > 65535) return WHY("store_frames %d out of range (0 = none, up to 65535)", c->store_frames);
+  if (c->telecine != 0 && c->telecine != 1) return WHY("telecine %d unknown (0 none, 1 inverse telecine: fields woven, duplicates dropped by the caller's plan)", c->telecine);
+  if (c->telecine && c->input_format != AV1MI_INPUT_PLANAR) return WHY("telecine %d needs input_format 0 (planar), not %d: the fields are woven from planar frames in the store", c->telecine, c->input_format);
   if (c->store_frames && c->input_format != AV1MI_INPUT_PLANAR) return WHY("a frame store (store_frames %d) needs input_format 0 (planar), not %d", c->store_frames, c->input_format);
   if (c->deinterlace < 0 || c->deinterlace > 2) return WHY("deinterlace %d unknown (0 none, 1 top field first, 2 bottom field first)", c->deinterlace);
   if (c->deinterlace && !c->store_frames) return WHY("deinterlace %d needs a frame store (store_frames > 0): the filter reads the frames before and after each frame", c->deinterlace);
@@ -455,6 +462,9 @@ const char *config_error(const av1mi_gop_config *c, char (&buf)[512]) {
   if (c->denoise < 0 || c->denoise > 16) return WHY("denoise %d out of range (0 none, 1 .. 16 the strength)", c->denoise);
   if (c->denoise && !c->store_frames) return WHY("denoise %d needs a frame store (store_frames > 0): the filter reads the frames before and after each frame", c->denoise);
   if (c->denoise && c->deinterlace) return WHY("denoise %d together with deinterlace %d is not built: the chain of the two needs a third copy of a group", c->denoise, c->deinterlace);
+  if (c->telecine && !c->store_frames) return WHY("telecine %d needs a frame store (store_frames > 0): a frame is woven from the fields of two stored frames", c->telecine);
+  if (c->telecine && c->deinterlace) return WHY("telecine %d together with deinterlace %d is not built: a source is woven back to film or deinterlaced, not both", c->telecine, c->deinterlace);
+  if (c->telecine && c->denoise) return WHY("telecine %d together with denoise %d is not built: the denoiser's neighbours would be video frames, not the woven film frames", c->telecine, c->denoise);
   if (c->denoise && c->source_bit_depth == 12) return WHY("denoise %d takes fed samples of 8 or 10 bits, not source_bit_depth 12", c->denoise);
   if (c->denoise_range != 0 && c->denoise_range != 4 && c->denoise_range != 8) return WHY("denoise_range %d unknown (0 none, 4 or 8 the block search's range)", c->denoise_range);
   if (c->denoise_range && !c->denoise) return WHY("denoise_range %d needs denoise (1 .. 16): it is the range of the denoiser's block search", c->denoise_range);
@@ -549,7 +559,7 @@ int setup(av1mi_gop *g) {
   if (c.store_frames) {
     for (Store &st : g->store) {
       for (int p = 0; p < 3; p++)
-        if (g->layout.plane[p].frame_bytes) G_TRY(dev_alloc(g, &st.d[p], g->layout.plane[p].frame_bytes * (size_t)c.store_frames));
+        if (g->layout.plane[p].frame_bytes) G_TRY(dev_alloc(g, &st.d[p], g->layout.plane[p].frame_bytes * (size_t)store_capacity(c)));
       G_HIP(hipEventCreateWithFlags(&st.filled, hipEventDisableTiming));
       G_HIP(hipEventCreateWithFlags(&st.read_done, hipEventDisableTiming));
     }
@@ -557,6 +567,11 @@ int setup(av1mi_gop *g) {
     G_TRY(host_alloc(g, &g->h_records, (size_t)c.store_frames * sizeof(av1mi_scene_record)));
     G_HIP(hipEventCreateWithFlags(&g->scene_done, hipEventDisableTiming));
     for (hipEvent_t &e : g->put_done) G_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (c.telecine) {
+      G_TRY(dev_alloc(g, &g->d_telecine, av1mi::telecine_layout(g->layout.bit_depth, g->layout.true_width, g->layout.true_height, store_capacity(c)).bytes));
+      G_TRY(host_alloc(g, &g->h_telecine, (size_t)store_capacity(c) * sizeof(av1mi_telecine_record)));
+      G_HIP(hipEventCreateWithFlags(&g->telecine_done, hipEventDisableTiming));
+    }
   }
   if (c.tone_map) {
     av1mi_tone_tables tables;
@@ -628,7 +643,7 @@ void av1mi_gop_close(av1mi_gop *g) {
   for (Slot &s : g->slot)
     for (hipEvent_t e : { s.uploaded, s.kernel_done, s.filters_done, s.downloaded, s.ent_done, s.quality_done, s.grain_done, s.search_down })
       if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : { g->store[0].filled, g->store[0].read_done, g->store[1].filled, g->store[1].read_done, g->scene_done, g->put_done[0], g->put_done[1], g->put_done[2] })
+  for (hipEvent_t e : { g->store[0].filled, g->store[0].read_done, g->store[1].filled, g->store[1].read_done, g->scene_done, g->telecine_done, g->put_done[0], g->put_done[1], g->put_done[2] })
     if (e) (void)hipEventDestroy(e);
   for (void *p : g->dev_allocs) (void)hipFree(p);
   for (void *p : g->host_allocs) (void)hipHostFree(p);
@@ -655,7 +670,10 @@ int av1mi_gop_max_in_flight(void) { return kSlots; }
 // A batch from the frame store (index != null: the store position per segment, -1 = a flat slot) is gathered into d_in on the main
 // stream instead of being uploaded: the stream itself orders the gather behind the slot's previous readers, store.filled orders it
 // behind the puts, and store.read_done lets the next put into that store wait for it.
-static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const void *src[3], int store = 0, const int32_t *index = nullptr) {
+// A woven batch (bottom != null, av1mi_gop_submit_woven): index[] holds the top source's position, bottom[] the bottom source's; the table
+// holds the two pointers and k_telecine_gather stands where k_frames_gather stands.  Same events.
+static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const void *src[3], int store = 0, const int32_t *index = nullptr,
+                       const int32_t *bottom = nullptr) {
   hipStream_t main = av1mi::ctx_stream(g->ctx);
   const av1mi_gop_config &c = g->cfg;
   const av1mi_source_layout &Y = g->layout;
@@ -668,14 +686,17 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
     const void **table = (const void **)s.h_table;
     const size_t frame_bytes[3] = { Y.plane[0].frame_bytes, Y.plane[1].frame_bytes, Y.plane[2].frame_bytes };
     auto frame = [&](int p, int pos) { return (const void *)((const char *)st.d[p] + frame_bytes[p] * (size_t)pos); };
-    const size_t table_bytes = (size_t)S * 3 * (three ? 3 : 1) * sizeof(void *);
+    const size_t table_bytes = (size_t)S * 3 * (three ? 3 : bottom ? 2 : 1) * sizeof(void *);
     uint8_t *phase = (uint8_t *)s.h_table + table_bytes;      // (field rate only: the slot's table was allocated with S bytes more)
     for (int sg = 0; sg < S; sg++) {
       const int pos = fields && index[sg] >= 0 ? index[sg] >> 1 : index[sg];
       if (fields) phase[sg] = index[sg] >= 0 ? (uint8_t)(index[sg] & 1) : 0;
       for (int p = 0; p < 3; p++) {
         const bool flat = pos < 0 || !frame_bytes[p];
-        if (!three) table[sg * 3 + p] = flat ? nullptr : frame(p, pos);
+        if (bottom) {
+          table[(sg * 3 + p) * 2] = flat ? nullptr : frame(p, pos);
+          table[(sg * 3 + p) * 2 + 1] = flat ? nullptr : frame(p, bottom[sg]);
+        } else if (!three) table[sg * 3 + p] = flat ? nullptr : frame(p, pos);
         else {      // P, C, N follow the POSITION in the store's run, clamped at its ends
           const void **e = table + (sg * 3 + p) * 3;
           e[0] = flat ? nullptr : frame(p, pos > 0 ? pos - 1 : 0);
@@ -709,6 +730,10 @@ static int feed_source(av1mi_gop *g, Slot &s, const void *const *dev_src, const 
         fed_geometry(g, &s, L);
         L.strength = c.denoise; L.scratch = g->d_grain_scratch; L.records = (av1mi_grain_record *)s.h_grain;
         G_HIP(av1mi::launch_denoise_gather(L, main));
+      } else if (bottom) {
+        av1mi::GatherPlanes L;
+        fed_geometry(g, &s, L);
+        G_HIP(av1mi::launch_telecine_gather(L, main));
       } else G_HIP(av1mi::launch_frames_gather(frame_bytes, S, (const void *const *)s.d_table, s.d_in, main));
       if (c.grain_cov) {           // one more launch behind either denoising gather: C from the table, out from the fed buffers
         av1mi::GrainCovLaunch L;
@@ -1081,7 +1106,7 @@ static int start_coder(av1mi_gop *g, Slot &s) {
 }
 
 // one batch through the stages above; dev_src as for feed_source
-static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src, int store = 0, const int32_t *index = nullptr) {
+static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src, int store = 0, const int32_t *index = nullptr, const int32_t *bottom = nullptr) {
   if (g->submitted - g->collected >= kSlots) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "%d batches in flight: collect first", (int)kSlots);
   if (frame_type < -1 || frame_type > 1) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "frame_type %d", frame_type);
   if (frame_type < 0) frame_type = g->gop_pos == 0 ? 0 : 1;
@@ -1093,7 +1118,7 @@ static int submit_batch(av1mi_gop *g, int frame_type, const void *const *dev_src
   if (s.q == g->cfg.base_q_idx) s.params = g->params[frame_type];
   else frame_params(s.q, g->bd, frame_type, &s.params);
   const void *src[3];
-  G_TRY(feed_source(g, s, dev_src, src, store, index));
+  G_TRY(feed_source(g, s, dev_src, src, store, index, bottom));
   if (s.ent_pending) G_HIP(hipStreamWaitEvent(av1mi::ctx_stream(g->ctx), s.ent_done, 0));      // the GPU coder of the slot's previous batch still reads its symbols
   G_TRY(code_blocks(g, s, frame_type, src));
   // symbols -> pinned host memory, beside the filters.  Not when the GPU codes the tiles (gpu_entropy == 1): the host then needs
@@ -1152,8 +1177,8 @@ int av1mi_gop_submit(av1mi_gop *g, int frame_type) {
 
 int av1mi_gop_store_put(av1mi_gop *g, int store, int first, int count) {
   if (!g) return AV1MI_E_INVAL;
-  const int N = g->cfg.store_frames;
-  if (!N) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "the session has no frame store (store_frames 0)");
+  const int N = store_capacity(g->cfg);
+  if (!g->cfg.store_frames) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "the session has no frame store (store_frames 0)");
   if (store < 0 || store > 1 || count < 1 || count > g->cfg.segments || first < 0 || first > N - count)
     return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "store_put: store %d, frames %d .. %d + %d of %d (at most %d at a time)", store, first, first, count, N, g->cfg.segments);
   if (!g->acquired) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "store_put without av1mi_gop_acquire_input");
@@ -1198,12 +1223,42 @@ int av1mi_gop_submit_stored(av1mi_gop *g, int store, const int32_t *index, int f
   if (frame_type != 0 && frame_type != 1) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: frame_type %d (0 key or 1 inter: the layout is the caller's)", frame_type);
   const int per = g->cfg.deinterlace_fields ? 2 : 1;      // output positions per source frame
   for (int s = 0; s < g->cfg.segments; s++)
-    if (index[s] < -1 || index[s] >= per * g->cfg.store_frames)
-      return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: index[%d] = %d outside the store of %d frames%s", s, (int)index[s], g->cfg.store_frames, per == 2 ? " (two output positions each)" : "");
+    if (index[s] < -1 || index[s] >= per * store_capacity(g->cfg))      // (a session that weaves: its context positions included)
+      return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: index[%d] = %d outside the store of %d frames%s", s, (int)index[s], store_capacity(g->cfg), per == 2 ? " (two output positions each)" : "");
   for (int s = 0; (g->cfg.deinterlace || g->cfg.denoise) && s < g->cfg.segments; s++)
     if (index[s] >= per * g->store[store].run)
       return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_stored: index[%d] = %d beyond the store's run of %d frames%s (the filter reads the neighbours inside it)", s, (int)index[s], g->store[store].run, per == 2 ? " (two output positions each)" : "");
   return submit_batch(g, frame_type, nullptr, store, index);
+}
+
+int av1mi_gop_store_telecine(av1mi_gop *g, int store, int frames, av1mi_telecine_record *out) {
+  if (!g) return AV1MI_E_INVAL;
+  if (!g->cfg.telecine) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "the session does not weave (telecine 0)");
+  if (store < 0 || store > 1 || frames < 1 || frames > store_capacity(g->cfg) || frames > g->store[store].run || !out)
+    return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "store_telecine: store %d, %d frames of a run of %d (the store holds %d)", store, frames, store >= 0 && store <= 1 ? g->store[store].run : 0, store_capacity(g->cfg));
+  G_HIP(hipSetDevice(av1mi::ctx_device(g->ctx)));
+  av1mi::TelecineLaunch L;
+  L.bd = g->layout.bit_depth; L.stride = g->layout.width; L.rows = g->layout.height; L.w = g->layout.true_width; L.h = g->layout.true_height; L.frames = frames;
+  L.luma = g->store[store].d[0]; L.scratch = g->d_telecine; L.out = (av1mi_telecine_record *)g->h_telecine;
+  // on the upload stream, behind the puts; the summing launch writes the records into pinned memory
+  G_HIP(av1mi::launch_telecine_analyse(L, g->up));
+  G_HIP(hipEventRecord(g->telecine_done, g->up));
+  G_HIP(hipEventSynchronize(g->telecine_done));
+  memcpy(out, g->h_telecine, (size_t)frames * sizeof(av1mi_telecine_record));
+  return AV1MI_OK;
+}
+
+int av1mi_gop_submit_woven(av1mi_gop *g, int store, const int32_t *top, const int32_t *bottom, int frame_type) {
+  if (!g) return AV1MI_E_INVAL;
+  if (!g->cfg.telecine) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "the session does not weave (telecine 0)");
+  if (store < 0 || store > 1 || !top || !bottom || !g->store[store].has_fill) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_woven: store %d holds nothing, or no positions", store);
+  if (frame_type != 0 && frame_type != 1) return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_woven: frame_type %d (0 key or 1 inter: the layout is the caller's)", frame_type);
+  for (int s = 0; s < g->cfg.segments; s++) {
+    if (top[s] == -1) continue;      // a flat slot: bottom[s] is not read
+    if (top[s] < 0 || bottom[s] < 0 || top[s] >= g->store[store].run || bottom[s] >= g->store[store].run)
+      return av1mi::ctx_fail(g->ctx, AV1MI_E_INVAL, "submit_woven: segment %d weaves positions %d / %d, outside the store's run of %d frames", s, (int)top[s], (int)bottom[s], g->store[store].run);
+  }
+  return submit_batch(g, frame_type, nullptr, store, top, bottom);
 }
 
 int av1mi_gop_submit_device(av1mi_gop *g, const void *d_y, const void *d_u, const void *d_v, int frame_type) {

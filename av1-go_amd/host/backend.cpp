@@ -13,6 +13,10 @@
 // -av1mi_scenecut asks for it: the session's gather deinterlaces every frame on its way from the store (av1mi_gop_config.deinterlace).
 // With -av1mi_deinterlace_rate field it makes two output frames of every stored frame: the groups, their layouts and the stored batches'
 // indices then count OUTPUT frames, the reader and the store source frames (SessionPlan::out_per_src; fieldrate.hpp).
+// With -av1mi_ivtc 1 a group of segments x gop OUTPUT frames is segments x gop x 5 / 4 source frames (fieldrate.hpp's ratio): they are put into
+// the store with one context frame on either side, the session gives their field-match records (av1mi_gop_store_telecine), the plan
+// (telecineplan.hpp) drops one frame of every five and names the two frames each kept one is woven from, and the batches are submitted as
+// woven pairs (av1mi_gop_submit_woven): run_groups_telecine.
 // With -av1mi_scenecut the GOPs of a group do not start every `gop` frames but where the scene analysis finds cuts: the group's frames go
 // into the session's frame store in file order (av1mi_gop_store_put), are analysed there (av1mi_gop_store_analyse), the planner
 // (sceneplan.hpp) lays the GOPs out, and every batch is gathered from the store (av1mi_gop_submit_stored).  The session has two stores:
@@ -41,6 +45,7 @@
 #include "fieldrate.hpp"
 #include "ratecontrol.hpp"
 #include "sceneplan.hpp"
+#include "telecineplan.hpp"
 #include "y4m.hpp"
 
 namespace av1mi_host {
@@ -72,6 +77,7 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
   // the output: -av1mi_deinterlace_rate field makes two frames of each source frame, at twice the rate; G counts OUTPUT frames
   const JobOutput output = JobOutputOf(job, src.interlace, src.fps_n, src.fps_d, src.known_frames);
   plan->out_per_src = output.per_source; plan->fps_n = output.fps_n; plan->fps_d = output.fps_d;
+  if (job.ivtc && (G & 3)) return refuse("with -av1mi_ivtc -g counts output frames, four per five source frames, and must be a multiple of 4: not -g " + std::to_string(G));
   if (output.per_source == 2 && (G & 1)) return refuse("with -av1mi_deinterlace_rate field -g counts output frames, two per source frame, and must be even: not -g " + std::to_string(G));
   if (output.frames >= 0) S = (int)std::max<long>(1, std::min<long>(S, (output.frames + G - 1) / G));      // no more segments than the file has GOPs
   av1mi_gop_config &cfg = plan->cfg;
@@ -104,6 +110,9 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
   }
   cfg.deinterlace = dei;
   cfg.deinterlace_fields = output.per_source == 2;
+  // -av1mi_ivtc: whatever the header's I parameter says; the session weaves what the plan asks for (telecineplan.hpp)
+  plan->telecine = job.ivtc != 0;
+  cfg.telecine = plan->telecine ? 1 : 0;
   // -av1mi_scenecut, or a job that deinterlaces: the frame store holds one group (the deinterlacer's run)
   // -av1mi_denoise: the same store, the denoiser in the gather; -av1mi_film_grain (1 unless told otherwise): parameters in every frame header
   cfg.denoise = job.denoise;
@@ -130,8 +139,8 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
   }
   plan->grainy = job.denoise > 0 && job.film_grain != 0;
   plan->analysed = job.scenecut > 0;
-  plan->stored = plan->analysed || dei != 0 || job.denoise > 0;
-  if (plan->stored) cfg.store_frames = S * G / output.per_source;      // SOURCE frames: a group of S G output frames
+  plan->stored = plan->analysed || dei != 0 || job.denoise > 0 || plan->telecine;
+  if (plan->stored) cfg.store_frames = (int)((long)S * G * output.den / output.num);      // SOURCE frames: a group of S G output frames (the session adds the context frames' room)
   // What the reader threads deliver, one segment's share of the pinned buffers: frames of the coded size (the source's edge replicated
   // into the padding) or, when the GPU scales, of the source size rounded up to 8; no chroma planes for a grey source.  (A config the
   // layout refuses, av1mi_gop_open refuses, with the reason.)
@@ -152,6 +161,7 @@ std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, c
   if (tags.lr) k += snprintf(line + k, sizeof(line) - (size_t)k, " lr:%d/%d", f.lr_filtered, f.lr_units);
   if (tags.cdef) k += snprintf(line + k, sizeof(line) - (size_t)k, " cdef:%d/%d", f.cdef_moved, f.cdef_sbs);
   if (tags.lf) k += snprintf(line + k, sizeof(line) - (size_t)k, " lf:%d/%d", f.lf_y, f.lf_uv);
+  if (tags.ivtc) k += snprintf(line + k, sizeof(line) - (size_t)k, " ivtc:%ld/%ld", f.ivtc_top, f.ivtc_bottom);
   if (cut) k += snprintf(line + k, sizeof(line) - (size_t)k, " cut:1");
   return std::string(line, (size_t)k);
 }
@@ -193,6 +203,12 @@ struct Run {
   int cur_store = 0;
   long next_frames = -1, next_put = 0;      // stored: frames of the group that goes into the other store (-1 = not asked yet), and those already put
   av1mi_gop_frame oldest;      // the batch collected last, until it is assembled
+  // -av1mi_ivtc: the plan of the group in the current store (output k of the group is woven from store positions ivtc_top[k] / ivtc_bottom[k]),
+  // and the file-wide number of the source frame at store position 0
+  std::vector<int32_t> ivtc_top, ivtc_bottom;
+  long ivtc_base = 0;
+  int put_offset = 0;          // the store position of frame 0 of the group put_chunk puts (-av1mi_ivtc: 1 behind a context frame)
+  std::vector<unsigned char> kept[3];      // -av1mi_ivtc: the last source frame of the group in flight, the next group's context
   std::string stats;           // the stats file's lines, in presentation order
   av1mi::quality::Summary summary;
   long long total_bytes = 0;
@@ -314,9 +330,28 @@ struct Run {
     int code = n > 0 ? start_reads(frame, &reads) : 0;
     if (code || (beside && (code = beside())) || n <= 0) return code;
     if (!reads.join()) return truncated();
-    if (av1mi_gop_store_put(gop, store, (int)*put, n) != AV1MI_OK) return lib_error("av1mi_gop_store_put");
+    if (av1mi_gop_store_put(gop, store, put_offset + (int)*put, n) != AV1MI_OK) return lib_error("av1mi_gop_store_put");
     *put += n;
     return 0;
+  }
+  // -av1mi_ivtc's context frames, one frame each.  put_one: frame i of the group the reader has prepared -> position pos of a store.
+  // keep_frame: frame i of the prepared group -> host memory (before the reader moves on to the next group); put_kept: that frame ->
+  // position pos of a store.
+  int put_one(int store, int pos, long i) {
+    Reads reads;
+    if (const int code = start_reads(std::vector<int32_t>(1, (int32_t)i), &reads)) return code;
+    if (!reads.join()) return truncated();
+    return av1mi_gop_store_put(gop, store, pos, 1) == AV1MI_OK ? 0 : lib_error("av1mi_gop_store_put");
+  }
+  int keep_frame(long i) {
+    for (int p = 0; p < 3; p++) kept[p].resize(plan.fed.plane[p].frame_bytes);
+    return y.read(i, plan.fed.width, plan.fed.height, kept[0].data(), kept[1].data(), kept[2].data()) ? 0 : truncated();
+  }
+  int put_kept(int store, int pos) {
+    void *plane[3];
+    if (av1mi_gop_acquire_input(gop, &plane[0], &plane[1], &plane[2]) != AV1MI_OK) return lib_error("av1mi_gop_acquire_input");
+    for (int p = 0; p < 3; p++) if (!kept[p].empty()) memcpy(plane[p], kept[p].data(), kept[p].size());
+    return av1mi_gop_store_put(gop, store, pos, 1) == AV1MI_OK ? 0 : lib_error("av1mi_gop_store_put");
   }
   int put_all(int store, long frames, long *put) {
     for (int code; *put < frames;) if ((code = put_chunk(store, frames, put))) return code;
@@ -354,6 +389,12 @@ struct Run {
       if (av1mi_gop_set_base_q_idx(gop, q) != AV1MI_OK) return lib_error("av1mi_gop_set_base_q_idx");
     }
     if (!plan.stored) return av1mi_gop_submit(gop, t == 0 ? 0 : 1) == AV1MI_OK ? 0 : lib_error("av1mi_gop_submit");
+    if (plan.telecine) {      // the group's output frames -> the two store positions the plan weaves each from
+      std::vector<int32_t> top = group.slots(t), bottom = top;
+      for (size_t s = 0; s < top.size(); s++)
+        if (top[s] >= 0) { bottom[s] = ivtc_bottom[(size_t)top[s]]; top[s] = ivtc_top[(size_t)top[s]]; }
+      return av1mi_gop_submit_woven(gop, cur_store, top.data(), bottom.data(), t == 0 ? 0 : 1) == AV1MI_OK ? 0 : lib_error("av1mi_gop_submit_woven");
+    }
     return av1mi_gop_submit_stored(gop, cur_store, group.slots(t).data(), t == 0 ? 0 : 1) == AV1MI_OK ? 0 : lib_error("av1mi_gop_submit_stored");
   }
   int collect() { return av1mi_gop_collect(gop, &oldest) == AV1MI_OK ? 0 : lib_error("av1mi_gop_collect"); }
@@ -395,6 +436,7 @@ struct Run {
         if (!oldest.lf_levels) return fail(2, "the session returned no deblocking levels");
         f.lf_y = oldest.lf_levels[(size_t)s * 4]; f.lf_uv = oldest.lf_levels[(size_t)s * 4 + 2];
       }
+      if (plan.telecine) { const int32_t k = group.index(s, t); f.ivtc_top = ivtc_base + ivtc_top[(size_t)k]; f.ivtc_bottom = ivtc_base + ivtc_bottom[(size_t)k]; }
       if (plan.measure) {
         if (!oldest.quality) return fail(2, "the session returned no quality records");
         memcpy(f.q, oldest.quality + (size_t)s * 3, sizeof(f.q));
@@ -435,7 +477,7 @@ struct Run {
   int write_group(const Group &group, const GroupOut &out) {
     StatsTags tags;
     tags.depth_from = plan.reduced_from; tags.depth_to = plan.coded_bd;
-    tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0; tags.ar = job.grain_lag > 0; tags.lr = job.lr_search != 0; tags.cdef = job.cdef_search != 0; tags.lf = job.lf_search != 0;
+    tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0; tags.ar = job.grain_lag > 0; tags.lr = job.lr_search != 0; tags.cdef = job.cdef_search != 0; tags.lf = job.lf_search != 0; tags.ivtc = plan.telecine;
     for (int s = 0; s < S; s++)
       for (size_t t = 0; t < out[(size_t)s].size(); t++) {
         const FrameOut &f = out[(size_t)s][t];
@@ -451,7 +493,48 @@ struct Run {
   // The loop over GROUPS of S GOPs: a file is read in place, a stream one group ahead of the encoder (y4m.hpp).  Stored: the group's
   // frames are in the current store before its batches run — the first group's are put here, nothing runs beside it; every later one was
   // put into the other store while the group before ran (code_group) — and the stores swap per group.
+  // -av1mi_ivtc: a group of S G output frames is S G 5 / 4 source frames.  They go into the store between the last source frame of the group
+  // before and the first of the group after (context: analysed and matched against, never output), the records are taken on the GPU, the
+  // plan says which frame of every five is dropped and which two frames each kept one is woven from, and the batches are submitted as
+  // woven pairs.  Every source frame is read ONCE, in order, so a pipe or FIFO feeds the job like a file: the group's last frame is kept on
+  // the host for the next group, and the next group's first frame is read one ahead.  The next group is put beside this group's batches
+  // like every stored job's (code_group).
+  int run_groups_telecine() {
+    const long per_group = (long)S * G * kTelecineCycle / (kTelecineCycle - 1);      // source frames
+    int code;
+    long have = y.prepare(0, per_group, err), put = 0;
+    if (have < 0) return 1;
+    if ((code = put_all(cur_store, have, &put))) return code;      // the first group: from position 0, nothing in front of it
+    put_offset = 1;                                                  // every later group lies behind its context frame
+    for (long k = 0, front = 0; have > 0; k++, g0 += S, front = 1) {
+      // the group's last frame, kept for the next group before the reader moves on; then the next group is prepared (a stream: it has
+      // been read ahead) and its first frame is this group's context behind
+      if ((code = keep_frame(have - 1))) return code;
+      if ((next_frames = y.prepare((k + 1) * per_group, per_group, err)) < 0) return 1;
+      next_put = 0;
+      const long back = next_frames > 0 ? 1 : 0, run = front + have + back;
+      if (back && (code = put_one(cur_store, (int)(front + have), 0))) return code;
+      std::vector<av1mi_telecine_record> rec((size_t)run);
+      if (av1mi_gop_store_telecine(gop, cur_store, (int)run, rec.data()) != AV1MI_OK) return lib_error("av1mi_gop_store_telecine");
+      ivtc_top.assign((size_t)have, 0); ivtc_bottom.assign((size_t)have, 0);
+      const int outs = PlanTelecine(rec.data(), (int)run, (int)front, (int)back, ivtc_top.data(), ivtc_bottom.data());
+      if (outs < 0) return fail(2, "the telecine plan refused its arguments");
+      ivtc_base = k * per_group - front;
+      total_frames += outs;
+      Group group;
+      if ((code = lay_out(outs, &group))) return code;
+      // the next group into the other store: its context in front now, its own frames chunk by chunk beside this group's batches
+      if (back && (code = put_kept(cur_store ^ 1, 0))) return code;
+      GroupOut out((size_t)S);
+      if ((code = code_group(group, &out)) || (code = write_group(group, out))) return code;
+      cur_store ^= 1;
+      have = next_frames;
+    }
+    return 0;
+  }
+
   int run_groups() {
+    if (plan.telecine) return run_groups_telecine();
     for (int code;; g0 += S) {
       long have = next_frames;
       const int F = plan.out_per_src;      // g0 and G count OUTPUT frames; the reader and the store count source frames (G is even where F is 2)

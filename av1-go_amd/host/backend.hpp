@@ -25,6 +25,7 @@ struct SessionPlan {
   // packed: the frames cross PCIe at 10 bits per sample; stored: the job runs through the frame store; analysed: its groups are laid out
   // on scene cuts; grainy: film grain parameters in every frame header; measure: the session returns quality records
   bool packed, stored, analysed, grainy, measure;
+  bool telecine;                // -av1mi_ivtc: the session weaves (cfg.telecine); the store's groups are planned by telecineplan.hpp
   int coded_bd;                 // the depth of the stream (-av1mi_depth): what the sequence header, the sink, the rate controller and the figures take
   int reduced_from;             // the source's depth where the job reduces it (10 or 12), else 0
   // the job's OUTPUT (fieldrate.hpp JobOutputOf): output frames per source frame (2 = field rate: -g, the groups' layouts and the
@@ -39,7 +40,7 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
 
 // one coded frame of a group: its temporal unit and what the stats file says about it (q: the session's records where the job measures;
 // grain: the luma scaling at mid grey where it denoises)
-struct FrameOut { std::vector<uint8_t> unit; av1mi_quality q[3]; int base_q_idx; int grain; int ar; int lr_filtered, lr_units; int cdef_moved, cdef_sbs; int lf_y, lf_uv; };      // ar: the ar_coeff_lag coded (-av1mi_grain_lag)
+struct FrameOut { std::vector<uint8_t> unit; av1mi_quality q[3]; int base_q_idx; int grain; int ar; int lr_filtered, lr_units; int cdef_moved, cdef_sbs; int lf_y, lf_uv; long ivtc_top, ivtc_bottom; };      // ar: the ar_coeff_lag coded (-av1mi_grain_lag)
 // the layout of a group of frames over the session's segments: GOP s holds frames start[s] .. start[s] + len[s] - 1 of the group; cut
 // (analysed jobs) flags the frames the scene analysis found.  At field rate the frames of a group are OUTPUT frames (two per source frame).
 struct Group {
@@ -53,7 +54,7 @@ struct Group {
 };
 // The stats file: the line of frame n in presentation order, and the summary line.  tags: what a line says beyond the
 // figures — the window, the colour record and the depth reduction " depth:10>8" (frame 0 only; w == 0 / null / depth_from 0 = none), q: (a job with a target), grain: (a job that denoises)
-struct StatsTags { CropRect win; const av1mi_colour *colour = nullptr; int depth_from = 0, depth_to = 0; bool q = false, grain = false, ar = false, lr = false, cdef = false, lf = false; };
+struct StatsTags { CropRect win; const av1mi_colour *colour = nullptr; int depth_from = 0, depth_to = 0; bool q = false, grain = false, ar = false, lr = false, cdef = false, lf = false, ivtc = false; };      // ivtc: " ivtc:<top source>/<bottom source>", file-wide source frame numbers
 std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, const StatsTags &tags, bool cut);
 std::string StatsSummaryLine(const av1mi::quality::Summary &sum, long long bytes, int bit_depth);
 

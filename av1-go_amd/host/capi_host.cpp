@@ -147,6 +147,30 @@ int av1mi_host_job_output(const char *joined, int interlace, int fps_n, int fps_
   out[0] = o.per_source; out[1] = o.fps_n; out[2] = o.fps_d; out[3] = o.frames;
   return 0;
 }
+// the same with the ratio: out = { output frames per source frame, fps_n, fps_d, frames, num, den } (num output frames per den source frames)
+int av1mi_host_job_output_ratio(const char *joined, int interlace, int fps_n, int fps_d, long long frames, long long *out, char *err, int cap) {
+  const std::vector<std::string> a = split_lines(joined);
+  BackendJob job; std::string e;
+  const bool ok = ParseBackendJob(a, &job, &e);
+  strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
+  if (!ok) return -1;
+  const JobOutput o = JobOutputOf(job, interlace, fps_n, fps_d, (long)frames);
+  out[0] = o.per_source; out[1] = o.fps_n; out[2] = o.fps_d; out[3] = o.frames; out[4] = o.num; out[5] = o.den;
+  return 0;
+}
+// ParseBackendJob's view of -av1mi_ivtc for an argv joined with '\n': BackendJob::ivtc (0, 1), or -1 with the text in err
+int av1mi_host_parse_ivtc_option(const char *joined, char *err, int cap) {
+  const std::vector<std::string> a = split_lines(joined);
+  BackendJob job; std::string e;
+  const bool ok = ParseBackendJob(a, &job, &e);
+  strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
+  return ok ? job.ivtc : -1;
+}
+// PlanTelecine (telecineplan.hpp): the woven outputs of a run of `frames` records with `front` / `back` context frames; the number of
+// outputs, or -1
+int av1mi_plan_telecine(const av1mi_telecine_record *rec, int frames, int front, int back, int32_t *top, int32_t *bottom) {
+  return PlanTelecine(rec, frames, front, back, top, bottom);
+}
 // FieldRateCuts (fieldrate.hpp): n source frames' cut flags -> 2 n output frames'
 void av1mi_host_field_rate_cuts(const uint8_t *cut, int n, uint8_t *out) { FieldRateCuts(cut, n, out); }
 // ScaleTarget (transcode.hpp): the size a filter chain yields on a source; 0, or -1 for a chain with an unsupported filter

@@ -312,6 +312,10 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
       if (v == "frame") job->deint_rate = 0; else if (v == "field") job->deint_rate = 1;
       else { if (err) *err = "Invalid argument: -av1mi_deinterlace_rate takes frame or field, not " + v; return false; }
     }
+    else if (args[i] == "-av1mi_ivtc") {
+      if (args[i + 1] != "0" && args[i + 1] != "1") { if (err) *err = "Invalid argument: -av1mi_ivtc takes 0 or 1, not " + args[i + 1]; return false; }
+      job->ivtc = args[i + 1] == "1";
+    }
     else if (args[i] == "-av1mi_denoise") {
       if (!plain_int(args[i + 1], &job->denoise) || job->denoise > 16) { if (err) *err = "Invalid argument: -av1mi_denoise takes a strength 1 .. 16 (0 = off), not " + args[i + 1]; return false; }
     }
@@ -443,6 +447,16 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
   if (job->deint_rate && job->deinterlace && job->gop >= 1 && (job->gop & 1)) {
     if (err) *err = "Invalid argument: with -av1mi_deinterlace_rate field -g counts output frames, two per source frame, and must be even: not -g " + std::to_string(job->gop);
     return false;
+  }
+  if (job->ivtc) {
+    if (job->deinterlace) { if (err) *err = "Invalid argument: -av1mi_ivtc weaves the film frames of a telecined source back together, -av1mi_deinterlace (or a deinterlacer in the chain) filters them: give one"; return false; }
+    if (job->denoise) { if (err) *err = "Invalid argument: -av1mi_ivtc together with -av1mi_denoise is not built: the denoiser's neighbours would be video frames, not the woven film frames"; return false; }
+    if (job->pack10) { if (err) *err = "Invalid argument: -av1mi_ivtc keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
+    if (job->scenecut) { if (err) *err = "Invalid argument: -av1mi_ivtc together with -av1mi_scenecut is not built: the cuts of the source frames would have to be mapped through the dropped frames"; return false; }
+    if (job->gop >= 1 && (job->gop & 3)) {
+      if (err) *err = "Invalid argument: with -av1mi_ivtc -g counts output frames, four per five source frames, and must be a multiple of 4: not -g " + std::to_string(job->gop);
+      return false;
+    }
   }
   if ((job->crop_mode || (job->have_vf && job->vf.find("crop=") != std::string::npos)) && job->pack10) { if (err) *err = "Invalid argument: a crop window is cut from planar planes on the GPU: not together with -av1mi_pack10 1"; return false; }
   if (job->crop_mode == 1) {      // (a regular file whose frames cannot be addressed is refused when it is opened: backend.cpp)

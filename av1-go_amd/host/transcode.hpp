@@ -88,14 +88,21 @@ struct BackendJob {
                            // (av1mi_plan_gops): key frames land on the cuts, GOPs are min_gop .. 3/2 gop frames long.  Not with -av1mi_pack10 1
   int deinterlace = 0;     // -av1mi_deinterlace off | auto | tff | bff (0 .. 3).  off (default): every source is coded as its frames are.  auto: a source whose
                            // Y4M header says It / Ib is deinterlaced on the GPU with that parity (include/av1mi.h "deinterlacing": same-rate, one
-                           // frame per frame unless -av1mi_deinterlace_rate field), a progressive one is coded as ever, Im is refused (inverse
-                           // telecine is not built).  tff / bff force a parity, for sources whose header lies.  A chain that names yadif, bwdif or deinterlace_vaapi
+                           // frame per frame unless -av1mi_deinterlace_rate field), a progressive one is coded as ever, Im is refused (film by
+                           // pulldown is -av1mi_ivtc's business).  tff / bff force a parity, for sources whose header lies.  A chain that names yadif, bwdif or deinterlace_vaapi
                            // (bare, mode=0 or mode=send_frame) means auto.  The job then runs through the frame store.  Not with -av1mi_pack10 1
   int deint_rate = 0;      // -av1mi_deinterlace_rate frame | field (0, 1).  frame (default): one output frame per source frame.  field: one per FIELD
                            // (include/av1mi.h "FIELD-RATE OUTPUT", av1mi_gop_config.deinterlace_fields): twice the frames at twice the rate
                            // (host/fieldrate.hpp), -g counts OUTPUT frames and must be even, a group holds segments x gop / 2 source frames.  It has
                            // a meaning only where the job deinterlaces: with -av1mi_deinterlace off, or auto on a progressive source, the job
                            // runs as ever.  The chain's own field-rate spellings (yadif=1, bwdif=mode=send_field ...) stay refused
+  int ivtc = 0;            // -av1mi_ivtc 0 | 1.  1: inverse telecine (include/av1mi.h "inverse telecine", av1mi_gop_config.telecine), whatever the Y4M header's I
+                           // parameter says, Im included: film carried by 3:2 pulldown is woven back from the right fields and the repeated frame of
+                           // every five is dropped.  -g counts OUTPUT frames and must be a multiple of 4; a group of segments x gop output frames is
+                           // segments x gop x 5 / 4 source frames, put into the store between the last frame of the group before and the first of the
+                           // group after (context), analysed on the GPU, planned (host/telecineplan.hpp) and submitted as woven pairs.  Rate and count
+                           // follow host/fieldrate.hpp (30000/1001 -> 24000/1001).  On material that is not telecined it drops one frame in five.  Not
+                           // with -av1mi_deinterlace, -av1mi_denoise, -av1mi_pack10 1 or -av1mi_scenecut
   int denoise = 0;         // -av1mi_denoise N: 0 (default) = off; 1 .. 16 = the strength of the temporal denoiser (include/av1mi.h "denoising",
                            // av1mi_gop_config.denoise).  The job then runs through the frame store (one group), also without -av1mi_scenecut; the
                            // first and last frame of a group pass through.  Not with -av1mi_pack10 1, not with -av1mi_deinterlace

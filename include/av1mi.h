@@ -750,7 +750,8 @@ int av1mi_crop_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int
  * A still picture gives the weave in both phases, exactly; the padding rule is unchanged.  CONSEQUENCE: output (f, phi = 1) is the
  * same-rate filter applied to the time-reversed triple with the opposite parity — filter(P = N, C = C, N = P, parity 1 - k) — because t,
  * the first term of m and the pair of bound terms are symmetric in P and N.
- * Inverse telecine and neighbours across the boundaries of a run are not built. */
+ * Film carried by 3:2 pulldown is not this filter's business: see "inverse telecine" below.  Neighbours across the boundaries of a
+ * deinterlacer's run are not built. */
 /* The gather with the filter in it, ONE launch for all planes and segments.  d_table: segments * 9 device pointers IN DEVICE MEMORY,
  * [(s * 3 + p) * 3 + i] = plane p of segment s's frame P (i = 0), C (1) and N (2), the run's clamping applied by whoever fills it; a null
  * C makes the slot flat (zeros).  Planes whose rows are whole 16-byte units must be 16-byte aligned, any other 4-byte.  plane_w x
@@ -767,6 +768,55 @@ int av1mi_deinterlace_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3]
  * holds P, C, N of the SOURCE frame o >> 1 of output o. */
 int av1mi_deinterlace_gather_fields(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int parity,
                                     int segments, const void *const *d_table, const uint8_t *d_phase, void *const d_dst[3]);
+
+/* ---- inverse telecine: film carried in 30000/1001 video by 3:2 pulldown becomes its 24000/1001 film frames again
+ * (av1-go_amd/csrc/telecine_kernels.hip; the plan: av1-go_amd/host/telecineplan.hpp).  Two of every five video frames of such a source hold
+ * the fields of two different film frames, and one field of every five is a repeat.  Nothing is filtered: the right fields are WOVEN
+ * back together and the frame that carries the repeat is dropped.  Integer arithmetic, bit exact by definition.
+ *   fields     the TOP field of a frame is its even lines, the BOTTOM field its odd lines.  The bottom field of every source frame is
+ *              kept; its top field is chosen among three candidates.  This covers both field orders and all five phases of the cadence:
+ *              the film frame of a combed video frame has its top field in the frame before or after, and the video frame that repeats
+ *              a film frame repeats its bottom field.
+ *   records    luma only, on m8(v) = v >> (bit_depth - 8), TRUE size w x h inside the buffer; nothing at or beyond the true size is
+ *              read.  A run is frames 0 .. n - 1.  For frame f: B = frame f; T_p, T_c, T_n = frames max(f - 1, 0), f, min(f + 1, n - 1)
+ *              (an absent neighbour equals c).  For j in p, c, n (comb[0], comb[1], comb[2]):
+ *                comb[j] = the sum over even y with 2 <= y <= h - 2 and over x < w of
+ *                          max(0, |2 T_j[y][x] - B[y - 1][x] - B[y + 1][x]| - |B[y - 1][x] - B[y + 1][x]| - 8)
+ *              : how far the candidate top line lies outside what the kept field's two lines around it explain, above a noise floor of
+ *              8.  (h <= 3 has no such line: comb = 0.)
+ *                bdiff   = the sum over odd y < h and x < w of |B_f[y][x] - B_{f-1}[y][x]|; frame 0 of a run has no predecessor and
+ *                          gets 2^64 - 1.
+ *              Every sum fits 64 bits with room (16384 x 16384 x 510 < 2^38).
+ *   the plan   (host, av1mi_plan_telecine) the run's first `front` (0 or 1) and last `back` (0 or 1) frames are CONTEXT: analysed, matched
+ *              against, never output and never counted.  The n own frames are counted in cycles of 5 from the first own frame.
+ *                match   of frame f: the candidate with the smallest comb, ties going to the earlier in the order c, p, n.  The top
+ *                        source is f (c), f - 1 (p) or f + 1 (n), clamped into the run; the bottom source is f.
+ *                drop    in every complete cycle the frame with the smallest bdiff is dropped, the first on ties; a tail of fewer than
+ *                        5 frames drops none.  n frames give n - floor(n / 5) outputs, in order.
+ *              PROPERTY: a sequence cut into runs of any multiple of 5 frames, each given the frame before and the frame after as
+ *              context where the sequence has one, has the plan of the sequence as one run (every comb and bdiff the plan reads is then
+ *              computed from the same three frames).
+ *   the weave  every plane is woven on its own by its own row parity: output row y of a plane of true size w x h comes from row
+ *              r = min(y, h - 1) of the TOP source if r is even, else of the BOTTOM source; columns at or beyond w repeat column w - 1 of
+ *              the same row.  So the output's padding replicates its own edge (the deinterlacer's rule) and the input's padding may be
+ *              undefined.  A plane with h == 1 is the top source's row.  Equal sources give that source's true area.
+ *   determinism  the records in two stages like the crop and quality records: integer partials in scratch with ONE writer each (per
+ *              frame and band of rows), then one workgroup per frame adds them in an order fixed by geometry.  No atomics. */
+typedef struct av1mi_telecine_record { uint64_t comb[3]; uint64_t bdiff; } av1mi_telecine_record;
+/* The records of a run of `frames` (1 .. 65535) frames whose luma planes are stacked in d_luma as for av1mi_crop_analyse: width x height
+ * samples each (multiples of 8, the buffers' size), uint8 at bit_depth 8, uint16 at 10 or 12; true_width x true_height the picture
+ * inside, less than 8 below.  d_records: `frames` records in device memory (or pinned host memory), 8-byte aligned; d_luma 16-byte
+ * aligned.  Two launches (k_telecine_rows walks the run once per band of rows and reads every sample once per role; k_telecine_sum),
+ * asynchronous on the context's stream; the partials live in the context (grown on demand).  AV1MI_K_SCENE in the profile. */
+int av1mi_telecine_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int true_width, int true_height, int frames, const void *d_luma,
+                           av1mi_telecine_record *d_records);
+/* The weave gather, ONE launch for all planes and segments; it stands where av1mi_frames_gather stands.  d_table: segments * 6 device
+ * pointers IN DEVICE MEMORY, [(s * 3 + p) * 2 + i] = plane p of segment s's top (i = 0) and bottom (1) source; a null top makes the slot
+ * flat (zeros).  Planes whose rows are whole 16-byte units must be 16-byte aligned and move in 16-byte units, any other 4-byte aligned, in
+ * dwords.  plane_w x plane_h, true_w x true_h, bit_depth (8: uint8 samples; 10 or 12: uint16) and d_dst as av1mi_deinterlace_gather's.
+ * The sources are only read.  Asynchronous on the context's stream; AV1MI_K_SCENE in the profile. */
+int av1mi_telecine_gather(av1mi_ctx *ctx, int bit_depth, const int plane_w[3], const int plane_h[3], const int true_w[3], const int true_h[3], int segments,
+                          const void *const *d_table, void *const d_dst[3]);
 
 /* ---- denoising: a temporal filter inside the gather (av1-go_amd/csrc/grain_kernels.hip), the deinterlacer's sibling: it removes what
  * changes from frame to frame while the picture stands still — film grain, sensor noise — so that the coder does not spend its bits on
@@ -1128,6 +1178,13 @@ typedef struct av1mi_gop_config {
    * byte per segment behind its pointers, in the same copy.  av1mi_gop_store_put / av1mi_gop_store_analyse keep SOURCE positions and
    * store_frames keeps counting source frames.  Everything behind the gather is unchanged. */
   int deinterlace_fields;
+  /* Inverse telecine ("inverse telecine"; 0 = none: nothing new is allocated, launched or accepted; 1 = on).  Needs store_frames > 0; refused
+   * together with deinterlace, denoise and AV1MI_INPUT_PACKED10.  Each store then holds store_frames + 2 frames, room for one context
+   * frame in front of a group and one behind it: positions 0 .. store_frames + 1 for av1mi_gop_store_put, av1mi_gop_store_telecine and
+   * av1mi_gop_submit_woven, which weaves every segment's frame from two store positions (k_telecine_gather in place of k_frames_gather).
+   * av1mi_gop_submit_stored keeps its meaning (its positions run over the context frames' room too).  Everything behind the gather sees
+   * ordinary fed frames. */
+  int telecine;
 } av1mi_gop_config;
 
 /* The source layout: what a session opened with a config is FED, as one description.  Everything a caller sizes or strides by — the
@@ -1267,6 +1324,14 @@ int av1mi_gop_store_analyse(av1mi_gop *g, int store, int frames, av1mi_scene_rec
  * ever.  frame_type must be 0 or 1: the layout is the caller's.  A later av1mi_gop_store_put into the same store is ordered behind this
  * batch's gather by an event.  In a session with deinterlace_fields index[s] is an OUTPUT position (source position * 2 + phase). */
 int av1mi_gop_submit_stored(av1mi_gop *g, int store, const int32_t *index, int frame_type);
+/* Inverse telecine (av1mi_gop_config.telecine; both are refused in a session without it).  av1mi_gop_store_telecine: the field-match records
+ * ("inverse telecine") of the run of frames 0 .. frames - 1 of the store, context frames included (frames up to store_frames + 2), copied
+ * to out; av1mi_gop_store_analyse's sibling: on the upload stream behind the puts, and it waits for ITS records only.
+ * av1mi_gop_submit_woven: av1mi_gop_submit_stored with TWO store positions per segment: segment s's frame is woven from the top field
+ * (even lines) of position top[s] and the bottom field of position bottom[s]; top[s] = -1 is a flat slot.  The weave gather is launched in
+ * place of k_frames_gather and is ordered against later puts by the same event. */
+int av1mi_gop_store_telecine(av1mi_gop *g, int store, int frames, av1mi_telecine_record *out);
+int av1mi_gop_submit_woven(av1mi_gop *g, int store, const int32_t *top, const int32_t *bottom, int frame_type);
 /* wait for the oldest batch in flight and describe its symbols; AV1MI_E_INVAL when nothing is in flight */
 int av1mi_gop_collect(av1mi_gop *g, av1mi_gop_frame *out);
 /* number of batches in flight (0..av1mi_gop_max_in_flight()) */

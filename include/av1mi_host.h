@@ -191,7 +191,10 @@ long long av1mi_obu_write_blocks_temporal_unit(const av1mi_obu_blocks *f, int wi
  * same frame rate, and refuses Im; a chain that names yadif, bwdif or deinterlace_vaapi — bare, mode=0 or mode=send_frame — means auto;
  * include/av1mi.h "deinterlacing", av1mi_gop_config.deinterlace); "-av1mi_deinterlace_rate frame | field" (frame = default; field = one
  * output frame per FIELD where the job deinterlaces, at twice the source's frame rate: "-g" then counts output frames and must be even;
- * av1mi_gop_config.deinterlace_fields; the chain's own field-rate spellings stay refused);
+ * av1mi_gop_config.deinterlace_fields; the chain's own field-rate spellings stay refused); "-av1mi_ivtc 0 | 1" (0 = default; 1 = inverse
+ * telecine, whatever the source's header's I parameter says, from a file or a stream: 4 output frames per 5 source frames at fps x 4 / 5, "-g" counts
+ * output frames and must be a multiple of 4; include/av1mi.h "inverse telecine", av1mi_gop_config.telecine; not with -av1mi_deinterlace,
+ * -av1mi_denoise, -av1mi_pack10 1 or -av1mi_scenecut);
  * everything else is accepted and ignored.  Returns 0 and leaves the output file in place on
  * success; -1 when the backend could not run at all (no HIP device: transcode.go:311); another non-zero code on failure.
  * err receives the reference-shaped text ("av1mi failed with exit code N: ...", at most 800 characters + "..."). */
