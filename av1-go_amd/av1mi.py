@@ -182,6 +182,8 @@ GRAIN_COV_DTYPE = np.dtype([("sum", "<i8", (4, 13))])      # av1mi_grain_cov_rec
 DENOISE_VEC_DTYPE = np.dtype([("dx_p", "i1"), ("dy_p", "i1"), ("dx_n", "i1"), ("dy_n", "i1")])      # av1mi_denoise_vec: a block's vectors towards P and N
 SCENE_DTYPE = np.dtype([("inter_sad", "<u8"), ("intra_sad", "<u8"), ("blocks", "<u4"), ("reserved", "<u4")])
 CROP_DTYPE = np.dtype([("top", "<u4"), ("bottom", "<u4"), ("left", "<u4"), ("right", "<u4")])      # av1mi_crop_record ("bar detection")
+# av1mi_noise_record ("noise records"): the histogram of the eligible blocks' mean |difference| in 1/16 code, their number, all whole blocks
+NOISE_DTYPE = np.dtype([("hist", "<u4", 256), ("eligible", "<u4"), ("blocks", "<u4")])
 # av1mi_telecine_record ("inverse telecine"): comb of the candidates p, c, n; bdiff
 TELECINE_DTYPE = np.dtype([("comb", "<u8", 3), ("bdiff", "<u8")])
 assert SCENE_DTYPE.itemsize == 24
@@ -880,6 +882,22 @@ class Context:
         try:
             self._chk(self.lib.av1mi_crop_analyse(self.h, int(bit_depth), w, h, int(true_size[0]), int(true_size[1]), n, d_y.ptr, int(limit), d_out.ptr))
             return d_out.download((n,), CROP_DTYPE)
+        finally:
+            d_y.free()
+            d_out.free()
+
+    def noise_analyse(self, Y, bit_depth, true_size):
+        """the noise records (NOISE_DTYPE [pairs]) of luma planes Y [2 * pairs, H8, W8], H8 and W8 multiples of 8, whose picture is true_size =
+        (width, height) (av1mi_noise_analyse): pair i is planes 2 i and 2 i + 1, two consecutive frames; av1stream.plan_denoise() turns
+        the records into a strength"""
+        Y = np.ascontiguousarray(Y, np.uint8 if bit_depth == 8 else np.uint16)
+        n, h, w = Y.shape
+        assert n % 2 == 0, "pairs of planes"
+        self.lib.av1mi_noise_analyse.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]
+        d_y, d_out = self.to_device(Y), self.alloc(max(n // 2, 1) * NOISE_DTYPE.itemsize)
+        try:
+            self._chk(self.lib.av1mi_noise_analyse(self.h, int(bit_depth), w, h, int(true_size[0]), int(true_size[1]), n // 2, d_y.ptr, d_out.ptr))
+            return d_out.download((n // 2,), NOISE_DTYPE)
         finally:
             d_y.free()
             d_out.free()

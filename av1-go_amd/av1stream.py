@@ -455,6 +455,48 @@ def plan_telecine(records, front=0, back=0):
     return top[:k].copy(), bottom[:k].copy()
 
 
+def plan_denoise(records):
+    """av1mi_plan_denoise (host/noiseplan.hpp): noise records (av1mi.NOISE_DTYPE layout) -> (strength 0 .. 16, the pairs' levels (-1 = not
+    valid), the file's sigma in 1/16 of an 8-bit code (-1 = no valid pair))"""
+    h = lib()
+    h.av1mi_plan_denoise.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    r = np.ascontiguousarray(records)
+    assert r.dtype.itemsize == 1032
+    q, s16 = np.full(max(len(r), 1), -7, np.int32), np.full(1, -7, np.int32)
+    k = h.av1mi_plan_denoise(r.ctypes.data if len(r) else None, len(r), q.ctypes.data, s16.ctypes.data)
+    if k < 0:
+        raise ValueError("av1mi_plan_denoise(%d pairs) refused" % len(r))
+    return k, q[:len(r)].copy(), int(s16[0])
+
+
+def noise_pair_slots(frames):
+    """the pair slots -av1mi_denoise auto samples in a file of `frames` frames (pair slot s = frames 2 s and 2 s + 1)"""
+    h = lib()
+    h.av1mi_host_noise_pair_slots.argtypes = [C.c_longlong, C.c_void_p]
+    slots = np.full(16, -7, np.int32)
+    return slots[:h.av1mi_host_noise_pair_slots(int(frames), slots.ctypes.data)].tolist()
+
+
+def parse_denoise_options(argv):
+    """what an argument vector asks of the denoiser: dict(denoise, auto, range, film_grain, grain_lag); ValueError with the host's text where
+    the vector is refused"""
+    h = lib()
+    h.av1mi_host_parse_denoise_options.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_int]
+    err, out = C.create_string_buffer(1024), (C.c_int * 5)()
+    if h.av1mi_host_parse_denoise_options("\n".join(str(x) for x in argv).encode(), out, err, 1024) < 0:
+        raise ValueError(err.value.decode())
+    return dict(zip(("denoise", "auto", "range", "film_grain", "grain_lag"), (int(v) for v in out)))
+
+
+def run_transcode_report(argv):
+    """run_transcode() with the job's report: (exit code, error text, the strength -av1mi_denoise auto planned or -1)"""
+    h = lib()
+    h.av1mi_host_run_transcode_report.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    buf, planned = C.create_string_buffer(2048), C.c_int(-7)
+    code = h.av1mi_host_run_transcode_report("\n".join(str(x) for x in argv).encode(), buf, 2048, C.byref(planned))
+    return code, buf.value.decode(), int(planned.value)
+
+
 def run_transcode(argv):
     """av1mi_run_transcode (include/av1mi_host.h) on an argument vector: (exit code, error text)"""
     h = lib()

@@ -271,6 +271,16 @@ struct CropAnalyseLaunch {
   const void *luma; void *scratch; av1mi_crop_record *out;
 };
 hipError_t launch_crop_analyse(const CropAnalyseLaunch &A, hipStream_t s);
+// noise records (noise_kernels.hip, include/av1mi.h "noise records"): `pairs` pairs of stacked luma planes (pair i = planes 2 i, 2 i + 1) of
+// TRUE size w x h in buffers of stride x rows samples -> one record per pair, two launches.  scratch: noise_layout().bytes bytes, 4-byte
+// aligned: 256 partials per (pair, tile).  bw x bh: the 8x8 blocks that lie wholly inside the true size
+struct NoiseLayout { int bw, bh, tiles_x, tiles_y; size_t bytes; };
+NoiseLayout noise_layout(int bd, int w, int h, int pairs);
+struct NoiseAnalyseLaunch {
+  int bd, stride, rows, w, h, pairs;
+  const void *luma; void *scratch; av1mi_noise_record *out;
+};
+hipError_t launch_noise_analyse(const NoiseAnalyseLaunch &A, hipStream_t s);
 
 // the quality records (quality_kernels.hip): source against the decoded picture, three planes of `frames` stacked frames of TRUE luma
 // size w x h in buffers of that size rounded up to 8; two launches (tiles, then a fixed-order sum per frame and plane).  dec1 / sel

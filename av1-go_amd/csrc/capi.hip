@@ -30,6 +30,8 @@ struct av1mi_ctx {
   size_t scene_scratch_bytes = 0;
   void *crop_scratch = nullptr;           // av1mi_crop_analyse: the partial row / column sums (grown on demand)
   size_t crop_scratch_bytes = 0;
+  void *noise_scratch = nullptr;          // av1mi_noise_analyse: the workgroups' partial histograms (grown on demand)
+  size_t noise_scratch_bytes = 0;
   void *telecine_scratch = nullptr;       // av1mi_telecine_analyse: the waves' partial sums (grown on demand)
   size_t telecine_scratch_bytes = 0;
   void *grain_scratch = nullptr;          // av1mi_denoise_gather: the workgroups' partial records (grown on demand)
@@ -244,6 +246,7 @@ void av1mi_close(av1mi_ctx *ctx) {
   if (ctx->me_scratch) (void)hipFree(ctx->me_scratch);
   if (ctx->scene_scratch) (void)hipFree(ctx->scene_scratch);
   if (ctx->crop_scratch) (void)hipFree(ctx->crop_scratch);
+  if (ctx->noise_scratch) (void)hipFree(ctx->noise_scratch);
   if (ctx->telecine_scratch) (void)hipFree(ctx->telecine_scratch);
   if (ctx->grain_scratch) (void)hipFree(ctx->grain_scratch);
   if (ctx->denoise_vectors) (void)hipFree(ctx->denoise_vectors);
@@ -888,6 +891,25 @@ int av1mi_crop_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int
   A.luma = d_luma; A.scratch = ctx->crop_scratch; A.out = d_records;
   ProfScope ps(ctx, AV1MI_K_SCENE);
   HIP_TRY(ctx, av1mi::launch_crop_analyse(A, ctx->stream));
+  return AV1MI_OK;
+}
+
+int av1mi_noise_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int true_width, int true_height, int pairs, const void *d_luma,
+                        av1mi_noise_record *d_records) {
+  BIND(ctx);
+  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return fail(ctx, AV1MI_E_INVAL, "av1mi_noise_analyse: bit depth %d not supported (8, 10 or 12)", bit_depth);
+  if (width < 8 || height < 8 || (width & 7) || (height & 7) || width > 16384 || height > 16384)
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_noise_analyse: the planes' size %dx%d must be a multiple of 8 (8 .. 16384)", width, height);
+  if (true_width < 1 || true_width > width || width - true_width >= 8 || true_height < 1 || true_height > height || height - true_height >= 8)
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_noise_analyse: the true size %dx%d must lie within 7 samples below the planes' size %dx%d", true_width, true_height, width, height);
+  if (pairs < 1 || pairs > 32767) return fail(ctx, AV1MI_E_INVAL, "av1mi_noise_analyse: pairs %d out of range (1 .. 32767)", pairs);
+  if (!d_luma || !d_records || ((uintptr_t)d_luma & 15) || ((uintptr_t)d_records & 3)) return fail(ctx, AV1MI_E_INVAL, "av1mi_noise_analyse: null or misaligned device pointer (planes 16 bytes, records 4)");
+  if (int rc = grow(ctx, &ctx->noise_scratch, &ctx->noise_scratch_bytes, av1mi::noise_layout(bit_depth, true_width, true_height, pairs).bytes)) return rc;
+  av1mi::NoiseAnalyseLaunch A;
+  A.bd = bit_depth; A.stride = width; A.rows = height; A.w = true_width; A.h = true_height; A.pairs = pairs;
+  A.luma = d_luma; A.scratch = ctx->noise_scratch; A.out = d_records;
+  ProfScope ps(ctx, AV1MI_K_SCENE);
+  HIP_TRY(ctx, av1mi::launch_noise_analyse(A, ctx->stream));
   return AV1MI_OK;
 }
 

@@ -26,12 +26,14 @@
 // session is opened: auto reads up to 32 frames spread evenly over a seekable file, uploads their luma planes, runs av1mi_crop_analyse
 // and plans the window (cropplan.hpp).  The session is then opened with the window (av1mi_gop_config.crop_*) and fed whole frames; the
 // rest of the chain sees the window's size.  No window = the path below as it has always been.
+// -av1mi_denoise auto is settled at the same point, the same way: up to 16 pairs of consecutive frames spread over a seekable file, their
+// luma uploaded as the file holds it, av1mi_noise_analyse, and the plan (noiseplan.hpp) makes the job the job -av1mi_denoise N.
 //
 // `segments` closed GOPs of the file are coded in lockstep (the session's batch dimension); while the host codes the
 // symbols of frame t the GPU already works on frames t + 1 and t + 2 (three batches in flight).
 //
 // RunBackend is a list of steps, each a method of Run (the job's state; its destructor releases what the steps opened) that returns the
-// exit code, 0 = go on: settle_window, session_config (SessionConfig: the policy, a pure function), open_session, run_groups, finish.
+// exit code, 0 = go on: settle_window, settle_denoise, session_config (SessionConfig: the policy, a pure function), open_session, run_groups, finish.
 #include "filmgrain.hpp"
 #include "backend.hpp"
 #include <cstdio>
@@ -43,6 +45,7 @@
 #include "av1_bitstream.hpp"
 #include "cropplan.hpp"
 #include "fieldrate.hpp"
+#include "noiseplan.hpp"
 #include "ratecontrol.hpp"
 #include "sceneplan.hpp"
 #include "telecineplan.hpp"
@@ -133,7 +136,7 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
   if (want == 10 && src.bd == 8)
     return refuse(std::string(job.depth == -1 ? "-av1mi_depth chain: the chain's last format= names a 10-bit format" : "-av1mi_depth 10") + " and the source has 8 bits: 8 -> 10 bits is not built");
   if (want == 8 && src.bd == 10) {
-    if (job.denoise) return refuse("a depth reduction together with -av1mi_denoise is not built: the grain records are measured in 10-bit codes and the grain would be synthesised into an 8-bit stream");
+    if (job.denoise || job.denoise_auto) return refuse("a depth reduction together with -av1mi_denoise is not built: the grain records are measured in 10-bit codes and the grain would be synthesised into an 8-bit stream");
     cfg.coded_bit_depth = 8; cfg.depth_dither = job.dither != 0;      // (ordered unless -av1mi_dither round)
     plan->coded_bd = 8; plan->reduced_from = src.src_bd;
   }
@@ -153,6 +156,7 @@ std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, c
   int k = snprintf(line, sizeof(line), "n:%ld type:%c bytes:%zu", n, key ? 'K' : 'P', f.unit.size());
   k += av1mi::quality::format_figures(av1mi::quality::frame_figures(f.q, bit_depth), line + k, sizeof(line) - (size_t)k);
   if (tags.win.w && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " crop:%dx%d+%d+%d", tags.win.w, tags.win.h, tags.win.x, tags.win.y);
+  if (tags.denoise_auto >= 0 && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " denoise:auto>%d", tags.denoise_auto);
   if (tags.depth_from && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " depth:%d>%d", tags.depth_from, tags.depth_to);
   if (tags.colour && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " colour:%d/%d/%d/%d", tags.colour->primaries, tags.colour->transfer, tags.colour->matrix, tags.colour->full_range);
   if (tags.q) k += snprintf(line + k, sizeof(line) - (size_t)k, " q:%d", f.base_q_idx);
@@ -184,13 +188,14 @@ struct Reads {
 typedef std::vector<std::vector<FrameOut>> GroupOut;      // [segment][t]: the coded frames of the group in flight
 
 struct Run {
-  const BackendJob &job;
+  BackendJob job;              // the caller's, until settle_denoise writes the planned strength into it
   std::string *err;
   av1mi_ctx *ctx = nullptr;
   Y4mSource y;
   av1mi_gop *gop = nullptr;
   StreamSink sink;
   CropRect window;             // settle_window: -av1mi_crop's, given or found (w == 0: none)
+  int planned_denoise = -1;    // settle_denoise: what -av1mi_denoise auto planned (-1: the job did not ask)
   SessionPlan plan = {};       // session_config
   av1::SequenceParams sp;
   int S = 0, G = 0, threads = 1, lag = 0;
@@ -256,9 +261,48 @@ struct Run {
     return 0;
   }
 
+  // The denoiser's strength, settled before the session is opened: -av1mi_denoise auto measures up to 16 pairs of consecutive frames
+  // spread evenly over the file (noiseplan.hpp NoisePairSlot), luma as the file holds it, and plans.  From here on the job IS the job
+  // -av1mi_denoise N; planned 0 = the job without the denoiser, and what only shapes the denoiser goes with it.  (Its own read of the
+  // file: sharing the sample with -av1mi_crop auto is not built.)
+  int settle_denoise() {
+    if (!job.denoise_auto) return 0;
+    if (!y.seekable()) return fail(1, "Invalid argument: -av1mi_denoise auto needs a seekable file: it samples frame pairs from all over the input, not from a pipe or FIFO");
+    // validity does not depend on content: what the job would be refused for with a strength, it is refused for before anything is read
+    SessionPlan dry;
+    if (const int code = SessionConfig(job, facts(), window, &dry, err)) return code;
+    const long have = y.prepare(0, y.known_frames(), err);
+    if (have < 0) return 1;
+    const int P = NoiseSamplePairs(have), W8 = (y.w + 7) & ~7, H8 = (y.h + 7) & ~7;
+    int strength = 0;      // a file of fewer than 2 frames
+    if (P > 0) {
+      const size_t plane = (size_t)W8 * H8 * (y.src_bd == 8 ? 1 : 2);
+      std::vector<unsigned char> luma(plane * 2 * (size_t)P), cu(plane), cv(plane);      // (the chroma planes are read and dropped)
+      for (int i = 0; i < P; i++)
+        for (int k = 0; k < 2; k++)
+          if (!y.read(2 * NoisePairSlot(i, have) + k, W8, H8, luma.data() + plane * (size_t)(2 * i + k), cu.data(), cv.data())) return truncated();
+      std::vector<av1mi_noise_record> rec((size_t)P);
+      void *d_luma = nullptr, *d_rec = nullptr;
+      int rc = av1mi_malloc(ctx, &d_luma, luma.size());
+      if (rc == AV1MI_OK) rc = av1mi_malloc(ctx, &d_rec, rec.size() * sizeof(av1mi_noise_record));
+      if (rc == AV1MI_OK) rc = av1mi_upload(ctx, d_luma, luma.data(), luma.size());
+      if (rc == AV1MI_OK) rc = av1mi_noise_analyse(ctx, y.src_bd, W8, H8, y.w, y.h, P, d_luma, (av1mi_noise_record *)d_rec);
+      if (rc == AV1MI_OK) rc = av1mi_download(ctx, rec.data(), d_rec, rec.size() * sizeof(av1mi_noise_record));
+      if (rc != AV1MI_OK) lib_error("av1mi_noise_analyse");
+      if (d_luma) (void)av1mi_free(ctx, d_luma);
+      if (d_rec) (void)av1mi_free(ctx, d_rec);
+      if (rc != AV1MI_OK) return 2;
+      if ((strength = PlanDenoise(rec.data(), P, nullptr, nullptr)) < 0) return fail(2, "the denoise plan refused its arguments");
+    }
+    planned_denoise = job.denoise = strength;
+    if (!strength) { job.denoise_range = 0; job.film_grain = -1; job.grain_lag = 0; }      // nothing is left for them to shape
+    fprintf(stderr, "[av1mi] denoise: auto planned strength %d from %d pairs of frames\n", strength, P);
+    return 0;
+  }
+
+  SourceFacts facts() const { return { y.w, y.h, y.bd, y.src_bd, y.chroma, y.sar_n, y.sar_d, y.fps_n, y.fps_d, y.interlace, y.colour_range, y.known_frames() }; }
   int session_config() {
-    const SourceFacts src = { y.w, y.h, y.bd, y.src_bd, y.chroma, y.sar_n, y.sar_d, y.fps_n, y.fps_d, y.interlace, y.colour_range, y.known_frames() };
-    if (const int code = SessionConfig(job, src, window, &plan, err)) return code;
+    if (const int code = SessionConfig(job, facts(), window, &plan, err)) return code;
     S = plan.cfg.segments; G = plan.cfg.gop_length;
     threads = job.threads > 0 ? job.threads : (int)std::max(1u, std::thread::hardware_concurrency());
     scratch.resize(plan.packed ? (size_t)S : 0);
@@ -477,7 +521,7 @@ struct Run {
   int write_group(const Group &group, const GroupOut &out) {
     StatsTags tags;
     tags.depth_from = plan.reduced_from; tags.depth_to = plan.coded_bd;
-    tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0; tags.ar = job.grain_lag > 0; tags.lr = job.lr_search != 0; tags.cdef = job.cdef_search != 0; tags.lf = job.lf_search != 0; tags.ivtc = plan.telecine;
+    tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0; tags.ar = job.grain_lag > 0; tags.lr = job.lr_search != 0; tags.cdef = job.cdef_search != 0; tags.lf = job.lf_search != 0; tags.ivtc = plan.telecine; tags.denoise_auto = planned_denoise;
     for (int s = 0; s < S; s++)
       for (size_t t = 0; t < out[(size_t)s].size(); t++) {
         const FrameOut &f = out[(size_t)s][t];
@@ -588,8 +632,9 @@ struct Run {
 
 }  // namespace
 
-int RunBackend(const BackendJob &job, std::string *err) {
+int RunBackend(const BackendJob &job, std::string *err, BackendReport *report) {
   Run r(job, err);
+  struct Tell { Run &r; BackendReport *to; ~Tell() { if (to) to->denoise = r.planned_denoise; } } tell = { r, report };      // (whichever way the job ends)
   if (av1mi_device_count() <= 0 || av1mi_open(job.device, &r.ctx) != AV1MI_OK) {
     r.ctx = nullptr;
     *err = "Error: no usable HIP device for the av1mi backend (device " + std::to_string(job.device) + ")";
@@ -597,7 +642,7 @@ int RunBackend(const BackendJob &job, std::string *err) {
   }
   if (!r.y.open(job.input, err, job.to_420)) return 1;
   int code;
-  if ((code = r.settle_window()) || (code = r.session_config()) || (code = r.open_session()) || (code = r.run_groups())) return code;
+  if ((code = r.settle_window()) || (code = r.settle_denoise()) || (code = r.session_config()) || (code = r.open_session()) || (code = r.run_groups())) return code;
   return r.finish();
 }
 

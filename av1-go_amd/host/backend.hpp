@@ -10,7 +10,9 @@
 namespace av1mi_host {
 // 0 = OK and job.output written; > 0 = failed after starting (bad input, I/O, device error mid-run);
 // < 0 = could not run (no HIP device / library unusable).  *err carries the text.
-int RunBackend(const BackendJob &job, std::string *err);
+// report (may be null): what the job found out about its source, for the caller's log.
+struct BackendReport { int denoise = -1; };      // the strength -av1mi_denoise auto planned (0 .. 16); -1 = not asked, or the job did not get that far
+int RunBackend(const BackendJob &job, std::string *err, BackendReport *report = nullptr);
 
 // What a job's session is opened with, as a pure function (SessionConfig): of the job, of the source's facts as plain values (the Y4M
 // header's, Y4mSource's fields of the same names; known_frames -1 = a stream) and of the settled crop window (w == 0: none).
@@ -54,7 +56,7 @@ struct Group {
 };
 // The stats file: the line of frame n in presentation order, and the summary line.  tags: what a line says beyond the
 // figures — the window, the colour record and the depth reduction " depth:10>8" (frame 0 only; w == 0 / null / depth_from 0 = none), q: (a job with a target), grain: (a job that denoises)
-struct StatsTags { CropRect win; const av1mi_colour *colour = nullptr; int depth_from = 0, depth_to = 0; bool q = false, grain = false, ar = false, lr = false, cdef = false, lf = false, ivtc = false; };      // ivtc: " ivtc:<top source>/<bottom source>", file-wide source frame numbers
+struct StatsTags { CropRect win; const av1mi_colour *colour = nullptr; int depth_from = 0, depth_to = 0; bool q = false, grain = false, ar = false, lr = false, cdef = false, lf = false, ivtc = false; int denoise_auto = -1; };      // denoise_auto: " denoise:auto>N", the planned strength (frame 0 only; -1 = the job did not ask); ivtc: " ivtc:<top source>/<bottom source>", file-wide source frame numbers
 std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, const StatsTags &tags, bool cut);
 std::string StatsSummaryLine(const av1mi::quality::Summary &sum, long long bytes, int bit_depth);
 

@@ -8,6 +8,7 @@
 #include "y4m.hpp"
 #include "backend.hpp"
 #include "fieldrate.hpp"
+#include "noiseplan.hpp"
 #include "../csrc/quality.hpp"
 
 using namespace av1mi_host;
@@ -171,6 +172,38 @@ int av1mi_host_parse_ivtc_option(const char *joined, char *err, int cap) {
 int av1mi_plan_telecine(const av1mi_telecine_record *rec, int frames, int front, int back, int32_t *top, int32_t *bottom) {
   return PlanTelecine(rec, frames, front, back, top, bottom);
 }
+// PlanDenoise (noiseplan.hpp): the strength 0 .. 16 that `pairs` noise records plan, or -1; pair_q (may be null): every pair's level or -1
+// for a pair that is not valid; s16 (may be null): the file's sigma in 1/16 of an 8-bit code, -1 without a valid pair
+int av1mi_plan_denoise(const av1mi_noise_record *rec, int pairs, int32_t *pair_q, int32_t *s16) { return PlanDenoise(rec, pairs, pair_q, s16); }
+// the pair slots -av1mi_denoise auto samples in a file of n frames (noiseplan.hpp NoisePairSlot): their number, slots[i] = the slot of pair i
+// (frames 2 slot, 2 slot + 1); slots holds 16 entries
+int av1mi_host_noise_pair_slots(long long n, int32_t *slots) {
+  const int P = NoiseSamplePairs((long)n);
+  for (int i = 0; i < P; i++) slots[i] = (int32_t)NoisePairSlot(i, (long)n);
+  return P;
+}
+// ParseBackendJob's view of the denoiser's options for an argv joined with '\n': 0 and out = { denoise, denoise_auto, denoise_range,
+// film_grain, grain_lag }, or -1 with the text in err
+int av1mi_host_parse_denoise_options(const char *joined, int *out, char *err, int cap) {
+  const std::vector<std::string> a = split_lines(joined);
+  BackendJob job; std::string e;
+  const bool ok = ParseBackendJob(a, &job, &e);
+  strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
+  out[0] = job.denoise; out[1] = job.denoise_auto ? 1 : 0; out[2] = job.denoise_range; out[3] = job.film_grain; out[4] = job.grain_lag;
+  return ok ? 0 : -1;
+}
+// the argv ProcessJob runs for a TranscodeConfig whose Denoise is `denoise` ("" = not given); av1mi_host_job_args's convention
+int av1mi_host_job_args_denoise(const char *in, const char *out, int height, const char *denoise, char *buf, int cap) {
+  ProbeResult pr; pr.has_video_stream = true; pr.VideoStream.Height = height;
+  std::vector<std::string> a; std::string err;
+  if (!TranscodeArgs("ffmpeg", in, out, pr, false, &a, &err)) return -1;
+  TranscodeConfig cfg; cfg.Denoise = denoise ? denoise : "";
+  AppendConfigArgs(cfg, &a);
+  std::string j;
+  for (size_t i = 0; i < a.size(); i++) j += (i ? "\n" : "") + a[i];
+  strncpy(buf, j.c_str(), cap - 1); buf[cap - 1] = 0;
+  return (int)a.size();
+}
 // FieldRateCuts (fieldrate.hpp): n source frames' cut flags -> 2 n output frames'
 void av1mi_host_field_rate_cuts(const uint8_t *cut, int n, uint8_t *out) { FieldRateCuts(cut, n, out); }
 // ScaleTarget (transcode.hpp): the size a filter chain yields on a source; 0, or -1 for a chain with an unsupported filter
@@ -269,6 +302,13 @@ int av1mi_host_run_transcode(const char *joined, char *buf, int cap) {
   const std::vector<std::string> a = split_lines(joined);
   const RunResult rr = RunTranscode("av1mi", a);
   strncpy(buf, rr.err.c_str(), cap - 1); buf[cap - 1] = 0;
+  return rr.exitCode;
+}
+// av1mi_host_run_transcode with the job's report: *denoise = the strength -av1mi_denoise auto planned, -1 = the job did not ask
+int av1mi_host_run_transcode_report(const char *joined, char *buf, int cap, int *denoise) {
+  const RunResult rr = RunTranscode("av1mi", split_lines(joined));
+  strncpy(buf, rr.err.c_str(), cap - 1); buf[cap - 1] = 0;
+  *denoise = rr.denoise;
   return rr.exitCode;
 }
 // ProcessJob on a source file; returns 0 when the reference would return nil; status and reason into the buffers

@@ -118,6 +118,7 @@ void AppendConfigArgs(const TranscodeConfig &cfg, std::vector<std::string> *a) {
   if (cfg.Format420) { const std::string out = args.back(); args.back() = "-av1mi_format"; args.push_back("420"); args.push_back(out); }
   if (!cfg.Depth.empty()) { const std::string out = args.back(); args.back() = "-av1mi_depth"; args.push_back(cfg.Depth); args.push_back(out); }
   if (!cfg.Dither.empty()) { const std::string out = args.back(); args.back() = "-av1mi_dither"; args.push_back(cfg.Dither); args.push_back(out); }
+  if (!cfg.Denoise.empty()) { const std::string out = args.back(); args.back() = "-av1mi_denoise"; args.push_back(cfg.Denoise); args.push_back(out); }
   if (cfg.MinPSNR > 0) {
     char bound[32];
     snprintf(bound, sizeof(bound), "%.6f", cfg.MinPSNR);
@@ -150,6 +151,7 @@ std::string ProcessJob(Job *job, const std::string &backendPath, const ProbeResu
   }
   AppendConfigArgs(cfg, &args);
   const RunResult rr = RunTranscode(backendPath, args);                                                                                 // :101
+  if (rr.denoise >= 0) fprintf(stderr, "[av1mi] job %s: -av1mi_denoise auto planned strength %d\n", job->ID.c_str(), rr.denoise);
   if (rr.exitCode == 3 && rr.err.compare(0, 14, "quality gate: ") == 0) {      // refused like a file the size gate refuses (:129-150)
     job->Status = "skipped"; job->Reason = rr.err;
     write_why(job->SourcePath, job->Reason);

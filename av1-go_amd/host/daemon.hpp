@@ -54,6 +54,9 @@ struct TranscodeConfig {           // daemon.go:185-188; Device is this backend'
   // reference's, and -global_quality maps 1:1 to the quantiser).  The reference's own estimate expects 0.15 / 0.12 / 0.10 at quality
   // 23 / 24 / 25 (cmd/av1d/main.go:413-427): a caller that wants the size gate to pass asks for that here.
   double TargetBitsPerPixel = 0;
+  // -av1mi_denoise on every job, carried as its value: "" = not given (the default: no denoiser), "auto" = the strength is planned per
+  // file from its measured noise (BackendJob::denoise_auto; what an unattended daemon wants), or a strength "1" .. "16".
+  std::string Denoise;
 };
 // the options a TranscodeConfig adds to the reference's argv (TranscodeArgs), in front of the output path; nothing for a default config
 void AppendConfigArgs(const TranscodeConfig &cfg, std::vector<std::string> *args);

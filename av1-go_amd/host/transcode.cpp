@@ -317,7 +317,9 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
       job->ivtc = args[i + 1] == "1";
     }
     else if (args[i] == "-av1mi_denoise") {
-      if (!plain_int(args[i + 1], &job->denoise) || job->denoise > 16) { if (err) *err = "Invalid argument: -av1mi_denoise takes a strength 1 .. 16 (0 = off), not " + args[i + 1]; return false; }
+      job->denoise_auto = args[i + 1] == "auto";
+      if (job->denoise_auto) job->denoise = 0;
+      else if (!plain_int(args[i + 1], &job->denoise) || job->denoise > 16) { if (err) *err = "Invalid argument: -av1mi_denoise takes a strength 1 .. 16 (0 = off) or auto, not " + args[i + 1]; return false; }
     }
     else if (args[i] == "-av1mi_denoise_range") {
       if (!plain_int(args[i + 1], &job->denoise_range) || (job->denoise_range != 0 && job->denoise_range != 4 && job->denoise_range != 8)) {
@@ -431,10 +433,11 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
       part.clear();
     }
   }
+  const bool denoises = job->denoise || job->denoise_auto;      // (auto: every refusal of -av1mi_denoise N holds whatever is planned later)
   if (job->dither >= 0 && !depth_given) { if (err) *err = "Invalid argument: -av1mi_dither needs -av1mi_depth: it is the rounding of the depth reduction"; return false; }
   if (job->tonemap_peak && !job->tonemap) { if (err) *err = "Invalid argument: -av1mi_tonemap_peak needs -av1mi_tonemap bt2390 (or tonemap_vaapi in the chain)"; return false; }
   if (job->tonemap) {
-    if (job->denoise) { if (err) *err = "Invalid argument: tone mapping together with -av1mi_denoise is not built: the grain would be measured in the source's light"; return false; }
+    if (denoises) { if (err) *err = "Invalid argument: tone mapping together with -av1mi_denoise is not built: the grain would be measured in the source's light"; return false; }
     const bool src_ok = (job->color_primaries < 0 || job->color_primaries == 2 || job->color_primaries == 9) && (job->color_trc < 0 || job->color_trc == 2 || job->color_trc == 16) &&
                         (job->colorspace < 0 || job->colorspace == 2 || job->colorspace == 9) && job->color_range <= 0;
     if (!src_ok) { if (err) *err = "Invalid argument: tone mapping takes a bt2020 / smpte2084 / bt2020nc / tv source: with it -color_* describe the source, and they say otherwise"; return false; }
@@ -450,7 +453,7 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
   }
   if (job->ivtc) {
     if (job->deinterlace) { if (err) *err = "Invalid argument: -av1mi_ivtc weaves the film frames of a telecined source back together, -av1mi_deinterlace (or a deinterlacer in the chain) filters them: give one"; return false; }
-    if (job->denoise) { if (err) *err = "Invalid argument: -av1mi_ivtc together with -av1mi_denoise is not built: the denoiser's neighbours would be video frames, not the woven film frames"; return false; }
+    if (denoises) { if (err) *err = "Invalid argument: -av1mi_ivtc together with -av1mi_denoise is not built: the denoiser's neighbours would be video frames, not the woven film frames"; return false; }
     if (job->pack10) { if (err) *err = "Invalid argument: -av1mi_ivtc keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
     if (job->scenecut) { if (err) *err = "Invalid argument: -av1mi_ivtc together with -av1mi_scenecut is not built: the cuts of the source frames would have to be mapped through the dropped frames"; return false; }
     if (job->gop >= 1 && (job->gop & 3)) {
@@ -466,11 +469,18 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
       return false;
     }
   }
-  if (job->denoise && job->pack10) { if (err) *err = "Invalid argument: -av1mi_denoise keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
-  if (job->denoise && job->deinterlace) { if (err) *err = "Invalid argument: -av1mi_denoise filters the group's frames on their way from the store, as -av1mi_deinterlace does: not together with -av1mi_deinterlace"; return false; }
-  if (job->denoise_range && !job->denoise) { if (err) *err = "Invalid argument: -av1mi_denoise_range needs -av1mi_denoise"; return false; }
-  if (job->film_grain >= 0 && !job->denoise) { if (err) *err = "Invalid argument: -av1mi_film_grain needs -av1mi_denoise"; return false; }
-  if (grain_lag_given && !job->denoise) { if (err) *err = "Invalid argument: -av1mi_grain_lag needs -av1mi_denoise"; return false; }
+  if (job->denoise_auto) {      // the same rule, for the same reason: a stream's first frames are its opening credits
+    struct stat st;
+    if (job->input == "-" || job->input == "pipe:0" || (!stat(job->input.c_str(), &st) && !S_ISREG(st.st_mode))) {
+      if (err) *err = "Invalid argument: -av1mi_denoise auto needs a seekable file: it samples frame pairs from all over the input, not from a pipe or FIFO";
+      return false;
+    }
+  }
+  if (denoises && job->pack10) { if (err) *err = "Invalid argument: -av1mi_denoise keeps the group's frames in a planar store on the GPU: not together with -av1mi_pack10 1"; return false; }
+  if (denoises && job->deinterlace) { if (err) *err = "Invalid argument: -av1mi_denoise filters the group's frames on their way from the store, as -av1mi_deinterlace does: not together with -av1mi_deinterlace"; return false; }
+  if (job->denoise_range && !denoises) { if (err) *err = "Invalid argument: -av1mi_denoise_range needs -av1mi_denoise"; return false; }
+  if (job->film_grain >= 0 && !denoises) { if (err) *err = "Invalid argument: -av1mi_film_grain needs -av1mi_denoise"; return false; }
+  if (grain_lag_given && !denoises) { if (err) *err = "Invalid argument: -av1mi_grain_lag needs -av1mi_denoise"; return false; }
   if (grain_lag_given && job->film_grain == 0) { if (err) *err = "Invalid argument: -av1mi_grain_lag shapes the film grain: not together with -av1mi_film_grain 0"; return false; }
   if (job->min_gop && !job->scenecut) { if (err) *err = "Invalid argument: -av1mi_min_gop needs -av1mi_scenecut"; return false; }
   if (job->min_gop && job->gop >= 1 && job->min_gop > job->gop - job->gop / 2) { if (err) *err = "Invalid argument: -av1mi_min_gop " + std::to_string(job->min_gop) + " above gop - gop / 2 = " + std::to_string(job->gop - job->gop / 2); return false; }
@@ -484,12 +494,13 @@ RunResult RunTranscode(const std::string &backendPath, const std::vector<std::st
   BackendJob job;
   std::string err;
   if (!ParseBackendJob(args, &job, &err)) return { 1, "av1mi failed with exit code 1: " + err };
-  const int code = RunBackend(job, &err);
-  if (code == 0) return { 0, "" };
+  BackendReport report;
+  const int code = RunBackend(job, &err, &report);
+  if (code == 0) return { 0, "", report.denoise };
   if (err.size() > 800) err = err.substr(0, 800) + "...";      // transcode.go:295-297
-  if (code < 0) return { -1, "av1mi execution failed: " + err };   // transcode.go:311 (could not run)
-  if (code == 3) return { 3, err };                                // the quality gate: "quality gate: psnr_y ..." as it is
-  return { code, "av1mi failed with exit code " + std::to_string(code) + ": " + err };   // transcode.go:299
+  if (code < 0) return { -1, "av1mi execution failed: " + err, report.denoise };   // transcode.go:311 (could not run)
+  if (code == 3) return { 3, err, report.denoise };                // the quality gate: "quality gate: psnr_y ..." as it is
+  return { code, "av1mi failed with exit code " + std::to_string(code) + ": " + err, report.denoise };   // transcode.go:299
 }
 
 }  // namespace av1mi_host

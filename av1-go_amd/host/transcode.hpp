@@ -106,6 +106,12 @@ struct BackendJob {
   int denoise = 0;         // -av1mi_denoise N: 0 (default) = off; 1 .. 16 = the strength of the temporal denoiser (include/av1mi.h "denoising",
                            // av1mi_gop_config.denoise).  The job then runs through the frame store (one group), also without -av1mi_scenecut; the
                            // first and last frame of a group pass through.  Not with -av1mi_pack10 1, not with -av1mi_deinterlace
+  bool denoise_auto = false;   // -av1mi_denoise auto: the strength is PLANNED per file before the session opens (host/noiseplan.hpp): needs a seekable
+                           // file; up to 16 pairs of consecutive frames spread evenly over it are uploaded and measured on the GPU
+                           // (av1mi_noise_analyse, include/av1mi.h "noise records").  Planned N >= 1: the job -av1mi_denoise N runs, byte for byte.
+                           // Planned 0: the job without -av1mi_denoise, byte for byte; -av1mi_denoise_range, -av1mi_film_grain and
+                           // -av1mi_grain_lag are then dropped with it.  Everything -av1mi_denoise N is refused with, auto is refused with,
+                           // whatever is planned later.  `denoise` stays 0 until the plan is made
   int denoise_range = 0;   // -av1mi_denoise_range N: 0 (default), 4 or 8 = the range of the denoiser's block search (include/av1mi.h "motion-compensated
                            // denoising", av1mi_gop_config.denoise_range); an error without -av1mi_denoise
   int grain_lag = 0;       // -av1mi_grain_lag N: 0 (default, white grain) .. 3 = the lag of the film grain's autoregressive filter, its coefficients from the
@@ -175,7 +181,8 @@ bool ChainTarget(int iw, int ih, int sar_n, int sar_d, const std::string &chain,
 // transcode.go:194-315 contract: (0, "") on success AND the output file exists; (code, text <= 800 chars) on failure;
 // (-1, text) when the backend could not run at all (no HIP device, library error before any frame).  Exit code 3 is the quality gate
 // (-av1mi_min_psnr): its text is handed on as it is, "quality gate: psnr_y ...", for ProcessJob to treat like the size gate.
-struct RunResult { int exitCode; std::string err; };
+// denoise: the strength -av1mi_denoise auto planned for the file (0 .. 16), for the caller's log; -1 = the job did not ask, or did not get that far.
+struct RunResult { int exitCode; std::string err; int denoise = -1; };
 RunResult RunTranscode(const std::string &backendPath, const std::vector<std::string> &args);
 
 }  // namespace av1mi_host

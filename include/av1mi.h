@@ -717,6 +717,48 @@ typedef struct av1mi_crop_record { uint32_t top, bottom, left, right; } av1mi_cr
 int av1mi_crop_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int true_width, int true_height, int frames, const void *d_luma, int limit,
                        av1mi_crop_record *d_records);
 
+/* ---- noise records: how much of a source changes from frame to frame where the picture stands still (av1-go_amd/csrc/noise_kernels.hip),
+ * from which the host plans the strength of "denoising" below (av1-go_amd/host/noiseplan.hpp, av1mi_plan_denoise of libav1mi_host.so).
+ * Integer arithmetic, bit exact by definition; luma only.
+ *   pairs          a record describes a pair (A, B) of consecutive frames: planes of TRUE size w x h inside buffers of W8 x H8 samples (the
+ *                  true size rounded up to 8); m8(v) = v >> (bit_depth - 8), as in "motion search".
+ *   blocks         only the 8 x 8 blocks that lie wholly inside the true size are looked at: block (bx, by), bx < floor(w / 8),
+ *                  by < floor(h / 8), covers the samples [8 bx, 8 bx + 8) x [8 by, 8 by + 8).  Nothing at or beyond the true size is read:
+ *                  the buffer's padding may be undefined (a true size under 8 in either direction has no block).
+ *   per block      on native samples, over the block's 64 samples: S = sum |A - B|;  M = sum m8(A);  S8 = S >> (bit_depth - 8).
+ *   eligible       a block is eligible iff 16 x 64 <= M <= 235 x 64.  A block whose mean lies outside the nominal video range is clipped
+ *                  or synthetic (black bars, credits, burnt whites): it carries no noise and would pull any low percentile to zero on
+ *                  a letterboxed film (has the same trap for the grain records).
+ *   bin            min(255, S8 >> 2): one bin is 1/16 of an 8-bit code of mean absolute difference; bin 255 = "16 codes or more", which
+ *                  is motion, not noise.
+ *   the record     hist[b] = the eligible blocks of bin b; eligible = their number (the sum of hist); blocks = floor(w / 8) x floor(h / 8).
+ *   determinism    two stages like the crop, scene and telecine records: per workgroup a histogram in LDS (integer atomics: integer
+ *                  addition gives the same bytes in any order), written as integer partials with ONE writer each, then one workgroup per
+ *                  pair adds them in an order fixed by geometry.
+ *   the plan       (host, av1mi_plan_denoise; a pure function of the records)
+ *                  per pair: counted = the sum of hist[0 .. 254].  The pair is VALID iff counted >= 1, 4 counted >= eligible and
+ *                  eligible >= floor(blocks / 16): at least a quarter of what could be judged stood still enough to be judged.  Its
+ *                  level q = the smallest bin whose cumulative count over bins 0 .. 254 reaches ceil(counted / 4): the lower quartile
+ *                  (motion, and texture that moved, only ever add to S: the still blocks are at the low end).
+ *                  per file: the valid pairs' q sorted ascending, Q = the one at index floor((n - 1) / 4) (noise is a property of the
+ *                  file; motion in some pairs only adds to it).  No valid pair: strength 0.
+ *                  sigma in 1/16 code: s16 = (227 Q + 128) >> 8 (the mean |difference| of two independent noises of sigma is 1.128 sigma;
+ *                  227 / 256 = 1 / 1.128).
+ *                  strength = 0 if s16 < 8 (sigma under half a code: rounding to 8 bits alone gives 0.29), else min(16, (3 s16 + 31) >> 5)
+ *                  = ceil(1.5 sigma).  The 1.5 follows from "denoising" below: w_F = 16 - floor(16 MAD / (3 T)), and a sample counts as
+ *                  grain iff w_P + w_N >= 24, i.e. w >= 12 per neighbour, i.e. MAD <= 3 T / 4; with MAD = 1.128 sigma that needs
+ *                  T >= 1.5 sigma: the smallest strength at which a still, noisy sample is on average counted as grain.
+ * The estimate is temporal: a file that moves everywhere in every pair plans 0. */
+typedef struct av1mi_noise_record { uint32_t hist[256]; uint32_t eligible, blocks; } av1mi_noise_record;
+/* The records of `pairs` (1 .. 32767) pairs whose 2 x pairs luma planes are stacked in d_luma as for av1mi_crop_analyse (pair i = planes
+ * 2 i and 2 i + 1): width x height samples each, both multiples of 8 (the buffers' size), uint8 at bit_depth 8, uint16 at 10 or 12;
+ * true_width x true_height the picture inside, less than 8 below the buffer's size.  d_records: `pairs` records in device memory, 4-byte
+ * aligned; d_luma 16-byte aligned.  Two launches (k_noise_blocks reads every sample of the whole blocks of both planes once, in whole
+ * 16-byte units where the rows allow; k_noise_sum), asynchronous on the context's stream; the partials live in the context (grown on
+ * demand).  AV1MI_K_SCENE in the profile. */
+int av1mi_noise_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int true_width, int true_height, int pairs, const void *d_luma,
+                        av1mi_noise_record *d_records);
+
 /* ---- deinterlacing: an interlaced source becomes progressive frames inside the gather (av1-go_amd/csrc/deint_kernels.hip).  AV1 has no
  * interlaced coding and no field signalling: combing that is coded stays in the picture.  The filter is SAME-RATE: one output frame per
  * input frame, at the time of the frame's FIRST field.  Integer arithmetic, bit exact by definition.

@@ -183,7 +183,9 @@ long long av1mi_obu_write_blocks_temporal_unit(const av1mi_obu_blocks *f, int wi
  * "-av1mi_segments", "-av1mi_gpu_entropy", "-av1mi_key_block_size", "-av1mi_tracks", "-threads", "-av1mi_scale WxH"; "-vf:v:0 <chain>"
  * is evaluated on the source (its scale filters are applied on the GPU, a filter that cannot be applied is an error: INTEGRATION.md §1);
  * "-av1mi_denoise N" (0 = default: off; 1 .. 16 = the strength of the temporal denoiser in the gather, include/av1mi.h "denoising"; the job
- * runs through the frame store; not with -av1mi_pack10 1 or -av1mi_deinterlace), "-av1mi_denoise_range N" (0 = default, 4 or 8: the filter
+ * runs through the frame store; not with -av1mi_pack10 1 or -av1mi_deinterlace), "-av1mi_denoise auto" (the strength is planned per file before the session
+ * opens: up to 16 pairs of consecutive frames of a seekable file are measured on the GPU, include/av1mi.h "noise records", and the job is the job
+ * -av1mi_denoise N from there on, or with N = 0 the job without the option; refused with everything -av1mi_denoise N is refused with), "-av1mi_denoise_range N" (0 = default, 4 or 8: the filter
  * follows the picture by a block search of that range, include/av1mi.h "motion-compensated denoising"; an error without -av1mi_denoise),
  * "-av1mi_film_grain 0 | 1" (1 by default when denoising:
  * film grain synthesis parameters from what was removed, av1mi_filmgrain.h; an error without -av1mi_denoise);
