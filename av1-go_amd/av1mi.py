@@ -184,6 +184,8 @@ SCENE_DTYPE = np.dtype([("inter_sad", "<u8"), ("intra_sad", "<u8"), ("blocks", "
 CROP_DTYPE = np.dtype([("top", "<u4"), ("bottom", "<u4"), ("left", "<u4"), ("right", "<u4")])      # av1mi_crop_record ("bar detection")
 # av1mi_noise_record ("noise records"): the histogram of the eligible blocks' mean |difference| in 1/16 code, their number, all whole blocks
 NOISE_DTYPE = np.dtype([("hist", "<u4", 256), ("eligible", "<u4"), ("blocks", "<u4")])
+# av1mi_peak_record ("peak records"): the histogram of a frame's max(R', G', B') as 10-bit PQ codes, and its pixels (the sum of hist)
+PEAK_DTYPE = np.dtype([("hist", "<u4", 1024), ("pixels", "<u4")])
 # av1mi_telecine_record ("inverse telecine"): comb of the candidates p, c, n; bdiff
 TELECINE_DTYPE = np.dtype([("comb", "<u8", 3), ("bdiff", "<u8")])
 assert SCENE_DTYPE.itemsize == 24
@@ -901,6 +903,22 @@ class Context:
         finally:
             d_y.free()
             d_out.free()
+
+    def peak_analyse(self, Y, U, V, true_size):
+        """the peak records (PEAK_DTYPE [frames]) of planar 4:2:0 uint16 frames Y [frames, H8, W8], U and V [frames, H8 / 2, W8 / 2], H8 and W8
+        multiples of 8, whose picture is true_size = (width, height) (av1mi_peak_analyse); av1stream.plan_peak() turns the records into the
+        tone map's source peak"""
+        Y, U, V = (np.ascontiguousarray(a, np.uint16) for a in (Y, U, V))
+        n, h, w = Y.shape
+        assert U.shape == V.shape == (n, h // 2, w // 2), "4:2:0 planes"
+        self.lib.av1mi_peak_analyse.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4
+        bufs = [self.to_device(a) for a in (Y, U, V)] + [self.alloc(max(n, 1) * PEAK_DTYPE.itemsize)]
+        try:
+            self._chk(self.lib.av1mi_peak_analyse(self.h, w, h, int(true_size[0]), int(true_size[1]), n, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr))
+            return bufs[3].download((n,), PEAK_DTYPE)
+        finally:
+            for b in bufs:
+                b.free()
 
     def denoise_gather(self, bit_depth, plane_sizes, true_sizes, strength, segments, d_table, d_dst, d_records=None):
         """the gather with the denoiser in it (av1mi_denoise_gather): deinterlace_gather's arguments with a strength (1 .. 16) in place of

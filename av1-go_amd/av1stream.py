@@ -469,6 +469,38 @@ def plan_denoise(records):
     return k, q[:len(r)].copy(), int(s16[0])
 
 
+def plan_peak(records):
+    """av1mi_plan_peak (host/peakplan.hpp): peak records (av1mi.PEAK_DTYPE layout) -> (the tone map's source peak in cd/m2, 400 .. 10000,
+    the frames' codes)"""
+    h = lib()
+    h.av1mi_plan_peak.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    r = np.ascontiguousarray(records)
+    assert r.dtype.itemsize == 4100
+    codes = np.full(max(len(r), 1), -7, np.int32)
+    peak = h.av1mi_plan_peak(r.ctypes.data if len(r) else None, len(r), codes.ctypes.data)
+    if peak < 0:
+        raise ValueError("av1mi_plan_peak(%d frames) refused" % len(r))
+    return peak, codes[:len(r)].copy()
+
+
+def peak_sample_slots(frames):
+    """the frames -av1mi_tonemap_peak auto samples in a file of `frames` frames (the crop sampler's slots)"""
+    h = lib()
+    h.av1mi_host_peak_sample_slots.argtypes = [C.c_longlong, C.c_void_p]
+    slots = np.full(32, -7, np.int32)
+    return slots[:h.av1mi_host_peak_sample_slots(int(frames), slots.ctypes.data)].tolist()
+
+
+def parse_peak_options(argv):
+    """what an argument vector asks of the tone map: dict(tonemap, peak, auto); ValueError with the host's text where the vector is refused"""
+    h = lib()
+    h.av1mi_host_parse_peak_options.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_int]
+    err, out = C.create_string_buffer(1024), (C.c_int * 3)()
+    if h.av1mi_host_parse_peak_options("\n".join(str(x) for x in argv).encode(), out, err, 1024) < 0:
+        raise ValueError(err.value.decode())
+    return dict(zip(("tonemap", "peak", "auto"), (int(v) for v in out)))
+
+
 def noise_pair_slots(frames):
     """the pair slots -av1mi_denoise auto samples in a file of `frames` frames (pair slot s = frames 2 s and 2 s + 1)"""
     h = lib()

@@ -281,6 +281,16 @@ struct NoiseAnalyseLaunch {
   const void *luma; void *scratch; av1mi_noise_record *out;
 };
 hipError_t launch_noise_analyse(const NoiseAnalyseLaunch &A, hipStream_t s);
+// peak records (peak_kernels.hip, include/av1mi.h "peak records"): `frames` stacked planar 4:2:0 uint16 frames of TRUE luma size tw x th in
+// buffers of w8 x h8 luma samples (chroma w8 / 2 x h8 / 2) -> one record per frame, two launches.  scratch: peak_layout().bytes bytes,
+// 16-byte aligned: 1024 partials per (frame, strip of rows)
+struct PeakLayout { int strips; size_t bytes; };
+PeakLayout peak_layout(int th, int frames);
+struct PeakAnalyseLaunch {
+  int w8, h8, tw, th, frames;
+  const void *y, *u, *v; void *scratch; av1mi_peak_record *out;
+};
+hipError_t launch_peak_analyse(const PeakAnalyseLaunch &A, hipStream_t s);
 
 // the quality records (quality_kernels.hip): source against the decoded picture, three planes of `frames` stacked frames of TRUE luma
 // size w x h in buffers of that size rounded up to 8; two launches (tiles, then a fixed-order sum per frame and plane).  dec1 / sel

@@ -32,6 +32,8 @@ struct av1mi_ctx {
   size_t crop_scratch_bytes = 0;
   void *noise_scratch = nullptr;          // av1mi_noise_analyse: the workgroups' partial histograms (grown on demand)
   size_t noise_scratch_bytes = 0;
+  void *peak_scratch = nullptr;           // av1mi_peak_analyse: the workgroups' partial histograms (grown on demand)
+  size_t peak_scratch_bytes = 0;
   void *telecine_scratch = nullptr;       // av1mi_telecine_analyse: the waves' partial sums (grown on demand)
   size_t telecine_scratch_bytes = 0;
   void *grain_scratch = nullptr;          // av1mi_denoise_gather: the workgroups' partial records (grown on demand)
@@ -247,6 +249,7 @@ void av1mi_close(av1mi_ctx *ctx) {
   if (ctx->scene_scratch) (void)hipFree(ctx->scene_scratch);
   if (ctx->crop_scratch) (void)hipFree(ctx->crop_scratch);
   if (ctx->noise_scratch) (void)hipFree(ctx->noise_scratch);
+  if (ctx->peak_scratch) (void)hipFree(ctx->peak_scratch);
   if (ctx->telecine_scratch) (void)hipFree(ctx->telecine_scratch);
   if (ctx->grain_scratch) (void)hipFree(ctx->grain_scratch);
   if (ctx->denoise_vectors) (void)hipFree(ctx->denoise_vectors);
@@ -910,6 +913,25 @@ int av1mi_noise_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, in
   A.luma = d_luma; A.scratch = ctx->noise_scratch; A.out = d_records;
   ProfScope ps(ctx, AV1MI_K_SCENE);
   HIP_TRY(ctx, av1mi::launch_noise_analyse(A, ctx->stream));
+  return AV1MI_OK;
+}
+
+int av1mi_peak_analyse(av1mi_ctx *ctx, int width, int height, int true_width, int true_height, int frames, const void *d_y, const void *d_u, const void *d_v,
+                       av1mi_peak_record *d_records) {
+  BIND(ctx);
+  if (width < 8 || height < 8 || (width & 7) || (height & 7) || width > 16384 || height > 16384)
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_peak_analyse: the planes' size %dx%d must be a multiple of 8 (8 .. 16384)", width, height);
+  if (true_width < 1 || true_width > width || width - true_width >= 8 || true_height < 1 || true_height > height || height - true_height >= 8)
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_peak_analyse: the true size %dx%d must lie within 7 samples below the planes' size %dx%d", true_width, true_height, width, height);
+  if (frames < 1 || frames > 65535) return fail(ctx, AV1MI_E_INVAL, "av1mi_peak_analyse: frames %d out of range (1 .. 65535)", frames);
+  if (!d_y || !d_u || !d_v || !d_records || (((uintptr_t)d_y | (uintptr_t)d_u | (uintptr_t)d_v) & 15) || ((uintptr_t)d_records & 3))
+    return fail(ctx, AV1MI_E_INVAL, "av1mi_peak_analyse: null or misaligned device pointer (planes 16 bytes, records 4)");
+  if (int rc = grow(ctx, &ctx->peak_scratch, &ctx->peak_scratch_bytes, av1mi::peak_layout(true_height, frames).bytes)) return rc;
+  av1mi::PeakAnalyseLaunch A;
+  A.w8 = width; A.h8 = height; A.tw = true_width; A.th = true_height; A.frames = frames;
+  A.y = d_y; A.u = d_u; A.v = d_v; A.scratch = ctx->peak_scratch; A.out = d_records;
+  ProfScope ps(ctx, AV1MI_K_SCENE);
+  HIP_TRY(ctx, av1mi::launch_peak_analyse(A, ctx->stream));
   return AV1MI_OK;
 }
 

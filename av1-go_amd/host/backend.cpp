@@ -28,12 +28,14 @@
 // rest of the chain sees the window's size.  No window = the path below as it has always been.
 // -av1mi_denoise auto is settled at the same point, the same way: up to 16 pairs of consecutive frames spread over a seekable file, their
 // luma uploaded as the file holds it, av1mi_noise_analyse, and the plan (noiseplan.hpp) makes the job the job -av1mi_denoise N.
+// -av1mi_tonemap_peak auto likewise: up to 32 frames in the crop sampler's slots, all three planes, av1mi_peak_analyse, and the plan
+// (peakplan.hpp) makes the job the job -av1mi_tonemap_peak N.
 //
 // `segments` closed GOPs of the file are coded in lockstep (the session's batch dimension); while the host codes the
 // symbols of frame t the GPU already works on frames t + 1 and t + 2 (three batches in flight).
 //
 // RunBackend is a list of steps, each a method of Run (the job's state; its destructor releases what the steps opened) that returns the
-// exit code, 0 = go on: settle_window, settle_denoise, session_config (SessionConfig: the policy, a pure function), open_session, run_groups, finish.
+// exit code, 0 = go on: settle_window, settle_denoise, settle_peak, session_config (SessionConfig: the policy, a pure function), open_session, run_groups, finish.
 #include "filmgrain.hpp"
 #include "backend.hpp"
 #include <cstdio>
@@ -46,6 +48,7 @@
 #include "cropplan.hpp"
 #include "fieldrate.hpp"
 #include "noiseplan.hpp"
+#include "peakplan.hpp"
 #include "ratecontrol.hpp"
 #include "sceneplan.hpp"
 #include "telecineplan.hpp"
@@ -125,6 +128,8 @@ int SessionConfig(const BackendJob &job, const SourceFacts &src, const CropRect 
   plan->colour = JobColour(job, src.colour_range);
   if (const char *why = av1::colour_error(plan->colour)) return refuse(why);
   if (job.tonemap) {
+    if (job.tonemap_peak_auto && (src.chroma != AV1MI_CHROMA_420 || src.src_bd != 10))
+      return refuse("-av1mi_tonemap_peak auto measures 4:2:0 10-bit frames as the file holds them: a 4:2:2, 4:4:4, grey, 8- or 12-bit source is not measured (give the peak as a number)");
     if (src.bd != 10) return refuse("tone mapping needs a 10-bit source (an 8-bit HDR10 source does not exist)");
     if (src.colour_range == 1) return refuse("tone mapping takes a limited-range source; the Y4M header says XCOLORRANGE=FULL");
     cfg.tone_map = 1;
@@ -157,6 +162,7 @@ std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, c
   k += av1mi::quality::format_figures(av1mi::quality::frame_figures(f.q, bit_depth), line + k, sizeof(line) - (size_t)k);
   if (tags.win.w && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " crop:%dx%d+%d+%d", tags.win.w, tags.win.h, tags.win.x, tags.win.y);
   if (tags.denoise_auto >= 0 && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " denoise:auto>%d", tags.denoise_auto);
+  if (tags.peak_auto >= 0 && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " peak:auto>%d", tags.peak_auto);
   if (tags.depth_from && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " depth:%d>%d", tags.depth_from, tags.depth_to);
   if (tags.colour && n == 0) k += snprintf(line + k, sizeof(line) - (size_t)k, " colour:%d/%d/%d/%d", tags.colour->primaries, tags.colour->transfer, tags.colour->matrix, tags.colour->full_range);
   if (tags.q) k += snprintf(line + k, sizeof(line) - (size_t)k, " q:%d", f.base_q_idx);
@@ -188,7 +194,7 @@ struct Reads {
 typedef std::vector<std::vector<FrameOut>> GroupOut;      // [segment][t]: the coded frames of the group in flight
 
 struct Run {
-  BackendJob job;              // the caller's, until settle_denoise writes the planned strength into it
+  BackendJob job;              // the caller's, until settle_denoise / settle_peak write what they planned into it
   std::string *err;
   av1mi_ctx *ctx = nullptr;
   Y4mSource y;
@@ -196,6 +202,7 @@ struct Run {
   StreamSink sink;
   CropRect window;             // settle_window: -av1mi_crop's, given or found (w == 0: none)
   int planned_denoise = -1;    // settle_denoise: what -av1mi_denoise auto planned (-1: the job did not ask)
+  int planned_peak = -1;       // settle_peak: what -av1mi_tonemap_peak auto planned, cd/m2 (-1: the job did not ask)
   SessionPlan plan = {};       // session_config
   av1::SequenceParams sp;
   int S = 0, G = 0, threads = 1, lag = 0;
@@ -297,6 +304,48 @@ struct Run {
     planned_denoise = job.denoise = strength;
     if (!strength) { job.denoise_range = 0; job.film_grain = -1; job.grain_lag = 0; }      // nothing is left for them to shape
     fprintf(stderr, "[av1mi] denoise: auto planned strength %d from %d pairs of frames\n", strength, P);
+    return 0;
+  }
+
+  // The tone map's peak, settled before the session is opened: -av1mi_tonemap_peak auto measures up to 32 frames spread evenly over the
+  // file (the crop sampler's slots and I/O budget), all three planes as the file holds them, and plans.  From here on the job IS the job
+  // -av1mi_tonemap_peak N.  The whole frame is measured, in front of crop and scale: black bars only add to `pixels`, and a crop window
+  // does not change the plan.  (Its own read of the file: together with -av1mi_crop auto the file is sampled twice; sharing is not built.)
+  int settle_peak() {
+    if (!job.tonemap_peak_auto) return 0;
+    if (!y.seekable()) return fail(1, "Invalid argument: -av1mi_tonemap_peak auto needs a seekable file: it samples frames from all over the input, not from a pipe or FIFO");
+    // validity does not depend on content: what the job would be refused for with a number, it is refused for before anything is read
+    SessionPlan dry;
+    if (const int code = SessionConfig(job, facts(), window, &dry, err)) return code;
+    const long have = y.prepare(0, y.known_frames(), err);
+    if (have < 0) return 1;
+    const int n = PeakSampleFrames(have), W8 = (y.w + 7) & ~7, H8 = (y.h + 7) & ~7;
+    if (n < 1) return fail(1, job.input + ": -av1mi_tonemap_peak auto found no frame to measure");
+    const size_t luma = (size_t)W8 * H8 * 2, chroma = luma / 4;
+    std::vector<unsigned char> py(luma * (size_t)n), pu(chroma * (size_t)n), pv(chroma * (size_t)n);
+    for (int i = 0; i < n; i++)
+      if (!y.read(PeakSampleSlot(i, have), W8, H8, py.data() + luma * (size_t)i, pu.data() + chroma * (size_t)i, pv.data() + chroma * (size_t)i)) return truncated();
+    std::vector<av1mi_peak_record> rec((size_t)n);
+    void *d[3] = { nullptr, nullptr, nullptr }, *d_rec = nullptr;
+    int rc = av1mi_malloc(ctx, &d[0], py.size());
+    if (rc == AV1MI_OK) rc = av1mi_malloc(ctx, &d[1], pu.size());
+    if (rc == AV1MI_OK) rc = av1mi_malloc(ctx, &d[2], pv.size());
+    if (rc == AV1MI_OK) rc = av1mi_malloc(ctx, &d_rec, rec.size() * sizeof(av1mi_peak_record));
+    if (rc == AV1MI_OK) rc = av1mi_upload(ctx, d[0], py.data(), py.size());
+    if (rc == AV1MI_OK) rc = av1mi_upload(ctx, d[1], pu.data(), pu.size());
+    if (rc == AV1MI_OK) rc = av1mi_upload(ctx, d[2], pv.data(), pv.size());
+    if (rc == AV1MI_OK) rc = av1mi_peak_analyse(ctx, W8, H8, y.w, y.h, n, d[0], d[1], d[2], (av1mi_peak_record *)d_rec);
+    if (rc == AV1MI_OK) rc = av1mi_download(ctx, rec.data(), d_rec, rec.size() * sizeof(av1mi_peak_record));
+    if (rc != AV1MI_OK) lib_error("av1mi_peak_analyse");
+    for (void *p : d) if (p) (void)av1mi_free(ctx, p);
+    if (d_rec) (void)av1mi_free(ctx, d_rec);
+    if (rc != AV1MI_OK) return 2;
+    av1mi_tone_tables tables;      // (lin[] does not depend on the peak)
+    if (av1mi_tone_map_tables(1000, &tables) != AV1MI_OK) return fail(2, "av1mi_tone_map_tables refused its arguments");
+    const int peak = PlanPeak(rec.data(), n, tables.lin, nullptr);
+    if (peak < 0) return fail(2, "the peak plan refused its arguments");
+    planned_peak = job.tonemap_peak = peak;
+    fprintf(stderr, "[av1mi] tone map: auto planned a source peak of %d cd/m2 from %d frames\n", peak, n);
     return 0;
   }
 
@@ -521,7 +570,7 @@ struct Run {
   int write_group(const Group &group, const GroupOut &out) {
     StatsTags tags;
     tags.depth_from = plan.reduced_from; tags.depth_to = plan.coded_bd;
-    tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0; tags.ar = job.grain_lag > 0; tags.lr = job.lr_search != 0; tags.cdef = job.cdef_search != 0; tags.lf = job.lf_search != 0; tags.ivtc = plan.telecine; tags.denoise_auto = planned_denoise;
+    tags.win = plan.win; tags.colour = sp.described() ? &plan.colour : nullptr; tags.q = rc != nullptr; tags.grain = job.denoise != 0; tags.ar = job.grain_lag > 0; tags.lr = job.lr_search != 0; tags.cdef = job.cdef_search != 0; tags.lf = job.lf_search != 0; tags.ivtc = plan.telecine; tags.denoise_auto = planned_denoise; tags.peak_auto = planned_peak;
     for (int s = 0; s < S; s++)
       for (size_t t = 0; t < out[(size_t)s].size(); t++) {
         const FrameOut &f = out[(size_t)s][t];
@@ -642,7 +691,7 @@ int RunBackend(const BackendJob &job, std::string *err, BackendReport *report) {
   }
   if (!r.y.open(job.input, err, job.to_420)) return 1;
   int code;
-  if ((code = r.settle_window()) || (code = r.settle_denoise()) || (code = r.session_config()) || (code = r.open_session()) || (code = r.run_groups())) return code;
+  if ((code = r.settle_window()) || (code = r.settle_denoise()) || (code = r.settle_peak()) || (code = r.session_config()) || (code = r.open_session()) || (code = r.run_groups())) return code;
   return r.finish();
 }
 

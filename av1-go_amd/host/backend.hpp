@@ -56,7 +56,7 @@ struct Group {
 };
 // The stats file: the line of frame n in presentation order, and the summary line.  tags: what a line says beyond the
 // figures — the window, the colour record and the depth reduction " depth:10>8" (frame 0 only; w == 0 / null / depth_from 0 = none), q: (a job with a target), grain: (a job that denoises)
-struct StatsTags { CropRect win; const av1mi_colour *colour = nullptr; int depth_from = 0, depth_to = 0; bool q = false, grain = false, ar = false, lr = false, cdef = false, lf = false, ivtc = false; int denoise_auto = -1; };      // denoise_auto: " denoise:auto>N", the planned strength (frame 0 only; -1 = the job did not ask); ivtc: " ivtc:<top source>/<bottom source>", file-wide source frame numbers
+struct StatsTags { CropRect win; const av1mi_colour *colour = nullptr; int depth_from = 0, depth_to = 0; bool q = false, grain = false, ar = false, lr = false, cdef = false, lf = false, ivtc = false; int denoise_auto = -1, peak_auto = -1; };      // denoise_auto: " denoise:auto>N", the planned strength (frame 0 only; -1 = the job did not ask); peak_auto: " peak:auto>N", the planned source peak in cd/m2, the same way; ivtc: " ivtc:<top source>/<bottom source>", file-wide source frame numbers
 std::string StatsFrameLine(long n, bool key, const FrameOut &f, int bit_depth, const StatsTags &tags, bool cut);
 std::string StatsSummaryLine(const av1mi::quality::Summary &sum, long long bytes, int bit_depth);
 

@@ -9,6 +9,7 @@
 #include "backend.hpp"
 #include "fieldrate.hpp"
 #include "noiseplan.hpp"
+#include "peakplan.hpp"
 #include "../csrc/quality.hpp"
 
 using namespace av1mi_host;
@@ -181,6 +182,29 @@ int av1mi_host_noise_pair_slots(long long n, int32_t *slots) {
   const int P = NoiseSamplePairs((long)n);
   for (int i = 0; i < P; i++) slots[i] = (int32_t)NoisePairSlot(i, (long)n);
   return P;
+}
+// PlanPeak (peakplan.hpp) with lin[] of av1mi_tone_map_tables: the source peak in cd/m2 (400 .. 10000) that `frames` peak records plan,
+// or -1; frame_code (may be null): every frame's code
+int av1mi_plan_peak(const av1mi_peak_record *rec, int frames, int32_t *frame_code) {
+  av1mi_tone_tables t;      // (lin[] does not depend on the peak)
+  if (av1mi_tone_map_tables(1000, &t) != AV1MI_OK) return -1;
+  return PlanPeak(rec, frames, t.lin, frame_code);
+}
+// the frames -av1mi_tonemap_peak auto samples in a file of n frames (peakplan.hpp PeakSampleSlot): their number; slots holds 32 entries
+int av1mi_host_peak_sample_slots(long long n, int32_t *slots) {
+  const int P = PeakSampleFrames((long)n);
+  for (int i = 0; i < P; i++) slots[i] = (int32_t)PeakSampleSlot(i, (long)n);
+  return P;
+}
+// ParseBackendJob's view of the tone map's options for an argv joined with '\n': 0 and out = { tonemap, tonemap_peak, tonemap_peak_auto },
+// or -1 with the text in err
+int av1mi_host_parse_peak_options(const char *joined, int *out, char *err, int cap) {
+  const std::vector<std::string> a = split_lines(joined);
+  BackendJob job; std::string e;
+  const bool ok = ParseBackendJob(a, &job, &e);
+  strncpy(err, e.c_str(), cap - 1); err[cap - 1] = 0;
+  out[0] = job.tonemap; out[1] = job.tonemap_peak; out[2] = job.tonemap_peak_auto ? 1 : 0;
+  return ok ? 0 : -1;
 }
 // ParseBackendJob's view of the denoiser's options for an argv joined with '\n': 0 and out = { denoise, denoise_auto, denoise_range,
 // film_grain, grain_lag }, or -1 with the text in err

@@ -396,7 +396,9 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
       else { if (err) *err = "Invalid argument: -av1mi_dither takes ordered or round, not " + args[i + 1]; return false; }
     }
     else if (args[i] == "-av1mi_tonemap_peak") {
-      if (!plain_int(args[i + 1], &job->tonemap_peak) || job->tonemap_peak < 100 || job->tonemap_peak > 10000) { if (err) *err = "Invalid argument: -av1mi_tonemap_peak takes cd/m2, 100 .. 10000, not " + args[i + 1]; return false; }
+      job->tonemap_peak_auto = args[i + 1] == "auto";
+      if (job->tonemap_peak_auto) job->tonemap_peak = 0;
+      else if (!plain_int(args[i + 1], &job->tonemap_peak) || job->tonemap_peak < 100 || job->tonemap_peak > 10000) { if (err) *err = "Invalid argument: -av1mi_tonemap_peak takes cd/m2, 100 .. 10000, or auto, not " + args[i + 1]; return false; }
     }
     else if (args[i] == "-vf:v:0" || args[i] == "-vf") { job->vf = args[i + 1]; job->have_vf = true; }
     else if (args[i] == "-av1mi_scale") {
@@ -435,7 +437,7 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
   }
   const bool denoises = job->denoise || job->denoise_auto;      // (auto: every refusal of -av1mi_denoise N holds whatever is planned later)
   if (job->dither >= 0 && !depth_given) { if (err) *err = "Invalid argument: -av1mi_dither needs -av1mi_depth: it is the rounding of the depth reduction"; return false; }
-  if (job->tonemap_peak && !job->tonemap) { if (err) *err = "Invalid argument: -av1mi_tonemap_peak needs -av1mi_tonemap bt2390 (or tonemap_vaapi in the chain)"; return false; }
+  if ((job->tonemap_peak || job->tonemap_peak_auto) && !job->tonemap) { if (err) *err = "Invalid argument: -av1mi_tonemap_peak needs -av1mi_tonemap bt2390 (or tonemap_vaapi in the chain)"; return false; }
   if (job->tonemap) {
     if (denoises) { if (err) *err = "Invalid argument: tone mapping together with -av1mi_denoise is not built: the grain would be measured in the source's light"; return false; }
     const bool src_ok = (job->color_primaries < 0 || job->color_primaries == 2 || job->color_primaries == 9) && (job->color_trc < 0 || job->color_trc == 2 || job->color_trc == 16) &&
@@ -466,6 +468,13 @@ bool ParseBackendJob(const std::vector<std::string> &args, BackendJob *job, std:
     struct stat st;
     if (job->input == "-" || job->input == "pipe:0" || (!stat(job->input.c_str(), &st) && !S_ISREG(st.st_mode))) {
       if (err) *err = "Invalid argument: -av1mi_crop auto needs a seekable file: it samples frames from all over the input, not from a pipe or FIFO";
+      return false;
+    }
+  }
+  if (job->tonemap_peak_auto) {      // the same rule: a stream's first frames say nothing about its brightest scene
+    struct stat st;
+    if (job->input == "-" || job->input == "pipe:0" || (!stat(job->input.c_str(), &st) && !S_ISREG(st.st_mode))) {
+      if (err) *err = "Invalid argument: -av1mi_tonemap_peak auto needs a seekable file: it samples frames from all over the input, not from a pipe or FIFO";
       return false;
     }
   }

@@ -139,6 +139,11 @@ struct BackendJob {
   // (av1mi_gop_config.tone_map); -av1mi_tonemap_peak N: the source's peak in cd/m2 (else the mastering display's maximum, else 1000).  The
   // output is then described as 1 / 1 / 1 limited without metadata, and -color_* describe the SOURCE (bt2020 / smpte2084 / bt2020nc / tv or nothing)
   int tonemap = 0, tonemap_peak = 0;
+  // -av1mi_tonemap_peak auto: the peak is PLANNED per file before the session opens (host/peakplan.hpp): needs tone mapping, a seekable file
+  // and a source that is 4:2:0 at 10 bits in the file; up to 32 frames spread evenly over it (the crop sampler's slots) are uploaded, all
+  // three planes, and measured on the GPU (av1mi_peak_analyse, include/av1mi.h "peak records").  The job -av1mi_tonemap_peak N then runs,
+  // byte for byte.  `tonemap_peak` stays 0 until the plan is made
+  bool tonemap_peak_auto = false;
   // -av1mi_depth 8 | 10 | source | chain: the depth that is CODED (av1mi_gop_config.coded_bit_depth).  source (0, the default): the source's, as
   // ever (8 -> 8, 10 -> 10, 12 -> 10).  8: a 10- or 12-bit source is reduced to 8 bits on the GPU at the end of the input chain, behind the
   // scaler and the tone map; nothing happens to an 8-bit source.  chain (-1): the LAST format= of the chain decides (chain_depth: nv12, yuv420p = 8;

@@ -759,6 +759,41 @@ typedef struct av1mi_noise_record { uint32_t hist[256]; uint32_t eligible, block
 int av1mi_noise_analyse(av1mi_ctx *ctx, int bit_depth, int width, int height, int true_width, int true_height, int pairs, const void *d_luma,
                         av1mi_noise_record *d_records);
 
+/* ---- peak records: how bright a PQ source gets, per frame, as the histogram of the very code that indexes the tone map's gain[]
+ * (av1-go_amd/csrc/peak_kernels.hip), from which the host plans the peak of "tone mapping" below (av1-go_amd/host/peakplan.hpp,
+ * av1mi_plan_peak of libav1mi_host.so).  Integer arithmetic, bit exact by definition; restated in numpy in tests/peak_ref.py.
+ *   frames         planar 4:2:0 frames of uint16 samples: luma of TRUE size w x h inside a buffer of W8 x H8 samples (the true size rounded
+ *                  up to 8), chroma in buffers of W8 / 2 x H8 / 2.  Nothing at or beyond the true size is read (luma x >= w or y >= h,
+ *                  chroma x >= ceil(w / 2) or y >= ceil(h / 2)): the buffers' padding may be undefined.
+ *   per pixel      (x, y) of the true picture: Y = min(luma[y][x], 1023), U = min(chromaU[y >> 1][x >> 1], 1023), V likewise; then steps 1
+ *                  and 2 of "tone mapping" verbatim with u = U - 512, v = V - 512: the same AV1MI_TONE_TO_RGB_* constants, the same >> 14,
+ *                  the same clamps to 0 .. 1023, M = max(R', G', B').  With the clamp at 1023 every intermediate fits 32 bits
+ *                  (|TO_RGB_Y (Y - 64) + 8192| < 2^25, |TO_RGB_BU u| < 2^25, the sums below 2^26).
+ *   the record     hist[M] counts the pixels of code M; pixels = w x h = the sum of hist (16384 x 16384 pixels fit 32 bits).
+ *   determinism    two stages like the crop, scene and noise records: per workgroup (a strip of rows of one frame) a histogram in LDS
+ *                  (integer atomics: integer addition gives the same bytes in any order), written as integer partials with ONE writer
+ *                  each, then one workgroup per frame adds them in an order fixed by geometry.
+ *   the plan       (host, av1mi_plan_peak; a pure function of the records and of lin[], the table of av1mi_tone_map_tables, which does
+ *                  not depend on the peak)
+ *                  per frame: skip = pixels >> 14 (0.006 % of the frame: 506 pixels at 3840 x 2160, 0 for frames under 16384 pixels), so
+ *                  that specular glints and hot pixels go.  The frame's code c_f = the largest c with hist[c] + .. + hist[1023] > skip,
+ *                  or 0 if there is none.
+ *                  per file: C = the maximum of c_f.  The peak belongs to the brightest scene: a maximum, not a quantile over frames.
+ *                  peak = min(max((lin[C] + 255) >> 8, 400), 10000) cd/m2 (lin[] is in 2^-8 cd/m2: rounded up).  The floor of 400 is the
+ *                  low end of the range over which "tone mapping" bounds gain[]'s monotonicity fix (at most 6 steps, peaks 400 .. 10000);
+ *                  it also keeps a dark sample of a bright film from planning a hard clip.
+ *                  frames < 1, or a record with pixels == 0: -1.
+ *                  The >> 14 and the 400 are POLICY, not measurements: nobody has tuned them on real footage. */
+typedef struct av1mi_peak_record { uint32_t hist[1024]; uint32_t pixels; } av1mi_peak_record;
+/* The records of `frames` (1 .. 65535) frames whose planes are stacked in d_y, d_u, d_v: luma width x height samples per frame, both
+ * multiples of 8 (8 .. 16384: the buffers' size, as for av1mi_crop_analyse), chroma width / 2 x height / 2, uint16; true_width x
+ * true_height the picture inside, less than 8 below the buffer's size.  d_records: `frames` records in device memory, 4-byte aligned; the
+ * planes 16-byte aligned.  AV1MI_E_INVAL and a text otherwise.  Two launches (k_peak_rows reads every sample of the true picture once, luma
+ * in whole 16-byte units, chroma in 8-byte units, a chroma sample once per 2x2 quad; k_peak_sum), asynchronous on the context's stream;
+ * the partials live in the context (grown on demand).  AV1MI_K_SCENE in the profile. */
+int av1mi_peak_analyse(av1mi_ctx *ctx, int width, int height, int true_width, int true_height, int frames, const void *d_y, const void *d_u, const void *d_v,
+                       av1mi_peak_record *d_records);
+
 /* ---- deinterlacing: an interlaced source becomes progressive frames inside the gather (av1-go_amd/csrc/deint_kernels.hip).  AV1 has no
  * interlaced coding and no field signalling: combing that is coded stays in the picture.  The filter is SAME-RATE: one output frame per
  * input frame, at the time of the frame's FIRST field.  Integer arithmetic, bit exact by definition.

@@ -197,10 +197,21 @@ long long av1mi_obu_write_blocks_temporal_unit(const av1mi_obu_blocks *f, int wi
  * telecine, whatever the source's header's I parameter says, from a file or a stream: 4 output frames per 5 source frames at fps x 4 / 5, "-g" counts
  * output frames and must be a multiple of 4; include/av1mi.h "inverse telecine", av1mi_gop_config.telecine; not with -av1mi_deinterlace,
  * -av1mi_denoise, -av1mi_pack10 1 or -av1mi_scenecut);
+ * "-av1mi_tonemap_peak N | auto" (with -av1mi_tonemap bt2390 or tonemap_vaapi in the chain: the source's peak in cd/m2, 100 .. 10000; auto =
+ * planned per file before the session opens: up to 32 frames of a seekable 4:2:0 10-bit file are measured on the GPU, include/av1mi.h "peak
+ * records", and the job is the job -av1mi_tonemap_peak N from there on; the first line of the stats file then holds " peak:auto>N");
  * everything else is accepted and ignored.  Returns 0 and leaves the output file in place on
  * success; -1 when the backend could not run at all (no HIP device: transcode.go:311); another non-zero code on failure.
  * err receives the reference-shaped text ("av1mi failed with exit code N: ...", at most 800 characters + "..."). */
 int av1mi_run_transcode(int argc, const char *const *argv, char *err, size_t errcap);
+
+/* libav1mi_host.so also exports the job's plans as functions of their own, for callers that drive the analyses themselves; like
+ * av1mi_plan_denoise they are listed here and not declared (tests/test_abi.py pins this header's declarations to the drop-in and the
+ * bitstream writers):
+ *   int av1mi_plan_peak(const av1mi_peak_record *records, int frames, int32_t *frame_code);
+ * the plan of -av1mi_tonemap_peak auto (av1-go_amd/host/peakplan.hpp; the rule: include/av1mi.h "peak records", the plan): `frames` >= 1
+ * records of av1mi_peak_analyse in host memory -> the source peak in cd/m2, 400 .. 10000, or -1 (frames < 1, no records, a record with
+ * pixels == 0).  frame_code (may be null): `frames` entries, every frame's code c_f.  Plain host code, no GPU. */
 
 #ifdef __cplusplus
 }
